@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X-native ELAS stereo hot path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: inputs, engine, W warm-up steps, exactly K timed steps, the result
+line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = wall milliseconds of one timed step).
+--dump-outputs DIR writes the maps the last timed step produced (a fixed sample of them, see dump_outputs) as .npy files.
+Everything described below from the parity gate on - the checks against the reference's digests, the per-kernel and
+roofline passes, the batch-1 latency, real frames, host-to-host, the other configurations, the host-share child and the
+CPU baseline - runs only with --full.
 
 A "step" is one pass of the whole hot path (gray pair -> final left disparity map + L/R-checked right map) over one
 batch of KITTI-shaped stereo pairs that is already resident in HBM.  Metric = BASELINE.json's "stereo pairs/sec" at
@@ -12,8 +19,9 @@ the optional chunked gather of finished maps on rank 0.  With --gpus N > 1 and n
 this process only starts N fresh ranks (launcher.py) and relays rank 0's line; under torch.distributed.run it is a rank.
 
 Before anything is timed the engine must reproduce the reference's maps for the workload's gate pair bit for bit
-(`parity_gate`: sha256 against tests/golden/digests.json; exit code 3 otherwise).  The timed region lasts at least
---min-seconds (5 s): `steps` on the line is the number of steps actually timed, `ms_per_step` x `steps` the timed wall.
+(`parity_gate`: sha256 against tests/golden/digests.json; exit code 3 otherwise).  The timed region runs exactly --steps
+steps unless --min-seconds asks for a minimum duration: `steps` on the line is the number of steps actually timed,
+`ms_per_step` x `steps` the timed wall.
 
 After the timed region every map its last step produced is compared with the same engine's idle-pipeline run of the same batch,
 and pair 0 with the reference's digests (`parity_after`; exit code 3 on a mismatch) - the gate alone would not see a race that
@@ -37,8 +45,8 @@ Also on the JSON line:
                   157 T byte-absdiff/s (live candidate counters of the no-overlap pass)
   host_to_host    SURVEY.md section 8(d)'s pair: gray L+R in host memory -> maps back in host memory, streamed
                   (sv_submit_batch_host), page-locked and pageable caller memory, three repetitions each; never `value`
-  cpu_baseline    the reference's own serial LIBELAS (oracle/_ref, compiled from /root/reference in the build
-                  container) or, if that artefact is absent, our CPU restatement, timed on this host, 1 thread;
+  cpu_baseline    the reference's own serial LIBELAS (oracle/_ref, compiled from the reference's sources by
+                  oracle/Makefile where they exist) or, if that artefact is absent, our CPU restatement, timed on this host, 1 thread;
                   cpu_baseline_all_cores: one pair per process on every core this process may use
 """
 import argparse
@@ -565,10 +573,13 @@ def timed_region(torch, engine, left, right, bufs, steps, barrier, sync_steps=Fa
 
 
 def run_config(ctx, name, steps_req, warmup, min_seconds, headline, gather):
-    """One BASELINE configuration on this rank's GPU: inputs, engine, parity gate, warm-up, timed region (>= min_seconds), latency.
-    Returns a dict (every rank; rank 0's is printed).  headline=True adds the per-kernel passes and keeps the engine for the
-    host-to-host measurements (returned under '_engine')."""
+    """One BASELINE configuration on this rank's GPU: inputs, engine, warm-up, timed region (`steps_req` steps, more when
+    min_seconds > 0 asks for it) and, with --full, parity gate, parity_after, latency.  Returns a dict (every rank; rank 0's is
+    printed).  headline=True adds, with --full, the per-kernel passes, and keeps the engine for the host-to-host measurements
+    (returned under '_engine')."""
     torch, dist, eng, synth, par, args = ctx["torch"], ctx["dist"], ctx["eng"], ctx["synth"], ctx["par"], ctx["args"]
+    full = args.full
+    checks = full and not args.no_gate  # parity gate before and parity_after behind the timed region
     rank, world, local_rank, backend, coll_dev = ctx["rank"], ctx["world"], ctx["local_rank"], ctx["backend"], ctx["coll_dev"]
     Wx, Hx, Dx, wb, wchunk, wslots, wscale, wseed, wdistinct = WORKLOADS[name]
     B = (args.batch or wb) if headline else wb
@@ -609,7 +620,7 @@ def run_config(ctx, name, steps_req, warmup, min_seconds, headline, gather):
     # ---- pass without kernel overlap (one slot, one stream; every kernel timed): clean per-kernel durations and the live
     # candidate counters of the matching kernels
     serial_k, counters = None, None
-    if headline and not args.no_kernel_timing:
+    if headline and full and not args.no_kernel_timing:
         schunk = chunk or (32 if Wx < 2000 else 4)
         es = eng.StereoEngine(Wx, Hx, params, device=local_rank, n_workers=args.workers, chunk=schunk, n_streams=1, n_slots=1)
         nb = min(B, 2 * schunk)
@@ -628,24 +639,27 @@ def run_config(ctx, name, steps_req, warmup, min_seconds, headline, gather):
 
     engine = eng.StereoEngine(Wx, Hx, params, device=local_rank, n_workers=args.workers if headline else 0, chunk=chunk, n_streams=args.streams if headline else 0, n_slots=slots)
     engine_info = engine.query()
-    gate = parity_gate(engine, torch, synth, name, sub) if not args.no_gate else {"status": "skipped"}
+    gate = parity_gate(engine, torch, synth, name, sub) if checks else {"status": "skipped"}
     for _ in range(max(1, warmup)):
         engine.process_device(left, right, d1, d2)
     torch.cuda.synchronize()
-    ref1, ref2 = d1.clone(), d2.clone()  # this batch's maps from an idle pipeline: what the timed steps' outputs are compared with afterwards
-    # seconds per step of the streamed form (what the timed region runs), from a few batches submitted back to back
-    n_est = 4 if Wx < 2000 else 2
-    torch.cuda.synchronize()
-    a = time.perf_counter()
-    for _ in range(n_est):
-        engine.submit_device(left, right, d1, d2)
-    engine.wait()
-    torch.cuda.synchronize()
-    est = (time.perf_counter() - a) / n_est
+    ref1, ref2 = (d1.clone(), d2.clone()) if checks else (None, None)  # this batch's maps from an idle pipeline: what the timed steps' outputs are compared with afterwards
+    # seconds per step of the streamed form (what the timed region runs), from a few batches submitted back to back: sizes the
+    # region when min_seconds > 0 and the gathered runs
+    est = None
+    if min_seconds > 0 or (gather and world > 1):
+        n_est = 4 if Wx < 2000 else 2
+        torch.cuda.synchronize()
+        a = time.perf_counter()
+        for _ in range(n_est):
+            engine.submit_device(left, right, d1, d2)
+        engine.wait()
+        torch.cuda.synchronize()
+        est = (time.perf_counter() - a) / n_est
     # ---- which kernel owns the most time in the configuration that is actually timed: a short pipelined pass with events around
     # every launch (costs 1-2 % of the rate, so it is not the timed region itself)
     pipe_k = None
-    if headline and not args.no_kernel_timing:
+    if headline and full and not args.no_kernel_timing:
         engine.timing(True)
         for _ in range(2):
             engine.submit_device(left, right, d1, d2)
@@ -673,12 +687,14 @@ def run_config(ctx, name, steps_req, warmup, min_seconds, headline, gather):
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         if float(t.item()) < 0.97 * min_seconds:
             steps = int(np.ceil(steps * 1.08 * min_seconds / max(float(t.item()), 1e-6)))
-            if headline and not args.no_kernel_timing:
+            if headline and full and not args.no_kernel_timing:
                 engine.timing(True, only=None if args.time_all_kernels else tuple({res["_dom"], max(serial_k, key=lambda k: serial_k[k][0])}))  # (resets the kernel's event totals)
             my_elapsed = timed_region(torch, engine, left, right, bufs[:1], steps, barrier, sync_steps=args.sync_steps and headline)
-    res["_ktimes"] = engine.kernel_times() if headline and not args.no_kernel_timing else {}
+    if headline and args.dump_outputs and rank == 0:
+        res["dump_outputs"] = dump_outputs(args.dump_outputs, d1, d2)
+    res["_ktimes"] = engine.kernel_times() if headline and full and not args.no_kernel_timing else {}
     engine.timing(False)
-    after = parity_after(torch, gate, (batch[0, 0], batch[0, 1]), d1, d2, ref1, ref2, "the timed region (last of %d streamed steps)" % steps) if not args.no_gate else {"status": "skipped"}
+    after = parity_after(torch, gate, (batch[0, 0], batch[0, 1]), d1, d2, ref1, ref2, "the timed region (last of %d streamed steps)" % steps) if checks else {"status": "skipped"}
     engine_info["gpu_triangulation_share"] = engine.gpu_triangulation_share()  # host mode: what the dispatcher's load balancing handed to the GPU kernel
     elapsed = par.max_over_ranks(my_elapsed, device=coll_dev)
     per_rank = [B * steps / my_elapsed]
@@ -689,8 +705,9 @@ def run_config(ctx, name, steps_req, warmup, min_seconds, headline, gather):
         per_rank = [B * steps / float(x) for x in t.tolist()]
     res.update({"pairs_per_s": round(B * world * steps / elapsed, 2), "ms_per_step": round(1e3 * elapsed / steps, 3), "steps": steps, "steps_requested": steps_req, "warmup": max(1, warmup),
                 "timed_seconds": round(elapsed, 3), "host_cpu_cores_busy": round(getattr(timed_region, "host_cpu_seconds", 0.0) / max(my_elapsed, 1e-9), 2), "pairs_per_gpu_per_step": B, "per_rank_pairs_per_s": [round(x, 1) for x in per_rank],
-                "parity_gate": {k: v for k, v in gate.items() if not k.startswith("_")}, "parity_after": after, "engine": engine_info, "valid_fraction": round(float((d1 >= 0).float().mean().item()), 4),
-                "checksum_rank0": float(d1.double().sum().item())})
+                "parity_gate": {k: v for k, v in gate.items() if not k.startswith("_")}, "parity_after": after, "engine": engine_info})
+    if full:
+        res.update({"valid_fraction": round(float((d1 >= 0).float().mean().item()), 4), "checksum_rank0": float(d1.double().sum().item())})
     # ---- the same run with the finished left maps gathered on rank 0 (RCCL), chunk by chunk, overlapping the kernels
     if gather and world > 1:
         g = min(B, GATHER_CHUNK.get(name, 64))
@@ -729,7 +746,7 @@ def run_config(ctx, name, steps_req, warmup, min_seconds, headline, gather):
             del gr
     # ---- batch-1 latency on rank 0 (ms/frame), SURVEY.md 8d config 2: the gate pair's size, one pair per call, device memory in and out
     lat_ms = None
-    if rank == 0 and not args.no_latency:
+    if rank == 0 and full and not args.no_latency:
         lat_pair = real if real is not None else (batch[0, 0], batch[0, 1])
         e1 = eng.StereoEngine(Wx, Hx, params, device=local_rank, n_workers=LATENCY_WORKERS, chunk=1, n_streams=1, n_slots=2)
         l1 = torch.from_numpy(np.array(lat_pair[0][None])).cuda()
@@ -778,15 +795,42 @@ def public(d):
     return {k: v for k, v in d.items() if not k.startswith("_")}
 
 
+DUMP_PAIRS = 8  # pairs of the batch whose maps --dump-outputs writes (a seeded choice, pair 0 always among them)
+DUMP_BUDGET = 32 << 20  # bytes of one dump at most; a map too large for it is written every n-th row
+
+
+def dump_outputs(path, d1, d2):
+    """--dump-outputs: what the caller of the timed path receives from its last step - the left and right float32 maps
+    [B, Hm, Wm] - as disparity_left.npy / disparity_right.npy, cut to a fixed sample that depends only on the shapes: pair 0
+    plus DUMP_PAIRS - 1 pairs drawn with seed 0, and every `row_step`-th row when even one pair's two maps exceed DUMP_BUDGET."""
+    import torch
+    B, Hm, Wm = d1.shape
+    k = min(B, DUMP_PAIRS)
+    pairs = np.sort(np.concatenate([[0], 1 + np.random.default_rng(0).choice(B - 1, k - 1, replace=False)])) if k > 1 else np.zeros(1, np.int64)
+    row_step = max(1, -(-2 * Hm * Wm * 4 // DUMP_BUDGET))
+    k = max(1, min(k, DUMP_BUDGET // (2 * 4 * Wm * -(-Hm // row_step))))
+    pairs = pairs[:k]
+    idx = torch.from_numpy(pairs).to(d1.device)
+    os.makedirs(path, exist_ok=True)
+    for name, d in (("disparity_left", d1), ("disparity_right", d2)):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(d.index_select(0, idx)[:, ::row_step].cpu().numpy(), dtype=np.float32))
+    return {"dir": path, "pairs": [int(i) for i in pairs], "row_step": row_step, "files": ["disparity_left.npy", "disparity_right.npy"]}
+
+
 def main():
-    ap = argparse.ArgumentParser(description="NOTE: --steps is a MINIMUM. The timed region lasts at least --min-seconds (default 5 s), so more steps than --steps are usually run: "
-                                 "`steps` on the JSON line is the number actually timed (ms_per_step x steps = timed_seconds), `steps_requested` the argument. "
-                                 "--min-seconds 0 times exactly --steps.")
+    ap = argparse.ArgumentParser(description="Times exactly --steps steps of the headline (unless --min-seconds asks for a minimum duration): `steps` on the JSON line is the "
+                                 "number actually timed (ms_per_step x steps = timed_seconds), `steps_requested` the argument. A plain run measures the headline only; "
+                                 "--full adds the parity checks, per-kernel / roofline passes, latency, real frames, host-to-host, the other configurations, the "
+                                 "host-share child and the CPU baseline (the --no-* options below switch parts of --full off).")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=4)
-    ap.add_argument("--min-seconds", type=float, default=5.0, help="the headline's timed region lasts at least this long: more steps than --steps are run when needed "
-                    "(`steps` on the line = steps actually timed; 0 = exactly --steps)")
+    ap.add_argument("--min-seconds", type=float, default=0.0, help="the headline's timed region lasts at least this long: more steps than --steps are run when needed "
+                    "(`steps` on the line = steps actually timed; 0, the default = exactly --steps)")
+    ap.add_argument("--full", action="store_true", help="also run every check and measurement beyond the headline (parity gate and parity_after, kernel timing and "
+                    "roofline, batch-1 latency, real frames, host-to-host, kitti_d256 / 4k_d192, host share, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write the maps of the last step (pair 0 plus a seeded sample of the batch, "
+                    "float32, at most 32 MB) as DIR/disparity_left.npy and DIR/disparity_right.npy")
     ap.add_argument("--batch", type=int, default=0, help="pairs per GPU per step (0 = the workload's default: 256 for the headline)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="kitti_d128", help="kitti_d128 is BASELINE.json's metric configuration")
     ap.add_argument("--workers", type=int, default=0, help="host pool threads (0 = library default)")
@@ -824,10 +868,10 @@ def main():
     if args.host_share_child > 0:
         launcher = importlib.import_module(PKG + ".launcher")
         kept_cpus = launcher.restrict_to_host_share(args.host_share_child, int(os.environ.get("LOCAL_RANK", "0")))
-    elif args.host_share > 1 and args.gpus == 1 and "WORLD_SIZE" not in os.environ and not args.no_configs:
+    elif args.full and args.host_share > 1 and args.gpus == 1 and "WORLD_SIZE" not in os.environ and not args.no_configs:
         launcher = importlib.import_module(PKG + ".launcher")
-        cmd = [sys.executable, os.path.abspath(__file__), "--host-share-child", str(args.host_share), "--host-share", "0", "--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup),
-               "--min-seconds", str(args.min_seconds), "--workload", args.workload, "--no-host", "--no-configs", "--no-latency", "--no-real", "--no-kernel-timing", "--cpu-sample", "0"]
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--host-share-child", str(args.host_share), "--host-share", "0", "--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup),
+               "--min-seconds", str(args.min_seconds or SUBCONFIG_MIN_SECONDS), "--workload", args.workload, "--no-host", "--no-configs", "--no-latency", "--no-real", "--no-kernel-timing", "--cpu-sample", "0"]
         for flag, on in (("--subsampling", args.subsampling), ("--synthetic-only", args.synthetic_only), ("--real-pair", args.real_pair), ("--no-gate", args.no_gate)):
             if on:
                 cmd.append(flag)
@@ -884,7 +928,7 @@ def main():
     ctx = {"torch": torch, "dist": dist, "eng": eng, "synth": synth, "par": par, "args": args, "rank": rank, "world": world,
            "local_rank": local_rank, "backend": backend, "coll_dev": coll_dev}
 
-    hl = run_config(ctx, args.workload, args.steps, args.warmup, args.min_seconds, True, gather=(args.gather or args.workload == "4k_d192"))
+    hl = run_config(ctx, args.workload, args.steps, args.warmup, args.min_seconds, True, gather=args.full and (args.gather or args.workload == "4k_d192"))
     engine, params, batch, real, B = hl["_engine"], hl["_params"], hl["_batch"], hl["_real"], hl["_B"]
     Wm, Hm = hl["_dims"][3], hl["_dims"][4]
     d1, d2 = hl["_bufs"][0]
@@ -894,7 +938,7 @@ def main():
     # cycled through the batch (real maps are far more fragmented than synthetic ones); afterwards every distinct frame's maps
     # must hash to the reference's digests
     real_rate = None
-    rp = load_real_pairs(W, H, D) if (rank == 0 and world == 1 and real is not None and not args.no_real and not args.real_pair) else []
+    rp = load_real_pairs(W, H, D) if (args.full and rank == 0 and world == 1 and real is not None and not args.no_real and not args.real_pair) else []
     if rp:  # (empty without PIL, or when no committed frame has a digest for this disparity range: the region is skipped, not a crash after the headline)
         import hashlib
         idx = [i % len(rp) for i in range(B)]
@@ -925,7 +969,7 @@ def main():
     # ---- host memory in / out through the same engine (PCIe inclusive)
     h2h = None
     lat_pair = real if real is not None else (batch[0, 0], batch[0, 1])
-    if rank == 0 and world == 1 and not args.no_host:
+    if args.full and rank == 0 and world == 1 and not args.no_host:
         h2h = host_to_host(eng, engine, params, batch, max(3, min(20, steps // 4)), lat_pair)
         if args.no_latency:
             h2h.pop("latency_ms_batch1_host", None)
@@ -936,7 +980,7 @@ def main():
     # ---- BASELINE.json's other configurations, each on its own engine with its own parity gate (>= 5 s of steps each):
     # configs[3] KITTI D=256 (one GPU) and configs[4] 4K D=192, 128 pairs per GPU, gathered on rank 0 when N > 1
     configs = {}
-    if args.workload == "kitti_d128" and not args.no_configs and not args.subsampling:
+    if args.full and args.workload == "kitti_d128" and not args.no_configs and not args.subsampling:
         for cname in (("kitti_d256", "4k_d192") if world == 1 else ("4k_d192",)):
             r = public(run_config(ctx, cname, 3, 2, SUBCONFIG_MIN_SECONDS, False, gather=(cname == "4k_d192")))
             r["config"] = "%dx%d D=%d, %d pairs per GPU per step, %d GPU(s)" % (WORKLOADS[cname][0], WORKLOADS[cname][1], WORKLOADS[cname][2], r["pairs_per_gpu_per_step"], world)
@@ -952,25 +996,30 @@ def main():
             "n_gpus": world, "steps": steps, "steps_requested": args.steps, "warmup": hl["warmup"],
             "ms_per_step": hl["ms_per_step"], "timed_seconds": hl["timed_seconds"], "host_cpu_cores_busy": hl["host_cpu_cores_busy"],
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "u8", "data": hl["data"],
-            "parity_gate": hl["parity_gate"]["status"], "parity_gate_detail": hl["parity_gate"], "parity_after": hl["parity_after"],
+            "dtype": "u8", "data": hl["data"], "full": args.full,
             "config": {"workload": "%s_%dx%d_D%d_batch%d_per_gpu_streamed" % (args.workload.split("_")[0], W, H, D, B), "width": W, "height": H, "disp_max": D - 1,
                        "preset": "driver(MIDDLEBURY+only_left+adaptive_mean+median)" + ("+subsampling" if args.subsampling else ""), "pairs_per_gpu_per_step": B,
                        "parallelism": "batch-sharded x%d, no data-path collective" % world, "engine": hl["engine"]},
             "launcher": os.environ.get("SV_LAUNCHER", "external (torch.distributed.run)" if world > 1 else "none"),
             "collective_backend": backend if world > 1 else None, "rccl_ranks": (dist.get_world_size() if world > 1 and backend == "nccl" else None),
             "per_rank_pairs_per_s": hl["per_rank_pairs_per_s"],
-            "with_gather": hl.get("with_gather"), "with_gather_u8": hl.get("with_gather_u8"),
-            "configs": configs,
-            "latency_ms_batch1": hl["latency_ms_batch1"], "value_real_pair": real_rate, "host_to_host": h2h,
-            "valid_fraction": hl["valid_fraction"], "checksum_rank0": hl["checksum_rank0"],
         }
+        if args.dump_outputs:
+            out["dump_outputs"] = hl["dump_outputs"]
+        if args.full:
+            out.update({
+                "parity_gate": hl["parity_gate"]["status"], "parity_gate_detail": hl["parity_gate"], "parity_after": hl["parity_after"],
+                "with_gather": hl.get("with_gather"), "with_gather_u8": hl.get("with_gather_u8"),
+                "configs": configs,
+                "latency_ms_batch1": hl["latency_ms_batch1"], "value_real_pair": real_rate, "host_to_host": h2h,
+                "valid_fraction": hl["valid_fraction"], "checksum_rank0": hl["checksum_rank0"],
+            })
         if h2h:
             out["value_host_to_host"] = h2h["pinned"]["pairs_per_s_d1"]
             out["value_host_to_host_spread"] = h2h["pinned"]["pairs_per_s_d1_runs"]
         if kept_cpus is not None:
             out["host_share_child"] = {"share": args.host_share_child, "cpus": kept_cpus, "local_world_size": os.environ.get("LOCAL_WORLD_SIZE")}
-        if args.host_share > 1 and args.host_share_child == 0:
+        if args.full and args.host_share > 1 and args.host_share_child == 0:
             key = "value_at_host_share_%d" % args.host_share
             if host_share and host_share.get("parity_gate") in ("pass", "skipped") and "value" in host_share:
                 out[key] = host_share["value"]
@@ -1090,13 +1139,13 @@ def main():
             out["roofline_by_kernel"] = rbk
             out["serial_kernel_us_per_pair_sum"] = round(sum(1e3 * v[0] / (v[1] * v[2]) for v in serial_k.values()), 3)
             out["kernel_ms_per_pair_timed_region"] = {k: round(v[0] / (B * steps), 5) for k, v in sorted(ktimes.items(), key=lambda kv: -kv[1][0])}
-        if world == 1 and args.cpu_sample > 0:
+        if args.full and world == 1 and args.cpu_sample > 0:
             one, many = cpu_baseline(args.cpu_sample if W < 2000 else min(args.cpu_sample, 4), synth, args.subsampling, scale=WORKLOADS[args.workload][6],
                                      all_cores_pairs=(4 * usable_cpus() if W < 2000 else 0))
             out["cpu_baseline"] = one
             if many:
                 out["cpu_baseline_all_cores"] = many
-        # the keys a reader of the line's tail needs, last (the line is ~15 KB; a tail keeps its end)
+        # the keys a reader of the line's tail needs, last (the --full line is ~15 KB; a tail keeps its end)
         out["trailer"] = {
             "value": rate, "parity_gate": hl["parity_gate"]["status"], "parity_after": hl["parity_after"]["status"],
             "value_host_to_host": out.get("value_host_to_host"), "host_to_host_dmap_u8": ((h2h or {}).get("pinned") or {}).get("pairs_per_s_dmap_u8"),
@@ -1116,6 +1165,8 @@ def main():
             "latency_ms_batch1_median": (hl["latency_ms_batch1"] or {}).get("median"),
             "roofline_frac": (out.get("roofline") or {}).get("frac"), "cpu_baseline_pairs_per_s": (out.get("cpu_baseline") or {}).get("value"),
         }
+        if not args.full:
+            del out["trailer"]  # (it repeats what only --full measures)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

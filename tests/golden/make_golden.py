@@ -2,7 +2,9 @@
 reference's serial LIBELAS compiled from /root/reference by oracle/Makefile), run in its canonical state
 (zero-filled scratch, IEEE flags).  Only runs in the build container:
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py                  # everything
+    python tests/golden/make_golden.py --extra-inputs   # only the input images of tests/test_oracle_vs_ref.py (+ ref_digests.json)
+    python tests/golden/make_golden.py --ref-digests    # only ref_digests.json (the reference's results of that module's cases)
 
 Fixtures are data only: gray input images and the arrays / digests the reference produced for them.
 Gray conversion of the bundled KITTI colour PNGs uses the OpenCV-4.x 15-bit BGR2GRAY weights the reference
@@ -48,6 +50,48 @@ def with_sub(p, case):
     p.subsampling = 1 if case.get("subsampling") else 0  # half-resolution mode (elas.h:83-85)
     p.disp_min = int(case.get("disp_min", 0))            # first disparity of the support search (elas.h:61, elas.cpp:318)
     return p
+
+
+KITTI_MINI_FRAMES = 21  # image_02 / image_03 pairs of datasets/kitti_mini
+PROFILE_PAIRS = ["aloe", "cones", "raindeer", "urban1", "urban2", "urban3", "urban4"]  # datasets/profile
+
+
+def extra_inputs():
+    """Input images only, for tests/test_oracle_vs_ref.py: the kitti_mini frames main() does not write (gray, kitti<f>_*.png,
+    digests of the frames without an entry in digests.json are not needed) and the datasets/profile pairs as lossless PNGs."""
+    for f in range(KITTI_MINI_FRAMES):
+        if os.path.exists(os.path.join(HERE, "kitti%d_left.png" % f)):
+            continue
+        for cam, side in (("image_02", "left"), ("image_03", "right")):
+            g = gray_cv4(REF + "/datasets/kitti_mini/%s/data/%010d.png" % (cam, f))
+            Image.fromarray(g).save(os.path.join(HERE, "kitti%d_%s.png" % (f, side)), optimize=True)
+    for name in PROFILE_PAIRS:
+        for side in ("left", "right"):
+            a = np.asarray(Image.open(REF + "/datasets/profile/%s_%s.pgm" % (name, side)))
+            Image.fromarray(a).save(os.path.join(HERE, "profile_%s_%s.png" % (name, side)), optimize=True)
+
+
+def ref_digests():
+    """ref_digests.json: the reference's side of tests/test_oracle_vs_ref.py - sha256 of every stage for each case the test
+    module generates (and of the triangles / maps where it compares those) - so that the test needs no oracle/_ref."""
+    sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+    import test_oracle_vs_ref as t
+
+    ref, out = RefElas(), {}
+    cases = [t.synthetic_case(*c, preset) for c in t.SYNTHETIC for preset in t.PRESETS] + list(t.noise_cases())
+    cases += [t.kitti_mini_case(f) for f in t.KITTI_MINI_FRAMES] + [t.profile_case(n, pr) for n in t.PROFILE_PAIRS for pr in ("robotics", "middlebury")]
+    driver, (key, p, L, R) = t.textureless_cases()
+    for k, p_, L_, R_ in cases + [driver]:
+        out[k] = t.stage_digests(ref, p_, L_, R_)
+    D1, D2, _ = ref.process(p, L, R)
+    out[key] = [sha(D1), sha(D2)]
+    out["delaunay_random_sets"] = {str(it): [int(a.shape[0]), sha(a)] for it, _, _, xy in t.delaunay_sets() for a in [ref.delaunay(xy)]}
+    for k, _, p_, L_, R_ in t.random_parameter_cases():
+        n = ref.run_stages(p_, L_, R_)
+        out[k] = t.stage_digests(ref, p_, L_, R_) if n >= 3 else {"n": n}
+    with open(os.path.join(HERE, "ref_digests.json"), "w") as f:
+        json.dump(out, f, indent=0, sort_keys=True)
+        f.write("\n")
 
 
 def main():
@@ -147,4 +191,8 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    if "--extra-inputs" not in sys.argv and "--ref-digests" not in sys.argv:
+        main()
+    if "--ref-digests" not in sys.argv:
+        extra_inputs()
+    ref_digests()

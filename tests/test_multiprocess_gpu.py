@@ -77,7 +77,7 @@ def test_bench_launches_its_own_ranks(tmp_path):
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_PORT")}
     env["BENCH_BACKEND"] = "gloo"
-    cmd = [sys.executable, os.path.join(util.ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--min-seconds", "0.5", "--batch", "128", "--no-host",
+    cmd = [sys.executable, os.path.join(util.ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--min-seconds", "0.5", "--batch", "128", "--no-host",
            "--no-latency", "--no-real", "--cpu-sample", "0", "--no-configs", "--gather"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=360)
     assert p.returncode == 0, p.stderr[-3000:]

@@ -1,33 +1,61 @@
-"""CPU, build container only: the oracle restatement against the reference itself (oracle/_ref) on inputs beyond
-the committed fixtures.  Skipped where oracle/_ref is absent."""
+"""CPU: the oracle restatement against the reference itself on inputs beyond the committed digests.json cases: seeded
+synthetic and random inputs and the reference's bundled image pairs (committed under tests/golden/).  The reference's side
+of every comparison: its results stored in tests/golden/ref_digests.json (sha256 of every stage, written from oracle/_ref by
+make_golden.py --ref-digests over the case generators below) and, where oracle/_ref was built, the compiled reference itself."""
+import json
+import os
+import sys
+
 import numpy as np
 import pytest
 
 import util
-from pyoracle import ElasParams
+from pyoracle import ElasParams, RefElas
 
-pytestmark = pytest.mark.ref
+SYNTHETIC = [(11, 140, 400, 64), (12, 90, 333, 48), (13, 200, 640, 128), (14, 64, 128, 32)]
+PRESETS = ["driver", "robotics", "middlebury"]
+KITTI_MINI_FRAMES = range(21)
+PROFILE_PAIRS = ["aloe", "cones", "raindeer", "urban1", "urban2", "urban3", "urban4"]
 
 
-def _compare(ref, oracle, p, L, R):
-    n1 = ref.run_stages(p, L, R)
-    n2 = oracle.run_stages(p, L, R)
-    assert n1 == n2
-    bad = [k for k in util.STAGES if not np.array_equal(ref.stage(k).view(np.uint8), oracle.stage(k).view(np.uint8))]
+@pytest.fixture(scope="module")
+def ref():
+    """The compiled reference where oracle/_ref exists, else None (the stored digests alone)."""
+    return RefElas() if RefElas.available() else None
+
+
+@pytest.fixture(scope="module")
+def stored():
+    with open(os.path.join(util.GOLDEN, "ref_digests.json")) as f:
+        return json.load(f)
+
+
+def stage_digests(lib, p, L, R):
+    """{"n": support points, "stages": {stage: sha256}} of one run of `lib` (the reference or the oracle)."""
+    n = lib.run_stages(p, L, R)
+    return {"n": n, "stages": {k: util.sha(lib.stage(k)) for k in util.STAGES}}
+
+
+def _compare(ref, oracle, stored, key, p, L, R):
+    got = stage_digests(oracle, p, L, R)
+    want = stored[key]
+    assert got["n"] == want["n"]
+    bad = [k for k in util.STAGES if got["stages"][k] != want["stages"][k]]
     assert not bad, bad
+    if ref is not None:
+        assert ref.run_stages(p, L, R) == got["n"]
+        bad = [k for k in util.STAGES if not np.array_equal(ref.stage(k).view(np.uint8), oracle.stage(k).view(np.uint8))]
+        assert not bad, bad
 
 
-@pytest.mark.parametrize("seed,H,W,D", [(11, 140, 400, 64), (12, 90, 333, 48), (13, 200, 640, 128), (14, 64, 128, 32)])
-@pytest.mark.parametrize("preset", ["driver", "robotics", "middlebury"])
-def test_synthetic_pairs(ref, oracle, seed, H, W, D, preset):
+def synthetic_case(seed, H, W, D, preset):
     L, R = util.pkg("synth").make_pair(seed, H, W, D)
     p = ElasParams.driver(D - 1) if preset == "driver" else ElasParams.preset(preset)
     p.disp_max = D - 1
-    _compare(ref, oracle, p, L, R)
+    return "synthetic_%d_%dx%d_d%d_%s" % (seed, W, H, D, preset), p, L, R
 
 
-def test_noise_images(ref, oracle):
-    """Pure noise: few, scattered support points, many invalid pixels, heavy speckle removal."""
+def noise_cases():
     rng = np.random.default_rng(3)
     L = rng.integers(0, 256, (100, 260), dtype=np.uint8)
     R = np.roll(L, -7, axis=1)
@@ -35,25 +63,20 @@ def test_noise_images(ref, oracle):
     for preset in ("robotics", "middlebury"):
         p = ElasParams.preset(preset)
         p.disp_max = 31
-        _compare(ref, oracle, p, L, R)
+        yield "noise_%s" % preset, p, L, R
 
 
-def test_textureless_images(ref, oracle):
-    """The reference's own smoke test feeds all-zero images (tests/test_demo.py:8-10): no lattice point passes the
-    texture gate, the driver preset still triangulates its six corner points; ROBOTICS returns early."""
+def textureless_cases():
+    """(driver stages case, ROBOTICS Elas::process case): all-zero images."""
     L = np.zeros((80, 200), np.uint8)
-    _compare(ref, oracle, ElasParams.driver(63), L, L)
     p = ElasParams.preset("robotics")
     p.disp_max = 63
-    D1r, D2r, _ = ref.process(p, L, L)
-    D1o, D2o, _ = oracle.process(p, L, L)
-    assert np.array_equal(D1r, D1o) and np.array_equal(D2r, D2o) and not D1r.any()
+    return ("textureless_driver", ElasParams.driver(63), L, L), ("textureless_robotics_maps", p, L, L)
 
 
-def test_delaunay_random_sets(ref, oracle):
-    """Lattice points (co-circular quadruples everywhere), duplicates (right-image collisions), strips."""
+def delaunay_sets():
+    """(iteration, mode, n, xy float32) of the random point sets Triangle is fed."""
     rng = np.random.default_rng(0)
-    done = 0
     for it in range(600):
         mode = it % 5
         n = int(rng.integers(3, 300)) if it % 10 else int(rng.integers(3, 10))
@@ -74,18 +97,11 @@ def test_delaunay_random_sets(ref, oracle):
         k = np.flatnonzero((d != 0).any(1))[0]
         if np.all(d[:, 0] * d[k, 1] == d[:, 1] * d[k, 0]):
             continue  # all collinear: Triangle yields no triangles; ELAS never feeds that
-        xy = pts.astype(np.float32)
-        a, b = ref.delaunay(xy), oracle.delaunay(xy)
-        assert a.shape == b.shape and np.array_equal(a, b), (it, mode, n)
-        done += 1
-    assert done > 400
+        yield it, mode, n, pts.astype(np.float32)
 
 
-def test_random_parameter_sets(ref, oracle):
-    """Parameter sets far from the presets (lattice step, window sizes, grid size, prior, thresholds, gap / speckle limits,
-    filter switches, half resolution): every stage of the restatement equals the reference's."""
-    import sys
-
+def random_parameter_cases():
+    """(key, values, params, L, R) of the parameter sets far from the presets."""
     sys.path.insert(0, util.ROOT + "/tools")
     import fuzz_params as fz
 
@@ -95,47 +111,85 @@ def test_random_parameter_sets(ref, oracle):
         vals = fz.random_params(rng)
         H, W = shapes[i % 3]
         L, R = util.pkg("synth").make_pair(500 + i, H, W, min(vals["disp_max"] + 1, 64))
-        p = fz.apply(ElasParams.preset("robotics"), vals)
-        n1 = ref.run_stages(p, L, R)
-        assert n1 == oracle.run_stages(p, L, R), vals
-        if n1 < 3:
+        yield "random_parameters_%d" % i, vals, fz.apply(ElasParams.preset("robotics"), vals), L, R
+
+
+def kitti_mini_case(frame):
+    return "kitti_mini_%d_d128" % frame, ElasParams.driver(127), util.load_png("kitti%d_left.png" % frame), util.load_png("kitti%d_right.png" % frame)
+
+
+def profile_case(name, preset):
+    return ("profile_%s_%s" % (name, preset), ElasParams.preset(preset), util.load_png("profile_%s_left.png" % name),
+            util.load_png("profile_%s_right.png" % name))
+
+
+@pytest.mark.parametrize("seed,H,W,D", SYNTHETIC)
+@pytest.mark.parametrize("preset", PRESETS)
+def test_synthetic_pairs(ref, oracle, stored, seed, H, W, D, preset):
+    _compare(ref, oracle, stored, *synthetic_case(seed, H, W, D, preset))
+
+
+def test_noise_images(ref, oracle, stored):
+    """Pure noise: few, scattered support points, many invalid pixels, heavy speckle removal."""
+    for case in noise_cases():
+        _compare(ref, oracle, stored, *case)
+
+
+def test_textureless_images(ref, oracle, stored):
+    """The reference's own smoke test feeds all-zero images (tests/test_demo.py:8-10): no lattice point passes the
+    texture gate, the driver preset still triangulates its six corner points; ROBOTICS returns early."""
+    driver, (key, p, L, _) = textureless_cases()
+    _compare(ref, oracle, stored, *driver)
+    D1o, D2o, _ = oracle.process(p, L, L)
+    assert [util.sha(D1o), util.sha(D2o)] == stored[key] and not D1o.any()
+    if ref is not None:
+        D1r, D2r, _ = ref.process(p, L, L)
+        assert np.array_equal(D1r, D1o) and np.array_equal(D2r, D2o) and not D1r.any()
+
+
+def test_delaunay_random_sets(ref, oracle, stored):
+    """Lattice points (co-circular quadruples everywhere), duplicates (right-image collisions), strips."""
+    want = stored["delaunay_random_sets"]
+    done = 0
+    for it, mode, n, xy in delaunay_sets():
+        b = oracle.delaunay(xy)
+        assert [b.shape[0], util.sha(b)] == want[str(it)], (it, mode, n)
+        if ref is not None:
+            a = ref.delaunay(xy)
+            assert a.shape == b.shape and np.array_equal(a, b), (it, mode, n)
+        done += 1
+    assert done > 400 and done == len(want)
+
+
+def test_random_parameter_sets(ref, oracle, stored):
+    """Parameter sets far from the presets (lattice step, window sizes, grid size, prior, thresholds, gap / speckle limits,
+    filter switches, half resolution): every stage of the restatement equals the reference's."""
+    for key, vals, p, L, R in random_parameter_cases():
+        want = stored[key]
+        n2 = oracle.run_stages(p, L, R)
+        assert n2 == want["n"], vals
+        if ref is not None:
+            assert ref.run_stages(p, L, R) == n2, vals
+        if n2 < 3:
             continue
-        bad = [k for k in util.STAGES if not np.array_equal(ref.stage(k).view(np.uint8), oracle.stage(k).view(np.uint8))]
+        bad = [k for k in util.STAGES if util.sha(oracle.stage(k)) != want["stages"][k]]
         assert not bad, (bad, vals)
+        if ref is not None:
+            bad = [k for k in util.STAGES if not np.array_equal(ref.stage(k).view(np.uint8), oracle.stage(k).view(np.uint8))]
+            assert not bad, (bad, vals)
 
 
-REF_DATA = "/root/reference/datasets"  # read in place, build container only (it does not exist on the GPU box; marker `ref` skips there)
-
-
-def _gray_cv4(path):
-    """OpenCV-4.x BGR2GRAY weights, as tests/golden/make_golden.py applies them."""
-    from PIL import Image
-    a = np.asarray(Image.open(path).convert("RGB")).astype(np.int64)
-    r, g, b = a[..., 0], a[..., 1], a[..., 2]
-    return ((b * 3735 + g * 19235 + r * 9798 + 16384) >> 15).astype(np.uint8)
-
-
-@pytest.mark.parametrize("frame", range(21))
-def test_every_kitti_mini_pair(ref, oracle, frame):
+@pytest.mark.parametrize("frame", KITTI_MINI_FRAMES)
+def test_every_kitti_mini_pair(ref, oracle, stored, frame):
     """All 21 pairs the reference ships under datasets/kitti_mini, D = 128, the driver's preset: every stage of the restatement
-    equals the compiled reference's (DESIGN.md section 1(c) claims it; the committed goldens hold frames 0, 3, 7, 10, 13, 17, 20)."""
-    import os
-    lp = "%s/kitti_mini/image_02/data/%010d.png" % (REF_DATA, frame)
-    if not os.path.exists(lp):
-        pytest.skip("the reference's datasets are not here")
-    L, R = _gray_cv4(lp), _gray_cv4(lp.replace("image_02", "image_03"))
-    _compare(ref, oracle, ElasParams.driver(127), L, R)
+    equals the compiled reference's (DESIGN.md section 1(c) claims it).  Inputs: the committed gray fixtures
+    tests/golden/kitti<frame>_{left,right}.png (make_golden.py's OpenCV-4.x BGR2GRAY of the colour frames)."""
+    _compare(ref, oracle, stored, *kitti_mini_case(frame))
 
 
-@pytest.mark.parametrize("name", ["aloe", "cones", "raindeer", "urban1", "urban2", "urban3", "urban4"])
+@pytest.mark.parametrize("name", PROFILE_PAIRS)
 @pytest.mark.parametrize("preset", ["robotics", "middlebury"])
-def test_every_bundled_profile_pair(ref, oracle, name, preset):
-    """The seven Middlebury / urban pairs of datasets/profile with both presets (disp_max 255, the presets' own value)."""
-    import os
-    from PIL import Image
-    lp = "%s/profile/%s_left.pgm" % (REF_DATA, name)
-    if not os.path.exists(lp):
-        pytest.skip("the reference's datasets are not here")
-    L = np.ascontiguousarray(np.asarray(Image.open(lp)))
-    R = np.ascontiguousarray(np.asarray(Image.open(lp.replace("_left", "_right"))))
-    _compare(ref, oracle, ElasParams.preset(preset), L, R)
+def test_every_bundled_profile_pair(ref, oracle, stored, name, preset):
+    """The seven Middlebury / urban pairs of datasets/profile with both presets (disp_max 255, the presets' own value).  Inputs:
+    the committed lossless copies tests/golden/profile_<name>_{left,right}.png."""
+    _compare(ref, oracle, stored, *profile_case(name, preset))

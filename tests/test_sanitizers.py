@@ -23,6 +23,10 @@ def test_host_stage_sanitizers(tmp_path, san):
         pytest.skip("sanitizer runtime not installed")
     assert r.returncode == 0, r.stderr[-2000:]
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    if san == "thread" and r.returncode != 0 and "unexpected memory mapping" in r.stderr and shutil.which("setarch"):
+        # GCC's ThreadSanitizer runtime does not fit its shadow layout around kernels with more mmap randomisation bits:
+        # the same binary again with address randomisation off for this one process (a personality flag, nothing system-wide)
+        r = subprocess.run(["setarch", os.uname().machine, "-R", exe], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "mismatches: 0" in r.stdout, (r.stdout[-500:], r.stderr[-3000:])
 
 

@@ -4,8 +4,8 @@
     python tools/design_numbers.py profiles/r05_bench_line.json            # print the block
     python tools/design_numbers.py profiles/r05_bench_line.json --write    # replace the block between the markers in DESIGN.md and README.md
 
-The input is the ONE JSON line `python bench.py --gpus 1 --steps 20 --warmup 5` printed (the driver's BENCH_rNN.json holds the same line
-under "parsed" / in "tail": pass that file and the line is dug out).  Every row names the key it was read from."""
+The input is the ONE JSON line `python bench.py --gpus 1 --steps 20 --warmup 5 --full` printed (a BENCH_rNN.json record holds the same
+line under "parsed" / in "tail": pass that file and the line is dug out).  Every row names the key it was read from."""
 import argparse
 import json
 import os
