@@ -1,7 +1,7 @@
 /*
  * libstereo_vision_hip.so — C ABI of the MI355X-native stereo disparity engine.
  *
- * Plain C: pointers and sizes only, no torch / C++ types.  Two groups of entry points:
+ * Plain C: pointers and sizes only, no torch / C++ types.  Three groups of entry points:
  *
  *  (A) The reference's own exported symbols, kept signature-for-signature so that the reference's
  *      ctypes binding (stereo_vision/sv.py:164-192) drives this library unchanged:
@@ -15,6 +15,9 @@
  *      exposed as a handle-based, batched API (sv_*): the reference keeps all state in file-scope
  *      globals and function statics (stereo_vision.cpp:50-89, 307-314, 582) and processes one pair
  *      per call; here state lives in an sv_handle and one call takes B independent pairs.
+ *
+ *  (C) The camera front end in front of (B): a calibrated rig (sv_rig_*) turns batches of colour or gray camera
+ *      frames into the engine's input; the legacy entry (A) is one of its clients.
  *
  * All sv_* functions return SV_OK (0) or a negative sv_status; sv_last_error() gives the text.
  * Nothing in this library calls exit().
@@ -256,6 +259,48 @@ int sv_default_host_threads(int ignore_quota);
  * - they are then the same support point twice and interchangeable - and returns -1 (a set it leaves to the host) otherwise. */
 int sv_host_kd_order(const int32_t *xy, int n, int32_t *ids_out);
 int sv_gpu_kd_order(const int32_t *xy, const int32_t *disp, int n, int width, int height, int step, int disp_max, int32_t *ids_out);
+
+/* ---- (C) calibrated stereo rig: camera frames -> the engine's input ------------------------------------------- */
+
+/* A rig is one calibrated stereo camera: the calibration, Q, and the rectification maps at the matching size.  Any number of
+ * rigs can live in one process, independent of each other and of the engine handles.  Its front end turns B pairs of camera
+ * frames into the gray, matching-size (and optionally rectified) u8 images sv_process_batch_device takes, with the arithmetic
+ * of the legacy entry (stereo_vision.cpp:338-341, 590-591, restated): cv::resize(INTER_LINEAR, exact 2x = INTER_AREA) per
+ * channel when the frame's size differs, cvtColor(...2GRAY) with 15-bit weights, cv::remap(INTER_LINEAR, border 0). */
+typedef enum sv_pixel_format { SV_PIX_BGRA8 = 0, SV_PIX_BGR8 = 1, SV_PIX_RGB8 = 2, SV_PIX_GRAY8 = 3 } sv_pixel_format;
+
+typedef struct sv_rig sv_rig;
+
+typedef struct sv_rig_config {
+    int32_t width, height; /* matching size: the engine's limits, 32..8192 x 32..4096 */
+    int32_t device;        /* HIP device of the front end's maps */
+    int32_t rectify;       /* 0: off (the reference's default: stereo_vision.cpp:341 is commented out), 1: remap */
+    float scale;           /* > 0: K1/K2's first two rows are divided by it (stereo_vision.cpp:364-376) */
+    int32_t reserved[3];   /* must be 0 */
+} sv_rig_config;
+
+/* Host only (touches no device): parses the OpenCV YAML (K1 K2 D1 D2 R T required, XR XT optional), stereoRectify at the
+ * matching size (alpha 0, CALIB_ZERO_DISPARITY) and, with rectify = 1, initUndistortRectifyMap for both cameras.  A bad
+ * argument or file returns SV_ERR_ARG; sv_rig_last_error(NULL) gives the text. */
+int sv_rig_create(const char *calibration_yaml, const sv_rig_config *cfg, sv_rig **out);
+int sv_rig_destroy(sv_rig *r);
+/* Text of the last failure on r; r == NULL: of the last failed sv_rig_create on this thread. */
+const char *sv_rig_last_error(const sv_rig *r);
+/* Q (row major 4x4) and the robot-frame transform XR (3x3) / XT (3) if the file has them; any pointer may be NULL.  Returns a
+ * bit mask of what the file had (1 = XR, 2 = XT), or SV_ERR_ARG. */
+int sv_rig_matrices(const sv_rig *r, double *Q16, double *XR9, double *XT3);
+/* The float maps [4][height][width] = lmapx lmapy rmapx rmapy; SV_ERR_STATE if rectification is off. */
+int sv_rig_maps(const sv_rig *r, float *maps);
+/* Front end of B pairs, enqueued on `stream` (a hipStream_t, NULL = the default stream) and not waited for.
+ *   left / right        : device, B frames back to back, each src_height rows of src_pitch bytes, pixel_format pixels
+ *   src_width/height    : the frames' size (<= 2^26 pixels); another size than the matching one is resized to it
+ *   gray_left/right     : device u8 [B][height][width] (the matching size)
+ *   left_bgra           : device u8 [B][height][width][4], 4-byte aligned, or NULL: the left image at the matching size before
+ *                         the remap, as BGRA (A = 255 for 3-channel and gray sources) - the colours getColor() returns
+ * The first call with rectification uploads the maps to cfg.device.  Calls on one rig are serialised; work from several rigs
+ * may interleave freely.  Returns SV_OK, SV_ERR_ARG (nothing enqueued), SV_ERR_NO_DEVICE or SV_ERR_HIP. */
+int sv_rig_frontend_device(sv_rig *r, const uint8_t *left, const uint8_t *right, int batch, int src_width, int src_height, int src_pitch, int pixel_format,
+                           uint8_t *gray_left, uint8_t *gray_right, uint8_t *left_bgra, void *stream);
 
 /* ---- (A) the reference's exported symbols ------------------------------------------------------------- */
 

@@ -8,8 +8,9 @@
 //                    convertTo(CV_8UC1, 4.0)), publishPointCloud (:222-259: (X,Y,Z) = Q*[x y d 1] / w)
 //   clean / getColor     :105-114 / :625-627
 //
-// Everything per frame runs on the GPU: gray conversion, the ELAS engine, the x4 u8 conversion and the reprojection
-// (legacy_kernels.hip); the host only moves the caller's buffers in and the point array out.
+// Everything per frame runs on the GPU: the front end (resize, gray conversion and remap) of an sv_rig (rig.cpp), the ELAS
+// engine, the x4 u8 conversion and the reprojection (legacy_kernels.hip); the host only moves the caller's buffers in and the
+// point array out.  The calibration, Q and the rectification maps are the rig's.
 //
 // Documented deviations from the reference: clean() does not exit(0); `points` is filled on every call
 // (the reference only fills it when graphics==true and otherwise returns uninitialised memory); YOLO object tracking,
@@ -29,7 +30,6 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/stereo_vision_hip.h"
-#include "calib.h"
 
 // engine.cpp (not part of the public header): one device-resident pair on a latency handle whose first GPU phase waits for `ready`
 // on the device instead of the caller synchronising its stream on the host
@@ -37,10 +37,7 @@ int sv_internal_process_after(sv_handle *h, hipEvent_t ready, const uint8_t *lef
 int sv_internal_copy2(sv_handle *h, void *dst_a, const void *src_a, void *dst_b, const void *src_b, size_t bytes_each);
 
 namespace sv {
-void launch_resize_bgra(const unsigned char *src, int sw, int sh, unsigned char *dst, int dw, int dh, hipStream_t st);
-void launch_bgra_to_gray(const unsigned char *bgra_l, const unsigned char *bgra_r, unsigned char *gray_l, unsigned char *gray_r, int n, hipStream_t st);
 void launch_dmap_and_cloud(const float *disp, unsigned char *dmap, double *points, const double *Q16, int W, int H, hipStream_t st);
-void launch_remap_gray(const unsigned char *src, unsigned char *dst, const float *mapx, const float *mapy, int W, int H, hipStream_t st);
 int launch_disp_to_u8(const float *disp, size_t n, unsigned char *out, hipStream_t st);
 int launch_reproject_batch(const float *disp, int batch, int W, int H, const double *Q16, const double *XR9, const double *XT3, unsigned char *dmap, double *points,
                            hipStream_t st);
@@ -53,16 +50,15 @@ struct Legacy {
     bool failed = false;
     int W = 0, H = 0;
     sv_handle *engine = nullptr;
-    sv::Rectification rect;
+    sv_rig *rig = nullptr;              // calibration, Q, rectification maps and the front end
+    double Q[16];
     double *d_Q = nullptr;
-    unsigned char *d_bgra_l = nullptr, *d_bgra_r = nullptr, *d_gray_l = nullptr, *d_gray_r = nullptr, *d_dmap = nullptr;
+    unsigned char *d_bgra_l = nullptr, *d_bgra_r = nullptr, *d_gray_l = nullptr, *d_gray_r = nullptr, *d_dmap = nullptr;  // gray: after the remap if it is on
     float *d_disp = nullptr, *d_disp2 = nullptr;
     double *d_points = nullptr;
     // rectification remap (stereo_vision.cpp:341, commented out in the reference; here: off unless sv_legacy_set_rectify(1))
     bool rectify = false;
-    float *d_maps = nullptr;            // [4][H][W]: lmapx, lmapy, rmapx, rmapy (stereo_vision.cpp:477-478)
-    unsigned char *d_rect_l = nullptr, *d_rect_r = nullptr;
-    std::vector<float> h_maps;
+    std::vector<float> h_maps;          // [4][H][W]: lmapx, lmapy, rmapx, rmapy (stereo_vision.cpp:477-478)
     Double3 *points = nullptr;          // host, library-owned (stereo_vision.cpp:89-93)
     std::vector<Uchar4> colors;         // last left image
     unsigned char *h_dmap = nullptr;    // last u8 disparity image (host, page-locked)
@@ -95,18 +91,21 @@ int g_want_device = 0;            // sv_legacy_set_device: likewise
 bool legacy_init(int width, int height, float scale, const char *yaml, bool subsampling) {
     g.W = width;
     g.H = height;
-    sv::Calibration c;
-    std::string err;
     printf("Using CAMERA_CALIBRATION_YAML : %s\n", yaml ? yaml : "(null)");
-    if (!sv::load_calibration_yaml(yaml, c, err)) {
-        fprintf(stderr, "stereo_vision_hip: %s\n", err.c_str());
+    // K1, K2 / scale_factor (stereo_vision.cpp:364-376), stereoRectify (:439, calib_img_size == out_img_size, :524-525) and
+    // findRectificationMap (:477-478) are the rig's
+    sv_rig_config rc;
+    memset(&rc, 0, sizeof(rc));
+    rc.width = width;
+    rc.height = height;
+    rc.device = g_want_device;
+    rc.rectify = g_want_rectify ? 1 : 0;
+    rc.scale = scale;
+    if (sv_rig_create(yaml, &rc, &g.rig) != SV_OK) {
+        fprintf(stderr, "stereo_vision_hip: %s\n", sv_rig_last_error(nullptr));
         return false;
     }
-    for (int i = 0; i < 6; i++) {  // K1, K2 first two rows /= scale_factor (stereo_vision.cpp:364-376)
-        c.K1[i] /= scale;
-        c.K2[i] /= scale;
-    }
-    sv::stereo_rectify(c, width, height, width, height, 0.0, g.rect);  // :439, calib_img_size == out_img_size (:524-525)
+    (void)sv_rig_matrices(g.rig, g.Q, nullptr, nullptr);
 
     sv_params p;
     sv_params_init(&p, SV_DRIVER);  // stereo_vision.cpp:307-311 (disp_max stays 255)
@@ -142,19 +141,11 @@ bool legacy_init(int width, int height, float scale, const char *yaml, bool subs
     L_TRY(hipMalloc((void **)&g.d_disp2, N * sizeof(float)));
     L_TRY(hipMalloc((void **)&g.d_points, N * 3 * sizeof(double)));
     L_TRY(hipMalloc((void **)&g.d_Q, 16 * sizeof(double)));
-    L_TRY(hipMemcpy(g.d_Q, g.rect.Q, 16 * sizeof(double), hipMemcpyHostToDevice));
+    L_TRY(hipMemcpy(g.d_Q, g.Q, 16 * sizeof(double), hipMemcpyHostToDevice));
     g.rectify = g_want_rectify;
-    if (g.rectify) {  // findRectificationMap's two initUndistortRectifyMap calls (stereo_vision.cpp:477-478)
+    if (g.rectify) {
         g.h_maps.assign(4 * N, 0.f);
-        if (!sv::init_undistort_rectify_map(c.K1, c.D1, g.rect.R1, g.rect.P1, width, height, g.h_maps.data(), g.h_maps.data() + N) ||
-            !sv::init_undistort_rectify_map(c.K2, c.D2, g.rect.R2, g.rect.P2, width, height, g.h_maps.data() + 2 * N, g.h_maps.data() + 3 * N)) {
-            fprintf(stderr, "stereo_vision_hip: singular rectification\n");
-            return false;
-        }
-        L_TRY(hipMalloc((void **)&g.d_maps, 4 * N * sizeof(float)));
-        L_TRY(hipMemcpy(g.d_maps, g.h_maps.data(), 4 * N * sizeof(float), hipMemcpyHostToDevice));
-        L_TRY(hipMalloc((void **)&g.d_rect_l, N));
-        L_TRY(hipMalloc((void **)&g.d_rect_r, N));
+        if (sv_rig_maps(g.rig, g.h_maps.data()) != SV_OK) return false;
     }
     // page-locked: the 11 MB of points per frame come back at PCIe speed instead of through a pageable bounce buffer
     L_TRY(hipHostMalloc((void **)&g.points, N * sizeof(Double3), hipHostMallocDefault));
@@ -208,22 +199,19 @@ bool legacy_frame(const unsigned char *left, const unsigned char *right, int wid
         L_TRY(hipMemcpyAsync(resize ? g.d_src_l : g.d_bgra_l, g.h_stage, Nin * 4, hipMemcpyHostToDevice, g.stream));
         L_TRY(hipMemcpyAsync(resize ? g.d_src_r : g.d_bgra_r, g.h_stage + Nin * 4, Nin * 4, hipMemcpyHostToDevice, g.stream));
     }
-    if (resize) {  // resize(left_img, left_img_OLD, out_img_size) (:590-591): cv::resize, INTER_LINEAR, 8UC4
-        sv::launch_resize_bgra(g.d_src_l, width, height, g.d_bgra_l, g.W, g.H, g.stream);
-        sv::launch_resize_bgra(g.d_src_r, width, height, g.d_bgra_r, g.W, g.H, g.stream);
-    }
-    sv::launch_bgra_to_gray(g.d_bgra_l, g.d_bgra_r, g.d_gray_l, g.d_gray_r, (int)N, g.stream);
-    const unsigned char *in_l = g.d_gray_l, *in_r = g.d_gray_r;
-    if (g.rectify) {  // remap(tmpL, img_left, lmapx, lmapy, INTER_LINEAR); remap(tmpR, img_right, rmapx, rmapy, INTER_LINEAR) (:341)
-        sv::launch_remap_gray(g.d_gray_l, g.d_rect_l, g.d_maps, g.d_maps + N, g.W, g.H, g.stream);
-        sv::launch_remap_gray(g.d_gray_r, g.d_rect_r, g.d_maps + 2 * N, g.d_maps + 3 * N, g.W, g.H, g.stream);
-        in_l = g.d_rect_l, in_r = g.d_rect_r;
+    // resize(left_img, left_img_OLD, out_img_size) (:590-591) when the sizes differ - left_img_OLD's colours kept for getColor -,
+    // cvtColor(BGRA2GRAY) (:338-339) and, if it is on, remap(..., INTER_LINEAR) (:341)
+    const int fe = sv_rig_frontend_device(g.rig, resize ? g.d_src_l : g.d_bgra_l, resize ? g.d_src_r : g.d_bgra_r, 1, width, height, width * 4, SV_PIX_BGRA8,
+                                          g.d_gray_l, g.d_gray_r, resize ? g.d_bgra_l : nullptr, g.stream);
+    if (fe != SV_OK) {
+        fprintf(stderr, "stereo_vision_hip: %s\n", sv_rig_last_error(g.rig));
+        return false;
     }
     L_TRY(hipEventRecord(g.ev_in, g.stream));
     // the colours of the left image as the viewer gets them (left_img_OLD, :590): the staged copy when the sizes agree
     if (!resize) memcpy(g.colors.data(), g.h_stage, N * 4);  // (while the GPU converts and matches)
     // the engine's first stream waits for ev_in on the device; the call returns when the maps are complete
-    if (sv_internal_process_after(g.engine, g.ev_in, in_l, in_r, g.W, g.d_disp, g.d_disp2) != SV_OK) {
+    if (sv_internal_process_after(g.engine, g.ev_in, g.d_gray_l, g.d_gray_r, g.W, g.d_disp, g.d_disp2) != SV_OK) {
         fprintf(stderr, "stereo_vision_hip: %s\n", sv_last_error(g.engine));
         return false;
     }
@@ -279,8 +267,9 @@ Double3 *generatePointCloud(unsigned char *left, unsigned char *right, char *CAM
 void clean(void) {
     std::lock_guard<std::mutex> lk(g_mu);
     if (g.engine) sv_destroy(g.engine);
+    if (g.rig) sv_rig_destroy(g.rig);
     if (g.ready || g.failed) (void)hipSetDevice(g.device);
-    void *dptrs[] = {g.d_bgra_l, g.d_bgra_r, g.d_gray_l, g.d_gray_r, g.d_dmap, g.d_disp, g.d_disp2, g.d_points, g.d_Q, g.d_maps, g.d_rect_l, g.d_rect_r, g.d_src_l, g.d_src_r};
+    void *dptrs[] = {g.d_bgra_l, g.d_bgra_r, g.d_gray_l, g.d_gray_r, g.d_dmap, g.d_disp, g.d_disp2, g.d_points, g.d_Q, g.d_src_l, g.d_src_r};
     for (void *p : dptrs)
         if (p) (void)hipFree(p);
     if (g.ev_in) (void)hipEventDestroy(g.ev_in);
@@ -300,7 +289,7 @@ const unsigned char *sv_legacy_last_dmap(int *width, int *height) {
     return g.h_dmap;
 }
 
-const double *sv_legacy_Q(void) { return g.ready ? g.rect.Q : nullptr; }
+const double *sv_legacy_Q(void) { return g.ready ? g.Q : nullptr; }
 
 void sv_legacy_set_rectify(int on) {
     std::lock_guard<std::mutex> lk(g_mu);
@@ -323,8 +312,8 @@ int sv_legacy_last_gray(unsigned char *left, unsigned char *right) {
     std::lock_guard<std::mutex> lk(g_mu);
     if (!g.ready || !left || !right) return -1;
     const size_t N = (size_t)g.W * g.H;
-    if (hipMemcpy(left, g.rectify ? g.d_rect_l : g.d_gray_l, N, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    if (hipMemcpy(right, g.rectify ? g.d_rect_r : g.d_gray_r, N, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    if (hipMemcpy(left, g.d_gray_l, N, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    if (hipMemcpy(right, g.d_gray_r, N, hipMemcpyDeviceToHost) != hipSuccess) return -1;
     return 0;
 }
 

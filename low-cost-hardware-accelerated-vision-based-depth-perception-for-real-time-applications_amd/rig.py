@@ -1,0 +1,195 @@
+"""A calibrated stereo camera as a handle (sv_rig_* of include/stereo_vision_hip.h): camera frames in, the engine's input,
+disparity, the driver's 8-bit map and point clouds out.
+
+    rig = StereoRig(1242, 375, calibration=DEFAULT_CALIBRATION, rectify=False, scale=1.0)
+    rig.Q, rig.XR, rig.XT                                            # numpy; XR / XT are None when the file has none
+    gl, gr = rig.frontend(left, right, pixel_format="bgr")           # u8 [B,H,W]
+    d1 = rig.disparity(left, right, pixel_format="bgr")              # f32 [B,H,W]
+    d1, dmap, points = rig.point_clouds(left, right, pixel_format="bgr")
+
+Frames are [B,Hs,Ws,C] (C = 4, 3, 3 for "bgra", "bgr", "rgb") or [B,Hs,Ws] for "gray"; one frame without B is accepted.
+Frames of another size than the rig's are resized to it.  CUDA tensors are processed on torch's current stream and CUDA
+tensors come back; numpy arrays go up through page-locked staging and numpy arrays come back.  Rows may be padded (a slice of
+a wider tensor); frames must lie back to back.
+"""
+import ctypes
+
+import numpy as np
+
+from .engine import SvParams, StereoEngine, StereoError, lib, pinned_array, reproject
+from .stereo_vision.sv import DEFAULT_CALIBRATION
+
+PIXEL_FORMATS = {"bgra": 0, "bgr": 1, "rgb": 2, "gray": 3}
+_CHANNELS = {"bgra": 4, "bgr": 3, "rgb": 3, "gray": 1}
+SV_ERR_ARG = -1
+
+
+class SvRigConfig(ctypes.Structure):
+    """sv_rig_config of include/stereo_vision_hip.h."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("device", ctypes.c_int32), ("rectify", ctypes.c_int32),
+                ("scale", ctypes.c_float), ("reserved", ctypes.c_int32 * 3)]
+
+
+_bound = False
+
+
+def rig_lib():
+    """The library with the sv_rig_* signatures declared."""
+    global _bound
+    L = lib()
+    if not _bound:
+        vp = ctypes.c_void_p
+        L.sv_rig_create.argtypes = [ctypes.c_char_p, ctypes.POINTER(SvRigConfig), ctypes.POINTER(vp)]
+        L.sv_rig_create.restype = ctypes.c_int
+        L.sv_rig_destroy.argtypes = [vp]
+        L.sv_rig_destroy.restype = ctypes.c_int
+        L.sv_rig_last_error.argtypes = [vp]
+        L.sv_rig_last_error.restype = ctypes.c_char_p
+        L.sv_rig_matrices.argtypes = [vp, vp, vp, vp]
+        L.sv_rig_matrices.restype = ctypes.c_int
+        L.sv_rig_maps.argtypes = [vp, vp]
+        L.sv_rig_maps.restype = ctypes.c_int
+        L.sv_rig_frontend_device.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
+        L.sv_rig_frontend_device.restype = ctypes.c_int
+        _bound = True
+    return L
+
+
+class StereoRig:
+    def __init__(self, width, height, calibration=DEFAULT_CALIBRATION, rectify=False, scale=1.0, params=None, device=0, **engine_kwargs):
+        """params: the engine's SvParams (default SvParams.driver(255), what generatePointCloud runs); engine_kwargs go to StereoEngine,
+        which is created by the first disparity() / point_clouds() call (a rig used for its front end only holds no engine)."""
+        L = rig_lib()
+        self.width, self.height, self.device = int(width), int(height), int(device)
+        self.rectify = bool(rectify)
+        self.params = params if params is not None else SvParams.driver(255)
+        self._engine_kwargs = engine_kwargs
+        self._engine = None
+        self._stage = {}
+        cfg = SvRigConfig(self.width, self.height, self.device, int(self.rectify), float(scale))
+        h = ctypes.c_void_p()
+        rc = L.sv_rig_create(str(calibration).encode(), ctypes.byref(cfg), ctypes.byref(h))
+        if rc != 0:
+            msg = "sv_rig_create failed (%d): %s" % (rc, L.sv_rig_last_error(None).decode())
+            raise ValueError(msg) if rc == SV_ERR_ARG else StereoError(msg)
+        self._h = h
+        Q, XR, XT = np.zeros(16), np.zeros(9), np.zeros(3)
+        has = L.sv_rig_matrices(self._h, Q.ctypes.data, XR.ctypes.data, XT.ctypes.data)
+        self.Q = Q.reshape(4, 4)
+        self.XR = XR.reshape(3, 3) if has & 1 else None
+        self.XT = XT if has & 2 else None
+
+    def close(self):
+        if self._engine is not None:
+            self._engine.close()
+            self._engine = None
+        if getattr(self, "_h", None):
+            rig_lib().sv_rig_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def maps(self):
+        """[4,H,W] float32 lmapx, lmapy, rmapx, rmapy (initUndistortRectifyMap), or None when rectification is off."""
+        if not self.rectify:
+            return None
+        m = np.zeros((4, self.height, self.width), np.float32)
+        self._check(rig_lib().sv_rig_maps(self._h, m.ctypes.data))
+        return m
+
+    @property
+    def engine(self):
+        if self._engine is None:
+            self._engine = StereoEngine(self.width, self.height, self.params, device=self.device, **self._engine_kwargs)
+        return self._engine
+
+    def _check(self, rc):
+        if rc != 0:
+            msg = "libstereo_vision_hip error %d: %s" % (rc, rig_lib().sv_rig_last_error(self._h).decode())
+            raise ValueError(msg) if rc == SV_ERR_ARG else StereoError(msg)
+
+    # ---- inputs
+    def _frames(self, x, fmt, side):
+        """-> (CUDA uint8 tensor [B,Hs,Ws(,C)] with unit pixel strides, row pitch in bytes, came_from_numpy)."""
+        import torch
+        C = _CHANNELS[fmt]
+        nd = 3 if C == 1 else 4
+        from_numpy = isinstance(x, np.ndarray)
+        if from_numpy:
+            x = np.asarray(x)
+            if x.dtype != np.uint8:
+                raise ValueError("frames must be uint8")
+            if x.ndim == nd - 1:
+                x = x[None]
+            if x.ndim != nd:
+                raise ValueError("expected %s frames [B,H,W%s], got shape %s" % (fmt, "" if C == 1 else ",%d" % C, x.shape))
+            buf = self._stage.get(side)
+            if buf is None or buf.size < x.size:
+                buf = pinned_array((x.size,), np.uint8)
+                self._stage[side] = buf
+            stage = buf[:x.size].reshape(x.shape)
+            np.copyto(stage, x)
+            x = torch.from_numpy(stage).to(torch.device("cuda", self.device), non_blocking=True)
+        elif not (isinstance(x, torch.Tensor) and x.is_cuda):
+            raise ValueError("frames must be numpy arrays or CUDA tensors")
+        if x.dtype != torch.uint8:
+            raise ValueError("frames must be uint8")
+        if x.device != torch.device("cuda", self.device):
+            raise ValueError("frames must be on cuda:%d (the rig's device)" % self.device)
+        if x.dim() == nd - 1:
+            x = x.unsqueeze(0)
+        if x.dim() != nd or (C > 1 and x.shape[3] != C):
+            raise ValueError("expected %s frames [B,H,W%s], got shape %s" % (fmt, "" if C == 1 else ",%d" % C, tuple(x.shape)))
+        B, Hs, Ws = x.shape[:3]
+        pix = (x.stride(3) == 1 and x.stride(2) == C) if C > 1 else x.stride(2) == 1
+        if not pix or x.stride(1) < Ws * C or (B > 1 and x.stride(0) != Hs * x.stride(1)):
+            x = x.contiguous()
+        return x, x.stride(1), from_numpy
+
+    def _run_frontend(self, left, right, pixel_format, colors):
+        import torch
+        fmt = str(pixel_format).lower()
+        if fmt not in PIXEL_FORMATS:
+            raise ValueError("pixel_format must be one of %s" % sorted(PIXEL_FORMATS))
+        l, pitch, from_numpy = self._frames(left, fmt, 0)
+        r, rpitch, _ = self._frames(right, fmt, 1)
+        if tuple(l.shape) != tuple(r.shape) or pitch != rpitch:
+            raise ValueError("left and right frames differ in shape or row pitch: %s / %s" % (tuple(l.shape), tuple(r.shape)))
+        B, Hs, Ws = l.shape[:3]
+        dev = l.device
+        gl = torch.empty((B, self.height, self.width), dtype=torch.uint8, device=dev)
+        gr = torch.empty_like(gl)
+        col = torch.empty((B, self.height, self.width, 4), dtype=torch.uint8, device=dev) if colors else None
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream
+            self._check(rig_lib().sv_rig_frontend_device(self._h, l.data_ptr(), r.data_ptr(), B, Ws, Hs, pitch, PIXEL_FORMATS[fmt], gl.data_ptr(),
+                                                         gr.data_ptr(), col.data_ptr() if col is not None else None, st))
+        return gl, gr, col, from_numpy
+
+    # ---- public
+    def frontend(self, left, right, pixel_format="bgr", colors=False):
+        """-> (gray_left, gray_right) u8 [B,H,W] (+ the left colours BGRA [B,H,W,4] with colors=True), enqueued on torch's current stream."""
+        gl, gr, col, from_numpy = self._run_frontend(left, right, pixel_format, colors)
+        out = (gl, gr) + ((col,) if colors else ())
+        return tuple(t.cpu().numpy() for t in out) if from_numpy else out
+
+    def disparity(self, left, right, pixel_format="bgr"):
+        """Left disparity maps f32 [B,H,W] of the engine (params of the rig) on the front end's images."""
+        gl, gr, _, from_numpy = self._run_frontend(left, right, pixel_format, False)
+        d1, _ = self.engine.process_device(gl, gr, want_d2=False)
+        return d1.cpu().numpy() if from_numpy else d1
+
+    def point_clouds(self, left, right, pixel_format="bgr", colors=False):
+        """-> (d1 f32 [B,H,W], dmap u8 [B,H,W] = saturate(round(4 d)), points f64 [B,H,W,3] = Q [x y dmap 1] / w[, colours BGRA [B,H,W,4]]):
+        the reference driver's per-frame outputs (stereo_vision.cpp:316, 233-256), for a batch."""
+        if self.params.subsampling:
+            raise ValueError("point_clouds does not support half-resolution maps (params.subsampling)")
+        gl, gr, col, from_numpy = self._run_frontend(left, right, pixel_format, colors)
+        d1, _ = self.engine.process_device(gl, gr, want_d2=False)
+        dmap, pts = reproject(d1, self.Q)
+        out = (d1, dmap, pts) + ((col,) if colors else ())
+        return tuple(t.cpu().numpy() for t in out) if from_numpy else out

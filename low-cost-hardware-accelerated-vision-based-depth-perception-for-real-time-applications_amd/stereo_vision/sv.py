@@ -142,7 +142,14 @@ def main(argv=None):
     parser.add_argument("-ctu", "--camera_to_use", default=-1, type=int, help="(cameras need cv2; not available)")
     parser.add_argument("-sw", "--swap", default=False, action="store_true", help="Swaps cameras")
     parser.add_argument("-n", "--frames", type=int, default=0, help="stop after this many frames (0 = all)")
+    parser.add_argument("--batch", type=int, default=0, help="run the folder through a StereoRig in batches of N pairs and print pairs/s")
+    parser.add_argument("--out", type=str, default="", help="write the 8-bit disparity maps (4 x disparity) as PNGs into this directory")
+    parser.add_argument("--rectify", default=False, action="store_true", help="rectify the images before matching (both paths)")
     args = parser.parse_args(argv)
+    if args.batch < 0:
+        parser.error("--batch must be >= 1")
+    if args.batch and args.subsampling:
+        parser.error("--batch does not take --subsampling (the per-frame path's zero-padded full-size map is not reproduced)")
 
     root = os.path.expanduser(args.kitti)
     if args.dataset == "kitti2015":
@@ -154,9 +161,20 @@ def main(argv=None):
     files = sorted(os.path.basename(p) for p in glob.glob(os.path.join(ldir, "*.png")))
     if not files:
         parser.error("no PNG images under %s" % ldir)
+    if args.frames:
+        files = files[:args.frames]
+    if args.out:
+        os.makedirs(args.out, exist_ok=True)
+    if args.batch:
+        _run_batched(args, ldir, rdir, files)
+        return
     s = stereo_vision(width=1242 // args.scale, height=375 // args.scale, objectTracking=args.object_track, display=False, graphics=False,
                       scale=args.scale, pc_extrapolation=int(args.pointcloud_interpolation), CAMERA_CALIBRATION_YAML=args.camera_calibration,
                       subsampling=bool(args.subsampling))
+    if args.rectify:
+        s.sv.sv_legacy_set_rectify.argtypes = [ctypes.c_int]
+        s.sv.sv_legacy_set_rectify.restype = None
+        s.sv.sv_legacy_set_rectify(1)
     import time
     n = 0
     for name in files:
@@ -167,7 +185,45 @@ def main(argv=None):
         pts = s.generatePointCloud(left, right)
         dt = time.perf_counter() - t0
         print("(FPS=%f) (%d, %d) (t_t=%f) valid=%.3f" % (1.0 / dt, s.height, s.width, dt, float(np.isfinite(pts[:, 2]).mean())))
+        if args.out:
+            _write_png(os.path.join(args.out, name), s.last_disparity_u8())
         n += 1
-        if args.frames and n >= args.frames:
-            break
     s.close()
+
+
+def _write_png(path, u8):
+    from PIL import Image
+    Image.fromarray(u8).save(path)
+
+
+def _run_batched(args, ldir, rdir, files):
+    """--batch N: the folder through a StereoRig (the batched front end and engine) N pairs at a time."""
+    import time
+    import torch
+    from ..engine import disparity_to_u8
+    from ..rig import StereoRig
+    rig = StereoRig(1242 // args.scale, 375 // args.scale, calibration=args.camera_calibration, rectify=args.rectify, scale=args.scale)
+    n, busy = 0, 0.0
+    try:
+        for i in range(0, len(files), args.batch):
+            names = files[i:i + args.batch]
+            lr = [(_imread_bgr(os.path.join(ldir, f), args.scale), _imread_bgr(os.path.join(rdir, f), args.scale)) for f in names]
+            if args.swap:
+                lr = [(r, l) for l, r in lr]
+            left = torch.from_numpy(np.stack([l for l, _ in lr])).cuda(rig.device)
+            right = torch.from_numpy(np.stack([r for _, r in lr])).cuda(rig.device)
+            torch.cuda.synchronize(rig.device)
+            t0 = time.perf_counter()
+            d1 = rig.disparity(left, right, pixel_format="bgr")
+            dmap = disparity_to_u8(d1)
+            torch.cuda.synchronize(rig.device)
+            busy += time.perf_counter() - t0
+            dmap = dmap.cpu().numpy()
+            for name, m in zip(names, dmap):
+                if args.out:
+                    _write_png(os.path.join(args.out, name), m)
+            n += len(names)
+            print("batch of %d (%d, %d): %.1f pairs/s so far" % (len(names), rig.height, rig.width, n / busy))
+    finally:
+        rig.close()
+    print("pairs/s %.1f (%d pairs, batch %d)" % (n / busy if busy else 0.0, n, args.batch))
