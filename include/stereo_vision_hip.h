@@ -19,6 +19,9 @@
  *  (C) The camera front end in front of (B): a calibrated rig (sv_rig_*) turns batches of colour or gray camera
  *      frames into the engine's input; the legacy entry (A) is one of its clients.
  *
+ *  (D) Behind (B): bird's-eye views (sv_top_view_*) - 2-D ground grids of where a batch of point clouds, or of clouds
+ *      reprojected from disparity maps on the fly, fell (the reference's points_2_top_view helper, stereo_vision/sv.py:87-134).
+ *
  * All sv_* functions return SV_OK (0) or a negative sv_status; sv_last_error() gives the text.
  * Nothing in this library calls exit().
  */
@@ -301,6 +304,57 @@ int sv_rig_maps(const sv_rig *r, float *maps);
  * may interleave freely.  Returns SV_OK, SV_ERR_ARG (nothing enqueued), SV_ERR_NO_DEVICE or SV_ERR_HIP. */
 int sv_rig_frontend_device(sv_rig *r, const uint8_t *left, const uint8_t *right, int batch, int src_width, int src_height, int src_pitch, int pixel_format,
                            uint8_t *gray_left, uint8_t *gray_right, uint8_t *left_bgra, void *stream);
+
+/* ---- (D) bird's-eye views: point clouds or disparity maps -> 2-D ground grids ---------------------------------- */
+
+/* The grid of the reference's points_2_top_view (stereo_vision/sv.py:87-134), restated in our stereo_vision/sv.py.  The axes are
+ * lidar axes: x forward becomes the rows, y left the columns.  For each point (X, Y, Z) of a frame, in double:
+ *   in range  x0 < X < x1 && y0 < Y < y1 && z0 < Z < z1 (strict: NaN and +-inf never pass)
+ *   cell      row = trunc(x1 s) - trunc(X s), col = trunc(y1 s) - trunc(Y s) (every in-range point lands in the grid)
+ *   value     (uint8) trunc(((max_dist - dist) / max_dist) * 255) with dist = sqrt(X*X + Y*Y), max_dist = sqrt(x1*x1 + y1*y1)
+ *             (no FMA, correctly rounded sqrt); 0 where dist > max_dist (the reference's cast of a negative is undefined)
+ * SV_TOPVIEW_REFERENCE: uint8 [B][rows][cols], each cell the value of its in-range point with the largest flat index (numpy's
+ * last-writer order of img[y_img, x_img] = dist_lim), 0 where empty.  SV_TOPVIEW_COUNT: int32 [B][rows][cols], the number of
+ * in-range points per cell.  Both are bitwise reproducible. */
+enum { SV_TOPVIEW_REFERENCE = 0, SV_TOPVIEW_COUNT = 1 };
+enum { SV_TOPVIEW_DMAP = 0, SV_TOPVIEW_D1 = 1 };
+
+typedef struct sv_top_view_spec {
+    double x_range[2], y_range[2], z_range[2]; /* x/y: integer-valued, lo < hi, |bound| <= 2^31; z: lo < hi (may be infinite) */
+    int32_t scale;                              /* >= 1 */
+    int32_t mode;                               /* SV_TOPVIEW_REFERENCE = 0 (u8), SV_TOPVIEW_COUNT = 1 (int32) */
+    int32_t disparity;                          /* SV_TOPVIEW_DMAP = 0, SV_TOPVIEW_D1 = 1 (disparity entry only) */
+    int32_t reserved[5];                        /* must be 0 */
+} sv_top_view_spec;
+
+/* Host only: rows = (x1 - x0) * scale + 1, cols = (y1 - y0) * scale + 1.  SV_ERR_ARG for a bad spec: a NULL spec or output, a
+ * non-integer, non-finite or too large x / y bound, lo >= hi (NaN included), scale < 1, mode or disparity not 0 / 1, a non-zero
+ * reserved word, a grid over 32768 in either dimension, or max_dist == 0 in reference mode (x1 = y1 = 0). */
+int sv_top_view_dims(const sv_top_view_spec *spec, int *rows, int *cols);
+/* Host only: bytes of the uint64 [batch][rows][cols] workspace reference mode needs; 0 in count mode; SIZE_MAX for a bad spec or
+ * batch < 0. */
+size_t sv_top_view_workspace_bytes(const sv_top_view_spec *spec, int batch);
+/* Grids of a batch of f64 clouds, enqueued on `stream` (a hipStream_t, NULL = the default stream) and not waited for.
+ *   points     : double [batch][n_points][3] device; n_points < 2^31
+ *   out        : device, uint8 (reference) or int32 (count) [batch][rows][cols]; every cell is written
+ *   workspace  : device, >= sv_top_view_workspace_bytes(spec, batch) bytes, 8-byte aligned (may be NULL in count mode)
+ * batch <= 65535.  Returns SV_OK (batch 0: nothing enqueued), SV_ERR_ARG (bad spec, NULL buffer, workspace too small, n_points out
+ * of range; nothing enqueued) or SV_ERR_HIP. */
+int sv_top_view_points_device(const double *points, int batch, int64_t n_points, const sv_top_view_spec *spec, void *out, void *workspace,
+                              size_t workspace_bytes, void *stream);
+/* The same from disparity maps, fused: each pixel's point is computed in registers with sv_reproject_batch_device's arithmetic and
+ * summation order, and no cloud is written.  spec->disparity: SV_TOPVIEW_DMAP reprojects the driver's dmap = saturate(
+ * round_half_even(4 d)) of every pixel, so the grid equals that of sv_reproject_batch_device's cloud (its points are at a quarter of
+ * metric depth: the driver's convention); SV_TOPVIEW_D1 reprojects the float d itself (metres) and skips pixels with d <= 0 (the
+ * engine's invalid pixels are -10).  The flat index of pixel (x, y) is y * width + x.
+ *   disp       : float [batch][height][width] device; width * height < 2^31, height <= 65535
+ *   Q16, XR9, XT3: HOST, as for sv_reproject_batch_device (XR9 and XT3 both NULL = no transform)
+ * Other arguments and results as sv_top_view_points_device. */
+int sv_top_view_disparity_device(const float *disp, int batch, int width, int height, const double *Q16, const double *XR9, const double *XT3,
+                                 const sv_top_view_spec *spec, void *out, void *workspace, size_t workspace_bytes, void *stream);
+/* Test hook for the calls above, process-wide: combine != 0 (the default) merges the lanes of a wavefront that hit the same cell
+ * into one atomic; atomics_device != NULL: every grid atomic issued is also counted into that device uint64.  Returns SV_OK. */
+int sv_debug_top_view(int combine, unsigned long long *atomics_device);
 
 /* ---- (A) the reference's exported symbols ------------------------------------------------------------- */
 

@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "reproject.h"
+
 namespace sv {
 
 __global__ __launch_bounds__(256) void k_dmap_cloud(const float *__restrict__ disp, uint8_t *__restrict__ dmap, double *__restrict__ pts, const double *__restrict__ Q, int W, int H) {
@@ -52,30 +54,15 @@ int launch_disp_to_u8(const float *disp, size_t n, unsigned char *out, hipStream
 }
 
 // Batched form with the CUDA variant's optional robot-frame transform (parallel_includes/main/stereo_vision.cu:188-212:
-// point = XR * (X, Y, Z) + XT); Q / XR / XT travel as kernel arguments.
-struct ReprojectArgs {
-    double Q[16], XR[9], XT[3];
-    int has_xf;
-};
-
+// point = XR * (X, Y, Z) + XT); the per-pixel arithmetic is reproject.h's, shared with the fused top view.
 __global__ __launch_bounds__(256) void k_reproject_batch(const float *__restrict__ disp, uint8_t *__restrict__ dmap, double *__restrict__ pts, ReprojectArgs a, int W, int H) {
     const int i = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
     if (i >= W) return;
     const size_t p = ((size_t)blockIdx.z * H + j) * W + i;
-    int v = __float2int_rn(disp[p] * 4.0f);  // convertTo(CV_8UC1, 4.0): round half to even, saturate
-    v = v < 0 ? 0 : (v > 255 ? 255 : v);
+    const int v = sv_dmap_u8(disp[p]);
     if (dmap) dmap[p] = (uint8_t)v;
-    const double x = (double)i, y = (double)j, d = (double)v;
-    double pos[4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) pos[r] = ((a.Q[4 * r] * x + a.Q[4 * r + 1] * y) + a.Q[4 * r + 2] * d) + a.Q[4 * r + 3];
-    double X = pos[0] / pos[3], Y = pos[1] / pos[3], Z = pos[2] / pos[3];
-    if (a.has_xf) {
-        const double px = ((a.XR[0] * X + a.XR[1] * Y) + a.XR[2] * Z) + a.XT[0];
-        const double py = ((a.XR[3] * X + a.XR[4] * Y) + a.XR[5] * Z) + a.XT[1];
-        const double pz = ((a.XR[6] * X + a.XR[7] * Y) + a.XR[8] * Z) + a.XT[2];
-        X = px, Y = py, Z = pz;
-    }
+    double X, Y, Z;
+    sv_reproject_point(a, (double)i, (double)j, (double)v, X, Y, Z);
     pts[3 * p] = X;
     pts[3 * p + 1] = Y;
     pts[3 * p + 2] = Z;

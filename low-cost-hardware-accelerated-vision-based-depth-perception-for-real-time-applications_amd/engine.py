@@ -460,6 +460,108 @@ def disparity_to_u8(disp, out=None):
     return out
 
 
+class SvTopViewSpec(ctypes.Structure):
+    """sv_top_view_spec of include/stereo_vision_hip.h."""
+    _fields_ = [("x_range", ctypes.c_double * 2), ("y_range", ctypes.c_double * 2), ("z_range", ctypes.c_double * 2), ("scale", ctypes.c_int32),
+                ("mode", ctypes.c_int32), ("disparity", ctypes.c_int32), ("reserved", ctypes.c_int32 * 5)]
+
+
+_TOP_VIEW_MODES = {"reference": 0, "count": 1}
+_TOP_VIEW_DISPARITY = {"dmap": 0, "d1": 1}
+_top_view_bound = False
+
+
+def top_view_lib():
+    """The library with the sv_top_view_* signatures declared."""
+    global _top_view_bound
+    L = lib()
+    if not _top_view_bound:
+        vp, sp = ctypes.c_void_p, ctypes.POINTER(SvTopViewSpec)
+        L.sv_top_view_dims.argtypes = [sp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+        L.sv_top_view_dims.restype = ctypes.c_int
+        L.sv_top_view_workspace_bytes.argtypes = [sp, ctypes.c_int]
+        L.sv_top_view_workspace_bytes.restype = ctypes.c_size_t
+        L.sv_top_view_points_device.argtypes = [vp, ctypes.c_int, ctypes.c_int64, sp, vp, vp, ctypes.c_size_t, vp]
+        L.sv_top_view_points_device.restype = ctypes.c_int
+        L.sv_top_view_disparity_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, sp, vp, vp, ctypes.c_size_t, vp]
+        L.sv_top_view_disparity_device.restype = ctypes.c_int
+        L.sv_debug_top_view.argtypes = [ctypes.c_int, vp]
+        L.sv_debug_top_view.restype = ctypes.c_int
+        _top_view_bound = True
+    return L
+
+
+def top_view_spec(x_range, y_range, z_range, scale, mode="reference", disparity="dmap"):
+    """-> (SvTopViewSpec, rows, cols); ValueError for a bad argument (the checks of sv_top_view_dims, made in Python first)."""
+    from .stereo_vision.sv import top_view_grid
+    rows, cols = top_view_grid(x_range, y_range, z_range, scale, mode)
+    if disparity not in _TOP_VIEW_DISPARITY:
+        raise ValueError("disparity must be one of %s, got %r" % (sorted(_TOP_VIEW_DISPARITY), disparity))
+    spec = SvTopViewSpec()
+    spec.x_range[:] = [float(v) for v in x_range]
+    spec.y_range[:] = [float(v) for v in y_range]
+    spec.z_range[:] = [float(v) for v in z_range]
+    spec.scale, spec.mode, spec.disparity = int(scale), _TOP_VIEW_MODES[mode], _TOP_VIEW_DISPARITY[disparity]
+    return spec, rows, cols
+
+
+def _top_view_buffers(spec, B, rows, cols, device):
+    """The grid (u8 or int32 [B,rows,cols]) and the reference mode's key workspace, from torch's allocator."""
+    import torch
+    out = torch.empty((B, rows, cols), dtype=torch.uint8 if spec.mode == 0 else torch.int32, device=device)
+    nbytes = top_view_lib().sv_top_view_workspace_bytes(ctypes.byref(spec), B)
+    ws = torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=device) if nbytes else None
+    return out, ws, nbytes
+
+
+def _top_view_check(rc, name):
+    if rc != 0:
+        msg = "%s failed (%d)" % (name, rc)
+        raise ValueError(msg) if rc == -1 else StereoError(msg)
+
+
+def top_view(points, x_range, y_range, z_range, scale, mode="reference"):
+    """Bird's-eye views of a batch of clouds on the device: points is a CUDA float64 tensor [B,...,3] (e.g. rig.point_clouds' [B,H,W,3]),
+    each frame's points in flat order.  Returns a CUDA tensor [B,rows,cols], uint8 (mode "reference") or int32 (mode "count"), equal
+    to stereo_vision.sv.points_2_top_view of each frame.  Enqueued on torch's current stream (not waited for)."""
+    import torch
+    spec, rows, cols = top_view_spec(x_range, y_range, z_range, scale, mode)
+    if not (isinstance(points, torch.Tensor) and points.is_cuda and points.dtype == torch.float64 and points.dim() >= 3 and points.shape[-1] == 3):
+        raise ValueError("points must be a CUDA float64 tensor [B,...,3]")
+    B = points.shape[0]
+    pts = points.contiguous()
+    n = pts.numel() // (3 * B) if B else 0
+    out, ws, nbytes = _top_view_buffers(spec, B, rows, cols, pts.device)
+    with torch.cuda.device(pts.device):
+        rc = top_view_lib().sv_top_view_points_device(pts.data_ptr(), B, n, ctypes.byref(spec), out.data_ptr(), ws.data_ptr() if ws is not None else None,
+                                                      nbytes, torch.cuda.current_stream(pts.device).cuda_stream)
+    _top_view_check(rc, "sv_top_view_points_device")
+    return out
+
+
+def top_view_from_disparity(disp, Q, x_range, y_range, z_range, scale, XR=None, XT=None, disparity="dmap", mode="reference"):
+    """Bird's-eye views straight from disparity maps (CUDA float32 [B,H,W]): each pixel's point is reproject()'s, computed in registers,
+    and no cloud is written.  disparity "dmap" reprojects the driver's saturate(round(4 d)) - the grid of top_view(reproject(disp, Q, XR,
+    XT)[1]), whose points are at a quarter of metric depth (the driver's convention) -; "d1" reprojects d itself (metres) and skips
+    pixels with d <= 0.  Returns what top_view returns; enqueued on torch's current stream."""
+    import torch
+    spec, rows, cols = top_view_spec(x_range, y_range, z_range, scale, mode, disparity)
+    if not (isinstance(disp, torch.Tensor) and disp.is_cuda and disp.dtype == torch.float32 and disp.dim() == 3):
+        raise ValueError("disp must be a CUDA float32 tensor [B,H,W]")
+    disp = disp.contiguous()
+    B, H, W = disp.shape
+    q = np.ascontiguousarray(Q, dtype=np.float64).reshape(16)
+    xr = None if XR is None else np.ascontiguousarray(XR, dtype=np.float64).reshape(9)
+    xt = None if XT is None else np.ascontiguousarray(XT, dtype=np.float64).reshape(3)
+    out, ws, nbytes = _top_view_buffers(spec, B, rows, cols, disp.device)
+    with torch.cuda.device(disp.device):
+        rc = top_view_lib().sv_top_view_disparity_device(disp.data_ptr(), B, W, H, q.ctypes.data, xr.ctypes.data if xr is not None else None,
+                                                         xt.ctypes.data if xt is not None else None, ctypes.byref(spec), out.data_ptr(),
+                                                         ws.data_ptr() if ws is not None else None, nbytes, torch.cuda.current_stream(disp.device).cuda_stream)
+    _top_view_check(rc, "sv_top_view_disparity_device")
+    return out
+
+
 def host_support_filter(params, dcan, width, height, threads=0, lattice=False):
     """Product host stage: lattice filters + corner points (CPU by design; see csrc/host_stage.h).  threads > 0: the lattice shared between
     that many threads (what single-pair calls do); lattice=True: also return the filtered lattice."""

@@ -6,6 +6,7 @@ disparity, the driver's 8-bit map and point clouds out.
     gl, gr = rig.frontend(left, right, pixel_format="bgr")           # u8 [B,H,W]
     d1 = rig.disparity(left, right, pixel_format="bgr")              # f32 [B,H,W]
     d1, dmap, points = rig.point_clouds(left, right, pixel_format="bgr")
+    grid = rig.top_view(left, right, (0, 40), (-20, 20), (-1.4, 1.0), 10, disparity="d1", transform=(CAMERA_TO_VEHICLE, None))
 
 Frames are [B,Hs,Ws,C] (C = 4, 3, 3 for "bgra", "bgr", "rgb") or [B,Hs,Ws] for "gray"; one frame without B is accepted.
 Frames of another size than the rig's are resized to it.  CUDA tensors are processed on torch's current stream and CUDA
@@ -16,8 +17,8 @@ import ctypes
 
 import numpy as np
 
-from .engine import SvParams, StereoEngine, StereoError, lib, pinned_array, reproject
-from .stereo_vision.sv import DEFAULT_CALIBRATION
+from .engine import SvParams, StereoEngine, StereoError, lib, pinned_array, reproject, top_view_from_disparity, top_view_spec
+from .stereo_vision.sv import CAMERA_TO_VEHICLE, DEFAULT_CALIBRATION  # noqa: F401 (CAMERA_TO_VEHICLE: re-exported for top_view)
 
 PIXEL_FORMATS = {"bgra": 0, "bgr": 1, "rgb": 2, "gray": 3}
 _CHANNELS = {"bgra": 4, "bgr": 3, "rgb": 3, "gray": 1}
@@ -193,3 +194,32 @@ class StereoRig:
         dmap, pts = reproject(d1, self.Q)
         out = (d1, dmap, pts) + ((col,) if colors else ())
         return tuple(t.cpu().numpy() for t in out) if from_numpy else out
+
+    def top_view(self, left, right, x_range, y_range, z_range, scale, pixel_format="bgr", mode="reference", disparity="dmap", transform=None):
+        """Bird's-eye views [B,rows,cols] of B pairs (uint8 for mode "reference", int32 for "count"; the grid of
+        stereo_vision.sv.points_2_top_view): front end, engine, then the fused disparity -> grid kernel - no point cloud is written.
+        disparity "dmap": the points of point_clouds (the driver's convention, a quarter of metric depth); "d1": the float disparity
+        reprojected, in metres, pixels with d <= 0 skipped.  transform: None, "rig" (the calibration file's XR / XT; ValueError if it
+        has none) or (XR, XT) - point = XR (X, Y, Z) + XT, either may be None.  The helper's axes are (forward, left, up); the camera's
+        are (right, down, forward), so a camera-fixed top view takes
+
+            XR = [[0, 0, 1], [-1, 0, 0], [0, -1, 0]], XT = 0       (rig.CAMERA_TO_VEHICLE)
+
+        e.g. rig.top_view(l, r, (0, 40), (-20, 20), (-1.4, 1.0), 10, disparity="d1", transform=(CAMERA_TO_VEHICLE, None))."""
+        if self.params.subsampling:
+            raise ValueError("top_view does not support half-resolution maps (params.subsampling)")
+        top_view_spec(x_range, y_range, z_range, scale, mode, disparity)  # argument errors before any work
+        if transform is None:
+            XR = XT = None
+        elif isinstance(transform, str) and transform == "rig":
+            if self.XR is None and self.XT is None:
+                raise ValueError("transform=\"rig\": the calibration file has no XR / XT")
+            XR, XT = self.XR, self.XT
+        elif isinstance(transform, (tuple, list)) and len(transform) == 2:
+            XR, XT = transform
+        else:
+            raise ValueError("transform must be None, \"rig\" or (XR, XT)")
+        gl, gr, _, from_numpy = self._run_frontend(left, right, pixel_format, False)
+        d1, _ = self.engine.process_device(gl, gr, want_d2=False)
+        grid = top_view_from_disparity(d1, self.Q, x_range, y_range, z_range, scale, XR=XR, XT=XT, disparity=disparity, mode=mode)
+        return grid.cpu().numpy() if from_numpy else grid

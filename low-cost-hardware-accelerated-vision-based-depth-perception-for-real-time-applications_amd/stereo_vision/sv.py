@@ -13,6 +13,12 @@ Differences, all forced by the environment or by bugs of the reference (SURVEY.m
     (removeSky, subsampling) - half-resolution mode is selected with sv_legacy_set_subsampling() before the first frame;
   * __del__ calls clean(), which here frees the library state but does NOT exit() the interpreter;
   * the dataset download helpers of the reference's CLI are not provided (no network); --demo reads --kitti.
+
+The reference's top-view helpers (sv.py:87-134) are here as a numpy restatement with the same names and signatures:
+normalize_depth, in_range_points and points_2_top_view (plus mode="count").  They are the CPU form of engine.top_view /
+engine.top_view_from_disparity / rig.StereoRig.top_view and the tests' oracle.  Deviations: a value whose
+quotient is negative (dist > max_dist) is 0; non-integer x / y ranges, lo >= hi, a scale that is not a positive integer and
+max_dist == 0 in "reference" mode raise ValueError.
 """
 import argparse
 import ctypes
@@ -25,6 +31,85 @@ from numpy.ctypeslib import ndpointer
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_STEREO_VISION_SO_PATH = os.path.join(os.path.dirname(HERE), "libstereo_vision_hip.so")
 DEFAULT_CALIBRATION = os.path.join(HERE, "data", "kitti_2011_09_26.yml")
+
+
+# --top-view: the camera's (right, down, forward) to the helper's lidar axes (forward, left, up), and the grid the CLI writes
+CAMERA_TO_VEHICLE = np.array([[0.0, 0.0, 1.0], [-1.0, 0.0, 0.0], [0.0, -1.0, 0.0]])
+CLI_TOP_VIEW = {"x_range": (0, 40), "y_range": (-20, 20), "z_range": (-1.4, 1.0), "scale": 10}
+TOP_VIEW_MODES = ("reference", "count")
+
+
+def _integer(v, what):
+    f = float(v)
+    if not (np.isfinite(f) and f == np.trunc(f)):
+        raise ValueError("%s must be integer-valued, got %r" % (what, v))
+    return f
+
+
+def top_view_grid(x_range, y_range, z_range, scale, mode="reference"):
+    """(rows, cols) of the top view, after the checks sv_top_view_dims makes (ValueError for a bad argument): x / y bounds
+    integer-valued with |bound| <= 2^31, lo < hi for all three ranges, scale a positive integer, rows and cols <= 32768, and
+    max_dist = sqrt(x1^2 + y1^2) > 0 in "reference" mode."""
+    if mode not in TOP_VIEW_MODES:
+        raise ValueError("mode must be one of %s, got %r" % (TOP_VIEW_MODES, mode))
+    if isinstance(scale, bool) or not _integer(scale, "scale") >= 1:
+        raise ValueError("scale must be a positive integer, got %r" % (scale,))
+    s = int(scale)
+    (x0, x1), (y0, y1) = [(_integer(r[0], name), _integer(r[1], name)) for r, name in ((x_range, "x_range"), (y_range, "y_range"))]
+    z0, z1 = float(z_range[0]), float(z_range[1])
+    for lo, hi, name in ((x0, x1, "x_range"), (y0, y1, "y_range"), (z0, z1, "z_range")):
+        if not lo < hi:
+            raise ValueError("%s needs lo < hi, got (%r, %r)" % (name, lo, hi))
+    if max(abs(x0), abs(x1), abs(y0), abs(y1)) > 2.0 ** 31:
+        raise ValueError("x / y bounds must lie within +-2^31")
+    rows, cols = (x1 - x0) * s + 1, (y1 - y0) * s + 1
+    if rows > 32768 or cols > 32768:
+        raise ValueError("grid of %d x %d cells: at most 32768 in either dimension" % (rows, cols))
+    if mode == "reference" and x1 == 0 and y1 == 0:
+        raise ValueError("max_dist = sqrt(x1^2 + y1^2) is 0: no value can be normalised")
+    return int(rows), int(cols)
+
+
+def normalize_depth(val, min_v, max_v):
+    """(uint8) trunc(((max_v - val) / (max_v - min_v)) * 255): near points get high values, like the driver's disparity image
+    (the reference's sv.py:87-92).  A negative quotient (val > max_v) gives 0; the reference's cast of it is undefined."""
+    q = ((max_v - val) / (max_v - min_v)) * 255
+    return np.where(q > 0, q, 0).astype(np.uint8)
+
+
+def in_range_points(points, x, y, z, x_range, y_range, z_range):
+    """The entries of `points` whose (x, y, z) lie strictly inside the three ranges (NaN and +-inf never do)."""
+    return points[np.logical_and.reduce((x > x_range[0], x < x_range[1], y > y_range[0], y < y_range[1], z > z_range[0], z < z_range[1]))]
+
+
+def points_2_top_view(points, x_range, y_range, z_range, scale, mode="reference"):
+    """Top view of one cloud `points` [N, >=3] (X forward, Y left, Z up; float64): a grid of rows = (x1 - x0) * scale + 1 by
+    cols = (y1 - y0) * scale + 1 cells, point (X, Y) in cell (trunc(x1 s) - trunc(X s), trunc(y1 s) - trunc(Y s)).
+    mode "reference": uint8, each cell the normalize_depth value of dist = sqrt(X^2 + Y^2) against max_dist = sqrt(x1^2 + y1^2) of
+    the in-range point with the largest index (what the reference's img[y_img, x_img] = dist_lim leaves), 0 where empty.
+    mode "count": int32, the number of in-range points per cell."""
+    rows, cols = top_view_grid(x_range, y_range, z_range, scale, mode)
+    s = float(int(scale))
+    x1, y1 = float(x_range[1]), float(y_range[1])
+    pts = np.asarray(points, dtype=np.float64)
+    pts = pts.reshape(-1, pts.shape[-1])
+    x, y, z = pts[:, 0], pts[:, 1], pts[:, 2]
+    idx = in_range_points(np.arange(len(pts)), x, y, z, x_range, y_range, z_range)
+    X, Y = x[idx], y[idx]
+    row = (np.trunc(x1 * s) - np.trunc(X * s)).astype(np.int64)
+    col = (np.trunc(y1 * s) - np.trunc(Y * s)).astype(np.int64)
+    # x0 s <= fl(X s) <= x1 s for x0 < X < x1 (monotone rounding, exact integer bounds), so 0 <= row <= (x1 - x0) s; y alike
+    assert row.size == 0 or (row.min() >= 0 and row.max() < rows and col.min() >= 0 and col.max() < cols)
+    flat = row * cols + col
+    if mode == "count":
+        return np.bincount(flat, minlength=rows * cols).astype(np.int32).reshape(rows, cols)
+    max_dist = np.sqrt(x1 * x1 + y1 * y1)
+    value = normalize_depth(np.sqrt(X * X + Y * Y), 0, max_dist)
+    img = np.zeros(rows * cols, np.uint8)
+    # the last (largest-index) point of each cell: the first occurrence in the reversed order
+    cells, first = np.unique(flat[::-1], return_index=True)
+    img[cells] = value[::-1][first]
+    return img.reshape(rows, cols)
 
 
 class stereo_vision:
@@ -145,7 +230,14 @@ def main(argv=None):
     parser.add_argument("--batch", type=int, default=0, help="run the folder through a StereoRig in batches of N pairs and print pairs/s")
     parser.add_argument("--out", type=str, default="", help="write the 8-bit disparity maps (4 x disparity) as PNGs into this directory")
     parser.add_argument("--rectify", default=False, action="store_true", help="rectify the images before matching (both paths)")
+    parser.add_argument("--top-view", type=str, default="", metavar="DIR",
+                        help="with --batch: write each frame's bird's-eye view (points_2_top_view, mode 'reference') as a PNG into DIR: "
+                             "the float disparity reprojected in metres (pixels with d <= 0 skipped), camera (right, down, forward) -> "
+                             "(forward, left, up) by XR = [[0,0,1],[-1,0,0],[0,-1,0]], XT = 0; x 0..40, y -20..20, z -1.4..1.0, "
+                             "scale 10 (401 x 401 cells, row 0 = 40 m ahead, column 0 = 20 m to the left)")
     args = parser.parse_args(argv)
+    if args.top_view and not args.batch:
+        parser.error("--top-view needs --batch")
     if args.batch < 0:
         parser.error("--batch must be >= 1")
     if args.batch and args.subsampling:
@@ -165,6 +257,8 @@ def main(argv=None):
         files = files[:args.frames]
     if args.out:
         os.makedirs(args.out, exist_ok=True)
+    if args.top_view:
+        os.makedirs(args.top_view, exist_ok=True)
     if args.batch:
         _run_batched(args, ldir, rdir, files)
         return
@@ -200,7 +294,7 @@ def _run_batched(args, ldir, rdir, files):
     """--batch N: the folder through a StereoRig (the batched front end and engine) N pairs at a time."""
     import time
     import torch
-    from ..engine import disparity_to_u8
+    from ..engine import disparity_to_u8, top_view_from_disparity
     from ..rig import StereoRig
     rig = StereoRig(1242 // args.scale, 375 // args.scale, calibration=args.camera_calibration, rectify=args.rectify, scale=args.scale)
     n, busy = 0, 0.0
@@ -216,12 +310,17 @@ def _run_batched(args, ldir, rdir, files):
             t0 = time.perf_counter()
             d1 = rig.disparity(left, right, pixel_format="bgr")
             dmap = disparity_to_u8(d1)
+            if args.top_view:  # what rig.top_view(..., disparity="d1", transform=(CAMERA_TO_VEHICLE, None)) gives, on the same d1
+                grids = top_view_from_disparity(d1, rig.Q, XR=CAMERA_TO_VEHICLE, disparity="d1", **CLI_TOP_VIEW)
             torch.cuda.synchronize(rig.device)
             busy += time.perf_counter() - t0
             dmap = dmap.cpu().numpy()
             for name, m in zip(names, dmap):
                 if args.out:
                     _write_png(os.path.join(args.out, name), m)
+            if args.top_view:
+                for name, g in zip(names, grids.cpu().numpy()):
+                    _write_png(os.path.join(args.top_view, name), g)
             n += len(names)
             print("batch of %d (%d, %d): %.1f pairs/s so far" % (len(names), rig.height, rig.width, n / busy))
     finally:
