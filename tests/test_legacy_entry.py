@@ -344,14 +344,12 @@ def _remap_linear_u8(src, mapx, mapy):
     H, W = src.shape
     sx, sy = np.rint(mapx * np.float32(32)).astype(np.int64), np.rint(mapy * np.float32(32)).astype(np.int64)
     ix, iy, fx, fy = sx >> 5, sy >> 5, sx & 31, sy & 31
-    pad = np.zeros((H + 2, W + 2), np.int64)
 
     def at(x, y):
         ok = (x >= 0) & (x < W) & (y >= 0) & (y < H)
         return np.where(ok, src[np.clip(y, 0, H - 1), np.clip(x, 0, W - 1)].astype(np.int64), 0)
 
     v = at(ix, iy) * (32 - fx) * (32 - fy) * 32 + at(ix + 1, iy) * fx * (32 - fy) * 32 + at(ix, iy + 1) * (32 - fx) * fy * 32 + at(ix + 1, iy + 1) * fx * fy * 32
-    del pad
     return ((v + (1 << 14)) >> 15).astype(np.uint8)
 
 
