@@ -47,7 +47,8 @@ typedef struct sv_params {
     int32_t disp_max;              /* elas.h:62  D = disp_max + 1, 10 <= disp_max <= 1023 */
     float support_threshold;       /* elas.h:63 */
     int32_t support_texture;       /* elas.h:64 */
-    int32_t candidate_stepsize;    /* elas.h:65 */
+    int32_t candidate_stepsize;    /* elas.h:65  >= 1; the support matching's LDS (160 KiB per workgroup) bounds it by disp_max: 32 (126 step + 3 disp_max + 22)
+                                    * + 4352 bytes must fit, i.e. step <= 15 at disp_max 1023, <= 37 at 63 (the even step of half resolution counts) */
     int32_t incon_window_size;     /* elas.h:66 */
     int32_t incon_threshold;       /* elas.h:67 */
     int32_t incon_min_support;     /* elas.h:68 */

@@ -344,6 +344,15 @@ int validate(const sv_params &p, const sv_config &c, std::string &err) {
         err = "plane radius ceil(sigma*sradius) must be <= 15";
         return SV_ERR_ARG;
     }
+    {  // support matching stages two rows of both images around 64 lattice points per workgroup: large steps with large ranges overflow the LDS
+        const int step = (int)std::min<long long>((long long)p.candidate_stepsize + (p.subsampling ? p.candidate_stepsize % 2 : 0), 1 << 20);  // the lattice step fill_kparams uses
+        if (!support_lds_fits(step, p.disp_max, support_split_pipeline())) {
+            snprintf(b, sizeof(b), "candidate_stepsize %d with disp_max %d: support matching needs %zu bytes of LDS (at most %zu per workgroup)", step, (int)p.disp_max,
+                     support_lds_bytes(step, p.disp_max, support_split_pipeline()), SV_LDS_PER_WORKGROUP);
+            err = b;
+            return SV_ERR_ARG;
+        }
+    }
     if ((size_t)c.width * c.height >= (1u << 30)) {
         err = "image too large";
         return SV_ERR_ARG;
@@ -443,6 +452,8 @@ void fill_kparams(sv_handle *h) {
     // needs incon_window_size <= 5 (any lattice size: its state lives in global memory)
     h->gpu_filter = h->cfg.gpu_lattice_filter != 2 && p.incon_window_size >= 0 && p.incon_window_size <= 5 &&
                     p.incon_min_support >= 0 && p.incon_min_support <= 60 && p.incon_threshold >= 0 && p.incon_threshold < 4096;  // c_late lives in 6 bits; the classify kernel's sentinel is 16384
+    // ... and orders a pair's uncertain points through a block table of its resolve step: larger lattices (8192 x 4096 at step <= 3) stay on the host
+    if ((size_t)d.Wc * d.Hc > support_filter_max_lattice()) h->gpu_filter = false;
     // (sv_create additionally keeps the filters on the host for chunk < 4: the GPU version is a ~0.4 ms latency chain,
     //  worth it only when many pairs share it)
 }

@@ -515,17 +515,29 @@ __global__ __launch_bounds__(64 * SPLIT) void k_support(KParams k, const uint8_t
     }
 }
 
+size_t support_lds_bytes(int step, int disp_max, int split) {
+    // two rows per image; each staged range starts up to 3 columns early and ends on a whole quad
+    const size_t span = (size_t)(SUP_POINTS - 1) * step;
+    return 2 * (size_t)(64 * split) * sizeof(uint2) + sizeof(uint4) * 2 * ((span + disp_max + 5 + 6) + (span + 2 * (size_t)disp_max + 5 + 6));
+}
+
+bool support_lds_fits(int step, int disp_max, int split) {  // the dynamic LDS above plus k_support's static s_tex, within a workgroup's 160 KiB
+    return support_lds_bytes(step, disp_max, split) + sizeof(uint32_t) * SUP_POINTS <= SV_LDS_PER_WORKGROUP;
+}
+
+int support_split_pipeline() { return SUP_SPLIT; }
+
 void launch_support(const KParams &k, const SlotDev &s, int n, hipStream_t st) {
     if (k.d.Wc < 2 || k.d.Hc < 2) {  // no lattice point besides row 0 / column 0: nothing to match, the lattice is all zero
         (void)hipMemsetAsync(s.dcan, 0, sizeof(int16_t) * (size_t)n * k.d.Wc * k.d.Hc, st);
         return;
     }
-    const int span = (SUP_POINTS - 1) * k.d.step;
     dim3 grid((k.d.Wc - 1 + SUP_POINTS - 1) / SUP_POINTS, k.d.Hc - 1, n);
-    const bool alone = !s.counters && (size_t)grid.x * grid.y * grid.z <= 512;  // fewer than two workgroups per CU
+    // fewer than two workgroups per CU: eight wavefronts per point, unless their records no longer fit next to the staged rows (large
+    // steps with large disparity ranges; sv_create admits only what fits at SUP_SPLIT)
+    const bool alone = !s.counters && (size_t)grid.x * grid.y * grid.z <= 512 && support_lds_fits(k.d.step, k.d.disp_max, SUP_SPLIT_ALONE);
     const int threads = 64 * (alone ? SUP_SPLIT_ALONE : SUP_SPLIT);
-    // two rows per image; each staged range starts up to 3 columns early and ends on a whole quad
-    const size_t shmem = 2 * threads * sizeof(uint2) + sizeof(uint4) * 2 * ((size_t)(span + k.d.disp_max + 5 + 6) + (size_t)(span + 2 * k.d.disp_max + 5 + 6));
+    const size_t shmem = support_lds_bytes(k.d.step, k.d.disp_max, alone ? SUP_SPLIT_ALONE : SUP_SPLIT);
     static std::atomic<size_t> granted[64], granted_c[64], granted_a[64];
     if (s.counters) {
         ensure_dynamic_lds(k_support<true, SUP_SPLIT>, shmem, granted_c, "support_match");
@@ -692,6 +704,7 @@ __global__ __launch_bounds__(FCL_THREADS) void k_filter_classify(Dims d, int win
 // classify block b with pref[b] <= q < pref[b + 1]: a binary search in the blocks' prefix sums (LDS) spreads the points evenly
 // over the threads however they cluster in the lattice (they do: along depth edges).
 #define RSV_MAX_BLOCKS 8192  // classify blocks per pair whose prefix sums fit the LDS table (lattices up to 2 M points)
+size_t support_filter_max_lattice() { return (size_t)RSV_MAX_BLOCKS * FCL_THREADS; }
 __global__ __launch_bounds__(RSV_THREADS) void k_filter_resolve(Dims d, int win, int thr, int need, uint32_t *fcs, const uint32_t *__restrict__ useg,
                                                                 const int32_t *__restrict__ ucnt, int nb, uint32_t *__restrict__ ulist, uint32_t *__restrict__ urest, int32_t *__restrict__ bcnt,
                                                                 int nb2) {

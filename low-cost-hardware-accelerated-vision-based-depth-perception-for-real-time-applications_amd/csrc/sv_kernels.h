@@ -95,6 +95,11 @@ int launch_check_amean_div(unsigned long long *d_mism, hipStream_t st);  // exha
 void launch_copy_block(void *dst, const void *src, size_t bytes, hipStream_t st);  // latency mode: small host <-> device blocks in stream order, by a kernel
 void launch_expand_debug(const KParams &k, const SlotDev &s, int n, uint8_t *desc, hipStream_t st);  // debug: the descriptor images for the stage snapshot
 void launch_support(const KParams &k, const SlotDev &s, int n, hipStream_t st);
+constexpr size_t SV_LDS_PER_WORKGROUP = 160 * 1024;  // gfx950
+size_t support_lds_bytes(int step, int disp_max, int split);  // dynamic LDS of the support matching's launch with `split` wavefronts per point
+bool support_lds_fits(int step, int disp_max, int split);     // ... and whether it fits a workgroup (sv_create refuses what does not at the pipeline's split)
+int support_split_pipeline();                                 // wavefronts per point of the batched support launch (SUP_SPLIT)
+size_t support_filter_max_lattice();                          // lattice points per pair the GPU lattice filter's resolve step can order (RSV_MAX_BLOCKS blocks)
 size_t support_filter_ws_bytes(const KParams &k, int cap);
 size_t ccl_ws_bytes(const KParams &k, int maps_cap);
 size_t ccl_lds_bytes(const KParams &k);

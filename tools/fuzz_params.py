@@ -21,17 +21,26 @@ FIELDS = ["disp_max", "support_threshold", "support_texture", "candidate_stepsiz
           "ipol_gap_width", "filter_median", "filter_adaptive_mean", "postprocess_only_left", "subsampling", "disp_min"]
 
 
-def random_params(rng):
+def random_params(rng, wide=False):
+    """wide: the same draws in the same order over what sv_create admits - disp_max up to 1023, steps 1 ... 16, grids 1 ... 64, plane
+    radii up to 15, disp_min up to disp_max + 2 (a step that the support matching's LDS cannot take with disp_max 1023 becomes 15)."""
     c = rng.choice
     sigma = float(rng.uniform(0.5, 3.0))
-    sradius = float(rng.uniform(1.0, min(4.0, 12.0 / sigma)))
-    return dict(disp_max=int(c([15, 31, 63, 100, 127, 200])), support_threshold=float(rng.uniform(0.7, 0.99)), support_texture=int(c([0, 10, 30])),
-                candidate_stepsize=int(c([3, 4, 5, 6, 7, 10])), incon_window_size=int(c([0, 1, 2, 3, 5, 6, 7])), incon_threshold=int(rng.integers(1, 9)),
-                incon_min_support=int(rng.integers(1, 13)), add_corners=int(c([0, 1])), grid_size=int(c([10, 16, 20, 25, 32])),
+    sradius = float(rng.uniform(1.0, min(4.0, 12.0 / sigma))) if not wide else float(rng.uniform(1.0, 15.0 / sigma))
+    vals = dict(disp_max=int(c([15, 31, 63, 100, 127, 200] if not wide else [10, 31, 32, 63, 255, 256, 300, 511, 767, 1023])),
+                support_threshold=float(rng.uniform(0.7, 0.99)), support_texture=int(c([0, 10, 30])),
+                candidate_stepsize=int(c([3, 4, 5, 6, 7, 10])) if not wide else int(rng.integers(1, 17)), incon_window_size=int(c([0, 1, 2, 3, 5, 6, 7])),
+                incon_threshold=int(rng.integers(1, 9)), incon_min_support=int(rng.integers(1, 13)), add_corners=int(c([0, 1])),
+                grid_size=int(c([10, 16, 20, 25, 32])) if not wide else int(rng.integers(1, 65)),
                 beta=float(rng.uniform(0.01, 0.05)), gamma=float(rng.uniform(1, 20)), sigma=sigma, sradius=sradius, match_texture=int(c([0, 1, 5])),
                 lr_threshold=int(c([0, 1, 2, 3])), speckle_sim_threshold=float(c([0.5, 1, 2, 3.5])), speckle_size=int(c([0, 10, 200, 1000])),
                 ipol_gap_width=int(c([0, 3, 7, 5000])), filter_median=int(c([0, 1])), filter_adaptive_mean=int(c([0, 1])),
-                postprocess_only_left=int(c([0, 1])), subsampling=int(c([0, 0, 1])), disp_min=int(c([0, 0, 0, 2, 5, -3])))  # (drawn last: the earlier draws stay what they were)
+                postprocess_only_left=int(c([0, 1])), subsampling=int(c([0, 0, 1])))
+    # (drawn last: the earlier draws stay what they were)
+    vals["disp_min"] = int(c([0, 0, 0, 2, 5, -3])) if not wide else int(rng.integers(-3, vals["disp_max"] + 3))
+    if wide and vals["disp_max"] > 1000 and vals["candidate_stepsize"] + vals["subsampling"] * (vals["candidate_stepsize"] % 2) > 15:
+        vals["candidate_stepsize"] = 15 - vals["subsampling"]  # (the even step of half resolution: 14)
+    return vals
 
 
 def apply(p, vals):
@@ -87,6 +96,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=40)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--wide", action="store_true", help="draw over the whole envelope sv_create admits")
     a = ap.parse_args()
     eng = importlib.import_module(PKG + ".engine")
     synth = importlib.import_module(PKG + ".synth")
@@ -95,7 +105,7 @@ def main():
     shapes = [(150, 260), (97, 203), (200, 320), (128, 401)]
     bad = 0
     for i in range(a.n):
-        vals = random_params(rng)
+        vals = random_params(rng, wide=a.wide)
         shape = shapes[i % len(shapes)]
         try:
             res = run_case(eng, orc, synth, vals, 100 + i, shape)
