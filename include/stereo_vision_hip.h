@@ -22,6 +22,10 @@
  *  (D) Behind (B): bird's-eye views (sv_top_view_*) - 2-D ground grids of where a batch of point clouds, or of clouds
  *      reprojected from disparity maps on the fly, fell (the reference's points_2_top_view helper, stereo_vision/sv.py:87-134).
  *
+ *  (E) Behind (B) as well: the 3-D position of each detected object (sv_box_positions_*) - the mean of the points inside a
+ *      detector's boxes, for batches, from disparity maps (fused: no cloud is written) or from point clouds (publishPointCloud's
+ *      per-object step, src/serial_includes/main/stereo_vision.cpp:261-278).
+ *
  * All sv_* functions return SV_OK (0) or a negative sv_status; sv_last_error() gives the text.
  * Nothing in this library calls exit().
  */
@@ -356,6 +360,76 @@ int sv_top_view_disparity_device(const float *disp, int batch, int width, int he
 /* Test hook for the calls above, process-wide: combine != 0 (the default) merges the lanes of a wavefront that hit the same cell
  * into one atomic; atomics_device != NULL: every grid atomic issued is also counted into that device uint64.  Returns SV_OK. */
 int sv_debug_top_view(int combine, unsigned long long *atomics_device);
+
+/* ---- (E) object positions: disparity maps or point clouds + detector boxes -> one 3-D point per box --------------- */
+
+/* What publishPointCloud computes for every tracked object (stereo_vision.cpp:261-278: the mean of the cloud inside the detector's
+ * box), for B pairs with up to max_boxes boxes each, and beside the reference's plain mean two selections that survive invalid pixels
+ * and background.  The boxes are the caller's (no detector is part of this library).
+ *
+ * Box: (x, y, w, h) int32, pixels of the width x height map.  Its pixels are the columns i in [clamp(x), clamp(x + w)) and the rows j
+ * in [clamp(y), clamp(y + h)) with clamp(a) = min(max(a, 0), size - 1), as in the reference (:263-264) and in sv_legacy_box_means: the
+ * map's last column and last row are never part of a box.  x + w and y + h are formed in 64 bits.  A box without a pixel (w <= 0,
+ * h <= 0, wholly outside) is legal: n_pixels = 0.
+ *
+ * Pixel: q = its quantised disparity in quarter pixels, P = its point, both with sv_reproject_batch_device's arithmetic (no FMA):
+ *   SV_BOX_DMAP  q = saturate_u8(round_half_even(4 d)) (0..255; NaN gives 0), P = reproject(i, j, (double)q) (+ XR / XT): the driver's
+ *                cloud, at a quarter of metric depth.  Valid iff q > 0.
+ *   SV_BOX_D1    q = min(round_half_even(4 d), 4095) (4 d in float), P = reproject(i, j, (double)d) (+ XR / XT), in metres.  Valid
+ *                iff d > 0 (NaN is invalid; the engine's invalid pixels are -10).
+ *
+ * Selection:
+ *   SV_BOX_ALL    every pixel of the box - the reference's mean; inf / NaN propagate as IEEE says (a pixel with q = 0 has pos.w = 0).
+ *                 With SV_BOX_DMAP this is sv_legacy_box_means for a batch.
+ *   SV_BOX_VALID  the valid pixels.
+ *   SV_BOX_NEAR   the valid pixels with |q - q_med| <= band; q_med = the lower median of q over the box's valid pixels (the smallest q
+ *                 whose cumulative count reaches (n_valid + 1) / 2), band >= 0 in quarter pixels.
+ *
+ * Results per box:
+ *   pos   double [3] = (sum of P over the selected pixels) / (double)n_selected; nothing selected: 0.0 / 0.0 = NaN, as the reference's
+ *         division gives
+ *   stat  int32 [4] = (n_pixels, n_valid, q_med or -1 when n_valid == 0, n_selected), the same for every selection.  The points
+ *         entry knows no disparity: (n_pixels, -1, -1, n_pixels).
+ *
+ * Summation order (per coordinate; the doubles are bitwise reproducible and independent of the batch, of the other boxes, of their
+ * order and of the launch): for each column of the box, left to right, the selected points are added in ascending row order onto
+ * +0.0 (unselected pixels are skipped, not added as zeros); the column sums - of every column, 0.0 where nothing was selected - are then
+ * added left to right onto +0.0.  stereo_vision.sv.box_positions restates it in numpy.  The reference (and sv_legacy_box_means) keeps
+ * ONE running accumulator over columns outer / rows inner, so SV_BOX_ALL agrees with it to rounding: identical for a box one column
+ * wide, otherwise both are recursive sums of the same n terms and per coordinate |ours - theirs| <= 2 g sum|P_i| with
+ * g = (n - 1) u / (1 - (n - 1) u), u = 2^-53; a sum that is not finite has the same class (+inf, -inf, NaN) in both. */
+enum { SV_BOX_ALL = 0, SV_BOX_VALID = 1, SV_BOX_NEAR = 2 };
+enum { SV_BOX_DMAP = 0, SV_BOX_D1 = 1 };
+
+typedef struct sv_box_spec {
+    int32_t select;      /* SV_BOX_ALL / SV_BOX_VALID / SV_BOX_NEAR */
+    int32_t disparity;   /* SV_BOX_DMAP / SV_BOX_D1 (read by the disparity entry; must be one of them for the points entry too) */
+    int32_t band;        /* >= 0, quarter pixels (SV_BOX_NEAR) */
+    int32_t reserved[5]; /* must be 0 */
+} sv_box_spec;
+
+/* From disparity maps, fused: each pixel's point is computed in registers and no cloud is written.  Enqueued on `stream` (a
+ * hipStream_t, NULL = the default stream) as ONE kernel and not waited for; nothing is allocated; safe under stream capture.
+ *   disp         : float [batch][height][width] device; width * height < 2^31
+ *   Q16, XR9, XT3: HOST, as for sv_reproject_batch_device (XR9 and XT3 both NULL = no transform)
+ *   boxes        : int32 [batch][max_boxes][4] device
+ *   n_boxes      : int32 [batch] device, or NULL = max_boxes each.  A value outside [0, max_boxes] is clamped by the kernel (it is
+ *                  device data the host does not read).  Rows of boxes at and beyond n_boxes[b] are left untouched in pos / stat.
+ *   pos          : double [batch][max_boxes][3] device
+ *   stat         : int32 [batch][max_boxes][4] device, or NULL
+ * Returns SV_OK (nothing enqueued for batch == 0 or max_boxes == 0), SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued, the outputs
+ * untouched, the text in sv_last_error(NULL) - for: a NULL spec, disp, Q16, boxes or pos; select or disparity out of range;
+ * band < 0; a non-zero reserved word; batch < 0 or > 65535; max_boxes < 0 or > 65535; width < 1 or height < 1;
+ * width * height >= 2^31. */
+int sv_box_positions_disparity_device(const float *disp, int batch, int width, int height, const double *Q16, const double *XR9, const double *XT3,
+                                      const int32_t *boxes, const int32_t *n_boxes, int max_boxes, const sv_box_spec *spec, double *pos, int32_t *stat,
+                                      void *stream);
+/* The same over f64 clouds: points double [batch][height][width][3] device (e.g. sv_reproject_batch_device's points_out), SV_BOX_ALL
+ * only - a cloud has no disparity to select by; any other selection is SV_ERR_ARG, as is a NULL points.  Other arguments, results and
+ * errors as above.  On sv_reproject_batch_device's cloud it returns what the disparity entry returns for SV_BOX_ALL, SV_BOX_DMAP, bit
+ * for bit. */
+int sv_box_positions_points_device(const double *points, int batch, int width, int height, const int32_t *boxes, const int32_t *n_boxes, int max_boxes,
+                                   const sv_box_spec *spec, double *pos, int32_t *stat, void *stream);
 
 /* ---- (A) the reference's exported symbols ------------------------------------------------------------- */
 

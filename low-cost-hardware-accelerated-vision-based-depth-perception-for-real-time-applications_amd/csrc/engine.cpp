@@ -2429,6 +2429,9 @@ int sv_internal_copy2(sv_handle *h, void *dst_a, const void *src_a, void *dst_b,
     return SV_OK;
 }
 
+// Internal helper for the entry points without a handle (box_positions.cpp): the text sv_last_error(NULL) returns on this thread.
+void sv_internal_set_error(const char *msg) { g_create_error = msg ? msg : ""; }
+
 extern "C" {
 
 void sv_params_init(sv_params *p, int setting) {

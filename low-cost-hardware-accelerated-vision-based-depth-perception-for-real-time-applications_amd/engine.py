@@ -562,6 +562,126 @@ def top_view_from_disparity(disp, Q, x_range, y_range, z_range, scale, XR=None, 
     return out
 
 
+class SvBoxSpec(ctypes.Structure):
+    """sv_box_spec of include/stereo_vision_hip.h."""
+    _fields_ = [("select", ctypes.c_int32), ("disparity", ctypes.c_int32), ("band", ctypes.c_int32), ("reserved", ctypes.c_int32 * 5)]
+
+
+_box_bound = False
+
+
+def box_lib():
+    """The library with the sv_box_positions_* signatures declared."""
+    global _box_bound
+    L = lib()
+    if not _box_bound:
+        vp, ci, sp = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(SvBoxSpec)
+        L.sv_box_positions_disparity_device.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, sp, vp, vp, vp]
+        L.sv_box_positions_disparity_device.restype = ci
+        L.sv_box_positions_points_device.argtypes = [vp, ci, ci, ci, vp, vp, ci, sp, vp, vp, vp]
+        L.sv_box_positions_points_device.restype = ci
+        _box_bound = True
+    return L
+
+
+def box_spec(select="near", disparity="d1", band=4):
+    """-> SvBoxSpec; ValueError for a bad argument (the checks of the C entry, made in Python first)."""
+    from .stereo_vision.sv import BOX_DISPARITY, BOX_SELECT
+    if select not in BOX_SELECT:
+        raise ValueError("select must be one of %s, got %r" % (sorted(BOX_SELECT), select))
+    if disparity not in BOX_DISPARITY:
+        raise ValueError("disparity must be one of %s, got %r" % (sorted(BOX_DISPARITY), disparity))
+    if isinstance(band, bool) or int(band) != band or not 0 <= band < 2 ** 31:
+        raise ValueError("band must be an integer >= 0, got %r" % (band,))
+    return SvBoxSpec(BOX_SELECT[select], BOX_DISPARITY[disparity], int(band))
+
+
+def _box_buffers(boxes, n_boxes, B, device):
+    """-> (boxes int32 [B,M,4] on the device, n_boxes int32 [B] there or None, pos pre-filled with NaN, stat with -1)."""
+    import torch
+
+    def dev(x, what):
+        if isinstance(x, torch.Tensor):
+            if x.is_floating_point():
+                raise ValueError("%s must be integers" % what)
+            return x.to(device=device, dtype=torch.int32).contiguous()
+        a = np.asarray(x)
+        if a.dtype.kind not in "iu":
+            raise ValueError("%s must be integers" % what)
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(device)
+
+    bx = dev(boxes, "boxes")
+    if bx.dim() == 2 and B == 1:
+        bx = bx.unsqueeze(0)
+    if bx.dim() != 3 or bx.shape[0] != B or bx.shape[2] != 4:
+        raise ValueError("boxes must be int32 [B,M,4] with B = %d (one frame: [M,4]), got shape %s" % (B, tuple(bx.shape)))
+    M = bx.shape[1]
+    if B > 65535 or M > 65535:
+        raise ValueError("at most 65535 pairs and 65535 boxes per pair")
+    nb = None
+    if n_boxes is not None:
+        nb = dev(n_boxes, "n_boxes").reshape(-1)
+        if nb.numel() != B:
+            raise ValueError("n_boxes must have one entry per pair (%d), got %d" % (B, nb.numel()))
+    pos = torch.full((B, M, 3), float("nan"), dtype=torch.float64, device=device)
+    stat = torch.full((B, M, 4), -1, dtype=torch.int32, device=device)
+    return bx, nb, pos, stat
+
+
+def _box_check(rc, name):
+    if rc != 0:
+        msg = "%s failed (%d): %s" % (name, rc, (box_lib().sv_last_error(None) or b"").decode())
+        raise ValueError(msg) if rc == -1 else StereoError(msg)
+
+
+def box_positions(points, boxes, n_boxes=None):
+    """Mean point of a batch of clouds inside detector boxes, on the device: points is a CUDA float64 tensor [B,H,W,3] (e.g.
+    rig.point_clouds' or reproject's; one frame [H,W,3] accepted), boxes int32 [B,M,4] = (x, y, w, h) (CUDA tensor or numpy; [M,4] for
+    one frame), n_boxes [B] = boxes in use per pair or None = all M.  Returns (pos float64 [B,M,3], stat int32 [B,M,4] = (n_pixels, -1,
+    -1, n_pixels)) CUDA tensors equal to stereo_vision.sv.box_positions(points, boxes, n_boxes) - every pixel of the box, the
+    reference's mean (inf / NaN propagate) in the library's summation order; rows at and beyond n_boxes[b] are NaN / -1.  Enqueued on
+    torch's current stream (not waited for)."""
+    import torch
+    if not (isinstance(points, torch.Tensor) and points.is_cuda and points.dtype == torch.float64 and points.dim() in (3, 4) and points.shape[-1] == 3):
+        raise ValueError("points must be a CUDA float64 tensor [B,H,W,3]")
+    pts = (points.unsqueeze(0) if points.dim() == 3 else points).contiguous()
+    B, H, W = pts.shape[:3]
+    spec = box_spec("all", "dmap", 0)
+    bx, nb, pos, stat = _box_buffers(boxes, n_boxes, B, pts.device)
+    with torch.cuda.device(pts.device):
+        rc = box_lib().sv_box_positions_points_device(pts.data_ptr(), B, W, H, bx.data_ptr(), nb.data_ptr() if nb is not None else None, bx.shape[1],
+                                                      ctypes.byref(spec), pos.data_ptr(), stat.data_ptr(), torch.cuda.current_stream(pts.device).cuda_stream)
+    _box_check(rc, "sv_box_positions_points_device")
+    return pos, stat
+
+
+def box_positions_from_disparity(disp, Q, boxes, n_boxes=None, XR=None, XT=None, select="near", disparity="d1", band=4):
+    """Object positions straight from disparity maps (CUDA float32 [B,H,W]; one frame [H,W] accepted): each pixel's point is reproject()'s,
+    computed in registers, and no cloud is written.  disparity "dmap": the driver's saturate(round(4 d)) reprojected (a quarter of metric
+    depth), valid where it is > 0; "d1": d itself (metres), valid where d > 0.  select "all": every pixel of the box (with "dmap":
+    box_positions(reproject(disp, Q, XR, XT)[1], boxes), bit for bit); "valid": the valid pixels; "near": the valid pixels within `band`
+    quarter pixels of the box's lower-median quantised disparity.  Returns (pos float64 [B,M,3], stat int32 [B,M,4] = (n_pixels,
+    n_valid, q_med, n_selected)) equal to stereo_vision.sv.box_positions(disp, boxes, n_boxes, Q, ...); boxes, n_boxes, the rows beyond
+    n_boxes and the stream as for box_positions."""
+    import torch
+    spec = box_spec(select, disparity, band)
+    if not (isinstance(disp, torch.Tensor) and disp.is_cuda and disp.dtype == torch.float32 and disp.dim() in (2, 3)):
+        raise ValueError("disp must be a CUDA float32 tensor [B,H,W]")
+    disp = (disp.unsqueeze(0) if disp.dim() == 2 else disp).contiguous()
+    B, H, W = disp.shape
+    q = np.ascontiguousarray(Q, dtype=np.float64).reshape(16)
+    xr = None if XR is None else np.ascontiguousarray(XR, dtype=np.float64).reshape(9)
+    xt = None if XT is None else np.ascontiguousarray(XT, dtype=np.float64).reshape(3)
+    bx, nb, pos, stat = _box_buffers(boxes, n_boxes, B, disp.device)
+    with torch.cuda.device(disp.device):
+        rc = box_lib().sv_box_positions_disparity_device(disp.data_ptr(), B, W, H, q.ctypes.data, xr.ctypes.data if xr is not None else None,
+                                                         xt.ctypes.data if xt is not None else None, bx.data_ptr(),
+                                                         nb.data_ptr() if nb is not None else None, bx.shape[1], ctypes.byref(spec), pos.data_ptr(),
+                                                         stat.data_ptr(), torch.cuda.current_stream(disp.device).cuda_stream)
+    _box_check(rc, "sv_box_positions_disparity_device")
+    return pos, stat
+
+
 def host_support_filter(params, dcan, width, height, threads=0, lattice=False):
     """Product host stage: lattice filters + corner points (CPU by design; see csrc/host_stage.h).  threads > 0: the lattice shared between
     that many threads (what single-pair calls do); lattice=True: also return the filtered lattice."""

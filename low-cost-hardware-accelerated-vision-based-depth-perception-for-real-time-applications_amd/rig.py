@@ -7,6 +7,7 @@ disparity, the driver's 8-bit map and point clouds out.
     d1 = rig.disparity(left, right, pixel_format="bgr")              # f32 [B,H,W]
     d1, dmap, points = rig.point_clouds(left, right, pixel_format="bgr")
     grid = rig.top_view(left, right, (0, 40), (-20, 20), (-1.4, 1.0), 10, disparity="d1", transform=(CAMERA_TO_VEHICLE, None))
+    pos, stat = rig.box_positions(left, right, boxes, n_boxes)       # f64 [B,M,3] metres, int32 [B,M,4]
 
 Frames are [B,Hs,Ws,C] (C = 4, 3, 3 for "bgra", "bgr", "rgb") or [B,Hs,Ws] for "gray"; one frame without B is accepted.
 Frames of another size than the rig's are resized to it.  CUDA tensors are processed on torch's current stream and CUDA
@@ -17,7 +18,8 @@ import ctypes
 
 import numpy as np
 
-from .engine import SvParams, StereoEngine, StereoError, lib, pinned_array, reproject, top_view_from_disparity, top_view_spec
+from .engine import (SvParams, StereoEngine, StereoError, box_positions_from_disparity, box_spec, lib, pinned_array, reproject, top_view_from_disparity,
+                     top_view_spec)
 from .stereo_vision.sv import CAMERA_TO_VEHICLE, DEFAULT_CALIBRATION  # noqa: F401 (CAMERA_TO_VEHICLE: re-exported for top_view)
 
 PIXEL_FORMATS = {"bgra": 0, "bgr": 1, "rgb": 2, "gray": 3}
@@ -171,6 +173,18 @@ class StereoRig:
                                                          gr.data_ptr(), col.data_ptr() if col is not None else None, st))
         return gl, gr, col, from_numpy
 
+    def _transform(self, transform):
+        """-> (XR, XT) of a transform argument: None, "rig" (the calibration file's; ValueError if it has none) or (XR, XT)."""
+        if transform is None:
+            return None, None
+        if isinstance(transform, str) and transform == "rig":
+            if self.XR is None and self.XT is None:
+                raise ValueError("transform=\"rig\": the calibration file has no XR / XT")
+            return self.XR, self.XT
+        if isinstance(transform, (tuple, list)) and len(transform) == 2:
+            return transform[0], transform[1]
+        raise ValueError("transform must be None, \"rig\" or (XR, XT)")
+
     # ---- public
     def frontend(self, left, right, pixel_format="bgr", colors=False):
         """-> (gray_left, gray_right) u8 [B,H,W] (+ the left colours BGRA [B,H,W,4] with colors=True), enqueued on torch's current stream."""
@@ -209,17 +223,25 @@ class StereoRig:
         if self.params.subsampling:
             raise ValueError("top_view does not support half-resolution maps (params.subsampling)")
         top_view_spec(x_range, y_range, z_range, scale, mode, disparity)  # argument errors before any work
-        if transform is None:
-            XR = XT = None
-        elif isinstance(transform, str) and transform == "rig":
-            if self.XR is None and self.XT is None:
-                raise ValueError("transform=\"rig\": the calibration file has no XR / XT")
-            XR, XT = self.XR, self.XT
-        elif isinstance(transform, (tuple, list)) and len(transform) == 2:
-            XR, XT = transform
-        else:
-            raise ValueError("transform must be None, \"rig\" or (XR, XT)")
+        XR, XT = self._transform(transform)
         gl, gr, _, from_numpy = self._run_frontend(left, right, pixel_format, False)
         d1, _ = self.engine.process_device(gl, gr, want_d2=False)
         grid = top_view_from_disparity(d1, self.Q, x_range, y_range, z_range, scale, XR=XR, XT=XT, disparity=disparity, mode=mode)
         return grid.cpu().numpy() if from_numpy else grid
+
+    def box_positions(self, left, right, boxes, n_boxes=None, pixel_format="bgr", select="near", disparity="d1", band=4, transform=None):
+        """3-D position of each detected object of B pairs: (pos float64 [B,M,3], stat int32 [B,M,4] = (n_pixels, n_valid, q_med,
+        n_selected)) for boxes int32 [B,M,4] = (x, y, w, h) in pixels of the rig's maps ([M,4] for one frame; n_boxes [B] = boxes in
+        use per pair, rows beyond come back NaN / -1) - front end, engine, then the fused disparity -> positions kernel: no point
+        cloud is written.  The defaults give metres from the float disparity ("d1"), over the valid pixels within `band` quarter
+        pixels of the box's median disparity ("near": background inside the box is left out); select "valid" / "all" and disparity
+        "dmap" (the driver's cloud, a quarter of metric depth; with "all" the reference's mean) as engine.box_positions_from_disparity.
+        transform as in top_view: None (camera axes), "rig" or (XR, XT).  The boxes come from your own detector."""
+        if self.params.subsampling:
+            raise ValueError("box_positions does not support half-resolution maps (params.subsampling)")
+        box_spec(select, disparity, band)  # argument errors before any work
+        XR, XT = self._transform(transform)
+        gl, gr, _, from_numpy = self._run_frontend(left, right, pixel_format, False)
+        d1, _ = self.engine.process_device(gl, gr, want_d2=False)
+        pos, stat = box_positions_from_disparity(d1, self.Q, boxes, n_boxes, XR=XR, XT=XT, select=select, disparity=disparity, band=band)
+        return (pos.cpu().numpy(), stat.cpu().numpy()) if from_numpy else (pos, stat)

@@ -19,6 +19,11 @@ normalize_depth, in_range_points and points_2_top_view (plus mode="count").  The
 engine.top_view_from_disparity / rig.StereoRig.top_view and the tests' oracle.  Deviations: a value whose
 quotient is negative (dist > max_dist) is 0; non-integer x / y ranges, lo >= hi, a scale that is not a positive integer and
 max_dist == 0 in "reference" mode raise ValueError.
+
+box_positions is the numpy restatement of the batched object positions (sv_box_positions_* of include/stereo_vision_hip.h (E);
+engine.box_positions / engine.box_positions_from_disparity / rig.StereoRig.box_positions on the GPU): the mean point inside each
+detector box in the library's summation order, usable without a GPU and the tests' oracle.  stereo_vision.object_positions stays
+the reference's one-frame form.
 """
 import argparse
 import ctypes
@@ -110,6 +115,135 @@ def points_2_top_view(points, x_range, y_range, z_range, scale, mode="reference"
     cells, first = np.unique(flat[::-1], return_index=True)
     img[cells] = value[::-1][first]
     return img.reshape(rows, cols)
+
+
+BOX_SELECT = {"all": 0, "valid": 1, "near": 2}
+BOX_DISPARITY = {"dmap": 0, "d1": 1}
+BOX_BINS = 4096
+
+
+def box_bounds(box, width, height):
+    """(i_lb, i_ub, j_lb, j_ub) of a box (x, y, w, h): columns [clamp(x), clamp(x + w)), rows [clamp(y), clamp(y + h)) with
+    clamp(a) = min(max(a, 0), size - 1) - the reference's clamp (stereo_vision.cpp:263-264): the last column and row never belong
+    to a box.  Python integers: x + w cannot overflow."""
+    x, y, w, h = (int(v) for v in box)
+    cl = lambda a, size: min(max(a, 0), size - 1)  # noqa: E731
+    return cl(x, width), cl(x + w, width), cl(y, height), cl(y + h, height)
+
+
+def box_quantise(disp, disparity="dmap"):
+    """(q int32, valid bool, d float64) per pixel of a float32 map: "dmap": q = saturate_u8(round_half_even(4 d)) (NaN gives 0),
+    valid = q > 0, d = q; "d1": q = min(round_half_even(4 d), 4095) where valid = d > 0 (0 elsewhere), d = the float itself."""
+    if disparity not in BOX_DISPARITY:
+        raise ValueError("disparity must be one of %s, got %r" % (sorted(BOX_DISPARITY), disparity))
+    d = np.asarray(disp, dtype=np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        r = np.rint(d * np.float32(4.0))
+        if disparity == "dmap":
+            q = np.clip(np.where(np.isnan(r), np.float32(0), r), 0, 255).astype(np.int32)
+            return q, q > 0, q.astype(np.float64)
+        valid = d > 0
+        q = np.where(valid, np.minimum(r, np.float32(BOX_BINS - 1)), np.float32(0)).astype(np.int32)
+        return q, valid, d.astype(np.float64)
+
+
+def _box_points(d, Q, XR, XT):
+    """reproject()'s arithmetic on a [H,W] float64 disparity: [H,W,3] points (products and sums rounded one by one, as written)."""
+    H, W = d.shape
+    Q = np.asarray(Q, np.float64).reshape(4, 4)
+    jj, ii = np.mgrid[0:H, 0:W]
+    x, y = ii.astype(np.float64), jj.astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        pos = [((Q[r, 0] * x + Q[r, 1] * y) + Q[r, 2] * d) + Q[r, 3] for r in range(4)]
+        X, Y, Z = pos[0] / pos[3], pos[1] / pos[3], pos[2] / pos[3]
+        if XR is not None or XT is not None:
+            XR = np.eye(3) if XR is None else np.asarray(XR, np.float64).reshape(3, 3)
+            XT = np.zeros(3) if XT is None else np.asarray(XT, np.float64).reshape(3)
+            X, Y, Z = [((XR[r, 0] * X + XR[r, 1] * Y) + XR[r, 2] * Z) + XT[r] for r in range(3)]
+    return np.stack([X, Y, Z], -1)
+
+
+def _box_sum(P, sel):
+    """The library's order on the box's points P [rows, cols, 3] (sel [rows, cols] bool or None = all): per column the selected
+    points in ascending row order onto +0.0 - an explicit loop over the rows, the columns side by side -, then the column sums
+    left to right onto +0.0 - an explicit loop over the columns."""
+    rows, cols = P.shape[:2]
+    col = np.zeros((cols, 3), np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for j in range(rows):
+            col = col + P[j] if sel is None else np.where(sel[j][:, None], col + P[j], col)
+        acc = np.zeros(3, np.float64)
+        for i in range(cols):
+            acc = acc + col[i]
+    return acc
+
+
+def box_positions(points_or_disp, boxes, n_boxes=None, Q=None, XR=None, XT=None, select="all", disparity="dmap", band=4):
+    """3-D position per detector box, the definition of include/stereo_vision_hip.h (E) in numpy.
+
+    Q None: points_or_disp is an f64 cloud [H,W,3] (or [B,H,W,3]); only select="all".  Q given: a float32 disparity map [H,W] (or
+    [B,H,W]), reprojected with Q (and XR / XT) as engine.reproject does - disparity "dmap": the driver's saturate(round(4 d)),
+    "d1": the float itself, in metres.  boxes: int [M,4] (or [B,M,4]) = (x, y, w, h); n_boxes: boxes in use per frame (None = all).
+    select "all" (the reference's mean: inf / NaN propagate), "valid" (valid pixels) or "near" (valid pixels within `band` quarter
+    pixels of the box's lower-median quantised disparity).
+    Returns (pos float64 [M,3], stat int32 [M,4] = (n_pixels, n_valid, q_med, n_selected)), with a leading B for batched input;
+    rows at and beyond n_boxes are NaN / -1.  pos = sum / n_selected in the order of _box_sum (0 selected: NaN)."""
+    if select not in BOX_SELECT:
+        raise ValueError("select must be one of %s, got %r" % (sorted(BOX_SELECT), select))
+    if disparity not in BOX_DISPARITY:
+        raise ValueError("disparity must be one of %s, got %r" % (sorted(BOX_DISPARITY), disparity))
+    if isinstance(band, bool) or int(band) != band or band < 0:
+        raise ValueError("band must be an integer >= 0, got %r" % (band,))
+    src = np.asarray(points_or_disp)
+    from_points = Q is None
+    if from_points and select != "all":
+        raise ValueError("a point cloud has no disparity: only select=\"all\" applies")
+    frame_dim = 3 if from_points else 2
+    if src.ndim not in (frame_dim, frame_dim + 1) or (from_points and src.shape[-1] != 3):
+        raise ValueError("expected %s, got shape %s" % ("points [B,H,W,3]" if from_points else "disp [B,H,W]", src.shape))
+    batched = src.ndim == frame_dim + 1
+    if not batched:
+        src = src[None]
+    bx = np.asarray(boxes)
+    if bx.ndim == 2:
+        bx = np.broadcast_to(bx[None], (src.shape[0],) + bx.shape)
+    if bx.ndim != 3 or bx.shape[0] != src.shape[0] or bx.shape[2] != 4:
+        raise ValueError("boxes must be [B,M,4] (or [M,4]), got shape %s" % (bx.shape,))
+    B, M = bx.shape[:2]
+    H, W = src.shape[1:3]
+    nb = np.full(B, M) if n_boxes is None else np.clip(np.asarray(n_boxes).reshape(B), 0, M)
+    pos = np.full((B, M, 3), np.nan)
+    stat = np.full((B, M, 4), -1, np.int32)
+    for b in range(B):
+        if from_points:
+            P = np.asarray(src[b], np.float64)
+            q = valid = None
+        else:
+            q, valid, d = box_quantise(src[b], disparity)
+            P = _box_points(d, Q, XR, XT)
+        for m in range(int(nb[b])):
+            i_lb, i_ub, j_lb, j_ub = box_bounds(bx[b, m], W, H)
+            ncols, nrows = max(i_ub - i_lb, 0), max(j_ub - j_lb, 0)
+            n_pixels = ncols * nrows
+            win = (slice(j_lb, j_lb + nrows), slice(i_lb, i_lb + ncols)) if n_pixels else (slice(0, 0), slice(0, 0))
+            n_valid = q_med = -1
+            n_sel, sel = n_pixels, None
+            if not from_points:
+                qb, vb = q[win], valid[win]
+                hist = np.bincount(qb[vb], minlength=BOX_BINS)
+                n_valid = int(hist.sum())
+                if n_valid:
+                    q_med = int(np.searchsorted(np.cumsum(hist), (n_valid + 1) // 2))  # the first bin whose cumulative count reaches it
+                if select == "valid":
+                    sel, n_sel = vb, n_valid
+                elif select == "near":
+                    sel = vb & (np.abs(qb - q_med) <= int(band))
+                    n_sel = int(sel.sum())
+            total = _box_sum(P[win], sel)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                pos[b, m] = total / np.float64(n_sel)
+            stat[b, m] = (n_pixels, n_valid, q_med, n_sel)
+    return (pos, stat) if batched else (pos[0], stat[0])
 
 
 class stereo_vision:
