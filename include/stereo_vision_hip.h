@@ -26,6 +26,10 @@
  *      detector's boxes, for batches, from disparity maps (fused: no cloud is written) or from point clouds (publishPointCloud's
  *      per-object step, src/serial_includes/main/stereo_vision.cpp:261-278).
  *
+ *  (F) Behind (B) as well: compact coloured point clouds (sv_cloud_*) - per pair the list of valid, cropped, thinned-out 3-D
+ *      points with their colours and pixel indices, in pixel order, from disparity maps (fused: no dense cloud is written).  It is
+ *      what the reference's viewer draws: Grapher pairs points[i] with colors[i] (src/common_includes/graphing.h:123-133).
+ *
  * All sv_* functions return SV_OK (0) or a negative sv_status; sv_last_error() gives the text.
  * Nothing in this library calls exit().
  */
@@ -430,6 +434,66 @@ int sv_box_positions_disparity_device(const float *disp, int batch, int width, i
  * for bit. */
 int sv_box_positions_points_device(const double *points, int batch, int width, int height, const int32_t *boxes, const int32_t *n_boxes, int max_boxes,
                                    const sv_box_spec *spec, double *pos, int32_t *stat, void *stream);
+
+/* ---- (F) compact coloured point clouds: disparity maps (+ colour images) -> lists of points per pair ----------------- */
+
+/* The points a viewer, a PLY file or a voxel grid takes: for B pairs, the 3-D points of the pixels that carry a disparity and lie
+ * inside a crop box, optionally thinned out to every step-th column and row, each with its colour and its pixel index.
+ *
+ * Frame b visits the pixels (x, y) with x % step == 0 && y % step == 0 in ascending flat index y * width + x.  All arithmetic is
+ * sv_reproject_batch_device's (double, no FMA):
+ *   SV_CLOUD_DMAP  q = saturate_u8(round_half_even(4 d)) (NaN gives 0); candidate iff q > 0; P = reproject(x, y, (double)q): the
+ *                  driver's cloud, at a quarter of metric depth (as in (D) and (E)).
+ *   SV_CLOUD_D1    candidate iff d > 0 (NaN is none; the engine's invalid pixels are -10); P = reproject(x, y, (double)d), metres.
+ *   XR9 / XT3      P = XR P + XT, as everywhere else.
+ *   crop           after the transform: a candidate is kept iff lo[k] < P[k] < hi[k] for k = 0, 1, 2, strictly.  lo = -inf /
+ *                  hi = +inf leave an axis open.  +-inf and NaN coordinates never pass, even with every axis open - so "d > 0" alone
+ *                  is not the predicate: a Q that makes pos.w = 0 for some positive disparity yields no point there.
+ * A kept point is written as
+ *   xyz    SV_CLOUD_F32: (float)P, IEEE round to nearest even (a coordinate beyond the float range becomes +-inf although it passed
+ *          the crop in double); SV_CLOUD_F64: P itself
+ *   color  the four bytes of pixel (x, y) of `colors` (e.g. sv_rig_frontend_device's BGRA output); optional
+ *   index  int32 y * width + x; optional
+ * counts[b] is the number of kept points of frame b, NOT capped by the capacity.  The frame's first min(counts[b], capacity) kept
+ * points, in pixel order, land in rows 0.. of the frame's slot; the rows beyond are left untouched.  The result of a frame is
+ * bitwise reproducible and independent of the batch it sits in, of the launch and of the other frames.
+ * stereo_vision.sv.compact_cloud restates all of it in numpy. */
+enum { SV_CLOUD_DMAP = 0, SV_CLOUD_D1 = 1 };
+enum { SV_CLOUD_F32 = 0, SV_CLOUD_F64 = 1 };
+
+typedef struct sv_cloud_spec {
+    double lo[3], hi[3];  /* lo < hi per axis (NaN refused); infinite = open */
+    int32_t disparity;    /* SV_CLOUD_DMAP / SV_CLOUD_D1 */
+    int32_t step;         /* >= 1: every step-th column and row */
+    int32_t dtype;        /* SV_CLOUD_F32 / SV_CLOUD_F64 */
+    int32_t reserved[5];  /* must be 0 */
+} sv_cloud_spec;
+
+/* Visited pixels per tile, the unit the kernels count and write by (a test hook: shapes around it are the edges of the tiling). */
+int sv_cloud_tile(void);
+/* Bytes of device workspace a call needs (4 per tile and pair; 0 for batch == 0).  Host only; SIZE_MAX for a bad spec, batch, width or
+ * height (the checks of the call below). */
+size_t sv_cloud_workspace_bytes(const sv_cloud_spec *spec, int batch, int width, int height);
+/* Enqueued on `stream` (a hipStream_t, NULL = the default stream) as at most three kernels - count per tile, scan per frame, write -
+ * and not waited for; nothing is allocated, no host synchronisation is made.
+ *   disp         : float [batch][height][width] device; width * height < 2^31
+ *   colors       : uint8 [batch][height][width][4] device, 4-byte aligned, or NULL
+ *   Q16, XR9, XT3: HOST, as for sv_reproject_batch_device (XR9 and XT3 both NULL = no transform)
+ *   capacity     : rows per pair of the three outputs, >= 0; 0: only the counts are produced (two kernels; xyz may be NULL)
+ *   xyz          : float or double [batch][capacity][3] device
+ *   color_out    : uint8 [batch][capacity][4] device, 4-byte aligned, or NULL; needs colors
+ *   index_out    : int32 [batch][capacity] device, or NULL
+ *   counts       : int32 [batch] device
+ *   workspace    : device, 4-byte aligned, workspace_bytes >= sv_cloud_workspace_bytes(spec, batch, width, height); its contents
+ *                  before and after the call mean nothing
+ * Returns SV_OK (nothing enqueued for batch == 0), SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued, the outputs untouched, the text in
+ * sv_last_error(NULL) - for: a NULL spec, disp, Q16 or counts; a NULL xyz with capacity > 0; color_out without colors; colors or
+ * color_out not 4-byte aligned; disparity or dtype out of range; step < 1; lo >= hi or a NaN bound; a non-zero reserved word;
+ * a workspace that is NULL, misaligned or too small; capacity < 0; batch < 0 or > 65535; width < 1 or height < 1;
+ * width * height >= 2^31.  These checks run before any HIP call. */
+int sv_cloud_disparity_device(const float *disp, const uint8_t *colors, int batch, int width, int height, const double *Q16, const double *XR9,
+                              const double *XT3, const sv_cloud_spec *spec, int capacity, void *xyz, uint8_t *color_out, int32_t *index_out, int32_t *counts,
+                              void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- (A) the reference's exported symbols ------------------------------------------------------------- */
 

@@ -1,0 +1,212 @@
+// Compact coloured point clouds from disparity maps: an ordered stream compaction over a batch, fused with the reprojection (no dense
+// cloud is written).  Specified in include/stereo_vision_hip.h (F), restated in stereo_vision/sv.py: compact_cloud.
+//
+//   visited   the pixels (x, y) with x % step == 0 && y % step == 0, numbered v = (y / step) * Wv + x / step, Wv = ceil(W / step):
+//             ascending v is ascending flat index y * W + x
+//   kept      candidate (DMAP: q > 0, D1: d > 0) and lo < P < hi on every axis, P from reproject.h's arithmetic; the strict comparison
+//             drops inf and NaN, so a positive disparity with pos.w = 0 is not kept
+//   tile      CLOUD_TILE = 1024 consecutive visited pixels, owned by ONE wavefront in both passes: four sweeps of 256, a lane taking
+//             four consecutive pixels (with step 1 one 16-byte load where the frame's address allows it)
+//   pass 1    k_cloud_count: tiles[b][t] = kept pixels of tile t
+//   pass 2    k_cloud_scan: one workgroup per frame turns tiles[b][.] into its exclusive prefix sum and writes counts[b]
+//   pass 3    k_cloud_write: the predicate again (the point is needed anyway), rank inside the sweep from four 64-bit ballots and
+//             mbcnt - lanes in order, a lane's four pixels in order -, row = tiles[b][t] + kept so far in the tile + rank; rows below
+//             capacity are stored
+//
+// The order between tiles comes from the launch boundaries alone: no workgroup waits for another one, and because a tile belongs to
+// one wavefront the two big kernels need neither LDS nor a barrier.  Every load is guarded by v < n_visited, every store by
+// row < capacity; a tile index is < n_tiles.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "cloud_kernels.h"
+
+namespace sv {
+
+namespace {
+
+// The lane's four visited pixels v0 .. v0 + 3 (those < n_visited): bit k of the result = pixel k is kept; pix[k] = its flat index,
+// P[k] = its point (read only where the bit is set).
+template <int SRC>
+__device__ __forceinline__ unsigned cloud_quad(const CloudArgs &a, const float *frame, bool vec_ok, uint32_t v0, int *pix, double (*P)[3]) {
+    const uint32_t n = (uint32_t)a.n_visited;
+    if (v0 >= n) return 0u;
+    const uint32_t vy = v0 / (uint32_t)a.Wv;
+    int vx = (int)(v0 - vy * (uint32_t)a.Wv), x[CLOUD_QUAD], y[CLOUD_QUAD];
+    int cx = vx * a.step, cy = (int)vy * a.step;  // <= W - 1, H - 1
+    const int have = n - v0 < (uint32_t)CLOUD_QUAD ? (int)(n - v0) : CLOUD_QUAD;
+#pragma unroll
+    for (int k = 0; k < CLOUD_QUAD; k++) {
+        x[k] = cx, y[k] = cy;
+        pix[k] = k < have ? cy * a.W + cx : 0;  // < W * H
+        if (k + 1 < have) {                      // the next pixel exists: cx <= W - 1, cy <= H - 1 whatever the step
+            if (++vx == a.Wv) vx = 0, cx = 0, cy += a.step;
+            else cx += a.step;
+        }
+    }
+    float dv[CLOUD_QUAD];
+    if (vec_ok && have == CLOUD_QUAD) {  // step 1: pix[k] = v0 + k, v0 % 4 == 0
+        const float4 f = *reinterpret_cast<const float4 *>(frame + v0);
+        dv[0] = f.x, dv[1] = f.y, dv[2] = f.z, dv[3] = f.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < CLOUD_QUAD; k++) dv[k] = k < have ? frame[pix[k]] : 0.f;  // 0 is no candidate
+    }
+    unsigned keep = 0u;
+#pragma unroll
+    for (int k = 0; k < CLOUD_QUAD; k++) {
+        double d;
+        bool cand;
+        if (SRC == CLOUD_SRC_DMAP) {
+            const int q = sv_dmap_u8(dv[k]);
+            cand = q > 0, d = (double)q;
+        } else {
+            cand = dv[k] > 0.f, d = (double)dv[k];  // NaN is no candidate
+        }
+        if (cand) {
+            double X, Y, Z;
+            sv_reproject_point(a.rp, (double)x[k], (double)y[k], d, X, Y, Z);
+            if (a.lo[0] < X && X < a.hi[0] && a.lo[1] < Y && Y < a.hi[1] && a.lo[2] < Z && Z < a.hi[2]) {
+                keep |= 1u << k;
+                P[k][0] = X, P[k][1] = Y, P[k][2] = Z;
+            }
+        }
+    }
+    return keep;
+}
+
+__device__ __forceinline__ int lanes_below(unsigned long long mask) {
+    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+}
+
+__device__ __forceinline__ bool frame_vec_ok(const CloudArgs &a, const float *frame) {
+    return a.step == 1 && (reinterpret_cast<uintptr_t>(frame) & 15) == 0;
+}
+
+template <int SRC>
+__global__ __launch_bounds__(64 * CLOUD_WAVES) void k_cloud_count(CloudArgs a) {
+    const int lane = threadIdx.x & 63, b = blockIdx.y;
+    const int tile = blockIdx.x * CLOUD_WAVES + (threadIdx.x >> 6);
+    if (tile >= a.n_tiles) return;  // the whole wavefront
+    const float *frame = a.disp + (size_t)b * a.W * a.H;
+    const bool vec_ok = frame_vec_ok(a, frame);
+    int total = 0;
+    for (int s = 0; s < CLOUD_TILE / (64 * CLOUD_QUAD); s++) {
+        const uint32_t v0 = (uint32_t)tile * CLOUD_TILE + (uint32_t)(s * 64 + lane) * CLOUD_QUAD;
+        int pix[CLOUD_QUAD];
+        double P[CLOUD_QUAD][3];
+        const unsigned keep = cloud_quad<SRC>(a, frame, vec_ok, v0, pix, P);
+#pragma unroll
+        for (int k = 0; k < CLOUD_QUAD; k++) total += __popcll(__ballot((keep >> k) & 1u));
+    }
+    if (lane == 0) a.tiles[(size_t)b * a.n_tiles + tile] = total;
+}
+
+// Exclusive prefix sum of a frame's tile counts in place: a thread owns a run of consecutive tiles.
+__global__ __launch_bounds__(256) void k_cloud_scan(CloudArgs a) {
+    __shared__ int s_wave[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
+    int32_t *t = a.tiles + (size_t)b * a.n_tiles;
+    const int per = (a.n_tiles + 255) / 256;  // <= 2^13
+    const int lo = tid * per < a.n_tiles ? tid * per : a.n_tiles, hi = lo + per < a.n_tiles ? lo + per : a.n_tiles;
+    int own = 0;
+    for (int k = lo; k < hi; k++) own += t[k];
+    int incl = own;
+    for (int s = 1; s < 64; s <<= 1) {
+        const int up = __shfl_up(incl, s);
+        if (lane >= s) incl += up;
+    }
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    int run = incl - own;
+    for (int k = 0; k < wave; k++) run += s_wave[k];
+    for (int k = lo; k < hi; k++) {
+        const int c = t[k];
+        t[k] = run;
+        run += c;
+    }
+    if (tid == 255) a.counts[b] = run;  // the last thread's run ends at the total (<= n_visited < 2^31)
+}
+
+template <int SRC, int DT>
+__global__ __launch_bounds__(64 * CLOUD_WAVES) void k_cloud_write(CloudArgs a) {
+    const int lane = threadIdx.x & 63, b = blockIdx.y;
+    const int tile = blockIdx.x * CLOUD_WAVES + (threadIdx.x >> 6);
+    if (tile >= a.n_tiles) return;  // the whole wavefront
+    int row = a.tiles[(size_t)b * a.n_tiles + tile];
+    const float *frame = a.disp + (size_t)b * a.W * a.H;
+    const bool vec_ok = frame_vec_ok(a, frame);
+    const size_t slot = (size_t)b * a.capacity;
+    for (int s = 0; s < CLOUD_TILE / (64 * CLOUD_QUAD) && row < a.capacity; s++) {  // rows only grow: nothing later is stored either
+        const uint32_t v0 = (uint32_t)tile * CLOUD_TILE + (uint32_t)(s * 64 + lane) * CLOUD_QUAD;
+        int pix[CLOUD_QUAD];
+        double P[CLOUD_QUAD][3];
+        const unsigned keep = cloud_quad<SRC>(a, frame, vec_ok, v0, pix, P);
+        int before = 0, total = 0;
+#pragma unroll
+        for (int k = 0; k < CLOUD_QUAD; k++) {
+            const unsigned long long m = __ballot((keep >> k) & 1u);
+            before += lanes_below(m);
+            total += __popcll(m);
+        }
+        int r = row + before;
+#pragma unroll
+        for (int k = 0; k < CLOUD_QUAD; k++) {
+            if ((keep >> k) & 1u) {
+                if (r < a.capacity) {
+                    const size_t o = slot + (size_t)r;
+                    if (DT == CLOUD_F32) {
+                        float *p = static_cast<float *>(a.xyz) + 3 * o;
+                        p[0] = (float)P[k][0], p[1] = (float)P[k][1], p[2] = (float)P[k][2];
+                    } else {
+                        double *p = static_cast<double *>(a.xyz) + 3 * o;
+                        p[0] = P[k][0], p[1] = P[k][1], p[2] = P[k][2];
+                    }
+                    if (a.color_out)
+                        reinterpret_cast<uint32_t *>(a.color_out)[o] = reinterpret_cast<const uint32_t *>(a.colors)[(size_t)b * a.W * a.H + pix[k]];
+                    if (a.index_out) a.index_out[o] = pix[k];
+                }
+                r++;
+            }
+        }
+        row += total;
+    }
+}
+
+dim3 tile_grid(const CloudArgs &a, int batch) { return dim3((a.n_tiles + CLOUD_WAVES - 1) / CLOUD_WAVES, batch); }
+
+template <int SRC>
+hipError_t launch_write_dt(int dtype, const CloudArgs &a, int batch, hipStream_t st) {
+    if (dtype == CLOUD_F32)
+        hipLaunchKernelGGL((k_cloud_write<SRC, CLOUD_F32>), tile_grid(a, batch), dim3(64 * CLOUD_WAVES), 0, st, a);
+    else if (dtype == CLOUD_F64)
+        hipLaunchKernelGGL((k_cloud_write<SRC, CLOUD_F64>), tile_grid(a, batch), dim3(64 * CLOUD_WAVES), 0, st, a);
+    else
+        return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_cloud_count(int src, const CloudArgs &a, int batch, hipStream_t st) {
+    if (src == CLOUD_SRC_DMAP)
+        hipLaunchKernelGGL((k_cloud_count<CLOUD_SRC_DMAP>), tile_grid(a, batch), dim3(64 * CLOUD_WAVES), 0, st, a);
+    else if (src == CLOUD_SRC_D1)
+        hipLaunchKernelGGL((k_cloud_count<CLOUD_SRC_D1>), tile_grid(a, batch), dim3(64 * CLOUD_WAVES), 0, st, a);
+    else
+        return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t launch_cloud_scan(const CloudArgs &a, int batch, hipStream_t st) {
+    hipLaunchKernelGGL(k_cloud_scan, dim3(batch), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_cloud_write(int src, int dtype, const CloudArgs &a, int batch, hipStream_t st) {
+    if (src == CLOUD_SRC_DMAP) return launch_write_dt<CLOUD_SRC_DMAP>(dtype, a, batch, st);
+    if (src == CLOUD_SRC_D1) return launch_write_dt<CLOUD_SRC_D1>(dtype, a, batch, st);
+    return hipErrorInvalidValue;
+}
+
+}  // namespace sv

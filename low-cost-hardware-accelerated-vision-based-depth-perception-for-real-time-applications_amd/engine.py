@@ -682,6 +682,119 @@ def box_positions_from_disparity(disp, Q, boxes, n_boxes=None, XR=None, XT=None,
     return pos, stat
 
 
+class SvCloudSpec(ctypes.Structure):
+    """sv_cloud_spec of include/stereo_vision_hip.h."""
+    _fields_ = [("lo", ctypes.c_double * 3), ("hi", ctypes.c_double * 3), ("disparity", ctypes.c_int32), ("step", ctypes.c_int32),
+                ("dtype", ctypes.c_int32), ("reserved", ctypes.c_int32 * 5)]
+
+
+_cloud_bound = False
+
+
+def cloud_lib():
+    """The library with the sv_cloud_* signatures declared."""
+    global _cloud_bound
+    L = lib()
+    if not _cloud_bound:
+        vp, ci, sp = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(SvCloudSpec)
+        L.sv_cloud_tile.argtypes = []
+        L.sv_cloud_tile.restype = ci
+        L.sv_cloud_workspace_bytes.argtypes = [sp, ci, ci, ci]
+        L.sv_cloud_workspace_bytes.restype = ctypes.c_size_t
+        L.sv_cloud_disparity_device.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp, sp, ci, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
+        L.sv_cloud_disparity_device.restype = ci
+        _cloud_bound = True
+    return L
+
+
+def cloud_tile():
+    """Visited pixels per tile of the compact-cloud kernels (sv_cloud_tile): the unit they count and write by."""
+    return int(cloud_lib().sv_cloud_tile())
+
+
+def cloud_spec(lo=None, hi=None, step=1, disparity="d1", dtype="f32"):
+    """-> SvCloudSpec; ValueError for a bad argument (the checks of the C entry, made in Python first)."""
+    from .stereo_vision.sv import CLOUD_DISPARITY, CLOUD_DTYPES, cloud_crop
+    lo, hi = cloud_crop(lo, hi, step, disparity, dtype)
+    spec = SvCloudSpec()
+    spec.lo[:] = lo.tolist()
+    spec.hi[:] = hi.tolist()
+    spec.disparity, spec.step, spec.dtype = CLOUD_DISPARITY[disparity], int(step), CLOUD_DTYPES[dtype]
+    return spec
+
+
+def compact_cloud_from_disparity(d1, Q, colors=None, XR=None, XT=None, lo=None, hi=None, step=1, disparity="d1", dtype="f32", capacity=None,
+                                 want_index=False):
+    """Compact coloured point clouds straight from disparity maps (CUDA float32 [B,H,W]; one frame [H,W] accepted): per frame the points
+    of the visited pixels (every step-th column and row) that carry a disparity and lie strictly inside the crop lo < P < hi (None =
+    open; inf / NaN never pass), in pixel order, each point reproject()'s, computed in registers - no dense cloud is written.  disparity
+    "dmap": the driver's saturate(round(4 d)) reprojected (a quarter of metric depth), candidates where it is > 0; "d1": d itself
+    (metres), candidates where d > 0.  colors: CUDA uint8 [B,H,W,4] (e.g. rig.frontend(..., colors=True)'s) or None; the C entry wants
+    them 4-byte aligned (SV_ERR_ARG otherwise), so a view that starts at an odd storage offset is copied first.
+    Returns (xyz [B,capacity,3] float32 or float64 ("f64"), color uint8 [B,capacity,4] or None, index int32 [B,capacity] = y * W + x or
+    None (want_index), counts int32 [B]): frame b's first min(counts[b], capacity) rows equal stereo_vision.sv.compact_cloud's; counts is
+    not capped by the capacity; rows at and beyond counts[b] are undefined.  capacity None = the number of visited pixels, which cannot
+    overflow.  CUDA tensors on the input's device, enqueued on torch's current stream (not waited for); split_clouds cuts them."""
+    import torch
+    spec = cloud_spec(lo, hi, step, disparity, dtype)
+    if not (isinstance(d1, torch.Tensor) and d1.is_cuda and d1.dtype == torch.float32 and d1.dim() in (2, 3)):
+        raise ValueError("d1 must be a CUDA float32 tensor [B,H,W]")
+    d1 = (d1.unsqueeze(0) if d1.dim() == 2 else d1).contiguous()
+    B, H, W = d1.shape
+    if B > 65535 or H < 1 or W < 1 or H * W >= 2 ** 31:
+        raise ValueError("at most 65535 pairs of 1 <= width * height < 2^31 pixels, got %s" % (tuple(d1.shape),))
+    if colors is not None:
+        if not (isinstance(colors, torch.Tensor) and colors.is_cuda and colors.dtype == torch.uint8 and colors.device == d1.device):
+            raise ValueError("colors must be a CUDA uint8 tensor [B,H,W,4] on d1's device")
+        colors = (colors.unsqueeze(0) if colors.dim() == 3 else colors).contiguous()
+        if tuple(colors.shape) != (B, H, W, 4):
+            raise ValueError("colors must be [B,H,W,4] matching d1 %s, got %s" % (tuple(d1.shape), tuple(colors.shape)))
+        if colors.data_ptr() % 4:  # a view at an odd storage offset: the C entry moves a pixel as one dword
+            colors = colors.clone()
+    n_visited = -(-W // int(step)) * -(-H // int(step))
+    if capacity is None:
+        capacity = n_visited
+    if isinstance(capacity, bool) or int(capacity) != capacity or not 0 <= capacity < 2 ** 31:
+        raise ValueError("capacity must be an integer >= 0, got %r" % (capacity,))
+    capacity = int(capacity)
+    q = np.ascontiguousarray(Q, dtype=np.float64).reshape(16)
+    xr = None if XR is None else np.ascontiguousarray(XR, dtype=np.float64).reshape(9)
+    xt = None if XT is None else np.ascontiguousarray(XT, dtype=np.float64).reshape(3)
+    dev = d1.device
+    xyz = torch.empty((B, capacity, 3), dtype=torch.float32 if dtype == "f32" else torch.float64, device=dev)
+    color = torch.empty((B, capacity, 4), dtype=torch.uint8, device=dev) if colors is not None else None
+    index = torch.empty((B, capacity), dtype=torch.int32, device=dev) if want_index else None
+    counts = torch.empty((B,), dtype=torch.int32, device=dev)  # the scan kernel writes every entry
+    if B == 0:  # nothing to enqueue
+        return xyz, color, index, counts
+    L = cloud_lib()
+    nbytes = L.sv_cloud_workspace_bytes(ctypes.byref(spec), B, W, H)
+    ws = torch.empty(((nbytes + 3) // 4,), dtype=torch.int32, device=dev) if nbytes else None
+    with torch.cuda.device(dev):
+        rc = L.sv_cloud_disparity_device(d1.data_ptr(), colors.data_ptr() if colors is not None else None, B, W, H, q.ctypes.data,
+                                         xr.ctypes.data if xr is not None else None, xt.ctypes.data if xt is not None else None, ctypes.byref(spec),
+                                         capacity, xyz.data_ptr() if capacity else None, color.data_ptr() if color is not None and capacity else None,
+                                         index.data_ptr() if index is not None and capacity else None, counts.data_ptr(),
+                                         ws.data_ptr() if ws is not None else None, nbytes, torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        msg = "sv_cloud_disparity_device failed (%d): %s" % (rc, (L.sv_last_error(None) or b"").decode())
+        raise ValueError(msg) if rc == -1 else StereoError(msg)
+    return xyz, color, index, counts
+
+
+def split_clouds(xyz, counts, *others):
+    """Per-frame views of compact_cloud_from_disparity's padded tensors, cut at min(counts[b], capacity): a list with one xyz[b, :n] per
+    frame or, with others (color, index, ...; None entries stay None), one tuple per frame.  Reads counts on the host: the one place that
+    synchronises."""
+    n = counts.cpu().tolist()
+    cap = xyz.shape[1]
+    out = []
+    for b in range(xyz.shape[0]):
+        k = min(int(n[b]), cap)
+        out.append(xyz[b, :k] if not others else (xyz[b, :k],) + tuple(None if o is None else o[b, :k] for o in others))
+    return out
+
+
 def host_support_filter(params, dcan, width, height, threads=0, lattice=False):
     """Product host stage: lattice filters + corner points (CPU by design; see csrc/host_stage.h).  threads > 0: the lattice shared between
     that many threads (what single-pair calls do); lattice=True: also return the filtered lattice."""

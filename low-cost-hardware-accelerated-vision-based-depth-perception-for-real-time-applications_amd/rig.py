@@ -8,6 +8,8 @@ disparity, the driver's 8-bit map and point clouds out.
     d1, dmap, points = rig.point_clouds(left, right, pixel_format="bgr")
     grid = rig.top_view(left, right, (0, 40), (-20, 20), (-1.4, 1.0), 10, disparity="d1", transform=(CAMERA_TO_VEHICLE, None))
     pos, stat = rig.box_positions(left, right, boxes, n_boxes)       # f64 [B,M,3] metres, int32 [B,M,4]
+    xyz, color, counts = rig.compact_clouds(left, right, lo=(0, -20, -1.4), hi=(40, 20, 1.0), transform=(CAMERA_TO_VEHICLE, None))
+    clouds = split_clouds(xyz, counts, color)                        # per frame (f32 [n,3] metres, BGRA u8 [n,4]), in pixel order
 
 Frames are [B,Hs,Ws,C] (C = 4, 3, 3 for "bgra", "bgr", "rgb") or [B,Hs,Ws] for "gray"; one frame without B is accepted.
 Frames of another size than the rig's are resized to it.  CUDA tensors are processed on torch's current stream and CUDA
@@ -18,8 +20,8 @@ import ctypes
 
 import numpy as np
 
-from .engine import (SvParams, StereoEngine, StereoError, box_positions_from_disparity, box_spec, lib, pinned_array, reproject, top_view_from_disparity,
-                     top_view_spec)
+from .engine import (SvParams, StereoEngine, StereoError, box_positions_from_disparity, box_spec, cloud_spec, compact_cloud_from_disparity, lib,
+                     pinned_array, reproject, split_clouds, top_view_from_disparity, top_view_spec)
 from .stereo_vision.sv import CAMERA_TO_VEHICLE, DEFAULT_CALIBRATION  # noqa: F401 (CAMERA_TO_VEHICLE: re-exported for top_view)
 
 PIXEL_FORMATS = {"bgra": 0, "bgr": 1, "rgb": 2, "gray": 3}
@@ -245,3 +247,26 @@ class StereoRig:
         d1, _ = self.engine.process_device(gl, gr, want_d2=False)
         pos, stat = box_positions_from_disparity(d1, self.Q, boxes, n_boxes, XR=XR, XT=XT, select=select, disparity=disparity, band=band)
         return (pos.cpu().numpy(), stat.cpu().numpy()) if from_numpy else (pos, stat)
+
+    def compact_clouds(self, left, right, pixel_format="bgr", lo=None, hi=None, step=1, disparity="d1", dtype="f32", transform=None, capacity=None,
+                       colors=True):
+        """Coloured point clouds of B pairs as lists of points - what a viewer, a PLY file (stereo_vision.sv.write_ply) or a voxel grid
+        takes: front end (with colours), engine, then the fused disparity -> compact cloud kernels; no dense cloud is written.  Per
+        frame the pixels of every step-th column and row that carry a disparity and whose point lies strictly inside lo < P < hi (None =
+        open; inf / NaN never pass), in pixel order.  disparity "d1": metres from the float disparity; "dmap": the driver's cloud, a
+        quarter of metric depth.  transform as in top_view: None (camera axes), "rig" or (XR, XT); the crop applies after it.
+        CUDA input: (xyz [B,capacity,3] float32 or float64 ("f64"), color BGRA uint8 [B,capacity,4] or None (colors=False), counts int32
+        [B]) as engine.compact_cloud_from_disparity - rows at and beyond counts[b] are undefined, counts is not capped by capacity
+        (None = the visited pixels: no overflow), nothing is waited for; engine.split_clouds cuts them.  numpy input: a list of
+        per-frame (xyz [n,3], color [n,4] or None) numpy arrays."""
+        if self.params.subsampling:
+            raise ValueError("compact_clouds does not support half-resolution maps (params.subsampling)")
+        cloud_spec(lo, hi, step, disparity, dtype)  # argument errors before any work
+        XR, XT = self._transform(transform)
+        gl, gr, col, from_numpy = self._run_frontend(left, right, pixel_format, bool(colors))
+        d1, _ = self.engine.process_device(gl, gr, want_d2=False)
+        xyz, color, _, counts = compact_cloud_from_disparity(d1, self.Q, colors=col, XR=XR, XT=XT, lo=lo, hi=hi, step=step, disparity=disparity,
+                                                             dtype=dtype, capacity=capacity)
+        if not from_numpy:
+            return xyz, color, counts
+        return [(p.cpu().numpy(), None if c is None else c.cpu().numpy()) for p, c in split_clouds(xyz, counts, color)]

@@ -24,6 +24,11 @@ box_positions is the numpy restatement of the batched object positions (sv_box_p
 engine.box_positions / engine.box_positions_from_disparity / rig.StereoRig.box_positions on the GPU): the mean point inside each
 detector box in the library's summation order, usable without a GPU and the tests' oracle.  stereo_vision.object_positions stays
 the reference's one-frame form.
+
+compact_cloud is the numpy restatement of the compact coloured point clouds (sv_cloud_* of include/stereo_vision_hip.h (F);
+engine.compact_cloud_from_disparity / rig.StereoRig.compact_clouds on the GPU): per frame the valid, cropped, thinned-out points in
+pixel order with their colours and pixel indices - the pairing of points[i] with colors[i] the reference's viewer draws
+(src/common_includes/graphing.h:123-133).  write_ply stores one as a binary PLY file.
 """
 import argparse
 import ctypes
@@ -42,6 +47,8 @@ DEFAULT_CALIBRATION = os.path.join(HERE, "data", "kitti_2011_09_26.yml")
 CAMERA_TO_VEHICLE = np.array([[0.0, 0.0, 1.0], [-1.0, 0.0, 0.0], [0.0, -1.0, 0.0]])
 CLI_TOP_VIEW = {"x_range": (0, 40), "y_range": (-20, 20), "z_range": (-1.4, 1.0), "scale": 10}
 TOP_VIEW_MODES = ("reference", "count")
+# --ply: the crop of CLI_TOP_VIEW as (lo, hi) of a compact cloud
+CLI_CLOUD_CROP = tuple(tuple(float(CLI_TOP_VIEW[k][i]) for k in ("x_range", "y_range", "z_range")) for i in (0, 1))
 
 
 def _integer(v, what):
@@ -246,6 +253,91 @@ def box_positions(points_or_disp, boxes, n_boxes=None, Q=None, XR=None, XT=None,
     return (pos, stat) if batched else (pos[0], stat[0])
 
 
+CLOUD_DISPARITY = {"dmap": 0, "d1": 1}
+CLOUD_DTYPES = {"f32": 0, "f64": 1}
+
+
+def cloud_crop(lo=None, hi=None, step=1, disparity="d1", dtype="f32"):
+    """(lo float64 [3], hi float64 [3]) of a compact-cloud request after the checks sv_cloud_disparity_device makes (ValueError for a bad
+    argument): None = every axis open, lo < hi per axis (NaN refused), step an integer in 1 .. 2^31 - 1, disparity / dtype known."""
+    if disparity not in CLOUD_DISPARITY:
+        raise ValueError("disparity must be one of %s, got %r" % (sorted(CLOUD_DISPARITY), disparity))
+    if dtype not in CLOUD_DTYPES:
+        raise ValueError("dtype must be one of %s, got %r" % (sorted(CLOUD_DTYPES), dtype))
+    if isinstance(step, bool) or int(step) != step or not 1 <= step < 2 ** 31:
+        raise ValueError("step must be an integer >= 1, got %r" % (step,))
+    lo = np.full(3, -np.inf) if lo is None else np.array(lo, np.float64).reshape(-1)
+    hi = np.full(3, np.inf) if hi is None else np.array(hi, np.float64).reshape(-1)
+    if lo.shape != (3,) or hi.shape != (3,) or not (lo < hi).all():
+        raise ValueError("the crop needs three lo < hi, got %r / %r" % (lo.tolist(), hi.tolist()))
+    return lo, hi
+
+
+def compact_cloud(disp, Q, XR=None, XT=None, lo=None, hi=None, step=1, disparity="d1", dtype="f32", colors=None):
+    """Compact coloured point cloud(s), the definition of include/stereo_vision_hip.h (F) in numpy.
+
+    disp: a float32 disparity map [H,W] (or [B,H,W]).  The pixels with x % step == 0 and y % step == 0 are visited in ascending flat
+    index y * W + x; a candidate ("dmap": q = saturate_u8(round_half_even(4 d)) > 0, its point that of (double)q, the driver's cloud at a
+    quarter of metric depth; "d1": d > 0, its point that of d itself, metres) is kept iff lo[k] < P[k] < hi[k] on all three axes of
+    P = reproject(x, y, .) (then XR P + XT) - strictly, so inf and NaN never pass; None leaves lo / hi open.
+    Returns (xyz [N,3] float32 - P.astype(float32), round to nearest even - or float64, color uint8 [N,4] = colors[y, x] (None without
+    colors [H,W,4]), index int32 [N] = y * W + x); for batched input a list of such tuples, one per frame."""
+    lo, hi = cloud_crop(lo, hi, step, disparity, dtype)
+    d = np.asarray(disp, dtype=np.float32)
+    if d.ndim not in (2, 3):
+        raise ValueError("expected disp [H,W] or [B,H,W], got shape %s" % (d.shape,))
+    batched = d.ndim == 3
+    if not batched:
+        d = d[None]
+    B, H, W = d.shape
+    col = None
+    if colors is not None:
+        col = np.asarray(colors)
+        col = col[None] if col.ndim == 3 else col
+        if col.dtype != np.uint8 or col.shape != (B, H, W, 4):
+            raise ValueError("colors must be uint8 [B,H,W,4] matching disp, got %s %s" % (col.dtype, col.shape))
+    s = int(step)
+    flat = (np.arange(0, H, s)[:, None] * W + np.arange(0, W, s)[None]).astype(np.int32)  # the visited pixels, in order
+    out = []
+    for b in range(B):
+        _, cand, dd = box_quantise(d[b], disparity)
+        P = _box_points(dd, Q, XR, XT)[::s, ::s]
+        keep = cand[::s, ::s].copy()
+        with np.errstate(invalid="ignore"):
+            for k in range(3):
+                keep &= (lo[k] < P[..., k]) & (P[..., k] < hi[k])
+        pts = P[keep]
+        with np.errstate(over="ignore"):
+            xyz = pts.astype(np.float32) if dtype == "f32" else pts
+        index = flat[keep]
+        out.append((xyz, None if col is None else col[b].reshape(-1, 4)[index], index))
+    return out if batched else out[0]
+
+
+def write_ply(path, xyz, color=None):
+    """A binary little-endian PLY of N points: `float x y z` (xyz [N,3], cast to float32), with color (uint8 [N,4], BGRA as the rig's
+    colours) also `uchar red green blue`."""
+    xyz = np.asarray(xyz)
+    if xyz.ndim != 2 or xyz.shape[1] != 3:
+        raise ValueError("xyz must be [N,3], got shape %s" % (xyz.shape,))
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    header = ["ply", "format binary_little_endian 1.0", "element vertex %d" % len(xyz), "property float x", "property float y", "property float z"]
+    if color is not None:
+        color = np.asarray(color)
+        if color.dtype != np.uint8 or color.shape != (len(xyz), 4):
+            raise ValueError("color must be uint8 [N,4] (BGRA), got %s %s" % (color.dtype, color.shape))
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        header += ["property uchar red", "property uchar green", "property uchar blue"]
+    rec = np.empty(len(xyz), dtype=np.dtype(fields))
+    with np.errstate(over="ignore"):
+        rec["x"], rec["y"], rec["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    if color is not None:
+        rec["red"], rec["green"], rec["blue"] = color[:, 2], color[:, 1], color[:, 0]
+    with open(path, "wb") as f:
+        f.write(("\n".join(header + ["end_header"]) + "\n").encode("ascii"))
+        f.write(rec.tobytes())
+
+
 class stereo_vision:
     def __init__(self, so_lib_path=DEFAULT_STEREO_VISION_SO_PATH, width=1242, height=375, defaultCalibFile=True, objectTracking=True,
                  graphics=False, display=False, scale=1, pc_extrapolation=1, YOLO_CFG="src/yolo/yolov4-tiny.cfg",
@@ -369,9 +461,15 @@ def main(argv=None):
                              "the float disparity reprojected in metres (pixels with d <= 0 skipped), camera (right, down, forward) -> "
                              "(forward, left, up) by XR = [[0,0,1],[-1,0,0],[0,-1,0]], XT = 0; x 0..40, y -20..20, z -1.4..1.0, "
                              "scale 10 (401 x 401 cells, row 0 = 40 m ahead, column 0 = 20 m to the left)")
+    parser.add_argument("--ply", type=str, default="", metavar="DIR",
+                        help="with --batch: write each frame's coloured point cloud as DIR/<name>.ply (binary little-endian; float x y z, "
+                             "uchar red green blue): the float disparity reprojected in metres, the axes and the crop of --top-view "
+                             "(forward 0..40, left -20..20, up -1.4..1.0)")
     args = parser.parse_args(argv)
     if args.top_view and not args.batch:
         parser.error("--top-view needs --batch")
+    if args.ply and not args.batch:
+        parser.error("--ply needs --batch")
     if args.batch < 0:
         parser.error("--batch must be >= 1")
     if args.batch and args.subsampling:
@@ -393,6 +491,8 @@ def main(argv=None):
         os.makedirs(args.out, exist_ok=True)
     if args.top_view:
         os.makedirs(args.top_view, exist_ok=True)
+    if args.ply:
+        os.makedirs(args.ply, exist_ok=True)
     if args.batch:
         _run_batched(args, ldir, rdir, files)
         return
@@ -428,7 +528,7 @@ def _run_batched(args, ldir, rdir, files):
     """--batch N: the folder through a StereoRig (the batched front end and engine) N pairs at a time."""
     import time
     import torch
-    from ..engine import disparity_to_u8, top_view_from_disparity
+    from ..engine import compact_cloud_from_disparity, disparity_to_u8, split_clouds, top_view_from_disparity
     from ..rig import StereoRig
     rig = StereoRig(1242 // args.scale, 375 // args.scale, calibration=args.camera_calibration, rectify=args.rectify, scale=args.scale)
     n, busy = 0, 0.0
@@ -442,7 +542,12 @@ def _run_batched(args, ldir, rdir, files):
             right = torch.from_numpy(np.stack([r for _, r in lr])).cuda(rig.device)
             torch.cuda.synchronize(rig.device)
             t0 = time.perf_counter()
-            d1 = rig.disparity(left, right, pixel_format="bgr")
+            if args.ply:  # what rig.compact_clouds(..., transform=(CAMERA_TO_VEHICLE, None), lo=, hi=) runs, keeping d1 for the other outputs
+                gl, gr, col = rig.frontend(left, right, pixel_format="bgr", colors=True)
+                d1, _ = rig.engine.process_device(gl, gr, want_d2=False)
+                clouds = compact_cloud_from_disparity(d1, rig.Q, colors=col, XR=CAMERA_TO_VEHICLE, lo=CLI_CLOUD_CROP[0], hi=CLI_CLOUD_CROP[1])
+            else:
+                d1 = rig.disparity(left, right, pixel_format="bgr")
             dmap = disparity_to_u8(d1)
             if args.top_view:  # what rig.top_view(..., disparity="d1", transform=(CAMERA_TO_VEHICLE, None)) gives, on the same d1
                 grids = top_view_from_disparity(d1, rig.Q, XR=CAMERA_TO_VEHICLE, disparity="d1", **CLI_TOP_VIEW)
@@ -455,6 +560,9 @@ def _run_batched(args, ldir, rdir, files):
             if args.top_view:
                 for name, g in zip(names, grids.cpu().numpy()):
                     _write_png(os.path.join(args.top_view, name), g)
+            if args.ply:
+                for name, (xyz, color) in zip(names, split_clouds(clouds[0], clouds[3], clouds[1])):
+                    write_ply(os.path.join(args.ply, os.path.splitext(name)[0] + ".ply"), xyz.cpu().numpy(), color.cpu().numpy())
             n += len(names)
             print("batch of %d (%d, %d): %.1f pairs/s so far" % (len(names), rig.height, rig.width, n / busy))
     finally:
