@@ -30,6 +30,10 @@
  *      points with their colours and pixel indices, in pixel order, from disparity maps (fused: no dense cloud is written).  It is
  *      what the reference's viewer draws: Grapher pairs points[i] with colors[i] (src/common_includes/graphing.h:123-133).
  *
+ *  (G) Behind (B) as well: the ground plane, obstacle labels and free space (sv_ground_*) - per pair the v-disparity histogram, the
+ *      ground line fitted to it, a label per pixel and per column the base of the nearest obstacle, from disparity maps.  The reference
+ *      has no counterpart; stereo_vision.sv states the definition in numpy.
+ *
  * All sv_* functions return SV_OK (0) or a negative sv_status; sv_last_error() gives the text.
  * Nothing in this library calls exit().
  */
@@ -494,6 +498,63 @@ size_t sv_cloud_workspace_bytes(const sv_cloud_spec *spec, int batch, int width,
 int sv_cloud_disparity_device(const float *disp, const uint8_t *colors, int batch, int width, int height, const double *Q16, const double *XR9,
                               const double *XT3, const sv_cloud_spec *spec, int capacity, void *xyz, uint8_t *color_out, int32_t *index_out, int32_t *counts,
                               void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- (G) ground plane, obstacle labels and free space: disparity maps -> a line, labels and a row per column ---------- */
+
+/* Where the ground is, what stands on it and how far one can go in each image column, for B pairs: Labayrade's v-disparity line fit
+ * followed by a per-column scan.  Integer work throughout; the results are bitwise reproducible and independent of the batch a pair sits
+ * in.  stereo_vision.sv (v_disparity, ground_line, ground_labels, free_space) restates all of it in numpy.
+ *
+ *   bins       a pixel is valid iff d > 0 (NaN is not; the engine's invalid pixels are -10); its bin is
+ *              q = min(rintf(4.0f * d), n_bins - 1): quarter pixels, round half to even - the only floating-point operations.
+ *   vdisp      vdisp[b][v][q] = the number of valid pixels of row v in bin q.
+ *   ground     the line through (row vh, bin 0) - the horizon - and (row height - 1, bin qb): with den = height - 1 - vh
+ *                ql(v) = (2 qb (v - vh) + den) / (2 den), integer division (v > vh: nothing is negative)
+ *                S(vh, qb) = sum over v = max(vh + 1, 0) .. height - 1 and k = -tol .. tol with 0 <= ql(v) + k < n_bins of vdisp[b][v][ql(v) + k]
+ *              over the candidates vh = vh_lo, vh_lo + vh_step, ... <= vh_hi and qb = qb_step, 2 qb_step, ... < n_bins.  The largest S
+ *              wins; ties go to the smallest vh, then the smallest qb.  ground[b] = {vh, qb, S, n_valid} (n_valid = the valid pixels
+ *              of the map), or {-1, -1, S, n_valid} - "no ground" - when S < min_support (an all-invalid map has S = 0).
+ *   labels     with g(v) = ql(v) for v > vh, 0 for v <= vh, and e = q - g(v):
+ *                0 invalid, 1 ground (|e| <= g_tol), 2 obstacle (e > g_tol), 3 below the ground (e < -g_tol);
+ *              with "no ground" every valid pixel is 3.
+ *   free space per column u, walking from row height - 1 upwards: the first row v such that the min_run rows v, v - 1, ...,
+ *              v - min_run + 1 exist and are all obstacle; free_row[b][u] = v, free_disp[b][u] = disp[b][v][u]; -1 and 0.0f for a
+ *              column without one. */
+typedef struct sv_ground_spec {
+    int32_t n_bins;       /* 8..4096; 4 * (disp_max + 1) holds every disparity of the engine */
+    int32_t vh_lo, vh_hi; /* -32768 <= vh_lo <= vh_hi <= height - 2 */
+    int32_t vh_step;      /* >= 1 */
+    int32_t qb_step;      /* 1..n_bins - 1: at least one candidate */
+    int32_t tol;          /* 0..16: half width of the band that is summed, in bins */
+    int32_t g_tol;        /* 0..4096: half width of the band that is labelled ground, in bins */
+    int32_t min_run;      /* >= 1: obstacle rows in a column that stop the free space */
+    int32_t min_support;  /* >= 0: the least S that is a ground */
+    int32_t reserved[7];  /* must be 0 */
+} sv_ground_spec;
+
+/* Bytes of device workspace a call needs (8 per candidate vh and 4 (n_bins + 1) per row, per pair; 0 for batch == 0).  Host only;
+ * SIZE_MAX for a bad spec, batch, width or height (the checks of the call below). */
+size_t sv_ground_workspace_bytes(const sv_ground_spec *spec, int batch, int width, int height);
+/* Enqueued on `stream` (a hipStream_t, NULL = the default stream) as four kernels - histogram and prefix sums, search, pick, labels
+ * and free space (left out when none of its three outputs is asked for) - and not waited for; nothing is allocated, no host
+ * synchronisation is made.
+ *   disp         : float [batch][height][width] device
+ *   vdisp        : uint32 [batch][height][n_bins] device, or NULL
+ *   ground       : int32 [batch][4] device
+ *   labels       : uint8 [batch][height][width] device, or NULL
+ *   free_row     : int32 [batch][width] device, or NULL
+ *   free_disp    : float [batch][width] device, or NULL
+ *   workspace    : device, 8-byte aligned, workspace_bytes >= sv_ground_workspace_bytes(spec, batch, width, height); its contents
+ *                  before and after the call mean nothing
+ * An output left out does not change the others.
+ * Returns SV_OK (nothing enqueued for batch == 0), SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued, the outputs untouched, the text in
+ * sv_last_error(NULL) - for: a NULL spec, disp or ground; disp, vdisp, ground, free_row or free_disp not 4-byte aligned; a spec word
+ * outside the range given beside it; a non-zero reserved word; a workspace that is NULL, misaligned or too small; batch < 0 or
+ * > 65535; width < 1 or height < 1; height > 32768; width * height >= 2^31.  These checks run before any HIP call.
+ * The environment variable SV_GROUND_HIST=plain selects the histogram kernel without wavefront aggregation (a measurement aid: the
+ * results are the same). */
+int sv_ground_disparity_device(const float *disp, int batch, int width, int height, const sv_ground_spec *spec, uint32_t *vdisp, int32_t *ground,
+                               uint8_t *labels, int32_t *free_row, float *free_disp, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- (A) the reference's exported symbols ------------------------------------------------------------- */
 

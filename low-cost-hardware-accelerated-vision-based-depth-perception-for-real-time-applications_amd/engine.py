@@ -795,6 +795,94 @@ def split_clouds(xyz, counts, *others):
     return out
 
 
+class SvGroundSpec(ctypes.Structure):
+    """sv_ground_spec of include/stereo_vision_hip.h."""
+    _fields_ = [("n_bins", ctypes.c_int32), ("vh_lo", ctypes.c_int32), ("vh_hi", ctypes.c_int32), ("vh_step", ctypes.c_int32),
+                ("qb_step", ctypes.c_int32), ("tol", ctypes.c_int32), ("g_tol", ctypes.c_int32), ("min_run", ctypes.c_int32),
+                ("min_support", ctypes.c_int32), ("reserved", ctypes.c_int32 * 7)]
+
+
+_ground_bound = False
+
+
+def ground_lib():
+    """The library with the sv_ground_* signatures declared."""
+    global _ground_bound
+    L = lib()
+    if not _ground_bound:
+        vp, ci, sp = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(SvGroundSpec)
+        L.sv_ground_workspace_bytes.argtypes = [sp, ci, ci, ci]
+        L.sv_ground_workspace_bytes.restype = ctypes.c_size_t
+        L.sv_ground_disparity_device.argtypes = [vp, ci, ci, ci, sp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
+        L.sv_ground_disparity_device.restype = ci
+        _ground_bound = True
+    return L
+
+
+def ground_spec(height, disp_max=None, n_bins=None, vh_lo=0, vh_hi=None, vh_step=2, qb_step=2, tol=2, g_tol=4, min_run=8, min_support=0):
+    """-> SvGroundSpec for maps of `height` rows; ValueError for a bad argument (the checks of the C entry, made in Python first:
+    stereo_vision.sv.ground_params).  n_bins None = 4 (disp_max + 1); vh_hi None = height - 2."""
+    from .stereo_vision.sv import ground_params
+    p = ground_params(height, disp_max, n_bins=n_bins, vh_lo=vh_lo, vh_hi=vh_hi, vh_step=vh_step, qb_step=qb_step, tol=tol, g_tol=g_tol, min_run=min_run,
+                      min_support=min_support)
+    spec = SvGroundSpec()
+    for k, v in p.items():
+        setattr(spec, k, v)
+    return spec
+
+
+class GroundResult:
+    """What ground_from_disparity returns, tensors on the input's device: ground int32 [B,4] = (vh, qb, S, n_valid) per pair ((-1, -1, S,
+    n_valid): no ground), vdisp uint32-valued int32 [B,H,n_bins], labels uint8 [B,H,W] (0 invalid, 1 ground, 2 obstacle, 3 below the
+    ground), free_row int32 [B,W] and free_disp float32 [B,W] (-1 / 0: no obstacle in the column) - None where not asked for - and the
+    spec in use.  StereoRig.ground adds pose (per pair (height_m, pitch_rad, slope_px_per_row) or None) and points (float64 [B,W,3]
+    numpy, NaN where free_row < 0), both on the host."""
+    __slots__ = ("ground", "vdisp", "labels", "free_row", "free_disp", "spec", "pose", "points")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+def ground_from_disparity(disp, disp_max=None, n_bins=None, vh_lo=0, vh_hi=None, vh_step=2, qb_step=2, tol=2, g_tol=4, min_run=8, min_support=None,
+                          want_vdisp=True, want_labels=True, want_free=True):
+    """Ground plane, obstacle labels and free space straight from disparity maps (CUDA float32 [B,H,W]; one frame [H,W] accepted), the
+    definition of stereo_vision.sv.ground on the GPU, bit for bit: the v-disparity histogram in quarter-pixel bins
+    (n_bins = 4 (disp_max + 1) unless given), the line through (row vh, bin 0) and (row H - 1, bin qb) with the largest support S within
+    tol bins - exhaustively over vh = vh_lo .. vh_hi (None = H - 2) in steps of vh_step and qb in steps of qb_step -, a label per
+    pixel within / above / below g_tol bins of that line, and per column the lowest row at which min_run obstacle rows begin.
+    min_support None = the width: a line with less support is "no ground".  -> GroundResult; enqueued on torch's current stream, not
+    waited for."""
+    import torch
+    if not (isinstance(disp, torch.Tensor) and disp.is_cuda and disp.dtype == torch.float32 and disp.dim() in (2, 3)):
+        raise ValueError("disp must be a CUDA float32 tensor [B,H,W]")
+    d = (disp.unsqueeze(0) if disp.dim() == 2 else disp).contiguous()
+    B, H, W = d.shape
+    if B > 65535 or H < 1 or W < 1 or H * W >= 2 ** 31:
+        raise ValueError("at most 65535 pairs of 1 <= width * height < 2^31 pixels, got %s" % (tuple(d.shape),))
+    spec = ground_spec(H, disp_max, n_bins, vh_lo, vh_hi, vh_step, qb_step, tol, g_tol, min_run, W if min_support is None else min_support)
+    dev = d.device
+    ground = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    vdisp = torch.empty((B, H, spec.n_bins), dtype=torch.int32, device=dev) if want_vdisp else None
+    labels = torch.empty((B, H, W), dtype=torch.uint8, device=dev) if want_labels else None
+    free_row = torch.empty((B, W), dtype=torch.int32, device=dev) if want_free else None
+    free_disp = torch.empty((B, W), dtype=torch.float32, device=dev) if want_free else None
+    res = GroundResult(ground=ground, vdisp=vdisp, labels=labels, free_row=free_row, free_disp=free_disp, spec=spec)
+    if B == 0:  # nothing to enqueue
+        return res
+    L = ground_lib()
+    nbytes = L.sv_ground_workspace_bytes(ctypes.byref(spec), B, W, H)
+    ws = torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=dev)
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    with torch.cuda.device(dev):
+        rc = L.sv_ground_disparity_device(d.data_ptr(), B, W, H, ctypes.byref(spec), ptr(vdisp), ground.data_ptr(), ptr(labels), ptr(free_row),
+                                          ptr(free_disp), ws.data_ptr(), nbytes, torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        msg = "sv_ground_disparity_device failed (%d): %s" % (rc, (L.sv_last_error(None) or b"").decode())
+        raise ValueError(msg) if rc == -1 else StereoError(msg)
+    return res
+
+
 def host_support_filter(params, dcan, width, height, threads=0, lattice=False):
     """Product host stage: lattice filters + corner points (CPU by design; see csrc/host_stage.h).  threads > 0: the lattice shared between
     that many threads (what single-pair calls do); lattice=True: also return the filtered lattice."""

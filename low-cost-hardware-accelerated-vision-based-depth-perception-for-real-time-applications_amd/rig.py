@@ -10,6 +10,8 @@ disparity, the driver's 8-bit map and point clouds out.
     pos, stat = rig.box_positions(left, right, boxes, n_boxes)       # f64 [B,M,3] metres, int32 [B,M,4]
     xyz, color, counts = rig.compact_clouds(left, right, lo=(0, -20, -1.4), hi=(40, 20, 1.0), transform=(CAMERA_TO_VEHICLE, None))
     clouds = split_clouds(xyz, counts, color)                        # per frame (f32 [n,3] metres, BGRA u8 [n,4]), in pixel order
+    g = rig.ground(left, right)                                      # g.ground [B,4] = (vh, qb, S, n_valid), g.labels u8 [B,H,W], g.free_row [B,W],
+                                                                     # g.pose[b] = (height m, pitch rad, slope), g.points f64 [B,W,3] metres
 
 Frames are [B,Hs,Ws,C] (C = 4, 3, 3 for "bgra", "bgr", "rgb") or [B,Hs,Ws] for "gray"; one frame without B is accepted.
 Frames of another size than the rig's are resized to it.  CUDA tensors are processed on torch's current stream and CUDA
@@ -20,9 +22,10 @@ import ctypes
 
 import numpy as np
 
-from .engine import (SvParams, StereoEngine, StereoError, box_positions_from_disparity, box_spec, cloud_spec, compact_cloud_from_disparity, lib,
-                     pinned_array, reproject, split_clouds, top_view_from_disparity, top_view_spec)
+from .engine import (SvParams, StereoEngine, StereoError, box_positions_from_disparity, box_spec, cloud_spec, compact_cloud_from_disparity,
+                     ground_from_disparity, ground_spec, lib, pinned_array, reproject, split_clouds, top_view_from_disparity, top_view_spec)
 from .stereo_vision.sv import CAMERA_TO_VEHICLE, DEFAULT_CALIBRATION  # noqa: F401 (CAMERA_TO_VEHICLE: re-exported for top_view)
+from .stereo_vision.sv import free_space_points, ground_pose
 
 PIXEL_FORMATS = {"bgra": 0, "bgr": 1, "rgb": 2, "gray": 3}
 _CHANNELS = {"bgra": 4, "bgr": 3, "rgb": 3, "gray": 1}
@@ -270,3 +273,33 @@ class StereoRig:
         if not from_numpy:
             return xyz, color, counts
         return [(p.cpu().numpy(), None if c is None else c.cpu().numpy()) for p, c in split_clouds(xyz, counts, color)]
+
+    def ground(self, left, right, pixel_format="bgr", transform=None, **spec):
+        """Where the ground is, what stands on it and how far one can go in each image column, for B pairs: front end, engine, then
+        engine.ground_from_disparity on the float disparity (n_bins from the rig's disp_max; spec: vh_lo, vh_hi, vh_step, qb_step, tol,
+        g_tol, min_run, min_support, want_vdisp, want_labels as there).  -> engine.GroundResult, with two host-side additions computed
+        from the few words per pair and the one row per pair that are read back (this call waits for them): pose[b] = (height_m,
+        pitch_rad, slope_px_per_row) of the camera over the fitted ground (stereo_vision.sv.ground_pose; None for a pair without
+        ground) and points float64 numpy [B,W,3] = the 3-D point of each column's obstacle base in metres (free_space_points; NaN for a
+        column without one), transform as in top_view: None (camera axes), "rig" or (XR, XT).  CUDA input: device tensors; numpy
+        input: numpy arrays."""
+        if self.params.subsampling:
+            raise ValueError("ground does not support half-resolution maps (params.subsampling)")
+        if "want_free" in spec or "disp_max" in spec or "n_bins" in spec:
+            raise ValueError("ground: want_free, disp_max and n_bins are not options of the rig (the free space is always computed, the bins follow the rig's disp_max)")
+        checked = {k: v for k, v in spec.items() if k not in ("want_vdisp", "want_labels")}
+        if checked.get("min_support") is None:
+            checked["min_support"] = self.width
+        ground_spec(self.height, self.params.disp_max, **checked)  # argument errors before any work
+        XR, XT = self._transform(transform)
+        gl, gr, _, from_numpy = self._run_frontend(left, right, pixel_format, False)
+        d1, _ = self.engine.process_device(gl, gr, want_d2=False)
+        res = ground_from_disparity(d1, self.params.disp_max, **spec)
+        rec, row, dsp = res.ground.cpu().numpy(), res.free_row.cpu().numpy(), res.free_disp.cpu().numpy()
+        res.pose = [ground_pose(self.Q, int(r[0]), int(r[1]), self.height) if r[1] > 0 else None for r in rec]
+        res.points = free_space_points(self.Q, row, dsp, XR, XT)
+        if from_numpy:
+            res.ground, res.free_row, res.free_disp = rec, row, dsp
+            res.vdisp = None if res.vdisp is None else res.vdisp.cpu().numpy()
+            res.labels = None if res.labels is None else res.labels.cpu().numpy()
+        return res

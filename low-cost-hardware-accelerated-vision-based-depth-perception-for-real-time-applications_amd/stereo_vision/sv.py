@@ -29,6 +29,11 @@ compact_cloud is the numpy restatement of the compact coloured point clouds (sv_
 engine.compact_cloud_from_disparity / rig.StereoRig.compact_clouds on the GPU): per frame the valid, cropped, thinned-out points in
 pixel order with their colours and pixel indices - the pairing of points[i] with colors[i] the reference's viewer draws
 (src/common_includes/graphing.h:123-133).  write_ply stores one as a binary PLY file.
+
+v_disparity, ground_line, ground_labels, free_space (together: ground), ground_pose and free_space_points are the definition of the ground
+plane, obstacle labels and free space (sv_ground_* of include/stereo_vision_hip.h (G); engine.ground_from_disparity /
+rig.StereoRig.ground on the GPU): Labayrade's v-disparity line fit in integers and a per-column scan for the nearest obstacle.  The
+reference has no counterpart.
 """
 import argparse
 import ctypes
@@ -336,6 +341,180 @@ def write_ply(path, xyz, color=None):
     with open(path, "wb") as f:
         f.write(("\n".join(header + ["end_header"]) + "\n").encode("ascii"))
         f.write(rec.tobytes())
+
+
+GROUND_BINS_MIN, GROUND_BINS_MAX = 8, 4096
+GROUND_VH_MIN, GROUND_TOL_MAX, GROUND_G_TOL_MAX, GROUND_HEIGHT_MAX = -32768, 16, 4096, 32768
+GROUND_LABELS = {"invalid": 0, "ground": 1, "obstacle": 2, "below": 3}
+
+
+def ground_params(height, disp_max=None, n_bins=None, vh_lo=0, vh_hi=None, vh_step=2, qb_step=2, tol=2, g_tol=4, min_run=8, min_support=0):
+    """The nine words of sv_ground_spec as a dict of ints, after the checks sv_ground_disparity_device makes (ValueError for a bad
+    argument).  n_bins = 4 (disp_max + 1) unless given: 8 <= n_bins <= 4096; vh_hi None = height - 2;
+    -32768 <= vh_lo <= vh_hi <= height - 2; vh_step >= 1; 1 <= qb_step < n_bins (so that a candidate exists); 0 <= tol <= 16;
+    0 <= g_tol <= 4096; min_run >= 1; min_support >= 0; 1 <= height <= 32768."""
+    if n_bins is None:
+        if disp_max is None:
+            raise ValueError("give disp_max or n_bins")
+        n_bins = 4 * (int(disp_max) + 1)
+    if vh_hi is None:
+        vh_hi = int(height) - 2
+    p = dict(n_bins=n_bins, vh_lo=vh_lo, vh_hi=vh_hi, vh_step=vh_step, qb_step=qb_step, tol=tol, g_tol=g_tol, min_run=min_run, min_support=min_support)
+    for k, v in p.items():
+        if isinstance(v, (bool, np.bool_)) or int(v) != v or not -2 ** 31 <= v < 2 ** 31:
+            raise ValueError("%s must be an int32, got %r" % (k, v))
+        p[k] = int(v)
+    if isinstance(height, bool) or int(height) != height or not 1 <= height <= GROUND_HEIGHT_MAX:
+        raise ValueError("height must be an integer in 1 .. %d, got %r" % (GROUND_HEIGHT_MAX, height))
+    if not GROUND_BINS_MIN <= p["n_bins"] <= GROUND_BINS_MAX:
+        raise ValueError("n_bins = %d outside %d .. %d" % (p["n_bins"], GROUND_BINS_MIN, GROUND_BINS_MAX))
+    if not GROUND_VH_MIN <= p["vh_lo"] <= p["vh_hi"] <= int(height) - 2:
+        raise ValueError("the horizon rows need %d <= vh_lo <= vh_hi <= height - 2, got %d .. %d at height %d" % (GROUND_VH_MIN, p["vh_lo"], p["vh_hi"], height))
+    if p["vh_step"] < 1 or not 1 <= p["qb_step"] < p["n_bins"]:
+        raise ValueError("vh_step must be >= 1 and qb_step in 1 .. n_bins - 1, got %d and %d" % (p["vh_step"], p["qb_step"]))
+    if not 0 <= p["tol"] <= GROUND_TOL_MAX or not 0 <= p["g_tol"] <= GROUND_G_TOL_MAX:
+        raise ValueError("tol must be in 0 .. %d and g_tol in 0 .. %d, got %d and %d" % (GROUND_TOL_MAX, GROUND_G_TOL_MAX, p["tol"], p["g_tol"]))
+    if p["min_run"] < 1 or p["min_support"] < 0:
+        raise ValueError("min_run must be >= 1 and min_support >= 0, got %d and %d" % (p["min_run"], p["min_support"]))
+    return p
+
+
+def ground_quantise(disp, n_bins):
+    """(q int32, valid bool) per pixel of a float32 map: valid = d > 0 (NaN is not), q = min(round_half_even(4 d), n_bins - 1) where
+    valid, 0 elsewhere - quarter-pixel bins, the box median's quantisation with n_bins in place of 4096."""
+    d = np.asarray(disp, dtype=np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        valid = d > 0
+        q = np.where(valid, np.minimum(np.rint(d * np.float32(4.0)), np.float32(n_bins - 1)), np.float32(0)).astype(np.int32)
+    return q, valid
+
+
+def v_disparity(disp, n_bins):
+    """The v-disparity histogram uint32 [H, n_bins] of a float32 map [H,W] ([B,H,n_bins] of [B,H,W]): per row the number of valid
+    pixels in each bin of ground_quantise."""
+    q, valid = ground_quantise(disp, n_bins)
+    if q.ndim not in (2, 3):
+        raise ValueError("expected disp [H,W] or [B,H,W], got shape %s" % (q.shape,))
+    rows = q.reshape(-1, q.shape[-1])
+    ok = valid.reshape(rows.shape)
+    out = np.zeros((rows.shape[0], n_bins), np.uint32)
+    for v in range(rows.shape[0]):
+        out[v] = np.bincount(rows[v][ok[v]], minlength=n_bins)
+    return out.reshape(q.shape[:-1] + (n_bins,))
+
+
+def ground_row_bins(vh, qb, height):
+    """g(v) int64 [height]: the ground line's bin per row - ql(v) = (2 qb (v - vh) + den) // (2 den), den = height - 1 - vh, below the
+    horizon row (v > vh), 0 at and above it.  ql(height - 1) = qb."""
+    v = np.arange(height, dtype=np.int64)
+    den = height - 1 - int(vh)
+    return np.where(v > vh, (2 * int(qb) * (v - int(vh)) + den) // (2 * den), 0)
+
+
+def ground_line(vdisp, vh_lo, vh_hi, vh_step, qb_step, tol, min_support=0):
+    """The ground line of one v-disparity histogram [H, n_bins]: (vh, qb, S, n_valid) as Python ints, by exhaustive search over the
+    horizon rows vh = vh_lo, vh_lo + vh_step, ... <= vh_hi and the bottom-row bins qb = qb_step, 2 qb_step, ... < n_bins.
+    S(vh, qb) = the histogram's mass within tol bins of ql(v) on the rows max(vh + 1, 0) .. H - 1 (bins outside 0 .. n_bins - 1 hold
+    nothing).  The largest S wins, ties go to the smallest vh, then the smallest qb; S < min_support gives (-1, -1, S, n_valid)."""
+    h = np.asarray(vdisp).astype(np.int64)
+    H, n_bins = h.shape
+    ground_params(H, n_bins=n_bins, vh_lo=vh_lo, vh_hi=vh_hi, vh_step=vh_step, qb_step=qb_step, tol=tol, min_support=min_support)
+    P = np.zeros((H, n_bins + 1), np.int64)
+    P[:, 1:] = np.cumsum(h, axis=1)
+    qbs = np.arange(qb_step, n_bins, qb_step, dtype=np.int64)
+    best = None
+    for vh in range(vh_lo, vh_hi + 1, vh_step):
+        den = H - 1 - vh
+        v = np.arange(max(vh + 1, 0), H, dtype=np.int64)[:, None]
+        ql = (2 * qbs[None, :] * (v - vh) + den) // (2 * den)
+        S = (P[v, np.minimum(ql + tol + 1, n_bins)] - P[v, np.maximum(ql - tol, 0)]).sum(0)
+        i = int(np.argmax(S))  # the first of equal maxima: the smallest qb
+        if best is None or S[i] > best[2]:  # strictly: the smallest vh stays
+            best = (vh, int(qbs[i]), int(S[i]))
+    n_valid = int(h.sum())
+    return (best[0], best[1], best[2], n_valid) if best[2] >= min_support else (-1, -1, best[2], n_valid)
+
+
+def ground_labels(disp, n_bins, vh, qb, g_tol):
+    """Labels uint8 [H,W] of a float32 map against the ground line (vh, qb): with e = q - g(v) (ground_quantise, ground_row_bins)
+    0 invalid, 1 ground (|e| <= g_tol), 2 obstacle (e > g_tol: nearer than the ground), 3 below the ground (e < -g_tol).
+    (vh, qb) = (-1, -1), "no ground": every valid pixel is 3."""
+    q, valid = ground_quantise(disp, n_bins)
+    if q.ndim != 2:
+        raise ValueError("expected disp [H,W], got shape %s" % (q.shape,))
+    if qb < 0:
+        return np.where(valid, 3, 0).astype(np.uint8)
+    e = q.astype(np.int64) - ground_row_bins(vh, qb, q.shape[0])[:, None]
+    return np.where(valid, np.where(e > g_tol, 2, np.where(e < -g_tol, 3, 1)), 0).astype(np.uint8)
+
+
+def free_space(labels, disp, min_run):
+    """(free_row int32 [W], free_disp float32 [W]): per column, walking up from the bottom row, the first row v whose min_run rows
+    v, v - 1, ..., v - min_run + 1 all exist and are labelled obstacle - the base of the nearest obstacle, the far end of the drivable
+    stretch - and disp[v, u] there; (-1, 0) for a column without one.  An explicit walk, one column after the other."""
+    lab = np.asarray(labels)
+    d = np.asarray(disp, dtype=np.float32)
+    H, W = lab.shape
+    free_row, free_disp = np.full(W, -1, np.int32), np.zeros(W, np.float32)
+    for u in range(W):
+        run = 0
+        for v in range(H - 1, -1, -1):
+            run = run + 1 if lab[v, u] == 2 else 0
+            if run == min_run:
+                free_row[u], free_disp[u] = v + min_run - 1, d[v + min_run - 1, u]
+                break
+    return free_row, free_disp
+
+
+def ground(disp, disp_max=None, **spec):
+    """All of include/stereo_vision_hip.h (G) for one float32 map [H,W] in numpy: a dict with vdisp, ground (int32 [4] = vh, qb, S,
+    n_valid), labels, free_row and free_disp; spec as ground_params, min_support None = the width."""
+    d = np.asarray(disp, dtype=np.float32)
+    if d.ndim != 2:
+        raise ValueError("expected disp [H,W], got shape %s" % (d.shape,))
+    if spec.get("min_support") is None:
+        spec["min_support"] = d.shape[1]
+    p = ground_params(d.shape[0], disp_max, **spec)
+    vdisp = v_disparity(d, p["n_bins"])
+    rec = ground_line(vdisp, p["vh_lo"], p["vh_hi"], p["vh_step"], p["qb_step"], p["tol"], p["min_support"])
+    labels = ground_labels(d, p["n_bins"], rec[0], rec[1], p["g_tol"])
+    free_row, free_disp = free_space(labels, d, p["min_run"])
+    return {"vdisp": vdisp, "ground": np.array(rec, np.int32), "labels": labels, "free_row": free_row, "free_disp": free_disp}
+
+
+def ground_pose(Q, vh, qb, height):
+    """(height_m, pitch_rad, slope_px_per_row) of the camera over the ground line (vh, qb) of maps with `height` rows, in float64:
+    with f = Q[2][3], cy = -Q[1][3] and the baseline 1 / |Q[3][2]|, the line d(v) = slope (v - vh), slope = qb / (4 den) pixels of
+    disparity per row (den = height - 1 - vh), is a plane at height = baseline cos(pitch) / slope under a camera pitched by
+    pitch = atan((cy - vh) / f) (positive: looking down).  ValueError for "no ground" (qb < 1)."""
+    Q = np.asarray(Q, np.float64).reshape(4, 4)
+    den = int(height) - 1 - int(vh)
+    if qb < 1 or den < 1:
+        raise ValueError("no ground line: vh = %r, qb = %r at height %r" % (vh, qb, height))
+    f, cy, baseline = Q[2, 3], -Q[1, 3], 1.0 / abs(Q[3, 2])
+    slope = float(qb) / (4.0 * den)
+    pitch = float(np.arctan((cy - float(vh)) / f))
+    return float(baseline * np.cos(pitch) / slope), pitch, slope
+
+
+def free_space_points(Q, free_row, free_disp, XR=None, XT=None):
+    """float64 [W,3] ([B,W,3] for [B,W] input): the 3-D point of each column's obstacle base - reproject()'s arithmetic in its "d1"
+    form on pixel (u, free_row[u]) with disparity free_disp[u], then XR P + XT -, NaN where free_row < 0."""
+    row, d = np.asarray(free_row), np.asarray(free_disp, dtype=np.float32).astype(np.float64)
+    if row.shape != d.shape or row.ndim not in (1, 2):
+        raise ValueError("free_row and free_disp must both be [W] or [B,W], got %s / %s" % (row.shape, d.shape))
+    Q = np.asarray(Q, np.float64).reshape(4, 4)
+    x, y = np.broadcast_to(np.arange(row.shape[-1], dtype=np.float64), row.shape), row.astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        pos = [((Q[r, 0] * x + Q[r, 1] * y) + Q[r, 2] * d) + Q[r, 3] for r in range(4)]
+        X, Y, Z = pos[0] / pos[3], pos[1] / pos[3], pos[2] / pos[3]
+        if XR is not None or XT is not None:
+            XR = np.eye(3) if XR is None else np.asarray(XR, np.float64).reshape(3, 3)
+            XT = np.zeros(3) if XT is None else np.asarray(XT, np.float64).reshape(3)
+            X, Y, Z = [((XR[r, 0] * X + XR[r, 1] * Y) + XR[r, 2] * Z) + XT[r] for r in range(3)]
+    P = np.stack([X, Y, Z], -1)
+    P[row < 0] = np.nan
+    return P
 
 
 class stereo_vision:
