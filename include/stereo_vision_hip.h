@@ -34,6 +34,10 @@
  *      ground line fitted to it, a label per pixel and per column the base of the nearest obstacle, from disparity maps.  The reference
  *      has no counterpart; stereo_vision.sv states the definition in numpy.
  *
+ *  (H) Behind (G): the stixel world and detector-free object boxes (sv_stixel_*) - per image column the vertical segments of obstacle
+ *      pixels that stand at one disparity, and the groups of neighbouring columns whose nearest segments agree, as boxes in (E)'s layout.
+ *      The reference takes its boxes from a detector; stereo_vision.sv states this definition in numpy.
+ *
  * All sv_* functions return SV_OK (0) or a negative sv_status; sv_last_error() gives the text.
  * Nothing in this library calls exit().
  */
@@ -555,6 +559,78 @@ size_t sv_ground_workspace_bytes(const sv_ground_spec *spec, int batch, int widt
  * results are the same). */
 int sv_ground_disparity_device(const float *disp, int batch, int width, int height, const sv_ground_spec *spec, uint32_t *vdisp, int32_t *ground,
                                uint8_t *labels, int32_t *free_row, float *free_disp, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- (H) stixels and detector-free object boxes: disparity maps + obstacle labels -> segments per column, boxes per pair ---- */
+
+/* What stands on the ground as things: per visited image column the vertical segments ("stixels") of obstacle pixels that stay near
+ * the disparity of their own base, and objects grouped from the nearest segment of neighbouring columns, as boxes that
+ * sv_box_positions_* takes.  Integers only after the bin; the results are bitwise reproducible and independent of the batch, of the
+ * launch and of the other pairs.  stereo_vision.sv (stixels, stixel_objects, stixel_world) restates all of it in numpy.
+ *
+ *   foreground a pixel with labels == 2 (the obstacle label of (G)), d > 0 and q >= q_min, q = min(rintf(4.0f * d), n_bins - 1) - (G)'s
+ *              bin, the only floating-point operations.  The labels are the caller's data: a NaN or a -10 under a label 2 is not
+ *              foreground.  q_min drops what is too far to matter.
+ *   stixels    column u is visited iff u % col_step == 0; the visited columns are numbered i = u / col_step < Wv = ceil(width / col_step).
+ *              Walk the column from row height - 1 upwards.  At a foreground row v a run starts with base qb = q[v][u].  A row above
+ *              matches iff it is foreground and |q - qb| <= sim - against the base, not the neighbouring row, so a run cannot drift
+ *              along a slanted surface.  The run extends upwards over matching rows and bridges rows that do not match; it ends at the
+ *              image top or as soon as max_gap + 1 consecutive rows fail to match.  t = its last matching row (t = v if none matched),
+ *              n = the number of matching rows, the base included.  n >= min_rows makes the run a stixel
+ *              (v_bottom, v_top, q_base, n_rows) = (v, t, qb, n).  Either way the walk continues at row t - 1: bridged rows belong to
+ *              the run and are not visited again, rows above t that only ended the run are.  The stixels of a column are its layers
+ *              0, 1, ... bottom-up.  n_stixels[b][i] = the column's count, not capped; the first max_layers are stored in
+ *              stixels[b][layer][i][4], the entries of layers at and beyond the count are -1.
+ *   objects    from layer 0 alone - it is what bounds the free space.  An object is a maximal run of consecutive visited columns that
+ *              each have a layer-0 stixel and whose q_base differs from the previous visited column's by at most sim_cols; it is kept iff
+ *              it spans at least min_cols visited columns.  Kept objects are listed left to right, two rows of four int32 each:
+ *                boxes = (x, y, w, h) = (first column, smallest v_top, last column - first column + 1, largest v_bottom - y + 1), in
+ *                        pixels: the box layout of (E).  (E) never counts the map's last column and last row, so a box that reaches
+ *                        them loses them there.
+ *                info  = (n_cols, q_lo, q_hi, q_med): the visited columns, the smallest and the largest q_base and their lower median,
+ *                        by (E)'s rank rule - the smallest value whose cumulative count reaches (n_cols + 1) / 2.
+ *              counts[b] = the kept objects, not capped; the first min(counts[b], capacity) are written and the rows beyond are left
+ *              untouched, as sv_cloud_* does.  counts can be passed as n_boxes to sv_box_positions_disparity_device with
+ *              max_boxes = capacity: that kernel clamps it.
+ *   identity   with sim >= n_bins, q_min = 0, max_gap = 0, col_step = 1 and min_rows = (G)'s min_run on (G)'s own labels, v_bottom of
+ *              layer 0 equals free_row, -1 ("no stixel") included. */
+typedef struct sv_stixel_spec {
+    int32_t n_bins;      /* 8..4096; the value given to (G) */
+    int32_t q_min;       /* 0..4095: the least bin that is foreground */
+    int32_t sim;         /* 0..4096: rows of a run are within sim bins of its base */
+    int32_t max_gap;     /* 0..255: consecutive rows a run bridges */
+    int32_t min_rows;    /* >= 1: matching rows that make a run a stixel */
+    int32_t max_layers;  /* 1..64: stixels stored per column */
+    int32_t col_step;    /* >= 1: every col_step-th column is visited */
+    int32_t sim_cols;    /* 0..4096: neighbouring columns of an object are within sim_cols bins of each other */
+    int32_t min_cols;    /* >= 1: visited columns that make an object */
+    int32_t reserved[7]; /* must be 0 */
+} sv_stixel_spec;
+
+/* Bytes of device workspace a call needs (16 per visited column, per pair: the first layer; 0 for batch == 0).  Host only; SIZE_MAX
+ * for a bad spec, batch, width or height (the checks of the call below). */
+size_t sv_stixel_workspace_bytes(const sv_stixel_spec *spec, int batch, int width, int height);
+/* Enqueued on `stream` (a hipStream_t, NULL = the default stream) as two kernels - the columns' walk, the objects - and not waited for;
+ * nothing is allocated, no host synchronisation is made.  With Wv = ceil(width / col_step):
+ *   disp         : float [batch][height][width] device
+ *   labels       : uint8 [batch][height][width] device, as sv_ground_disparity_device writes them
+ *   stixels      : int32 [batch][max_layers][Wv][4] device, or NULL
+ *   n_stixels    : int32 [batch][Wv] device, or NULL
+ *   boxes        : int32 [batch][capacity][4] device, or NULL
+ *   info         : int32 [batch][capacity][4] device, or NULL
+ *   counts       : int32 [batch] device
+ *   workspace    : device, 16-byte aligned, workspace_bytes >= sv_stixel_workspace_bytes(spec, batch, width, height); its contents
+ *                  before and after the call mean nothing
+ * An output left out does not change the others.
+ * Returns SV_OK (nothing enqueued for batch == 0), SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued, the outputs untouched, the text in
+ * sv_last_error(NULL) - for: a NULL spec, disp, labels or counts; disp, n_stixels or counts not 4-byte aligned; stixels, boxes or info
+ * not 16-byte aligned (a record is stored as one 16-byte word); a spec word outside the range given beside it; a non-zero reserved
+ * word; capacity < 0; a workspace that is NULL, misaligned or too small; batch < 0 or > 65535; width < 1 or height < 1;
+ * height > 32768; width * height >= 2^31.  These checks run before any HIP call.
+ * The environment variable SV_STIXEL_STAGE=columns leaves the second kernel out (a measurement aid: boxes, info and counts are then
+ * not written). */
+int sv_stixel_disparity_device(const float *disp, const uint8_t *labels, int batch, int width, int height, const sv_stixel_spec *spec, int capacity,
+                               int32_t *stixels, int32_t *n_stixels, int32_t *boxes, int32_t *info, int32_t *counts, void *workspace,
+                               size_t workspace_bytes, void *stream);
 
 /* ---- (A) the reference's exported symbols ------------------------------------------------------------- */
 

@@ -883,6 +883,102 @@ def ground_from_disparity(disp, disp_max=None, n_bins=None, vh_lo=0, vh_hi=None,
     return res
 
 
+class SvStixelSpec(ctypes.Structure):
+    """sv_stixel_spec of include/stereo_vision_hip.h."""
+    _fields_ = [("n_bins", ctypes.c_int32), ("q_min", ctypes.c_int32), ("sim", ctypes.c_int32), ("max_gap", ctypes.c_int32),
+                ("min_rows", ctypes.c_int32), ("max_layers", ctypes.c_int32), ("col_step", ctypes.c_int32), ("sim_cols", ctypes.c_int32),
+                ("min_cols", ctypes.c_int32), ("reserved", ctypes.c_int32 * 7)]
+
+
+_stixel_bound = False
+
+
+def stixel_lib():
+    """The library with the sv_stixel_* signatures declared."""
+    global _stixel_bound
+    L = lib()
+    if not _stixel_bound:
+        vp, ci, sp = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(SvStixelSpec)
+        L.sv_stixel_workspace_bytes.argtypes = [sp, ci, ci, ci]
+        L.sv_stixel_workspace_bytes.restype = ctypes.c_size_t
+        L.sv_stixel_disparity_device.argtypes = [vp, vp, ci, ci, ci, sp, ci, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
+        L.sv_stixel_disparity_device.restype = ci
+        _stixel_bound = True
+    return L
+
+
+def stixel_spec(disp_max=None, n_bins=None, q_min=16, sim=6, max_gap=2, min_rows=8, max_layers=8, col_step=1, sim_cols=8, min_cols=16):
+    """-> SvStixelSpec; ValueError for a bad argument (the checks of the C entry, made in Python first:
+    stereo_vision.sv.stixel_params).  n_bins None = 4 (disp_max + 1), the bins ground_from_disparity uses for the same disp_max."""
+    from .stereo_vision.sv import stixel_params
+    p = stixel_params(disp_max, n_bins=n_bins, q_min=q_min, sim=sim, max_gap=max_gap, min_rows=min_rows, max_layers=max_layers, col_step=col_step,
+                      sim_cols=sim_cols, min_cols=min_cols)
+    spec = SvStixelSpec()
+    for k, v in p.items():
+        setattr(spec, k, v)
+    return spec
+
+
+class StixelResult:
+    """What stixels_from_disparity returns, tensors on the input's device, Wv = ceil(W / col_step) visited columns: stixels int32
+    [B,max_layers,Wv,4] = (v_bottom, v_top, q_base, n_rows) per column and layer, bottom-up, -1 beyond a column's count; n_stixels int32
+    [B,Wv], not capped; boxes int32 [B,capacity,4] = (x, y, w, h) and info int32 [B,capacity,4] = (n_cols, q_lo, q_hi, q_med) per object,
+    left to right, 0 in the rows at and beyond counts[b]; counts int32 [B], not capped by the capacity - None where not asked for - and
+    the spec in use.  StereoRig.objects adds positions (float64 [B,capacity,3] metres, NaN beyond counts) and ground (a GroundResult)."""
+    __slots__ = ("stixels", "n_stixels", "boxes", "info", "counts", "spec", "positions", "stat", "ground")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+def stixels_from_disparity(d1, labels, disp_max=None, n_bins=None, q_min=16, sim=6, max_gap=2, min_rows=8, max_layers=8, col_step=1, sim_cols=8,
+                           min_cols=16, capacity=64, want_stixels=True, want_objects=True):
+    """The stixel world and detector-free object boxes of disparity maps (CUDA float32 [B,H,W]; one frame [H,W] accepted) and their
+    obstacle labels (CUDA uint8, the same shape: ground_from_disparity's), the definition of stereo_vision.sv.stixels and
+    stixel_objects on the GPU, bit for bit.  Per visited column (every col_step-th) the runs of foreground rows - label 2, d > 0, bin
+    >= q_min - within sim bins of the run's bottom row, bridging up to max_gap rows, of at least min_rows rows; objects are runs of at
+    least min_cols visited columns whose first stixels are within sim_cols bins of their left neighbour's.  boxes / counts go straight
+    into box_positions_from_disparity(d1, Q, boxes, counts).  n_bins None = 4 (disp_max + 1), as for the labels.  -> StixelResult;
+    enqueued on torch's current stream, not waited for."""
+    import torch
+    if not (isinstance(d1, torch.Tensor) and d1.is_cuda and d1.dtype == torch.float32 and d1.dim() in (2, 3)):
+        raise ValueError("d1 must be a CUDA float32 tensor [B,H,W]")
+    if not (isinstance(labels, torch.Tensor) and labels.is_cuda and labels.dtype == torch.uint8 and labels.device == d1.device and
+            tuple(labels.shape) == tuple(d1.shape)):
+        raise ValueError("labels must be a CUDA uint8 tensor of d1's shape on d1's device")
+    d = (d1.unsqueeze(0) if d1.dim() == 2 else d1).contiguous()
+    lab = (labels.unsqueeze(0) if labels.dim() == 2 else labels).contiguous()
+    B, H, W = d.shape
+    if B > 65535 or H < 1 or W < 1 or H > 32768 or H * W >= 2 ** 31:
+        raise ValueError("at most 65535 pairs of 1 <= width * height < 2^31 pixels and at most 32768 rows, got %s" % (tuple(d.shape),))
+    if isinstance(capacity, bool) or int(capacity) != capacity or not 0 <= capacity < 2 ** 31:
+        raise ValueError("capacity must be an integer >= 0, got %r" % (capacity,))
+    capacity = int(capacity)
+    spec = stixel_spec(disp_max, n_bins, q_min, sim, max_gap, min_rows, max_layers, col_step, sim_cols, min_cols)
+    dev = d.device
+    Wv = -(-W // spec.col_step)
+    stixels = torch.empty((B, spec.max_layers, Wv, 4), dtype=torch.int32, device=dev) if want_stixels else None
+    n_stixels = torch.empty((B, Wv), dtype=torch.int32, device=dev) if want_stixels else None
+    boxes = torch.zeros((B, capacity, 4), dtype=torch.int32, device=dev) if want_objects else None  # the rows beyond counts are not written
+    info = torch.zeros((B, capacity, 4), dtype=torch.int32, device=dev) if want_objects else None
+    counts = torch.empty((B,), dtype=torch.int32, device=dev)
+    res = StixelResult(stixels=stixels, n_stixels=n_stixels, boxes=boxes, info=info, counts=counts, spec=spec)
+    if B == 0:  # nothing to enqueue
+        return res
+    L = stixel_lib()
+    nbytes = L.sv_stixel_workspace_bytes(ctypes.byref(spec), B, W, H)
+    ws = torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=dev)
+    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()  # noqa: E731
+    with torch.cuda.device(dev):
+        rc = L.sv_stixel_disparity_device(d.data_ptr(), lab.data_ptr(), B, W, H, ctypes.byref(spec), capacity, ptr(stixels), ptr(n_stixels), ptr(boxes),
+                                          ptr(info), counts.data_ptr(), ws.data_ptr(), nbytes, torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        msg = "sv_stixel_disparity_device failed (%d): %s" % (rc, (L.sv_last_error(None) or b"").decode())
+        raise ValueError(msg) if rc == -1 else StereoError(msg)
+    return res
+
+
 def host_support_filter(params, dcan, width, height, threads=0, lattice=False):
     """Product host stage: lattice filters + corner points (CPU by design; see csrc/host_stage.h).  threads > 0: the lattice shared between
     that many threads (what single-pair calls do); lattice=True: also return the filtered lattice."""

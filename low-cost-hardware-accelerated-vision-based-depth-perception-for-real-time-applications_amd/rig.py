@@ -12,6 +12,8 @@ disparity, the driver's 8-bit map and point clouds out.
     clouds = split_clouds(xyz, counts, color)                        # per frame (f32 [n,3] metres, BGRA u8 [n,4]), in pixel order
     g = rig.ground(left, right)                                      # g.ground [B,4] = (vh, qb, S, n_valid), g.labels u8 [B,H,W], g.free_row [B,W],
                                                                      # g.pose[b] = (height m, pitch rad, slope), g.points f64 [B,W,3] metres
+    o = rig.objects(left, right)                                     # no detector: o.boxes int32 [B,64,4] = (x, y, w, h), o.counts [B],
+                                                                     # o.positions f64 [B,64,3] metres, o.stixels int32 [B,layers,W,4]
 
 Frames are [B,Hs,Ws,C] (C = 4, 3, 3 for "bgra", "bgr", "rgb") or [B,Hs,Ws] for "gray"; one frame without B is accepted.
 Frames of another size than the rig's are resized to it.  CUDA tensors are processed on torch's current stream and CUDA
@@ -23,7 +25,8 @@ import ctypes
 import numpy as np
 
 from .engine import (SvParams, StereoEngine, StereoError, box_positions_from_disparity, box_spec, cloud_spec, compact_cloud_from_disparity,
-                     ground_from_disparity, ground_spec, lib, pinned_array, reproject, split_clouds, top_view_from_disparity, top_view_spec)
+                     ground_from_disparity, ground_spec, lib, pinned_array, reproject, split_clouds, stixel_spec, stixels_from_disparity,
+                     top_view_from_disparity, top_view_spec)
 from .stereo_vision.sv import CAMERA_TO_VEHICLE, DEFAULT_CALIBRATION  # noqa: F401 (CAMERA_TO_VEHICLE: re-exported for top_view)
 from .stereo_vision.sv import free_space_points, ground_pose
 
@@ -302,4 +305,43 @@ class StereoRig:
             res.ground, res.free_row, res.free_disp = rec, row, dsp
             res.vdisp = None if res.vdisp is None else res.vdisp.cpu().numpy()
             res.labels = None if res.labels is None else res.labels.cpu().numpy()
+        return res
+
+    def objects(self, left, right, pixel_format="bgr", transform=None, capacity=64, positions=True, **spec):
+        """What stands on the ground, as boxes with a 3-D position each and without a detector, for B pairs: front end, engine,
+        engine.ground_from_disparity (labels only), engine.stixels_from_disparity on the float disparity and those labels and, with
+        positions, engine.box_positions_from_disparity(select="near", disparity="d1") on the boxes and counts as they lie on the device -
+        nothing dense crosses the host link and nothing is waited for.  spec: the words of ground_from_disparity (vh_lo, vh_hi, vh_step,
+        qb_step, tol, g_tol, min_run, min_support) and of stixels_from_disparity (q_min, sim, max_gap, min_rows, max_layers, col_step,
+        sim_cols, min_cols); the bins follow the rig's disp_max.  -> engine.StixelResult with boxes, info int32 [B,capacity,4], counts
+        int32 [B] (not capped by the capacity), n_stixels, stixels, positions float64 [B,capacity,3] in metres (NaN at and beyond
+        counts[b]; None without positions), stat (box_positions' int32 [B,capacity,4]) and ground (the GroundResult).  transform as in
+        top_view: None (camera axes), "rig" or (XR, XT).  CUDA input: device tensors; numpy input: numpy arrays."""
+        if self.params.subsampling:
+            raise ValueError("objects does not support half-resolution maps (params.subsampling)")
+        if "disp_max" in spec or "n_bins" in spec:
+            raise ValueError("objects: disp_max and n_bins are not options of the rig (the bins follow the rig's disp_max)")
+        words = ("q_min", "sim", "max_gap", "min_rows", "max_layers", "col_step", "sim_cols", "min_cols")
+        mine = {k: spec.pop(k) for k in words if k in spec}
+        if spec.get("min_support") is None:
+            spec["min_support"] = self.width
+        ground_spec(self.height, self.params.disp_max, **spec)  # argument errors before any work
+        stixel_spec(self.params.disp_max, **mine)
+        if isinstance(capacity, bool) or int(capacity) != capacity or not 0 <= capacity <= 65535:
+            raise ValueError("capacity must be an integer in 0 .. 65535, got %r" % (capacity,))
+        XR, XT = self._transform(transform)
+        gl, gr, _, from_numpy = self._run_frontend(left, right, pixel_format, False)
+        d1, _ = self.engine.process_device(gl, gr, want_d2=False)
+        g = ground_from_disparity(d1, self.params.disp_max, want_vdisp=False, want_free=False, **spec)
+        res = stixels_from_disparity(d1, g.labels, self.params.disp_max, capacity=int(capacity), **mine)
+        res.ground = g
+        if positions and capacity == 0:  # no row to fill, and an empty tensor has no address to give
+            res.positions, res.stat = res.boxes.new_empty((d1.shape[0], 0, 3)).double(), res.boxes.new_empty((d1.shape[0], 0, 4))
+        elif positions:
+            res.positions, res.stat = box_positions_from_disparity(d1, self.Q, res.boxes, res.counts, XR=XR, XT=XT, select="near", disparity="d1")
+        if from_numpy:
+            for k in ("stixels", "n_stixels", "boxes", "info", "counts", "positions", "stat"):
+                t = getattr(res, k)
+                setattr(res, k, None if t is None else t.cpu().numpy())
+            g.ground, g.labels = g.ground.cpu().numpy(), g.labels.cpu().numpy()
         return res

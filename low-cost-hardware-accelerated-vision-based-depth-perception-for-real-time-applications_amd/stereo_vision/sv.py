@@ -517,6 +517,126 @@ def free_space_points(Q, free_row, free_disp, XR=None, XT=None):
     return P
 
 
+STIXEL_Q_MIN_MAX, STIXEL_SIM_MAX, STIXEL_GAP_MAX, STIXEL_LAYERS_MAX = 4095, 4096, 255, 64
+_STIXEL_WORDS = ("q_min", "sim", "max_gap", "min_rows", "max_layers", "col_step", "sim_cols", "min_cols")
+
+
+def stixel_params(disp_max=None, n_bins=None, q_min=16, sim=6, max_gap=2, min_rows=8, max_layers=8, col_step=1, sim_cols=8, min_cols=16):
+    """The nine words of sv_stixel_spec as a dict of ints, after the checks sv_stixel_disparity_device makes (ValueError for a bad
+    argument).  n_bins = 4 (disp_max + 1) unless given: 8 <= n_bins <= 4096; 0 <= q_min <= 4095; 0 <= sim <= 4096; 0 <= max_gap <= 255;
+    min_rows >= 1; 1 <= max_layers <= 64; col_step >= 1; 0 <= sim_cols <= 4096; min_cols >= 1."""
+    if n_bins is None:
+        if disp_max is None:
+            raise ValueError("give disp_max or n_bins")
+        n_bins = 4 * (int(disp_max) + 1)
+    p = dict(n_bins=n_bins, q_min=q_min, sim=sim, max_gap=max_gap, min_rows=min_rows, max_layers=max_layers, col_step=col_step, sim_cols=sim_cols,
+             min_cols=min_cols)
+    for k, v in p.items():
+        if isinstance(v, (bool, np.bool_)) or int(v) != v or not -2 ** 31 <= v < 2 ** 31:
+            raise ValueError("%s must be an int32, got %r" % (k, v))
+        p[k] = int(v)
+    if not GROUND_BINS_MIN <= p["n_bins"] <= GROUND_BINS_MAX:
+        raise ValueError("n_bins = %d outside %d .. %d" % (p["n_bins"], GROUND_BINS_MIN, GROUND_BINS_MAX))
+    if not 0 <= p["q_min"] <= STIXEL_Q_MIN_MAX:
+        raise ValueError("q_min must be in 0 .. %d, got %d" % (STIXEL_Q_MIN_MAX, p["q_min"]))
+    if not 0 <= p["sim"] <= STIXEL_SIM_MAX or not 0 <= p["sim_cols"] <= STIXEL_SIM_MAX:
+        raise ValueError("sim and sim_cols must be in 0 .. %d, got %d and %d" % (STIXEL_SIM_MAX, p["sim"], p["sim_cols"]))
+    if not 0 <= p["max_gap"] <= STIXEL_GAP_MAX:
+        raise ValueError("max_gap must be in 0 .. %d, got %d" % (STIXEL_GAP_MAX, p["max_gap"]))
+    if not 1 <= p["max_layers"] <= STIXEL_LAYERS_MAX:
+        raise ValueError("max_layers must be in 1 .. %d, got %d" % (STIXEL_LAYERS_MAX, p["max_layers"]))
+    if p["min_rows"] < 1 or p["col_step"] < 1 or p["min_cols"] < 1:
+        raise ValueError("min_rows, col_step and min_cols must be >= 1, got %d, %d and %d" % (p["min_rows"], p["col_step"], p["min_cols"]))
+    return p
+
+
+def stixels(disp, labels, disp_max=None, **spec):
+    """(stixels int32 [max_layers, Wv, 4], n_stixels int32 [Wv]) of one float32 map [H,W] and its labels uint8 [H,W]
+    (ground_labels'), Wv = ceil(W / col_step): the definition of include/stereo_vision_hip.h (H) as an explicit walk, one visited
+    column (u % col_step == 0) after the other.  A pixel is foreground iff its label is 2, d > 0 and q = ground_quantise's bin
+    >= q_min.  From row H - 1 upwards: a foreground row v starts a run with base qb = q[v]; a row above matches iff it is foreground
+    and |q - qb| <= sim (against the base, not the neighbour); the run ends at the top or after max_gap + 1 consecutive rows that
+    do not match; t = its last matching row, n = its matching rows.  n >= min_rows makes it a stixel (v, t, qb, n); the walk goes
+    on at row t - 1 either way.  The first max_layers stixels of a column, bottom-up, are stored, -1 beyond the column's count;
+    n_stixels is not capped.  spec as stixel_params (sim_cols and min_cols are not used here)."""
+    p = stixel_params(disp_max, **spec)
+    d, lab = np.asarray(disp, dtype=np.float32), np.asarray(labels)
+    if d.ndim != 2 or lab.shape != d.shape:
+        raise ValueError("expected disp [H,W] and labels of the same shape, got %s / %s" % (d.shape, lab.shape))
+    q, valid = ground_quantise(d, p["n_bins"])
+    q = np.where((lab == 2) & valid & (q >= p["q_min"]), q, -1)  # -1: not foreground
+    H, W = d.shape
+    cols = range(0, W, p["col_step"])
+    out, count = np.full((p["max_layers"], len(cols), 4), -1, np.int32), np.zeros(len(cols), np.int32)
+    for i, u in enumerate(cols):
+        c = q[:, u].tolist()
+        v = H - 1
+        while v >= 0:
+            if c[v] < 0:
+                v -= 1
+                continue
+            qb, t, n, gap, r = c[v], v, 1, 0, v - 1
+            while r >= 0 and gap <= p["max_gap"]:
+                if c[r] >= 0 and abs(c[r] - qb) <= p["sim"]:
+                    t, n, gap = r, n + 1, 0
+                else:
+                    gap += 1
+                r -= 1
+            if n >= p["min_rows"]:
+                if count[i] < p["max_layers"]:
+                    out[count[i], i] = (v, t, qb, n)
+                count[i] += 1
+            v = t - 1
+    return out, count
+
+
+def stixel_objects(layer0, col_step=1, sim_cols=8, min_cols=16, capacity=None):
+    """(boxes int32 [n,4], info int32 [n,4], count) from the first layer of stixels() ([Wv,4]): an object is a maximal run of
+    consecutive visited columns that each have a stixel and whose q_base differs from the previous visited column's by at most
+    sim_cols, kept iff it spans >= min_cols visited columns; left to right.  boxes = (x, y, w, h) = (first column, smallest v_top,
+    last column - first column + 1, largest v_bottom - y + 1) in pixels - the box layout of box_positions -, info = (n_cols, q_lo,
+    q_hi, q_med) with q_med the lower median of the columns' q_base (the smallest value whose cumulative count reaches
+    (n_cols + 1) // 2).  count is not capped; n = min(count, capacity) rows are returned (capacity None = all)."""
+    p = stixel_params(n_bins=GROUND_BINS_MIN, col_step=col_step, sim_cols=sim_cols, min_cols=min_cols)
+    if capacity is not None and (isinstance(capacity, bool) or int(capacity) != capacity or not 0 <= capacity < 2 ** 31):
+        raise ValueError("capacity must be an integer >= 0, got %r" % (capacity,))
+    s = np.asarray(layer0)
+    if s.ndim != 2 or s.shape[1] != 4:
+        raise ValueError("expected the first layer of stixels [Wv,4], got shape %s" % (s.shape,))
+    boxes, info = [], []
+    i, n = 0, s.shape[0]
+    while i < n:
+        if s[i, 0] < 0:
+            i += 1
+            continue
+        j = i
+        while j + 1 < n and s[j + 1, 0] >= 0 and abs(int(s[j + 1, 2]) - int(s[j, 2])) <= p["sim_cols"]:
+            j += 1
+        if j - i + 1 >= p["min_cols"]:
+            seg = s[i:j + 1].astype(np.int64)
+            y = int(seg[:, 1].min())
+            qs = np.sort(seg[:, 2])
+            boxes.append((i * p["col_step"], y, (j - i) * p["col_step"] + 1, int(seg[:, 0].max()) - y + 1))
+            info.append((j - i + 1, int(qs[0]), int(qs[-1]), int(qs[(len(qs) + 1) // 2 - 1])))
+        i = j + 1
+    count = len(boxes)
+    keep = count if capacity is None else min(count, int(capacity))
+    return np.array(boxes[:keep], np.int32).reshape(keep, 4), np.array(info[:keep], np.int32).reshape(keep, 4), count
+
+
+def stixel_world(disp, disp_max=None, capacity=None, **spec):
+    """ground() first, then stixels() on its labels and stixel_objects() on their first layer, for one float32 map [H,W]: ground()'s
+    dict plus stixels, n_stixels, boxes, info and count.  spec: the words of ground_params and of stixel_params (n_bins is shared)."""
+    d = np.asarray(disp, dtype=np.float32)
+    mine = {k: spec.pop(k) for k in _STIXEL_WORDS if k in spec}
+    out = ground(d, disp_max, **spec)
+    mine["n_bins"] = out["vdisp"].shape[1]
+    out["stixels"], out["n_stixels"] = stixels(d, out["labels"], **mine)
+    p = stixel_params(**mine)
+    out["boxes"], out["info"], out["count"] = stixel_objects(out["stixels"][0], p["col_step"], p["sim_cols"], p["min_cols"], capacity)
+    return out
+
+
 class stereo_vision:
     def __init__(self, so_lib_path=DEFAULT_STEREO_VISION_SO_PATH, width=1242, height=375, defaultCalibFile=True, objectTracking=True,
                  graphics=False, display=False, scale=1, pc_extrapolation=1, YOLO_CFG="src/yolo/yolov4-tiny.cfg",
