@@ -38,6 +38,10 @@
  *      pixels that stand at one disparity, and the groups of neighbouring columns whose nearest segments agree, as boxes in (E)'s layout.
  *      The reference takes its boxes from a detector; stereo_vision.sv states this definition in numpy.
  *
+ *  (I) Behind (B) as well: voxel-grid downsampled clouds (sv_voxel_*) - per pair one row per occupied cell of a regular 3-D grid over
+ *      (F)'s points: the centroid, the mean colour and the number of points, in the order a scan of the image meets the cells, from
+ *      disparity maps (fused: neither a dense cloud nor the list of points is written).  stereo_vision.sv states the definition in numpy.
+ *
  * All sv_* functions return SV_OK (0) or a negative sv_status; sv_last_error() gives the text.
  * Nothing in this library calls exit().
  */
@@ -631,6 +635,82 @@ size_t sv_stixel_workspace_bytes(const sv_stixel_spec *spec, int batch, int widt
 int sv_stixel_disparity_device(const float *disp, const uint8_t *labels, int batch, int width, int height, const sv_stixel_spec *spec, int capacity,
                                int32_t *stixels, int32_t *n_stixels, int32_t *boxes, int32_t *info, int32_t *counts, void *workspace,
                                size_t workspace_bytes, void *stream);
+
+/* ---- (I) voxel clouds: disparity maps (+ colour images) -> one row per occupied cell of a 3-D grid, per pair ------------------- */
+
+/* What registration, mapping, an occupancy grid or a planner takes instead of (F)'s list: a voxel-grid filter over it, fused with it.
+ * The grid covers the crop box with cubic cells of edge `size`; unlike (F) the crop is finite.  Per axis k it has
+ * n_k = max(1, (int64)ceil((hi_k - lo_k) / size)) cells, at most 2^20 (a cell index fits an int32, the three of them 60 bits).
+ *
+ *   kept pixels  exactly (F)'s: the visited pixels (x % step == 0 && y % step == 0, ascending flat index y * width + x), the candidate
+ *                rule of spec->disparity, P = reproject(x, y, .) in double without FMA, the transform included; kept iff lo < P < hi
+ *                strictly on all three axes.
+ *   cell         of a kept point, per axis, in double and in this order: t = (P - lo) / size; c = min((int64)t, n - 1);
+ *                u = min((int64)((t - (double)c) * 65536.0), 65535) - the offset inside the cell in 1/65536 of its edge.  t >= c >= 0,
+ *                so nothing is negative; the two min catch a quotient that rounds up onto n.
+ *   voxel        the kept points of a frame with equal (c_x, c_y, c_z).  Per voxel: n = its points, first = the smallest flat pixel
+ *                index among them, S_k = sum of u_k and, with colours, C_j = sum of channel j.  All are integers: n and first have 32
+ *                bits (width * height < 2^31), S_k <= 65535 n < 2^47 and C_j <= 255 n < 2^39 have 64, so no admitted map overflows them
+ *                and the sums do not depend on the order in which the points are met.
+ *   rows         a frame's voxels in ascending `first` - the order in which a scan of the image meets them, so a prefix of the list is
+ *                the voxels of a prefix of the image.  A row is
+ *     xyz[3]     m_k = lo_k + ((double)c_k + ((double)S_k + 0.5 * (double)n) / (65536.0 * (double)n)) * size, evaluated in double as
+ *                written, no FMA; SV_CLOUD_F32 stores (float)m_k.  It is the centroid with each point's offset truncated to 1/65536 of
+ *                the cell and re-centred: |m_k - true mean| <= size * 2^-17, plus double rounding.
+ *     cell[3]    int32 c; n int32; first int32 (each optional)
+ *     color[4]   uint8 (2 C_j + n) / (2 n) per channel, integer division: the mean rounded half up (optional; needs colors)
+ *   counts[b]    the number V of voxels of frame b if V <= capacity, and -1 if V > capacity: raise the capacity; the frame's rows then
+ *                mean nothing.  A function of the input alone.  It is deliberately not (F)'s uncapped count: the table that finds the
+ *                voxels is sized by the capacity.  Rows at and beyond counts[b] are left untouched.
+ * The result of a frame is bitwise reproducible and independent of the batch it sits in, of the launch, of the other frames and of
+ * repetition.  stereo_vision.sv.voxel_cloud restates all of it in numpy. */
+typedef struct sv_voxel_spec {
+    double lo[3], hi[3];  /* finite, lo < hi per axis */
+    double size;          /* finite, > 0: the edge of a cell; ceil((hi - lo) / size) <= 2^20 per axis */
+    int32_t disparity;    /* SV_CLOUD_DMAP / SV_CLOUD_D1 */
+    int32_t step;         /* >= 1: every step-th column and row */
+    int32_t dtype;        /* SV_CLOUD_F32 / SV_CLOUD_F64 */
+    int32_t reserved[5];  /* must be 0 */
+} sv_voxel_spec;
+
+/* Entries of the open-addressing table a pair gets for `capacity` rows: the power of two >= 2 * max(capacity, 512), 72 bytes each;
+ * -1 for a capacity outside 1 .. 2^26. */
+int64_t sv_voxel_table_slots(int capacity);
+/* Bytes of device workspace a call needs: per pair the table, 16 bytes of counters and one bit per visited pixel (padded to 16 bytes),
+ * then (F)'s 4 bytes per tile and pair; 0 for batch == 0.  Host only; SIZE_MAX for a bad spec, batch, width, height or capacity (the
+ * checks of the call below). */
+size_t sv_voxel_workspace_bytes(const sv_voxel_spec *spec, int batch, int width, int height, int capacity);
+/* Enqueued on `stream` (a hipStream_t, NULL = the default stream) as six kernels - clear the tables, insert the points, mark each
+ * voxel's first pixel, count the marks per tile, (F)'s scan per frame, write the rows - and not waited for; nothing is allocated, no
+ * host synchronisation is made.
+ *   disp         : float [batch][height][width] device; width * height < 2^31
+ *   colors       : uint8 [batch][height][width][4] device, 4-byte aligned, or NULL
+ *   Q16, XR9, XT3: HOST, as for sv_reproject_batch_device (XR9 and XT3 both NULL = no transform)
+ *   capacity     : rows per pair of the outputs, 1 .. 2^26
+ *   xyz          : float or double [batch][capacity][3] device
+ *   color_out    : uint8 [batch][capacity][4] device, 4-byte aligned, or NULL; needs colors
+ *   cell_out     : int32 [batch][capacity][3] device, or NULL
+ *   n_out        : int32 [batch][capacity] device, or NULL
+ *   first_out    : int32 [batch][capacity] device, or NULL
+ *   counts       : int32 [batch] device
+ *   workspace    : device, 16-byte aligned, workspace_bytes >= sv_voxel_workspace_bytes(spec, batch, width, height, capacity); its
+ *                  contents before and after the call mean nothing
+ * An output left out does not change the others.
+ * Returns SV_OK (nothing enqueued for batch == 0), SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued, the outputs untouched, the text in
+ * sv_last_error(NULL) - for: a NULL spec, disp, Q16, counts or xyz; color_out without colors; colors or color_out not 4-byte aligned;
+ * disparity or dtype out of range; step < 1; a bound of the crop that is not finite; lo >= hi; a size that is not finite or <= 0; more
+ * than 2^20 cells on an axis; a non-zero reserved word; capacity < 1 or > 2^26; a workspace that is NULL, misaligned or too small;
+ * batch < 0 or > 65535; width < 1 or height < 1; width * height >= 2^31.  These checks run before any HIP call.
+ * The environment variable SV_VOXEL_STAGE = clear, insert, mark or scan leaves out the kernels behind that stage (a measurement aid:
+ * the rows, and before "scan" the counts, are then not written). */
+int sv_voxel_disparity_device(const float *disp, const uint8_t *colors, int batch, int width, int height, const double *Q16, const double *XR9,
+                              const double *XT3, const sv_voxel_spec *spec, int capacity, void *xyz, uint8_t *color_out, int32_t *cell_out, int32_t *n_out,
+                              int32_t *first_out, int32_t *counts, void *workspace, size_t workspace_bytes, void *stream);
+/* Test hook for the call above, process-wide: combine != 0 (the default) merges the lanes of a wavefront that hold neighbouring
+ * pixels of one cell into one table update; counters_device != NULL: a device uint64 [2] that receives [0] the table updates issued
+ * (without the merge: one per kept point) and [1] the atomic instructions issued for them (per update one compare-and-swap per probed
+ * slot, 5 or, with colours, 9 sums, and 1 or 2 for a claimed slot).  The results do not depend on it.  Returns SV_OK. */
+int sv_debug_voxel(int combine, unsigned long long *counters_device);
 
 /* ---- (A) the reference's exported symbols ------------------------------------------------------------- */
 

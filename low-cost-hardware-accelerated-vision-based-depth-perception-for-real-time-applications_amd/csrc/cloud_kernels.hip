@@ -25,56 +25,6 @@ namespace sv {
 
 namespace {
 
-// The lane's four visited pixels v0 .. v0 + 3 (those < n_visited): bit k of the result = pixel k is kept; pix[k] = its flat index,
-// P[k] = its point (read only where the bit is set).
-template <int SRC>
-__device__ __forceinline__ unsigned cloud_quad(const CloudArgs &a, const float *frame, bool vec_ok, uint32_t v0, int *pix, double (*P)[3]) {
-    const uint32_t n = (uint32_t)a.n_visited;
-    if (v0 >= n) return 0u;
-    const uint32_t vy = v0 / (uint32_t)a.Wv;
-    int vx = (int)(v0 - vy * (uint32_t)a.Wv), x[CLOUD_QUAD], y[CLOUD_QUAD];
-    int cx = vx * a.step, cy = (int)vy * a.step;  // <= W - 1, H - 1
-    const int have = n - v0 < (uint32_t)CLOUD_QUAD ? (int)(n - v0) : CLOUD_QUAD;
-#pragma unroll
-    for (int k = 0; k < CLOUD_QUAD; k++) {
-        x[k] = cx, y[k] = cy;
-        pix[k] = k < have ? cy * a.W + cx : 0;  // < W * H
-        if (k + 1 < have) {                      // the next pixel exists: cx <= W - 1, cy <= H - 1 whatever the step
-            if (++vx == a.Wv) vx = 0, cx = 0, cy += a.step;
-            else cx += a.step;
-        }
-    }
-    float dv[CLOUD_QUAD];
-    if (vec_ok && have == CLOUD_QUAD) {  // step 1: pix[k] = v0 + k, v0 % 4 == 0
-        const float4 f = *reinterpret_cast<const float4 *>(frame + v0);
-        dv[0] = f.x, dv[1] = f.y, dv[2] = f.z, dv[3] = f.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < CLOUD_QUAD; k++) dv[k] = k < have ? frame[pix[k]] : 0.f;  // 0 is no candidate
-    }
-    unsigned keep = 0u;
-#pragma unroll
-    for (int k = 0; k < CLOUD_QUAD; k++) {
-        double d;
-        bool cand;
-        if (SRC == CLOUD_SRC_DMAP) {
-            const int q = sv_dmap_u8(dv[k]);
-            cand = q > 0, d = (double)q;
-        } else {
-            cand = dv[k] > 0.f, d = (double)dv[k];  // NaN is no candidate
-        }
-        if (cand) {
-            double X, Y, Z;
-            sv_reproject_point(a.rp, (double)x[k], (double)y[k], d, X, Y, Z);
-            if (a.lo[0] < X && X < a.hi[0] && a.lo[1] < Y && Y < a.hi[1] && a.lo[2] < Z && Z < a.hi[2]) {
-                keep |= 1u << k;
-                P[k][0] = X, P[k][1] = Y, P[k][2] = Z;
-            }
-        }
-    }
-    return keep;
-}
-
 __device__ __forceinline__ int lanes_below(unsigned long long mask) {
     return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
 }

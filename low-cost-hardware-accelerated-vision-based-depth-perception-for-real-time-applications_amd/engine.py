@@ -795,6 +795,120 @@ def split_clouds(xyz, counts, *others):
     return out
 
 
+class SvVoxelSpec(ctypes.Structure):
+    """sv_voxel_spec of include/stereo_vision_hip.h."""
+    _fields_ = [("lo", ctypes.c_double * 3), ("hi", ctypes.c_double * 3), ("size", ctypes.c_double), ("disparity", ctypes.c_int32),
+                ("step", ctypes.c_int32), ("dtype", ctypes.c_int32), ("reserved", ctypes.c_int32 * 5)]
+
+
+_voxel_bound = False
+
+
+def voxel_lib():
+    """The library with the sv_voxel_* signatures declared."""
+    global _voxel_bound
+    L = cloud_lib()
+    if not _voxel_bound:
+        vp, ci, sp = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(SvVoxelSpec)
+        L.sv_voxel_table_slots.argtypes = [ci]
+        L.sv_voxel_table_slots.restype = ctypes.c_int64
+        L.sv_voxel_workspace_bytes.argtypes = [sp, ci, ci, ci, ci]
+        L.sv_voxel_workspace_bytes.restype = ctypes.c_size_t
+        L.sv_voxel_disparity_device.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp, sp, ci, vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
+        L.sv_voxel_disparity_device.restype = ci
+        L.sv_debug_voxel.argtypes = [ci, vp]
+        L.sv_debug_voxel.restype = ci
+        _voxel_bound = True
+    return L
+
+
+def voxel_spec(size, lo, hi, step=1, disparity="d1", dtype="f32", capacity=None):
+    """-> SvVoxelSpec; ValueError for a bad argument (the checks of the C entry, made in Python first)."""
+    from .stereo_vision.sv import CLOUD_DISPARITY, CLOUD_DTYPES, voxel_grid
+    lo, hi, size, _ = voxel_grid(size, lo, hi, step, disparity, dtype, capacity)
+    spec = SvVoxelSpec()
+    spec.lo[:] = lo.tolist()
+    spec.hi[:] = hi.tolist()
+    spec.size, spec.disparity, spec.step, spec.dtype = size, CLOUD_DISPARITY[disparity], int(step), CLOUD_DTYPES[dtype]
+    return spec
+
+
+def voxel_cloud_from_disparity(d1, Q, size, lo, hi, colors=None, XR=None, XT=None, step=1, disparity="d1", dtype="f32", capacity=None,
+                               want_cell=False, want_n=True, want_first=False):
+    """Voxel-grid downsampled clouds straight from disparity maps (CUDA float32 [B,H,W]; one frame [H,W] accepted): the points
+    compact_cloud_from_disparity would list (same d1, Q, XR / XT, step, disparity; the crop lo < P < hi must be finite), gathered per
+    cubic cell of edge `size`: one row per occupied cell with its centroid, the mean colour and the number of points, in the order a
+    scan of the image meets the cells.  Neither a dense cloud nor the list of points is written.  colors: CUDA uint8 [B,H,W,4] or None.
+    Returns (xyz [B,capacity,3] float32 or float64 ("f64"), color uint8 [B,capacity,4] or None, cell int32 [B,capacity,3] or None
+    (want_cell), n int32 [B,capacity] or None (want_n), first int32 [B,capacity] = the smallest y * W + x of the voxel or None
+    (want_first), counts int32 [B]): frame b's first counts[b] rows equal stereo_vision.sv.voxel_cloud's, bit for bit; counts[b] is -1
+    for a frame with more voxels than `capacity` (its rows mean nothing: raise the capacity); rows at and beyond counts[b] are
+    undefined.  capacity None = the number of visited pixels (at most 2^26), which cannot overflow - but the workspace holds a table of
+    sv_voxel_table_slots(capacity) entries of 72 bytes PER PAIR, 75 MB for a 1242 x 375 map, and every call clears it: a caller with
+    a batch passes a capacity a little above the voxels a frame can have.  CUDA tensors on the input's device, enqueued on torch's
+    current stream (not waited for); split_voxel_clouds cuts them."""
+    import torch
+    spec = voxel_spec(size, lo, hi, step, disparity, dtype, capacity)
+    if not (isinstance(d1, torch.Tensor) and d1.is_cuda and d1.dtype == torch.float32 and d1.dim() in (2, 3)):
+        raise ValueError("d1 must be a CUDA float32 tensor [B,H,W]")
+    d1 = (d1.unsqueeze(0) if d1.dim() == 2 else d1).contiguous()
+    B, H, W = d1.shape
+    if B > 65535 or H < 1 or W < 1 or H * W >= 2 ** 31:
+        raise ValueError("at most 65535 pairs of 1 <= width * height < 2^31 pixels, got %s" % (tuple(d1.shape),))
+    if colors is not None:
+        if not (isinstance(colors, torch.Tensor) and colors.is_cuda and colors.dtype == torch.uint8 and colors.device == d1.device):
+            raise ValueError("colors must be a CUDA uint8 tensor [B,H,W,4] on d1's device")
+        colors = (colors.unsqueeze(0) if colors.dim() == 3 else colors).contiguous()
+        if tuple(colors.shape) != (B, H, W, 4):
+            raise ValueError("colors must be [B,H,W,4] matching d1 %s, got %s" % (tuple(d1.shape), tuple(colors.shape)))
+        if colors.data_ptr() % 4:  # a view at an odd storage offset: the C entry moves a pixel as one dword
+            colors = colors.clone()
+    if capacity is None:
+        capacity = min(-(-W // int(step)) * -(-H // int(step)), 2 ** 26)
+    capacity = int(capacity)
+    q = np.ascontiguousarray(Q, dtype=np.float64).reshape(16)
+    xr = None if XR is None else np.ascontiguousarray(XR, dtype=np.float64).reshape(9)
+    xt = None if XT is None else np.ascontiguousarray(XT, dtype=np.float64).reshape(3)
+    dev = d1.device
+    xyz = torch.empty((B, capacity, 3), dtype=torch.float32 if dtype == "f32" else torch.float64, device=dev)
+    color = torch.empty((B, capacity, 4), dtype=torch.uint8, device=dev) if colors is not None else None
+    cell = torch.empty((B, capacity, 3), dtype=torch.int32, device=dev) if want_cell else None
+    n = torch.empty((B, capacity), dtype=torch.int32, device=dev) if want_n else None
+    first = torch.empty((B, capacity), dtype=torch.int32, device=dev) if want_first else None
+    counts = torch.empty((B,), dtype=torch.int32, device=dev)  # the scan kernel writes every entry
+    if B == 0:  # nothing to enqueue
+        return xyz, color, cell, n, first, counts
+    L = voxel_lib()
+    nbytes = L.sv_voxel_workspace_bytes(ctypes.byref(spec), B, W, H, capacity)
+    if nbytes == ctypes.c_size_t(-1).value:
+        raise ValueError("sv_voxel_workspace_bytes refused the request")
+    ws = torch.empty(((nbytes + 15) // 16, 2), dtype=torch.int64, device=dev)  # torch's allocations start on 512 bytes
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    with torch.cuda.device(dev):
+        rc = L.sv_voxel_disparity_device(d1.data_ptr(), ptr(colors), B, W, H, q.ctypes.data, xr.ctypes.data if xr is not None else None,
+                                         xt.ctypes.data if xt is not None else None, ctypes.byref(spec), capacity, xyz.data_ptr(), ptr(color), ptr(cell),
+                                         ptr(n), ptr(first), counts.data_ptr(), ws.data_ptr(), nbytes, torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        msg = "sv_voxel_disparity_device failed (%d): %s" % (rc, (L.sv_last_error(None) or b"").decode())
+        raise ValueError(msg) if rc == -1 else StereoError(msg)
+    return xyz, color, cell, n, first, counts
+
+
+def split_voxel_clouds(xyz, counts, *others):
+    """split_clouds for voxel_cloud_from_disparity's padded tensors: per-frame views cut at counts[b].  Raises StereoError for a frame
+    whose count is -1 (more voxels than the capacity: its rows mean nothing).  Reads counts on the host: the one place that synchronises."""
+    over = [b for b, k in enumerate(counts.cpu().tolist()) if k < 0]
+    if over:
+        raise StereoError("frames %s hold more voxels than the capacity of %d rows: raise the capacity" % (over, xyz.shape[1]))
+    return split_clouds(xyz, counts, *others)
+
+
+def debug_voxel(combine=True, counters=None):
+    """sv_debug_voxel: the wavefront merge of the insert kernel on / off and a CUDA int64 [2] tensor (or None) that receives the table
+    updates and the atomic instructions issued.  Process-wide; a test hook."""
+    return int(voxel_lib().sv_debug_voxel(1 if combine else 0, None if counters is None else counters.data_ptr()))
+
+
 class SvGroundSpec(ctypes.Structure):
     """sv_ground_spec of include/stereo_vision_hip.h."""
     _fields_ = [("n_bins", ctypes.c_int32), ("vh_lo", ctypes.c_int32), ("vh_hi", ctypes.c_int32), ("vh_step", ctypes.c_int32),

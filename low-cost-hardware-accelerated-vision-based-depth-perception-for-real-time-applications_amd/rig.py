@@ -10,6 +10,8 @@ disparity, the driver's 8-bit map and point clouds out.
     pos, stat = rig.box_positions(left, right, boxes, n_boxes)       # f64 [B,M,3] metres, int32 [B,M,4]
     xyz, color, counts = rig.compact_clouds(left, right, lo=(0, -20, -1.4), hi=(40, 20, 1.0), transform=(CAMERA_TO_VEHICLE, None))
     clouds = split_clouds(xyz, counts, color)                        # per frame (f32 [n,3] metres, BGRA u8 [n,4]), in pixel order
+    xyz, color, n, counts = rig.voxel_clouds(left, right, 0.1, (0, -20, -1.4), (40, 20, 1.0), transform=(CAMERA_TO_VEHICLE, None), capacity=65536)
+    voxels = split_voxel_clouds(xyz, counts, color, n)               # per frame (centroids f32 [V,3], mean BGRA u8 [V,4], points per voxel)
     g = rig.ground(left, right)                                      # g.ground [B,4] = (vh, qb, S, n_valid), g.labels u8 [B,H,W], g.free_row [B,W],
                                                                      # g.pose[b] = (height m, pitch rad, slope), g.points f64 [B,W,3] metres
     o = rig.objects(left, right)                                     # no detector: o.boxes int32 [B,64,4] = (x, y, w, h), o.counts [B],
@@ -26,7 +28,7 @@ import numpy as np
 
 from .engine import (SvParams, StereoEngine, StereoError, box_positions_from_disparity, box_spec, cloud_spec, compact_cloud_from_disparity,
                      ground_from_disparity, ground_spec, lib, pinned_array, reproject, split_clouds, stixel_spec, stixels_from_disparity,
-                     top_view_from_disparity, top_view_spec)
+                     top_view_from_disparity, top_view_spec, split_voxel_clouds, voxel_cloud_from_disparity, voxel_spec)
 from .stereo_vision.sv import CAMERA_TO_VEHICLE, DEFAULT_CALIBRATION  # noqa: F401 (CAMERA_TO_VEHICLE: re-exported for top_view)
 from .stereo_vision.sv import free_space_points, ground_pose
 
@@ -276,6 +278,30 @@ class StereoRig:
         if not from_numpy:
             return xyz, color, counts
         return [(p.cpu().numpy(), None if c is None else c.cpu().numpy()) for p, c in split_clouds(xyz, counts, color)]
+
+    def voxel_clouds(self, left, right, size, lo, hi, pixel_format="bgr", step=1, disparity="d1", dtype="f32", transform=None, capacity=None,
+                     colors=True):
+        """Voxel-grid downsampled coloured clouds of B pairs - what registration, a map or a planner takes instead of compact_clouds'
+        lists: front end (with colours), engine, then the fused disparity -> voxel cloud kernels; neither a dense cloud nor the list
+        of points is written.  One row per occupied cubic cell of edge `size` (metres with disparity "d1") of the finite crop
+        lo < P < hi: the centroid, the mean colour and the number of points, in the order a scan of the image meets the cells.  step,
+        disparity, dtype, transform as in compact_clouds; the crop applies after the transform.
+        CUDA input: (xyz [B,capacity,3] float32 or float64 ("f64"), color BGRA uint8 [B,capacity,4] or None (colors=False), n int32
+        [B,capacity], counts int32 [B]) as engine.voxel_cloud_from_disparity - counts[b] = -1 for a frame with more voxels than
+        capacity (None = the visited pixels: no overflow, but a large workspace per pair - pass one for batches), rows at and beyond
+        counts[b] are undefined, nothing is waited for; engine.split_voxel_clouds cuts them.  numpy input: a list of per-frame
+        (xyz [V,3], color [V,4] or None, n [V]) numpy arrays."""
+        if self.params.subsampling:
+            raise ValueError("voxel_clouds does not support half-resolution maps (params.subsampling)")
+        voxel_spec(size, lo, hi, step, disparity, dtype, capacity)  # argument errors before any work
+        XR, XT = self._transform(transform)
+        gl, gr, col, from_numpy = self._run_frontend(left, right, pixel_format, bool(colors))
+        d1, _ = self.engine.process_device(gl, gr, want_d2=False)
+        xyz, color, _, n, _, counts = voxel_cloud_from_disparity(d1, self.Q, size, lo, hi, colors=col, XR=XR, XT=XT, step=step, disparity=disparity,
+                                                                 dtype=dtype, capacity=capacity)
+        if not from_numpy:
+            return xyz, color, n, counts
+        return [(p.cpu().numpy(), None if c is None else c.cpu().numpy(), k.cpu().numpy()) for p, c, k in split_voxel_clouds(xyz, counts, color, n)]
 
     def ground(self, left, right, pixel_format="bgr", transform=None, **spec):
         """Where the ground is, what stands on it and how far one can go in each image column, for B pairs: front end, engine, then

@@ -30,6 +30,11 @@ engine.compact_cloud_from_disparity / rig.StereoRig.compact_clouds on the GPU): 
 pixel order with their colours and pixel indices - the pairing of points[i] with colors[i] the reference's viewer draws
 (src/common_includes/graphing.h:123-133).  write_ply stores one as a binary PLY file.
 
+voxel_cloud is the definition of the voxel-grid downsampled clouds (sv_voxel_* of include/stereo_vision_hip.h (I);
+engine.voxel_cloud_from_disparity / rig.StereoRig.voxel_clouds on the GPU): compact_cloud's points gathered per cell of a regular 3-D
+grid - centroid, mean colour, number of points - with integer sums only, so that the result does not depend on any order.  The reference
+has no counterpart.
+
 v_disparity, ground_line, ground_labels, free_space (together: ground), ground_pose and free_space_points are the definition of the ground
 plane, obstacle labels and free space (sv_ground_* of include/stereo_vision_hip.h (G); engine.ground_from_disparity /
 rig.StereoRig.ground on the GPU): Labayrade's v-disparity line fit in integers and a per-column scan for the nearest obstacle.  The
@@ -341,6 +346,90 @@ def write_ply(path, xyz, color=None):
     with open(path, "wb") as f:
         f.write(("\n".join(header + ["end_header"]) + "\n").encode("ascii"))
         f.write(rec.tobytes())
+
+
+VOXEL_CELLS_MAX = 2 ** 20      # cells per axis: a cell index fits an int32, the packed key 60 bits
+VOXEL_CAPACITY_MAX = 2 ** 26   # rows per pair the C entry takes
+VOXEL_MIN_CAPACITY = 512       # the table is never smaller than for this capacity
+
+
+def voxel_grid(size, lo, hi, step=1, disparity="d1", dtype="f32", capacity=None):
+    """(lo float64 [3], hi float64 [3], size float, cells int64 [3]) of a voxel-cloud request after the checks
+    sv_voxel_disparity_device makes (ValueError for a bad argument): compact_cloud's, and lo / hi / size finite, lo < hi, size > 0,
+    cells[k] = max(1, ceil((hi[k] - lo[k]) / size)) <= 2^20, capacity None or an integer in 1 .. 2^26."""
+    if lo is None or hi is None:
+        raise ValueError("a voxel cloud needs a finite crop: lo and hi")
+    lo, hi = cloud_crop(lo, hi, step, disparity, dtype)
+    try:
+        size = float(size)
+    except (TypeError, ValueError):
+        raise ValueError("size must be a number, got %r" % (size,))
+    if not (np.isfinite(size) and size > 0):
+        raise ValueError("size must be finite and > 0, got %r" % (size,))
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+        raise ValueError("the crop of a voxel cloud must be finite, got %r / %r" % (lo.tolist(), hi.tolist()))
+    with np.errstate(over="ignore"):
+        cells = np.ceil((hi - lo) / np.float64(size))
+    if not (cells <= VOXEL_CELLS_MAX).all():
+        raise ValueError("more than 2^20 cells on an axis: %r" % (cells.tolist(),))
+    if capacity is not None and (isinstance(capacity, bool) or int(capacity) != capacity or not 1 <= capacity <= VOXEL_CAPACITY_MAX):
+        raise ValueError("capacity must be an integer in 1 .. 2^26, got %r" % (capacity,))
+    return lo, hi, size, np.maximum(cells, 1).astype(np.int64)
+
+
+def voxel_table_slots(capacity):
+    """Entries of the table sv_voxel_disparity_device uses per pair (sv_voxel_table_slots): the power of two >= 2 * max(capacity, 512)."""
+    if isinstance(capacity, bool) or int(capacity) != capacity or not 1 <= capacity <= VOXEL_CAPACITY_MAX:
+        raise ValueError("capacity must be an integer in 1 .. 2^26, got %r" % (capacity,))
+    slots = 1024
+    while slots < 2 * max(int(capacity), VOXEL_MIN_CAPACITY):
+        slots *= 2
+    return slots
+
+
+def voxel_cloud(disp, Q, size, lo, hi, XR=None, XT=None, step=1, disparity="d1", dtype="f32", colors=None, capacity=None):
+    """Voxel-grid downsampled cloud(s), the definition of include/stereo_vision_hip.h (I) in numpy.
+
+    The kept pixels are compact_cloud's (same disp, Q, XR / XT, lo / hi, step, disparity); lo / hi must be finite.  A kept point P lies
+    in the cell c = min(int(t), cells - 1) per axis, t = (P - lo) / size, at the offset u = min(int((t - c) * 65536), 65535) inside it.
+    A voxel is the kept points of one cell: n of them, the smallest flat pixel index `first`, the integer sums S = sum u and C = sum of
+    the colour channels.  The voxels are listed in ascending `first`.
+    Returns (xyz [V,3] float32 or float64 - lo + (c + (S + 0.5 n) / (65536 n)) * size in double, as written; color uint8 [V,4] =
+    (2 C + n) // (2 n) (None without colors [H,W,4]); cell int32 [V,3]; n int32 [V]; first int32 [V]; count) with count = V, or, for
+    a capacity with V > capacity, count = -1 and no rows - what the C entry reports.  For batched input a list of such tuples, one per
+    frame.  write_ply takes xyz and color as they are."""
+    lo, hi, size, cells = voxel_grid(size, lo, hi, step, disparity, dtype, capacity)
+    d = np.asarray(disp, dtype=np.float32)
+    batched = d.ndim == 3
+    frames = compact_cloud(d, Q, XR, XT, lo, hi, step, disparity, "f64", colors)
+    out = []
+    for P, col, index in (frames if batched else [frames]):
+        t = (P - lo) / np.float64(size)
+        c = np.minimum(t.astype(np.int64), cells - 1)
+        u = np.minimum(((t - c.astype(np.float64)) * 65536.0).astype(np.int64), 65535)
+        key = c[:, 0] | (c[:, 1] << 20) | (c[:, 2] << 40)
+        _, where, inverse, n = np.unique(key, return_index=True, return_inverse=True, return_counts=True)
+        order = np.argsort(where)  # index ascends with the row, so the first row of a voxel is its smallest pixel index
+        rank = np.empty_like(order)
+        rank[order] = np.arange(len(order))
+        row = rank[inverse.reshape(-1)]  # of each point
+        V = len(order)
+        if capacity is not None and V > capacity:
+            out.append((np.zeros((0, 3), np.float32 if dtype == "f32" else np.float64), None if col is None else np.zeros((0, 4), np.uint8),
+                        np.zeros((0, 3), np.int32), np.zeros(0, np.int32), np.zeros(0, np.int32), -1))
+            continue
+        n, where = n[order].astype(np.int64), where[order]
+        S = np.zeros((V, 3), np.int64)
+        np.add.at(S, row, u)
+        nf = n.astype(np.float64)[:, None]
+        xyz = lo + (c[where].astype(np.float64) + (S.astype(np.float64) + 0.5 * nf) / (65536.0 * nf)) * np.float64(size)
+        color = None
+        if col is not None:
+            C = np.zeros((V, 4), np.int64)
+            np.add.at(C, row, col.astype(np.int64))
+            color = ((2 * C + n[:, None]) // (2 * n[:, None])).astype(np.uint8)
+        out.append((xyz.astype(np.float32) if dtype == "f32" else xyz, color, c[where].astype(np.int32), n.astype(np.int32), index[where].astype(np.int32), V))
+    return out if batched else out[0]
 
 
 GROUND_BINS_MIN, GROUND_BINS_MAX = 8, 4096
@@ -764,7 +853,14 @@ def main(argv=None):
                         help="with --batch: write each frame's coloured point cloud as DIR/<name>.ply (binary little-endian; float x y z, "
                              "uchar red green blue): the float disparity reprojected in metres, the axes and the crop of --top-view "
                              "(forward 0..40, left -20..20, up -1.4..1.0)")
+    parser.add_argument("--voxel", type=float, default=0.0, metavar="METRES",
+                        help="with --batch --ply: write the voxel-grid downsampled cloud instead - per occupied cube of this edge inside the "
+                             "same crop one vertex, the centroid of its points with their mean colour")
     args = parser.parse_args(argv)
+    if args.voxel and not args.ply:
+        parser.error("--voxel needs --ply")
+    if args.voxel and not (np.isfinite(args.voxel) and args.voxel > 0):
+        parser.error("--voxel must be a length > 0")
     if args.top_view and not args.batch:
         parser.error("--top-view needs --batch")
     if args.ply and not args.batch:
@@ -827,7 +923,8 @@ def _run_batched(args, ldir, rdir, files):
     """--batch N: the folder through a StereoRig (the batched front end and engine) N pairs at a time."""
     import time
     import torch
-    from ..engine import compact_cloud_from_disparity, disparity_to_u8, split_clouds, top_view_from_disparity
+    from ..engine import (compact_cloud_from_disparity, disparity_to_u8, split_clouds, split_voxel_clouds, top_view_from_disparity,
+                          voxel_cloud_from_disparity)
     from ..rig import StereoRig
     rig = StereoRig(1242 // args.scale, 375 // args.scale, calibration=args.camera_calibration, rectify=args.rectify, scale=args.scale)
     n, busy = 0, 0.0
@@ -844,7 +941,10 @@ def _run_batched(args, ldir, rdir, files):
             if args.ply:  # what rig.compact_clouds(..., transform=(CAMERA_TO_VEHICLE, None), lo=, hi=) runs, keeping d1 for the other outputs
                 gl, gr, col = rig.frontend(left, right, pixel_format="bgr", colors=True)
                 d1, _ = rig.engine.process_device(gl, gr, want_d2=False)
-                clouds = compact_cloud_from_disparity(d1, rig.Q, colors=col, XR=CAMERA_TO_VEHICLE, lo=CLI_CLOUD_CROP[0], hi=CLI_CLOUD_CROP[1])
+                if args.voxel:  # what rig.voxel_clouds(..., args.voxel, lo, hi, transform=(CAMERA_TO_VEHICLE, None)) runs
+                    voxels = voxel_cloud_from_disparity(d1, rig.Q, args.voxel, CLI_CLOUD_CROP[0], CLI_CLOUD_CROP[1], colors=col, XR=CAMERA_TO_VEHICLE)
+                else:
+                    clouds = compact_cloud_from_disparity(d1, rig.Q, colors=col, XR=CAMERA_TO_VEHICLE, lo=CLI_CLOUD_CROP[0], hi=CLI_CLOUD_CROP[1])
             else:
                 d1 = rig.disparity(left, right, pixel_format="bgr")
             dmap = disparity_to_u8(d1)
@@ -860,7 +960,8 @@ def _run_batched(args, ldir, rdir, files):
                 for name, g in zip(names, grids.cpu().numpy()):
                     _write_png(os.path.join(args.top_view, name), g)
             if args.ply:
-                for name, (xyz, color) in zip(names, split_clouds(clouds[0], clouds[3], clouds[1])):
+                parts = split_voxel_clouds(voxels[0], voxels[5], voxels[1]) if args.voxel else split_clouds(clouds[0], clouds[3], clouds[1])
+                for name, (xyz, color) in zip(names, parts):
                     write_ply(os.path.join(args.ply, os.path.splitext(name)[0] + ".ply"), xyz.cpu().numpy(), color.cpu().numpy())
             n += len(names)
             print("batch of %d (%d, %d): %.1f pairs/s so far" % (len(names), rig.height, rig.width, n / busy))
