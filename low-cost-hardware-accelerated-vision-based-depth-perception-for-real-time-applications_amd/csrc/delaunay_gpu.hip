@@ -295,6 +295,19 @@ __device__ __forceinline__ bool d_node(int m, int d, int j, int &lo, int &n, uin
     return true;
 }
 
+#ifdef DG_HOST_EMULATION
+// Trip-count bound of the emulated merges (tests/emu_delaunay_gpu.cpp).  A merge of a node of n vertices walks hull edges (six walks of at
+// most n steps), removes edges of the two halves (fewer than 3n exist) and adds edges between them (fewer than 3n): under 12n trips.
+struct DgEmu {
+    uint32_t step_limit = 0xFFFFFFFFu, worst_permille = 0, overruns = 0;  // worst_permille: the largest share of its bound a merge has used
+    void node(int n) { step_limit = 12u * (uint32_t)n + 16u; }
+};
+static DgEmu dg_emu;
+#define DG_EMU_NODE(n) dg_emu.node(n)
+#else
+#define DG_EMU_NODE(n)
+#endif
+
 // triangle.cpp:5362-5651 (mergehulls) on a mesh MT - Mesh (LDS, 16-bit handles) or MeshG (global memory, 32-bit handles); the two new
 // triangles take slots `slot` and `slot + 1`.  Every triangle the merge looks at is held in registers (MT::TRT) from ONE access, the
 // coordinates of the moving vertices are kept beside their ids, the two sides' next candidates are fetched together, and the in-circle
@@ -305,10 +318,23 @@ __device__ __forceinline__ void d_merge_mesh(const MT &M, uint32_t &farleft, uin
     typedef typename MT::TRT TR;
     constexpr uint32_t GHOST = MT::NOV;  // (shadows the 16-bit constant of the namespace)
     uint32_t steps = 0;
+#ifdef DG_HOST_EMULATION
+    // the CPU emulation bounds every loop trip of every merge, on either mesh, by the size of the node being merged: a walk that would
+    // not end on the GPU ends here, is counted, and fails the emulation with the set's name
+#define D_STEP()                              \
+    do {                                      \
+        if (++steps > dg_emu.step_limit) {    \
+            dg_emu.overruns++;                \
+            return;                           \
+        }                                     \
+        if ((uint64_t)steps * 1000u > (uint64_t)dg_emu.worst_permille * dg_emu.step_limit) dg_emu.worst_permille = (uint32_t)((uint64_t)steps * 1000u / dg_emu.step_limit); \
+    } while (0)
+#else
 #define D_STEP()                                           \
     do {                                                   \
         if (MT::GUARDED && ++steps > M.step_limit) return; \
     } while (0)
+#endif
     TR TL, TRr;  // the triangles of innerleft / innerright
     M.load2(innerleft >> 2, innerright >> 2, TL, TRr);
     DVL ild, ila, iro, ira;  // dest / apex of innerleft, org / apex of innerright
@@ -526,6 +552,7 @@ __device__ __forceinline__ void d_process_node(const Mesh &M, DG_LDS uint32_t *r
         const uint32_t rl = res[(2 << d) + 2 * j], rr = res[(2 << d) + 2 * j + 1];  // children: heap index 2h, 2h+1 with h = (1<<d)+j
         fl = rl & 0xFFFFu;
         fr = rr >> 16;
+        DG_EMU_NODE(n);
         d_merge_mesh<NARROW>(M, fl, rl >> 16, rr & 0xFFFFu, fr, axis, slot + 2 * n - 4);
     }
     res[(1 << d) + j] = fl | (fr << 16);
@@ -560,6 +587,7 @@ __device__ __forceinline__ void dg_top_node(const MeshG &M, DG_VOLATILE uint32_t
     if (!d_node(m, d, j, lo, n, slot, axis)) return;
     const int hl = (2 << d) + 2 * j, hr = hl + 1;  // children of heap node (1 << d) + j
     uint32_t fl = gres[2 * hl], fr = gres[2 * hr + 1];
+    DG_EMU_NODE(n);
     d_merge_mesh<NARROW>(M, fl, gres[2 * hl + 1], gres[2 * hr], fr, axis, slot + 2 * n - 4);
     gres[2 * ((1 << d) + j)] = fl;
     gres[2 * ((1 << d) + j) + 1] = fr;

@@ -203,6 +203,7 @@ static inline int atomicMin(int *p, int v) { return __hip_atomic_fetch_min(p, v,
 
 #include "delaunay_gpu.hip"
 #include "host_stage.h"
+#include "corpus_file.h"
 
 using namespace sv::dg;
 
@@ -362,6 +363,47 @@ int main(int argc, char **argv) {
         check_global(c, it++, 0, 4999, -1), handed_back++;
         c.sup.insert(c.sup.end(), {c.sup[0], c.sup[1], c.sup[2] + 1});
         check_global(c, it++, 0, 6000, -1), handed_back++;
+    }
+    // ---- the structured sets of tests/degenerate_sets.py that are vertex sets of a support lattice (rows at multiples of 5; argv[2]):
+    // collinear rows / columns, fans, strips, collinear halves, complete lattices, translated to negative x, sorted and shuffled; with
+    // coincident points (all with one disparity: interchangeable, merged up to DG_DUP_MAX of them, handed back beyond).  The image is the
+    // smallest that holds the set; in LDS where the bit maps fit, else in global scratch.
+    if (argc > 2) {
+        std::vector<CorpusSet> corpus;
+        if (!load_corpus(argv[2], corpus)) {
+            printf("cannot read the corpus %s\n", argv[2]);
+            return 2;
+        }
+        int in_lds = 0, in_global = 0, off_lattice = 0, too_large = 0;
+        for (const CorpusSet &s : corpus) {
+            const int n = s.n();
+            if (!s.on_lattice(5)) {
+                off_lattice++;
+                continue;
+            }
+            if (n > 0xFFFF) {
+                too_large++;
+                continue;
+            }
+            int xmin = 0, xmax = 0, ymax = 0;
+            for (int i = 0; i < n; i++) xmin = std::min(xmin, s.xy[2 * i]), xmax = std::max(xmax, s.xy[2 * i]), ymax = std::max(ymax, s.xy[2 * i + 1]);
+            Case c{std::max(xmax + 1, 32), std::max(ymax + 1, 32), 5, std::max(-xmin, 15), {}};
+            for (int i = 0; i < n; i++) c.sup.insert(c.sup.end(), {s.xy[2 * i], s.xy[2 * i + 1], 0});
+            const int m = host_order(c, 0, xy, ids);
+            const int before = bad;
+            const bool lds = sv::delaunay_resident_lds_bytes(c.W, c.H, c.step, c.disp_max, n) <= 160 * 1024;
+            if (lds) {
+                check_lds(c, it, 0, (n > DG_PREP_MAX || n - m > DG_DUP_MAX) ? -1 : m);
+                in_lds++;
+            } else {
+                check_global(c, it, 0, n + 5, n - m > DG_DUP_MAX ? -1 : m);
+                in_global++;
+            }
+            if (bad != before) printf("  ... corpus set %s (%d points, %d distinct)\n", s.name.c_str(), n, m);
+            it++;
+        }
+        printf("corpus sets: %d (in LDS: %d, in global scratch: %d, off the lattice: %d, beyond 65535 vertices: %d)\n", (int)corpus.size(), in_lds, in_global, off_lattice, too_large);
+        if (in_lds + in_global + off_lattice + too_large != (int)corpus.size()) bad++;  // (tests/test_sanitizers.py asserts each of the four)
     }
     printf("preparation emulated: %d cases, %d handed back as expected\n", it, handed_back);
     bad += simt::divergent_runs;

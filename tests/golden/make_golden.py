@@ -86,6 +86,17 @@ def ref_digests():
     D1, D2, _ = ref.process(p, L, R)
     out[key] = [sha(D1), sha(D2)]
     out["delaunay_random_sets"] = {str(it): [int(a.shape[0]), sha(a)] for it, _, _, xy in t.delaunay_sets() for a in [ref.delaunay(xy)]}
+    import degenerate_sets as ds
+    out["delaunay_structured_sets"] = {name: [int(a.shape[0]), sha(a)] for name, xy in ds.sets() for a in [ref.delaunay(xy.astype(np.float32))]}
+    for case in ds.pair_cases():
+        k, p_, L_, R_, by_ref = t.degenerate_pair_case(case[0])
+        if by_ref:
+            lib = ref
+        else:  # (a pair the compiled reference cannot run: the restatement's own result, under a key that says so)
+            from pyoracle import Oracle
+            lib = Oracle()
+        out[k] = t.stage_digests(lib, p_, L_, R_)
+        out[k]["triangles"] = [int(lib.stage("tri1").size // 3), int(lib.stage("tri2").size // 3)]
     for k, _, p_, L_, R_ in t.random_parameter_cases():
         n = ref.run_stages(p_, L_, R_)
         out[k] = t.stage_digests(ref, p_, L_, R_) if n >= 3 else {"n": n}

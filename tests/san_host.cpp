@@ -1,6 +1,7 @@
 // Sanitizer harness for the host stage (tests/test_sanitizers.py): split triangulations with early and late helpers against
 // the sequential result, and the vectorised lattice filters on random lattices (they read up to LATTICE_PAD elements past the end).
 #include "host_stage.h"
+#include "corpus_file.h"
 #include <chrono>
 #include <cstdio>
 #include <cstring>
@@ -23,7 +24,7 @@ struct Helper {
         });
     }
 };
-int main() {
+int main(int argc, char **argv) {
     std::mt19937 rng(5);
     int bad = 0;
     for (int it = 0; it < 300; it++) {
@@ -66,6 +67,48 @@ int main() {
         const int nb = support_filter_threads(p, rm2.data(), W, H, out_b.data(), Wc * Hc + 6, 2 + it % 4);
         if (na != nb || (na > 0 && memcmp(out_a.data(), out_b.data(), sizeof(int32_t) * 3 * na)) || rm != rm2) bad++;
         support_filter_t(p, T.data(), W, H, out.data(), Wc * Hc + 6);
+    }
+    // the structured sets of tests/degenerate_sets.py (collinear sets and halves, fans, strips, complete lattices, the extremes of the
+    // coordinate box): sequential against halves / quarters / eighths with early and late helpers, and the preparation alone
+    if (argc > 1) {
+        std::vector<CorpusSet> corpus;
+        if (!load_corpus(argv[1], corpus)) {
+            printf("cannot read the corpus %s\n", argv[1]);
+            return 2;
+        }
+        int ran = 0;
+        for (const CorpusSet &c : corpus) {
+            const int n = c.n();
+            std::vector<int32_t> a(6 * (size_t)n + 24), b(6 * (size_t)n + 24), ids(n);
+            Delaunay d1, d3;
+            const int na = d1.triangulate(c.xy.data(), n, a.data(), 2 * n + 8);
+            const int m = d3.kd_ordered_ids(c.xy.data(), n, ids.data());
+            bool ok = na >= 0 && m >= 1 && m <= n;
+            for (int i = 0; ok && i < m; i++) ok = ids[i] >= 0 && ids[i] < n;
+            for (int i = 0; ok && i < 3 * na; i++) ok = a[i] >= 0 && a[i] < n;
+            for (int depth = 1; ok && depth <= 3; depth++) {
+                Helper h{{}, {}, (ran % 7 == 0 && depth == 1) ? 2000 : 0};
+                Delaunay::Spawn sp{&Helper::run, &h, depth};
+                Delaunay d2;
+                const int nb = d2.triangulate(c.xy.data(), n, b.data(), 2 * n + 8, &sp);
+                for (size_t i = 0;; i++) {
+                    std::thread t;
+                    {
+                        std::lock_guard<std::mutex> lk(h.mu);
+                        if (i >= h.threads.size()) break;
+                        t = std::move(h.threads[i]);
+                    }
+                    t.join();
+                }
+                ok = na == nb && !memcmp(a.data(), b.data(), sizeof(int32_t) * 3 * (size_t)na);
+            }
+            if (!ok) {
+                bad++;
+                if (bad < 8) printf("mismatch: corpus set %s\n", c.name.c_str());
+            }
+            ran++;
+        }
+        printf("corpus sets: %d\n", ran);
     }
     printf("sanitizer run done, delaunay / filter-team mismatches: %d\n", bad);
     return bad != 0;

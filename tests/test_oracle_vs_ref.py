@@ -9,6 +9,7 @@ import sys
 import numpy as np
 import pytest
 
+import degenerate_sets
 import util
 from pyoracle import ElasParams, RefElas
 
@@ -159,6 +160,58 @@ def test_delaunay_random_sets(ref, oracle, stored):
             assert a.shape == b.shape and np.array_equal(a, b), (it, mode, n)
         done += 1
     assert done > 400 and done == len(want)
+
+
+def test_delaunay_structured_sets(ref, oracle, stored):
+    """The structured sets of tests/degenerate_sets.py - wholly collinear sets (no triangle), collinear halves, fans, strips, complete
+    lattices up to a 4K support grid, co-circular quadruples at the extremes of the coordinate box: the restatement's triangle list
+    equals the reference's Triangle's.  No set is left out."""
+    want = stored["delaunay_structured_sets"]
+    done = empty = 0
+    for name, xy in degenerate_sets.sets():
+        b = oracle.delaunay(xy.astype(np.float32))
+        assert [b.shape[0], util.sha(b)] == want[name], name
+        if degenerate_sets.is_collinear(xy):
+            assert b.shape[0] == 0, name
+            empty += 1
+        if ref is not None:
+            a = ref.delaunay(xy.astype(np.float32))
+            assert a.shape == b.shape and np.array_equal(a, b), name
+        done += 1
+    assert done == len(want) == 592 and empty == 100
+
+
+def degenerate_pair_case(name):
+    """(key, params, L, R, the reference can run it).  Images of at most 40 rows: the compiled reference does not survive them
+    (tests/test_gpu_parity.py::test_small_and_odd_image_sizes); the memory-safe restatement defines the result, and the key says so."""
+    L, R, _, _ = degenerate_sets.make_pair(name)
+    by_ref = L.shape[0] > 40
+    return ("degenerate_pair_" if by_ref else "oracle_defined_degenerate_pair_") + name, degenerate_sets.pair_params(ElasParams, name), L, R, by_ref
+
+
+@pytest.mark.parametrize("name", [c[0] for c in degenerate_sets.pair_cases()])
+def test_pairs_with_degenerate_support_sets(ref, oracle, stored, name):
+    """ROBOTICS with add_corners = 0.  One textured band on one lattice row (column) of a flat image: three or more support points, all on
+    one line in both images (in the left image only) - a triangulation without a triangle, and the pipeline carries on.  A complete support
+    lattice; two lattice rows at the smallest admitted height.  Every stage of the restatement equals the reference's (for the 32-row pair,
+    which the reference cannot run, the stored digests are the restatement's own: a regression record under a key that says so); the shape
+    of the support set is what each case is for."""
+    key, p, L, R, by_ref = degenerate_pair_case(name)
+    kind = {c[0]: c[1] for c in degenerate_sets.pair_cases()}[name]
+    _compare(ref if by_ref else None, oracle, stored, key, p, L, R)
+    n, t1, t2 = stored[key]["n"], oracle.stage("tri1").size // 3, oracle.stage("tri2").size // 3
+    sup = oracle.stage("support").reshape(-1, 3)
+    us, vs = np.unique(sup[:, 0]), np.unique(sup[:, 1])
+    assert n >= 3 and [t1, t2] == stored[key]["triangles"]
+    if kind == "row":
+        assert len(vs) == 1 and t1 == 0 and t2 == 0
+    elif kind == "col":
+        assert len(us) == 1 and t1 == 0 and t2 > 0
+    elif kind == "lattice":
+        assert n == len(us) * len(vs) and len(us) >= 8 and len(vs) >= 8 and t1 > 0 and t2 > 0
+        assert (np.diff(us) == p.candidate_stepsize).all() and (np.diff(vs) == p.candidate_stepsize).all()
+    else:
+        assert L.shape[0] == 32 and len(vs) == 2 and vs[1] - vs[0] == p.candidate_stepsize and n >= 6 and t1 > 0 and t2 > 0
 
 
 def test_random_parameter_sets(ref, oracle, stored):
