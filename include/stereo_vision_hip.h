@@ -712,6 +712,72 @@ int sv_voxel_disparity_device(const float *disp, const uint8_t *colors, int batc
  * slot, 5 or, with colours, 9 sums, and 1 or 2 for a claimed slot).  The results do not depend on it.  Returns SV_OK. */
 int sv_debug_voxel(int combine, unsigned long long *counters_device);
 
+/* ---- (J) occupancy and elevation grids: disparity maps + labels + free space -> evidence, sight lines and a state per cell ---- */
+
+/* What a planner takes: per cell of (D)'s bird's-eye grid the ground and obstacle pixels that fell into it, the height span of what
+ * was seen there, the number of sight lines that crossed it and a state - unknown, free or occupied - for B pairs.  "Seen and empty"
+ * (a sight line crossed the cell) is told from "never seen".  Integers from the cell index on; the results are bitwise reproducible
+ * and independent of the batch, of the launch and of the other pairs.  stereo_vision.sv.occupancy_grid restates all of it in numpy.
+ *
+ *   grid       (D)'s in SV_TOPVIEW_COUNT mode, with (D)'s checks: rows = (x1 - x0) scale + 1, cols = (y1 - y0) scale + 1; a point (X, Y)
+ *              lies in cell (R1 - trunc(X s), C1 - trunc(Y s)), R1 = trunc(x1 s), C1 = trunc(y1 s), products in double.
+ *   evidence   a pixel counts iff d > 0 (NaN does not) and its label is 1 (ground) or 2 (obstacle) - (G)'s labels; 0 and 3 never count,
+ *              so a pair without ground (every valid pixel 3) yields an all-unknown grid.  Its point is P = reproject(x, y, (double)d)
+ *              (+ XR / XT), double, no FMA, as SV_TOPVIEW_D1; it is kept iff x0 < X < x1, y0 < Y < y1, z0 < Z < z1, strictly (inf and NaN
+ *              drop out).  Its height is h = min(trunc((Z - z0) * z_scale), 65535): z_scale height steps per metre, an integer, so no
+ *              division stands between Z and h.
+ *   cells      int32 [4] per cell = (n_ground, n_obstacle, h_lo, h_hi): the kept pixels of either label, and the smallest and the
+ *              largest h over both; h_lo = h_hi = -1 for a cell without one.
+ *   n_rays     per image column u one sight line from the origin cell (R1 - trunc(Ox s), C1 - trunc(Oy s)), O = XT3 or 0 - the camera
+ *              centre in the caller's frame; it is not range-tested and may lie outside the grid - to the cell of
+ *                free_row[u] >= 0: the point of pixel (u, free_row[u]) with disparity free_disp[u] - the obstacle's base.  Only the three
+ *                                  numbers are used; no pixel is read.
+ *                free_row[u] < 0 : the point of the topmost pixel of the column with label 1 and d > 0 - a ground end; a column without
+ *                                  such a pixel casts no line.
+ *              A line is dropped when a coordinate of its end is not finite or |trunc(X s)| or |trunc(Y s)| is >= 2^24.  With dr, dc =
+ *              the end cell minus the origin cell and n = max(|dr|, |dc|) the line visits
+ *                r_k = r0 + (2 k dr + n) / (2 n),  c_k = c0 + (2 k dc + n) / (2 n)      (floor division, 64-bit products)
+ *              for k = 0 .. n - 1 (obstacle end: its own cell is evidence, not free space; n = 0 visits nothing) or k = 0 .. n (ground
+ *              end; n = 0 visits the origin's cell).  Every visited cell inside the grid adds 1 to n_rays.  z_range does not apply.
+ *   state      uint8: 2 (occupied) iff n_obstacle >= min_obstacle; else 1 (free) iff n_ground >= min_ground or n_rays >= min_rays;
+ *              else 0 (unknown). */
+typedef struct sv_occupancy_spec {
+    double x_range[2], y_range[2], z_range[2]; /* as sv_top_view_spec */
+    int32_t scale;                             /* cells per unit, >= 1 */
+    int32_t z_scale;                           /* 1..65536: height steps per unit */
+    int32_t min_obstacle;                      /* >= 1: obstacle pixels that make a cell occupied */
+    int32_t min_ground;                        /* >= 1: ground pixels that make a cell free */
+    int32_t min_rays;                          /* >= 1: sight lines that make a cell free */
+    int32_t reserved[5];                       /* must be 0 */
+} sv_occupancy_spec;
+
+/* rows x cols of the grid of a spec.  Host only; SV_ERR_ARG (outputs untouched) for a NULL argument or a bad spec. */
+int sv_occupancy_dims(const sv_occupancy_spec *spec, int *rows, int *cols);
+/* Enqueued on `stream` (a hipStream_t, NULL = the default stream) as four kernels - clear, evidence, sight lines, finalize - and not
+ * waited for; the outputs are the accumulators: no workspace, nothing is allocated, no host synchronisation is made, and nothing is
+ * assumed of what the outputs held before.
+ *   disp         : float [batch][height][width] device; width * height < 2^31
+ *   labels       : uint8 [batch][height][width] device, as sv_ground_disparity_device writes them
+ *   free_row     : int32 [batch][width] device, free_disp : float [batch][width] device, as sv_ground_disparity_device writes them
+ *   Q16, XR9, XT3: HOST, as for sv_reproject_batch_device (XR9 and XT3 both NULL = no transform)
+ *   cells        : int32 [batch][rows][cols][4] device, 16-byte aligned
+ *   n_rays       : int32 [batch][rows][cols] device
+ *   state        : uint8 [batch][rows][cols] device, or NULL
+ * Returns SV_OK (nothing enqueued for batch == 0), SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued, the outputs untouched, the text in
+ * sv_last_error(NULL) - for: a NULL spec, disp, labels, free_row, free_disp, Q16, cells or n_rays; disp, free_row, free_disp or n_rays not
+ * 4-byte aligned; cells not 16-byte aligned; a grid sv_top_view_dims refuses; z_scale outside 1..65536; a threshold < 1; a non-zero
+ * reserved word; |XT3[0] scale| or |XT3[1] scale| not below 2^24; batch < 0 or > 65535; width < 1 or height < 1; height > 32768;
+ * width * height >= 2^31.  These checks run before any HIP call.
+ * The environment variable SV_OCCUPANCY_STAGE = clear, evidence or rays leaves out the kernels behind that stage (a measurement aid:
+ * the outputs are then unfinished). */
+int sv_occupancy_disparity_device(const float *disp, const uint8_t *labels, const int32_t *free_row, const float *free_disp, int batch, int width, int height,
+                                  const double *Q16, const double *XR9, const double *XT3, const sv_occupancy_spec *spec, int32_t *cells, int32_t *n_rays,
+                                  uint8_t *state, void *stream);
+/* Test hook for the call above, process-wide: combine != 0 (the default) merges the lanes of a wavefront that hold neighbouring pixels
+ * of one cell into one set of atomics; atomics_device != NULL: a device uint64 that receives the number of atomics the evidence kernel
+ * issued on the cells (without the merge: three per kept pixel).  The results do not depend on it.  Returns SV_OK. */
+int sv_debug_occupancy(int combine, unsigned long long *atomics_device);
+
 /* ---- (A) the reference's exported symbols ------------------------------------------------------------- */
 
 typedef struct {

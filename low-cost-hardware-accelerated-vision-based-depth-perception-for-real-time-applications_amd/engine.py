@@ -1093,6 +1093,115 @@ def stixels_from_disparity(d1, labels, disp_max=None, n_bins=None, q_min=16, sim
     return res
 
 
+class SvOccupancySpec(ctypes.Structure):
+    """sv_occupancy_spec of include/stereo_vision_hip.h."""
+    _fields_ = [("x_range", ctypes.c_double * 2), ("y_range", ctypes.c_double * 2), ("z_range", ctypes.c_double * 2), ("scale", ctypes.c_int32),
+                ("z_scale", ctypes.c_int32), ("min_obstacle", ctypes.c_int32), ("min_ground", ctypes.c_int32), ("min_rays", ctypes.c_int32),
+                ("reserved", ctypes.c_int32 * 5)]
+
+
+_occupancy_bound = False
+
+
+def occupancy_lib():
+    """The library with the sv_occupancy_* signatures declared."""
+    global _occupancy_bound
+    L = lib()
+    if not _occupancy_bound:
+        vp, ci, sp = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(SvOccupancySpec)
+        L.sv_occupancy_dims.argtypes = [sp, ctypes.POINTER(ci), ctypes.POINTER(ci)]
+        L.sv_occupancy_dims.restype = ci
+        L.sv_occupancy_disparity_device.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, sp, vp, vp, vp, vp]
+        L.sv_occupancy_disparity_device.restype = ci
+        L.sv_debug_occupancy.argtypes = [ci, vp]
+        L.sv_debug_occupancy.restype = ci
+        _occupancy_bound = True
+    return L
+
+
+def occupancy_spec(x_range, y_range, z_range, scale, z_scale=20, min_obstacle=3, min_ground=1, min_rays=1, XT=None):
+    """-> (SvOccupancySpec, rows, cols); ValueError for a bad argument (the checks of the C entry, made in Python first:
+    stereo_vision.sv.occupancy_params)."""
+    from .stereo_vision.sv import occupancy_params
+    rows, cols, p = occupancy_params(x_range, y_range, z_range, scale, z_scale, min_obstacle, min_ground, min_rays, XT)
+    spec = SvOccupancySpec()
+    spec.x_range[:] = [float(v) for v in x_range]
+    spec.y_range[:] = [float(v) for v in y_range]
+    spec.z_range[:] = [float(v) for v in z_range]
+    spec.scale = int(scale)
+    for k, v in p.items():
+        setattr(spec, k, v)
+    return spec, rows, cols
+
+
+class OccupancyResult:
+    """What occupancy_from_disparity returns, tensors on the input's device: cells int32 [B,rows,cols,4] = (n_ground, n_obstacle, h_lo,
+    h_hi) per cell (h in steps of 1 / z_scale above z_range[0], -1 for a cell without evidence: stereo_vision.sv.occupancy_heights turns
+    them into metres), n_rays int32 [B,rows,cols] = the sight lines that crossed the cell, state uint8 [B,rows,cols] (0 unknown, 1 free,
+    2 occupied; None where not asked for) and the spec in use.  StereoRig.occupancy adds ground, the GroundResult the grid was made
+    from."""
+    __slots__ = ("cells", "n_rays", "state", "spec", "ground")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+def occupancy_from_disparity(d1, labels, free_row, free_disp, Q, x_range, y_range, z_range, scale, z_scale=20, XR=None, XT=None, min_obstacle=3,
+                             min_ground=1, min_rays=1, want_state=True):
+    """Occupancy and elevation grids straight from disparity maps (CUDA float32 [B,H,W]; one frame [H,W] accepted), their labels (uint8
+    [B,H,W]) and free space (free_row int32 [B,W], free_disp float32 [B,W]) as ground_from_disparity returns them - the definition of
+    stereo_vision.sv.occupancy_grid on the GPU, bit for bit.  The grid is top_view's (x_range, y_range, z_range, scale, mode "count") in
+    the frame XR P + XT of the "d1" points, metres.  Per cell: the ground and obstacle pixels that fell into it, the lowest and highest
+    height step (z_scale per metre above z_range[0]) of either, the sight lines - one per image column, from the camera centre to the
+    column's obstacle base or else its topmost ground pixel - that crossed it, and a state: 2 occupied (n_obstacle >= min_obstacle), else
+    1 free (n_ground >= min_ground or n_rays >= min_rays), else 0 unknown.  Nothing dense is read back and no cloud is written.
+    -> OccupancyResult; enqueued on torch's current stream, not waited for."""
+    import torch
+    spec, rows, cols = occupancy_spec(x_range, y_range, z_range, scale, z_scale, min_obstacle, min_ground, min_rays, XT)
+    if not (isinstance(d1, torch.Tensor) and d1.is_cuda and d1.dtype == torch.float32 and d1.dim() in (2, 3)):
+        raise ValueError("d1 must be a CUDA float32 tensor [B,H,W]")
+    one = d1.dim() == 2
+    d = (d1.unsqueeze(0) if one else d1).contiguous()
+    B, H, W = d.shape
+    dev = d.device
+    if B > 65535 or H < 1 or W < 1 or H > 32768 or H * W >= 2 ** 31:
+        raise ValueError("at most 65535 pairs of 1 <= width * height < 2^31 pixels and at most 32768 rows, got %s" % (tuple(d.shape),))
+    ins = []
+    for t, dtype, shape, name in ((labels, torch.uint8, (B, H, W), "labels"), (free_row, torch.int32, (B, W), "free_row"), (free_disp, torch.float32, (B, W), "free_disp")):
+        if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dtype):
+            raise ValueError("%s must be a %s tensor on the device of d1" % (name, dtype))
+        t = t.unsqueeze(0) if one and t.dim() == len(shape) - 1 else t
+        if tuple(t.shape) != shape:
+            raise ValueError("%s must be %s, got %s" % (name, list(shape), list(t.shape)))
+        ins.append(t.contiguous())
+    q = np.ascontiguousarray(Q, dtype=np.float64).reshape(16)
+    xr = None if XR is None else np.ascontiguousarray(XR, dtype=np.float64).reshape(9)
+    xt = None if XT is None else np.ascontiguousarray(XT, dtype=np.float64).reshape(3)
+    cells = torch.empty((B, rows, cols, 4), dtype=torch.int32, device=dev)
+    n_rays = torch.empty((B, rows, cols), dtype=torch.int32, device=dev)
+    state = torch.empty((B, rows, cols), dtype=torch.uint8, device=dev) if want_state else None
+    res = OccupancyResult(cells=cells, n_rays=n_rays, state=state, spec=spec)
+    if B == 0:  # nothing to enqueue
+        return res
+    L = occupancy_lib()
+    with torch.cuda.device(dev):
+        rc = L.sv_occupancy_disparity_device(d.data_ptr(), ins[0].data_ptr(), ins[1].data_ptr(), ins[2].data_ptr(), B, W, H, q.ctypes.data,
+                                             xr.ctypes.data if xr is not None else None, xt.ctypes.data if xt is not None else None, ctypes.byref(spec),
+                                             cells.data_ptr(), n_rays.data_ptr(), state.data_ptr() if state is not None else None,
+                                             torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        msg = "sv_occupancy_disparity_device failed (%d): %s" % (rc, (L.sv_last_error(None) or b"").decode())
+        raise ValueError(msg) if rc == -1 else StereoError(msg)
+    return res
+
+
+def debug_occupancy(combine=True, counter=None):
+    """sv_debug_occupancy: the wavefront merge of the evidence kernel on / off and a CUDA int64 [1] tensor (or None) that receives the
+    atomics issued on the cells.  Process-wide; a test hook."""
+    return int(occupancy_lib().sv_debug_occupancy(1 if combine else 0, None if counter is None else counter.data_ptr()))
+
+
 def host_support_filter(params, dcan, width, height, threads=0, lattice=False):
     """Product host stage: lattice filters + corner points (CPU by design; see csrc/host_stage.h).  threads > 0: the lattice shared between
     that many threads (what single-pair calls do); lattice=True: also return the filtered lattice."""

@@ -16,6 +16,9 @@ disparity, the driver's 8-bit map and point clouds out.
                                                                      # g.pose[b] = (height m, pitch rad, slope), g.points f64 [B,W,3] metres
     o = rig.objects(left, right)                                     # no detector: o.boxes int32 [B,64,4] = (x, y, w, h), o.counts [B],
                                                                      # o.positions f64 [B,64,3] metres, o.stixels int32 [B,layers,W,4]
+    occ = rig.occupancy(left, right, (0, 40), (-20, 20), (-1.4, 1.0), 10, transform=(CAMERA_TO_VEHICLE, None))
+                                                                     # occ.state u8 [B,401,401] (0 unknown, 1 free, 2 occupied), occ.cells
+                                                                     # int32 [B,401,401,4] = (n_ground, n_obstacle, h_lo, h_hi), occ.n_rays
 
 Frames are [B,Hs,Ws,C] (C = 4, 3, 3 for "bgra", "bgr", "rgb") or [B,Hs,Ws] for "gray"; one frame without B is accepted.
 Frames of another size than the rig's are resized to it.  CUDA tensors are processed on torch's current stream and CUDA
@@ -27,7 +30,7 @@ import ctypes
 import numpy as np
 
 from .engine import (SvParams, StereoEngine, StereoError, box_positions_from_disparity, box_spec, cloud_spec, compact_cloud_from_disparity,
-                     ground_from_disparity, ground_spec, lib, pinned_array, reproject, split_clouds, stixel_spec, stixels_from_disparity,
+                     ground_from_disparity, ground_spec, lib, occupancy_from_disparity, occupancy_spec, pinned_array, reproject, split_clouds, stixel_spec, stixels_from_disparity,
                      top_view_from_disparity, top_view_spec, split_voxel_clouds, voxel_cloud_from_disparity, voxel_spec)
 from .stereo_vision.sv import CAMERA_TO_VEHICLE, DEFAULT_CALIBRATION  # noqa: F401 (CAMERA_TO_VEHICLE: re-exported for top_view)
 from .stereo_vision.sv import free_space_points, ground_pose
@@ -370,4 +373,34 @@ class StereoRig:
                 t = getattr(res, k)
                 setattr(res, k, None if t is None else t.cpu().numpy())
             g.ground, g.labels = g.ground.cpu().numpy(), g.labels.cpu().numpy()
+        return res
+
+    def occupancy(self, left, right, x_range, y_range, z_range, scale, pixel_format="bgr", transform=None, ground=None, **spec):
+        """Occupancy and elevation grids of B pairs - what a planner takes: front end, engine, engine.ground_from_disparity (labels and
+        free space; `ground`: a dict of its spec words vh_lo, vh_hi, vh_step, qb_step, tol, g_tol, min_run, min_support, or None) and
+        engine.occupancy_from_disparity on the float disparity, all on the device - nothing dense crosses the host link and nothing is
+        waited for.  The grid is top_view's (x_range, y_range, z_range, scale) in the frame of `transform` (as in top_view: None - camera
+        axes -, "rig" or (XR, XT); a vehicle grid takes (CAMERA_TO_VEHICLE, None)); spec: z_scale, min_obstacle, min_ground, min_rays,
+        want_state as there.  -> engine.OccupancyResult with cells, n_rays, state and ground (the GroundResult).  CUDA input: device
+        tensors; numpy input: numpy arrays."""
+        if self.params.subsampling:
+            raise ValueError("occupancy does not support half-resolution maps (params.subsampling)")
+        gspec = dict(ground or {})
+        if any(k in gspec for k in ("want_free", "want_labels", "want_vdisp", "disp_max", "n_bins")):
+            raise ValueError("occupancy: ground takes the spec words of ground_from_disparity only (labels and free space are always computed, the bins follow the rig's disp_max)")
+        if gspec.get("min_support") is None:
+            gspec["min_support"] = self.width
+        XR, XT = self._transform(transform)
+        ground_spec(self.height, self.params.disp_max, **gspec)  # argument errors before any work
+        occupancy_spec(x_range, y_range, z_range, scale, XT=XT, **{k: v for k, v in spec.items() if k != "want_state"})
+        gl, gr, _, from_numpy = self._run_frontend(left, right, pixel_format, False)
+        d1, _ = self.engine.process_device(gl, gr, want_d2=False)
+        g = ground_from_disparity(d1, self.params.disp_max, want_vdisp=False, **gspec)
+        res = occupancy_from_disparity(d1, g.labels, g.free_row, g.free_disp, self.Q, x_range, y_range, z_range, scale, XR=XR, XT=XT, **spec)
+        res.ground = g
+        if from_numpy:
+            for obj, names in ((res, ("cells", "n_rays", "state")), (g, ("ground", "labels", "free_row", "free_disp"))):
+                for k in names:
+                    t = getattr(obj, k)
+                    setattr(obj, k, None if t is None else t.cpu().numpy())
         return res

@@ -39,6 +39,12 @@ v_disparity, ground_line, ground_labels, free_space (together: ground), ground_p
 plane, obstacle labels and free space (sv_ground_* of include/stereo_vision_hip.h (G); engine.ground_from_disparity /
 rig.StereoRig.ground on the GPU): Labayrade's v-disparity line fit in integers and a per-column scan for the nearest obstacle.  The
 reference has no counterpart.
+
+occupancy_params, occupancy_grid (with occupancy_ray_cells / occupancy_ray_clip) and occupancy_heights are the definition of the
+occupancy and elevation grids (sv_occupancy_* of include/stereo_vision_hip.h (J); engine.occupancy_from_disparity /
+rig.StereoRig.occupancy on the GPU): per cell of the top view's grid the ground and obstacle pixels that fell into it, the height span
+of what was seen, the sight lines that crossed it and a state - unknown, free or occupied.  Integers from the cell index on.  The
+reference has no counterpart.
 """
 import argparse
 import ctypes
@@ -726,6 +732,158 @@ def stixel_world(disp, disp_max=None, capacity=None, **spec):
     return out
 
 
+OCCUPANCY_Z_SCALE_MAX, OCCUPANCY_H_MAX, OCCUPANCY_CELL_MAX = 65536, 65535, 2 ** 24
+OCCUPANCY_STATES = {"unknown": 0, "free": 1, "occupied": 2}
+OCCUPANCY_PNG = np.array([0, 127, 255], np.uint8)  # --occupancy: the grey of each state
+_OCCUPANCY_FULL_WALK = 1 << 16  # rays of more steps than this are walked over their clipped k range only
+
+
+def occupancy_params(x_range, y_range, z_range, scale, z_scale=20, min_obstacle=3, min_ground=1, min_rays=1, XT=None):
+    """(rows, cols, dict of the four integer words of sv_occupancy_spec) after the checks sv_occupancy_disparity_device makes (ValueError
+    for a bad argument): top_view_grid's in "count" mode; z_scale an integer in 1 .. 65536 (height steps per metre); the three thresholds
+    integers in 1 .. 2^31 - 1; with XT, the origin of the sight lines, |XT[0] scale| and |XT[1] scale| below 2^24 (NaN refused)."""
+    rows, cols = top_view_grid(x_range, y_range, z_range, scale, "count")
+    p = dict(z_scale=z_scale, min_obstacle=min_obstacle, min_ground=min_ground, min_rays=min_rays)
+    for k, v in p.items():
+        if isinstance(v, (bool, np.bool_)) or int(v) != v or not 1 <= v <= (OCCUPANCY_Z_SCALE_MAX if k == "z_scale" else 2 ** 31 - 1):
+            raise ValueError("%s must be an integer in 1 .. %s, got %r" % (k, "65536" if k == "z_scale" else "2^31 - 1", v))
+        p[k] = int(v)
+    if XT is not None:
+        o = np.asarray(XT, np.float64).reshape(3)
+        with np.errstate(over="ignore", invalid="ignore"):
+            if not (np.abs(o[:2] * float(int(scale))) < OCCUPANCY_CELL_MAX).all():
+                raise ValueError("the origin of the sight lines, XT = %r, lies 2^24 cells or more from the frame's origin" % (o.tolist(),))
+    return rows, cols, p
+
+
+def occupancy_ray_clip(r0, c0, r1, c1, rows, cols, obstacle_end):
+    """(k_lo, k_hi), inclusive, of the steps of the sight line from cell (r0, c0) to cell (r1, c1) whose cells lie inside a grid of
+    rows x cols - (0, -1) for none - without walking it.  With dr = r1 - r0, dc = c1 - c0 and n = max(|dr|, |dc|) step k is at
+    (r0 + (2 k dr + n) // (2 n), c0 + (2 k dc + n) // (2 n)); k runs over 0 .. n - 1 for an obstacle end and 0 .. n for a ground end
+    (n = 0: the origin's cell alone, for a ground end).  Each coordinate is monotone in k, so per axis the admissible k form an interval:
+    0 <= a0 + (2 k da + n) // (2 n) <= size - 1  <=>  n (2 lo - 1) <= 2 k da <= n (2 hi + 1) - 1  with lo = -a0, hi = size - 1 - a0.
+    A line whose span misses the grid on an axis is dropped first, which also keeps every product below 2^63 in the kernel."""
+    r0, c0, r1, c1 = int(r0), int(c0), int(r1), int(c1)
+    dr, dc = r1 - r0, c1 - c0
+    n = max(abs(dr), abs(dc))
+    k_lo, k_hi = 0, (n - 1 if obstacle_end else n)
+    if max(r0, r1) < 0 or min(r0, r1) > rows - 1 or max(c0, c1) < 0 or min(c0, c1) > cols - 1:
+        return 0, -1
+    if n == 0:
+        return k_lo, k_hi  # the origin's cell, inside the grid by the test above
+    for a0, da, size in ((r0, dr, rows), (c0, dc, cols)):
+        lo, hi = n * (2 * (-a0) - 1), n * (2 * (size - 1 - a0) + 1) - 1
+        if da == 0:
+            if not lo <= 0 <= hi:
+                return 0, -1
+        elif da > 0:
+            k_lo, k_hi = max(k_lo, -(-lo // (2 * da))), min(k_hi, hi // (2 * da))  # ceil and floor: // is the floor for either sign
+        else:
+            k_lo, k_hi = max(k_lo, -(-hi // (2 * da))), min(k_hi, lo // (2 * da))
+    return (k_lo, k_hi) if k_lo <= k_hi else (0, -1)
+
+
+def occupancy_ray_cells(r0, c0, r1, c1, obstacle_end, k_lo=0, k_hi=None):
+    """(r int64 [m], c int64 [m]): the cells of the steps k_lo .. k_hi (None: the last step) of the sight line of occupancy_ray_clip,
+    inside the grid or not."""
+    r0, c0 = int(r0), int(c0)
+    dr, dc = int(r1) - r0, int(c1) - c0
+    n = max(abs(dr), abs(dc))
+    last = n - 1 if obstacle_end else n
+    k = np.arange(k_lo, (last if k_hi is None else k_hi) + 1, dtype=np.int64)
+    if n == 0:
+        return np.full(k.size, r0, np.int64), np.full(k.size, c0, np.int64)
+    return r0 + (2 * k * dr + n) // (2 * n), c0 + (2 * k * dc + n) // (2 * n)
+
+
+def occupancy_grid(disp, labels, free_row, free_disp, Q, x_range, y_range, z_range, scale, z_scale=20, XR=None, XT=None, min_obstacle=3,
+                   min_ground=1, min_rays=1):
+    """Occupancy and elevation grid of one float32 map [H,W], its labels uint8 [H,W] and its free space (free_row int32 [W], free_disp
+    float32 [W]; ground()'s outputs), the definition of include/stereo_vision_hip.h (J) in numpy: a dict with
+      cells  int32 [rows, cols, 4] = (n_ground, n_obstacle, h_lo, h_hi) - the pixels with d > 0 and label 1 / label 2 whose point
+             (reproject()'s "d1" form, then XR P + XT) lies strictly inside the three ranges, in the cell
+             (trunc(x1 s) - trunc(X s), trunc(y1 s) - trunc(Y s)) of top_view_grid(mode="count"), and the smallest and largest
+             h = min(trunc((Z - z0) * z_scale), 65535) over both kinds; h_lo = h_hi = -1 for a cell without one;
+      n_rays int32 [rows, cols] - the sight lines that crossed the cell: per image column one line from the cell of the camera centre
+             (XT, or 0; not range-tested) to the cell of the column's obstacle base (free_row >= 0: free_space_points' point; the end cell
+             itself is left out) or else of its topmost ground pixel (label 1, d > 0; the end cell is counted), by the closed form of
+             occupancy_ray_clip; a column with neither, or with an end that is not finite or 2^24 cells or more from the frame's origin,
+             casts none; z_range does not apply;
+      state  uint8 [rows, cols] - 2 occupied iff n_obstacle >= min_obstacle, else 1 free iff n_ground >= min_ground or
+             n_rays >= min_rays, else 0 unknown.
+    Labels 0 and 3 never count: a map without ground (every valid pixel 3) gives an all-unknown grid."""
+    rows, cols, p = occupancy_params(x_range, y_range, z_range, scale, z_scale, min_obstacle, min_ground, min_rays, XT)
+    d = np.asarray(disp, dtype=np.float32)
+    lab = np.asarray(labels)
+    row, fd = np.asarray(free_row), np.asarray(free_disp, dtype=np.float32)
+    if d.ndim != 2 or lab.shape != d.shape or row.shape != (d.shape[1],) or fd.shape != row.shape:
+        raise ValueError("expected disp [H,W], labels [H,W], free_row [W] and free_disp [W], got %s / %s / %s / %s" % (d.shape, lab.shape, row.shape, fd.shape))
+    H, W = d.shape
+    s = float(int(scale))
+    x0, x1, y0, y1, z0, z1 = (float(v) for v in (x_range[0], x_range[1], y_range[0], y_range[1], z_range[0], z_range[1]))
+    R1, C1 = int(np.trunc(x1 * s)), int(np.trunc(y1 * s))
+    with np.errstate(invalid="ignore"):
+        valid = d > 0
+    # evidence
+    P = _box_points(d.astype(np.float64), Q, XR, XT)
+    X, Y, Z = P[..., 0], P[..., 1], P[..., 2]
+    with np.errstate(invalid="ignore"):
+        keep = valid & ((lab == 1) | (lab == 2)) & (X > x0) & (X < x1) & (Y > y0) & (Y < y1) & (Z > z0) & (Z < z1)
+    Xk, Yk, Zk, kind = X[keep], Y[keep], Z[keep], lab[keep]
+    flat = (R1 - np.trunc(Xk * s).astype(np.int64)) * cols + (C1 - np.trunc(Yk * s).astype(np.int64))
+    assert flat.size == 0 or (flat.min() >= 0 and flat.max() < rows * cols)
+    with np.errstate(over="ignore"):
+        h = np.minimum(np.trunc((Zk - z0) * float(p["z_scale"])), float(OCCUPANCY_H_MAX)).astype(np.int64)
+    cells = np.zeros((rows * cols, 4), np.int64)
+    cells[:, 0] = np.bincount(flat[kind == 1], minlength=rows * cols)
+    cells[:, 1] = np.bincount(flat[kind == 2], minlength=rows * cols)
+    cells[:, 2], cells[:, 3] = 2 ** 31 - 1, -1
+    np.minimum.at(cells[:, 2], flat, h)
+    np.maximum.at(cells[:, 3], flat, h)
+    cells[cells[:, 3] < 0, 2] = -1
+    # sight lines
+    n_rays = np.zeros(rows * cols, np.int64)
+    o = np.zeros(3) if XT is None else np.asarray(XT, np.float64).reshape(3)
+    r0, c0 = R1 - int(np.trunc(o[0] * s)), C1 - int(np.trunc(o[1] * s))
+    ground_px = (lab == 1) & valid
+    top = np.where(ground_px.any(0), ground_px.argmax(0), -1)  # the topmost ground pixel of each column
+    obstacle = row >= 0
+    v_end = np.where(obstacle, row, top).astype(np.int64)
+    d_end = np.where(obstacle, fd, d[np.maximum(top, 0), np.arange(W)]).astype(np.float32)
+    E = free_space_points(Q, v_end, d_end, XR, XT)  # NaN where v_end < 0: no ray
+    with np.errstate(over="ignore", invalid="ignore"):
+        tX, tY = np.trunc(E[:, 0] * s), np.trunc(E[:, 1] * s)
+        cast = np.isfinite(E).all(1) & (np.abs(tX) < OCCUPANCY_CELL_MAX) & (np.abs(tY) < OCCUPANCY_CELL_MAX)
+    for u in np.nonzero(cast)[0]:
+        r1, c1 = R1 - int(tX[u]), C1 - int(tY[u])
+        if max(abs(r1 - r0), abs(c1 - c0)) <= _OCCUPANCY_FULL_WALK:
+            r, c = occupancy_ray_cells(r0, c0, r1, c1, bool(obstacle[u]))
+            inside = (r >= 0) & (r < rows) & (c >= 0) & (c < cols)
+            r, c = r[inside], c[inside]
+        else:
+            r, c = occupancy_ray_cells(r0, c0, r1, c1, bool(obstacle[u]), *occupancy_ray_clip(r0, c0, r1, c1, rows, cols, bool(obstacle[u])))
+        n_rays[r * cols + c] += 1  # a line visits a cell once: its major coordinate advances with every step
+    state = np.where(cells[:, 1] >= p["min_obstacle"], 2, np.where((cells[:, 0] >= p["min_ground"]) | (n_rays >= p["min_rays"]), 1, 0))
+    return {"cells": cells.astype(np.int32).reshape(rows, cols, 4), "n_rays": n_rays.astype(np.int32).reshape(rows, cols),
+            "state": state.astype(np.uint8).reshape(rows, cols)}
+
+
+def occupancy_heights(cells, z0, z_scale):
+    """(z_lo, z_hi) float64, the shape of cells[..., 0]: the heights h_lo / h_hi of occupancy_grid's cells back in metres,
+    z0 + h / z_scale - the lower edge of the height step: a point with that h lies in [z, z + 1 / z_scale), and h = 65535 is open
+    above - and NaN for an empty cell."""
+    c = np.asarray(cells)
+    if c.shape[-1] != 4:
+        raise ValueError("cells must be [..., 4], got shape %s" % (c.shape,))
+    if isinstance(z_scale, bool) or int(z_scale) != z_scale or not 1 <= z_scale <= OCCUPANCY_Z_SCALE_MAX:
+        raise ValueError("z_scale must be an integer in 1 .. 65536, got %r" % (z_scale,))
+    out = []
+    for k in (2, 3):
+        hk = c[..., k].astype(np.float64)
+        out.append(np.where(c[..., k] >= 0, float(z0) + hk / float(int(z_scale)), np.nan))
+    return out[0], out[1]
+
+
 class stereo_vision:
     def __init__(self, so_lib_path=DEFAULT_STEREO_VISION_SO_PATH, width=1242, height=375, defaultCalibFile=True, objectTracking=True,
                  graphics=False, display=False, scale=1, pc_extrapolation=1, YOLO_CFG="src/yolo/yolov4-tiny.cfg",
@@ -856,6 +1014,10 @@ def main(argv=None):
     parser.add_argument("--voxel", type=float, default=0.0, metavar="METRES",
                         help="with --batch --ply: write the voxel-grid downsampled cloud instead - per occupied cube of this edge inside the "
                              "same crop one vertex, the centroid of its points with their mean colour")
+    parser.add_argument("--occupancy", type=str, default="", metavar="DIR",
+                        help="with --batch: write each frame's occupancy grid as a PNG into DIR (0 unknown, 127 free, 255 occupied): ground "
+                             "plane and obstacle labels from the float disparity, then per cell of the grid of --top-view (vehicle axes) the "
+                             "ground and obstacle pixels and the sight lines that crossed it")
     args = parser.parse_args(argv)
     if args.voxel and not args.ply:
         parser.error("--voxel needs --ply")
@@ -865,6 +1027,8 @@ def main(argv=None):
         parser.error("--top-view needs --batch")
     if args.ply and not args.batch:
         parser.error("--ply needs --batch")
+    if args.occupancy and not args.batch:
+        parser.error("--occupancy needs --batch")
     if args.batch < 0:
         parser.error("--batch must be >= 1")
     if args.batch and args.subsampling:
@@ -888,6 +1052,8 @@ def main(argv=None):
         os.makedirs(args.top_view, exist_ok=True)
     if args.ply:
         os.makedirs(args.ply, exist_ok=True)
+    if args.occupancy:
+        os.makedirs(args.occupancy, exist_ok=True)
     if args.batch:
         _run_batched(args, ldir, rdir, files)
         return
@@ -923,8 +1089,8 @@ def _run_batched(args, ldir, rdir, files):
     """--batch N: the folder through a StereoRig (the batched front end and engine) N pairs at a time."""
     import time
     import torch
-    from ..engine import (compact_cloud_from_disparity, disparity_to_u8, split_clouds, split_voxel_clouds, top_view_from_disparity,
-                          voxel_cloud_from_disparity)
+    from ..engine import (compact_cloud_from_disparity, disparity_to_u8, ground_from_disparity, occupancy_from_disparity, split_clouds,
+                          split_voxel_clouds, top_view_from_disparity, voxel_cloud_from_disparity)
     from ..rig import StereoRig
     rig = StereoRig(1242 // args.scale, 375 // args.scale, calibration=args.camera_calibration, rectify=args.rectify, scale=args.scale)
     n, busy = 0, 0.0
@@ -950,6 +1116,9 @@ def _run_batched(args, ldir, rdir, files):
             dmap = disparity_to_u8(d1)
             if args.top_view:  # what rig.top_view(..., disparity="d1", transform=(CAMERA_TO_VEHICLE, None)) gives, on the same d1
                 grids = top_view_from_disparity(d1, rig.Q, XR=CAMERA_TO_VEHICLE, disparity="d1", **CLI_TOP_VIEW)
+            if args.occupancy:  # what rig.occupancy(..., transform=(CAMERA_TO_VEHICLE, None), **CLI_TOP_VIEW) gives, on the same d1
+                g = ground_from_disparity(d1, rig.params.disp_max, want_vdisp=False)
+                occ = occupancy_from_disparity(d1, g.labels, g.free_row, g.free_disp, rig.Q, XR=CAMERA_TO_VEHICLE, **CLI_TOP_VIEW)
             torch.cuda.synchronize(rig.device)
             busy += time.perf_counter() - t0
             dmap = dmap.cpu().numpy()
@@ -959,6 +1128,9 @@ def _run_batched(args, ldir, rdir, files):
             if args.top_view:
                 for name, g in zip(names, grids.cpu().numpy()):
                     _write_png(os.path.join(args.top_view, name), g)
+            if args.occupancy:
+                for name, st in zip(names, occ.state.cpu().numpy()):
+                    _write_png(os.path.join(args.occupancy, name), OCCUPANCY_PNG[st])
             if args.ply:
                 parts = split_voxel_clouds(voxels[0], voxels[5], voxels[1]) if args.voxel else split_clouds(clouds[0], clouds[3], clouds[1])
                 for name, (xyz, color) in zip(names, parts):
