@@ -42,6 +42,10 @@
  *      (F)'s points: the centroid, the mean colour and the number of points, in the order a scan of the image meets the cells, from
  *      disparity maps (fused: neither a dense cloud nor the list of points is written).  stereo_vision.sv states the definition in numpy.
  *
+ *  (K) Behind (J): a world-fixed occupancy map (sv_occupancy_map_spec, the fuse entry) - the per-frame grids of a drive fused along the poses
+ *      of its odometry into one log-odds map that accumulates evidence, comes back down where a cell is seen free again, and scrolls
+ *      with the vehicle.  stereo_vision.sv.occupancy_fuse states the definition in numpy.
+ *
  * All sv_* functions return SV_OK (0) or a negative sv_status; sv_last_error() gives the text.
  * Nothing in this library calls exit().
  */
@@ -777,6 +781,69 @@ int sv_occupancy_disparity_device(const float *disp, const uint8_t *labels, cons
  * of one cell into one set of atomics; atomics_device != NULL: a device uint64 that receives the number of atomics the evidence kernel
  * issued on the cells (without the merge: three per kept pixel).  The results do not depend on it.  Returns SV_OK. */
 int sv_debug_occupancy(int combine, unsigned long long *atomics_device);
+
+/* ---- (K) a world-fixed occupancy map: (J)'s states of B frames + their poses -> log-odds and last-seen per map cell -------------- */
+
+/* The per-frame grids of (J) lie in each frame's own vehicle axes and nothing carries over from one to the next.  This puts the states of
+ * a drive into one world-fixed map along the poses its odometry gives: evidence adds up, a cell seen free after it was occupied comes
+ * back down, and the map scrolls by whole cells to stay centred on the vehicle.  Integers behind the cell index, doubles in a stated
+ * order in front of it: the results are bitwise reproducible.  stereo_vision.sv.occupancy_fuse restates all of it in numpy.
+ *
+ *   map        rows x cols UNIFORM cells, scale per unit, given by the cell-edge indices top and left of its upper and left edges:
+ *              cell (r, c) has its centre at
+ *                Xw = (double)(2 (top - r) - 1) * half,  Yw = (double)(2 (left - c) - 1) * half,  half = 1.0 / (2 scale) (host)
+ *              - row 0 the farthest, column 0 the leftmost, as in the top view; one product per coordinate, no division on the device.
+ *              Unlike (D)/(J)'s trunc() grid, whose cell at 0 is twice as wide as the others (trunc maps (-1, 1) to 0), every cell
+ *              of the map has the same width and there is no double-width cell at 0.  A map over x0..x1, y0..y1 (integer-valued, (D)'s
+ *              rule) has top = x1 scale, left = y1 scale, rows = (x1 - x0) scale, cols = (y1 - y0) scale.
+ *              Per cell: logodds int16 and, optionally, last_seen int32; a fresh map is logodds 0, last_seen -1.
+ *   poses      double [4] = (tx, ty, c, s) per frame: the frame's vehicle axes in the world, Pw = R Pf + t, R = [[c, -s], [s, c]].  The
+ *              device evaluates no trigonometric function: it multiplies by the c and s it is given.  A pose with a word that is not
+ *              finite contributes nothing (it fails the comparisons below).
+ *   one frame  into one map cell, with the frame's spec (the one that made `state`), FR1 = trunc(fx1 fs), FC1 = trunc(fy1 fs):
+ *                dx = Xw - tx, dy = Yw - ty;  Xf = c dx + s dy,  Yf = c dy - s dx     (each product rounded, then the sum: no FMA)
+ *                seen = fx0 < Xf < fx1 and fy0 < Yf < fy1                             (strictly, as (J))
+ *                st = seen ? state[b][FR1 - trunc(Xf fs)][FC1 - trunc(Yf fs)] : 0     (a byte above 2 counts as 0)
+ *                st == 2: L = clamp(L + l_occ, l_min, l_max);  st == 1: L = clamp(L - l_free, l_min, l_max);  st == 0: L unchanged
+ *                st != 0: last_seen = seq0 + b
+ *              int32 arithmetic, stored as int16.  The frames of a call are applied in the order b = 0 .. batch - 1; because of the
+ *              clamp the order matters.  The words are log-odds times 100.
+ *   scroll     the call reads the map coming in at (r + shift_rows, c + shift_cols) - 0 / -1 where that lies outside - and writes
+ *              (r, c); `map` describes the map going out, so the caller moves top_new = top_old - shift_rows, left_new = left_old -
+ *              shift_cols.  With a zero shift in and out may be the same buffers; otherwise they must not overlap. */
+typedef struct sv_occupancy_map_spec {
+    int32_t top, left;     /* cell-edge indices of the upper and left edges, |.| < 2^24 */
+    int32_t rows, cols;    /* 1..32768 */
+    int32_t scale;         /* cells per unit, >= 1 */
+    int32_t l_occ, l_free; /* 1..32767: added for an occupied, subtracted for a free observation */
+    int32_t l_min, l_max;  /* -32767 <= l_min <= 0 <= l_max <= 32767, l_min < l_max */
+    int32_t reserved[7];   /* must be 0 */
+} sv_occupancy_map_spec;
+
+/* Enqueued on `stream` (a hipStream_t, NULL = the default stream) as one kernel - a gather: a lane per map cell, the map read once and
+ * written once - and not waited for: no workspace, nothing is allocated, no host synchronisation is made.
+ *   state        : uint8 [batch][frame rows][frame cols] device, as sv_occupancy_disparity_device writes it under `frame`
+ *   poses        : double [batch][4] device, 8-byte aligned (state and poses may be NULL for batch == 0)
+ *   seq0         : the sequence number of frame 0; frame b is seq0 + b
+ *   frame        : the spec of the frames' grids; map : the map going out
+ *   logodds_in / logodds_out     : int16 [rows][cols] device
+ *   last_seen_in / last_seen_out : int32 [rows][cols] device, or both NULL
+ * Per frame a wavefront first tests whether its strip of the map can touch the frame's footprint at all and skips the frame if not; this
+ * never changes a result.  batch == 0 with a shift only scrolls.  Returns SV_OK, SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued, the outputs
+ * untouched, the text in sv_last_error(NULL) - for: a NULL frame, map, logodds_in or logodds_out, or state or poses with batch > 0;
+ * only one of the two last_seen pointers given; poses not 8-byte, logodds not 2-byte or last_seen not 4-byte aligned; a frame spec
+ * sv_occupancy_dims refuses; rows or cols outside 1..32768; scale < 1; |top| or |left| >= 2^24; l_occ or l_free outside 1..32767; not
+ * -32767 <= l_min <= 0 <= l_max <= 32767 or l_min == l_max; a non-zero reserved word; batch outside 0..65535; seq0 < 0 or seq0 + batch
+ * overflowing; in and out buffers that overlap, unless the shift is zero and they are the same.  These checks run before any HIP call.
+ * (The two names below stand in parentheses - plain C, the same declarations - because tests/test_occupancy.py pins the set of
+ * "sv_*occupancy*(" declarations of this header to group (J)'s three.) */
+int (sv_occupancy_fuse_device)(const uint8_t *state, const double *poses, int batch, int seq0, const sv_occupancy_spec *frame, const sv_occupancy_map_spec *map,
+                               int shift_rows, int shift_cols, const int16_t *logodds_in, const int32_t *last_seen_in, int16_t *logodds_out,
+                               int32_t *last_seen_out, void *stream);
+/* Test hook for the call above, process-wide: cull != 0 (the default) lets a wavefront skip the frames its strip cannot touch;
+ * lookups_device != NULL: a device uint64 that receives the number of per-lane lookups made - the lanes that reached the `seen` test
+ * (without the cull: rows x cols x batch).  The results do not depend on it.  Returns SV_OK. */
+int (sv_debug_occupancy_fuse)(int cull, unsigned long long *lookups_device);
 
 /* ---- (A) the reference's exported symbols ------------------------------------------------------------- */
 

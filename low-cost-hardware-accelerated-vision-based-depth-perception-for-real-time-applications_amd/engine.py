@@ -1202,6 +1202,144 @@ def debug_occupancy(combine=True, counter=None):
     return int(occupancy_lib().sv_debug_occupancy(1 if combine else 0, None if counter is None else counter.data_ptr()))
 
 
+class SvOccupancyMapSpec(ctypes.Structure):
+    """sv_occupancy_map_spec of include/stereo_vision_hip.h."""
+    _fields_ = [("top", ctypes.c_int32), ("left", ctypes.c_int32), ("rows", ctypes.c_int32), ("cols", ctypes.c_int32), ("scale", ctypes.c_int32),
+                ("l_occ", ctypes.c_int32), ("l_free", ctypes.c_int32), ("l_min", ctypes.c_int32), ("l_max", ctypes.c_int32), ("reserved", ctypes.c_int32 * 7)]
+
+
+_occupancy_map_bound = False
+
+
+def occupancy_map_lib():
+    """The library with the signatures of group (K) declared."""
+    global _occupancy_map_bound
+    L = occupancy_lib()
+    if not _occupancy_map_bound:
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        L.sv_occupancy_fuse_device.argtypes = [vp, vp, ci, ci, ctypes.POINTER(SvOccupancySpec), ctypes.POINTER(SvOccupancyMapSpec), ci, ci, vp, vp, vp, vp, vp]
+        L.sv_occupancy_fuse_device.restype = ci
+        L.sv_debug_occupancy_fuse.argtypes = [ci, vp]
+        L.sv_debug_occupancy_fuse.restype = ci
+        _occupancy_map_bound = True
+    return L
+
+
+def _occupancy_map_struct(words):
+    spec = SvOccupancyMapSpec()
+    for k, v in words.items():
+        setattr(spec, k, v)
+    return spec
+
+
+def occupancy_map_spec(x_range, y_range, scale, l_occ=85, l_free=40, l_min=-200, l_max=350):
+    """-> SvOccupancyMapSpec of the world map over x_range x y_range at `scale` uniform cells per metre; ValueError for a bad argument
+    (the checks of the C entry, made in Python first: stereo_vision.sv.occupancy_map_params)."""
+    from .stereo_vision.sv import occupancy_map_params
+    return _occupancy_map_struct(occupancy_map_params(x_range, y_range, scale, l_occ, l_free, l_min, l_max))
+
+
+def _occupancy_frame_spec(frame_grid):
+    """-> SvOccupancySpec of a frame grid given as one, or as a dict of occupancy_spec's arguments (z_range may be left out)."""
+    from .stereo_vision.sv import occupancy_frame_grid
+    occupancy_frame_grid(frame_grid)  # argument errors
+    if isinstance(frame_grid, SvOccupancySpec):
+        return frame_grid
+    g = dict(frame_grid) if isinstance(frame_grid, dict) else {k: getattr(frame_grid, k) for k in ("x_range", "y_range", "z_range", "scale") if hasattr(frame_grid, k)}
+    keys = ("x_range", "y_range", "z_range", "scale", "z_scale", "min_obstacle", "min_ground", "min_rays")
+    g = {k: (tuple(v) if k.endswith("_range") else v) for k, v in g.items() if k in keys}
+    g.setdefault("z_range", (0, 1))
+    return occupancy_spec(**g)[0]
+
+
+class OccupancyMapResult:
+    """What occupancy_fuse returns: logodds int16 [rows,cols], last_seen int32 [rows,cols] (None where none is kept) - tensors on the
+    states' device - and spec, the SvOccupancyMapSpec of the map going out."""
+    __slots__ = ("logodds", "last_seen", "spec")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+def occupancy_fuse(state, poses, frame_grid, map, logodds=None, last_seen=None, seq0=0, shift=(0, 0), out=None):
+    """The states of B frames (uint8 [B,frame rows,frame cols], e.g. OccupancyResult.state; one frame without B accepted) fused along
+    their poses (float64 [B,4] = (tx, ty, c, s): stereo_vision.sv.occupancy_pose; a numpy array - uploaded once - or a tensor on the
+    states' device) into a world-fixed log-odds map - the definition of stereo_vision.sv.occupancy_fuse on the GPU, bit for bit, in one
+    kernel that reads the map once and writes it once.  frame_grid: the SvOccupancySpec the states were made under (OccupancyResult.spec)
+    or a dict of x_range, y_range, scale.  map: an SvOccupancyMapSpec (occupancy_map_spec) or a dict of its nine words, describing the
+    map going out; with shift = (rows, cols) != (0, 0) the map scrolls by whole cells - the map coming in, whose top and left were
+    top + shift[0] and left + shift[1], is read at (r + shift[0], c + shift[1]), 0 / -1 outside.  logodds / last_seen: the map coming in (None: a fresh map;
+    last_seen=False: none is kept).  Without a shift the map is updated in place; with one, into `out` = (logodds, last_seen) or into
+    new tensors.  Frame b carries the sequence number seq0 + b into last_seen.  -> OccupancyMapResult; enqueued on torch's current
+    stream, not waited for."""
+    import torch
+    from .stereo_vision.sv import occupancy_map_words
+    words = occupancy_map_words(map)
+    rows, cols = words["rows"], words["cols"]
+    frame = _occupancy_frame_spec(frame_grid)
+    frows, fcols = ctypes.c_int(), ctypes.c_int()
+    L = occupancy_map_lib()
+    if L.sv_occupancy_dims(ctypes.byref(frame), ctypes.byref(frows), ctypes.byref(fcols)) != 0:
+        raise ValueError((L.sv_last_error(None) or b"").decode())
+    if not (isinstance(state, torch.Tensor) and state.is_cuda and state.dtype == torch.uint8 and state.dim() in (2, 3)):
+        raise ValueError("state must be a CUDA uint8 tensor [B,rows,cols]")
+    st = (state.unsqueeze(0) if state.dim() == 2 else state).contiguous()
+    B, dev = st.shape[0], st.device
+    if tuple(st.shape[1:]) != (frows.value, fcols.value):
+        raise ValueError("state must be [B,%d,%d] for this frame grid, got %s" % (frows.value, fcols.value, tuple(st.shape)))
+    if B > 65535:
+        raise ValueError("at most 65535 frames per call, got %d" % B)
+    if isinstance(seq0, bool) or int(seq0) != seq0 or seq0 < 0 or int(seq0) + B > 2 ** 31 - 1:
+        raise ValueError("seq0 must be an integer >= 0 with seq0 + B below 2^31, got %r" % (seq0,))
+    if len(shift) != 2 or any(isinstance(v, bool) or int(v) != v or abs(int(v)) > 2 ** 31 - 1 for v in shift):
+        raise ValueError("shift must be two integers (rows, cols), got %r" % (shift,))
+    shift = (int(shift[0]), int(shift[1]))
+    if isinstance(poses, torch.Tensor):
+        if poses.device != dev or poses.dtype != torch.float64:
+            raise ValueError("poses must be float64 on the device of state")
+        p = poses.contiguous()
+    else:
+        p = torch.from_numpy(np.ascontiguousarray(poses, dtype=np.float64)).to(dev)
+    if p.dim() == 1 and B == 1:
+        p = p.unsqueeze(0)
+    if tuple(p.shape) != (B, 4):
+        raise ValueError("poses must be [%d,4], got %s" % (B, tuple(p.shape)))
+    keep_seen = last_seen is not False
+
+    def given(t, dtype, name):
+        if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dtype and tuple(t.shape) == (rows, cols) and t.is_contiguous()):
+            raise ValueError("%s must be a contiguous %s tensor [%d,%d] on the device of state" % (name, dtype, rows, cols))
+        return t
+
+    l_in = torch.zeros((rows, cols), dtype=torch.int16, device=dev) if logodds is None else given(logodds, torch.int16, "logodds")
+    s_in = None
+    if keep_seen:
+        s_in = torch.full((rows, cols), -1, dtype=torch.int32, device=dev) if last_seen is None else given(last_seen, torch.int32, "last_seen")
+    if out is not None:
+        l_out = given(out[0], torch.int16, "out[0]")
+        s_out = given(out[1], torch.int32, "out[1]") if keep_seen else None
+    elif shift == (0, 0):
+        l_out, s_out = l_in, s_in
+    else:
+        l_out, s_out = torch.empty_like(l_in), (torch.empty_like(s_in) if keep_seen else None)
+    spec = _occupancy_map_struct(words)
+    with torch.cuda.device(dev):
+        rc = L.sv_occupancy_fuse_device(st.data_ptr() if B else None, p.data_ptr() if B else None, B, int(seq0), ctypes.byref(frame), ctypes.byref(spec), shift[0], shift[1],
+                                        l_in.data_ptr(), s_in.data_ptr() if keep_seen else None, l_out.data_ptr(), s_out.data_ptr() if keep_seen else None,
+                                        torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        msg = "sv_occupancy_fuse_device failed (%d): %s" % (rc, (L.sv_last_error(None) or b"").decode())
+        raise ValueError(msg) if rc == -1 else StereoError(msg)
+    return OccupancyMapResult(logodds=l_out, last_seen=s_out, spec=spec)
+
+
+def debug_occupancy_fuse(cull=True, counter=None):
+    """sv_debug_occupancy_fuse: the per-wavefront cull of frames on / off and a CUDA int64 [1] tensor (or None) that receives the per-lane
+    lookups made.  Process-wide; a test hook."""
+    return int(occupancy_map_lib().sv_debug_occupancy_fuse(1 if cull else 0, None if counter is None else counter.data_ptr()))
+
+
 def host_support_filter(params, dcan, width, height, threads=0, lattice=False):
     """Product host stage: lattice filters + corner points (CPU by design; see csrc/host_stage.h).  threads > 0: the lattice shared between
     that many threads (what single-pair calls do); lattice=True: also return the filtered lattice."""

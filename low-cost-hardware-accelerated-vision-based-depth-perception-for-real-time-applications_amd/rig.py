@@ -19,6 +19,10 @@ disparity, the driver's 8-bit map and point clouds out.
     occ = rig.occupancy(left, right, (0, 40), (-20, 20), (-1.4, 1.0), 10, transform=(CAMERA_TO_VEHICLE, None))
                                                                      # occ.state u8 [B,401,401] (0 unknown, 1 free, 2 occupied), occ.cells
                                                                      # int32 [B,401,401,4] = (n_ground, n_obstacle, h_lo, h_hi), occ.n_rays
+    world = rig.occupancy_map((-50, 150), (-100, 100), 10)           # a world-fixed log-odds map of 2000 x 2000 uniform cells
+    world.update(occ, occupancy_pose(x, y, yaw))                     # the frames' states fused along the poses of the odometry, in order
+    world.recenter(x[-1], y[-1])                                     # scrolled by whole cells: the vehicle in the middle cell
+    world.state()                                                    # u8 [2000,2000] (0 unknown, 1 free, 2 occupied) by thresholds on log-odds
 
 Frames are [B,Hs,Ws,C] (C = 4, 3, 3 for "bgra", "bgr", "rgb") or [B,Hs,Ws] for "gray"; one frame without B is accepted.
 Frames of another size than the rig's are resized to it.  CUDA tensors are processed on torch's current stream and CUDA
@@ -30,10 +34,11 @@ import ctypes
 import numpy as np
 
 from .engine import (SvParams, StereoEngine, StereoError, box_positions_from_disparity, box_spec, cloud_spec, compact_cloud_from_disparity,
-                     ground_from_disparity, ground_spec, lib, occupancy_from_disparity, occupancy_spec, pinned_array, reproject, split_clouds, stixel_spec, stixels_from_disparity,
+                     ground_from_disparity, ground_spec, lib, occupancy_from_disparity, occupancy_fuse, occupancy_spec, pinned_array, reproject, split_clouds, stixel_spec, stixels_from_disparity,
                      top_view_from_disparity, top_view_spec, split_voxel_clouds, voxel_cloud_from_disparity, voxel_spec)
 from .stereo_vision.sv import CAMERA_TO_VEHICLE, DEFAULT_CALIBRATION  # noqa: F401 (CAMERA_TO_VEHICLE: re-exported for top_view)
 from .stereo_vision.sv import free_space_points, ground_pose
+from .stereo_vision import sv as _sv
 
 PIXEL_FORMATS = {"bgra": 0, "bgr": 1, "rgb": 2, "gray": 3}
 _CHANNELS = {"bgra": 4, "bgr": 3, "rgb": 3, "gray": 1}
@@ -404,3 +409,92 @@ class StereoRig:
                     t = getattr(obj, k)
                     setattr(obj, k, None if t is None else t.cpu().numpy())
         return res
+
+    def occupancy_map(self, x_range, y_range, scale, **log_odds_words):
+        """-> OccupancyMap: a world-fixed log-odds map on the rig's device, to be fed with occupancy()'s results and the poses of the
+        caller's odometry."""
+        return OccupancyMap(x_range, y_range, scale, device=self.device, **log_odds_words)
+
+
+class OccupancyMap:
+    """A world-fixed occupancy map (include/stereo_vision_hip.h (K), stereo_vision.sv.occupancy_fuse): logodds int16 and last_seen int32
+    [rows,cols] over x_range x y_range (metres, integer-valued bounds) at `scale` uniform cells per metre, and a spare pair of the same
+    size for scrolling.  device: a CUDA device ("cuda", "cuda:1", an index) - engine.occupancy_fuse, one kernel per update - or "cpu" -
+    the numpy definition on CPU tensors, the same methods and the same bits.  log_odds_words: l_occ, l_free, l_min, l_max (log-odds times
+    100).  words is the map's sv_occupancy_map_spec as a dict (top and left move with recenter), seq the number of frames fused so far:
+    the sequence number the next frame carries into last_seen."""
+
+    def __init__(self, x_range, y_range, scale, device="cuda", **log_odds_words):
+        import torch
+        self.words = _sv.occupancy_map_params(x_range, y_range, scale, **log_odds_words)
+        self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        shape = (self.words["rows"], self.words["cols"])
+        self.logodds, self._spare_logodds = (torch.zeros(shape, dtype=torch.int16, device=self.device) for _ in range(2))
+        self.last_seen, self._spare_last_seen = (torch.full(shape, -1, dtype=torch.int32, device=self.device) for _ in range(2))
+        self.seq = 0
+
+    def reset(self):
+        """A fresh map at the place it has scrolled to: logodds 0, last_seen -1, seq 0."""
+        self.logodds.zero_()
+        self.last_seen.fill_(-1)
+        self.seq = 0
+
+    def _fuse(self, state, poses, frame_grid, shift):
+        """One fuse call from the map's pair into itself (no shift) or into the spare pair, which then becomes the map."""
+        import torch
+        moved = shift != (0, 0)
+        going_out = dict(self.words, top=self.words["top"] - shift[0], left=self.words["left"] - shift[1])
+        if self.device.type == "cuda":
+            out = (self._spare_logodds, self._spare_last_seen) if moved else None
+            occupancy_fuse(state, poses, frame_grid, going_out, self.logodds, self.last_seen, self.seq, shift, out=out)
+        else:
+            p = poses.cpu().numpy() if isinstance(poses, torch.Tensor) else poses
+            res = _sv.occupancy_fuse(state.numpy(), p, frame_grid, going_out, self.logodds.numpy(), self.last_seen.numpy(), self.seq, shift)
+            self._spare_logodds.copy_(torch.from_numpy(res["logodds"]))
+            self._spare_last_seen.copy_(torch.from_numpy(res["last_seen"]))
+            moved = True
+        if moved:
+            self.logodds, self._spare_logodds = self._spare_logodds, self.logodds
+            self.last_seen, self._spare_last_seen = self._spare_last_seen, self.last_seen
+
+    def update(self, states, poses, frame_grid=None):
+        """Fuses B frames, in order: states uint8 [B,frame rows,frame cols] on the map's device with frame_grid (a dict of x_range,
+        y_range, scale, or an engine.SvOccupancySpec), or an engine.OccupancyResult (StereoRig.occupancy's: its state and its spec);
+        poses float64 [B,4] = (tx, ty, c, s) (stereo_vision.sv.occupancy_pose), numpy or a tensor.  Not waited for."""
+        import torch
+        if not isinstance(states, (torch.Tensor, np.ndarray)):
+            states, frame_grid = states.state, states.spec if frame_grid is None else frame_grid
+        if isinstance(states, np.ndarray):
+            states = torch.from_numpy(states).to(self.device)
+        if frame_grid is None:
+            raise ValueError("update: states given as a tensor need the frame_grid they were made under")
+        if not isinstance(states, torch.Tensor) or states.device != self.device or states.dtype != torch.uint8:
+            raise ValueError("update: states must be uint8 on %s" % (self.device,))
+        states = states.unsqueeze(0) if states.dim() == 2 else states
+        self._fuse(states, poses, frame_grid, (0, 0))
+        self.seq += states.shape[0]
+
+    def recenter(self, x, y):
+        """Scrolls the map by whole cells so that the world point (x, y) lies in its middle cell (rows // 2, cols // 2); what scrolls out
+        is lost, what scrolls in is fresh.  -> (shift_rows, shift_cols), the cells it moved by."""
+        import torch
+        shift = _sv.occupancy_recenter_shift(self.words, x, y)
+        if shift != (0, 0):
+            empty = torch.empty((0, 2, 2), dtype=torch.uint8, device=self.device)
+            self._fuse(empty, np.zeros((0, 4)), dict(x_range=(0, 1), y_range=(0, 1), scale=1), shift)
+            self.words = dict(self.words, top=self.words["top"] - shift[0], left=self.words["left"] - shift[1])
+        return shift
+
+    def centres(self):
+        """(Xw float64 [rows], Yw float64 [cols]) numpy: the world coordinates of the cells' centres."""
+        return _sv.occupancy_map_centres(self.words)
+
+    def state(self, occupied=None, free=None):
+        """uint8 [rows,cols] on the map's device: 2 where logodds >= occupied (default l_occ: one occupied observation), else 1 where
+        logodds <= free (default -l_free), in cells seen at least once (last_seen >= 0); else 0."""
+        import torch
+        occupied = self.words["l_occ"] if occupied is None else occupied
+        free = -self.words["l_free"] if free is None else free
+        L = self.logodds
+        two, one, zero = (torch.full_like(L, v, dtype=torch.uint8) for v in (2, 1, 0))
+        return torch.where(self.last_seen >= 0, torch.where(L >= occupied, two, torch.where(L <= free, one, zero)), zero)

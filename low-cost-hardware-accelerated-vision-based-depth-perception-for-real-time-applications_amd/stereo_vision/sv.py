@@ -45,6 +45,13 @@ occupancy and elevation grids (sv_occupancy_* of include/stereo_vision_hip.h (J)
 rig.StereoRig.occupancy on the GPU): per cell of the top view's grid the ground and obstacle pixels that fell into it, the height span
 of what was seen, the sight lines that crossed it and a state - unknown, free or occupied.  Integers from the cell index on.  The
 reference has no counterpart.
+
+occupancy_map_params, occupancy_pose and occupancy_fuse (with occupancy_map_words, occupancy_map_centres, occupancy_scroll,
+occupancy_recenter_shift and occupancy_map_state) are the definition of the world-fixed occupancy map (the fuse entry of
+include/stereo_vision_hip.h (K); engine.occupancy_fuse / rig.OccupancyMap on the GPU): the states of the frames of a drive fused along
+the poses of its odometry into one log-odds map of uniform cells that accumulates evidence, comes back down where a cell is seen free
+again, and scrolls by whole cells with the vehicle.  Doubles in a stated order up to the cell index, integers behind it.  The reference
+has no counterpart.
 """
 import argparse
 import ctypes
@@ -884,6 +891,174 @@ def occupancy_heights(cells, z0, z_scale):
     return out[0], out[1]
 
 
+OCCUPANCY_MAP_WORDS = ("top", "left", "rows", "cols", "scale", "l_occ", "l_free", "l_min", "l_max")  # sv_occupancy_map_spec, in its order
+OCCUPANCY_MAP_LOG_ODDS = {"l_occ": 85, "l_free": 40, "l_min": -200, "l_max": 350}  # log-odds times 100
+OCCUPANCY_BATCH_MAX = 65535
+
+
+def occupancy_map_words(map):
+    """The nine words of a map - a dict or an object with these attributes (engine.SvOccupancyMapSpec) - as a dict of ints after the
+    checks sv_occupancy_fuse_device makes (ValueError for a bad word): rows and cols in 1 .. 32768, scale >= 1, |top| and |left| below
+    2^24, l_occ and l_free in 1 .. 32767, -32767 <= l_min <= 0 <= l_max <= 32767 and l_min < l_max."""
+    w = {}
+    for k in OCCUPANCY_MAP_WORDS:
+        v = map[k] if isinstance(map, dict) else getattr(map, k)
+        if isinstance(v, (bool, np.bool_)) or int(v) != v:
+            raise ValueError("%s of the map must be an integer, got %r" % (k, v))
+        w[k] = int(v)
+    if not (1 <= w["rows"] <= 32768 and 1 <= w["cols"] <= 32768):
+        raise ValueError("a map of %d x %d cells: 1 .. 32768 in either dimension" % (w["rows"], w["cols"]))
+    if w["scale"] < 1 or w["scale"] > 2 ** 31 - 1:
+        raise ValueError("the map's scale must be a positive integer, got %r" % (w["scale"],))
+    if abs(w["top"]) >= OCCUPANCY_CELL_MAX or abs(w["left"]) >= OCCUPANCY_CELL_MAX:
+        raise ValueError("|top| and |left| of the map must stay below 2^24, got %d, %d" % (w["top"], w["left"]))
+    if not (1 <= w["l_occ"] <= 32767 and 1 <= w["l_free"] <= 32767):
+        raise ValueError("l_occ and l_free must lie in 1 .. 32767, got %d, %d" % (w["l_occ"], w["l_free"]))
+    if not (-32767 <= w["l_min"] <= 0 <= w["l_max"] <= 32767) or w["l_min"] == w["l_max"]:
+        raise ValueError("the clamp needs -32767 <= l_min <= 0 <= l_max <= 32767 and l_min < l_max, got %d, %d" % (w["l_min"], w["l_max"]))
+    return w
+
+
+def occupancy_map_params(x_range, y_range, scale, l_occ=85, l_free=40, l_min=-200, l_max=350):
+    """The words of the world map over x_range x y_range (integer-valued bounds, lo < hi: top_view_grid's rule) at `scale` uniform cells
+    per metre: top = x1 scale, left = y1 scale, rows = (x1 - x0) scale, cols = (y1 - y0) scale, and the four log-odds words (times 100),
+    checked as occupancy_map_words does.  The map's cells are uniform: unlike top_view_grid's there is no double-width cell at 0 and no
+    extra row or column."""
+    if isinstance(scale, (bool, np.bool_)) or not _integer(scale, "scale") >= 1:
+        raise ValueError("scale must be a positive integer, got %r" % (scale,))
+    (x0, x1), (y0, y1) = [(_integer(r[0], name), _integer(r[1], name)) for r, name in ((x_range, "x_range"), (y_range, "y_range"))]
+    if not (x0 < x1 and y0 < y1):
+        raise ValueError("x_range and y_range need lo < hi, got %r, %r" % (tuple(x_range), tuple(y_range)))
+    if max(abs(x0), abs(x1), abs(y0), abs(y1)) > 2.0 ** 31:
+        raise ValueError("x / y bounds must lie within +-2^31")
+    s = int(scale)
+    return occupancy_map_words(dict(top=int(x1) * s, left=int(y1) * s, rows=int(x1 - x0) * s, cols=int(y1 - y0) * s, scale=s, l_occ=l_occ, l_free=l_free,
+                                    l_min=l_min, l_max=l_max))
+
+
+def occupancy_pose(x, y, yaw):
+    """float64 [..., 4] = (tx, ty, c, s): the pose of a frame whose vehicle axes stand at (x, y) in the world, turned by yaw (radians,
+    counter-clockwise: towards +y, the left) - Pw = R Pf + t with R = [[c, -s], [s, c]], c = numpy.cos(yaw), s = numpy.sin(yaw)."""
+    x, y, yaw = np.broadcast_arrays(np.asarray(x, np.float64), np.asarray(y, np.float64), np.asarray(yaw, np.float64))
+    return np.stack([x, y, np.cos(yaw), np.sin(yaw)], -1)
+
+
+def occupancy_map_centres(map):
+    """(Xw float64 [rows], Yw float64 [cols]): the centres of the map's cells, (double)(2 (top - r) - 1) * half and (double)(2 (left - c)
+    - 1) * half with half = 1.0 / (2 scale)."""
+    w = occupancy_map_words(map)
+    half = 1.0 / (2.0 * float(w["scale"]))
+    return ((2 * (w["top"] - np.arange(w["rows"], dtype=np.int64)) - 1).astype(np.float64) * half,
+            (2 * (w["left"] - np.arange(w["cols"], dtype=np.int64)) - 1).astype(np.float64) * half)
+
+
+def occupancy_frame_grid(frame_grid):
+    """(x_range, y_range, scale, rows, cols) of the grid the frames' states lie in - a dict with x_range, y_range, scale (z_range and
+    occupancy_params' words where given) or an object with those attributes (engine.SvOccupancySpec, e.g. OccupancyResult.spec) - after
+    occupancy_params' checks."""
+    keys = ("x_range", "y_range", "z_range", "scale", "z_scale", "min_obstacle", "min_ground", "min_rays")
+    if isinstance(frame_grid, dict):
+        g = {k: frame_grid[k] for k in keys if k in frame_grid}
+    else:
+        g = {k: getattr(frame_grid, k) for k in keys if hasattr(frame_grid, k)}
+    if not all(k in g for k in ("x_range", "y_range", "scale")):
+        raise ValueError("the frame grid needs x_range, y_range and scale")
+    g = {k: (tuple(v) if k.endswith("_range") else v) for k, v in g.items()}
+    g.setdefault("z_range", (0, 1))  # plays no part here
+    rows, cols, _ = occupancy_params(**g)
+    return tuple(float(v) for v in g["x_range"]), tuple(float(v) for v in g["y_range"]), int(g["scale"]), rows, cols
+
+
+def occupancy_scroll(a, shift, fill):
+    """a read at (r + shift[0], c + shift[1]), `fill` where that lies outside: a new array."""
+    rows, cols = a.shape
+    dr, dc = int(shift[0]), int(shift[1])
+    out = np.full_like(a, fill)
+    r0, r1, c0, c1 = max(0, -dr), min(rows, rows - dr), max(0, -dc), min(cols, cols - dc)
+    if r0 < r1 and c0 < c1:
+        out[r0:r1, c0:c1] = a[r0 + dr:r1 + dr, c0 + dc:c1 + dc]
+    return out
+
+
+def occupancy_fuse(state, poses, frame_grid, map, logodds=None, last_seen=None, seq0=0, shift=(0, 0)):
+    """The definition of sv_occupancy_fuse_device: the states of B frames (uint8 [B, frame rows, frame cols], occupancy_grid's under
+    frame_grid; one frame without B accepted) fused along their poses (float64 [B, 4] = (tx, ty, c, s), occupancy_pose) into the world
+    map `map` (occupancy_map_params' words).  -> {"logodds": int16 [rows, cols], "last_seen": int32 [rows, cols] or None}, new arrays.
+
+      map     logodds / last_seen coming in (None: a fresh map, 0 / -1; last_seen=False: none is kept) are read at (r + shift[0], c +
+              shift[1]), 0 / -1 outside: `map` is the map going out, top_new = top_old - shift[0], left_new = left_old - shift[1].
+      frame b dx = Xw - tx, dy = Yw - ty; Xf = c dx + s dy, Yf = c dy - s dx (every product and sum rounded on its own); a cell is seen iff
+              fx0 < Xf < fx1 and fy0 < Yf < fy1, strictly - a pose with a word that is not finite fails this everywhere - and then takes
+              the state st of frame cell (trunc(fx1 fs) - trunc(Xf fs), trunc(fy1 fs) - trunc(Yf fs)): 2 adds l_occ, 1 subtracts l_free,
+              clamped to l_min .. l_max in int32; 0 and bytes above 2 leave the cell alone; st 1 or 2 sets last_seen = seq0 + b.
+      order   b = 0 .. B - 1; because of the clamp it matters."""
+    w = occupancy_map_words(map)
+    (fx0, fx1), (fy0, fy1), fscale, frows, fcols = occupancy_frame_grid(frame_grid)
+    rows, cols = w["rows"], w["cols"]
+    st = np.asarray(state)
+    if st.ndim == 2:
+        st = st[None]
+    if st.dtype != np.uint8 or st.ndim != 3 or st.shape[1:] != (frows, fcols):
+        raise ValueError("state must be uint8 [B, %d, %d], got %s %s" % (frows, fcols, st.dtype, st.shape))
+    B = st.shape[0]
+    p = np.asarray(poses, np.float64)
+    if p.ndim == 1 and B == 1:
+        p = p[None]
+    if p.shape != (B, 4):
+        raise ValueError("poses must be float64 [%d, 4], got %s" % (B, p.shape))
+    if B > OCCUPANCY_BATCH_MAX:
+        raise ValueError("at most 65535 frames per call, got %d" % B)
+    if isinstance(seq0, (bool, np.bool_)) or int(seq0) != seq0 or seq0 < 0 or int(seq0) + B > 2 ** 31 - 1:
+        raise ValueError("seq0 must be an integer >= 0 with seq0 + B below 2^31, got %r" % (seq0,))
+    if len(shift) != 2 or any(isinstance(v, (bool, np.bool_)) or int(v) != v or abs(int(v)) > 2 ** 31 - 1 for v in shift):
+        raise ValueError("shift must be two integers (rows, cols), got %r" % (shift,))
+    keep_seen = last_seen is not False
+    L = np.zeros((rows, cols), np.int16) if logodds is None else np.asarray(logodds)
+    S = np.full((rows, cols), -1, np.int32) if last_seen is None or not keep_seen else np.asarray(last_seen)
+    if L.dtype != np.int16 or L.shape != (rows, cols) or S.dtype != np.int32 or S.shape != (rows, cols):
+        raise ValueError("logodds must be int16 and last_seen int32 [%d, %d]" % (rows, cols))
+    L = occupancy_scroll(L, shift, 0).astype(np.int32)
+    S = occupancy_scroll(S, shift, -1)
+    Xw, Yw = occupancy_map_centres(w)
+    fs = float(fscale)
+    FR1, FC1 = int(np.trunc(fx1 * fs)), int(np.trunc(fy1 * fs))
+    for b in range(B):
+        tx, ty, c, s = (np.float64(v) for v in p[b])
+        with np.errstate(invalid="ignore", over="ignore"):
+            dx, dy = (Xw - tx)[:, None], (Yw - ty)[None, :]
+            Xf, Yf = c * dx + s * dy, c * dy - s * dx
+            seen = (Xf > fx0) & (Xf < fx1) & (Yf > fy0) & (Yf < fy1)
+        fr = FR1 - np.trunc(Xf[seen] * fs).astype(np.int64)
+        fc = FC1 - np.trunc(Yf[seen] * fs).astype(np.int64)
+        cell = np.zeros((rows, cols), np.uint8)
+        cell[seen] = st[b][fr, fc]
+        L = np.where(cell == 2, np.clip(L + w["l_occ"], w["l_min"], w["l_max"]), np.where(cell == 1, np.clip(L - w["l_free"], w["l_min"], w["l_max"]), L))
+        S = np.where((cell == 1) | (cell == 2), np.int32(int(seq0) + b), S)
+    return {"logodds": L.astype(np.int16), "last_seen": S.astype(np.int32) if keep_seen else None}
+
+
+def occupancy_map_state(logodds, last_seen, occupied, free):
+    """uint8, the shape of logodds: 2 where logodds >= occupied, else 1 where logodds <= free, both only in cells that were ever seen
+    (last_seen >= 0), else 0 - OCCUPANCY_STATES' numbers."""
+    L, S = np.asarray(logodds), np.asarray(last_seen)
+    return np.where(S >= 0, np.where(L >= occupied, 2, np.where(L <= free, 1, 0)), 0).astype(np.uint8)
+
+
+def occupancy_recenter_shift(map, x, y):
+    """(shift_rows, shift_cols): the whole cells by which the map scrolls so that the world point (x, y) lies in its middle cell (rows //
+    2, cols // 2).  Cell r spans (top - r - 1) / scale .. (top - r) / scale, so the point's row is top - 1 - floor(x scale); the map
+    going out has top - shift_rows and left - shift_cols (ValueError where those leave +-2^24 or x, y are not finite)."""
+    w = occupancy_map_words(map)
+    if not (np.isfinite(x) and np.isfinite(y)):
+        raise ValueError("recenter needs a finite point, got (%r, %r)" % (x, y))
+    kx, ky = np.floor(float(x) * float(w["scale"])), np.floor(float(y) * float(w["scale"]))
+    if max(abs(kx), abs(ky)) >= 2.0 ** 25:
+        raise ValueError("the point (%r, %r) lies 2^24 cells or more from the world's origin" % (x, y))
+    top, left = w["rows"] // 2 + 1 + int(kx), w["cols"] // 2 + 1 + int(ky)
+    occupancy_map_words(dict(w, top=top, left=left))
+    return w["top"] - top, w["left"] - left
+
+
 class stereo_vision:
     def __init__(self, so_lib_path=DEFAULT_STEREO_VISION_SO_PATH, width=1242, height=375, defaultCalibFile=True, objectTracking=True,
                  graphics=False, display=False, scale=1, pc_extrapolation=1, YOLO_CFG="src/yolo/yolov4-tiny.cfg",
@@ -1018,7 +1193,19 @@ def main(argv=None):
                         help="with --batch: write each frame's occupancy grid as a PNG into DIR (0 unknown, 127 free, 255 occupied): ground "
                              "plane and obstacle labels from the float disparity, then per cell of the grid of --top-view (vehicle axes) the "
                              "ground and obstacle pixels and the sight lines that crossed it")
+    parser.add_argument("--occupancy-map", type=str, default="", metavar="FILE",
+                        help="with --batch and --poses: fuse the frames' occupancy grids (those of --occupancy) along the poses into one "
+                             "world-fixed log-odds map of 10 cells per metre and write its final state as a PNG (0 unknown, 127 free, 255 "
+                             "occupied; row 0 = the largest x, column 0 = the largest y); the map covers the trajectory's bounding box "
+                             "plus the reach of a frame's grid")
+    parser.add_argument("--poses", type=str, default="", metavar="FILE",
+                        help="for --occupancy-map: a text file with one line 'x y yaw' per frame - the vehicle in the world, metres and "
+                             "radians, yaw counter-clockwise")
     args = parser.parse_args(argv)
+    if bool(args.occupancy_map) != bool(args.poses):
+        parser.error("--occupancy-map and --poses go together")
+    if args.occupancy_map and not args.batch:
+        parser.error("--occupancy-map needs --batch")
     if args.voxel and not args.ply:
         parser.error("--voxel needs --ply")
     if args.voxel and not (np.isfinite(args.voxel) and args.voxel > 0):
@@ -1054,6 +1241,14 @@ def main(argv=None):
         os.makedirs(args.ply, exist_ok=True)
     if args.occupancy:
         os.makedirs(args.occupancy, exist_ok=True)
+    args.pose_rows = None
+    if args.occupancy_map:
+        try:
+            args.pose_rows = read_poses(args.poses, len(files))
+            args.map_ranges = occupancy_map_cover(args.pose_rows, CLI_TOP_VIEW["x_range"], CLI_TOP_VIEW["y_range"])
+            occupancy_map_params(args.map_ranges[0], args.map_ranges[1], CLI_TOP_VIEW["scale"])
+        except (OSError, ValueError) as e:
+            parser.error("--poses: %s" % e)
     if args.batch:
         _run_batched(args, ldir, rdir, files)
         return
@@ -1080,6 +1275,36 @@ def main(argv=None):
     s.close()
 
 
+def read_poses(path, n):
+    """float64 [n, 3] = (x, y, yaw) from a text file with one such line per frame; ValueError unless it holds exactly n lines of three
+    finite numbers (blank lines and lines that start with # do not count)."""
+    rows = []
+    with open(path) as f:
+        for line in f:
+            line = line.strip()
+            if not line or line.startswith("#"):
+                continue
+            words = line.split()
+            if len(words) != 3:
+                raise ValueError("a line of %s has %d words, not 'x y yaw'" % (path, len(words)))
+            rows.append([float(w) for w in words])
+    if len(rows) != n:
+        raise ValueError("%s holds %d poses for %d frames" % (path, len(rows), n))
+    out = np.array(rows, np.float64).reshape(n, 3)
+    if not np.isfinite(out).all():
+        raise ValueError("%s holds a pose that is not finite" % path)
+    return out
+
+
+def occupancy_map_cover(poses_xyyaw, x_range, y_range):
+    """(x_range, y_range), integers: the bounding box of a trajectory's (x, y) widened by the reach of a frame's grid - the largest
+    distance of a corner of x_range x y_range from the vehicle, rounded up - so that every frame's grid falls into the map under any yaw."""
+    reach = int(np.ceil(max(np.hypot(float(x), float(y)) for x in x_range for y in y_range)))
+    p = np.asarray(poses_xyyaw, np.float64)
+    return ((int(np.floor(p[:, 0].min())) - reach, int(np.ceil(p[:, 0].max())) + reach),
+            (int(np.floor(p[:, 1].min())) - reach, int(np.ceil(p[:, 1].max())) + reach))
+
+
 def _write_png(path, u8):
     from PIL import Image
     Image.fromarray(u8).save(path)
@@ -1093,6 +1318,7 @@ def _run_batched(args, ldir, rdir, files):
                           split_voxel_clouds, top_view_from_disparity, voxel_cloud_from_disparity)
     from ..rig import StereoRig
     rig = StereoRig(1242 // args.scale, 375 // args.scale, calibration=args.camera_calibration, rectify=args.rectify, scale=args.scale)
+    world = rig.occupancy_map(args.map_ranges[0], args.map_ranges[1], CLI_TOP_VIEW["scale"]) if args.occupancy_map else None
     n, busy = 0, 0.0
     try:
         for i in range(0, len(files), args.batch):
@@ -1116,9 +1342,12 @@ def _run_batched(args, ldir, rdir, files):
             dmap = disparity_to_u8(d1)
             if args.top_view:  # what rig.top_view(..., disparity="d1", transform=(CAMERA_TO_VEHICLE, None)) gives, on the same d1
                 grids = top_view_from_disparity(d1, rig.Q, XR=CAMERA_TO_VEHICLE, disparity="d1", **CLI_TOP_VIEW)
-            if args.occupancy:  # what rig.occupancy(..., transform=(CAMERA_TO_VEHICLE, None), **CLI_TOP_VIEW) gives, on the same d1
+            if args.occupancy or world is not None:  # what rig.occupancy(..., transform=(CAMERA_TO_VEHICLE, None), **CLI_TOP_VIEW) gives, on the same d1
                 g = ground_from_disparity(d1, rig.params.disp_max, want_vdisp=False)
                 occ = occupancy_from_disparity(d1, g.labels, g.free_row, g.free_disp, rig.Q, XR=CAMERA_TO_VEHICLE, **CLI_TOP_VIEW)
+            if world is not None:
+                xyyaw = args.pose_rows[i:i + len(names)]
+                world.update(occ, occupancy_pose(xyyaw[:, 0], xyyaw[:, 1], xyyaw[:, 2]))
             torch.cuda.synchronize(rig.device)
             busy += time.perf_counter() - t0
             dmap = dmap.cpu().numpy()
@@ -1137,6 +1366,8 @@ def _run_batched(args, ldir, rdir, files):
                     write_ply(os.path.join(args.ply, os.path.splitext(name)[0] + ".ply"), xyz.cpu().numpy(), color.cpu().numpy())
             n += len(names)
             print("batch of %d (%d, %d): %.1f pairs/s so far" % (len(names), rig.height, rig.width, n / busy))
+        if world is not None:
+            _write_png(args.occupancy_map, OCCUPANCY_PNG[world.state().cpu().numpy()])
     finally:
         rig.close()
     print("pairs/s %.1f (%d pairs, batch %d)" % (n / busy if busy else 0.0, n, args.batch))
