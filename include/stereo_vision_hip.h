@@ -46,6 +46,10 @@
  *      of its odometry into one log-odds map that accumulates evidence, comes back down where a cell is seen free again, and scrolls
  *      with the vehicle.  stereo_vision.sv.occupancy_fuse states the definition in numpy.
  *
+ *  (L) Behind (K): the correlative match (sv_map_match_*) - how well a frame's grid of (J) fits the map of (K) at each of a set of candidate
+ *      poses, and the best of them, so that a drifting pose can be corrected before the frame is fused.  stereo_vision.sv.occupancy_match
+ *      states the definition in numpy.
+ *
  * All sv_* functions return SV_OK (0) or a negative sv_status; sv_last_error() gives the text.
  * Nothing in this library calls exit().
  */
@@ -844,6 +848,58 @@ int (sv_occupancy_fuse_device)(const uint8_t *state, const double *poses, int ba
  * lookups_device != NULL: a device uint64 that receives the number of per-lane lookups made - the lanes that reached the `seen` test
  * (without the cull: rows x cols x batch).  The results do not depend on it.  Returns SV_OK. */
 int (sv_debug_occupancy_fuse)(int cull, unsigned long long *lookups_device);
+
+/* ---- (L) a frame matched against the world map: (J)'s states + candidate poses + (K)'s log-odds -> sums, counts and the best pose ---- */
+
+/* The fuse of (K) trusts its poses to the cell.  This scores a frame against the map at every pose of a set of candidates - a window around
+ * the odometry's guess: a correlative scan match (Olson 2009) - and names the best, reading only what lies on the device already.  Doubles
+ * in a stated order in front of the cell index, integer sums behind it: the results are bitwise reproducible, whatever the order of the
+ * additions.  stereo_vision.sv.occupancy_match restates all of it in numpy.
+ *
+ *   point      frame cell (fr, fc), with FR1 = trunc(fx1 fs), FC1 = trunc(fy1 fs), kx = FR1 - fr, ky = FC1 - fc, stands for the point
+ *                Xf = (double)(2 kx + sgn(kx)) * hf,  Yf = (double)(2 ky + sgn(ky)) * hf,  hf = 1.0 / (2 fs) (host)
+ *              - the middle of the cell, 0 for the double-width cell at 0 - and trunc(Xf fs) == kx: the fuse looks the point up in the
+ *              same cell.
+ *   world      Xw = (c Xf - s Yf) + tx,  Yw = (s Xf + c Yf) + ty   (each product rounded, then the difference or sum, then the
+ *              translation: no FMA), poses as in (K): Pw = R Pf + t.  No trigonometric function on the device.
+ *   map        gx = floor(Xw ms), gy = floor(Yw ms), ms = (double)scale of the map.  The cell counts iff top - rows <= gx <= top - 1 and
+ *              left - cols <= gy <= left - 1, compared in double - NaN, inf and far-away poses fail before any conversion to integer - and
+ *              is then map cell (top - 1 - gx, left - 1 - gy).
+ *   sums       per frame b and candidate p: H = the sum of logodds over the map cells the state-2 frame cells land on, n_occ = how many
+ *              landed; M and n_free the same for the state-1 cells.  Bytes 0 and above 2 play no part.  logodds is taken as stored,
+ *              over the whole int16 range.  With w_free == 0 free cells are not visited: M = n_free = 0.
+ *   score      w_occ H - w_free M in int64; best[b] = the lowest p whose score is the largest, best_score[b] that score.  A frame without
+ *              a contributing cell has all scores 0 and best 0: put the guess first and ties keep it. */
+
+/* Host only: the bytes of the workspace sv_map_match_device needs for `batch` frames under `frame` - per frame the list of its contributing
+ * cells, its counters and the partial maxima.  SV_ERR_ARG (bytes untouched) for a NULL argument, a frame spec sv_occupancy_dims refuses,
+ * batch outside 0..65535 or w_free outside 0..32767. */
+int sv_map_match_workspace(const sv_occupancy_spec *frame, int batch, int w_free, size_t *bytes);
+/* Enqueued on `stream` (a hipStream_t, NULL = the default stream) as a clear of the lists' counters and three kernels - lists, scores, best -
+ * and not waited for: nothing is allocated, no host synchronisation is made, and nothing is assumed of what the outputs or the workspace
+ * held before.
+ *   state        : uint8 [batch][frame rows][frame cols] device, as sv_occupancy_disparity_device writes it under `frame`
+ *   poses        : double [batch][n_poses][4] device, 8-byte aligned: frame b's own candidates (tx, ty, c, s)
+ *   frame, map   : the spec of the frames' grids and the map's, as for the fuse entry of (K); logodds : int16 [rows][cols] device
+ *   w_occ, w_free: 0..32767, not both 0
+ *   sums         : int64 [batch][n_poses][2] = (H, M) device, counts : int32 [batch][n_poses][2] = (n_occ, n_free) device; both or neither
+ *   best         : int32 [batch] device, best_score : int64 [batch] device; both or neither (at least one of the two pairs is given)
+ *   workspace    : device, 16-byte aligned, workspace_bytes >= what sv_map_match_workspace gives
+ * Every output given is written in full.  Returns SV_OK (nothing enqueued for batch == 0), SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued,
+ * the outputs untouched, the text in sv_last_error(NULL) - for: a NULL frame, map or logodds, or state, poses or workspace with batch > 0;
+ * only one pointer of a pair, or neither pair; poses, sums or best_score not 8-byte, counts or best not 4-byte, logodds not 2-byte, the
+ * workspace not 16-byte aligned; a frame spec sv_occupancy_dims refuses; a map spec the fuse entry refuses; batch outside 0..65535;
+ * n_poses outside 1..65535; batch x n_poses >= 2^31; a weight outside 0..32767 or both 0; too small a workspace.  These checks run before
+ * any HIP call.  The environment variable SV_MAP_MATCH_STAGE = lists or scores leaves out the kernels behind that stage (a measurement
+ * aid: the outputs are then unfinished). */
+int sv_map_match_device(const uint8_t *state, const double *poses, int batch, int n_poses, const sv_occupancy_spec *frame, const sv_occupancy_map_spec *map,
+                        const int16_t *logodds, int w_occ, int w_free, int64_t *sums, int32_t *counts, int32_t *best, int64_t *best_score, void *workspace,
+                        size_t workspace_bytes, void *stream);
+/* Test hook for the call above, process-wide: group = 0 (the default) lets the call choose how many candidates a workgroup scores, a power
+ * of two in 1..256 fixes it (1: the candidate uniform per workgroup, its lanes striding over the list); lookups_device != NULL: a device
+ * uint64 that receives the number of map lookups made - list entries x candidates, summed over the frames.  The results do not depend on
+ * it.  Returns SV_OK, or SV_ERR_ARG for another group. */
+int sv_debug_map_match(int group, unsigned long long *lookups_device);
 
 /* ---- (A) the reference's exported symbols ------------------------------------------------------------- */
 

@@ -1340,6 +1340,116 @@ def debug_occupancy_fuse(cull=True, counter=None):
     return int(occupancy_map_lib().sv_debug_occupancy_fuse(1 if cull else 0, None if counter is None else counter.data_ptr()))
 
 
+_map_match_bound = False
+
+
+def map_match_lib():
+    """The library with the signatures of group (L) declared."""
+    global _map_match_bound
+    L = occupancy_map_lib()
+    if not _map_match_bound:
+        vp, ci, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
+        L.sv_map_match_workspace.argtypes = [ctypes.POINTER(SvOccupancySpec), ci, ci, ctypes.POINTER(sz)]
+        L.sv_map_match_workspace.restype = ci
+        L.sv_map_match_device.argtypes = [vp, vp, ci, ci, ctypes.POINTER(SvOccupancySpec), ctypes.POINTER(SvOccupancyMapSpec), vp, ci, ci, vp, vp, vp, vp, vp, sz, vp]
+        L.sv_map_match_device.restype = ci
+        L.sv_debug_map_match.argtypes = [ci, vp]
+        L.sv_debug_map_match.restype = ci
+        _map_match_bound = True
+    return L
+
+
+class MapMatchResult:
+    """What occupancy_match returns, tensors on the states' device: sums int64 [B,P,2] = (H, M), counts int32 [B,P,2] = (n_occ, n_free)
+    (both None where not asked for), best int32 [B] and best_score int64 [B] (both None where not asked for)."""
+    __slots__ = ("sums", "counts", "best", "best_score")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+    def score(self, w_occ=1, w_free=0):
+        """int64 [B,P]: w_occ H - w_free M of the sums."""
+        return w_occ * self.sums[..., 0] - w_free * self.sums[..., 1]
+
+
+def occupancy_match(state, poses, frame_grid, map, logodds, w_occ=1, w_free=0, want_sums=True, want_best=True):
+    """The states of B frames (CUDA uint8 [B,frame rows,frame cols], e.g. OccupancyResult.state; one frame without B accepted) scored
+    against a world map's logodds (int16 [rows,cols] on the same device, e.g. OccupancyMapResult.logodds) at P candidate poses per frame
+    (float64 [B,P,4] = (tx, ty, c, s): stereo_vision.sv.occupancy_pose of occupancy_pose_window's rows; a numpy array - uploaded once -
+    or a tensor on the states' device; [P,4] accepted for one frame) - the definition of stereo_vision.sv.occupancy_match on the GPU, bit
+    for bit: per candidate the sum of the map's log-odds under the frame's occupied cells (and, with w_free > 0, under its free cells) and
+    how many landed in the map, and per frame the lowest candidate with the largest score w_occ H - w_free M.  frame_grid and map as for
+    occupancy_fuse.  Nothing dense is read back; the workspace comes from torch.  -> MapMatchResult; enqueued on torch's current stream,
+    not waited for."""
+    import torch
+    from .stereo_vision.sv import occupancy_map_words
+    words = occupancy_map_words(map)
+    rows, cols = words["rows"], words["cols"]
+    frame = _occupancy_frame_spec(frame_grid)
+    frows, fcols = ctypes.c_int(), ctypes.c_int()
+    L = map_match_lib()
+    if L.sv_occupancy_dims(ctypes.byref(frame), ctypes.byref(frows), ctypes.byref(fcols)) != 0:
+        raise ValueError((L.sv_last_error(None) or b"").decode())
+    if not (isinstance(state, torch.Tensor) and state.is_cuda and state.dtype == torch.uint8 and state.dim() in (2, 3)):
+        raise ValueError("state must be a CUDA uint8 tensor [B,rows,cols]")
+    st = (state.unsqueeze(0) if state.dim() == 2 else state).contiguous()
+    B, dev = st.shape[0], st.device
+    if tuple(st.shape[1:]) != (frows.value, fcols.value):
+        raise ValueError("state must be [B,%d,%d] for this frame grid, got %s" % (frows.value, fcols.value, tuple(st.shape)))
+    if isinstance(poses, torch.Tensor):
+        if poses.device != dev or poses.dtype != torch.float64:
+            raise ValueError("poses must be float64 on the device of state")
+        p = poses.contiguous()
+    else:
+        p = torch.from_numpy(np.ascontiguousarray(poses, dtype=np.float64)).to(dev)
+    if p.dim() == 2 and B == 1:
+        p = p.unsqueeze(0)
+    if p.dim() != 3 or p.shape[0] != B or p.shape[2] != 4:
+        raise ValueError("poses must be [%d,P,4], got %s" % (B, tuple(p.shape)))
+    n_poses = p.shape[1]
+    if B > 65535 or not 1 <= n_poses <= 65535 or B * n_poses >= 2 ** 31:
+        raise ValueError("at most 65535 frames of 1 .. 65535 poses each and fewer than 2^31 in all, got %d x %d" % (B, n_poses))
+    for v in (w_occ, w_free):
+        if isinstance(v, bool) or int(v) != v or not 0 <= v <= 32767:
+            raise ValueError("w_occ and w_free must be integers in 0 .. 32767, got %r, %r" % (w_occ, w_free))
+    if int(w_occ) == 0 and int(w_free) == 0:
+        raise ValueError("w_occ and w_free must not both be 0")
+    if not (want_sums or want_best):
+        raise ValueError("neither the sums nor the best are asked for")
+    if not (isinstance(logodds, torch.Tensor) and logodds.device == dev and logodds.dtype == torch.int16 and tuple(logodds.shape) == (rows, cols) and logodds.is_contiguous()):
+        raise ValueError("logodds must be a contiguous int16 tensor [%d,%d] on the device of state" % (rows, cols))
+    res = MapMatchResult()
+    if want_sums:
+        res.sums = torch.empty((B, n_poses, 2), dtype=torch.int64, device=dev)
+        res.counts = torch.empty((B, n_poses, 2), dtype=torch.int32, device=dev)
+    if want_best:
+        res.best = torch.empty((B,), dtype=torch.int32, device=dev)
+        res.best_score = torch.empty((B,), dtype=torch.int64, device=dev)
+    if B == 0:  # nothing to enqueue
+        return res
+    nbytes = ctypes.c_size_t()
+    if L.sv_map_match_workspace(ctypes.byref(frame), B, int(w_free), ctypes.byref(nbytes)) != 0:
+        raise ValueError((L.sv_last_error(None) or b"").decode())
+    ws = torch.empty((nbytes.value + 15) // 16 * 2, dtype=torch.int64, device=dev)
+    spec = _occupancy_map_struct(words)
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    with torch.cuda.device(dev):
+        rc = L.sv_map_match_device(st.data_ptr(), p.data_ptr(), B, n_poses, ctypes.byref(frame), ctypes.byref(spec), logodds.data_ptr(), int(w_occ), int(w_free),
+                                   ptr(res.sums), ptr(res.counts), ptr(res.best), ptr(res.best_score), ws.data_ptr(), ws.numel() * 8,
+                                   torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        msg = "sv_map_match_device failed (%d): %s" % (rc, (L.sv_last_error(None) or b"").decode())
+        raise ValueError(msg) if rc == -1 else StereoError(msg)
+    return res  # ws goes back to torch's allocator, which hands it out again on this stream only: behind the kernels
+
+
+def debug_map_match(group=0, counter=None):
+    """sv_debug_map_match: the candidates a workgroup scores (0: the call chooses; a power of two in 1 .. 256) and a CUDA int64 [1] tensor
+    (or None) that receives the map lookups made.  Process-wide; a test hook."""
+    return int(map_match_lib().sv_debug_map_match(int(group), None if counter is None else counter.data_ptr()))
+
+
 def host_support_filter(params, dcan, width, height, threads=0, lattice=False):
     """Product host stage: lattice filters + corner points (CPU by design; see csrc/host_stage.h).  threads > 0: the lattice shared between
     that many threads (what single-pair calls do); lattice=True: also return the filtered lattice."""

@@ -23,6 +23,8 @@ disparity, the driver's 8-bit map and point clouds out.
     world.update(occ, occupancy_pose(x, y, yaw))                     # the frames' states fused along the poses of the odometry, in order
     world.recenter(x[-1], y[-1])                                     # scrolled by whole cells: the vehicle in the middle cell
     world.state()                                                    # u8 [2000,2000] (0 unknown, 1 free, 2 occupied) by thresholds on log-odds
+    xyyaw, m = world.localize(occ, guess, (0.5, 0.5, 0.04), (7, 7, 5))  # per frame the best pose of a 245-pose window around the odometry's
+                                                                     # guess [B,3]; m.sums / m.counts / m.best / m.best_score on the device
 
 Frames are [B,Hs,Ws,C] (C = 4, 3, 3 for "bgra", "bgr", "rgb") or [B,Hs,Ws] for "gray"; one frame without B is accepted.
 Frames of another size than the rig's are resized to it.  CUDA tensors are processed on torch's current stream and CUDA
@@ -34,7 +36,7 @@ import ctypes
 import numpy as np
 
 from .engine import (SvParams, StereoEngine, StereoError, box_positions_from_disparity, box_spec, cloud_spec, compact_cloud_from_disparity,
-                     ground_from_disparity, ground_spec, lib, occupancy_from_disparity, occupancy_fuse, occupancy_spec, pinned_array, reproject, split_clouds, stixel_spec, stixels_from_disparity,
+                     ground_from_disparity, ground_spec, lib, occupancy_from_disparity, occupancy_fuse, occupancy_match, occupancy_spec, pinned_array, reproject, split_clouds, stixel_spec, stixels_from_disparity,
                      top_view_from_disparity, top_view_spec, split_voxel_clouds, voxel_cloud_from_disparity, voxel_spec)
 from .stereo_vision.sv import CAMERA_TO_VEHICLE, DEFAULT_CALIBRATION  # noqa: F401 (CAMERA_TO_VEHICLE: re-exported for top_view)
 from .stereo_vision.sv import free_space_points, ground_pose
@@ -428,6 +430,8 @@ class OccupancyMap:
         import torch
         self.words = _sv.occupancy_map_params(x_range, y_range, scale, **log_odds_words)
         self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:  # "cuda": the current device, named as its tensors name it
+            self.device = torch.device("cuda", torch.cuda.current_device())
         shape = (self.words["rows"], self.words["cols"])
         self.logodds, self._spare_logodds = (torch.zeros(shape, dtype=torch.int16, device=self.device) for _ in range(2))
         self.last_seen, self._spare_last_seen = (torch.full(shape, -1, dtype=torch.int32, device=self.device) for _ in range(2))
@@ -461,18 +465,50 @@ class OccupancyMap:
         """Fuses B frames, in order: states uint8 [B,frame rows,frame cols] on the map's device with frame_grid (a dict of x_range,
         y_range, scale, or an engine.SvOccupancySpec), or an engine.OccupancyResult (StereoRig.occupancy's: its state and its spec);
         poses float64 [B,4] = (tx, ty, c, s) (stereo_vision.sv.occupancy_pose), numpy or a tensor.  Not waited for."""
+        states, frame_grid = self._states(states, frame_grid, "update")
+        self._fuse(states, poses, frame_grid, (0, 0))
+        self.seq += states.shape[0]
+
+    def _states(self, states, frame_grid, what):
+        """update's first two arguments -> (uint8 tensor [B,frame rows,frame cols] on the map's device, frame grid)."""
         import torch
         if not isinstance(states, (torch.Tensor, np.ndarray)):
             states, frame_grid = states.state, states.spec if frame_grid is None else frame_grid
         if isinstance(states, np.ndarray):
             states = torch.from_numpy(states).to(self.device)
         if frame_grid is None:
-            raise ValueError("update: states given as a tensor need the frame_grid they were made under")
+            raise ValueError("%s: states given as a tensor need the frame_grid they were made under" % what)
         if not isinstance(states, torch.Tensor) or states.device != self.device or states.dtype != torch.uint8:
-            raise ValueError("update: states must be uint8 on %s" % (self.device,))
-        states = states.unsqueeze(0) if states.dim() == 2 else states
-        self._fuse(states, poses, frame_grid, (0, 0))
-        self.seq += states.shape[0]
+            raise ValueError("%s: states must be uint8 on %s" % (what, self.device))
+        return (states.unsqueeze(0) if states.dim() == 2 else states), frame_grid
+
+    def match(self, states, poses, frame_grid=None, w_occ=1, w_free=0):
+        """Scores B frames against the map as it stands (stereo_vision.sv.occupancy_match): states as for update, poses float64 [B,P,4] =
+        (tx, ty, c, s), numpy or a tensor - frame b's own P candidates.  -> engine.MapMatchResult with sums [B,P,2], counts [B,P,2], best
+        [B] and best_score [B] as tensors on the map's device.  The map is not changed; not waited for."""
+        import torch
+        from .engine import MapMatchResult
+        states, frame_grid = self._states(states, frame_grid, "match")
+        if self.device.type == "cuda":
+            return occupancy_match(states, poses, frame_grid, self.words, self.logodds, w_occ, w_free)
+        p = poses.cpu().numpy() if isinstance(poses, torch.Tensor) else poses
+        res = _sv.occupancy_match(states.numpy(), p, frame_grid, self.words, self.logodds.numpy(), w_occ, w_free)
+        return MapMatchResult(**{k: torch.from_numpy(np.ascontiguousarray(res[k])) for k in MapMatchResult.__slots__})
+
+    def localize(self, states, guess_xyyaw, half, steps, frame_grid=None, w_occ=1, w_free=0):
+        """The best pose per frame of a window around its guess: guess_xyyaw float64 [B,3] = (x, y, yaw) ([3] for one frame), half = (dx,
+        dy, dyaw) and steps = (nx, ny, nyaw) as stereo_vision.sv.occupancy_pose_window takes them - the guess is candidate 0 and keeps
+        ties.  -> (float64 numpy [B,3], the refined (x, y, yaw); the MapMatchResult).  Waits for the best indices - B words - and reads
+        nothing else back."""
+        states, frame_grid = self._states(states, frame_grid, "localize")
+        g = np.asarray(guess_xyyaw, np.float64)
+        g = g[None] if g.ndim == 1 else g
+        if g.shape != (states.shape[0], 3):
+            raise ValueError("localize: guess_xyyaw must be [%d,3], got %s" % (states.shape[0], g.shape))
+        window = np.stack([_sv.occupancy_pose_window(x, y, yaw, half, steps) for x, y, yaw in g]) if len(g) else np.zeros((0, 1, 3))
+        res = self.match(states, _sv.occupancy_pose(window[..., 0], window[..., 1], window[..., 2]), frame_grid, w_occ, w_free)
+        best = res.best.cpu().numpy().astype(np.int64)
+        return window[np.arange(len(g)), best], res
 
     def recenter(self, x, y):
         """Scrolls the map by whole cells so that the world point (x, y) lies in its middle cell (rows // 2, cols // 2); what scrolls out

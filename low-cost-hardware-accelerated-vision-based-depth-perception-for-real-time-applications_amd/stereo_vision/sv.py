@@ -52,6 +52,12 @@ include/stereo_vision_hip.h (K); engine.occupancy_fuse / rig.OccupancyMap on the
 the poses of its odometry into one log-odds map of uniform cells that accumulates evidence, comes back down where a cell is seen free
 again, and scrolls by whole cells with the vehicle.  Doubles in a stated order up to the cell index, integers behind it.  The reference
 has no counterpart.
+
+occupancy_match and occupancy_pose_window are the definition of the correlative match (sv_map_match_* of include/stereo_vision_hip.h (L);
+engine.occupancy_match / rig.OccupancyMap.match and .localize on the GPU): a frame's occupied (and free) cells carried into the map at
+every pose of a window around the odometry's guess, the map's log-odds summed under them, and the best pose named - so that a drifting
+pose can be corrected before the frame is fused.  Integer sums behind the cell index: bit for bit.  The reference has no counterpart
+(DESIGN.md §8).
 """
 import argparse
 import ctypes
@@ -894,6 +900,7 @@ def occupancy_heights(cells, z0, z_scale):
 OCCUPANCY_MAP_WORDS = ("top", "left", "rows", "cols", "scale", "l_occ", "l_free", "l_min", "l_max")  # sv_occupancy_map_spec, in its order
 OCCUPANCY_MAP_LOG_ODDS = {"l_occ": 85, "l_free": 40, "l_min": -200, "l_max": 350}  # log-odds times 100
 OCCUPANCY_BATCH_MAX = 65535
+OCCUPANCY_POSES_MAX = 65535  # candidates per frame of occupancy_match
 
 
 def occupancy_map_words(map):
@@ -1035,6 +1042,107 @@ def occupancy_fuse(state, poses, frame_grid, map, logodds=None, last_seen=None, 
         L = np.where(cell == 2, np.clip(L + w["l_occ"], w["l_min"], w["l_max"]), np.where(cell == 1, np.clip(L - w["l_free"], w["l_min"], w["l_max"]), L))
         S = np.where((cell == 1) | (cell == 2), np.int32(int(seq0) + b), S)
     return {"logodds": L.astype(np.int16), "last_seen": S.astype(np.int32) if keep_seen else None}
+
+
+def occupancy_pose_window(x, y, yaw, half, steps):
+    """float64 [P, 3] = (x, y, yaw): the candidates of a window around the guess (x, y, yaw) - half = (dx, dy, dyaw), the window's half
+    widths (metres, metres, radians; finite, >= 0), steps = (nx, ny, nyaw), odd integers >= 1 with P = nx ny nyaw <= 65535.  Row 0 is the
+    guess itself, so that ties keep it; the other P - 1 follow in row-major (i, j, k) order over numpy.linspace(-half, +half, n) per axis
+    (n = 1: the offset 0), the middle one - the guess - left out.  occupancy_pose turns the rows into poses."""
+    g = [float(v) for v in (x, y, yaw)]
+    if len(half) != 3 or len(steps) != 3:
+        raise ValueError("half and steps must have three entries each, got %r, %r" % (half, steps))
+    h = [float(v) for v in half]
+    if not all(np.isfinite(v) for v in g + h) or min(h) < 0:
+        raise ValueError("the guess and half must be finite and half >= 0, got %r, %r" % (g, h))
+    for v in steps:
+        if isinstance(v, (bool, np.bool_)) or int(v) != v or v < 1 or int(v) % 2 != 1:
+            raise ValueError("steps must be odd integers >= 1, got %r" % (steps,))
+    n = [int(v) for v in steps]
+    if n[0] * n[1] * n[2] > OCCUPANCY_POSES_MAX:
+        raise ValueError("a window of %d poses: at most 65535" % (n[0] * n[1] * n[2]))
+    off = [np.linspace(-h[a], h[a], n[a]) if n[a] > 1 else np.zeros(1) for a in range(3)]
+    grid = np.stack(np.meshgrid(g[0] + off[0], g[1] + off[1], g[2] + off[2], indexing="ij"), -1).reshape(-1, 3)
+    mid = (n[0] // 2 * n[1] + n[1] // 2) * n[2] + n[2] // 2
+    return np.concatenate([np.array([g]), grid[:mid], grid[mid + 1:]])
+
+
+def occupancy_frame_points(frame_grid):
+    """(Xf float64 [rows], Yf float64 [cols]): the point each row and each column of the frames' grid stands for in the match - with kx =
+    trunc(fx1 fs) - fr, Xf = (double)(2 kx + sgn(kx)) * hf, hf = 1.0 / (2 fs): the middle of the cell, 0 for the double-width cell at 0;
+    the same along y.  trunc(Xf fs) == kx: occupancy_fuse looks the point up in the same cell."""
+    (_, fx1), (_, fy1), fscale, frows, fcols = occupancy_frame_grid(frame_grid)
+    fs = float(fscale)
+    hf = 1.0 / (2.0 * fs)
+    kx = int(np.trunc(fx1 * fs)) - np.arange(frows, dtype=np.int64)
+    ky = int(np.trunc(fy1 * fs)) - np.arange(fcols, dtype=np.int64)
+    return (2 * kx + np.sign(kx)).astype(np.float64) * hf, (2 * ky + np.sign(ky)).astype(np.float64) * hf
+
+
+def occupancy_match(state, poses, frame_grid, map, logodds, w_occ=1, w_free=0):
+    """The definition of sv_map_match_device: the states of B frames (uint8 [B, frame rows, frame cols] under frame_grid; one frame
+    without B accepted) scored against the world map `map` (occupancy_map_params' words) with its logodds (int16 [rows, cols]) at P
+    candidate poses per frame (float64 [B, P, 4] = (tx, ty, c, s), occupancy_pose's; [P, 4] accepted for one frame).
+    -> {"sums": int64 [B, P, 2] = (H, M), "counts": int32 [B, P, 2] = (n_occ, n_free), "score": int64 [B, P], "best": int32 [B],
+        "best_score": int64 [B]}.
+
+      point   frame cell (fr, fc) stands for (Xf[fr], Yf[fc]) of occupancy_frame_points.
+      world   Xw = (c Xf - s Yf) + tx, Yw = (s Xf + c Yf) + ty, every product, difference and sum rounded on its own.
+      map     gx = floor(Xw ms), gy = floor(Yw ms); the cell counts iff top - rows <= gx <= top - 1 and left - cols <= gy <= left - 1 - a
+              pose with a word that is not finite fails this everywhere - and is map cell (top - 1 - gx, left - 1 - gy): the row rule of
+              occupancy_recenter_shift.
+      sums    H = the sum of logodds (as stored, not clamped) under the state-2 cells that count, n_occ their number; M and n_free the
+              same for the state-1 cells, 0 with w_free == 0 (they are not visited).  Bytes 0 and above 2 play no part.
+      score   w_occ H - w_free M, weights in 0 .. 32767 and not both 0; best = the lowest p with the largest score."""
+    w = occupancy_map_words(map)
+    _, _, _, frows, fcols = occupancy_frame_grid(frame_grid)
+    rows, cols, top, left = w["rows"], w["cols"], w["top"], w["left"]
+    st = np.asarray(state)
+    if st.ndim == 2:
+        st = st[None]
+    if st.dtype != np.uint8 or st.ndim != 3 or st.shape[1:] != (frows, fcols):
+        raise ValueError("state must be uint8 [B, %d, %d], got %s %s" % (frows, fcols, st.dtype, st.shape))
+    B = st.shape[0]
+    p = np.asarray(poses, np.float64)
+    if p.ndim == 2 and B == 1:
+        p = p[None]
+    if p.ndim != 3 or p.shape[0] != B or p.shape[2] != 4:
+        raise ValueError("poses must be float64 [%d, P, 4], got %s" % (B, p.shape))
+    P = p.shape[1]
+    if B > OCCUPANCY_BATCH_MAX or not 1 <= P <= OCCUPANCY_POSES_MAX or B * P >= 2 ** 31:
+        raise ValueError("at most 65535 frames of 1 .. 65535 poses each and fewer than 2^31 in all, got %d x %d" % (B, P))
+    for v in (w_occ, w_free):
+        if isinstance(v, (bool, np.bool_)) or int(v) != v or not 0 <= v <= 32767:
+            raise ValueError("w_occ and w_free must be integers in 0 .. 32767, got %r, %r" % (w_occ, w_free))
+    w_occ, w_free = int(w_occ), int(w_free)
+    if w_occ == 0 and w_free == 0:
+        raise ValueError("w_occ and w_free must not both be 0")
+    L = np.asarray(logodds)
+    if L.dtype != np.int16 or L.shape != (rows, cols):
+        raise ValueError("logodds must be int16 [%d, %d], got %s %s" % (rows, cols, L.dtype, L.shape))
+    Xp, Yp = occupancy_frame_points(frame_grid)
+    ms = float(w["scale"])
+    sums, counts = np.zeros((B, P, 2), np.int64), np.zeros((B, P, 2), np.int32)
+    for b in range(B):
+        for slot, byte in ((0, 2), (1, 1)):
+            if byte == 1 and w_free == 0:
+                continue
+            fr, fc = np.nonzero(st[b] == byte)
+            if fr.size == 0:
+                continue
+            Xf, Yf = Xp[fr][None, :], Yp[fc][None, :]
+            tx, ty, c, s = (p[b, :, k][:, None] for k in range(4))
+            with np.errstate(invalid="ignore", over="ignore"):
+                Xw, Yw = (c * Xf - s * Yf) + tx, (s * Xf + c * Yf) + ty
+                gx, gy = np.floor(Xw * ms), np.floor(Yw * ms)
+                inside = (gx >= top - rows) & (gx <= top - 1) & (gy >= left - cols) & (gy <= left - 1)
+            r = np.where(inside, top - 1 - np.where(inside, gx, 0.0), 0).astype(np.int64)
+            cc = np.where(inside, left - 1 - np.where(inside, gy, 0.0), 0).astype(np.int64)
+            sums[b, :, slot] = np.where(inside, L[r, cc].astype(np.int64), 0).sum(1)
+            counts[b, :, slot] = inside.sum(1)
+    score = w_occ * sums[..., 0] - w_free * sums[..., 1]
+    best = score.argmax(1).astype(np.int32)  # the first of the largest
+    return {"sums": sums, "counts": counts, "score": score, "best": best, "best_score": score[np.arange(B), best] if B else np.zeros(0, np.int64)}
 
 
 def occupancy_map_state(logodds, last_seen, occupied, free):
@@ -1201,7 +1309,24 @@ def main(argv=None):
     parser.add_argument("--poses", type=str, default="", metavar="FILE",
                         help="for --occupancy-map: a text file with one line 'x y yaw' per frame - the vehicle in the world, metres and "
                              "radians, yaw counter-clockwise")
+    parser.add_argument("--match", type=str, default="", metavar="DX,DY,DYAW[,NX,NY,NYAW]",
+                        help="with --occupancy-map and --poses: take the poses as guesses - frame 0 is fused where its line says; every later "
+                             "frame is first matched against the map built so far over a window of +-DX, +-DY metres and +-DYAW radians "
+                             "around its line (NX x NY x NYAW poses, odd, default 7,7,5; the line itself wins ties) and fused at the best "
+                             "pose.  The refined poses are written next to FILE as <FILE without .png>.poses.txt, one 'x y yaw' per frame")
     args = parser.parse_args(argv)
+    args.match_window = None
+    if args.match:
+        if not args.occupancy_map:
+            parser.error("--match needs --occupancy-map and --poses")
+        try:
+            words = args.match.split(",")
+            if len(words) not in (3, 6):
+                raise ValueError("%d words, not DX,DY,DYAW[,NX,NY,NYAW]" % len(words))
+            args.match_window = (tuple(float(w) for w in words[:3]), tuple(int(w) for w in words[3:]) or (7, 7, 5))
+            occupancy_pose_window(0.0, 0.0, 0.0, *args.match_window)
+        except ValueError as e:
+            parser.error("--match: %s" % e)
     if bool(args.occupancy_map) != bool(args.poses):
         parser.error("--occupancy-map and --poses go together")
     if args.occupancy_map and not args.batch:
@@ -1319,7 +1444,7 @@ def _run_batched(args, ldir, rdir, files):
     from ..rig import StereoRig
     rig = StereoRig(1242 // args.scale, 375 // args.scale, calibration=args.camera_calibration, rectify=args.rectify, scale=args.scale)
     world = rig.occupancy_map(args.map_ranges[0], args.map_ranges[1], CLI_TOP_VIEW["scale"]) if args.occupancy_map else None
-    n, busy = 0, 0.0
+    n, busy, refined = 0, 0.0, []
     try:
         for i in range(0, len(files), args.batch):
             names = files[i:i + args.batch]
@@ -1347,7 +1472,12 @@ def _run_batched(args, ldir, rdir, files):
                 occ = occupancy_from_disparity(d1, g.labels, g.free_row, g.free_disp, rig.Q, XR=CAMERA_TO_VEHICLE, **CLI_TOP_VIEW)
             if world is not None:
                 xyyaw = args.pose_rows[i:i + len(names)]
-                world.update(occ, occupancy_pose(xyyaw[:, 0], xyyaw[:, 1], xyyaw[:, 2]))
+                if args.match_window is None:
+                    world.update(occ, occupancy_pose(xyyaw[:, 0], xyyaw[:, 1], xyyaw[:, 2]))
+                for k in range(len(names) if args.match_window is not None else 0):  # one at a time: a frame is matched against the frames before it
+                    at = xyyaw[k] if world.seq == 0 else world.localize(occ.state[k:k + 1], xyyaw[k], *args.match_window, frame_grid=occ.spec)[0][0]
+                    refined.append(at)
+                    world.update(occ.state[k:k + 1], occupancy_pose(at[0], at[1], at[2])[None], occ.spec)
             torch.cuda.synchronize(rig.device)
             busy += time.perf_counter() - t0
             dmap = dmap.cpu().numpy()
@@ -1368,6 +1498,9 @@ def _run_batched(args, ldir, rdir, files):
             print("batch of %d (%d, %d): %.1f pairs/s so far" % (len(names), rig.height, rig.width, n / busy))
         if world is not None:
             _write_png(args.occupancy_map, OCCUPANCY_PNG[world.state().cpu().numpy()])
+        if args.match_window is not None:
+            with open(os.path.splitext(args.occupancy_map)[0] + ".poses.txt", "w") as f:
+                f.write("".join("%r %r %r\n" % tuple(float(v) for v in at) for at in refined))
     finally:
         rig.close()
     print("pairs/s %.1f (%d pairs, batch %d)" % (n / busy if busy else 0.0, n, args.batch))
