@@ -50,6 +50,10 @@
  *      poses, and the best of them, so that a drifting pose can be corrected before the frame is fused.  stereo_vision.sv.occupancy_match
  *      states the definition in numpy.
  *
+ *  (M) Behind (K) as well: what a planner asks of the map (sv_clearance_*) - the capped exact squared distance from every cell to the
+ *      nearest occupied (or never seen) cell, and a batched check of candidate paths' footprints against that field.
+ *      stereo_vision.sv.occupancy_clearance and clearance_paths state the definitions in numpy.
+ *
  * All sv_* functions return SV_OK (0) or a negative sv_status; sv_last_error() gives the text.
  * Nothing in this library calls exit().
  */
@@ -900,6 +904,62 @@ int sv_map_match_device(const uint8_t *state, const double *poses, int batch, in
  * uint64 that receives the number of map lookups made - list entries x candidates, summed over the frames.  The results do not depend on
  * it.  Returns SV_OK, or SV_ERR_ARG for another group. */
 int sv_debug_map_match(int group, unsigned long long *lookups_device);
+
+/* ---- (M) the clearance field of the world map and path checks: (K)'s log-odds -> squared distances; paths + a footprint -> hits ---- */
+
+/* A planner does not ask whether a cell is occupied but how far the nearest obstacle is, and which of many candidate paths keeps the
+ * vehicle's footprint clear.  Both are integer problems - the second behind one floor() - so the results are bitwise reproducible whatever
+ * algorithm computes them.  stereo_vision.sv.occupancy_clearance / occupancy_clearance_brute / clearance_paths restate them in numpy.
+ *
+ *   source     a cell with logodds >= t_occ or, with unknown == 1, last_seen < 0.  Cells outside the map are not sources: the map's edge
+ *              is no obstacle.
+ *   field      d2[r][c] = the minimum over all sources (r', c') of (r - r')^2 + (c - c')^2, as uint16; 65535 where that exceeds R^2 or
+ *              there is no source (R <= 254: R^2 <= 64516 cannot be taken for it); 0 on a source.
+ *   disc       a footprint is n_discs discs in vehicle axes: centre (px, py), squared radius r2 in cells.  At pose (tx, ty, c, s) - as in
+ *              (K) and (L) - the centre lies at Xw = (c px - s py) + tx, Yw = (s px + c py) + ty (each product rounded, then the
+ *              difference or sum, then the translation: no FMA), gx = floor(Xw ms), gy = floor(Yw ms), ms = (double)scale of the map.  The
+ *              lookup is inside iff top - rows <= gx <= top - 1 and left - cols <= gy <= left - 1, compared in double - NaN, inf and
+ *              far-away poses are outside - and then reads map cell (top - 1 - gx, left - 1 - gy): (L)'s rule.  No trigonometric function
+ *              on the device.
+ *   path       per path of n_steps poses: first_hit = the lowest step at which some disc that is inside has d2[cell] <= r2 (n_steps if
+ *              none), min_d2 = the minimum of d2[cell] over all inside lookups (65535 if there were none), n_outside = the number of
+ *              (step, disc) lookups that fell outside.  Every r2 must be <= radius^2 of the field, or a saturated cell would hide a hit. */
+
+/* Host only: the bytes of the workspace sv_clearance_device needs - a byte per cell, rounded up to 16.  SV_ERR_ARG (bytes untouched) for a
+ * NULL bytes or rows or cols outside 1..32768. */
+int sv_clearance_workspace(int rows, int cols, size_t *bytes);
+/* Enqueued on `stream` (a hipStream_t, NULL = the default stream) as two kernels - per column the rows to the nearest source, then per row
+ * the minimum of dc^2 + that^2, a wavefront stopping as soon as nothing further out can win - and not waited for: nothing is allocated, no
+ * host synchronisation is made, and nothing is assumed of what d2 or the workspace held before.
+ *   logodds      : int16 [rows][cols] device; last_seen : int32 [rows][cols] device, or NULL with unknown == 0 (it is then not read)
+ *   radius       : R in cells, 1..254; t_occ : -32768..32767; unknown : 0 or 1
+ *   d2           : uint16 [rows][cols] device, written in full
+ *   workspace    : device, 16-byte aligned, workspace_bytes >= what sv_clearance_workspace gives
+ * Returns SV_OK, SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued, the outputs untouched, the text in sv_last_error(NULL) - for: a NULL logodds,
+ * d2 or workspace; unknown == 1 without last_seen; logodds or d2 not 2-byte, last_seen not 4-byte, the workspace not 16-byte aligned; rows
+ * or cols outside 1..32768; radius outside 1..254; t_occ outside the int16 range; unknown neither 0 nor 1; too small a workspace; d2
+ * overlapping logodds, last_seen or the workspace.  These checks run before any HIP call.  The environment variable SV_CLEARANCE_PASS =
+ * cols or rows enqueues that kernel alone (a measurement aid: d2 is then unfinished or made from the workspace as it stands). */
+int sv_clearance_device(const int16_t *logodds, const int32_t *last_seen, int rows, int cols, int radius, int t_occ, int unknown, uint16_t *d2, void *workspace,
+                        size_t workspace_bytes, void *stream);
+/* Enqueued on `stream` as one kernel - a wavefront per path - and not waited for; nothing is allocated and no host synchronisation is made.
+ *   d2           : uint16 [rows][cols] device, the field of `map` made with `radius`
+ *   map          : the map's spec, as for the fuse entry of (K)
+ *   poses        : double [n_paths][n_steps][4] device, 8-byte aligned: (tx, ty, c, s) per step
+ *   centres      : double [n_discs][2] = (px, py), r2 : int32 [n_discs] - HOST pointers, read before the call returns and passed to the
+ *                  kernel by value
+ *   first_hit, min_d2, n_outside : int32 [n_paths] device each, written in full
+ * Returns SV_OK (nothing enqueued for n_paths == 0), SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued, the outputs untouched, the text in
+ * sv_last_error(NULL) - for: a NULL map, d2, centres or r2, or poses or an output with n_paths > 0; d2 not 2-byte, poses or centres not
+ * 8-byte, r2 or an output not 4-byte aligned; a map spec the fuse entry refuses; n_paths outside 0..65535; n_steps outside 1..65535;
+ * n_discs outside 1..64; radius outside 1..254; an r2 that is negative or above radius^2.  These checks run before any HIP call. */
+int sv_clearance_paths_device(const uint16_t *d2, const sv_occupancy_map_spec *map, const double *poses, int n_paths, int n_steps, const double *centres,
+                              const int32_t *r2, int n_discs, int radius, int32_t *first_hit, int32_t *min_d2, int32_t *n_outside, void *stream);
+/* Test hook for sv_clearance_device, process-wide: variant 0 (the default) lets the call choose; 1 = both passes in one kernel over 64 x 64
+ * cells with the halo in LDS, where radius <= 32 (the two kernels above that); 2 = the two kernels; 3 = the two kernels with every lane
+ * walking all 2 R + 1 taps.  taps_device != NULL: a device uint64 that receives the number of taps the row walk made (with variant 3:
+ * rows x cols x (2 radius + 1)).  The results do not depend on it.  Returns SV_OK, or SV_ERR_ARG for another variant. */
+int sv_debug_clearance(int variant, unsigned long long *taps_device);
 
 /* ---- (A) the reference's exported symbols ------------------------------------------------------------- */
 

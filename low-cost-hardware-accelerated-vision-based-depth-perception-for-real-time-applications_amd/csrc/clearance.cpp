@@ -1,0 +1,137 @@
+// Group (M) of include/stereo_vision_hip.h: the obstacle-clearance field of the world map and the footprint check of candidate paths
+// (clearance_kernels.hip).  Everything here is argument checking and launch set-up; every check runs before anything is enqueued, and a
+// refused call leaves its text for sv_last_error(NULL).
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <atomic>
+
+#include <hip/hip_runtime.h>
+
+#include "../../include/stereo_vision_hip.h"
+#include "clearance_kernels.h"
+
+void sv_internal_set_error(const char *msg);  // engine.cpp: the text sv_last_error(NULL) returns on this thread
+
+namespace {
+
+std::atomic<int> g_variant{sv::CLEARANCE_AUTO};
+std::atomic<unsigned long long *> g_taps{nullptr};
+
+int refuse(const char *msg) {
+    sv_internal_set_error(msg);
+    return SV_ERR_ARG;
+}
+
+// NULL for a good map spec, else what is wrong with it: the fuse entry's rules.
+const char *check_map(const sv_occupancy_map_spec *m) {
+    if (!m) return "sv_clearance_paths: the map spec is NULL";
+    for (int k = 0; k < 7; k++)
+        if (m->reserved[k] != 0) return "sv_clearance_paths: a reserved word of the map spec is not 0";
+    if (m->rows < 1 || m->rows > 32768 || m->cols < 1 || m->cols > 32768) return "sv_clearance_paths: rows or cols of the map outside 1..32768";
+    if (m->scale < 1) return "sv_clearance_paths: the map's scale < 1";
+    if (m->top <= -(1 << 24) || m->top >= (1 << 24) || m->left <= -(1 << 24) || m->left >= (1 << 24)) return "sv_clearance_paths: |top| or |left| of the map is 2^24 or more";
+    if (m->l_occ < 1 || m->l_occ > 32767 || m->l_free < 1 || m->l_free > 32767) return "sv_clearance_paths: l_occ or l_free outside 1..32767";
+    if (!(-32767 <= m->l_min && m->l_min <= 0 && 0 <= m->l_max && m->l_max <= 32767) || m->l_min == m->l_max)
+        return "sv_clearance_paths: the clamp needs -32767 <= l_min <= 0 <= l_max <= 32767 and l_min < l_max";
+    return nullptr;
+}
+
+size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
+
+bool overlap(const void *p, size_t pn, const void *q, size_t qn) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+    return p && q && a < b + qn && b < a + pn;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sv_clearance_workspace(int rows, int cols, size_t *bytes) {
+    if (!bytes) return refuse("sv_clearance_workspace: bytes is NULL");
+    if (rows < 1 || rows > 32768 || cols < 1 || cols > 32768) return refuse("sv_clearance_workspace: rows or cols outside 1..32768");
+    *bytes = align16((size_t)rows * cols);  // the column pass's byte per cell
+    return SV_OK;
+}
+
+int sv_clearance_device(const int16_t *logodds, const int32_t *last_seen, int rows, int cols, int radius, int t_occ, int unknown, uint16_t *d2, void *workspace,
+                        size_t workspace_bytes, void *stream) {
+    if (!logodds || !d2 || !workspace) return refuse("sv_clearance: logodds, d2 or the workspace is NULL");
+    if (rows < 1 || rows > 32768 || cols < 1 || cols > 32768) return refuse("sv_clearance: rows or cols outside 1..32768");
+    if (radius < 1 || radius > sv::CLEARANCE_MAX_R) return refuse("sv_clearance: radius outside 1..254");
+    if (t_occ < -32768 || t_occ > 32767) return refuse("sv_clearance: t_occ outside the int16 range");
+    if (unknown != 0 && unknown != 1) return refuse("sv_clearance: unknown is neither 0 nor 1");
+    if (unknown == 1 && !last_seen) return refuse("sv_clearance: unknown == 1 needs last_seen");
+    if (reinterpret_cast<uintptr_t>(logodds) & 1) return refuse("sv_clearance: logodds is not 2-byte aligned");
+    if (reinterpret_cast<uintptr_t>(last_seen) & 3) return refuse("sv_clearance: last_seen is not 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d2) & 1) return refuse("sv_clearance: d2 is not 2-byte aligned");
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return refuse("sv_clearance: the workspace is not 16-byte aligned");
+    const size_t cells = (size_t)rows * cols, need = align16(cells);
+    if (workspace_bytes < need) return refuse("sv_clearance: the workspace is smaller than sv_clearance_workspace asks for");
+    if (overlap(d2, cells * 2, logodds, cells * 2) || overlap(d2, cells * 2, last_seen, cells * 4) || overlap(d2, cells * 2, workspace, need))
+        return refuse("sv_clearance: d2 overlaps logodds, last_seen or the workspace");
+
+    sv::ClearanceArgs a;
+    memset(&a, 0, sizeof(a));
+    a.logodds = logodds, a.last_seen = last_seen, a.g = static_cast<uint8_t *>(workspace), a.d2 = d2;
+    a.taps = g_taps.load();
+    a.rows = rows, a.cols = cols, a.R = radius, a.t_occ = t_occ, a.unknown = unknown;
+    const int variant = g_variant.load();
+    a.early_exit = variant != sv::CLEARANCE_TWO_PASS_FULL;
+    // the call's own choice is the two kernels at every radius (DESIGN.md §4l has the measurement); the fused kernel where the test hook
+    // asks for it and its halo fits
+    const bool fused = variant == sv::CLEARANCE_FUSED && radius <= sv::CLEARANCE_FUSED_MAX_R;
+    int passes = 3;
+    if (const char *s = getenv("SV_CLEARANCE_PASS")) passes = !strcmp(s, "cols") ? 1 : !strcmp(s, "rows") ? 2 : 3;
+    if (sv::launch_clearance(a, static_cast<hipStream_t>(stream), fused, passes) != hipSuccess) {
+        sv_internal_set_error("sv_clearance: a launch failed");
+        return SV_ERR_HIP;
+    }
+    return SV_OK;
+}
+
+int sv_clearance_paths_device(const uint16_t *d2, const sv_occupancy_map_spec *map, const double *poses, int n_paths, int n_steps, const double *centres,
+                              const int32_t *r2, int n_discs, int radius, int32_t *first_hit, int32_t *min_d2, int32_t *n_outside, void *stream) {
+    if (const char *bad = check_map(map)) return refuse(bad);
+    if (n_paths < 0 || n_paths > 65535) return refuse("sv_clearance_paths: n_paths outside 0..65535");
+    if (n_steps < 1 || n_steps > 65535) return refuse("sv_clearance_paths: n_steps outside 1..65535");
+    if (n_discs < 1 || n_discs > sv::CLEARANCE_MAX_DISCS) return refuse("sv_clearance_paths: n_discs outside 1..64");
+    if (radius < 1 || radius > sv::CLEARANCE_MAX_R) return refuse("sv_clearance_paths: radius outside 1..254");
+    if (!d2 || !centres || !r2) return refuse("sv_clearance_paths: d2, centres or r2 is NULL");
+    if (n_paths > 0 && (!poses || !first_hit || !min_d2 || !n_outside)) return refuse("sv_clearance_paths: poses, first_hit, min_d2 or n_outside is NULL");
+    if (reinterpret_cast<uintptr_t>(d2) & 1) return refuse("sv_clearance_paths: d2 is not 2-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(poses) | reinterpret_cast<uintptr_t>(centres)) & 7) return refuse("sv_clearance_paths: poses or centres is not 8-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(r2) | reinterpret_cast<uintptr_t>(first_hit) | reinterpret_cast<uintptr_t>(min_d2) | reinterpret_cast<uintptr_t>(n_outside)) & 3)
+        return refuse("sv_clearance_paths: r2, first_hit, min_d2 or n_outside is not 4-byte aligned");
+    for (int k = 0; k < n_discs; k++)
+        if (r2[k] < 0 || r2[k] > radius * radius) return refuse("sv_clearance_paths: an r2 is negative or above radius^2, where a saturated cell would hide a hit");
+    if (n_paths == 0) return SV_OK;  // nothing to do
+
+    sv::ClearancePathsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.d2 = d2, a.poses = poses, a.first_hit = first_hit, a.min_d2 = min_d2, a.n_outside = n_outside;
+    a.n_paths = n_paths, a.n_steps = n_steps, a.n_discs = n_discs;
+    a.rows = map->rows, a.cols = map->cols, a.top = map->top, a.left = map->left;
+    a.ms = (double)map->scale;
+    a.gx_lo = (double)(map->top - map->rows), a.gx_hi = (double)(map->top - 1);
+    a.gy_lo = (double)(map->left - map->cols), a.gy_hi = (double)(map->left - 1);
+    sv::ClearanceDiscs discs;
+    memset(&discs, 0, sizeof(discs));
+    for (int k = 0; k < n_discs; k++) discs.px[k] = centres[2 * k], discs.py[k] = centres[2 * k + 1], discs.r2[k] = r2[k];
+    if (sv::launch_clearance_paths(a, discs, static_cast<hipStream_t>(stream)) != hipSuccess) {
+        sv_internal_set_error("sv_clearance_paths: a launch failed");
+        return SV_ERR_HIP;
+    }
+    return SV_OK;
+}
+
+int sv_debug_clearance(int variant, unsigned long long *taps_device) {
+    if (variant < sv::CLEARANCE_AUTO || variant > sv::CLEARANCE_TWO_PASS_FULL) return refuse("sv_debug_clearance: variant must be 0 (the call chooses), 1, 2 or 3");
+    g_variant.store(variant);
+    g_taps.store(taps_device);
+    return SV_OK;
+}
+
+} /* extern "C" */

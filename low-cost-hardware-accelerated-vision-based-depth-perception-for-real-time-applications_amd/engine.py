@@ -1450,6 +1450,128 @@ def debug_map_match(group=0, counter=None):
     return int(map_match_lib().sv_debug_map_match(int(group), None if counter is None else counter.data_ptr()))
 
 
+_clearance_bound = False
+
+
+def clearance_lib():
+    """The library with the signatures of group (M) declared."""
+    global _clearance_bound
+    L = occupancy_map_lib()
+    if not _clearance_bound:
+        vp, ci, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
+        L.sv_clearance_workspace.argtypes = [ci, ci, ctypes.POINTER(sz)]
+        L.sv_clearance_workspace.restype = ci
+        L.sv_clearance_device.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, sz, vp]
+        L.sv_clearance_device.restype = ci
+        L.sv_clearance_paths_device.argtypes = [vp, ctypes.POINTER(SvOccupancyMapSpec), vp, ci, ci, vp, vp, ci, ci, vp, vp, vp, vp]
+        L.sv_clearance_paths_device.restype = ci
+        L.sv_debug_clearance.argtypes = [ci, vp]
+        L.sv_debug_clearance.restype = ci
+        _clearance_bound = True
+    return L
+
+
+def occupancy_clearance(logodds, radius, t_occ, last_seen=None, unknown=False, out=None, workspace=None):
+    """The clearance field of a world map - the definition of stereo_vision.sv.occupancy_clearance on the GPU, bit for bit, in one fused
+    call of two kernels: logodds a contiguous CUDA int16 tensor [rows,cols] (e.g. OccupancyMapResult.logodds), last_seen an int32 tensor
+    of the same shape on the same device or None, radius in cells (1 .. 254), t_occ in the int16 range; with unknown, cells never seen
+    (last_seen < 0) are sources too.  out: a contiguous uint16 tensor [rows,cols] to write into; workspace: a uint8 tensor of at least
+    rows x cols bytes (rounded up to 16) to reuse - both come from torch where not given.  -> the uint16 tensor [rows,cols]: per cell
+    the squared distance in cells to the nearest source, 65535 beyond radius; enqueued on torch's current stream, not waited for."""
+    import torch
+    from .stereo_vision.sv import CLEARANCE_RADIUS_MAX
+    if not (isinstance(logodds, torch.Tensor) and logodds.is_cuda and logodds.dtype == torch.int16 and logodds.dim() == 2 and logodds.is_contiguous()):
+        raise ValueError("logodds must be a contiguous CUDA int16 tensor [rows,cols]")
+    rows, cols = logodds.shape
+    dev = logodds.device
+    if not (1 <= rows <= 32768 and 1 <= cols <= 32768):
+        raise ValueError("a map of %d x %d cells: 1 .. 32768 in either dimension" % (rows, cols))
+    for v, lo, hi, what in ((radius, 1, CLEARANCE_RADIUS_MAX, "radius"), (t_occ, -32768, 32767, "t_occ")):
+        if isinstance(v, bool) or int(v) != v or not lo <= v <= hi:
+            raise ValueError("%s must be an integer in %d .. %d, got %r" % (what, lo, hi, v))
+    if not isinstance(unknown, bool) and unknown not in (0, 1):
+        raise ValueError("unknown must be 0 or 1, got %r" % (unknown,))
+    if unknown and last_seen is None:
+        raise ValueError("unknown needs last_seen")
+    if last_seen is not None and not (isinstance(last_seen, torch.Tensor) and last_seen.device == dev and last_seen.dtype == torch.int32
+                                      and tuple(last_seen.shape) == (rows, cols) and last_seen.is_contiguous()):
+        raise ValueError("last_seen must be a contiguous int32 tensor [%d,%d] on the device of logodds" % (rows, cols))
+    if out is None:
+        out = torch.empty((rows, cols), dtype=torch.uint16, device=dev)
+    elif not (isinstance(out, torch.Tensor) and out.device == dev and out.dtype == torch.uint16 and tuple(out.shape) == (rows, cols) and out.is_contiguous()):
+        raise ValueError("out must be a contiguous uint16 tensor [%d,%d] on the device of logodds" % (rows, cols))
+    L = clearance_lib()
+    nbytes = ctypes.c_size_t()
+    if L.sv_clearance_workspace(rows, cols, ctypes.byref(nbytes)) != 0:
+        raise ValueError((L.sv_last_error(None) or b"").decode())
+    if workspace is None:
+        workspace = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    elif not (isinstance(workspace, torch.Tensor) and workspace.device == dev and workspace.dtype == torch.uint8 and workspace.is_contiguous()
+              and workspace.numel() >= nbytes.value):
+        raise ValueError("workspace must be a contiguous uint8 tensor of at least %d bytes on the device of logodds" % nbytes.value)
+    with torch.cuda.device(dev):
+        rc = L.sv_clearance_device(logodds.data_ptr(), None if last_seen is None else last_seen.data_ptr(), rows, cols, int(radius), int(t_occ), int(bool(unknown)),
+                                   out.data_ptr(), workspace.data_ptr(), workspace.numel(), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        msg = "sv_clearance_device failed (%d): %s" % (rc, (L.sv_last_error(None) or b"").decode())
+        raise ValueError(msg) if rc == -1 else StereoError(msg)
+    return out  # a workspace of torch's goes back to its allocator, which hands it out again on this stream only: behind the kernels
+
+
+class ClearancePathsResult:
+    """What clearance_paths returns, int32 tensors [K] on the field's device: first_hit (the number of steps where a path is clear),
+    min_d2 (65535 where nothing was looked up) and n_outside."""
+    __slots__ = ("first_hit", "min_d2", "n_outside")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+def clearance_paths(d2, map, poses, discs, radius):
+    """K candidate paths checked against a clearance field - the definition of stereo_vision.sv.clearance_paths on the GPU, bit for bit,
+    in one kernel: d2 a contiguous CUDA uint16 tensor [rows,cols] (occupancy_clearance's with `radius`), map an SvOccupancyMapSpec or a
+    dict of its nine words, poses float64 [K,T,4] = (tx, ty, c, s) (a numpy array - uploaded once - or a tensor on d2's device), discs =
+    (centres float64 [n,2], r2 int [n]) as stereo_vision.sv.clearance_discs gives them, every r2 <= radius^2.  -> ClearancePathsResult;
+    enqueued on torch's current stream, not waited for; nothing dense is read back."""
+    import torch
+    from .stereo_vision.sv import CLEARANCE_PATHS_MAX, _clearance_footprint, occupancy_map_words
+    words = occupancy_map_words(map)
+    rows, cols = words["rows"], words["cols"]
+    centres, r2, radius = _clearance_footprint(discs[0], discs[1], radius)
+    if not (isinstance(d2, torch.Tensor) and d2.is_cuda and d2.dtype == torch.uint16 and tuple(d2.shape) == (rows, cols) and d2.is_contiguous()):
+        raise ValueError("d2 must be a contiguous CUDA uint16 tensor [%d,%d]" % (rows, cols))
+    dev = d2.device
+    if isinstance(poses, torch.Tensor):
+        if poses.device != dev or poses.dtype != torch.float64:
+            raise ValueError("poses must be float64 on the device of d2")
+        p = poses.contiguous()
+    else:
+        p = torch.from_numpy(np.ascontiguousarray(poses, dtype=np.float64)).to(dev)
+    if p.dim() != 3 or p.shape[2] != 4 or p.shape[0] > CLEARANCE_PATHS_MAX or not 1 <= p.shape[1] <= CLEARANCE_PATHS_MAX:
+        raise ValueError("poses must be [K,T,4] with K <= 65535 and 1 <= T <= 65535, got %s" % (tuple(p.shape),))
+    K, T = p.shape[:2]
+    res = ClearancePathsResult(**{k: torch.empty((K,), dtype=torch.int32, device=dev) for k in ClearancePathsResult.__slots__})
+    if K == 0:  # nothing to enqueue
+        return res
+    spec = _occupancy_map_struct(words)
+    L = clearance_lib()
+    with torch.cuda.device(dev):
+        rc = L.sv_clearance_paths_device(d2.data_ptr(), ctypes.byref(spec), p.data_ptr(), K, T, centres.ctypes.data, r2.ctypes.data, len(r2), radius,
+                                         res.first_hit.data_ptr(), res.min_d2.data_ptr(), res.n_outside.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        msg = "sv_clearance_paths_device failed (%d): %s" % (rc, (L.sv_last_error(None) or b"").decode())
+        raise ValueError(msg) if rc == -1 else StereoError(msg)
+    return res
+
+
+def debug_clearance(variant=0, counter=None):
+    """sv_debug_clearance: the kernels of occupancy_clearance (0: the call chooses; 1: both passes in one kernel where radius <= 32; 2: the
+    two kernels; 3: the two kernels without the early exit) and a CUDA int64 [1] tensor (or None) that receives the taps of the row walk.
+    Process-wide; a test hook."""
+    return int(clearance_lib().sv_debug_clearance(int(variant), None if counter is None else counter.data_ptr()))
+
+
 def host_support_filter(params, dcan, width, height, threads=0, lattice=False):
     """Product host stage: lattice filters + corner points (CPU by design; see csrc/host_stage.h).  threads > 0: the lattice shared between
     that many threads (what single-pair calls do); lattice=True: also return the filtered lattice."""

@@ -36,7 +36,7 @@ import ctypes
 import numpy as np
 
 from .engine import (SvParams, StereoEngine, StereoError, box_positions_from_disparity, box_spec, cloud_spec, compact_cloud_from_disparity,
-                     ground_from_disparity, ground_spec, lib, occupancy_from_disparity, occupancy_fuse, occupancy_match, occupancy_spec, pinned_array, reproject, split_clouds, stixel_spec, stixels_from_disparity,
+                     ground_from_disparity, ground_spec, lib, occupancy_from_disparity, occupancy_fuse, occupancy_match, occupancy_clearance, clearance_paths, occupancy_spec, pinned_array, reproject, split_clouds, stixel_spec, stixels_from_disparity,
                      top_view_from_disparity, top_view_spec, split_voxel_clouds, voxel_cloud_from_disparity, voxel_spec)
 from .stereo_vision.sv import CAMERA_TO_VEHICLE, DEFAULT_CALIBRATION  # noqa: F401 (CAMERA_TO_VEHICLE: re-exported for top_view)
 from .stereo_vision.sv import free_space_points, ground_pose
@@ -424,7 +424,8 @@ class OccupancyMap:
     size for scrolling.  device: a CUDA device ("cuda", "cuda:1", an index) - engine.occupancy_fuse, one kernel per update - or "cpu" -
     the numpy definition on CPU tensors, the same methods and the same bits.  log_odds_words: l_occ, l_free, l_min, l_max (log-odds times
     100).  words is the map's sv_occupancy_map_spec as a dict (top and left move with recenter), seq the number of frames fused so far:
-    the sequence number the next frame carries into last_seen."""
+    the sequence number the next frame carries into last_seen.  clearance() and check_paths() are group (M): the squared distance to the nearest
+    obstacle per cell, and candidate paths checked against it; clearance_radius is the radius in cells of the last clearance()."""
 
     def __init__(self, x_range, y_range, scale, device="cuda", **log_odds_words):
         import torch
@@ -436,6 +437,7 @@ class OccupancyMap:
         self.logodds, self._spare_logodds = (torch.zeros(shape, dtype=torch.int16, device=self.device) for _ in range(2))
         self.last_seen, self._spare_last_seen = (torch.full(shape, -1, dtype=torch.int32, device=self.device) for _ in range(2))
         self.seq = 0
+        self._d2, self._clearance_workspace, self.clearance_radius = None, None, None  # clearance()'s, made on its first call
 
     def reset(self):
         """A fresh map at the place it has scrolled to: logodds 0, last_seen -1, seq 0."""
@@ -520,6 +522,53 @@ class OccupancyMap:
             self._fuse(empty, np.zeros((0, 4)), dict(x_range=(0, 1), y_range=(0, 1), scale=1), shift)
             self.words = dict(self.words, top=self.words["top"] - shift[0], left=self.words["left"] - shift[1])
         return shift
+
+    def clearance(self, radius_m, occupied=None, unknown=False):
+        """The clearance field of the map as it stands (stereo_vision.sv.occupancy_clearance): uint16 [rows,cols] on the map's device, per
+        cell the squared distance in cells to the nearest cell with logodds >= occupied (default l_occ, as state()) - and, with unknown,
+        to the nearest cell never seen - 65535 beyond the radius of ceil(radius_m scale) cells (ValueError above 254).  The tensor and
+        its workspace stay with the map and are written again by the next call; check_paths uses them.  Not waited for."""
+        import torch
+        if not np.isfinite(radius_m) or radius_m <= 0:
+            raise ValueError("clearance: the radius must be a positive number of metres, got %r" % (radius_m,))
+        R = int(np.ceil(float(radius_m) * self.words["scale"]))
+        if not 1 <= R <= _sv.CLEARANCE_RADIUS_MAX:
+            raise ValueError("clearance: %r m are %d cells at scale %d: 1 .. 254" % (radius_m, R, self.words["scale"]))
+        t_occ = self.words["l_occ"] if occupied is None else occupied
+        if self.device.type == "cuda":
+            if self._d2 is None:
+                self._d2 = torch.empty(self.logodds.shape, dtype=torch.uint16, device=self.device)
+                self._clearance_workspace = torch.empty((self.logodds.numel() + 15) // 16 * 16, dtype=torch.uint8, device=self.device)
+            occupancy_clearance(self.logodds, R, t_occ, self.last_seen, unknown, out=self._d2, workspace=self._clearance_workspace)
+        else:
+            self._d2 = torch.from_numpy(_sv.occupancy_clearance(self.logodds.numpy(), R, t_occ, self.last_seen.numpy(), unknown))
+        self.clearance_radius = R
+        return self._d2
+
+    def check_paths(self, paths, discs_m, d2=None):
+        """K candidate paths checked against the last clearance() (or the field d2 of the same radius): paths float64 [K,T,3] = (x, y,
+        yaw) or [K,T,4] = (tx, ty, c, s) poses, numpy or a tensor; discs_m [n,3] = (px, py, radius) in metres in vehicle axes, the
+        footprint (stereo_vision.sv.clearance_discs rounds the radii up to whole cells; none may exceed clearance()'s).
+        -> engine.ClearancePathsResult with first_hit, min_d2 and n_outside as int32 tensors [K] on the map's device.  Not waited for."""
+        import torch
+        from .engine import ClearancePathsResult
+        d2 = self._d2 if d2 is None else d2
+        if d2 is None:
+            raise ValueError("check_paths: no clearance field yet - call clearance() first")
+        discs = _sv.clearance_discs(discs_m, self.words["scale"])
+        p = paths
+        if not isinstance(p, torch.Tensor):
+            p = np.asarray(p, np.float64)
+        if p.ndim != 3 or p.shape[2] not in (3, 4):
+            raise ValueError("check_paths: paths must be [K,T,3] = (x, y, yaw) or [K,T,4] poses, got %s" % (tuple(p.shape),))
+        if p.shape[2] == 3:
+            p = p.cpu().numpy() if isinstance(p, torch.Tensor) else p
+            p = _sv.occupancy_pose(p[..., 0], p[..., 1], p[..., 2])
+        if self.device.type == "cuda":
+            return clearance_paths(d2, self.words, p, discs, self.clearance_radius)
+        p = p.cpu().numpy() if isinstance(p, torch.Tensor) else p
+        res = _sv.clearance_paths(d2.numpy(), self.words, p, discs[0], discs[1], self.clearance_radius)
+        return ClearancePathsResult(**{k: torch.from_numpy(res[k]) for k in ClearancePathsResult.__slots__})
 
     def centres(self):
         """(Xw float64 [rows], Yw float64 [cols]) numpy: the world coordinates of the cells' centres."""

@@ -58,6 +58,12 @@ engine.occupancy_match / rig.OccupancyMap.match and .localize on the GPU): a fra
 every pose of a window around the odometry's guess, the map's log-odds summed under them, and the best pose named - so that a drifting
 pose can be corrected before the frame is fused.  Integer sums behind the cell index: bit for bit.  The reference has no counterpart
 (DESIGN.md §8).
+
+occupancy_clearance (with occupancy_clearance_brute, the all-pairs form), clearance_paths and clearance_discs are the definition of the
+clearance field and the path check (sv_clearance_* of include/stereo_vision_hip.h (M); engine.occupancy_clearance / engine.clearance_paths /
+rig.OccupancyMap.clearance and .check_paths on the GPU): per map cell the squared distance in cells to the nearest occupied (or never seen)
+cell, capped at a radius, and per candidate path the first step at which a footprint of discs touches an obstacle, the least clearance met
+and the lookups that left the map.  Minima and counts of integers: bit for bit.  The reference has no counterpart.
 """
 import argparse
 import ctypes
@@ -1167,6 +1173,153 @@ def occupancy_recenter_shift(map, x, y):
     return w["top"] - top, w["left"] - left
 
 
+CLEARANCE_RADIUS_MAX = 254  # cells: R^2 <= 64516 < CLEARANCE_FAR
+CLEARANCE_FAR = 65535       # d2 of a cell with no source within R
+CLEARANCE_DISCS_MAX = 64
+CLEARANCE_PATHS_MAX = 65535
+
+
+def _clearance_sources(logodds, radius, t_occ, last_seen, unknown):
+    """The checks of sv_clearance_device -> (sources bool [rows, cols], R)."""
+    L = np.asarray(logodds)
+    if L.dtype != np.int16 or L.ndim != 2 or not (1 <= L.shape[0] <= 32768 and 1 <= L.shape[1] <= 32768):
+        raise ValueError("logodds must be int16 [rows, cols] of 1 .. 32768 in either dimension, got %s %s" % (L.dtype, L.shape))
+    for v, lo, hi, what in ((radius, 1, CLEARANCE_RADIUS_MAX, "radius"), (t_occ, -32768, 32767, "t_occ")):
+        if isinstance(v, (bool, np.bool_)) or int(v) != v or not lo <= v <= hi:
+            raise ValueError("%s must be an integer in %d .. %d, got %r" % (what, lo, hi, v))
+    if not isinstance(unknown, (bool, np.bool_)) and unknown not in (0, 1):
+        raise ValueError("unknown must be 0 or 1, got %r" % (unknown,))
+    src = L >= int(t_occ)
+    if unknown:
+        if last_seen is None:
+            raise ValueError("unknown needs last_seen")
+    if last_seen is not None:
+        S = np.asarray(last_seen)
+        if S.dtype != np.int32 or S.shape != L.shape:
+            raise ValueError("last_seen must be int32 %s, got %s %s" % (L.shape, S.dtype, S.shape))
+        if unknown:
+            src = src | (S < 0)
+    return src, int(radius)
+
+
+def occupancy_clearance(logodds, radius, t_occ, last_seen=None, unknown=False):
+    """The definition of sv_clearance_device: uint16 [rows, cols], per cell of a map (logodds int16 [rows, cols], last_seen int32 of the
+    same shape or None) the squared distance in cells to the nearest source - a cell with logodds >= t_occ or, with unknown, last_seen < 0
+    - as the minimum over all sources of (r - r')^2 + (c - c')^2; CLEARANCE_FAR where that exceeds radius^2 (radius in cells, 1 .. 254) or
+    there is no source; 0 on a source.  Cells outside the map are no sources.  This is the separable form: g = the rows to the nearest
+    source of the same column (255 beyond radius), then the minimum over dc of dc^2 + g[c + dc]^2.  A minimum of integers: every order
+    and every decomposition gives the same bits (occupancy_clearance_brute is the all-pairs form)."""
+    src, R = _clearance_sources(logodds, radius, t_occ, last_seen, unknown)
+    rows, cols = src.shape
+    at = np.arange(rows, dtype=np.int64)[:, None]
+    above = np.maximum.accumulate(np.where(src, at, -(1 << 20)), 0)          # the last source at or above
+    below = np.minimum.accumulate(np.where(src, at, 1 << 20)[::-1], 0)[::-1]  # the first at or below
+    g = np.minimum(at - above, below - at)
+    g = np.where(g > R, 255, g)
+    g2 = g * g  # 65025 > R^2 where there is none
+    best = g2.copy()
+    for dc in range(1, min(R, cols - 1) + 1):
+        best[:, dc:] = np.minimum(best[:, dc:], g2[:, :-dc] + dc * dc)
+        best[:, :-dc] = np.minimum(best[:, :-dc], g2[:, dc:] + dc * dc)
+    return np.where(best > R * R, CLEARANCE_FAR, best).astype(np.uint16)
+
+
+def occupancy_clearance_brute(logodds, radius, t_occ, last_seen=None, unknown=False):
+    """occupancy_clearance as the minimum over all (cell, source) pairs, written out: for tests on small maps only."""
+    src, R = _clearance_sources(logodds, radius, t_occ, last_seen, unknown)
+    rows, cols = src.shape
+    sr, sc = np.nonzero(src)
+    out = np.full((rows, cols), CLEARANCE_FAR, np.int64)
+    if sr.size:
+        r, c = np.mgrid[0:rows, 0:cols]
+        d = ((r[..., None] - sr) ** 2 + (c[..., None] - sc) ** 2).min(-1)
+        out = np.where(d > R * R, CLEARANCE_FAR, d)
+    return out.astype(np.uint16)
+
+
+def clearance_discs(discs_m, scale):
+    """A footprint given in metres -> (centres float64 [n, 2], r2 int32 [n]) as clearance_paths takes them: discs_m [n, 3] = (px, py,
+    radius) in vehicle axes, scale = the map's cells per metre; r2 = ceil(radius scale)^2 - rounded up, the conservative side."""
+    d = np.asarray(discs_m, np.float64)
+    if d.ndim != 2 or d.shape[1] != 3 or not 1 <= d.shape[0] <= CLEARANCE_DISCS_MAX:
+        raise ValueError("discs must be [n, 3] = (px, py, radius) with 1 <= n <= 64, got %s" % (d.shape,))
+    if isinstance(scale, (bool, np.bool_)) or not _integer(scale, "scale") >= 1:
+        raise ValueError("scale must be a positive integer, got %r" % (scale,))
+    if not np.isfinite(d).all() or (d[:, 2] < 0).any():
+        raise ValueError("disc centres and radii must be finite and the radii >= 0")
+    cells = np.ceil(d[:, 2] * float(scale))
+    if (cells > CLEARANCE_RADIUS_MAX).any():
+        raise ValueError("a disc radius of more than 254 cells")
+    return np.ascontiguousarray(d[:, :2]), (cells.astype(np.int64) ** 2).astype(np.int32)
+
+
+def clearance_png(d2):
+    """uint8, the shape of d2: the distance in whole cells, min(255, isqrt(d2)), 255 where d2 is CLEARANCE_FAR - what --clearance writes."""
+    D = np.asarray(d2).astype(np.int64)
+    root = np.floor(np.sqrt(D.astype(np.float64))).astype(np.int64)  # below 2^16: the double's root of a square is exact
+    return np.where(D == CLEARANCE_FAR, 255, np.minimum(root, 255)).astype(np.uint8)
+
+
+def _clearance_footprint(centres, r2, radius):
+    """The checks of sv_clearance_paths_device on the footprint -> (centres float64 [n, 2], r2 int32 [n], R)."""
+    if isinstance(radius, (bool, np.bool_)) or int(radius) != radius or not 1 <= radius <= CLEARANCE_RADIUS_MAX:
+        raise ValueError("radius must be an integer in 1 .. 254, got %r" % (radius,))
+    P = np.asarray(centres, np.float64)
+    q = np.asarray(r2)
+    if P.ndim != 2 or P.shape[1] != 2 or not 1 <= P.shape[0] <= CLEARANCE_DISCS_MAX:
+        raise ValueError("centres must be float64 [n, 2] with 1 <= n <= 64, got %s" % (P.shape,))
+    if q.shape != (P.shape[0],) or q.dtype.kind not in "iu":
+        raise ValueError("r2 must be %d integers, got %s %s" % (P.shape[0], q.dtype, q.shape))
+    if (q < 0).any() or (q > int(radius) ** 2).any():
+        raise ValueError("every r2 must lie in 0 .. radius^2 = %d - beyond it a saturated cell would hide a hit - got %s" % (int(radius) ** 2, q.tolist()))
+    return np.ascontiguousarray(P), q.astype(np.int32), int(radius)
+
+
+def clearance_cells(map, poses, centres):
+    """(inside bool [..., n], r int64 [..., n], c int64 [..., n]): the map cell each disc centre (float64 [n, 2], vehicle axes) falls into
+    under each pose (float64 [..., 4] = (tx, ty, c, s)) - occupancy_match's arithmetic and cell rule; r and c are 0 where not inside."""
+    w = occupancy_map_words(map)
+    rows, cols, top, left, ms = w["rows"], w["cols"], w["top"], w["left"], float(w["scale"])
+    p = np.asarray(poses, np.float64)[..., None, :]
+    px, py = np.asarray(centres, np.float64)[:, 0], np.asarray(centres, np.float64)[:, 1]
+    tx, ty, c, s = p[..., 0], p[..., 1], p[..., 2], p[..., 3]
+    with np.errstate(invalid="ignore", over="ignore"):
+        Xw, Yw = (c * px - s * py) + tx, (s * px + c * py) + ty
+        gx, gy = np.floor(Xw * ms), np.floor(Yw * ms)
+        inside = (gx >= top - rows) & (gx <= top - 1) & (gy >= left - cols) & (gy <= left - 1)
+    r = np.where(inside, top - 1 - np.where(inside, gx, 0.0), 0).astype(np.int64)
+    cc = np.where(inside, left - 1 - np.where(inside, gy, 0.0), 0).astype(np.int64)
+    return inside, r, cc
+
+
+def clearance_paths(d2, map, poses, centres, r2, radius):
+    """The definition of sv_clearance_paths_device: K candidate paths of T poses each (float64 [K, T, 4] = (tx, ty, c, s), occupancy_pose's)
+    checked against the field d2 (uint16 [rows, cols], occupancy_clearance's with `radius`) of the map `map` (occupancy_map_params' words)
+    for a footprint of n discs (clearance_discs: centres float64 [n, 2] in vehicle axes, r2 int32 [n] squared radii in cells, each
+    <= radius^2).  -> {"first_hit": int32 [K], "min_d2": int32 [K], "n_outside": int32 [K]}.
+
+      world   Xw = (c px - s py) + tx, Yw = (s px + c py) + ty, every product, difference and sum rounded on its own.
+      map     gx = floor(Xw ms), gy = floor(Yw ms); the lookup is inside iff top - rows <= gx <= top - 1 and left - cols <= gy <= left - 1
+              - a pose with a word that is not finite is outside - and reads map cell (top - 1 - gx, left - 1 - gy): occupancy_match's.
+      path    first_hit = the lowest step with an inside disc whose d2[cell] <= r2, T if none; min_d2 = the least d2[cell] over the
+              inside lookups, CLEARANCE_FAR if none; n_outside = the (step, disc) lookups that were not inside."""
+    w = occupancy_map_words(map)
+    P, q, _ = _clearance_footprint(centres, r2, radius)
+    D = np.asarray(d2)
+    if D.dtype != np.uint16 or D.shape != (w["rows"], w["cols"]):
+        raise ValueError("d2 must be uint16 [%d, %d], got %s %s" % (w["rows"], w["cols"], D.dtype, D.shape))
+    p = np.asarray(poses, np.float64)
+    if p.ndim != 3 or p.shape[2] != 4 or p.shape[0] > CLEARANCE_PATHS_MAX or not 1 <= p.shape[1] <= CLEARANCE_PATHS_MAX:
+        raise ValueError("poses must be float64 [K, T, 4] with K <= 65535 and 1 <= T <= 65535, got %s" % (p.shape,))
+    K, T = p.shape[:2]
+    inside, r, cc = clearance_cells(w, p, P)
+    v = np.where(inside, D[r, cc].astype(np.int64), CLEARANCE_FAR)
+    hit = (inside & (v <= q)).any(-1)  # [K, T]
+    first = np.where(hit.any(1), hit.argmax(1), T)
+    return {"first_hit": first.astype(np.int32), "min_d2": v.reshape(K, -1).min(1).astype(np.int32) if K else np.zeros(0, np.int32),
+            "n_outside": (~inside).reshape(K, -1).sum(1).astype(np.int32)}
+
+
 class stereo_vision:
     def __init__(self, so_lib_path=DEFAULT_STEREO_VISION_SO_PATH, width=1242, height=375, defaultCalibFile=True, objectTracking=True,
                  graphics=False, display=False, scale=1, pc_extrapolation=1, YOLO_CFG="src/yolo/yolov4-tiny.cfg",
@@ -1314,8 +1467,17 @@ def main(argv=None):
                              "frame is first matched against the map built so far over a window of +-DX, +-DY metres and +-DYAW radians "
                              "around its line (NX x NY x NYAW poses, odd, default 7,7,5; the line itself wins ties) and fused at the best "
                              "pose.  The refined poses are written next to FILE as <FILE without .png>.poses.txt, one 'x y yaw' per frame")
+    parser.add_argument("--clearance", type=float, default=0.0, metavar="METRES",
+                        help="with --occupancy-map: also write the final map's clearance field next to FILE as <FILE without "
+                             ".png>.clearance.png, 8 bits, in FILE's orientation: per cell the distance in whole cells to the nearest "
+                             "occupied cell (rounded down, at most 255), 255 beyond METRES")
     args = parser.parse_args(argv)
     args.match_window = None
+    if args.clearance:
+        if not args.occupancy_map:
+            parser.error("--clearance needs --occupancy-map")
+        if not (np.isfinite(args.clearance) and 0 < args.clearance and np.ceil(args.clearance * CLI_TOP_VIEW["scale"]) <= CLEARANCE_RADIUS_MAX):
+            parser.error("--clearance: 1 .. 254 cells of %g m, got %r m" % (1.0 / CLI_TOP_VIEW["scale"], args.clearance))
     if args.match:
         if not args.occupancy_map:
             parser.error("--match needs --occupancy-map and --poses")
@@ -1498,6 +1660,8 @@ def _run_batched(args, ldir, rdir, files):
             print("batch of %d (%d, %d): %.1f pairs/s so far" % (len(names), rig.height, rig.width, n / busy))
         if world is not None:
             _write_png(args.occupancy_map, OCCUPANCY_PNG[world.state().cpu().numpy()])
+            if args.clearance:
+                _write_png(os.path.splitext(args.occupancy_map)[0] + ".clearance.png", clearance_png(world.clearance(args.clearance).cpu().numpy()))
         if args.match_window is not None:
             with open(os.path.splitext(args.occupancy_map)[0] + ".poses.txt", "w") as f:
                 f.write("".join("%r %r %r\n" % tuple(float(v) for v in at) for at in refined))
