@@ -8,15 +8,11 @@
 
 #include "../../include/stereo_vision_hip.h"
 #include "box_kernels.h"
-
-void sv_internal_set_error(const char *msg);  // engine.cpp: the text sv_last_error(NULL) returns on this thread
+#include "stage_glue.h"
 
 namespace {
 
-int refuse(const char *msg) {
-    sv_internal_set_error(msg);
-    return SV_ERR_ARG;
-}
+using namespace sv::glue;
 
 // NULL for a good call, else what is wrong with it.
 const char *check(const sv_box_spec *s, bool points_entry, const void *src, const void *boxes, const void *pos, int batch, int width, int height, int max_boxes) {
@@ -65,10 +61,7 @@ int sv_box_positions_disparity_device(const float *disp, int batch, int width, i
     if (!Q16) return refuse("sv_box_positions: Q16 is NULL");
     if (batch == 0 || max_boxes == 0) return SV_OK;
     sv::BoxArgs a = base_args(spec, width, height, boxes, n_boxes, max_boxes, pos, stat);
-    for (int i = 0; i < 16; i++) a.rp.Q[i] = Q16[i];  // as launch_reproject_batch sets them up
-    a.rp.has_xf = (XR9 || XT3) ? 1 : 0;
-    for (int i = 0; i < 9; i++) a.rp.XR[i] = XR9 ? XR9[i] : (i % 4 == 0 ? 1.0 : 0.0);
-    for (int i = 0; i < 3; i++) a.rp.XT[i] = XT3 ? XT3[i] : 0.0;
+    set_reproject(a.rp, Q16, XR9, XT3);
     a.disp = disp;
     return launch(spec->disparity == SV_BOX_D1 ? sv::BOX_SRC_D1 : sv::BOX_SRC_DMAP, spec, a, batch, stream);
 }

@@ -11,39 +11,14 @@
 
 #include "../../include/stereo_vision_hip.h"
 #include "clearance_kernels.h"
-
-void sv_internal_set_error(const char *msg);  // engine.cpp: the text sv_last_error(NULL) returns on this thread
+#include "stage_glue.h"
 
 namespace {
 
+using namespace sv::glue;
+
 std::atomic<int> g_variant{sv::CLEARANCE_AUTO};
 std::atomic<unsigned long long *> g_taps{nullptr};
-
-int refuse(const char *msg) {
-    sv_internal_set_error(msg);
-    return SV_ERR_ARG;
-}
-
-// NULL for a good map spec, else what is wrong with it: the fuse entry's rules.
-const char *check_map(const sv_occupancy_map_spec *m) {
-    if (!m) return "sv_clearance_paths: the map spec is NULL";
-    for (int k = 0; k < 7; k++)
-        if (m->reserved[k] != 0) return "sv_clearance_paths: a reserved word of the map spec is not 0";
-    if (m->rows < 1 || m->rows > 32768 || m->cols < 1 || m->cols > 32768) return "sv_clearance_paths: rows or cols of the map outside 1..32768";
-    if (m->scale < 1) return "sv_clearance_paths: the map's scale < 1";
-    if (m->top <= -(1 << 24) || m->top >= (1 << 24) || m->left <= -(1 << 24) || m->left >= (1 << 24)) return "sv_clearance_paths: |top| or |left| of the map is 2^24 or more";
-    if (m->l_occ < 1 || m->l_occ > 32767 || m->l_free < 1 || m->l_free > 32767) return "sv_clearance_paths: l_occ or l_free outside 1..32767";
-    if (!(-32767 <= m->l_min && m->l_min <= 0 && 0 <= m->l_max && m->l_max <= 32767) || m->l_min == m->l_max)
-        return "sv_clearance_paths: the clamp needs -32767 <= l_min <= 0 <= l_max <= 32767 and l_min < l_max";
-    return nullptr;
-}
-
-size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
-
-bool overlap(const void *p, size_t pn, const void *q, size_t qn) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-    return p && q && a < b + qn && b < a + pn;
-}
 
 }  // namespace
 
@@ -94,7 +69,7 @@ int sv_clearance_device(const int16_t *logodds, const int32_t *last_seen, int ro
 
 int sv_clearance_paths_device(const uint16_t *d2, const sv_occupancy_map_spec *map, const double *poses, int n_paths, int n_steps, const double *centres,
                               const int32_t *r2, int n_discs, int radius, int32_t *first_hit, int32_t *min_d2, int32_t *n_outside, void *stream) {
-    if (const char *bad = check_map(map)) return refuse(bad);
+    if (const char *bad = check_map("sv_clearance_paths", map)) return refuse(bad);
     if (n_paths < 0 || n_paths > 65535) return refuse("sv_clearance_paths: n_paths outside 0..65535");
     if (n_steps < 1 || n_steps > 65535) return refuse("sv_clearance_paths: n_steps outside 1..65535");
     if (n_discs < 1 || n_discs > sv::CLEARANCE_MAX_DISCS) return refuse("sv_clearance_paths: n_discs outside 1..64");

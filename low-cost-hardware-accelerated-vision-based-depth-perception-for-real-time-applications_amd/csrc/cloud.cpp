@@ -8,15 +8,11 @@
 
 #include "../../include/stereo_vision_hip.h"
 #include "cloud_kernels.h"
-
-void sv_internal_set_error(const char *msg);  // engine.cpp: the text sv_last_error(NULL) returns on this thread
+#include "stage_glue.h"
 
 namespace {
 
-int refuse(const char *msg) {
-    sv_internal_set_error(msg);
-    return SV_ERR_ARG;
-}
+using namespace sv::glue;
 
 // NULL for a good spec and good sizes, else what is wrong with them.
 const char *check_shape(const sv_cloud_spec *s, int batch, int width, int height) {
@@ -28,10 +24,7 @@ const char *check_shape(const sv_cloud_spec *s, int batch, int width, int height
     if (s->step < 1) return "sv_cloud: step < 1";
     for (int k = 0; k < 3; k++)
         if (!(s->lo[k] < s->hi[k])) return "sv_cloud: the crop needs lo < hi on every axis (NaN is refused)";
-    if (batch < 0 || batch > 65535) return "sv_cloud: batch outside 0..65535";
-    if (width < 1 || height < 1) return "sv_cloud: width or height < 1";
-    if ((int64_t)width * height >= ((int64_t)1 << 31)) return "sv_cloud: width * height >= 2^31";
-    return nullptr;
+    return check_frame("sv_cloud", batch, width, height, 0);
 }
 
 // The visited lattice of a checked shape.
@@ -73,10 +66,7 @@ int sv_cloud_disparity_device(const float *disp, const uint8_t *colors, int batc
 
     sv::CloudArgs a;
     memset(&a, 0, sizeof(a));
-    for (int i = 0; i < 16; i++) a.rp.Q[i] = Q16[i];  // as launch_reproject_batch sets them up
-    a.rp.has_xf = (XR9 || XT3) ? 1 : 0;
-    for (int i = 0; i < 9; i++) a.rp.XR[i] = XR9 ? XR9[i] : (i % 4 == 0 ? 1.0 : 0.0);
-    for (int i = 0; i < 3; i++) a.rp.XT[i] = XT3 ? XT3[i] : 0.0;
+    set_reproject(a.rp, Q16, XR9, XT3);
     for (int k = 0; k < 3; k++) a.lo[k] = spec->lo[k], a.hi[k] = spec->hi[k];
     a.disp = disp, a.colors = colors;
     a.xyz = xyz, a.color_out = color_out, a.index_out = index_out, a.counts = counts;

@@ -9,25 +9,18 @@
 
 #include "../../include/stereo_vision_hip.h"
 #include "ground_kernels.h"
-
-void sv_internal_set_error(const char *msg);  // engine.cpp: the text sv_last_error(NULL) returns on this thread
+#include "stage_glue.h"
 
 namespace {
 
-int refuse(const char *msg) {
-    sv_internal_set_error(msg);
-    return SV_ERR_ARG;
-}
+using namespace sv::glue;
 
 // NULL for a good spec and good sizes, else what is wrong with them.
 const char *check_shape(const sv_ground_spec *s, int batch, int width, int height) {
     if (!s) return "sv_ground: spec is NULL";
     for (int k = 0; k < 7; k++)
         if (s->reserved[k] != 0) return "sv_ground: a reserved word of the spec is not 0";
-    if (batch < 0 || batch > 65535) return "sv_ground: batch outside 0..65535";
-    if (width < 1 || height < 1) return "sv_ground: width or height < 1";
-    if (height > 32768) return "sv_ground: height > 32768";
-    if ((int64_t)width * height >= ((int64_t)1 << 31)) return "sv_ground: width * height >= 2^31";
+    if (const char *bad = check_frame("sv_ground", batch, width, height, 32768)) return bad;
     if (s->n_bins < 8 || s->n_bins > sv::GROUND_BINS_MAX) return "sv_ground: n_bins outside 8..4096";
     if (s->vh_lo < -32768 || s->vh_lo > s->vh_hi || s->vh_hi > height - 2) return "sv_ground: the horizon rows need -32768 <= vh_lo <= vh_hi <= height - 2";
     if (s->vh_step < 1) return "sv_ground: vh_step < 1";

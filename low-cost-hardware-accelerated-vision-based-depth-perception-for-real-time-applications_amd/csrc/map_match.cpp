@@ -12,34 +12,14 @@
 
 #include "../../include/stereo_vision_hip.h"
 #include "map_match_kernels.h"
-
-void sv_internal_set_error(const char *msg);  // engine.cpp: the text sv_last_error(NULL) returns on this thread
+#include "stage_glue.h"
 
 namespace {
 
+using namespace sv::glue;
+
 std::atomic<int> g_group{0};
 std::atomic<unsigned long long *> g_lookups{nullptr};
-
-int refuse(const char *msg) {
-    sv_internal_set_error(msg);
-    return SV_ERR_ARG;
-}
-
-// NULL for a good map spec, else what is wrong with it: the fuse entry's rules.
-const char *check_map(const sv_occupancy_map_spec *m) {
-    if (!m) return "sv_map_match: the map spec is NULL";
-    for (int k = 0; k < 7; k++)
-        if (m->reserved[k] != 0) return "sv_map_match: a reserved word of the map spec is not 0";
-    if (m->rows < 1 || m->rows > 32768 || m->cols < 1 || m->cols > 32768) return "sv_map_match: rows or cols of the map outside 1..32768";
-    if (m->scale < 1) return "sv_map_match: the map's scale < 1";
-    if (m->top <= -(1 << 24) || m->top >= (1 << 24) || m->left <= -(1 << 24) || m->left >= (1 << 24)) return "sv_map_match: |top| or |left| of the map is 2^24 or more";
-    if (m->l_occ < 1 || m->l_occ > 32767 || m->l_free < 1 || m->l_free > 32767) return "sv_map_match: l_occ or l_free outside 1..32767";
-    if (!(-32767 <= m->l_min && m->l_min <= 0 && 0 <= m->l_max && m->l_max <= 32767) || m->l_min == m->l_max)
-        return "sv_map_match: the clamp needs -32767 <= l_min <= 0 <= l_max <= 32767 and l_min < l_max";
-    return nullptr;
-}
-
-size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
 
 // The three parts of the workspace, each a multiple of 16 bytes.
 void layout(size_t cap, int batch, size_t *headers, size_t *partials, size_t *lists) {
@@ -70,7 +50,7 @@ int sv_map_match_device(const uint8_t *state, const double *poses, int batch, in
     int frows, fcols;
     if (!frame) return refuse("sv_map_match: the frame spec is NULL");
     if (sv_occupancy_dims(frame, &frows, &fcols) != SV_OK) return refuse("sv_map_match: the frame spec is not one sv_occupancy_dims admits");
-    if (const char *bad = check_map(map)) return refuse(bad);
+    if (const char *bad = check_map("sv_map_match", map)) return refuse(bad);
     if (batch < 0 || batch > 65535) return refuse("sv_map_match: batch outside 0..65535");
     if (n_poses < 1 || n_poses > 65535) return refuse("sv_map_match: n_poses outside 1..65535");
     if ((long long)batch * n_poses >= (1ll << 31)) return refuse("sv_map_match: batch x n_poses is 2^31 or more");

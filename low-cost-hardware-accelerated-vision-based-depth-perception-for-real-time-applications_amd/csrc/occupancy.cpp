@@ -12,18 +12,14 @@
 
 #include "../../include/stereo_vision_hip.h"
 #include "occupancy_kernels.h"
-
-void sv_internal_set_error(const char *msg);  // engine.cpp: the text sv_last_error(NULL) returns on this thread
+#include "stage_glue.h"
 
 namespace {
 
+using namespace sv::glue;
+
 std::atomic<int> g_combine{1};
 std::atomic<unsigned long long *> g_atomics{nullptr};
-
-int refuse(const char *msg) {
-    sv_internal_set_error(msg);
-    return SV_ERR_ARG;
-}
 
 // NULL for a good spec, else what is wrong with it; the grid comes from the top view's own checks.
 const char *check_spec(const sv_occupancy_spec *s, int *rows, int *cols) {
@@ -39,14 +35,6 @@ const char *check_spec(const sv_occupancy_spec *s, int *rows, int *cols) {
     if (sv_top_view_dims(&tv, rows, cols) != SV_OK) return "sv_occupancy: the ranges or the scale are not a grid sv_top_view_dims admits";
     if (s->z_scale < 1 || s->z_scale > 65536) return "sv_occupancy: z_scale outside 1..65536";
     if (s->min_obstacle < 1 || s->min_ground < 1 || s->min_rays < 1) return "sv_occupancy: min_obstacle, min_ground or min_rays < 1";
-    return nullptr;
-}
-
-const char *check_shape(int batch, int width, int height) {
-    if (batch < 0 || batch > 65535) return "sv_occupancy: batch outside 0..65535";
-    if (width < 1 || height < 1) return "sv_occupancy: width or height < 1";
-    if (height > 32768) return "sv_occupancy: height > 32768";
-    if ((int64_t)width * height >= ((int64_t)1 << 31)) return "sv_occupancy: width * height >= 2^31";
     return nullptr;
 }
 
@@ -68,7 +56,7 @@ int sv_occupancy_disparity_device(const float *disp, const uint8_t *labels, cons
                                   uint8_t *state, void *stream) {
     int rows, cols;
     if (const char *bad = check_spec(spec, &rows, &cols)) return refuse(bad);
-    if (const char *bad = check_shape(batch, width, height)) return refuse(bad);
+    if (const char *bad = check_frame("sv_occupancy", batch, width, height, 32768)) return refuse(bad);
     if (!disp || !labels || !free_row || !free_disp) return refuse("sv_occupancy: disp, labels, free_row or free_disp is NULL");
     if (!Q16) return refuse("sv_occupancy: Q16 is NULL");
     if (!cells || !n_rays) return refuse("sv_occupancy: cells or n_rays is NULL");
@@ -83,10 +71,7 @@ int sv_occupancy_disparity_device(const float *disp, const uint8_t *labels, cons
 
     sv::OccupancyArgs a;
     memset(&a, 0, sizeof(a));
-    for (int i = 0; i < 16; i++) a.rp.Q[i] = Q16[i];  // as sv_top_view_disparity_device sets them up
-    a.rp.has_xf = (XR9 || XT3) ? 1 : 0;
-    for (int i = 0; i < 9; i++) a.rp.XR[i] = XR9 ? XR9[i] : (i % 4 == 0 ? 1.0 : 0.0);
-    for (int i = 0; i < 3; i++) a.rp.XT[i] = XT3 ? XT3[i] : 0.0;
+    set_reproject(a.rp, Q16, XR9, XT3);
     a.disp = disp, a.labels = labels, a.free_row = free_row, a.free_disp = free_disp;
     a.cells = cells, a.n_rays = n_rays, a.state = state;
     a.atomics = g_atomics.load();

@@ -12,38 +12,16 @@
 
 #include "../../include/stereo_vision_hip.h"
 #include "occupancy_map_kernels.h"
-
-void sv_internal_set_error(const char *msg);  // engine.cpp: the text sv_last_error(NULL) returns on this thread
+#include "stage_glue.h"
 
 namespace {
+
+using namespace sv::glue;
 
 std::atomic<int> g_cull{1};
 std::atomic<unsigned long long *> g_lookups{nullptr};
 
-int refuse(const char *msg) {
-    sv_internal_set_error(msg);
-    return SV_ERR_ARG;
-}
-
-// NULL for a good map spec, else what is wrong with it.
-const char *check_map(const sv_occupancy_map_spec *m) {
-    if (!m) return "sv_occupancy_fuse: the map spec is NULL";
-    for (int k = 0; k < 7; k++)
-        if (m->reserved[k] != 0) return "sv_occupancy_fuse: a reserved word of the map spec is not 0";
-    if (m->rows < 1 || m->rows > 32768 || m->cols < 1 || m->cols > 32768) return "sv_occupancy_fuse: rows or cols of the map outside 1..32768";
-    if (m->scale < 1) return "sv_occupancy_fuse: the map's scale < 1";
-    if (m->top <= -sv::OCCMAP_CELL_MAX || m->top >= sv::OCCMAP_CELL_MAX || m->left <= -sv::OCCMAP_CELL_MAX || m->left >= sv::OCCMAP_CELL_MAX)
-        return "sv_occupancy_fuse: |top| or |left| of the map is 2^24 or more";
-    if (m->l_occ < 1 || m->l_occ > 32767 || m->l_free < 1 || m->l_free > 32767) return "sv_occupancy_fuse: l_occ or l_free outside 1..32767";
-    if (!(-32767 <= m->l_min && m->l_min <= 0 && 0 <= m->l_max && m->l_max <= 32767) || m->l_min == m->l_max)
-        return "sv_occupancy_fuse: the clamp needs -32767 <= l_min <= 0 <= l_max <= 32767 and l_min < l_max";
-    return nullptr;
-}
-
-bool overlap(const void *p, const void *q, size_t bytes) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-    return a < b + bytes && b < a + bytes;
-}
+static_assert(MAP_CELL_MAX == sv::OCCMAP_CELL_MAX, "check_map admits the offsets the kernel can address");
 
 }  // namespace
 
@@ -55,7 +33,7 @@ int sv_occupancy_fuse_device(const uint8_t *state, const double *poses, int batc
     int frows, fcols;
     if (!frame) return refuse("sv_occupancy_fuse: the frame spec is NULL");
     if (sv_occupancy_dims(frame, &frows, &fcols) != SV_OK) return refuse("sv_occupancy_fuse: the frame spec is not one sv_occupancy_dims admits");
-    if (const char *bad = check_map(map)) return refuse(bad);
+    if (const char *bad = check_map("sv_occupancy_fuse", map)) return refuse(bad);
     if (batch < 0 || batch > 65535) return refuse("sv_occupancy_fuse: batch outside 0..65535");
     if (seq0 < 0 || seq0 > INT_MAX - batch) return refuse("sv_occupancy_fuse: seq0 < 0 or seq0 + batch overflows");
     if (batch > 0 && (!state || !poses)) return refuse("sv_occupancy_fuse: state or poses is NULL");
@@ -68,9 +46,9 @@ int sv_occupancy_fuse_device(const uint8_t *state, const double *poses, int batc
     const size_t cells = (size_t)map->rows * map->cols;
     const bool shifted = shift_rows != 0 || shift_cols != 0;
     // in place is one lane reading and writing its own cell: only with a zero shift and the very same buffers
-    if (overlap(logodds_in, logodds_out, cells * 2) && (shifted || logodds_in != logodds_out))
+    if (overlap(logodds_in, cells * 2, logodds_out, cells * 2) && (shifted || logodds_in != logodds_out))
         return refuse("sv_occupancy_fuse: logodds_in and logodds_out overlap (allowed only as the same buffer with a zero shift)");
-    if (last_seen_in && overlap(last_seen_in, last_seen_out, cells * 4) && (shifted || last_seen_in != last_seen_out))
+    if (last_seen_in && overlap(last_seen_in, cells * 4, last_seen_out, cells * 4) && (shifted || last_seen_in != last_seen_out))
         return refuse("sv_occupancy_fuse: last_seen_in and last_seen_out overlap (allowed only as the same buffer with a zero shift)");
     if (batch == 0 && !shifted && logodds_in == logodds_out && last_seen_in == last_seen_out) return SV_OK;  // nothing to do
 

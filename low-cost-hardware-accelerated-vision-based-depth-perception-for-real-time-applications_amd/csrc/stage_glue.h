@@ -1,0 +1,75 @@
+// What the stage entries of groups (D) to (M) of include/stereo_vision_hip.h share on the host (top_view.cpp ... clearance.cpp): the
+// refusal of a bad call, the checks that several groups state in the same words, and the set-up of sv::ReprojectArgs.  Host code only:
+// no .hip file includes it.
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include <string>
+
+#include "../../include/stereo_vision_hip.h"
+#include "reproject.h"
+
+void sv_internal_set_error(const char *msg);  // engine.cpp: the text sv_last_error(NULL) returns on this thread (it copies msg)
+
+namespace sv {
+namespace glue {
+
+constexpr int MAP_CELL_MAX = 1 << 24;  // |top|, |left| of a world map stay below it (sv::OCCMAP_CELL_MAX: occupancy_map.cpp asserts it)
+
+inline int refuse(const char *msg) {
+    sv_internal_set_error(msg);
+    return SV_ERR_ARG;
+}
+
+// "<prefix>: <body>" for the checks below, whose bodies are the same for every entry.  The text lives in a buffer of the calling thread
+// until the next call: long enough to hand it to refuse(), or to drop it where only the verdict counts (the *_workspace_bytes entries).
+inline const char *prefixed(const char *prefix, const std::string &body) {
+    static thread_local std::string text;
+    text = std::string(prefix) + ": " + body;
+    return text.c_str();
+}
+
+// NULL for a batch of frames every kernel can index, else what is wrong with it; max_height 0 = no limit of its own.
+inline const char *check_frame(const char *prefix, int batch, int width, int height, int max_height) {
+    if (batch < 0 || batch > 65535) return prefixed(prefix, "batch outside 0..65535");
+    if (width < 1 || height < 1) return prefixed(prefix, "width or height < 1");
+    if (max_height > 0 && height > max_height) return prefixed(prefix, "height > " + std::to_string(max_height));
+    if ((int64_t)width * height >= ((int64_t)1 << 31)) return prefixed(prefix, "width * height >= 2^31");
+    return nullptr;
+}
+
+// NULL for a good map spec, else what is wrong with it: the rules of the fuse entry, which every reader of the map repeats.
+inline const char *check_map(const char *prefix, const sv_occupancy_map_spec *m) {
+    if (!m) return prefixed(prefix, "the map spec is NULL");
+    for (int k = 0; k < 7; k++)
+        if (m->reserved[k] != 0) return prefixed(prefix, "a reserved word of the map spec is not 0");
+    if (m->rows < 1 || m->rows > 32768 || m->cols < 1 || m->cols > 32768) return prefixed(prefix, "rows or cols of the map outside 1..32768");
+    if (m->scale < 1) return prefixed(prefix, "the map's scale < 1");
+    if (m->top <= -MAP_CELL_MAX || m->top >= MAP_CELL_MAX || m->left <= -MAP_CELL_MAX || m->left >= MAP_CELL_MAX)
+        return prefixed(prefix, "|top| or |left| of the map is 2^24 or more");
+    if (m->l_occ < 1 || m->l_occ > 32767 || m->l_free < 1 || m->l_free > 32767) return prefixed(prefix, "l_occ or l_free outside 1..32767");
+    if (!(-32767 <= m->l_min && m->l_min <= 0 && 0 <= m->l_max && m->l_max <= 32767) || m->l_min == m->l_max)
+        return prefixed(prefix, "the clamp needs -32767 <= l_min <= 0 <= l_max <= 32767 and l_min < l_max");
+    return nullptr;
+}
+
+// Q, and XR / XT or the identity where they are NULL, as launch_reproject_batch (legacy_kernels.hip) sets them up.
+inline void set_reproject(ReprojectArgs &rp, const double *Q16, const double *XR9, const double *XT3) {
+    for (int i = 0; i < 16; i++) rp.Q[i] = Q16[i];
+    rp.has_xf = (XR9 || XT3) ? 1 : 0;
+    for (int i = 0; i < 9; i++) rp.XR[i] = XR9 ? XR9[i] : (i % 4 == 0 ? 1.0 : 0.0);
+    for (int i = 0; i < 3; i++) rp.XT[i] = XT3 ? XT3[i] : 0.0;
+}
+
+inline size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
+
+// Do the pn bytes at p and the qn bytes at q share a byte?  Never with a NULL pointer.
+inline bool overlap(const void *p, size_t pn, const void *q, size_t qn) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+    return p && q && a < b + qn && b < a + pn;
+}
+
+}  // namespace glue
+}  // namespace sv

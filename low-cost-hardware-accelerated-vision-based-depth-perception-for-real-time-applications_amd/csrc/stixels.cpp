@@ -8,26 +8,19 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/stereo_vision_hip.h"
+#include "stage_glue.h"
 #include "stixel_kernels.h"
-
-void sv_internal_set_error(const char *msg);  // engine.cpp: the text sv_last_error(NULL) returns on this thread
 
 namespace {
 
-int refuse(const char *msg) {
-    sv_internal_set_error(msg);
-    return SV_ERR_ARG;
-}
+using namespace sv::glue;
 
 // NULL for a good spec and good sizes, else what is wrong with them.
 const char *check_shape(const sv_stixel_spec *s, int batch, int width, int height) {
     if (!s) return "sv_stixel: spec is NULL";
     for (int k = 0; k < 7; k++)
         if (s->reserved[k] != 0) return "sv_stixel: a reserved word of the spec is not 0";
-    if (batch < 0 || batch > 65535) return "sv_stixel: batch outside 0..65535";
-    if (width < 1 || height < 1) return "sv_stixel: width or height < 1";
-    if (height > 32768) return "sv_stixel: height > 32768";
-    if ((int64_t)width * height >= ((int64_t)1 << 31)) return "sv_stixel: width * height >= 2^31";
+    if (const char *bad = check_frame("sv_stixel", batch, width, height, 32768)) return bad;
     if (s->n_bins < 8 || s->n_bins > 4096) return "sv_stixel: n_bins outside 8..4096";
     if (s->q_min < 0 || s->q_min > 4095) return "sv_stixel: q_min outside 0..4095";
     if (s->sim < 0 || s->sim > 4096) return "sv_stixel: sim outside 0..4096";

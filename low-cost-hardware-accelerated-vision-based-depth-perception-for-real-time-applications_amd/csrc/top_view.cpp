@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/stereo_vision_hip.h"
+#include "stage_glue.h"
 #include "top_view_kernels.h"
 
 namespace {
@@ -110,10 +111,7 @@ int sv_top_view_disparity_device(const float *disp, int batch, int width, int he
     if (!buffers_ok(spec, batch, out, workspace, workspace_bytes)) return SV_ERR_ARG;
     if (batch == 0) return SV_OK;
     sv::TopViewArgs a = base_args(spec, rows, cols, spec->mode == SV_TOPVIEW_REFERENCE ? workspace : out);
-    for (int i = 0; i < 16; i++) a.rp.Q[i] = Q16[i];  // as launch_reproject_batch sets them up
-    a.rp.has_xf = (XR9 || XT3) ? 1 : 0;
-    for (int i = 0; i < 9; i++) a.rp.XR[i] = XR9 ? XR9[i] : (i % 4 == 0 ? 1.0 : 0.0);
-    for (int i = 0; i < 3; i++) a.rp.XT[i] = XT3 ? XT3[i] : 0.0;
+    sv::glue::set_reproject(a.rp, Q16, XR9, XT3);
     a.disp = disp;
     a.W = width, a.H = height;
     return run(spec->disparity == SV_TOPVIEW_D1 ? sv::TV_SRC_D1 : sv::TV_SRC_DMAP, spec, batch, rows, cols, a, out, workspace, static_cast<hipStream_t>(stream));

@@ -11,21 +11,17 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/stereo_vision_hip.h"
+#include "stage_glue.h"
 #include "voxel_kernels.h"
 
-void sv_internal_set_error(const char *msg);  // engine.cpp: the text sv_last_error(NULL) returns on this thread
-
 namespace {
+
+using namespace sv::glue;
 
 std::atomic<int> g_combine{1};
 std::atomic<unsigned long long *> g_counters{nullptr};
 
 constexpr int MAX_CAPACITY = 1 << 26;  // slots <= 2^27: a table of 9.7 GB per pair, and every launch below 2^32 threads per row
-
-int refuse(const char *msg) {
-    sv_internal_set_error(msg);
-    return SV_ERR_ARG;
-}
 
 // NULL for a good spec and good sizes, else what is wrong with them; nc = the cells per axis of a good spec.
 const char *check_shape(const sv_voxel_spec *s, int batch, int width, int height, int *nc) {
@@ -43,10 +39,7 @@ const char *check_shape(const sv_voxel_spec *s, int batch, int width, int height
         if (!(cells <= 1048576.0)) return "sv_voxel: more than 2^20 cells on an axis";
         nc[k] = cells < 1.0 ? 1 : (int)cells;
     }
-    if (batch < 0 || batch > 65535) return "sv_voxel: batch outside 0..65535";
-    if (width < 1 || height < 1) return "sv_voxel: width or height < 1";
-    if ((int64_t)width * height >= ((int64_t)1 << 31)) return "sv_voxel: width * height >= 2^31";
-    return nullptr;
+    return check_frame("sv_voxel", batch, width, height, 0);
 }
 
 const char *check_capacity(int capacity) {
@@ -134,10 +127,7 @@ int sv_voxel_disparity_device(const float *disp, const uint8_t *colors, int batc
 
     sv::VoxelArgs a;
     memset(&a, 0, sizeof(a));
-    for (int i = 0; i < 16; i++) a.c.rp.Q[i] = Q16[i];  // as launch_reproject_batch sets them up
-    a.c.rp.has_xf = (XR9 || XT3) ? 1 : 0;
-    for (int i = 0; i < 9; i++) a.c.rp.XR[i] = XR9 ? XR9[i] : (i % 4 == 0 ? 1.0 : 0.0);
-    for (int i = 0; i < 3; i++) a.c.rp.XT[i] = XT3 ? XT3[i] : 0.0;
+    set_reproject(a.c.rp, Q16, XR9, XT3);
     for (int k = 0; k < 3; k++) a.c.lo[k] = spec->lo[k], a.c.hi[k] = spec->hi[k], a.nc[k] = nc[k];
     a.size = spec->size;
     a.c.disp = disp, a.c.colors = color_out ? colors : nullptr;  // colours are summed only where they are asked for

@@ -426,9 +426,7 @@ def reproject(disp, Q, XR=None, XT=None, want_dmap=True):
     assert disp.is_cuda and disp.dtype == torch.float32 and disp.dim() == 3
     disp = disp.contiguous()
     B, H, W = disp.shape
-    q = np.ascontiguousarray(Q, dtype=np.float64).reshape(16)
-    xr = None if XR is None else np.ascontiguousarray(XR, dtype=np.float64).reshape(9)
-    xt = None if XT is None else np.ascontiguousarray(XT, dtype=np.float64).reshape(3)
+    q, xr, xt = _reproject_pointers(Q, XR, XT)
     dmap = torch.empty((B, H, W), dtype=torch.uint8, device=disp.device) if want_dmap else None
     pts = torch.empty((B, H, W, 3), dtype=torch.float64, device=disp.device)
     torch.cuda.current_stream(disp.device).synchronize()
@@ -436,8 +434,7 @@ def reproject(disp, Q, XR=None, XT=None, want_dmap=True):
     L.sv_reproject_batch_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                             ctypes.c_void_p, ctypes.c_void_p]
     with torch.cuda.device(disp.device):
-        rc = L.sv_reproject_batch_device(disp.data_ptr(), B, W, H, q.ctypes.data, xr.ctypes.data if xr is not None else None,
-                                         xt.ctypes.data if xt is not None else None, dmap.data_ptr() if dmap is not None else None, pts.data_ptr())
+        rc = L.sv_reproject_batch_device(disp.data_ptr(), B, W, H, q, xr, xt, dmap.data_ptr() if dmap is not None else None, pts.data_ptr())
     if rc != 0:
         raise StereoError("sv_reproject_batch_device failed (%d)" % rc)
     return dmap, pts
@@ -466,29 +463,200 @@ class SvTopViewSpec(ctypes.Structure):
                 ("mode", ctypes.c_int32), ("disparity", ctypes.c_int32), ("reserved", ctypes.c_int32 * 5)]
 
 
+class SvBoxSpec(ctypes.Structure):
+    """sv_box_spec of include/stereo_vision_hip.h."""
+    _fields_ = [("select", ctypes.c_int32), ("disparity", ctypes.c_int32), ("band", ctypes.c_int32), ("reserved", ctypes.c_int32 * 5)]
+
+
+class SvCloudSpec(ctypes.Structure):
+    """sv_cloud_spec of include/stereo_vision_hip.h."""
+    _fields_ = [("lo", ctypes.c_double * 3), ("hi", ctypes.c_double * 3), ("disparity", ctypes.c_int32), ("step", ctypes.c_int32),
+                ("dtype", ctypes.c_int32), ("reserved", ctypes.c_int32 * 5)]
+
+
+class SvVoxelSpec(ctypes.Structure):
+    """sv_voxel_spec of include/stereo_vision_hip.h."""
+    _fields_ = [("lo", ctypes.c_double * 3), ("hi", ctypes.c_double * 3), ("size", ctypes.c_double), ("disparity", ctypes.c_int32),
+                ("step", ctypes.c_int32), ("dtype", ctypes.c_int32), ("reserved", ctypes.c_int32 * 5)]
+
+
+class SvGroundSpec(ctypes.Structure):
+    """sv_ground_spec of include/stereo_vision_hip.h."""
+    _fields_ = [("n_bins", ctypes.c_int32), ("vh_lo", ctypes.c_int32), ("vh_hi", ctypes.c_int32), ("vh_step", ctypes.c_int32),
+                ("qb_step", ctypes.c_int32), ("tol", ctypes.c_int32), ("g_tol", ctypes.c_int32), ("min_run", ctypes.c_int32),
+                ("min_support", ctypes.c_int32), ("reserved", ctypes.c_int32 * 7)]
+
+
+class SvStixelSpec(ctypes.Structure):
+    """sv_stixel_spec of include/stereo_vision_hip.h."""
+    _fields_ = [("n_bins", ctypes.c_int32), ("q_min", ctypes.c_int32), ("sim", ctypes.c_int32), ("max_gap", ctypes.c_int32),
+                ("min_rows", ctypes.c_int32), ("max_layers", ctypes.c_int32), ("col_step", ctypes.c_int32), ("sim_cols", ctypes.c_int32),
+                ("min_cols", ctypes.c_int32), ("reserved", ctypes.c_int32 * 7)]
+
+
+class SvOccupancySpec(ctypes.Structure):
+    """sv_occupancy_spec of include/stereo_vision_hip.h."""
+    _fields_ = [("x_range", ctypes.c_double * 2), ("y_range", ctypes.c_double * 2), ("z_range", ctypes.c_double * 2), ("scale", ctypes.c_int32),
+                ("z_scale", ctypes.c_int32), ("min_obstacle", ctypes.c_int32), ("min_ground", ctypes.c_int32), ("min_rays", ctypes.c_int32),
+                ("reserved", ctypes.c_int32 * 5)]
+
+
+class SvOccupancyMapSpec(ctypes.Structure):
+    """sv_occupancy_map_spec of include/stereo_vision_hip.h."""
+    _fields_ = [("top", ctypes.c_int32), ("left", ctypes.c_int32), ("rows", ctypes.c_int32), ("cols", ctypes.c_int32), ("scale", ctypes.c_int32),
+                ("l_occ", ctypes.c_int32), ("l_free", ctypes.c_int32), ("l_min", ctypes.c_int32), ("l_max", ctypes.c_int32), ("reserved", ctypes.c_int32 * 7)]
+
+
+def _signatures():
+    """The table below: per stage group of the C API, (D) to (M), its functions and per function (restype, argtypes), parameter by
+    parameter as include/stereo_vision_hip.h declares them - tests/test_stage_signatures.py holds the two against each other."""
+    P = ctypes.POINTER
+    vp, ci, sz, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_int64
+    tv, bx, cl, vx, gr, sx = P(SvTopViewSpec), P(SvBoxSpec), P(SvCloudSpec), P(SvVoxelSpec), P(SvGroundSpec), P(SvStixelSpec)
+    oc, om = P(SvOccupancySpec), P(SvOccupancyMapSpec)
+    return {
+        "top_view": {  # (D)
+            "sv_top_view_dims": (ci, [tv, P(ci), P(ci)]),
+            "sv_top_view_workspace_bytes": (sz, [tv, ci]),
+            "sv_top_view_points_device": (ci, [vp, ci, i64, tv, vp, vp, sz, vp]),
+            "sv_top_view_disparity_device": (ci, [vp, ci, ci, ci, vp, vp, vp, tv, vp, vp, sz, vp]),
+            "sv_debug_top_view": (ci, [ci, vp]),
+        },
+        "box": {  # (E)
+            "sv_box_positions_disparity_device": (ci, [vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, bx, vp, vp, vp]),
+            "sv_box_positions_points_device": (ci, [vp, ci, ci, ci, vp, vp, ci, bx, vp, vp, vp]),
+        },
+        "cloud": {  # (F)
+            "sv_cloud_tile": (ci, []),
+            "sv_cloud_workspace_bytes": (sz, [cl, ci, ci, ci]),
+            "sv_cloud_disparity_device": (ci, [vp, vp, ci, ci, ci, vp, vp, vp, cl, ci, vp, vp, vp, vp, vp, sz, vp]),
+        },
+        "ground": {  # (G)
+            "sv_ground_workspace_bytes": (sz, [gr, ci, ci, ci]),
+            "sv_ground_disparity_device": (ci, [vp, ci, ci, ci, gr, vp, vp, vp, vp, vp, vp, sz, vp]),
+        },
+        "stixel": {  # (H)
+            "sv_stixel_workspace_bytes": (sz, [sx, ci, ci, ci]),
+            "sv_stixel_disparity_device": (ci, [vp, vp, ci, ci, ci, sx, ci, vp, vp, vp, vp, vp, vp, sz, vp]),
+        },
+        "voxel": {  # (I)
+            "sv_voxel_table_slots": (i64, [ci]),
+            "sv_voxel_workspace_bytes": (sz, [vx, ci, ci, ci, ci]),
+            "sv_voxel_disparity_device": (ci, [vp, vp, ci, ci, ci, vp, vp, vp, vx, ci, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+            "sv_debug_voxel": (ci, [ci, vp]),
+        },
+        "occupancy": {  # (J)
+            "sv_occupancy_dims": (ci, [oc, P(ci), P(ci)]),
+            "sv_occupancy_disparity_device": (ci, [vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, oc, vp, vp, vp, vp]),
+            "sv_debug_occupancy": (ci, [ci, vp]),
+        },
+        "occupancy_map": {  # (K)
+            "sv_occupancy_fuse_device": (ci, [vp, vp, ci, ci, oc, om, ci, ci, vp, vp, vp, vp, vp]),
+            "sv_debug_occupancy_fuse": (ci, [ci, vp]),
+        },
+        "map_match": {  # (L)
+            "sv_map_match_workspace": (ci, [oc, ci, ci, P(sz)]),
+            "sv_map_match_device": (ci, [vp, vp, ci, ci, oc, om, vp, ci, ci, vp, vp, vp, vp, vp, sz, vp]),
+            "sv_debug_map_match": (ci, [ci, vp]),
+        },
+        "clearance": {  # (M)
+            "sv_clearance_workspace": (ci, [ci, ci, P(sz)]),
+            "sv_clearance_device": (ci, [vp, vp, ci, ci, ci, ci, ci, vp, vp, sz, vp]),
+            "sv_clearance_paths_device": (ci, [vp, om, vp, ci, ci, vp, vp, ci, ci, vp, vp, vp, vp]),
+            "sv_debug_clearance": (ci, [ci, vp]),
+        },
+    }
+
+
+STAGE_SIGNATURES = _signatures()  # plain data: made without loading the library
+_GROUP_NEEDS = {"voxel": ("cloud",), "occupancy_map": ("occupancy",), "map_match": ("occupancy_map",), "clearance": ("occupancy_map",)}
+_bound_groups = set()
+
+
+def _bind(group):
+    """The library with the signatures of `group`, and of the groups its callers use with it, declared.  Group by group and only when one
+    is first asked for: a library under SV_LIB_PATH that lacks a later group still loads and serves the earlier ones."""
+    L = lib()
+    if group not in _bound_groups:
+        for g in _GROUP_NEEDS.get(group, ()):
+            _bind(g)
+        for name, (restype, argtypes) in STAGE_SIGNATURES[group].items():
+            f = getattr(L, name)
+            f.restype, f.argtypes = restype, argtypes
+        _bound_groups.add(group)
+    return L
+
+
+def _check(rc, name, text=True):
+    """Raises for a non-zero return code of the C entry `name` - ValueError for SV_ERR_ARG (-1), StereoError for anything else - with the
+    text the entry left for sv_last_error(NULL).  text=False for group (D), whose entries leave none: what another call left there is
+    not theirs."""
+    if rc != 0:
+        msg = "%s failed (%d)" % (name, rc)
+        if text:
+            msg += ": " + (lib().sv_last_error(None) or b"").decode()
+        raise ValueError(msg) if rc == -1 else StereoError(msg)
+
+
+def _ptr(t):
+    """The device pointer of an optional output: NULL for None and for a tensor without elements."""
+    return None if t is None or t.numel() == 0 else t.data_ptr()
+
+
+def _reproject_pointers(Q, XR=None, XT=None):
+    """-> Q16, XR9, XT3 as a C entry takes them: pointers to contiguous float64 copies (None for an XR / XT not given), each of which
+    holds its array for as long as it lives - keep them until the call has returned."""
+    return [None if m is None else np.ascontiguousarray(m, dtype=np.float64).reshape(n).ctypes.data_as(ctypes.c_void_p)
+            for m, n in ((Q, 16), (XR, 9), (XT, 3))]
+
+
+def _disparity_batch(t, name, max_rows=None, one_frame=True):
+    """The disparity maps of a stage, checked for what every kernel assumes -> (the contiguous CUDA float32 [B,H,W] tensor, whether it
+    was one frame [H,W] that got its B here).  max_rows: the stage's own limit on H, if it has one."""
+    import torch
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() in ((2, 3) if one_frame else (3,))):
+        raise ValueError("%s must be a CUDA float32 tensor [B,H,W]" % name)
+    one = t.dim() == 2
+    t = (t.unsqueeze(0) if one else t).contiguous()
+    B, H, W = t.shape
+    if B > 65535 or H < 1 or W < 1 or H * W >= 2 ** 31 or (max_rows is not None and H > max_rows):
+        raise ValueError("%s: at most 65535 pairs of 1 <= width * height < 2^31 pixels%s, got %s"
+                         % (name, "" if max_rows is None else " and at most %d rows" % max_rows, tuple(t.shape)))
+    return t, one
+
+
+def _colors_batch(colors, d1):
+    """The colour images of a cloud stage, checked against its maps d1 [B,H,W] -> None, or the contiguous CUDA uint8 [B,H,W,4] tensor the
+    C entry wants: 4-byte aligned, so a view that starts at an odd storage offset is copied."""
+    import torch
+    if colors is None:
+        return None
+    if not (isinstance(colors, torch.Tensor) and colors.is_cuda and colors.dtype == torch.uint8 and colors.device == d1.device):
+        raise ValueError("colors must be a CUDA uint8 tensor [B,H,W,4] on d1's device")
+    colors = (colors.unsqueeze(0) if colors.dim() == 3 else colors).contiguous()
+    if tuple(colors.shape) != tuple(d1.shape) + (4,):
+        raise ValueError("colors must be [B,H,W,4] matching d1 %s, got %s" % (tuple(d1.shape), tuple(colors.shape)))
+    if colors.data_ptr() % 4:  # the C entry moves a pixel as one dword
+        colors = colors.clone()
+    return colors
+
+
+class _Result:
+    """What the result classes below share: every slot is set from the keyword of its name, None where none is given."""
+    __slots__ = ()
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
 _TOP_VIEW_MODES = {"reference": 0, "count": 1}
 _TOP_VIEW_DISPARITY = {"dmap": 0, "d1": 1}
-_top_view_bound = False
 
 
 def top_view_lib():
     """The library with the sv_top_view_* signatures declared."""
-    global _top_view_bound
-    L = lib()
-    if not _top_view_bound:
-        vp, sp = ctypes.c_void_p, ctypes.POINTER(SvTopViewSpec)
-        L.sv_top_view_dims.argtypes = [sp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
-        L.sv_top_view_dims.restype = ctypes.c_int
-        L.sv_top_view_workspace_bytes.argtypes = [sp, ctypes.c_int]
-        L.sv_top_view_workspace_bytes.restype = ctypes.c_size_t
-        L.sv_top_view_points_device.argtypes = [vp, ctypes.c_int, ctypes.c_int64, sp, vp, vp, ctypes.c_size_t, vp]
-        L.sv_top_view_points_device.restype = ctypes.c_int
-        L.sv_top_view_disparity_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, sp, vp, vp, ctypes.c_size_t, vp]
-        L.sv_top_view_disparity_device.restype = ctypes.c_int
-        L.sv_debug_top_view.argtypes = [ctypes.c_int, vp]
-        L.sv_debug_top_view.restype = ctypes.c_int
-        _top_view_bound = True
-    return L
+    return _bind("top_view")
 
 
 def top_view_spec(x_range, y_range, z_range, scale, mode="reference", disparity="dmap"):
@@ -514,12 +682,6 @@ def _top_view_buffers(spec, B, rows, cols, device):
     return out, ws, nbytes
 
 
-def _top_view_check(rc, name):
-    if rc != 0:
-        msg = "%s failed (%d)" % (name, rc)
-        raise ValueError(msg) if rc == -1 else StereoError(msg)
-
-
 def top_view(points, x_range, y_range, z_range, scale, mode="reference"):
     """Bird's-eye views of a batch of clouds on the device: points is a CUDA float64 tensor [B,...,3] (e.g. rig.point_clouds' [B,H,W,3]),
     each frame's points in flat order.  Returns a CUDA tensor [B,rows,cols], uint8 (mode "reference") or int32 (mode "count"), equal
@@ -533,9 +695,9 @@ def top_view(points, x_range, y_range, z_range, scale, mode="reference"):
     n = pts.numel() // (3 * B) if B else 0
     out, ws, nbytes = _top_view_buffers(spec, B, rows, cols, pts.device)
     with torch.cuda.device(pts.device):
-        rc = top_view_lib().sv_top_view_points_device(pts.data_ptr(), B, n, ctypes.byref(spec), out.data_ptr(), ws.data_ptr() if ws is not None else None,
-                                                      nbytes, torch.cuda.current_stream(pts.device).cuda_stream)
-    _top_view_check(rc, "sv_top_view_points_device")
+        rc = top_view_lib().sv_top_view_points_device(pts.data_ptr(), B, n, ctypes.byref(spec), out.data_ptr(), _ptr(ws), nbytes,
+                                                      torch.cuda.current_stream(pts.device).cuda_stream)
+    _check(rc, "sv_top_view_points_device", text=False)
     return out
 
 
@@ -546,42 +708,20 @@ def top_view_from_disparity(disp, Q, x_range, y_range, z_range, scale, XR=None, 
     pixels with d <= 0.  Returns what top_view returns; enqueued on torch's current stream."""
     import torch
     spec, rows, cols = top_view_spec(x_range, y_range, z_range, scale, mode, disparity)
-    if not (isinstance(disp, torch.Tensor) and disp.is_cuda and disp.dtype == torch.float32 and disp.dim() == 3):
-        raise ValueError("disp must be a CUDA float32 tensor [B,H,W]")
-    disp = disp.contiguous()
+    disp, _ = _disparity_batch(disp, "disp", 65535, one_frame=False)
     B, H, W = disp.shape
-    q = np.ascontiguousarray(Q, dtype=np.float64).reshape(16)
-    xr = None if XR is None else np.ascontiguousarray(XR, dtype=np.float64).reshape(9)
-    xt = None if XT is None else np.ascontiguousarray(XT, dtype=np.float64).reshape(3)
+    q, xr, xt = _reproject_pointers(Q, XR, XT)
     out, ws, nbytes = _top_view_buffers(spec, B, rows, cols, disp.device)
     with torch.cuda.device(disp.device):
-        rc = top_view_lib().sv_top_view_disparity_device(disp.data_ptr(), B, W, H, q.ctypes.data, xr.ctypes.data if xr is not None else None,
-                                                         xt.ctypes.data if xt is not None else None, ctypes.byref(spec), out.data_ptr(),
-                                                         ws.data_ptr() if ws is not None else None, nbytes, torch.cuda.current_stream(disp.device).cuda_stream)
-    _top_view_check(rc, "sv_top_view_disparity_device")
+        rc = top_view_lib().sv_top_view_disparity_device(disp.data_ptr(), B, W, H, q, xr, xt, ctypes.byref(spec), out.data_ptr(), _ptr(ws), nbytes,
+                                                         torch.cuda.current_stream(disp.device).cuda_stream)
+    _check(rc, "sv_top_view_disparity_device", text=False)
     return out
-
-
-class SvBoxSpec(ctypes.Structure):
-    """sv_box_spec of include/stereo_vision_hip.h."""
-    _fields_ = [("select", ctypes.c_int32), ("disparity", ctypes.c_int32), ("band", ctypes.c_int32), ("reserved", ctypes.c_int32 * 5)]
-
-
-_box_bound = False
 
 
 def box_lib():
     """The library with the sv_box_positions_* signatures declared."""
-    global _box_bound
-    L = lib()
-    if not _box_bound:
-        vp, ci, sp = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(SvBoxSpec)
-        L.sv_box_positions_disparity_device.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, sp, vp, vp, vp]
-        L.sv_box_positions_disparity_device.restype = ci
-        L.sv_box_positions_points_device.argtypes = [vp, ci, ci, ci, vp, vp, ci, sp, vp, vp, vp]
-        L.sv_box_positions_points_device.restype = ci
-        _box_bound = True
-    return L
+    return _bind("box")
 
 
 def box_spec(select="near", disparity="d1", band=4):
@@ -628,12 +768,6 @@ def _box_buffers(boxes, n_boxes, B, device):
     return bx, nb, pos, stat
 
 
-def _box_check(rc, name):
-    if rc != 0:
-        msg = "%s failed (%d): %s" % (name, rc, (box_lib().sv_last_error(None) or b"").decode())
-        raise ValueError(msg) if rc == -1 else StereoError(msg)
-
-
 def box_positions(points, boxes, n_boxes=None):
     """Mean point of a batch of clouds inside detector boxes, on the device: points is a CUDA float64 tensor [B,H,W,3] (e.g.
     rig.point_clouds' or reproject's; one frame [H,W,3] accepted), boxes int32 [B,M,4] = (x, y, w, h) (CUDA tensor or numpy; [M,4] for
@@ -649,9 +783,9 @@ def box_positions(points, boxes, n_boxes=None):
     spec = box_spec("all", "dmap", 0)
     bx, nb, pos, stat = _box_buffers(boxes, n_boxes, B, pts.device)
     with torch.cuda.device(pts.device):
-        rc = box_lib().sv_box_positions_points_device(pts.data_ptr(), B, W, H, bx.data_ptr(), nb.data_ptr() if nb is not None else None, bx.shape[1],
-                                                      ctypes.byref(spec), pos.data_ptr(), stat.data_ptr(), torch.cuda.current_stream(pts.device).cuda_stream)
-    _box_check(rc, "sv_box_positions_points_device")
+        rc = box_lib().sv_box_positions_points_device(pts.data_ptr(), B, W, H, bx.data_ptr(), _ptr(nb), bx.shape[1], ctypes.byref(spec),
+                                                      pos.data_ptr(), stat.data_ptr(), torch.cuda.current_stream(pts.device).cuda_stream)
+    _check(rc, "sv_box_positions_points_device")
     return pos, stat
 
 
@@ -665,46 +799,20 @@ def box_positions_from_disparity(disp, Q, boxes, n_boxes=None, XR=None, XT=None,
     n_boxes and the stream as for box_positions."""
     import torch
     spec = box_spec(select, disparity, band)
-    if not (isinstance(disp, torch.Tensor) and disp.is_cuda and disp.dtype == torch.float32 and disp.dim() in (2, 3)):
-        raise ValueError("disp must be a CUDA float32 tensor [B,H,W]")
-    disp = (disp.unsqueeze(0) if disp.dim() == 2 else disp).contiguous()
+    disp, _ = _disparity_batch(disp, "disp")
     B, H, W = disp.shape
-    q = np.ascontiguousarray(Q, dtype=np.float64).reshape(16)
-    xr = None if XR is None else np.ascontiguousarray(XR, dtype=np.float64).reshape(9)
-    xt = None if XT is None else np.ascontiguousarray(XT, dtype=np.float64).reshape(3)
+    q, xr, xt = _reproject_pointers(Q, XR, XT)
     bx, nb, pos, stat = _box_buffers(boxes, n_boxes, B, disp.device)
     with torch.cuda.device(disp.device):
-        rc = box_lib().sv_box_positions_disparity_device(disp.data_ptr(), B, W, H, q.ctypes.data, xr.ctypes.data if xr is not None else None,
-                                                         xt.ctypes.data if xt is not None else None, bx.data_ptr(),
-                                                         nb.data_ptr() if nb is not None else None, bx.shape[1], ctypes.byref(spec), pos.data_ptr(),
-                                                         stat.data_ptr(), torch.cuda.current_stream(disp.device).cuda_stream)
-    _box_check(rc, "sv_box_positions_disparity_device")
+        rc = box_lib().sv_box_positions_disparity_device(disp.data_ptr(), B, W, H, q, xr, xt, bx.data_ptr(), _ptr(nb), bx.shape[1], ctypes.byref(spec),
+                                                         pos.data_ptr(), stat.data_ptr(), torch.cuda.current_stream(disp.device).cuda_stream)
+    _check(rc, "sv_box_positions_disparity_device")
     return pos, stat
-
-
-class SvCloudSpec(ctypes.Structure):
-    """sv_cloud_spec of include/stereo_vision_hip.h."""
-    _fields_ = [("lo", ctypes.c_double * 3), ("hi", ctypes.c_double * 3), ("disparity", ctypes.c_int32), ("step", ctypes.c_int32),
-                ("dtype", ctypes.c_int32), ("reserved", ctypes.c_int32 * 5)]
-
-
-_cloud_bound = False
 
 
 def cloud_lib():
     """The library with the sv_cloud_* signatures declared."""
-    global _cloud_bound
-    L = lib()
-    if not _cloud_bound:
-        vp, ci, sp = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(SvCloudSpec)
-        L.sv_cloud_tile.argtypes = []
-        L.sv_cloud_tile.restype = ci
-        L.sv_cloud_workspace_bytes.argtypes = [sp, ci, ci, ci]
-        L.sv_cloud_workspace_bytes.restype = ctypes.c_size_t
-        L.sv_cloud_disparity_device.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp, sp, ci, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
-        L.sv_cloud_disparity_device.restype = ci
-        _cloud_bound = True
-    return L
+    return _bind("cloud")
 
 
 def cloud_tile():
@@ -737,29 +845,16 @@ def compact_cloud_from_disparity(d1, Q, colors=None, XR=None, XT=None, lo=None, 
     overflow.  CUDA tensors on the input's device, enqueued on torch's current stream (not waited for); split_clouds cuts them."""
     import torch
     spec = cloud_spec(lo, hi, step, disparity, dtype)
-    if not (isinstance(d1, torch.Tensor) and d1.is_cuda and d1.dtype == torch.float32 and d1.dim() in (2, 3)):
-        raise ValueError("d1 must be a CUDA float32 tensor [B,H,W]")
-    d1 = (d1.unsqueeze(0) if d1.dim() == 2 else d1).contiguous()
+    d1, _ = _disparity_batch(d1, "d1")
     B, H, W = d1.shape
-    if B > 65535 or H < 1 or W < 1 or H * W >= 2 ** 31:
-        raise ValueError("at most 65535 pairs of 1 <= width * height < 2^31 pixels, got %s" % (tuple(d1.shape),))
-    if colors is not None:
-        if not (isinstance(colors, torch.Tensor) and colors.is_cuda and colors.dtype == torch.uint8 and colors.device == d1.device):
-            raise ValueError("colors must be a CUDA uint8 tensor [B,H,W,4] on d1's device")
-        colors = (colors.unsqueeze(0) if colors.dim() == 3 else colors).contiguous()
-        if tuple(colors.shape) != (B, H, W, 4):
-            raise ValueError("colors must be [B,H,W,4] matching d1 %s, got %s" % (tuple(d1.shape), tuple(colors.shape)))
-        if colors.data_ptr() % 4:  # a view at an odd storage offset: the C entry moves a pixel as one dword
-            colors = colors.clone()
+    colors = _colors_batch(colors, d1)
     n_visited = -(-W // int(step)) * -(-H // int(step))
     if capacity is None:
         capacity = n_visited
     if isinstance(capacity, bool) or int(capacity) != capacity or not 0 <= capacity < 2 ** 31:
         raise ValueError("capacity must be an integer >= 0, got %r" % (capacity,))
     capacity = int(capacity)
-    q = np.ascontiguousarray(Q, dtype=np.float64).reshape(16)
-    xr = None if XR is None else np.ascontiguousarray(XR, dtype=np.float64).reshape(9)
-    xt = None if XT is None else np.ascontiguousarray(XT, dtype=np.float64).reshape(3)
+    q, xr, xt = _reproject_pointers(Q, XR, XT)
     dev = d1.device
     xyz = torch.empty((B, capacity, 3), dtype=torch.float32 if dtype == "f32" else torch.float64, device=dev)
     color = torch.empty((B, capacity, 4), dtype=torch.uint8, device=dev) if colors is not None else None
@@ -771,14 +866,9 @@ def compact_cloud_from_disparity(d1, Q, colors=None, XR=None, XT=None, lo=None, 
     nbytes = L.sv_cloud_workspace_bytes(ctypes.byref(spec), B, W, H)
     ws = torch.empty(((nbytes + 3) // 4,), dtype=torch.int32, device=dev) if nbytes else None
     with torch.cuda.device(dev):
-        rc = L.sv_cloud_disparity_device(d1.data_ptr(), colors.data_ptr() if colors is not None else None, B, W, H, q.ctypes.data,
-                                         xr.ctypes.data if xr is not None else None, xt.ctypes.data if xt is not None else None, ctypes.byref(spec),
-                                         capacity, xyz.data_ptr() if capacity else None, color.data_ptr() if color is not None and capacity else None,
-                                         index.data_ptr() if index is not None and capacity else None, counts.data_ptr(),
-                                         ws.data_ptr() if ws is not None else None, nbytes, torch.cuda.current_stream(dev).cuda_stream)
-    if rc != 0:
-        msg = "sv_cloud_disparity_device failed (%d): %s" % (rc, (L.sv_last_error(None) or b"").decode())
-        raise ValueError(msg) if rc == -1 else StereoError(msg)
+        rc = L.sv_cloud_disparity_device(d1.data_ptr(), _ptr(colors), B, W, H, q, xr, xt, ctypes.byref(spec), capacity, _ptr(xyz), _ptr(color), _ptr(index),
+                                         counts.data_ptr(), _ptr(ws), nbytes, torch.cuda.current_stream(dev).cuda_stream)
+    _check(rc, "sv_cloud_disparity_device")
     return xyz, color, index, counts
 
 
@@ -795,31 +885,9 @@ def split_clouds(xyz, counts, *others):
     return out
 
 
-class SvVoxelSpec(ctypes.Structure):
-    """sv_voxel_spec of include/stereo_vision_hip.h."""
-    _fields_ = [("lo", ctypes.c_double * 3), ("hi", ctypes.c_double * 3), ("size", ctypes.c_double), ("disparity", ctypes.c_int32),
-                ("step", ctypes.c_int32), ("dtype", ctypes.c_int32), ("reserved", ctypes.c_int32 * 5)]
-
-
-_voxel_bound = False
-
-
 def voxel_lib():
     """The library with the sv_voxel_* signatures declared."""
-    global _voxel_bound
-    L = cloud_lib()
-    if not _voxel_bound:
-        vp, ci, sp = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(SvVoxelSpec)
-        L.sv_voxel_table_slots.argtypes = [ci]
-        L.sv_voxel_table_slots.restype = ctypes.c_int64
-        L.sv_voxel_workspace_bytes.argtypes = [sp, ci, ci, ci, ci]
-        L.sv_voxel_workspace_bytes.restype = ctypes.c_size_t
-        L.sv_voxel_disparity_device.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp, sp, ci, vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
-        L.sv_voxel_disparity_device.restype = ci
-        L.sv_debug_voxel.argtypes = [ci, vp]
-        L.sv_debug_voxel.restype = ci
-        _voxel_bound = True
-    return L
+    return _bind("voxel")
 
 
 def voxel_spec(size, lo, hi, step=1, disparity="d1", dtype="f32", capacity=None):
@@ -849,26 +917,13 @@ def voxel_cloud_from_disparity(d1, Q, size, lo, hi, colors=None, XR=None, XT=Non
     current stream (not waited for); split_voxel_clouds cuts them."""
     import torch
     spec = voxel_spec(size, lo, hi, step, disparity, dtype, capacity)
-    if not (isinstance(d1, torch.Tensor) and d1.is_cuda and d1.dtype == torch.float32 and d1.dim() in (2, 3)):
-        raise ValueError("d1 must be a CUDA float32 tensor [B,H,W]")
-    d1 = (d1.unsqueeze(0) if d1.dim() == 2 else d1).contiguous()
+    d1, _ = _disparity_batch(d1, "d1")
     B, H, W = d1.shape
-    if B > 65535 or H < 1 or W < 1 or H * W >= 2 ** 31:
-        raise ValueError("at most 65535 pairs of 1 <= width * height < 2^31 pixels, got %s" % (tuple(d1.shape),))
-    if colors is not None:
-        if not (isinstance(colors, torch.Tensor) and colors.is_cuda and colors.dtype == torch.uint8 and colors.device == d1.device):
-            raise ValueError("colors must be a CUDA uint8 tensor [B,H,W,4] on d1's device")
-        colors = (colors.unsqueeze(0) if colors.dim() == 3 else colors).contiguous()
-        if tuple(colors.shape) != (B, H, W, 4):
-            raise ValueError("colors must be [B,H,W,4] matching d1 %s, got %s" % (tuple(d1.shape), tuple(colors.shape)))
-        if colors.data_ptr() % 4:  # a view at an odd storage offset: the C entry moves a pixel as one dword
-            colors = colors.clone()
+    colors = _colors_batch(colors, d1)
     if capacity is None:
         capacity = min(-(-W // int(step)) * -(-H // int(step)), 2 ** 26)
     capacity = int(capacity)
-    q = np.ascontiguousarray(Q, dtype=np.float64).reshape(16)
-    xr = None if XR is None else np.ascontiguousarray(XR, dtype=np.float64).reshape(9)
-    xt = None if XT is None else np.ascontiguousarray(XT, dtype=np.float64).reshape(3)
+    q, xr, xt = _reproject_pointers(Q, XR, XT)
     dev = d1.device
     xyz = torch.empty((B, capacity, 3), dtype=torch.float32 if dtype == "f32" else torch.float64, device=dev)
     color = torch.empty((B, capacity, 4), dtype=torch.uint8, device=dev) if colors is not None else None
@@ -883,14 +938,10 @@ def voxel_cloud_from_disparity(d1, Q, size, lo, hi, colors=None, XR=None, XT=Non
     if nbytes == ctypes.c_size_t(-1).value:
         raise ValueError("sv_voxel_workspace_bytes refused the request")
     ws = torch.empty(((nbytes + 15) // 16, 2), dtype=torch.int64, device=dev)  # torch's allocations start on 512 bytes
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     with torch.cuda.device(dev):
-        rc = L.sv_voxel_disparity_device(d1.data_ptr(), ptr(colors), B, W, H, q.ctypes.data, xr.ctypes.data if xr is not None else None,
-                                         xt.ctypes.data if xt is not None else None, ctypes.byref(spec), capacity, xyz.data_ptr(), ptr(color), ptr(cell),
-                                         ptr(n), ptr(first), counts.data_ptr(), ws.data_ptr(), nbytes, torch.cuda.current_stream(dev).cuda_stream)
-    if rc != 0:
-        msg = "sv_voxel_disparity_device failed (%d): %s" % (rc, (L.sv_last_error(None) or b"").decode())
-        raise ValueError(msg) if rc == -1 else StereoError(msg)
+        rc = L.sv_voxel_disparity_device(d1.data_ptr(), _ptr(colors), B, W, H, q, xr, xt, ctypes.byref(spec), capacity, xyz.data_ptr(), _ptr(color), _ptr(cell),
+                                         _ptr(n), _ptr(first), counts.data_ptr(), ws.data_ptr(), nbytes, torch.cuda.current_stream(dev).cuda_stream)
+    _check(rc, "sv_voxel_disparity_device")
     return xyz, color, cell, n, first, counts
 
 
@@ -909,28 +960,9 @@ def debug_voxel(combine=True, counters=None):
     return int(voxel_lib().sv_debug_voxel(1 if combine else 0, None if counters is None else counters.data_ptr()))
 
 
-class SvGroundSpec(ctypes.Structure):
-    """sv_ground_spec of include/stereo_vision_hip.h."""
-    _fields_ = [("n_bins", ctypes.c_int32), ("vh_lo", ctypes.c_int32), ("vh_hi", ctypes.c_int32), ("vh_step", ctypes.c_int32),
-                ("qb_step", ctypes.c_int32), ("tol", ctypes.c_int32), ("g_tol", ctypes.c_int32), ("min_run", ctypes.c_int32),
-                ("min_support", ctypes.c_int32), ("reserved", ctypes.c_int32 * 7)]
-
-
-_ground_bound = False
-
-
 def ground_lib():
     """The library with the sv_ground_* signatures declared."""
-    global _ground_bound
-    L = lib()
-    if not _ground_bound:
-        vp, ci, sp = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(SvGroundSpec)
-        L.sv_ground_workspace_bytes.argtypes = [sp, ci, ci, ci]
-        L.sv_ground_workspace_bytes.restype = ctypes.c_size_t
-        L.sv_ground_disparity_device.argtypes = [vp, ci, ci, ci, sp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
-        L.sv_ground_disparity_device.restype = ci
-        _ground_bound = True
-    return L
+    return _bind("ground")
 
 
 def ground_spec(height, disp_max=None, n_bins=None, vh_lo=0, vh_hi=None, vh_step=2, qb_step=2, tol=2, g_tol=4, min_run=8, min_support=0):
@@ -945,17 +977,13 @@ def ground_spec(height, disp_max=None, n_bins=None, vh_lo=0, vh_hi=None, vh_step
     return spec
 
 
-class GroundResult:
+class GroundResult(_Result):
     """What ground_from_disparity returns, tensors on the input's device: ground int32 [B,4] = (vh, qb, S, n_valid) per pair ((-1, -1, S,
     n_valid): no ground), vdisp uint32-valued int32 [B,H,n_bins], labels uint8 [B,H,W] (0 invalid, 1 ground, 2 obstacle, 3 below the
     ground), free_row int32 [B,W] and free_disp float32 [B,W] (-1 / 0: no obstacle in the column) - None where not asked for - and the
     spec in use.  StereoRig.ground adds pose (per pair (height_m, pitch_rad, slope_px_per_row) or None) and points (float64 [B,W,3]
     numpy, NaN where free_row < 0), both on the host."""
     __slots__ = ("ground", "vdisp", "labels", "free_row", "free_disp", "spec", "pose", "points")
-
-    def __init__(self, **kw):
-        for k in self.__slots__:
-            setattr(self, k, kw.get(k))
 
 
 def ground_from_disparity(disp, disp_max=None, n_bins=None, vh_lo=0, vh_hi=None, vh_step=2, qb_step=2, tol=2, g_tol=4, min_run=8, min_support=None,
@@ -968,12 +996,8 @@ def ground_from_disparity(disp, disp_max=None, n_bins=None, vh_lo=0, vh_hi=None,
     min_support None = the width: a line with less support is "no ground".  -> GroundResult; enqueued on torch's current stream, not
     waited for."""
     import torch
-    if not (isinstance(disp, torch.Tensor) and disp.is_cuda and disp.dtype == torch.float32 and disp.dim() in (2, 3)):
-        raise ValueError("disp must be a CUDA float32 tensor [B,H,W]")
-    d = (disp.unsqueeze(0) if disp.dim() == 2 else disp).contiguous()
+    d, _ = _disparity_batch(disp, "disp")
     B, H, W = d.shape
-    if B > 65535 or H < 1 or W < 1 or H * W >= 2 ** 31:
-        raise ValueError("at most 65535 pairs of 1 <= width * height < 2^31 pixels, got %s" % (tuple(d.shape),))
     spec = ground_spec(H, disp_max, n_bins, vh_lo, vh_hi, vh_step, qb_step, tol, g_tol, min_run, W if min_support is None else min_support)
     dev = d.device
     ground = torch.empty((B, 4), dtype=torch.int32, device=dev)
@@ -987,38 +1011,16 @@ def ground_from_disparity(disp, disp_max=None, n_bins=None, vh_lo=0, vh_hi=None,
     L = ground_lib()
     nbytes = L.sv_ground_workspace_bytes(ctypes.byref(spec), B, W, H)
     ws = torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=dev)
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     with torch.cuda.device(dev):
-        rc = L.sv_ground_disparity_device(d.data_ptr(), B, W, H, ctypes.byref(spec), ptr(vdisp), ground.data_ptr(), ptr(labels), ptr(free_row),
-                                          ptr(free_disp), ws.data_ptr(), nbytes, torch.cuda.current_stream(dev).cuda_stream)
-    if rc != 0:
-        msg = "sv_ground_disparity_device failed (%d): %s" % (rc, (L.sv_last_error(None) or b"").decode())
-        raise ValueError(msg) if rc == -1 else StereoError(msg)
+        rc = L.sv_ground_disparity_device(d.data_ptr(), B, W, H, ctypes.byref(spec), _ptr(vdisp), ground.data_ptr(), _ptr(labels), _ptr(free_row),
+                                          _ptr(free_disp), ws.data_ptr(), nbytes, torch.cuda.current_stream(dev).cuda_stream)
+    _check(rc, "sv_ground_disparity_device")
     return res
-
-
-class SvStixelSpec(ctypes.Structure):
-    """sv_stixel_spec of include/stereo_vision_hip.h."""
-    _fields_ = [("n_bins", ctypes.c_int32), ("q_min", ctypes.c_int32), ("sim", ctypes.c_int32), ("max_gap", ctypes.c_int32),
-                ("min_rows", ctypes.c_int32), ("max_layers", ctypes.c_int32), ("col_step", ctypes.c_int32), ("sim_cols", ctypes.c_int32),
-                ("min_cols", ctypes.c_int32), ("reserved", ctypes.c_int32 * 7)]
-
-
-_stixel_bound = False
 
 
 def stixel_lib():
     """The library with the sv_stixel_* signatures declared."""
-    global _stixel_bound
-    L = lib()
-    if not _stixel_bound:
-        vp, ci, sp = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(SvStixelSpec)
-        L.sv_stixel_workspace_bytes.argtypes = [sp, ci, ci, ci]
-        L.sv_stixel_workspace_bytes.restype = ctypes.c_size_t
-        L.sv_stixel_disparity_device.argtypes = [vp, vp, ci, ci, ci, sp, ci, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
-        L.sv_stixel_disparity_device.restype = ci
-        _stixel_bound = True
-    return L
+    return _bind("stixel")
 
 
 def stixel_spec(disp_max=None, n_bins=None, q_min=16, sim=6, max_gap=2, min_rows=8, max_layers=8, col_step=1, sim_cols=8, min_cols=16):
@@ -1033,17 +1035,13 @@ def stixel_spec(disp_max=None, n_bins=None, q_min=16, sim=6, max_gap=2, min_rows
     return spec
 
 
-class StixelResult:
+class StixelResult(_Result):
     """What stixels_from_disparity returns, tensors on the input's device, Wv = ceil(W / col_step) visited columns: stixels int32
     [B,max_layers,Wv,4] = (v_bottom, v_top, q_base, n_rows) per column and layer, bottom-up, -1 beyond a column's count; n_stixels int32
     [B,Wv], not capped; boxes int32 [B,capacity,4] = (x, y, w, h) and info int32 [B,capacity,4] = (n_cols, q_lo, q_hi, q_med) per object,
     left to right, 0 in the rows at and beyond counts[b]; counts int32 [B], not capped by the capacity - None where not asked for - and
     the spec in use.  StereoRig.objects adds positions (float64 [B,capacity,3] metres, NaN beyond counts) and ground (a GroundResult)."""
     __slots__ = ("stixels", "n_stixels", "boxes", "info", "counts", "spec", "positions", "stat", "ground")
-
-    def __init__(self, **kw):
-        for k in self.__slots__:
-            setattr(self, k, kw.get(k))
 
 
 def stixels_from_disparity(d1, labels, disp_max=None, n_bins=None, q_min=16, sim=6, max_gap=2, min_rows=8, max_layers=8, col_step=1, sim_cols=8,
@@ -1056,16 +1054,12 @@ def stixels_from_disparity(d1, labels, disp_max=None, n_bins=None, q_min=16, sim
     into box_positions_from_disparity(d1, Q, boxes, counts).  n_bins None = 4 (disp_max + 1), as for the labels.  -> StixelResult;
     enqueued on torch's current stream, not waited for."""
     import torch
-    if not (isinstance(d1, torch.Tensor) and d1.is_cuda and d1.dtype == torch.float32 and d1.dim() in (2, 3)):
-        raise ValueError("d1 must be a CUDA float32 tensor [B,H,W]")
+    d, _ = _disparity_batch(d1, "d1", 32768)
     if not (isinstance(labels, torch.Tensor) and labels.is_cuda and labels.dtype == torch.uint8 and labels.device == d1.device and
             tuple(labels.shape) == tuple(d1.shape)):
         raise ValueError("labels must be a CUDA uint8 tensor of d1's shape on d1's device")
-    d = (d1.unsqueeze(0) if d1.dim() == 2 else d1).contiguous()
     lab = (labels.unsqueeze(0) if labels.dim() == 2 else labels).contiguous()
     B, H, W = d.shape
-    if B > 65535 or H < 1 or W < 1 or H > 32768 or H * W >= 2 ** 31:
-        raise ValueError("at most 65535 pairs of 1 <= width * height < 2^31 pixels and at most 32768 rows, got %s" % (tuple(d.shape),))
     if isinstance(capacity, bool) or int(capacity) != capacity or not 0 <= capacity < 2 ** 31:
         raise ValueError("capacity must be an integer >= 0, got %r" % (capacity,))
     capacity = int(capacity)
@@ -1083,40 +1077,16 @@ def stixels_from_disparity(d1, labels, disp_max=None, n_bins=None, q_min=16, sim
     L = stixel_lib()
     nbytes = L.sv_stixel_workspace_bytes(ctypes.byref(spec), B, W, H)
     ws = torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=dev)
-    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()  # noqa: E731
     with torch.cuda.device(dev):
-        rc = L.sv_stixel_disparity_device(d.data_ptr(), lab.data_ptr(), B, W, H, ctypes.byref(spec), capacity, ptr(stixels), ptr(n_stixels), ptr(boxes),
-                                          ptr(info), counts.data_ptr(), ws.data_ptr(), nbytes, torch.cuda.current_stream(dev).cuda_stream)
-    if rc != 0:
-        msg = "sv_stixel_disparity_device failed (%d): %s" % (rc, (L.sv_last_error(None) or b"").decode())
-        raise ValueError(msg) if rc == -1 else StereoError(msg)
+        rc = L.sv_stixel_disparity_device(d.data_ptr(), lab.data_ptr(), B, W, H, ctypes.byref(spec), capacity, _ptr(stixels), _ptr(n_stixels), _ptr(boxes),
+                                          _ptr(info), counts.data_ptr(), ws.data_ptr(), nbytes, torch.cuda.current_stream(dev).cuda_stream)
+    _check(rc, "sv_stixel_disparity_device")
     return res
-
-
-class SvOccupancySpec(ctypes.Structure):
-    """sv_occupancy_spec of include/stereo_vision_hip.h."""
-    _fields_ = [("x_range", ctypes.c_double * 2), ("y_range", ctypes.c_double * 2), ("z_range", ctypes.c_double * 2), ("scale", ctypes.c_int32),
-                ("z_scale", ctypes.c_int32), ("min_obstacle", ctypes.c_int32), ("min_ground", ctypes.c_int32), ("min_rays", ctypes.c_int32),
-                ("reserved", ctypes.c_int32 * 5)]
-
-
-_occupancy_bound = False
 
 
 def occupancy_lib():
     """The library with the sv_occupancy_* signatures declared."""
-    global _occupancy_bound
-    L = lib()
-    if not _occupancy_bound:
-        vp, ci, sp = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(SvOccupancySpec)
-        L.sv_occupancy_dims.argtypes = [sp, ctypes.POINTER(ci), ctypes.POINTER(ci)]
-        L.sv_occupancy_dims.restype = ci
-        L.sv_occupancy_disparity_device.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, sp, vp, vp, vp, vp]
-        L.sv_occupancy_disparity_device.restype = ci
-        L.sv_debug_occupancy.argtypes = [ci, vp]
-        L.sv_debug_occupancy.restype = ci
-        _occupancy_bound = True
-    return L
+    return _bind("occupancy")
 
 
 def occupancy_spec(x_range, y_range, z_range, scale, z_scale=20, min_obstacle=3, min_ground=1, min_rays=1, XT=None):
@@ -1134,17 +1104,13 @@ def occupancy_spec(x_range, y_range, z_range, scale, z_scale=20, min_obstacle=3,
     return spec, rows, cols
 
 
-class OccupancyResult:
+class OccupancyResult(_Result):
     """What occupancy_from_disparity returns, tensors on the input's device: cells int32 [B,rows,cols,4] = (n_ground, n_obstacle, h_lo,
     h_hi) per cell (h in steps of 1 / z_scale above z_range[0], -1 for a cell without evidence: stereo_vision.sv.occupancy_heights turns
     them into metres), n_rays int32 [B,rows,cols] = the sight lines that crossed the cell, state uint8 [B,rows,cols] (0 unknown, 1 free,
     2 occupied; None where not asked for) and the spec in use.  StereoRig.occupancy adds ground, the GroundResult the grid was made
     from."""
     __slots__ = ("cells", "n_rays", "state", "spec", "ground")
-
-    def __init__(self, **kw):
-        for k in self.__slots__:
-            setattr(self, k, kw.get(k))
 
 
 def occupancy_from_disparity(d1, labels, free_row, free_disp, Q, x_range, y_range, z_range, scale, z_scale=20, XR=None, XT=None, min_obstacle=3,
@@ -1159,14 +1125,9 @@ def occupancy_from_disparity(d1, labels, free_row, free_disp, Q, x_range, y_rang
     -> OccupancyResult; enqueued on torch's current stream, not waited for."""
     import torch
     spec, rows, cols = occupancy_spec(x_range, y_range, z_range, scale, z_scale, min_obstacle, min_ground, min_rays, XT)
-    if not (isinstance(d1, torch.Tensor) and d1.is_cuda and d1.dtype == torch.float32 and d1.dim() in (2, 3)):
-        raise ValueError("d1 must be a CUDA float32 tensor [B,H,W]")
-    one = d1.dim() == 2
-    d = (d1.unsqueeze(0) if one else d1).contiguous()
+    d, one = _disparity_batch(d1, "d1", 32768)
     B, H, W = d.shape
     dev = d.device
-    if B > 65535 or H < 1 or W < 1 or H > 32768 or H * W >= 2 ** 31:
-        raise ValueError("at most 65535 pairs of 1 <= width * height < 2^31 pixels and at most 32768 rows, got %s" % (tuple(d.shape),))
     ins = []
     for t, dtype, shape, name in ((labels, torch.uint8, (B, H, W), "labels"), (free_row, torch.int32, (B, W), "free_row"), (free_disp, torch.float32, (B, W), "free_disp")):
         if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dtype):
@@ -1175,9 +1136,7 @@ def occupancy_from_disparity(d1, labels, free_row, free_disp, Q, x_range, y_rang
         if tuple(t.shape) != shape:
             raise ValueError("%s must be %s, got %s" % (name, list(shape), list(t.shape)))
         ins.append(t.contiguous())
-    q = np.ascontiguousarray(Q, dtype=np.float64).reshape(16)
-    xr = None if XR is None else np.ascontiguousarray(XR, dtype=np.float64).reshape(9)
-    xt = None if XT is None else np.ascontiguousarray(XT, dtype=np.float64).reshape(3)
+    q, xr, xt = _reproject_pointers(Q, XR, XT)
     cells = torch.empty((B, rows, cols, 4), dtype=torch.int32, device=dev)
     n_rays = torch.empty((B, rows, cols), dtype=torch.int32, device=dev)
     state = torch.empty((B, rows, cols), dtype=torch.uint8, device=dev) if want_state else None
@@ -1186,13 +1145,9 @@ def occupancy_from_disparity(d1, labels, free_row, free_disp, Q, x_range, y_rang
         return res
     L = occupancy_lib()
     with torch.cuda.device(dev):
-        rc = L.sv_occupancy_disparity_device(d.data_ptr(), ins[0].data_ptr(), ins[1].data_ptr(), ins[2].data_ptr(), B, W, H, q.ctypes.data,
-                                             xr.ctypes.data if xr is not None else None, xt.ctypes.data if xt is not None else None, ctypes.byref(spec),
-                                             cells.data_ptr(), n_rays.data_ptr(), state.data_ptr() if state is not None else None,
-                                             torch.cuda.current_stream(dev).cuda_stream)
-    if rc != 0:
-        msg = "sv_occupancy_disparity_device failed (%d): %s" % (rc, (L.sv_last_error(None) or b"").decode())
-        raise ValueError(msg) if rc == -1 else StereoError(msg)
+        rc = L.sv_occupancy_disparity_device(d.data_ptr(), ins[0].data_ptr(), ins[1].data_ptr(), ins[2].data_ptr(), B, W, H, q, xr, xt,
+                                             ctypes.byref(spec), cells.data_ptr(), n_rays.data_ptr(), _ptr(state), torch.cuda.current_stream(dev).cuda_stream)
+    _check(rc, "sv_occupancy_disparity_device")
     return res
 
 
@@ -1202,27 +1157,9 @@ def debug_occupancy(combine=True, counter=None):
     return int(occupancy_lib().sv_debug_occupancy(1 if combine else 0, None if counter is None else counter.data_ptr()))
 
 
-class SvOccupancyMapSpec(ctypes.Structure):
-    """sv_occupancy_map_spec of include/stereo_vision_hip.h."""
-    _fields_ = [("top", ctypes.c_int32), ("left", ctypes.c_int32), ("rows", ctypes.c_int32), ("cols", ctypes.c_int32), ("scale", ctypes.c_int32),
-                ("l_occ", ctypes.c_int32), ("l_free", ctypes.c_int32), ("l_min", ctypes.c_int32), ("l_max", ctypes.c_int32), ("reserved", ctypes.c_int32 * 7)]
-
-
-_occupancy_map_bound = False
-
-
 def occupancy_map_lib():
     """The library with the signatures of group (K) declared."""
-    global _occupancy_map_bound
-    L = occupancy_lib()
-    if not _occupancy_map_bound:
-        vp, ci = ctypes.c_void_p, ctypes.c_int
-        L.sv_occupancy_fuse_device.argtypes = [vp, vp, ci, ci, ctypes.POINTER(SvOccupancySpec), ctypes.POINTER(SvOccupancyMapSpec), ci, ci, vp, vp, vp, vp, vp]
-        L.sv_occupancy_fuse_device.restype = ci
-        L.sv_debug_occupancy_fuse.argtypes = [ci, vp]
-        L.sv_debug_occupancy_fuse.restype = ci
-        _occupancy_map_bound = True
-    return L
+    return _bind("occupancy_map")
 
 
 def _occupancy_map_struct(words):
@@ -1252,14 +1189,34 @@ def _occupancy_frame_spec(frame_grid):
     return occupancy_spec(**g)[0]
 
 
-class OccupancyMapResult:
+def _state_batch(L, state, frame):
+    """The states of a batch of frames, checked against the frame grid they were made under -> the contiguous CUDA uint8 tensor [B,frame
+    rows,frame cols] (one frame gets its B here)."""
+    import torch
+    frows, fcols = ctypes.c_int(), ctypes.c_int()
+    _check(L.sv_occupancy_dims(ctypes.byref(frame), ctypes.byref(frows), ctypes.byref(fcols)), "sv_occupancy_dims")
+    if not (isinstance(state, torch.Tensor) and state.is_cuda and state.dtype == torch.uint8 and state.dim() in (2, 3)):
+        raise ValueError("state must be a CUDA uint8 tensor [B,rows,cols]")
+    st = (state.unsqueeze(0) if state.dim() == 2 else state).contiguous()
+    if tuple(st.shape[1:]) != (frows.value, fcols.value):
+        raise ValueError("state must be [B,%d,%d] for this frame grid, got %s" % (frows.value, fcols.value, tuple(st.shape)))
+    return st
+
+
+def _device_poses(poses, dev):
+    """Poses (tx, ty, c, s) as a contiguous float64 tensor on dev: a tensor there as it is, a numpy array uploaded once."""
+    import torch
+    if isinstance(poses, torch.Tensor):
+        if poses.device != dev or poses.dtype != torch.float64:
+            raise ValueError("poses must be float64 on the device (%s) of the other tensors" % (dev,))
+        return poses.contiguous()
+    return torch.from_numpy(np.ascontiguousarray(poses, dtype=np.float64)).to(dev)
+
+
+class OccupancyMapResult(_Result):
     """What occupancy_fuse returns: logodds int16 [rows,cols], last_seen int32 [rows,cols] (None where none is kept) - tensors on the
     states' device - and spec, the SvOccupancyMapSpec of the map going out."""
     __slots__ = ("logodds", "last_seen", "spec")
-
-    def __init__(self, **kw):
-        for k in self.__slots__:
-            setattr(self, k, kw.get(k))
 
 
 def occupancy_fuse(state, poses, frame_grid, map, logodds=None, last_seen=None, seq0=0, shift=(0, 0), out=None):
@@ -1278,16 +1235,9 @@ def occupancy_fuse(state, poses, frame_grid, map, logodds=None, last_seen=None, 
     words = occupancy_map_words(map)
     rows, cols = words["rows"], words["cols"]
     frame = _occupancy_frame_spec(frame_grid)
-    frows, fcols = ctypes.c_int(), ctypes.c_int()
     L = occupancy_map_lib()
-    if L.sv_occupancy_dims(ctypes.byref(frame), ctypes.byref(frows), ctypes.byref(fcols)) != 0:
-        raise ValueError((L.sv_last_error(None) or b"").decode())
-    if not (isinstance(state, torch.Tensor) and state.is_cuda and state.dtype == torch.uint8 and state.dim() in (2, 3)):
-        raise ValueError("state must be a CUDA uint8 tensor [B,rows,cols]")
-    st = (state.unsqueeze(0) if state.dim() == 2 else state).contiguous()
+    st = _state_batch(L, state, frame)
     B, dev = st.shape[0], st.device
-    if tuple(st.shape[1:]) != (frows.value, fcols.value):
-        raise ValueError("state must be [B,%d,%d] for this frame grid, got %s" % (frows.value, fcols.value, tuple(st.shape)))
     if B > 65535:
         raise ValueError("at most 65535 frames per call, got %d" % B)
     if isinstance(seq0, bool) or int(seq0) != seq0 or seq0 < 0 or int(seq0) + B > 2 ** 31 - 1:
@@ -1295,12 +1245,7 @@ def occupancy_fuse(state, poses, frame_grid, map, logodds=None, last_seen=None, 
     if len(shift) != 2 or any(isinstance(v, bool) or int(v) != v or abs(int(v)) > 2 ** 31 - 1 for v in shift):
         raise ValueError("shift must be two integers (rows, cols), got %r" % (shift,))
     shift = (int(shift[0]), int(shift[1]))
-    if isinstance(poses, torch.Tensor):
-        if poses.device != dev or poses.dtype != torch.float64:
-            raise ValueError("poses must be float64 on the device of state")
-        p = poses.contiguous()
-    else:
-        p = torch.from_numpy(np.ascontiguousarray(poses, dtype=np.float64)).to(dev)
+    p = _device_poses(poses, dev)
     if p.dim() == 1 and B == 1:
         p = p.unsqueeze(0)
     if tuple(p.shape) != (B, 4):
@@ -1325,12 +1270,9 @@ def occupancy_fuse(state, poses, frame_grid, map, logodds=None, last_seen=None, 
         l_out, s_out = torch.empty_like(l_in), (torch.empty_like(s_in) if keep_seen else None)
     spec = _occupancy_map_struct(words)
     with torch.cuda.device(dev):
-        rc = L.sv_occupancy_fuse_device(st.data_ptr() if B else None, p.data_ptr() if B else None, B, int(seq0), ctypes.byref(frame), ctypes.byref(spec), shift[0], shift[1],
-                                        l_in.data_ptr(), s_in.data_ptr() if keep_seen else None, l_out.data_ptr(), s_out.data_ptr() if keep_seen else None,
-                                        torch.cuda.current_stream(dev).cuda_stream)
-    if rc != 0:
-        msg = "sv_occupancy_fuse_device failed (%d): %s" % (rc, (L.sv_last_error(None) or b"").decode())
-        raise ValueError(msg) if rc == -1 else StereoError(msg)
+        rc = L.sv_occupancy_fuse_device(_ptr(st), _ptr(p), B, int(seq0), ctypes.byref(frame), ctypes.byref(spec), shift[0], shift[1], l_in.data_ptr(), _ptr(s_in),
+                                        l_out.data_ptr(), _ptr(s_out), torch.cuda.current_stream(dev).cuda_stream)
+    _check(rc, "sv_occupancy_fuse_device")
     return OccupancyMapResult(logodds=l_out, last_seen=s_out, spec=spec)
 
 
@@ -1340,33 +1282,15 @@ def debug_occupancy_fuse(cull=True, counter=None):
     return int(occupancy_map_lib().sv_debug_occupancy_fuse(1 if cull else 0, None if counter is None else counter.data_ptr()))
 
 
-_map_match_bound = False
-
-
 def map_match_lib():
     """The library with the signatures of group (L) declared."""
-    global _map_match_bound
-    L = occupancy_map_lib()
-    if not _map_match_bound:
-        vp, ci, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
-        L.sv_map_match_workspace.argtypes = [ctypes.POINTER(SvOccupancySpec), ci, ci, ctypes.POINTER(sz)]
-        L.sv_map_match_workspace.restype = ci
-        L.sv_map_match_device.argtypes = [vp, vp, ci, ci, ctypes.POINTER(SvOccupancySpec), ctypes.POINTER(SvOccupancyMapSpec), vp, ci, ci, vp, vp, vp, vp, vp, sz, vp]
-        L.sv_map_match_device.restype = ci
-        L.sv_debug_map_match.argtypes = [ci, vp]
-        L.sv_debug_map_match.restype = ci
-        _map_match_bound = True
-    return L
+    return _bind("map_match")
 
 
-class MapMatchResult:
+class MapMatchResult(_Result):
     """What occupancy_match returns, tensors on the states' device: sums int64 [B,P,2] = (H, M), counts int32 [B,P,2] = (n_occ, n_free)
     (both None where not asked for), best int32 [B] and best_score int64 [B] (both None where not asked for)."""
     __slots__ = ("sums", "counts", "best", "best_score")
-
-    def __init__(self, **kw):
-        for k in self.__slots__:
-            setattr(self, k, kw.get(k))
 
     def score(self, w_occ=1, w_free=0):
         """int64 [B,P]: w_occ H - w_free M of the sums."""
@@ -1387,22 +1311,10 @@ def occupancy_match(state, poses, frame_grid, map, logodds, w_occ=1, w_free=0, w
     words = occupancy_map_words(map)
     rows, cols = words["rows"], words["cols"]
     frame = _occupancy_frame_spec(frame_grid)
-    frows, fcols = ctypes.c_int(), ctypes.c_int()
     L = map_match_lib()
-    if L.sv_occupancy_dims(ctypes.byref(frame), ctypes.byref(frows), ctypes.byref(fcols)) != 0:
-        raise ValueError((L.sv_last_error(None) or b"").decode())
-    if not (isinstance(state, torch.Tensor) and state.is_cuda and state.dtype == torch.uint8 and state.dim() in (2, 3)):
-        raise ValueError("state must be a CUDA uint8 tensor [B,rows,cols]")
-    st = (state.unsqueeze(0) if state.dim() == 2 else state).contiguous()
+    st = _state_batch(L, state, frame)
     B, dev = st.shape[0], st.device
-    if tuple(st.shape[1:]) != (frows.value, fcols.value):
-        raise ValueError("state must be [B,%d,%d] for this frame grid, got %s" % (frows.value, fcols.value, tuple(st.shape)))
-    if isinstance(poses, torch.Tensor):
-        if poses.device != dev or poses.dtype != torch.float64:
-            raise ValueError("poses must be float64 on the device of state")
-        p = poses.contiguous()
-    else:
-        p = torch.from_numpy(np.ascontiguousarray(poses, dtype=np.float64)).to(dev)
+    p = _device_poses(poses, dev)
     if p.dim() == 2 and B == 1:
         p = p.unsqueeze(0)
     if p.dim() != 3 or p.shape[0] != B or p.shape[2] != 4:
@@ -1429,18 +1341,14 @@ def occupancy_match(state, poses, frame_grid, map, logodds, w_occ=1, w_free=0, w
     if B == 0:  # nothing to enqueue
         return res
     nbytes = ctypes.c_size_t()
-    if L.sv_map_match_workspace(ctypes.byref(frame), B, int(w_free), ctypes.byref(nbytes)) != 0:
-        raise ValueError((L.sv_last_error(None) or b"").decode())
+    _check(L.sv_map_match_workspace(ctypes.byref(frame), B, int(w_free), ctypes.byref(nbytes)), "sv_map_match_workspace")
     ws = torch.empty((nbytes.value + 15) // 16 * 2, dtype=torch.int64, device=dev)
     spec = _occupancy_map_struct(words)
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     with torch.cuda.device(dev):
         rc = L.sv_map_match_device(st.data_ptr(), p.data_ptr(), B, n_poses, ctypes.byref(frame), ctypes.byref(spec), logodds.data_ptr(), int(w_occ), int(w_free),
-                                   ptr(res.sums), ptr(res.counts), ptr(res.best), ptr(res.best_score), ws.data_ptr(), ws.numel() * 8,
+                                   _ptr(res.sums), _ptr(res.counts), _ptr(res.best), _ptr(res.best_score), ws.data_ptr(), ws.numel() * 8,
                                    torch.cuda.current_stream(dev).cuda_stream)
-    if rc != 0:
-        msg = "sv_map_match_device failed (%d): %s" % (rc, (L.sv_last_error(None) or b"").decode())
-        raise ValueError(msg) if rc == -1 else StereoError(msg)
+    _check(rc, "sv_map_match_device")
     return res  # ws goes back to torch's allocator, which hands it out again on this stream only: behind the kernels
 
 
@@ -1450,25 +1358,9 @@ def debug_map_match(group=0, counter=None):
     return int(map_match_lib().sv_debug_map_match(int(group), None if counter is None else counter.data_ptr()))
 
 
-_clearance_bound = False
-
-
 def clearance_lib():
     """The library with the signatures of group (M) declared."""
-    global _clearance_bound
-    L = occupancy_map_lib()
-    if not _clearance_bound:
-        vp, ci, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
-        L.sv_clearance_workspace.argtypes = [ci, ci, ctypes.POINTER(sz)]
-        L.sv_clearance_workspace.restype = ci
-        L.sv_clearance_device.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, sz, vp]
-        L.sv_clearance_device.restype = ci
-        L.sv_clearance_paths_device.argtypes = [vp, ctypes.POINTER(SvOccupancyMapSpec), vp, ci, ci, vp, vp, ci, ci, vp, vp, vp, vp]
-        L.sv_clearance_paths_device.restype = ci
-        L.sv_debug_clearance.argtypes = [ci, vp]
-        L.sv_debug_clearance.restype = ci
-        _clearance_bound = True
-    return L
+    return _bind("clearance")
 
 
 def occupancy_clearance(logodds, radius, t_occ, last_seen=None, unknown=False, out=None, workspace=None):
@@ -1502,30 +1394,23 @@ def occupancy_clearance(logodds, radius, t_occ, last_seen=None, unknown=False, o
         raise ValueError("out must be a contiguous uint16 tensor [%d,%d] on the device of logodds" % (rows, cols))
     L = clearance_lib()
     nbytes = ctypes.c_size_t()
-    if L.sv_clearance_workspace(rows, cols, ctypes.byref(nbytes)) != 0:
-        raise ValueError((L.sv_last_error(None) or b"").decode())
+    _check(L.sv_clearance_workspace(rows, cols, ctypes.byref(nbytes)), "sv_clearance_workspace")
     if workspace is None:
         workspace = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
     elif not (isinstance(workspace, torch.Tensor) and workspace.device == dev and workspace.dtype == torch.uint8 and workspace.is_contiguous()
               and workspace.numel() >= nbytes.value):
         raise ValueError("workspace must be a contiguous uint8 tensor of at least %d bytes on the device of logodds" % nbytes.value)
     with torch.cuda.device(dev):
-        rc = L.sv_clearance_device(logodds.data_ptr(), None if last_seen is None else last_seen.data_ptr(), rows, cols, int(radius), int(t_occ), int(bool(unknown)),
+        rc = L.sv_clearance_device(logodds.data_ptr(), _ptr(last_seen), rows, cols, int(radius), int(t_occ), int(bool(unknown)),
                                    out.data_ptr(), workspace.data_ptr(), workspace.numel(), torch.cuda.current_stream(dev).cuda_stream)
-    if rc != 0:
-        msg = "sv_clearance_device failed (%d): %s" % (rc, (L.sv_last_error(None) or b"").decode())
-        raise ValueError(msg) if rc == -1 else StereoError(msg)
+    _check(rc, "sv_clearance_device")
     return out  # a workspace of torch's goes back to its allocator, which hands it out again on this stream only: behind the kernels
 
 
-class ClearancePathsResult:
+class ClearancePathsResult(_Result):
     """What clearance_paths returns, int32 tensors [K] on the field's device: first_hit (the number of steps where a path is clear),
     min_d2 (65535 where nothing was looked up) and n_outside."""
     __slots__ = ("first_hit", "min_d2", "n_outside")
-
-    def __init__(self, **kw):
-        for k in self.__slots__:
-            setattr(self, k, kw.get(k))
 
 
 def clearance_paths(d2, map, poses, discs, radius):
@@ -1542,12 +1427,7 @@ def clearance_paths(d2, map, poses, discs, radius):
     if not (isinstance(d2, torch.Tensor) and d2.is_cuda and d2.dtype == torch.uint16 and tuple(d2.shape) == (rows, cols) and d2.is_contiguous()):
         raise ValueError("d2 must be a contiguous CUDA uint16 tensor [%d,%d]" % (rows, cols))
     dev = d2.device
-    if isinstance(poses, torch.Tensor):
-        if poses.device != dev or poses.dtype != torch.float64:
-            raise ValueError("poses must be float64 on the device of d2")
-        p = poses.contiguous()
-    else:
-        p = torch.from_numpy(np.ascontiguousarray(poses, dtype=np.float64)).to(dev)
+    p = _device_poses(poses, dev)
     if p.dim() != 3 or p.shape[2] != 4 or p.shape[0] > CLEARANCE_PATHS_MAX or not 1 <= p.shape[1] <= CLEARANCE_PATHS_MAX:
         raise ValueError("poses must be [K,T,4] with K <= 65535 and 1 <= T <= 65535, got %s" % (tuple(p.shape),))
     K, T = p.shape[:2]
@@ -1559,9 +1439,7 @@ def clearance_paths(d2, map, poses, discs, radius):
     with torch.cuda.device(dev):
         rc = L.sv_clearance_paths_device(d2.data_ptr(), ctypes.byref(spec), p.data_ptr(), K, T, centres.ctypes.data, r2.ctypes.data, len(r2), radius,
                                          res.first_hit.data_ptr(), res.min_d2.data_ptr(), res.n_outside.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-    if rc != 0:
-        msg = "sv_clearance_paths_device failed (%d): %s" % (rc, (L.sv_last_error(None) or b"").decode())
-        raise ValueError(msg) if rc == -1 else StereoError(msg)
+    _check(rc, "sv_clearance_paths_device")
     return res
 
 
