@@ -100,6 +100,11 @@ def ref_digests():
     for k, _, p_, L_, R_ in t.random_parameter_cases():
         n = ref.run_stages(p_, L_, R_)
         out[k] = t.stage_digests(ref, p_, L_, R_) if n >= 3 else {"n": n}
+    import content_cases as cc
+    for key in cc.keys():
+        k, p_, L_, R_ = t.content_case(key)
+        n = ref.run_stages(p_, L_, R_)
+        out[k] = {"n": n, "stages": {s: sha(ref.stage(s)) for s in (STAGES if n >= 3 else t.CONTENT_EARLY_STAGES)}}
     with open(os.path.join(HERE, "ref_digests.json"), "w") as f:
         json.dump(out, f, indent=0, sort_keys=True)
         f.write("\n")

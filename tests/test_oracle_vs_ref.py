@@ -9,6 +9,7 @@ import sys
 import numpy as np
 import pytest
 
+import content_cases
 import degenerate_sets
 import util
 from pyoracle import ElasParams, RefElas
@@ -16,6 +17,7 @@ from pyoracle import ElasParams, RefElas
 SYNTHETIC = [(11, 140, 400, 64), (12, 90, 333, 48), (13, 200, 640, 128), (14, 64, 128, 32)]
 PRESETS = ["driver", "robotics", "middlebury"]
 KITTI_MINI_FRAMES = range(21)
+CONTENT_EARLY_STAGES = ["desc1", "desc2", "dcan_raw", "support"]  # what a pair with fewer than three support points produces
 PROFILE_PAIRS = ["aloe", "cones", "raindeer", "urban1", "urban2", "urban3", "urban4"]
 
 
@@ -212,6 +214,32 @@ def test_pairs_with_degenerate_support_sets(ref, oracle, stored, name):
         assert (np.diff(us) == p.candidate_stepsize).all() and (np.diff(vs) == p.candidate_stepsize).all()
     else:
         assert L.shape[0] == 32 and len(vs) == 2 and vs[1] - vs[0] == p.candidate_stepsize and n >= 6 and t1 > 0 and t2 > 0
+
+
+def content_case(key):
+    """(digest key, params, L, R) of one of tests/content_cases.py.  The compiled reference runs every one of them."""
+    _, preset, over, L, R = content_cases.make(key)
+    return content_cases.digest_key(key), content_cases.params(ElasParams, preset, over), L, R
+
+
+@pytest.mark.parametrize("key", content_cases.keys())
+def test_content_cases(ref, oracle, stored, key):
+    """Pairs whose content forces exact ties, saturated descriptor bytes and matches at the ends of the disparity range
+    (tests/content_cases.py; what each family is for is asserted in tests/test_content_edges.py): the support count and every stage of the
+    restatement equal the reference's.  A pair with fewer than three support points ends after the support stage in both (elas.cpp:63-69):
+    there the stages up to the support list are compared."""
+    dkey, p, L, R = content_case(key)
+    want = stored[dkey]
+    names = util.STAGES if want["n"] >= 3 else CONTENT_EARLY_STAGES
+    assert sorted(want["stages"]) == sorted(names)
+    n = oracle.run_stages(p, L, R)
+    assert n == want["n"]
+    bad = [k for k in names if util.sha(oracle.stage(k)) != want["stages"][k]]
+    assert not bad, bad
+    if ref is not None:
+        assert ref.run_stages(p, L, R) == n
+        bad = [k for k in names if not np.array_equal(ref.stage(k).view(np.uint8), oracle.stage(k).view(np.uint8))]
+        assert not bad, bad
 
 
 def test_random_parameter_sets(ref, oracle, stored):
