@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "box_kernels.h"
+#include "wave_ops.h"
 
 namespace sv {
 
@@ -111,23 +112,9 @@ __global__ __launch_bounds__(256) void k_box_positions(BoxArgs a) {
                                                                                                         colsum, acc);
         __syncthreads();
         // prefix sums over the bins: a thread owns 16 consecutive bins; inclusive scan inside the wavefront, then across the four
-        const int lane = tid & 63, wave = tid >> 6;
         int own = 0;
         for (int k = 0; k < BOX_BINS / 256; k++) own += (int)hist[tid * (BOX_BINS / 256) + k];
-        int incl = own;
-        for (int s = 1; s < 64; s <<= 1) {
-            const int up = __shfl_up(incl, s);
-            if (lane >= s) incl += up;
-        }
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        int before = 0;
-        n_valid = 0;
-        for (int k = 0; k < 4; k++) {
-            if (k < wave) before += s_wave[k];
-            n_valid += s_wave[k];
-        }
-        incl += before;
+        const int incl = block_exclusive_scan<256>(own, s_wave, &n_valid) + own;
         const int rank = (n_valid + 1) / 2;  // lower median: the smallest q whose cumulative count reaches it
         if (n_valid > 0 && incl - own < rank && rank <= incl) {  // exactly one thread
             int cum = incl - own;

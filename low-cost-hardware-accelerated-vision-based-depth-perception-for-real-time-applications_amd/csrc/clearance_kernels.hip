@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include "clearance_kernels.h"
+#include "wave_ops.h"
 
 namespace sv {
 
@@ -165,11 +166,7 @@ __global__ __launch_bounds__(CLEARANCE_THREADS) void k_clearance_paths(Clearance
         step += step_q, k += step_r;
         if (k >= a.n_discs) k -= a.n_discs, step++;
     }
-    for (int d = 32; d >= 1; d >>= 1) {
-        first = min(first, __shfl_down(first, d));
-        least = min(least, __shfl_down(least, d));
-        outside += __shfl_down(outside, d);
-    }
+    first = wave_min(first), least = wave_min(least), outside = wave_sum(outside);
     if (lane == 0) a.first_hit[path] = first, a.min_d2[path] = least, a.n_outside[path] = outside;
 }
 

@@ -20,14 +20,11 @@
 #include <stdint.h>
 
 #include "cloud_kernels.h"
+#include "wave_ops.h"
 
 namespace sv {
 
 namespace {
-
-__device__ __forceinline__ int lanes_below(unsigned long long mask) {
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
 
 __device__ __forceinline__ bool frame_vec_ok(const CloudArgs &a, const float *frame) {
     return a.step == 1 && (reinterpret_cast<uintptr_t>(frame) & 15) == 0;
@@ -55,21 +52,14 @@ __global__ __launch_bounds__(64 * CLOUD_WAVES) void k_cloud_count(CloudArgs a) {
 // Exclusive prefix sum of a frame's tile counts in place: a thread owns a run of consecutive tiles.
 __global__ __launch_bounds__(256) void k_cloud_scan(CloudArgs a) {
     __shared__ int s_wave[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
+    const int tid = threadIdx.x, b = blockIdx.x;
     int32_t *t = a.tiles + (size_t)b * a.n_tiles;
     const int per = (a.n_tiles + 255) / 256;  // <= 2^13
     const int lo = tid * per < a.n_tiles ? tid * per : a.n_tiles, hi = lo + per < a.n_tiles ? lo + per : a.n_tiles;
     int own = 0;
     for (int k = lo; k < hi; k++) own += t[k];
-    int incl = own;
-    for (int s = 1; s < 64; s <<= 1) {
-        const int up = __shfl_up(incl, s);
-        if (lane >= s) incl += up;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int run = incl - own;
-    for (int k = 0; k < wave; k++) run += s_wave[k];
+    int total;
+    int run = block_exclusive_scan<256>(own, s_wave, &total);  // every thread gets here
     for (int k = lo; k < hi; k++) {
         const int c = t[k];
         t[k] = run;

@@ -32,6 +32,7 @@
 // __syncthreads, __shfl_up and the atomics.
 #if !defined(DG_HOST_EMULATION) || defined(DG_SIMT_EMULATION)
 #define DG_COOP 1
+#include "wave_ops.h"
 #endif
 
 namespace sv {
@@ -813,35 +814,13 @@ __host__ __device__ inline size_t dg_prep_scratch_words(const DgPrep &pp, int m)
 constexpr int DG_PREP_CHUNK = 16;                          // consecutive positions a thread owns in the k-d passes
 constexpr int DG_PREP_MAX = DG_THREADS * DG_PREP_CHUNK;    // 4096 vertices
 
-__device__ __forceinline__ int dg_block_scan(int val, DG_LDS int *cells, int *total) {  // exclusive prefix sum over the workgroup's DG_THREADS values
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = val;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(incl, off, 64);
-        incl += lane >= off ? o : 0;
-    }
-    if (lane == 63) cells[wave] = incl;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < DG_THREADS / 64; w++) {
-        const int c = cells[w];
-        base += w < wave ? c : 0;
-        tot += c;
-    }
-    __syncthreads();
-    *total = tot;
-    return base + incl - val;
-}
-
 // Exclusive prefix sums of the set bits of the bit map's words: pm[w] = bits set in words [0, w).  Returns through *total the bit count.
 __device__ __forceinline__ void dg_word_prefix(DG_LDS const uint32_t *bm, DG_LDS uint16_t *pm, int nwords, DG_LDS int *cells, int *total) {
     const int per = (nwords + DG_THREADS - 1) / DG_THREADS;
     const int w0 = min((int)threadIdx.x * per, nwords), w1 = min(w0 + per, nwords);
     int mine = 0;
     for (int w = w0; w < w1; w++) mine += __popc(bm[w]);
-    int acc = dg_block_scan(mine, cells, total);
+    int acc = block_exclusive_scan<DG_THREADS>(mine, cells, total);
     for (int w = w0; w < w1; w++) {
         pm[w] = (uint16_t)acc;
         acc += __popc(bm[w]);
@@ -975,7 +954,7 @@ __device__ __forceinline__ int dg_prepare(const DgLds &L, int npts, const DgPrep
                 }
             }
         }
-        const int base = dg_block_scan(__popc(bits), cells, &total);
+        const int base = block_exclusive_scan<DG_THREADS>((int)__popc(bits), cells, &total);
         chunk[tid] = (uint32_t)base | (bits << 16);
         __syncthreads();
 #pragma unroll
@@ -1021,34 +1000,12 @@ struct DgPrepScratch {  // per set: bit map, word prefixes, three vertex-order a
 __device__ __forceinline__ uint32_t gld(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ __forceinline__ void gst(uint32_t *p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 
-__device__ __forceinline__ int dgp_block_scan(int val, int *cells, int *total) {  // exclusive prefix sum over DGP_THREADS values (cells: LDS, 16 ints)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = val;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(incl, off, 64);
-        incl += lane >= off ? o : 0;
-    }
-    if (lane == 63) cells[wave] = incl;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < DGP_THREADS / 64; w++) {
-        const int c = cells[w];
-        base += w < wave ? c : 0;
-        tot += c;
-    }
-    __syncthreads();
-    *total = tot;
-    return base + incl - val;
-}
-
 __device__ __forceinline__ void dgp_word_prefix(const uint32_t *bm, uint32_t *pm, int nwords, int *cells) {
     const int per = (nwords + DGP_THREADS - 1) / DGP_THREADS;
     const int w0 = min((int)threadIdx.x * per, nwords), w1 = min(w0 + per, nwords);
     int mine = 0, total;
     for (int w = w0; w < w1; w++) mine += __popc(gld(bm + w));
-    int acc = dgp_block_scan(mine, cells, &total);
+    int acc = block_exclusive_scan<DGP_THREADS>(mine, cells, &total);
     for (int w = w0; w < w1; w++) {
         gst(pm + w, (uint32_t)acc);
         acc += __popc(gld(bm + w));
@@ -1179,7 +1136,7 @@ __device__ __forceinline__ int dg_prepare_global(const int32_t *__restrict__ sup
             mine += (int)flag;
         }
         int total;
-        int acc = dgp_block_scan(mine, cells, &total);
+        int acc = block_exclusive_scan<DGP_THREADS>(mine, cells, &total);
         for (int i = c0; i < c1; i++) {
             const uint32_t f = pref[i] >> 31;
             pref[i] = (f << 31) | (uint32_t)acc;

@@ -22,6 +22,7 @@
 #include <stdint.h>
 
 #include "ground_kernels.h"
+#include "wave_ops.h"
 
 namespace sv {
 
@@ -34,7 +35,7 @@ template <bool AGGREGATE>
 __global__ __launch_bounds__(GROUND_THREADS) void k_ground_hist(GroundArgs a) {
     __shared__ uint32_t s_bins[GROUND_BINS_MAX];
     __shared__ uint32_t s_wave[GROUND_THREADS / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, b = blockIdx.y;
     const int per = (a.n_bins + GROUND_THREADS - 1) / GROUND_THREADS;  // <= 16: the thread's run of bins in the scan
     const int lo = tid * per < a.n_bins ? tid * per : a.n_bins, hi = lo + per < a.n_bins ? lo + per : a.n_bins;
     for (int j = tid; j < a.n_bins; j += GROUND_THREADS) s_bins[j] = 0u;
@@ -51,6 +52,7 @@ __global__ __launch_bounds__(GROUND_THREADS) void k_ground_hist(GroundArgs a) {
                 if (d > 0.f) key = ground_bin(d, a.n_bins);
             }
             if (AGGREGATE) {
+                // issues from the run's head, not from its tail as wave_ops.h's wave_run would: no __shfl_down, and not timed otherwise
                 const int prev = __shfl_up(key, 1);
                 const bool head = lane == 0 || key != prev;
                 const unsigned long long heads = __ballot(head);
@@ -66,18 +68,8 @@ __global__ __launch_bounds__(GROUND_THREADS) void k_ground_hist(GroundArgs a) {
             for (int j = tid; j < a.n_bins; j += GROUND_THREADS) a.vdisp[r * a.n_bins + j] = s_bins[j];
         uint32_t own = 0u;
         for (int j = lo; j < hi; j++) own += s_bins[j];
-        uint32_t incl = own;
-        for (int s = 1; s < 64; s <<= 1) {
-            const uint32_t up = __shfl_up(incl, s);
-            if (lane >= s) incl += up;
-        }
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        uint32_t run = incl - own, total = 0u;
-        for (int k = 0; k < GROUND_THREADS / 64; k++) {
-            if (k < wave) run += s_wave[k];
-            total += s_wave[k];
-        }
+        uint32_t total;
+        uint32_t run = block_exclusive_scan<GROUND_THREADS>(own, s_wave, &total);
         for (int j = lo; j < hi; j++) {
             const uint32_t c = s_bins[j];
             s_bins[j] = run;
@@ -92,14 +84,6 @@ __global__ __launch_bounds__(GROUND_THREADS) void k_ground_hist(GroundArgs a) {
         if (tid == 0) p[a.n_bins] = total;
         __syncthreads();
     }
-}
-
-__device__ __forceinline__ unsigned long long wave_max(unsigned long long k) {
-    for (int s = 32; s >= 1; s >>= 1) {
-        const unsigned long long o = __shfl_xor(k, s);
-        k = o > k ? o : k;
-    }
-    return k;
 }
 
 __global__ __launch_bounds__(GROUND_THREADS) void k_ground_search(GroundArgs a) {
@@ -155,7 +139,7 @@ __global__ __launch_bounds__(GROUND_THREADS) void k_ground_pick(GroundArgs a) {
     int valid = 0;  // <= W * H < 2^31
     for (int v = tid; v < a.H; v += GROUND_THREADS) valid += (int)a.prefix[((size_t)b * a.H + v) * (a.n_bins + 1) + a.n_bins];
     best = wave_max(best);
-    for (int s = 32; s >= 1; s >>= 1) valid += __shfl_xor(valid, s);
+    valid = wave_sum(valid);
     if ((tid & 63) == 0) s_key[tid >> 6] = best, s_valid[tid >> 6] = valid;
     __syncthreads();
     if (tid == 0) {

@@ -7,6 +7,7 @@
 // Integer byte work (descriptors, SAD) uses v_sad_u8 on 4-byte words; there is no matrix contraction here and
 // therefore no MFMA.  Batch dimension: blockIdx.z (or .y) walks the pairs of a launch.
 #include "sv_kernels.h"
+#include "wave_ops.h"
 
 #include <algorithm>
 #include <atomic>
@@ -72,8 +73,7 @@ __device__ __forceinline__ void map_st(T *base, uint32_t idx, T v) { *reinterpre
 
 // work counters (sv_debug_counters): one atomic per wavefront, only in the COUNT instantiations of the matching kernels
 __device__ __forceinline__ void count_add(unsigned long long *slot, int mine) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) mine += __shfl_xor(mine, off, 64);
+    mine = wave_sum(mine);
     if ((threadIdx.x & 63) == 0 && mine) atomicAdd(slot, (unsigned long long)mine);
 }
 
@@ -588,30 +588,6 @@ void launch_support(const KParams &k, const SlotDev &s, int n, hipStream_t st) {
 #define FLT_THREADS 256   // lattice points per collect block (1 024 until round 5: a 16-wavefront workgroup waits for a CU with four free wavefront slots per SIMD - 12 x its own duration inside the pipeline)
 #define RSV_THREADS 256   // threads of the resolve workgroup
 
-// exclusive prefix sum over the workgroup (NT threads): wavefront scans by shuffles, one barrier pair for the wavefront totals
-template <int NT>
-__device__ __forceinline__ int block_exclusive_scan(int val, int *s_wave, int *total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = val;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(incl, off, 64);
-        incl += lane >= off ? o : 0;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < NT / 64; w++) {
-        const int c = s_wave[w];
-        base += w < wave ? c : 0;
-        tot += c;
-    }
-    __syncthreads();
-    *total = tot;
-    return base + incl - val;
-}
-
 __host__ __device__ inline int filter_collect_blocks(int lat) { return (lat + FLT_THREADS - 1) / FLT_THREADS; }
 
 // ---- (1) classification (elas.cpp:152-176), one thread per lattice point.  A block of 256 consecutive indices needs the
@@ -996,8 +972,7 @@ __global__ __launch_bounds__(FLT_THREADS) void k_filter_collect(KParams k, const
     if (wave == 0) {  // this block's first list position: the sum of its predecessors' counts
         int acc = 0;
         for (int j = lane; j < b; j += 64) acc += bcnt[(size_t)pair * nb2 + j];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
+        acc = wave_sum(acc);
         if (lane == 0) s_excl = acc;
     }
     __syncthreads();
@@ -1023,7 +998,7 @@ __global__ __launch_bounds__(FLT_THREADS) void k_filter_collect(KParams k, const
             if (dist < 10000000) key = ((unsigned long long)dist << 34) | ((unsigned long long)q << 11) | (unsigned long long)dv;
         }
 #pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
+        for (int off = 32; off >= 1; off >>= 1) {  // wave_ops.h's wave_min, written out: the call reorders this kernel's instructions
             const unsigned long long o = __shfl_xor(key, off, 64);
             key = o < key ? o : key;
         }
@@ -1055,7 +1030,7 @@ __global__ __launch_bounds__(64) void k_filter_corners(KParams k, const int32_t 
             }
     }
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
+    for (int off = 32; off >= 1; off >>= 1) {  // wave_ops.h's wave_sum and wave_min, written out as one loop: five calls reorder this kernel's instructions
         n_main += __shfl_xor(n_main, off, 64);
 #pragma unroll
         for (int c = 0; c < 4; c++) {
@@ -2098,7 +2073,7 @@ __global__ __launch_bounds__(NT) void k_ccl_band(KParams k, int nproc, int epoch
             const int c = c0 + lane;
             const int cnt = c < nch ? __popcll(Sm[r * nch + c]) : 0;
             int incl = cnt;
-            for (int o = 1; o < 64; o <<= 1) {
+            for (int o = 1; o < 64; o <<= 1) {  // wave_ops.h's wave_inclusive_sum, written out: the call changes this kernel's instructions
                 const int t = __shfl_up(incl, o, 64);
                 if (lane >= o) incl += t;
             }
@@ -2414,7 +2389,7 @@ __global__ __launch_bounds__(GAPR_THREADS) void k_gap_rows(KParams k, int nproc,
             const unsigned long long w = c < nch ? mw[c] : 0ull;
             int last = w ? c * 64 + 63 - __clzll((long long)w) : -1;
 #pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
+            for (int o = 1; o < 64; o <<= 1) {  // wave_ops.h's wave_inclusive_max, written out: the call changes this kernel's instructions
                 const int t = __shfl_up(last, o, 64);
                 if (lane >= o) last = max(last, t);
             }
@@ -2430,7 +2405,7 @@ __global__ __launch_bounds__(GAPR_THREADS) void k_gap_rows(KParams k, int nproc,
             const unsigned long long w = c < nch ? mw[c] : 0ull;
             int first = w ? c * 64 + __ffsll((long long)w) - 1 : 0x7FFFFFFF;
 #pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
+            for (int o = 1; o < 64; o <<= 1) {  // the mirror image (a running minimum from the right) has this one user and no helper
                 const int t = __shfl_down(first, o, 64);
                 if (lane + o < 64) first = min(first, t);
             }

@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "occupancy_kernels.h"
+#include "wave_ops.h"
 
 namespace sv {
 
@@ -65,19 +66,13 @@ __global__ __launch_bounds__(256) void k_occupancy_evidence(OccupancyArgs a) {
     }
     bool issue = cell >= 0;
     if (COMBINE) {  // every lane of the block gets here: no early return above
-        const int lane = __lane_id();
-        const int prev = __shfl_up(cell, 1), next = __shfl_down(cell, 1);
-        const bool head = lane == 0 || prev != cell, tail = lane == 63 || next != cell;
-        const unsigned long long heads = __ballot(head);
-        const unsigned long long upto = lane == 63 ? ~0ull : ((2ull << lane) - 1);  // lanes 0..lane
-        const int head_lane = 63 - __clzll((long long)(heads & upto));
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {  // inclusive segmented scan: the tail holds the run's counts, minimum and maximum
+        const WaveRun run = wave_run(cell);
+        wave_run_scan(run, [&](int d, bool take) {  // the tail holds the run's counts, minimum and maximum
             const uint32_t c = __shfl_up(cnt, d);
             const int l = __shfl_up(lo, d), h = __shfl_up(hi, d);
-            if (lane - d >= head_lane) cnt += c, lo = min(lo, l), hi = max(hi, h);
-        }
-        issue = issue && tail;
+            if (take) cnt += c, lo = min(lo, l), hi = max(hi, h);
+        });
+        issue = issue && run.tail;
     }
     if (issue) {
         int32_t *c = a.cells + 4 * (((size_t)b * a.rows) * a.cols + cell);

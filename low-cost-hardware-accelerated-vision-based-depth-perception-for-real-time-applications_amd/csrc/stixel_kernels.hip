@@ -12,10 +12,10 @@
 //             second kernel reads: it does not depend on the stixels output being asked for.
 //   objects   k_stixel_objects: a workgroup per pair, the visited columns in chunks of STIXEL_THREADS with carried prefixes.  A thread
 //             per column flags "a segment starts here" and "a segment ends here" from the first layer of the columns i - 1, i, i + 1.  A
-//             running maximum of the start positions (wave scan by __shfl_up, wave totals through LDS, the carry from the chunk before)
+//             running maximum of the start positions (wave_ops.h's wave_inclusive_max, wave totals through LDS, the carry from the chunk before)
 //             tells the column that ends a segment where it began; a prefix sum over "ends a kept segment" gives the segment its output
 //             row.  The kept segments of a chunk are queued in LDS and taken by the four wavefronts in turn: 64 lanes stride over the
-//             segment's columns for top, bottom, q_lo, q_hi (__shfl_xor), then find the lower median by bisection on the value - at most
+//             segment's columns for top, bottom, q_lo, q_hi (wave_min / wave_max), then find the lower median by bisection on the value - at most
 //             12 counting passes over q_lo .. q_hi.  A rank count, not an LDS histogram per segment: a segment of a few columns would
 //             pay for clearing up to 4096 bins, four of them would have to sit side by side, and the passes read 16 bytes per column
 //             that the cache holds.  No atomics anywhere, no workgroup waits for another.
@@ -26,6 +26,7 @@
 #include <stdint.h>
 
 #include "stixel_kernels.h"
+#include "wave_ops.h"
 
 namespace sv {
 
@@ -91,27 +92,6 @@ __global__ __launch_bounds__(STIXEL_COLUMNS) void k_stixel_columns(StixelArgs a)
     a.layer0[(size_t)b * a.Wv + i] = first;
 }
 
-__device__ __forceinline__ int wave_min(int x) {
-    for (int s = 32; s >= 1; s >>= 1) {
-        const int o = __shfl_xor(x, s);
-        x = o < x ? o : x;
-    }
-    return x;
-}
-
-__device__ __forceinline__ int wave_max_i(int x) {
-    for (int s = 32; s >= 1; s >>= 1) {
-        const int o = __shfl_xor(x, s);
-        x = o > x ? o : x;
-    }
-    return x;
-}
-
-__device__ __forceinline__ int wave_sum(int x) {
-    for (int s = 32; s >= 1; s >>= 1) x += __shfl_xor(x, s);
-    return x;
-}
-
 __global__ __launch_bounds__(STIXEL_THREADS) void k_stixel_objects(StixelArgs a) {
     constexpr int WAVES = STIXEL_THREADS / 64;
     __shared__ int s_start[WAVES], s_kept[WAVES];
@@ -146,10 +126,7 @@ __global__ __launch_bounds__(STIXEL_THREADS) void k_stixel_objects(StixelArgs a)
             }
         }
         // the running maximum of the start positions: where the segment of column i began
-        for (int s = 1; s < 64; s <<= 1) {
-            const int up = __shfl_up(start, s);
-            if (lane >= s && up > start) start = up;
-        }
+        start = wave_inclusive_max(start);
         if (lane == 63) s_start[wave] = start;
         __syncthreads();
         int before = carry_start, all = carry_start;
@@ -161,18 +138,8 @@ __global__ __launch_bounds__(STIXEL_THREADS) void k_stixel_objects(StixelArgs a)
         if (before > start) start = before;
         const bool kept = ends && i - start + 1 >= a.min_cols;  // ends: column i has a stixel, so a segment began at or before it
         // the prefix sum over "ends a kept segment": the segment's output row
-        int incl = kept ? 1 : 0;
-        for (int s = 1; s < 64; s <<= 1) {
-            const int up = __shfl_up(incl, s);
-            if (lane >= s) incl += up;
-        }
-        if (lane == 63) s_kept[wave] = incl;
-        __syncthreads();
-        int local = incl - (kept ? 1 : 0), total = 0;
-        for (int k = 0; k < WAVES; k++) {
-            if (k < wave) local += s_kept[k];
-            total += s_kept[k];
-        }
+        int total;
+        const int local = block_exclusive_scan<STIXEL_THREADS>(kept ? 1 : 0, s_kept, &total);
         if (kept && carry_kept + local < a.capacity) s_first[local] = start, s_last[local] = i;
         __syncthreads();
         // the chunk's segments with an output row, a wavefront each; rows at and beyond the capacity are counted, not written
@@ -189,7 +156,7 @@ __global__ __launch_bounds__(STIXEL_THREADS) void k_stixel_objects(StixelArgs a)
                     q_lo = s.z < q_lo ? s.z : q_lo;
                     q_hi = s.z > q_hi ? s.z : q_hi;
                 }
-                v_top = wave_min(v_top), v_bot = wave_max_i(v_bot), q_lo = wave_min(q_lo), q_hi = wave_max_i(q_hi);
+                v_top = wave_min(v_top), v_bot = wave_max(v_bot), q_lo = wave_min(q_lo), q_hi = wave_max(q_hi);
                 // the smallest x with #{q_base <= x} >= rank; lo and hi are the same in every lane
                 const int rank = (n_cols + 1) / 2;
                 int lo = q_lo, hi = q_hi;

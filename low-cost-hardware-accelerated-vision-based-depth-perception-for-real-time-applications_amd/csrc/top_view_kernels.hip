@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include "top_view_kernels.h"
+#include "wave_ops.h"
 
 namespace sv {
 
@@ -64,15 +65,9 @@ __global__ __launch_bounds__(256) void k_top_view(TopViewArgs a) {
     bool issue = cell >= 0;
     int count = 1;
     if (COMBINE) {  // every lane of the block gets here: no early return above
-        const int lane = __lane_id();
-        const int prev = __shfl_up(cell, 1), next = __shfl_down(cell, 1);
-        const bool head = lane == 0 || prev != cell, tail = lane == 63 || next != cell;
-        issue = issue && tail;
-        if (MODE == TV_MODE_COUNT) {
-            const unsigned long long heads = __ballot(head);
-            const unsigned long long upto = lane == 63 ? ~0ull : ((2ull << lane) - 1);  // lanes 0..lane
-            count = lane - (63 - __clzll((long long)(heads & upto))) + 1;
-        }
+        const WaveRun run = wave_run(cell);
+        issue = issue && run.tail;
+        if (MODE == TV_MODE_COUNT) count = (int)__lane_id() - run.head_lane + 1;  // the run's length
     }
     if (issue) {
         if (MODE == TV_MODE_REFERENCE) {

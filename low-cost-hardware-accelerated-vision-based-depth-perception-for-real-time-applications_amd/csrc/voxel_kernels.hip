@@ -29,6 +29,7 @@
 #include <stdint.h>
 
 #include "voxel_kernels.h"
+#include "wave_ops.h"
 
 namespace sv {
 
@@ -146,22 +147,17 @@ __global__ __launch_bounds__(64 * CLOUD_WAVES) void k_voxel_insert(VoxelArgs a) 
         }
         bool issue = keep;
         if (COMBINE) {  // every lane of the wavefront gets here
-            const unsigned long long prev = __shfl_up(key, 1), next = __shfl_down(key, 1);
-            const bool is_head = lane == 0 || prev != key, is_tail = lane == 63 || next != key;
-            const unsigned long long heads = __ballot(is_head);
-            const unsigned long long upto = lane == 63 ? ~0ull : ((2ull << lane) - 1);  // lanes 0..lane
-            const int head_lane = 63 - __clzll((long long)(heads & upto));
+            const WaveRun run = wave_run(key);
             uint32_t c01 = C[0] | (C[1] << 16), c23 = C[2] | (C[3] << 16);  // a run's sums are <= 64 * 255 < 2^16
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {  // inclusive segmented scan: the tail holds the run's sums
+            wave_run_scan(run, [&](int d, bool take) {  // the tail holds the run's sums
                 const uint32_t s0 = __shfl_up(S[0], d), s1 = __shfl_up(S[1], d), s2 = __shfl_up(S[2], d);
                 const uint32_t t01 = colors ? __shfl_up(c01, d) : 0u, t23 = colors ? __shfl_up(c23, d) : 0u;
-                if (lane - d >= head_lane) S[0] += s0, S[1] += s1, S[2] += s2, c01 += t01, c23 += t23;
-            }
+                if (take) S[0] += s0, S[1] += s1, S[2] += s2, c01 += t01, c23 += t23;
+            });
             C[0] = c01 & 0xFFFFu, C[1] = c01 >> 16, C[2] = c23 & 0xFFFFu, C[3] = c23 >> 16;
-            n = (uint32_t)(lane - head_lane + 1);  // the run's lanes hold consecutive visited pixels, all kept
+            n = (uint32_t)(lane - run.head_lane + 1);  // the run's lanes hold consecutive visited pixels, all kept
             first = v - (n - 1);
-            issue = keep && is_tail;
+            issue = keep && run.tail;
         }
         if (issue) voxel_add<COUNT_ATOMICS>(a, w, key, n, first, S, C, colors);
     }
@@ -205,13 +201,8 @@ __global__ __launch_bounds__(64 * CLOUD_WAVES) void k_voxel_write(VoxelArgs a) {
     }
     const int word = tile * (CLOUD_TILE / 32) + (lane >> 1);
     uint32_t bits = word < a.n_words ? (w.mask[word] >> (16 * (lane & 1))) & 0xFFFFu : 0u;
-    int incl = __popc(bits);
-    const int own = incl;
-    for (int d = 1; d < 64; d <<= 1) {
-        const int up = __shfl_up(incl, d);
-        if (lane >= d) incl += up;
-    }
-    int r = a.c.tiles[(size_t)b * a.c.n_tiles + tile] + incl - own;
+    const int own = __popc(bits);
+    int r = a.c.tiles[(size_t)b * a.c.n_tiles + tile] + wave_inclusive_sum(own) - own;
     const float *frame = a.c.disp + (size_t)b * a.c.W * a.c.H;
     const uint32_t last = (uint32_t)(((size_t)1 << a.log2_slots) - 1);
     for (; bits; bits &= bits - 1, r++) {
