@@ -961,6 +961,81 @@ int sv_clearance_paths_device(const uint16_t *d2, const sv_occupancy_map_spec *m
  * rows x cols x (2 radius + 1)).  The results do not depend on it.  Returns SV_OK, or SV_ERR_ARG for another variant. */
 int sv_debug_clearance(int variant, unsigned long long *taps_device);
 
+/* ---- (N) the cost-to-goal field of the world map and routes through it: (M)'s field -> penalties -> path lengths -> cells to drive ---- */
+
+/* (M) judges paths that someone else produced; this group produces them.  A penalty per cell is made from the clearance field, the length
+ * of the cheapest path from every cell to the nearest goal is relaxed to its fixed point, and a route follows that field downhill from any
+ * start.  All arithmetic is integer and a shortest-path length under strictly positive weights is unique, so the results are bitwise
+ * reproducible whatever order relaxes them.  stereo_vision.sv.cost_cells / cost_to_goal / cost_to_goal_relax / cost_routes restate them in
+ * numpy.
+ *
+ *   pen        uint8 per cell: 255 (blocked) where d2 <= r2_block, elsewhere min(254, weight * max(0, soft - isqrt(d2))) with isqrt the
+ *              floor of the root, and 0 where d2 == 65535.  A caller may pass any uint8 array of its own.
+ *   free       a cell inside the map with pen != 255.  Outside the map is blocked: here the map's edge is a wall.
+ *   move       between 8-neighbours a and b, admissible iff both are free and, for a diagonal move, the two cells that share the corner,
+ *              (a.r, b.c) and (b.r, a.c), are free too: no corner is cut.  A step costs 10 along an axis and 14 diagonally.
+ *   field      cost = 0 on every goal that is inside the map and free (the others are ignored); on any other free cell a, cost[a] =
+ *              pen[a] + the minimum over the admissible b with a finite cost of cost[b] + step; 0x7FFFFFFF (COST_INF) where there is
+ *              none, and on blocked cells.  rows * cols <= 8 000 000 keeps (cells - 1) * 268 below 2^31 - 1.
+ *   sweep      one launch over tiles of 64 x 64 cells: a tile is read with a one-cell halo from one of two cost buffers, relaxed on its
+ *              own until nothing in it changes (or a fixed inner bound), and written to the other buffer.  Workgroups exchange data
+ *              across launch boundaries only.  A tile runs in a sweep iff it or one of its 8 neighbour tiles changed in the sweep
+ *              before - in the first sweep after init, iff it holds a goal; a tile that does not run leaves the field alone: it did
+ *              not change in the sweep before, so its cells are equal in both buffers.  Stopped before its fixed point the field is an
+ *              upper bound of the definition, cell by cell, and the same bits on every run.
+ *   route      from the start, repeat: write the current cell; stop with status 0 if its cost is 0; otherwise take, among the admissible
+ *              neighbours with a finite cost, the one with the least cost[b] + step, ties to the first in the order (-1,0), (0,-1),
+ *              (0,1), (1,0), (-1,-1), (-1,1), (1,-1), (1,1).  Status 1: the start is outside the map; 2: it is blocked or its cost is
+ *              COST_INF (length 0 for both); 4: the neighbour taken - if any - has no cost below the current cell's, i.e. the field was
+ *              not converged: the route stops there and is kept; 3: capacity cells were written before a goal was reached.  Cells past
+ *              length are -1. */
+
+/* Enqueued on `stream` (a hipStream_t, NULL = the default stream) as one element-wise kernel and not waited for.
+ *   d2           : uint16 [rows][cols] device, (M)'s field made with `radius` (1..254)
+ *   r2_block     : 0..radius^2 - above it a saturated cell would hide an obstacle; soft, weight : 0..254
+ *   pen          : uint8 [rows][cols] device, written in full
+ * Returns SV_OK, SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued, pen untouched, the text in sv_last_error(NULL) - for: a NULL d2 or pen; d2
+ * not 2-byte aligned; rows or cols outside 1..32768; radius outside 1..254; r2_block outside 0..radius^2; soft or weight outside 0..254;
+ * pen overlapping d2.  These checks run before any HIP call. */
+int sv_cost_cells_device(const uint16_t *d2, int rows, int cols, int radius, int r2_block, int soft, int weight, uint8_t *pen, void *stream);
+/* Host only: the bytes of the workspace sv_cost_to_goal_device needs - the words the sweeps of a call report into, the second cost buffer
+ * and two bytes per tile, each rounded up to 16.  SV_ERR_ARG (bytes untouched) for a NULL bytes, rows or cols outside 1..32768 or
+ * rows * cols above 8 000 000. */
+int sv_cost_to_goal_workspace(int rows, int cols, size_t *bytes);
+/* Enqueued on `stream` as one memset, with init == 1 two small kernels that start the field from the goals, exactly `sweeps` launches of
+ * the sweep above and one kernel that writes `info` - and not waited for: nothing is allocated, no host synchronisation is made, and
+ * every loop on the device has a bound fixed at launch.
+ *   pen          : uint8 [rows][cols] device
+ *   goals        : int32 [n_goals][2] = (row, col) device, 1 <= n_goals <= 1024
+ *   init         : 1 starts from the goals (nothing is assumed of cost or the workspace); 0 continues the field in `cost` with the state
+ *                  the previous call left in `workspace` - same pen, goals, rows, cols and buffers
+ *   sweeps       : even, 2..1024: the result always lands in `cost`, never in the workspace's twin
+ *   cost         : int32 [rows][cols] device
+ *   workspace    : device, 16-byte aligned, workspace_bytes >= what sv_cost_to_goal_workspace gives
+ *   info         : int32 [4] device: [0] = 1 if the last sweep changed any cell - the field is converged iff 0; [1] = the sweeps of this
+ *                  call that changed something; [2], [3] = 0
+ * Returns SV_OK, SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued, the outputs untouched, the text in sv_last_error(NULL) - for: a NULL pen,
+ * goals, cost, workspace or info; goals, cost or info not 4-byte, the workspace not 16-byte aligned; rows or cols outside 1..32768 or
+ * rows * cols above 8 000 000; n_goals outside 1..1024; init neither 0 nor 1; sweeps odd or outside 2..1024; too small a workspace; cost,
+ * info or the workspace overlapping one another, pen or goals.  These checks run before any HIP call. */
+int sv_cost_to_goal_device(const uint8_t *pen, int rows, int cols, const int32_t *goals, int n_goals, int init, int sweeps, int32_t *cost, void *workspace,
+                           size_t workspace_bytes, int32_t *info, void *stream);
+/* Enqueued on `stream` as one memset (the -1 of the cells) and one kernel - 8 lanes per route, one neighbour each - and not waited for.
+ *   cost, pen    : int32 and uint8 [rows][cols] device
+ *   starts       : int32 [n_routes][2] = (row, col) device, 0 <= n_routes <= 65535
+ *   capacity     : 1..65535 cells per route
+ *   cells        : int16 [n_routes][capacity][2] device; length, status : int32 [n_routes] device each; all written in full
+ * Returns SV_OK (nothing enqueued for n_routes == 0), SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued, the outputs untouched, the text in
+ * sv_last_error(NULL) - for: a NULL cost or pen, or a NULL starts or output with n_routes > 0; cost, starts, cells, length or status not
+ * 4-byte aligned; rows or cols outside 1..32768 or rows * cols above 8 000 000; n_routes outside 0..65535; capacity outside 1..65535; an
+ * output overlapping an input or another output.  These checks run before any HIP call. */
+int sv_cost_routes_device(const int32_t *cost, const uint8_t *pen, int rows, int cols, const int32_t *starts, int n_routes, int capacity, int16_t *cells,
+                          int32_t *length, int32_t *status, void *stream);
+/* Test hook for sv_cost_to_goal_device, process-wide: variant 0 (the default) runs the tiles the rule above names, 1 runs every tile in
+ * every sweep.  counters_device != NULL: two device uint64 that receive the tiles run and the inner iterations they made, added up over
+ * the calls.  cost and info do not depend on it.  Returns SV_OK, or SV_ERR_ARG for another variant. */
+int sv_debug_cost_to_goal(int variant, unsigned long long *counters_device);
+
 /* ---- (A) the reference's exported symbols ------------------------------------------------------------- */
 
 typedef struct {

@@ -508,7 +508,7 @@ class SvOccupancyMapSpec(ctypes.Structure):
 
 
 def _signatures():
-    """The table below: per stage group of the C API, (D) to (M), its functions and per function (restype, argtypes), parameter by
+    """The table below: per stage group of the C API, (D) to (N), its functions and per function (restype, argtypes), parameter by
     parameter as include/stereo_vision_hip.h declares them - tests/test_stage_signatures.py holds the two against each other."""
     P = ctypes.POINTER
     vp, ci, sz, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_int64
@@ -565,11 +565,18 @@ def _signatures():
             "sv_clearance_paths_device": (ci, [vp, om, vp, ci, ci, vp, vp, ci, ci, vp, vp, vp, vp]),
             "sv_debug_clearance": (ci, [ci, vp]),
         },
+        "cost": {  # (N)
+            "sv_cost_cells_device": (ci, [vp, ci, ci, ci, ci, ci, ci, vp, vp]),
+            "sv_cost_to_goal_workspace": (ci, [ci, ci, P(sz)]),
+            "sv_cost_to_goal_device": (ci, [vp, ci, ci, vp, ci, ci, ci, vp, vp, sz, vp, vp]),
+            "sv_cost_routes_device": (ci, [vp, vp, ci, ci, vp, ci, ci, vp, vp, vp, vp]),
+            "sv_debug_cost_to_goal": (ci, [ci, vp]),
+        },
     }
 
 
 STAGE_SIGNATURES = _signatures()  # plain data: made without loading the library
-_GROUP_NEEDS = {"voxel": ("cloud",), "occupancy_map": ("occupancy",), "map_match": ("occupancy_map",), "clearance": ("occupancy_map",)}
+_GROUP_NEEDS = {"voxel": ("cloud",), "occupancy_map": ("occupancy",), "map_match": ("occupancy_map",), "clearance": ("occupancy_map",), "cost": ("clearance",)}
 _bound_groups = set()
 
 
@@ -1448,6 +1455,155 @@ def debug_clearance(variant=0, counter=None):
     two kernels; 3: the two kernels without the early exit) and a CUDA int64 [1] tensor (or None) that receives the taps of the row walk.
     Process-wide; a test hook."""
     return int(clearance_lib().sv_debug_clearance(int(variant), None if counter is None else counter.data_ptr()))
+
+
+def cost_lib():
+    """The library with the signatures of group (N) declared."""
+    return _bind("cost")
+
+
+def _map_tensor(t, dtype, name, like=None):
+    """A field of the world map, checked: a contiguous CUDA tensor [rows,cols] of `dtype`, on the device and of the shape of `like` where
+    that is given -> (rows, cols)."""
+    import torch
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.dim() == 2 and t.is_contiguous()
+            and (like is None or (t.device == like.device and t.shape == like.shape))):
+        raise ValueError("%s must be a contiguous CUDA %s tensor [rows,cols]%s" % (name, str(dtype).replace("torch.", ""),
+                                                                                 "" if like is None else " %s on %s" % (tuple(like.shape), like.device)))
+    rows, cols = t.shape
+    if not (1 <= rows <= 32768 and 1 <= cols <= 32768):
+        raise ValueError("a map of %d x %d cells: 1 .. 32768 in either dimension" % (rows, cols))
+    return rows, cols
+
+
+def _cell_list(cells, dev, lo, hi, name):
+    """Goals or starts -> a contiguous int32 tensor [n,2] on dev: a numpy array or a list is uploaded, a tensor on dev is taken as it is."""
+    import torch
+    from .stereo_vision.sv import _cost_cell_list
+    if isinstance(cells, torch.Tensor):
+        if cells.device != dev or cells.dtype != torch.int32 or cells.dim() != 2 or cells.shape[1] != 2 or not lo <= cells.shape[0] <= hi:
+            raise ValueError("%s as a tensor must be int32 [n,2] on %s with %d <= n <= %d" % (name, dev, lo, hi))
+        return cells.contiguous()
+    return torch.from_numpy(_cost_cell_list(cells, lo, hi, name)).to(dev)
+
+
+def cost_cells(d2, radius, r2_block, soft=0, weight=0, out=None):
+    """The penalties of a clearance field - the definition of stereo_vision.sv.cost_cells on the GPU, bit for bit, in one element-wise
+    kernel: d2 a contiguous CUDA uint16 tensor [rows,cols] (occupancy_clearance's with `radius`), r2_block in 0 .. radius^2, soft and
+    weight in 0 .. 254; out: a contiguous uint8 tensor [rows,cols] to write into.  -> the uint8 tensor: 255 where d2 <= r2_block,
+    elsewhere min(254, weight * max(0, soft - isqrt(d2))); enqueued on torch's current stream, not waited for."""
+    import torch
+    rows, cols = _map_tensor(d2, torch.uint16, "d2")
+    if out is None:
+        out = torch.empty((rows, cols), dtype=torch.uint8, device=d2.device)
+    else:
+        _map_tensor(out, torch.uint8, "out", like=d2)
+    for v, what in ((radius, "radius"), (r2_block, "r2_block"), (soft, "soft"), (weight, "weight")):
+        if isinstance(v, bool) or int(v) != v or abs(v) > 2 ** 31 - 1:
+            raise ValueError("%s must be an integer, got %r" % (what, v))
+    with torch.cuda.device(d2.device):
+        rc = cost_lib().sv_cost_cells_device(d2.data_ptr(), rows, cols, int(radius), int(r2_block), int(soft), int(weight), out.data_ptr(),
+                                             torch.cuda.current_stream(d2.device).cuda_stream)
+    _check(rc, "sv_cost_cells_device")
+    return out
+
+
+class CostToGoalResult(_Result):
+    """What occupancy_cost_to_goal returns: cost (int32 tensor [rows,cols]), converged (bool), sweeps (int: the sweeps that changed a
+    cell, and one more for the sweep that confirmed the fixed point where it was reached) and workspace (the uint8 tensor the state of the
+    sweeps lives in)."""
+    __slots__ = ("cost", "converged", "sweeps", "workspace")
+
+
+def occupancy_cost_to_goal(pen, goals, max_sweeps=4096, round=16, out=None, workspace=None):
+    """The cost-to-goal field of a world map - the definition of stereo_vision.sv.cost_to_goal on the GPU, bit for bit once converged: pen
+    a contiguous CUDA uint8 tensor [rows,cols] (cost_cells', or the caller's own; 255 = blocked; rows x cols <= 8 000 000), goals integers
+    [G,2] = (row, col), 1 <= G <= 1024 (numpy - uploaded once - or an int32 tensor on pen's device); those outside the map or on blocked
+    cells are ignored.  out: a contiguous int32 tensor [rows,cols] to write into; workspace: a uint8 tensor of at least
+    sv_cost_to_goal_workspace's bytes to reuse.
+
+    The C entry is called in rounds of `round` sweeps (even, 2 .. 1024; the last round is cut to what max_sweeps leaves, made even) and
+    enqueues on torch's current stream without waiting; after each round the 16 bytes of its info are read back - the only wait - and
+    the rounds stop once a round's last sweep changed nothing, or after max_sweeps.  -> CostToGoalResult.  With converged == False the
+    field is an upper bound of the definition, cell by cell: every finite cost in it is the length of some admissible path, only not
+    yet of the cheapest one."""
+    import torch
+    rows, cols = _map_tensor(pen, torch.uint8, "pen")
+    dev = pen.device
+    if rows * cols > 8000000:
+        raise ValueError("a field of %d x %d cells: at most 8 000 000, so that every cost stays below 2^31 - 1" % (rows, cols))
+    for v, lo, hi, what in ((max_sweeps, 1, 2 ** 31 - 1, "max_sweeps"), (round, 2, 1024, "round")):
+        if isinstance(v, bool) or int(v) != v or not lo <= v <= hi:
+            raise ValueError("%s must be an integer in %d .. %d, got %r" % (what, lo, hi, v))
+    if round % 2:
+        raise ValueError("round must be even, got %r" % (round,))
+    g = _cell_list(goals, dev, 1, 1024, "goals")
+    if out is None:
+        out = torch.empty((rows, cols), dtype=torch.int32, device=dev)
+    else:
+        _map_tensor(out, torch.int32, "out", like=pen)
+    L = cost_lib()
+    nbytes = ctypes.c_size_t()
+    _check(L.sv_cost_to_goal_workspace(rows, cols, ctypes.byref(nbytes)), "sv_cost_to_goal_workspace")
+    if workspace is None:
+        workspace = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    elif not (isinstance(workspace, torch.Tensor) and workspace.device == dev and workspace.dtype == torch.uint8 and workspace.is_contiguous()
+              and workspace.numel() >= nbytes.value):
+        raise ValueError("workspace must be a contiguous uint8 tensor of at least %d bytes on the device of pen" % nbytes.value)
+    info = torch.empty(4, dtype=torch.int32, device=dev)
+    done, changing, converged = 0, 0, False
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        while done < max_sweeps and not converged:
+            n = min(int(round), int(max_sweeps) - done)
+            n += n & 1
+            rc = L.sv_cost_to_goal_device(pen.data_ptr(), rows, cols, g.data_ptr(), g.shape[0], int(done == 0), n, out.data_ptr(), workspace.data_ptr(),
+                                          workspace.numel(), info.data_ptr(), stream)
+            _check(rc, "sv_cost_to_goal_device")
+            words = info.cpu().numpy()  # 16 bytes: the wait of the round
+            done += n
+            changing += int(words[1])
+            converged = int(words[0]) == 0
+    return CostToGoalResult(cost=out, converged=converged, sweeps=changing + int(converged), workspace=workspace)
+
+
+class CostRoutesResult(_Result):
+    """What cost_routes returns, tensors on the field's device: cells int16 [K,capacity,2] = (row, col), -1 past a route's length; length
+    int32 [K]; status int32 [K] - 0 a goal was reached, 1 the start is outside the map, 2 it is blocked or no goal reaches it, 3 capacity
+    cells were written first, 4 the field was not converged where the route stopped."""
+    __slots__ = ("cells", "length", "status")
+
+
+def cost_routes(cost, pen, starts, capacity):
+    """K routes walked down a cost-to-goal field - the definition of stereo_vision.sv.cost_routes on the GPU, bit for bit, in one kernel
+    of 8 lanes per route: cost a contiguous CUDA int32 tensor [rows,cols] (occupancy_cost_to_goal's), pen the uint8 tensor it was made
+    from, starts integers [K,2] = (row, col), 0 <= K <= 65535 (numpy or an int32 tensor on the device), capacity in 1 .. 65535 cells per
+    route.  -> CostRoutesResult; enqueued on torch's current stream, not waited for."""
+    import torch
+    rows, cols = _map_tensor(cost, torch.int32, "cost")
+    _map_tensor(pen, torch.uint8, "pen", like=cost)
+    dev = cost.device
+    if rows * cols > 8000000:
+        raise ValueError("a field of %d x %d cells: at most 8 000 000" % (rows, cols))
+    if isinstance(capacity, bool) or int(capacity) != capacity or not 1 <= capacity <= 65535:
+        raise ValueError("capacity must be an integer in 1 .. 65535, got %r" % (capacity,))
+    s = _cell_list(starts, dev, 0, 65535, "starts")
+    K = s.shape[0]
+    res = CostRoutesResult(cells=torch.empty((K, int(capacity), 2), dtype=torch.int16, device=dev), length=torch.empty((K,), dtype=torch.int32, device=dev),
+                           status=torch.empty((K,), dtype=torch.int32, device=dev))
+    if K == 0:  # nothing to enqueue
+        return res
+    with torch.cuda.device(dev):
+        rc = cost_lib().sv_cost_routes_device(cost.data_ptr(), pen.data_ptr(), rows, cols, s.data_ptr(), K, int(capacity), res.cells.data_ptr(),
+                                              res.length.data_ptr(), res.status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    _check(rc, "sv_cost_routes_device")
+    return res
+
+
+def debug_cost_to_goal(variant=0, counters=None):
+    """sv_debug_cost_to_goal: the tiles a sweep of occupancy_cost_to_goal runs (0: those the dirty bytes name; 1: every tile in every
+    sweep) and a CUDA int64 [2] tensor (or None) that receives the tiles run and their inner iterations.  Process-wide; a test hook."""
+    return int(cost_lib().sv_debug_cost_to_goal(int(variant), None if counters is None else counters.data_ptr()))
 
 
 def host_support_filter(params, dcan, width, height, threads=0, lattice=False):

@@ -36,7 +36,7 @@ import ctypes
 import numpy as np
 
 from .engine import (SvParams, StereoEngine, StereoError, box_positions_from_disparity, box_spec, cloud_spec, compact_cloud_from_disparity,
-                     ground_from_disparity, ground_spec, lib, occupancy_from_disparity, occupancy_fuse, occupancy_match, occupancy_clearance, clearance_paths, occupancy_spec, pinned_array, reproject, split_clouds, stixel_spec, stixels_from_disparity,
+                     ground_from_disparity, ground_spec, lib, occupancy_from_disparity, occupancy_fuse, occupancy_match, occupancy_clearance, clearance_paths, cost_cells, cost_routes, occupancy_cost_to_goal, occupancy_spec, pinned_array, reproject, split_clouds, stixel_spec, stixels_from_disparity,
                      top_view_from_disparity, top_view_spec, split_voxel_clouds, voxel_cloud_from_disparity, voxel_spec)
 from .stereo_vision.sv import CAMERA_TO_VEHICLE, DEFAULT_CALIBRATION  # noqa: F401 (CAMERA_TO_VEHICLE: re-exported for top_view)
 from .stereo_vision.sv import free_space_points, ground_pose
@@ -425,7 +425,8 @@ class OccupancyMap:
     the numpy definition on CPU tensors, the same methods and the same bits.  log_odds_words: l_occ, l_free, l_min, l_max (log-odds times
     100).  words is the map's sv_occupancy_map_spec as a dict (top and left move with recenter), seq the number of frames fused so far:
     the sequence number the next frame carries into last_seen.  clearance() and check_paths() are group (M): the squared distance to the nearest
-    obstacle per cell, and candidate paths checked against it; clearance_radius is the radius in cells of the last clearance()."""
+    obstacle per cell, and candidate paths checked against it; clearance_radius is the radius in cells of the last clearance().
+    cost_to_goal() and routes() are group (N): the length of the cheapest path from every cell to a goal, and the cells to drive."""
 
     def __init__(self, x_range, y_range, scale, device="cuda", **log_odds_words):
         import torch
@@ -438,6 +439,7 @@ class OccupancyMap:
         self.last_seen, self._spare_last_seen = (torch.full(shape, -1, dtype=torch.int32, device=self.device) for _ in range(2))
         self.seq = 0
         self._d2, self._clearance_workspace, self.clearance_radius = None, None, None  # clearance()'s, made on its first call
+        self._pen, self._cost, self._cost_workspace = None, None, None  # cost_to_goal()'s, made on its first call
 
     def reset(self):
         """A fresh map at the place it has scrolled to: logodds 0, last_seen -1, seq 0."""
@@ -569,6 +571,60 @@ class OccupancyMap:
         p = p.cpu().numpy() if isinstance(p, torch.Tensor) else p
         res = _sv.clearance_paths(d2.numpy(), self.words, p, discs[0], discs[1], self.clearance_radius)
         return ClearancePathsResult(**{k: torch.from_numpy(res[k]) for k in ClearancePathsResult.__slots__})
+
+    def cost_to_goal(self, goal_xy, block_m, soft_m=0.0, weight=0, max_sweeps=4096):
+        """The cost-to-goal field of the map under the last clearance() (stereo_vision.sv.cost_cells and cost_to_goal): goal_xy float64
+        [G,2] ([2] for one goal) world points in metres - stereo_vision.sv.occupancy_cells_of names their cells; a cell within block_m
+        of an obstacle is blocked (r2_block = ceil(block_m scale)^2; ValueError if that radius exceeds clearance()'s), a free cell
+        nearer than soft_m pays weight per cell of the difference (soft = ceil(soft_m scale)).  -> engine.CostToGoalResult with cost
+        int32 [rows,cols] on the map's device, converged and sweeps; with converged == False (max_sweeps reached) the field is an upper
+        bound of the definition.  pen, cost and the workspace stay with the map and are written again by the next call; routes() uses
+        them.  Waits for 16 bytes per round of sweeps."""
+        import torch
+        from .engine import CostToGoalResult
+        if self._d2 is None:
+            raise ValueError("cost_to_goal: no clearance field yet - call clearance() first")
+        for v, what in ((block_m, "block_m"), (soft_m, "soft_m")):
+            if not np.isfinite(v) or v < 0:
+                raise ValueError("cost_to_goal: %s must be a number of metres >= 0, got %r" % (what, v))
+        block, soft = (int(np.ceil(float(v) * self.words["scale"])) for v in (block_m, soft_m))
+        if block > self.clearance_radius:
+            raise ValueError("cost_to_goal: block_m = %r m are %d cells, beyond the %d of the last clearance()" % (block_m, block, self.clearance_radius))
+        g = np.asarray(goal_xy, np.float64)
+        goals = _sv.occupancy_cells_of(self.words, g[None] if g.ndim == 1 else g)
+        if self.device.type == "cuda":
+            if self._pen is None:
+                self._pen = torch.empty(self.logodds.shape, dtype=torch.uint8, device=self.device)
+                self._cost = torch.empty(self.logodds.shape, dtype=torch.int32, device=self.device)
+            cost_cells(self._d2, self.clearance_radius, block * block, soft, weight, out=self._pen)
+            res = occupancy_cost_to_goal(self._pen, goals, max_sweeps=max_sweeps, out=self._cost, workspace=self._cost_workspace)
+            self._cost_workspace = res.workspace
+            return res
+        pen = _sv.cost_cells(self._d2.numpy(), block * block, soft, weight, radius=self.clearance_radius)
+        self._pen, self._cost = torch.from_numpy(pen), torch.from_numpy(_sv.cost_to_goal(pen, goals))
+        return CostToGoalResult(cost=self._cost, converged=True, sweeps=None)
+
+    def routes(self, start_xy, capacity=4096):
+        """K routes down the last cost_to_goal() (stereo_vision.sv.cost_routes): start_xy float64 [K,2] ([2] for one) world points in
+        metres.  -> (engine.CostRoutesResult with cells int16 [K,capacity,2], length and status int32 [K] on the map's device; xy float64
+        numpy [K,capacity,2], the centres of the routes' cells as centres() gives them, NaN past a route's length).  Waits for the
+        cells, which xy is made from."""
+        import torch
+        from .engine import CostRoutesResult
+        if self._cost is None:
+            raise ValueError("routes: no cost-to-goal field yet - call cost_to_goal() first")
+        s = np.asarray(start_xy, np.float64)
+        starts = _sv.occupancy_cells_of(self.words, s[None] if s.ndim == 1 else s)
+        if self.device.type == "cuda":
+            res = cost_routes(self._cost, self._pen, starts, capacity)
+        else:
+            got = _sv.cost_routes(self._cost.numpy(), self._pen.numpy(), starts, capacity)
+            res = CostRoutesResult(**{k: torch.from_numpy(got[k]) for k in CostRoutesResult.__slots__})
+        cells = res.cells.cpu().numpy().astype(np.int64)
+        Xw, Yw = self.centres()
+        on = cells[..., 0] >= 0
+        xy = np.stack([np.where(on, Xw[np.where(on, cells[..., 0], 0)], np.nan), np.where(on, Yw[np.where(on, cells[..., 1], 0)], np.nan)], -1)
+        return res, xy
 
     def centres(self):
         """(Xw float64 [rows], Yw float64 [cols]) numpy: the world coordinates of the cells' centres."""

@@ -64,6 +64,13 @@ clearance field and the path check (sv_clearance_* of include/stereo_vision_hip.
 rig.OccupancyMap.clearance and .check_paths on the GPU): per map cell the squared distance in cells to the nearest occupied (or never seen)
 cell, capped at a radius, and per candidate path the first step at which a footprint of discs touches an obstacle, the least clearance met
 and the lookups that left the map.  Minima and counts of integers: bit for bit.  The reference has no counterpart.
+
+cost_cells, cost_to_goal (with cost_to_goal_relax, the whole-array relaxation), cost_routes and occupancy_cells_of are the definition of
+the cost-to-goal field and the routes traced through it (sv_cost_* of include/stereo_vision_hip.h (N); engine.cost_cells /
+engine.occupancy_cost_to_goal / engine.cost_routes / rig.OccupancyMap.cost_to_goal and .routes on the GPU): per map cell a penalty made
+from the clearance field, the length of the cheapest 8-connected path to the nearest goal that cuts no corner, and per start cell the
+route that follows the field downhill.  Shortest paths under strictly positive integer weights: unique, so bit for bit.  The reference
+has no counterpart.
 """
 import argparse
 import ctypes
@@ -1320,6 +1327,236 @@ def clearance_paths(d2, map, poses, centres, r2, radius):
             "n_outside": (~inside).reshape(K, -1).sum(1).astype(np.int32)}
 
 
+COST_INF = 0x7FFFFFFF      # cost of a cell no goal reaches, and of a blocked cell
+COST_BLOCKED = 255         # pen of a cell no path may enter
+COST_PEN_MAX = 254         # the largest penalty of a free cell; also the largest soft and weight
+COST_STEP_AXIAL, COST_STEP_DIAGONAL = 10, 14
+COST_CELLS_MAX = 8000000   # (cells - 1) * (254 + 14) stays below 2^31 - 1
+COST_GOALS_MAX = 1024
+COST_ROUTES_MAX = 65535
+COST_CAPACITY_MAX = 65535
+COST_MOVES = ((-1, 0), (0, -1), (0, 1), (1, 0), (-1, -1), (-1, 1), (1, -1), (1, 1))  # a route's ties go to the first of these
+ROUTE_GOAL, ROUTE_OUTSIDE, ROUTE_UNREACHABLE, ROUTE_CAPACITY, ROUTE_STUCK = 0, 1, 2, 3, 4  # cost_routes' status
+
+
+def _cost_int(v, lo, hi, what):
+    if isinstance(v, (bool, np.bool_)) or int(v) != v or not lo <= v <= hi:
+        raise ValueError("%s must be an integer in %d .. %d, got %r" % (what, lo, hi, v))
+    return int(v)
+
+
+def cost_isqrt(v):
+    """floor(sqrt(v)) of integers in 0 .. 65535, exactly: the compare ladder the kernel runs - bit 7 down to bit 0, a bit stays where
+    the square of the root so far does not exceed v."""
+    v = np.asarray(v).astype(np.int64)
+    r = np.zeros_like(v)
+    for b in (128, 64, 32, 16, 8, 4, 2, 1):
+        t = r | b
+        r = np.where(t * t <= v, t, r)
+    return r
+
+
+def cost_cells(d2, r2_block, soft=0, weight=0, radius=CLEARANCE_RADIUS_MAX):
+    """The definition of sv_cost_cells_device: pen uint8, the shape of d2 (uint16 [rows, cols], occupancy_clearance's with `radius`) -
+    COST_BLOCKED = 255 where d2 <= r2_block, elsewhere min(254, weight * max(0, soft - isqrt(d2))) with isqrt the floor of the root,
+    and 0 where d2 is CLEARANCE_FAR.  0 <= r2_block <= radius^2: above it a saturated cell would hide an obstacle, as for
+    clearance_paths' r2.  soft and weight in 0 .. 254."""
+    D = np.asarray(d2)
+    if D.dtype != np.uint16 or D.ndim != 2 or not (1 <= D.shape[0] <= 32768 and 1 <= D.shape[1] <= 32768):
+        raise ValueError("d2 must be uint16 [rows, cols] of 1 .. 32768 in either dimension, got %s %s" % (D.dtype, D.shape))
+    R = _cost_int(radius, 1, CLEARANCE_RADIUS_MAX, "radius")
+    r2_block = _cost_int(r2_block, 0, R * R, "r2_block (0 .. radius^2: beyond it a saturated cell would hide an obstacle)")
+    soft, weight = _cost_int(soft, 0, COST_PEN_MAX, "soft"), _cost_int(weight, 0, COST_PEN_MAX, "weight")
+    v = D.astype(np.int64)
+    pen = np.minimum(COST_PEN_MAX, weight * np.maximum(0, soft - cost_isqrt(v)))
+    pen = np.where(v == CLEARANCE_FAR, 0, pen)
+    return np.where(v <= r2_block, COST_BLOCKED, pen).astype(np.uint8)
+
+
+def _cost_pen(pen):
+    P = np.asarray(pen)
+    if P.dtype != np.uint8 or P.ndim != 2 or not (1 <= P.shape[0] <= 32768 and 1 <= P.shape[1] <= 32768):
+        raise ValueError("pen must be uint8 [rows, cols] of 1 .. 32768 in either dimension, got %s %s" % (P.dtype, P.shape))
+    if P.shape[0] * P.shape[1] > COST_CELLS_MAX:
+        raise ValueError("a field of %d x %d cells: at most %d, so that every cost stays below 2^31 - 1" % (P.shape + (COST_CELLS_MAX,)))
+    return P
+
+
+def _cost_cell_list(cells, lo, hi, what):
+    g = np.asarray(cells)
+    if g.dtype.kind not in "iu" or g.ndim != 2 or g.shape[1] != 2 or not lo <= g.shape[0] <= hi:
+        raise ValueError("%s must be integers [n, 2] = (row, col) with %d <= n <= %d, got %s %s" % (what, lo, hi, g.dtype, g.shape))
+    if g.size and (np.abs(g.astype(np.int64)) > 2 ** 31 - 1).any():
+        raise ValueError("%s must fit int32" % what)
+    return g.astype(np.int32)
+
+
+def _cost_seeds(P, goals):
+    """The goals that count: inside the map and on a free cell -> (rows int64 [n], cols int64 [n])."""
+    g = _cost_cell_list(goals, 1, COST_GOALS_MAX, "goals").astype(np.int64)
+    ok = (g[:, 0] >= 0) & (g[:, 0] < P.shape[0]) & (g[:, 1] >= 0) & (g[:, 1] < P.shape[1])
+    g = g[ok]
+    g = g[P[g[:, 0], g[:, 1]] != COST_BLOCKED]
+    return g[:, 0], g[:, 1]
+
+
+def _cost_admissible(P):
+    """bool [8, rows, cols]: may a path step from cell a = (r, c) to a + COST_MOVES[k]?  Both cells free and, for a diagonal move, the
+    two cells that share the corner as well; outside the map is blocked."""
+    rows, cols = P.shape
+    free = np.zeros((rows + 2, cols + 2), bool)
+    free[1:-1, 1:-1] = P != COST_BLOCKED
+    at = lambda dr, dc: free[1 + dr:1 + dr + rows, 1 + dc:1 + dc + cols]  # noqa: E731
+    return np.stack([at(0, 0) & at(dr, dc) & at(dr, 0) & at(0, dc) for dr, dc in COST_MOVES])
+
+
+def cost_to_goal(pen, goals):
+    """The definition of sv_cost_to_goal_device at its fixed point: int32 [rows, cols], per cell of a map with penalties pen (uint8,
+    cost_cells' or the caller's own; 255 = blocked) the length of the cheapest path to the nearest goal.
+
+      free    a cell inside the map with pen != 255.  Outside the map is blocked: here the map's edge is a wall.
+      move    between 8-neighbours a and b, admissible iff both are free and, for a diagonal move, the two cells that share the corner -
+              (a.r, b.c) and (b.r, a.c) - are free too: no corner is cut.  A step costs 10 along an axis and 14 diagonally.
+      goals   integers [G, 2] = (row, col), 1 <= G <= 1024; a goal outside the map or on a blocked cell is ignored.
+      cost    0 on every remaining goal; on any other free cell a, pen[a] + the minimum over the admissible b with a finite cost of
+              cost[b] + step; COST_INF where there is none, and on blocked cells.
+
+    The shortest-path length under strictly positive weights: unique, so every relaxation order that reaches a fixed point from the
+    all-COST_INF start gives these bits.  This form is Dijkstra's with a heap; cost_to_goal_relax is the second derivation."""
+    import heapq
+    P = _cost_pen(pen)
+    rows, cols = P.shape
+    ok = [m.tolist() for m in _cost_admissible(P).reshape(8, -1)]  # plain lists over the flat cell index: the loop below is Python's
+    pen_of = P.reshape(-1).tolist()
+    moves = [(dr * cols + dc, COST_STEP_AXIAL if k < 4 else COST_STEP_DIAGONAL, ok[k]) for k, (dr, dc) in enumerate(COST_MOVES)]
+    cost = [COST_INF] * (rows * cols)
+    gr, gc = _cost_seeds(P, goals)
+    heap = sorted(set((gr * cols + gc).tolist()))
+    for a in heap:
+        cost[a] = 0
+    heap = [(0, a) for a in heap]
+    while heap:
+        d, a = heapq.heappop(heap)
+        if d != cost[a]:
+            continue
+        for off, step, admissible in moves:  # admissibility is symmetric: b reaches a iff a reaches b
+            if admissible[a]:
+                b = a + off
+                nd = d + step + pen_of[b]
+                if nd < cost[b]:
+                    cost[b] = nd
+                    heapq.heappush(heap, (nd, b))
+    return np.array(cost, np.int64).astype(np.int32).reshape(rows, cols)
+
+
+def cost_relax_once(cost, pen, ok=None):
+    """One whole-array Jacobi relaxation of cost_to_goal's rule: int64 [rows, cols], min(cost[a], pen[a] + min over the admissible b with
+    a finite cost of cost[b] + step) per free cell a, every right-hand side read from `cost` as it was passed."""
+    P = np.asarray(pen)
+    ok = _cost_admissible(P) if ok is None else ok
+    rows, cols = P.shape
+    big = np.full((rows + 2, cols + 2), COST_INF, np.int64)
+    big[1:-1, 1:-1] = cost
+    best = np.full((rows, cols), COST_INF, np.int64)
+    for k, (dr, dc) in enumerate(COST_MOVES):
+        b = big[1 + dr:1 + dr + rows, 1 + dc:1 + dc + cols]
+        cand = b + (COST_STEP_AXIAL if k < 4 else COST_STEP_DIAGONAL) + P.astype(np.int64)
+        best = np.minimum(best, np.where(ok[k] & (b != COST_INF), cand, COST_INF))
+    return np.minimum(np.asarray(cost, np.int64), best)
+
+
+def cost_to_goal_relax(pen, goals):
+    """cost_to_goal by whole-array Jacobi relaxations from the all-COST_INF start until nothing changes: the second derivation of the
+    same field, for tests on small maps."""
+    P = _cost_pen(pen)
+    ok = _cost_admissible(P)
+    cost = np.full(P.shape, COST_INF, np.int64)
+    gr, gc = _cost_seeds(P, goals)
+    cost[gr, gc] = 0
+    while True:
+        new = cost_relax_once(cost, P, ok)
+        if np.array_equal(new, cost):
+            return cost.astype(np.int32)
+        cost = new
+
+
+def cost_routes(cost, pen, starts, capacity):
+    """The definition of sv_cost_routes_device: K routes walked down the field `cost` (int32 [rows, cols], cost_to_goal's) of the map with
+    penalties pen (uint8, the same shape), from starts (integers [K, 2] = (row, col), 0 <= K <= 65535), at most capacity (1 .. 65535)
+    cells each.  -> {"cells": int16 [K, capacity, 2], "length": int32 [K], "status": int32 [K]}.
+
+    From the start, repeat: write the current cell; stop with status 0 if its cost is 0; otherwise take, among the admissible neighbours
+    (cost_to_goal's moves) with a finite cost, the one with the least cost[b] + step - ties go to the first in the order COST_MOVES.
+
+      status 1   the start is outside the map; length 0.
+      status 2   the start is blocked or its cost is COST_INF; length 0.
+      status 4   the neighbour taken - if there is one - has no cost below the current cell's: the field was not converged.  The route
+                 stops at the current cell and is kept.
+      status 3   capacity cells were written before a goal was reached.
+
+    Cells past length are -1.  On a converged field every step lowers the cost, so the walk ends; status 4 and capacity bound it on any
+    other input."""
+    P = _cost_pen(pen)
+    C = np.asarray(cost)
+    if C.dtype != np.int32 or C.shape != P.shape:
+        raise ValueError("cost must be int32 %s, got %s %s" % (P.shape, C.dtype, C.shape))
+    S = _cost_cell_list(starts, 0, COST_ROUTES_MAX, "starts")
+    capacity = _cost_int(capacity, 1, COST_CAPACITY_MAX, "capacity")
+    rows, cols = P.shape
+    ok = _cost_admissible(P)
+    K = S.shape[0]
+    cells = np.full((K, capacity, 2), -1, np.int16)
+    length, status = np.zeros(K, np.int32), np.zeros(K, np.int32)
+    for k in range(K):
+        r, c = int(S[k, 0]), int(S[k, 1])
+        if not (0 <= r < rows and 0 <= c < cols):
+            status[k] = ROUTE_OUTSIDE
+            continue
+        if P[r, c] == COST_BLOCKED or C[r, c] == COST_INF:
+            status[k] = ROUTE_UNREACHABLE
+            continue
+        n = 0
+        while True:
+            cells[k, n] = (r, c)
+            n += 1
+            here = int(C[r, c])
+            if here == 0:
+                status[k] = ROUTE_GOAL
+                break
+            best = None
+            for m, (dr, dc) in enumerate(COST_MOVES):
+                if ok[m, r, c] and C[r + dr, c + dc] != COST_INF:
+                    v = int(C[r + dr, c + dc]) + (COST_STEP_AXIAL if m < 4 else COST_STEP_DIAGONAL)
+                    if best is None or v < best[0]:
+                        best = (v, r + dr, c + dc)
+            if best is None or int(C[best[1], best[2]]) >= here:
+                status[k] = ROUTE_STUCK
+                break
+            if n == capacity:
+                status[k] = ROUTE_CAPACITY
+                break
+            r, c = best[1], best[2]
+        length[k] = n
+    return {"cells": cells, "length": length, "status": status}
+
+
+def occupancy_cells_of(map, xy):
+    """int32 [..., 2] = (row, col): the map cell each world point xy (float64 [..., 2] = (Xw, Yw), metres) falls into, by clearance_cells'
+    rule - gx = floor(Xw ms), gy = floor(Yw ms), cell (top - 1 - gx, left - 1 - gy).  A point outside the map, or not finite, gives
+    (-1, -1): a goal there is ignored, a route from there has status 1."""
+    w = occupancy_map_words(map)
+    p = np.asarray(xy, np.float64)
+    if p.shape[-1:] != (2,):
+        raise ValueError("xy must be [..., 2] = (Xw, Yw), got %s" % (p.shape,))
+    ms = float(w["scale"])
+    with np.errstate(invalid="ignore", over="ignore"):
+        gx, gy = np.floor(p[..., 0] * ms), np.floor(p[..., 1] * ms)
+        inside = (gx >= w["top"] - w["rows"]) & (gx <= w["top"] - 1) & (gy >= w["left"] - w["cols"]) & (gy <= w["left"] - 1)
+    r = np.where(inside, w["top"] - 1 - np.where(inside, gx, 0.0), -1)
+    c = np.where(inside, w["left"] - 1 - np.where(inside, gy, 0.0), -1)
+    return np.stack([r, c], -1).astype(np.int32)
+
+
 class stereo_vision:
     def __init__(self, so_lib_path=DEFAULT_STEREO_VISION_SO_PATH, width=1242, height=375, defaultCalibFile=True, objectTracking=True,
                  graphics=False, display=False, scale=1, pc_extrapolation=1, YOLO_CFG="src/yolo/yolov4-tiny.cfg",
@@ -1471,8 +1708,23 @@ def main(argv=None):
                         help="with --occupancy-map: also write the final map's clearance field next to FILE as <FILE without "
                              ".png>.clearance.png, 8 bits, in FILE's orientation: per cell the distance in whole cells to the nearest "
                              "occupied cell (rounded down, at most 255), 255 beyond METRES")
+    parser.add_argument("--goal", type=str, default="", metavar="X,Y",
+                        help="with --occupancy-map, --poses and --clearance: after the drive, the cost-to-goal field of the final map "
+                             "towards the world point (X, Y) in metres - cells within --clearance's METRES of an obstacle are blocked - "
+                             "and the route from the last pose, written next to FILE as route.txt, one 'row col x y' line per cell; "
+                             "prints the route's status, its length and the cost at its start")
     args = parser.parse_args(argv)
     args.match_window = None
+    args.goal_xy = None
+    if args.goal:
+        if not (args.occupancy_map and args.poses and args.clearance):
+            parser.error("--goal needs --occupancy-map, --poses and --clearance")
+        try:
+            args.goal_xy = tuple(float(w) for w in args.goal.split(","))
+            if len(args.goal_xy) != 2 or not np.isfinite(args.goal_xy).all():
+                raise ValueError("not two finite numbers")
+        except ValueError as e:
+            parser.error("--goal: X,Y in metres (%s)" % e)
     if args.clearance:
         if not args.occupancy_map:
             parser.error("--clearance needs --occupancy-map")
@@ -1662,6 +1914,15 @@ def _run_batched(args, ldir, rdir, files):
             _write_png(args.occupancy_map, OCCUPANCY_PNG[world.state().cpu().numpy()])
             if args.clearance:
                 _write_png(os.path.splitext(args.occupancy_map)[0] + ".clearance.png", clearance_png(world.clearance(args.clearance).cpu().numpy()))
+            if args.goal_xy is not None:  # the field under the clearance just made, and the route from where the drive ended
+                field = world.cost_to_goal(args.goal_xy, args.clearance)
+                route, xy = world.routes(refined[-1][:2] if refined else args.pose_rows[-1, :2])
+                length, status = int(route.length[0]), int(route.status[0])
+                cells = route.cells[0, :length].cpu().numpy()
+                with open(os.path.join(os.path.dirname(os.path.abspath(args.occupancy_map)), "route.txt"), "w") as f:
+                    f.write("".join("%d %d %r %r\n" % (r, c, float(x), float(y)) for (r, c), (x, y) in zip(cells, xy[0, :length])))
+                at_start = int(field.cost[int(cells[0, 0]), int(cells[0, 1])]) if length else None
+                print("route: status %d, %d cells, cost at the start %s%s" % (status, length, at_start, "" if field.converged else " (field not converged)"))
         if args.match_window is not None:
             with open(os.path.splitext(args.occupancy_map)[0] + ".poses.txt", "w") as f:
                 f.write("".join("%r %r %r\n" % tuple(float(v) for v in at) for at in refined))
