@@ -263,27 +263,62 @@ __device__ __forceinline__ GradImg grad_image(const uint8_t *grad, const Dims &d
 // descriptor.cpp:48-50, 96-98: rows that carry descriptors (every second line from 4 at half resolution)
 __device__ __forceinline__ bool desc_row_ok(const Dims &d, int y) { return y < d.H - 3 && (d.sub ? (y >= 4 && !(y & 1)) : y >= 3); }
 
-// The four descriptors of image columns c .. c+3 (c a multiple of 4) of row y -> out[0..3].  16 aligned word loads from the
-// planes (consecutive lanes = consecutive quads: every load instruction is one contiguous 256-byte piece), 32 v_perm_b32.
-__device__ __forceinline__ void expand_quad(const GradImg &g, const Dims &d, int y, int c, uint4 *out) {
-    if (!desc_row_ok(d, y)) {  // wave-uniform in every caller (one row per workgroup / loop trip)
-        out[0] = out[1] = out[2] = out[3] = make_uint4(0, 0, 0, 0);
-        return;
-    }
-#define LDW(base, row, off) (*reinterpret_cast<const uint32_t *>((base) + (size_t)(row) * g.P + c + (off)))
+// The source rows of descriptor row y of one image, for a whole wavefront: y is wave-uniform in every caller (one row per
+// workgroup / loop trip), so the eight pointers live in scalar registers and a quad adds one 32-bit byte offset to them.
+// They point at byte GRAD_MARGIN - 4 of the padded rows (image column -4, the first word a quad at column 0 reads).
+struct DescRows {
+    const uint8_t *u0, *u1, *u2, *u3, *u4;  // du rows y-2 .. y+2
+    const uint8_t *v1, *v2, *v3;            // dv rows y-1 .. y+1
+    int W;
+    bool ok;                                // the row carries descriptors (desc_row_ok); otherwise its quads are zeros and nothing is read
+};
+
+__device__ __forceinline__ DescRows desc_rows(const GradImg &g, const Dims &d, int y) {
+    DescRows r;
+    r.W = d.W;
+    r.ok = desc_row_ok(d, y);
+    const uint8_t *du = g.DU + (size_t)((r.ok ? y : 2) - 2) * g.P - 4, *dv = du + grad_plane_bytes(d) + g.P;  // (g.DV = g.DU + one plane)
+    const size_t P = (size_t)g.P;
+    r.u0 = du, r.u1 = du + P, r.u2 = du + 2 * P, r.u3 = du + 3 * P, r.u4 = du + 4 * P;
+    r.v1 = dv, r.v2 = dv + P, r.v3 = dv + 2 * P;
+    return r;
+}
+
+// The four descriptors of image columns c .. c+3 (c a multiple of 4, 0 <= c < W + 4) of the row of r -> out[0..3], in two steps
+// so that a caller can have the loads of several quads in flight.  desc_load (rows with descriptors only): 16 aligned word loads
+// from the planes at scalar base + one per-lane offset (consecutive lanes = consecutive quads: every load instruction is one
+// contiguous 256-byte piece; the compiler fetches the three words of a row window as one 12-byte load).  desc_finish: 32
+// v_perm_b32.  Columns outside [3, W-3) hold zeros: only the first and the last two quads of an image row have such columns,
+// so one ballot per wavefront keeps the selects off everybody else's path.
+__device__ __forceinline__ DescWin desc_load(const DescRows &r, int c) {
+    uint32_t off = (uint32_t)c;  // zero-extended onto the scalar bases; the words at columns c-4, c, c+4 are words 0, 1, 2 from there
+    asm("" : "+v"(off));         // (opaque to the loop optimiser, which otherwise may keep eight 64-bit row addresses per lane as induction variables)
+#define LDW(row, word) (reinterpret_cast<const uint32_t *>((row) + off)[word])
     DescWin w;
-    w.r0 = LDW(g.DU, y - 2, 0), w.r4 = LDW(g.DU, y + 2, 0);
-    w.r1a = LDW(g.DU, y - 1, -4), w.r1b = LDW(g.DU, y - 1, 0), w.r1c = LDW(g.DU, y - 1, 4);
-    w.r2a = LDW(g.DU, y, -4), w.r2b = LDW(g.DU, y, 0), w.r2c = LDW(g.DU, y, 4);
-    w.r3a = LDW(g.DU, y + 1, -4), w.r3b = LDW(g.DU, y + 1, 0), w.r3c = LDW(g.DU, y + 1, 4);
-    w.v1 = LDW(g.DV, y - 1, 0), w.v3 = LDW(g.DV, y + 1, 0);
-    w.v2a = LDW(g.DV, y, -4), w.v2b = LDW(g.DV, y, 0), w.v2c = LDW(g.DV, y, 4);
+    w.r0 = LDW(r.u0, 1), w.r4 = LDW(r.u4, 1);
+    w.r1a = LDW(r.u1, 0), w.r1b = LDW(r.u1, 1), w.r1c = LDW(r.u1, 2);
+    w.r2a = LDW(r.u2, 0), w.r2b = LDW(r.u2, 1), w.r2c = LDW(r.u2, 2);
+    w.r3a = LDW(r.u3, 0), w.r3b = LDW(r.u3, 1), w.r3c = LDW(r.u3, 2);
+    w.v1 = LDW(r.v1, 1), w.v3 = LDW(r.v3, 1);
+    w.v2a = LDW(r.v2, 0), w.v2b = LDW(r.v2, 1), w.v2c = LDW(r.v2, 2);
 #undef LDW
-    const uint4 z = make_uint4(0, 0, 0, 0);
-    out[0] = (c + 0 >= 3 && c + 0 < d.W - 3) ? desc_assemble<0>(w) : z;
-    out[1] = (c + 1 >= 3 && c + 1 < d.W - 3) ? desc_assemble<1>(w) : z;
-    out[2] = (c + 2 >= 3 && c + 2 < d.W - 3) ? desc_assemble<2>(w) : z;
-    out[3] = (c + 3 >= 3 && c + 3 < d.W - 3) ? desc_assemble<3>(w) : z;
+    return w;
+}
+
+__device__ __forceinline__ void desc_finish(const DescRows &r, int c, const DescWin &w, uint4 *out) {
+    uint4 o0 = desc_assemble<0>(w), o1 = desc_assemble<1>(w), o2 = desc_assemble<2>(w), o3 = desc_assemble<3>(w);
+    if (__builtin_amdgcn_ballot_w64(c < 3 || c + 3 >= r.W - 3)) {  // some quad of this wavefront touches an image border
+        auto keep = [&](int x, const uint4 &o) { return x >= 3 && x < r.W - 3 ? make_uint4(o.x, o.y, o.z, o.w) : make_uint4(0, 0, 0, 0); };  // (by value)
+        o0 = keep(c + 0, o0), o1 = keep(c + 1, o1), o2 = keep(c + 2, o2), o3 = keep(c + 3, o3);
+    }
+    out[0] = o0, out[1] = o1, out[2] = o2, out[3] = o3;
+}
+
+__device__ __forceinline__ void expand_quad(const DescRows &r, int c, uint4 *out) {
+    if (!r.ok)
+        out[0] = out[1] = out[2] = out[3] = make_uint4(0, 0, 0, 0);
+    else
+        desc_finish(r, c, desc_load(r, c), out);
 }
 
 // sum |byte - 128| over the 16 bytes of the descriptor at (x, y), a valid descriptor position (elas.cpp:296-298): straight from
@@ -301,7 +336,7 @@ __global__ __launch_bounds__(256) void k_expand_all(const uint8_t *__restrict__ 
     if (4 * q >= d.W) return;
     const GradImg g = grad_image(grad, d, pair, img);
     uint4 o[4];
-    expand_quad(g, d, y, 4 * q, o);
+    expand_quad(desc_rows(g, d, y), 4 * q, o);
     uint4 *out = reinterpret_cast<uint4 *>(desc + ((size_t)(pair * 2 + img) * d.N + (size_t)y * d.W) * 16);
     for (int j = 0; j < 4; j++)
         if (4 * q + j < d.W) out[4 * q + j] = o[j];
@@ -466,12 +501,30 @@ __global__ __launch_bounds__(64 * SPLIT) void k_support(KParams k, const uint8_t
     uint2 *rec = reinterpret_cast<uint2 *>(sup_lds);  // [2 passes][SUP_SPLIT][SUP_POINTS]
     uint4 *sR0 = sup_lds + 2 * SUP_THREADS_T * sizeof(uint2) / sizeof(uint4), *sR1 = sR0 + nR, *sL0 = sR1 + nR, *sL1 = sL0 + nL;
     // rows v-2 and v+2 of both descriptor images, assembled from the gradient planes (rows without descriptors come out as zeros)
-    for (int i = threadIdx.x; i < 2 * (qR + qL); i += SUP_THREADS_T) {
-        const int row = i & 1, q = i >> 1;  // consecutive lanes alternate between the two rows of one quad column
-        if (q < qR)
-            expand_quad(g2, d, row ? v + 2 : v - 2, r_c0 + 4 * q, (row ? sR1 : sR0) + 4 * q);
-        else
-            expand_quad(g1, d, row ? v + 2 : v - 2, l_c0 + 4 * (q - qR), (row ? sL1 : sL0) + 4 * (q - qR));
+    // One staged row per wavefront (two wavefronts per row at eight): right image rows v-2 and v+2, left image rows v-2 and v+2.
+    // Image and source rows are wave-uniform; a lane has the loads of two of its quads in flight.  (The four rows one after the
+    // other, each strided over the whole workgroup, issues the same instructions but was measured 5 % slower per launch: four
+    // dependent rounds of loads in the first wavefronts instead of two.)
+    static_assert(SPLIT % 4 == 0, "a staged row per wavefront");
+    {
+        constexpr int STRIDE = 64 * (SPLIT / 4);
+        const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        const bool left = (wave >> 1) & 1, lower = wave & 1;
+        const DescRows rows = desc_rows(left ? g1 : g2, d, lower ? v + 2 : v - 2);
+        const int c0 = left ? l_c0 : r_c0, nq = left ? qL : qR;
+        uint4 *dst = left ? (lower ? sL1 : sL0) : (lower ? sR1 : sR0);
+        const int q0 = (wave >> 2) * 64 + (threadIdx.x & 63);
+        if (!rows.ok) {
+            for (int q = q0; q < nq; q += STRIDE) expand_quad(rows, c0 + 4 * q, dst + 4 * q);  // zeros
+        } else {
+            for (int q = q0; q < nq; q += 2 * STRIDE) {
+                const int q2 = q + STRIDE;
+                const bool two = q2 < nq;  // (a lane without a second quad loads its first one twice: no branch between the loads)
+                const DescWin w = desc_load(rows, c0 + 4 * q), w2 = desc_load(rows, c0 + 4 * (two ? q2 : q));
+                desc_finish(rows, c0 + 4 * q, w, dst + 4 * q);
+                if (two) desc_finish(rows, c0 + 4 * q2, w2, dst + 4 * q2);
+            }
+        }
     }
     __syncthreads();
     const SupRows L{sL0, sL1, l_c0}, R{sR0, sR1, r_c0};
@@ -1670,14 +1723,11 @@ __global__ __launch_bounds__(256) DENSE_WAVES_ATTR void k_dense(KParams k, const
     const int r0 = max(x0 - d.disp_max, 0) & ~3, r1 = x1 - 1;          // right image [r0, r1]
     const int qL = (l1 - l0 + 4) >> 2, qR = (r1 - r0 + 4) >> 2;        // quads per image
     uint4 *sL = dense_lds, *sR = dense_lds + dense_seg(d);
-    {
-        const GradImg gL = grad_image(grad, d, pair, 0), gR = grad_image(grad, d, pair, 1);
-        for (int q = threadIdx.x; q < qL + qR; q += 256) {
-            if (q < qL)
-                expand_quad(gL, d, yd, l0 + 4 * q, sL + 4 * q);
-            else
-                expand_quad(gR, d, yd, r0 + 4 * (q - qL), sR + 4 * (q - qL));
-        }
+    for (int img = 0; img < 2; img++) {  // the left image's quads, then the right image's: one set of scalar row pointers at a time
+        const DescRows rows = desc_rows(grad_image(grad, d, pair, img), d, yd);
+        const int c0 = img ? r0 : l0, nq = img ? qR : qL;
+        uint4 *dst = img ? sR : sL;
+        for (int q = threadIdx.x; q < nq; q += 256) expand_quad(rows, c0 + 4 * q, dst + 4 * q);
     }
     // per-pixel global operands of this thread's pixels (two per side), requested before the barrier
     int tt[2][DENSE_TW / 256];
