@@ -236,6 +236,19 @@ int sv_elas_process(sv_handle *h, const uint8_t *I1, const uint8_t *I2, float *D
  * frame that is due the sleeping helpers poll again (default: period / 16 within 0.3 - 2 ms).  Returns SV_OK or SV_ERR_ARG for an unknown key. */
 int sv_debug_set(sv_handle *h, const char *key, int value);
 
+/* Test hook: hands the second half of the engine (L/R check, speckle removal, gap interpolation, adaptive mean, median) maps of the
+ * caller's choice.  stage "wta": in place of dense_match's maps, in front of the L/R check; "lr": in place of the L/R check's maps, in
+ * front of speckle removal.  left / right: float [Hm][Wm] each, the layout sv_debug_get reports for wta1/2 and lr1/2; they are copied
+ * into the handle and overwrite the device maps of every later pair that the debug snapshots describe and that has three or more
+ * support points, before that stage's snapshot is taken (sv_debug_get returns what was injected).  left == right == NULL clears them.
+ * Only on a keep_debug handle (waits for submitted work first); a handle without keep_debug executes nothing of this.
+ * Value contract - only what the engine itself can produce at that stage, anything else is refused here on the host, so that a painted
+ * map never drives a kernel outside the range it was written for:
+ *   "lr"  : -10.0f, or an integer-valued float in 0 .. disp_max (the labelling relies on every invalid pixel being exactly -10);
+ *   "wta" : an integer in 0 .. disp_max, or one of dense_match's two invalid values: -10 (no triangle / low texture), -1 (no match).
+ * Returns SV_OK, or SV_ERR_ARG with a text for sv_last_error (no keep_debug, unknown stage, one map missing, a value outside the contract). */
+int sv_debug_inject(sv_handle *h, const char *stage, const float *left, const float *right);
+
 /* Per-stage intermediates of the last pair processed (cfg.keep_debug != 0).  Names and layouts follow
  * oracle/elas_oracle.h: desc1 desc2 dcan_raw support tri1 tri2 planes1 planes2 grid1 grid2 wta1 wta2 lr1 lr2
  * speckle1 gap1 amean1 final1 ...  Returns the byte count, -1 unknown name, -2 cap too small. */

@@ -248,6 +248,8 @@ struct sv_handle {
     std::atomic<int64_t> host_filter_ns{0}, host_delaunay_ns{0}, host_tasks{0};
     // debug
     std::map<std::string, std::vector<uint8_t>> dbg;
+    int inj_stage = 0;                         // sv_debug_inject: 0 none, 1 "wta", 2 "lr"
+    std::vector<float> inj_maps[2];            // ... the staged left / right maps, [Hm][Wm] each
     unsigned long long *d_counters = nullptr;  // work counters of the matching kernels (sv_debug_counters)
     uint8_t *dbg_desc = nullptr;               // keep_debug: descriptor images [cap][2][N][16] for the stage snapshot
     bool lat_trace = false;                    // SV_LAT_TRACE=1: wall-clock split of the latency path, printed by sv_destroy
@@ -551,6 +553,27 @@ void dbg_maps_nproc(sv_handle *h, hipStream_t st, const char *stage, const float
         const float *base = (side < h->nproc) ? cur : disp;
         dbg_from_device(h, st, name, base + ((size_t)j * 2 + side) * N, N * sizeof(float));
     }
+}
+
+// sv_debug_inject: the staged maps over the slot's maps of pair j, in stream order (the stream is drained first, the copy is synchronous)
+void dbg_inject_wta(sv_handle *h, hipStream_t st, int16_t *base, int j) {
+    const size_t N = h->kp.d.Nm;
+    std::vector<int16_t> raw(N);
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int side = 0; side < 2; side++) {
+        const float *f = h->inj_maps[side].data();
+        for (size_t i = 0; i < N; i++) raw[i] = (int16_t)f[i];
+        HIP_TRY(hipMemcpy(base + ((size_t)j * 2 + side) * N, raw.data(), N * sizeof(int16_t), hipMemcpyHostToDevice));
+    }
+}
+
+// ... `right_out`: where the L/R kernel wrote the final right map of the chunk with postprocess_only_left (or nullptr)
+void dbg_inject_lr(sv_handle *h, hipStream_t st, float *base, float *right_out, int j) {
+    const size_t N = h->kp.d.Nm;
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int side = 0; side < 2; side++)
+        HIP_TRY(hipMemcpy(base + ((size_t)j * 2 + side) * N, h->inj_maps[side].data(), N * sizeof(float), hipMemcpyHostToDevice));
+    if (right_out) HIP_TRY(hipMemcpy(right_out + (size_t)j * N, h->inj_maps[1].data(), N * sizeof(float), hipMemcpyDefault));
 }
 
 // compacted candidate lists in the reference's layout (elas.cpp:631-648) from the device bit masks
@@ -1591,10 +1614,12 @@ void issue_phase2(sv_handle *h, Slot *s, hipStream_t st) {
         u2 = job.d2 ? s->d_out + (size_t)s->dev.cap * d.Nm : nullptr;
     }
     const bool only_left = h->nproc == 1;
+    const bool active = dbg && blob[(size_t)(n - 1) * META_WORDS] >= 3;
+    if (active && h->inj_stage == 1) dbg_inject_wta(h, st, s->dev.wta, n - 1);  // tests (sv_debug_inject): painted maps in place of k_dense's
     // with postprocess_only_left the checked right map is final: it goes straight to the caller (or nowhere)
     launch_lr(km, s->dev, n, st, only_left ? u2 : nullptr, !only_left || dbg);
+    if (active && h->inj_stage == 2) dbg_inject_lr(h, st, s->dev.disp, only_left ? u2 : nullptr, n - 1);  // ... in place of the L/R check's
     if (job.host && only_left && u2) HIP_TRY(hipEventRecord(s->ev_lr, st));  // ... and its download may overlap the rest of phase 2
-    const bool active = dbg && blob[(size_t)(n - 1) * META_WORDS] >= 3;
     if (active) {
         const int j = n - 1;
         const int32_t *meta = blob + (size_t)j * META_WORDS;
@@ -2858,6 +2883,47 @@ int sv_debug_set(sv_handle *h, const char *key, int value) {
         h->error = "sv_debug_set: unknown key";
         return SV_ERR_ARG;
     }
+    return SV_OK;
+}
+
+int sv_debug_inject(sv_handle *h, const char *stage, const float *left, const float *right) {
+    if (!h) {
+        g_create_error = "sv_debug_inject: null handle";
+        return SV_ERR_ARG;
+    }
+    (void)wait_jobs(h);  // the finisher reads the staged maps while a pair is in flight
+    auto refuse = [h](const std::string &why) {
+        h->error = "sv_debug_inject: " + why;
+        return SV_ERR_ARG;
+    };
+    if (!h->cfg.keep_debug) return refuse("the handle was not created with keep_debug");
+    if (!left && !right) {
+        h->inj_stage = 0;
+        h->inj_maps[0].clear();
+        h->inj_maps[1].clear();
+        return SV_OK;
+    }
+    const std::string name(stage ? stage : "");
+    const int which = name == "wta" ? 1 : (name == "lr" ? 2 : 0);
+    if (!which) return refuse("unknown stage '" + name + "' (\"wta\" or \"lr\")");
+    if (!left || !right) return refuse("both maps or neither");
+    // only values the engine itself produces at that stage: the kernels behind it were written for nothing else
+    const size_t N = h->kp.d.Nm;
+    const float dmax = (float)h->kp.d.disp_max;
+    const float *maps[2] = {left, right};
+    for (int side = 0; side < 2; side++)
+        for (size_t i = 0; i < N; i++) {
+            const float x = maps[side][i];
+            const bool disparity = x >= 0.0f && x <= dmax && x == (float)(int)x;
+            if (disparity || x == -10.0f || (which == 1 && x == -1.0f)) continue;  // (NaN fails every comparison)
+            char b[160];
+            snprintf(b, sizeof(b), "%s map, pixel %zu: %g is neither an integer in 0..%d nor %s", side ? "right" : "left", i, (double)x, (int)dmax,
+                     which == 1 ? "-1 / -10 (what dense_match writes for no match / no triangle)" : "-10");
+            return refuse(b);
+        }
+    h->inj_maps[0].assign(left, left + N);
+    h->inj_maps[1].assign(right, right + N);
+    h->inj_stage = which;
     return SV_OK;
 }
 

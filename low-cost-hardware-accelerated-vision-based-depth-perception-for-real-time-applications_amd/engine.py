@@ -201,6 +201,22 @@ class StereoEngine:
         L.sv_debug_set.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int]
         self._check(L.sv_debug_set(self._h, key.encode(), int(value)))
 
+    def debug_inject(self, stage, left=None, right=None):
+        """Test hook (sv_debug_inject): float32 [map_height, map_width] maps that replace dense_match's (stage "wta") or the L/R check's
+        (stage "lr") for every later pair of this keep_debug handle; left = right = None clears them.  The library refuses values the
+        engine itself cannot produce at that stage (include/stereo_vision_hip.h)."""
+        L = lib()
+        L.sv_debug_inject.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.sv_debug_inject.restype = ctypes.c_int
+        if left is None and right is None:
+            return self._check(L.sv_debug_inject(self._h, stage.encode(), None, None))
+        maps = []
+        for m, name in ((left, "left"), (right, "right")):
+            if not (isinstance(m, np.ndarray) and m.dtype == np.float32 and m.shape == (self.map_height, self.map_width)):
+                raise ValueError("%s must be a float32 array [%d,%d]" % (name, self.map_height, self.map_width))
+            maps.append(np.ascontiguousarray(m))
+        self._check(L.sv_debug_inject(self._h, stage.encode(), maps[0].ctypes.data, maps[1].ctypes.data))
+
     def _check(self, rc):
         if rc != 0:
             raise StereoError("libstereo_vision_hip error %d: %s" % (rc, lib().sv_last_error(self._h).decode()))

@@ -45,6 +45,7 @@ void orc_lr_check(const elas_params *p, float *D1, float *D2, int W, int H);
 void orc_speckle(const elas_params *p, float *D, int W, int H);
 void orc_gap(const elas_params *p, float *D, int W, int H);
 void orc_adaptive_mean(float *D, int W, int H);
+void orc_adaptive_mean_sub(float *D, int W, int H); /* the half-resolution branch, elas.cpp:1332-1397 */
 void orc_median(float *D, int W, int H);
 
 #ifdef __cplusplus

@@ -189,6 +189,46 @@ class Oracle(_StageLib):
         if not os.path.exists(path):
             build()
         super().__init__(path)
+        fp, pp = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ElasParams)
+        for name, args in (("orc_lr_check", [pp, fp, fp]), ("orc_speckle", [pp, fp]), ("orc_gap", [pp, fp]),
+                           ("orc_adaptive_mean", [fp]), ("orc_adaptive_mean_sub", [fp]), ("orc_median", [fp])):
+            f = getattr(self.lib, name)
+            f.restype = None
+            f.argtypes = args + [ctypes.c_int, ctypes.c_int]
+
+    # ---- the post-processing stages on maps of the caller's choice; each returns new float32 [H, W] maps, the arguments stay as they are
+    @staticmethod
+    def _map(D):
+        D = np.array(D, dtype=np.float32, order="C")  # (a copy: the stages work in place)
+        assert D.ndim == 2
+        return D, D.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+
+    def lr_check(self, params, D1, D2):
+        (D1, p1), (D2, p2) = self._map(D1), self._map(D2)
+        assert D1.shape == D2.shape
+        self.lib.orc_lr_check(ctypes.byref(params), p1, p2, D1.shape[1], D1.shape[0])
+        return D1, D2
+
+    def speckle(self, params, D):
+        D, p = self._map(D)
+        self.lib.orc_speckle(ctypes.byref(params), p, D.shape[1], D.shape[0])
+        return D
+
+    def gap(self, params, D):
+        D, p = self._map(D)
+        self.lib.orc_gap(ctypes.byref(params), p, D.shape[1], D.shape[0])
+        return D
+
+    def adaptive_mean(self, D, sub=False):
+        """sub: the half-resolution branch (elas.cpp:1332-1397), what the pipeline takes with params.subsampling."""
+        D, p = self._map(D)
+        (self.lib.orc_adaptive_mean_sub if sub else self.lib.orc_adaptive_mean)(p, D.shape[1], D.shape[0])
+        return D
+
+    def median(self, D):
+        D, p = self._map(D)
+        self.lib.orc_median(p, D.shape[1], D.shape[0])
+        return D
 
 
 def build(ref=True):
