@@ -1049,6 +1049,67 @@ int sv_cost_routes_device(const int32_t *cost, const uint8_t *pen, int rows, int
  * the calls.  cost and info do not depend on it.  Returns SV_OK, or SV_ERR_ARG for another variant. */
 int sv_debug_cost_to_goal(int variant, unsigned long long *counters_device);
 
+/* ---- (O) frontiers of the world map: (K)'s log-odds + (N)'s penalties -> frontier cells -> connected clusters, one goal each ---- */
+
+/* (N) takes its goals from the caller; this group proposes them.  A frontier cell is a free cell that touches space no frame ever decided;
+ * the frontier cells are grouped into 8-connected clusters, and every cluster offers one of its own cells as a goal for (N).  Integers
+ * throughout: a label is a function of the partition alone and every statistic is a sum, a minimum or a maximum, so the results are bitwise
+ * reproducible whatever order the unions and the atomics take.  stereo_vision.sv.frontier_cells / frontier_clusters / frontier_goals
+ * restate them in numpy.
+ *
+ *   state      of a cell, as stereo_vision.sv.occupancy_map_state: 2 where last_seen >= 0 and logodds >= occupied, else 1 where
+ *              last_seen >= 0 and logodds <= free, else 0 (unknown).
+ *   frontier   mask = 1 iff the cell's state is 1, pen is NULL or pen != 255 there (a cell the vehicle cannot stand on is no goal), and at
+ *              least one of its 4-neighbours (-1,0), (0,-1), (0,1), (1,0) lies inside the map and has state 0; else 0.  Cells outside the
+ *              map are not unknown: the map's edge makes no frontier, as it is a wall in (N).
+ *   member     a cell whose mask byte is non-zero; a caller may pass any bytes.
+ *   label      -1 on non-members; on a member the least linear index r * cols + c of its 8-connected component.  rows * cols <= 8 000 000
+ *              keeps an index below 2^23.
+ *   clusters   the components of at least min_cells members in ascending order of label - the order in which a scan of the map meets
+ *              them; row k of the k-th is (label, size, rep_r, rep_c, r0, c0, r1, c1) with the inclusive bounding box r0..c1 and the
+ *              representative (rep_r, rep_c): the member that minimises (r - cr)^2 + (c - cc)^2 to the integer centroid cell cr = (2 sum_r
+ *              + size) / (2 size), cc likewise - rounded half up, inside the box -, ties to the least linear index.  Rows from min(kept,
+ *              capacity) on are all -1.  sums holds (sum_r, sum_c) of each written row's members, 0 in the rows behind them.
+ *   info       [0] the kept components - it may exceed capacity: rows were dropped then -, [1] all components, [2] the members, [3] the
+ *              rows written.
+ *   launches   tiles of 64 x 64 cells are labelled by a union-find in LDS; a second launch unites the pieces over the tiles' seams in
+ *              global memory, always hooking the larger root under the smaller by an atomic minimum - the only launch in which workgroups
+ *              share words, and there every access is a relaxed device-wide atomic; nothing waits for another thread, and every loop ends
+ *              by the data alone.  All other steps exchange data across launch boundaries only. */
+
+/* Enqueued on `stream` (a hipStream_t, NULL = the default stream) as one kernel and not waited for.
+ *   logodds      : int16 [rows][cols] device; last_seen : int32 [rows][cols] device - (K)'s pair
+ *   pen          : uint8 [rows][cols] device - (N)'s penalties or the caller's own - or NULL
+ *   occupied, free_ : the thresholds of the state
+ *   mask         : uint8 [rows][cols] device, written in full
+ * Returns SV_OK, SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued, mask untouched, the text in sv_last_error(NULL) - for: a NULL logodds,
+ * last_seen or mask; logodds not 2-byte or last_seen not 4-byte aligned; rows or cols outside 1..32768; mask overlapping an input.  These
+ * checks run before any HIP call. */
+int sv_frontier_cells_device(const int16_t *logodds, const int32_t *last_seen, const uint8_t *pen, int rows, int cols, int occupied, int free_, uint8_t *mask,
+                             void *stream);
+/* Host only: the bytes of the workspace sv_frontier_clusters_device needs - two int32 per cell, a 64-bit key per row and four words per
+ * 1024 cells, each block rounded up to 16.  SV_ERR_ARG (bytes untouched) for a NULL bytes, rows or cols outside 1..32768, rows * cols above
+ * 8 000 000 or capacity outside 1..65535. */
+int sv_frontier_clusters_workspace(int rows, int cols, int capacity, size_t *bytes);
+/* Enqueued on `stream` as four memsets - the -1 of clusters, the 0 of sums and two blocks of the workspace - and nine kernels, and not
+ * waited for: nothing is allocated and no host synchronisation is made.
+ *   mask         : uint8 [rows][cols] device
+ *   min_cells    : 1..8 000 000; capacity : 1..65535 rows
+ *   label        : int32 [rows][cols] device; clusters : int32 [capacity][8] device; sums : int64 [capacity][2] device; info : int32 [4]
+ *                  device - all written in full
+ *   workspace    : device, 16-byte aligned, workspace_bytes >= what sv_frontier_clusters_workspace gives
+ * Returns SV_OK, SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued, the outputs untouched, the text in sv_last_error(NULL) - for: a NULL pointer;
+ * label, clusters or info not 4-byte, sums not 8-byte, the workspace not 16-byte aligned; rows or cols outside 1..32768 or rows * cols above
+ * 8 000 000; min_cells outside 1..8 000 000; capacity outside 1..65535; too small a workspace; label, clusters, sums, info or the workspace
+ * overlapping one another or mask.  These checks run before any HIP call. */
+int sv_frontier_clusters_device(const uint8_t *mask, int rows, int cols, int min_cells, int capacity, int32_t *label, int32_t *clusters, int64_t *sums, int32_t *info,
+                                void *workspace, size_t workspace_bytes, void *stream);
+/* Test hook for sv_frontier_clusters_device, process-wide: variant 0 (the default) labels the tiles in LDS and unites them over their seams,
+ * 1 skips the tile phase - every member starts as its own parent and unites with its four backward neighbours in global memory.
+ * counters_device != NULL: two device uint64 that receive the atomic minima issued on global memory and the tiles that held a member, added
+ * up over the calls.  The results and info do not depend on it.  Returns SV_OK, or SV_ERR_ARG for another variant. */
+int sv_debug_frontier(int variant, unsigned long long *counters_device);
+
 /* ---- (A) the reference's exported symbols ------------------------------------------------------------- */
 
 typedef struct {

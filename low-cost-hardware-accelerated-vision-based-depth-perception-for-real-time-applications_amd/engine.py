@@ -524,7 +524,7 @@ class SvOccupancyMapSpec(ctypes.Structure):
 
 
 def _signatures():
-    """The table below: per stage group of the C API, (D) to (N), its functions and per function (restype, argtypes), parameter by
+    """The table below: per stage group of the C API, (D) to (O), its functions and per function (restype, argtypes), parameter by
     parameter as include/stereo_vision_hip.h declares them - tests/test_stage_signatures.py holds the two against each other."""
     P = ctypes.POINTER
     vp, ci, sz, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_int64
@@ -588,11 +588,17 @@ def _signatures():
             "sv_cost_routes_device": (ci, [vp, vp, ci, ci, vp, ci, ci, vp, vp, vp, vp]),
             "sv_debug_cost_to_goal": (ci, [ci, vp]),
         },
+        "frontier": {  # (O)
+            "sv_frontier_cells_device": (ci, [vp, vp, vp, ci, ci, ci, ci, vp, vp]),
+            "sv_frontier_clusters_workspace": (ci, [ci, ci, ci, P(sz)]),
+            "sv_frontier_clusters_device": (ci, [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, sz, vp]),
+            "sv_debug_frontier": (ci, [ci, vp]),
+        },
     }
 
 
 STAGE_SIGNATURES = _signatures()  # plain data: made without loading the library
-_GROUP_NEEDS = {"voxel": ("cloud",), "occupancy_map": ("occupancy",), "map_match": ("occupancy_map",), "clearance": ("occupancy_map",), "cost": ("clearance",)}
+_GROUP_NEEDS = {"voxel": ("cloud",), "occupancy_map": ("occupancy",), "map_match": ("occupancy_map",), "clearance": ("occupancy_map",), "cost": ("clearance",), "frontier": ("cost",)}
 _bound_groups = set()
 
 
@@ -1620,6 +1626,93 @@ def debug_cost_to_goal(variant=0, counters=None):
     """sv_debug_cost_to_goal: the tiles a sweep of occupancy_cost_to_goal runs (0: those the dirty bytes name; 1: every tile in every
     sweep) and a CUDA int64 [2] tensor (or None) that receives the tiles run and their inner iterations.  Process-wide; a test hook."""
     return int(cost_lib().sv_debug_cost_to_goal(int(variant), None if counters is None else counters.data_ptr()))
+
+
+def frontier_lib():
+    """The library with the signatures of group (O) declared."""
+    return _bind("frontier")
+
+
+def frontier_cells(logodds, last_seen, occupied, free, pen=None, out=None):
+    """The frontier cells of a world map - the definition of stereo_vision.sv.frontier_cells on the GPU, bit for bit, in one kernel:
+    logodds a contiguous CUDA int16 tensor [rows,cols], last_seen an int32 tensor and pen a uint8 tensor (cost_cells', or None) of the
+    same shape on the same device, occupied and free the thresholds of the state; out: a contiguous uint8 tensor [rows,cols] to write
+    into.  -> the uint8 tensor: 1 on a free cell that the vehicle can stand on and that touches a cell nobody has decided yet, else 0;
+    enqueued on torch's current stream, not waited for."""
+    import torch
+    rows, cols = _map_tensor(logodds, torch.int16, "logodds")
+    _map_tensor(last_seen, torch.int32, "last_seen", like=logodds)
+    if pen is not None:
+        _map_tensor(pen, torch.uint8, "pen", like=logodds)
+    if out is None:
+        out = torch.empty((rows, cols), dtype=torch.uint8, device=logodds.device)
+    else:
+        _map_tensor(out, torch.uint8, "out", like=logodds)
+    for v, what in ((occupied, "occupied"), (free, "free")):
+        if isinstance(v, bool) or int(v) != v or abs(v) > 2 ** 31 - 1:
+            raise ValueError("%s must be an integer, got %r" % (what, v))
+    with torch.cuda.device(logodds.device):
+        rc = frontier_lib().sv_frontier_cells_device(logodds.data_ptr(), last_seen.data_ptr(), _ptr(pen), rows, cols, int(occupied), int(free), out.data_ptr(),
+                                                     torch.cuda.current_stream(logodds.device).cuda_stream)
+    _check(rc, "sv_frontier_cells_device")
+    return out
+
+
+class FrontierResult(_Result):
+    """What frontier_clusters returns, tensors on the mask's device: label int32 [rows,cols] (-1 on non-members, else the least linear
+    index of the cell's 8-connected component), clusters int32 [capacity,8] = (label, size, rep_r, rep_c, r0, c0, r1, c1) per kept
+    component in ascending order of label (-1 past the written rows), sums int64 [capacity,2] = (sum_r, sum_c), info int32 [4] = (kept
+    components, all components, members, rows written) and workspace (the uint8 tensor the call worked in)."""
+    __slots__ = ("label", "clusters", "sums", "info", "workspace")
+
+
+def frontier_clusters(mask, min_cells=1, capacity=1024, out=None, workspace=None):
+    """The connected clusters of a byte mask - the definition of stereo_vision.sv.frontier_clusters on the GPU, bit for bit: mask a
+    contiguous CUDA uint8 tensor [rows,cols] (frontier_cells', or the caller's own: a member is a non-zero byte; rows x cols <=
+    8 000 000), min_cells in 1 .. 8 000 000, capacity in 1 .. 65535 rows.  out: a FrontierResult (or a tuple (label, clusters, sums,
+    info)) of contiguous tensors of the right shapes to write into; workspace: a uint8 tensor of at least
+    sv_frontier_clusters_workspace's bytes to reuse.  -> FrontierResult; enqueued on torch's current stream - four memsets and nine
+    kernels - and not waited for."""
+    import torch
+    rows, cols = _map_tensor(mask, torch.uint8, "mask")
+    dev = mask.device
+    if rows * cols > 8000000:
+        raise ValueError("a mask of %d x %d cells: at most 8 000 000, so that a linear index stays below 2^23" % (rows, cols))
+    for v, lo, hi, what in ((min_cells, 1, 8000000, "min_cells"), (capacity, 1, 65535, "capacity")):
+        if isinstance(v, bool) or int(v) != v or not lo <= v <= hi:
+            raise ValueError("%s must be an integer in %d .. %d, got %r" % (what, lo, hi, v))
+    capacity = int(capacity)
+    shapes = (("label", (rows, cols), torch.int32), ("clusters", (capacity, 8), torch.int32), ("sums", (capacity, 2), torch.int64), ("info", (4,), torch.int32))
+    if out is None:
+        given = [torch.empty(shape, dtype=dtype, device=dev) for _, shape, dtype in shapes]
+    else:
+        given = [getattr(out, name) for name, _, _ in shapes] if isinstance(out, FrontierResult) else list(out)
+        if len(given) != 4:
+            raise ValueError("out must be a FrontierResult or (label, clusters, sums, info)")
+        for t, (name, shape, dtype) in zip(given, shapes):
+            if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous()):
+                raise ValueError("out: %s must be a contiguous %s tensor %s on the device of mask" % (name, str(dtype).replace("torch.", ""), list(shape)))
+    L = frontier_lib()
+    nbytes = ctypes.c_size_t()
+    _check(L.sv_frontier_clusters_workspace(rows, cols, capacity, ctypes.byref(nbytes)), "sv_frontier_clusters_workspace")
+    if workspace is None:
+        workspace = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    elif not (isinstance(workspace, torch.Tensor) and workspace.device == dev and workspace.dtype == torch.uint8 and workspace.is_contiguous()
+              and workspace.numel() >= nbytes.value):
+        raise ValueError("workspace must be a contiguous uint8 tensor of at least %d bytes on the device of mask" % nbytes.value)
+    label, clusters, sums, info = given
+    with torch.cuda.device(dev):
+        rc = L.sv_frontier_clusters_device(mask.data_ptr(), rows, cols, int(min_cells), capacity, label.data_ptr(), clusters.data_ptr(), sums.data_ptr(),
+                                           info.data_ptr(), workspace.data_ptr(), workspace.numel(), torch.cuda.current_stream(dev).cuda_stream)
+    _check(rc, "sv_frontier_clusters_device")
+    return FrontierResult(label=label, clusters=clusters, sums=sums, info=info, workspace=workspace)
+
+
+def debug_frontier(variant=0, counters=None):
+    """sv_debug_frontier: how frontier_clusters labels (0: tiles in LDS, then their seams; 1: no tile phase, every link through global
+    memory) and a CUDA int64 [2] tensor (or None) that receives the atomic minima issued on global memory and the tiles that held a
+    member.  Process-wide; a test hook."""
+    return int(frontier_lib().sv_debug_frontier(int(variant), None if counters is None else counters.data_ptr()))
 
 
 def host_support_filter(params, dcan, width, height, threads=0, lattice=False):

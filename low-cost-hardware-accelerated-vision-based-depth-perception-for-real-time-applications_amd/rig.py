@@ -36,7 +36,7 @@ import ctypes
 import numpy as np
 
 from .engine import (SvParams, StereoEngine, StereoError, box_positions_from_disparity, box_spec, cloud_spec, compact_cloud_from_disparity,
-                     ground_from_disparity, ground_spec, lib, occupancy_from_disparity, occupancy_fuse, occupancy_match, occupancy_clearance, clearance_paths, cost_cells, cost_routes, occupancy_cost_to_goal, occupancy_spec, pinned_array, reproject, split_clouds, stixel_spec, stixels_from_disparity,
+                     ground_from_disparity, ground_spec, lib, occupancy_from_disparity, occupancy_fuse, occupancy_match, occupancy_clearance, clearance_paths, cost_cells, cost_routes, frontier_cells, frontier_clusters, occupancy_cost_to_goal, occupancy_spec, pinned_array, reproject, split_clouds, stixel_spec, stixels_from_disparity,
                      top_view_from_disparity, top_view_spec, split_voxel_clouds, voxel_cloud_from_disparity, voxel_spec)
 from .stereo_vision.sv import CAMERA_TO_VEHICLE, DEFAULT_CALIBRATION  # noqa: F401 (CAMERA_TO_VEHICLE: re-exported for top_view)
 from .stereo_vision.sv import free_space_points, ground_pose
@@ -426,7 +426,9 @@ class OccupancyMap:
     100).  words is the map's sv_occupancy_map_spec as a dict (top and left move with recenter), seq the number of frames fused so far:
     the sequence number the next frame carries into last_seen.  clearance() and check_paths() are group (M): the squared distance to the nearest
     obstacle per cell, and candidate paths checked against it; clearance_radius is the radius in cells of the last clearance().
-    cost_to_goal() and routes() are group (N): the length of the cheapest path from every cell to a goal, and the cells to drive."""
+    cost_to_goal() and routes() are group (N): the length of the cheapest path from every cell to a goal, and the cells to drive.
+    frontiers() and frontier_goals() are group (O): the free cells that touch undecided space, their clusters and one goal per cluster -
+    the loop clearance -> cost_to_goal(any goal) or cost_cells -> frontiers -> cost_to_goal(frontier_goals) -> routes(vehicle)."""
 
     def __init__(self, x_range, y_range, scale, device="cuda", **log_odds_words):
         import torch
@@ -440,6 +442,7 @@ class OccupancyMap:
         self.seq = 0
         self._d2, self._clearance_workspace, self.clearance_radius = None, None, None  # clearance()'s, made on its first call
         self._pen, self._cost, self._cost_workspace = None, None, None  # cost_to_goal()'s, made on its first call
+        self._frontier_mask, self._frontiers = None, None  # frontiers()'s, made on its first call
 
     def reset(self):
         """A fresh map at the place it has scrolled to: logodds 0, last_seen -1, seq 0."""
@@ -625,6 +628,47 @@ class OccupancyMap:
         on = cells[..., 0] >= 0
         xy = np.stack([np.where(on, Xw[np.where(on, cells[..., 0], 0)], np.nan), np.where(on, Yw[np.where(on, cells[..., 1], 0)], np.nan)], -1)
         return res, xy
+
+    def frontiers(self, min_cells=8, capacity=1024, occupied=None, free=None, reachable=True):
+        """The frontier clusters of the map as it stands (stereo_vision.sv.frontier_cells and frontier_clusters): the free cells that
+        touch a cell nobody has decided yet, grouped into 8-connected clusters of at least min_cells cells, at most capacity of them in
+        the order a scan of the map meets them.  occupied and free default as state()'s.  reachable: a cell that the pen of the last
+        cost_to_goal() blocks is no frontier cell (ValueError if there is no cost_to_goal() yet); False: no pen.  -> engine.FrontierResult
+        with label int32 [rows,cols], clusters int32 [capacity,8], sums int64 [capacity,2] and info int32 [4] on the map's device.  The
+        tensors and the workspace stay with the map and are written again by the next call.  Not waited for.
+
+        The exploration loop: clearance -> cost_to_goal(any goal) or cost_cells -> frontiers -> cost_to_goal(frontier_goals) ->
+        routes(vehicle): the route from the vehicle's cell ends at the frontier that is cheapest to reach."""
+        import torch
+        from .engine import FrontierResult
+        occupied = self.words["l_occ"] if occupied is None else occupied
+        free = -self.words["l_free"] if free is None else free
+        if reachable and self._pen is None:
+            raise ValueError("frontiers: reachable needs the pen of a cost_to_goal() - call it first, or pass reachable=False")
+        pen = self._pen if reachable else None
+        if self.device.type == "cuda":
+            if self._frontier_mask is None:
+                self._frontier_mask = torch.empty(self.logodds.shape, dtype=torch.uint8, device=self.device)
+            frontier_cells(self.logodds, self.last_seen, occupied, free, pen=pen, out=self._frontier_mask)
+            old = self._frontiers
+            reuse = old is not None and old.clusters.shape[0] == capacity
+            self._frontiers = frontier_clusters(self._frontier_mask, min_cells, capacity, out=old if reuse else None, workspace=old.workspace if reuse else None)
+            return self._frontiers
+        self._frontier_mask = torch.from_numpy(_sv.frontier_cells(self.logodds.numpy(), self.last_seen.numpy(), occupied, free, None if pen is None else pen.numpy()))
+        got = _sv.frontier_clusters(self._frontier_mask.numpy(), min_cells, capacity)
+        self._frontiers = FrontierResult(**{k: torch.from_numpy(got[k]) for k in ("label", "clusters", "sums", "info")})
+        return self._frontiers
+
+    def frontier_goals(self, result=None):
+        """The goals the clusters of a frontiers() result offer (the last one's where none is given): float64 numpy [n,2] = (Xw, Yw),
+        the centres of the representatives of the written rows (stereo_vision.sv.frontier_goals) - what cost_to_goal takes, the next
+        step of the loop clearance -> cost_to_goal(any goal) or cost_cells -> frontiers -> cost_to_goal(frontier_goals) ->
+        routes(vehicle).  Waits for info and the written rows only."""
+        result = self._frontiers if result is None else result
+        if result is None:
+            raise ValueError("frontier_goals: no frontiers yet - call frontiers() first")
+        n = int(result.info.cpu().numpy()[3])
+        return _sv.frontier_goals(self.words, result.clusters[:n].cpu().numpy())
 
     def centres(self):
         """(Xw float64 [rows], Yw float64 [cols]) numpy: the world coordinates of the cells' centres."""

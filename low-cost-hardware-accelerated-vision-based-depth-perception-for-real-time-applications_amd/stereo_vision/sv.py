@@ -71,6 +71,13 @@ engine.occupancy_cost_to_goal / engine.cost_routes / rig.OccupancyMap.cost_to_go
 from the clearance field, the length of the cheapest 8-connected path to the nearest goal that cuts no corner, and per start cell the
 route that follows the field downhill.  Shortest paths under strictly positive integer weights: unique, so bit for bit.  The reference
 has no counterpart.
+
+frontier_cells, frontier_clusters (with frontier_labels, the union-find on its own) and frontier_goals are the definition of the frontiers
+of the world map (sv_frontier_* of include/stereo_vision_hip.h (O); engine.frontier_cells / engine.frontier_clusters /
+rig.OccupancyMap.frontiers and .frontier_goals on the GPU): the free cells that touch undecided space, their 8-connected clusters - label,
+size, bounding box and a representative cell each, in the order a scan meets them - and the world points cost_to_goal takes as goals.
+Labels are least indices and the statistics sums, minima and maxima of integers: bit for bit.  The reference has no counterpart
+(DESIGN.md §8).
 """
 import argparse
 import ctypes
@@ -1557,6 +1564,155 @@ def occupancy_cells_of(map, xy):
     return np.stack([r, c], -1).astype(np.int32)
 
 
+FRONTIER_CELLS_MAX = 8000000      # a linear index r * cols + c stays below 2^23
+FRONTIER_INDEX_BITS = 23
+FRONTIER_CAPACITY_MAX = 65535
+FRONTIER_NEIGHBOURS = ((-1, 0), (0, -1), (0, 1), (1, 0))  # where a free cell looks for unknown space
+FRONTIER_LINKS = ((0, -1), (-1, -1), (-1, 0), (-1, 1))    # W, NW, N, NE: with their opposites, the 8 neighbours that make a cluster
+
+
+def frontier_cells(logodds, last_seen, occupied, free, pen=None):
+    """The definition of sv_frontier_cells_device: uint8 [rows, cols] of 0 and 1 - 1 iff the cell's state (occupancy_map_state's, with
+    these thresholds) is 1, pen is None or pen[r, c] != COST_BLOCKED (a cell the vehicle cannot stand on is not a goal), and at least one
+    of its 4-neighbours lies inside the map and has state 0.  Cells outside the map are not unknown: the map's edge makes no frontier,
+    as it is a wall for cost_to_goal; what lies beyond is gained by recentering the map."""
+    L, S = np.asarray(logodds), np.asarray(last_seen)
+    if L.dtype != np.int16 or L.ndim != 2 or not (1 <= L.shape[0] <= 32768 and 1 <= L.shape[1] <= 32768):
+        raise ValueError("logodds must be int16 [rows, cols] of 1 .. 32768 in either dimension, got %s %s" % (L.dtype, L.shape))
+    if S.dtype != np.int32 or S.shape != L.shape:
+        raise ValueError("last_seen must be int32 %s, got %s %s" % (L.shape, S.dtype, S.shape))
+    occupied, free = _cost_int(occupied, -2 ** 31, 2 ** 31 - 1, "occupied"), _cost_int(free, -2 ** 31, 2 ** 31 - 1, "free")
+    rows, cols = L.shape
+    state = occupancy_map_state(L.astype(np.int64), S, occupied, free)
+    unknown = np.zeros((rows + 2, cols + 2), bool)  # False around the map
+    unknown[1:-1, 1:-1] = state == 0
+    near = np.zeros((rows, cols), bool)
+    for dr, dc in FRONTIER_NEIGHBOURS:
+        near |= unknown[1 + dr:1 + dr + rows, 1 + dc:1 + dc + cols]
+    mask = (state == 1) & near
+    if pen is not None:
+        P = np.asarray(pen)
+        if P.dtype != np.uint8 or P.shape != L.shape:
+            raise ValueError("pen must be uint8 %s, got %s %s" % (L.shape, P.dtype, P.shape))
+        mask &= P != COST_BLOCKED
+    return mask.astype(np.uint8)
+
+
+def _frontier_mask(mask, min_cells, capacity):
+    M = np.asarray(mask)
+    if M.dtype != np.uint8 or M.ndim != 2 or not (1 <= M.shape[0] <= 32768 and 1 <= M.shape[1] <= 32768):
+        raise ValueError("mask must be uint8 [rows, cols] of 1 .. 32768 in either dimension, got %s %s" % (M.dtype, M.shape))
+    if M.shape[0] * M.shape[1] > FRONTIER_CELLS_MAX:
+        raise ValueError("a mask of %d x %d cells: at most %d, so that a linear index stays below 2^23" % (M.shape + (FRONTIER_CELLS_MAX,)))
+    return M, _cost_int(min_cells, 1, FRONTIER_CELLS_MAX, "min_cells"), _cost_int(capacity, 1, FRONTIER_CAPACITY_MAX, "capacity")
+
+
+def frontier_labels(mask):
+    """int32, the shape of mask: -1 where mask is 0, elsewhere the least linear index r * cols + c of the cell's 8-connected component of
+    non-zero cells.  A union-find over the whole array: every pair of linked members hooks the larger of its two roots under the
+    smaller one, all chains are halved until they are flat, and both repeat until no linked pair has two roots.  Parents only ever
+    descend, so a tree's root is the least index of its set: the label does not depend on the order of the unions."""
+    M = np.asarray(mask) != 0
+    rows, cols = M.shape
+    index = np.arange(rows * cols, dtype=np.int64).reshape(rows, cols)
+    pairs = []
+    for dr, dc in FRONTIER_LINKS:
+        c0, c1 = max(0, -dc), cols - max(0, dc)  # the cells a = (r, c) whose partner b = (r + dr, c + dc) is inside the map
+        a, b = (slice(-dr, rows), slice(c0, c1)), (slice(0, rows + dr), slice(c0 + dc, c1 + dc))
+        both = M[a] & M[b]
+        pairs.append(np.stack([index[a][both], index[b][both]], 1))
+    pairs = np.concatenate(pairs)
+    parent = index.reshape(-1).copy()
+    while True:
+        ra, rb = parent[pairs[:, 0]], parent[pairs[:, 1]]  # roots: the chains are flat here
+        apart = ra != rb
+        if not apart.any():
+            break
+        pairs, ra, rb = pairs[apart], ra[apart], rb[apart]  # a pair once united stays so
+        np.minimum.at(parent, np.maximum(ra, rb), np.minimum(ra, rb))
+        while True:
+            up = parent[parent]
+            if (up == parent).all():
+                break
+            parent = up
+    return np.where(M, parent.reshape(rows, cols), -1).astype(np.int32)
+
+
+def frontier_clusters(mask, min_cells=1, capacity=1024):
+    """The definition of sv_frontier_clusters_device: mask uint8 [rows, cols] (a member is a non-zero byte; rows, cols in 1 .. 32768, rows
+    * cols <= 8 000 000), min_cells in 1 .. 8 000 000, capacity in 1 .. 65535 -> dict of
+
+      label     int32 [rows, cols]: frontier_labels'
+      clusters  int32 [capacity, 8]: row k = (label, size, rep_r, rep_c, r0, c0, r1, c1) of the k-th component of at least min_cells
+                members in ascending order of label - the order in which a scan of the map meets them; r0 .. c1 the inclusive bounding
+                box; (rep_r, rep_c) the member nearest to the integer centroid cell cr = (2 sum_r + size) // (2 size), cc likewise
+                (rounded half up: inside the box) by (r - cr)^2 + (c - cc)^2, ties to the least linear index.  Rows from min(kept,
+                capacity) on are -1
+      sums      int64 [capacity, 2]: (sum_r, sum_c) over the members of the row's component, 0 past the written rows
+      info      int32 [4]: the kept components (above capacity: rows were dropped), all components, the members, the rows written."""
+    M, min_cells, capacity = _frontier_mask(mask, min_cells, capacity)
+    rows, cols = M.shape
+    label = frontier_labels(M)
+    clusters, sums = np.full((capacity, 8), -1, np.int32), np.zeros((capacity, 2), np.int64)
+    at = np.flatnonzero(label.reshape(-1) >= 0).astype(np.int64)
+    roots, which, size = np.unique(label.reshape(-1)[at], return_inverse=True, return_counts=True)  # ascending labels
+    keep = size >= min_cells
+    kept, members = int(keep.sum()), len(at)
+    n = min(kept, capacity)
+    rank = np.where(keep, np.cumsum(keep) - 1, -1)
+    rank = np.where(rank < capacity, rank, -1)[which.reshape(-1)]  # per member; -1: its component has no row
+    at, rank = at[rank >= 0], rank[rank >= 0]
+    r, c = at // cols, at % cols
+    if n:
+        sum_r, sum_c, sz = np.zeros(n, np.int64), np.zeros(n, np.int64), size[keep][:n].astype(np.int64)
+        np.add.at(sum_r, rank, r), np.add.at(sum_c, rank, c)
+        box = np.stack([np.full(n, rows, np.int64), np.full(n, cols, np.int64), np.full(n, -1, np.int64), np.full(n, -1, np.int64)], 1)
+        np.minimum.at(box[:, 0], rank, r), np.minimum.at(box[:, 1], rank, c), np.maximum.at(box[:, 2], rank, r), np.maximum.at(box[:, 3], rank, c)
+        cr, cc = (2 * sum_r + sz) // (2 * sz), (2 * sum_c + sz) // (2 * sz)
+        key = np.full(n, np.iinfo(np.int64).max, np.int64)
+        np.minimum.at(key, rank, ((r - cr[rank]) ** 2 + (c - cc[rank]) ** 2) << FRONTIER_INDEX_BITS | at)
+        rep = key & ((1 << FRONTIER_INDEX_BITS) - 1)
+        clusters[:n] = np.concatenate([np.stack([roots[keep][:n], sz, rep // cols, rep % cols], 1), box], 1)
+        sums[:n] = np.stack([sum_r, sum_c], 1)
+    return {"label": label, "clusters": clusters, "sums": sums, "info": np.array([kept, len(roots), members, n], np.int32)}
+
+
+def frontier_goals(map, clusters):
+    """float64 [n, 2] = (Xw, Yw): the world centres (occupancy_map_centres) of the representatives of the written rows of clusters (int32
+    [capacity, 8], frontier_clusters') - the points cost_to_goal takes as its goals."""
+    C = np.asarray(clusters)
+    if C.ndim != 2 or C.shape[1] != 8 or C.dtype.kind not in "iu":
+        raise ValueError("clusters must be integers [capacity, 8], got %s %s" % (C.dtype, C.shape))
+    Xw, Yw = occupancy_map_centres(map)
+    C = C[C[:, 0] >= 0].astype(np.int64)
+    return np.stack([Xw[C[:, 2]], Yw[C[:, 3]]], 1) if len(C) else np.zeros((0, 2), np.float64)
+
+
+def frontier_lines(map, clusters, info):
+    """What --frontiers prints: a line for the counts of info, then one per written row of clusters - rank, size, the representative's
+    world centre in metres and the inclusive box in cells."""
+    C = np.asarray(clusters)
+    C = C[C[:, 0] >= 0]
+    xy = frontier_goals(map, C)
+    head = "frontiers: %d clusters kept of %d, %d cells, %d rows" % tuple(int(v) for v in np.asarray(info))
+    return [head] + ["frontier %d: %d cells, representative (%r, %r) m, rows %d..%d, cols %d..%d" % (k, row[1], float(x), float(y), row[4], row[6], row[5], row[7])
+                     for k, (row, (x, y)) in enumerate(zip(C.tolist(), xy))]
+
+
+def frontier_png(label, clusters):
+    """uint8, the shape of label: 0 on non-members and on members whose component has no row, 1 + (rank mod 255) on the members of the
+    written row `rank` - what --frontiers writes."""
+    L, C = np.asarray(label), np.asarray(clusters)
+    roots = C[C[:, 0] >= 0, 0].astype(np.int64)
+    out = np.zeros(L.shape, np.uint8)
+    if len(roots):
+        flat = L.reshape(-1).astype(np.int64)
+        k = np.searchsorted(roots, np.maximum(flat, 0))  # the rows ascend by label
+        hit = (flat >= 0) & (k < len(roots)) & (roots[np.minimum(k, len(roots) - 1)] == flat)
+        out.reshape(-1)[hit] = (1 + k[hit] % 255).astype(np.uint8)
+    return out
+
+
 class stereo_vision:
     def __init__(self, so_lib_path=DEFAULT_STEREO_VISION_SO_PATH, width=1242, height=375, defaultCalibFile=True, objectTracking=True,
                  graphics=False, display=False, scale=1, pc_extrapolation=1, YOLO_CFG="src/yolo/yolov4-tiny.cfg",
@@ -1713,9 +1869,20 @@ def main(argv=None):
                              "towards the world point (X, Y) in metres - cells within --clearance's METRES of an obstacle are blocked - "
                              "and the route from the last pose, written next to FILE as route.txt, one 'row col x y' line per cell; "
                              "prints the route's status, its length and the cost at its start")
+    parser.add_argument("--frontiers", type=int, default=0, metavar="MIN_CELLS",
+                        help="with --occupancy-map, --poses and --clearance: after the drive, the frontier clusters of the final map - the "
+                             "free cells that touch undecided space and lie at least --clearance's METRES from an obstacle, in 8-connected "
+                             "clusters of at least MIN_CELLS cells; prints one line per cluster (size, representative in metres, box) and "
+                             "writes the label image next to FILE as <FILE without .png>.frontiers.png: 0, or 1 + (rank mod 255) on a "
+                             "cluster's cells.  Without --goal the representatives are the goals of the cost-to-goal field and the route")
     args = parser.parse_args(argv)
     args.match_window = None
     args.goal_xy = None
+    if args.frontiers:
+        if not (args.occupancy_map and args.poses and args.clearance):
+            parser.error("--frontiers needs --occupancy-map, --poses and --clearance")
+        if not 1 <= args.frontiers <= FRONTIER_CELLS_MAX:
+            parser.error("--frontiers: MIN_CELLS in 1 .. %d, got %d" % (FRONTIER_CELLS_MAX, args.frontiers))
     if args.goal:
         if not (args.occupancy_map and args.poses and args.clearance):
             parser.error("--goal needs --occupancy-map, --poses and --clearance")
@@ -1914,9 +2081,21 @@ def _run_batched(args, ldir, rdir, files):
             _write_png(args.occupancy_map, OCCUPANCY_PNG[world.state().cpu().numpy()])
             if args.clearance:
                 _write_png(os.path.splitext(args.occupancy_map)[0] + ".clearance.png", clearance_png(world.clearance(args.clearance).cpu().numpy()))
+            field, last_xy = None, (refined[-1][:2] if refined else args.pose_rows[-1, :2])
             if args.goal_xy is not None:  # the field under the clearance just made, and the route from where the drive ended
                 field = world.cost_to_goal(args.goal_xy, args.clearance)
-                route, xy = world.routes(refined[-1][:2] if refined else args.pose_rows[-1, :2])
+            if args.frontiers:  # under the pen of a cost-to-goal field: the one just made, or one towards where the drive ended
+                if field is None:
+                    world.cost_to_goal(last_xy, args.clearance)
+                found = world.frontiers(min_cells=args.frontiers)
+                clusters = found.clusters.cpu().numpy()
+                print("".join(line + "\n" for line in frontier_lines(world.words, clusters, found.info.cpu().numpy())), end="")
+                _write_png(os.path.splitext(args.occupancy_map)[0] + ".frontiers.png", frontier_png(found.label.cpu().numpy(), clusters))
+                goals = world.frontier_goals(found)
+                if field is None and len(goals):
+                    field = world.cost_to_goal(goals, args.clearance)
+            if field is not None:
+                route, xy = world.routes(last_xy)
                 length, status = int(route.length[0]), int(route.status[0])
                 cells = route.cells[0, :length].cpu().numpy()
                 with open(os.path.join(os.path.dirname(os.path.abspath(args.occupancy_map)), "route.txt"), "w") as f:
