@@ -1110,6 +1110,65 @@ int sv_frontier_clusters_device(const uint8_t *mask, int rows, int cols, int min
  * up over the calls.  The results and info do not depend on it.  Returns SV_OK, or SV_ERR_ARG for another variant. */
 int sv_debug_frontier(int variant, unsigned long long *counters_device);
 
+/* ---- (P) the expected view of the world map: (K)'s log-odds + candidate poses + rays -> the distinct cells seen, by state, and the best pose ---- */
+
+/* (O) says where the frontiers are; this group says what the vehicle would see from a pose: rays are cast through the map from each
+ * candidate, and the DISTINCT cells they see are counted by state.  The unknown count is the worth of a pose for exploration (next-best
+ * view), the rays' end cells are a virtual range scan of the map.  Doubles place the origin and the rays' ends; from there on everything
+ * is integers, and the results are bitwise reproducible whatever order the lanes take.  stereo_vision.sv.occupancy_view restates it in
+ * numpy; view_rays makes `ends` and `reach` - the only trigonometry, on the host.
+ *
+ *   candidates K = n_groups * n_poses poses (tx, ty, c, s) as in (L) and (M); the best is chosen per group.
+ *   origin     gx = floor(tx ms), gy = floor(ty ms), cell (top - 1 - gx, left - 1 - gy): (M)'s rule.  A candidate with a word that is not
+ *              finite or an origin outside the map is invalid: every ray status 5, every end (-1, -1), counts 0, score -1.
+ *   ray end    Xw = (c ex - s ey) + tx, Yw = (s ex + c ey) + ty, every product, difference and sum rounded on its own; its cell by the
+ *              same rule, not clipped to the map.  With (dr, dc) from the origin's cell to it, a ray whose end is not finite or has |dr| >
+ *              reach or |dc| > reach is invalid on its own: status 5, end (-1, -1), and it marks nothing.  Nothing is clamped.
+ *   walk       steps k = 0 .. n, n = max(|dr|, |dc|), at (r0 + floor((2 k dr + n) / (2 n)), c0 + floor((2 k dc + n) / (2 n))): (J)'s sight
+ *              line with a ground end.  Step 0, the origin's cell, is visible and never ends the ray.  For k >= 1, in this order:
+ *                cell k outside the map                                       -> status 2 (edge); cell k is not visible
+ *                a diagonal step - both coordinates changed - whose two side
+ *                cells (r_prev, c) and (r, c_prev) are both occupied or outside  -> status 3 (corner); cell k is not visible
+ *                cell k is visible;
+ *                its state is 2                                                -> status 1 (hit)
+ *                its state is 0 and it is the max_unknown-th such cell among
+ *                the steps k >= 1 of this ray, max_unknown > 0                 -> status 4 (unknown)
+ *              A ray that reaches k = n has status 0 (full).  A ray's end cell is its last visible cell.
+ *   ray states the map's edge is a wall, as in (N) and (O); unknown cells are seen through, up to max_unknown of them per ray (0: no limit);
+ *              occupied cells are seen and then stop the ray; free cells are seen and passed.
+ *   corner     a ray must not slip between two occupied cells that touch at a corner: the guard applies on diagonal steps only and needs
+ *   guard      BOTH side cells blocked - one open side lets the ray pass.  After the edge test both side cells lie inside the map.
+ *   counts     (unknown, free, occupied): the number of distinct visible cells of each state over all rays of the candidate; a cell that
+ *              fifty rays cross counts once.
+ *   best       score = counts[0], -1 for an invalid candidate; best[g] is the lowest p with the largest score of group g, best_score[g]
+ *              that score. */
+
+/* Host only: the bytes of the workspace sv_view_device needs - a byte per cell rounded up to 16 and 262 144 for the scores of up to
+ * 65535 candidates.  SV_ERR_ARG (bytes untouched) for a NULL bytes or rows or cols outside 1..32768. */
+int sv_view_workspace(int rows, int cols, size_t *bytes);
+/* Enqueued on `stream` (a hipStream_t, NULL = the default stream) as three kernels - the states of the map's cells, a workgroup per
+ * candidate that walks its rays, the best per group - and not waited for: nothing is allocated and no host synchronisation is made.
+ *   logodds      : int16 [rows][cols] device; last_seen : int32 [rows][cols] device - (K)'s pair; map : its words, host
+ *   poses        : double [n_groups][n_poses][4] device; n_groups * n_poses in 0..65535, n_poses >= 1; n_groups == 0: nothing to do
+ *   ends         : double [n_rays][2] device, metres in vehicle axes; n_rays in 1..1024; reach in 1..254 cells
+ *   occupied, free_ : the thresholds of the state, as in (O); max_unknown in 0..255
+ *   counts       : int32 [n_groups][n_poses][3]; end_cells : int16 [n_groups][n_poses][n_rays][2] = (row, col); status : uint8
+ *                  [n_groups][n_poses][n_rays]; best, best_score : int32 [n_groups] - device, all written in full
+ *   workspace    : device, 16-byte aligned, workspace_bytes >= what sv_view_workspace gives
+ * Returns SV_OK, SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued, the outputs untouched, the text in sv_last_error(NULL) - for: a bad word
+ * of the map (as in (K)); n_poses < 1; n_groups < 0 or n_groups * n_poses above 65535; n_rays outside 1..1024; reach outside 1..254;
+ * max_unknown outside 0..255; a NULL logodds, last_seen, ends or workspace, or with n_groups > 0 a NULL poses or output; logodds not 2-byte,
+ * last_seen, counts, end_cells, best or best_score not 4-byte, poses or ends not 8-byte, the workspace not 16-byte aligned; too small a
+ * workspace; an output overlapping an input or another output.  These checks run before any HIP call. */
+int sv_view_device(const int16_t *logodds, const int32_t *last_seen, const sv_occupancy_map_spec *map, const double *poses, int n_groups, int n_poses,
+                   const double *ends, int n_rays, int reach, int occupied, int free_, int max_unknown, int32_t *counts, int16_t *end_cells, uint8_t *status,
+                   int32_t *best, int32_t *best_score, void *workspace, size_t workspace_bytes, void *stream);
+/* Test and measurement hook for sv_view_device, process-wide: variant 0 (the default) sizes the LDS window of a workgroup by the call's
+ * reach, 1 always lays it out for reach 254 (509 rows of 16 words); stages 3 (the default) is the whole call, 1 enqueues the state kernel
+ * alone and 2 leaves the best out.  The results of a whole call do not depend on the variant.  Returns SV_OK, or SV_ERR_ARG for another
+ * variant or stages outside 1..3. */
+int sv_debug_view(int variant, int stages);
+
 /* ---- (A) the reference's exported symbols ------------------------------------------------------------- */
 
 typedef struct {

@@ -524,7 +524,7 @@ class SvOccupancyMapSpec(ctypes.Structure):
 
 
 def _signatures():
-    """The table below: per stage group of the C API, (D) to (O), its functions and per function (restype, argtypes), parameter by
+    """The table below: per stage group of the C API, (D) to (P), its functions and per function (restype, argtypes), parameter by
     parameter as include/stereo_vision_hip.h declares them - tests/test_stage_signatures.py holds the two against each other."""
     P = ctypes.POINTER
     vp, ci, sz, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_int64
@@ -594,11 +594,17 @@ def _signatures():
             "sv_frontier_clusters_device": (ci, [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, sz, vp]),
             "sv_debug_frontier": (ci, [ci, vp]),
         },
+        "view": {  # (P)
+            "sv_view_workspace": (ci, [ci, ci, P(sz)]),
+            "sv_view_device": (ci, [vp, vp, om, vp, ci, ci, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, sz, vp]),
+            "sv_debug_view": (ci, [ci, ci]),
+        },
     }
 
 
 STAGE_SIGNATURES = _signatures()  # plain data: made without loading the library
 _GROUP_NEEDS = {"voxel": ("cloud",), "occupancy_map": ("occupancy",), "map_match": ("occupancy_map",), "clearance": ("occupancy_map",), "cost": ("clearance",), "frontier": ("cost",)}
+_GROUP_NEEDS["view"] = ("occupancy_map",)
 _bound_groups = set()
 
 
@@ -1713,6 +1719,81 @@ def debug_frontier(variant=0, counters=None):
     memory) and a CUDA int64 [2] tensor (or None) that receives the atomic minima issued on global memory and the tiles that held a
     member.  Process-wide; a test hook."""
     return int(frontier_lib().sv_debug_frontier(int(variant), None if counters is None else counters.data_ptr()))
+
+
+def view_lib():
+    """The library with the signatures of group (P) declared."""
+    return _bind("view")
+
+
+class ViewResult(_Result):
+    """What occupancy_view returns, tensors on the map's device: counts int32 [G,P,3] = (unknown, free, occupied) - the distinct cells
+    the rays of a candidate see, by state -, end_cells int16 [G,P,n_rays,2] = (row, col) of each ray's last visible cell, (-1, -1) for
+    an invalid one, status uint8 [G,P,n_rays] (stereo_vision.sv.VIEW_FULL .. VIEW_INVALID), best int32 [G] (the lowest p with the
+    most unknown cells), best_score int32 [G] (that count, -1 where every candidate is invalid) and workspace (the uint8 tensor the call
+    worked in)."""
+    __slots__ = ("counts", "end_cells", "status", "best", "best_score", "workspace")
+
+
+def occupancy_view(logodds, last_seen, map, poses, ends, reach, occupied, free, max_unknown=0, out=None, workspace=None):
+    """The expected view of a world map from candidate poses - the definition of stereo_vision.sv.occupancy_view on the GPU, bit for bit,
+    in three kernels: logodds a contiguous CUDA int16 tensor [rows,cols] and last_seen an int32 tensor of the same shape on the same
+    device, map an SvOccupancyMapSpec or a dict of its nine words, poses float64 [G,P,4] = (tx, ty, c, s) with G * P <= 65535 and ends
+    float64 [n_rays,2] (stereo_vision.sv.view_rays', with its reach) - numpy arrays, uploaded once, or tensors on the device -, occupied
+    and free the thresholds of the state, max_unknown in 0 .. 255.  out: a ViewResult (or a tuple (counts, end_cells, status, best,
+    best_score)) of contiguous tensors of the right shapes to write into; workspace: a uint8 tensor of at least sv_view_workspace's bytes
+    to reuse.  -> ViewResult; enqueued on torch's current stream, not waited for; nothing dense is read back."""
+    import torch
+    from .stereo_vision.sv import VIEW_POSES_MAX, VIEW_RAYS_MAX, VIEW_REACH_MAX, occupancy_map_words
+    words = occupancy_map_words(map)
+    rows, cols = words["rows"], words["cols"]
+    if _map_tensor(logodds, torch.int16, "logodds") != (rows, cols):
+        raise ValueError("logodds must be [%d,%d] as the map's words say, got %s" % (rows, cols, tuple(logodds.shape)))
+    _map_tensor(last_seen, torch.int32, "last_seen", like=logodds)
+    dev = logodds.device
+    p, e = _device_poses(poses, dev), _device_poses(ends, dev)
+    if p.dim() != 3 or p.shape[2] != 4 or p.shape[1] < 1 or p.shape[0] * p.shape[1] > VIEW_POSES_MAX:
+        raise ValueError("poses must be [G,P,4] with P >= 1 and G * P <= 65535, got %s" % (tuple(p.shape),))
+    if e.dim() != 2 or e.shape[1] != 2 or not 1 <= e.shape[0] <= VIEW_RAYS_MAX:
+        raise ValueError("ends must be [n_rays,2] with 1 <= n_rays <= 1024, got %s" % (tuple(e.shape),))
+    for v, lo, hi, what in ((reach, 1, VIEW_REACH_MAX, "reach"), (max_unknown, 0, 255, "max_unknown"), (occupied, -2 ** 31, 2 ** 31 - 1, "occupied"),
+                            (free, -2 ** 31, 2 ** 31 - 1, "free")):
+        if isinstance(v, bool) or int(v) != v or not lo <= v <= hi:
+            raise ValueError("%s must be an integer in %d .. %d, got %r" % (what, lo, hi, v))
+    G, P, n_rays = p.shape[0], p.shape[1], e.shape[0]
+    shapes = (("counts", (G, P, 3), torch.int32), ("end_cells", (G, P, n_rays, 2), torch.int16), ("status", (G, P, n_rays), torch.uint8),
+              ("best", (G,), torch.int32), ("best_score", (G,), torch.int32))
+    if out is None:
+        given = [torch.empty(shape, dtype=dtype, device=dev) for _, shape, dtype in shapes]
+    else:
+        given = [getattr(out, name) for name, _, _ in shapes] if isinstance(out, ViewResult) else list(out)
+        if len(given) != 5:
+            raise ValueError("out must be a ViewResult or (counts, end_cells, status, best, best_score)")
+        for t, (name, shape, dtype) in zip(given, shapes):
+            if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous()):
+                raise ValueError("out: %s must be a contiguous %s tensor %s on the device of logodds" % (name, str(dtype).replace("torch.", ""), list(shape)))
+    L = view_lib()
+    nbytes = ctypes.c_size_t()
+    _check(L.sv_view_workspace(rows, cols, ctypes.byref(nbytes)), "sv_view_workspace")
+    if workspace is None:
+        workspace = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    elif not (isinstance(workspace, torch.Tensor) and workspace.device == dev and workspace.dtype == torch.uint8 and workspace.is_contiguous()
+              and workspace.numel() >= nbytes.value):
+        raise ValueError("workspace must be a contiguous uint8 tensor of at least %d bytes on the device of logodds" % nbytes.value)
+    counts, end_cells, status, best, best_score = given
+    spec = _occupancy_map_struct(words)
+    with torch.cuda.device(dev):
+        rc = L.sv_view_device(logodds.data_ptr(), last_seen.data_ptr(), ctypes.byref(spec), _ptr(p), G, P, e.data_ptr(), n_rays, int(reach), int(occupied), int(free),
+                              int(max_unknown), _ptr(counts), _ptr(end_cells), _ptr(status), _ptr(best), _ptr(best_score), workspace.data_ptr(), workspace.numel(),
+                              torch.cuda.current_stream(dev).cuda_stream)
+    _check(rc, "sv_view_device")
+    return ViewResult(counts=counts, end_cells=end_cells, status=status, best=best, best_score=best_score, workspace=workspace)
+
+
+def debug_view(variant=0, stages=3):
+    """sv_debug_view: the LDS window of occupancy_view's workgroups (0: sized by the call's reach; 1: always 509 cells a side) and the
+    kernels a call enqueues (3: all; 1: the state plane alone; 2: without the best).  Process-wide; a test and measurement hook."""
+    return int(view_lib().sv_debug_view(int(variant), int(stages)))
 
 
 def host_support_filter(params, dcan, width, height, threads=0, lattice=False):

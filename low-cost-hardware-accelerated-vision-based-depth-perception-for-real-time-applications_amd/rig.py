@@ -36,7 +36,7 @@ import ctypes
 import numpy as np
 
 from .engine import (SvParams, StereoEngine, StereoError, box_positions_from_disparity, box_spec, cloud_spec, compact_cloud_from_disparity,
-                     ground_from_disparity, ground_spec, lib, occupancy_from_disparity, occupancy_fuse, occupancy_match, occupancy_clearance, clearance_paths, cost_cells, cost_routes, frontier_cells, frontier_clusters, occupancy_cost_to_goal, occupancy_spec, pinned_array, reproject, split_clouds, stixel_spec, stixels_from_disparity,
+                     ground_from_disparity, ground_spec, lib, occupancy_from_disparity, occupancy_fuse, occupancy_match, occupancy_clearance, clearance_paths, cost_cells, cost_routes, frontier_cells, frontier_clusters, occupancy_cost_to_goal, occupancy_view, occupancy_spec, pinned_array, reproject, split_clouds, stixel_spec, stixels_from_disparity,
                      top_view_from_disparity, top_view_spec, split_voxel_clouds, voxel_cloud_from_disparity, voxel_spec)
 from .stereo_vision.sv import CAMERA_TO_VEHICLE, DEFAULT_CALIBRATION  # noqa: F401 (CAMERA_TO_VEHICLE: re-exported for top_view)
 from .stereo_vision.sv import free_space_points, ground_pose
@@ -428,7 +428,9 @@ class OccupancyMap:
     obstacle per cell, and candidate paths checked against it; clearance_radius is the radius in cells of the last clearance().
     cost_to_goal() and routes() are group (N): the length of the cheapest path from every cell to a goal, and the cells to drive.
     frontiers() and frontier_goals() are group (O): the free cells that touch undecided space, their clusters and one goal per cluster -
-    the loop clearance -> cost_to_goal(any goal) or cost_cells -> frontiers -> cost_to_goal(frontier_goals) -> routes(vehicle)."""
+    the loop clearance -> cost_to_goal(any goal) or cost_cells -> frontiers -> cost_to_goal(frontier_goals) -> routes(vehicle).
+    view() and frontier_views() are group (P): the distinct cells the vehicle would see from candidate poses, and with them a heading and a
+    worth per frontier - frontiers -> frontier_views -> cost_to_goal(the goals worth the trip) -> routes."""
 
     def __init__(self, x_range, y_range, scale, device="cuda", **log_odds_words):
         import torch
@@ -443,6 +445,7 @@ class OccupancyMap:
         self._d2, self._clearance_workspace, self.clearance_radius = None, None, None  # clearance()'s, made on its first call
         self._pen, self._cost, self._cost_workspace = None, None, None  # cost_to_goal()'s, made on its first call
         self._frontier_mask, self._frontiers = None, None  # frontiers()'s, made on its first call
+        self._view = None  # view()'s result and workspace, made on its first call
 
     def reset(self):
         """A fresh map at the place it has scrolled to: logodds 0, last_seen -1, seq 0."""
@@ -669,6 +672,53 @@ class OccupancyMap:
             raise ValueError("frontier_goals: no frontiers yet - call frontiers() first")
         n = int(result.info.cpu().numpy()[3])
         return _sv.frontier_goals(self.words, result.clusters[:n].cpu().numpy())
+
+    def view(self, poses, fov, range_m, n_rays=128, max_unknown=0, occupied=None, free=None):
+        """What the vehicle would see of the map as it stands from candidate poses (stereo_vision.sv.occupancy_view): poses float64 [K,3]
+        or [G,P,3] = (x, y, yaw), or [...,4] = (tx, ty, c, s), numpy or a tensor - [K,*] is K groups of one candidate; a fan of n_rays
+        rays over fov radians that reach range_m metres (stereo_vision.sv.view_rays); max_unknown: the unknown cells a ray sees through
+        (0: no limit); occupied and free default as state()'s.  -> engine.ViewResult with counts int32 [G,P,3] = (unknown, free,
+        occupied) distinct cells seen, end_cells int16 [G,P,n_rays,2], status uint8 [G,P,n_rays], best and best_score int32 [G] on the
+        map's device.  The tensors and the workspace stay with the map and are written again by the next call of the same shapes.  Not
+        waited for."""
+        import torch
+        from .engine import ViewResult
+        occupied = self.words["l_occ"] if occupied is None else occupied
+        free = -self.words["l_free"] if free is None else free
+        ends, reach = _sv.view_rays(fov, n_rays, range_m, self.words["scale"])
+        p = poses
+        if not isinstance(p, torch.Tensor):
+            p = np.asarray(p, np.float64)
+        if p.ndim not in (2, 3) or p.shape[-1] not in (3, 4):
+            raise ValueError("view: poses must be [K,3] or [G,P,3] = (x, y, yaw), or [...,4] poses, got %s" % (tuple(p.shape),))
+        if p.shape[-1] == 3:
+            p = p.cpu().numpy() if isinstance(p, torch.Tensor) else p
+            p = _sv.occupancy_pose(p[..., 0], p[..., 1], p[..., 2])
+        if p.ndim == 2:
+            p = p[:, None, :]
+        if self.device.type == "cuda":
+            old = self._view
+            shape = (p.shape[0], p.shape[1], len(ends), 2)
+            reuse = old is not None and tuple(old.end_cells.shape) == shape
+            self._view = occupancy_view(self.logodds, self.last_seen, self.words, p, ends, reach, occupied, free, max_unknown, out=old if reuse else None,
+                                        workspace=None if old is None else old.workspace)
+            return self._view
+        p = p.cpu().numpy() if isinstance(p, torch.Tensor) else p
+        got = _sv.occupancy_view(self.logodds.numpy(), self.last_seen.numpy(), self.words, p, ends, reach, occupied, free, max_unknown)
+        self._view = ViewResult(**{k: torch.from_numpy(np.ascontiguousarray(got[k])) for k in ("counts", "end_cells", "status", "best", "best_score")})
+        return self._view
+
+    def frontier_views(self, result=None, headings=16, fov=np.pi / 2, range_m=10.0, n_rays=128, max_unknown=0):
+        """The best arrival pose per frontier: the goals of a frontiers() result (the last one's where none is given) crossed with
+        `headings` yaws 2 pi p / headings (stereo_vision.sv.view_headings), each viewed as view() does; the best heading of a frontier
+        is the first that sees the most unknown cells.  -> (float64 numpy [n,3] = (x, y, yaw), the ViewResult with counts [n,headings,3]).
+        Waits for best and best_score only - 2 n words - beside what frontier_goals reads."""
+        goals = self.frontier_goals(result)
+        window = _sv.view_headings(goals, headings)  # [n, headings, 4]
+        res = self.view(window, fov, range_m, n_rays, max_unknown)
+        best = res.best.cpu().numpy().astype(np.int64)
+        yaw = 2 * np.pi * np.arange(int(headings), dtype=np.float64) / int(headings)
+        return np.stack([goals[:, 0], goals[:, 1], yaw[best]], 1), res
 
     def centres(self):
         """(Xw float64 [rows], Yw float64 [cols]) numpy: the world coordinates of the cells' centres."""

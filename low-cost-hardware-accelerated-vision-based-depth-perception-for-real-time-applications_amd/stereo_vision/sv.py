@@ -78,6 +78,12 @@ rig.OccupancyMap.frontiers and .frontier_goals on the GPU): the free cells that 
 size, bounding box and a representative cell each, in the order a scan meets them - and the world points cost_to_goal takes as goals.
 Labels are least indices and the statistics sums, minima and maxima of integers: bit for bit.  The reference has no counterpart
 (DESIGN.md §8).
+
+view_rays, view_headings, occupancy_view, view_ranges and view_lines are the definition of the expected view of the world map from
+candidate poses (sv_view_* of include/stereo_vision_hip.h (P); engine.occupancy_view / rig.OccupancyMap.view and .frontier_views on the
+GPU): rays cast through the map from each pose, the distinct cells they see counted by state - the unknown ones are what a trip there
+would uncover -, the last visible cell of every ray - a virtual range scan - and the best pose per group.  The trigonometry stays on
+the host; the walk is integers: bit for bit.  The reference has no counterpart.
 """
 import argparse
 import ctypes
@@ -1713,6 +1719,169 @@ def frontier_png(label, clusters):
     return out
 
 
+VIEW_REACH_MAX = 254    # cells a ray may span on either axis: the window of a candidate is at most 509 cells a side
+VIEW_RAYS_MAX = 1024
+VIEW_POSES_MAX = 65535  # candidates per call, G * P
+VIEW_FULL, VIEW_HIT, VIEW_EDGE, VIEW_CORNER, VIEW_UNKNOWN, VIEW_INVALID = range(6)  # the status of a ray
+
+
+def view_rays(fov, n_rays, range_m, scale):
+    """(ends float64 [n_rays, 2], reach int): a fan of n_rays rays (1 .. 1024) over the field of view fov (radians, 0 < fov <= 2 pi) that
+    reach range_m metres, for a map of `scale` cells per metre.  Ray j points at a_j = (j + 0.5) / n_rays * fov - fov / 2 - angle 0 is
+    the vehicle's +x, angles grow counter-clockwise as occupancy_pose's yaw - and ends at range_m (cos a_j, sin a_j) in vehicle axes;
+    reach = ceil(range_m scale) + 1 cells bounds the end of every ray from wherever in its cell the vehicle stands (ValueError above
+    254).  The only trigonometry of the stage: it runs on the host."""
+    if isinstance(n_rays, (bool, np.bool_)) or int(n_rays) != n_rays or not 1 <= n_rays <= VIEW_RAYS_MAX:
+        raise ValueError("n_rays must be an integer in 1 .. 1024, got %r" % (n_rays,))
+    if isinstance(scale, (bool, np.bool_)) or not np.isfinite(scale) or int(scale) != scale or scale < 1:
+        raise ValueError("scale must be a positive integer, got %r" % (scale,))
+    if not (np.isfinite(fov) and 0 < fov <= 2 * np.pi):
+        raise ValueError("fov must lie in (0, 2 pi] radians, got %r" % (fov,))
+    if not (np.isfinite(range_m) and range_m > 0):
+        raise ValueError("range_m must be a positive number of metres, got %r" % (range_m,))
+    reach = int(np.ceil(float(range_m) * int(scale))) + 1
+    if reach > VIEW_REACH_MAX:
+        raise ValueError("%r m are %d cells at scale %d, a reach of %d: at most 254" % (range_m, reach - 1, scale, reach))
+    n = int(n_rays)
+    a = (np.arange(n, dtype=np.float64) + 0.5) / n * float(fov) - float(fov) / 2
+    return float(range_m) * np.stack([np.cos(a), np.sin(a)], 1), reach
+
+
+def view_headings(xy, n):
+    """float64 [len(xy), n, 4]: occupancy_pose of each point of xy (float64 [m, 2], world metres) at the n yaws 2 pi p / n."""
+    p = np.asarray(xy, np.float64).reshape(-1, 2)
+    if isinstance(n, (bool, np.bool_)) or int(n) != n or n < 1:
+        raise ValueError("n must be a positive integer, got %r" % (n,))
+    yaw = 2 * np.pi * np.arange(int(n), dtype=np.float64) / int(n)
+    return occupancy_pose(p[:, None, 0], p[:, None, 1], yaw[None, :])
+
+
+def _view_ray(S, r0, c0, r1, c1, max_unknown):
+    """One valid ray through the states S from cell (r0, c0) towards cell (r1, c1) -> (status, the steps that are visible)."""
+    rows, cols = S.shape
+    r, c = occupancy_ray_cells(r0, c0, r1, c1, obstacle_end=False)  # the project's one line rule
+    inside = (r >= 0) & (r < rows) & (c >= 0) & (c < cols)
+
+    def states(rr, cc):  # 2 outside the map: the edge is a wall
+        ok = (rr >= 0) & (rr < rows) & (cc >= 0) & (cc < cols)
+        return np.where(ok, S[np.where(ok, rr, 0), np.where(ok, cc, 0)], 2)
+
+    st = states(r, c)
+    later = np.arange(len(r)) >= 1  # step 0 is the origin's cell: visible, and it never ends the ray
+    corner = np.zeros(len(r), bool)
+    corner[1:] = (r[1:] != r[:-1]) & (c[1:] != c[:-1]) & (states(r[:-1], c[1:]) == 2) & (states(r[1:], c[:-1]) == 2)
+    edge = later & ~inside
+    corner &= later & inside
+    hit = later & inside & (st == 2)
+    unknown = later & inside & (st == 0)
+    spent = unknown & (np.cumsum(unknown) == max_unknown) if max_unknown > 0 else np.zeros(len(r), bool)
+    stop = edge | corner | hit | spent
+    if not stop.any():
+        return VIEW_FULL, len(r)
+    k = int(stop.argmax())
+    if edge[k]:
+        return VIEW_EDGE, k
+    if corner[k]:
+        return VIEW_CORNER, k
+    return (VIEW_HIT if hit[k] else VIEW_UNKNOWN), k + 1
+
+
+def occupancy_view(logodds, last_seen, map, poses, ends, reach, occupied, free, max_unknown=0):
+    """The definition of sv_view_device: what the vehicle would see of the map (logodds int16 and last_seen int32 [rows, cols] with the
+    words `map`) from each of the candidate poses (float64 [G, P, 4] = (tx, ty, c, s), G * P <= 65535) along the rays `ends` (float64
+    [n_rays, 2], vehicle axes, metres) of at most `reach` cells (view_rays' pair), with the thresholds of occupancy_map_state and
+    max_unknown in 0 .. 255 (0: no limit).  -> dict of counts int32 [G, P, 3] = (unknown, free, occupied), end_cells int16 [G, P, n_rays,
+    2], status uint8 [G, P, n_rays], best int32 [G], best_score int32 [G].
+
+      origin  gx = floor(tx ms), gy = floor(ty ms), cell (top - 1 - gx, left - 1 - gy): clearance_cells' rule.  A candidate with a word
+              that is not finite or an origin outside the map is invalid: every ray VIEW_INVALID with end (-1, -1), counts 0, score -1.
+      end     Xw = (c ex - s ey) + tx, Yw = (s ex + c ey) + ty, every product, difference and sum rounded on its own (clearance_paths'),
+              and its cell by the same rule, not clipped to the map.  With (dr, dc) from the origin's cell to it, a ray is invalid on its
+              own - VIEW_INVALID, end (-1, -1), it marks nothing - if its end is not finite or |dr| > reach or |dc| > reach.  Nothing is
+              clamped: this guard is what bounds the window a candidate can see.
+      walk    the steps k = 0 .. max(|dr|, |dc|) of occupancy_ray_cells(r0, c0, r1, c1, obstacle_end=False).  Step 0, the origin's cell,
+              is visible and never ends the ray.  For k >= 1, in this order: cell k outside the map -> VIEW_EDGE, the cell not visible
+              (the map's edge is a wall, as for cost_to_goal and frontier_cells); the step diagonal - both coordinates changed - and
+              both side cells (r_prev, c), (r, c_prev) occupied or outside the map -> VIEW_CORNER, the cell not visible (a ray must not
+              slip through a diagonal wall; one open side lets it pass); else cell k is visible, and its state 2 -> VIEW_HIT (occupied
+              cells are seen and then stop the ray); its state 0 and it the max_unknown-th unknown cell among the steps k >= 1 of this
+              ray, max_unknown > 0 -> VIEW_UNKNOWN (unknown cells are seen through, up to max_unknown).  A ray that reaches its last
+              step is VIEW_FULL.  A ray's end cell is its last visible cell.
+      counts  the DISTINCT visible cells of each state over all rays of the candidate: a cell crossed by fifty rays counts once.
+      best    score = counts[..., 0], -1 for an invalid candidate; best[g] the lowest p with the largest score, best_score[g] that score."""
+    w = occupancy_map_words(map)
+    rows, cols, top, left, ms = w["rows"], w["cols"], w["top"], w["left"], float(w["scale"])
+    L, Sn = np.asarray(logodds), np.asarray(last_seen)
+    if L.dtype != np.int16 or L.shape != (rows, cols):
+        raise ValueError("logodds must be int16 [%d, %d], got %s %s" % (rows, cols, L.dtype, L.shape))
+    if Sn.dtype != np.int32 or Sn.shape != L.shape:
+        raise ValueError("last_seen must be int32 %s, got %s %s" % (L.shape, Sn.dtype, Sn.shape))
+    p, e = np.asarray(poses, np.float64), np.asarray(ends, np.float64)
+    if p.ndim != 3 or p.shape[2] != 4 or p.shape[1] < 1 or p.shape[0] * p.shape[1] > VIEW_POSES_MAX:
+        raise ValueError("poses must be float64 [G, P, 4] with P >= 1 and G * P <= 65535, got %s" % (p.shape,))
+    if e.ndim != 2 or e.shape[1] != 2 or not 1 <= e.shape[0] <= VIEW_RAYS_MAX:
+        raise ValueError("ends must be float64 [n_rays, 2] with 1 <= n_rays <= 1024, got %s" % (e.shape,))
+    reach, max_unknown = _cost_int(reach, 1, VIEW_REACH_MAX, "reach"), _cost_int(max_unknown, 0, 255, "max_unknown")
+    occupied, free = _cost_int(occupied, -2 ** 31, 2 ** 31 - 1, "occupied"), _cost_int(free, -2 ** 31, 2 ** 31 - 1, "free")
+    S = occupancy_map_state(L.astype(np.int64), Sn, occupied, free)
+    G, P, n_rays = p.shape[0], p.shape[1], e.shape[0]
+    counts = np.zeros((G, P, 3), np.int32)
+    end_cells = np.full((G, P, n_rays, 2), -1, np.int16)
+    status = np.full((G, P, n_rays), VIEW_INVALID, np.uint8)
+    score = np.full((G, P), -1, np.int32)
+    tx, ty, c, s = (p[..., None, k] for k in range(4))
+    with np.errstate(invalid="ignore", over="ignore"):
+        gx0, gy0 = np.floor(tx * ms), np.floor(ty * ms)  # [G, P, 1]
+        origin = np.isfinite(p).all(-1)[..., None] & (gx0 >= top - rows) & (gx0 <= top - 1) & (gy0 >= left - cols) & (gy0 <= left - 1)
+        Xw, Yw = (c * e[:, 0] - s * e[:, 1]) + tx, (s * e[:, 0] + c * e[:, 1]) + ty  # [G, P, n_rays]
+        gx1, gy1 = np.floor(Xw * ms), np.floor(Yw * ms)
+        dr, dc = gx0 - gx1, gy0 - gy1  # rows and columns count against gx and gy
+        valid = origin & np.isfinite(gx1) & np.isfinite(gy1) & (np.abs(dr) <= reach) & (np.abs(dc) <= reach)
+    for g, q in zip(*np.nonzero(origin[..., 0])):
+        r0, c0 = top - 1 - int(gx0[g, q, 0]), left - 1 - int(gy0[g, q, 0])
+        seen = []
+        for j in np.flatnonzero(valid[g, q]):
+            r1, c1 = r0 + int(dr[g, q, j]), c0 + int(dc[g, q, j])
+            status[g, q, j], m = _view_ray(S, r0, c0, r1, c1, max_unknown)
+            r, cc = occupancy_ray_cells(r0, c0, r1, c1, obstacle_end=False, k_hi=m - 1)
+            end_cells[g, q, j] = r[-1], cc[-1]
+            seen.append(r * cols + cc)
+        cells = np.unique(np.concatenate(seen)) if seen else np.zeros(0, np.int64)
+        counts[g, q] = np.bincount(S.reshape(-1)[cells], minlength=3)[:3]
+        score[g, q] = counts[g, q, 0]
+    best = score.argmax(1).astype(np.int32) if G else np.zeros(0, np.int32)  # the first of the largest
+    return {"counts": counts, "end_cells": end_cells, "status": status, "best": best,
+            "best_score": score[np.arange(G), best] if G else np.zeros(0, np.int32)}
+
+
+def view_ranges(map, poses, end_cells):
+    """float64, the shape of end_cells without its last axis: the virtual range scan of a view - per ray the metres from the centre of
+    the origin's cell (poses float64 [..., 4], the candidates of the view) to the centre of its end cell (end_cells [..., n_rays, 2],
+    occupancy_view's), sqrt(dx dx + dy dy) over occupancy_map_centres; NaN for an invalid ray."""
+    w = occupancy_map_words(map)
+    E = np.asarray(end_cells).astype(np.int64)
+    origin = occupancy_cells_of(w, np.asarray(poses, np.float64)[..., :2]).astype(np.int64)[..., None, :]
+    Xw, Yw = occupancy_map_centres(w)
+    on = (E[..., 0] >= 0) & (origin[..., 0] >= 0)
+    dx = Xw[np.where(on, E[..., 0], 0)] - Xw[np.where(on, origin[..., 0], 0)]
+    dy = Yw[np.where(on, E[..., 1], 0)] - Yw[np.where(on, origin[..., 1], 0)]
+    return np.where(on, np.sqrt(dx * dx + dy * dy), np.nan)
+
+
+def view_lines(poses_xyyaw, counts, best, best_score):
+    """What --view prints: per frontier one line with its best arrival heading in degrees and the distinct cells seen from there -
+    poses_xyyaw float64 [n, 3] (the best pose per frontier), counts [n, P, 3], best and best_score [n] (occupancy_view's)."""
+    X, C, B, Sc = np.asarray(poses_xyyaw, np.float64), np.asarray(counts), np.asarray(best), np.asarray(best_score)
+    lines = []
+    for k in range(len(X)):
+        if Sc[k] < 0:
+            lines.append("view %d: no valid pose" % k)
+        else:
+            u, f, o = (int(v) for v in C[k, int(B[k])])
+            lines.append("view %d: heading %r deg, sees %d unknown, %d free, %d occupied cells" % (k, float(np.degrees(X[k, 2])), u, f, o))
+    return lines
+
+
 class stereo_vision:
     def __init__(self, so_lib_path=DEFAULT_STEREO_VISION_SO_PATH, width=1242, height=375, defaultCalibFile=True, objectTracking=True,
                  graphics=False, display=False, scale=1, pc_extrapolation=1, YOLO_CFG="src/yolo/yolov4-tiny.cfg",
@@ -1875,9 +2044,28 @@ def main(argv=None):
                              "clusters of at least MIN_CELLS cells; prints one line per cluster (size, representative in metres, box) and "
                              "writes the label image next to FILE as <FILE without .png>.frontiers.png: 0, or 1 + (rank mod 255) on a "
                              "cluster's cells.  Without --goal the representatives are the goals of the cost-to-goal field and the route")
+    parser.add_argument("--view", type=str, default="", metavar="FOV_DEG,RANGE_M[,RAYS[,HEADINGS]]",
+                        help="with --frontiers: the best arrival heading per frontier - from each cluster's representative, HEADINGS yaws "
+                             "(default 16) of a fan of RAYS rays (default 128) over FOV_DEG degrees that reach RANGE_M metres are cast "
+                             "through the final map; prints per frontier the heading in degrees that sees the most undecided cells and "
+                             "the distinct unknown, free and occupied cells seen from there")
     args = parser.parse_args(argv)
     args.match_window = None
     args.goal_xy = None
+    args.view_spec = None
+    if args.view:
+        if not args.frontiers:
+            parser.error("--view needs --frontiers")
+        try:
+            words = args.view.split(",")
+            fov_deg, range_m = float(words[0]), float(words[1])
+            rays, headings = (int(words[2]) if len(words) > 2 else 128), (int(words[3]) if len(words) > 3 else 16)
+            if len(words) > 4 or headings < 1 or headings > VIEW_POSES_MAX:
+                raise ValueError
+            view_rays(np.radians(fov_deg), rays, range_m, CLI_TOP_VIEW["scale"])
+        except (ValueError, IndexError):
+            parser.error("--view: FOV_DEG in (0, 360], RANGE_M > 0 of at most 253 cells, RAYS in 1 .. 1024, HEADINGS >= 1, got %r" % (args.view,))
+        args.view_spec = (np.radians(fov_deg), range_m, rays, headings)
     if args.frontiers:
         if not (args.occupancy_map and args.poses and args.clearance):
             parser.error("--frontiers needs --occupancy-map, --poses and --clearance")
@@ -2092,6 +2280,10 @@ def _run_batched(args, ldir, rdir, files):
                 print("".join(line + "\n" for line in frontier_lines(world.words, clusters, found.info.cpu().numpy())), end="")
                 _write_png(os.path.splitext(args.occupancy_map)[0] + ".frontiers.png", frontier_png(found.label.cpu().numpy(), clusters))
                 goals = world.frontier_goals(found)
+                if args.view_spec is not None:
+                    fov, range_m, rays, headings = args.view_spec
+                    arrive, seen = world.frontier_views(found, headings=headings, fov=fov, range_m=range_m, n_rays=rays)
+                    print("".join(line + "\n" for line in view_lines(arrive, seen.counts.cpu().numpy(), seen.best.cpu().numpy(), seen.best_score.cpu().numpy())), end="")
                 if field is None and len(goals):
                     field = world.cost_to_goal(goals, args.clearance)
             if field is not None:
