@@ -54,6 +54,10 @@
  *      nearest occupied (or never seen) cell, and a batched check of candidate paths' footprints against that field.
  *      stereo_vision.sv.occupancy_clearance and clearance_paths state the definitions in numpy.
  *
+ *  (Q) Behind (I) and (F): a world-fixed voxel map (sv_voxel_map_*) - the voxel rows or the compact clouds of the frames of a drive, moved
+ *      into the world by one pose per frame and accumulated per cubic cell in a table that persists from call to call: one coloured 3-D
+ *      model of what the drive has seen.  stereo_vision.sv.voxel_map_insert and voxel_map_rows state the definition in numpy.
+ *
  * All sv_* functions return SV_OK (0) or a negative sv_status; sv_last_error() gives the text.
  * Nothing in this library calls exit().
  */
@@ -1168,6 +1172,80 @@ int sv_view_device(const int16_t *logodds, const int32_t *last_seen, const sv_oc
  * alone and 2 leaves the best out.  The results of a whole call do not depend on the variant.  Returns SV_OK, or SV_ERR_ARG for another
  * variant or stages outside 1..3. */
 int sv_debug_view(int variant, int stages);
+
+/* ---- (Q) a world-fixed voxel map: per-frame clouds of (I) or (F) + a pose per frame -> integer sums per world cell -> one row per voxel ---- */
+
+/* (I) gives the occupied cells of one pair, and its table is cleared on every call; this group keeps a table across calls and reads it out.
+ * Doubles place a row in the world; from there on everything is integers, and the map's content is bitwise reproducible whatever order
+ * the lanes take.  stereo_vision.sv.voxel_map_insert / voxel_map_rows restate it in numpy.
+ *
+ *   world      Pw[k] = ((R[k][0] x + R[k][1] y) + R[k][2] z) + t[k] in double, every product and sum rounded on its own; an f32 row is
+ *              widened first.  A pose is 12 doubles: R row-major, then t (stereo_vision.sv.voxel_map_pose).
+ *   rows       frame b contributes its first min(counts[b], cap) rows, none for counts[b] <= 0; a row's weight w is n[b][i], or 1
+ *   dropped    a row with w <= 0, or for which lo < Pw < hi does not hold strictly on every axis (NaN and inf never pass)
+ *   cell       (I)'s rule per axis with t = (Pw - lo) / size: c = min((int64)t, cells - 1), u = min((int64)((t - c) * 65536), 65535),
+ *              cells = max(1, ceil((hi - lo) / size)) <= 2^20; key = c_x | c_y << 20 | c_z << 40
+ *   voxel      a kept row adds n += w, S[k] += w u[k], C[j] += w colour[j], m += 1, first_seq = min(., seq0 + b), last_seq = max(., seq0 + b):
+ *              64-bit integer sums.  Contract: the total weight of a voxel stays below 2^47, sequence numbers in 0 .. 2^31 - 2.
+ *   row        xyz = lo + (c + (S + 0.5 n) / (65536 n)) * size in double, as written; colour = (2 C + n) / (2 n), integer division
+ *
+ * The map is one device buffer of sv_voxel_map_bytes(capacity) bytes, 16-byte aligned:
+ *   bytes 0 .. 31          the head: uint32 claimed voxels, uint32 overflowed (sticky), uint64 dropped rows, 16 spare bytes
+ *   then slots * 88 bytes  the open-addressing table, slots = sv_voxel_map_slots(capacity); an entry is eleven 64-bit words:
+ *                          key (all ones: empty) | n | S[3] | C[4] | m | first_seq (low half), last_seq (high half)
+ *   then slots / 256 * 4   int32 scratch of the read-out
+ * Where a voxel's entry lies depends on the schedule of the inserts; no value in it does.  After an overflow - more than `capacity`
+ * voxels claimed - the content is undefined until the map is cleared; every call still ends and stays inside the buffer. */
+typedef struct sv_voxel_map_spec {
+    double lo[3], hi[3]; /* the map's box, metres, world axes: finite, lo < hi */
+    double size;         /* edge of a cell, finite and > 0; at most 2^20 cells per axis */
+    int32_t capacity;    /* voxels the map may hold, 1 .. 2^26 */
+    int32_t reserved[7]; /* must be 0 */
+} sv_voxel_map_spec;
+
+/* Host only, callable without a device.  The entries of the table for `capacity`: the power of two >= 2 * max(capacity, 512), (I)'s rule;
+ * -1 for a capacity outside 1 .. 2^26. */
+int64_t sv_voxel_map_slots(int capacity);
+/* Host only: the bytes of the map's buffer; SIZE_MAX for a capacity outside 1 .. 2^26. */
+size_t sv_voxel_map_bytes(int capacity);
+/* Host only: the slot at which the probing for `key` starts in a table of `slots` entries (a power of two in 2 .. 2^32), (key *
+ * 0x9E3779B97F4A7C15 mod 2^64) >> (64 - log2 slots); -1 for other slots.  Tests build colliding keys with it. */
+int64_t sv_voxel_map_slot_of(int64_t key, int64_t slots);
+/* Enqueues one kernel on `stream` (a hipStream_t, NULL = the default stream) that empties the map: head zero, every key empty.  A new
+ * buffer must be cleared before its first use.  Returns SV_OK, SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued - for a bad spec (NULL, a
+ * reserved word not 0, lo / hi / size not finite, lo >= hi, size <= 0, more than 2^20 cells on an axis, capacity outside 1 .. 2^26) or a
+ * map that is NULL, not 16-byte aligned or smaller than sv_voxel_map_bytes(capacity). */
+int sv_voxel_map_clear_device(void *map, size_t map_bytes, const sv_voxel_map_spec *spec, void *stream);
+/* Enqueues one kernel on `stream` - a lane per input row - and does not wait for it: nothing is allocated and no host synchronisation is made.
+ *   xyz          : float (SV_CLOUD_F32) or double (SV_CLOUD_F64) [batch][cap][3] device - (I)'s or (F)'s rows
+ *   color        : uint8 [batch][cap][4] device, 4-byte aligned, or NULL (no colour is added)
+ *   n            : int32 [batch][cap] device - (I)'s n - or NULL (every weight 1)
+ *   counts       : int32 [batch] device - (I)'s or (F)'s counts, read on the device
+ *   poses        : double [batch][12] device, read on the device
+ *   seq0         : the sequence number of frame 0; seq0 >= 0 and seq0 + batch <= 2^31 - 1
+ * Returns SV_OK, SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued, the map untouched, the text in sv_last_error(NULL) - for: what the clear
+ * entry refuses; another dtype; batch outside 0..65535; cap < 0; bad sequence numbers; with batch > 0 a NULL counts or poses, and with
+ * cap > 0 as well a NULL xyz; xyz not aligned to its element, color, n or counts not 4-byte, poses not 8-byte aligned.  batch == 0 or cap
+ * == 0: nothing to do. */
+int sv_voxel_map_insert_device(void *map, size_t map_bytes, const sv_voxel_map_spec *spec, const void *xyz, int dtype, const uint8_t *color, const int32_t *n,
+                               const int32_t *counts, const double *poses, int batch, int cap, int seq0, void *stream);
+/* Enqueues three kernels on `stream` - the qualifying slots per tile of 256, their prefix sum, the rows - and does not wait: the voxels with
+ * n >= min_n, m >= min_rows and last_seq >= since, in the order of their slots, which depends on the schedule of the inserts (sort by key
+ * for a canonical order).  Uses the scratch at the end of the map's buffer: two read-outs of one map must not run at the same time.
+ *   xyz          : float or double (dtype) [out_capacity][3]; key : int64 [out_capacity] - required with out_capacity > 0
+ *   color        : uint8 [out_capacity][4], 4-byte aligned; cell : int32 [out_capacity][3]; n, m : int64 [out_capacity]; first_seq,
+ *                  last_seq : int32 [out_capacity] - each may be NULL
+ *   count        : int32 [1]: the qualifying voxels, NOT capped by out_capacity - the rows are complete only while count <= out_capacity -,
+ *                  or -1 for an overflowed map (no row is written)
+ * All device memory.  Returns SV_OK, SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued, the outputs untouched - for: what the clear entry
+ * refuses; another dtype; out_capacity < 0; a NULL count; with out_capacity > 0 a NULL xyz or key; a misaligned output. */
+int sv_voxel_map_rows_device(void *map, size_t map_bytes, const sv_voxel_map_spec *spec, int64_t min_n, int64_t min_rows, int since, int dtype, int out_capacity,
+                             void *xyz, uint8_t *color, int32_t *cell, int64_t *n, int64_t *m, int32_t *first_seq, int32_t *last_seq, int64_t *key, int32_t *count,
+                             void *stream);
+/* Test and measurement hook for sv_voxel_map_insert_device, process-wide: combine 1 (the default) merges the runs of equal cells of a
+ * wavefront into one table update each, 0 issues one update per kept row.  counters_device != NULL: two device uint64 that receive the
+ * table updates and the atomic instructions they issued, added up over the calls.  The map's content does not depend on it. */
+int sv_debug_voxel_map(int combine, unsigned long long *counters_device);
 
 /* ---- (A) the reference's exported symbols ------------------------------------------------------------- */
 

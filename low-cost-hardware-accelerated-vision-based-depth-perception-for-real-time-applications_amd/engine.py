@@ -523,13 +523,19 @@ class SvOccupancyMapSpec(ctypes.Structure):
                 ("l_occ", ctypes.c_int32), ("l_free", ctypes.c_int32), ("l_min", ctypes.c_int32), ("l_max", ctypes.c_int32), ("reserved", ctypes.c_int32 * 7)]
 
 
+class SvVoxelMapSpec(ctypes.Structure):
+    """sv_voxel_map_spec of include/stereo_vision_hip.h."""
+    _fields_ = [("lo", ctypes.c_double * 3), ("hi", ctypes.c_double * 3), ("size", ctypes.c_double), ("capacity", ctypes.c_int32),
+                ("reserved", ctypes.c_int32 * 7)]
+
+
 def _signatures():
-    """The table below: per stage group of the C API, (D) to (P), its functions and per function (restype, argtypes), parameter by
+    """The table below: per stage group of the C API, (D) to (Q), its functions and per function (restype, argtypes), parameter by
     parameter as include/stereo_vision_hip.h declares them - tests/test_stage_signatures.py holds the two against each other."""
     P = ctypes.POINTER
     vp, ci, sz, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_int64
     tv, bx, cl, vx, gr, sx = P(SvTopViewSpec), P(SvBoxSpec), P(SvCloudSpec), P(SvVoxelSpec), P(SvGroundSpec), P(SvStixelSpec)
-    oc, om = P(SvOccupancySpec), P(SvOccupancyMapSpec)
+    oc, om, vm = P(SvOccupancySpec), P(SvOccupancyMapSpec), P(SvVoxelMapSpec)
     return {
         "top_view": {  # (D)
             "sv_top_view_dims": (ci, [tv, P(ci), P(ci)]),
@@ -598,6 +604,15 @@ def _signatures():
             "sv_view_workspace": (ci, [ci, ci, P(sz)]),
             "sv_view_device": (ci, [vp, vp, om, vp, ci, ci, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, sz, vp]),
             "sv_debug_view": (ci, [ci, ci]),
+        },
+        "voxel_map": {  # (Q)
+            "sv_voxel_map_slots": (i64, [ci]),
+            "sv_voxel_map_bytes": (sz, [ci]),
+            "sv_voxel_map_slot_of": (i64, [i64, i64]),
+            "sv_voxel_map_clear_device": (ci, [vp, sz, vm, vp]),
+            "sv_voxel_map_insert_device": (ci, [vp, sz, vm, vp, ci, vp, vp, vp, vp, ci, ci, ci, vp]),
+            "sv_voxel_map_rows_device": (ci, [vp, sz, vm, i64, i64, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+            "sv_debug_voxel_map": (ci, [ci, vp]),
         },
     }
 
@@ -1794,6 +1809,176 @@ def debug_view(variant=0, stages=3):
     """sv_debug_view: the LDS window of occupancy_view's workgroups (0: sized by the call's reach; 1: always 509 cells a side) and the
     kernels a call enqueues (3: all; 1: the state plane alone; 2: without the best).  Process-wide; a test and measurement hook."""
     return int(view_lib().sv_debug_view(int(variant), int(stages)))
+
+
+def voxel_map_lib():
+    """The library with the signatures of group (Q) declared."""
+    return _bind("voxel_map")
+
+
+VOXEL_MAP_ROW_FIELDS = ("xyz", "color", "cell", "n", "m", "first_seq", "last_seq", "key")  # of voxel_map_rows' dict, besides count
+
+
+def voxel_map_spec(params):
+    """-> SvVoxelMapSpec from a dict with lo, hi, size and capacity (stereo_vision.sv.voxel_map_params', whose checks are made again:
+    ValueError for a bad word)."""
+    from .stereo_vision.sv import voxel_map_params
+    w = voxel_map_params(params["lo"], params["hi"], params["size"], params["capacity"])
+    spec = SvVoxelMapSpec()
+    spec.lo[:] = w["lo"]
+    spec.hi[:] = w["hi"]
+    spec.size, spec.capacity = w["size"], w["capacity"]
+    return spec
+
+
+def voxel_map_slot_of(key, slots):
+    """sv_voxel_map_slot_of for one key: the slot at which the table's probing starts.  Needs no device."""
+    h = int(voxel_map_lib().sv_voxel_map_slot_of(int(key), int(slots)))
+    if h < 0:
+        raise ValueError("slots must be a power of two in 2 .. 2^32, got %r" % (slots,))
+    return h
+
+
+def _voxel_map_buffer(buf, spec):
+    """The map's buffer, checked: a contiguous CUDA int64 tensor of at least sv_voxel_map_bytes(capacity) bytes -> its bytes."""
+    import torch
+    need = voxel_map_lib().sv_voxel_map_bytes(spec.capacity)
+    if not (isinstance(buf, torch.Tensor) and buf.is_cuda and buf.dtype == torch.int64 and buf.is_contiguous() and buf.numel() * 8 >= need):
+        raise ValueError("the map must be a contiguous CUDA int64 tensor of at least %d bytes (voxel_map_new)" % need)
+    return buf.numel() * 8
+
+
+def voxel_map_new(params, device="cuda"):
+    """-> the buffer of an empty voxel map for `params` on `device`: an int64 tensor of sv_voxel_map_bytes(capacity) bytes - a head of 32
+    bytes, sv_voxel_map_slots(capacity) entries of 88 bytes, the read-out's scratch -, cleared on torch's current stream."""
+    import torch
+    spec = voxel_map_spec(params)
+    nbytes = voxel_map_lib().sv_voxel_map_bytes(spec.capacity)
+    buf = torch.empty((nbytes // 8,), dtype=torch.int64, device=device)  # torch's allocations start on 512 bytes
+    return voxel_map_clear(buf, params)
+
+
+def voxel_map_clear(buf, params):
+    """Empties the map in `buf` (sv_voxel_map_clear_device) on torch's current stream; -> buf."""
+    import torch
+    spec = voxel_map_spec(params)
+    nbytes = _voxel_map_buffer(buf, spec)
+    with torch.cuda.device(buf.device):
+        rc = voxel_map_lib().sv_voxel_map_clear_device(buf.data_ptr(), nbytes, ctypes.byref(spec), torch.cuda.current_stream(buf.device).cuda_stream)
+    _check(rc, "sv_voxel_map_clear_device")
+    return buf
+
+
+def voxel_map_poses(poses, dev):
+    """The poses of voxel_map_insert as a contiguous float64 [B,12] tensor on dev: [B,12] (R row-major, then t) as they are, the occupancy
+    map's [B,4] = (tx, ty, c, s) expanded as stereo_vision.sv.voxel_map_pose does with z = 0; numpy arrays are uploaded once."""
+    import torch
+    if not isinstance(poses, torch.Tensor):
+        from .stereo_vision.sv import voxel_map_pose_words
+        return torch.from_numpy(voxel_map_pose_words(poses)).to(dev)
+    if poses.device != dev or poses.dtype != torch.float64 or poses.dim() != 2 or poses.shape[1] not in (4, 12):
+        raise ValueError("poses must be float64 [B,12] or [B,4] on the device (%s) of the map" % (dev,))
+    if poses.shape[1] == 12:
+        return poses.contiguous()
+    tx, ty, c, s = poses.unbind(1)
+    zero, one = torch.zeros_like(tx), torch.ones_like(tx)
+    return torch.stack([c, -s, zero, s, c, zero, zero, zero, one, tx, ty, zero], 1).contiguous()
+
+
+def voxel_map_insert(buf, params, xyz, color, n, counts, poses, seq0=0):
+    """Adds B frames of rows to the voxel map in `buf` - the definition of stereo_vision.sv.voxel_map_insert on the GPU, one kernel: xyz
+    CUDA float32 or float64 [B,cap,3], color uint8 [B,cap,4] or None, n int32 [B,cap] or None, counts int32 [B] - what
+    voxel_cloud_from_disparity and compact_cloud_from_disparity return, on the map's device -, poses float64 [B,12] or [B,4] (numpy, or a
+    tensor on the device), seq0 the sequence number of frame 0.  counts and poses are read on the device.  Enqueued on torch's current
+    stream, not waited for; -> buf."""
+    import torch
+    spec = voxel_map_spec(params)
+    nbytes = _voxel_map_buffer(buf, spec)
+    dev = buf.device
+    if not (isinstance(xyz, torch.Tensor) and xyz.device == dev and xyz.dtype in (torch.float32, torch.float64) and xyz.dim() == 3 and xyz.shape[2] == 3):
+        raise ValueError("xyz must be a float32 or float64 tensor [B,cap,3] on the map's device")
+    B, cap = int(xyz.shape[0]), int(xyz.shape[1])
+    for t, name, dtype, shape in ((color, "color", torch.uint8, (B, cap, 4)), (n, "n", torch.int32, (B, cap)), (counts, "counts", torch.int32, (B,))):
+        if t is None and name != "counts":
+            continue
+        if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dtype and tuple(t.shape) == shape):
+            raise ValueError("%s must be a %s tensor %s on the map's device" % (name, str(dtype).replace("torch.", ""), list(shape)))
+    if B > 65535:
+        raise ValueError("at most 65535 frames per call, got %d" % B)
+    if isinstance(seq0, bool) or int(seq0) != seq0 or seq0 < 0 or seq0 + B > 2 ** 31 - 1:
+        raise ValueError("the sequence numbers seq0 .. seq0 + B - 1 must stay in 0 .. 2^31 - 2, got seq0 = %r" % (seq0,))
+    p = voxel_map_poses(poses, dev)
+    if p.shape[0] != B:
+        raise ValueError("poses must hold one pose per frame: %d, got %d" % (B, p.shape[0]))
+    xyz, counts = xyz.contiguous(), counts.contiguous()
+    color = None if color is None else color.contiguous()
+    if color is not None and color.data_ptr() % 4:  # the C entry moves a colour as one dword
+        color = color.clone()
+    n = None if n is None else n.contiguous()
+    with torch.cuda.device(dev):
+        rc = voxel_map_lib().sv_voxel_map_insert_device(buf.data_ptr(), nbytes, ctypes.byref(spec), _ptr(xyz), 0 if xyz.dtype == torch.float32 else 1, _ptr(color),
+                                                        _ptr(n), _ptr(counts), _ptr(p), B, cap, int(seq0), torch.cuda.current_stream(dev).cuda_stream)
+    _check(rc, "sv_voxel_map_insert_device")
+    return buf
+
+
+def voxel_map_rows(buf, params, min_n=1, min_rows=1, since=0, dtype="f32", capacity=None, sort=True):
+    """The voxels of the map in `buf` with n >= min_n, m >= min_rows and last_seq >= since (sv_voxel_map_rows_device: three kernels) as a
+    dict of tensors on the map's device - xyz float32 or float64 ("f64") [V,3], color uint8 [V,4], cell int32 [V,3], n int64 [V], m
+    int64 [V], first_seq int32 [V], last_seq int32 [V], key int64 [V] - and count.  capacity: the rows of the output tensors (None: the
+    map's capacity, which always suffices).
+    sort=True: count is read back (the one synchronisation), the rows are cut at it and ordered by key with torch.sort and a gather: the
+    result equals stereo_vision.sv.voxel_map_rows' in shape, dtype and bits; count is an int, -1 (and no rows) for an overflowed map;
+    StereoError where count exceeds `capacity`.
+    sort=False: what the C entry wrote, not waited for: tensors of `capacity` rows in slot order - which depends on the schedule of the
+    inserts - of which the first count are rows (all of them only while count <= capacity), and count an int32 tensor [1]."""
+    import torch
+    from .stereo_vision.sv import CLOUD_DTYPES
+    spec = voxel_map_spec(params)
+    nbytes = _voxel_map_buffer(buf, spec)
+    if dtype not in CLOUD_DTYPES:
+        raise ValueError("dtype must be one of %s, got %r" % (sorted(CLOUD_DTYPES), dtype))
+    for v, what in ((min_n, "min_n"), (min_rows, "min_rows")):
+        if isinstance(v, bool) or int(v) != v or not -2 ** 63 <= v < 2 ** 63:
+            raise ValueError("%s must be an integer, got %r" % (what, v))
+    if isinstance(since, bool) or int(since) != since or not -2 ** 31 <= since < 2 ** 31:
+        raise ValueError("since must be a 32-bit integer, got %r" % (since,))
+    cap = spec.capacity if capacity is None else capacity
+    if isinstance(cap, bool) or int(cap) != cap or not 0 <= cap < 2 ** 31:
+        raise ValueError("capacity must be an integer in 0 .. 2^31 - 1, got %r" % (capacity,))
+    cap, dev = int(cap), buf.device
+    shapes = {"xyz": ((cap, 3), torch.float32 if dtype == "f32" else torch.float64), "color": ((cap, 4), torch.uint8), "cell": ((cap, 3), torch.int32),
+              "n": ((cap,), torch.int64), "m": ((cap,), torch.int64), "first_seq": ((cap,), torch.int32), "last_seq": ((cap,), torch.int32),
+              "key": ((cap,), torch.int64)}
+    out = {k: torch.empty(shape, dtype=dt, device=dev) for k, (shape, dt) in shapes.items()}
+    count = torch.empty((1,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = voxel_map_lib().sv_voxel_map_rows_device(buf.data_ptr(), nbytes, ctypes.byref(spec), int(min_n), int(min_rows), int(since), CLOUD_DTYPES[dtype], cap,
+                                                      *[_ptr(out[k]) for k in VOXEL_MAP_ROW_FIELDS], count.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    _check(rc, "sv_voxel_map_rows_device")
+    if not sort:
+        out["count"] = count
+        return out
+    V = int(count.item())
+    if V > cap:
+        raise StereoError("%d voxels qualify but the output holds %d rows: raise the capacity" % (V, cap))
+    order = torch.sort(out["key"][:max(V, 0)]).indices
+    out = {k: t[:max(V, 0)][order] for k, t in out.items()}
+    out["count"] = V
+    return out
+
+
+def voxel_map_stats(buf):
+    """(claimed voxels, dropped rows, overflowed) of the map in `buf`: its head, read back - this synchronises."""
+    head = buf[:2].cpu().numpy()
+    words = head.view(np.uint32)
+    return int(words[0]), int(head.view(np.uint64)[1]), bool(words[1])
+
+
+def debug_voxel_map(combine=True, counters=None):
+    """sv_debug_voxel_map: the wavefront merge of the insert kernel on / off and a CUDA int64 [2] tensor (or None) that receives the table
+    updates and the atomic instructions they issued.  Process-wide; a test and measurement hook."""
+    return int(voxel_map_lib().sv_debug_voxel_map(1 if combine else 0, None if counters is None else counters.data_ptr()))
 
 
 def host_support_filter(params, dcan, width, height, threads=0, lattice=False):

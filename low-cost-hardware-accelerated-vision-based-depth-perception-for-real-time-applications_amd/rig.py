@@ -25,6 +25,9 @@ disparity, the driver's 8-bit map and point clouds out.
     world.state()                                                    # u8 [2000,2000] (0 unknown, 1 free, 2 occupied) by thresholds on log-odds
     xyyaw, m = world.localize(occ, guess, (0.5, 0.5, 0.04), (7, 7, 5))  # per frame the best pose of a 245-pose window around the odometry's
                                                                      # guess [B,3]; m.sums / m.counts / m.best / m.best_score on the device
+    model = rig.voxel_map((-50, -100, -2), (150, 100, 4), 0.1, 1 << 21)  # a world-fixed voxel map: one coloured 3-D model of a drive
+    model.update(xyz, color, n, counts, voxel_map_pose(x, y, yaw))   # voxel_clouds' (or compact_clouds') rows fused along the same odometry
+    model.write_ply("drive.ply", min_rows=2)                         # the voxels that at least two rows fell into, ordered by cell
 
 Frames are [B,Hs,Ws,C] (C = 4, 3, 3 for "bgra", "bgr", "rgb") or [B,Hs,Ws] for "gray"; one frame without B is accepted.
 Frames of another size than the rig's are resized to it.  CUDA tensors are processed on torch's current stream and CUDA
@@ -37,7 +40,8 @@ import numpy as np
 
 from .engine import (SvParams, StereoEngine, StereoError, box_positions_from_disparity, box_spec, cloud_spec, compact_cloud_from_disparity,
                      ground_from_disparity, ground_spec, lib, occupancy_from_disparity, occupancy_fuse, occupancy_match, occupancy_clearance, clearance_paths, cost_cells, cost_routes, frontier_cells, frontier_clusters, occupancy_cost_to_goal, occupancy_view, occupancy_spec, pinned_array, reproject, split_clouds, stixel_spec, stixels_from_disparity,
-                     top_view_from_disparity, top_view_spec, split_voxel_clouds, voxel_cloud_from_disparity, voxel_spec)
+                     top_view_from_disparity, top_view_spec, split_voxel_clouds, voxel_cloud_from_disparity, voxel_map_clear, voxel_map_insert, voxel_map_new,
+                     voxel_map_rows, voxel_map_stats, voxel_spec)
 from .stereo_vision.sv import CAMERA_TO_VEHICLE, DEFAULT_CALIBRATION  # noqa: F401 (CAMERA_TO_VEHICLE: re-exported for top_view)
 from .stereo_vision.sv import free_space_points, ground_pose
 from .stereo_vision import sv as _sv
@@ -416,6 +420,82 @@ class StereoRig:
         """-> OccupancyMap: a world-fixed log-odds map on the rig's device, to be fed with occupancy()'s results and the poses of the
         caller's odometry."""
         return OccupancyMap(x_range, y_range, scale, device=self.device, **log_odds_words)
+
+
+    def voxel_map(self, lo, hi, size, capacity):
+        """-> VoxelMap: a world-fixed voxel map on the rig's device, to be fed with voxel_clouds' or compact_clouds' rows and the poses of
+        the caller's odometry."""
+        return VoxelMap(lo, hi, size, capacity, device=self.device)
+
+
+class VoxelMap:
+    """A world-fixed voxel map (include/stereo_vision_hip.h (Q), stereo_vision.sv.voxel_map_insert / voxel_map_rows): per cubic cell of
+    edge `size` of the box lo .. hi (metres, world axes) the integer sums of the rows that fell into it, for at most `capacity` voxels.
+    device: a CUDA device ("cuda", "cuda:1", an index) - engine.voxel_map_insert, one kernel per update, and engine.voxel_map_rows - or
+    "cpu" - the numpy definition on CPU tensors or numpy arrays, the same methods and the same bits.  params is the map's
+    sv_voxel_map_spec as a dict, seq the number of frames added so far: the sequence number the next frame carries."""
+
+    def __init__(self, lo, hi, size, capacity, device="cuda"):
+        import torch
+        self.params = _sv.voxel_map_params(lo, hi, size, capacity)
+        self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.seq = 0
+        if self.device.type == "cuda":
+            self.buffer, self._state = voxel_map_new(self.params, self.device), None
+        else:
+            self.buffer, self._state = None, _sv.voxel_map_state(self.params)
+
+    def reset(self):
+        """An empty map: no voxel, dropped 0, not overflowed, seq 0."""
+        if self._state is None:
+            voxel_map_clear(self.buffer, self.params)
+        else:
+            self._state = _sv.voxel_map_state(self.params)
+        self.seq = 0
+
+    def update(self, xyz, color, n, counts, poses):
+        """Adds B frames: xyz float32 or float64 [B,cap,3], color uint8 [B,cap,4] or None, n int32 [B,cap] or None (every weight 1), counts
+        int32 [B] - StereoRig.voxel_clouds' or compact_clouds' tensors on the map's device -, poses float64 [B,12]
+        (stereo_vision.sv.voxel_map_pose) or the occupancy map's [B,4] (occupancy_pose), numpy or a tensor.  The frames are numbered on
+        from the last call.  Not waited for."""
+        import torch
+        if self._state is None:
+            voxel_map_insert(self.buffer, self.params, xyz, color, n, counts, poses, self.seq)
+        else:
+            host = [None if t is None else (t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)) for t in (xyz, color, n, counts, poses)]
+            host[4] = _sv.voxel_map_pose_words(host[4])
+            _sv.voxel_map_insert(self._state, *host, seq0=self.seq)
+        self.seq += int(xyz.shape[0])
+
+    def rows(self, min_n=1, min_rows=1, since=0, dtype="f32"):
+        """The voxels with n >= min_n, m >= min_rows rows and last_seq >= since, in ascending key, as a dict of tensors on the map's
+        device: xyz [V,3], color uint8 [V,4], cell int32 [V,3], n, m int64 [V], first_seq, last_seq int32 [V], key int64 [V], and count
+        (an int; -1 and no rows for an overflowed map).  Reads the count back."""
+        import torch
+        if self._state is None:
+            return voxel_map_rows(self.buffer, self.params, min_n, min_rows, since, dtype, sort=True)
+        res = _sv.voxel_map_rows(self._state, min_n, min_rows, since, dtype)
+        return {k: v if k == "count" else torch.from_numpy(v) for k, v in res.items()}
+
+    def stats(self):
+        """{"claimed", "dropped", "overflowed"}: the voxels the map holds, the rows it dropped, whether it ever held more than its
+        capacity.  The one read-back of the map's head."""
+        if self._state is None:
+            claimed, dropped, overflowed = voxel_map_stats(self.buffer)
+        else:
+            claimed, dropped, overflowed = len(self._state["key"]), self._state["dropped"], self._state["overflowed"]
+        return {"claimed": int(claimed), "dropped": int(dropped), "overflowed": bool(overflowed)}
+
+    def write_ply(self, path, min_n=1, min_rows=1, since=0):
+        """rows(...) as a binary PLY of coloured points (stereo_vision.sv.write_ply); -> the number of points.  RuntimeError for an
+        overflowed map."""
+        res = self.rows(min_n, min_rows, since)
+        if res["count"] < 0:
+            raise RuntimeError("the voxel map overflowed its capacity of %d voxels: raise it" % self.params["capacity"])
+        _sv.write_ply(path, res["xyz"].cpu().numpy(), res["color"].cpu().numpy())
+        return res["count"]
 
 
 class OccupancyMap:

@@ -84,6 +84,12 @@ candidate poses (sv_view_* of include/stereo_vision_hip.h (P); engine.occupancy_
 GPU): rays cast through the map from each pose, the distinct cells they see counted by state - the unknown ones are what a trip there
 would uncover -, the last visible cell of every ray - a virtual range scan - and the best pose per group.  The trigonometry stays on
 the host; the walk is integers: bit for bit.  The reference has no counterpart.
+
+voxel_map_params, voxel_map_pose, voxel_map_state, voxel_map_insert, voxel_map_rows and voxel_map_slot_of are the definition of the
+world-fixed voxel map (sv_voxel_map_* of include/stereo_vision_hip.h (Q); engine.voxel_map_insert / voxel_map_rows and rig.VoxelMap on the
+GPU): voxel_cloud's or compact_cloud's rows of the frames of a drive, moved into the world by one pose per frame and accumulated per cubic
+cell - integer sums of weights, offsets and colours, the rows, the first and the last frame -, read out as one row per voxel in ascending
+key.  The reference shows its cloud frame by frame and keeps none.
 """
 import argparse
 import ctypes
@@ -475,6 +481,157 @@ def voxel_cloud(disp, Q, size, lo, hi, XR=None, XT=None, step=1, disparity="d1",
             color = ((2 * C + n[:, None]) // (2 * n[:, None])).astype(np.uint8)
         out.append((xyz.astype(np.float32) if dtype == "f32" else xyz, color, c[where].astype(np.int32), n.astype(np.int32), index[where].astype(np.int32), V))
     return out if batched else out[0]
+
+
+VOXEL_MAP_SEQ_MAX = 2 ** 31 - 2  # the largest sequence number of a frame
+
+
+def voxel_map_slots(capacity):
+    """Entries of the table of a voxel map of `capacity` voxels (sv_voxel_map_slots): voxel_table_slots' rule."""
+    return voxel_table_slots(capacity)
+
+
+def voxel_map_params(lo, hi, size, capacity):
+    """The words of a world-fixed voxel map (sv_voxel_map_spec) as a dict - lo, hi (tuples of 3 floats), size, capacity, and cells (3 ints)
+    = max(1, ceil((hi - lo) / size)) - after voxel_grid's checks (ValueError): lo / hi / size finite, lo < hi, size > 0, at most 2^20
+    cells per axis, capacity an integer in 1 .. 2^26."""
+    if capacity is None:
+        raise ValueError("a voxel map needs a capacity in 1 .. 2^26")
+    lo, hi, size, cells = voxel_grid(size, lo, hi, capacity=capacity)
+    return {"lo": tuple(lo.tolist()), "hi": tuple(hi.tolist()), "size": size, "capacity": int(capacity), "cells": tuple(int(c) for c in cells)}
+
+
+def voxel_map_pose(x, y, yaw, z=0.0):
+    """float64 [..., 12] = R row-major, then t: the pose of a frame whose vehicle axes stand at (x, y, z) in the world, turned by yaw about
+    the z axis - Pw = R Pf + t with R = [[c, -s, 0], [s, c, 0], [0, 0, 1]], c and s exactly occupancy_pose's, so the same odometry drives
+    both maps.  voxel_map_insert takes any rigid R | t in this layout as it is."""
+    p = occupancy_pose(x, y, yaw)
+    tx, ty, c, s = p[..., 0], p[..., 1], p[..., 2], p[..., 3]
+    z = np.broadcast_to(np.asarray(z, np.float64), tx.shape)
+    zero, one = np.zeros_like(tx), np.ones_like(tx)
+    return np.stack([c, -s, zero, s, c, zero, zero, zero, one, tx, ty, z], -1)
+
+
+def voxel_map_pose_words(poses):
+    """float64 [B,12] from [B,12] poses (as they are) or the occupancy map's [B,4] = (tx, ty, c, s) (expanded as voxel_map_pose does,
+    z = 0)."""
+    p = np.asarray(poses, np.float64)
+    if p.ndim == 1:
+        p = p[None]
+    if p.ndim != 2 or p.shape[1] not in (4, 12):
+        raise ValueError("poses must be [B,12] or [B,4], got shape %s" % (p.shape,))
+    if p.shape[1] == 12:
+        return np.ascontiguousarray(p)
+    zero, one = np.zeros(len(p)), np.ones(len(p))
+    return np.stack([p[:, 2], -p[:, 3], zero, p[:, 3], p[:, 2], zero, zero, zero, one, p[:, 0], p[:, 1], zero], -1)
+
+
+def voxel_map_slot_of(key, slots):
+    """The slot at which the table's probing for `key` starts (sv_voxel_map_slot_of): (key * 0x9E3779B97F4A7C15 mod 2^64) >> (64 - log2
+    slots), slots a power of two in 2 .. 2^32.  int64, of key's shape."""
+    if isinstance(slots, bool) or int(slots) != slots or not 2 <= slots <= 2 ** 32 or int(slots) & (int(slots) - 1):
+        raise ValueError("slots must be a power of two in 2 .. 2^32, got %r" % (slots,))
+    k = np.asarray(key, np.int64).astype(np.uint64)
+    with np.errstate(over="ignore"):
+        h = (k * np.uint64(0x9E3779B97F4A7C15)) >> np.uint64(64 - (int(slots).bit_length() - 1))
+    return h.astype(np.int64)
+
+
+def voxel_map_state(params):
+    """An empty map: params (voxel_map_params' dict, checked again), no voxel, dropped 0, not overflowed."""
+    w = voxel_map_params(params["lo"], params["hi"], params["size"], params["capacity"])
+    return {"params": w, "key": np.zeros(0, np.int64), "n": np.zeros(0, np.int64), "S": np.zeros((0, 3), np.int64), "C": np.zeros((0, 4), np.int64),
+            "m": np.zeros(0, np.int64), "first_seq": np.zeros(0, np.int64), "last_seq": np.zeros(0, np.int64), "dropped": 0, "overflowed": False}
+
+
+def voxel_map_insert(map_state, xyz, color, n, counts, poses, seq0=0):
+    """Adds B frames of rows to a world-fixed voxel map, the definition of include/stereo_vision_hip.h (Q) in numpy; map_state
+    (voxel_map_state's dict) is changed in place and returned.
+
+    xyz float32 or float64 [B,cap,3], color uint8 [B,cap,4] or None, n int32 [B,cap] or None (every weight 1), counts int32 [B] - what
+    voxel_cloud_from_disparity and compact_cloud_from_disparity return -, poses float64 [B,12] (voxel_map_pose's layout).  Frame b
+    contributes its first min(counts[b], cap) rows (none for counts[b] < 0).  A row (x, y, z), widened exactly to double, lies in the
+    world at Pw[k] = ((R[k,0] x + R[k,1] y) + R[k,2] z) + t[k], in double and in that order.  It is dropped - and counted in
+    map_state["dropped"] - when its weight w <= 0 or lo < Pw < hi does not hold strictly on every axis (NaN and inf never pass).  A kept
+    row lies per axis in the cell c = min(int(t), cells - 1), t = (Pw - lo) / size, at the offset u = min(int((t - c) * 65536), 65535),
+    and adds to the voxel of its cell n += w, S += w u, C += w colour, m += 1, first_seq = min(., seq0 + b), last_seq = max(., seq0 + b):
+    all integers, 64-bit sums.  Contract: the total weight of a voxel stays below 2^47, 0 <= seq0 and seq0 + B - 1 <= 2^31 - 2.  A map
+    that holds more than params["capacity"] voxels after the call is overflowed for good."""
+    w = map_state["params"]
+    lo, hi, size, cells = np.array(w["lo"]), np.array(w["hi"]), np.float64(w["size"]), np.array(w["cells"], np.int64)
+    xyz = np.asarray(xyz)
+    if xyz.dtype not in (np.float32, np.float64) or xyz.ndim != 3 or xyz.shape[2] != 3:
+        raise ValueError("xyz must be float32 or float64 [B,cap,3], got %s %s" % (xyz.dtype, xyz.shape))
+    B, cap = xyz.shape[:2]
+    counts = np.asarray(counts)
+    poses = np.asarray(poses, np.float64)
+    if counts.shape != (B,) or poses.shape != (B, 12):
+        raise ValueError("counts must be [B] and poses [B,12] for B = %d, got %s and %s" % (B, counts.shape, poses.shape))
+    if color is not None and (np.asarray(color).dtype != np.uint8 or np.asarray(color).shape != (B, cap, 4)):
+        raise ValueError("color must be uint8 [B,cap,4] or None")
+    if n is not None and np.asarray(n).shape != (B, cap):
+        raise ValueError("n must be [B,cap] or None")
+    if isinstance(seq0, bool) or int(seq0) != seq0 or seq0 < 0 or seq0 + B - 1 > VOXEL_MAP_SEQ_MAX:
+        raise ValueError("the sequence numbers seq0 .. seq0 + B - 1 must stay in 0 .. 2^31 - 2, got seq0 = %r" % (seq0,))
+    rows = np.arange(cap)[None, :] < np.minimum(counts.astype(np.int64), cap)[:, None]  # [B,cap]: the rows a frame contributes
+    R = poses[:, None, :]
+    with np.errstate(invalid="ignore", over="ignore"):  # rows beyond counts may hold anything
+        P = xyz.astype(np.float64)
+        x, y, z = P[..., 0], P[..., 1], P[..., 2]
+        Pw = np.stack([((R[..., 3 * k] * x + R[..., 3 * k + 1] * y) + R[..., 3 * k + 2] * z) + R[..., 9 + k] for k in range(3)], -1)
+        inside = ((lo < Pw) & (Pw < hi)).all(-1)
+    wt = np.ones((B, cap), np.int64) if n is None else np.asarray(n).astype(np.int64)
+    keep = rows & inside & (wt > 0)
+    map_state["dropped"] += int((rows & ~keep).sum())
+    b_of = np.broadcast_to(np.arange(B, dtype=np.int64)[:, None], (B, cap))[keep]
+    t = (Pw[keep] - lo) / size
+    c = np.minimum(t.astype(np.int64), cells - 1)
+    u = np.minimum(((t - c.astype(np.float64)) * 65536.0).astype(np.int64), 65535)
+    key = c[:, 0] | (c[:, 1] << 20) | (c[:, 2] << 40)
+    wk = wt[keep]
+    col = np.zeros((len(key), 4), np.int64) if color is None else np.asarray(color)[keep].astype(np.int64)
+    seq = int(seq0) + b_of
+    allkey = np.concatenate([map_state["key"], key])
+    ukey, inv = np.unique(allkey, return_inverse=True)
+    inv = inv.reshape(-1)
+    V = len(ukey)
+    acc = {"n": np.zeros(V, np.int64), "S": np.zeros((V, 3), np.int64), "C": np.zeros((V, 4), np.int64), "m": np.zeros(V, np.int64),
+           "first_seq": np.full(V, np.iinfo(np.int64).max), "last_seq": np.full(V, -1, np.int64)}
+    old, new = inv[:len(map_state["key"])], inv[len(map_state["key"]):]
+    for f in ("n", "S", "C", "m", "first_seq", "last_seq"):
+        acc[f][old] = map_state[f]
+    np.add.at(acc["n"], new, wk)
+    np.add.at(acc["S"], new, wk[:, None] * u)
+    np.add.at(acc["C"], new, wk[:, None] * col)
+    np.add.at(acc["m"], new, 1)
+    np.minimum.at(acc["first_seq"], new, seq)
+    np.maximum.at(acc["last_seq"], new, seq)
+    map_state.update(acc, key=ukey)
+    if V > w["capacity"]:
+        map_state["overflowed"] = True
+    return map_state
+
+
+def voxel_map_rows(map_state, min_n=1, min_rows=1, since=0, dtype="f32"):
+    """The voxels of a map with n >= min_n, m >= min_rows and last_seq >= since, in ascending key cx | cy << 20 | cz << 40, as a dict:
+    xyz [V,3] float32 or float64 ("f64") = lo + (c + (S + 0.5 n) / (65536 n)) * size in double, as written; color uint8 [V,4] =
+    (2 C + n) // (2 n); cell int32 [V,3]; n int64 [V]; m int64 [V]; first_seq, last_seq int32 [V]; key int64 [V]; count = V.  An
+    overflowed map reports count -1 and no rows."""
+    if dtype not in CLOUD_DTYPES:
+        raise ValueError("dtype must be one of %s, got %r" % (sorted(CLOUD_DTYPES), dtype))
+    w = map_state["params"]
+    sel = (map_state["n"] >= min_n) & (map_state["m"] >= min_rows) & (map_state["last_seq"] >= since)
+    if map_state["overflowed"]:
+        sel = np.zeros(0, bool)
+    key = map_state["key"][sel] if len(sel) else np.zeros(0, np.int64)
+    pick = (lambda f: map_state[f][sel]) if len(sel) else (lambda f: map_state[f][:0])
+    n, S, C = pick("n"), pick("S"), pick("C")
+    c = np.stack([key & 0xFFFFF, (key >> 20) & 0xFFFFF, (key >> 40) & 0xFFFFF], -1)
+    nf = n.astype(np.float64)[:, None]
+    xyz = np.array(w["lo"]) + (c.astype(np.float64) + (S.astype(np.float64) + 0.5 * nf) / (65536.0 * nf)) * np.float64(w["size"])
+    return {"xyz": xyz.astype(np.float32) if dtype == "f32" else xyz, "color": ((2 * C + n[:, None]) // (2 * n[:, None])).astype(np.uint8),
+            "cell": c.astype(np.int32), "n": n, "m": pick("m"), "first_seq": pick("first_seq").astype(np.int32), "last_seq": pick("last_seq").astype(np.int32),
+            "key": key, "count": -1 if map_state["overflowed"] else int(len(key))}
 
 
 GROUND_BINS_MIN, GROUND_BINS_MAX = 8, 4096
@@ -2012,6 +2169,10 @@ def main(argv=None):
     parser.add_argument("--voxel", type=float, default=0.0, metavar="METRES",
                         help="with --batch --ply: write the voxel-grid downsampled cloud instead - per occupied cube of this edge inside the "
                              "same crop one vertex, the centroid of its points with their mean colour")
+    parser.add_argument("--voxel-map", type=str, default="", metavar="FILE.ply",
+                        help="with --batch --ply --voxel --poses: fuse the frames' voxel clouds along the poses into one world-fixed voxel map "
+                             "of the same edge and write it as one PLY of the whole drive: per occupied cube the centroid and the mean "
+                             "colour of everything the drive saw in it, ordered by cell")
     parser.add_argument("--occupancy", type=str, default="", metavar="DIR",
                         help="with --batch: write each frame's occupancy grid as a PNG into DIR (0 unknown, 127 free, 255 occupied): ground "
                              "plane and obstacle labels from the float disparity, then per cell of the grid of --top-view (vehicle axes) the "
@@ -2022,7 +2183,7 @@ def main(argv=None):
                              "occupied; row 0 = the largest x, column 0 = the largest y); the map covers the trajectory's bounding box "
                              "plus the reach of a frame's grid")
     parser.add_argument("--poses", type=str, default="", metavar="FILE",
-                        help="for --occupancy-map: a text file with one line 'x y yaw' per frame - the vehicle in the world, metres and "
+                        help="for --occupancy-map and --voxel-map: a text file with one line 'x y yaw' per frame - the vehicle in the world, metres and "
                              "radians, yaw counter-clockwise")
     parser.add_argument("--match", type=str, default="", metavar="DX,DY,DYAW[,NX,NY,NYAW]",
                         help="with --occupancy-map and --poses: take the poses as guesses - frame 0 is fused where its line says; every later "
@@ -2096,8 +2257,12 @@ def main(argv=None):
             occupancy_pose_window(0.0, 0.0, 0.0, *args.match_window)
         except ValueError as e:
             parser.error("--match: %s" % e)
-    if bool(args.occupancy_map) != bool(args.poses):
+    if args.occupancy_map and not args.poses:
         parser.error("--occupancy-map and --poses go together")
+    if args.poses and not (args.occupancy_map or args.voxel_map):
+        parser.error("--poses needs --occupancy-map or --voxel-map")
+    if args.voxel_map and not (args.batch and args.ply and args.voxel and args.poses):
+        parser.error("--voxel-map needs --batch, --ply, --voxel and --poses")
     if args.occupancy_map and not args.batch:
         parser.error("--occupancy-map needs --batch")
     if args.voxel and not args.ply:
@@ -2136,6 +2301,13 @@ def main(argv=None):
     if args.occupancy:
         os.makedirs(args.occupancy, exist_ok=True)
     args.pose_rows = None
+    if args.voxel_map:
+        try:
+            args.pose_rows = read_poses(args.poses, len(files))
+            args.voxel_map_box = cli_voxel_map_box(args.pose_rows)
+            voxel_map_params(args.voxel_map_box[0], args.voxel_map_box[1], args.voxel, CLI_VOXEL_MAP_CAPACITY)
+        except (OSError, ValueError) as e:
+            parser.error("--poses / --voxel-map: %s" % e)
     if args.occupancy_map:
         try:
             args.pose_rows = read_poses(args.poses, len(files))
@@ -2199,6 +2371,15 @@ def occupancy_map_cover(poses_xyyaw, x_range, y_range):
             (int(np.floor(p[:, 1].min())) - reach, int(np.ceil(p[:, 1].max())) + reach))
 
 
+CLI_VOXEL_MAP_CAPACITY = 1 << 22  # voxels of --voxel-map's map: a table of 2^23 entries, 738 MB
+
+
+def cli_voxel_map_box(poses_xyyaw):
+    """(lo, hi) of --voxel-map's map: occupancy_map_cover of the trajectory in x and y, the CLI crop's z range."""
+    (x0, x1), (y0, y1) = occupancy_map_cover(poses_xyyaw, CLI_TOP_VIEW["x_range"], CLI_TOP_VIEW["y_range"])
+    return (float(x0), float(y0), CLI_CLOUD_CROP[0][2]), (float(x1), float(y1), CLI_CLOUD_CROP[1][2])
+
+
 def _write_png(path, u8):
     from PIL import Image
     Image.fromarray(u8).save(path)
@@ -2213,6 +2394,7 @@ def _run_batched(args, ldir, rdir, files):
     from ..rig import StereoRig
     rig = StereoRig(1242 // args.scale, 375 // args.scale, calibration=args.camera_calibration, rectify=args.rectify, scale=args.scale)
     world = rig.occupancy_map(args.map_ranges[0], args.map_ranges[1], CLI_TOP_VIEW["scale"]) if args.occupancy_map else None
+    model = rig.voxel_map(args.voxel_map_box[0], args.voxel_map_box[1], args.voxel, CLI_VOXEL_MAP_CAPACITY) if args.voxel_map else None
     n, busy, refined = 0, 0.0, []
     try:
         for i in range(0, len(files), args.batch):
@@ -2229,6 +2411,9 @@ def _run_batched(args, ldir, rdir, files):
                 d1, _ = rig.engine.process_device(gl, gr, want_d2=False)
                 if args.voxel:  # what rig.voxel_clouds(..., args.voxel, lo, hi, transform=(CAMERA_TO_VEHICLE, None)) runs
                     voxels = voxel_cloud_from_disparity(d1, rig.Q, args.voxel, CLI_CLOUD_CROP[0], CLI_CLOUD_CROP[1], colors=col, XR=CAMERA_TO_VEHICLE)
+                    if model is not None:  # a frame that overflowed (count -1) adds nothing here and stops the run below, at split_voxel_clouds
+                        at = args.pose_rows[i:i + len(names)]
+                        model.update(voxels[0], voxels[1], voxels[3], voxels[5], voxel_map_pose(at[:, 0], at[:, 1], at[:, 2]))
                 else:
                     clouds = compact_cloud_from_disparity(d1, rig.Q, colors=col, XR=CAMERA_TO_VEHICLE, lo=CLI_CLOUD_CROP[0], hi=CLI_CLOUD_CROP[1])
             else:
@@ -2265,6 +2450,8 @@ def _run_batched(args, ldir, rdir, files):
                     write_ply(os.path.join(args.ply, os.path.splitext(name)[0] + ".ply"), xyz.cpu().numpy(), color.cpu().numpy())
             n += len(names)
             print("batch of %d (%d, %d): %.1f pairs/s so far" % (len(names), rig.height, rig.width, n / busy))
+        if model is not None:
+            print("voxel map: %d voxels of %g m written to %s" % (model.write_ply(args.voxel_map), args.voxel, args.voxel_map))
         if world is not None:
             _write_png(args.occupancy_map, OCCUPANCY_PNG[world.state().cpu().numpy()])
             if args.clearance:
