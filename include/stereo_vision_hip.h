@@ -58,6 +58,10 @@
  *      into the world by one pose per frame and accumulated per cubic cell in a table that persists from call to call: one coloured 3-D
  *      model of what the drive has seen.  stereo_vision.sv.voxel_map_insert and voxel_map_rows state the definition in numpy.
  *
+ *  (R) Behind (Q): a frame matched against the voxel map (sv_voxel_match_*) - how well the rows of a frame fit the map of (Q) at each of a
+ *      set of candidate 3-D poses, and the best of them, so that a pose - its height and its heading included - can be corrected before the
+ *      frame is inserted.  stereo_vision.sv.voxel_map_match states the definition in numpy.
+ *
  * All sv_* functions return SV_OK (0) or a negative sv_status; sv_last_error() gives the text.
  * Nothing in this library calls exit().
  */
@@ -1246,6 +1250,56 @@ int sv_voxel_map_rows_device(void *map, size_t map_bytes, const sv_voxel_map_spe
  * wavefront into one table update each, 0 issues one update per kept row.  counters_device != NULL: two device uint64 that receive the
  * table updates and the atomic instructions they issued, added up over the calls.  The map's content does not depend on it. */
 int sv_debug_voxel_map(int combine, unsigned long long *counters_device);
+
+/* ---- (R) a frame matched against the voxel map: per-frame rows of (I) or (F) + candidate poses + (Q)'s table -> sums per candidate and the best pose ---- */
+
+/* The insert of (Q) trusts its pose to the cell, and (L) knows nothing of z.  This scores a frame's rows against the voxel map at every pose
+ * of a set of candidates - a window around the odometry's guess in x, y, z and yaw, or any rigid poses - and names the best, reading only
+ * what lies on the device already.  Doubles in (Q)'s order in front of the key, integers behind it: the results are bitwise reproducible,
+ * whatever the order of the additions.  The map is only read.  stereo_vision.sv.voxel_map_match restates all of it in numpy.
+ *
+ *   rows       (Q)'s: frame b has its first min(counts[b], cap) rows, none for counts[b] <= 0; a row's weight w is n[b][i], or 1
+ *   world      Pw[k] = ((R[k][0] x + R[k][1] y) + R[k][2] z) + t[k] in double under candidate p of the row's frame, every product and sum
+ *              rounded on its own; an f32 row is widened first: (Q)'s expression, in its order
+ *   kept       w > 0 and lo < Pw < hi strictly on every axis; NaN, inf and a pose with a word that is not finite keep nothing
+ *   cell       (Q)'s: t = (Pw - lo) / size, c = min((int64)t, cells - 1), u = min((int64)((t - c) * 65536), 65535), key = c_x | c_y << 20 |
+ *              c_z << 40
+ *   hit        the map holds a voxel of that key with n >= min_n, m >= min_rows and last_seq >= since - the three filters of the read-out
+ *              of (Q), with the same meaning: a caller can match against settled voxels only
+ *   sums       per frame b and candidate p: inside = the kept rows, hits = the kept rows that hit, weight = the sum of w over the hit
+ *              rows, d2 = the sum over the hit rows and the three axes of (u_k - S_k / n)^2, unweighted, S and n the voxel's and / the
+ *              integer division: the squared distance, in 1 / 65536 of a cell, between the row and the floor of the voxel's mean offset.
+ *              For frames of at most 2^26 rows d2 < 2^26 * 3 * 65535^2 < 2^60 and weight < 2^57.
+ *   best       best[b] = the candidate with the largest weight, among those the one with the smallest d2, among those the lowest p - put
+ *              the guess first and ties keep it -; best_weight[b] and best_d2[b] are its sums.  A frame without rows has best 0.
+ *   overflowed for an overflowed map every sum is 0, best is -1, best_weight and best_d2 are 0. */
+
+/* Host only: the bytes of the workspace sv_voxel_match_device needs for `batch` frames of `cap` rows and `n_poses` candidates each - the
+ * partial sums per candidate and chunk of rows (at most 64 chunks a frame) and the partial bests.  SV_ERR_ARG (bytes untouched) for a NULL
+ * bytes, cap < 0, batch outside 0..65535, n_poses outside 1..65535 or batch x n_poses >= 2^31. */
+int sv_voxel_match_workspace(int cap, int n_poses, int batch, size_t *bytes);
+/* Enqueued on `stream` (a hipStream_t, NULL = the default stream) as three kernels - scores, sums, best - and not waited for: nothing is
+ * allocated, no host synchronisation is made, the map is read only, and nothing is assumed of what the outputs or the workspace held before.
+ *   map, spec    : (Q)'s buffer and its spec; xyz, dtype, n, counts, cap : as for sv_voxel_map_insert_device
+ *   poses        : double [batch][n_poses][12] device, 8-byte aligned: frame b's own candidates, R row-major, then t
+ *   min_n, min_rows, since : the filters of sv_voxel_map_rows_device
+ *   inside, hits : int32 [batch][n_poses] device; weight, d2 : int64 [batch][n_poses] device - all four, or all four NULL where only the
+ *                  best is wanted
+ *   best         : int32 [batch] device; best_weight, best_d2 : int64 [batch] device
+ *   workspace    : device, 16-byte aligned, workspace_bytes >= what sv_voxel_match_workspace gives
+ * Every output given is written in full.  Returns SV_OK (nothing enqueued for batch == 0), SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued, the
+ * outputs untouched, the text in sv_last_error(NULL) - for: a bad spec or map as the clear entry of (Q) refuses them; another dtype; cap < 0;
+ * batch outside 0..65535; n_poses outside 1..65535; batch x n_poses >= 2^31; with batch > 0 a NULL counts, poses, best, best_weight, best_d2
+ * or workspace, and with cap > 0 as well a NULL xyz; one to three of inside, hits, weight and d2; xyz not aligned to its element, n, counts,
+ * inside, hits or best not 4-byte, poses, weight, d2, best_weight or best_d2 not 8-byte, the workspace not 16-byte aligned; too small a
+ * workspace.  These checks run before any HIP call. */
+int sv_voxel_match_device(const void *map, size_t map_bytes, const sv_voxel_map_spec *spec, const void *xyz, int dtype, const int32_t *n, const int32_t *counts,
+                          const double *poses, int batch, int cap, int n_poses, int64_t min_n, int64_t min_rows, int since, int32_t *inside, int32_t *hits,
+                          int64_t *weight, int64_t *d2, int32_t *best, int64_t *best_weight, int64_t *best_d2, void *workspace, size_t workspace_bytes,
+                          void *stream);
+/* Test hook for the call above, process-wide: group = 0 (the default) lets the call choose how many candidates a workgroup of the score
+ * kernel walks, a power of two in 1..64 fixes it.  The results do not depend on it.  Returns SV_OK, or SV_ERR_ARG for another group. */
+int sv_debug_voxel_match(int group);
 
 /* ---- (A) the reference's exported symbols ------------------------------------------------------------- */
 

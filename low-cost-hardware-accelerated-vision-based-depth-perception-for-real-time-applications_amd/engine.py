@@ -530,7 +530,7 @@ class SvVoxelMapSpec(ctypes.Structure):
 
 
 def _signatures():
-    """The table below: per stage group of the C API, (D) to (Q), its functions and per function (restype, argtypes), parameter by
+    """The table below: per stage group of the C API, (D) to (R), its functions and per function (restype, argtypes), parameter by
     parameter as include/stereo_vision_hip.h declares them - tests/test_stage_signatures.py holds the two against each other."""
     P = ctypes.POINTER
     vp, ci, sz, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_int64
@@ -614,12 +614,18 @@ def _signatures():
             "sv_voxel_map_rows_device": (ci, [vp, sz, vm, i64, i64, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
             "sv_debug_voxel_map": (ci, [ci, vp]),
         },
+        "voxel_match": {  # (R)
+            "sv_voxel_match_workspace": (ci, [ci, ci, ci, P(sz)]),
+            "sv_voxel_match_device": (ci, [vp, sz, vm, vp, ci, vp, vp, vp, ci, ci, ci, i64, i64, ci, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+            "sv_debug_voxel_match": (ci, [ci]),
+        },
     }
 
 
 STAGE_SIGNATURES = _signatures()  # plain data: made without loading the library
 _GROUP_NEEDS = {"voxel": ("cloud",), "occupancy_map": ("occupancy",), "map_match": ("occupancy_map",), "clearance": ("occupancy_map",), "cost": ("clearance",), "frontier": ("cost",)}
 _GROUP_NEEDS["view"] = ("occupancy_map",)
+_GROUP_NEEDS["voxel_match"] = ("voxel_map",)
 _bound_groups = set()
 
 
@@ -1979,6 +1985,91 @@ def debug_voxel_map(combine=True, counters=None):
     """sv_debug_voxel_map: the wavefront merge of the insert kernel on / off and a CUDA int64 [2] tensor (or None) that receives the table
     updates and the atomic instructions they issued.  Process-wide; a test and measurement hook."""
     return int(voxel_map_lib().sv_debug_voxel_map(1 if combine else 0, None if counters is None else counters.data_ptr()))
+
+
+def voxel_match_lib():
+    """The library with the signatures of group (R) declared."""
+    return _bind("voxel_match")
+
+
+class VoxelMatchResult(_Result):
+    """What voxel_map_match returns, tensors on the map's device: inside, hits int32 [B,P], weight, d2 int64 [B,P] (all four None where
+    not asked for), best int32 [B], best_weight and best_d2 int64 [B]."""
+    __slots__ = ("inside", "hits", "weight", "d2", "best", "best_weight", "best_d2")
+
+
+def voxel_match_poses(poses, B, dev):
+    """The candidates of voxel_map_match as a contiguous float64 [B,P,12] tensor on dev: a numpy array - uploaded once - or a tensor on
+    dev; [P,12] accepted for one frame."""
+    import torch
+    p = poses if isinstance(poses, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(poses, dtype=np.float64)).to(dev)
+    if p.device != dev or p.dtype != torch.float64:
+        raise ValueError("poses must be float64 on the device (%s) of the map" % (dev,))
+    if p.dim() == 2 and B == 1:
+        p = p.unsqueeze(0)
+    if p.dim() != 3 or p.shape[0] != B or p.shape[2] != 12:
+        raise ValueError("poses must be [%d,P,12], got %s" % (B, tuple(p.shape)))
+    return p.contiguous()
+
+
+def voxel_map_match(buf, params, xyz, n, counts, poses, min_n=1, min_rows=1, since=0, want_sums=True):
+    """The rows of B frames - xyz CUDA float32 or float64 [B,cap,3], n int32 [B,cap] or None, counts int32 [B], as voxel_map_insert takes
+    them - scored against the voxel map in `buf` at P candidate poses per frame (float64 [B,P,12], stereo_vision.sv.voxel_map_pose of
+    voxel_map_pose_window's rows or any rigid poses; numpy or a tensor on the map's device; [P,12] accepted for one frame) - the
+    definition of stereo_vision.sv.voxel_map_match on the GPU, bit for bit (sv_voxel_match_device: three kernels): per candidate the rows
+    that fall into the map's box, those that fall into a voxel with n >= min_n, m >= min_rows and last_seq >= since, their weight and
+    their squared sub-cell distance to the voxels' means, and per frame the candidate with the largest weight (then the smallest d2, then
+    the lowest index).  want_sums=False leaves the four per-candidate tensors out.  The map is not changed, nothing is read back, and the
+    workspace comes from torch's allocator, which keeps it for the next call of the shape.  -> VoxelMatchResult; enqueued on torch's
+    current stream, not waited for."""
+    import torch
+    spec = voxel_map_spec(params)
+    nbytes = _voxel_map_buffer(buf, spec)
+    dev = buf.device
+    if not (isinstance(xyz, torch.Tensor) and xyz.device == dev and xyz.dtype in (torch.float32, torch.float64) and xyz.dim() == 3 and xyz.shape[2] == 3):
+        raise ValueError("xyz must be a float32 or float64 tensor [B,cap,3] on the map's device")
+    B, cap = int(xyz.shape[0]), int(xyz.shape[1])
+    for t, name, dtype, shape in ((n, "n", torch.int32, (B, cap)), (counts, "counts", torch.int32, (B,))):
+        if t is None and name != "counts":
+            continue
+        if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dtype and tuple(t.shape) == shape):
+            raise ValueError("%s must be a %s tensor %s on the map's device" % (name, str(dtype).replace("torch.", ""), list(shape)))
+    p = voxel_match_poses(poses, B, dev)
+    n_poses = int(p.shape[1])
+    if B > 65535 or not 1 <= n_poses <= 65535 or B * n_poses >= 2 ** 31:
+        raise ValueError("at most 65535 frames of 1 .. 65535 poses each and fewer than 2^31 in all, got %d x %d" % (B, n_poses))
+    for v, what in ((min_n, "min_n"), (min_rows, "min_rows")):
+        if isinstance(v, bool) or int(v) != v or not -2 ** 63 <= v < 2 ** 63:
+            raise ValueError("%s must be an integer, got %r" % (what, v))
+    if isinstance(since, bool) or int(since) != since or not -2 ** 31 <= since < 2 ** 31:
+        raise ValueError("since must be a 32-bit integer, got %r" % (since,))
+    res = VoxelMatchResult(best=torch.empty((B,), dtype=torch.int32, device=dev), best_weight=torch.empty((B,), dtype=torch.int64, device=dev),
+                           best_d2=torch.empty((B,), dtype=torch.int64, device=dev))
+    if want_sums:
+        res.inside, res.hits = (torch.empty((B, n_poses), dtype=torch.int32, device=dev) for _ in range(2))
+        res.weight, res.d2 = (torch.empty((B, n_poses), dtype=torch.int64, device=dev) for _ in range(2))
+    if B == 0:  # nothing to enqueue
+        return res
+    L = voxel_match_lib()
+    need = ctypes.c_size_t()
+    _check(L.sv_voxel_match_workspace(cap, n_poses, B, ctypes.byref(need)), "sv_voxel_match_workspace")
+    ws = torch.empty((need.value + 15) // 16 * 2, dtype=torch.int64, device=dev)
+    xyz, counts = xyz.contiguous(), counts.contiguous()
+    n = None if n is None else n.contiguous()
+    out = [res.inside, res.hits, res.weight, res.d2] if want_sums else [None] * 4
+    with torch.cuda.device(dev):
+        rc = L.sv_voxel_match_device(buf.data_ptr(), nbytes, ctypes.byref(spec), _ptr(xyz), 0 if xyz.dtype == torch.float32 else 1, _ptr(n), counts.data_ptr(),
+                                     p.data_ptr(), B, cap, n_poses, int(min_n), int(min_rows), int(since), *[None if t is None else t.data_ptr() for t in out],
+                                     res.best.data_ptr(), res.best_weight.data_ptr(), res.best_d2.data_ptr(), ws.data_ptr(), ws.numel() * 8,
+                                     torch.cuda.current_stream(dev).cuda_stream)
+    _check(rc, "sv_voxel_match_device")
+    return res  # ws goes back to torch's allocator, which hands it out again on this stream only: behind the kernels
+
+
+def debug_voxel_match(group=0):
+    """sv_debug_voxel_match: the candidates a workgroup of the score kernel walks (0: the call chooses; a power of two in 1 .. 64).
+    Process-wide; a test hook."""
+    return int(voxel_match_lib().sv_debug_voxel_match(int(group)))
 
 
 def host_support_filter(params, dcan, width, height, threads=0, lattice=False):

@@ -27,6 +27,8 @@ disparity, the driver's 8-bit map and point clouds out.
                                                                      # guess [B,3]; m.sums / m.counts / m.best / m.best_score on the device
     model = rig.voxel_map((-50, -100, -2), (150, 100, 4), 0.1, 1 << 21)  # a world-fixed voxel map: one coloured 3-D model of a drive
     model.update(xyz, color, n, counts, voxel_map_pose(x, y, yaw))   # voxel_clouds' (or compact_clouds') rows fused along the same odometry
+    xyzyaw, m = model.localize(xyz, n, counts, guess, (0.5, 0.5, 0.2, 0.04), (5, 5, 3, 5))  # per frame the best pose of a 375-pose window
+                                                                     # around the guess [B,4], before the frame is inserted there
     model.write_ply("drive.ply", min_rows=2)                         # the voxels that at least two rows fell into, ordered by cell
 
 Frames are [B,Hs,Ws,C] (C = 4, 3, 3 for "bgra", "bgr", "rgb") or [B,Hs,Ws] for "gray"; one frame without B is accepted.
@@ -40,7 +42,7 @@ import numpy as np
 
 from .engine import (SvParams, StereoEngine, StereoError, box_positions_from_disparity, box_spec, cloud_spec, compact_cloud_from_disparity,
                      ground_from_disparity, ground_spec, lib, occupancy_from_disparity, occupancy_fuse, occupancy_match, occupancy_clearance, clearance_paths, cost_cells, cost_routes, frontier_cells, frontier_clusters, occupancy_cost_to_goal, occupancy_view, occupancy_spec, pinned_array, reproject, split_clouds, stixel_spec, stixels_from_disparity,
-                     top_view_from_disparity, top_view_spec, split_voxel_clouds, voxel_cloud_from_disparity, voxel_map_clear, voxel_map_insert, voxel_map_new,
+                     top_view_from_disparity, top_view_spec, split_voxel_clouds, voxel_cloud_from_disparity, voxel_map_clear, voxel_map_insert, voxel_map_match, voxel_map_new,
                      voxel_map_rows, voxel_map_stats, voxel_spec)
 from .stereo_vision.sv import CAMERA_TO_VEHICLE, DEFAULT_CALIBRATION  # noqa: F401 (CAMERA_TO_VEHICLE: re-exported for top_view)
 from .stereo_vision.sv import free_space_points, ground_pose
@@ -433,7 +435,9 @@ class VoxelMap:
     edge `size` of the box lo .. hi (metres, world axes) the integer sums of the rows that fell into it, for at most `capacity` voxels.
     device: a CUDA device ("cuda", "cuda:1", an index) - engine.voxel_map_insert, one kernel per update, and engine.voxel_map_rows - or
     "cpu" - the numpy definition on CPU tensors or numpy arrays, the same methods and the same bits.  params is the map's
-    sv_voxel_map_spec as a dict, seq the number of frames added so far: the sequence number the next frame carries."""
+    sv_voxel_map_spec as a dict, seq the number of frames added so far: the sequence number the next frame carries.  match() and localize()
+    are group (R): a frame's rows scored against the map at candidate poses, and the best pose of a window around a guess - localize, then
+    update at the refined pose."""
 
     def __init__(self, lo, hi, size, capacity, device="cuda"):
         import torch
@@ -478,6 +482,34 @@ class VoxelMap:
             return voxel_map_rows(self.buffer, self.params, min_n, min_rows, since, dtype, sort=True)
         res = _sv.voxel_map_rows(self._state, min_n, min_rows, since, dtype)
         return {k: v if k == "count" else torch.from_numpy(v) for k, v in res.items()}
+
+    def match(self, xyz, n, counts, poses, min_n=1, min_rows=1, since=0):
+        """Scores B frames against the map as it stands (include/stereo_vision_hip.h (R), stereo_vision.sv.voxel_map_match): xyz, n and
+        counts as for update, poses float64 [B,P,12] (stereo_vision.sv.voxel_map_pose), numpy or a tensor - frame b's own P candidates.
+        A row hits where its cell holds a voxel with n >= min_n, m >= min_rows and last_seq >= since.  -> engine.VoxelMatchResult with
+        inside, hits, weight, d2 [B,P] and best, best_weight, best_d2 [B] as tensors on the map's device.  The map is not changed; not
+        waited for."""
+        import torch
+        from .engine import VoxelMatchResult
+        if self._state is None:
+            return voxel_map_match(self.buffer, self.params, xyz, n, counts, poses, min_n, min_rows, since)
+        host = [None if t is None else (t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)) for t in (xyz, n, counts, poses)]
+        res = _sv.voxel_map_match(self._state, *host, min_n=min_n, min_rows=min_rows, since=since)
+        return VoxelMatchResult(**{k: torch.from_numpy(np.ascontiguousarray(res[k])) for k in VoxelMatchResult.__slots__})
+
+    def localize(self, xyz, n, counts, guess_xyzyaw, half, steps, min_n=1, min_rows=1, since=0):
+        """The best pose per frame of a window around its guess: guess_xyzyaw float64 [B,4] = (x, y, z, yaw) ([4] for one frame), half =
+        (dx, dy, dz, dyaw) and steps = (nx, ny, nz, nyaw) as stereo_vision.sv.voxel_map_pose_window takes them - the guess is candidate 0
+        and keeps ties.  -> (float64 numpy [B,4], the refined (x, y, z, yaw); the VoxelMatchResult).  Waits for the best indices - B words
+        - and reads nothing else back; a frame whose best is -1 (an overflowed map) keeps its guess."""
+        g = np.asarray(guess_xyzyaw, np.float64)
+        g = g[None] if g.ndim == 1 else g
+        if g.shape != (int(xyz.shape[0]), 4):
+            raise ValueError("localize: guess_xyzyaw must be [%d,4], got %s" % (int(xyz.shape[0]), g.shape))
+        window = np.stack([_sv.voxel_map_pose_window(x, y, z, yaw, half, steps) for x, y, z, yaw in g]) if len(g) else np.zeros((0, 1, 4))
+        res = self.match(xyz, n, counts, _sv.voxel_map_pose(window[..., 0], window[..., 1], window[..., 3], window[..., 2]), min_n, min_rows, since)
+        best = res.best.cpu().numpy().astype(np.int64)
+        return window[np.arange(len(g)), np.maximum(best, 0)], res  # row 0 is the guess
 
     def stats(self):
         """{"claimed", "dropped", "overflowed"}: the voxels the map holds, the rows it dropped, whether it ever held more than its

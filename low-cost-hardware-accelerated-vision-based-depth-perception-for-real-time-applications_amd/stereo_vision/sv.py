@@ -90,6 +90,12 @@ world-fixed voxel map (sv_voxel_map_* of include/stereo_vision_hip.h (Q); engine
 GPU): voxel_cloud's or compact_cloud's rows of the frames of a drive, moved into the world by one pose per frame and accumulated per cubic
 cell - integer sums of weights, offsets and colours, the rows, the first and the last frame -, read out as one row per voxel in ascending
 key.  The reference shows its cloud frame by frame and keeps none.
+
+voxel_map_pose_window and voxel_map_match are the definition of a frame matched against the voxel map (sv_voxel_match_* of
+include/stereo_vision_hip.h (R); engine.voxel_map_match / rig.VoxelMap.match and .localize on the GPU): the rows of a frame under every
+pose of a window in x, y, z and yaw, looked up in the map - the rows that land in a voxel, their weight and their squared sub-cell
+distance to the voxels' means per candidate, and the best candidate per frame -, so that a pose is corrected before the frame is
+inserted.  The reference has no counterpart.
 """
 import argparse
 import ctypes
@@ -632,6 +638,113 @@ def voxel_map_rows(map_state, min_n=1, min_rows=1, since=0, dtype="f32"):
     return {"xyz": xyz.astype(np.float32) if dtype == "f32" else xyz, "color": ((2 * C + n[:, None]) // (2 * n[:, None])).astype(np.uint8),
             "cell": c.astype(np.int32), "n": n, "m": pick("m"), "first_seq": pick("first_seq").astype(np.int32), "last_seq": pick("last_seq").astype(np.int32),
             "key": key, "count": -1 if map_state["overflowed"] else int(len(key))}
+
+
+VOXEL_MATCH_BATCH_MAX = 65535
+VOXEL_MATCH_POSES_MAX = 65535  # candidates per frame of voxel_map_match
+_VOXEL_MATCH_BLOCK = 1 << 18   # row x candidate pairs voxel_map_match holds at a time
+
+
+def voxel_map_pose_window(x, y, z, yaw, half, steps):
+    """float64 [P, 4] = (x, y, z, yaw): the candidates of a window around the guess (x, y, z, yaw) - occupancy_pose_window's rule on four
+    axes: half = (dx, dy, dz, dyaw), the window's half widths (metres, metres, metres, radians; finite, >= 0), steps = (nx, ny, nz, nyaw),
+    odd integers >= 1 with P = nx ny nz nyaw <= 65535.  Row 0 is the guess itself, so that ties keep it; the other P - 1 follow in
+    row-major (i, j, k, l) order over numpy.linspace(-half, +half, n) per axis (n = 1: the offset 0), the middle one - the guess - left
+    out.  voxel_map_pose(x, y, yaw, z) turns the rows into poses."""
+    g = [float(v) for v in (x, y, z, yaw)]
+    if len(half) != 4 or len(steps) != 4:
+        raise ValueError("half and steps must have four entries each, got %r, %r" % (half, steps))
+    h = [float(v) for v in half]
+    if not all(np.isfinite(v) for v in g + h) or min(h) < 0:
+        raise ValueError("the guess and half must be finite and half >= 0, got %r, %r" % (g, h))
+    for v in steps:
+        if isinstance(v, (bool, np.bool_)) or int(v) != v or v < 1 or int(v) % 2 != 1:
+            raise ValueError("steps must be odd integers >= 1, got %r" % (steps,))
+    n = [int(v) for v in steps]
+    if n[0] * n[1] * n[2] * n[3] > VOXEL_MATCH_POSES_MAX:
+        raise ValueError("a window of %d poses: at most 65535" % (n[0] * n[1] * n[2] * n[3]))
+    off = [np.linspace(-h[a], h[a], n[a]) if n[a] > 1 else np.zeros(1) for a in range(4)]
+    grid = np.stack(np.meshgrid(*[g[a] + off[a] for a in range(4)], indexing="ij"), -1).reshape(-1, 4)
+    mid = ((n[0] // 2 * n[1] + n[1] // 2) * n[2] + n[2] // 2) * n[3] + n[3] // 2
+    return np.concatenate([np.array([g]), grid[:mid], grid[mid + 1:]])
+
+
+def voxel_map_match(map_state, xyz, n, counts, poses, min_n=1, min_rows=1, since=0):
+    """The definition of include/stereo_vision_hip.h (R) in numpy: the rows of B frames scored against a voxel map at P candidate poses
+    per frame.  map_state, xyz (float32 or float64 [B,cap,3]), n (int32 [B,cap], or None: every weight 1) and counts (int32 [B]) are
+    voxel_map_insert's; poses float64 [B,P,12] in voxel_map_pose's layout ([P,12] accepted for one frame), 1 <= P <= 65535, B <= 65535,
+    B P < 2^31 (ValueError).  The map is not changed.
+    -> {"inside": int32 [B,P], "hits": int32 [B,P], "weight": int64 [B,P], "d2": int64 [B,P], "best": int32 [B], "best_weight": int64 [B],
+        "best_d2": int64 [B]}.
+
+      rows    frame b has its first min(counts[b], cap) rows, none for counts[b] <= 0; a row's weight w is n[b][i], or 1.
+      world   Pw[k] = ((R[k,0] x + R[k,1] y) + R[k,2] z) + t[k] under candidate p, in double and in that order: voxel_map_insert's.
+      kept    w > 0 and lo < Pw < hi strictly on every axis (NaN, inf and a pose with a word that is not finite keep nothing); inside
+              counts the kept rows.
+      cell    the insert's: t = (Pw - lo) / size, c = min(int(t), cells - 1), u = min(int((t - c) * 65536), 65535), key = cx | cy << 20
+              | cz << 40.
+      hit     the map holds a voxel of that key with n >= min_n, m >= min_rows and last_seq >= since - voxel_map_rows' filters; hits
+              counts the kept rows that hit, weight adds up their w, and d2 adds up, unweighted, (u_k - S_k // n)^2 over the three axes
+              with the voxel's S and n: the squared distance, in 1 / 65536 of a cell, to the floor of the voxel's mean offset.
+      best    the candidate with the largest weight, among those the smallest d2, among those the lowest p.
+    For an overflowed map every per-candidate output is 0, best -1, best_weight and best_d2 0."""
+    w = map_state["params"]
+    lo, hi, size, cells = np.array(w["lo"]), np.array(w["hi"]), np.float64(w["size"]), np.array(w["cells"], np.int64)
+    xyz = np.asarray(xyz)
+    if xyz.dtype not in (np.float32, np.float64) or xyz.ndim != 3 or xyz.shape[2] != 3:
+        raise ValueError("xyz must be float32 or float64 [B,cap,3], got %s %s" % (xyz.dtype, xyz.shape))
+    B, cap = xyz.shape[:2]
+    counts = np.asarray(counts)
+    if counts.shape != (B,):
+        raise ValueError("counts must be [%d], got %s" % (B, counts.shape))
+    if n is not None and np.asarray(n).shape != (B, cap):
+        raise ValueError("n must be [B,cap] or None")
+    p = np.asarray(poses, np.float64)
+    if p.ndim == 2 and B == 1:
+        p = p[None]
+    if p.ndim != 3 or p.shape[0] != B or p.shape[2] != 12:
+        raise ValueError("poses must be float64 [%d, P, 12], got %s" % (B, p.shape))
+    P = p.shape[1]
+    if B > VOXEL_MATCH_BATCH_MAX or not 1 <= P <= VOXEL_MATCH_POSES_MAX or B * P >= 2 ** 31:
+        raise ValueError("at most 65535 frames of 1 .. 65535 poses each and fewer than 2^31 in all, got %d x %d" % (B, P))
+    out = {"inside": np.zeros((B, P), np.int32), "hits": np.zeros((B, P), np.int32), "weight": np.zeros((B, P), np.int64), "d2": np.zeros((B, P), np.int64)}
+    if map_state["overflowed"]:
+        return dict(out, best=np.full(B, -1, np.int32), best_weight=np.zeros(B, np.int64), best_d2=np.zeros(B, np.int64))
+    sel = (map_state["n"] >= min_n) & (map_state["m"] >= min_rows) & (map_state["last_seq"] >= since)
+    by_key = np.argsort(map_state["key"][sel], kind="stable")
+    vkey = map_state["key"][sel][by_key]
+    vmean = (map_state["S"][sel] // map_state["n"][sel][:, None])[by_key]
+    for b in range(B):
+        rows = int(min(max(int(counts[b]), 0), cap))
+        if rows == 0:
+            continue
+        X = xyz[b, :rows].astype(np.float64)
+        x, y, z = X[None, :, 0], X[None, :, 1], X[None, :, 2]
+        wt = np.ones(rows, np.int64) if n is None else np.asarray(n)[b, :rows].astype(np.int64)
+        step = max(1, _VOXEL_MATCH_BLOCK // rows)
+        for p0 in range(0, P, step):
+            R = p[b, p0:p0 + step, None, :]
+            with np.errstate(invalid="ignore", over="ignore"):
+                Pw = np.stack([((R[..., 3 * k] * x + R[..., 3 * k + 1] * y) + R[..., 3 * k + 2] * z) + R[..., 9 + k] for k in range(3)], -1)
+                keep = ((lo < Pw) & (Pw < hi)).all(-1) & (wt > 0)[None, :]  # [candidates, rows]
+            t = (Pw[keep] - lo) / size
+            c = np.minimum(t.astype(np.int64), cells - 1)
+            u = np.minimum(((t - c.astype(np.float64)) * 65536.0).astype(np.int64), 65535)
+            key = c[:, 0] | (c[:, 1] << 20) | (c[:, 2] << 40)
+            at = np.minimum(np.searchsorted(vkey, key), max(len(vkey) - 1, 0))
+            hit = vkey[at] == key if len(vkey) else np.zeros(len(key), bool)
+            cand, row = np.nonzero(keep)
+            d = u[hit] - vmean[at[hit]] if len(vkey) else np.zeros((0, 3), np.int64)
+            m = R.shape[0]
+            out["inside"][b, p0:p0 + m] = keep.sum(1)
+            out["hits"][b, p0:p0 + m] = np.bincount(cand[hit], minlength=m)
+            np.add.at(out["weight"][b, p0:p0 + m], cand[hit], wt[row[hit]])
+            np.add.at(out["d2"][b, p0:p0 + m], cand[hit], (d * d).sum(1))
+    order = [np.lexsort((np.arange(P), out["d2"][b], -out["weight"][b]))[0] for b in range(B)]
+    best = np.array(order, np.int64)
+    at = np.arange(B)
+    return dict(out, best=best.astype(np.int32), best_weight=out["weight"][at, best] if B else np.zeros(0, np.int64),
+                best_d2=out["d2"][at, best] if B else np.zeros(0, np.int64))
 
 
 GROUND_BINS_MIN, GROUND_BINS_MAX = 8, 4096
@@ -2173,6 +2286,12 @@ def main(argv=None):
                         help="with --batch --ply --voxel --poses: fuse the frames' voxel clouds along the poses into one world-fixed voxel map "
                              "of the same edge and write it as one PLY of the whole drive: per occupied cube the centroid and the mean "
                              "colour of everything the drive saw in it, ordered by cell")
+    parser.add_argument("--voxel-match", type=str, default="", metavar="DX,DY,DZ,DYAW[,NX,NY,NZ,NYAW]",
+                        help="with --voxel-map: take the poses as guesses at height 0 - frame 0 is inserted where its line says; every later "
+                             "frame's voxel cloud is first matched against the voxel map built so far over a window of +-DX, +-DY, +-DZ metres "
+                             "and +-DYAW radians around its line (NX x NY x NZ x NYAW poses, odd, default 5,5,3,5; the line itself wins ties) "
+                             "and inserted at the best pose.  The refined poses are written next to FILE.ply as <FILE without "
+                             ".ply>.poses.txt, one 'x y z yaw' per frame")
     parser.add_argument("--occupancy", type=str, default="", metavar="DIR",
                         help="with --batch: write each frame's occupancy grid as a PNG into DIR (0 unknown, 127 free, 255 occupied): ground "
                              "plane and obstacle labels from the float disparity, then per cell of the grid of --top-view (vehicle axes) the "
@@ -2212,6 +2331,7 @@ def main(argv=None):
                              "the distinct unknown, free and occupied cells seen from there")
     args = parser.parse_args(argv)
     args.match_window = None
+    args.voxel_match_window = None
     args.goal_xy = None
     args.view_spec = None
     if args.view:
@@ -2257,6 +2377,17 @@ def main(argv=None):
             occupancy_pose_window(0.0, 0.0, 0.0, *args.match_window)
         except ValueError as e:
             parser.error("--match: %s" % e)
+    if args.voxel_match:
+        if not args.voxel_map:
+            parser.error("--voxel-match needs --voxel-map")
+        try:
+            words = args.voxel_match.split(",")
+            if len(words) not in (4, 8):
+                raise ValueError("%d words, not DX,DY,DZ,DYAW[,NX,NY,NZ,NYAW]" % len(words))
+            args.voxel_match_window = (tuple(float(w) for w in words[:4]), tuple(int(w) for w in words[4:]) or (5, 5, 3, 5))
+            voxel_map_pose_window(0.0, 0.0, 0.0, 0.0, *args.voxel_match_window)
+        except ValueError as e:
+            parser.error("--voxel-match: %s" % e)
     if args.occupancy_map and not args.poses:
         parser.error("--occupancy-map and --poses go together")
     if args.poses and not (args.occupancy_map or args.voxel_map):
@@ -2395,7 +2526,7 @@ def _run_batched(args, ldir, rdir, files):
     rig = StereoRig(1242 // args.scale, 375 // args.scale, calibration=args.camera_calibration, rectify=args.rectify, scale=args.scale)
     world = rig.occupancy_map(args.map_ranges[0], args.map_ranges[1], CLI_TOP_VIEW["scale"]) if args.occupancy_map else None
     model = rig.voxel_map(args.voxel_map_box[0], args.voxel_map_box[1], args.voxel, CLI_VOXEL_MAP_CAPACITY) if args.voxel_map else None
-    n, busy, refined = 0, 0.0, []
+    n, busy, refined, refined_3d = 0, 0.0, [], []
     try:
         for i in range(0, len(files), args.batch):
             names = files[i:i + args.batch]
@@ -2413,7 +2544,14 @@ def _run_batched(args, ldir, rdir, files):
                     voxels = voxel_cloud_from_disparity(d1, rig.Q, args.voxel, CLI_CLOUD_CROP[0], CLI_CLOUD_CROP[1], colors=col, XR=CAMERA_TO_VEHICLE)
                     if model is not None:  # a frame that overflowed (count -1) adds nothing here and stops the run below, at split_voxel_clouds
                         at = args.pose_rows[i:i + len(names)]
-                        model.update(voxels[0], voxels[1], voxels[3], voxels[5], voxel_map_pose(at[:, 0], at[:, 1], at[:, 2]))
+                        if args.voxel_match_window is None:
+                            model.update(voxels[0], voxels[1], voxels[3], voxels[5], voxel_map_pose(at[:, 0], at[:, 1], at[:, 2]))
+                        for k in range(len(names) if args.voxel_match_window is not None else 0):  # one at a time: against the frames before it
+                            one = [t[k:k + 1] for t in (voxels[0], voxels[1], voxels[3], voxels[5])]
+                            guess = np.array([at[k, 0], at[k, 1], 0.0, at[k, 2]])
+                            to = guess if model.seq == 0 else model.localize(one[0], one[2], one[3], guess, *args.voxel_match_window)[0][0]
+                            refined_3d.append(to)
+                            model.update(*one, voxel_map_pose(to[0], to[1], to[3], to[2])[None])
                 else:
                     clouds = compact_cloud_from_disparity(d1, rig.Q, colors=col, XR=CAMERA_TO_VEHICLE, lo=CLI_CLOUD_CROP[0], hi=CLI_CLOUD_CROP[1])
             else:
@@ -2452,6 +2590,9 @@ def _run_batched(args, ldir, rdir, files):
             print("batch of %d (%d, %d): %.1f pairs/s so far" % (len(names), rig.height, rig.width, n / busy))
         if model is not None:
             print("voxel map: %d voxels of %g m written to %s" % (model.write_ply(args.voxel_map), args.voxel, args.voxel_map))
+            if args.voxel_match_window is not None:
+                with open(os.path.splitext(args.voxel_map)[0] + ".poses.txt", "w") as f:
+                    f.write("".join("%r %r %r %r\n" % tuple(float(v) for v in to) for to in refined_3d))
         if world is not None:
             _write_png(args.occupancy_map, OCCUPANCY_PNG[world.state().cpu().numpy()])
             if args.clearance:
