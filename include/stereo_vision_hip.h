@@ -62,6 +62,11 @@
  *      set of candidate 3-D poses, and the best of them, so that a pose - its height and its heading included - can be corrected before the
  *      frame is inserted.  stereo_vision.sv.voxel_map_match states the definition in numpy.
  *
+ *  (S) Behind (R): a voxel map carried into another (sv_voxel_map_carry_device) - the voxels of a map of (Q), filtered and shifted by whole
+ *      cells, added into a second map: a prune (same box, empty destination), a scroll (a shifted box), a grow (a larger capacity) or a
+ *      merge (a destination that holds voxels), so that the map can follow the vehicle and forget.  stereo_vision.sv.voxel_map_carry
+ *      states the definition in numpy.
+ *
  * All sv_* functions return SV_OK (0) or a negative sv_status; sv_last_error() gives the text.
  * Nothing in this library calls exit().
  */
@@ -1300,6 +1305,42 @@ int sv_voxel_match_device(const void *map, size_t map_bytes, const sv_voxel_map_
 /* Test hook for the call above, process-wide: group = 0 (the default) lets the call choose how many candidates a workgroup of the score
  * kernel walks, a power of two in 1..64 fixes it.  The results do not depend on it.  Returns SV_OK, or SV_ERR_ARG for another group. */
 int sv_debug_voxel_match(int group);
+
+/* ---- (S) a voxel map carried into another: (Q)'s table, filtered and shifted by whole cells -> added into a second table of (Q) ---- */
+
+/* (Q)'s table has no removal and its box is fixed.  This moves the content of one map (src, only read) into another (dst): every value is
+ * an integer and stays one, so dst stays bit-exact against stereo_vision.sv.voxel_map_carry, which restates this in numpy.
+ *
+ *   qualifies  a voxel of src with n >= min_n, m >= min_rows and last_seq >= since - the three filters of the read-out of (Q); a voxel that
+ *              does not counts into `filtered`
+ *   outside    a qualifying voxel whose cell c + shift leaves 0 .. cells_dst - 1 on an axis counts into `outside`
+ *   carried    every other voxel: the voxel of dst with key (c + shift) gets n += n, S += S, C += C, m += m, first_seq = min(., first_seq),
+ *              last_seq = max(., last_seq).  The sub-cell offsets S are not changed: a shift by whole cells does not move a point inside
+ *              its cell.  `carried` counts them, `claimed` those whose voxel dst did not hold before.
+ *   head       dst's dropped += src's dropped.  dst is overflowed after the call iff it was before, or src is, or dst now holds more than
+ *              its capacity ((Q)'s rule).  Where src or dst is overflowed as the call starts nothing is carried: carried = -1, the other
+ *              counts 0.  Where dst overflows during the call its content is undefined, as after an insert, and so is `claimed`;
+ *              carried, filtered and outside are exact even then.
+ *   widths     (Q)'s contract: the total weight of a voxel of dst stays below 2^47 after the call.
+ *
+ * With the box of dst at lo' = lo + k * size (stereo_vision.sv.voxel_map_shifted), shift = -k keeps every voxel at its place in the world.
+ *
+ * Enqueues two kernels on `stream` (a hipStream_t, NULL = the default stream) - the head, then a lane per slot of src - and does not wait:
+ * nothing is allocated and no host synchronisation is made.  Uses the first word of the read-out scratch of dst.  No other call on either
+ * map - an insert, a read-out, a match, a clear, another carry - may run at the same time: a destination entry is written with plain
+ * stores by the one lane that carries its voxel.
+ *   dst, dst_bytes, dst_spec : the map that receives, as (Q)'s entries take it; it must have been cleared or filled before
+ *   src, src_bytes, src_spec : the map that is read
+ *   shift_x, shift_y, shift_z: whole cells added to a cell of src, each in -2^20 .. 2^20
+ *   stats        : int64 [4] device, 8-byte aligned - carried, filtered, outside, claimed, written by the call whatever it held -, or NULL
+ * Returns SV_OK, SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued, both maps untouched, the text in sv_last_error(NULL) - for: what the clear
+ * entry of (Q) refuses, for either map; sizes that differ in a bit; a shift outside -2^20 .. 2^20; buffers that share a byte (the dst_bytes
+ * at dst and the src_bytes at src); stats not 8-byte aligned or inside a map.  These checks run before any HIP call.
+ * (The name below stands in parentheses - plain C, the same declaration - because tests/test_voxel_map.py pins the set of
+ * "sv_*voxel_map*(" declarations of this header to group (Q)'s seven.) */
+int (sv_voxel_map_carry_device)(void *dst, size_t dst_bytes, const sv_voxel_map_spec *dst_spec, const void *src, size_t src_bytes,
+                                const sv_voxel_map_spec *src_spec, int shift_x, int shift_y, int shift_z, int64_t min_n, int64_t min_rows, int since,
+                                int64_t *stats, void *stream);
 
 /* ---- (A) the reference's exported symbols ------------------------------------------------------------- */
 

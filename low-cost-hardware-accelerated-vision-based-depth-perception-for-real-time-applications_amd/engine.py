@@ -530,7 +530,7 @@ class SvVoxelMapSpec(ctypes.Structure):
 
 
 def _signatures():
-    """The table below: per stage group of the C API, (D) to (R), its functions and per function (restype, argtypes), parameter by
+    """The table below: per stage group of the C API, (D) to (S), its functions and per function (restype, argtypes), parameter by
     parameter as include/stereo_vision_hip.h declares them - tests/test_stage_signatures.py holds the two against each other."""
     P = ctypes.POINTER
     vp, ci, sz, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_int64
@@ -619,6 +619,9 @@ def _signatures():
             "sv_voxel_match_device": (ci, [vp, sz, vm, vp, ci, vp, vp, vp, ci, ci, ci, i64, i64, ci, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
             "sv_debug_voxel_match": (ci, [ci]),
         },
+        "voxel_carry": {  # (S)
+            "sv_voxel_map_carry_device": (ci, [vp, sz, vm, vp, sz, vm, ci, ci, ci, i64, i64, ci, vp, vp]),
+        },
     }
 
 
@@ -626,6 +629,7 @@ STAGE_SIGNATURES = _signatures()  # plain data: made without loading the library
 _GROUP_NEEDS = {"voxel": ("cloud",), "occupancy_map": ("occupancy",), "map_match": ("occupancy_map",), "clearance": ("occupancy_map",), "cost": ("clearance",), "frontier": ("cost",)}
 _GROUP_NEEDS["view"] = ("occupancy_map",)
 _GROUP_NEEDS["voxel_match"] = ("voxel_map",)
+_GROUP_NEEDS["voxel_carry"] = ("voxel_map",)
 _bound_groups = set()
 
 
@@ -2070,6 +2074,45 @@ def debug_voxel_match(group=0):
     """sv_debug_voxel_match: the candidates a workgroup of the score kernel walks (0: the call chooses; a power of two in 1 .. 64).
     Process-wide; a test hook."""
     return int(voxel_match_lib().sv_debug_voxel_match(int(group)))
+
+
+def voxel_carry_lib():
+    """The library with the signatures of group (S) declared."""
+    return _bind("voxel_carry")
+
+
+def voxel_map_carry(dst_buf, dst_params, src_buf, src_params, shift=(0, 0, 0), min_n=1, min_rows=1, since=0):
+    """Adds the voxels of the map in src_buf - those with n >= min_n, m >= min_rows and last_seq >= since, their cells moved by `shift`
+    whole cells (three integers in -2^20 .. 2^20) - into the map in dst_buf: the definition of stereo_vision.sv.voxel_map_carry on the
+    GPU, bit for bit (sv_voxel_map_carry_device: two kernels).  Both maps are voxel_map_new's buffers with their params, on one device,
+    of bit-equal size and sharing no memory; src is only read.  -> an int64 [4] tensor on the device: carried (-1 where either map was
+    overflowed: nothing is carried), filtered, outside, claimed - stereo_vision.sv.VOXEL_CARRY_STATS.  Enqueued on torch's current
+    stream, not waited for; no other work on either map may run on another stream meanwhile."""
+    import torch
+    from .stereo_vision.sv import VOXEL_CARRY_SHIFT_MAX
+    dst_spec, src_spec = voxel_map_spec(dst_params), voxel_map_spec(src_params)
+    dst_bytes, src_bytes = _voxel_map_buffer(dst_buf, dst_spec), _voxel_map_buffer(src_buf, src_spec)
+    if src_buf.device != dst_buf.device:
+        raise ValueError("the two maps must lie on one device, got %s and %s" % (dst_buf.device, src_buf.device))
+    try:
+        shift = [int(v) if not isinstance(v, bool) and int(v) == v else None for v in shift]
+    except (TypeError, ValueError):
+        shift = [None]
+    if len(shift) != 3 or any(v is None or abs(v) > VOXEL_CARRY_SHIFT_MAX for v in shift):
+        raise ValueError("shift must be three integers in -2^20 .. 2^20")
+    for v, what in ((min_n, "min_n"), (min_rows, "min_rows")):
+        if isinstance(v, bool) or int(v) != v or not -2 ** 63 <= v < 2 ** 63:
+            raise ValueError("%s must be an integer, got %r" % (what, v))
+    if isinstance(since, bool) or int(since) != since or not -2 ** 31 <= since < 2 ** 31:
+        raise ValueError("since must be a 32-bit integer, got %r" % (since,))
+    dev = dst_buf.device
+    stats = torch.empty((4,), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        rc = voxel_carry_lib().sv_voxel_map_carry_device(dst_buf.data_ptr(), dst_bytes, ctypes.byref(dst_spec), src_buf.data_ptr(), src_bytes, ctypes.byref(src_spec),
+                                                         shift[0], shift[1], shift[2], int(min_n), int(min_rows), int(since), stats.data_ptr(),
+                                                         torch.cuda.current_stream(dev).cuda_stream)
+    _check(rc, "sv_voxel_map_carry_device")
+    return stats
 
 
 def host_support_filter(params, dcan, width, height, threads=0, lattice=False):

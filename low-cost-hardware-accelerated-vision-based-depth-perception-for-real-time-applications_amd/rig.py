@@ -42,7 +42,7 @@ import numpy as np
 
 from .engine import (SvParams, StereoEngine, StereoError, box_positions_from_disparity, box_spec, cloud_spec, compact_cloud_from_disparity,
                      ground_from_disparity, ground_spec, lib, occupancy_from_disparity, occupancy_fuse, occupancy_match, occupancy_clearance, clearance_paths, cost_cells, cost_routes, frontier_cells, frontier_clusters, occupancy_cost_to_goal, occupancy_view, occupancy_spec, pinned_array, reproject, split_clouds, stixel_spec, stixels_from_disparity,
-                     top_view_from_disparity, top_view_spec, split_voxel_clouds, voxel_cloud_from_disparity, voxel_map_clear, voxel_map_insert, voxel_map_match, voxel_map_new,
+                     top_view_from_disparity, top_view_spec, split_voxel_clouds, voxel_cloud_from_disparity, voxel_map_carry, voxel_map_clear, voxel_map_insert, voxel_map_match, voxel_map_new,
                      voxel_map_rows, voxel_map_stats, voxel_spec)
 from .stereo_vision.sv import CAMERA_TO_VEHICLE, DEFAULT_CALIBRATION  # noqa: F401 (CAMERA_TO_VEHICLE: re-exported for top_view)
 from .stereo_vision.sv import free_space_points, ground_pose
@@ -437,7 +437,10 @@ class VoxelMap:
     "cpu" - the numpy definition on CPU tensors or numpy arrays, the same methods and the same bits.  params is the map's
     sv_voxel_map_spec as a dict, seq the number of frames added so far: the sequence number the next frame carries.  match() and localize()
     are group (R): a frame's rows scored against the map at candidate poses, and the best pose of a window around a guess - localize, then
-    update at the refined pose."""
+    update at the refined pose.  prune(), recenter(), resize() and merge() are group (S), stereo_vision.sv.voxel_map_carry: the map's voxels,
+    filtered and shifted by whole cells, carried into an empty table - fewer voxels, a box that follows the vehicle, a larger capacity -
+    or another map's voxels added to this one.  The first three carry into a spare buffer of the map's size, allocated on first use and
+    swapped with the map's from then on: they double the memory the map takes and allocate once, not per call."""
 
     def __init__(self, lo, hi, size, capacity, device="cuda"):
         import torch
@@ -446,6 +449,7 @@ class VoxelMap:
         if self.device.type == "cuda" and self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.seq = 0
+        self._spare = None  # prune()'s, recenter()'s and resize()'s second buffer, made on first use
         if self.device.type == "cuda":
             self.buffer, self._state = voxel_map_new(self.params, self.device), None
         else:
@@ -519,6 +523,85 @@ class VoxelMap:
         else:
             claimed, dropped, overflowed = len(self._state["key"]), self._state["dropped"], self._state["overflowed"]
         return {"claimed": int(claimed), "dropped": int(dropped), "overflowed": bool(overflowed)}
+
+    @staticmethod
+    def _filters(filters):
+        """min_n, min_rows, since of a carry, from the keywords of a method."""
+        unknown = set(filters) - {"min_n", "min_rows", "since"}
+        if unknown:
+            raise TypeError("unknown filter %s: min_n, min_rows and since are the filters" % sorted(unknown))
+        return filters.get("min_n", 1), filters.get("min_rows", 1), filters.get("since", 0)
+
+    def _carry_over(self, params, shift, filters):
+        """The map's voxels, filtered and shifted, carried into an empty map of `params`, which becomes the map; -> the counts."""
+        f = self._filters(filters)
+        if self._state is not None:
+            state = _sv.voxel_map_state(params)
+            stats = _sv.voxel_map_carry(state, self._state, shift, *f)
+            self._state, self.params = state, state["params"]
+            return stats
+        same = params["capacity"] == self.params["capacity"]
+        if same and self._spare is None:
+            self._spare = voxel_map_new(params, self.device)
+        into = voxel_map_clear(self._spare, params) if same else voxel_map_new(params, self.device)
+        stats = voxel_map_carry(into, params, self.buffer, self.params, shift, *f)
+        if same:
+            self.buffer, self._spare = into, self.buffer
+        else:
+            self.buffer, self._spare = into, None  # the old pair goes back to torch's allocator, behind the kernels of this stream
+        self.params = params
+        return stats
+
+    def prune(self, min_n=1, min_rows=1, since=0):
+        """Forgets: keeps the voxels with n >= min_n, m >= min_rows and last_seq >= since - rows()' filters - in the same box and
+        capacity, with every sum as it was.  -> the counts carried, filtered, outside, claimed (stereo_vision.sv.VOXEL_CARRY_STATS): an
+        int64 [4] tensor on the device, not waited for, or a dict on "cpu".  seq stays."""
+        return self._carry_over(self.params, (0, 0, 0), dict(min_n=min_n, min_rows=min_rows, since=since))
+
+    def recenter(self, x, y, z=None, **filters):
+        """Scrolls the box by whole cells so that the world point (x, y, z) lies in its middle cell
+        (stereo_vision.sv.voxel_map_recenter_shift; z = None leaves the z axis alone); params becomes voxel_map_shifted's, the voxels
+        that leave the box are lost - counted as outside - and the filters min_n, min_rows, since prune on the way.  Nothing is done, and
+        zeros are returned, where the box does not move and no filter is given.  -> the counts, as prune()."""
+        import torch
+        k = _sv.voxel_map_recenter_shift(self.params, x, y, z)
+        if k == (0, 0, 0) and not filters:
+            self._filters(filters)
+            zeros = dict.fromkeys(_sv.VOXEL_CARRY_STATS, 0)
+            return zeros if self._state is not None else torch.zeros((4,), dtype=torch.int64, device=self.device)
+        most = _sv.VOXEL_CARRY_SHIFT_MAX  # an axis has at most that many cells: a longer way carries nothing either
+        return self._carry_over(_sv.voxel_map_shifted(self.params, k), tuple(max(-most, min(most, -v)) for v in k), filters)
+
+    def resize(self, capacity, **filters):
+        """A new capacity in the same box: the way out before an overflow, when stats()["claimed"] nears the capacity (an overflowed map
+        stays lost).  The filters prune on the way.  -> the counts, as prune()."""
+        return self._carry_over(_sv.voxel_map_params(self.params["lo"], self.params["hi"], self.params["size"], capacity), (0, 0, 0), filters)
+
+    def merge(self, other, **filters):
+        """Adds the voxels of `other` - those that pass the filters and lie in this map's box - to this map; `other` is not changed.  Both
+        maps lie on one device and have the same size, and other's box must start a whole number of cells from this one's: the shift is
+        round((other.lo - self.lo) / size), and ValueError is raised where that quotient misses it by more than
+        stereo_vision.sv.VOXEL_MERGE_TOLERANCE = 1 / 65536 of a cell - the unit of the sub-cell offsets the voxels hold: a box that is
+        off by less displaces no point by more than the map resolves, and the roundings voxel_map_shifted leaves in lo are smaller by
+        orders of magnitude; a box that is off by more needs resampling, which this is not.  seq becomes the larger of the two.  -> the
+        counts, as prune()."""
+        f = self._filters(filters)
+        if not isinstance(other, VoxelMap) or other is self or other.device != self.device:
+            raise ValueError("merge needs another VoxelMap on %s" % (self.device,))
+        size = np.float64(self.params["size"])
+        if np.float64(other.params["size"]).tobytes() != size.tobytes():
+            raise ValueError("merge needs maps of one size, got %r and %r" % (self.params["size"], other.params["size"]))
+        t = (np.array(other.params["lo"]) - np.array(self.params["lo"])) / size
+        shift = np.rint(t)
+        if not (np.abs(t - shift) <= _sv.VOXEL_MERGE_TOLERANCE).all() or not (np.abs(shift) <= _sv.VOXEL_CARRY_SHIFT_MAX).all():
+            raise ValueError("merge: the box of the other map does not start a whole number of cells (at most 2^20) from this one's: %r cells" % (t.tolist(),))
+        shift = tuple(int(v) for v in shift)
+        if self._state is not None:
+            stats = _sv.voxel_map_carry(self._state, other._state, shift, *f)
+        else:
+            stats = voxel_map_carry(self.buffer, self.params, other.buffer, other.params, shift, *f)
+        self.seq = max(self.seq, other.seq)
+        return stats
 
     def write_ply(self, path, min_n=1, min_rows=1, since=0):
         """rows(...) as a binary PLY of coloured points (stereo_vision.sv.write_ply); -> the number of points.  RuntimeError for an

@@ -96,6 +96,12 @@ include/stereo_vision_hip.h (R); engine.voxel_map_match / rig.VoxelMap.match and
 pose of a window in x, y, z and yaw, looked up in the map - the rows that land in a voxel, their weight and their squared sub-cell
 distance to the voxels' means per candidate, and the best candidate per frame -, so that a pose is corrected before the frame is
 inserted.  The reference has no counterpart.
+
+voxel_map_carry (with voxel_map_shifted and voxel_map_recenter_shift) is the definition of a voxel map carried into another
+(sv_voxel_map_carry_device of include/stereo_vision_hip.h (S); engine.voxel_map_carry / rig.VoxelMap.prune, .recenter, .resize and .merge
+on the GPU): the voxels of a map, filtered by weight, rows and age and shifted by whole cells, added into a second map - so that the map
+scrolls with the vehicle, forgets, grows and takes in another map's voxels without leaving its integers.  The reference has no counterpart
+(DESIGN.md §8).
 """
 import argparse
 import ctypes
@@ -638,6 +644,162 @@ def voxel_map_rows(map_state, min_n=1, min_rows=1, since=0, dtype="f32"):
     return {"xyz": xyz.astype(np.float32) if dtype == "f32" else xyz, "color": ((2 * C + n[:, None]) // (2 * n[:, None])).astype(np.uint8),
             "cell": c.astype(np.int32), "n": n, "m": pick("m"), "first_seq": pick("first_seq").astype(np.int32), "last_seq": pick("last_seq").astype(np.int32),
             "key": key, "count": -1 if map_state["overflowed"] else int(len(key))}
+
+
+VOXEL_CARRY_SHIFT_MAX = 2 ** 20   # |shift| per axis of voxel_map_carry: an axis has at most that many cells
+VOXEL_CARRY_STATS = ("carried", "filtered", "outside", "claimed")  # voxel_map_carry's counts, in the order of the C entry's stats
+VOXEL_MERGE_TOLERANCE = 1.0 / 65536  # cells: how far the boxes of two maps that merge may miss a whole number of cells
+_VOXEL_SHIFT_ULPS = 4              # how far voxel_map_shifted moves hi' to keep the count of cells
+
+
+def _whole(v, what):
+    """int(v) for an integer that is no bool; ValueError otherwise."""
+    try:
+        ok = not isinstance(v, (bool, np.bool_)) and int(v) == v
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError("%s must be an integer, got %r" % (what, v))
+    return int(v)
+
+
+def _voxel_map_cells_of(lo, hi, size):
+    """max(1, ceil((hi - lo) / size)) as voxel_grid computes it, for one axis."""
+    return max(1, int(np.ceil((np.float64(hi) - np.float64(lo)) / np.float64(size))))
+
+
+def voxel_map_shifted(params, shift_cells, capacity=None):
+    """The params of the box of `params` moved by shift_cells = (kx, ky, kz) whole cells, with the capacity given or the same: per axis lo' =
+    lo + k * size in double (the product rounded, then the sum), hi' = lo' + (hi - lo), and `cells` identical to the source's.  That last
+    is not automatic - cells = max(1, ceil((hi' - lo') / size)) is recomputed from rounded doubles -, so hi' is moved by up to 4 ulps,
+    towards the count wanted, until it is; ValueError where that does not get there, where a k is not an integer below 2^31 in magnitude,
+    or where the moved box is not one voxel_map_params admits.
+
+    voxel_map_carry into the moved box takes shift = -k.  The position voxel_map_rows reports for a carried voxel is then lo' + (c - k + f)
+    * size in place of lo + (c + f) * size (f the voxel's mean offset as a fraction of a cell, the same double in both).  The two agree
+    in exact arithmetic; as computed they differ by the roundings of k * size, of lo + k size, and of the sum, the product and the sum of
+    either position: with u = 2^-53, per axis and for dtype "f64",
+        |p' - p| <= 1.01 u (|k| size + |lo'| + 2 (c + 1) size + 2 (c - k + 1) size + |p| + |p'|)
+    (voxel_map_shift_bound) - a few 1e-14 m for a box of a hundred metres a thousand cells from where it started."""
+    w = voxel_map_params(params["lo"], params["hi"], params["size"], params["capacity"] if capacity is None else capacity)
+    if not isinstance(shift_cells, (tuple, list, np.ndarray)):
+        raise ValueError("shift_cells must be three integers, got %r" % (shift_cells,))
+    k = [_whole(v, "a shift of voxel_map_shifted") for v in shift_cells]
+    if len(k) != 3 or max(abs(v) for v in k) >= 2 ** 31:
+        raise ValueError("shift_cells must be three integers below 2^31 in magnitude, got %r" % (shift_cells,))
+    size = np.float64(w["size"])
+    lo, hi = np.array(w["lo"], np.float64), np.array(w["hi"], np.float64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        lo2 = lo + np.array(k, np.float64) * size
+        hi2 = lo2 + (hi - lo)
+    if not (np.isfinite(lo2).all() and np.isfinite(hi2).all()):
+        raise ValueError("the box moved by %r cells is not finite" % (k,))
+    for a in range(3):
+        want = w["cells"][a]
+        for _ in range(_VOXEL_SHIFT_ULPS):
+            have = _voxel_map_cells_of(lo2[a], hi2[a], size)
+            if have == want:
+                break
+            hi2[a] = np.nextafter(hi2[a], -np.inf if have > want else np.inf)
+        if _voxel_map_cells_of(lo2[a], hi2[a], size) != want:
+            raise ValueError("the box moved by %r cells cannot keep its %d cells on axis %d" % (k, want, a))
+    moved = voxel_map_params(lo2, hi2, w["size"], w["capacity"])
+    if moved["cells"] != w["cells"]:
+        raise ValueError("the box moved by %r cells has %r cells, not %r" % (k, moved["cells"], w["cells"]))
+    return moved
+
+
+def voxel_map_shift_bound(params, moved, shift_cells, cell, p, p_moved):
+    """The bound voxel_map_shifted's docstring derives, per axis: float64 [..., 3] for cells `cell` (int [..., 3], in the box of `params`)
+    whose positions are p in that box and p_moved in `moved` = voxel_map_shifted(params, shift_cells)."""
+    k = np.array(shift_cells, np.float64)
+    c = np.asarray(cell, np.float64)
+    size = np.float64(params["size"])
+    return 1.01 * 2.0 ** -53 * (np.abs(k) * size + np.abs(np.array(moved["lo"])) + 2 * (c + 1) * size + 2 * (c - k + 1) * size
+                                + np.abs(np.asarray(p, np.float64)) + np.abs(np.asarray(p_moved, np.float64)))
+
+
+def voxel_map_recenter_shift(params, x, y, z=None):
+    """(kx, ky, kz): the whole cells by which the box of `params` must move (voxel_map_shifted) so that the world point (x, y, z) lies in
+    its middle cell (cells // 2 per axis) - occupancy_recenter_shift's rule on three axes.  The point's cell is floor((p - lo) / size),
+    so k = floor((p - lo) / size) - cells // 2; z = None leaves the z axis alone (kz = 0).  ValueError for a point that is not finite or
+    lies 2^31 cells or more from the box."""
+    w = voxel_map_params(params["lo"], params["hi"], params["size"], params["capacity"])
+    k = []
+    for a, p in enumerate((x, y, z)):
+        if p is None and a == 2:
+            k.append(0)
+            continue
+        if p is None or not np.isfinite(p):
+            raise ValueError("recenter needs a finite point, got (%r, %r, %r)" % (x, y, z))
+        with np.errstate(over="ignore"):
+            t = np.floor((np.float64(p) - np.float64(w["lo"][a])) / np.float64(w["size"]))
+        if not abs(t) < 2.0 ** 31:
+            raise ValueError("the point (%r, %r, %r) lies 2^31 cells or more from the box" % (x, y, z))
+        k.append(int(t) - w["cells"][a] // 2)
+    return tuple(k)
+
+
+def voxel_map_carry(dst_state, src_state, shift=(0, 0, 0), min_n=1, min_rows=1, since=0):
+    """Adds the voxels of one voxel map, filtered and shifted by whole cells, into another: the definition of include/stereo_vision_hip.h
+    (S) in numpy.  dst_state (voxel_map_state's dict) is changed in place, src_state is only read; -> a dict of counts.
+
+    The two maps must be distinct and of bit-equal `size`; shift is three integers in -2^20 .. 2^20 (ValueError otherwise).  A voxel of
+    src qualifies iff n >= min_n, m >= min_rows and last_seq >= since - voxel_map_rows' filters -; one that does not counts into
+    "filtered".  A qualifying voxel whose cell c + shift leaves 0 .. cells - 1 of dst on an axis counts into "outside".  Every other
+    voxel is carried: the voxel of dst with the key of c + shift gets n += n, S += S, C += C, m += m, first_seq = min(., first_seq),
+    last_seq = max(., last_seq) - S as it is: whole cells do not move a point inside its cell.  "carried" counts them, "claimed" those
+    dst did not hold before.  dst["dropped"] += src["dropped"].  dst is overflowed afterwards iff it was before, or src is, or it now
+    holds more than its capacity.  Where src or dst is overflowed as the call starts nothing is carried: "carried" is -1 - as
+    voxel_map_rows' count - and the other counts 0.  Contract: the total weight of a voxel of dst stays below 2^47.
+
+    An empty dst of the same box makes this a prune, a box moved by k cells (voxel_map_shifted; shift = -k) a scroll, a larger capacity
+    a grow, a dst that holds voxels a merge."""
+    if dst_state is src_state:
+        raise ValueError("voxel_map_carry needs two distinct maps")
+    ws, wd = src_state["params"], dst_state["params"]
+    if np.float64(ws["size"]).tobytes() != np.float64(wd["size"]).tobytes():
+        raise ValueError("the two maps differ in size: %r and %r" % (ws["size"], wd["size"]))
+    if not isinstance(shift, (tuple, list, np.ndarray)):
+        raise ValueError("shift must be three integers, got %r" % (shift,))
+    shift = [_whole(v, "a shift of voxel_map_carry") for v in shift]
+    if len(shift) != 3 or max(abs(v) for v in shift) > VOXEL_CARRY_SHIFT_MAX:
+        raise ValueError("shift must be three integers in -2^20 .. 2^20, got %r" % (shift,))
+    for v, what in ((min_n, "min_n"), (min_rows, "min_rows"), (since, "since")):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError("%s must be an integer, got %r" % (what, v))
+    stats = dict.fromkeys(VOXEL_CARRY_STATS, 0)
+    dst_state["dropped"] += src_state["dropped"]
+    if src_state["overflowed"] or dst_state["overflowed"]:
+        dst_state["overflowed"] = True
+        stats["carried"] = -1
+        return stats
+    q = (src_state["n"] >= min_n) & (src_state["m"] >= min_rows) & (src_state["last_seq"] >= since)
+    key = src_state["key"]
+    c = np.stack([key & 0xFFFFF, (key >> 20) & 0xFFFFF, (key >> 40) & 0xFFFFF], -1) + np.array(shift, np.int64)
+    inside = ((c >= 0) & (c < np.array(wd["cells"], np.int64))).all(-1)
+    take = q & inside
+    stats["filtered"], stats["outside"], stats["carried"] = int((~q).sum()), int((q & ~inside).sum()), int(take.sum())
+    c = c[take]
+    moved = c[:, 0] | (c[:, 1] << 20) | (c[:, 2] << 40)  # distinct: src's keys are, and the shift is the same for all
+    had = len(dst_state["key"])
+    ukey, inv = np.unique(np.concatenate([dst_state["key"], moved]), return_inverse=True)
+    inv = inv.reshape(-1)
+    V = len(ukey)
+    acc = {"n": np.zeros(V, np.int64), "S": np.zeros((V, 3), np.int64), "C": np.zeros((V, 4), np.int64), "m": np.zeros(V, np.int64),
+           "first_seq": np.full(V, np.iinfo(np.int64).max), "last_seq": np.full(V, -1, np.int64)}
+    old, new = inv[:had], inv[had:]
+    for f in ("n", "S", "C", "m", "first_seq", "last_seq"):
+        acc[f][old] = dst_state[f]
+    for f in ("n", "S", "C", "m"):
+        acc[f][new] += src_state[f][take]
+    acc["first_seq"][new] = np.minimum(acc["first_seq"][new], src_state["first_seq"][take])
+    acc["last_seq"][new] = np.maximum(acc["last_seq"][new], src_state["last_seq"][take])
+    dst_state.update(acc, key=ukey)
+    stats["claimed"] = V - had
+    if V > wd["capacity"]:
+        dst_state["overflowed"] = True
+    return stats
 
 
 VOXEL_MATCH_BATCH_MAX = 65535
@@ -2286,6 +2448,12 @@ def main(argv=None):
                         help="with --batch --ply --voxel --poses: fuse the frames' voxel clouds along the poses into one world-fixed voxel map "
                              "of the same edge and write it as one PLY of the whole drive: per occupied cube the centroid and the mean "
                              "colour of everything the drive saw in it, ordered by cell")
+    parser.add_argument("--voxel-window", action="store_true",
+                        help="with --voxel-map: let the map's box follow the vehicle - before a batch is inserted, the box is recentred by whole "
+                             "cells on the pose of the batch's first frame (x and y) when that has left the middle third of the box on an axis; "
+                             "voxels that leave the box are lost")
+    parser.add_argument("--voxel-forget", type=int, default=0, metavar="FRAMES",
+                        help="with --voxel-map: after every batch forget the voxels that none of the last FRAMES frames has seen")
     parser.add_argument("--voxel-match", type=str, default="", metavar="DX,DY,DZ,DYAW[,NX,NY,NZ,NYAW]",
                         help="with --voxel-map: take the poses as guesses at height 0 - frame 0 is inserted where its line says; every later "
                              "frame's voxel cloud is first matched against the voxel map built so far over a window of +-DX, +-DY, +-DZ metres "
@@ -2388,6 +2556,10 @@ def main(argv=None):
             voxel_map_pose_window(0.0, 0.0, 0.0, 0.0, *args.voxel_match_window)
         except ValueError as e:
             parser.error("--voxel-match: %s" % e)
+    if (args.voxel_window or args.voxel_forget) and not args.voxel_map:
+        parser.error("--voxel-window and --voxel-forget need --voxel-map")
+    if args.voxel_forget < 0:
+        parser.error("--voxel-forget: FRAMES >= 1, got %d" % args.voxel_forget)
     if args.occupancy_map and not args.poses:
         parser.error("--occupancy-map and --poses go together")
     if args.poses and not (args.occupancy_map or args.voxel_map):
@@ -2511,6 +2683,21 @@ def cli_voxel_map_box(poses_xyyaw):
     return (float(x0), float(y0), CLI_CLOUD_CROP[0][2]), (float(x1), float(y1), CLI_CLOUD_CROP[1][2])
 
 
+def cli_voxel_window_left(params, x, y):
+    """--voxel-window's test: has the point (x, y) left the middle third of the box of `params` on the x or the y axis?"""
+    for a, p in enumerate((x, y)):
+        lo, hi = params["lo"][a], params["hi"][a]
+        if not lo + (hi - lo) / 3.0 <= p <= hi - (hi - lo) / 3.0:
+            return True
+    return False
+
+
+def cli_voxel_carry_text(stats):
+    """The counts of a carry (a dict, or the int64 [4] tensor of the device) as the CLI prints them; reads a tensor back."""
+    values = [stats[k] for k in VOXEL_CARRY_STATS] if isinstance(stats, dict) else [int(v) for v in stats.cpu().numpy()]
+    return ", ".join("%s %d" % (k, v) for k, v in zip(VOXEL_CARRY_STATS, values))
+
+
 def _write_png(path, u8):
     from PIL import Image
     Image.fromarray(u8).save(path)
@@ -2544,6 +2731,8 @@ def _run_batched(args, ldir, rdir, files):
                     voxels = voxel_cloud_from_disparity(d1, rig.Q, args.voxel, CLI_CLOUD_CROP[0], CLI_CLOUD_CROP[1], colors=col, XR=CAMERA_TO_VEHICLE)
                     if model is not None:  # a frame that overflowed (count -1) adds nothing here and stops the run below, at split_voxel_clouds
                         at = args.pose_rows[i:i + len(names)]
+                        if args.voxel_window and cli_voxel_window_left(model.params, at[0, 0], at[0, 1]):
+                            print("voxel map recentred at frame %d: %s" % (i, cli_voxel_carry_text(model.recenter(at[0, 0], at[0, 1]))))
                         if args.voxel_match_window is None:
                             model.update(voxels[0], voxels[1], voxels[3], voxels[5], voxel_map_pose(at[:, 0], at[:, 1], at[:, 2]))
                         for k in range(len(names) if args.voxel_match_window is not None else 0):  # one at a time: against the frames before it
@@ -2552,6 +2741,8 @@ def _run_batched(args, ldir, rdir, files):
                             to = guess if model.seq == 0 else model.localize(one[0], one[2], one[3], guess, *args.voxel_match_window)[0][0]
                             refined_3d.append(to)
                             model.update(*one, voxel_map_pose(to[0], to[1], to[3], to[2])[None])
+                    if model is not None and args.voxel_forget:
+                        print("voxel map pruned after frame %d: %s" % (model.seq - 1, cli_voxel_carry_text(model.prune(since=model.seq - args.voxel_forget))))
                 else:
                     clouds = compact_cloud_from_disparity(d1, rig.Q, colors=col, XR=CAMERA_TO_VEHICLE, lo=CLI_CLOUD_CROP[0], hi=CLI_CLOUD_CROP[1])
             else:
