@@ -67,6 +67,10 @@
  *      merge (a destination that holds voxels), so that the map can follow the vehicle and forget.  stereo_vision.sv.voxel_map_carry
  *      states the definition in numpy.
  *
+ *  (T) Behind (S): a voxel map carved by the sight lines of frames (sv_voxel_carve_device) - a ray per row of a frame from the sensor's cell
+ *      through the table of (Q); a voxel that enough rays of later frames pass through is emptied, so that the map can un-see a car that
+ *      drove away or a mismatch at a depth edge.  stereo_vision.sv.voxel_map_carve states the definition in numpy.
+ *
  * All sv_* functions return SV_OK (0) or a negative sv_status; sv_last_error() gives the text.
  * Nothing in this library calls exit().
  */
@@ -1341,6 +1345,56 @@ int sv_debug_voxel_match(int group);
 int (sv_voxel_map_carry_device)(void *dst, size_t dst_bytes, const sv_voxel_map_spec *dst_spec, const void *src, size_t src_bytes,
                                 const sv_voxel_map_spec *src_spec, int shift_x, int shift_y, int shift_z, int64_t min_n, int64_t min_rows, int since,
                                 int64_t *stats, void *stream);
+
+/* ---- (T) a voxel map carved by the sight lines of frames: per-frame rows of (I) or (F) + poses + (Q)'s table -> voxels seen through, emptied ---- */
+
+/* (Q)'s table only gains voxels, and (S) removes them by age or weight alone.  This removes what later frames see through: every kept
+ * row of a frame is the end of a sight line from the sensor, and a voxel that enough sight lines of later frames pass through is carved.
+ * Everything behind the two cell computations is an integer, so the result is bit-exact against stereo_vision.sv.voxel_map_carve, which
+ * restates this in numpy, whatever the schedule.
+ *
+ *   sensor   O[k] = ((R[k,0] ox + R[k,1] oy) + R[k,2] oz) + t[k] with (ox, oy, oz) = origin: the insert's expression, in its order, no
+ *            FMA.  Frame b casts rays iff all twelve words of its pose are finite and lo < O < hi strictly on every axis; its cell c0 is
+ *            the insert's rule, min(int((O - lo) / size), cells - 1) per axis.
+ *   rows     frame b has its first min(counts[b], cap) rows, none for counts[b] <= 0.  A row is kept by exactly the insert's rule -
+ *            w > 0 and lo < Pw < hi strictly; NaN and inf never pass -, and its cell c1 is the insert's.
+ *   ray      with d = c1 - c0 and nst = max |d_a|, a kept row of a casting frame casts a ray iff nst <= reach; it counts into `rays`.
+ *            Its steps are k = 1 .. nst - 1 - margin (there may be none) and count into `steps`; the cell of step k is (J)'s line rule
+ *            on three axes, c0_a + (2 k d_a + nst) // (2 nst) with a flooring division (a negative d_a floors, half-way steps round
+ *            towards +inf).  The major axis moves by exactly one per step: a ray visits no cell twice and never leaves the box.
+ *   miss     at each step, where the map holds the key of the cell and that voxel's last_seq < seq0 + b: miss[voxel] += w, the row's
+ *            weight (n[b][i], or 1).  A voxel this frame or a later one has seen is never counted against by this frame: what an insert
+ *            of the same frames just added is safe, and inside a batch frame b + 1 sees through what only frame b saw.  miss starts
+ *            from zero in every call; it does not persist.  Contract: miss < 2^47 per voxel.
+ *   verdict  a voxel with miss > 0 counts into `touched`.  It is carved iff miss >= min_miss and 256 miss >= ratio n, n its own weight
+ *            (both products stay below 2^63 under the contracts), and counts into `carved`.
+ *   apply    with apply = 1 the entry of a carved voxel goes back to the values of a slot that has just been claimed and not yet added
+ *            to: n, S, C, m zero, first_seq all ones, last_seq zero (which is also what the miss rule reads of it).  THE KEY STAYS: a
+ *            tombstone of an open-addressing table, so probe chains through it stay intact, and a later insert or carry of that cell
+ *            adds to it as to a fresh voxel.  Every call skips it at min_n >= 1 - every default -, a carry (a prune) counts it as
+ *            `filtered` and frees the slot; `claimed` in the map's head is not changed by a carve.  The one consequence: until the next
+ *            prune, the read-out of a carved map is defined for min_n >= 1 only - n = 0 divides.
+ * An overflowed map: nothing is done, stats = -1, 0, 0, 0 and miss all zero.
+ *
+ * Enqueues three kernels on `stream` (a hipStream_t, NULL = the default stream) - miss and stats cleared; a lane per row, its step loop
+ * and one integer atomic add per counted step; a lane per slot - and does not wait: nothing is allocated and no host synchronisation is
+ * made.  With apply = 0 the map is only read.  No other call on the map may run at the same time.
+ *   map, map_bytes, spec : the map, as (Q)'s entries take it
+ *   xyz, dtype, n, counts, poses, batch, cap, seq0 : the frames, as sv_voxel_map_insert_device takes them (device pointers)
+ *   origin       : HOST, three doubles, read by the call: the sensor's centre in the frame's axes
+ *   reach        : cells, 1 .. 1023: rows whose cell lies further from the sensor's on an axis cast no ray
+ *   margin       : cells, 0 .. 255, left alone in front of the row's own cell
+ *   min_miss     : >= 1;  ratio: 0 .. 65535, in 1 / 256;  apply: 0 or 1
+ *   miss         : device, sv_voxel_map_slots(capacity) words, 8-byte aligned, outside the map: per slot of the table, written by the call
+ *   stats        : int64 [4] device, 8-byte aligned - rays, steps, touched, carved, written by the call whatever it held -, or NULL
+ * Returns SV_OK, SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued, everything untouched, the text in sv_last_error(NULL) - for: what the clear
+ * entry of (Q) refuses; a dtype that is neither SV_CLOUD_F32 nor SV_CLOUD_F64; batch outside 0 .. 65535; cap < 0; seq0 < 0 or seq0 + batch
+ * > 2^31 - 1; reach, margin, min_miss, ratio or apply outside the ranges above; counts or poses NULL with batch > 0, xyz NULL with rows;
+ * a pointer not aligned to its element; origin NULL or not finite; miss NULL; miss or stats sharing a byte with the map or with each
+ * other.  These checks run before any HIP call. */
+int sv_voxel_carve_device(void *map, size_t map_bytes, const sv_voxel_map_spec *spec, const void *xyz, int dtype, const int32_t *n, const int32_t *counts,
+                          const double *poses, const double *origin, int batch, int cap, int seq0, int reach, int margin, int64_t min_miss, int ratio, int apply,
+                          uint64_t *miss, int64_t *stats, void *stream);
 
 /* ---- (A) the reference's exported symbols ------------------------------------------------------------- */
 

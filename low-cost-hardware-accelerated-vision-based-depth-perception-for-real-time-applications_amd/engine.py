@@ -622,6 +622,9 @@ def _signatures():
         "voxel_carry": {  # (S)
             "sv_voxel_map_carry_device": (ci, [vp, sz, vm, vp, sz, vm, ci, ci, ci, i64, i64, ci, vp, vp]),
         },
+        "voxel_carve": {  # (T)
+            "sv_voxel_carve_device": (ci, [vp, sz, vm, vp, ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, i64, ci, ci, vp, vp, vp]),
+        },
     }
 
 
@@ -630,6 +633,7 @@ _GROUP_NEEDS = {"voxel": ("cloud",), "occupancy_map": ("occupancy",), "map_match
 _GROUP_NEEDS["view"] = ("occupancy_map",)
 _GROUP_NEEDS["voxel_match"] = ("voxel_map",)
 _GROUP_NEEDS["voxel_carry"] = ("voxel_map",)
+_GROUP_NEEDS["voxel_carve"] = ("voxel_map",)
 _bound_groups = set()
 
 
@@ -2113,6 +2117,96 @@ def voxel_map_carry(dst_buf, dst_params, src_buf, src_params, shift=(0, 0, 0), m
                                                          torch.cuda.current_stream(dev).cuda_stream)
     _check(rc, "sv_voxel_map_carry_device")
     return stats
+
+
+def voxel_carve_lib():
+    """The library with the signatures of group (T) declared."""
+    return _bind("voxel_carve")
+
+
+class VoxelCarveResult(_Result):
+    """What voxel_map_carve returns, tensors on the map's device: stats int64 [4] - rays (-1 for an overflowed map: nothing was done),
+    steps, touched, carved (stereo_vision.sv.VOXEL_CARVE_STATS) - and miss int64 [slots], the weight counted against the voxel of every
+    slot of the table.  Neither is waited for."""
+    __slots__ = ("stats", "miss")
+
+
+def voxel_carve_miss(buf, params):
+    """-> the per-slot tensor voxel_map_carve writes: int64 [sv_voxel_map_slots(capacity)] on the device of the map in `buf`."""
+    import torch
+    slots = int(voxel_map_lib().sv_voxel_map_slots(voxel_map_spec(params).capacity))
+    return torch.empty((slots,), dtype=torch.int64, device=buf.device)
+
+
+def voxel_map_carve(buf, params, xyz, n, counts, poses, origin=(0.0, 0.0, 0.0), seq0=0, reach=1023, margin=1, min_miss=1, ratio=0, apply=True, miss=None):
+    """Carves free space out of the voxel map in `buf` along the sight lines of B frames - the definition of
+    stereo_vision.sv.voxel_map_carve on the GPU, bit for bit (sv_voxel_carve_device: three kernels): xyz, n, counts, poses and seq0 as
+    voxel_map_insert takes them (usually the insert's own arguments, behind it), origin the sensor's centre in the frame's axes (three
+    finite numbers, read here), reach 1 .. 1023 and margin 0 .. 255 in cells, min_miss >= 1, ratio 0 .. 65535 in 1 / 256 of a voxel's
+    weight.  A voxel no later frame has seen, with enough weight of rays through it, is emptied under `apply`: its key stays in the table
+    - a tombstone that every call skips at min_n >= 1 and the next carry drops; until then the read-out is defined for min_n >= 1 only.
+    miss: voxel_carve_miss' tensor to write into (None: a new one).  -> VoxelCarveResult; enqueued on torch's current stream, not waited
+    for, and no other work on the map may run on another stream meanwhile."""
+    import torch
+    from .stereo_vision.sv import VOXEL_CARVE_MARGIN_MAX, VOXEL_CARVE_REACH_MAX
+    spec = voxel_map_spec(params)
+    nbytes = _voxel_map_buffer(buf, spec)
+    dev = buf.device
+    if not (isinstance(xyz, torch.Tensor) and xyz.device == dev and xyz.dtype in (torch.float32, torch.float64) and xyz.dim() == 3 and xyz.shape[2] == 3):
+        raise ValueError("xyz must be a float32 or float64 tensor [B,cap,3] on the map's device")
+    B, cap = int(xyz.shape[0]), int(xyz.shape[1])
+    for t, name, dtype, shape in ((n, "n", torch.int32, (B, cap)), (counts, "counts", torch.int32, (B,))):
+        if t is None and name != "counts":
+            continue
+        if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dtype and tuple(t.shape) == shape):
+            raise ValueError("%s must be a %s tensor %s on the map's device" % (name, str(dtype).replace("torch.", ""), list(shape)))
+    if B > 65535:
+        raise ValueError("at most 65535 frames per call, got %d" % B)
+    if isinstance(seq0, bool) or int(seq0) != seq0 or seq0 < 0 or seq0 + B > 2 ** 31 - 1:
+        raise ValueError("the sequence numbers seq0 .. seq0 + B - 1 must stay in 0 .. 2^31 - 2, got seq0 = %r" % (seq0,))
+    for v, what, lo, hi in ((reach, "reach", 1, VOXEL_CARVE_REACH_MAX), (margin, "margin", 0, VOXEL_CARVE_MARGIN_MAX), (min_miss, "min_miss", 1, 2 ** 63 - 1),
+                            (ratio, "ratio", 0, 65535), (apply, "apply", 0, 1)):
+        if (isinstance(v, bool) and what != "apply") or int(v) != v or not lo <= v <= hi:
+            raise ValueError("%s must be an integer in %d .. %d, got %r" % (what, lo, hi, v))
+    try:
+        o = np.array([float(v) for v in origin], np.float64)
+    except (TypeError, ValueError):
+        o = np.zeros(0)
+    if o.shape != (3,) or not np.isfinite(o).all():
+        raise ValueError("origin must be three finite numbers, got %r" % (origin,))
+    p = voxel_map_poses(poses, dev)
+    if p.shape[0] != B:
+        raise ValueError("poses must hold one pose per frame: %d, got %d" % (B, p.shape[0]))
+    slots = int(voxel_map_lib().sv_voxel_map_slots(spec.capacity))
+    if miss is None:
+        miss = torch.empty((slots,), dtype=torch.int64, device=dev)
+    elif not (isinstance(miss, torch.Tensor) and miss.device == dev and miss.dtype == torch.int64 and miss.is_contiguous() and tuple(miss.shape) == (slots,)):
+        raise ValueError("miss must be a contiguous int64 tensor [%d] on the map's device (voxel_carve_miss)" % slots)
+    res = VoxelCarveResult(stats=torch.empty((4,), dtype=torch.int64, device=dev), miss=miss)
+    xyz, counts = xyz.contiguous(), counts.contiguous()
+    n = None if n is None else n.contiguous()
+    with torch.cuda.device(dev):
+        rc = voxel_carve_lib().sv_voxel_carve_device(buf.data_ptr(), nbytes, ctypes.byref(spec), _ptr(xyz), 0 if xyz.dtype == torch.float32 else 1, _ptr(n),
+                                                     _ptr(counts), _ptr(p), o.ctypes.data, B, cap, int(seq0), int(reach), int(margin), int(min_miss), int(ratio),
+                                                     int(apply), miss.data_ptr(), res.stats.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    _check(rc, "sv_voxel_carve_device")
+    return res
+
+
+def voxel_carve_touched(buf, params, miss):
+    """-> (key, miss) of the slots with miss > 0, ordered by key: two int64 tensors on the map's device, what
+    stereo_vision.sv.voxel_map_carve returns as "key" and "miss".  The keys are read through a strided int64 view of the map's buffer -
+    the first word of each entry of eleven behind the head of four.  Reads the number of touched slots back: this synchronises."""
+    import torch
+    spec = voxel_map_spec(params)
+    _voxel_map_buffer(buf, spec)
+    slots = int(voxel_map_lib().sv_voxel_map_slots(spec.capacity))
+    if not (isinstance(miss, torch.Tensor) and miss.device == buf.device and miss.dtype == torch.int64 and tuple(miss.shape) == (slots,)):
+        raise ValueError("miss must be the int64 tensor [%d] of voxel_map_carve on the map's device" % slots)
+    keys = buf[4:].as_strided((slots,), (11,))
+    at = torch.nonzero(miss > 0).reshape(-1)
+    order = torch.sort(keys[at]).indices
+    return keys[at][order], miss[at][order]
 
 
 def host_support_filter(params, dcan, width, height, threads=0, lattice=False):

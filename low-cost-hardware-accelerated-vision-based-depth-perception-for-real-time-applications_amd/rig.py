@@ -440,7 +440,9 @@ class VoxelMap:
     update at the refined pose.  prune(), recenter(), resize() and merge() are group (S), stereo_vision.sv.voxel_map_carry: the map's voxels,
     filtered and shifted by whole cells, carried into an empty table - fewer voxels, a box that follows the vehicle, a larger capacity -
     or another map's voxels added to this one.  The first three carry into a spare buffer of the map's size, allocated on first use and
-    swapped with the map's from then on: they double the memory the map takes and allocate once, not per call."""
+    swapped with the map's from then on: they double the memory the map takes and allocate once, not per call.  carve() is group (T),
+    stereo_vision.sv.voxel_map_carve: the voxels that the sight lines of later frames pass through are emptied, and keep their slots until
+    the next prune()."""
 
     def __init__(self, lo, hi, size, capacity, device="cuda"):
         import torch
@@ -450,6 +452,7 @@ class VoxelMap:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.seq = 0
         self._spare = None  # prune()'s, recenter()'s and resize()'s second buffer, made on first use
+        self._miss = None   # carve()'s word per slot, made on first use
         if self.device.type == "cuda":
             self.buffer, self._state = voxel_map_new(self.params, self.device), None
         else:
@@ -602,6 +605,47 @@ class VoxelMap:
             stats = voxel_map_carry(self.buffer, self.params, other.buffer, other.params, shift, *f)
         self.seq = max(self.seq, other.seq)
         return stats
+
+    def carve(self, xyz, n, counts, poses, origin=None, seq0=None, reach_m=20.0, margin=1, min_miss=2, ratio=0, apply=True, prune=False):
+        """Un-sees: carves free space out of the map along the sight lines of B frames (include/stereo_vision_hip.h (T),
+        stereo_vision.sv.voxel_map_carve).  xyz, n, counts and poses as for update; seq0 the sequence number of frame 0, None = seq - B:
+        the frames update() has just added, so that `m.update(xyz, color, n, counts, poses); m.carve(xyz, n, counts, poses)` is the
+        idiom - a voxel those frames (or later ones) have seen is never counted against.  origin: the sensor's centre in the frame's
+        axes (None: 0, 0, 0).  A kept row casts a ray from the sensor's cell if its own cell lies within reach = ceil(reach_m / size)
+        cells of it (ValueError above 1023); the last `margin` cells in front of the row's are left alone; a voxel with at least min_miss
+        weight of rays through it, and at least ratio / 256 of its own weight, is emptied under `apply`.  An emptied voxel keeps its slot
+        until the next prune() - prune=True follows with one -: stats()["claimed"] does not change, every method skips it at min_n >= 1,
+        and rows() is defined for min_n >= 1 only until then.  -> engine.VoxelCarveResult (stats int64 [4] = rays, steps, touched,
+        carved, and the per-slot miss tensor, which the map allocates once and reuses: valid until the next carve) on the device, not
+        waited for; on "cpu" the definition's dict.  touched() turns either into (key, miss)."""
+        import torch
+        from .engine import voxel_carve_miss, voxel_map_carve
+        B = int(xyz.shape[0])
+        seq0 = self.seq - B if seq0 is None else seq0
+        reach = int(np.ceil(np.float64(reach_m) / np.float64(self.params["size"]))) if np.isfinite(reach_m) else 0
+        if not 1 <= reach <= _sv.VOXEL_CARVE_REACH_MAX:
+            raise ValueError("carve: reach_m = %r is %d cells of %r m: 1 .. 1023 cells" % (reach_m, reach, self.params["size"]))
+        origin = (0.0, 0.0, 0.0) if origin is None else origin
+        if self._state is None:
+            if self._miss is None or self._miss.numel() != _sv.voxel_map_slots(self.params["capacity"]):
+                self._miss = voxel_carve_miss(self.buffer, self.params)
+            res = voxel_map_carve(self.buffer, self.params, xyz, n, counts, poses, origin, seq0, reach, margin, min_miss, ratio, apply, miss=self._miss)
+        else:
+            host = [None if t is None else (t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)) for t in (xyz, n, counts, poses)]
+            host[3] = _sv.voxel_map_pose_words(host[3])
+            res = _sv.voxel_map_carve(self._state, *host, origin=origin, seq0=seq0, reach=reach, margin=margin, min_miss=min_miss, ratio=ratio, apply=apply)
+        if prune:
+            self.prune()
+        return res
+
+    def touched(self, result):
+        """(key, miss) of the voxels carve() counted rays against, ascending in key: int64 tensors on the map's device.  Call it before
+        anything else changes the map - prune() included, so not behind carve(prune=True) -; reads back."""
+        import torch
+        from .engine import voxel_carve_touched
+        if self._state is None:
+            return voxel_carve_touched(self.buffer, self.params, result.miss)
+        return torch.from_numpy(result["key"]), torch.from_numpy(result["miss"])
 
     def write_ply(self, path, min_n=1, min_rows=1, since=0):
         """rows(...) as a binary PLY of coloured points (stereo_vision.sv.write_ply); -> the number of points.  RuntimeError for an

@@ -102,6 +102,12 @@ voxel_map_carry (with voxel_map_shifted and voxel_map_recenter_shift) is the def
 on the GPU): the voxels of a map, filtered by weight, rows and age and shifted by whole cells, added into a second map - so that the map
 scrolls with the vehicle, forgets, grows and takes in another map's voxels without leaving its integers.  The reference has no counterpart
 (DESIGN.md §8).
+
+voxel_map_carve is the definition of a voxel map carved by the sight lines of frames (sv_voxel_carve_device of
+include/stereo_vision_hip.h (T); engine.voxel_map_carve / rig.VoxelMap.carve on the GPU): a ray per kept row from the sensor's cell to the
+row's, occupancy_ray_cells' line rule on three axes, the weight of the rays that pass through a voxel no later frame has seen, and the
+voxels emptied that enough of it passed through - so that the map un-sees what is no longer there.  The reference has no counterpart
+(DESIGN.md §8).
 """
 import argparse
 import ctypes
@@ -800,6 +806,114 @@ def voxel_map_carry(dst_state, src_state, shift=(0, 0, 0), min_n=1, min_rows=1, 
     if V > wd["capacity"]:
         dst_state["overflowed"] = True
     return stats
+
+
+VOXEL_CARVE_REACH_MAX = 1023  # cells a ray of voxel_map_carve may span on its major axis: 2 k d + nst stays below 2^22
+VOXEL_CARVE_MARGIN_MAX = 255
+VOXEL_CARVE_STATS = ("rays", "steps", "touched", "carved")  # voxel_map_carve's counts, in the order of the C entry's stats
+
+
+def voxel_map_carve(map_state, xyz, n, counts, poses, origin=(0.0, 0.0, 0.0), seq0=0, reach=VOXEL_CARVE_REACH_MAX, margin=1, min_miss=1, ratio=0, apply=True):
+    """Carves free space out of a voxel map along the sight lines of B frames: the definition of include/stereo_vision_hip.h (T) in numpy.
+    map_state (voxel_map_state's dict) is changed in place under `apply`; xyz, n, counts, poses and seq0 are voxel_map_insert's - the usual
+    call repeats the insert's own arguments, behind the insert.  -> {"rays", "steps", "touched", "carved": ints, "key": int64 [T] - the
+    touched voxels, ascending -, "miss": int64 [T] - theirs}.
+
+      sensor   O[k] = ((R[k,0] ox + R[k,1] oy) + R[k,2] oz) + t[k] with origin = (ox, oy, oz), the sensor's centre in the frame's axes:
+               the insert's expression.  Frame b casts rays iff its twelve pose words are finite and lo < O < hi strictly; c0 is O's cell
+               by the insert's rule, min(int((O - lo) / size), cells - 1).
+      rows     the insert's: the first min(counts[b], cap), kept iff w > 0 and lo < Pw < hi strictly; c1 is the row's cell.
+      ray      d = c1 - c0, nst = max |d_a|; a kept row of a casting frame casts a ray iff nst <= reach (1 .. 1023 cells) - "rays".  Its
+               steps k = 1 .. nst - 1 - margin (margin 0 .. 255 cells in front of the row's own cell are left alone; there may be no
+               step) - "steps" - lie in the cells c0_a + (2 k d_a + nst) // (2 nst): occupancy_ray_cells' rule per axis, flooring.
+      miss     a step whose cell holds a voxel with last_seq < seq0 + b adds the row's weight to that voxel's miss: a voxel this frame
+               or a later one has seen is never counted against.  (An emptied voxel reads as last_seq 0, the word the table holds.)
+               miss starts from zero in every call.  Contract: miss < 2^47 per voxel.
+      verdict  "touched": the voxels with miss > 0.  "carved": those with miss >= min_miss (>= 1) and 256 miss >= ratio n (ratio 0 ..
+               65535, in 1 / 256 of the voxel's own weight n).
+      apply    a carved voxel keeps its row - its key - with n = S = C = m = 0 and the first_seq / last_seq an insert starts a voxel
+               from: the tombstone of the device's table.  A later insert or carry adds to it as to a fresh voxel, every call skips it
+               at min_n >= 1 - the defaults -, and a carry (a prune) drops it as "filtered".  Until then voxel_map_rows is defined for
+               min_n >= 1 only: n = 0 divides.  The number of voxels the map holds does not change.
+    An overflowed map: nothing is done, rays is -1 and the other counts 0.  ValueError for a bad argument."""
+    w = map_state["params"]
+    lo, hi, size, cells = np.array(w["lo"]), np.array(w["hi"]), np.float64(w["size"]), np.array(w["cells"], np.int64)
+    xyz = np.asarray(xyz)
+    if xyz.dtype not in (np.float32, np.float64) or xyz.ndim != 3 or xyz.shape[2] != 3:
+        raise ValueError("xyz must be float32 or float64 [B,cap,3], got %s %s" % (xyz.dtype, xyz.shape))
+    B, cap = xyz.shape[:2]
+    counts = np.asarray(counts)
+    poses = np.asarray(poses, np.float64)
+    if counts.shape != (B,) or poses.shape != (B, 12):
+        raise ValueError("counts must be [B] and poses [B,12] for B = %d, got %s and %s" % (B, counts.shape, poses.shape))
+    if n is not None and np.asarray(n).shape != (B, cap):
+        raise ValueError("n must be [B,cap] or None")
+    if B > VOXEL_MATCH_BATCH_MAX:
+        raise ValueError("at most 65535 frames per call, got %d" % B)
+    try:
+        origin = np.array([float(v) for v in origin], np.float64)
+    except (TypeError, ValueError):
+        origin = np.zeros(0)
+    if origin.shape != (3,) or not np.isfinite(origin).all():
+        raise ValueError("origin must be three finite numbers")
+    seq0, reach, margin = _whole(seq0, "seq0"), _whole(reach, "reach"), _whole(margin, "margin")
+    min_miss, ratio = _whole(min_miss, "min_miss"), _whole(ratio, "ratio")
+    if seq0 < 0 or seq0 + B - 1 > VOXEL_MAP_SEQ_MAX:
+        raise ValueError("the sequence numbers seq0 .. seq0 + B - 1 must stay in 0 .. 2^31 - 2, got seq0 = %r" % (seq0,))
+    if not 1 <= reach <= VOXEL_CARVE_REACH_MAX or not 0 <= margin <= VOXEL_CARVE_MARGIN_MAX:
+        raise ValueError("reach must be in 1 .. %d and margin in 0 .. %d, got %d and %d" % (VOXEL_CARVE_REACH_MAX, VOXEL_CARVE_MARGIN_MAX, reach, margin))
+    if not 1 <= min_miss < 2 ** 63 or not 0 <= ratio <= 65535:
+        raise ValueError("min_miss must be an int64 >= 1 and ratio in 0 .. 65535, got %d and %d" % (min_miss, ratio))
+    if apply not in (0, 1):
+        raise ValueError("apply must be 0 or 1, got %r" % (apply,))
+    out = dict.fromkeys(VOXEL_CARVE_STATS, 0)
+    out.update(key=np.zeros(0, np.int64), miss=np.zeros(0, np.int64))
+    if map_state["overflowed"]:
+        out["rays"] = -1
+        return out
+    rows = np.arange(cap)[None, :] < np.minimum(counts.astype(np.int64), cap)[:, None]  # [B,cap]: the rows a frame has
+    R = poses[:, None, :]
+    with np.errstate(invalid="ignore", over="ignore"):  # rows beyond counts, and poses that cast nothing, may hold anything
+        ox, oy, oz = origin
+        O = np.stack([((poses[:, 3 * k] * ox + poses[:, 3 * k + 1] * oy) + poses[:, 3 * k + 2] * oz) + poses[:, 9 + k] for k in range(3)], -1)  # [B,3]
+        casts = np.isfinite(poses).all(1) & ((lo < O) & (O < hi)).all(-1)
+        P = xyz.astype(np.float64)
+        x, y, z = P[..., 0], P[..., 1], P[..., 2]
+        Pw = np.stack([((R[..., 3 * k] * x + R[..., 3 * k + 1] * y) + R[..., 3 * k + 2] * z) + R[..., 9 + k] for k in range(3)], -1)
+        inside = ((lo < Pw) & (Pw < hi)).all(-1)
+    wt = np.ones((B, cap), np.int64) if n is None else np.asarray(n).astype(np.int64)
+    keep = rows & inside & (wt > 0) & casts[:, None]
+    b_of = np.broadcast_to(np.arange(B, dtype=np.int64)[:, None], (B, cap))[keep]
+    c0 = np.minimum(((np.where(casts[:, None], O, lo) - lo) / size).astype(np.int64), cells - 1)[b_of]  # [rows kept, 3]
+    c1 = np.minimum(((Pw[keep] - lo) / size).astype(np.int64), cells - 1)
+    d = c1 - c0
+    nst = np.abs(d).max(-1) if len(d) else np.zeros(0, np.int64)
+    ray = nst <= reach
+    c0, d, nst, wk, seq = c0[ray], d[ray], nst[ray], wt[keep][ray], seq0 + b_of[ray]
+    ns = np.maximum(nst - 1 - margin, 0)
+    out["rays"], out["steps"] = int(ray.sum()), int(ns.sum())
+    by_key = np.argsort(map_state["key"], kind="stable")
+    vkey = map_state["key"][by_key]
+    vlast = np.maximum(map_state["last_seq"][by_key], 0)  # what the table holds for a voxel that was emptied
+    miss = np.zeros(len(vkey), np.int64)
+    for k in range(1, int(ns.max()) + 1 if len(ns) and len(vkey) else 1):
+        on = ns >= k  # nst >= 2 there
+        den = 2 * nst[on][:, None]
+        c = c0[on] + (2 * k * d[on] + nst[on][:, None]) // den
+        key = c[:, 0] | (c[:, 1] << 20) | (c[:, 2] << 40)
+        at = np.minimum(np.searchsorted(vkey, key), len(vkey) - 1)
+        hit = (vkey[at] == key) & (vlast[at] < seq[on])
+        np.add.at(miss, at[hit], wk[on][hit])
+    touched = miss > 0
+    carved = touched & (miss >= min_miss) & (256 * miss >= ratio * map_state["n"][by_key])
+    out["touched"], out["carved"] = int(touched.sum()), int(carved.sum())
+    out["key"], out["miss"] = vkey[touched], miss[touched]
+    if apply:
+        gone = by_key[carved]
+        for f in ("n", "S", "C", "m"):
+            map_state[f][gone] = 0
+        map_state["first_seq"][gone], map_state["last_seq"][gone] = np.iinfo(np.int64).max, -1
+    return out
 
 
 VOXEL_MATCH_BATCH_MAX = 65535
@@ -2454,6 +2568,12 @@ def main(argv=None):
                              "voxels that leave the box are lost")
     parser.add_argument("--voxel-forget", type=int, default=0, metavar="FRAMES",
                         help="with --voxel-map: after every batch forget the voxels that none of the last FRAMES frames has seen")
+    parser.add_argument("--voxel-carve", type=str, default="", metavar="REACH_M[,MIN_MISS[,RATIO]]",
+                        help="with --voxel-map: after every batch's insert, carve the map along the batch's sight lines - a ray from the "
+                             "camera's centre to every voxel row within REACH_M metres (at most 1023 cells); a voxel that none of the "
+                             "batch's frames from the casting one on has seen, with at least MIN_MISS (default 2) rows' weight of rays "
+                             "through it and at least RATIO / 256 (default 0) of its own weight, is emptied.  Prints rays, steps, touched "
+                             "and carved per batch")
     parser.add_argument("--voxel-match", type=str, default="", metavar="DX,DY,DZ,DYAW[,NX,NY,NZ,NYAW]",
                         help="with --voxel-map: take the poses as guesses at height 0 - frame 0 is inserted where its line says; every later "
                              "frame's voxel cloud is first matched against the voxel map built so far over a window of +-DX, +-DY, +-DZ metres "
@@ -2500,6 +2620,7 @@ def main(argv=None):
     args = parser.parse_args(argv)
     args.match_window = None
     args.voxel_match_window = None
+    args.voxel_carve_spec = None
     args.goal_xy = None
     args.view_spec = None
     if args.view:
@@ -2556,6 +2677,16 @@ def main(argv=None):
             voxel_map_pose_window(0.0, 0.0, 0.0, 0.0, *args.voxel_match_window)
         except ValueError as e:
             parser.error("--voxel-match: %s" % e)
+    if args.voxel_carve:
+        if not args.voxel_map:
+            parser.error("--voxel-carve needs --voxel-map")
+        try:
+            words = args.voxel_carve.split(",")
+            if not 1 <= len(words) <= 3:
+                raise ValueError("%d words, not REACH_M[,MIN_MISS[,RATIO]]" % len(words))
+            args.voxel_carve_spec = cli_voxel_carve_spec(float(words[0]), int(words[1]) if len(words) > 1 else 2, int(words[2]) if len(words) > 2 else 0, args.voxel)
+        except ValueError as e:
+            parser.error("--voxel-carve: %s" % e)
     if (args.voxel_window or args.voxel_forget) and not args.voxel_map:
         parser.error("--voxel-window and --voxel-forget need --voxel-map")
     if args.voxel_forget < 0:
@@ -2698,6 +2829,23 @@ def cli_voxel_carry_text(stats):
     return ", ".join("%s %d" % (k, v) for k, v in zip(VOXEL_CARRY_STATS, values))
 
 
+def cli_voxel_carve_spec(reach_m, min_miss, ratio, size):
+    """(reach_m, min_miss, ratio) of --voxel-carve, checked as rig.VoxelMap.carve and voxel_map_carve check them: ValueError with the
+    text the CLI prints."""
+    if not (np.isfinite(reach_m) and reach_m > 0 and size > 0 and np.ceil(np.float64(reach_m) / np.float64(size)) <= VOXEL_CARVE_REACH_MAX):
+        raise ValueError("REACH_M must be > 0 and at most %d cells of %g m, got %r" % (VOXEL_CARVE_REACH_MAX, size, reach_m))
+    if min_miss < 1 or not 0 <= ratio <= 65535:
+        raise ValueError("MIN_MISS >= 1 and RATIO in 0 .. 65535, got %d and %d" % (min_miss, ratio))
+    return float(reach_m), int(min_miss), int(ratio)
+
+
+def cli_voxel_carve_text(res):
+    """The counts of a carve (the definition's dict, or the device's result with its int64 [4] stats) as the CLI prints them; reads a
+    tensor back."""
+    values = [res[k] for k in VOXEL_CARVE_STATS] if isinstance(res, dict) else [int(v) for v in res.stats.cpu().numpy()]
+    return ", ".join("%s %d" % (k, v) for k, v in zip(VOXEL_CARVE_STATS, values))
+
+
 def _write_png(path, u8):
     from PIL import Image
     Image.fromarray(u8).save(path)
@@ -2733,14 +2881,20 @@ def _run_batched(args, ldir, rdir, files):
                         at = args.pose_rows[i:i + len(names)]
                         if args.voxel_window and cli_voxel_window_left(model.params, at[0, 0], at[0, 1]):
                             print("voxel map recentred at frame %d: %s" % (i, cli_voxel_carry_text(model.recenter(at[0, 0], at[0, 1]))))
+                        went = voxel_map_pose(at[:, 0], at[:, 1], at[:, 2])  # the poses the batch's frames are inserted at
                         if args.voxel_match_window is None:
-                            model.update(voxels[0], voxels[1], voxels[3], voxels[5], voxel_map_pose(at[:, 0], at[:, 1], at[:, 2]))
+                            model.update(voxels[0], voxels[1], voxels[3], voxels[5], went)
                         for k in range(len(names) if args.voxel_match_window is not None else 0):  # one at a time: against the frames before it
                             one = [t[k:k + 1] for t in (voxels[0], voxels[1], voxels[3], voxels[5])]
                             guess = np.array([at[k, 0], at[k, 1], 0.0, at[k, 2]])
                             to = guess if model.seq == 0 else model.localize(one[0], one[2], one[3], guess, *args.voxel_match_window)[0][0]
                             refined_3d.append(to)
-                            model.update(*one, voxel_map_pose(to[0], to[1], to[3], to[2])[None])
+                            went[k] = voxel_map_pose(to[0], to[1], to[3], to[2])
+                            model.update(*one, went[k:k + 1])
+                        if args.voxel_carve_spec is not None:  # the camera's centre is the origin of the vehicle axes: CAMERA_TO_VEHICLE only turns
+                            reach_m, min_miss, ratio = args.voxel_carve_spec
+                            res = model.carve(voxels[0], voxels[3], voxels[5], went, reach_m=reach_m, min_miss=min_miss, ratio=ratio)
+                            print("voxel map carved after frame %d: %s" % (model.seq - 1, cli_voxel_carve_text(res)))
                     if model is not None and args.voxel_forget:
                         print("voxel map pruned after frame %d: %s" % (model.seq - 1, cli_voxel_carry_text(model.prune(since=model.seq - args.voxel_forget))))
                 else:
