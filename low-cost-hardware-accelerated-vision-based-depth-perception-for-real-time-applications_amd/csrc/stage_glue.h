@@ -3,6 +3,7 @@
 // no .hip file includes it.
 #pragma once
 
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -52,6 +53,31 @@ inline const char *check_map(const char *prefix, const sv_occupancy_map_spec *m)
     if (m->l_occ < 1 || m->l_occ > 32767 || m->l_free < 1 || m->l_free > 32767) return prefixed(prefix, "l_occ or l_free outside 1..32767");
     if (!(-32767 <= m->l_min && m->l_min <= 0 && 0 <= m->l_max && m->l_max <= 32767) || m->l_min == m->l_max)
         return prefixed(prefix, "the clamp needs -32767 <= l_min <= 0 <= l_max <= 32767 and l_min < l_max");
+    return nullptr;
+}
+
+inline bool misaligned(const void *p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }  // a: a power of two
+
+// NULL for a voxel map spec and a buffer that (Q)'s clear entry admits, else what is wrong with them: the check of every entry of (Q)
+// to (T).  nc = the cells per axis, log2_slots = of the table; sv_voxel_map_slots (voxel_map.cpp) holds the rule of the capacity.
+inline const char *check_voxel_map(const char *prefix, const void *map, size_t map_bytes, const sv_voxel_map_spec *s, int *nc, int *log2_slots) {
+    if (!s) return prefixed(prefix, "spec is NULL");
+    for (int k = 0; k < 7; k++)
+        if (s->reserved[k] != 0) return prefixed(prefix, "a reserved word of the spec is not 0");
+    if (!(s->size > 0.0) || !isfinite(s->size)) return prefixed(prefix, "size is not a finite number > 0");
+    for (int k = 0; k < 3; k++) {
+        if (!isfinite(s->lo[k]) || !isfinite(s->hi[k])) return prefixed(prefix, "the box must be finite");
+        if (!(s->lo[k] < s->hi[k])) return prefixed(prefix, "the box needs lo < hi on every axis");
+        const double cells = ceil((s->hi[k] - s->lo[k]) / s->size);  // +inf where the difference or the quotient overflows
+        if (!(cells <= 1048576.0)) return prefixed(prefix, "more than 2^20 cells on an axis");
+        nc[k] = cells < 1.0 ? 1 : (int)cells;
+    }
+    const int64_t slots = sv_voxel_map_slots(s->capacity);
+    if (slots < 0) return prefixed(prefix, "capacity outside 1 .. 2^26");
+    if (!map || misaligned(map, 16) || map_bytes < sv_voxel_map_bytes(s->capacity))
+        return prefixed(prefix, "the map is NULL, not 16-byte aligned or smaller than sv_voxel_map_bytes");
+    *log2_slots = 0;
+    while (((int64_t)1 << *log2_slots) < slots) (*log2_slots)++;
     return nullptr;
 }
 

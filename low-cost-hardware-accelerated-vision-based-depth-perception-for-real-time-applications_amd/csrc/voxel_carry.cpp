@@ -1,6 +1,6 @@
 // Group (S) of include/stereo_vision_hip.h: the voxels of one voxel map of (Q) carried into another (voxel_carry_kernels.hip).
 // Everything here is argument checking and launch set-up; every check runs before anything is enqueued, and a refused call leaves its
-// text for sv_last_error(NULL).  The checks of a map's spec and buffer are (Q)'s, restated: voxel_map.cpp keeps its own.
+// text for sv_last_error(NULL).  The check of a map's spec and buffer is stage_glue.h's.
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
@@ -17,30 +17,6 @@ using namespace sv::glue;
 
 constexpr int MAX_SHIFT = 1 << 20;  // cells: an axis has at most that many, so a larger shift carries nothing either
 
-bool misaligned(const void *p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
-// NULL for a spec and a buffer (Q)'s clear entry admits, else what is wrong with them; nc = the cells per axis, l = log2 of the slots.
-const char *check_map(const char *which, const void *map, size_t map_bytes, const sv_voxel_map_spec *s, int *nc, int *l) {
-    if (!s) return prefixed(which, "spec is NULL");
-    for (int k = 0; k < 7; k++)
-        if (s->reserved[k] != 0) return prefixed(which, "a reserved word of the spec is not 0");
-    if (!(s->size > 0.0) || !isfinite(s->size)) return prefixed(which, "size is not a finite number > 0");
-    for (int k = 0; k < 3; k++) {
-        if (!isfinite(s->lo[k]) || !isfinite(s->hi[k])) return prefixed(which, "the box must be finite");
-        if (!(s->lo[k] < s->hi[k])) return prefixed(which, "the box needs lo < hi on every axis");
-        const double cells = ceil((s->hi[k] - s->lo[k]) / s->size);  // +inf where the difference or the quotient overflows
-        if (!(cells <= 1048576.0)) return prefixed(which, "more than 2^20 cells on an axis");
-        nc[k] = cells < 1.0 ? 1 : (int)cells;
-    }
-    const int64_t slots = sv_voxel_map_slots(s->capacity);
-    if (slots < 0) return prefixed(which, "capacity outside 1 .. 2^26");
-    if (!map || misaligned(map, 16) || map_bytes < sv_voxel_map_bytes(s->capacity))
-        return prefixed(which, "the map is NULL, not 16-byte aligned or smaller than sv_voxel_map_bytes");
-    *l = 0;
-    while (((int64_t)1 << *l) < slots) (*l)++;
-    return nullptr;
-}
-
 }  // namespace
 
 extern "C" {
@@ -48,8 +24,8 @@ extern "C" {
 int sv_voxel_map_carry_device(void *dst, size_t dst_bytes, const sv_voxel_map_spec *dst_spec, const void *src, size_t src_bytes, const sv_voxel_map_spec *src_spec,
                               int shift_x, int shift_y, int shift_z, int64_t min_n, int64_t min_rows, int since, int64_t *stats, void *stream) {
     int dst_nc[3], src_nc[3], dst_l, src_l;
-    if (const char *bad = check_map("sv_voxel_map_carry: dst", dst, dst_bytes, dst_spec, dst_nc, &dst_l)) return refuse(bad);
-    if (const char *bad = check_map("sv_voxel_map_carry: src", src, src_bytes, src_spec, src_nc, &src_l)) return refuse(bad);
+    if (const char *bad = check_voxel_map("sv_voxel_map_carry: dst", dst, dst_bytes, dst_spec, dst_nc, &dst_l)) return refuse(bad);
+    if (const char *bad = check_voxel_map("sv_voxel_map_carry: src", src, src_bytes, src_spec, src_nc, &src_l)) return refuse(bad);
     if (memcmp(&dst_spec->size, &src_spec->size, sizeof(double)) != 0) return refuse("sv_voxel_map_carry: the two maps differ in size");
     const int shift[3] = {shift_x, shift_y, shift_z};
     for (int k = 0; k < 3; k++)

@@ -1,6 +1,6 @@
 // The voxels of one world-fixed voxel map, filtered and shifted by whole cells, added into another: include/stereo_vision_hip.h (S),
-// restated in stereo_vision/sv.py (voxel_map_carry).  Both buffers are voxel_map_kernels.h's; the source is only read.  slot_of and the
-// read-out's three filters are voxel_map_kernels.hip's, restated here (tests/test_voxel_carry.py holds the texts against each other).
+// restated in stereo_vision/sv.py (voxel_map_carry).  Both buffers are voxel_map_kernels.h's; the source is only read.  The read-out's
+// three filters and the claiming probe are voxel_map_table.h's, the insert's own.
 //
 //   head    one wavefront, in front of the table kernel in stream order: the four counts zeroed, the source's `dropped` added to the
 //           destination's, and the verdict "nothing is carried" - either map is overflowed as the call starts - stored in the first word
@@ -28,38 +28,18 @@
 #include <stdint.h>
 
 #include "voxel_carry_kernels.h"
+#include "voxel_map_table.h"
 
 namespace sv {
 
 namespace {
 
-constexpr unsigned long long VMAP_EMPTY = ~0ull;
-
-// The destination, as the probing needs it.
-struct CarryTable {
-    uint32_t *head;  // [0] claimed slots, [1] overflowed
-    unsigned long long *table;
-    int log2_slots, capacity;
-};
-
-__device__ __forceinline__ uint32_t slot_of(const CarryTable &a, unsigned long long key) {
-    return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> (64 - a.log2_slots));  // log2_slots in 10 .. 27
-}
-
-__device__ __forceinline__ uint32_t overflowed(const uint32_t *head) { return __hip_atomic_load(head + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ int32_t *tiles_of(uint8_t *map, int log2_slots) {
-    return reinterpret_cast<int32_t *>(map + VMAP_HEAD_BYTES + ((size_t)VMAP_ENTRY_WORDS * 8 << log2_slots));
-}
-
 __global__ __launch_bounds__(64) void k_vcarry_head(VoxelCarryArgs a) {
     if (threadIdx.x != 0) return;
-    uint32_t *dh = reinterpret_cast<uint32_t *>(a.dst);
-    const uint32_t *sh = reinterpret_cast<const uint32_t *>(a.src);
-    const bool lost = sh[1] != 0u || dh[1] != 0u;
-    tiles_of(a.dst, a.dst_log2_slots)[0] = lost ? 1 : 0;
-    *reinterpret_cast<unsigned long long *>(a.dst + 8) += *reinterpret_cast<const unsigned long long *>(a.src + 8);  // dropped
-    if (lost) dh[1] = 1u;
+    const bool lost = vmap_overflowed_before(a.src) || vmap_overflowed_before(a.dst);
+    vmap_tiles(a.dst, a.dst_log2_slots)[0] = lost ? 1 : 0;
+    *vmap_dropped(a.dst) += *vmap_dropped(a.src);
+    if (lost) vmap_head(a.dst)[1] = 1u;
     if (a.stats) {
         a.stats[0] = lost ? -1ll : 0ll;
         for (int k = 1; k < VCARRY_STATS; k++) a.stats[k] = 0ll;
@@ -67,58 +47,47 @@ __global__ __launch_bounds__(64) void k_vcarry_head(VoxelCarryArgs a) {
 }
 
 // Adds the source entry e to the voxel `key` of the destination; true where that claimed a slot.  See the precondition above.
-__device__ __forceinline__ bool carry_entry(const CarryTable &a, unsigned long long key, const unsigned long long *e, unsigned long long n, unsigned long long m,
+__device__ __forceinline__ bool carry_entry(const VoxelCarryArgs &a, unsigned long long key, const unsigned long long *e, unsigned long long n, unsigned long long m,
                                             unsigned long long seqs) {
-    const uint32_t last = (uint32_t)(((size_t)1 << a.log2_slots) - 1);
-    uint32_t h = slot_of(a, key);
-    for (uint32_t probe = 0; probe <= last; probe++, h = (h + 1) & last) {
-        if ((probe & 15) == 15 && overflowed(a.head)) break;  // a full table of a map that is lost anyway
-        unsigned long long *d = a.table + (size_t)h * VMAP_ENTRY_WORDS;
-        const unsigned long long old = atomicCAS(d, VMAP_EMPTY, key);
-        if (old != VMAP_EMPTY && old != key) continue;  // someone else's: the next slot
-        d[1] += n;
+    bool claimed;
+    unsigned long long *d = vmap_claim(vmap_head(a.dst), vmap_table(a.dst), a.dst_log2_slots, key, claimed);
+    if (!d) return false;
+    d[VMAP_N] += n;
 #pragma unroll
-        for (int k = 2; k < 9; k++) d[k] += e[k];  // S[3], C[4]
-        d[9] += m;
-        const unsigned long long have = d[10];
-        const uint32_t f0 = (uint32_t)have, f1 = (uint32_t)seqs, l0 = (uint32_t)(have >> 32), l1 = (uint32_t)(seqs >> 32);
-        d[10] = (unsigned long long)(f0 < f1 ? f0 : f1) | (unsigned long long)(l0 > l1 ? l0 : l1) << 32;
-        return old == VMAP_EMPTY;
-    }
-    atomicOr(a.head + 1, 1u);  // no slot within `slots` probes: more voxels than the capacity
-    return false;
+    for (int k = VMAP_S; k < VMAP_M; k++) d[k] += e[k];  // S[3], C[4]
+    d[VMAP_M] += m;
+    const unsigned long long have = d[VMAP_SEQ];
+    const uint32_t f0 = vmap_first_seq(have), f1 = vmap_first_seq(seqs), l0 = vmap_last_seq(have), l1 = vmap_last_seq(seqs);
+    d[VMAP_SEQ] = (unsigned long long)(f0 < f1 ? f0 : f1) | (unsigned long long)(l0 > l1 ? l0 : l1) << 32;
+    return claimed;
 }
 
 __global__ __launch_bounds__(VCARRY_THREADS) void k_vcarry_table(VoxelCarryArgs a) {
     __shared__ uint32_t s_count[VCARRY_THREADS / 64][VCARRY_STATS];
-    if (tiles_of(a.dst, a.dst_log2_slots)[0]) return;  // the whole grid: a map was overflowed as the call started
+    if (vmap_tiles(a.dst, a.dst_log2_slots)[0]) return;  // the whole grid: a map was overflowed as the call started
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const size_t slots = (size_t)1 << a.src_log2_slots;  // a multiple of VCARRY_THREADS
-    CarryTable t;
-    t.head = reinterpret_cast<uint32_t *>(a.dst);
-    t.table = reinterpret_cast<unsigned long long *>(a.dst + VMAP_HEAD_BYTES);
-    t.log2_slots = a.dst_log2_slots, t.capacity = a.dst_capacity;
     uint32_t n_carried = 0, n_filtered = 0, n_outside = 0, n_claimed = 0;  // of this wavefront, over its trips: at most slots <= 2^27
     for (size_t slot = (size_t)blockIdx.x * VCARRY_THREADS + threadIdx.x; slot < slots; slot += (size_t)gridDim.x * VCARRY_THREADS) {  // the same trips for a workgroup
-        const unsigned long long *e = reinterpret_cast<const unsigned long long *>(a.src + VMAP_HEAD_BYTES) + slot * VMAP_ENTRY_WORDS;
-        const unsigned long long key = e[0];
+        const unsigned long long *e = vmap_table(a.src) + slot * VMAP_ENTRY_WORDS;
+        const unsigned long long key = e[VMAP_KEY];
         const bool occupied = key != VMAP_EMPTY;
         unsigned long long n = 0, m = 0, seqs = 0;
         bool q = false;
         if (occupied) {
-            n = e[1], m = e[9], seqs = e[10];
-            q = (long long)n >= a.min_n && (long long)m >= a.min_rows && (int32_t)(seqs >> 32) >= a.since;  // the read-out's filters
+            n = e[VMAP_N], m = e[VMAP_M], seqs = e[VMAP_SEQ];
+            q = vmap_passes(a, e);
         }
         bool inside = q;
         unsigned long long moved = 0;
 #pragma unroll
         for (int k = 0; k < 3; k++) {
-            const int c = (int)((key >> (20 * k)) & 0xFFFFFull) + a.shift[k];  // -2^20 .. 2^21
+            const int c = vmap_key_cell(key, k) + a.shift[k];  // -2^20 .. 2^21
             inside = inside && c >= 0 && c < a.dst_nc[k];
             moved |= (unsigned long long)(uint32_t)(c & 0xFFFFF) << (20 * k);  // used where inside: c itself
         }
         bool claimed = false;
-        if (inside) claimed = carry_entry(t, moved, e, n, m, seqs);
+        if (inside) claimed = carry_entry(a, moved, e, n, m, seqs);
         // every lane of the wavefront gets here
         n_claimed += (uint32_t)__popcll(__ballot(claimed)), n_carried += (uint32_t)__popcll(__ballot(inside));
         n_filtered += (uint32_t)__popcll(__ballot(occupied && !q)), n_outside += (uint32_t)__popcll(__ballot(q && !inside));
@@ -132,8 +101,9 @@ __global__ __launch_bounds__(VCARRY_THREADS) void k_vcarry_table(VoxelCarryArgs 
     for (int w = 0; w < VCARRY_THREADS / 64; w++) total += s_count[w][threadIdx.x];
     if (total == 0) return;
     if (threadIdx.x == VCARRY_STATS - 1) {  // the claims: the insert's rule
-        const bool over = atomicAdd(t.head, total) + total > (uint32_t)t.capacity;
-        if (over) atomicOr(t.head + 1, 1u);
+        uint32_t *head = vmap_head(a.dst);
+        const bool over = atomicAdd(head, total) + total > (uint32_t)a.dst_capacity;
+        if (over) atomicOr(head + 1, 1u);
     }
     if (a.stats) atomicAdd(reinterpret_cast<unsigned long long *>(a.stats) + threadIdx.x, (unsigned long long)total);
 }

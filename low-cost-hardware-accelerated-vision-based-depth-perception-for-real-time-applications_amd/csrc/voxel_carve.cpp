@@ -1,6 +1,6 @@
 // Group (T) of include/stereo_vision_hip.h: a voxel map of (Q) carved by the sight lines of frames (voxel_carve_kernels.hip).
 // Everything here is argument checking and launch set-up; every check runs before anything is enqueued, and a refused call leaves its
-// text for sv_last_error(NULL).  The checks of a map's spec and buffer are (Q)'s, restated: voxel_map.cpp keeps its own.
+// text for sv_last_error(NULL).  The check of a map's spec and buffer is stage_glue.h's.
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
@@ -15,30 +15,6 @@ namespace {
 
 using namespace sv::glue;
 
-bool misaligned(const void *p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
-// NULL for a spec and a buffer (Q)'s clear entry admits, else what is wrong with them; nc = the cells per axis, l = log2 of the slots.
-const char *check_map(const char *which, const void *map, size_t map_bytes, const sv_voxel_map_spec *s, int *nc, int *l) {
-    if (!s) return prefixed(which, "spec is NULL");
-    for (int k = 0; k < 7; k++)
-        if (s->reserved[k] != 0) return prefixed(which, "a reserved word of the spec is not 0");
-    if (!(s->size > 0.0) || !isfinite(s->size)) return prefixed(which, "size is not a finite number > 0");
-    for (int k = 0; k < 3; k++) {
-        if (!isfinite(s->lo[k]) || !isfinite(s->hi[k])) return prefixed(which, "the box must be finite");
-        if (!(s->lo[k] < s->hi[k])) return prefixed(which, "the box needs lo < hi on every axis");
-        const double cells = ceil((s->hi[k] - s->lo[k]) / s->size);  // +inf where the difference or the quotient overflows
-        if (!(cells <= 1048576.0)) return prefixed(which, "more than 2^20 cells on an axis");
-        nc[k] = cells < 1.0 ? 1 : (int)cells;
-    }
-    const int64_t slots = sv_voxel_map_slots(s->capacity);
-    if (slots < 0) return prefixed(which, "capacity outside 1 .. 2^26");
-    if (!map || misaligned(map, 16) || map_bytes < sv_voxel_map_bytes(s->capacity))
-        return prefixed(which, "the map is NULL, not 16-byte aligned or smaller than sv_voxel_map_bytes");
-    *l = 0;
-    while (((int64_t)1 << *l) < slots) (*l)++;
-    return nullptr;
-}
-
 }  // namespace
 
 extern "C" {
@@ -47,7 +23,7 @@ int sv_voxel_carve_device(void *map, size_t map_bytes, const sv_voxel_map_spec *
                           const double *poses, const double *origin, int batch, int cap, int seq0, int reach, int margin, int64_t min_miss, int ratio, int apply,
                           uint64_t *miss, int64_t *stats, void *stream) {
     int nc[3], l;
-    if (const char *bad = check_map("sv_voxel_carve", map, map_bytes, spec, nc, &l)) return refuse(bad);
+    if (const char *bad = check_voxel_map("sv_voxel_carve", map, map_bytes, spec, nc, &l)) return refuse(bad);
     if (dtype != SV_CLOUD_F32 && dtype != SV_CLOUD_F64) return refuse("sv_voxel_carve: dtype is not SV_CLOUD_F32 / SV_CLOUD_F64");
     if (batch < 0 || batch > 65535) return refuse("sv_voxel_carve: batch outside 0..65535");
     if (cap < 0) return refuse("sv_voxel_carve: cap < 0");

@@ -1,7 +1,6 @@
 // A world-fixed voxel map carved by the sight lines of frames: include/stereo_vision_hip.h (T), restated in stereo_vision/sv.py
-// (voxel_map_carve).  The map's buffer is voxel_map_kernels.h's.  The transform, the kept rule, the cell rule and slot_of are
-// voxel_map_kernels.hip's and the read-only probe is voxel_match_kernels.hip's, restated here (tests/test_voxel_carve.py holds the texts
-// against each other).  Three kernels in stream order; no workgroup waits for another:
+// (voxel_map_carve).  The map's buffer is voxel_map_kernels.h's; the transform, the kept rule, the cell rule, slot_of and the read-only
+// probe are voxel_map_table.h's.  Three kernels in stream order; no workgroup waits for another:
 //
 //   zero    miss (a 64-bit word per slot, outside the map) and stats cleared, 16 bytes per store; for an overflowed map the verdict
 //           rays = -1 instead.  The "do nothing" word the other two kernels read is the map's own overflow flag: no kernel of this call
@@ -34,32 +33,12 @@
 #include <stdint.h>
 
 #include "voxel_carve_kernels.h"
+#include "voxel_map_table.h"
 #include "wave_ops.h"
 
 namespace sv {
 
 namespace {
-
-constexpr unsigned long long VMAP_EMPTY = ~0ull;
-
-__device__ __forceinline__ uint32_t slot_of(const VoxelCarveArgs &a, unsigned long long key) {
-    return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> (64 - a.log2_slots));  // log2_slots in 10 .. 27
-}
-
-__device__ __forceinline__ bool overflowed(const VoxelCarveArgs &a) { return reinterpret_cast<const uint32_t *>(a.map)[1] != 0u; }
-
-// The slot of `key`, or -1 where the map holds none.
-__device__ __forceinline__ long long find(const VoxelCarveArgs &a, const unsigned long long *table, unsigned long long key) {
-    const uint32_t last = (uint32_t)(((size_t)1 << a.log2_slots) - 1);
-    uint32_t h = slot_of(a, key);
-    for (uint32_t probe = 0; probe <= last; probe++, h = (h + 1) & last) {
-        const unsigned long long *e = table + (size_t)h * VMAP_ENTRY_WORDS;
-        const unsigned long long k = e[0];
-        if (k == key) return (long long)h;
-        if (k == VMAP_EMPTY) return -1;
-    }
-    return -1;  // a full table without the key
-}
 
 __global__ __launch_bounds__(VCARVE_THREADS) void k_vcarve_zero(VoxelCarveArgs a) {
     const size_t slots = (size_t)1 << a.log2_slots;
@@ -72,7 +51,7 @@ __global__ __launch_bounds__(VCARVE_THREADS) void k_vcarve_zero(VoxelCarveArgs a
         else a.miss[w0 >= 0 ? w0 : 0] = 0ull;  // the first word of a buffer that starts on an odd word, or its last
     }
     if (u == 0 && a.stats) {
-        a.stats[0] = overflowed(a) ? -1ll : 0ll;
+        a.stats[0] = vmap_overflowed_before(a.map) ? -1ll : 0ll;
         for (int k = 1; k < VCARVE_STATS; k++) a.stats[k] = 0ll;
     }
 }
@@ -83,22 +62,18 @@ __global__ __launch_bounds__(VCARVE_THREADS) void k_vcarve_rays(VoxelCarveArgs a
     __shared__ unsigned long long s_count[VCARVE_THREADS / 64][2];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, b = blockIdx.y;
     const long long i = (long long)blockIdx.x * VCARVE_THREADS + threadIdx.x;  // the frame's row
-    int cnt = a.counts[b];
-    cnt = cnt < a.cap ? cnt : a.cap;
+    const int cnt = vmap_rows_of(a.counts, b, a.cap);
     if ((long long)blockIdx.x * VCARVE_THREADS >= cnt) return;  // the whole workgroup: no row of the frame in it (a count <= 0 included)
-    if (overflowed(a)) return;                                   // the whole grid
+    if (vmap_overflowed_before(a.map)) return;  // the whole grid
     const double *pose = a.poses + (size_t)b * 12;
     if (threadIdx.x == 0) {
         bool keep = true;
         for (int k = 0; k < 12; k++) keep = keep && __builtin_isfinite(pose[k]);
-        const double x = a.origin[0], y = a.origin[1], z = a.origin[2];
 #pragma unroll
         for (int k = 0; k < 3; k++) {
-            const double P = ((pose[3 * k] * x + pose[3 * k + 1] * y) + pose[3 * k + 2] * z) + pose[9 + k];
-            keep = keep && a.lo[k] < P && P < a.hi[k];  // false for NaN
-            const double t = keep ? (P - a.lo[k]) / a.size : 0.0;
-            long long c = (long long)t;
-            if (c > a.nc[k] - 1) c = a.nc[k] - 1;
+            double t;
+            long long c;
+            keep = vmap_cell(a, pose, k, a.origin[0], a.origin[1], a.origin[2], keep, t, c);
             s_c0[k] = (int)c;
         }
         s_c0[3] = keep ? 1 : 0;
@@ -112,24 +87,16 @@ __global__ __launch_bounds__(VCARVE_THREADS) void k_vcarve_rays(VoxelCarveArgs a
     double x = 0.0, y = 0.0, z = 0.0;
     long long wt = 1;
     if (keep) {
-        if (DT == VMAP_F32) {
-            const float *p = static_cast<const float *>(a.xyz) + 3 * o;
-            x = (double)p[0], y = (double)p[1], z = (double)p[2];
-        } else {
-            const double *p = static_cast<const double *>(a.xyz) + 3 * o;
-            x = p[0], y = p[1], z = p[2];
-        }
+        vmap_load_row<DT>(a.xyz, o, x, y, z);
         if (a.weight) wt = a.weight[o];
         keep = wt > 0;
     }
     int d[3], nst = 0;
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-        const double P = ((pose[3 * k] * x + pose[3 * k + 1] * y) + pose[3 * k + 2] * z) + pose[9 + k];
-        keep = keep && a.lo[k] < P && P < a.hi[k];  // false for NaN
-        const double t = keep ? (P - a.lo[k]) / a.size : 0.0;
-        long long c = (long long)t;
-        if (c > a.nc[k] - 1) c = a.nc[k] - 1;
+        double t;
+        long long c;
+        keep = vmap_cell(a, pose, k, x, y, z, keep, t, c);
         d[k] = (int)c - s_c0[k];  // |d| < 2^20
         const int m = d[k] < 0 ? -d[k] : d[k];
         nst = m > nst ? m : nst;
@@ -137,7 +104,7 @@ __global__ __launch_bounds__(VCARVE_THREADS) void k_vcarve_rays(VoxelCarveArgs a
     const bool ray = keep && nst <= a.reach;
     const int n_steps = ray && nst - 1 - a.margin > 0 ? nst - 1 - a.margin : 0;  // <= reach - 1
 
-    const unsigned long long *table = reinterpret_cast<const unsigned long long *>(a.map + VMAP_HEAD_BYTES);
+    const unsigned long long *table = vmap_table(a.map);
     const uint32_t seq = (uint32_t)(a.seq0 + b);
     int c[3] = {s_c0[0], s_c0[1], s_c0[2]}, rem[3] = {nst, nst, nst};  // 2 k d + nst = (c - c0) * 2 nst + rem, 0 <= rem < 2 nst
     const int n_most = wave_max(n_steps);  // every lane of the wavefront gets here, and walks as far as its longest ray: the merge below shuffles
@@ -153,20 +120,20 @@ __global__ __launch_bounds__(VCARVE_THREADS) void k_vcarve_rays(VoxelCarveArgs a
                 if (rem[j] < 0) rem[j] += 2 * nst, c[j]--;
             }
             // a step beyond the ray's last is not looked up: its cell may lie outside the box
-            key[u] = k0 + u <= n_steps ? (unsigned long long)c[0] | (unsigned long long)c[1] << 20 | (unsigned long long)c[2] << 40 : VMAP_EMPTY;
-            h[u] = slot_of(a, key[u]);
+            key[u] = k0 + u <= n_steps ? vmap_key(c[0], c[1], c[2]) : VMAP_EMPTY;
+            h[u] = vmap_slot_of(a.log2_slots, key[u]);
         }
 #pragma unroll
-        for (int u = 0; u < VCARVE_STEPS; u++) word[u] = key[u] != VMAP_EMPTY ? table[(size_t)h[u] * VMAP_ENTRY_WORDS] : VMAP_EMPTY;  // the first probe of each
+        for (int u = 0; u < VCARVE_STEPS; u++) word[u] = key[u] != VMAP_EMPTY ? table[(size_t)h[u] * VMAP_ENTRY_WORDS + VMAP_KEY] : VMAP_EMPTY;  // the first probe of each
         long long at[VCARVE_STEPS];
 #pragma unroll
         for (int u = 0; u < VCARVE_STEPS; u++)  // an empty first slot: no voxel; another key there: the whole probe, which is rare
-            at[u] = word[u] == VMAP_EMPTY ? -1 : (word[u] == key[u] ? (long long)h[u] : find(a, table, key[u]));
+            at[u] = word[u] == VMAP_EMPTY ? -1 : (word[u] == key[u] ? (long long)h[u] : vmap_find(table, a.log2_slots, key[u]));
 #pragma unroll
-        for (int u = 0; u < VCARVE_STEPS; u++) word[u] = at[u] >= 0 ? table[(size_t)at[u] * VMAP_ENTRY_WORDS + 10] : ~0ull;  // last_seq all ones: never older
+        for (int u = 0; u < VCARVE_STEPS; u++) word[u] = at[u] >= 0 ? table[(size_t)at[u] * VMAP_ENTRY_WORDS + VMAP_SEQ] : ~0ull;  // last_seq all ones: never older
 #pragma unroll
         for (int u = 0; u < VCARVE_STEPS; u++) {
-            const bool add = (uint32_t)(word[u] >> 32) < seq;  // the voxel is older than the frame
+            const bool add = vmap_last_seq(word[u]) < seq;  // the voxel is older than the frame
             // neighbouring rows are neighbouring cells, and near the sensor their rays share cells: one add per run of equal slots
             const WaveRun run = wave_run(add ? at[u] : -1ll - lane);
             unsigned long long w = add ? (unsigned long long)wt : 0ull;
@@ -190,7 +157,7 @@ __global__ __launch_bounds__(VCARVE_THREADS) void k_vcarve_rays(VoxelCarveArgs a
 
 __global__ __launch_bounds__(VCARVE_THREADS) void k_vcarve_apply(VoxelCarveArgs a) {
     __shared__ uint32_t s_count[VCARVE_THREADS / 64][2];
-    if (overflowed(a)) return;  // the whole grid
+    if (vmap_overflowed_before(a.map)) return;  // the whole grid
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const size_t slots = (size_t)1 << a.log2_slots;  // a multiple of VCARVE_THREADS
     uint32_t n_touched = 0, n_carved = 0;            // of this wavefront, over its trips: at most slots <= 2^27
@@ -198,14 +165,10 @@ __global__ __launch_bounds__(VCARVE_THREADS) void k_vcarve_apply(VoxelCarveArgs 
         const unsigned long long miss = a.miss[slot];
         bool carved = false;
         if (miss > 0ull) {
-            unsigned long long *e = reinterpret_cast<unsigned long long *>(a.map + VMAP_HEAD_BYTES) + slot * VMAP_ENTRY_WORDS;
-            const unsigned long long n = e[1];
+            unsigned long long *e = vmap_table(a.map) + slot * VMAP_ENTRY_WORDS;
+            const unsigned long long n = e[VMAP_N];
             carved = (long long)miss >= a.min_miss && 256ull * miss >= (unsigned long long)a.ratio * n;  // miss, n < 2^47: both below 2^63
-            if (carved && a.apply) {
-#pragma unroll
-                for (int k = 1; k < 10; k++) e[k] = 0ull;
-                e[10] = 0xFFFFFFFFull;  // first_seq all ones, last_seq 0: a slot just claimed
-            }
+            if (carved && a.apply) vmap_clear_values(e);
         }
         // every lane of the wavefront gets here
         n_touched += (uint32_t)__popcll(__ballot(miss > 0ull)), n_carved += (uint32_t)__popcll(__ballot(carved));

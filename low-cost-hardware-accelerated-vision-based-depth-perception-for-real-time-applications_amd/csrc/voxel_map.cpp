@@ -12,6 +12,7 @@
 #include "../../include/stereo_vision_hip.h"
 #include "stage_glue.h"
 #include "voxel_map_kernels.h"
+#include "voxel_map_table.h"
 
 namespace {
 
@@ -32,32 +33,10 @@ int log2_slots(int capacity) {  // of a checked capacity: 10 .. 27
 
 bool capacity_ok(int capacity) { return capacity >= 1 && capacity <= MAX_CAPACITY; }
 
-bool misaligned(const void *p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
-// NULL for a good spec, else what is wrong with it; nc = the cells per axis of a good spec.
-const char *check_spec(const sv_voxel_map_spec *s, int *nc) {
-    if (!s) return "sv_voxel_map: spec is NULL";
-    for (int k = 0; k < 7; k++)
-        if (s->reserved[k] != 0) return "sv_voxel_map: a reserved word of the spec is not 0";
-    if (!(s->size > 0.0) || !isfinite(s->size)) return "sv_voxel_map: size is not a finite number > 0";
-    for (int k = 0; k < 3; k++) {
-        if (!isfinite(s->lo[k]) || !isfinite(s->hi[k])) return "sv_voxel_map: the box must be finite";
-        if (!(s->lo[k] < s->hi[k])) return "sv_voxel_map: the box needs lo < hi on every axis";
-        const double cells = ceil((s->hi[k] - s->lo[k]) / s->size);  // +inf where the difference or the quotient overflows
-        if (!(cells <= 1048576.0)) return "sv_voxel_map: more than 2^20 cells on an axis";
-        nc[k] = cells < 1.0 ? 1 : (int)cells;
-    }
-    if (s->capacity < 1) return "sv_voxel_map: capacity < 1";
-    if (s->capacity > MAX_CAPACITY) return "sv_voxel_map: capacity > 2^26";
-    return nullptr;
-}
-
 // The checks of the buffer every device entry makes, and the arguments all kernels share.
 const char *check_buffer(void *map, size_t map_bytes, const sv_voxel_map_spec *spec, sv::VoxelMapArgs *a) {
-    int nc[3];
-    if (const char *bad = check_spec(spec, nc)) return bad;
-    const int l = log2_slots(spec->capacity);
-    if (!map || misaligned(map, 16) || map_bytes < sv::vmap_bytes(l)) return "sv_voxel_map: the map is NULL, not 16-byte aligned or smaller than sv_voxel_map_bytes";
+    int nc[3], l;
+    if (const char *bad = check_voxel_map("sv_voxel_map", map, map_bytes, spec, nc, &l)) return bad;
     memset(a, 0, sizeof(*a));
     a->map = static_cast<uint8_t *>(map);
     a->log2_slots = l, a->capacity = spec->capacity, a->size = spec->size;
@@ -83,7 +62,7 @@ int64_t sv_voxel_map_slot_of(int64_t key, int64_t slots) {
     if (slots < 2 || slots > ((int64_t)1 << 32) || (slots & (slots - 1))) return -1;
     int l = 1;
     while (((int64_t)1 << l) < slots) l++;
-    return (int64_t)(((uint64_t)key * 0x9E3779B97F4A7C15ull) >> (64 - l));
+    return (int64_t)sv::vmap_slot_of(l, (unsigned long long)key);  // the function the kernels inline
 }
 
 int sv_debug_voxel_map(int combine, unsigned long long *counters_device) {

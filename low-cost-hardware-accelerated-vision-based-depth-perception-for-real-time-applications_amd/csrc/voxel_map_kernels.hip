@@ -24,6 +24,8 @@
 //   rows      tile = VMAP_TILE slots and one wavefront: the qualifying slots per tile, their exclusive prefix sum (one workgroup, the
 //             scan of cloud_kernels.hip), then the rows in slot order with the rank from a ballot.  Plain loads: a kernel boundary lies
 //             between the insert and the read-out.
+// The world, kept and cell rules, the entry's words and the parts of the buffer are voxel_map_table.h's, which match, carry and carve
+// share.
 //
 // Every load of the input is guarded by row < min(counts[b], cap), every slot index is masked by slots - 1, every store of a row by
 // row < out_capacity; a tile index is < slots / VMAP_TILE.
@@ -31,35 +33,12 @@
 #include <stdint.h>
 
 #include "voxel_map_kernels.h"
+#include "voxel_map_table.h"
 #include "wave_ops.h"
 
 namespace sv {
 
 namespace {
-
-constexpr unsigned long long VMAP_EMPTY = ~0ull;
-
-struct MapWs {
-    uint32_t *head;               // [0] claimed slots, [1] overflowed
-    unsigned long long *dropped;  // behind them
-    unsigned long long *table;
-    int32_t *tiles;
-};
-
-__device__ __forceinline__ MapWs map_ws(const VoxelMapArgs &a) {
-    MapWs w;
-    w.head = reinterpret_cast<uint32_t *>(a.map);
-    w.dropped = reinterpret_cast<unsigned long long *>(a.map + 8);
-    w.table = reinterpret_cast<unsigned long long *>(a.map + VMAP_HEAD_BYTES);
-    w.tiles = reinterpret_cast<int32_t *>(a.map + VMAP_HEAD_BYTES + ((size_t)VMAP_ENTRY_WORDS * 8 << a.log2_slots));
-    return w;
-}
-
-__device__ __forceinline__ uint32_t overflowed(const uint32_t *head) { return __hip_atomic_load(head + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ uint32_t slot_of(const VoxelMapArgs &a, unsigned long long key) {
-    return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> (64 - a.log2_slots));  // log2_slots in 10 .. 27
-}
 
 __global__ __launch_bounds__(256) void k_vmap_clear(VoxelMapArgs a) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;  // 16-byte unit of the buffer
@@ -72,40 +51,45 @@ __global__ __launch_bounds__(256) void k_vmap_clear(VoxelMapArgs a) {
         w[k] = 0ull;
         if (word >= head_words && word - head_words < table_words) {
             const unsigned r = (unsigned)((word - head_words) % VMAP_ENTRY_WORDS);
-            w[k] = r == 0 ? VMAP_EMPTY : (r == VMAP_ENTRY_WORDS - 1 ? 0xFFFFFFFFull : 0ull);  // first_seq all ones, last_seq 0
+            w[k] = r == VMAP_KEY ? VMAP_EMPTY : (r == VMAP_SEQ ? VMAP_SEQ_CLEARED : 0ull);
         }
     }
     *reinterpret_cast<ulonglong2 *>(a.map + i * 16) = make_ulonglong2(w[0], w[1]);
 }
 
 // Adds a run (m rows of frame `seq`, weight n, offset sums S, colour sums C) to the voxel `key`; true where that claimed a slot.
+// The probe loop is vmap_claim's (voxel_map_table.h), restated around the update and the `issued` count: with the update behind the
+// loop instead, as the carry has it, the kernels without `combine` take three to four more vector registers.
+// tests/test_voxel_map.py holds the two texts against each other.
 template <bool COUNT_ATOMICS>
-__device__ __forceinline__ bool vmap_add(const VoxelMapArgs &a, const MapWs &w, unsigned long long key, unsigned long long n, unsigned long long m, uint32_t seq,
+__device__ __forceinline__ bool vmap_add(const VoxelMapArgs &a, uint32_t *head, unsigned long long key, unsigned long long n, unsigned long long m, uint32_t seq,
                                          const unsigned long long *S, const unsigned long long *C, bool colors) {
-    const uint32_t last = (uint32_t)(((size_t)1 << a.log2_slots) - 1);
-    uint32_t h = slot_of(a, key), issued = 0;
+    unsigned long long *table = vmap_table(a.map);
+    const int log2_slots = a.log2_slots;
+    const uint32_t last = (uint32_t)(((size_t)1 << log2_slots) - 1);
+    uint32_t h = vmap_slot_of(log2_slots, key), issued = 0;
     for (uint32_t probe = 0; probe <= last; probe++, h = (h + 1) & last) {
-        if ((probe & 15) == 15 && overflowed(w.head)) break;  // a full table of a map that is lost anyway
-        unsigned long long *e = w.table + (size_t)h * VMAP_ENTRY_WORDS;
-        const unsigned long long old = atomicCAS(e, VMAP_EMPTY, key);
+        if ((probe & 15) == 15 && vmap_overflowed_meanwhile(head)) break;
+        unsigned long long *e = table + (size_t)h * VMAP_ENTRY_WORDS;
+        const unsigned long long old = atomicCAS(e + VMAP_KEY, VMAP_EMPTY, key);
         issued++;
         if (old != VMAP_EMPTY && old != key) continue;  // someone else's: the next slot
-        atomicAdd(e + 1, n);
+        atomicAdd(e + VMAP_N, n);
 #pragma unroll
-        for (int k = 0; k < 3; k++) atomicAdd(e + 2 + k, S[k]);
+        for (int k = 0; k < 3; k++) atomicAdd(e + VMAP_S + k, S[k]);
         if (colors) {
 #pragma unroll
-            for (int j = 0; j < 4; j++) atomicAdd(e + 5 + j, C[j]);
+            for (int j = 0; j < 4; j++) atomicAdd(e + VMAP_C + j, C[j]);
         }
-        atomicAdd(e + 9, m);
-        uint32_t *fl = reinterpret_cast<uint32_t *>(e + 10);
+        atomicAdd(e + VMAP_M, m);
+        uint32_t *fl = reinterpret_cast<uint32_t *>(e + VMAP_SEQ);
         atomicMin(fl, seq);
         atomicMax(fl + 1, seq);
         issued += colors ? 11 : 7;
         if (COUNT_ATOMICS) atomicAdd(a.counters, 1ull), atomicAdd(a.counters + 1, (unsigned long long)issued);
         return old == VMAP_EMPTY;
     }
-    atomicOr(w.head + 1, 1u);  // no slot within `slots` probes: more voxels than the capacity
+    atomicOr(head + 1, 1u);  // no slot within `slots` probes: more voxels than the capacity
     if (COUNT_ATOMICS) atomicAdd(a.counters + 1, (unsigned long long)issued + 1);
     return false;
 }
@@ -114,11 +98,10 @@ template <int DT, bool COMBINE, bool COUNT_ATOMICS>
 __global__ __launch_bounds__(64 * VMAP_WAVES) void k_vmap_insert(VoxelMapArgs a) {
     const int lane = threadIdx.x & 63, b = blockIdx.y;
     const long long i = (long long)blockIdx.x * (64 * VMAP_WAVES) + threadIdx.x;  // the frame's row
-    int cnt = a.counts[b];
-    cnt = cnt < a.cap ? cnt : a.cap;
+    const int cnt = vmap_rows_of(a.counts, b, a.cap);
     if (i - lane >= cnt) return;  // the whole wavefront: no row of the frame in it (a count <= 0 included)
-    const MapWs w = map_ws(a);
-    if (__shfl(overflowed(w.head), 0)) return;  // the whole wavefront: the map's content means nothing any more
+    uint32_t *head = vmap_head(a.map);
+    if (__shfl(vmap_overflowed_meanwhile(head), 0)) return;  // the whole wavefront: the map's content means nothing any more
     const bool valid = i < cnt, colors = a.color != nullptr;
     const size_t o = (size_t)b * a.cap + (size_t)(valid ? i : 0);
     const double *pose = a.poses + (size_t)b * 12;
@@ -126,13 +109,7 @@ __global__ __launch_bounds__(64 * VMAP_WAVES) void k_vmap_insert(VoxelMapArgs a)
     double x = 0.0, y = 0.0, z = 0.0;
     long long wt = 1;
     if (valid) {
-        if (DT == VMAP_F32) {
-            const float *p = static_cast<const float *>(a.xyz) + 3 * o;
-            x = (double)p[0], y = (double)p[1], z = (double)p[2];
-        } else {
-            const double *p = static_cast<const double *>(a.xyz) + 3 * o;
-            x = p[0], y = p[1], z = p[2];
-        }
+        vmap_load_row<DT>(a.xyz, o, x, y, z);
         if (a.weight) wt = a.weight[o];
         keep = wt > 0;
     }
@@ -140,19 +117,15 @@ __global__ __launch_bounds__(64 * VMAP_WAVES) void k_vmap_insert(VoxelMapArgs a)
     uint32_t u[3] = {0u, 0u, 0u};
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-        const double P = ((pose[3 * k] * x + pose[3 * k + 1] * y) + pose[3 * k + 2] * z) + pose[9 + k];
-        keep = keep && a.lo[k] < P && P < a.hi[k];  // false for NaN
-        const double t = keep ? (P - a.lo[k]) / a.size : 0.0;
-        long long c = (long long)t;
-        if (c > a.nc[k] - 1) c = a.nc[k] - 1;
-        long long f = (long long)((t - (double)c) * 65536.0);
-        if (f > 65535) f = 65535;
-        u[k] = (uint32_t)f;
-        key |= (unsigned long long)c << (20 * k);
+        double t;
+        long long c;
+        keep = vmap_cell(a, pose, k, x, y, z, keep, t, c);
+        u[k] = (uint32_t)vmap_offset(t, c);
+        key |= vmap_key_part(c, k);
     }
     if (!keep) key = VMAP_EMPTY;
     const int n_dropped = __popcll(__ballot(valid && !keep));
-    if (lane == 0 && n_dropped) atomicAdd(w.dropped, (unsigned long long)n_dropped);
+    if (lane == 0 && n_dropped) atomicAdd(vmap_dropped(a.map), (unsigned long long)n_dropped);
 
     unsigned long long n = (unsigned long long)wt, m = 1, S[3], C[4] = {0ull, 0ull, 0ull, 0ull};
 #pragma unroll
@@ -181,18 +154,18 @@ __global__ __launch_bounds__(64 * VMAP_WAVES) void k_vmap_insert(VoxelMapArgs a)
         issue = keep && run.tail;
     }
     bool claimed = false;
-    if (issue) claimed = vmap_add<COUNT_ATOMICS>(a, w, key, n, m, (uint32_t)(a.seq0 + b), S, C, colors);
+    if (issue) claimed = vmap_add<COUNT_ATOMICS>(a, head, key, n, m, (uint32_t)(a.seq0 + b), S, C, colors);
     const uint32_t n_claimed = (uint32_t)__popcll(__ballot(claimed));  // every lane of the wavefront gets here
     if (lane == 0 && n_claimed) {
-        const bool over = atomicAdd(w.head, n_claimed) + n_claimed > (uint32_t)a.capacity;
-        if (over) atomicOr(w.head + 1, 1u);
+        const bool over = atomicAdd(head, n_claimed) + n_claimed > (uint32_t)a.capacity;
+        if (over) atomicOr(head + 1, 1u);
         if (COUNT_ATOMICS) atomicAdd(a.counters + 1, over ? 2ull : 1ull);
     }
 }
 
 // Is slot h's entry a row of the read-out?
 __device__ __forceinline__ bool qualifies(const VoxelMapArgs &a, const unsigned long long *e) {
-    return e[0] != VMAP_EMPTY && (long long)e[1] >= a.min_n && (long long)e[9] >= a.min_rows && (int32_t)(e[10] >> 32) >= a.since;
+    return e[VMAP_KEY] != VMAP_EMPTY && vmap_passes(a, e);
 }
 
 __global__ __launch_bounds__(64 * VMAP_WAVES) void k_vmap_count(VoxelMapArgs a) {
@@ -200,34 +173,34 @@ __global__ __launch_bounds__(64 * VMAP_WAVES) void k_vmap_count(VoxelMapArgs a) 
     const uint32_t tile = blockIdx.x * VMAP_WAVES + (threadIdx.x >> 6);
     const uint32_t n_tiles = (uint32_t)(((size_t)1 << a.log2_slots) / VMAP_TILE);
     if (tile >= n_tiles) return;  // the whole wavefront
-    const MapWs w = map_ws(a);
+    const unsigned long long *table = vmap_table(a.map);
     int total = 0;
-    if (!w.head[1]) {
+    if (!vmap_overflowed_before(a.map)) {
         for (int s = 0; s < VMAP_TILE / 64; s++) {
             const size_t h = (size_t)tile * VMAP_TILE + (size_t)(s * 64 + lane);
-            total += __popcll(__ballot(qualifies(a, w.table + h * VMAP_ENTRY_WORDS)));
+            total += __popcll(__ballot(qualifies(a, table + h * VMAP_ENTRY_WORDS)));
         }
     }
-    if (lane == 0) w.tiles[tile] = total;
+    if (lane == 0) vmap_tiles(a.map, a.log2_slots)[tile] = total;
 }
 
 __global__ __launch_bounds__(256) void k_vmap_scan(VoxelMapArgs a) {
     __shared__ int s_wave[4];
     const int tid = threadIdx.x;
-    const MapWs w = map_ws(a);
+    int32_t *tiles = vmap_tiles(a.map, a.log2_slots);
     const int n_tiles = (int)(((size_t)1 << a.log2_slots) / VMAP_TILE);  // 4 .. 2^19
     const int per = (n_tiles + 255) / 256;
     const int lo = tid * per < n_tiles ? tid * per : n_tiles, hi = lo + per < n_tiles ? lo + per : n_tiles;
     int own = 0;
-    for (int k = lo; k < hi; k++) own += w.tiles[k];
+    for (int k = lo; k < hi; k++) own += tiles[k];
     int total;
     int run = block_exclusive_scan<256>(own, s_wave, &total);  // every thread gets here
     for (int k = lo; k < hi; k++) {
-        const int c = w.tiles[k];
-        w.tiles[k] = run;
+        const int c = tiles[k];
+        tiles[k] = run;
         run += c;
     }
-    if (tid == 255) *a.count_out = w.head[1] ? -1 : run;  // the last thread's run ends at the total (<= slots <= 2^27)
+    if (tid == 255) *a.count_out = vmap_overflowed_before(a.map) ? -1 : run;  // the last thread's run ends at the total (<= slots <= 2^27)
 }
 
 template <int DT>
@@ -236,23 +209,22 @@ __global__ __launch_bounds__(64 * VMAP_WAVES) void k_vmap_write(VoxelMapArgs a) 
     const uint32_t tile = blockIdx.x * VMAP_WAVES + (threadIdx.x >> 6);
     const uint32_t n_tiles = (uint32_t)(((size_t)1 << a.log2_slots) / VMAP_TILE);
     if (tile >= n_tiles) return;  // the whole wavefront
-    const MapWs w = map_ws(a);
-    if (w.head[1]) return;  // overflowed: no rows
-    int row = w.tiles[tile];
+    if (vmap_overflowed_before(a.map)) return;  // no rows
+    int row = vmap_tiles(a.map, a.log2_slots)[tile];
     for (int s = 0; s < VMAP_TILE / 64 && row < a.out_capacity; s++) {  // rows only grow: nothing later is stored either
         const size_t h = (size_t)tile * VMAP_TILE + (size_t)(s * 64 + lane);
-        const unsigned long long *e = w.table + h * VMAP_ENTRY_WORDS;
+        const unsigned long long *e = vmap_table(a.map) + h * VMAP_ENTRY_WORDS;
         const bool q = qualifies(a, e);
         const unsigned long long mask = __ballot(q);
         const int r = row + lanes_below(mask);
         row += __popcll(mask);
         if (!q || r >= a.out_capacity) continue;
-        const unsigned long long key = e[0], n = e[1];
+        const unsigned long long key = e[VMAP_KEY], n = e[VMAP_N];
 #pragma unroll
         for (int k = 0; k < 3; k++) {
-            const int32_t ci = (int32_t)((key >> (20 * k)) & 0xFFFFFull);
+            const int32_t ci = vmap_key_cell(key, k);
             const double c = (double)ci;
-            const double p = a.lo[k] + (c + ((double)(long long)e[2 + k] + 0.5 * (double)(long long)n) / (65536.0 * (double)(long long)n)) * a.size;
+            const double p = a.lo[k] + (c + ((double)(long long)e[VMAP_S + k] + 0.5 * (double)(long long)n) / (65536.0 * (double)(long long)n)) * a.size;
             if (DT == VMAP_F32) static_cast<float *>(a.xyz_out)[3 * (size_t)r + k] = (float)p;
             else static_cast<double *>(a.xyz_out)[3 * (size_t)r + k] = p;
             if (a.cell_out) a.cell_out[3 * (size_t)r + k] = ci;
@@ -260,13 +232,13 @@ __global__ __launch_bounds__(64 * VMAP_WAVES) void k_vmap_write(VoxelMapArgs a) 
         if (a.color_out) {
             uint32_t c = 0;
 #pragma unroll
-            for (int j = 0; j < 4; j++) c |= (uint32_t)((2ull * e[5 + j] + n) / (2ull * n)) << (8 * j);  // <= 255
+            for (int j = 0; j < 4; j++) c |= (uint32_t)((2ull * e[VMAP_C + j] + n) / (2ull * n)) << (8 * j);  // <= 255
             reinterpret_cast<uint32_t *>(a.color_out)[r] = c;
         }
         if (a.n_out) a.n_out[r] = (long long)n;
-        if (a.m_out) a.m_out[r] = (long long)e[9];
-        if (a.first_out) a.first_out[r] = (int32_t)(uint32_t)e[10];
-        if (a.last_out) a.last_out[r] = (int32_t)(e[10] >> 32);
+        if (a.m_out) a.m_out[r] = (long long)e[VMAP_M];
+        if (a.first_out) a.first_out[r] = (int32_t)vmap_first_seq(e[VMAP_SEQ]);
+        if (a.last_out) a.last_out[r] = (int32_t)vmap_last_seq(e[VMAP_SEQ]);
         a.key_out[r] = (long long)key;
     }
 }

@@ -1,7 +1,6 @@
 // Group (R) of include/stereo_vision_hip.h: a frame's rows matched against the voxel map of (Q) over candidate poses
 // (voxel_match_kernels.hip).  Everything here is argument checking and launch set-up; every check runs before anything is enqueued, and a
-// refused call leaves its text for sv_last_error(NULL).  The checks of the map's spec and buffer are (Q)'s, restated: voxel_map.cpp keeps
-// its own.
+// refused call leaves its text for sv_last_error(NULL).  The check of the map's spec and buffer is stage_glue.h's.
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
@@ -19,25 +18,6 @@ namespace {
 using namespace sv::glue;
 
 std::atomic<int> g_group{0};
-
-bool misaligned(const void *p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
-// NULL for a spec (Q) admits, else what is wrong with it; nc = the cells per axis of a good spec.
-const char *check_spec(const sv_voxel_map_spec *s, int *nc) {
-    if (!s) return "sv_voxel_match: spec is NULL";
-    for (int k = 0; k < 7; k++)
-        if (s->reserved[k] != 0) return "sv_voxel_match: a reserved word of the spec is not 0";
-    if (!(s->size > 0.0) || !isfinite(s->size)) return "sv_voxel_match: size is not a finite number > 0";
-    for (int k = 0; k < 3; k++) {
-        if (!isfinite(s->lo[k]) || !isfinite(s->hi[k])) return "sv_voxel_match: the box must be finite";
-        if (!(s->lo[k] < s->hi[k])) return "sv_voxel_match: the box needs lo < hi on every axis";
-        const double cells = ceil((s->hi[k] - s->lo[k]) / s->size);  // +inf where the difference or the quotient overflows
-        if (!(cells <= 1048576.0)) return "sv_voxel_match: more than 2^20 cells on an axis";
-        nc[k] = cells < 1.0 ? 1 : (int)cells;
-    }
-    if (sv_voxel_map_slots(s->capacity) < 0) return "sv_voxel_match: capacity outside 1 .. 2^26";
-    return nullptr;
-}
 
 // NULL for a shape the kernels can index, else what is wrong with it.
 const char *check_shape(int cap, int n_poses, int batch) {
@@ -75,11 +55,8 @@ int sv_voxel_match_workspace(int cap, int n_poses, int batch, size_t *bytes) {
 int sv_voxel_match_device(const void *map, size_t map_bytes, const sv_voxel_map_spec *spec, const void *xyz, int dtype, const int32_t *n, const int32_t *counts,
                           const double *poses, int batch, int cap, int n_poses, int64_t min_n, int64_t min_rows, int since, int32_t *inside, int32_t *hits,
                           int64_t *weight, int64_t *d2, int32_t *best, int64_t *best_weight, int64_t *best_d2, void *workspace, size_t workspace_bytes, void *stream) {
-    int nc[3];
-    if (const char *bad = check_spec(spec, nc)) return refuse(bad);
-    const int64_t slots = sv_voxel_map_slots(spec->capacity);
-    if (!map || misaligned(map, 16) || map_bytes < sv_voxel_map_bytes(spec->capacity))
-        return refuse("sv_voxel_match: the map is NULL, not 16-byte aligned or smaller than sv_voxel_map_bytes");
+    int nc[3], l;
+    if (const char *bad = check_voxel_map("sv_voxel_match", map, map_bytes, spec, nc, &l)) return refuse(bad);
     if (dtype != SV_CLOUD_F32 && dtype != SV_CLOUD_F64) return refuse("sv_voxel_match: dtype is not SV_CLOUD_F32 / SV_CLOUD_F64");
     if (const char *bad = check_shape(cap, n_poses, batch)) return refuse(bad);
     if (batch > 0 && (!counts || !poses)) return refuse("sv_voxel_match: counts or poses is NULL");
@@ -103,8 +80,7 @@ int sv_voxel_match_device(const void *map, size_t map_bytes, const sv_voxel_map_
     sv::VoxelMatchArgs a;
     memset(&a, 0, sizeof(a));
     a.map = static_cast<const uint8_t *>(map);
-    while (((int64_t)1 << a.log2_slots) < slots) a.log2_slots++;
-    a.size = spec->size;
+    a.log2_slots = l, a.size = spec->size;
     for (int k = 0; k < 3; k++) a.lo[k] = spec->lo[k], a.hi[k] = spec->hi[k], a.nc[k] = nc[k];
     a.xyz = xyz, a.weight = n, a.counts = counts, a.poses = poses;
     a.cap = cap, a.B = batch, a.P = n_poses;

@@ -1,7 +1,6 @@
 // A frame's rows matched against the world-fixed voxel map over candidate 3-D poses: include/stereo_vision_hip.h (R), restated in
-// stereo_vision/sv.py (voxel_map_match).  The map's buffer is voxel_map_kernels.h's and is only read; the cell rule and slot_of are
-// voxel_map_kernels.hip's, restated here (tests/test_voxel_match.py holds the two against each other).  Three kernels, no atomics, and no
-// workgroup waits for another:
+// stereo_vision/sv.py (voxel_map_match).  The map's buffer is voxel_map_kernels.h's and is only read; the row's way into a cell, the
+// probe and the filters are voxel_map_table.h's.  Three kernels, no atomics, and no workgroup waits for another:
 //
 //   scores  grid (row chunk, candidate group, frame).  A lane holds VMATCH_ROWS rows of its frame - x, y, z widened to double, and w -
 //           in registers; the workgroup walks its group's candidates, whose twelve pose words every lane reads from the same address (a
@@ -26,6 +25,7 @@
 #include <limits.h>
 #include <stdint.h>
 
+#include "voxel_map_table.h"
 #include "voxel_match_kernels.h"
 #include "wave_ops.h"
 
@@ -33,32 +33,10 @@ namespace sv {
 
 namespace {
 
-constexpr unsigned long long VMAP_EMPTY = ~0ull;
-
-__device__ __forceinline__ uint32_t slot_of(const VoxelMatchArgs &a, unsigned long long key) {
-    return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> (64 - a.log2_slots));  // log2_slots in 10 .. 27
-}
-
-__device__ __forceinline__ bool overflowed(const VoxelMatchArgs &a) { return reinterpret_cast<const uint32_t *>(a.map)[1] != 0u; }
-
 // The rows frame b has: min(counts[b], cap), 0 for a count below 1.
 __device__ __forceinline__ int rows_of(const VoxelMatchArgs &a, int b) {
-    int cnt = a.counts[b];
-    cnt = cnt < a.cap ? cnt : a.cap;
+    const int cnt = vmap_rows_of(a.counts, b, a.cap);
     return cnt > 0 ? cnt : 0;
-}
-
-// The entry of `key`, or NULL where the map holds none.
-__device__ __forceinline__ const unsigned long long *find(const VoxelMatchArgs &a, const unsigned long long *table, unsigned long long key) {
-    const uint32_t last = (uint32_t)(((size_t)1 << a.log2_slots) - 1);
-    uint32_t h = slot_of(a, key);
-    for (uint32_t probe = 0; probe <= last; probe++, h = (h + 1) & last) {
-        const unsigned long long *e = table + (size_t)h * VMAP_ENTRY_WORDS;
-        const unsigned long long k = e[0];
-        if (k == key) return e;
-        if (k == VMAP_EMPTY) return nullptr;
-    }
-    return nullptr;  // a full table without the key
 }
 
 template <int DT>
@@ -69,10 +47,10 @@ __global__ __launch_bounds__(VMATCH_THREADS) void k_vmatch_scores(VoxelMatchArgs
     const int p0 = (int)blockIdx.y << a.log_group;                                    // < P
     const int np = a.P - p0 < (1 << a.log_group) ? a.P - p0 : (1 << a.log_group);  // candidates of this workgroup, >= 1
     const int rows = rows_of(a, b);
-    if (overflowed(a) || (long long)chunk * VMATCH_TILE >= rows) return;  // the whole workgroup
+    if (vmap_overflowed_before(a.map) || (long long)chunk * VMATCH_TILE >= rows) return;  // the whole workgroup
     for (int i = tid; i < (VMATCH_THREADS / 64 << VMATCH_MAX_LOG_GROUP) * VMATCH_PLANES; i += VMATCH_THREADS) (&s_acc[0][0][0])[i] = 0ull;
     __syncthreads();
-    const unsigned long long *table = reinterpret_cast<const unsigned long long *>(a.map + VMAP_HEAD_BYTES);
+    const unsigned long long *table = vmap_table(a.map);
 
     for (long long tile = chunk; tile * VMATCH_TILE < rows; tile += a.n_chunks) {  // the same trips for every thread
         double x[VMATCH_ROWS], y[VMATCH_ROWS], z[VMATCH_ROWS];
@@ -83,13 +61,7 @@ __global__ __launch_bounds__(VMATCH_THREADS) void k_vmatch_scores(VoxelMatchArgs
             x[r] = y[r] = z[r] = 0.0, wt[r] = 0;  // a weight of 0: not kept
             if (i < rows) {
                 const size_t o = (size_t)b * a.cap + (size_t)i;
-                if (DT == VMAP_F32) {
-                    const float *p = static_cast<const float *>(a.xyz) + 3 * o;
-                    x[r] = (double)p[0], y[r] = (double)p[1], z[r] = (double)p[2];
-                } else {
-                    const double *p = static_cast<const double *>(a.xyz) + 3 * o;
-                    x[r] = p[0], y[r] = p[1], z[r] = p[2];
-                }
+                vmap_load_row<DT>(a.xyz, o, x[r], y[r], z[r]);
                 wt[r] = a.weight ? a.weight[o] : 1;
             }
         }
@@ -103,27 +75,24 @@ __global__ __launch_bounds__(VMATCH_THREADS) void k_vmatch_scores(VoxelMatchArgs
                 long long u[3];
 #pragma unroll
                 for (int k = 0; k < 3; k++) {
-                    const double P = ((pose[3 * k] * x[r] + pose[3 * k + 1] * y[r]) + pose[3 * k + 2] * z[r]) + pose[9 + k];
-                    keep = keep && a.lo[k] < P && P < a.hi[k];  // false for NaN
-                    const double t = keep ? (P - a.lo[k]) / a.size : 0.0;
-                    long long cell = (long long)t;
-                    if (cell > a.nc[k] - 1) cell = a.nc[k] - 1;
-                    long long f = (long long)((t - (double)cell) * 65536.0);
-                    if (f > 65535) f = 65535;
-                    u[k] = f;
-                    key |= (unsigned long long)cell << (20 * k);
+                    double t;
+                    long long cell;
+                    keep = vmap_cell(a, pose, k, x[r], y[r], z[r], keep, t, cell);
+                    u[k] = vmap_offset(t, cell);
+                    key |= vmap_key_part(cell, k);
                 }
                 if (!keep) continue;
                 cnt += 1ull;
-                const unsigned long long *e = find(a, table, key);
-                if (!e) continue;
-                const unsigned long long n = e[1];
-                if (!((long long)n >= a.min_n && (long long)e[9] >= a.min_rows && (int32_t)(e[10] >> 32) >= a.since) || n == 0ull) continue;
+                const long long at = vmap_find(table, a.log2_slots, key);
+                if (at < 0) continue;
+                const unsigned long long *e = table + (size_t)at * VMAP_ENTRY_WORDS;
+                const unsigned long long n = e[VMAP_N];
+                if (!vmap_passes(a, e) || n == 0ull) continue;
                 cnt += 1ull << 32;
                 wsum += (unsigned long long)wt[r];
 #pragma unroll
                 for (int k = 0; k < 3; k++) {
-                    const long long d = u[k] - (long long)(e[2 + k] / n);
+                    const long long d = u[k] - (long long)(e[VMAP_S + k] / n);
                     dsum += (unsigned long long)(d * d);
                 }
             }
@@ -168,7 +137,7 @@ __global__ __launch_bounds__(VMATCH_THREADS) void k_vmatch_sums(VoxelMatchArgs a
     const int tid = (int)threadIdx.x, b = (int)blockIdx.y, p = (int)blockIdx.x * VMATCH_GROUPS + tid;
     const int rows = rows_of(a, b);
     const int tiles = (int)(((long long)rows + VMATCH_TILE - 1) / VMATCH_TILE);
-    const int live = overflowed(a) ? 0 : (tiles < a.n_chunks ? tiles : a.n_chunks);  // the chunks whose partials were stored
+    const int live = vmap_overflowed_before(a.map) ? 0 : (tiles < a.n_chunks ? tiles : a.n_chunks);  // the chunks whose partials were stored
     unsigned long long cnt = 0, wsum = 0, dsum = 0;
     if (p < a.P) {
         const unsigned long long *in = a.partials + (size_t)b * a.n_chunks * VMATCH_PLANES * (size_t)a.P + (size_t)p;
@@ -195,7 +164,7 @@ __global__ __launch_bounds__(VMATCH_THREADS) void k_vmatch_best(VoxelMatchArgs a
     const bool live = tid < groups;
     block_best(s_w, s_d, s_i, live ? in[tid].weight : LLONG_MIN, live ? in[tid].d2 : 0ll, live ? in[tid].index : INT_MAX);
     if (tid == 0) {
-        const bool over = overflowed(a);
+        const bool over = vmap_overflowed_before(a.map);
         a.best[b] = over ? -1 : s_i[0], a.best_weight[b] = over ? 0ll : s_w[0], a.best_d2[b] = over ? 0ll : s_d[0];
     }
 }

@@ -255,13 +255,11 @@ def test_header_build_and_loader_agree(sv):
     assert all(n in sv.__doc__ for n in ("voxel_map_carry", "voxel_map_shifted", "voxel_map_recenter_shift")) and "(S)" in sv.__doc__
     source = open(os.path.join(build.CSRC, "voxel_carry_kernels.hip")).read()
     assert "asm" not in source and "atomicAdd(float" not in source
-    # slot_of and the probing are restated from the insert kernel: the same text in both files
-    insert = open(os.path.join(build.CSRC, "voxel_map_kernels.hip")).read()
-    squeeze = lambda s: re.sub(r"\s+", "", s)  # noqa: E731
-    for line in ("return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> (64 - a.log2_slots));", "for (uint32_t probe = 0; probe <= last; probe++, h = (h + 1) & last) {",
-                 "if (old != VMAP_EMPTY && old != key) continue;", "const uint32_t last = (uint32_t)(((size_t)1 << a.log2_slots) - 1);",
-                 "uint32_t overflowed(const uint32_t *head) { return __hip_atomic_load(head + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }"):
-        assert squeeze(line) in squeeze(source) and squeeze(line) in squeeze(insert), line
+    # slot_of, the claiming probe with its look at the overflow flag, and the filters are the map's own, defined once
+    header = cases.check_map_table(build)
+    assert source.count("vmap_claim(") == 1 and source.count("vmap_passes(") == 1
+    for line in ("if (old != VMAP_EMPTY && old != key) continue;", "if ((probe & 15) == 15 && vmap_overflowed_meanwhile(head)) break;"):
+        assert cases.squeeze(line) in header and cases.squeeze(line) not in cases.squeeze(source), line
 
 
 def test_cli_argument_errors(sv, tmp_path):

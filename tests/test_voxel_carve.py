@@ -318,19 +318,16 @@ def test_header_build_and_loader_agree(sv):
     code = re.sub(r"//.*", "", source)
     assert "asm" not in code and "float" not in re.sub(r"const float \*p|static_cast<const float \*>", "", code) and code.count("atomicAdd(a.miss") == 1
     assert len(re.findall(r"\batomic\w*\(", code)) == 3  # the miss, and one flush of the counters per workgroup in two kernels
-    # slot_of, the transform, the kept rule and the cell rule are restated from the insert kernel, the read-only probe from the match kernel
-    insert = open(os.path.join(build.CSRC, "voxel_map_kernels.hip")).read()
+    # slot_of, the transform, the kept rule, the cell rule and the read-only probe are the map's own, defined once; the match uses the same probe
+    header = cases.check_map_table(build)
     match = open(os.path.join(build.CSRC, "voxel_match_kernels.hip")).read()
-    squeeze = lambda s: re.sub(r"\s+", "", s)  # noqa: E731
-    for line in ("return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> (64 - a.log2_slots));",
-                 "const double P = ((pose[3 * k] * x + pose[3 * k + 1] * y) + pose[3 * k + 2] * z) + pose[9 + k];", "keep = keep && a.lo[k] < P && P < a.hi[k];",
-                 "const double t = keep ? (P - a.lo[k]) / a.size : 0.0;", "long long c = (long long)t;", "if (c > a.nc[k] - 1) c = a.nc[k] - 1;", "if (a.weight) wt = a.weight[o];",
-                 "keep = wt > 0;", "cnt = cnt < a.cap ? cnt : a.cap;"):
-        assert squeeze(source).count(squeeze(line)) >= 1 and squeeze(line) in squeeze(insert), line
-    for line in ("const uint32_t last = (uint32_t)(((size_t)1 << a.log2_slots) - 1);", "for (uint32_t probe = 0; probe <= last; probe++, h = (h + 1) & last) {",
-                 "const unsigned long long *e = table + (size_t)h * VMAP_ENTRY_WORDS;", "const unsigned long long k = e[0];", "if (k == VMAP_EMPTY) return"):
-        assert squeeze(line) in squeeze(source) and squeeze(line) in squeeze(match), line
-    assert squeeze(source).count(squeeze("keep = keep && a.lo[k] < P && P < a.hi[k];")) == 2  # the sensor and the row
+    assert cases.squeeze("if (k == VMAP_EMPTY) return") in header and code.count("vmap_find(") == 1 and match.count("vmap_find(") == 1
+    assert code.count("vmap_slot_of(") == 1 and code.count("vmap_rows_of(") == 1
+    assert code.count("vmap_cell(") == 2  # the sensor and the row
+    # the weight's part of the kept rule stays with the insert's, restated: the same text in both files
+    insert = open(os.path.join(build.CSRC, "voxel_map_kernels.hip")).read()
+    for line in ("if (a.weight) wt = a.weight[o];", "keep = wt > 0;"):
+        assert cases.squeeze(line) in cases.squeeze(source) and cases.squeeze(line) in cases.squeeze(insert), line
 
 
 # ---------------------------------------------------------------------------------------------------------------- GPU

@@ -247,6 +247,13 @@ def test_header_build_and_loader_agree(sv, eng):
     assert all(n in sv.__doc__ for n in ("voxel_map_params", "voxel_map_pose", "voxel_map_insert", "voxel_map_rows", "voxel_map_slot_of")) and "(Q)" in sv.__doc__
     source = open(os.path.join(build.CSRC, "voxel_map_kernels.hip")).read()
     assert "asm" not in source and "atomicAdd(float" not in source
+    header = cases.check_map_table(build)
+    assert "sv::vmap_slot_of(" in open(os.path.join(build.CSRC, "voxel_map.cpp")).read()  # test_the_hash covers the function the kernels inline
+    # the insert keeps the claiming probe around its update, restated from the header's vmap_claim: the same text in both files
+    for line in ("const uint32_t last = (uint32_t)(((size_t)1 << log2_slots) - 1);", "uint32_t h = vmap_slot_of(log2_slots, key)", cases.PROBE_LOOP,
+                 "if ((probe & 15) == 15 && vmap_overflowed_meanwhile(head)) break;", "unsigned long long *e = table + (size_t)h * VMAP_ENTRY_WORDS;",
+                 "const unsigned long long old = atomicCAS(e + VMAP_KEY, VMAP_EMPTY, key);", "if (old != VMAP_EMPTY && old != key) continue;", "atomicOr(head + 1, 1u);"):
+        assert cases.squeeze(line) in cases.squeeze(source) and cases.squeeze(line) in header, line
 
 
 def test_cli_argument_errors(sv, tmp_path):

@@ -215,13 +215,9 @@ def test_header_build_and_loader_agree(sv):
     assert all(n in sv.__doc__ for n in ("voxel_map_pose_window", "voxel_map_match")) and "(R)" in sv.__doc__
     source = open(os.path.join(build.CSRC, "voxel_match_kernels.hip")).read()
     assert "asm" not in source and "atomic" not in source.replace("no atomics", "")  # plain loads and stores only
-    # the cell rule and slot_of are restated from the insert kernel: the same text in both files
-    insert = open(os.path.join(build.CSRC, "voxel_map_kernels.hip")).read()
-    squeeze = lambda s: re.sub(r"\s+", "", s)  # noqa: E731
-    assert squeeze("return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> (64 - a.log2_slots));") in squeeze(source) and \
-        squeeze("return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> (64 - a.log2_slots));") in squeeze(insert)
-    for line in ("keep = keep && a.lo[k] < P && P < a.hi[k];", "const double t = keep ? (P - a.lo[k]) / a.size : 0.0;", "if (f > 65535) f = 65535;"):
-        assert squeeze(line) in squeeze(source) and squeeze(line) in squeeze(insert), line
+    # the cell rule, the offsets, slot_of and the probe are the map's own, defined once
+    cases.check_map_table(build)
+    assert all(source.count(call) == 1 for call in ("vmap_cell(", "vmap_offset(", "vmap_find(", "vmap_passes("))
 
 
 # ---------------------------------------------------------------------------------------------------------------- GPU

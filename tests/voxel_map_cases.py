@@ -3,6 +3,8 @@ ints only.  A case is (params, calls): params a dict of lo, hi, size, capacity a
 arrays as voxel_map_insert takes them, one call per update.  The painted cases build wavefront layouts lane by lane: a frame's row i is
 lane i % 64 of wavefront i // 64, and four wavefronts make a workgroup."""
 import math
+import os
+import re
 
 import numpy as np
 
@@ -10,6 +12,47 @@ IDENTITY = np.array([1.0, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0])
 QUARTER = np.array([0.0, -1, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0])  # (c, s) = (0, 1), exact
 FIELDS = ("xyz", "color", "cell", "n", "m", "first_seq", "last_seq", "key")
 BOX16 = dict(lo=(0.0, 0.0, 0.0), hi=(16.0, 16.0, 16.0), size=1.0, capacity=512)  # 16 cells per axis, a table of 1024 slots
+MAP_STAGES = ("voxel_map", "voxel_match", "voxel_carry", "voxel_carve")  # each a <stage>_kernels.hip and a <stage>.cpp
+# The texts that define the map's table and cell rules, and how often csrc/voxel_map_table.h states each: once, but for the probe loop's
+# line, which its read-only probe (vmap_find) and its claiming probe (vmap_claim) have each.  No other file of the stages states one,
+# but for the insert's copy of the claiming probe (voxel_map_kernels.hip: vmap_add), which test_voxel_map.py holds against the header.
+PROBE_LOOP = "for (uint32_t probe = 0; probe <= last; probe++, h = (h + 1) & last) {"
+TABLE_TEXTS = {
+    "0x9E3779B97F4A7C15": 1,
+    "VMAP_EMPTY = ~0ull": 1,
+    PROBE_LOOP: 2,
+    "__hip_atomic_load(head + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)": 1,
+    "const double P = ((pose[3 * k] * x + pose[3 * k + 1] * y) + pose[3 * k + 2] * z) + pose[9 + k];": 1,
+    "keep = keep && a.lo[k] < P && P < a.hi[k];": 1,
+    "t = keep ? (P - a.lo[k]) / a.size : 0.0;": 1,
+    "c = (long long)t;": 1,
+    "if (c > a.nc[k] - 1) c = a.nc[k] - 1;": 1,
+    "const long long f = (long long)((t - (double)c) * 65536.0);": 1,
+    "return f > 65535 ? 65535 : f;": 1,
+    "return cnt < cap ? cnt : cap;": 1,
+}
+
+
+def squeeze(text):
+    return re.sub(r"\s+", "", text)
+
+
+def check_map_table(build):
+    """The rules that the stages of the map share are defined once, in csrc/voxel_map_table.h.  Returns the squeezed text of the header."""
+    assert "voxel_map_table.h" in build.HEADERS
+    read = lambda name: open(os.path.join(build.CSRC, name)).read()  # noqa: E731
+    header = squeeze(read("voxel_map_table.h"))
+    for stage in MAP_STAGES:
+        kernels = read(stage + "_kernels.hip")
+        assert '#include "voxel_map_table.h"' in kernels, stage
+        # an entry's words go by their names (VMAP_N ...), never by a bare number
+        assert re.findall(r"(?<!int )\b[ed]\[\d", re.sub(r"//.*", "", kernels)) == [], stage
+    others = {name: squeeze(read(name)) for stage in MAP_STAGES for name in (stage + "_kernels.hip", stage + ".cpp")}
+    for text, times in TABLE_TEXTS.items():
+        assert header.count(squeeze(text)) == times, text
+        for name, source in others.items():
+            assert source.count(squeeze(text)) == (1 if (text, name) == (PROBE_LOOP, "voxel_map_kernels.hip") else 0), (text, name)
+    return header
 
 
 def _cells(params):
