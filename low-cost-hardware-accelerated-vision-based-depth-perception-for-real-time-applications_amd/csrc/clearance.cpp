@@ -26,7 +26,7 @@ extern "C" {
 
 int sv_clearance_workspace(int rows, int cols, size_t *bytes) {
     if (!bytes) return refuse("sv_clearance_workspace: bytes is NULL");
-    if (rows < 1 || rows > 32768 || cols < 1 || cols > 32768) return refuse("sv_clearance_workspace: rows or cols outside 1..32768");
+    if (const char *bad = check_map_shape("sv_clearance_workspace", rows, cols)) return refuse(bad);
     *bytes = align16((size_t)rows * cols);  // the column pass's byte per cell
     return SV_OK;
 }
@@ -34,15 +34,15 @@ int sv_clearance_workspace(int rows, int cols, size_t *bytes) {
 int sv_clearance_device(const int16_t *logodds, const int32_t *last_seen, int rows, int cols, int radius, int t_occ, int unknown, uint16_t *d2, void *workspace,
                         size_t workspace_bytes, void *stream) {
     if (!logodds || !d2 || !workspace) return refuse("sv_clearance: logodds, d2 or the workspace is NULL");
-    if (rows < 1 || rows > 32768 || cols < 1 || cols > 32768) return refuse("sv_clearance: rows or cols outside 1..32768");
+    if (const char *bad = check_map_shape("sv_clearance", rows, cols)) return refuse(bad);
     if (radius < 1 || radius > sv::CLEARANCE_MAX_R) return refuse("sv_clearance: radius outside 1..254");
     if (t_occ < -32768 || t_occ > 32767) return refuse("sv_clearance: t_occ outside the int16 range");
     if (unknown != 0 && unknown != 1) return refuse("sv_clearance: unknown is neither 0 nor 1");
     if (unknown == 1 && !last_seen) return refuse("sv_clearance: unknown == 1 needs last_seen");
-    if (reinterpret_cast<uintptr_t>(logodds) & 1) return refuse("sv_clearance: logodds is not 2-byte aligned");
-    if (reinterpret_cast<uintptr_t>(last_seen) & 3) return refuse("sv_clearance: last_seen is not 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d2) & 1) return refuse("sv_clearance: d2 is not 2-byte aligned");
-    if (reinterpret_cast<uintptr_t>(workspace) & 15) return refuse("sv_clearance: the workspace is not 16-byte aligned");
+    if (misaligned(logodds, 2)) return refuse("sv_clearance: logodds is not 2-byte aligned");
+    if (misaligned(last_seen, 4)) return refuse("sv_clearance: last_seen is not 4-byte aligned");
+    if (misaligned(d2, 2)) return refuse("sv_clearance: d2 is not 2-byte aligned");
+    if (misaligned(workspace, 16)) return refuse("sv_clearance: the workspace is not 16-byte aligned");
     const size_t cells = (size_t)rows * cols, need = align16(cells);
     if (workspace_bytes < need) return refuse("sv_clearance: the workspace is smaller than sv_clearance_workspace asks for");
     if (overlap(d2, cells * 2, logodds, cells * 2) || overlap(d2, cells * 2, last_seen, cells * 4) || overlap(d2, cells * 2, workspace, need))
@@ -76,9 +76,9 @@ int sv_clearance_paths_device(const uint16_t *d2, const sv_occupancy_map_spec *m
     if (radius < 1 || radius > sv::CLEARANCE_MAX_R) return refuse("sv_clearance_paths: radius outside 1..254");
     if (!d2 || !centres || !r2) return refuse("sv_clearance_paths: d2, centres or r2 is NULL");
     if (n_paths > 0 && (!poses || !first_hit || !min_d2 || !n_outside)) return refuse("sv_clearance_paths: poses, first_hit, min_d2 or n_outside is NULL");
-    if (reinterpret_cast<uintptr_t>(d2) & 1) return refuse("sv_clearance_paths: d2 is not 2-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(poses) | reinterpret_cast<uintptr_t>(centres)) & 7) return refuse("sv_clearance_paths: poses or centres is not 8-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(r2) | reinterpret_cast<uintptr_t>(first_hit) | reinterpret_cast<uintptr_t>(min_d2) | reinterpret_cast<uintptr_t>(n_outside)) & 3)
+    if (misaligned(d2, 2)) return refuse("sv_clearance_paths: d2 is not 2-byte aligned");
+    if (any_misaligned(8, poses, centres)) return refuse("sv_clearance_paths: poses or centres is not 8-byte aligned");
+    if (any_misaligned(4, r2, first_hit, min_d2, n_outside))
         return refuse("sv_clearance_paths: r2, first_hit, min_d2 or n_outside is not 4-byte aligned");
     for (int k = 0; k < n_discs; k++)
         if (r2[k] < 0 || r2[k] > radius * radius) return refuse("sv_clearance_paths: an r2 is negative or above radius^2, where a saturated cell would hide a hit");
@@ -88,10 +88,7 @@ int sv_clearance_paths_device(const uint16_t *d2, const sv_occupancy_map_spec *m
     memset(&a, 0, sizeof(a));
     a.d2 = d2, a.poses = poses, a.first_hit = first_hit, a.min_d2 = min_d2, a.n_outside = n_outside;
     a.n_paths = n_paths, a.n_steps = n_steps, a.n_discs = n_discs;
-    a.rows = map->rows, a.cols = map->cols, a.top = map->top, a.left = map->left;
-    a.ms = (double)map->scale;
-    a.gx_lo = (double)(map->top - map->rows), a.gx_hi = (double)(map->top - 1);
-    a.gy_lo = (double)(map->left - map->cols), a.gy_hi = (double)(map->left - 1);
+    a.m = sv::map_cells_of(*map);
     sv::ClearanceDiscs discs;
     memset(&discs, 0, sizeof(discs));
     for (int k = 0; k < n_discs; k++) discs.px[k] = centres[2 * k], discs.py[k] = centres[2 * k + 1], discs.r2[k] = r2[k];

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "occupancy_map_cells.h"
+
 namespace sv {
 
 // A column-pass lane owns CLEARANCE_STRIP rows of one column (their source flags are one 64-bit word); a row-pass workgroup owns
@@ -36,9 +38,7 @@ struct ClearancePathsArgs {
     const double *poses;          // [n_paths][n_steps][4] = tx, ty, c, s
     int32_t *first_hit, *min_d2, *n_outside;  // [n_paths] each
     int n_paths, n_steps, n_discs;
-    int rows, cols, top, left;
-    double ms;                          // the map's scale
-    double gx_lo, gx_hi, gy_lo, gy_hi;  // top - rows, top - 1, left - cols, left - 1
+    MapCells m;                   // the map
 };
 
 // The field on `st`: passes & 1 the column pass, passes & 2 the row pass (3 is the call; the others are measurement aids), or - fused -

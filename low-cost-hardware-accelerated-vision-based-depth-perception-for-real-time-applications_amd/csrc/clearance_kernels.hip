@@ -18,12 +18,13 @@
 //           small R (clearance.cpp).
 //
 //   paths   a wavefront per path, its lanes striding over the n_steps x n_discs lookups with the step as the slow index, so that a
-//           lane meets its steps in rising order; the world point in map_match_kernels.hip's arithmetic, word for word; three wave
-//           reductions by shuffle and one store per path and output.  The discs arrive by value and are staged in LDS once.
+//           lane meets its steps in rising order; the world point and its cell by occupancy_map_cells.h, the match's very functions;
+//           three wave reductions by shuffle and one store per path and output.  The discs arrive by value and are staged in LDS once.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "clearance_kernels.h"
+#include "occupancy_map_cells.h"
 #include "wave_ops.h"
 
 namespace sv {
@@ -147,17 +148,11 @@ __global__ __launch_bounds__(CLEARANCE_THREADS) void k_clearance_paths(Clearance
     int first = a.n_steps, least = CLEARANCE_FAR, outside = 0;
     for (int i = lane; i < total; i += 64) {
         const double tx = poses[(size_t)step * 4], ty = poses[(size_t)step * 4 + 1], pc = poses[(size_t)step * 4 + 2], ps = poses[(size_t)step * 4 + 3];
-        const double X = s_px[k], Y = s_py[k];
-        const double Xw = (pc * X - ps * Y) + tx, Yw = (ps * X + pc * Y) + ty;
-        const double gx = floor(Xw * a.ms), gy = floor(Yw * a.ms);
-        bool inside = gx >= a.gx_lo && gx <= a.gx_hi && gy >= a.gy_lo && gy <= a.gy_hi;  // NaN, inf and far away fail before any conversion
-        int r = 0, cc = 0;
-        if (inside) {
-            r = a.top - 1 - (int)gx, cc = a.left - 1 - (int)gy;
-            inside = (unsigned)r < (unsigned)a.rows && (unsigned)cc < (unsigned)a.cols;  // always true here; no input can address outside the map
-        }
-        if (inside) {
-            const int v = a.d2[(size_t)r * a.cols + cc];
+        double Xw, Yw;
+        map_world(tx, ty, pc, ps, s_px[k], s_py[k], Xw, Yw);
+        int r, cc;
+        if (map_cell(a.m, map_grid(a.m, Xw), map_grid(a.m, Yw), r, cc)) {
+            const int v = a.d2[(size_t)r * a.m.cols + cc];
             least = min(least, v);
             if (v <= s_r2[k]) first = min(first, step);
         } else {

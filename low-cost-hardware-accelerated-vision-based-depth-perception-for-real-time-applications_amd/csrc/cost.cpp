@@ -21,7 +21,7 @@ std::atomic<unsigned long long *> g_counters{nullptr};
 
 // NULL for a map the field's int32 costs can hold, else what is wrong with it.
 const char *check_cells(const char *prefix, int rows, int cols) {
-    if (rows < 1 || rows > 32768 || cols < 1 || cols > 32768) return prefixed(prefix, "rows or cols outside 1..32768");
+    if (const char *bad = check_map_shape(prefix, rows, cols)) return bad;
     if ((int64_t)rows * cols > sv::COST_CELLS_MAX) return prefixed(prefix, "rows * cols above 8 000 000, where a cost could reach 2^31 - 1");
     return nullptr;
 }
@@ -48,11 +48,11 @@ extern "C" {
 
 int sv_cost_cells_device(const uint16_t *d2, int rows, int cols, int radius, int r2_block, int soft, int weight, uint8_t *pen, void *stream) {
     if (!d2 || !pen) return refuse("sv_cost_cells: d2 or pen is NULL");
-    if (rows < 1 || rows > 32768 || cols < 1 || cols > 32768) return refuse("sv_cost_cells: rows or cols outside 1..32768");
+    if (const char *bad = check_map_shape("sv_cost_cells", rows, cols)) return refuse(bad);
     if (radius < 1 || radius > 254) return refuse("sv_cost_cells: radius outside 1..254");
     if (r2_block < 0 || r2_block > radius * radius) return refuse("sv_cost_cells: r2_block is negative or above radius^2, where a saturated cell would hide an obstacle");
     if (soft < 0 || soft > sv::COST_PEN_MAX || weight < 0 || weight > sv::COST_PEN_MAX) return refuse("sv_cost_cells: soft or weight outside 0..254");
-    if (reinterpret_cast<uintptr_t>(d2) & 1) return refuse("sv_cost_cells: d2 is not 2-byte aligned");
+    if (misaligned(d2, 2)) return refuse("sv_cost_cells: d2 is not 2-byte aligned");
     const size_t cells = (size_t)rows * cols;
     if (overlap(pen, cells, d2, cells * 2)) return refuse("sv_cost_cells: pen overlaps d2");
 
@@ -80,15 +80,14 @@ int sv_cost_to_goal_device(const uint8_t *pen, int rows, int cols, const int32_t
     if (n_goals < 1 || n_goals > sv::COST_GOALS_MAX) return refuse("sv_cost_to_goal: n_goals outside 1..1024");
     if (init != 0 && init != 1) return refuse("sv_cost_to_goal: init is neither 0 nor 1");
     if (sweeps < 2 || sweeps > sv::COST_SWEEPS_MAX || (sweeps & 1)) return refuse("sv_cost_to_goal: sweeps is odd or outside 2..1024");
-    if ((reinterpret_cast<uintptr_t>(goals) | reinterpret_cast<uintptr_t>(cost) | reinterpret_cast<uintptr_t>(info)) & 3)
+    if (any_misaligned(4, goals, cost, info))
         return refuse("sv_cost_to_goal: goals, cost or info is not 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(workspace) & 15) return refuse("sv_cost_to_goal: the workspace is not 16-byte aligned");
+    if (misaligned(workspace, 16)) return refuse("sv_cost_to_goal: the workspace is not 16-byte aligned");
     const Layout l = layout_of(rows, cols);
     if (workspace_bytes < l.total) return refuse("sv_cost_to_goal: the workspace is smaller than sv_cost_to_goal_workspace asks for");
     const size_t cells = (size_t)rows * cols, goal_bytes = (size_t)n_goals * 8;
-    if (overlap(cost, cells * 4, pen, cells) || overlap(cost, cells * 4, goals, goal_bytes) || overlap(cost, cells * 4, workspace, l.total) || overlap(cost, cells * 4, info, 16) ||
-        overlap(info, 16, pen, cells) || overlap(info, 16, goals, goal_bytes) || overlap(info, 16, workspace, l.total) || overlap(workspace, l.total, pen, cells) ||
-        overlap(workspace, l.total, goals, goal_bytes))
+    const Span spans[5] = {{pen, cells}, {goals, goal_bytes}, {cost, cells * 4}, {info, 16}, {workspace, l.total}};
+    if (outputs_overlap(spans, 5, 2))  // cost is the first output
         return refuse("sv_cost_to_goal: cost, info and the workspace overlap one another, pen or goals");
 
     sv::CostFieldArgs a;
@@ -115,18 +114,13 @@ int sv_cost_routes_device(const int32_t *cost, const uint8_t *pen, int rows, int
     if (capacity < 1 || capacity > 65535) return refuse("sv_cost_routes: capacity outside 1..65535");
     if (!cost || !pen) return refuse("sv_cost_routes: cost or pen is NULL");
     if (n_routes > 0 && (!starts || !cells || !length || !status)) return refuse("sv_cost_routes: starts, cells, length or status is NULL");
-    if ((reinterpret_cast<uintptr_t>(cost) | reinterpret_cast<uintptr_t>(starts) | reinterpret_cast<uintptr_t>(cells) | reinterpret_cast<uintptr_t>(length) |
-         reinterpret_cast<uintptr_t>(status)) & 3)
+    if (any_misaligned(4, cost, starts, cells, length, status))
         return refuse("sv_cost_routes: cost, starts, cells, length or status is not 4-byte aligned");
     if (n_routes == 0) return SV_OK;  // nothing to do
     const size_t map_cells = (size_t)rows * cols, k = (size_t)n_routes, cell_bytes = k * capacity * 4;
-    const struct {
-        const void *p;
-        size_t n;
-    } spans[6] = {{cost, map_cells * 4}, {pen, map_cells}, {starts, k * 8}, {cells, cell_bytes}, {length, k * 4}, {status, k * 4}};
-    for (int o = 3; o < 6; o++)  // each output against every input and every output before it
-        for (int j = 0; j < o; j++)
-            if (overlap(spans[o].p, spans[o].n, spans[j].p, spans[j].n)) return refuse("sv_cost_routes: an output overlaps an input or another output");
+    const Span spans[6] = {{cost, map_cells * 4}, {pen, map_cells}, {starts, k * 8}, {cells, cell_bytes}, {length, k * 4}, {status, k * 4}};
+    if (outputs_overlap(spans, 6, 3))  // cells is the first output
+        return refuse("sv_cost_routes: an output overlaps an input or another output");
 
     sv::CostRoutesArgs a;
     memset(&a, 0, sizeof(a));

@@ -21,7 +21,7 @@ std::atomic<unsigned long long *> g_counters{nullptr};
 
 // NULL for a map whose linear indices fit 23 bits and a table of rows the kernels can index, else what is wrong with them.
 const char *check_shape(const char *prefix, int rows, int cols, int capacity) {
-    if (rows < 1 || rows > 32768 || cols < 1 || cols > 32768) return prefixed(prefix, "rows or cols outside 1..32768");
+    if (const char *bad = check_map_shape(prefix, rows, cols)) return bad;
     if ((int64_t)rows * cols > sv::FRONTIER_CELLS_MAX) return prefixed(prefix, "rows * cols above 8 000 000, where a linear index could reach 2^23");
     if (capacity < 1 || capacity > sv::FRONTIER_CAPACITY_MAX) return prefixed(prefix, "capacity outside 1..65535");
     return nullptr;
@@ -54,9 +54,9 @@ extern "C" {
 int sv_frontier_cells_device(const int16_t *logodds, const int32_t *last_seen, const uint8_t *pen, int rows, int cols, int occupied, int free_, uint8_t *mask,
                              void *stream) {
     if (!logodds || !last_seen || !mask) return refuse("sv_frontier_cells: logodds, last_seen or mask is NULL");
-    if (rows < 1 || rows > 32768 || cols < 1 || cols > 32768) return refuse("sv_frontier_cells: rows or cols outside 1..32768");
-    if (reinterpret_cast<uintptr_t>(logodds) & 1) return refuse("sv_frontier_cells: logodds is not 2-byte aligned");
-    if (reinterpret_cast<uintptr_t>(last_seen) & 3) return refuse("sv_frontier_cells: last_seen is not 4-byte aligned");
+    if (const char *bad = check_map_shape("sv_frontier_cells", rows, cols)) return refuse(bad);
+    if (misaligned(logodds, 2)) return refuse("sv_frontier_cells: logodds is not 2-byte aligned");
+    if (misaligned(last_seen, 4)) return refuse("sv_frontier_cells: last_seen is not 4-byte aligned");
     const size_t cells = (size_t)rows * cols;
     if (overlap(mask, cells, logodds, cells * 2) || overlap(mask, cells, last_seen, cells * 4) || overlap(mask, cells, pen, cells))
         return refuse("sv_frontier_cells: mask overlaps logodds, last_seen or pen");
@@ -83,21 +83,16 @@ int sv_frontier_clusters_device(const uint8_t *mask, int rows, int cols, int min
     if (!mask || !label || !clusters || !sums || !info || !workspace) return refuse("sv_frontier_clusters: mask, label, clusters, sums, info or the workspace is NULL");
     if (const char *bad = check_shape("sv_frontier_clusters", rows, cols, capacity)) return refuse(bad);
     if (min_cells < 1 || min_cells > sv::FRONTIER_CELLS_MAX) return refuse("sv_frontier_clusters: min_cells outside 1..8 000 000");
-    if ((reinterpret_cast<uintptr_t>(label) | reinterpret_cast<uintptr_t>(clusters) | reinterpret_cast<uintptr_t>(info)) & 3)
+    if (any_misaligned(4, label, clusters, info))
         return refuse("sv_frontier_clusters: label, clusters or info is not 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(sums) & 7) return refuse("sv_frontier_clusters: sums is not 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(workspace) & 15) return refuse("sv_frontier_clusters: the workspace is not 16-byte aligned");
+    if (misaligned(sums, 8)) return refuse("sv_frontier_clusters: sums is not 8-byte aligned");
+    if (misaligned(workspace, 16)) return refuse("sv_frontier_clusters: the workspace is not 16-byte aligned");
     const Layout l = layout_of(rows, cols, capacity);
     if (workspace_bytes < l.total) return refuse("sv_frontier_clusters: the workspace is smaller than sv_frontier_clusters_workspace asks for");
     const size_t cells = (size_t)rows * cols;
-    const struct {
-        const void *p;
-        size_t n;
-    } spans[6] = {{mask, cells}, {label, cells * 4}, {clusters, (size_t)capacity * 32}, {sums, (size_t)capacity * 16}, {info, 16}, {workspace, l.total}};
-    for (int o = 1; o < 6; o++)  // each output against the input and every output before it
-        for (int j = 0; j < o; j++)
-            if (overlap(spans[o].p, spans[o].n, spans[j].p, spans[j].n))
-                return refuse("sv_frontier_clusters: label, clusters, sums, info and the workspace overlap one another or mask");
+    const Span spans[6] = {{mask, cells}, {label, cells * 4}, {clusters, (size_t)capacity * 32}, {sums, (size_t)capacity * 16}, {info, 16}, {workspace, l.total}};
+    if (outputs_overlap(spans, 6, 1))  // mask is the only input
+        return refuse("sv_frontier_clusters: label, clusters, sums, info and the workspace overlap one another or mask");
 
     sv::FrontierArgs a;
     memset(&a, 0, sizeof(a));

@@ -6,9 +6,10 @@
 //   cells    a workgroup owns FRONTIER_SPAN consecutive cells of the map taken as one line.  It decides the state of every cell it needs
 //            once and stages it as a byte in LDS: its own cells with one cell before and behind them and - where a row has at most
 //            FRONTIER_HALO_COLS cells - the row above and the row below, which lie `cols` cells before and behind in the same line.  With
-//            longer rows the states above and below are decided from global memory where a free cell asks for them.  Chunks of 16 cells:
-//            two 16-byte loads of logodds and four of last_seen where both arrays are 16-byte aligned, one 16-byte load of pen and one
-//            16-byte store of the mask where those are; cell by cell elsewhere, in a cut chunk and outside the map.
+//            longer rows the states above and below are decided from global memory where a free cell asks for them.  The state is
+//            occupancy_map_cells.h's, as the view decides it.  Chunks of 16 cells: that header's wide loader where logodds and last_seen
+//            are 16-byte aligned, one 16-byte load of pen and one 16-byte store of the mask where those are; cell by cell elsewhere, in
+//            a cut chunk and outside the map.
 //
 //   tiles    a workgroup of 256 threads per tile of 64 x 64 cells: a union-find over the tile in LDS.  Every member starts as its own
 //            parent and unites with its W, NW, N and NE neighbours inside the tile; after a barrier each member looks its root up and
@@ -47,6 +48,7 @@
 #include <stdint.h>
 
 #include "frontier_kernels.h"
+#include "occupancy_map_cells.h"
 #include "wave_ops.h"
 
 namespace sv {
@@ -54,8 +56,6 @@ namespace sv {
 namespace {
 
 enum { FRONTIER_WAVE_CELLS = 1024 };  // the cells one wavefront counts and ranks: 16 sweeps of 64
-
-__device__ __forceinline__ uint32_t frontier_state(int l, int s, const FrontierCellsArgs &a) { return s >= 0 ? (l >= a.occupied ? 2u : l <= a.free_ ? 1u : 0u) : 0u; }
 
 // ---- the union-find in LDS (tiles) -----------------------------------------------------------------------------------------------
 
@@ -137,24 +137,13 @@ __global__ __launch_bounds__(FRONTIER_THREADS) void k_frontier_cells(FrontierCel
         const int64_t g = lo + (int64_t)ch * FRONTIER_CHUNK;
         uint32_t w[4] = {0, 0, 0, 0};
         if (wide_in && g >= 0 && g + FRONTIER_CHUNK <= cells) {
-            const uint4 l0 = *reinterpret_cast<const uint4 *>(a.logodds + g), l1 = *reinterpret_cast<const uint4 *>(a.logodds + g + 8);
-            const uint32_t lw[8] = {l0.x, l0.y, l0.z, l0.w, l1.x, l1.y, l1.z, l1.w};
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const int4 s = *reinterpret_cast<const int4 *>(a.last_seen + g + 4 * q);
-                const int sv4[4] = {s.x, s.y, s.z, s.w};
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const int l = (int)(int16_t)(lw[2 * q + (k >> 1)] >> (16 * (k & 1)));
-                    w[q] |= frontier_state(l, sv4[k], a) << (8 * k);
-                }
-            }
+            map_state16(a.logodds + g, a.last_seen + g, a.occupied, a.free_, w);
         } else {
 #pragma unroll
             for (int k = 0; k < FRONTIER_CHUNK; k++) {
                 const int64_t i = g + k;
                 uint32_t st = 2;
-                if (i >= 0 && i < cells) st = frontier_state(a.logodds[i], a.last_seen[i], a);
+                if (i >= 0 && i < cells) st = map_state(a.logodds[i], a.last_seen[i], a.occupied, a.free_);
                 w[k >> 2] |= st << (8 * (k & 3));
             }
         }
@@ -183,8 +172,8 @@ __global__ __launch_bounds__(FRONTIER_THREADS) void k_frontier_cells(FrontierCel
                 uint32_t m = 0;
                 if (s_state[at] == 1) {
                     bool unknown = (c > 0 && s_state[at - 1] == 0) || (c + 1 < a.cols && s_state[at + 1] == 0);
-                    if (i >= a.cols) unknown |= (rows_staged ? (uint32_t)s_state[at - a.cols] : frontier_state(a.logodds[i - a.cols], a.last_seen[i - a.cols], a)) == 0;
-                    if (i + a.cols < cells) unknown |= (rows_staged ? (uint32_t)s_state[at + a.cols] : frontier_state(a.logodds[i + a.cols], a.last_seen[i + a.cols], a)) == 0;
+                    if (i >= a.cols) unknown |= (rows_staged ? (uint32_t)s_state[at - a.cols] : map_state(a.logodds[i - a.cols], a.last_seen[i - a.cols], a.occupied, a.free_)) == 0;
+                    if (i + a.cols < cells) unknown |= (rows_staged ? (uint32_t)s_state[at + a.cols] : map_state(a.logodds[i + a.cols], a.last_seen[i + a.cols], a.occupied, a.free_)) == 0;
                     if (unknown) {
                         const uint32_t pen = !a.pen ? 0u : whole ? (pw[k >> 2] >> (8 * (k & 3)) & 255u) : (uint32_t)a.pen[i];
                         m = pen != FRONTIER_BLOCKED;

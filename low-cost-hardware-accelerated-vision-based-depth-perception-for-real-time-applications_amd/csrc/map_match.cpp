@@ -65,11 +65,11 @@ int sv_map_match_device(const uint8_t *state, const double *poses, int batch, in
     layout((size_t)frows * fcols, batch, &h, &p, &l);
     if (batch > 0 && !workspace) return refuse("sv_map_match: the workspace is NULL");
     if (workspace_bytes < h + p + l) return refuse("sv_map_match: the workspace is smaller than sv_map_match_workspace asks for");
-    if (reinterpret_cast<uintptr_t>(poses) & 7) return refuse("sv_map_match: poses is not 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(logodds) & 1) return refuse("sv_map_match: logodds is not 2-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(sums) | reinterpret_cast<uintptr_t>(best_score)) & 7) return refuse("sv_map_match: sums or best_score is not 8-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(counts) | reinterpret_cast<uintptr_t>(best)) & 3) return refuse("sv_map_match: counts or best is not 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(workspace) & 15) return refuse("sv_map_match: the workspace is not 16-byte aligned");
+    if (misaligned(poses, 8)) return refuse("sv_map_match: poses is not 8-byte aligned");
+    if (misaligned(logodds, 2)) return refuse("sv_map_match: logodds is not 2-byte aligned");
+    if (any_misaligned(8, sums, best_score)) return refuse("sv_map_match: sums or best_score is not 8-byte aligned");
+    if (any_misaligned(4, counts, best)) return refuse("sv_map_match: counts or best is not 4-byte aligned");
+    if (misaligned(workspace, 16)) return refuse("sv_map_match: the workspace is not 16-byte aligned");
     if (batch == 0) return SV_OK;  // nothing to do
 
     sv::MapMatchArgs a;
@@ -84,14 +84,11 @@ int sv_map_match_device(const uint8_t *state, const double *poses, int batch, in
     a.cap = (size_t)frows * fcols;
     a.B = batch, a.P = n_poses;
     a.frows = frows, a.fcols = fcols;
-    a.rows = map->rows, a.cols = map->cols, a.top = map->top, a.left = map->left;
+    a.m = sv::map_cells_of(*map);
     a.w_occ = w_occ, a.w_free = w_free;
     const double fs = (double)frame->scale;
     a.hf = 1.0 / (2.0 * fs);
     a.fr1 = trunc(frame->x_range[1] * fs), a.fc1 = trunc(frame->y_range[1] * fs);  // |.| <= 2^46: exact
-    a.ms = (double)map->scale;
-    a.gx_lo = (double)(map->top - map->rows), a.gx_hi = (double)(map->top - 1);
-    a.gy_lo = (double)(map->left - map->cols), a.gy_hi = (double)(map->left - 1);
     // candidates per workgroup: as many as still leave the chip about 1024 workgroups, or what the test hook asks for; never more
     // workgroups per frame than a frame has pairs for
     auto groups = [&](int g) { return (n_poses + (1 << g) - 1) >> g; };

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "occupancy_map_cells.h"
+
 namespace sv {
 
 // MAPMATCH_CHUNK list entries are staged in LDS at a time; a compaction workgroup covers MAPMATCH_COMPACT_CELLS frame cells; a frame has at
@@ -35,13 +37,11 @@ struct MapMatchArgs {
     size_t cap;                    // frows * fcols
     int B, P;
     int frows, fcols;
-    int rows, cols, top, left;
+    MapCells m;                    // the map
     int w_occ, w_free;
     int log_group, n_groups;       // a workgroup scores 1 << log_group candidates; ceil(P / that) workgroups per frame
     double hf;                     // 1 / (2 fs)
     double fr1, fc1;               // trunc(fx1 fs), trunc(fy1 fs) (integers)
-    double ms;                     // the map's scale
-    double gx_lo, gx_hi, gy_lo, gy_hi;  // top - rows, top - 1, left - cols, left - 1
 };
 
 // Three kernels on `st`: the lists (their counters cleared first), the sums and the score per candidate, the best per frame (left out

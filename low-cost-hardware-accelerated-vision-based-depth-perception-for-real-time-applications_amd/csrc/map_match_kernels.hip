@@ -12,8 +12,8 @@
 //           the chip, down to 1 - the candidate uniform per workgroup, the lanes striding over the list - for a single small window.
 //           Either way every lane's doubles are one lookup: a candidate's pose sits in four registers of its lane.  The list is staged
 //           1024 entries at a time in LDS as the doubles (Xf, Yf) - the conversion from the packed word is made once per workgroup, not
-//           per lookup.  Per lookup: four products, two sums, the translation, the map's scale, floor, four comparisons in double - NaN,
-//           inf and far-away poses fail them before any conversion to integer - and one int16 load.  Sums in int32 per chunk (1024 x
+//           per lookup.  Per lookup the way into a cell that every reader of the map takes (occupancy_map_cells.h: four products, two
+//           sums, the translation, the map's scale, floor, four comparisons in double) and one int16 load.  Sums in int32 per chunk (1024 x
 //           32768 < 2^31), int64 across chunks.  The 256 / G partial sums of a candidate meet in an LDS tree; one thread stores its
 //           (H, M), its counts and, where the best is wanted, the workgroup's maximum as one (score, lowest index) pair.
 //
@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "map_match_kernels.h"
+#include "occupancy_map_cells.h"
 
 namespace sv {
 
@@ -91,17 +92,13 @@ __global__ __launch_bounds__(MAPMATCH_THREADS) void k_map_match_scores(MapMatchA
 
     // entry k of the staged chunk under this lane's pose -> the map's word, or no hit
     auto lookup = [&](int k, int &sum, int &hits) {
-        const double X = s_x[k], Y = s_y[k];
-        const double Xw = (pc * X - ps * Y) + tx, Yw = (ps * X + pc * Y) + ty;
-        const double gx = floor(Xw * a.ms), gy = floor(Yw * a.ms);
+        double Xw, Yw;
+        map_world(tx, ty, pc, ps, s_x[k], s_y[k], Xw, Yw);
         if (COUNT) lookups++;
-        if (gx >= a.gx_lo && gx <= a.gx_hi && gy >= a.gy_lo && gy <= a.gy_hi) {
-            const int r = a.top - 1 - (int)gx, cc = a.left - 1 - (int)gy;
-            // always true after the comparisons; kept so that no input can ever address outside the map
-            if ((unsigned)r < (unsigned)a.rows && (unsigned)cc < (unsigned)a.cols) {
-                sum += a.logodds[(size_t)r * a.cols + cc];
-                hits++;
-            }
+        int r, cc;
+        if (map_cell(a.m, map_grid(a.m, Xw), map_grid(a.m, Yw), r, cc)) {
+            sum += a.logodds[(size_t)r * a.m.cols + cc];
+            hits++;
         }
     };
 

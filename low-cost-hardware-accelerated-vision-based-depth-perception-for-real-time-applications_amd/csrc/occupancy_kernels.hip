@@ -15,7 +15,7 @@
 //             (2 n)), floor division, n = max(|dr|, |dc|): a closed form in k, monotone per axis, so the steps inside the grid are one
 //             interval, found per axis from  n (2 lo - 1) <= 2 k da <= n (2 hi + 1) - 1  (lo = -a0, hi = size - 1 - a0), and the walk
 //             takes at most max(rows, cols) + 1 steps whatever the end.  Between steps the quotient and remainder of each axis are
-//             carried along (|2 da| <= 2 n: one correction at most), so the loop holds no division.
+//             carried along (occupancy_map_cells.h: line_step, the world map's view walks the same line), so the loop holds no division.
 //             64-bit range: |trunc(X s)| < 2^24 for both ends, so |dr|, |dc|, n < 2^25; a line whose span misses the grid on an axis
 //             is dropped first, which leaves |a0| < 2^25 + 2^15 and every product below 2^54.
 //   finalize  h_lo of a cell without evidence becomes -1; state = 2 iff n_obstacle >= min_obstacle, else 1 iff n_ground >= min_ground
@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "occupancy_kernels.h"
+#include "occupancy_map_cells.h"
 #include "wave_ops.h"
 
 namespace sv {
@@ -153,11 +154,7 @@ __global__ __launch_bounds__(64) void k_occupancy_rays(OccupancyArgs a) {
         // always true by the clip; kept so that no input can ever address outside the grid
         if ((unsigned long long)r < (unsigned long long)a.rows && (unsigned long long)c < (unsigned long long)a.cols)
             atomicAdd(out + (size_t)r * a.cols + (size_t)c, 1);
-        mr += 2 * dr, mc += 2 * dc;
-        if (mr >= two_n) mr -= two_n, qr++;
-        else if (mr < 0) mr += two_n, qr--;
-        if (mc >= two_n) mc -= two_n, qc++;
-        else if (mc < 0) mc += two_n, qc--;
+        line_step(mr, qr, 2 * dr, two_n), line_step(mc, qc, 2 * dc, two_n);
     }
 }
 

@@ -39,9 +39,9 @@ int sv_occupancy_fuse_device(const uint8_t *state, const double *poses, int batc
     if (batch > 0 && (!state || !poses)) return refuse("sv_occupancy_fuse: state or poses is NULL");
     if (!logodds_in || !logodds_out) return refuse("sv_occupancy_fuse: logodds_in or logodds_out is NULL");
     if ((last_seen_in == nullptr) != (last_seen_out == nullptr)) return refuse("sv_occupancy_fuse: only one of last_seen_in and last_seen_out is given");
-    if (reinterpret_cast<uintptr_t>(poses) & 7) return refuse("sv_occupancy_fuse: poses is not 8-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(logodds_in) | reinterpret_cast<uintptr_t>(logodds_out)) & 1) return refuse("sv_occupancy_fuse: logodds_in or logodds_out is not 2-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(last_seen_in) | reinterpret_cast<uintptr_t>(last_seen_out)) & 3)
+    if (misaligned(poses, 8)) return refuse("sv_occupancy_fuse: poses is not 8-byte aligned");
+    if (any_misaligned(2, logodds_in, logodds_out)) return refuse("sv_occupancy_fuse: logodds_in or logodds_out is not 2-byte aligned");
+    if (any_misaligned(4, last_seen_in, last_seen_out))
         return refuse("sv_occupancy_fuse: last_seen_in or last_seen_out is not 4-byte aligned");
     const size_t cells = (size_t)map->rows * map->cols;
     const bool shifted = shift_rows != 0 || shift_cols != 0;

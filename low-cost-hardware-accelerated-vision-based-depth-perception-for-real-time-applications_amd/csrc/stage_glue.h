@@ -41,12 +41,18 @@ inline const char *check_frame(const char *prefix, int batch, int width, int hei
     return nullptr;
 }
 
+// NULL for the rows and columns a world map may have, else what is wrong with them: for the entries that take the two numbers bare.
+inline const char *check_map_shape(const char *prefix, int rows, int cols) {
+    if (rows < 1 || rows > 32768 || cols < 1 || cols > 32768) return prefixed(prefix, "rows or cols outside 1..32768");
+    return nullptr;
+}
+
 // NULL for a good map spec, else what is wrong with it: the rules of the fuse entry, which every reader of the map repeats.
 inline const char *check_map(const char *prefix, const sv_occupancy_map_spec *m) {
     if (!m) return prefixed(prefix, "the map spec is NULL");
     for (int k = 0; k < 7; k++)
         if (m->reserved[k] != 0) return prefixed(prefix, "a reserved word of the map spec is not 0");
-    if (m->rows < 1 || m->rows > 32768 || m->cols < 1 || m->cols > 32768) return prefixed(prefix, "rows or cols of the map outside 1..32768");
+    if (check_map_shape(prefix, m->rows, m->cols)) return prefixed(prefix, "rows or cols of the map outside 1..32768");
     if (m->scale < 1) return prefixed(prefix, "the map's scale < 1");
     if (m->top <= -MAP_CELL_MAX || m->top >= MAP_CELL_MAX || m->left <= -MAP_CELL_MAX || m->left >= MAP_CELL_MAX)
         return prefixed(prefix, "|top| or |left| of the map is 2^24 or more");
@@ -57,6 +63,9 @@ inline const char *check_map(const char *prefix, const sv_occupancy_map_spec *m)
 }
 
 inline bool misaligned(const void *p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }  // a: a power of two
+
+template <class... P>
+inline bool any_misaligned(unsigned a, const P *...p) { return (... || misaligned(p, a)); }  // NULL is aligned
 
 // NULL for a voxel map spec and a buffer that (Q)'s clear entry admits, else what is wrong with them: the check of every entry of (Q)
 // to (T).  nc = the cells per axis, log2_slots = of the table; sv_voxel_map_slots (voxel_map.cpp) holds the rule of the capacity.
@@ -95,6 +104,16 @@ inline size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
 inline bool overlap(const void *p, size_t pn, const void *q, size_t qn) {
     const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
     return p && q && a < b + qn && b < a + pn;
+}
+
+// The arguments of a call as spans of bytes, the inputs first: does an output - spans[first_out] and everything behind it - share a
+// byte with an input or with an output before it?  A span of no bytes shares none.
+struct Span { const void *p; size_t n; };
+inline bool outputs_overlap(const Span *spans, int n_spans, int first_out) {
+    for (int o = first_out; o < n_spans; o++)
+        for (int j = 0; j < o; j++)
+            if (spans[o].n && spans[j].n && overlap(spans[o].p, spans[o].n, spans[j].p, spans[j].n)) return true;
+    return false;
 }
 
 }  // namespace glue

@@ -30,7 +30,7 @@ extern "C" {
 
 int sv_view_workspace(int rows, int cols, size_t *bytes) {
     if (!bytes) return refuse("sv_view_workspace: bytes is NULL");
-    if (rows < 1 || rows > 32768 || cols < 1 || cols > 32768) return refuse("sv_view_workspace: rows or cols outside 1..32768");
+    if (const char *bad = check_map_shape("sv_view_workspace", rows, cols)) return refuse(bad);
     *bytes = state_bytes(rows, cols) + score_bytes();
     return SV_OK;
 }
@@ -47,24 +47,19 @@ int sv_view_device(const int16_t *logodds, const int32_t *last_seen, const sv_oc
     if (!logodds || !last_seen || !ends || !workspace) return refuse("sv_view: logodds, last_seen, ends or the workspace is NULL");
     if (n_groups > 0 && (!poses || !counts || !end_cells || !status || !best || !best_score))
         return refuse("sv_view: poses, counts, end_cells, status, best or best_score is NULL");
-    if (reinterpret_cast<uintptr_t>(logodds) & 1) return refuse("sv_view: logodds is not 2-byte aligned");
-    if (reinterpret_cast<uintptr_t>(last_seen) & 3) return refuse("sv_view: last_seen is not 4-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(poses) | reinterpret_cast<uintptr_t>(ends)) & 7) return refuse("sv_view: poses or ends is not 8-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(counts) | reinterpret_cast<uintptr_t>(end_cells) | reinterpret_cast<uintptr_t>(best) | reinterpret_cast<uintptr_t>(best_score)) & 3)
+    if (misaligned(logodds, 2)) return refuse("sv_view: logodds is not 2-byte aligned");
+    if (misaligned(last_seen, 4)) return refuse("sv_view: last_seen is not 4-byte aligned");
+    if (any_misaligned(8, poses, ends)) return refuse("sv_view: poses or ends is not 8-byte aligned");
+    if (any_misaligned(4, counts, end_cells, best, best_score))
         return refuse("sv_view: counts, end_cells, best or best_score is not 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(workspace) & 15) return refuse("sv_view: the workspace is not 16-byte aligned");
+    if (misaligned(workspace, 16)) return refuse("sv_view: the workspace is not 16-byte aligned");
     const size_t states = state_bytes(map->rows, map->cols), need = states + score_bytes();
     if (workspace_bytes < need) return refuse("sv_view: the workspace is smaller than sv_view_workspace asks for");
     const size_t cells = (size_t)map->rows * map->cols, K = (size_t)n_groups * n_poses;
-    const struct {
-        const void *p;
-        size_t n;
-    } spans[10] = {{logodds, cells * 2}, {last_seen, cells * 4}, {poses, K * 32}, {ends, (size_t)n_rays * 16}, {counts, K * 12}, {end_cells, K * n_rays * 4},
-                   {status, K * n_rays}, {best, (size_t)n_groups * 4}, {best_score, (size_t)n_groups * 4}, {workspace, need}};
-    for (int o = 4; o < 10; o++)  // each output against the inputs and every output before it
-        for (int j = 0; j < o; j++)
-            if (spans[o].n && spans[j].n && overlap(spans[o].p, spans[o].n, spans[j].p, spans[j].n))
-                return refuse("sv_view: counts, end_cells, status, best, best_score and the workspace overlap one another or an input");
+    const Span spans[10] = {{logodds, cells * 2}, {last_seen, cells * 4}, {poses, K * 32}, {ends, (size_t)n_rays * 16}, {counts, K * 12}, {end_cells, K * n_rays * 4},
+                            {status, K * n_rays}, {best, (size_t)n_groups * 4}, {best_score, (size_t)n_groups * 4}, {workspace, need}};
+    if (outputs_overlap(spans, 10, 4))  // counts is the first output
+        return refuse("sv_view: counts, end_cells, status, best, best_score and the workspace overlap one another or an input");
     if (n_groups == 0) return SV_OK;  // nothing to do
 
     sv::ViewArgs a;
@@ -72,10 +67,7 @@ int sv_view_device(const int16_t *logodds, const int32_t *last_seen, const sv_oc
     uint8_t *ws = static_cast<uint8_t *>(workspace);
     a.logodds = logodds, a.last_seen = last_seen, a.state = ws, a.score = reinterpret_cast<int32_t *>(ws + states);
     a.poses = poses, a.ends = ends, a.counts = counts, a.end_cells = end_cells, a.status = status, a.best = best, a.best_score = best_score;
-    a.rows = map->rows, a.cols = map->cols, a.top = map->top, a.left = map->left;
-    a.ms = (double)map->scale;
-    a.gx_lo = (double)(map->top - map->rows), a.gx_hi = (double)(map->top - 1);
-    a.gy_lo = (double)(map->left - map->cols), a.gy_hi = (double)(map->left - 1);
+    a.m = sv::map_cells_of(*map);
     a.G = n_groups, a.P = n_poses, a.n_rays = n_rays, a.reach = reach, a.occupied = occupied, a.free_ = free_, a.max_unknown = max_unknown;
     a.window = g_variant.load() == sv::VIEW_WINDOW_FULL ? (int)sv::VIEW_REACH_MAX : reach;
     if (sv::launch_view(a, static_cast<hipStream_t>(stream), g_stages.load()) != hipSuccess) {

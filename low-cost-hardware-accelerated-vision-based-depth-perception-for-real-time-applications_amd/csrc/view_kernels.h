@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "occupancy_map_cells.h"
+
 namespace sv {
 
 // A workgroup of VIEW_THREADS threads walks the rays of one candidate; the state kernel gives a thread VIEW_CHUNK consecutive cells.  A
@@ -28,8 +30,7 @@ struct ViewArgs {
     int16_t *end_cells;        // [K][n_rays][2]
     uint8_t *status;           // [K][n_rays]
     int32_t *best, *best_score;  // [G]
-    int rows, cols, top, left;
-    double ms, gx_lo, gx_hi, gy_lo, gy_hi;
+    MapCells m;                // the map
     int G, P, n_rays, reach, window, occupied, free_, max_unknown;  // window: the reach the LDS bitmap is laid out for, >= reach
 };
 

@@ -1,12 +1,12 @@
 // The expected view of the world map from candidate poses: include/stereo_vision_hip.h (P), restated in stereo_vision/sv.py
 // (occupancy_view).  Rays are cast through the map from every candidate, and the DISTINCT cells they see are counted by state.  Doubles
-// place the origin and the ends of the rays - clearance_paths' arithmetic, every product, difference and sum rounded on its own -,
+// place the origin and the ends of the rays - by occupancy_map_cells.h, as the match and the path check place their points -,
 // everything after that is integers: the same bits whatever order the lanes take.
 //
 //   state    one pass over the map: the state of every cell (occupancy_map_state's: 0 unknown, 1 free, 2 occupied) as a byte of the
-//            workspace.  Chunks of 16 cells: two 16-byte loads of logodds, four of last_seen and one 16-byte store where the inputs are
-//            16-byte aligned (the workspace always is); cell by cell elsewhere and in the cut chunk at the end.  The walk then loads one
-//            byte per lookup, not six.
+//            workspace.  Chunks of 16 cells: the wide loader (occupancy_map_cells.h: map_state16) and one 16-byte store where the inputs
+//            are 16-byte aligned (the workspace always is); cell by cell elsewhere and in the cut chunk at the end.  The walk then loads
+//            one byte per lookup, not six.
 //
 //   walk     a workgroup of 256 threads per candidate; its lanes stride over the rays.  The workgroup holds a bitmap of the (2 w + 1)^2
 //            window of cells around its origin in LDS, rows padded to whole 32-bit words, w = the call's reach (or 254 under
@@ -17,9 +17,8 @@
 //            wavefront by shuffles (wave_ops.h) and over the four wavefronts through twelve LDS words.
 //
 //            The line is occupancy_ray_cells' (obstacle_end = False): step k is at r0 + floor((2 k dr + n) / (2 n)) with n = max(|dr|,
-//            |dc|).  It is walked with a remainder per axis instead of a division per step: acc = (2 k dr + n) mod 2 n starts at n, takes
-//            2 dr per step and carries into the coordinate when it leaves 0 .. 2 n - 1; |2 dr| <= 2 n, so a coordinate moves by at
-//            most one per step, and the coordinate is the floor exactly.
+//            |dc|).  It is walked with a remainder per axis instead of a division per step (occupancy_map_cells.h: line_step), so a
+//            coordinate moves by at most one per step.
 //
 //   best     a wavefront per group g: the largest score of its P candidates, ties to the lowest index, as one 64-bit key (score + 1 in
 //            the high word, ~index in the low one) under wave_max.  map_match's better() compares separate pairs in an LDS ladder of its
@@ -33,39 +32,23 @@
 #include <stdint.h>
 
 #include "view_kernels.h"
+#include "occupancy_map_cells.h"
 #include "wave_ops.h"
 
 namespace sv {
 
-namespace {
-
-__device__ __forceinline__ uint32_t view_state(int l, int s, const ViewArgs &a) { return s >= 0 ? (l >= a.occupied ? 2u : l <= a.free_ ? 1u : 0u) : 0u; }
-
-}  // namespace
-
 __global__ __launch_bounds__(VIEW_THREADS) void k_view_state(ViewArgs a) {
-    const int64_t cells = (int64_t)a.rows * a.cols;
+    const int64_t cells = (int64_t)a.m.rows * a.m.cols;
     const int64_t g = ((int64_t)blockIdx.x * VIEW_THREADS + threadIdx.x) * VIEW_CHUNK;
     if (g >= cells) return;  // no barrier in this kernel
     const bool wide_in = ((reinterpret_cast<uintptr_t>(a.logodds) | reinterpret_cast<uintptr_t>(a.last_seen)) & 15) == 0;
     if (wide_in && g + VIEW_CHUNK <= cells) {
-        const uint4 l0 = *reinterpret_cast<const uint4 *>(a.logodds + g), l1 = *reinterpret_cast<const uint4 *>(a.logodds + g + 8);
-        const uint32_t lw[8] = {l0.x, l0.y, l0.z, l0.w, l1.x, l1.y, l1.z, l1.w};
-        uint32_t w[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const int4 s = *reinterpret_cast<const int4 *>(a.last_seen + g + 4 * q);
-            const int s4[4] = {s.x, s.y, s.z, s.w};
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const int l = (int)(int16_t)(lw[2 * q + (k >> 1)] >> (16 * (k & 1)));
-                w[q] |= view_state(l, s4[k], a) << (8 * k);
-            }
-        }
+        uint32_t w[4];
+        map_state16(a.logodds + g, a.last_seen + g, a.occupied, a.free_, w);
         *reinterpret_cast<uint4 *>(a.state + g) = make_uint4(w[0], w[1], w[2], w[3]);  // g is a multiple of 16, the workspace 16-byte aligned
     } else {
         const int n = (int)min((int64_t)VIEW_CHUNK, cells - g);
-        for (int k = 0; k < n; k++) a.state[g + k] = (uint8_t)view_state(a.logodds[g + k], a.last_seen[g + k], a);
+        for (int k = 0; k < n; k++) a.state[g + k] = (uint8_t)map_state(a.logodds[g + k], a.last_seen[g + k], a.occupied, a.free_);
     }
 }
 
@@ -80,15 +63,10 @@ __global__ __launch_bounds__(VIEW_THREADS) void k_view_walk(ViewArgs a) {
     uint32_t *ends_out = reinterpret_cast<uint32_t *>(a.end_cells) + (size_t)cand * a.n_rays;  // a cell is one 4-byte word: (row, col) as two int16
     const uint32_t none = 0xFFFFFFFFu;                                                       // (-1, -1)
 
-    // the origin: uniform over the workgroup.  NaN, inf and far away fail the comparisons before any conversion.
-    const double gx0 = floor(tx * a.ms), gy0 = floor(ty * a.ms);
-    bool ok = isfinite(tx) && isfinite(ty) && isfinite(pc) && isfinite(ps) && gx0 >= a.gx_lo && gx0 <= a.gx_hi && gy0 >= a.gy_lo && gy0 <= a.gy_hi;
+    // the origin: uniform over the workgroup
+    const double gx0 = map_grid(a.m, tx), gy0 = map_grid(a.m, ty);
     int r0 = 0, c0 = 0;
-    if (ok) {
-        r0 = a.top - 1 - (int)gx0, c0 = a.left - 1 - (int)gy0;
-        ok = (unsigned)r0 < (unsigned)a.rows && (unsigned)c0 < (unsigned)a.cols;  // always true here; no input can address outside the map
-    }
-    if (!ok) {  // the whole workgroup, before any barrier
+    if (!(isfinite(tx) && isfinite(ty) && isfinite(pc) && isfinite(ps) && map_cell(a.m, gx0, gy0, r0, c0))) {  // the whole workgroup, before any barrier
         for (int j = tid; j < a.n_rays; j += VIEW_THREADS) status[j] = (uint8_t)VIEW_INVALID, ends_out[j] = none;
         if (tid == 0) {
             a.counts[(size_t)cand * 3] = 0, a.counts[(size_t)cand * 3 + 1] = 0, a.counts[(size_t)cand * 3 + 2] = 0;
@@ -104,9 +82,9 @@ __global__ __launch_bounds__(VIEW_THREADS) void k_view_walk(ViewArgs a) {
     int seen0 = 0, seen1 = 0, seen2 = 0;  // this lane's first visits, by state
     const double reach = (double)a.reach;
     for (int j = tid; j < a.n_rays; j += VIEW_THREADS) {
-        const double ex = a.ends[2 * j], ey = a.ends[2 * j + 1];
-        const double Xw = (pc * ex - ps * ey) + tx, Yw = (ps * ex + pc * ey) + ty;
-        const double gx1 = floor(Xw * a.ms), gy1 = floor(Yw * a.ms);
+        double Xw, Yw;
+        map_world(tx, ty, pc, ps, a.ends[2 * j], a.ends[2 * j + 1], Xw, Yw);
+        const double gx1 = map_grid(a.m, Xw), gy1 = map_grid(a.m, Yw);
         const double ddr = gx0 - gx1, ddc = gy0 - gy1;  // the end cell minus the origin cell: rows and columns count against gx and gy
         // NaN fails the comparisons; an end further than reach cells away on an axis must not walk, whatever its direction: this bounds the window
         if (!(isfinite(gx1) && isfinite(gy1) && fabs(ddr) <= reach && fabs(ddc) <= reach)) {
@@ -119,23 +97,19 @@ __global__ __launch_bounds__(VIEW_THREADS) void k_view_walk(ViewArgs a) {
         for (int k = 0; k <= n; k++) {
             if (k > 0) {
                 const int pr = r, pcol = c;
-                acc_r += 2 * dr, acc_c += 2 * dc;
-                if (acc_r >= two_n) acc_r -= two_n, r++;
-                else if (acc_r < 0) acc_r += two_n, r--;
-                if (acc_c >= two_n) acc_c -= two_n, c++;
-                else if (acc_c < 0) acc_c += two_n, c--;
-                if ((unsigned)r >= (unsigned)a.rows || (unsigned)c >= (unsigned)a.cols) {
+                line_step(acc_r, r, 2 * dr, two_n), line_step(acc_c, c, 2 * dc, two_n);
+                if ((unsigned)r >= (unsigned)a.m.rows || (unsigned)c >= (unsigned)a.m.cols) {
                     st = VIEW_EDGE;
                     break;
                 }
                 if (r != pr && c != pcol) {  // a diagonal step: the two cells beside it.  (pr, pcol) is inside the map, so (pr, c) and (r, pcol) are too
-                    if (a.state[(size_t)pr * a.cols + c] == 2 && a.state[(size_t)r * a.cols + pcol] == 2) {
+                    if (a.state[(size_t)pr * a.m.cols + c] == 2 && a.state[(size_t)r * a.m.cols + pcol] == 2) {
                         st = VIEW_CORNER;
                         break;
                     }
                 }
             }
-            const uint32_t cell = a.state[(size_t)r * a.cols + c];
+            const uint32_t cell = a.state[(size_t)r * a.m.cols + c];
             const int wr = r - r0 + W, wc = c - c0 + W;  // 0 .. 2 W: |r - r0| <= |dr| <= reach <= W
             const uint32_t bit = 1u << (wc & 31);
             const uint32_t old = atomicOr(&s_seen[wr * row_words + (wc >> 5)], bit);
@@ -183,7 +157,7 @@ __global__ __launch_bounds__(VIEW_THREADS) void k_view_best(ViewArgs a) {
 }
 
 hipError_t launch_view(const ViewArgs &a, hipStream_t st, int stages) {
-    const int64_t chunks = ((int64_t)a.rows * a.cols + VIEW_CHUNK - 1) / VIEW_CHUNK;
+    const int64_t chunks = ((int64_t)a.m.rows * a.m.cols + VIEW_CHUNK - 1) / VIEW_CHUNK;
     hipLaunchKernelGGL(k_view_state, dim3((unsigned)((chunks + VIEW_THREADS - 1) / VIEW_THREADS)), dim3(VIEW_THREADS), 0, st, a);
     if (stages >= 2) {
         const int W = a.window;

@@ -9,7 +9,7 @@
 //   rays    grid (ceil(cap / 256), frame), a lane per row.  Thread 0 works out whether the frame casts and the sensor's cell c0 - twelve
 //           pose words that must be finite, the insert's transform of `origin`, lo < O < hi, the insert's cell rule - and leaves them in
 //           LDS: once per workgroup.  A lane does the insert's transform and cell rule for its row, then walks k = 1 .. nst - 1 - margin
-//           with three error accumulators: per axis rem += 2 d with one wrap by 2 nst at most, which is c0 + (2 k d + nst) // (2 nst) with
+//           with three error accumulators (occupancy_map_cells.h: line_step, the flat map's): per axis c0 + (2 k d + nst) // (2 nst) with
 //           a flooring division, term by term (|2 k d + nst| < 2^22 at reach <= 1023).  VCARVE_STEPS steps make a trip: their keys, then
 //           the first probe of each - independent loads, in flight together -, then for a first slot that holds another key the whole
 //           read-only linear probe from slot_of (ended by the key, by an empty key or after `slots` probes), then the found entries'
@@ -32,6 +32,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "occupancy_map_cells.h"
 #include "voxel_carve_kernels.h"
 #include "voxel_map_table.h"
 #include "wave_ops.h"
@@ -114,11 +115,7 @@ __global__ __launch_bounds__(VCARVE_THREADS) void k_vcarve_rays(VoxelCarveArgs a
 #pragma unroll
         for (int u = 0; u < VCARVE_STEPS; u++) {
 #pragma unroll
-            for (int j = 0; j < 3; j++) {
-                rem[j] += 2 * d[j];  // |2 d| <= 2 nst: one wrap at most
-                if (rem[j] >= 2 * nst) rem[j] -= 2 * nst, c[j]++;
-                if (rem[j] < 0) rem[j] += 2 * nst, c[j]--;
-            }
+            for (int j = 0; j < 3; j++) line_step(rem[j], c[j], 2 * d[j], 2 * nst);  // |2 d| <= 2 nst: one wrap at most
             // a step beyond the ray's last is not looked up: its cell may lie outside the box
             key[u] = k0 + u <= n_steps ? vmap_key(c[0], c[1], c[2]) : VMAP_EMPTY;
             h[u] = vmap_slot_of(a.log2_slots, key[u]);

@@ -11,14 +11,58 @@ fuse     FUSE_BATCHES frames around the cull's round of 64 on the two SMALL case
 match    MATCH_GRIDS: frame grids of 4095, 4096, 4097, 8193 and 12293 = 3 x 4096 + 5 cells - all of them exact under sv_occupancy_dims'
          rule rows = (x1 - x0) scale + 1 - and the two thinnest grids of 32768 cells in one direction; match_states() per grid;
          candidate_case() a list of three cells whose best candidate stands where the caller puts it.
-paths    long_paths(): 65535 steps whose only hit is the last step's last disc, or step 0's disc 0."""
+paths    long_paths(): 65535 steps whose only hit is the last step's last disc, or step 0's disc 0.
+cells    check_map_cells(build): the rules the map's readers share are stated once, in csrc/occupancy_map_cells.h and csrc/stage_glue.h."""
 import functools
+import os
+import re
 
 import numpy as np
 
 NAN, INF = float("nan"), float("inf")
 INT_MAX = 2 ** 31 - 1
 STRIP_ROWS, STRIP_COLS = 2, 32  # a wavefront's strip of the fuse: OCCMAP_WAVE_ROWS x OCCMAP_TILE_COLS
+
+# --------------------------------------------------------------------------------------------------------------- cells
+
+CELLS_HEADER = "occupancy_map_cells.h"
+CELLS_KERNELS = ("map_match_kernels.hip", "clearance_kernels.hip", "view_kernels.hip", "frontier_kernels.hip", "occupancy_kernels.hip")
+MAP_HOSTS = ("occupancy_map.cpp", "map_match.cpp", "clearance.cpp", "cost.cpp", "frontier.cpp", "view.cpp")
+# The texts that define the way of a point into a cell, a cell's state and the line's step: each stands once in csrc/, in the header.
+CELLS_TEXTS = ("floor(v * m.ms)",                                        # a world coordinate in cells
+               "top - 1 - (int)",                                        # the row of floor(X ms), after the comparisons in double
+               "s >= 0 ? (l >= occupied ? 2u : l <= free_ ? 1u : 0u) : 0u",  # the state of a cell
+               "(pc * X - ps * Y) + tx",                                 # a vehicle point under a pose
+               ">> (16 * (k & 1))",                                      # the wide loader's 16-bit extraction
+               "-= two_n")                                               # the line rule's carry
+# the same rules whatever the operands are called: no second statement of one under other names
+CELLS_SHAPES = (r"floor\(\w+\*[\w.>-]*ms\)", r"top-1-\(int\)", r"\?\(\w+>=[\w.]*occupied\?2u?:", r"\w+\*\w+-\w+\*\w+\)\+\w+,", r"\(\w+>>1\)\]>>\(16\*\(\w+&1\)\)",
+                r"-=two_n")
+
+
+def squeeze(text):
+    """Without // comments and without blanks."""
+    return re.sub(r"\s+", "", re.sub(r"//.*", "", text))
+
+
+def check_map_cells(build):
+    """The rules that the readers of the flat world map share are defined once, in csrc/occupancy_map_cells.h, and the checks their
+    entries share once, in csrc/stage_glue.h.  Returns the squeezed text of the header."""
+    assert CELLS_HEADER in build.HEADERS
+    names = sorted(n for n in os.listdir(build.CSRC) if n.endswith((".h", ".hip", ".cpp")))
+    code = {n: squeeze(open(os.path.join(build.CSRC, n)).read()) for n in names}
+    for n in CELLS_KERNELS:
+        assert '#include"%s"' % CELLS_HEADER in code[n], n
+    for text, shape in zip(CELLS_TEXTS, CELLS_SHAPES):
+        for n in names:
+            want = 1 if n == CELLS_HEADER else 0
+            assert code[n].count(squeeze(text)) == want and len(re.findall(shape, code[n])) == want, (text, n)
+    for n in names:
+        assert ("rows>32768||cols<1" in code[n]) == (n == "stage_glue.h"), n
+    for n in MAP_HOSTS:
+        assert "reinterpret_cast<uintptr_t>" not in code[n], n
+    return code[CELLS_HEADER]
+
 
 # ---------------------------------------------------------------------------------------------------------------- fuse
 

@@ -13,6 +13,7 @@ import re
 import numpy as np
 import pytest
 
+import map_stage_cases as mc
 import util
 from test_top_view import _cuda, eng, sv  # noqa: F401 (fixtures)
 from test_occupancy_map import CLI_GRID, _drive_frames, drive  # noqa: F401 (drive: the committed KITTI frames' states, a fixture)
@@ -236,6 +237,7 @@ def test_header_build_and_loader_agree(eng):
     build = util.pkg("build")
     assert "clearance_kernels.hip" in build.SOURCES and "clearance.cpp" in build.SOURCES and "clearance_kernels.h" in build.HEADERS
     assert all(os.path.exists(os.path.join(build.CSRC, n)) for n in ("clearance_kernels.hip", "clearance.cpp", "clearance_kernels.h"))
+    mc.check_map_cells(build)  # the cell rules the map's readers share are defined once
     sv_mod = util.pkg("stereo_vision.sv")
     assert all(n in sv_mod.__doc__ for n in ("occupancy_clearance", "occupancy_clearance_brute", "clearance_paths", "clearance_discs")) and "(M)" in text
 

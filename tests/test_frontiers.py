@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import frontier_cases as fc
+import map_stage_cases as mc
 import util
 from test_top_view import _cuda, eng, sv  # noqa: F401 (fixtures)
 from test_occupancy_map import CLI_GRID, _drive_frames, drive  # noqa: F401 (drive: the committed KITTI frames' states, a fixture)
@@ -216,6 +217,7 @@ def test_header_build_and_loader_agree(eng):
     build = util.pkg("build")
     assert "frontier_kernels.hip" in build.SOURCES and "frontier.cpp" in build.SOURCES and "frontier_kernels.h" in build.HEADERS
     assert all(os.path.exists(os.path.join(build.CSRC, n)) for n in ("frontier_kernels.hip", "frontier.cpp", "frontier_kernels.h"))
+    mc.check_map_cells(build)  # the cell rules the map's readers share are defined once
     sv_mod = util.pkg("stereo_vision.sv")
     assert all(n in sv_mod.__doc__ for n in ("frontier_cells", "frontier_clusters", "frontier_goals")) and "(O)" in sv_mod.__doc__
     assert not re.search(r"^\s*(import|from)\s+scipy", open(sv_mod.__file__).read(), flags=re.M)  # the package does not import scipy

@@ -12,6 +12,7 @@ import re
 import numpy as np
 import pytest
 
+import map_stage_cases as mc
 import util
 from test_top_view import _cuda, eng, sv  # noqa: F401 (fixtures)
 from test_occupancy_map import CLI_GRID, DRIVE_MAP, _drive_frames, drive  # noqa: F401 (drive: the committed KITTI frames' states, a fixture)
@@ -292,6 +293,7 @@ def test_header_build_and_loader_agree(eng):
     build = util.pkg("build")
     assert "map_match_kernels.hip" in build.SOURCES and "map_match.cpp" in build.SOURCES and "map_match_kernels.h" in build.HEADERS
     assert all(os.path.exists(os.path.join(build.CSRC, n)) for n in ("map_match_kernels.hip", "map_match.cpp", "map_match_kernels.h"))
+    mc.check_map_cells(build)  # the cell rules the map's readers share are defined once
     sv_mod = util.pkg("stereo_vision.sv")
     assert "occupancy_match" in sv_mod.__doc__ and "occupancy_pose_window" in sv_mod.__doc__ and "(L)" in text and "sgn(kx)" in text
 

@@ -13,6 +13,7 @@ import re
 import numpy as np
 import pytest
 
+import map_stage_cases as mc
 import util
 import view_cases as vc
 from test_top_view import _cuda, eng, sv  # noqa: F401 (fixtures)
@@ -196,6 +197,7 @@ def test_header_build_and_loader_agree(eng):
     build = util.pkg("build")
     assert "view_kernels.hip" in build.SOURCES and "view.cpp" in build.SOURCES and "view_kernels.h" in build.HEADERS
     assert all(os.path.exists(os.path.join(build.CSRC, n)) for n in ("view_kernels.hip", "view.cpp", "view_kernels.h"))
+    mc.check_map_cells(build)  # the cell rules the map's readers share are defined once
     sv_mod = util.pkg("stereo_vision.sv")
     assert all(n in sv_mod.__doc__ for n in ("view_rays", "view_headings", "occupancy_view", "view_ranges")) and "(P)" in sv_mod.__doc__
 
