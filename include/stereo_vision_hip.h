@@ -71,6 +71,10 @@
  *      through the table of (Q); a voxel that enough rays of later frames pass through is emptied, so that the map can un-see a car that
  *      drove away or a mismatch at a depth edge.  stereo_vision.sv.voxel_map_carve states the definition in numpy.
  *
+ *  (U) Behind (T): the voxel map rendered into a camera (sv_voxel_render_device) - per view the nearest voxel of (Q)'s table under every
+ *      pixel: its depth, key and colour, the disparity the rig would measure there, and a per-pixel comparison with the disparity it did
+ *      measure, which names what is new and what was seen through.  stereo_vision.sv.voxel_map_render states the definition in numpy.
+ *
  * All sv_* functions return SV_OK (0) or a negative sv_status; sv_last_error() gives the text.
  * Nothing in this library calls exit().
  */
@@ -1396,7 +1400,68 @@ int sv_voxel_carve_device(void *map, size_t map_bytes, const sv_voxel_map_spec *
                           const double *poses, const double *origin, int batch, int cap, int seq0, int reach, int margin, int64_t min_miss, int ratio, int apply,
                           uint64_t *miss, int64_t *stats, void *stream);
 
-/* ---- (A) the reference's exported symbols ------------------------------------------------------------- */
+/* ---- (U) the voxel map rendered into a camera: (Q)'s table + world-to-camera poses + the rig's Q -> expected depth, colour, disparity ---- */
+
+/* (Q)'s map can be listed; this answers what a camera should see from a pose if the map is right.  Every product, sum and quotient below
+ * is a double, rounded on its own, in the order written (no FMA); everything behind them is an integer, so the result is bit-exact against
+ * stereo_vision.sv.voxel_map_render, which restates this in numpy, whatever the schedule.  Camera axes are Q's: x right, y down, z forward.
+ *
+ *   voxels   those with n >= min_n, m >= min_rows and last_seq >= since, the three filters of (Q)'s read-out; min_n >= 1, so a tombstone
+ *            of (T), whose n is 0, is never drawn.  A voxel's centre is the read-out's, Pw = lo + (c + (S + 0.5 n) / (65536 n)) * size.
+ *   camera   per view v, cams[v] = R row-major, then t, world to camera: Pc[k] = ((R[k,0] Pw.x + R[k,1] Pw.y) + R[k,2] Pw.z) + t[k].
+ *   depth    tz = Pc[2] / size, in cells.  The voxel is kept iff near <= tz && tz < far (NaN never passes); zq = (int)(tz * 256.0) < 2^28.
+ *   pixel    u = (f * Pc[0]) / Pc[2] + cx, v = (f * Pc[1]) / Pc[2] + cy; kept iff -2^30 < u < 2^30 and -2^30 < v < 2^30;
+ *            px = floor(u + 0.5), py = floor(v + 0.5).
+ *   square   r = r_max where half_px / tz >= r_max, else (int)(half_px / tz).  The voxel covers the pixels px - r .. px + r by py - r ..
+ *            py + r, clipped to the image; one that covers at least one pixel counts into `drawn`.
+ *   winner   of a pixel: the covering voxel with the smallest zq, then the smallest key - never the slot, which depends on the order in
+ *            which concurrent inserts claimed colliding entries.  `covered` counts the pixels that have one.
+ *   outputs  depth = zq, key = the winner's, color = its (2 C + n) / (2 n) per channel (the read-out's), disparity = (float)e with
+ *            z = (((double)zq + 0.5) / 256.0) * size and e = (f / z - q33) / q32 - what (B) would measure, in its units.  A pixel
+ *            without a winner holds -1, -1, 0 and -1.
+ *   compare  with `measured`: a measured pixel is valid iff it is finite and > 0; d is the float widened to double.  label = 0 neither
+ *            measured nor expected, 1 measured only, 2 expected only, 3 |d - e| <= tol, 4 d - e > tol (measured nearer: something new),
+ *            5 d - e < -tol (measured farther: the voxel was seen through); counts[v] = the pixels per label.
+ * An overflowed map: nothing is drawn, stats = -1, 0 per view, and every pixel is one without a winner.
+ *
+ * Enqueues four kernels on `stream` (a hipStream_t, NULL = the default stream) - the images cleared; a lane per slot of the table and an
+ * integer atomic minimum of zq per covered pixel; the same walk with a minimum of the key where the depth is the lane's; a lane per pixel
+ * - and does not wait: nothing is allocated and no host synchronisation is made.  views = 0 enqueues nothing.  The map is only read; no
+ * call that writes it may run at the same time. */
+typedef struct {
+    double f, cx, cy, q32, q33; /* of Q: f = Q[2][3], cx = -Q[0][3], cy = -Q[1][3], q32 = Q[3][2], q33 = Q[3][3]; finite, f > 0, q32 != 0 */
+    double half_px;             /* half the edge of a voxel in pixels at a depth of one cell: 0.5 f for a square as wide as the voxel; finite, >= 0 */
+    double near, far;           /* cells: 0 < near < far <= 2^20 */
+    int32_t width, height;      /* 1 .. 8192 each */
+    int32_t r_max;              /* 0 .. 8 */
+    int32_t reserved[5];        /* must be 0 */
+} sv_voxel_render_spec;
+
+/*   map, map_bytes, spec : the map, as (Q)'s entries take it
+ *   cam          : the camera; views * width * height < 2^31
+ *   cams         : float64 [views][12] device, 8-byte aligned; views in 0 .. 4096
+ *   min_n, min_rows, since : the filters; min_n >= 1
+ *   depth        : int32 [views][height][width] device;  key: int64 [views][height][width] device, 8-byte aligned
+ *   color        : uint8 [views][height][width][4] device, 4-byte aligned, or NULL;  disparity: float [views][height][width] device, or NULL
+ *   measured     : float [views][height][width] device, or NULL: no comparison; given iff label and counts are
+ *   tol          : HOST, one double >= 0, read by the call, in pixels of disparity; not read without `measured`
+ *   label        : uint8 [views][height][width] device;  counts: int64 [views][6] device, 8-byte aligned
+ *   stats        : int64 [views][2] device, 8-byte aligned - drawn, covered
+ * Returns SV_OK, SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued, everything untouched, the text in sv_last_error(NULL) - for: what the clear
+ * entry of (Q) refuses; cam NULL or a reserved word of it not 0; views outside 0 .. 4096; width or height outside 1 .. 8192; views * width *
+ * height >= 2^31; a camera word that is not finite, f <= 0 or q32 == 0; half_px < 0; r_max outside 0 .. 8; near or far outside the range
+ * above; min_n < 1; measured without label and counts or either of them without measured; tol NULL, negative or NaN with measured; cams,
+ * depth, key or stats NULL with views > 0; a pointer not aligned to its element; an output sharing a byte with the map, cams, measured or
+ * another output.  These checks run before any HIP call. */
+int sv_voxel_render_device(const void *map, size_t map_bytes, const sv_voxel_map_spec *spec, const sv_voxel_render_spec *cam, const double *cams, int views,
+                           int64_t min_n, int64_t min_rows, int since, int32_t *depth, int64_t *key, uint8_t *color, float *disparity, const float *measured,
+                           const double *tol, uint8_t *label, int64_t *stats, int64_t *counts, void *stream);
+/* Test and measurement hook, process-wide: the workgroups of the two table walks at most (0: the call chooses; 1 .. 2048), and the kernels
+ * a call enqueues (0: all four; 1 .. 3: the first that many - clear, depth, key -, which leaves the outputs unfinished).  A value outside
+ * its range leaves that word as it was.  Returns the groups before. */
+int sv_debug_voxel_render(int groups, int stages);
+
+/* ---- (A)the reference's exported symbols ------------------------------------------------------------- */
 
 typedef struct {
     double x, y, z;

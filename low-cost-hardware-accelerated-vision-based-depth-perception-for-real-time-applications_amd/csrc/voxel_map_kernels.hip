@@ -223,8 +223,7 @@ __global__ __launch_bounds__(64 * VMAP_WAVES) void k_vmap_write(VoxelMapArgs a) 
 #pragma unroll
         for (int k = 0; k < 3; k++) {
             const int32_t ci = vmap_key_cell(key, k);
-            const double c = (double)ci;
-            const double p = a.lo[k] + (c + ((double)(long long)e[VMAP_S + k] + 0.5 * (double)(long long)n) / (65536.0 * (double)(long long)n)) * a.size;
+            const double p = vmap_centre(a.lo[k], a.size, key, k, e[VMAP_S + k], n);
             if (DT == VMAP_F32) static_cast<float *>(a.xyz_out)[3 * (size_t)r + k] = (float)p;
             else static_cast<double *>(a.xyz_out)[3 * (size_t)r + k] = p;
             if (a.cell_out) a.cell_out[3 * (size_t)r + k] = ci;

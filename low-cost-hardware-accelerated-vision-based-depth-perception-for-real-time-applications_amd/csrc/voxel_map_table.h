@@ -1,9 +1,9 @@
 // The rules that make the world-fixed voxel map one map across its stages - insert and read-out (voxel_map_kernels.hip), match
-// (voxel_match_kernels.hip), carry (voxel_carry_kernels.hip), carve (voxel_carve_kernels.hip) -, written down once: the buffer's parts,
-// the entry's words, the hash, the two probes, and a row's way from the frame into a cell.  Plain inline functions and named constants;
-// what a stage does with an entry it has found stays in the stage.  The layout is voxel_map_kernels.h's; the definitions are
-// include/stereo_vision_hip.h (Q)'s.  The per-frame voxel cloud (voxel_kernels.hip) has another entry and another life cycle and shares
-// nothing with this.
+// (voxel_match_kernels.hip), carry (voxel_carry_kernels.hip), carve (voxel_carve_kernels.hip), render (voxel_render_kernels.hip) -,
+// written down once: the buffer's parts, the entry's words, the hash, the two probes, a row's way from the frame into a cell, and a
+// voxel's centre.  Plain inline functions and named constants; what a stage does with an entry it has found stays in the stage.  The
+// layout is voxel_map_kernels.h's; the definitions are include/stereo_vision_hip.h (Q)'s.  The per-frame voxel cloud
+// (voxel_kernels.hip) has another entry and another life cycle and shares nothing with this.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -49,6 +49,13 @@ __host__ __device__ inline int32_t vmap_key_cell(unsigned long long key, int k) 
 __host__ __device__ inline long long vmap_offset(double t, long long c) {
     const long long f = (long long)((t - (double)c) * 65536.0);
     return f > 65535 ? 65535 : f;
+}
+
+// A voxel's centre on axis k - the read-out's, which the render shares -: lo + (c + (S + 0.5 n) / (65536 n)) * size in double, as written,
+// from the key, the axis' offset sum S and the weight n >= 1.
+__host__ __device__ inline double vmap_centre(double lo, double size, unsigned long long key, int k, unsigned long long S, unsigned long long n) {
+    const double c = (double)vmap_key_cell(key, k);
+    return lo + (c + ((double)(long long)S + 0.5 * (double)(long long)n) / (65536.0 * (double)(long long)n)) * size;
 }
 
 // The read-out's three filters on the entry e, a word of which is only loaded where the ones before it passed.  Args has min_n, min_rows

@@ -529,6 +529,13 @@ class SvVoxelMapSpec(ctypes.Structure):
                 ("reserved", ctypes.c_int32 * 7)]
 
 
+class SvVoxelRenderSpec(ctypes.Structure):
+    """sv_voxel_render_spec of include/stereo_vision_hip.h."""
+    _fields_ = [("f", ctypes.c_double), ("cx", ctypes.c_double), ("cy", ctypes.c_double), ("q32", ctypes.c_double), ("q33", ctypes.c_double),
+                ("half_px", ctypes.c_double), ("near", ctypes.c_double), ("far", ctypes.c_double), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("r_max", ctypes.c_int32), ("reserved", ctypes.c_int32 * 5)]
+
+
 def _signatures():
     """The table below: per stage group of the C API, (D) to (S), its functions and per function (restype, argtypes), parameter by
     parameter as include/stereo_vision_hip.h declares them - tests/test_stage_signatures.py holds the two against each other."""
@@ -625,6 +632,10 @@ def _signatures():
         "voxel_carve": {  # (T)
             "sv_voxel_carve_device": (ci, [vp, sz, vm, vp, ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, i64, ci, ci, vp, vp, vp]),
         },
+        "voxel_render": {  # (U)
+            "sv_voxel_render_device": (ci, [vp, sz, vm, P(SvVoxelRenderSpec), vp, ci, i64, i64, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+            "sv_debug_voxel_render": (ci, [ci, ci]),
+        },
     }
 
 
@@ -634,6 +645,7 @@ _GROUP_NEEDS["view"] = ("occupancy_map",)
 _GROUP_NEEDS["voxel_match"] = ("voxel_map",)
 _GROUP_NEEDS["voxel_carry"] = ("voxel_map",)
 _GROUP_NEEDS["voxel_carve"] = ("voxel_map",)
+_GROUP_NEEDS["voxel_render"] = ("voxel_map",)
 _bound_groups = set()
 
 
@@ -2207,6 +2219,98 @@ def voxel_carve_touched(buf, params, miss):
     at = torch.nonzero(miss > 0).reshape(-1)
     order = torch.sort(keys[at]).indices
     return keys[at][order], miss[at][order]
+
+
+def voxel_render_lib():
+    """The library with the signatures of group (U) declared."""
+    return _bind("voxel_render")
+
+
+class VoxelRenderResult(_Result):
+    """What voxel_map_render returns, tensors on the map's device: depth int32 [V,H,W] (zq, -1 where no voxel covers the pixel), key int64
+    [V,H,W] (the winner's, or -1), color uint8 [V,H,W,4] (0), disparity float32 [V,H,W] (-1), stats int64 [V,2] = drawn, covered (-1, 0 for
+    an overflowed map), and with `measured` label uint8 [V,H,W] (stereo_vision.sv.VOXEL_RENDER_LABELS) and counts int64 [V,6] - None
+    without.  color and disparity are None where they were left out.  None is waited for."""
+    __slots__ = ("depth", "key", "color", "disparity", "stats", "label", "counts")
+
+
+def voxel_render_spec(camera, r_max=4, near=None, far=None):
+    """-> SvVoxelRenderSpec from a camera dict (stereo_vision.sv.voxel_render_camera's) and the call's r_max, near and far, after
+    stereo_vision.sv.voxel_render_words' checks (ValueError for a bad word)."""
+    from .stereo_vision.sv import voxel_render_words
+    w = voxel_render_words(camera, r_max, near, far)
+    spec = SvVoxelRenderSpec()
+    for k in ("f", "cx", "cy", "q32", "q33", "half_px", "near", "far", "width", "height", "r_max"):
+        setattr(spec, k, w[k])
+    return spec
+
+
+def voxel_map_render(buf, params, cams, camera, measured=None, tol=1.0, near=None, far=None, r_max=4, min_n=1, min_rows=1, since=0, color=True,
+                     disparity=True, out=None):
+    """The voxel map in `buf` rendered into V views of one camera - the definition of stereo_vision.sv.voxel_map_render on the GPU, bit
+    for bit (sv_voxel_render_device: four kernels): cams float64 [V,12], world to camera (stereo_vision.sv.voxel_render_cams; numpy,
+    uploaded once, or a tensor on the map's device), camera a dict of f, cx, cy, q32, q33, half_px, width and height
+    (stereo_vision.sv.voxel_render_camera), near < far in cells (None: 1 and 2^20), r_max 0 .. 8 pixels, min_n >= 1, min_rows and since
+    the read-out's filters.  measured: a float32 tensor [V,H,W] on the map's device (the engine's D1) to compare the expected disparity
+    with, at `tol` pixels: label and counts are then returned too.  color / disparity = False leaves that output out.  out: a
+    VoxelRenderResult of an earlier call of the same shapes to write into.  The map is only read.  -> VoxelRenderResult; enqueued on
+    torch's current stream, not waited for."""
+    import torch
+    spec = voxel_map_spec(params)
+    nbytes = _voxel_map_buffer(buf, spec)
+    dev = buf.device
+    cam = voxel_render_spec(camera, r_max, near, far)
+    H, W = int(cam.height), int(cam.width)
+    p = cams if isinstance(cams, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(cams, dtype=np.float64)).to(dev)
+    if p.device != dev or p.dtype != torch.float64 or p.dim() != 2 or p.shape[1] != 12:
+        raise ValueError("cams must be float64 [V,12] on the device (%s) of the map" % (dev,))
+    p = p.contiguous()
+    V = int(p.shape[0])
+    if V > 4096 or V * H * W >= 2 ** 31:
+        raise ValueError("at most 4096 views and fewer than 2^31 pixels in all, got %d x %d x %d" % (V, H, W))
+    for v, what, lo in ((min_n, "min_n", 1), (min_rows, "min_rows", -2 ** 63)):
+        if isinstance(v, bool) or int(v) != v or not lo <= v < 2 ** 63:
+            raise ValueError("%s must be an integer >= %d, got %r" % (what, lo, v))
+    if isinstance(since, bool) or int(since) != since or not -2 ** 31 <= since < 2 ** 31:
+        raise ValueError("since must be a 32-bit integer, got %r" % (since,))
+    if measured is not None:
+        if not (isinstance(measured, torch.Tensor) and measured.device == dev and measured.dtype == torch.float32 and tuple(measured.shape) == (V, H, W)):
+            raise ValueError("measured must be a float32 tensor [%d,%d,%d] on the map's device" % (V, H, W))
+        measured = measured.contiguous()
+        if not (isinstance(tol, (int, float)) and tol >= 0):
+            raise ValueError("tol must be a number >= 0, got %r" % (tol,))
+    shapes = {"depth": ((V, H, W), torch.int32), "key": ((V, H, W), torch.int64), "color": ((V, H, W, 4), torch.uint8), "disparity": ((V, H, W), torch.float32),
+              "stats": ((V, 2), torch.int64), "label": ((V, H, W), torch.uint8), "counts": ((V, 6), torch.int64)}
+    wanted = [k for k in VoxelRenderResult.__slots__ if not ((k == "color" and not color) or (k == "disparity" and not disparity)
+                                                             or (k in ("label", "counts") and measured is None))]
+    if out is not None and not isinstance(out, VoxelRenderResult):
+        raise ValueError("out must be a VoxelRenderResult")
+    res = VoxelRenderResult()
+    for k in wanted:
+        shape, dtype = shapes[k]
+        t = None if out is None else getattr(out, k)
+        if t is None:
+            t = torch.empty(shape, dtype=dtype, device=dev)
+        elif not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous()):
+            raise ValueError("out: %s must be a contiguous %s tensor %s on the map's device" % (k, str(dtype).replace("torch.", ""), list(shape)))
+        setattr(res, k, t)
+    if V == 0:  # nothing to enqueue
+        return res
+    tol_word = ctypes.c_double(float(tol))
+    with torch.cuda.device(dev):
+        rc = voxel_render_lib().sv_voxel_render_device(buf.data_ptr(), nbytes, ctypes.byref(spec), ctypes.byref(cam), p.data_ptr(), V, int(min_n), int(min_rows), int(since),
+                                                       res.depth.data_ptr(), res.key.data_ptr(), _ptr(res.color), _ptr(res.disparity), _ptr(measured),
+                                                       ctypes.addressof(tol_word) if measured is not None else None, _ptr(res.label), res.stats.data_ptr(),
+                                                       _ptr(res.counts), torch.cuda.current_stream(dev).cuda_stream)
+    _check(rc, "sv_voxel_render_device")
+    return res
+
+
+def debug_voxel_render(groups=0, stages=0):
+    """sv_debug_voxel_render: the workgroups of voxel_map_render's two table walks at most (0: the call chooses; 1 .. 2048) and the
+    kernels a call enqueues (0: all four; 1 .. 3: the first that many - clear, depth, key).  Returns the groups before.  Process-wide; a
+    test and measurement hook."""
+    return int(voxel_render_lib().sv_debug_voxel_render(int(groups), int(stages)))
 
 
 def host_support_filter(params, dcan, width, height, threads=0, lattice=False):

@@ -429,6 +429,12 @@ class StereoRig:
         the caller's odometry."""
         return VoxelMap(lo, hi, size, capacity, device=self.device)
 
+    def render_camera(self, size, footprint=1.0):
+        """-> the camera VoxelMap.render draws into, from the rig's own Q, width and height and the map's voxel size
+        (stereo_vision.sv.voxel_render_camera): `m.render(poses, rig.render_camera(m.params["size"]), transform=..., measured=d1)` is
+        the idiom.  footprint: the edge of a voxel's square in voxels."""
+        return _sv.voxel_render_camera(self.Q, self.width, self.height, size, footprint)
+
 
 class VoxelMap:
     """A world-fixed voxel map (include/stereo_vision_hip.h (Q), stereo_vision.sv.voxel_map_insert / voxel_map_rows): per cubic cell of
@@ -442,7 +448,8 @@ class VoxelMap:
     or another map's voxels added to this one.  The first three carry into a spare buffer of the map's size, allocated on first use and
     swapped with the map's from then on: they double the memory the map takes and allocate once, not per call.  carve() is group (T),
     stereo_vision.sv.voxel_map_carve: the voxels that the sight lines of later frames pass through are emptied, and keep their slots until
-    the next prune()."""
+    the next prune().  render() is group (U), stereo_vision.sv.voxel_map_render: what a camera should see of the map from given poses -
+    depth, colour and expected disparity per pixel - and, against a measured disparity, what is new and what was seen through."""
 
     def __init__(self, lo, hi, size, capacity, device="cuda"):
         import torch
@@ -646,6 +653,25 @@ class VoxelMap:
         if self._state is None:
             return voxel_carve_touched(self.buffer, self.params, result.miss)
         return torch.from_numpy(result["key"]), torch.from_numpy(result["miss"])
+
+    def render(self, poses, camera, transform=None, measured=None, tol=1.0, near=None, far=None, r_max=4, min_n=1, min_rows=1, since=0):
+        """What a camera should see of the map from V poses (include/stereo_vision_hip.h (U), stereo_vision.sv.voxel_map_render): poses
+        as for update - frame to world, float64 [V,12] or [V,4], numpy or a tensor -, camera StereoRig.render_camera's dict, transform
+        the rig's (XR, XT) from the camera's axes to the frame's (None: the frame's axes are the camera's); the world-to-camera words
+        are made on the host (stereo_vision.sv.voxel_render_cams).  measured: float32 [V,H,W] on the map's device - the engine's D1 of
+        the frames at those poses - to compare the expected disparity with, at tol pixels.  near, far in cells (None: 1 and 2^20), r_max
+        in pixels, min_n >= 1, min_rows, since: rows()' filters.  -> engine.VoxelRenderResult - depth, key, color, disparity, stats, and
+        with measured label and counts - of tensors on the map's device.  The map is not changed; not waited for."""
+        import torch
+        from .engine import VoxelRenderResult, voxel_map_render
+        p = poses.cpu().numpy() if isinstance(poses, torch.Tensor) else poses
+        XR, XT = (None, None) if transform is None else transform
+        cams = _sv.voxel_render_cams(p, XR, XT)
+        if self._state is None:
+            return voxel_map_render(self.buffer, self.params, cams, camera, measured, tol, near, far, r_max, min_n, min_rows, since)
+        m = measured.cpu().numpy() if isinstance(measured, torch.Tensor) else measured
+        res = _sv.voxel_map_render(self._state, cams, camera, m, tol, near, far, r_max, min_n, min_rows, since)
+        return VoxelRenderResult(**{k: None if v is None else torch.from_numpy(v) for k, v in res.items()})
 
     def write_ply(self, path, min_n=1, min_rows=1, since=0):
         """rows(...) as a binary PLY of coloured points (stereo_vision.sv.write_ply); -> the number of points.  RuntimeError for an

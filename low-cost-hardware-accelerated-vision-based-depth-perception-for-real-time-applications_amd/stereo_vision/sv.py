@@ -108,6 +108,12 @@ include/stereo_vision_hip.h (T); engine.voxel_map_carve / rig.VoxelMap.carve on 
 row's, occupancy_ray_cells' line rule on three axes, the weight of the rays that pass through a voxel no later frame has seen, and the
 voxels emptied that enough of it passed through - so that the map un-sees what is no longer there.  The reference has no counterpart
 (DESIGN.md §8).
+
+voxel_map_render (with voxel_map_render_brute, the plain loop, voxel_render_camera and voxel_render_cams) is the definition of the voxel
+map rendered into a camera (sv_voxel_render_device of include/stereo_vision_hip.h (U); engine.voxel_map_render / rig.VoxelMap.render on
+the GPU): per view the nearest voxel under every pixel - its depth, key and colour -, the disparity the rig would measure there, and its
+comparison with the disparity it did measure, pixel by pixel: nearer means something new, farther a voxel that was seen through.  The
+3-D counterpart of occupancy_view.  The reference has no counterpart.
 """
 import argparse
 import ctypes
@@ -913,6 +919,229 @@ def voxel_map_carve(map_state, xyz, n, counts, poses, origin=(0.0, 0.0, 0.0), se
         for f in ("n", "S", "C", "m"):
             map_state[f][gone] = 0
         map_state["first_seq"][gone], map_state["last_seq"][gone] = np.iinfo(np.int64).max, -1
+    return out
+
+
+VOXEL_RENDER_VIEWS_MAX = 4096
+VOXEL_RENDER_SIDE_MAX = 8192    # width and height of a rendered image at most
+VOXEL_RENDER_R_MAX = 8          # r_max at most: a voxel covers at most 17 x 17 pixels
+VOXEL_RENDER_FAR_MAX = 2.0 ** 20  # cells: zq = int(tz * 256) stays below 2^28
+VOXEL_RENDER_LABELS = ("none", "measured", "expected", "agree", "nearer", "farther")  # voxel_map_render's label, 0 .. 5
+VOXEL_RENDER_PNG = np.array([[0, 0, 0], [96, 96, 96], [40, 60, 140], [40, 160, 40], [230, 60, 40], [60, 120, 250]], np.uint8)  # --voxel-render: RGB per label
+_VOXEL_RENDER_LIM = 2.0 ** 30  # |u|, |v| of a voxel that is kept stay below it
+
+
+def voxel_render_camera(Q, width, height, size, footprint=1.0):
+    """The camera voxel_map_render draws into, from the rig's Q (4x4, the rectified form compact_cloud reprojects with: rows (1, 0, 0, -cx),
+    (0, 1, 0, -cy), (0, 0, 0, f), (0, 0, q32, q33)) as a dict: f = Q[2,3], cx = -Q[0,3], cy = -Q[1,3], q32 = Q[3,2], q33 = Q[3,3], width,
+    height, size and half_px = (0.5 * footprint) * f - half the edge in pixels, at a depth of one cell, of a square `footprint` voxels
+    wide (a voxel of `size` metres at tz cells spans f * size / (tz * size) pixels: the size cancels, and is only checked and kept).
+    ValueError for a Q of another form, f <= 0, q32 == 0 or a word that is not finite."""
+    Q = np.asarray(Q, np.float64)
+    if Q.size != 16:
+        raise ValueError("Q must be 4x4, got shape %s" % (Q.shape,))
+    Q = Q.reshape(4, 4)
+    zeros = [Q[0, 1], Q[0, 2], Q[1, 0], Q[1, 2], Q[2, 0], Q[2, 1], Q[2, 2], Q[3, 0], Q[3, 1]]
+    if not (np.isfinite(Q).all() and Q[0, 0] == 1.0 and Q[1, 1] == 1.0 and all(v == 0.0 for v in zeros) and Q[2, 3] > 0.0 and Q[3, 2] != 0.0):
+        raise ValueError("Q is not of the rectified form (1 0 0 -cx; 0 1 0 -cy; 0 0 0 f; 0 0 q32 q33) with f > 0 and q32 != 0")
+    size, footprint = np.float64(size), np.float64(footprint)
+    if not (np.isfinite(size) and size > 0 and np.isfinite(footprint) and footprint >= 0):
+        raise ValueError("size must be finite and > 0 and footprint finite and >= 0, got %r and %r" % (size, footprint))
+    cam = {"f": float(Q[2, 3]), "cx": float(-Q[0, 3]), "cy": float(-Q[1, 3]), "q32": float(Q[3, 2]), "q33": float(Q[3, 3]), "width": width, "height": height,
+           "size": float(size), "half_px": float((np.float64(0.5) * footprint) * Q[2, 3])}
+    voxel_render_words(cam)
+    return cam
+
+
+def voxel_render_words(camera, r_max=4, near=None, far=None):
+    """The words of sv_voxel_render_spec as a dict - f, cx, cy, q32, q33, half_px, near, far (floats), width, height, r_max (ints) - from a
+    camera dict (voxel_render_camera's) and a call's r_max, near and far (cells; None: 1 and 2^20), after the checks the C entry makes
+    (ValueError): every float finite, f > 0, q32 != 0, half_px >= 0, width and height in 1 .. 8192, r_max in 0 .. 8, 0 < near < far <= 2^20."""
+    try:
+        w = {k: float(camera[k]) for k in ("f", "cx", "cy", "q32", "q33", "half_px")}
+        w["near"], w["far"] = 1.0 if near is None else float(near), VOXEL_RENDER_FAR_MAX if far is None else float(far)
+    except (KeyError, TypeError, ValueError):
+        raise ValueError("a camera needs the numbers f, cx, cy, q32, q33 and half_px, and near and far must be numbers")
+    if not all(np.isfinite(v) for v in w.values()) or not w["f"] > 0 or w["q32"] == 0 or w["half_px"] < 0:
+        raise ValueError("the camera's words must be finite with f > 0, q32 != 0 and half_px >= 0, got %r" % (w,))
+    if not 0 < w["near"] < w["far"] <= VOXEL_RENDER_FAR_MAX:
+        raise ValueError("near and far need 0 < near < far <= 2^20 cells, got %r and %r" % (near, far))
+    for k, v, lo, hi in (("width", camera.get("width"), 1, VOXEL_RENDER_SIDE_MAX), ("height", camera.get("height"), 1, VOXEL_RENDER_SIDE_MAX), ("r_max", r_max, 0, VOXEL_RENDER_R_MAX)):
+        if v is None or isinstance(v, bool) or int(v) != v or not lo <= v <= hi:
+            raise ValueError("%s must be an integer in %d .. %d, got %r" % (k, lo, hi, v))
+        w[k] = int(v)
+    return w
+
+
+def voxel_render_cams(poses, XR=None, XT=None):
+    """float64 [V,12], world to camera (R row-major, then t, voxel_map_pose's layout) - what voxel_map_render takes -, from the poses
+    update() inserts frames at ([V,12], or the occupancy map's [V,4]: frame to world, Pw = R Pf + t) and the rig's transform (camera to
+    frame, Pf = XR Pc + XT; None: the identity, zero).  R and XR must be rotations: the inverse is the transpose.  On the host, in
+    double, every product and sum on its own and in this order: M[i,j] = (R[i,0] XR[0,j] + R[i,1] XR[1,j]) + R[i,2] XR[2,j];
+    o[i] = ((R[i,0] XT[0] + R[i,1] XT[1]) + R[i,2] XT[2]) + t[i], the camera's centre in the world; then Rc = M transposed and
+    tc[k] = -((Rc[k,0] o[0] + Rc[k,1] o[1]) + Rc[k,2] o[2]), so that Pc = Rc Pw + tc."""
+    p = voxel_map_pose_words(poses)
+    R, t = p[:, :9].reshape(-1, 3, 3), p[:, 9:]
+    XR = np.eye(3) if XR is None else np.asarray(XR, np.float64).reshape(3, 3)
+    XT = np.zeros(3) if XT is None else np.asarray(XT, np.float64).reshape(3)
+    M = np.stack([np.stack([(R[:, i, 0] * XR[0, j] + R[:, i, 1] * XR[1, j]) + R[:, i, 2] * XR[2, j] for j in range(3)], -1) for i in range(3)], 1)
+    o = np.stack([((R[:, i, 0] * XT[0] + R[:, i, 1] * XT[1]) + R[:, i, 2] * XT[2]) + t[:, i] for i in range(3)], -1)
+    Rc = M.transpose(0, 2, 1)
+    tc = np.stack([-((Rc[:, k, 0] * o[:, 0] + Rc[:, k, 1] * o[:, 1]) + Rc[:, k, 2] * o[:, 2]) for k in range(3)], -1)
+    return np.ascontiguousarray(np.concatenate([Rc.reshape(-1, 9), tc], 1))
+
+
+def _voxel_render_setup(map_state, cams, camera, measured, tol, near, far, r_max, min_n, min_rows, since):
+    """What voxel_map_render and voxel_map_render_brute share: the checked arguments, the indices of the voxels that pass the filters
+    (none for an overflowed map) and the outputs, every pixel without a winner."""
+    w = voxel_render_words(camera, r_max, near, far)
+    cams = np.asarray(cams, np.float64)
+    if cams.ndim != 2 or cams.shape[1] != 12 or len(cams) > VOXEL_RENDER_VIEWS_MAX or len(cams) * w["width"] * w["height"] >= 2 ** 31:
+        raise ValueError("cams must be [V,12] with V <= 4096 and V * width * height < 2^31, got shape %s" % (cams.shape,))
+    if isinstance(min_n, bool) or int(min_n) != min_n or min_n < 1:
+        raise ValueError("min_n must be an integer >= 1 - a carved voxel has n = 0 and divides -, got %r" % (min_n,))
+    V, H, W = len(cams), w["height"], w["width"]
+    out = {"depth": np.full((V, H, W), -1, np.int32), "key": np.full((V, H, W), -1, np.int64), "color": np.zeros((V, H, W, 4), np.uint8),
+           "disparity": np.full((V, H, W), -1, np.float32), "stats": np.zeros((V, 2), np.int64), "label": None, "counts": None}
+    if measured is not None:
+        measured = np.asarray(measured)
+        if measured.dtype != np.float32 or measured.shape != (V, H, W):
+            raise ValueError("measured must be float32 [%d,%d,%d], got %s %s" % (V, H, W, measured.dtype, measured.shape))
+        if not tol >= 0:
+            raise ValueError("tol must be a number >= 0, got %r" % (tol,))
+        out["label"], out["counts"] = np.zeros((V, H, W), np.uint8), np.zeros((V, 6), np.int64)
+    if map_state["overflowed"]:
+        out["stats"][:, 0] = -1
+        sel = np.zeros(0, np.int64)
+    else:
+        sel = np.flatnonzero((map_state["n"] >= min_n) & (map_state["m"] >= min_rows) & (map_state["last_seq"] >= since))
+    return w, cams, measured, sel, out
+
+
+def voxel_map_render(map_state, cams, camera, measured=None, tol=1.0, near=None, far=None, r_max=4, min_n=1, min_rows=1, since=0):
+    """A voxel map rendered into V views of one camera, the definition of include/stereo_vision_hip.h (U) in numpy: what the camera should
+    see from each pose if the map is right.  The map is only read.
+
+    cams float64 [V,12]: world to camera, R row-major then t (voxel_render_cams); camera: voxel_render_camera's dict; near < far in cells
+    (None: 1 and 2^20); r_max 0 .. 8; min_n >= 1, min_rows, since: voxel_map_rows' filters.  Camera axes are Q's: x right, y down, z
+    forward.  Every product, sum and quotient is a double, rounded on its own, in the order written.  Per view and voxel that passes
+    the filters: the centre Pw = lo + (c + (S + 0.5 n) / (65536 n)) * size (voxel_map_rows' xyz); Pc[k] = ((R[k,0] Pw.x + R[k,1] Pw.y) +
+    R[k,2] Pw.z) + t[k]; tz = Pc[2] / size, kept iff near <= tz < far, zq = int(tz * 256.0); u = (f * Pc[0]) / Pc[2] + cx, v = (f * Pc[1])
+    / Pc[2] + cy, kept iff both lie strictly inside -2^30 .. 2^30, px = floor(u + 0.5), py = floor(v + 0.5); r = r_max where half_px / tz
+    >= r_max, else int(half_px / tz).  The voxel covers the pixels px - r .. px + r by py - r .. py + r, clipped to the image; one that
+    covers a pixel counts into drawn.  The winner of a pixel is the covering voxel with the smallest zq, then the smallest key.
+    Returns a dict: depth int32 [V,H,W] = zq (-1 without a winner), key int64 [V,H,W] (-1), color uint8 [V,H,W,4] = the winner's
+    (2 C + n) // (2 n) (0), disparity float32 [V,H,W] = float32(e) with z = ((zq + 0.5) / 256.0) * size and e = (f / z - q33) / q32
+    (-1), stats int64 [V,2] = drawn, covered - the pixels with a winner; (-1, 0) and no winner anywhere for an overflowed map.
+    With measured (float32 [V,H,W], valid where finite and > 0; d = the float widened) also label uint8 [V,H,W] - 0 neither measured
+    nor expected, 1 measured only, 2 expected only, 3 |d - e| <= tol, 4 d - e > tol (nearer: something new), 5 d - e < -tol (farther: the
+    voxel was seen through) - and counts int64 [V,6], the pixels per label; both None without."""
+    w, cams, measured, sel, out = _voxel_render_setup(map_state, cams, camera, measured, tol, near, far, r_max, min_n, min_rows, since)
+    V, H, W, rm = len(cams), w["height"], w["width"], w["r_max"]
+    p = map_state["params"]
+    size = np.float64(p["size"])
+    key, n, C = map_state["key"][sel], map_state["n"][sel], map_state["C"][sel]
+    c = np.stack([key & 0xFFFFF, (key >> 20) & 0xFFFFF, (key >> 40) & 0xFFFFF], -1)
+    nf = n.astype(np.float64)[:, None]
+    Pw = np.array(p["lo"]) + (c.astype(np.float64) + (map_state["S"][sel].astype(np.float64) + 0.5 * nf) / (65536.0 * nf)) * size
+    f, cx, cy = (np.float64(w[k]) for k in ("f", "cx", "cy"))
+    for v in range(V):
+        R = cams[v]
+        with np.errstate(all="ignore"):
+            Pc = [((R[3 * k] * Pw[:, 0] + R[3 * k + 1] * Pw[:, 1]) + R[3 * k + 2] * Pw[:, 2]) + R[9 + k] for k in range(3)]
+            tz = Pc[2] / size
+            uu, vv = (f * Pc[0]) / Pc[2] + cx, (f * Pc[1]) / Pc[2] + cy
+            keep = (w["near"] <= tz) & (tz < w["far"]) & (-_VOXEL_RENDER_LIM < uu) & (uu < _VOXEL_RENDER_LIM) & (-_VOXEL_RENDER_LIM < vv) & (vv < _VOXEL_RENDER_LIM)
+            at = np.flatnonzero(keep)
+            zq = (tz[at] * 256.0).astype(np.int64)
+            px, py = np.floor(uu[at] + 0.5).astype(np.int64), np.floor(vv[at] + 0.5).astype(np.int64)
+            q = np.float64(w["half_px"]) / tz[at]
+            r = np.where(q >= rm, rm, np.minimum(q, rm).astype(np.int64))
+        drawn = (np.maximum(px - r, 0) <= np.minimum(px + r, W - 1)) & (np.maximum(py - r, 0) <= np.minimum(py + r, H - 1))
+        out["stats"][v, 0] += int(drawn.sum())
+        at, zq, px, py, r = at[drawn], zq[drawn], px[drawn], py[drawn], r[drawn]
+        if len(at):
+            d = np.arange(-int(r.max()), int(r.max()) + 1)
+            X, Y = np.broadcast_arrays(px[:, None, None] + d[None, None, :], py[:, None, None] + d[None, :, None])
+            ok = (np.abs(d)[None, None, :] <= r[:, None, None]) & (np.abs(d)[None, :, None] <= r[:, None, None]) & (0 <= X) & (X < W) & (0 <= Y) & (Y < H)
+            who = np.broadcast_to(np.arange(len(at))[:, None, None], ok.shape)[ok]
+            pix = (Y * W + X)[ok]
+            order = np.lexsort((key[at][who], zq[who], pix))  # by pixel, then zq, then key
+            first = np.ones(len(order), bool)
+            first[1:] = pix[order][1:] != pix[order][:-1]
+            win, pix = who[order[first]], pix[order[first]]
+            nw = n[at[win]]
+            out["depth"][v].reshape(-1)[pix] = zq[win]
+            out["key"][v].reshape(-1)[pix] = key[at[win]]
+            out["color"][v].reshape(-1, 4)[pix] = ((2 * C[at[win]] + nw[:, None]) // (2 * nw[:, None])).astype(np.uint8)
+    has = out["depth"] >= 0
+    out["stats"][:, 1] = has.sum((1, 2))
+    with np.errstate(all="ignore"):
+        z = ((out["depth"].astype(np.float64) + 0.5) / 256.0) * size
+        e = (f / z - np.float64(w["q33"])) / np.float64(w["q32"])
+        out["disparity"][has] = e[has].astype(np.float32)
+        if measured is not None:
+            valid = np.isfinite(measured) & (measured > 0)
+            diff = measured.astype(np.float64) - e
+            both = np.where(diff > tol, 4, np.where(diff < -tol, 5, 3))
+            out["label"][...] = np.where(valid & has, both, valid * 1 + has * 2).astype(np.uint8)
+            out["counts"][...] = np.stack([(out["label"] == k).sum((1, 2)) for k in range(6)], -1)
+    return out
+
+
+def voxel_map_render_brute(map_state, cams, camera, measured=None, tol=1.0, near=None, far=None, r_max=4, min_n=1, min_rows=1, since=0):
+    """voxel_map_render's definition as a plain loop over views, voxels and pixels on Python floats and ints: the form the vectorised one
+    is checked against.  Same arguments, same dict."""
+    import math
+    w, cams, measured, sel, out = _voxel_render_setup(map_state, cams, camera, measured, tol, near, far, r_max, min_n, min_rows, since)
+    V, H, W, rm = len(cams), w["height"], w["width"], w["r_max"]
+    p = map_state["params"]
+    lo, size = [float(x) for x in p["lo"]], float(p["size"])
+    best = {}  # (view, y, x) -> (zq, key, voxel)
+    for v in range(V):
+        R = [float(x) for x in cams[v]]
+        for i in sel:
+            key, n = int(map_state["key"][i]), int(map_state["n"][i])
+            Pw = [lo[k] + (float((key >> (20 * k)) & 0xFFFFF) + (float(int(map_state["S"][i, k])) + 0.5 * float(n)) / (65536.0 * float(n))) * size for k in range(3)]
+            Pc = [((R[3 * k] * Pw[0] + R[3 * k + 1] * Pw[1]) + R[3 * k + 2] * Pw[2]) + R[9 + k] for k in range(3)]
+            tz = Pc[2] / size
+            if not (w["near"] <= tz and tz < w["far"]):
+                continue
+            zq = int(tz * 256.0)
+            uu, vv = (w["f"] * Pc[0]) / Pc[2] + w["cx"], (w["f"] * Pc[1]) / Pc[2] + w["cy"]
+            if not (-_VOXEL_RENDER_LIM < uu < _VOXEL_RENDER_LIM and -_VOXEL_RENDER_LIM < vv < _VOXEL_RENDER_LIM):
+                continue
+            px, py = math.floor(uu + 0.5), math.floor(vv + 0.5)
+            q = w["half_px"] / tz
+            r = rm if q >= rm else int(q)
+            covers = False
+            for y in range(max(py - r, 0), min(py + r, H - 1) + 1):
+                for x in range(max(px - r, 0), min(px + r, W - 1) + 1):
+                    covers = True
+                    if (v, y, x) not in best or (zq, key) < best[v, y, x][:2]:
+                        best[v, y, x] = (zq, key, i)
+            out["stats"][v, 0] += 1 if covers else 0
+    for (v, y, x), (zq, key, i) in best.items():
+        n = int(map_state["n"][i])
+        out["depth"][v, y, x], out["key"][v, y, x] = zq, key
+        out["color"][v, y, x] = [(2 * int(map_state["C"][i, j]) + n) // (2 * n) for j in range(4)]
+        out["stats"][v, 1] += 1
+    with np.errstate(over="ignore"):
+        for v in range(V):
+            for y in range(H):
+                for x in range(W):
+                    has, e = (v, y, x) in best, 0.0
+                    if has:
+                        z = ((float(best[v, y, x][0]) + 0.5) / 256.0) * size
+                        e = (w["f"] / z - w["q33"]) / w["q32"]
+                        out["disparity"][v, y, x] = np.float32(e)
+                    if measured is None:
+                        continue
+                    d = float(measured[v, y, x])
+                    valid = math.isfinite(d) and d > 0
+                    lab = (4 if d - e > tol else 5 if d - e < -tol else 3) if valid and has else (1 if valid else 0) + (2 if has else 0)
+                    out["label"][v, y, x] = lab
+                    out["counts"][v, lab] += 1
     return out
 
 
@@ -2574,6 +2803,11 @@ def main(argv=None):
                              "batch's frames from the casting one on has seen, with at least MIN_MISS (default 2) rows' weight of rays "
                              "through it and at least RATIO / 256 (default 0) of its own weight, is emptied.  Prints rays, steps, touched "
                              "and carved per batch")
+    parser.add_argument("--voxel-render", type=str, default="", metavar="DIR[,TOL_PX]",
+                        help="with --voxel-map: before a batch is inserted, render the map built so far into the camera at the batch's "
+                             "poses and compare the expected disparity with the batch's measured one at TOL_PX pixels (default 1); "
+                             "writes per frame DIR/NNNNNN.expected.png (the model's colours) and DIR/NNNNNN.change.png (none, measured "
+                             "only, expected only, agree, nearer = new, farther = seen through) and prints the pixels per label")
     parser.add_argument("--voxel-match", type=str, default="", metavar="DX,DY,DZ,DYAW[,NX,NY,NZ,NYAW]",
                         help="with --voxel-map: take the poses as guesses at height 0 - frame 0 is inserted where its line says; every later "
                              "frame's voxel cloud is first matched against the voxel map built so far over a window of +-DX, +-DY, +-DZ metres "
@@ -2687,6 +2921,14 @@ def main(argv=None):
             args.voxel_carve_spec = cli_voxel_carve_spec(float(words[0]), int(words[1]) if len(words) > 1 else 2, int(words[2]) if len(words) > 2 else 0, args.voxel)
         except ValueError as e:
             parser.error("--voxel-carve: %s" % e)
+    args.voxel_render_spec = None
+    if args.voxel_render:
+        if not args.voxel_map:
+            parser.error("--voxel-render needs --voxel-map")
+        try:
+            args.voxel_render_spec = cli_voxel_render_spec(args.voxel_render)
+        except ValueError as e:
+            parser.error("--voxel-render: %s" % e)
     if (args.voxel_window or args.voxel_forget) and not args.voxel_map:
         parser.error("--voxel-window and --voxel-forget need --voxel-map")
     if args.voxel_forget < 0:
@@ -2734,6 +2976,8 @@ def main(argv=None):
         os.makedirs(args.ply, exist_ok=True)
     if args.occupancy:
         os.makedirs(args.occupancy, exist_ok=True)
+    if args.voxel_render_spec is not None:
+        os.makedirs(args.voxel_render_spec[0], exist_ok=True)
     args.pose_rows = None
     if args.voxel_map:
         try:
@@ -2846,6 +3090,23 @@ def cli_voxel_carve_text(res):
     return ", ".join("%s %d" % (k, v) for k, v in zip(VOXEL_CARVE_STATS, values))
 
 
+def cli_voxel_render_spec(text):
+    """(DIR, TOL_PX) of --voxel-render's DIR[,TOL_PX]: ValueError with the text the CLI prints."""
+    words = text.rsplit(",", 1)
+    try:
+        tol = float(words[1]) if len(words) > 1 else 1.0
+    except ValueError:
+        raise ValueError("TOL_PX must be a number, got %r" % (words[1],))
+    if not words[0] or not (np.isfinite(tol) and tol >= 0):
+        raise ValueError("DIR[,TOL_PX] with TOL_PX >= 0, got %r" % (text,))
+    return words[0], tol
+
+
+def cli_voxel_render_text(counts):
+    """The pixels per label of one view (six integers) as the CLI prints them."""
+    return ", ".join("%s %d" % (k, int(v)) for k, v in zip(VOXEL_RENDER_LABELS, counts))
+
+
 def _write_png(path, u8):
     from PIL import Image
     Image.fromarray(u8).save(path)
@@ -2872,6 +3133,7 @@ def _run_batched(args, ldir, rdir, files):
             right = torch.from_numpy(np.stack([r for _, r in lr])).cuda(rig.device)
             torch.cuda.synchronize(rig.device)
             t0 = time.perf_counter()
+            seen = None
             if args.ply:  # what rig.compact_clouds(..., transform=(CAMERA_TO_VEHICLE, None), lo=, hi=) runs, keeping d1 for the other outputs
                 gl, gr, col = rig.frontend(left, right, pixel_format="bgr", colors=True)
                 d1, _ = rig.engine.process_device(gl, gr, want_d2=False)
@@ -2882,6 +3144,8 @@ def _run_batched(args, ldir, rdir, files):
                         if args.voxel_window and cli_voxel_window_left(model.params, at[0, 0], at[0, 1]):
                             print("voxel map recentred at frame %d: %s" % (i, cli_voxel_carry_text(model.recenter(at[0, 0], at[0, 1]))))
                         went = voxel_map_pose(at[:, 0], at[:, 1], at[:, 2])  # the poses the batch's frames are inserted at
+                        if args.voxel_render_spec is not None:  # the map of the frames before this batch, seen from this batch's poses
+                            seen = model.render(went, rig.render_camera(args.voxel), transform=(CAMERA_TO_VEHICLE, None), measured=d1, tol=args.voxel_render_spec[1])
                         if args.voxel_match_window is None:
                             model.update(voxels[0], voxels[1], voxels[3], voxels[5], went)
                         for k in range(len(names) if args.voxel_match_window is not None else 0):  # one at a time: against the frames before it
@@ -2927,6 +3191,11 @@ def _run_batched(args, ldir, rdir, files):
             if args.occupancy:
                 for name, st in zip(names, occ.state.cpu().numpy()):
                     _write_png(os.path.join(args.occupancy, name), OCCUPANCY_PNG[st])
+            if seen is not None:  # BGRA to RGB; the labels through the palette
+                for k, (bgra, lab, cnt) in enumerate(zip(seen.color.cpu().numpy(), seen.label.cpu().numpy(), seen.counts.cpu().numpy())):
+                    _write_png(os.path.join(args.voxel_render_spec[0], "%06d.expected.png" % (i + k)), np.ascontiguousarray(bgra[..., 2::-1]))
+                    _write_png(os.path.join(args.voxel_render_spec[0], "%06d.change.png" % (i + k)), VOXEL_RENDER_PNG[lab])
+                    print("voxel map rendered before frame %d: %s" % (i + k, cli_voxel_render_text(cnt)))
             if args.ply:
                 parts = split_voxel_clouds(voxels[0], voxels[5], voxels[1]) if args.voxel else split_clouds(clouds[0], clouds[3], clouds[1])
                 for name, (xyz, color) in zip(names, parts):
