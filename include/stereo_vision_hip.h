@@ -75,6 +75,10 @@
  *      pixel: its depth, key and colour, the disparity the rig would measure there, and a per-pixel comparison with the disparity it did
  *      measure, which names what is new and what was seen through.  stereo_vision.sv.voxel_map_render states the definition in numpy.
  *
+ *  (V) Behind (T): the voxel map flattened into (K)'s layout (sv_voxel_flatten_device) - the voxels of (Q)'s table sliced by their height
+ *      above an absolute or a local floor into ground, obstacle and overhead, and per flat cell the logodds and last_seen words that (M)
+ *      to (P) take, so that the planner runs on the voxel map.  stereo_vision.sv.voxel_map_flatten states the definition in numpy.
+ *
  * All sv_* functions return SV_OK (0) or a negative sv_status; sv_last_error() gives the text.
  * Nothing in this library calls exit().
  */
@@ -1460,6 +1464,65 @@ int sv_voxel_render_device(const void *map, size_t map_bytes, const sv_voxel_map
  * a call enqueues (0: all four; 1 .. 3: the first that many - clear, depth, key -, which leaves the outputs unfinished).  A value outside
  * its range leaves that word as it was.  Returns the groups before. */
 int sv_debug_voxel_render(int groups, int stages);
+
+/* ---- (V) the voxel map flattened into an occupancy map: (Q)'s table + (K)'s map spec + a height rule -> logodds, last_seen, floor, top ---- */
+
+/* (Q)'s map holds heights; (K)'s layout is what the planner stages (M) to (P) take.  This writes the one from the other.  The centre of a
+ * voxel and its flat cell are doubles, every product, sum and quotient rounded on its own, in the order written (no FMA); everything behind
+ * them is an integer minimum, maximum or sum, so the result is bit-exact against stereo_vision.sv.voxel_map_flatten, which restates this
+ * in numpy, whatever the schedule and wherever the inserts left an entry in the table.
+ *
+ *   voxels   those with n >= min_n, m >= min_rows and last_seq >= since, the three filters of (Q)'s read-out; min_n >= 1, so a tombstone
+ *            of (T), whose n is 0, never takes part.
+ *   cell     X, Y = the read-out's centre on axes 0 and 1, lo + (c + (S + 0.5 n) / (65536 n)) * size; gx = floor(X ms), gy = floor(Y ms),
+ *            ms = (double)scale; the flat cell is (top - 1 - gx, left - 1 - gy) where top - rows <= gx <= top - 1 and left - cols <= gy <=
+ *            left - 1, compared in double before anything is converted.  A voxel outside counts into `outside` and does nothing else.
+ *   height   zq = cz * 256 + ((S_z / n) >> 8) in integers: 1/256 of a voxel cell above lo[2]; S_z / n <= 65535, so zq < 2^28.
+ *   low/seen per flat cell the least zq and the largest last_seq of its voxels.
+ *   floor    mode 0: base = z_ref_q in every cell.  mode 1: base of a cell = the least `low` over the cells within `radius` rows and
+ *            columns of it that lie inside the map and hold a voxel - a wall's own column has no ground voxel under it, its neighbours
+ *            have.  A cell that holds a voxel has a base.
+ *   classify with h = zq - base of the voxel's cell: h < -step_q below (counted, ignored in its cell; mode 0 only), else h < step_q
+ *            ground, else h < height_q obstacle, else overhead.  cells[r][c] = the cell's ground, obstacle and overhead voxels; top[r][c] =
+ *            the largest zq among its ground and obstacle voxels, -1 without one.
+ *   resolve  obstacle >= min_obstacle: L = min(l_max, obstacle * l_occ); else ground >= min_ground: L = max(l_min, -(ground * l_free)) -
+ *            the products in 64 bits -, both with last_seen = seen; else L = 0 and last_seen = -1: a cell that holds overhead voxels only
+ *            stays unknown.  l_occ, l_free, l_min and l_max are the flat map's.
+ *   outputs  logodds, last_seen; floor = base (mode 1: -1 where the window holds no voxel); top; cells; stats = drawn (the voxels that
+ *            took part and fell inside), outside, below, ground, obstacle, overhead, occupied_cells, free_cells.
+ * An overflowed map: stats[0] = -1, the other counts 0, and the outputs of a map without voxels.
+ *
+ * Enqueues four or five kernels on `stream` (a hipStream_t, NULL = the default stream) - the outputs cleared; a lane per slot of the table
+ * with integer atomic minima and maxima for low and seen; in mode 1 with radius > 0 a lane per flat cell for the floor; the same walk with
+ * an atomic add on one of the cell's counts and a maximum on top; a lane per flat cell for L and last_seen - and does not wait: nothing
+ * is allocated and no host synchronisation is made.  The voxel map is only read; no call that writes it may run at the same time. */
+typedef struct {
+    int32_t mode;                     /* 0: an absolute floor at z_ref_q; 1: a local floor, the lowest voxel within `radius` flat cells */
+    int32_t z_ref_q;                  /* mode 0: the floor in zq units, floor((z_ref - lo[2]) / size * 256) on the host; |.| < 2^30.  Not read in mode 1 */
+    int32_t step_q, height_q;         /* zq units: 1 <= step_q < height_q < 2^28 */
+    int32_t radius;                   /* 0 .. 8 flat cells */
+    int32_t min_obstacle, min_ground; /* >= 1 */
+    int32_t reserved[9];              /* must be 0 */
+} sv_voxel_flatten_spec;
+
+/*   map, map_bytes, spec : the voxel map, as (Q)'s entries take it
+ *   flat         : the flat map's words, as (K)'s entries take them; rows * cols <= 8 000 000, what (N) and (O) take
+ *   flatten      : the height rule
+ *   min_n, min_rows, since : the filters; min_n >= 1
+ *   logodds      : int16 [rows][cols] device, 2-byte aligned;  last_seen, floor, top: int32 [rows][cols] device
+ *   cells        : int32 [rows][cols][3] device;  stats: int64 [8] device, 8-byte aligned
+ * Returns SV_OK, SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued, everything untouched, the text in sv_last_error(NULL) - for: what the clear
+ * entry of (Q) refuses; what (K)'s fuse entry refuses of a map spec; rows * cols above 8 000 000; flatten NULL or a reserved word of it
+ * not 0; mode neither 0 nor 1; |z_ref_q| >= 2^30 in mode 0; step_q, height_q, radius, min_obstacle or min_ground outside the ranges
+ * above; min_n < 1; an output NULL; a pointer not aligned to its element; an output sharing a byte with the voxel map or another output.
+ * These checks run before any HIP call. */
+int sv_voxel_flatten_device(const void *map, size_t map_bytes, const sv_voxel_map_spec *spec, const sv_occupancy_map_spec *flat, const sv_voxel_flatten_spec *flatten,
+                            int64_t min_n, int64_t min_rows, int since, int16_t *logodds, int32_t *last_seen, int32_t *floor, int32_t *top, int32_t *cells,
+                            int64_t *stats, void *stream);
+/* Test and measurement hook, process-wide: the workgroups of the two table walks at most (0: the call chooses; 1 .. 2048), and the kernels
+ * a call enqueues (0: all; 1 .. 4: the first that many of clear, walk A, floor, walk B - the floor counts where it is skipped, too -, which
+ * leaves the outputs unfinished).  A value outside its range leaves that word as it was.  Returns the groups before. */
+int sv_debug_voxel_flatten(int groups, int stages);
 
 /* ---- (A)the reference's exported symbols ------------------------------------------------------------- */
 

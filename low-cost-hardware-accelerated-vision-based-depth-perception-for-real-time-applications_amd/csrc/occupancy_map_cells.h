@@ -1,5 +1,6 @@
 // The rules that make the flat world map one map for its readers - the match (map_match_kernels.hip), the path check
-// (clearance_kernels.hip), the view (view_kernels.hip), the frontier cells (frontier_kernels.hip) -, written down once: the map's geometry
+// (clearance_kernels.hip), the view (view_kernels.hip), the frontier cells (frontier_kernels.hip) - and for the voxel map's way into it
+// (voxel_flatten_kernels.hip) -, written down once: the map's geometry
 // words, a vehicle point's way under a pose into a cell, a cell's state, and the step of the line rule, which the per-frame grid's ray
 // kernel (occupancy_kernels.hip) walks as well.  Plain inline functions and one struct; what a stage does with the cell it has found
 // stays in the stage.  The definitions are include/stereo_vision_hip.h (K)'s, restated in stereo_vision/sv.py (occupancy_cells_of,

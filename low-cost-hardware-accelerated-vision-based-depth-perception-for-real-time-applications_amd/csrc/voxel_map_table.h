@@ -1,9 +1,9 @@
 // The rules that make the world-fixed voxel map one map across its stages - insert and read-out (voxel_map_kernels.hip), match
-// (voxel_match_kernels.hip), carry (voxel_carry_kernels.hip), carve (voxel_carve_kernels.hip), render (voxel_render_kernels.hip) -,
-// written down once: the buffer's parts, the entry's words, the hash, the two probes, a row's way from the frame into a cell, and a
-// voxel's centre.  Plain inline functions and named constants; what a stage does with an entry it has found stays in the stage.  The
-// layout is voxel_map_kernels.h's; the definitions are include/stereo_vision_hip.h (Q)'s.  The per-frame voxel cloud
-// (voxel_kernels.hip) has another entry and another life cycle and shares nothing with this.
+// (voxel_match_kernels.hip), carry (voxel_carry_kernels.hip), carve (voxel_carve_kernels.hip), render (voxel_render_kernels.hip), flatten
+// (voxel_flatten_kernels.hip) -, written down once: the buffer's parts, the entry's words, the hash, the two probes, a row's way from the
+// frame into a cell, and a voxel's centre and height.  Plain inline functions and named constants; what a stage does with an entry it
+// has found stays in the stage.  The layout is voxel_map_kernels.h's; the definitions are include/stereo_vision_hip.h (Q)'s.  The
+// per-frame voxel cloud (voxel_kernels.hip) has another entry and another life cycle and shares nothing with this.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -56,6 +56,12 @@ __host__ __device__ inline long long vmap_offset(double t, long long c) {
 __host__ __device__ inline double vmap_centre(double lo, double size, unsigned long long key, int k, unsigned long long S, unsigned long long n) {
     const double c = (double)vmap_key_cell(key, k);
     return lo + (c + ((double)(long long)S + 0.5 * (double)(long long)n) / (65536.0 * (double)(long long)n)) * size;
+}
+
+// A voxel's mean position on axis k in 1/256 of a cell from lo - what the flatten slices by -: c * 256 + ((S / n) >> 8), integers only, from
+// the key, the axis' offset sum S and the weight n >= 1.  S / n <= 65535, so the result stays below 2^28.
+__host__ __device__ inline int32_t vmap_zq(unsigned long long key, int k, unsigned long long S, unsigned long long n) {
+    return vmap_key_cell(key, k) * 256 + (int32_t)((S / n) >> 8);
 }
 
 // The read-out's three filters on the entry e, a word of which is only loaded where the ones before it passed.  Args has min_n, min_rows

@@ -536,6 +536,12 @@ class SvVoxelRenderSpec(ctypes.Structure):
                 ("r_max", ctypes.c_int32), ("reserved", ctypes.c_int32 * 5)]
 
 
+class SvVoxelFlattenSpec(ctypes.Structure):
+    """sv_voxel_flatten_spec of include/stereo_vision_hip.h."""
+    _fields_ = [("mode", ctypes.c_int32), ("z_ref_q", ctypes.c_int32), ("step_q", ctypes.c_int32), ("height_q", ctypes.c_int32), ("radius", ctypes.c_int32),
+                ("min_obstacle", ctypes.c_int32), ("min_ground", ctypes.c_int32), ("reserved", ctypes.c_int32 * 9)]
+
+
 def _signatures():
     """The table below: per stage group of the C API, (D) to (S), its functions and per function (restype, argtypes), parameter by
     parameter as include/stereo_vision_hip.h declares them - tests/test_stage_signatures.py holds the two against each other."""
@@ -636,6 +642,10 @@ def _signatures():
             "sv_voxel_render_device": (ci, [vp, sz, vm, P(SvVoxelRenderSpec), vp, ci, i64, i64, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
             "sv_debug_voxel_render": (ci, [ci, ci]),
         },
+        "voxel_flatten": {  # (V)
+            "sv_voxel_flatten_device": (ci, [vp, sz, vm, om, P(SvVoxelFlattenSpec), i64, i64, ci, vp, vp, vp, vp, vp, vp, vp]),
+            "sv_debug_voxel_flatten": (ci, [ci, ci]),
+        },
     }
 
 
@@ -646,6 +656,7 @@ _GROUP_NEEDS["voxel_match"] = ("voxel_map",)
 _GROUP_NEEDS["voxel_carry"] = ("voxel_map",)
 _GROUP_NEEDS["voxel_carve"] = ("voxel_map",)
 _GROUP_NEEDS["voxel_render"] = ("voxel_map",)
+_GROUP_NEEDS["voxel_flatten"] = ("voxel_map", "occupancy_map")
 _bound_groups = set()
 
 
@@ -2311,6 +2322,81 @@ def debug_voxel_render(groups=0, stages=0):
     kernels a call enqueues (0: all four; 1 .. 3: the first that many - clear, depth, key).  Returns the groups before.  Process-wide; a
     test and measurement hook."""
     return int(voxel_render_lib().sv_debug_voxel_render(int(groups), int(stages)))
+
+
+def voxel_flatten_lib():
+    """The library with the signatures of group (V) declared."""
+    return _bind("voxel_flatten")
+
+
+class VoxelFlattenResult(_Result):
+    """What voxel_map_flatten returns, tensors on the voxel map's device: logodds int16 and last_seen int32 [rows,cols] - the flat map's
+    layout, what occupancy_clearance, frontier_cells and occupancy_view take -, floor and top int32 [rows,cols] (zq units, -1 where there
+    is none), cells int32 [rows,cols,3] = ground, obstacle and overhead voxels, and stats int64 [8]
+    (stereo_vision.sv.VOXEL_FLATTEN_STATS; drawn = -1 for an overflowed map), which stays on the device until it is asked for.  None is
+    waited for."""
+    __slots__ = ("logodds", "last_seen", "floor", "top", "cells", "stats")
+
+
+def voxel_flatten_spec(spec):
+    """-> SvVoxelFlattenSpec from a dict of its words (stereo_vision.sv.voxel_flatten_params'), after stereo_vision.sv.voxel_flatten_words'
+    checks (ValueError for a bad word)."""
+    from .stereo_vision.sv import voxel_flatten_words
+    out = SvVoxelFlattenSpec()
+    for k, v in voxel_flatten_words(spec).items():
+        setattr(out, k, v)
+    return out
+
+
+def voxel_map_flatten(buf, params, flat_map, spec, min_n=1, min_rows=1, since=0, out=None):
+    """The voxel map in `buf` flattened into the layout of the flat map `flat_map` - the definition of
+    stereo_vision.sv.voxel_map_flatten on the GPU, bit for bit (sv_voxel_flatten_device: four or five kernels): flat_map an
+    SvOccupancyMapSpec or a dict of its nine words (stereo_vision.sv.occupancy_map_params), at most 8 000 000 cells; spec a dict of the
+    height rule's words (stereo_vision.sv.voxel_flatten_params); min_n >= 1, min_rows and since the read-out's filters.  out: a
+    VoxelFlattenResult to write into - an earlier call's, or one whose logodds and last_seen are a map's own tensors; a slot that is None
+    is allocated.  The voxel map is only read.  -> VoxelFlattenResult; enqueued on torch's current stream, not waited for."""
+    import torch
+    from .stereo_vision.sv import VOXEL_FLATTEN_CELLS_MAX, occupancy_map_words
+    vspec = voxel_map_spec(params)
+    nbytes = _voxel_map_buffer(buf, vspec)
+    dev = buf.device
+    words = occupancy_map_words(flat_map)
+    rows, cols = words["rows"], words["cols"]
+    if rows * cols > VOXEL_FLATTEN_CELLS_MAX:
+        raise ValueError("a flat map of %d x %d cells: at most 8 000 000" % (rows, cols))
+    fspec = voxel_flatten_spec(spec)
+    for v, what, lo in ((min_n, "min_n", 1), (min_rows, "min_rows", -2 ** 63)):
+        if isinstance(v, bool) or int(v) != v or not lo <= v < 2 ** 63:
+            raise ValueError("%s must be an integer >= %d, got %r" % (what, lo, v))
+    if isinstance(since, bool) or int(since) != since or not -2 ** 31 <= since < 2 ** 31:
+        raise ValueError("since must be a 32-bit integer, got %r" % (since,))
+    shapes = {"logodds": ((rows, cols), torch.int16), "last_seen": ((rows, cols), torch.int32), "floor": ((rows, cols), torch.int32), "top": ((rows, cols), torch.int32),
+              "cells": ((rows, cols, 3), torch.int32), "stats": ((8,), torch.int64)}
+    if out is not None and not isinstance(out, VoxelFlattenResult):
+        raise ValueError("out must be a VoxelFlattenResult")
+    res = VoxelFlattenResult()
+    for k in VoxelFlattenResult.__slots__:
+        shape, dtype = shapes[k]
+        t = None if out is None else getattr(out, k)
+        if t is None:
+            t = torch.empty(shape, dtype=dtype, device=dev)
+        elif not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous()):
+            raise ValueError("out: %s must be a contiguous %s tensor %s on the voxel map's device" % (k, str(dtype).replace("torch.", ""), list(shape)))
+        setattr(res, k, t)
+    flat = _occupancy_map_struct(words)
+    with torch.cuda.device(dev):
+        rc = voxel_flatten_lib().sv_voxel_flatten_device(buf.data_ptr(), nbytes, ctypes.byref(vspec), ctypes.byref(flat), ctypes.byref(fspec), int(min_n), int(min_rows),
+                                                         int(since), res.logodds.data_ptr(), res.last_seen.data_ptr(), res.floor.data_ptr(), res.top.data_ptr(),
+                                                         res.cells.data_ptr(), res.stats.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    _check(rc, "sv_voxel_flatten_device")
+    return res
+
+
+def debug_voxel_flatten(groups=0, stages=0):
+    """sv_debug_voxel_flatten: the workgroups of voxel_map_flatten's two table walks at most (0: the call chooses; 1 .. 2048) and the
+    kernels a call enqueues (0: all; 1 .. 4: the first that many of clear, walk A, floor, walk B).  Returns the groups before.
+    Process-wide; a test and measurement hook."""
+    return int(voxel_flatten_lib().sv_debug_voxel_flatten(int(groups), int(stages)))
 
 
 def host_support_filter(params, dcan, width, height, threads=0, lattice=False):

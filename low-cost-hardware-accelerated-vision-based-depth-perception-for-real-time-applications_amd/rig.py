@@ -449,7 +449,9 @@ class VoxelMap:
     swapped with the map's from then on: they double the memory the map takes and allocate once, not per call.  carve() is group (T),
     stereo_vision.sv.voxel_map_carve: the voxels that the sight lines of later frames pass through are emptied, and keep their slots until
     the next prune().  render() is group (U), stereo_vision.sv.voxel_map_render: what a camera should see of the map from given poses -
-    depth, colour and expected disparity per pixel - and, against a measured disparity, what is new and what was seen through."""
+    depth, colour and expected disparity per pixel - and, against a measured disparity, what is new and what was seen through.
+    flatten() is group (V), stereo_vision.sv.voxel_map_flatten: the voxels sliced by height above the floor and written out as the
+    logodds and last_seen of a flat map, which OccupancyMap.load_voxels takes."""
 
     def __init__(self, lo, hi, size, capacity, device="cuda"):
         import torch
@@ -673,6 +675,24 @@ class VoxelMap:
         res = _sv.voxel_map_render(self._state, cams, camera, m, tol, near, far, r_max, min_n, min_rows, since)
         return VoxelRenderResult(**{k: None if v is None else torch.from_numpy(v) for k, v in res.items()})
 
+    def flatten(self, flat_map, z_ref=None, step=0.2, height=2.0, radius=2, min_obstacle=1, min_ground=1, min_n=1, min_rows=1, since=0, out=None):
+        """The map sliced by height and written out in a flat map's layout (include/stereo_vision_hip.h (V),
+        stereo_vision.sv.voxel_map_flatten): flat_map an OccupancyMap or the dict of a flat map's words
+        (stereo_vision.sv.occupancy_map_params); z_ref the height of the floor in the world, metres, or None for the local floor - per
+        flat cell the lowest voxel within `radius` cells; a voxel less than `step` metres from the floor is ground, one below `height`
+        metres an obstacle, one above it overhead - a bridge, a crown - and no obstacle; a cell is occupied from min_obstacle obstacle
+        voxels on, else free from min_ground ground voxels on, else unknown; min_n >= 1, min_rows, since: rows()' filters.  out: an
+        engine.VoxelFlattenResult to write into.  -> engine.VoxelFlattenResult - logodds, last_seen, floor, top, cells, stats - of
+        tensors on the map's device.  The map is not changed; not waited for.  OccupancyMap.load_voxels puts the result into a flat map."""
+        import torch
+        from .engine import VoxelFlattenResult, voxel_map_flatten
+        words = flat_map.words if isinstance(flat_map, OccupancyMap) else flat_map
+        spec = _sv.voxel_flatten_params(self.params, z_ref, step, height, radius, min_obstacle, min_ground)
+        if self._state is None:
+            return voxel_map_flatten(self.buffer, self.params, words, spec, min_n, min_rows, since, out=out)
+        res = _sv.voxel_map_flatten(self._state, words, spec, min_n, min_rows, since)
+        return VoxelFlattenResult(**{k: torch.from_numpy(v) for k, v in res.items()})
+
     def write_ply(self, path, min_n=1, min_rows=1, since=0):
         """rows(...) as a binary PLY of coloured points (stereo_vision.sv.write_ply); -> the number of points.  RuntimeError for an
         overflowed map."""
@@ -695,7 +715,9 @@ class OccupancyMap:
     frontiers() and frontier_goals() are group (O): the free cells that touch undecided space, their clusters and one goal per cluster -
     the loop clearance -> cost_to_goal(any goal) or cost_cells -> frontiers -> cost_to_goal(frontier_goals) -> routes(vehicle).
     view() and frontier_views() are group (P): the distinct cells the vehicle would see from candidate poses, and with them a heading and a
-    worth per frontier - frontiers -> frontier_views -> cost_to_goal(the goals worth the trip) -> routes."""
+    worth per frontier - frontiers -> frontier_views -> cost_to_goal(the goals worth the trip) -> routes.
+    load_voxels() is group (V), stereo_vision.sv.voxel_map_flatten: the map's words replaced by a VoxelMap's evidence, sliced by height,
+    so that the planner runs on the voxel map - vm.update -> vm.carve -> om.load_voxels(vm) -> clearance -> cost_to_goal -> routes."""
 
     def __init__(self, x_range, y_range, scale, device="cuda", **log_odds_words):
         import torch
@@ -711,6 +733,7 @@ class OccupancyMap:
         self._pen, self._cost, self._cost_workspace = None, None, None  # cost_to_goal()'s, made on its first call
         self._frontier_mask, self._frontiers = None, None  # frontiers()'s, made on its first call
         self._view = None  # view()'s result and workspace, made on its first call
+        self._flatten = None  # load_voxels()'s result, made on its first call
 
     def reset(self):
         """A fresh map at the place it has scrolled to: logodds 0, last_seen -1, seq 0."""
@@ -795,6 +818,31 @@ class OccupancyMap:
             self._fuse(empty, np.zeros((0, 4)), dict(x_range=(0, 1), y_range=(0, 1), scale=1), shift)
             self.words = dict(self.words, top=self.words["top"] - shift[0], left=self.words["left"] - shift[1])
         return shift
+
+    def load_voxels(self, voxel_map, **flatten):
+        """Replaces the map's logodds and last_seen by a VoxelMap's, flattened at the map's current top and left (VoxelMap.flatten, whose
+        keywords - z_ref, step, height, radius, min_obstacle, min_ground, min_n, min_rows, since - are taken here): the evidence is the
+        voxel map's, nothing of the map's own is blended in.  seq becomes one past the largest last_seen, 0 for an empty result, and the
+        results of clearance(), cost_to_goal(), frontiers() and view() that the map holds are dropped:
+        `om.load_voxels(vm); om.clearance(...); om.cost_to_goal(...)` is the idiom.  -> the engine.VoxelFlattenResult, whose logodds and
+        last_seen are the map's own tensors; floor, top, cells and stats stay with the map and are written again by the next call.  Waits
+        for one word, the largest last_seen."""
+        from .engine import VoxelFlattenResult
+        if not isinstance(voxel_map, VoxelMap) or voxel_map.device != self.device:
+            raise ValueError("load_voxels: a VoxelMap on the map's device (%s) is needed" % (self.device,))
+        if self.device.type == "cuda":
+            old = self._flatten
+            out = VoxelFlattenResult(logodds=self.logodds, last_seen=self.last_seen, **({} if old is None else {k: getattr(old, k) for k in ("floor", "top", "cells", "stats")}))
+            res = voxel_map.flatten(self.words, out=out, **flatten)
+        else:
+            res = voxel_map.flatten(self.words, **flatten)
+            self.logodds.copy_(res.logodds)
+            self.last_seen.copy_(res.last_seen)
+            res.logodds, res.last_seen = self.logodds, self.last_seen
+        self._flatten = res
+        self.seq = int(self.last_seen.max()) + 1  # -1 everywhere: 0
+        self._d2, self.clearance_radius, self._pen, self._cost, self._frontier_mask, self._frontiers, self._view = None, None, None, None, None, None, None
+        return res
 
     def clearance(self, radius_m, occupied=None, unknown=False):
         """The clearance field of the map as it stands (stereo_vision.sv.occupancy_clearance): uint16 [rows,cols] on the map's device, per

@@ -114,6 +114,13 @@ map rendered into a camera (sv_voxel_render_device of include/stereo_vision_hip.
 the GPU): per view the nearest voxel under every pixel - its depth, key and colour -, the disparity the rig would measure there, and its
 comparison with the disparity it did measure, pixel by pixel: nearer means something new, farther a voxel that was seen through.  The
 3-D counterpart of occupancy_view.  The reference has no counterpart.
+
+voxel_map_flatten (with voxel_map_flatten_brute, the plain loops, voxel_flatten_params and voxel_flatten_words) is the definition of the
+voxel map flattened into an occupancy map (sv_voxel_flatten_device of include/stereo_vision_hip.h (V); engine.voxel_map_flatten /
+rig.VoxelMap.flatten / rig.OccupancyMap.load_voxels on the GPU): the voxels sliced by their height above an absolute or a local floor into
+ground, obstacle and overhead, and per flat cell the log-odds and last_seen words that occupancy_clearance, cost_to_goal, frontier_cells
+and occupancy_view take - a bridge overhead is no obstacle, a kerb below the step is ground.  The reference has no counterpart (DESIGN.md
+§8).
 """
 import argparse
 import ctypes
@@ -1142,6 +1149,203 @@ def voxel_map_render_brute(map_state, cams, camera, measured=None, tol=1.0, near
                     lab = (4 if d - e > tol else 5 if d - e < -tol else 3) if valid and has else (1 if valid else 0) + (2 if has else 0)
                     out["label"][v, y, x] = lab
                     out["counts"][v, lab] += 1
+    return out
+
+
+VOXEL_FLATTEN_WORDS = ("mode", "z_ref_q", "step_q", "height_q", "radius", "min_obstacle", "min_ground")  # sv_voxel_flatten_spec, in its order
+VOXEL_FLATTEN_STATS = ("drawn", "outside", "below", "ground", "obstacle", "overhead", "occupied_cells", "free_cells")  # voxel_map_flatten's stats
+VOXEL_FLATTEN_RADIUS_MAX = 8        # flat cells: the window of the local floor is at most 17 x 17
+VOXEL_FLATTEN_CELLS_MAX = 8000000   # rows * cols of the flat map at most: what cost_to_goal and the frontiers take
+VOXEL_FLATTEN_ZQ_MAX = 2 ** 28      # a voxel's zq stays below it; step_q < height_q < it
+VOXEL_FLATTEN_REF_MAX = 2 ** 30     # |z_ref_q| stays below it, so zq - z_ref_q is an int32
+_VOXEL_FLATTEN_NONE = 2 ** 31 - 1   # the minimum over no voxel
+
+
+def voxel_flatten_words(spec):
+    """The words of sv_voxel_flatten_spec as a dict of ints - mode, z_ref_q, step_q, height_q, radius, min_obstacle, min_ground - from a
+    dict of them (voxel_flatten_params'; a "reserved" entry must hold zeros only), after the checks the C entry makes (ValueError): mode 0
+    or 1, |z_ref_q| < 2^30, 1 <= step_q < height_q < 2^28, radius in 0 .. 8, min_obstacle and min_ground in 1 .. 2^31 - 1."""
+    w = {}
+    for k in VOXEL_FLATTEN_WORDS:
+        v = spec.get(k) if isinstance(spec, dict) else getattr(spec, k, None)
+        w[k] = _whole(v, k + " of the flatten spec")
+    reserved = spec.get("reserved", ()) if isinstance(spec, dict) else getattr(spec, "reserved", ())
+    if any(int(v) != 0 for v in reserved):
+        raise ValueError("a reserved word of the flatten spec is not 0: %r" % (list(reserved),))
+    if w["mode"] not in (0, 1):
+        raise ValueError("mode must be 0 (an absolute floor) or 1 (a local floor), got %d" % w["mode"])
+    if abs(w["z_ref_q"]) >= VOXEL_FLATTEN_REF_MAX:
+        raise ValueError("|z_ref_q| must stay below 2^30, got %d" % w["z_ref_q"])
+    if not 1 <= w["step_q"] < w["height_q"] < VOXEL_FLATTEN_ZQ_MAX:
+        raise ValueError("1 <= step_q < height_q < 2^28 must hold, got %d and %d" % (w["step_q"], w["height_q"]))
+    if not 0 <= w["radius"] <= VOXEL_FLATTEN_RADIUS_MAX:
+        raise ValueError("radius must lie in 0 .. 8 flat cells, got %d" % w["radius"])
+    if not (1 <= w["min_obstacle"] < 2 ** 31 and 1 <= w["min_ground"] < 2 ** 31):
+        raise ValueError("min_obstacle and min_ground must lie in 1 .. 2^31 - 1, got %d and %d" % (w["min_obstacle"], w["min_ground"]))
+    return w
+
+
+def voxel_flatten_params(voxel_params, z_ref=None, step=0.2, height=2.0, radius=2, min_obstacle=1, min_ground=1):
+    """The words of a flatten (sv_voxel_flatten_spec) as a dict, from metres: voxel_params the voxel map's (its lo[2] and size), z_ref the
+    height of an absolute floor in the world (mode 0; z_ref_q = floor((z_ref - lo_z) / size * 256), in zq units: 1 / 256 of a voxel cell
+    above lo_z) or None for the local floor (mode 1, z_ref_q = 0: the lowest voxel within `radius` flat cells); step: what is still
+    ground above and below the floor, height: from where on a voxel is overhead, both in metres, step_q and height_q = round(metres / size
+    * 256); a cell is occupied from min_obstacle obstacle voxels on, else free from min_ground ground voxels on.  ValueError for a z_ref,
+    step or height that is not finite and for what voxel_flatten_words refuses (step >= height, radius outside 0 .. 8, ...)."""
+    lo_z, size = float(voxel_params["lo"][2]), float(voxel_params["size"])
+    try:
+        words = [float(step), float(height)] + ([] if z_ref is None else [float(z_ref)])
+    except (TypeError, ValueError):
+        raise ValueError("z_ref, step and height must be numbers, got %r, %r, %r" % (z_ref, step, height))
+    if not (all(np.isfinite(v) for v in words) and np.isfinite(size) and size > 0 and np.isfinite(lo_z)):
+        raise ValueError("z_ref, step and height must be finite and the voxel size > 0, got %r, %r, %r and %r" % (z_ref, step, height, size))
+    q = [v / size * 256.0 for v in words]
+    if any(abs(v) >= 2.0 ** 40 for v in q):
+        raise ValueError("z_ref, step or height is too many voxel cells of %r m: %r, %r, %r" % (size, z_ref, step, height))
+    ref_q = 0 if z_ref is None else int(np.floor((words[2] - lo_z) / size * 256.0))
+    return voxel_flatten_words(dict(mode=0 if z_ref is not None else 1, z_ref_q=ref_q, step_q=int(round(q[0])), height_q=int(round(q[1])), radius=radius,
+                                    min_obstacle=min_obstacle, min_ground=min_ground))
+
+
+def _voxel_flatten_setup(map_state, flat_map, spec, min_n, min_rows, since):
+    """What voxel_map_flatten and voxel_map_flatten_brute share: the checked words, the indices of the voxels that take part (none for an
+    overflowed map) and the outputs of a map without any."""
+    w, s = occupancy_map_words(flat_map), voxel_flatten_words(spec)
+    if w["rows"] * w["cols"] > VOXEL_FLATTEN_CELLS_MAX:
+        raise ValueError("a flat map of %d x %d cells: at most 8 000 000" % (w["rows"], w["cols"]))
+    if isinstance(min_n, bool) or int(min_n) != min_n or min_n < 1:
+        raise ValueError("min_n must be an integer >= 1 - a carved voxel has n = 0 and divides -, got %r" % (min_n,))
+    shape = (w["rows"], w["cols"])
+    out = {"logodds": np.zeros(shape, np.int16), "last_seen": np.full(shape, -1, np.int32), "floor": np.full(shape, s["z_ref_q"] if s["mode"] == 0 else -1, np.int32),
+           "top": np.full(shape, -1, np.int32), "cells": np.zeros(shape + (3,), np.int32), "stats": np.zeros(8, np.int64)}
+    if map_state["overflowed"]:
+        out["stats"][0] = -1
+        sel = np.zeros(0, np.int64)
+    else:
+        sel = np.flatnonzero((map_state["n"] >= min_n) & (map_state["m"] >= min_rows) & (map_state["last_seq"] >= since))
+    return w, s, sel, out
+
+
+def voxel_map_flatten(map_state, flat_map, spec, min_n=1, min_rows=1, since=0):
+    """A voxel map sliced by height above the floor and written out in the flat map's layout, the definition of
+    include/stereo_vision_hip.h (V) in numpy: what occupancy_clearance, cost_to_goal, frontier_cells and occupancy_view take.  The voxel
+    map is only read.
+
+    flat_map: occupancy_map_params' dict (or an object with its nine words), rows * cols <= 8 000 000; spec: voxel_flatten_params' dict;
+    min_n >= 1, min_rows, since: voxel_map_rows' filters.  A voxel that passes them has X, Y = its centre on axes 0 and 1, lo + (c + (S +
+    0.5 n) / (65536 n)) * size in double as written (voxel_map_rows' xyz), gx = floor(X ms), gy = floor(Y ms) with ms = float(scale), the
+    flat cell (top - 1 - gx, left - 1 - gy) (occupancy_cells_of's rule: compared in double first; a voxel outside the flat map counts into
+    `outside` and does nothing else) and the height zq = cz * 256 + ((S_z // n) >> 8), an integer < 2^28.  Behind that everything is an
+    integer.  Per cell low = the least zq and seen = the largest last_seq of its voxels.  The floor: base = z_ref_q everywhere (mode 0),
+    or per cell the least low over the cells within `radius` rows and columns of it that lie inside the map and hold a voxel (mode 1: a
+    wall's own column has no ground voxel under it, its neighbours have).  A voxel with h = zq - base of its cell is below for h <
+    -step_q (counted, and ignored in its cell; mode 0 only), ground for h < step_q, an obstacle for h < height_q and overhead from there
+    on.  A cell with obstacle >= min_obstacle voxels gets L = min(l_max, obstacle * l_occ), else one with ground >= min_ground gets L =
+    max(l_min, -(ground * l_free)), both with last_seen = seen; every other cell - one that holds overhead voxels only, too - L = 0 and
+    last_seen = -1: unknown.
+
+    Returns a dict: logodds int16 and last_seen int32 [rows,cols]; floor int32 [rows,cols] = base (mode 1: -1 where the window holds no
+    voxel); top int32 [rows,cols] = the largest zq of the cell's ground and obstacle voxels, -1 without one; cells int32 [rows,cols,3] =
+    ground, obstacle, overhead voxels; stats int64 [8] = drawn (the voxels that took part and fell inside), outside, below, ground,
+    obstacle, overhead, occupied_cells, free_cells (VOXEL_FLATTEN_STATS).  An overflowed map: drawn = -1 and the outputs of a map without
+    voxels."""
+    w, s, sel, out = _voxel_flatten_setup(map_state, flat_map, spec, min_n, min_rows, since)
+    rows, cols, R = w["rows"], w["cols"], s["radius"]
+    p = map_state["params"]
+    size, ms = np.float64(p["size"]), np.float64(w["scale"])
+    key, n, S, last = map_state["key"][sel], map_state["n"][sel], map_state["S"][sel], map_state["last_seq"][sel]
+    nf = n.astype(np.float64)
+    g = []
+    for k in range(2):
+        c = ((key >> (20 * k)) & 0xFFFFF).astype(np.float64)
+        g.append(np.floor((np.float64(p["lo"][k]) + (c + (S[:, k].astype(np.float64) + 0.5 * nf) / (65536.0 * nf)) * size) * ms))
+    inside = (g[0] >= w["top"] - rows) & (g[0] <= w["top"] - 1) & (g[1] >= w["left"] - cols) & (g[1] <= w["left"] - 1)
+    if not map_state["overflowed"]:
+        out["stats"][:2] = int(inside.sum()), int((~inside).sum())
+    cell = (w["top"] - 1 - g[0][inside].astype(np.int64)) * cols + (w["left"] - 1 - g[1][inside].astype(np.int64))
+    zq = ((key[inside] >> 40) & 0xFFFFF) * 256 + ((S[inside, 2] // n[inside]) >> 8)
+    low, seen = np.full(rows * cols, _VOXEL_FLATTEN_NONE, np.int64), np.full(rows * cols, -1, np.int64)
+    np.minimum.at(low, cell, zq)
+    np.maximum.at(seen, cell, last[inside])
+    if s["mode"] == 0:
+        base = np.full(rows * cols, s["z_ref_q"], np.int64)
+    else:
+        padded = np.full((rows + 2 * R, cols + 2 * R), _VOXEL_FLATTEN_NONE, np.int64)
+        padded[R:R + rows, R:R + cols] = low.reshape(rows, cols)
+        base = np.min([padded[dr:dr + rows, dc:dc + cols] for dr in range(2 * R + 1) for dc in range(2 * R + 1)], axis=0).reshape(-1)
+        out["floor"][...] = np.where(base == _VOXEL_FLATTEN_NONE, -1, base).reshape(rows, cols)
+    h = zq - base[cell]
+    kind = np.where(h < -s["step_q"], 0, np.where(h < s["step_q"], 1, np.where(h < s["height_q"], 2, 3)))  # below, ground, obstacle, overhead
+    counts = np.zeros((rows * cols, 3), np.int64)
+    np.add.at(counts, (cell[kind > 0], kind[kind > 0] - 1), 1)
+    top = np.full(rows * cols, -1, np.int64)
+    solid = (kind == 1) | (kind == 2)
+    np.maximum.at(top, cell[solid], zq[solid])
+    occupied = counts[:, 1] >= s["min_obstacle"]
+    free = ~occupied & (counts[:, 0] >= s["min_ground"])
+    L = np.where(occupied, np.minimum(w["l_max"], counts[:, 1] * w["l_occ"]), np.where(free, np.maximum(w["l_min"], -(counts[:, 0] * w["l_free"])), 0))
+    out["logodds"][...] = L.astype(np.int16).reshape(rows, cols)
+    out["last_seen"][...] = np.where(occupied | free, seen, -1).astype(np.int32).reshape(rows, cols)
+    out["top"][...], out["cells"][...] = top.reshape(rows, cols), counts.reshape(rows, cols, 3)
+    out["stats"][2:] = [int((kind == k).sum()) for k in range(4)] + [int(occupied.sum()), int(free.sum())]
+    return out
+
+
+def voxel_map_flatten_brute(map_state, flat_map, spec, min_n=1, min_rows=1, since=0):
+    """voxel_map_flatten's definition as plain loops over voxels and cells on Python floats and ints: the form the vectorised one is
+    checked against.  Same arguments, same dict.  The local floor is spread from every cell that holds a voxel to the cells of its window
+    - the window is symmetric, so that is the minimum each cell takes over its own."""
+    import math
+    w, s, sel, out = _voxel_flatten_setup(map_state, flat_map, spec, min_n, min_rows, since)
+    rows, cols, R = w["rows"], w["cols"], s["radius"]
+    p = map_state["params"]
+    lo, size, ms = [float(x) for x in p["lo"]], float(p["size"]), float(w["scale"])
+    voxels = {}  # (r, c) -> [(zq, last_seq), ...]
+    for i in sel:
+        key, n = int(map_state["key"][i]), int(map_state["n"][i])
+        X, Y = (lo[k] + (float((key >> (20 * k)) & 0xFFFFF) + (float(int(map_state["S"][i, k])) + 0.5 * float(n)) / (65536.0 * float(n))) * size for k in range(2))
+        gx, gy = math.floor(X * ms), math.floor(Y * ms)
+        if not (w["top"] - rows <= gx <= w["top"] - 1 and w["left"] - cols <= gy <= w["left"] - 1):
+            out["stats"][1] += 1
+            continue
+        out["stats"][0] += 1
+        zq = ((key >> 40) & 0xFFFFF) * 256 + ((int(map_state["S"][i, 2]) // n) >> 8)
+        voxels.setdefault((w["top"] - 1 - gx, w["left"] - 1 - gy), []).append((zq, int(map_state["last_seq"][i])))
+    base = {}
+    if s["mode"] == 1:
+        for (r, c), held in voxels.items():
+            low = min(zq for zq, _ in held)
+            for rr in range(max(r - R, 0), min(r + R, rows - 1) + 1):
+                for cc in range(max(c - R, 0), min(c + R, cols - 1) + 1):
+                    base[rr, cc] = min(base.get((rr, cc), low), low)
+        for (r, c), b in base.items():
+            out["floor"][r, c] = b
+    for (r, c), held in voxels.items():
+        b = s["z_ref_q"] if s["mode"] == 0 else base[r, c]
+        ground = obstacle = overhead = 0
+        top = -1
+        for zq, _ in held:
+            h = zq - b
+            if h < -s["step_q"]:
+                out["stats"][2] += 1
+                continue
+            if h < s["step_q"]:
+                ground += 1
+            elif h < s["height_q"]:
+                obstacle += 1
+            else:
+                overhead += 1
+                continue
+            top = max(top, zq)
+        out["cells"][r, c], out["top"][r, c] = (ground, obstacle, overhead), top
+        out["stats"][3:6] += (ground, obstacle, overhead)
+        if obstacle >= s["min_obstacle"]:
+            out["logodds"][r, c], out["stats"][6] = min(w["l_max"], obstacle * w["l_occ"]), out["stats"][6] + 1
+        elif ground >= s["min_ground"]:
+            out["logodds"][r, c], out["stats"][7] = max(w["l_min"], -(ground * w["l_free"])), out["stats"][7] + 1
+        else:
+            continue
+        out["last_seen"][r, c] = max(seq for _, seq in held)
     return out
 
 
@@ -2808,6 +3012,14 @@ def main(argv=None):
                              "poses and compare the expected disparity with the batch's measured one at TOL_PX pixels (default 1); "
                              "writes per frame DIR/NNNNNN.expected.png (the model's colours) and DIR/NNNNNN.change.png (none, measured "
                              "only, expected only, agree, nearer = new, farther = seen through) and prints the pixels per label")
+    parser.add_argument("--voxel-flatten", type=str, default="", metavar="X0,X1,Y0,Y1,SCALE[,STEP_M[,HEIGHT_M]]",
+                        help="with --voxel-map: at the end of the run, flatten the voxel map into a flat map over X0 .. X1 by Y0 .. Y1 metres "
+                             "(whole numbers; write --voxel-flatten=-5,45,... for a negative X0) at SCALE cells per metre - a voxel less than STEP_M (default 0.2) from the lowest voxel "
+                             "within 2 cells is ground, one below HEIGHT_M (default 2) an obstacle, one above it overhead and no obstacle - "
+                             "and write logodds, last_seen, floor, top and the map's words (map_top, map_left, ...: `top` is a plane here) to "
+                             "<FILE without extension>.flat.npz; with "
+                             "--clearance and --goal also the clearance field of that map (.flat.clearance.png) and the route from where "
+                             "the drive ended (.flat.route.txt)")
     parser.add_argument("--voxel-match", type=str, default="", metavar="DX,DY,DZ,DYAW[,NX,NY,NZ,NYAW]",
                         help="with --voxel-map: take the poses as guesses at height 0 - frame 0 is inserted where its line says; every later "
                              "frame's voxel cloud is first matched against the voxel map built so far over a window of +-DX, +-DY, +-DZ metres "
@@ -2921,6 +3133,14 @@ def main(argv=None):
             args.voxel_carve_spec = cli_voxel_carve_spec(float(words[0]), int(words[1]) if len(words) > 1 else 2, int(words[2]) if len(words) > 2 else 0, args.voxel)
         except ValueError as e:
             parser.error("--voxel-carve: %s" % e)
+    args.voxel_flatten_spec = None
+    if args.voxel_flatten:
+        if not args.voxel_map:
+            parser.error("--voxel-flatten needs --voxel-map")
+        try:
+            args.voxel_flatten_spec = cli_voxel_flatten_spec(args.voxel_flatten, args.voxel)
+        except ValueError as e:
+            parser.error("--voxel-flatten: %s" % e)
     args.voxel_render_spec = None
     if args.voxel_render:
         if not args.voxel_map:
@@ -3102,6 +3322,29 @@ def cli_voxel_render_spec(text):
     return words[0], tol
 
 
+def cli_voxel_flatten_spec(text, size):
+    """((x0, x1), (y0, y1), scale, step_m, height_m) of --voxel-flatten's X0,X1,Y0,Y1,SCALE[,STEP_M[,HEIGHT_M]] for voxels of `size` metres,
+    after occupancy_map_params' and voxel_flatten_params' checks: ValueError with the text the CLI prints."""
+    words = text.split(",")
+    if not 5 <= len(words) <= 7:
+        raise ValueError("X0,X1,Y0,Y1,SCALE[,STEP_M[,HEIGHT_M]], got %r" % (text,))
+    try:
+        x0, x1, y0, y1, scale = (int(w) for w in words[:5])
+        step, height = [float(w) for w in words[5:]] + [0.2, 2.0][len(words) - 5:]
+    except ValueError:
+        raise ValueError("X0, X1, Y0, Y1 and SCALE must be whole numbers, STEP_M and HEIGHT_M numbers, got %r" % (text,))
+    flat = occupancy_map_params((x0, x1), (y0, y1), scale)
+    if flat["rows"] * flat["cols"] > VOXEL_FLATTEN_CELLS_MAX:
+        raise ValueError("a flat map of %d x %d cells: at most 8 000 000" % (flat["rows"], flat["cols"]))
+    voxel_flatten_params(dict(lo=(0.0, 0.0, 0.0), size=size), None, step, height)
+    return (x0, x1), (y0, y1), scale, step, height
+
+
+def cli_voxel_flatten_text(stats):
+    """voxel_map_flatten's eight counts as the CLI prints them."""
+    return ", ".join("%s %d" % (k.replace("_", " "), int(v)) for k, v in zip(VOXEL_FLATTEN_STATS, stats))
+
+
 def cli_voxel_render_text(counts):
     """The pixels per label of one view (six integers) as the CLI prints them."""
     return ", ".join("%s %d" % (k, int(v)) for k, v in zip(VOXEL_RENDER_LABELS, counts))
@@ -3207,6 +3450,22 @@ def _run_batched(args, ldir, rdir, files):
             if args.voxel_match_window is not None:
                 with open(os.path.splitext(args.voxel_map)[0] + ".poses.txt", "w") as f:
                     f.write("".join("%r %r %r %r\n" % tuple(float(v) for v in to) for to in refined_3d))
+            if args.voxel_flatten_spec is not None:  # the planner's map from the voxel map's evidence
+                x_range, y_range, scale, step, height = args.voxel_flatten_spec
+                stem = os.path.splitext(args.voxel_map)[0] + ".flat"
+                flat = rig.occupancy_map(x_range, y_range, scale)
+                res = flat.load_voxels(model, step=step, height=height)
+                np.savez(stem + ".npz", **dict({k: getattr(res, k).cpu().numpy() for k in ("logodds", "last_seen", "floor", "top")}, **{"map_" + k: v for k, v in flat.words.items()}))
+                print("voxel map flattened into %d x %d cells, written to %s: %s" % (flat.words["rows"], flat.words["cols"], stem + ".npz", cli_voxel_flatten_text(res.stats.cpu().numpy())))
+                if args.clearance and np.ceil(args.clearance * scale) <= CLEARANCE_RADIUS_MAX:
+                    _write_png(stem + ".clearance.png", clearance_png(flat.clearance(args.clearance).cpu().numpy()))
+                    if args.goal_xy is not None:
+                        field = flat.cost_to_goal(args.goal_xy, args.clearance)
+                        route, xy = flat.routes(refined[-1][:2] if refined else args.pose_rows[-1, :2])
+                        length = int(route.length[0])
+                        with open(stem + ".route.txt", "w") as f:
+                            f.write("".join("%d %d %r %r\n" % (r, c, float(x), float(y)) for (r, c), (x, y) in zip(route.cells[0, :length].cpu().numpy(), xy[0, :length])))
+                        print("route on the flattened map: status %d, %d cells%s" % (int(route.status[0]), length, "" if field.converged else " (field not converged)"))
         if world is not None:
             _write_png(args.occupancy_map, OCCUPANCY_PNG[world.state().cpu().numpy()])
             if args.clearance:
