@@ -79,6 +79,11 @@
  *      above an absolute or a local floor into ground, obstacle and overhead, and per flat cell the logodds and last_seen words that (M)
  *      to (P) take, so that the planner runs on the voxel map.  stereo_vision.sv.voxel_map_flatten states the definition in numpy.
  *
+ *  (W) Behind (V): the voxel map clustered (sv_voxel_clusters_device) - the 6-, 18- or 26-connected components of the voxels of (Q)'s
+ *      table inside a height band, over an absolute floor or over (V)'s: a row of counts, sums and a box per component, a label per slot,
+ *      and the components below a size emptied - the objects of the map and its speckle filter.  stereo_vision.sv.voxel_map_clusters
+ *      states the definition in numpy.
+ *
  * All sv_* functions return SV_OK (0) or a negative sv_status; sv_last_error() gives the text.
  * Nothing in this library calls exit().
  */
@@ -1523,6 +1528,77 @@ int sv_voxel_flatten_device(const void *map, size_t map_bytes, const sv_voxel_ma
  * a call enqueues (0: all; 1 .. 4: the first that many of clear, walk A, floor, walk B - the floor counts where it is skipped, too -, which
  * leaves the outputs unfinished).  A value outside its range leaves that word as it was.  Returns the groups before. */
 int sv_debug_voxel_flatten(int groups, int stages);
+
+/* ---- (W) the voxel map clustered: (Q)'s table + a height band + a neighbourhood -> a row per connected component, a label per slot ---- */
+
+/* Which voxels of (Q)'s map belong to one thing.  Integers throughout, but for the flat cell of mode 1, which is (V)'s: doubles, every
+ * product, sum and quotient rounded on its own, in the order written.  The result is bit-exact against
+ * stereo_vision.sv.voxel_map_clusters, which restates this in numpy, whatever the schedule and wherever the inserts left an entry.
+ *
+ *   members    the slots whose key is a voxel's, whose entry has n >= min_n, m >= min_rows and last_seq >= since - (Q)'s filters; min_n
+ *              >= 1, so a tombstone of (T) or of this group, whose n is 0, is never one - and whose height lies in the band: h_lo_q <=
+ *              zq - base < h_hi_q with zq = cz * 256 + ((S_z / n) >> 8), (V)'s, in 1/256 of a voxel cell.  mode 0: base = z_ref_q.  mode
+ *              1: base = floor[cell], `floor` (V)'s plane of the flat map `flat` and `cell` the flat cell under the voxel's centre on
+ *              axes 0 and 1, exactly (V)'s; a voxel outside the flat map or over a cell with floor = -1 is no member.  With h_lo_q =
+ *              step_q, h_hi_q = height_q and (V)'s filters the members are (V)'s obstacle voxels.
+ *   neighbours connectivity 6, 18 or 26: two cells that differ by at most 1 on every axis, on 1, up to 2 or up to 3 axes.  A cell outside
+ *              0 .. cells[k] - 1 on an axis does not exist: the cells are tested per axis, never the keys.
+ *   component  the transitive closure over pairs of members in neighbouring cells.  Its identity is the least KEY of its members -
+ *              never a slot, which depends on the schedule of the inserts.
+ *   row        int64 [16] per component with voxels >= min_voxels: 0 the least key; 1 voxels; 2 the sum of n; 3-5 the least and 6-8 the
+ *              largest cell per axis; 9-11 the sum over the members of c_k * 256 + ((S_k / n) >> 8), axes 0 to 2; 12 the least first_seq;
+ *              13 the largest last_seq; 14 the sum of m; 15 zero.
+ *   capacity   THE CHOICE FOR CUT ROWS.  This entry writes the rows of the first min(kept, capacity) kept components in the order of their
+ *              roots' slots - an order that follows the inserts' schedule; the rows behind them are zero.  Which components are cut when
+ *              kept > capacity is therefore unspecified HERE.  The definition - the numpy form, and engine.voxel_map_clusters with
+ *              sort=True - is "the rows in ascending least key, cut to `capacity`": the engine calls this entry with a row workspace of
+ *              min(65535, the map's capacity) rows, sorts what came back by least key and cuts behind the sort, so the rows are the
+ *              `capacity` least keys whenever the map holds at most 65535 kept components.  sort=False hands out this entry's order.
+ *   info       int64 [8]: 0 members; 1 components; 2 kept components (voxels >= min_voxels, cut or not); 3 the voxels in components below
+ *              min_voxels; 4 the voxels emptied; 5 the voxels of the largest component; 6, 7 zero.
+ *   label      int32 per slot: -1 no member; -2 a member of a component below min_voxels; -3 a member of a kept component that got no
+ *              row; >= 0 the component's row.
+ *   drop       1: every member of a component below min_voxels is emptied as (T)'s apply empties: n = S = C = m = 0, the sequence word of
+ *              a fresh slot, the key stays - a tombstone.  `claimed` does not change; the next carry into an empty map frees the slots.
+ *              0: the map is only read.
+ * An overflowed map: nothing is done to it, info[0] = -1, the other words and the rows 0, every label -1.
+ *
+ * Enqueues eight kernels on `stream` (a hipStream_t, NULL = the default stream) - init, link (a lock-free union-find over the slots:
+ * relaxed agent-scope fetch_min only, no flag, no grid barrier, no cooperative launch), roots, count, scan, rank, stats, resolve - and
+ * does not wait: nothing is allocated and no host synchronisation is made.  No other call on the map may run at the same time. */
+typedef struct {
+    int32_t connectivity;  /* 6, 18 or 26 */
+    int32_t mode;          /* 0: base = z_ref_q; 1: base = floor[cell] */
+    int32_t z_ref_q;       /* mode 0: |.| <= 2^30.  Not read in mode 1 */
+    int32_t h_lo_q, h_hi_q; /* -2^30 <= h_lo_q < h_hi_q <= 2^30 */
+    int32_t min_voxels;    /* >= 1 */
+    int32_t capacity;      /* rows: 1 .. 65535 */
+    int32_t drop;          /* 0 or 1 */
+    int32_t reserved[8];   /* must be 0 */
+} sv_voxel_cluster_spec;
+
+/* Bytes of the workspace for a map of `capacity_of_map` voxels and `capacity` rows; 0 for a capacity outside 1 .. 2^26 or 1 .. 65535. */
+size_t sv_voxel_clusters_workspace_bytes(int64_t capacity_of_map, int capacity);
+/*   map, map_bytes, spec : the voxel map, as (Q)'s entries take it; written only under drop
+ *   cluster      : the words above
+ *   flat, floor  : mode 1: the flat map's words, as (K)'s entries take them, and int32 [rows][cols] device, (V)'s floor; not read in mode 0
+ *   min_n, min_rows, since : the filters; min_n >= 1
+ *   label        : int32 [slots] device, slots = sv_voxel_map_slots(capacity of the map)
+ *   clusters     : int64 [capacity][16] device;  info: int64 [8] device; both 8-byte aligned
+ *   workspace, workspace_bytes : device, 4-byte aligned, at least sv_voxel_clusters_workspace_bytes
+ * Returns SV_OK, SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued, everything untouched, the text in sv_last_error(NULL) - for: what the clear
+ * entry of (Q) refuses; cluster NULL or a reserved word of it not 0; connectivity none of 6, 18, 26; mode neither 0 nor 1; |z_ref_q| above
+ * 2^30 in mode 0; a band that is not -2^30 <= h_lo_q < h_hi_q <= 2^30; min_voxels < 1; capacity outside 1 .. 65535; drop neither 0 nor 1;
+ * in mode 1 what (K)'s fuse entry refuses of a map spec, floor NULL or not 4-byte aligned; min_n < 1; label, clusters, info or workspace
+ * NULL; a pointer not aligned to its element; workspace_bytes too small; an output or the workspace sharing a byte with the map, the
+ * floor or one another.  These checks run before any HIP call. */
+int sv_voxel_clusters_device(void *map, size_t map_bytes, const sv_voxel_map_spec *spec, const sv_voxel_cluster_spec *cluster, const sv_occupancy_map_spec *flat, const int32_t *floor, int64_t min_n, int64_t min_rows, int since, int32_t *label, int64_t *clusters, int64_t *info, void *workspace, size_t workspace_bytes, void *stream);
+/* Test and measurement hook, process-wide: the workgroups of the table walks at most (0: the call chooses; 1 .. 2048), and `stages`: the
+ * low four bits the kernels a call enqueues (0: all; 1 .. 7: the first that many of init, link, roots, count, scan, rank, stats, which
+ * leaves the outputs unfinished), 16: roots and stats issue one atomic per member instead of combining equal destinations over the
+ * wavefront, 32: the link kernel does not compress paths (by default it lowers a member's own parent word to the root its links
+ * ended at).  A value outside its range leaves that word as it was.  Returns the groups before. */
+int sv_debug_voxel_clusters(int groups, int stages);
 
 /* ---- (A)the reference's exported symbols ------------------------------------------------------------- */
 

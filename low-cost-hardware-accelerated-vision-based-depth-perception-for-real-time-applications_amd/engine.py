@@ -542,6 +542,12 @@ class SvVoxelFlattenSpec(ctypes.Structure):
                 ("min_obstacle", ctypes.c_int32), ("min_ground", ctypes.c_int32), ("reserved", ctypes.c_int32 * 9)]
 
 
+class SvVoxelClusterSpec(ctypes.Structure):
+    """sv_voxel_cluster_spec of include/stereo_vision_hip.h."""
+    _fields_ = [("connectivity", ctypes.c_int32), ("mode", ctypes.c_int32), ("z_ref_q", ctypes.c_int32), ("h_lo_q", ctypes.c_int32), ("h_hi_q", ctypes.c_int32),
+                ("min_voxels", ctypes.c_int32), ("capacity", ctypes.c_int32), ("drop", ctypes.c_int32), ("reserved", ctypes.c_int32 * 8)]
+
+
 def _signatures():
     """The table below: per stage group of the C API, (D) to (S), its functions and per function (restype, argtypes), parameter by
     parameter as include/stereo_vision_hip.h declares them - tests/test_stage_signatures.py holds the two against each other."""
@@ -646,6 +652,11 @@ def _signatures():
             "sv_voxel_flatten_device": (ci, [vp, sz, vm, om, P(SvVoxelFlattenSpec), i64, i64, ci, vp, vp, vp, vp, vp, vp, vp]),
             "sv_debug_voxel_flatten": (ci, [ci, ci]),
         },
+        "voxel_clusters": {  # (W)
+            "sv_voxel_clusters_workspace_bytes": (sz, [i64, ci]),
+            "sv_voxel_clusters_device": (ci, [vp, sz, vm, P(SvVoxelClusterSpec), om, vp, i64, i64, ci, vp, vp, vp, vp, sz, vp]),
+            "sv_debug_voxel_clusters": (ci, [ci, ci]),
+        },
     }
 
 
@@ -657,6 +668,7 @@ _GROUP_NEEDS["voxel_carry"] = ("voxel_map",)
 _GROUP_NEEDS["voxel_carve"] = ("voxel_map",)
 _GROUP_NEEDS["voxel_render"] = ("voxel_map",)
 _GROUP_NEEDS["voxel_flatten"] = ("voxel_map", "occupancy_map")
+_GROUP_NEEDS["voxel_clusters"] = ("voxel_map", "occupancy_map")
 _bound_groups = set()
 
 
@@ -2397,6 +2409,133 @@ def debug_voxel_flatten(groups=0, stages=0):
     kernels a call enqueues (0: all; 1 .. 4: the first that many of clear, walk A, floor, walk B).  Returns the groups before.
     Process-wide; a test and measurement hook."""
     return int(voxel_flatten_lib().sv_debug_voxel_flatten(int(groups), int(stages)))
+
+
+def voxel_clusters_lib():
+    """The library with the signatures of group (W) declared."""
+    return _bind("voxel_clusters")
+
+
+class VoxelClusterResult(_Result):
+    """What voxel_map_clusters returns, tensors on the voxel map's device: clusters int64 [R,16] (stereo_vision.sv.VOXEL_CLUSTER_ROW),
+    info int64 [8] (stereo_vision.sv.VOXEL_CLUSTER_INFO; members = -1 for an overflowed map), label int32 [slots] - per slot of the
+    table the component's row, -1 no member, -2 in a component below min_voxels, -3 in a kept component without a row - and keys, the
+    int64 [slots] strided view of the table's key words (valid while the map's buffer is).  rows and workspace are the tensors the call
+    wrote through - hand the result back as `out` and nothing is allocated.  sorted: whether clusters are in ascending least key and cut
+    behind that order."""
+    __slots__ = ("clusters", "info", "label", "keys", "rows", "workspace", "sorted")
+
+
+def voxel_cluster_spec(spec):
+    """-> SvVoxelClusterSpec from a dict of its words (stereo_vision.sv.voxel_cluster_params'), after stereo_vision.sv.voxel_cluster_words'
+    checks (ValueError for a bad word)."""
+    from .stereo_vision.sv import voxel_cluster_words
+    out = SvVoxelClusterSpec()
+    for k, v in voxel_cluster_words(spec).items():
+        setattr(out, k, v)
+    return out
+
+
+def voxel_map_clusters(buf, params, connectivity=26, min_voxels=1, capacity=1024, mode=0, z_ref=None, h_lo=None, h_hi=None, flat_map=None, floor=None, min_n=1,
+                       min_rows=1, since=0, drop=False, sort=True, out=None, spec=None):
+    """The connected components of the voxel map in `buf` - the definition of stereo_vision.sv.voxel_map_clusters on the GPU, bit for
+    bit (sv_voxel_clusters_device: eight kernels).  connectivity 6, 18 or 26; a component needs min_voxels voxels for a row; capacity
+    rows at most (1 .. 65535); mode 0: heights from z_ref (metres; None: the box's floor) in the band h_lo .. h_hi (metres; None: every
+    height); mode 1: heights above `floor`, the int32 [rows,cols] floor plane of a voxel_map_flatten on `flat_map` (its words), in the
+    band h_lo .. h_hi (None: 0.2 and 2.0 m, the flatten's obstacle voxels) - stereo_vision.sv.voxel_cluster_params; spec: that function's
+    dict instead of the words before it.  min_n >= 1, min_rows, since: the read-out's filters.  drop: the members of components below
+    min_voxels are emptied - tombstones until the next carry.  out: an earlier VoxelClusterResult of this map whose tensors are written
+    again.
+    sort=True: the kept count is read back (the one synchronisation); the C entry writes the rows of up to min(65535, the map's
+    capacity) kept components in the order of their roots' slots, torch.sort orders them by least key, the cut to `capacity` is made
+    behind that, and label is remapped through the inverse permutation: clusters [min(kept, capacity),16] and label equal the numpy
+    form's (voxel_cluster_labels) in shape, dtype and bits while the map holds at most 65535 kept components.
+    sort=False: what the C entry wrote with `capacity` rows, not waited for: clusters [capacity,16] in the order of the roots' slots -
+    which depends on the schedule of the inserts, as does which components are cut -, zero rows behind min(kept, capacity).
+    -> VoxelClusterResult; enqueued on torch's current stream; no other work on the map may run on another stream meanwhile."""
+    import torch
+    from .stereo_vision.sv import VOXEL_CLUSTER_CAPACITY_MAX, VOXEL_CLUSTER_CUT, occupancy_map_words, voxel_cluster_params
+    vspec = voxel_map_spec(params)
+    nbytes = _voxel_map_buffer(buf, vspec)
+    dev = buf.device
+    words = voxel_cluster_params(params, connectivity, min_voxels, capacity, mode, z_ref, h_lo, h_hi, drop) if spec is None else dict(spec)
+    cspec = voxel_cluster_spec(words)
+    capacity = cspec.capacity
+    for v, what, lo in ((min_n, "min_n", 1), (min_rows, "min_rows", -2 ** 63)):
+        if isinstance(v, bool) or int(v) != v or not lo <= v < 2 ** 63:
+            raise ValueError("%s must be an integer >= %d, got %r" % (what, lo, v))
+    if isinstance(since, bool) or int(since) != since or not -2 ** 31 <= since < 2 ** 31:
+        raise ValueError("since must be a 32-bit integer, got %r" % (since,))
+    flat = None
+    if cspec.mode == 1:
+        if flat_map is None or floor is None:
+            raise ValueError("mode 1 needs flat_map and floor: the words and the floor plane of a flatten")
+        fw = occupancy_map_words(flat_map)
+        if not (isinstance(floor, torch.Tensor) and floor.device == dev and floor.dtype == torch.int32 and tuple(floor.shape) == (fw["rows"], fw["cols"]) and floor.is_contiguous()):
+            raise ValueError("floor must be a contiguous int32 tensor [%d,%d] on the voxel map's device" % (fw["rows"], fw["cols"]))
+        flat = _occupancy_map_struct(fw)
+    L = voxel_clusters_lib()
+    slots = int(L.sv_voxel_map_slots(vspec.capacity))
+    n_rows = min(VOXEL_CLUSTER_CAPACITY_MAX, max(capacity, vspec.capacity)) if sort else capacity  # sort: the cut is made behind the order
+    ws_bytes = int(L.sv_voxel_clusters_workspace_bytes(vspec.capacity, n_rows))
+    shapes = {"rows": ((n_rows, 16), torch.int64), "info": ((8,), torch.int64), "label": ((slots,), torch.int32), "workspace": ((ws_bytes // 4,), torch.int32)}
+    if out is not None and not isinstance(out, VoxelClusterResult):
+        raise ValueError("out must be a VoxelClusterResult")
+    res = VoxelClusterResult(sorted=bool(sort))
+    for k, (shape, dtype) in shapes.items():
+        t = None if out is None else getattr(out, k)
+        if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous()):
+            t = torch.empty(shape, dtype=dtype, device=dev)  # another map, another capacity or another sort: new tensors
+        setattr(res, k, t)
+    res.keys = buf[4:].as_strided((slots,), (11,))
+    cspec.capacity = n_rows
+    with torch.cuda.device(dev):
+        rc = L.sv_voxel_clusters_device(buf.data_ptr(), nbytes, ctypes.byref(vspec), ctypes.byref(cspec), None if flat is None else ctypes.byref(flat),
+                                        None if flat is None else floor.data_ptr(), int(min_n), int(min_rows), int(since), res.label.data_ptr(), res.rows.data_ptr(),
+                                        res.info.data_ptr(), res.workspace.data_ptr(), ws_bytes, torch.cuda.current_stream(dev).cuda_stream)
+    _check(rc, "sv_voxel_clusters_device")
+    if not sort:
+        res.clusters = res.rows
+        return res
+    written = min(max(int(res.info[2]), 0), n_rows)  # the synchronisation
+    order = torch.sort(res.rows[:written, 0]).indices
+    res.clusters = res.rows[:written][order][:capacity].contiguous()
+    rank = torch.empty((written + 3,), dtype=torch.int32, device=dev)  # the inverse permutation, and -3, -2, -1 onto themselves behind it
+    rank[order] = torch.arange(written, dtype=torch.int32, device=dev)
+    rank[:written][rank[:written] >= capacity] = VOXEL_CLUSTER_CUT
+    rank[written:] = torch.tensor([-3, -2, -1], dtype=torch.int32, device=dev)
+    res.label = rank[res.label.long()]  # a negative label indexes from the end
+    return res
+
+
+def voxel_cluster_labels(result):
+    """-> (key, cluster) of the slots that hold a key, ordered by key: an int64 and an int32 tensor on the map's device, what
+    stereo_vision.sv.voxel_map_clusters returns as "key" and "label".  Reads the number of such slots back: this synchronises.  Call
+    it before anything else changes the map's keys."""
+    import torch
+    at = torch.nonzero(result.keys != -1).reshape(-1)
+    order = torch.sort(result.keys[at]).indices
+    return result.keys[at][order], result.label[at][order]
+
+
+def voxel_cluster_boxes(result, params):
+    """The rows of a VoxelClusterResult (or an int64 [R,16] tensor or array of them) in metres, in double on the host:
+    stereo_vision.sv.voxel_cluster_boxes' dict of numpy arrays - centre, lo, hi [R,3], key, voxels, n, first_seq, last_seq [R].  Rows
+    without voxels - the zero rows behind the kept ones of sort=False - are left out.  Reads the rows back."""
+    import torch
+    from .stereo_vision import sv
+    rows = result.clusters if isinstance(result, VoxelClusterResult) else result
+    rows = rows.cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)
+    rows = rows.reshape(-1, 16)
+    return sv.voxel_cluster_boxes(rows[rows[:, 1] > 0], params)
+
+
+def debug_voxel_clusters(groups=0, stages=0):
+    """sv_debug_voxel_clusters: the workgroups of voxel_map_clusters' table walks at most (0: the call chooses; 1 .. 2048) and `stages`:
+    the low four bits the kernels a call enqueues (0: all; 1 .. 7: the first that many of init, link, roots, count, scan, rank, stats),
+    16: no combining of equal destinations over the wavefront, 32: no path compression in the link kernel.  Returns the groups before.
+    Process-wide; a test and measurement hook."""
+    return int(voxel_clusters_lib().sv_debug_voxel_clusters(int(groups), int(stages)))
 
 
 def host_support_filter(params, dcan, width, height, threads=0, lattice=False):

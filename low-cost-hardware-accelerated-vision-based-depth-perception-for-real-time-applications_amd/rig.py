@@ -451,7 +451,9 @@ class VoxelMap:
     the next prune().  render() is group (U), stereo_vision.sv.voxel_map_render: what a camera should see of the map from given poses -
     depth, colour and expected disparity per pixel - and, against a measured disparity, what is new and what was seen through.
     flatten() is group (V), stereo_vision.sv.voxel_map_flatten: the voxels sliced by height above the floor and written out as the
-    logodds and last_seen of a flat map, which OccupancyMap.load_voxels takes."""
+    logodds and last_seen of a flat map, which OccupancyMap.load_voxels takes.  clusters() and despeckle() are group (W),
+    stereo_vision.sv.voxel_map_clusters: the connected components of the voxels - a row of counts, sums and a box per object, a label per
+    voxel - and the components below a size emptied."""
 
     def __init__(self, lo, hi, size, capacity, device="cuda"):
         import torch
@@ -462,6 +464,7 @@ class VoxelMap:
         self.seq = 0
         self._spare = None  # prune()'s, recenter()'s and resize()'s second buffer, made on first use
         self._miss = None   # carve()'s word per slot, made on first use
+        self._clusters = None  # clusters()' result and workspace, made on first use
         if self.device.type == "cuda":
             self.buffer, self._state = voxel_map_new(self.params, self.device), None
         else:
@@ -692,6 +695,55 @@ class VoxelMap:
             return voxel_map_flatten(self.buffer, self.params, words, spec, min_n, min_rows, since, out=out)
         res = _sv.voxel_map_flatten(self._state, words, spec, min_n, min_rows, since)
         return VoxelFlattenResult(**{k: torch.from_numpy(v) for k, v in res.items()})
+
+    def clusters(self, connectivity=26, min_voxels=1, capacity=1024, z_ref=None, h_lo=None, h_hi=None, flat=None, flat_map=None, floor=None, min_n=1, min_rows=1,
+                 since=0, drop=False, sort=True):
+        """The connected components of the map (include/stereo_vision_hip.h (W), stereo_vision.sv.voxel_map_clusters): the objects in
+        it.  connectivity 6, 18 or 26; a component of at least min_voxels voxels gets a row, `capacity` rows at most.  Without a floor
+        the heights count from z_ref (metres in the world; None: the box's floor) and the band h_lo .. h_hi, metres, None = open, says
+        which voxels take part.  With a floor - flat = an engine.VoxelFlattenResult of flatten() together with flat_map = the flat map it
+        was made for, or flat = an OccupancyMap that load_voxels() has just filled, or flat_map and floor themselves - the heights count
+        from that floor plane and the band defaults to 0.2 .. 2.0 m, the flatten's obstacle voxels, so that the ground does not glue the
+        things that stand on it into one piece.  min_n >= 1, min_rows, since: rows()' filters.  drop: despeckle().  -> an
+        engine.VoxelClusterResult - clusters int64 [R,16], info int64 [8], label int32 per slot - on the device, whose tensors the map
+        keeps and the next call writes again; on "cpu" the definition's dict as tensors, with label per entry in ascending key.
+        engine.voxel_cluster_labels / voxel_cluster_boxes read either.  sort=True waits for one word; sort=False (device only) for
+        nothing."""
+        import torch
+        from .engine import VoxelFlattenResult, voxel_map_clusters
+        if isinstance(flat, OccupancyMap):
+            if flat._flatten is None:
+                raise ValueError("clusters: flat is an OccupancyMap that load_voxels() has not filled")
+            flat_map, floor = flat.words, flat._flatten.floor
+        elif isinstance(flat, VoxelFlattenResult):
+            if flat_map is None:
+                raise ValueError("clusters: a flatten result needs flat_map, the flat map it was made for")
+            floor = flat.floor
+        elif flat is not None:
+            raise ValueError("clusters: flat must be an engine.VoxelFlattenResult or an OccupancyMap")
+        if isinstance(flat_map, OccupancyMap):
+            flat_map = flat_map.words
+        mode = 0 if floor is None else 1
+        spec = _sv.voxel_cluster_params(self.params, connectivity, min_voxels, capacity, mode, z_ref, h_lo, h_hi, drop)
+        if self._state is None:
+            self._clusters = voxel_map_clusters(self.buffer, self.params, flat_map=flat_map, floor=floor, min_n=min_n, min_rows=min_rows, since=since, sort=sort,
+                                                out=self._clusters, spec=spec)
+            return self._clusters
+        fl = floor.cpu().numpy() if isinstance(floor, torch.Tensor) else floor
+        res = _sv.voxel_map_clusters(self._state, spec, flat_map, fl, min_n, min_rows, since)
+        return {k: torch.from_numpy(v) for k, v in res.items()}
+
+    def despeckle(self, min_voxels, connectivity=26, prune=False, **filters):
+        """The speckle filter in three dimensions: every voxel of a connected component of fewer than min_voxels voxels is emptied - the
+        floating islands that mismatches leave, which no later sight line may ever cross.  filters: min_n, min_rows, since, which say
+        what counts as a voxel here.  An emptied voxel keeps its slot until the next prune() - prune=True follows with one -:
+        stats()["claimed"] does not change, and every method skips it at min_n >= 1.  -> the info words of clusters(): int64 [8] on the
+        device, not waited for (info[4] = the voxels emptied), or a tensor on "cpu"."""
+        f = self._filters(filters)
+        res = self.clusters(connectivity, min_voxels, 1, min_n=f[0], min_rows=f[1], since=f[2], drop=True, sort=False if self._state is None else True)
+        if prune:
+            self.prune()
+        return res.info if self._state is None else res["info"]
 
     def write_ply(self, path, min_n=1, min_rows=1, since=0):
         """rows(...) as a binary PLY of coloured points (stereo_vision.sv.write_ply); -> the number of points.  RuntimeError for an

@@ -121,6 +121,13 @@ rig.VoxelMap.flatten / rig.OccupancyMap.load_voxels on the GPU): the voxels slic
 ground, obstacle and overhead, and per flat cell the log-odds and last_seen words that occupancy_clearance, cost_to_goal, frontier_cells
 and occupancy_view take - a bridge overhead is no obstacle, a kerb below the step is ground.  The reference has no counterpart (DESIGN.md
 §8).
+
+voxel_map_clusters (with voxel_map_clusters_brute, the plain flood fill, voxel_cluster_params, voxel_cluster_words and voxel_cluster_boxes)
+is the definition of the voxel map clustered (sv_voxel_clusters_device of include/stereo_vision_hip.h (W); engine.voxel_map_clusters /
+rig.VoxelMap.clusters / .despeckle on the GPU): the 6-, 18- or 26-connected components of the voxels inside a height band over an
+absolute floor or over the flatten's, a row of counts, sums and a box per component in ascending least key, a label per voxel, and the
+components below a size emptied - the objects of the map and its speckle filter in three dimensions.  The reference has no counterpart
+(DESIGN.md §8).
 """
 import argparse
 import ctypes
@@ -1347,6 +1354,239 @@ def voxel_map_flatten_brute(map_state, flat_map, spec, min_n=1, min_rows=1, sinc
             continue
         out["last_seen"][r, c] = max(seq for _, seq in held)
     return out
+
+
+VOXEL_CLUSTER_WORDS = ("connectivity", "mode", "z_ref_q", "h_lo_q", "h_hi_q", "min_voxels", "capacity", "drop")  # sv_voxel_cluster_spec, in its order
+VOXEL_CLUSTER_INFO = ("members", "components", "kept", "small_voxels", "emptied", "largest")  # voxel_map_clusters' info, words 0 .. 5
+VOXEL_CLUSTER_ROW = ("key", "voxels", "n", "cmin_x", "cmin_y", "cmin_z", "cmax_x", "cmax_y", "cmax_z", "sum_x", "sum_y", "sum_z", "first_seq", "last_seq", "m", "zero")
+VOXEL_CLUSTER_CAPACITY_MAX = 65535  # rows per call of the C entry
+VOXEL_CLUSTER_BAND_MAX = 2 ** 30    # |z_ref_q|, |h_lo_q|, |h_hi_q| at most: with zq < 2^28 the height stays an int32 over an absolute floor
+VOXEL_CLUSTER_SMALL, VOXEL_CLUSTER_CUT = -2, -3  # labels: a member of a component below min_voxels; of a kept component without a row
+VOXEL_CLUSTER_OFFSETS = tuple((o % 3 - 1, (o // 3) % 3 - 1, o // 9 - 1) for o in range(13))  # (dx, dy, dz): the half that is negative in (dz, dy, dx) order
+
+
+def voxel_cluster_words(spec):
+    """The words of sv_voxel_cluster_spec as a dict of ints - VOXEL_CLUSTER_WORDS - from a dict of them (voxel_cluster_params'; a
+    "reserved" entry must hold zeros only), after the checks the C entry makes (ValueError): connectivity 6, 18 or 26, mode 0 or 1,
+    |z_ref_q| <= 2^30, -2^30 <= h_lo_q < h_hi_q <= 2^30, min_voxels in 1 .. 2^31 - 1, capacity in 1 .. 65535, drop 0 or 1."""
+    w = {}
+    for k in VOXEL_CLUSTER_WORDS:
+        v = spec.get(k) if isinstance(spec, dict) else getattr(spec, k, None)
+        w[k] = int(v) if k == "drop" and isinstance(v, (bool, np.bool_)) else _whole(v, k + " of the cluster spec")
+    reserved = spec.get("reserved", ()) if isinstance(spec, dict) else getattr(spec, "reserved", ())
+    if any(int(v) != 0 for v in reserved):
+        raise ValueError("a reserved word of the cluster spec is not 0: %r" % (list(reserved),))
+    if w["connectivity"] not in (6, 18, 26):
+        raise ValueError("connectivity must be 6, 18 or 26, got %d" % w["connectivity"])
+    if w["mode"] not in (0, 1):
+        raise ValueError("mode must be 0 (an absolute floor) or 1 (the floor plane of a flatten), got %d" % w["mode"])
+    if abs(w["z_ref_q"]) > VOXEL_CLUSTER_BAND_MAX:
+        raise ValueError("|z_ref_q| must not exceed 2^30, got %d" % w["z_ref_q"])
+    if not -VOXEL_CLUSTER_BAND_MAX <= w["h_lo_q"] < w["h_hi_q"] <= VOXEL_CLUSTER_BAND_MAX:
+        raise ValueError("-2^30 <= h_lo_q < h_hi_q <= 2^30 must hold, got %d and %d" % (w["h_lo_q"], w["h_hi_q"]))
+    if not 1 <= w["min_voxels"] < 2 ** 31:
+        raise ValueError("min_voxels must lie in 1 .. 2^31 - 1, got %d" % w["min_voxels"])
+    if not 1 <= w["capacity"] <= VOXEL_CLUSTER_CAPACITY_MAX:
+        raise ValueError("capacity must lie in 1 .. 65535, got %d" % w["capacity"])
+    if w["drop"] not in (0, 1):
+        raise ValueError("drop must be 0 or 1, got %d" % w["drop"])
+    return w
+
+
+def voxel_cluster_params(voxel_params, connectivity=26, min_voxels=1, capacity=1024, mode=0, z_ref=None, h_lo=None, h_hi=None, drop=False):
+    """The words of a clustering (sv_voxel_cluster_spec) as a dict, from metres: voxel_params the voxel map's (its lo[2] and size).  mode 0:
+    heights count from z_ref, metres in the world (None: the box's lo[2]; z_ref_q = floor((z_ref - lo_z) / size * 256)), and h_lo, h_hi
+    = None take every height (-2^30 and 2^30).  mode 1: heights count from the floor plane of a flatten, z_ref is not used, and h_lo, h_hi
+    = None are the flatten's own step and height, 0.2 m and 2.0 m: its obstacle voxels.  h_lo_q and h_hi_q = round(metres / size * 256).
+    ValueError for a number that is not finite and for what voxel_cluster_words refuses."""
+    lo_z, size = float(voxel_params["lo"][2]), float(voxel_params["size"])
+    if mode not in (0, 1):
+        raise ValueError("mode must be 0 or 1, got %r" % (mode,))
+    if mode == 1:
+        z_ref, h_lo, h_hi = None, 0.2 if h_lo is None else h_lo, 2.0 if h_hi is None else h_hi
+    try:
+        given = [None if v is None else float(v) for v in (z_ref, h_lo, h_hi)]
+    except (TypeError, ValueError):
+        raise ValueError("z_ref, h_lo and h_hi must be numbers or None, got %r, %r, %r" % (z_ref, h_lo, h_hi))
+    if not (all(v is None or np.isfinite(v) for v in given) and np.isfinite(size) and size > 0 and np.isfinite(lo_z)):
+        raise ValueError("z_ref, h_lo and h_hi must be finite and the voxel size > 0, got %r, %r, %r and %r" % (z_ref, h_lo, h_hi, size))
+    q = [None if v is None else v / size * 256.0 for v in given]
+    if any(v is not None and abs(v) >= 2.0 ** 40 for v in q):
+        raise ValueError("z_ref, h_lo or h_hi is too many voxel cells of %r m: %r, %r, %r" % (size, z_ref, h_lo, h_hi))
+    return voxel_cluster_words(dict(connectivity=connectivity, mode=mode, z_ref_q=0 if given[0] is None else int(np.floor((given[0] - lo_z) / size * 256.0)),
+                                    h_lo_q=-VOXEL_CLUSTER_BAND_MAX if q[1] is None else int(round(q[1])), h_hi_q=VOXEL_CLUSTER_BAND_MAX if q[2] is None else int(round(q[2])),
+                                    min_voxels=min_voxels, capacity=capacity, drop=drop))
+
+
+def _voxel_cluster_setup(map_state, spec, flat_map, floor, min_n, min_rows, since):
+    """What voxel_map_clusters and voxel_map_clusters_brute share: the checked words, the map's entries in ascending key (`order`: indices
+    into the state) and which of them are members (none for an overflowed map)."""
+    s = voxel_cluster_words(spec)
+    if isinstance(min_n, bool) or int(min_n) != min_n or min_n < 1:
+        raise ValueError("min_n must be an integer >= 1 - an emptied voxel has n = 0 and divides -, got %r" % (min_n,))
+    order = np.argsort(map_state["key"], kind="stable")
+    key, n, S = map_state["key"][order], map_state["n"][order], map_state["S"][order]
+    member = (n >= min_n) & (map_state["m"][order] >= min_rows) & (map_state["last_seq"][order] >= since)
+    if map_state["overflowed"]:
+        member[:] = False
+    at = np.flatnonzero(member)
+    nm = n[at]
+    base = np.full(len(at), s["z_ref_q"], np.int64)
+    ok = np.ones(len(at), bool)
+    if s["mode"] == 1:
+        if flat_map is None or floor is None:
+            raise ValueError("mode 1 needs flat_map and floor: the words and the floor plane of a flatten")
+        w = occupancy_map_words(flat_map)
+        floor = np.asarray(floor)
+        if floor.dtype != np.int32 or floor.shape != (w["rows"], w["cols"]):
+            raise ValueError("floor must be int32 [%d,%d], got %s %s" % (w["rows"], w["cols"], floor.dtype, floor.shape))
+        p = map_state["params"]
+        size, ms, nf = np.float64(p["size"]), np.float64(w["scale"]), nm.astype(np.float64)
+        g = []
+        for k in range(2):
+            c = ((key[at] >> (20 * k)) & 0xFFFFF).astype(np.float64)
+            g.append(np.floor((np.float64(p["lo"][k]) + (c + (S[at, k].astype(np.float64) + 0.5 * nf) / (65536.0 * nf)) * size) * ms))
+        ok = (g[0] >= w["top"] - w["rows"]) & (g[0] <= w["top"] - 1) & (g[1] >= w["left"] - w["cols"]) & (g[1] <= w["left"] - 1)
+        r, c = np.where(ok, w["top"] - 1 - g[0], 0).astype(np.int64), np.where(ok, w["left"] - 1 - g[1], 0).astype(np.int64)
+        base = floor[r, c].astype(np.int64)
+        ok &= base != -1
+    h = ((key[at] >> 40) & 0xFFFFF) * 256 + ((S[at, 2] // np.maximum(nm, 1)) >> 8) - base
+    member[at] = ok & (s["h_lo_q"] <= h) & (h < s["h_hi_q"])
+    return s, order, member
+
+
+def _voxel_cluster_result(map_state, s, order, member, comp):
+    """The outputs from the partition: comp int64 per member, in ascending key, = the index among the members of the component's least
+    key.  Applies `drop` to the state."""
+    key = map_state["key"][order]
+    info, label = np.zeros(8, np.int64), np.full(len(key), -1, np.int32)
+    if map_state["overflowed"]:
+        info[0] = -1
+        return {"clusters": np.zeros((0, 16), np.int64), "info": info, "key": key, "label": label}
+    at = order[member]  # the members, into the state, in ascending key
+    roots, inv, voxels = np.unique(comp, return_inverse=True, return_counts=True)  # ascending least key
+    inv = inv.reshape(-1)
+    keep = voxels >= s["min_voxels"]
+    row = np.where(keep, np.cumsum(keep) - 1, VOXEL_CLUSTER_SMALL)
+    row[keep & (row >= s["capacity"])] = VOXEL_CLUSTER_CUT
+    label[member] = row[inv]
+    small = ~keep[inv]
+    info[:6] = [len(at), len(roots), int(keep.sum()), int(small.sum()), int(small.sum()) if s["drop"] else 0, int(voxels.max()) if len(voxels) else 0]
+    R = min(int(keep.sum()), s["capacity"])
+    rows = np.zeros((R, 16), np.int64)
+    mine = row[inv] >= 0
+    to, src = row[inv][mine], at[mine]
+    k, n = map_state["key"][src], map_state["n"][src]
+    cell = np.stack([(k >> (20 * a)) & 0xFFFFF for a in range(3)], -1)
+    rows[:, 0], rows[:, 3:6], rows[:, 6:9], rows[:, 12], rows[:, 13] = np.iinfo(np.int64).max, np.iinfo(np.int64).max, -1, np.iinfo(np.int64).max, -1
+    np.minimum.at(rows[:, 0], to, k)
+    np.add.at(rows[:, 1], to, 1)
+    np.add.at(rows[:, 2], to, n)
+    for a in range(3):
+        np.minimum.at(rows[:, 3 + a], to, cell[:, a])
+        np.maximum.at(rows[:, 6 + a], to, cell[:, a])
+        np.add.at(rows[:, 9 + a], to, cell[:, a] * 256 + ((map_state["S"][src, a] // n) >> 8))
+    np.minimum.at(rows[:, 12], to, map_state["first_seq"][src])
+    np.maximum.at(rows[:, 13], to, map_state["last_seq"][src])
+    np.add.at(rows[:, 14], to, map_state["m"][src])
+    if s["drop"]:
+        gone = at[small]
+        for f in ("n", "S", "C", "m"):
+            map_state[f][gone] = 0
+        map_state["first_seq"][gone], map_state["last_seq"][gone] = np.iinfo(np.int64).max, -1
+    return {"clusters": rows, "info": info, "key": key, "label": label}
+
+
+def voxel_map_clusters(map_state, spec, flat_map=None, floor=None, min_n=1, min_rows=1, since=0):
+    """The connected components of a voxel map, the definition of include/stereo_vision_hip.h (W) in numpy; integers throughout but for
+    the flat cell of mode 1.  map_state (voxel_map_state's dict) is changed under spec["drop"] only.
+
+    spec: voxel_cluster_params' dict.  A voxel is a member iff n >= min_n (>= 1: an emptied voxel never is), m >= min_rows, last_seq >=
+    since and h_lo_q <= zq - base < h_hi_q with zq = cz * 256 + ((S_z // n) >> 8), voxel_map_flatten's, and base = z_ref_q (mode 0) or
+    floor[cell] (mode 1): floor the int32 [rows,cols] floor plane of voxel_map_flatten on flat_map, cell the flat cell under the voxel's
+    centre by voxel_map_flatten's rule; a voxel outside flat_map or over a cell with floor -1 is no member.  Two members are neighbours
+    iff their cells differ by at most 1 on every axis, on 1 (connectivity 6), up to 2 (18) or up to 3 (26) axes; the cells are tested
+    against the box per axis before a key is made of them.  A component is the transitive closure; its identity is its least key.
+
+    Sorted keys, searchsorted neighbours over VOXEL_CLUSTER_OFFSETS, least-label propagation with pointer jumping to a fixed point.
+
+    Returns a dict: clusters int64 [R,16], R = min(kept, capacity): the components with voxels >= min_voxels in ascending least key, cut
+    to `capacity` - the cut is made behind the order, so the rows are the least keys - with the words VOXEL_CLUSTER_ROW (least key,
+    voxels, sum n, least and largest cell per axis, sum over the members of c_k * 256 + ((S_k // n) >> 8) per axis, least first_seq,
+    largest last_seq, sum m, 0); info int64 [8] = members, components, kept, voxels in components below min_voxels, voxels emptied,
+    voxels of the largest component, 0, 0; key int64 [V], every entry of the map in ascending key, and label int32 [V], its row, -1 for
+    no member, -2 in a component below min_voxels, -3 in a kept component behind the cut.  drop: the members labelled -2 are emptied as
+    voxel_map_carve empties.  An overflowed map: info[0] = -1, no rows, every label -1, nothing done."""
+    s, order, member = _voxel_cluster_setup(map_state, spec, flat_map, floor, min_n, min_rows, since)
+    cells = np.array(map_state["params"]["cells"], np.int64)
+    mk = map_state["key"][order][member]
+    M = len(mk)
+    c = np.stack([(mk >> (20 * a)) & 0xFFFFF for a in range(3)], -1) if M else np.zeros((0, 3), np.int64)
+    most = {6: 1, 18: 2, 26: 3}[s["connectivity"]]
+    ei, ej = [], []
+    for d in VOXEL_CLUSTER_OFFSETS:
+        if sum(v != 0 for v in d) > most or not M:
+            continue
+        nb = c + np.array(d, np.int64)
+        inside = ((nb >= 0) & (nb < cells)).all(-1)  # per axis, before a key is made
+        nkey = nb[:, 0] | (nb[:, 1] << 20) | (nb[:, 2] << 40)
+        at = np.minimum(np.searchsorted(mk, nkey), M - 1)
+        hit = inside & (mk[at] == nkey)
+        ei.append(np.flatnonzero(hit)), ej.append(at[hit])
+    ei, ej = (np.concatenate(ei), np.concatenate(ej)) if ei else (np.zeros(0, np.int64), np.zeros(0, np.int64))
+    lab = np.arange(M, dtype=np.int64)
+    while True:
+        new = lab.copy()
+        np.minimum.at(new, ei, lab[ej])
+        np.minimum.at(new, ej, lab[ei])
+        while True:  # pointer jumping
+            jumped = new[new]
+            if (jumped == new).all():
+                break
+            new = jumped
+        if (new == lab).all():
+            break
+        lab = new
+    return _voxel_cluster_result(map_state, s, order, member, lab)
+
+
+def voxel_map_clusters_brute(map_state, spec, flat_map=None, floor=None, min_n=1, min_rows=1, since=0):
+    """voxel_map_clusters' definition as a plain flood fill over a dict of cells: the form the vectorised one is checked against.  Same
+    arguments, same dict."""
+    s, order, member = _voxel_cluster_setup(map_state, spec, flat_map, floor, min_n, min_rows, since)
+    cells = [int(v) for v in map_state["params"]["cells"]]
+    mk = [int(k) for k in map_state["key"][order][member]]
+    where = {(k & 0xFFFFF, (k >> 20) & 0xFFFFF, (k >> 40) & 0xFFFFF): i for i, k in enumerate(mk)}
+    most = {6: 1, 18: 2, 26: 3}[s["connectivity"]]
+    steps = [(dx, dy, dz) for dx in (-1, 0, 1) for dy in (-1, 0, 1) for dz in (-1, 0, 1) if 1 <= (dx != 0) + (dy != 0) + (dz != 0) <= most]
+    comp = [-1] * len(mk)
+    for cell, i in sorted(where.items(), key=lambda item: item[1]):  # ascending key: a fill starts at its component's least
+        if comp[i] >= 0:
+            continue
+        comp[i], stack = i, [cell]
+        while stack:
+            x, y, z = stack.pop()
+            for dx, dy, dz in steps:
+                nb = (x + dx, y + dy, z + dz)
+                if not all(0 <= nb[a] < cells[a] for a in range(3)):
+                    continue
+                j = where.get(nb)
+                if j is not None and comp[j] < 0:
+                    comp[j] = i
+                    stack.append(nb)
+    return _voxel_cluster_result(map_state, s, order, member, np.array(comp, np.int64).reshape(-1))
+
+
+def voxel_cluster_boxes(clusters, params):
+    """Cluster rows in metres, in double on the host: clusters int64 [R,16] (voxel_map_clusters' rows), params the voxel map's.  -> a dict
+    of float64 [R,3] arrays: centre = lo + (sum_q / voxels) / 256 * size, the mean of the members' mean positions; lo and hi = the box's
+    corners, lo + cmin * size and lo + (cmax + 1) * size - and of int64 [R] arrays key, voxels, n, first_seq, last_seq."""
+    rows = np.asarray(clusters, np.int64).reshape(-1, 16)
+    lo, size = np.array(params["lo"], np.float64), np.float64(params["size"])
+    voxels = rows[:, 1].astype(np.float64)[:, None]
+    return {"centre": lo + (rows[:, 9:12].astype(np.float64) / voxels) / 256.0 * size, "lo": lo + rows[:, 3:6].astype(np.float64) * size,
+            "hi": lo + (rows[:, 6:9].astype(np.float64) + 1.0) * size, "key": rows[:, 0].copy(), "voxels": rows[:, 1].copy(), "n": rows[:, 2].copy(),
+            "first_seq": rows[:, 12].copy(), "last_seq": rows[:, 13].copy()}
 
 
 VOXEL_MATCH_BATCH_MAX = 65535
@@ -3020,6 +3260,13 @@ def main(argv=None):
                              "<FILE without extension>.flat.npz; with "
                              "--clearance and --goal also the clearance field of that map (.flat.clearance.png) and the route from where "
                              "the drive ended (.flat.route.txt)")
+    parser.add_argument("--voxel-clusters", type=str, default="", metavar="MIN_VOXELS[,CONNECTIVITY[,H_LO_M,H_HI_M]]",
+                        help="with --voxel-map: at the end of the run, the connected components of the voxel map (CONNECTIVITY 6, 18 or 26, "
+                             "default 26) with at least MIN_VOXELS voxels, among the voxels H_LO_M .. H_HI_M metres above the floor: the "
+                             "box's without --voxel-flatten (default: every height), with it that flat map's local floor (default: its "
+                             "STEP_M .. HEIGHT_M, the obstacle voxels, so the ground does not join the objects).  Writes <FILE without "
+                             "extension>.clusters.txt, a line per cluster - least key, voxels, centre, box corners, first and last frame - "
+                             "and .clusters.ply, the clustered voxels coloured by cluster")
     parser.add_argument("--voxel-match", type=str, default="", metavar="DX,DY,DZ,DYAW[,NX,NY,NZ,NYAW]",
                         help="with --voxel-map: take the poses as guesses at height 0 - frame 0 is inserted where its line says; every later "
                              "frame's voxel cloud is first matched against the voxel map built so far over a window of +-DX, +-DY, +-DZ metres "
@@ -3141,6 +3388,14 @@ def main(argv=None):
             args.voxel_flatten_spec = cli_voxel_flatten_spec(args.voxel_flatten, args.voxel)
         except ValueError as e:
             parser.error("--voxel-flatten: %s" % e)
+    args.voxel_clusters_spec = None
+    if args.voxel_clusters:
+        if not args.voxel_map:
+            parser.error("--voxel-clusters needs --voxel-map")
+        try:
+            args.voxel_clusters_spec = cli_voxel_clusters_spec(args.voxel_clusters, args.voxel)
+        except ValueError as e:
+            parser.error("--voxel-clusters: %s" % e)
     args.voxel_render_spec = None
     if args.voxel_render:
         if not args.voxel_map:
@@ -3345,6 +3600,40 @@ def cli_voxel_flatten_text(stats):
     return ", ".join("%s %d" % (k.replace("_", " "), int(v)) for k, v in zip(VOXEL_FLATTEN_STATS, stats))
 
 
+CLI_VOXEL_CLUSTERS_ROWS = 65535  # rows of --voxel-clusters
+
+
+def cli_voxel_clusters_spec(text, size):
+    """(min_voxels, connectivity, h_lo_m, h_hi_m) of --voxel-clusters' MIN_VOXELS[,CONNECTIVITY[,H_LO_M,H_HI_M]] for voxels of `size`
+    metres - the band None, None where it is not given -, after voxel_cluster_params' checks: ValueError with the text the CLI prints."""
+    words = text.split(",")
+    if len(words) not in (1, 2, 4):
+        raise ValueError("MIN_VOXELS[,CONNECTIVITY[,H_LO_M,H_HI_M]], got %r" % (text,))
+    try:
+        min_voxels, connectivity = int(words[0]), int(words[1]) if len(words) > 1 else 26
+        h_lo, h_hi = (float(words[2]), float(words[3])) if len(words) == 4 else (None, None)
+    except ValueError:
+        raise ValueError("MIN_VOXELS and CONNECTIVITY must be whole numbers, H_LO_M and H_HI_M numbers, got %r" % (text,))
+    voxel_cluster_params(dict(lo=(0.0, 0.0, 0.0), size=size), connectivity, min_voxels, CLI_VOXEL_CLUSTERS_ROWS, 0, None, h_lo, h_hi)
+    return min_voxels, connectivity, h_lo, h_hi
+
+
+def cli_voxel_cluster_lines(boxes):
+    """voxel_cluster_boxes' dict as the lines of <FILE>.clusters.txt: least key, voxels, the centre, the box's two corners, first and last
+    frame."""
+    return ["%d %d %s %d %d" % (key, voxels, " ".join(repr(float(v)) for v in list(c) + list(a) + list(b)), first, last)
+            for key, voxels, c, a, b, first, last in zip(boxes["key"], boxes["voxels"], boxes["centre"], boxes["lo"], boxes["hi"], boxes["first_seq"], boxes["last_seq"])]
+
+
+def voxel_cluster_colors(label):
+    """uint8 [V,4] BGRA per voxel from its cluster's row (int [V], >= 0): a fixed hash of the row, never black."""
+    lab = np.asarray(label, np.int64).astype(np.uint64)
+    with np.errstate(over="ignore"):
+        h = lab * np.uint64(0x9E3779B97F4A7C15) + np.uint64(0x7F4A7C15)
+    rgb = np.stack([(h >> np.uint64(s)) & np.uint64(0xFF) for s in (40, 48, 56)], -1).astype(np.int64)
+    return np.concatenate([64 + rgb * 3 // 4, np.full((len(lab), 1), 255)], -1).astype(np.uint8)
+
+
 def cli_voxel_render_text(counts):
     """The pixels per label of one view (six integers) as the CLI prints them."""
     return ", ".join("%s %d" % (k, int(v)) for k, v in zip(VOXEL_RENDER_LABELS, counts))
@@ -3466,6 +3755,27 @@ def _run_batched(args, ldir, rdir, files):
                         with open(stem + ".route.txt", "w") as f:
                             f.write("".join("%d %d %r %r\n" % (r, c, float(x), float(y)) for (r, c), (x, y) in zip(route.cells[0, :length].cpu().numpy(), xy[0, :length])))
                         print("route on the flattened map: status %d, %d cells%s" % (int(route.status[0]), length, "" if field.converged else " (field not converged)"))
+            if args.voxel_clusters_spec is not None:  # the objects of the map; over the flat map's floor where one was made
+                from ..engine import voxel_cluster_boxes, voxel_cluster_labels
+                min_voxels, connectivity, h_lo, h_hi = args.voxel_clusters_spec
+                over = {}
+                if args.voxel_flatten_spec is not None:
+                    over = dict(flat=flat, h_lo=args.voxel_flatten_spec[3] if h_lo is None else h_lo, h_hi=args.voxel_flatten_spec[4] if h_hi is None else h_hi)
+                else:
+                    over = dict(h_lo=h_lo, h_hi=h_hi)
+                found = model.clusters(connectivity, min_voxels, CLI_VOXEL_CLUSTERS_ROWS, **over)
+                stem = os.path.splitext(args.voxel_map)[0] + ".clusters"
+                boxes = voxel_cluster_boxes(found, model.params)
+                with open(stem + ".txt", "w") as f:
+                    f.write("".join(line + "\n" for line in cli_voxel_cluster_lines(boxes)))
+                key, lab = (t.cpu().numpy() for t in voxel_cluster_labels(found))
+                rows = model.rows()
+                at = np.searchsorted(key, rows["key"].cpu().numpy())  # every voxel of rows() holds a key of the table
+                in_cluster = lab[at] >= 0
+                write_ply(stem + ".ply", rows["xyz"].cpu().numpy()[in_cluster], voxel_cluster_colors(lab[at][in_cluster]))
+                info = found.info.cpu().numpy()
+                print("voxel map clustered: %d members, %d components, %d of at least %d voxels (the largest %d), written to %s and %s"
+                      % (info[0], info[1], info[2], min_voxels, info[5], stem + ".txt", stem + ".ply"))
         if world is not None:
             _write_png(args.occupancy_map, OCCUPANCY_PNG[world.state().cpu().numpy()])
             if args.clearance:
