@@ -84,6 +84,11 @@
  *      and the components below a size emptied - the objects of the map and its speckle filter.  stereo_vision.sv.voxel_map_clusters
  *      states the definition in numpy.
  *
+ *  (X) Behind (R): a frame aligned to the voxel map (sv_voxel_align_*) - every row of a frame paired with the nearest voxel mean of (Q)'s
+ *      table and the pairs reduced to the nineteen integers a closed-form rigid fit needs: one round of iterative closest point, so
+ *      that a pose is refined below (R)'s step and in roll and pitch as well.  stereo_vision.sv.voxel_map_align_sums states the definition
+ *      in numpy; voxel_align_solve and voxel_map_align are the fit and the loop around both.
+ *
  * All sv_* functions return SV_OK (0) or a negative sv_status; sv_last_error() gives the text.
  * Nothing in this library calls exit().
  */
@@ -1599,6 +1604,62 @@ int sv_voxel_clusters_device(void *map, size_t map_bytes, const sv_voxel_map_spe
  * wavefront, 32: the link kernel does not compress paths (by default it lowers a member's own parent word to the root its links
  * ended at).  A value outside its range leaves that word as it was.  Returns the groups before. */
 int sv_debug_voxel_clusters(int groups, int stages);
+
+/* ---- (X) a frame aligned to the voxel map: per-frame rows of (I) or (F) + one pose per frame + (Q)'s table -> the sums of one ICP round ---- */
+
+/* (R) answers no finer than its window's step and has no axis for roll and pitch.  This pairs every row of a frame, under the frame's one
+ * pose, with the nearest voxel mean of the map and reduces the pairs to the integers a closed-form rigid fit (Kabsch; about z alone for
+ * four degrees of freedom) needs; the host solves, applies and calls again: iterative closest point.  Doubles in (Q)'s order in front of
+ * the cell, integers behind it: the sums are bitwise reproducible, whatever the schedule.  The map is only read.
+ * stereo_vision.sv.voxel_map_align_sums restates all of it in numpy, voxel_align_origin / voxel_align_solve / voxel_map_align are the
+ * host's part.
+ *
+ *   rows, world, kept, cell : exactly (R)'s, under poses[b]; u the 16-bit offset.  sums[b][0] = inside counts the kept rows.
+ *   positions  integers from here on, in 1/256 of a cell from lo and below 2^28: a kept row stands at p_k = 256 c_k + (u_k >> 8), a voxel
+ *              at q_k = 256 cell_k + ((S_k / n) >> 8), / the integer division - the position (V) slices by.
+ *   candidates the voxels of the up to 27 cells c + d, d in {-1, 0, 1}^3, with 0 <= c_k + d_k < cells_k - a cell outside the box is no
+ *              cell: its "key" would be another cell's or the empty word -, that pass the read-out's filters with n >= max(min_n, 1),
+ *              m >= min_rows, last_seq >= since.  A tombstone of (T) or (W) has n = 0 and is never a partner, whatever min_n is.
+ *   nearest    the candidate with the smallest d2 = sum_k (p_k - q_k)^2, among those the smallest key; d2 <= 3 * 511^2 = 783363.
+ *   pair       a kept row with a nearest candidate and d2 <= max_d2, max_d2 in 0 .. 783363.  For max_d2 <= 256^2 - a max_dist of at
+ *              most one cell - the partner is the nearest voxel mean of the WHOLE map, not only of the 27 cells: a voxel within 256
+ *              units differs by at most one cell per axis.
+ *   sums       int64 [batch][19]: inside, pairs, W = sum w, D = sum w d2, P[3] = sum w (p - o), Q[3] = sum w (q - o), H[9] = sum w
+ *              (p - o)_i (q - o)_j row-major (i the row's axis), over the pairs; o = origin[b], int32 [3] in the positions' unit,
+ *              |o_k| <= 2^30.  64-bit two's complement sums; contract: sum w r^2 < 2^63, r the largest |p - o| or |q - o| - with room
+ *              for any frame of a stereo rig around an origin at the sensor.
+ *   per row    pair_key int64 [batch][cap] and pair_d2 int32 [batch][cap], both or neither: the nearest candidate's key and d2, also
+ *              where d2 > max_d2 and the row is no pair; -1 and -1 for a row that is not kept, a kept row without a candidate, and every
+ *              index at or beyond min(counts[b], cap).
+ *   overflowed for an overflowed map every sum is 0 and every per-row word is -1. */
+
+/* Host only: the bytes of the workspace sv_voxel_align_device needs for `batch` frames of `cap` rows: 19 words per chunk of 256 rows, at
+ * most 512 chunks a frame.  SV_ERR_ARG (bytes untouched) for a NULL bytes, cap < 0 or batch outside 0..65535. */
+int sv_voxel_align_workspace(int cap, int batch, size_t *bytes);
+/* Enqueued on `stream` (a hipStream_t, NULL = the default stream) as two kernels - the pairs and their sums per chunk of rows, the chunks'
+ * sums per frame - and not waited for: nothing is allocated, no host synchronisation is made, no atomic is issued, the map is read only,
+ * and nothing is assumed of what the outputs or the workspace held before.
+ *   map, spec    : (Q)'s buffer and its spec; xyz, dtype, n, counts, cap : as for sv_voxel_map_insert_device
+ *   poses        : double [batch][12] device, 8-byte aligned: frame b's pose, R row-major, then t
+ *   origin       : int32 [batch][3] device, 4-byte aligned
+ *   max_d2       : 0 .. 783363
+ *   min_n, min_rows, since : the filters of sv_voxel_map_rows_device; a min_n below 1 counts as 1
+ *   sums         : int64 [batch][19] device, 8-byte aligned
+ *   pair_key     : int64 [batch][cap] device, 8-byte aligned, and pair_d2 : int32 [batch][cap] device, 4-byte aligned; or both NULL
+ *   workspace    : device, 8-byte aligned, workspace_bytes >= what sv_voxel_align_workspace gives
+ * Every output given is written in full.  Returns SV_OK (nothing enqueued for batch == 0), SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued, the
+ * outputs untouched, the text in sv_last_error(NULL) - for: a bad spec or map as the clear entry of (Q) refuses them; another dtype; cap < 0;
+ * batch outside 0..65535; max_d2 outside 0..783363; with batch > 0 a NULL counts, poses, origin, sums or workspace, and with cap > 0 as well
+ * a NULL xyz; one of pair_key and pair_d2 without the other; xyz not aligned to its element, n, counts, origin or pair_d2 not 4-byte, poses,
+ * sums, pair_key or the workspace not 8-byte aligned; too small a workspace.  These checks run before any HIP call. */
+int sv_voxel_align_device(const void *map, size_t map_bytes, const sv_voxel_map_spec *spec, const void *xyz, int dtype, const int32_t *n, const int32_t *counts,
+                          const double *poses, const int32_t *origin, int batch, int cap, int max_d2, int64_t min_n, int64_t min_rows, int since, int64_t *sums,
+                          int64_t *pair_key, int32_t *pair_d2, void *workspace, size_t workspace_bytes, void *stream);
+/* Test and measurement hook for the call above, process-wide: max_chunks = 0 (the default) leaves the chunks of rows per frame at 512 at
+ * most, 1 .. 512 lowers that, so that a workgroup takes several chunks of a short frame; flags bit 0 makes the score kernel look into every
+ * one of the 27 cells instead of leaving out those that cannot hold the nearest.  The results do not depend on either.  Returns SV_OK, or
+ * SV_ERR_ARG for other values. */
+int sv_debug_voxel_align(int max_chunks, int flags);
 
 /* ---- (A)the reference's exported symbols ------------------------------------------------------------- */
 

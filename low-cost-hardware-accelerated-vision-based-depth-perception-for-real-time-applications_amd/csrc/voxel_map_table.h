@@ -1,6 +1,6 @@
 // The rules that make the world-fixed voxel map one map across its stages - insert and read-out (voxel_map_kernels.hip), match
 // (voxel_match_kernels.hip), carry (voxel_carry_kernels.hip), carve (voxel_carve_kernels.hip), render (voxel_render_kernels.hip), flatten
-// (voxel_flatten_kernels.hip), clusters (voxel_cluster_kernels.hip) -, written down once: the buffer's parts, the entry's words, the hash, the two probes, a row's way from the
+// (voxel_flatten_kernels.hip), clusters (voxel_cluster_kernels.hip), align (voxel_align_kernels.hip) -, written down once: the buffer's parts, the entry's words, the hash, the two probes, a row's way from the
 // frame into a cell, and a voxel's centre and height.  Plain inline functions and named constants; what a stage does with an entry it
 // has found stays in the stage.  The layout is voxel_map_kernels.h's; the definitions are include/stereo_vision_hip.h (Q)'s.  The
 // per-frame voxel cloud (voxel_kernels.hip) has another entry and another life cycle and shares nothing with this.
@@ -109,6 +109,11 @@ __device__ __forceinline__ long long vmap_find(const unsigned long long *table, 
     }
     return -1;  // a full table without the key
 }
+
+// vmap_find's sequence by its steps, for a caller that keeps several probes in flight and steps them side by side: whether a probe for
+// `key` that saw `seen` in its slot goes on - it ends at the key and at an empty key; the caller counts to `slots` -, and the slot behind h.
+__host__ __device__ inline bool vmap_probe_goes_on(unsigned long long seen, unsigned long long key) { return seen != key && seen != VMAP_EMPTY; }
+__host__ __device__ inline uint32_t vmap_next_slot(int log2_slots, uint32_t h) { return (h + 1) & (uint32_t)(((size_t)1 << log2_slots) - 1); }
 
 // The entry of `key`, claimed where the map held none: the same probe sequence with a CAS on the key word that moves on at someone
 // else's key and never waits.  A lane looks at the overflow flag every sixteenth probe and gives up where it is set - a full table of a

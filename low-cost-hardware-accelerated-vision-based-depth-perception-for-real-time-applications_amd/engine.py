@@ -657,6 +657,11 @@ def _signatures():
             "sv_voxel_clusters_device": (ci, [vp, sz, vm, P(SvVoxelClusterSpec), om, vp, i64, i64, ci, vp, vp, vp, vp, sz, vp]),
             "sv_debug_voxel_clusters": (ci, [ci, ci]),
         },
+        "voxel_align": {  # (X)
+            "sv_voxel_align_workspace": (ci, [ci, ci, P(sz)]),
+            "sv_voxel_align_device": (ci, [vp, sz, vm, vp, ci, vp, vp, vp, vp, ci, ci, ci, i64, i64, ci, vp, vp, vp, vp, sz, vp]),
+            "sv_debug_voxel_align": (ci, [ci, ci]),
+        },
     }
 
 
@@ -669,6 +674,7 @@ _GROUP_NEEDS["voxel_carve"] = ("voxel_map",)
 _GROUP_NEEDS["voxel_render"] = ("voxel_map",)
 _GROUP_NEEDS["voxel_flatten"] = ("voxel_map", "occupancy_map")
 _GROUP_NEEDS["voxel_clusters"] = ("voxel_map", "occupancy_map")
+_GROUP_NEEDS["voxel_align"] = ("voxel_map",)
 _bound_groups = set()
 
 
@@ -2536,6 +2542,129 @@ def debug_voxel_clusters(groups=0, stages=0):
     16: no combining of equal destinations over the wavefront, 32: no path compression in the link kernel.  Returns the groups before.
     Process-wide; a test and measurement hook."""
     return int(voxel_clusters_lib().sv_debug_voxel_clusters(int(groups), int(stages)))
+
+
+def voxel_align_lib():
+    """The library with the signatures of group (X) declared."""
+    return _bind("voxel_align")
+
+
+class VoxelAlignResult(_Result):
+    """What voxel_map_align_sums returns, tensors on the map's device: sums int64 [B,19] (stereo_vision.sv.VOXEL_ALIGN_SUMS names the
+    words), pair_key int64 [B,cap] and pair_d2 int32 [B,cap] (both None where not asked for).  voxel_map_align fills the rest, host
+    numpy: poses float64 [B,12], ok bool [B], rounds, pairs int64 [rounds,B], rms float64 [rounds,B]."""
+    __slots__ = ("sums", "pair_key", "pair_d2", "poses", "ok", "rounds", "pairs", "rms")
+
+
+def _voxel_align_frames(buf, params, xyz, n, counts, min_n, min_rows, since):
+    """The checks of a frame batch that voxel_map_align_sums and voxel_map_align share -> (spec, the map's bytes, xyz, n, counts), the
+    tensors contiguous."""
+    import torch
+    spec = voxel_map_spec(params)
+    nbytes = _voxel_map_buffer(buf, spec)
+    dev = buf.device
+    if not (isinstance(xyz, torch.Tensor) and xyz.device == dev and xyz.dtype in (torch.float32, torch.float64) and xyz.dim() == 3 and xyz.shape[2] == 3):
+        raise ValueError("xyz must be a float32 or float64 tensor [B,cap,3] on the map's device")
+    B, cap = int(xyz.shape[0]), int(xyz.shape[1])
+    for t, name, dtype, shape in ((n, "n", torch.int32, (B, cap)), (counts, "counts", torch.int32, (B,))):
+        if t is None and name != "counts":
+            continue
+        if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dtype and tuple(t.shape) == shape):
+            raise ValueError("%s must be a %s tensor %s on the map's device" % (name, str(dtype).replace("torch.", ""), list(shape)))
+    if B > 65535:
+        raise ValueError("at most 65535 frames per call, got %d" % B)
+    for v, what in ((min_n, "min_n"), (min_rows, "min_rows")):
+        if isinstance(v, bool) or int(v) != v or not -2 ** 63 <= v < 2 ** 63:
+            raise ValueError("%s must be an integer, got %r" % (what, v))
+    if isinstance(since, bool) or int(since) != since or not -2 ** 31 <= since < 2 ** 31:
+        raise ValueError("since must be a 32-bit integer, got %r" % (since,))
+    return spec, nbytes, xyz.contiguous(), None if n is None else n.contiguous(), counts.contiguous()
+
+
+def _voxel_align_origin(origin, B, dev):
+    """origin as a contiguous int32 [B,3] tensor on dev: a numpy array of integers within +-2^30 - uploaded once - or such a tensor."""
+    import torch
+    if isinstance(origin, torch.Tensor):
+        if origin.device != dev or origin.dtype != torch.int32 or tuple(origin.shape) != (B, 3):
+            raise ValueError("origin must be an int32 tensor [%d,3] on the device (%s) of the map" % (B, dev))
+        return origin.contiguous()
+    o = np.asarray(origin)
+    if o.shape != (B, 3) or o.dtype.kind not in "iu" or (np.abs(o.astype(np.int64)) > 2 ** 30).any():
+        raise ValueError("origin must be integers [%d,3] within +-2^30, got %s %s" % (B, o.dtype, o.shape))
+    return torch.from_numpy(np.ascontiguousarray(o, dtype=np.int32)).to(dev)
+
+
+def voxel_map_align_sums(buf, params, xyz, n, counts, poses, origin, max_dist=1.0, min_n=1, min_rows=1, since=0, want_rows=False, out=None, workspace=None):
+    """The rows of B frames - xyz CUDA float32 or float64 [B,cap,3], n int32 [B,cap] or None, counts int32 [B], as voxel_map_insert takes
+    them -, each under its one pose (float64 [B,12] or [B,4]; numpy or a tensor on the map's device), paired with the nearest voxel
+    means of the map in `buf`, and the pairs' sums about origin (integers [B,3] in 1/256 of a cell from lo,
+    stereo_vision.sv.voxel_align_origin; numpy or an int32 tensor on the device): the definition of
+    stereo_vision.sv.voxel_map_align_sums on the GPU, bit for bit (sv_voxel_align_device: two kernels, no atomics).  max_dist in cells;
+    min_n, min_rows and since are the read-out's filters.  want_rows=True also returns the nearest voxel's key and d2 per row.  out: a
+    VoxelAlignResult of an earlier call of the same shape to write into; workspace: an int64 tensor to use (None: torch's allocator,
+    which keeps it for the next call of the shape).  The map is not changed and nothing is read back.  -> VoxelAlignResult; enqueued on
+    torch's current stream, not waited for."""
+    import torch
+    from .stereo_vision.sv import voxel_align_max_d2
+    max_d2 = voxel_align_max_d2(max_dist)
+    spec, nbytes, xyz, n, counts = _voxel_align_frames(buf, params, xyz, n, counts, min_n, min_rows, since)
+    dev = buf.device
+    B, cap = int(xyz.shape[0]), int(xyz.shape[1])
+    p = voxel_map_poses(poses, dev)
+    if p.shape[0] != B:
+        raise ValueError("poses must hold one pose per frame: %d, got %d" % (B, p.shape[0]))
+    o = _voxel_align_origin(origin, B, dev)
+    res = out if out is not None else VoxelAlignResult(sums=torch.empty((B, 19), dtype=torch.int64, device=dev))
+    if want_rows and res.pair_key is None:
+        res.pair_key, res.pair_d2 = torch.empty((B, cap), dtype=torch.int64, device=dev), torch.empty((B, cap), dtype=torch.int32, device=dev)
+    if tuple(res.sums.shape) != (B, 19) or (want_rows and tuple(res.pair_key.shape) != (B, cap)):
+        raise ValueError("out is of another shape")
+    if B == 0:  # nothing to enqueue
+        return res
+    L = voxel_align_lib()
+    need = ctypes.c_size_t()
+    _check(L.sv_voxel_align_workspace(cap, B, ctypes.byref(need)), "sv_voxel_align_workspace")
+    ws = workspace if workspace is not None else torch.empty((max(need.value // 8, 1),), dtype=torch.int64, device=dev)
+    rows = [res.pair_key, res.pair_d2] if want_rows else [None, None]
+    with torch.cuda.device(dev):
+        rc = L.sv_voxel_align_device(buf.data_ptr(), nbytes, ctypes.byref(spec), _ptr(xyz), 0 if xyz.dtype == torch.float32 else 1, _ptr(n), counts.data_ptr(),
+                                     p.data_ptr(), o.data_ptr(), B, cap, max_d2, int(min_n), int(min_rows), int(since), res.sums.data_ptr(),
+                                     *[None if t is None else t.data_ptr() for t in rows], ws.data_ptr(), ws.numel() * 8, torch.cuda.current_stream(dev).cuda_stream)
+    _check(rc, "sv_voxel_align_device")
+    return res  # ws goes back to torch's allocator, which hands it out again on this stream only: behind the kernels
+
+
+def voxel_map_align(buf, params, xyz, n, counts, poses, iterations=10, max_dist=1.0, dof=6, min_pairs=6, eps=(1e-5, 1.0 / 256), min_n=1, min_rows=1, since=0):
+    """Iterative closest point of B frames against the map in `buf` - stereo_vision.sv.voxel_map_align with the sums from the device: per
+    round the origin from the current poses, voxel_map_align_sums, the B x 19 words read back - the stage's one wait, once per round -
+    and stereo_vision.sv.voxel_align_solve on them, until every fitted frame's step is below eps or `iterations` rounds are done.  The
+    fit and the loop are the numpy definition's own functions on equal sums, so the poses, ok, rounds, pairs and rms equal the CPU
+    path's bit for bit.  poses: the start, float64 [B,12] or [B,4], numpy or a tensor.  -> VoxelAlignResult with sums (the last round's,
+    on the device), poses float64 numpy [B,12], ok, rounds, pairs and rms."""
+    import torch
+    from .stereo_vision.sv import voxel_align_loop, voxel_align_max_d2, voxel_map_pose_words
+    voxel_align_max_d2(max_dist)
+    _, _, xyz, n, counts = _voxel_align_frames(buf, params, xyz, n, counts, min_n, min_rows, since)
+    B = int(xyz.shape[0])
+    start = voxel_map_pose_words(poses.cpu().numpy() if isinstance(poses, torch.Tensor) else poses) if B else np.zeros((0, 12))
+    if start.shape[0] != B:
+        raise ValueError("poses must hold one pose per frame: %d, got %d" % (B, start.shape[0]))
+    res = VoxelAlignResult(sums=torch.zeros((B, 19), dtype=torch.int64, device=buf.device))
+
+    def sums_of(cur, origin):
+        voxel_map_align_sums(buf, params, xyz, n, counts, cur, origin, max_dist, min_n, min_rows, since, out=res)
+        return res.sums.cpu().numpy()  # the wait of the round
+
+    got = voxel_align_loop(sums_of, params, start, iterations, dof, min_pairs, eps)
+    res.poses, res.ok, res.rounds, res.pairs, res.rms = got["poses"], got["ok"], got["rounds"], got["pairs"], got["rms"]
+    return res
+
+
+def debug_voxel_align(max_chunks=0, skip=True):
+    """sv_debug_voxel_align: the chunks of rows per frame at most (0: the default, 512; 1 .. 512 lowers it, so that a workgroup takes
+    several chunks) and whether the score kernel leaves out the cells that cannot hold the nearest voxel.  The results depend on
+    neither.  Process-wide; a test and measurement hook."""
+    return int(voxel_align_lib().sv_debug_voxel_align(int(max_chunks), 0 if skip else 1))
 
 
 def host_support_filter(params, dcan, width, height, threads=0, lattice=False):

@@ -42,7 +42,7 @@ import numpy as np
 
 from .engine import (SvParams, StereoEngine, StereoError, box_positions_from_disparity, box_spec, cloud_spec, compact_cloud_from_disparity,
                      ground_from_disparity, ground_spec, lib, occupancy_from_disparity, occupancy_fuse, occupancy_match, occupancy_clearance, clearance_paths, cost_cells, cost_routes, frontier_cells, frontier_clusters, occupancy_cost_to_goal, occupancy_view, occupancy_spec, pinned_array, reproject, split_clouds, stixel_spec, stixels_from_disparity,
-                     top_view_from_disparity, top_view_spec, split_voxel_clouds, voxel_cloud_from_disparity, voxel_map_carry, voxel_map_clear, voxel_map_insert, voxel_map_match, voxel_map_new,
+                     top_view_from_disparity, top_view_spec, split_voxel_clouds, voxel_cloud_from_disparity, voxel_map_align, voxel_map_carry, voxel_map_clear, voxel_map_insert, voxel_map_match, voxel_map_new,
                      voxel_map_rows, voxel_map_stats, voxel_spec)
 from .stereo_vision.sv import CAMERA_TO_VEHICLE, DEFAULT_CALIBRATION  # noqa: F401 (CAMERA_TO_VEHICLE: re-exported for top_view)
 from .stereo_vision.sv import free_space_points, ground_pose
@@ -453,7 +453,8 @@ class VoxelMap:
     flatten() is group (V), stereo_vision.sv.voxel_map_flatten: the voxels sliced by height above the floor and written out as the
     logodds and last_seen of a flat map, which OccupancyMap.load_voxels takes.  clusters() and despeckle() are group (W),
     stereo_vision.sv.voxel_map_clusters: the connected components of the voxels - a row of counts, sums and a box per object, a label per
-    voxel - and the components below a size emptied."""
+    voxel - and the components below a size emptied.  align() is group (X), stereo_vision.sv.voxel_map_align: a frame's pose refined by
+    iterative closest point against the voxels' means, below localize's step and in roll and pitch as well."""
 
     def __init__(self, lo, hi, size, capacity, device="cuda"):
         import torch
@@ -529,6 +530,26 @@ class VoxelMap:
         res = self.match(xyz, n, counts, _sv.voxel_map_pose(window[..., 0], window[..., 1], window[..., 3], window[..., 2]), min_n, min_rows, since)
         best = res.best.cpu().numpy().astype(np.int64)
         return window[np.arange(len(g)), np.maximum(best, 0)], res  # row 0 is the guess
+
+    def align(self, xyz, n, counts, poses, iterations=10, max_dist=1.0, dof=6, min_pairs=6, eps=(1e-5, 1.0 / 256), min_n=1, min_rows=1, since=0):
+        """Refines one pose per frame by iterative closest point against the map as it stands (include/stereo_vision_hip.h (X),
+        stereo_vision.sv.voxel_map_align): xyz, n and counts as for update, poses float64 [B,12] or [B,4] - the start: localize's best,
+        or the odometry's.  Per round every row is paired with the nearest voxel mean within max_dist cells and the pairs are fitted in
+        closed form: dof=6 all of the rotation and the translation, dof=4 yaw and the translation.  -> (float64 numpy [B,12], the
+        refined poses; engine.VoxelAlignResult with sums, poses, ok, rounds, pairs and rms).  A frame the last round could not fit (ok
+        False: fewer than min_pairs pairs, an overflowed map) keeps the pose it had.  Waits once per round, for B x 19 words.  The idiom:
+        g, _ = vm.localize(...); poses, _ = vm.align(xyz, n, counts, sv.voxel_map_pose(g[:, 0], g[:, 1], g[:, 3], g[:, 2]));
+        vm.update(xyz, color, n, counts, poses).  The map is not changed."""
+        import torch
+        from .engine import VoxelAlignResult
+        if self._state is None:
+            res = voxel_map_align(self.buffer, self.params, xyz, n, counts, poses, iterations, max_dist, dof, min_pairs, eps, min_n, min_rows, since)
+            return res.poses, res
+        host = [None if t is None else (t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)) for t in (xyz, n, counts, poses)]
+        got = _sv.voxel_map_align(self._state, *host, iterations=iterations, max_dist=max_dist, dof=dof, min_pairs=min_pairs, eps=eps, min_n=min_n,
+                                  min_rows=min_rows, since=since)
+        res = VoxelAlignResult(**dict(got, sums=torch.from_numpy(got["sums"])))
+        return res.poses, res
 
     def stats(self):
         """{"claimed", "dropped", "overflowed"}: the voxels the map holds, the rows it dropped, whether it ever held more than its

@@ -128,6 +128,14 @@ rig.VoxelMap.clusters / .despeckle on the GPU): the 6-, 18- or 26-connected comp
 absolute floor or over the flatten's, a row of counts, sums and a box per component in ascending least key, a label per voxel, and the
 components below a size emptied - the objects of the map and its speckle filter in three dimensions.  The reference has no counterpart
 (DESIGN.md §8).
+
+voxel_map_align_sums (with voxel_map_align_sums_brute, the plain loop per row) is the definition of a frame aligned to the voxel map
+(sv_voxel_align_* of include/stereo_vision_hip.h (X); engine.voxel_map_align_sums / voxel_map_align and rig.VoxelMap.align on the GPU):
+every row of a frame paired with the nearest voxel mean of the map, and the pairs reduced to the nineteen integers a closed-form rigid
+fit needs.  voxel_align_origin, voxel_align_solve and voxel_map_align are the host's part of iterative closest point - the origin the
+sums are taken about, the fit (Kabsch for six degrees of freedom, about z alone for four) and the loop -, shared by the CPU and the GPU
+path, so that both give the same poses bit for bit.  It refines a pose below voxel_map_match's step, and in roll and pitch.  The
+reference has no counterpart.
 """
 import argparse
 import ctypes
@@ -1694,6 +1702,294 @@ def voxel_map_match(map_state, xyz, n, counts, poses, min_n=1, min_rows=1, since
     at = np.arange(B)
     return dict(out, best=best.astype(np.int32), best_weight=out["weight"][at, best] if B else np.zeros(0, np.int64),
                 best_d2=out["d2"][at, best] if B else np.zeros(0, np.int64))
+
+
+VOXEL_ALIGN_BATCH_MAX = 65535
+VOXEL_ALIGN_D2_MAX = 3 * 511 ** 2  # 783363: the largest d2 between a row and a voxel of its 27 cells
+VOXEL_ALIGN_ORIGIN_MAX = 2 ** 30   # |origin| per axis at most: p - o and q - o stay 32-bit numbers
+VOXEL_ALIGN_SUMS = ("inside", "pairs", "W", "D", "Px", "Py", "Pz", "Qx", "Qy", "Qz", "Hxx", "Hxy", "Hxz", "Hyx", "Hyy", "Hyz", "Hzx", "Hzy", "Hzz")  # the 19 words
+VOXEL_ALIGN_OFFSETS = tuple((o % 3 - 1, (o // 3) % 3 - 1, o // 9 - 1) for o in range(27))  # (dx, dy, dz) of the 27 cells
+
+
+def voxel_align_max_d2(max_dist):
+    """max_d2 = min(783363, int((256 max_dist)^2)) of a max_dist in cells: finite and >= 0 (ValueError)."""
+    try:
+        m = float(max_dist)
+    except (TypeError, ValueError):
+        raise ValueError("max_dist must be a finite number of cells >= 0, got %r" % (max_dist,))
+    if not np.isfinite(m) or m < 0:
+        raise ValueError("max_dist must be a finite number of cells >= 0, got %r" % (max_dist,))
+    return min(VOXEL_ALIGN_D2_MAX, int((256.0 * min(m, 4.0)) ** 2))
+
+
+def _voxel_align_setup(map_state, xyz, n, counts, poses, origin):
+    """The checks voxel_map_align_sums and its brute form share -> (xyz, n, counts, poses [B,12], origin int64 [B,3])."""
+    xyz = np.asarray(xyz)
+    if xyz.dtype not in (np.float32, np.float64) or xyz.ndim != 3 or xyz.shape[2] != 3:
+        raise ValueError("xyz must be float32 or float64 [B,cap,3], got %s %s" % (xyz.dtype, xyz.shape))
+    B, cap = xyz.shape[:2]
+    if B > VOXEL_ALIGN_BATCH_MAX:
+        raise ValueError("at most 65535 frames per call, got %d" % B)
+    counts = np.asarray(counts)
+    if counts.shape != (B,):
+        raise ValueError("counts must be [%d], got %s" % (B, counts.shape))
+    if n is not None and np.asarray(n).shape != (B, cap):
+        raise ValueError("n must be [B,cap] or None")
+    p = np.asarray(poses, np.float64)
+    if p.ndim != 2 or p.shape[0] != B or p.shape[1] not in (4, 12):
+        raise ValueError("poses must be float64 [%d,12] or [%d,4], got %s" % (B, B, p.shape))
+    p = voxel_map_pose_words(p) if B else np.zeros((0, 12))
+    o = np.asarray(origin)
+    if o.shape != (B, 3) or o.dtype.kind not in "iu" or (np.abs(o.astype(np.int64)) > VOXEL_ALIGN_ORIGIN_MAX).any():
+        raise ValueError("origin must be integers [%d,3] within +-2^30, got %s %s" % (B, o.dtype, o.shape))
+    return xyz, None if n is None else np.asarray(n), counts, p, o.astype(np.int64)
+
+
+def _voxel_align_voxels(map_state, min_n, min_rows, since):
+    """(key, q) of the voxels a row may pair with, in ascending key: q int64 [V,3] = 256 cell + ((S // n) >> 8)."""
+    sel = (map_state["n"] >= max(min_n, 1)) & (map_state["m"] >= min_rows) & (map_state["last_seq"] >= since)
+    key, n, S = map_state["key"][sel], map_state["n"][sel], map_state["S"][sel]
+    by_key = np.argsort(key, kind="stable")
+    key, n, S = key[by_key], n[by_key], S[by_key]
+    cell = np.stack([key & 0xFFFFF, (key >> 20) & 0xFFFFF, (key >> 40) & 0xFFFFF], -1)
+    return key, 256 * cell + ((S // n[:, None]) >> 8)
+
+
+def _voxel_align_rows(params, X, wt, pose):
+    """The kept rows of one frame under `pose` -> (their indices, c int64 [K,3], p int64 [K,3]): voxel_map_match's rules."""
+    lo, hi, size, cells = np.array(params["lo"]), np.array(params["hi"]), np.float64(params["size"]), np.array(params["cells"], np.int64)
+    x, y, z = X[:, 0], X[:, 1], X[:, 2]
+    with np.errstate(invalid="ignore", over="ignore"):
+        Pw = np.stack([((pose[3 * k] * x + pose[3 * k + 1] * y) + pose[3 * k + 2] * z) + pose[9 + k] for k in range(3)], -1)
+        keep = ((lo < Pw) & (Pw < hi)).all(-1) & (wt > 0)
+    t = (Pw[keep] - lo) / size
+    c = np.minimum(t.astype(np.int64), cells - 1)
+    u = np.minimum(((t - c.astype(np.float64)) * 65536.0).astype(np.int64), 65535)
+    return np.flatnonzero(keep), c, 256 * c + (u >> 8)
+
+
+def _voxel_align_add(sums, wt, p, q, d2, o):
+    """The pairs of one frame added up: 64-bit two's complement sums."""
+    with np.errstate(over="ignore"):
+        dp, dq = p - o, q - o
+        sums[1], sums[2], sums[3] = len(wt), wt.sum(), (wt * d2).sum()
+        sums[4:7], sums[7:10] = (wt[:, None] * dp).sum(0), (wt[:, None] * dq).sum(0)
+        sums[10:19] = ((wt[:, None] * dp)[:, :, None] * dq[:, None, :]).sum(0).reshape(9)
+
+
+def voxel_map_align_sums(map_state, xyz, n, counts, poses, origin, max_dist=1.0, min_n=1, min_rows=1, since=0):
+    """The definition of include/stereo_vision_hip.h (X) in numpy: the rows of B frames, each under its one pose, paired with the nearest
+    voxels of a voxel map, and the pairs' sums - what one round of iterative closest point needs.  map_state, xyz (float32 or float64
+    [B,cap,3]), n (int32 [B,cap], or None: every weight 1) and counts (int32 [B]) are voxel_map_insert's; poses float64 [B,12] in
+    voxel_map_pose's layout ([B,4] goes through voxel_map_pose_words); origin integers [B,3] in 1/256 of a cell from lo, |o| <= 2^30
+    (voxel_align_origin); B <= 65535 (ValueError).  The map is not changed.
+    -> {"sums": int64 [B,19], "pair_key": int64 [B,cap], "pair_d2": int32 [B,cap]}.
+
+      rows, world, kept, cell, offset   exactly voxel_map_match's: the insert's transform in double and in that order, strict lo < Pw <
+              hi, w > 0, c = min(int(t), cells - 1), u = min(int((t - c) * 65536), 65535).  sums[b][0] = inside counts the kept rows.
+      positions  integers from here on, in 1/256 of a cell from lo and below 2^28: a kept row stands at p_k = 256 c_k + (u_k >> 8), a
+              voxel at q_k = 256 cell_k + ((S_k // n) >> 8) - what voxel_map_flatten slices by.
+      candidates the voxels of the up to 27 cells c + d, d in {-1, 0, 1}^3, 0 <= c_k + d_k < cells_k, that pass voxel_map_rows' filters
+              with n >= max(min_n, 1): a tombstone that voxel_map_carve or a despeckle left has n = 0 and is never a partner.
+      nearest the candidate with the smallest d2 = sum_k (p_k - q_k)^2, then the smallest key; d2 <= 3 * 511^2 = 783363.
+      pair    a kept row with a nearest candidate and d2 <= max_d2 = min(783363, int((256 max_dist)^2)); max_dist in cells, finite and
+              >= 0 (ValueError).  For max_dist <= 1 the partner is the nearest voxel mean of the whole map, not only of the 27 cells: a
+              voxel within 256 units differs by at most one cell per axis.
+      sums    inside, pairs, W = sum w, D = sum w d2, P[3] = sum w (p - o), Q[3] = sum w (q - o), H[9] = sum w (p - o)_i (q - o)_j
+              row-major, over the pairs; 64-bit two's complement sums.  Contract: sum w r^2 < 2^63, r the largest |p - o| or |q - o|.
+      per row pair_key, pair_d2: the nearest candidate's key and d2, also where d2 > max_d2 and the row is no pair; -1 and -1 for a row
+              that is not kept, a kept row with no candidate, and every index at or beyond min(counts[b], cap).
+    For an overflowed map every sum is 0 and every per-row word is -1."""
+    max_d2 = voxel_align_max_d2(max_dist)
+    xyz, n, counts, poses, origin = _voxel_align_setup(map_state, xyz, n, counts, poses, origin)
+    B, cap = xyz.shape[:2]
+    out = {"sums": np.zeros((B, 19), np.int64), "pair_key": np.full((B, cap), -1, np.int64), "pair_d2": np.full((B, cap), -1, np.int32)}
+    if map_state["overflowed"]:
+        return out
+    w = map_state["params"]
+    cells = np.array(w["cells"], np.int64)
+    vkey, vq = _voxel_align_voxels(map_state, min_n, min_rows, since)
+    if not len(vkey):  # a stand-in that no cell's key equals
+        vkey, vq = np.array([-1], np.int64), np.zeros((1, 3), np.int64)
+    for b in range(B):
+        rows = int(min(max(int(counts[b]), 0), cap))
+        wt = np.ones(rows, np.int64) if n is None else n[b, :rows].astype(np.int64)
+        at_row, c, p = _voxel_align_rows(w, xyz[b, :rows].astype(np.float64), wt, poses[b])
+        K = len(at_row)
+        out["sums"][b, 0] = K
+        best_d2, best_key, best_q = np.full(K, VOXEL_ALIGN_D2_MAX + 1, np.int64), np.full(K, -1, np.int64), np.zeros((K, 3), np.int64)
+        for d in VOXEL_ALIGN_OFFSETS:
+            cc = c + np.array(d, np.int64)
+            on = ((cc >= 0) & (cc < cells)).all(-1)  # before a key is formed: a cell of -1 or of `cells` is no cell
+            key = np.where(on, cc[:, 0] | (cc[:, 1] << 20) | (cc[:, 2] << 40), -2)
+            at = np.minimum(np.searchsorted(vkey, key), len(vkey) - 1)
+            q = vq[at]
+            d2 = ((p - q) ** 2).sum(1)
+            take = on & (vkey[at] == key) & ((best_key < 0) | (d2 < best_d2) | ((d2 == best_d2) & (key < best_key)))
+            best_d2[take], best_key[take], best_q[take] = d2[take], key[take], q[take]
+        have = best_key >= 0
+        out["pair_key"][b, at_row[have]] = best_key[have]
+        out["pair_d2"][b, at_row[have]] = best_d2[have]
+        pair = have & (best_d2 <= max_d2)
+        _voxel_align_add(out["sums"][b], wt[at_row[pair]], p[pair], best_q[pair], best_d2[pair], origin[b])
+    return out
+
+
+def voxel_map_align_sums_brute(map_state, xyz, n, counts, poses, origin, max_dist=1.0, min_n=1, min_rows=1, since=0):
+    """voxel_map_align_sums by a Python loop per row over all voxels of the map that differ from the row's cell by at most one cell per
+    axis: Python floats and ints only, no key is formed for a neighbour cell and nothing is looked up.  The independent model."""
+    max_d2 = voxel_align_max_d2(max_dist)
+    xyz, n, counts, poses, origin = _voxel_align_setup(map_state, xyz, n, counts, poses, origin)
+    B, cap = xyz.shape[:2]
+    out = {"sums": np.zeros((B, 19), np.int64), "pair_key": np.full((B, cap), -1, np.int64), "pair_d2": np.full((B, cap), -1, np.int32)}
+    if map_state["overflowed"]:
+        return out
+    w = map_state["params"]
+    voxels = []
+    for key, vn, S, m, last in zip(map_state["key"].tolist(), map_state["n"].tolist(), map_state["S"].tolist(), map_state["m"].tolist(), map_state["last_seq"].tolist()):
+        if vn >= max(min_n, 1) and m >= min_rows and last >= since:
+            cell = [(key >> (20 * k)) & 0xFFFFF for k in range(3)]
+            voxels.append((key, cell, [256 * cell[k] + ((S[k] // vn) >> 8) for k in range(3)]))
+    wrap = lambda v: (v + 2 ** 63) % 2 ** 64 - 2 ** 63  # noqa: E731
+    for b in range(B):
+        pose, o = [float(v) for v in poses[b]], [int(v) for v in origin[b]]
+        sums = [0] * 19
+        for i in range(max(0, min(int(counts[b]), cap))):
+            wt = 1 if n is None else int(n[b, i])
+            if wt <= 0:
+                continue
+            x, y, z = (float(v) for v in xyz[b, i])
+            c, p = [], []
+            for k in range(3):
+                with np.errstate(all="ignore"):
+                    Pw = float(((np.float64(pose[3 * k]) * x + np.float64(pose[3 * k + 1]) * y) + np.float64(pose[3 * k + 2]) * z) + np.float64(pose[9 + k]))
+                if not (w["lo"][k] < Pw < w["hi"][k]):
+                    break
+                t = (Pw - w["lo"][k]) / w["size"]
+                c.append(min(int(t), w["cells"][k] - 1))
+                p.append(256 * c[k] + (min(int((t - float(c[k])) * 65536.0), 65535) >> 8))
+            if len(c) < 3:
+                continue
+            sums[0] += 1
+            best = None
+            for key, cell, q in voxels:
+                if all(abs(cell[k] - c[k]) <= 1 for k in range(3)):
+                    d2 = sum((p[k] - q[k]) ** 2 for k in range(3))
+                    if best is None or (d2, key) < best[:2]:
+                        best = (d2, key, q)
+            if best is None:
+                continue
+            out["pair_key"][b, i], out["pair_d2"][b, i] = best[1], best[0]
+            if best[0] <= max_d2:
+                dp, dq = [p[k] - o[k] for k in range(3)], [best[2][k] - o[k] for k in range(3)]
+                sums[1] += 1
+                sums[2] += wt
+                sums[3] += wt * best[0]
+                for k in range(3):
+                    sums[4 + k] += wt * dp[k]
+                    sums[7 + k] += wt * dq[k]
+                    for j in range(3):
+                        sums[10 + 3 * k + j] += wt * dp[k] * dq[j]
+        out["sums"][b] = [wrap(v) for v in sums]
+    return out
+
+
+def voxel_align_origin(params, poses):
+    """int32 [B,3]: the origin the sums of voxel_map_align_sums are taken about - floor((t - lo) / size * 256) of each pose's translation,
+    in 1/256 of a cell from lo, clamped into +-2^30 (0 for a word that is not finite).  An origin at the sensor keeps the sums small."""
+    p = voxel_map_pose_words(poses) if len(np.asarray(poses)) else np.zeros((0, 12))
+    with np.errstate(invalid="ignore", over="ignore"):
+        o = np.floor((p[:, 9:] - np.array(params["lo"])) / np.float64(params["size"]) * 256.0)
+    o = np.where(np.isfinite(o), o, 0.0)
+    return np.clip(o, -VOXEL_ALIGN_ORIGIN_MAX, VOXEL_ALIGN_ORIGIN_MAX).astype(np.int32)
+
+
+def voxel_align_solve(sums, poses, origin, params, dof=6, min_pairs=6):
+    """The closed-form rigid fit of one round: from the sums of voxel_map_align_sums, the poses they were taken under and their origin
+    -> (poses' float64 [B,12], ok bool [B], step float64 [B,2]).  The centred cross-covariance W H_ij - P_i Q_j is formed exactly in
+    Python integers and then divided by W in double.  dof=6: Kabsch - the SVD U S V^T of the centred H, R_d = V diag(1, 1, det(V U^T))
+    U^T; dof=4: the rotation about z alone, by atan2(H01 - H10, H00 + H11).  t_d = Q / W - R_d P / W, and the new pose is (R_d R, R_d (t -
+    X_o) + X_o + t_d size / 256) with X_o = lo + o size / 256.  step = (the angle of R_d in radians, |t_d| in cells).  A frame with pairs
+    < min_pairs, or whose sums give no finite fit, keeps its pose: ok False and step 0 for it."""
+    if dof not in (4, 6) or isinstance(dof, bool):
+        raise ValueError("dof must be 6 (all of the rotation) or 4 (yaw only), got %r" % (dof,))
+    if isinstance(min_pairs, bool) or int(min_pairs) != min_pairs:
+        raise ValueError("min_pairs must be an integer, got %r" % (min_pairs,))
+    sums, poses = np.asarray(sums), voxel_map_pose_words(poses) if len(np.asarray(poses)) else np.zeros((0, 12))
+    B = len(poses)
+    origin = np.asarray(origin)
+    if sums.shape != (B, 19) or origin.shape != (B, 3):
+        raise ValueError("sums must be [%d,19] and origin [%d,3], got %s and %s" % (B, B, sums.shape, origin.shape))
+    lo, size = np.array(params["lo"]), np.float64(params["size"])
+    out, ok, step = poses.copy(), np.zeros(B, bool), np.zeros((B, 2))
+    for b in range(B):
+        s = [int(v) for v in sums[b]]
+        W = s[2]
+        if s[1] < max(int(min_pairs), 1) or W <= 0:
+            continue
+        P, Q = s[4:7], s[7:10]
+        H = np.array([[(W * s[10 + 3 * i + j] - P[i] * Q[j]) / W for j in range(3)] for i in range(3)])  # exact numerators, one rounding each
+        if dof == 6:
+            try:
+                U, _, Vt = np.linalg.svd(H)
+            except np.linalg.LinAlgError:
+                continue
+            V = Vt.T
+            Rd = V @ np.diag([1.0, 1.0, 1.0 if np.linalg.det(V @ U.T) > 0 else -1.0]) @ U.T
+            axis = np.array([Rd[2, 1] - Rd[1, 2], Rd[0, 2] - Rd[2, 0], Rd[1, 0] - Rd[0, 1]])
+            angle = float(np.arctan2(0.5 * np.sqrt((axis * axis).sum()), 0.5 * (np.trace(Rd) - 1.0)))
+        else:
+            theta = float(np.arctan2(H[0, 1] - H[1, 0], H[0, 0] + H[1, 1]))
+            c, sn = np.cos(theta), np.sin(theta)
+            Rd, angle = np.array([[c, -sn, 0.0], [sn, c, 0.0], [0.0, 0.0, 1.0]]), abs(theta)
+        td = np.array([Q[k] / W for k in range(3)]) - Rd @ np.array([P[k] / W for k in range(3)])
+        Xo = lo + origin[b].astype(np.float64) * size / 256.0
+        new = np.concatenate([(Rd @ poses[b, :9].reshape(3, 3)).reshape(9), Rd @ (poses[b, 9:] - Xo) + Xo + td * size / 256.0])
+        if not np.isfinite(new).all():
+            continue
+        out[b], ok[b], step[b] = new, True, (angle, float(np.sqrt((td * td).sum())) / 256.0)
+    return out, ok, step
+
+
+def voxel_align_loop(sums_of, params, poses, iterations=10, dof=6, min_pairs=6, eps=(1e-5, 1.0 / 256)):
+    """The loop of voxel_map_align around any source of sums - sums_of(poses [B,12], origin [B,3]) -> int64 [B,19]: the numpy definition's
+    or the device's, read back.  Everything else is host numpy, the same for both."""
+    if isinstance(iterations, bool) or int(iterations) != iterations or iterations < 0:
+        raise ValueError("iterations must be an integer >= 0, got %r" % (iterations,))
+    if dof not in (4, 6) or isinstance(dof, bool):
+        raise ValueError("dof must be 6 (all of the rotation) or 4 (yaw only), got %r" % (dof,))
+    if len(eps) != 2 or not all(np.isfinite(float(e)) and float(e) >= 0 for e in eps):
+        raise ValueError("eps must be two finite numbers >= 0: radians and cells, got %r" % (eps,))
+    poses = voxel_map_pose_words(poses) if len(np.asarray(poses)) else np.zeros((0, 12))
+    B = len(poses)
+    sums, ok = np.zeros((B, 19), np.int64), np.zeros(B, bool)
+    pairs, rms, rounds = [], [], 0
+    size = np.float64(params["size"])
+    for _ in range(int(iterations)):
+        origin = voxel_align_origin(params, poses)
+        sums = np.ascontiguousarray(sums_of(poses, origin), np.int64)
+        poses, ok, step = voxel_align_solve(sums, poses, origin, params, dof, min_pairs)
+        rounds += 1
+        W, D = sums[:, 2].astype(np.float64), sums[:, 3].astype(np.float64)
+        pairs.append(sums[:, 1].copy())
+        rms.append(np.where(W > 0, np.sqrt(D / np.maximum(W, 1.0)) * size / 256.0, 0.0))
+        if ((step[ok, 0] < eps[0]) & (step[ok, 1] < eps[1])).all():
+            break
+    return {"poses": poses, "ok": ok, "sums": sums, "rounds": rounds, "pairs": np.array(pairs, np.int64).reshape(rounds, B), "rms": np.array(rms, np.float64).reshape(rounds, B)}
+
+
+def voxel_map_align(map_state, xyz, n, counts, poses, iterations=10, max_dist=1.0, dof=6, min_pairs=6, eps=(1e-5, 1.0 / 256), min_n=1, min_rows=1, since=0):
+    """Iterative closest point of B frames against a voxel map: each round takes the origin from the current poses (voxel_align_origin),
+    then the sums (voxel_map_align_sums), then the fit (voxel_align_solve), and the loop stops when the step of every frame that was
+    fitted is below eps = (radians, cells), or after `iterations` rounds.  poses float64 [B,12] or [B,4]: the start - voxel_map_match's
+    best, or the odometry's.  -> {"poses": float64 [B,12], "ok": bool [B] - the last round fitted the frame -, "sums": the last round's
+    int64 [B,19], "rounds": the rounds used, "pairs": int64 [rounds,B], "rms": float64 [rounds,B] = sqrt(D / W) size / 256, the pairs'
+    root mean square distance in metres as each round found it}.  A frame with fewer than min_pairs pairs in a round keeps its pose in
+    that round.  The map is not changed."""
+    voxel_align_max_d2(max_dist)
+    xyz, n, counts, p, _ = _voxel_align_setup(map_state, xyz, n, counts, poses, np.zeros((np.asarray(xyz).shape[0], 3), np.int64))
+    sums_of = lambda cur, origin: voxel_map_align_sums(map_state, xyz, n, counts, cur, origin, max_dist, min_n, min_rows, since)["sums"]  # noqa: E731
+    return voxel_align_loop(sums_of, map_state["params"], p, iterations, dof, min_pairs, eps)
 
 
 GROUND_BINS_MIN, GROUND_BINS_MAX = 8, 4096
@@ -3273,6 +3569,13 @@ def main(argv=None):
                              "and +-DYAW radians around its line (NX x NY x NZ x NYAW poses, odd, default 5,5,3,5; the line itself wins ties) "
                              "and inserted at the best pose.  The refined poses are written next to FILE.ply as <FILE without "
                              ".ply>.poses.txt, one 'x y z yaw' per frame")
+    parser.add_argument("--voxel-align", type=str, default="", metavar="ROUNDS[,MAX_DIST_CELLS[,DOF]]",
+                        help="with --voxel-map: before a batch's frames are inserted, refine their poses - the lines of --poses, or what "
+                             "--voxel-match made of them - by at most ROUNDS rounds of iterative closest point against the voxel map built "
+                             "so far: every row is paired with the nearest voxel within MAX_DIST_CELLS cells (default 1) and the pairs are "
+                             "fitted in closed form, DOF 6 (default: roll and pitch as well) or 4 (yaw and the translation).  The refined "
+                             "poses are written next to FILE.ply as <FILE without .ply>.aligned.txt, twelve words per frame: the rotation "
+                             "row-major, then the translation")
     parser.add_argument("--occupancy", type=str, default="", metavar="DIR",
                         help="with --batch: write each frame's occupancy grid as a PNG into DIR (0 unknown, 127 free, 255 occupied): ground "
                              "plane and obstacle labels from the float disparity, then per cell of the grid of --top-view (vehicle axes) the "
@@ -3370,6 +3673,14 @@ def main(argv=None):
             voxel_map_pose_window(0.0, 0.0, 0.0, 0.0, *args.voxel_match_window)
         except ValueError as e:
             parser.error("--voxel-match: %s" % e)
+    args.voxel_align_spec = None
+    if args.voxel_align:
+        if not args.voxel_map:
+            parser.error("--voxel-align needs --voxel-map")
+        try:
+            args.voxel_align_spec = cli_voxel_align_spec(args.voxel_align)
+        except ValueError as e:
+            parser.error("--voxel-align: %s" % e)
     if args.voxel_carve:
         if not args.voxel_map:
             parser.error("--voxel-carve needs --voxel-map")
@@ -3548,6 +3859,18 @@ def cli_voxel_carry_text(stats):
     return ", ".join("%s %d" % (k, v) for k, v in zip(VOXEL_CARRY_STATS, values))
 
 
+def cli_voxel_align_spec(text):
+    """(rounds, max_dist in cells, dof) of --voxel-align ROUNDS[,MAX_DIST_CELLS[,DOF]]; ValueError for what voxel_map_align refuses."""
+    words = text.split(",")
+    if not 1 <= len(words) <= 3:
+        raise ValueError("%d words, not ROUNDS[,MAX_DIST_CELLS[,DOF]]" % len(words))
+    rounds, max_dist, dof = int(words[0]), float(words[1]) if len(words) > 1 else 1.0, int(words[2]) if len(words) > 2 else 6
+    if rounds < 1 or dof not in (4, 6):
+        raise ValueError("ROUNDS >= 1 and DOF 4 or 6, got %r" % (text,))
+    voxel_align_max_d2(max_dist)
+    return rounds, max_dist, dof
+
+
 def cli_voxel_carve_spec(reach_m, min_miss, ratio, size):
     """(reach_m, min_miss, ratio) of --voxel-carve, checked as rig.VoxelMap.carve and voxel_map_carve check them: ValueError with the
     text the CLI prints."""
@@ -3654,7 +3977,7 @@ def _run_batched(args, ldir, rdir, files):
     rig = StereoRig(1242 // args.scale, 375 // args.scale, calibration=args.camera_calibration, rectify=args.rectify, scale=args.scale)
     world = rig.occupancy_map(args.map_ranges[0], args.map_ranges[1], CLI_TOP_VIEW["scale"]) if args.occupancy_map else None
     model = rig.voxel_map(args.voxel_map_box[0], args.voxel_map_box[1], args.voxel, CLI_VOXEL_MAP_CAPACITY) if args.voxel_map else None
-    n, busy, refined, refined_3d = 0, 0.0, [], []
+    n, busy, refined, refined_3d, aligned_3d = 0, 0.0, [], [], []
     try:
         for i in range(0, len(files), args.batch):
             names = files[i:i + args.batch]
@@ -3679,6 +4002,8 @@ def _run_batched(args, ldir, rdir, files):
                         if args.voxel_render_spec is not None:  # the map of the frames before this batch, seen from this batch's poses
                             seen = model.render(went, rig.render_camera(args.voxel), transform=(CAMERA_TO_VEHICLE, None), measured=d1, tol=args.voxel_render_spec[1])
                         if args.voxel_match_window is None:
+                            if args.voxel_align_spec is not None and model.seq > 0:  # the whole batch against the frames before it
+                                went = model.align(voxels[0], voxels[3], voxels[5], went, args.voxel_align_spec[0], args.voxel_align_spec[1], args.voxel_align_spec[2])[0]
                             model.update(voxels[0], voxels[1], voxels[3], voxels[5], went)
                         for k in range(len(names) if args.voxel_match_window is not None else 0):  # one at a time: against the frames before it
                             one = [t[k:k + 1] for t in (voxels[0], voxels[1], voxels[3], voxels[5])]
@@ -3686,7 +4011,10 @@ def _run_batched(args, ldir, rdir, files):
                             to = guess if model.seq == 0 else model.localize(one[0], one[2], one[3], guess, *args.voxel_match_window)[0][0]
                             refined_3d.append(to)
                             went[k] = voxel_map_pose(to[0], to[1], to[3], to[2])
+                            if args.voxel_align_spec is not None and model.seq > 0:
+                                went[k] = model.align(one[0], one[2], one[3], went[k:k + 1], args.voxel_align_spec[0], args.voxel_align_spec[1], args.voxel_align_spec[2])[0][0]
                             model.update(*one, went[k:k + 1])
+                        aligned_3d.extend(went)
                         if args.voxel_carve_spec is not None:  # the camera's centre is the origin of the vehicle axes: CAMERA_TO_VEHICLE only turns
                             reach_m, min_miss, ratio = args.voxel_carve_spec
                             res = model.carve(voxels[0], voxels[3], voxels[5], went, reach_m=reach_m, min_miss=min_miss, ratio=ratio)
@@ -3739,6 +4067,9 @@ def _run_batched(args, ldir, rdir, files):
             if args.voxel_match_window is not None:
                 with open(os.path.splitext(args.voxel_map)[0] + ".poses.txt", "w") as f:
                     f.write("".join("%r %r %r %r\n" % tuple(float(v) for v in to) for to in refined_3d))
+            if args.voxel_align_spec is not None:
+                with open(os.path.splitext(args.voxel_map)[0] + ".aligned.txt", "w") as f:
+                    f.write("".join(" ".join("%r" % float(v) for v in to) + "\n" for to in aligned_3d))
             if args.voxel_flatten_spec is not None:  # the planner's map from the voxel map's evidence
                 x_range, y_range, scale, step, height = args.voxel_flatten_spec
                 stem = os.path.splitext(args.voxel_map)[0] + ".flat"
