@@ -89,6 +89,12 @@
  *      that a pose is refined below (R)'s step and in roll and pitch as well.  stereo_vision.sv.voxel_map_align_sums states the definition
  *      in numpy; voxel_align_solve and voxel_map_align are the fit and the loop around both.
  *
+ *  (Y) Behind (X): the surface normals of the voxels (sv_voxel_normals_device) - per voxel of (Q)'s table a plane fitted to the means of
+ *      the voxels around it, as the best of a fixed table of integer directions under an exact integer criterion - and the sums of one
+ *      round of point-to-plane alignment against them (sv_voxel_plane_align_*): (X)'s pairs, each reduced along its partner's normal, so
+ *      that a row may slide along the ground or a wall it lies on and the loop converges in a few rounds where (X)'s creeps.
+ *      stereo_vision.sv.voxel_map_normals and voxel_map_align_plane_sums state the definitions in numpy; voxel_align_solve_plane is the fit.
+ *
  * All sv_* functions return SV_OK (0) or a negative sv_status; sv_last_error() gives the text.
  * Nothing in this library calls exit().
  */
@@ -1660,6 +1666,84 @@ int sv_voxel_align_device(const void *map, size_t map_bytes, const sv_voxel_map_
  * one of the 27 cells instead of leaving out those that cannot hold the nearest.  The results do not depend on either.  Returns SV_OK, or
  * SV_ERR_ARG for other values. */
 int sv_debug_voxel_align(int max_chunks, int flags);
+
+/* ---- (Y) normals of the voxel map and point-to-plane alignment: (Q)'s table -> a direction per slot; (X)'s pairs + the directions -> the sums of one round ---- */
+
+/* (X) pairs a row with the nearest voxel MEAN, which holds the row back along every plane it lies on: on a street most rows lie on the road
+ * and on walls, and the loop creeps.  Here every voxel gets the normal of the plane through the means around it, and a round's sums are
+ * those of the point-to-plane residuals.  Integers from the cell on: both are bit-exact against stereo_vision.sv.voxel_map_normals and
+ * voxel_map_align_plane_sums, which restate them in numpy, whatever the schedule and wherever the inserts left an entry - which rules out
+ * an eigen-solver in floating point: the normal is found by an exhaustive search over a table of integer directions.  The map is only read.
+ *
+ * (Y1) normals
+ *   members    the slots whose entry passes (Q)'s filters with n >= max(min_n, 1); a tombstone is neither a member nor a neighbour.
+ *   position   q_k = 256 cell_k + ((S_k / n) >> 8), (X)'s, in 1/256 of a cell.
+ *   neighbours of member v the members in the up to 27 cells c + d, d in {-1, 0, 1}^3, inside the box - a cell is tested against the box
+ *              before a key is formed -, v itself among them.  e = q_j - q_v, |e_k| <= 511; N their number (1 .. 27), s1 = sum e, s2 = sum
+ *              e e^T, C = N s2 - s1 s1^T: symmetric, positive semi-definite, |C_ij| < 2^28.  T = C00 + C11 + C22.
+ *   directions dirs int8 [n_dirs][4], 1 <= n_dirs <= 4096, the fourth byte ignored (stereo_vision.sv.voxel_normal_dirs makes a table of
+ *              nearly equal lengths).  s_k = |d_k|^2, Q_k = d_k^T C d_k, 0 <= Q_k < 2^46.  k is flatter than j iff Q_k s_j < Q_j s_k, or
+ *              the two are equal and k < j; a direction with s_k = 0 is never chosen.  best the flattest, worst the one with the
+ *              largest Q / s, ties to the lower index.  lam3 = Q_best / s_best, lam1 = Q_worst / s_worst, integer divisions (both 0 for
+ *              a table of zero vectors); lam2 = T - lam1 - lam3.
+ *   verdict    normal = best where N >= min_nb, lam2 > 0, 256 lam3 <= flat lam2 and 256 lam2 >= wide lam1, else -1: a pole or an edge
+ *              has one wide axis and gets no normal, a blob gets none either.
+ *   outputs    normal int32 per slot, -1 for everything that is not a member; fit int64 [slots][4], optional: N, lam1, lam2, lam3 of
+ *              every member, zeros elsewhere; counts int64 [4]: members, members with N >= min_nb, normals given, 0.
+ *   overflowed every normal -1, fit and counts 0.
+ *
+ * (Y2) the sums of one point-to-plane round
+ *   rows, world, kept, p, candidates, nearest, pair : (X)'s, word for word.
+ *   plane pair a pair whose partner's word of `normal` is a direction of the table: 0 <= normal[slot] < n_dirs.  The array is taken as it
+ *              is; nothing is fitted again.  nu = dirs[normal[slot]] as integers.
+ *   per pair   l = (p - o) >> 4, an arithmetic shift: the lever arm in 1/16 of a cell.  b = nu . (q - p).  a = (l x nu, nu), six integers.
+ *   sums       int64 [batch][32]: inside, pairs - (X)'s -, planes, and over the plane pairs W = sum w, E = sum w b^2, g[6] = sum w a_i b,
+ *              A[21] = sum w a_i a_j for i <= j, row-major.  64-bit two's complement sums; contract: sum w (256 |l|max)^2 < 2^63 - without
+ *              the shift a_i a_j would reach (2 * 127 * r)^2 and 20 000 rows of a street frame would stand at 2^56.
+ *   per row    pair_key, pair_d2: (X)'s; pair_normal int32: the nearest candidate's word of `normal` where that is a direction of the
+ *              table, else -1 - also for a row that is not kept and every index at or beyond min(counts[b], cap).  All three or none.
+ *   overflowed every sum is 0 and every per-row word is -1.
+ * The host solves A x = g (stereo_vision.sv.voxel_align_solve_plane): omega = x[0..2] / 16, t = x[3..5] in 1/256 of a cell. */
+
+/* Enqueued on `stream` (a hipStream_t, NULL = the default stream) as a memset of the counts and one kernel, a lane per slot, and not waited
+ * for: nothing is allocated, no host synchronisation is made, the map is read only, and the only atomics are the three counts', one flush
+ * per workgroup.
+ *   map, map_bytes, spec : the voxel map, as (Q)'s entries take it
+ *   dirs, n_dirs : int8 [n_dirs][4] device, 4-byte aligned; 1 .. 4096
+ *   min_nb       : 3 .. 27;  flat, wide : 0 .. 256
+ *   min_n, min_rows, since : the filters of sv_voxel_map_rows_device; a min_n below 1 counts as 1
+ *   normal, n_normal : int32 [n_normal] device, 4-byte aligned; n_normal = sv_voxel_map_slots(capacity of the map)
+ *   fit          : int64 [n_normal][4] device, 8-byte aligned, or NULL
+ *   counts       : int64 [4] device, 8-byte aligned
+ * Returns SV_OK, SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued, the outputs untouched, the text in sv_last_error(NULL) - for: what the clear
+ * entry of (Q) refuses; n_dirs outside 1 .. 4096; dirs, normal or counts NULL; n_normal not the table's slots; min_nb, flat or wide outside
+ * its range; a pointer not aligned to its element; an output sharing a byte with the map, the table or another output.  These checks run
+ * before any HIP call. */
+int sv_voxel_normals_device(const void *map, size_t map_bytes, const sv_voxel_map_spec *spec, const int8_t *dirs, int n_dirs, int min_nb, int flat, int wide, int64_t min_n,
+                            int64_t min_rows, int since, int32_t *normal, int64_t n_normal, int64_t *fit, int64_t *counts, void *stream);
+/* Host only: the bytes of the workspace sv_voxel_plane_align_device needs for `batch` frames of `cap` rows: 32 words per chunk of 256 rows,
+ * at most 512 chunks a frame.  SV_ERR_ARG (bytes untouched) for a NULL bytes, cap < 0 or batch outside 0..65535. */
+int sv_voxel_plane_align_workspace(int cap, int batch, size_t *bytes);
+/* Enqueued on `stream` as two kernels - the plane pairs and their sums per chunk of rows, the chunks' sums per frame - and not waited for:
+ * nothing is allocated, no host synchronisation is made, no atomic is issued, the map is read only, and nothing is assumed of what the
+ * outputs or the workspace held before.  Every argument of sv_voxel_align_device means here what it means there, and besides:
+ *   normal, n_normal : int32 [n_normal] device, 4-byte aligned: (Y1)'s output for this map, or any array of that length
+ *   dirs, n_dirs : the table the words of `normal` index
+ *   sums         : int64 [batch][32] device, 8-byte aligned
+ *   pair_key, pair_d2, pair_normal : [batch][cap] device, all three or all NULL
+ *   workspace    : device, 8-byte aligned, workspace_bytes >= what sv_voxel_plane_align_workspace gives
+ * Every output given is written in full.  Returns SV_OK (nothing enqueued for batch == 0), SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued, the
+ * outputs untouched - for what sv_voxel_align_device refuses, and for: n_dirs outside 1 .. 4096; with batch > 0 a NULL dirs or normal; an
+ * n_normal that is not the table's slots; dirs, normal or pair_normal not 4-byte aligned; only some of the three per-row outputs. */
+int sv_voxel_plane_align_device(const void *map, size_t map_bytes, const sv_voxel_map_spec *spec, const void *xyz, int dtype, const int32_t *n, const int32_t *counts,
+                                const double *poses, const int32_t *origin, int batch, int cap, int max_d2, int64_t min_n, int64_t min_rows, int since, const int32_t *normal,
+                                int64_t n_normal, const int8_t *dirs, int n_dirs, int64_t *sums, int64_t *pair_key, int32_t *pair_d2, int32_t *pair_normal, void *workspace,
+                                size_t workspace_bytes, void *stream);
+/* Test and measurement hook for the two calls above, process-wide: max_chunks as sv_debug_voxel_align's, for the plane score kernel; flags
+ * bit 0 makes that kernel look into every one of the 27 cells, bit 1 makes the normals kernel search the table for every member - by
+ * default a member with N < min_nb, which gets no normal whatever the table says, is not searched where no fit is asked for.  The results
+ * do not depend on any of them.  Returns SV_OK, or SV_ERR_ARG for other values. */
+int sv_debug_voxel_normals(int max_chunks, int flags);
 
 /* ---- (A)the reference's exported symbols ------------------------------------------------------------- */
 

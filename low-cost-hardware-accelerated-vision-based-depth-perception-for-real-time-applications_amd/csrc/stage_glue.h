@@ -1,4 +1,4 @@
-// What the stage entries of groups (D) to (X) of include/stereo_vision_hip.h share on the host (top_view.cpp ... voxel_align.cpp): the
+// What the stage entries of groups (D) to (Y) of include/stereo_vision_hip.h share on the host (top_view.cpp ... voxel_normals.cpp): the
 // refusal of a bad call, the checks that several groups state in the same words, and the set-up of sv::ReprojectArgs.  Host code only:
 // no .hip file includes it.
 #pragma once
@@ -68,7 +68,7 @@ template <class... P>
 inline bool any_misaligned(unsigned a, const P *...p) { return (... || misaligned(p, a)); }  // NULL is aligned
 
 // NULL for a voxel map spec and a buffer that (Q)'s clear entry admits, else what is wrong with them: the check of every entry of (Q)
-// to (X).  nc = the cells per axis, log2_slots = of the table; sv_voxel_map_slots (voxel_map.cpp) holds the rule of the capacity.
+// to (Y).  nc = the cells per axis, log2_slots = of the table; sv_voxel_map_slots (voxel_map.cpp) holds the rule of the capacity.
 inline const char *check_voxel_map(const char *prefix, const void *map, size_t map_bytes, const sv_voxel_map_spec *s, int *nc, int *log2_slots) {
     if (!s) return prefixed(prefix, "spec is NULL");
     for (int k = 0; k < 7; k++)

@@ -1,6 +1,6 @@
 // The rules that make the world-fixed voxel map one map across its stages - insert and read-out (voxel_map_kernels.hip), match
 // (voxel_match_kernels.hip), carry (voxel_carry_kernels.hip), carve (voxel_carve_kernels.hip), render (voxel_render_kernels.hip), flatten
-// (voxel_flatten_kernels.hip), clusters (voxel_cluster_kernels.hip), align (voxel_align_kernels.hip) -, written down once: the buffer's parts, the entry's words, the hash, the two probes, a row's way from the
+// (voxel_flatten_kernels.hip), clusters (voxel_cluster_kernels.hip), align (voxel_align_kernels.hip), normals and plane sums (voxel_normal_kernels.hip) -, written down once: the buffer's parts, the entry's words, the hash, the two probes, a row's way from the
 // frame into a cell, and a voxel's centre and height.  Plain inline functions and named constants; what a stage does with an entry it
 // has found stays in the stage.  The layout is voxel_map_kernels.h's; the definitions are include/stereo_vision_hip.h (Q)'s.  The
 // per-frame voxel cloud (voxel_kernels.hip) has another entry and another life cycle and shares nothing with this.

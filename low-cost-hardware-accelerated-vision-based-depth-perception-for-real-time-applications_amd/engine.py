@@ -662,6 +662,12 @@ def _signatures():
             "sv_voxel_align_device": (ci, [vp, sz, vm, vp, ci, vp, vp, vp, vp, ci, ci, ci, i64, i64, ci, vp, vp, vp, vp, sz, vp]),
             "sv_debug_voxel_align": (ci, [ci, ci]),
         },
+        "voxel_normals": {  # (Y)
+            "sv_voxel_normals_device": (ci, [vp, sz, vm, vp, ci, ci, ci, ci, i64, i64, ci, vp, i64, vp, vp, vp]),
+            "sv_voxel_plane_align_workspace": (ci, [ci, ci, P(sz)]),
+            "sv_voxel_plane_align_device": (ci, [vp, sz, vm, vp, ci, vp, vp, vp, vp, ci, ci, ci, i64, i64, ci, vp, i64, vp, ci, vp, vp, vp, vp, vp, sz, vp]),
+            "sv_debug_voxel_normals": (ci, [ci, ci]),
+        },
     }
 
 
@@ -675,6 +681,7 @@ _GROUP_NEEDS["voxel_render"] = ("voxel_map",)
 _GROUP_NEEDS["voxel_flatten"] = ("voxel_map", "occupancy_map")
 _GROUP_NEEDS["voxel_clusters"] = ("voxel_map", "occupancy_map")
 _GROUP_NEEDS["voxel_align"] = ("voxel_map",)
+_GROUP_NEEDS["voxel_normals"] = ("voxel_map",)
 _bound_groups = set()
 
 
@@ -2634,28 +2641,52 @@ def voxel_map_align_sums(buf, params, xyz, n, counts, poses, origin, max_dist=1.
     return res  # ws goes back to torch's allocator, which hands it out again on this stream only: behind the kernels
 
 
-def voxel_map_align(buf, params, xyz, n, counts, poses, iterations=10, max_dist=1.0, dof=6, min_pairs=6, eps=(1e-5, 1.0 / 256), min_n=1, min_rows=1, since=0):
+def voxel_map_align(buf, params, xyz, n, counts, poses, iterations=10, max_dist=1.0, dof=6, min_pairs=6, eps=None, min_n=1, min_rows=1, since=0, method="point",
+                    normals=None):
     """Iterative closest point of B frames against the map in `buf` - stereo_vision.sv.voxel_map_align with the sums from the device: per
     round the origin from the current poses, voxel_map_align_sums, the B x 19 words read back - the stage's one wait, once per round -
     and stereo_vision.sv.voxel_align_solve on them, until every fitted frame's step is below eps or `iterations` rounds are done.  The
     fit and the loop are the numpy definition's own functions on equal sums, so the poses, ok, rounds, pairs and rms equal the CPU
     path's bit for bit.  poses: the start, float64 [B,12] or [B,4], numpy or a tensor.  -> VoxelAlignResult with sums (the last round's,
-    on the device), poses float64 numpy [B,12], ok, rounds, pairs and rms."""
+    on the device), poses float64 numpy [B,12], ok, rounds, pairs and rms.  eps None: (1e-5, 1 / 256), and
+    stereo_vision.sv.VOXEL_ALIGN_PLANE_EPS for the planes.
+    method="plane": the point-to-plane rounds of group (Y) - voxel_map_align_plane_sums, B x 32 words read back per round, and
+    stereo_vision.sv.voxel_align_solve_plane -> VoxelPlaneResult.  normals: a VoxelNormalsResult of this map (None: voxel_map_normals with
+    its defaults and these filters, one kernel more in front of the loop)."""
     import torch
-    from .stereo_vision.sv import voxel_align_loop, voxel_align_max_d2, voxel_map_pose_words
+    from .stereo_vision.sv import VOXEL_ALIGN_METHODS, VOXEL_ALIGN_PLANE_EPS, voxel_align_loop, voxel_align_max_d2, voxel_align_plane_solver, voxel_map_pose_words
     voxel_align_max_d2(max_dist)
+    if method not in VOXEL_ALIGN_METHODS:
+        raise ValueError("method must be 'point' or 'plane', got %r" % (method,))
+    if method == "point" and normals is not None:
+        raise ValueError("normals go with method='plane'")
     _, _, xyz, n, counts = _voxel_align_frames(buf, params, xyz, n, counts, min_n, min_rows, since)
     B = int(xyz.shape[0])
     start = voxel_map_pose_words(poses.cpu().numpy() if isinstance(poses, torch.Tensor) else poses) if B else np.zeros((0, 12))
     if start.shape[0] != B:
         raise ValueError("poses must hold one pose per frame: %d, got %d" % (B, start.shape[0]))
+    if method == "plane":
+        if normals is None:
+            normals = voxel_map_normals(buf, params, None, min_n=min_n, min_rows=min_rows, since=since)
+        elif not isinstance(normals, VoxelNormalsResult):
+            raise ValueError("normals must be a VoxelNormalsResult of this map")
+        res = VoxelPlaneResult(sums=torch.zeros((B, 32), dtype=torch.int64, device=buf.device))
+
+        def plane_sums_of(cur, origin):
+            voxel_map_align_plane_sums(buf, params, xyz, n, counts, cur, origin, normals, max_dist, min_n, min_rows, since, out=res)
+            return res.sums.cpu().numpy()  # the wait of the round
+
+        got = voxel_align_loop(plane_sums_of, params, start, iterations, dof, min_pairs, VOXEL_ALIGN_PLANE_EPS if eps is None else eps,
+                               voxel_align_plane_solver(normals.dirs.cpu().numpy()))
+        res.poses, res.ok, res.rounds, res.pairs, res.rms = got["poses"], got["ok"], got["rounds"], got["pairs"], got["rms"]
+        return res
     res = VoxelAlignResult(sums=torch.zeros((B, 19), dtype=torch.int64, device=buf.device))
 
     def sums_of(cur, origin):
         voxel_map_align_sums(buf, params, xyz, n, counts, cur, origin, max_dist, min_n, min_rows, since, out=res)
         return res.sums.cpu().numpy()  # the wait of the round
 
-    got = voxel_align_loop(sums_of, params, start, iterations, dof, min_pairs, eps)
+    got = voxel_align_loop(sums_of, params, start, iterations, dof, min_pairs, (1e-5, 1.0 / 256) if eps is None else eps)
     res.poses, res.ok, res.rounds, res.pairs, res.rms = got["poses"], got["ok"], got["rounds"], got["pairs"], got["rms"]
     return res
 
@@ -2665,6 +2696,134 @@ def debug_voxel_align(max_chunks=0, skip=True):
     several chunks) and whether the score kernel leaves out the cells that cannot hold the nearest voxel.  The results depend on
     neither.  Process-wide; a test and measurement hook."""
     return int(voxel_align_lib().sv_debug_voxel_align(int(max_chunks), 0 if skip else 1))
+
+
+def voxel_normals_lib():
+    """The library with the signatures of group (Y) declared."""
+    return _bind("voxel_normals")
+
+
+class VoxelNormalsResult(_Result):
+    """What voxel_map_normals returns, tensors on the map's device: normal int32 [slots] (the index of a direction of `dirs`, -1 for none
+    and for every slot that is no member), fit int64 [slots,4] (N, lam1, lam2, lam3 of a member; None where not asked for), counts int64
+    [4] (stereo_vision.sv.VOXEL_NORMAL_COUNTS), dirs int8 [K,4] - the table, uploaded once -, and keys, a view of the map's key words."""
+    __slots__ = ("normal", "fit", "counts", "dirs", "keys")
+
+
+class VoxelPlaneResult(_Result):
+    """What voxel_map_align_plane_sums returns, tensors on the map's device: sums int64 [B,32] (stereo_vision.sv.VOXEL_PLANE_SUMS names the
+    words), pair_key int64, pair_d2 and pair_normal int32 [B,cap] (None where not asked for).  voxel_map_align(method="plane") fills the
+    rest, host numpy: poses float64 [B,12], ok bool [B], rounds, pairs int64 [rounds,B] - the plane pairs -, rms float64 [rounds,B]."""
+    __slots__ = ("sums", "pair_key", "pair_d2", "pair_normal", "poses", "ok", "rounds", "pairs", "rms")
+
+
+def voxel_normal_table(dirs, dev):
+    """A table of directions as a contiguous int8 [K,4] tensor on dev, 1 <= K <= 4096: a numpy array (stereo_vision.sv.voxel_normal_dirs')
+    is uploaded once, a tensor is checked."""
+    import torch
+    if isinstance(dirs, torch.Tensor):
+        if dirs.device != dev or dirs.dtype != torch.int8 or dirs.dim() != 2 or dirs.shape[1] != 4 or not 1 <= dirs.shape[0] <= 4096:
+            raise ValueError("dirs must be an int8 tensor [K,4] with 1 <= K <= 4096 on the device (%s) of the map" % (dev,))
+        return dirs.contiguous()
+    d = np.asarray(dirs)
+    if d.dtype != np.int8 or d.ndim != 2 or d.shape[1] != 4 or not 1 <= d.shape[0] <= 4096:
+        raise ValueError("dirs must be int8 [K,4] with 1 <= K <= 4096, got %s %s" % (d.dtype, d.shape))
+    return torch.from_numpy(np.ascontiguousarray(d)).to(dev)
+
+
+def voxel_map_normals(buf, params, dirs=None, min_nb=5, flat=64, wide=16, min_n=1, min_rows=1, since=0, want_fit=False, out=None):
+    """The surface normals of the voxels of the map in `buf`: the definition of stereo_vision.sv.voxel_map_normals on the GPU, bit for bit
+    (sv_voxel_normals_device: one kernel, a lane per slot).  dirs: the table of directions, int8 [K,4], numpy or a tensor on the map's
+    device (None: stereo_vision.sv.voxel_normal_dirs()); min_nb in 3 .. 27, flat and wide in 0 .. 256; min_n, min_rows and since are the
+    read-out's filters.  want_fit=True also returns N, lam1, lam2, lam3 per slot.  out: a VoxelNormalsResult of an earlier call on a map
+    of the same capacity to write into.  The map is not changed and nothing is read back.  -> VoxelNormalsResult, per SLOT - the numpy
+    form answers per entry in ascending key; voxel_normal_labels orders this one so -; enqueued on torch's current stream, not waited for."""
+    import torch
+    from .stereo_vision import sv
+    sv._voxel_normal_words(min_nb, flat, wide)
+    spec = voxel_map_spec(params)
+    nbytes = _voxel_map_buffer(buf, spec)
+    dev = buf.device
+    for v, what in ((min_n, "min_n"), (min_rows, "min_rows")):
+        if isinstance(v, bool) or int(v) != v or not -2 ** 63 <= v < 2 ** 63:
+            raise ValueError("%s must be an integer, got %r" % (what, v))
+    if isinstance(since, bool) or int(since) != since or not -2 ** 31 <= since < 2 ** 31:
+        raise ValueError("since must be a 32-bit integer, got %r" % (since,))
+    table = voxel_normal_table(sv.voxel_normal_dirs() if dirs is None else dirs, dev)
+    slots = sv.voxel_map_slots(spec.capacity)
+    res = out if out is not None else VoxelNormalsResult(normal=torch.empty((slots,), dtype=torch.int32, device=dev), counts=torch.empty((4,), dtype=torch.int64, device=dev))
+    if want_fit and res.fit is None:
+        res.fit = torch.empty((slots, 4), dtype=torch.int64, device=dev)
+    if tuple(res.normal.shape) != (slots,) or res.normal.device != dev:
+        raise ValueError("out is of another map's shape")
+    res.dirs, res.keys = table, buf[4:].as_strided((slots,), (11,))
+    with torch.cuda.device(dev):
+        rc = voxel_normals_lib().sv_voxel_normals_device(buf.data_ptr(), nbytes, ctypes.byref(spec), table.data_ptr(), int(table.shape[0]), int(min_nb), int(flat), int(wide),
+                                                         int(min_n), int(min_rows), int(since), res.normal.data_ptr(), slots, res.fit.data_ptr() if want_fit else None,
+                                                         res.counts.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    _check(rc, "sv_voxel_normals_device")
+    return res
+
+
+def voxel_normal_labels(result):
+    """-> (key, normal, fit or None) of the slots that hold a key, ordered by key: what stereo_vision.sv.voxel_map_normals returns as
+    "key", "normal" and "fit".  Reads the number of such slots back: this synchronises.  Call it before anything else changes the map's
+    keys."""
+    import torch
+    at = torch.nonzero(result.keys != -1).reshape(-1)
+    at = at[torch.sort(result.keys[at]).indices]
+    return result.keys[at], result.normal[at], None if result.fit is None else result.fit[at]
+
+
+def voxel_map_align_plane_sums(buf, params, xyz, n, counts, poses, origin, normals, max_dist=1.0, min_n=1, min_rows=1, since=0, want_rows=False, out=None, workspace=None):
+    """The sums of one round of point-to-plane alignment: the definition of stereo_vision.sv.voxel_map_align_plane_sums on the GPU, bit for
+    bit (sv_voxel_plane_align_device: two kernels, no atomics).  Every argument of voxel_map_align_sums means here what it means there;
+    normals is a VoxelNormalsResult of this map - its per-slot normal and its table are taken as they are -, or a pair (normal int32
+    [slots] tensor, dirs).  want_rows=True also returns pair_key, pair_d2 and pair_normal per row.  -> VoxelPlaneResult; enqueued on
+    torch's current stream, not waited for."""
+    import torch
+    from .stereo_vision.sv import voxel_align_max_d2, voxel_map_slots
+    max_d2 = voxel_align_max_d2(max_dist)
+    spec, nbytes, xyz, n, counts = _voxel_align_frames(buf, params, xyz, n, counts, min_n, min_rows, since)
+    dev = buf.device
+    B, cap = int(xyz.shape[0]), int(xyz.shape[1])
+    normal, dirs = (normals.normal, normals.dirs) if isinstance(normals, VoxelNormalsResult) else normals
+    table = voxel_normal_table(dirs, dev)
+    slots = voxel_map_slots(spec.capacity)
+    if not (isinstance(normal, torch.Tensor) and normal.device == dev and normal.dtype == torch.int32 and tuple(normal.shape) == (slots,)):
+        raise ValueError("normal must be an int32 tensor [%d], one word per slot, on the map's device" % slots)
+    normal = normal.contiguous()
+    p = voxel_map_poses(poses, dev)
+    if p.shape[0] != B:
+        raise ValueError("poses must hold one pose per frame: %d, got %d" % (B, p.shape[0]))
+    o = _voxel_align_origin(origin, B, dev)
+    res = out if out is not None else VoxelPlaneResult(sums=torch.empty((B, 32), dtype=torch.int64, device=dev))
+    if want_rows and res.pair_key is None:
+        res.pair_key = torch.empty((B, cap), dtype=torch.int64, device=dev)
+        res.pair_d2, res.pair_normal = torch.empty((B, cap), dtype=torch.int32, device=dev), torch.empty((B, cap), dtype=torch.int32, device=dev)
+    if tuple(res.sums.shape) != (B, 32) or (want_rows and tuple(res.pair_key.shape) != (B, cap)):
+        raise ValueError("out is of another shape")
+    if B == 0:  # nothing to enqueue
+        return res
+    L = voxel_normals_lib()
+    need = ctypes.c_size_t()
+    _check(L.sv_voxel_plane_align_workspace(cap, B, ctypes.byref(need)), "sv_voxel_plane_align_workspace")
+    ws = workspace if workspace is not None else torch.empty((max(need.value // 8, 1),), dtype=torch.int64, device=dev)
+    rows = [res.pair_key, res.pair_d2, res.pair_normal] if want_rows else [None, None, None]
+    with torch.cuda.device(dev):
+        rc = L.sv_voxel_plane_align_device(buf.data_ptr(), nbytes, ctypes.byref(spec), _ptr(xyz), 0 if xyz.dtype == torch.float32 else 1, _ptr(n), counts.data_ptr(),
+                                           p.data_ptr(), o.data_ptr(), B, cap, max_d2, int(min_n), int(min_rows), int(since), normal.data_ptr(), slots, table.data_ptr(),
+                                           int(table.shape[0]), res.sums.data_ptr(), *[None if t is None else t.data_ptr() for t in rows], ws.data_ptr(), ws.numel() * 8,
+                                           torch.cuda.current_stream(dev).cuda_stream)
+    _check(rc, "sv_voxel_plane_align_device")
+    return res  # ws goes back to torch's allocator, which hands it out again on this stream only: behind the kernels
+
+
+def debug_voxel_normals(max_chunks=0, skip=True, prune=True):
+    """sv_debug_voxel_normals: the chunks of rows per frame at most of the plane score kernel (0: the default, 512), whether it leaves out
+    the cells that cannot hold the nearest voxel, and whether the normals kernel leaves out the search of a member with N < min_nb where
+    no fit is asked for.  The results depend on none of them.  Process-wide; a test and measurement hook."""
+    return int(voxel_normals_lib().sv_debug_voxel_normals(int(max_chunks), (0 if skip else 1) | (0 if prune else 2)))
 
 
 def host_support_filter(params, dcan, width, height, threads=0, lattice=False):

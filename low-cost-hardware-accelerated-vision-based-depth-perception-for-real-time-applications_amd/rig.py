@@ -454,7 +454,8 @@ class VoxelMap:
     logodds and last_seen of a flat map, which OccupancyMap.load_voxels takes.  clusters() and despeckle() are group (W),
     stereo_vision.sv.voxel_map_clusters: the connected components of the voxels - a row of counts, sums and a box per object, a label per
     voxel - and the components below a size emptied.  align() is group (X), stereo_vision.sv.voxel_map_align: a frame's pose refined by
-    iterative closest point against the voxels' means, below localize's step and in roll and pitch as well."""
+    iterative closest point against the voxels' means, below localize's step and in roll and pitch as well.  normals() is group (Y),
+    stereo_vision.sv.voxel_map_normals: a plane per voxel through the means around it, which align(method="plane") fits the rows to."""
 
     def __init__(self, lo, hi, size, capacity, device="cuda"):
         import torch
@@ -466,6 +467,7 @@ class VoxelMap:
         self._spare = None  # prune()'s, recenter()'s and resize()'s second buffer, made on first use
         self._miss = None   # carve()'s word per slot, made on first use
         self._clusters = None  # clusters()' result and workspace, made on first use
+        self._normals, self._normals_fresh = None, False  # normals()' (arguments, result), and whether the map is still the one it describes
         if self.device.type == "cuda":
             self.buffer, self._state = voxel_map_new(self.params, self.device), None
         else:
@@ -478,6 +480,7 @@ class VoxelMap:
         else:
             self._state = _sv.voxel_map_state(self.params)
         self.seq = 0
+        self._stale()
 
     def update(self, xyz, color, n, counts, poses):
         """Adds B frames: xyz float32 or float64 [B,cap,3], color uint8 [B,cap,4] or None, n int32 [B,cap] or None (every weight 1), counts
@@ -492,6 +495,7 @@ class VoxelMap:
             host[4] = _sv.voxel_map_pose_words(host[4])
             _sv.voxel_map_insert(self._state, *host, seq0=self.seq)
         self.seq += int(xyz.shape[0])
+        self._stale()
 
     def rows(self, min_n=1, min_rows=1, since=0, dtype="f32"):
         """The voxels with n >= min_n, m >= min_rows rows and last_seq >= since, in ascending key, as a dict of tensors on the map's
@@ -531,7 +535,34 @@ class VoxelMap:
         best = res.best.cpu().numpy().astype(np.int64)
         return window[np.arange(len(g)), np.maximum(best, 0)], res  # row 0 is the guess
 
-    def align(self, xyz, n, counts, poses, iterations=10, max_dist=1.0, dof=6, min_pairs=6, eps=(1e-5, 1.0 / 256), min_n=1, min_rows=1, since=0):
+    def normals(self, m=16, min_nb=5, flat=64, wide=16, **filters):
+        """The surface normals of the voxels (include/stereo_vision_hip.h (Y), stereo_vision.sv.voxel_map_normals): per voxel the plane
+        through the means of the voxels around it, as the best of the 2 m^2 + 1 directions of stereo_vision.sv.voxel_normal_dirs(m); a
+        voxel with fewer than min_nb neighbours, on a pole or an edge, or in a blob gets none (flat, wide: the thresholds, in 1/256).
+        filters: min_n, min_rows, since.  -> engine.VoxelNormalsResult on the device - normal int32 per slot, counts, dirs, not waited
+        for -, or on "cpu" the definition's dict with normal per entry in ascending key.  The map keeps the result, and
+        align(method="plane") uses it until update, an applied carve, despeckle, prune, recenter, resize or merge has changed the map."""
+        from .engine import voxel_map_normals
+        f = self._filters(filters)
+        asked = (int(m), int(min_nb), int(flat), int(wide)) + tuple(int(v) for v in f)
+        dirs = _sv.voxel_normal_dirs(m)
+        if self._state is None:
+            keep = self._normals[1] if self._normals is not None else None
+            if keep is not None and keep.normal.numel() != _sv.voxel_map_slots(self.params["capacity"]):
+                keep = None  # of the map before a resize
+            if keep is not None and self._normals[0][0] == asked[0]:
+                dirs = keep.dirs  # the table is already on the device
+            res = voxel_map_normals(self.buffer, self.params, dirs, min_nb, flat, wide, *f, out=keep)
+        else:
+            res = _sv.voxel_map_normals(self._state, dirs, min_nb, flat, wide, *f)
+        self._normals, self._normals_fresh = (asked, res), True
+        return res
+
+    def _stale(self):
+        """The map has changed: what normals() kept no longer describes it."""
+        self._normals_fresh = False
+
+    def align(self, xyz, n, counts, poses, iterations=10, max_dist=1.0, dof=6, min_pairs=6, eps=None, min_n=1, min_rows=1, since=0, method="point"):
         """Refines one pose per frame by iterative closest point against the map as it stands (include/stereo_vision_hip.h (X),
         stereo_vision.sv.voxel_map_align): xyz, n and counts as for update, poses float64 [B,12] or [B,4] - the start: localize's best,
         or the odometry's.  Per round every row is paired with the nearest voxel mean within max_dist cells and the pairs are fitted in
@@ -539,16 +570,30 @@ class VoxelMap:
         refined poses; engine.VoxelAlignResult with sums, poses, ok, rounds, pairs and rms).  A frame the last round could not fit (ok
         False: fewer than min_pairs pairs, an overflowed map) keeps the pose it had.  Waits once per round, for B x 19 words.  The idiom:
         g, _ = vm.localize(...); poses, _ = vm.align(xyz, n, counts, sv.voxel_map_pose(g[:, 0], g[:, 1], g[:, 3], g[:, 2]));
-        vm.update(xyz, color, n, counts, poses).  The map is not changed."""
+        vm.update(xyz, color, n, counts, poses).  The map is not changed.  method="plane" (group (Y)) fits the rows to the planes of
+        normals() instead of to the voxels' means, which lets a row slide along the road or the wall it lies on: a few rounds where
+        "point" takes many; it uses the normals the map keeps and fits them again - as normals() was last called, or with its defaults
+        and these filters - where the map has changed since.  -> (poses, engine.VoxelPlaneResult)."""
         import torch
-        from .engine import VoxelAlignResult
+        from .engine import VoxelAlignResult, VoxelPlaneResult
+        if method not in _sv.VOXEL_ALIGN_METHODS:
+            raise ValueError("method must be 'point' or 'plane', got %r" % (method,))
+        kept = None
+        if method == "plane":
+            if not self._normals_fresh:
+                if self._normals is None:
+                    self.normals(min_n=min_n, min_rows=min_rows, since=since)
+                else:
+                    m, min_nb, flat, wide, f0, f1, f2 = self._normals[0]
+                    self.normals(m, min_nb, flat, wide, min_n=f0, min_rows=f1, since=f2)
+            kept = self._normals[1]
         if self._state is None:
-            res = voxel_map_align(self.buffer, self.params, xyz, n, counts, poses, iterations, max_dist, dof, min_pairs, eps, min_n, min_rows, since)
+            res = voxel_map_align(self.buffer, self.params, xyz, n, counts, poses, iterations, max_dist, dof, min_pairs, eps, min_n, min_rows, since, method, kept)
             return res.poses, res
         host = [None if t is None else (t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)) for t in (xyz, n, counts, poses)]
         got = _sv.voxel_map_align(self._state, *host, iterations=iterations, max_dist=max_dist, dof=dof, min_pairs=min_pairs, eps=eps, min_n=min_n,
-                                  min_rows=min_rows, since=since)
-        res = VoxelAlignResult(**dict(got, sums=torch.from_numpy(got["sums"])))
+                                  min_rows=min_rows, since=since, method=method, normals=kept)
+        res = (VoxelAlignResult if method == "point" else VoxelPlaneResult)(**dict(got, sums=torch.from_numpy(got["sums"])))
         return res.poses, res
 
     def stats(self):
@@ -571,6 +616,7 @@ class VoxelMap:
     def _carry_over(self, params, shift, filters):
         """The map's voxels, filtered and shifted, carried into an empty map of `params`, which becomes the map; -> the counts."""
         f = self._filters(filters)
+        self._stale()
         if self._state is not None:
             state = _sv.voxel_map_state(params)
             stats = _sv.voxel_map_carry(state, self._state, shift, *f)
@@ -637,6 +683,7 @@ class VoxelMap:
         else:
             stats = voxel_map_carry(self.buffer, self.params, other.buffer, other.params, shift, *f)
         self.seq = max(self.seq, other.seq)
+        self._stale()
         return stats
 
     def carve(self, xyz, n, counts, poses, origin=None, seq0=None, reach_m=20.0, margin=1, min_miss=2, ratio=0, apply=True, prune=False):
@@ -667,6 +714,8 @@ class VoxelMap:
             host = [None if t is None else (t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)) for t in (xyz, n, counts, poses)]
             host[3] = _sv.voxel_map_pose_words(host[3])
             res = _sv.voxel_map_carve(self._state, *host, origin=origin, seq0=seq0, reach=reach, margin=margin, min_miss=min_miss, ratio=ratio, apply=apply)
+        if apply:
+            self._stale()
         if prune:
             self.prune()
         return res
@@ -762,6 +811,7 @@ class VoxelMap:
         device, not waited for (info[4] = the voxels emptied), or a tensor on "cpu"."""
         f = self._filters(filters)
         res = self.clusters(connectivity, min_voxels, 1, min_n=f[0], min_rows=f[1], since=f[2], drop=True, sort=False if self._state is None else True)
+        self._stale()
         if prune:
             self.prune()
         return res.info if self._state is None else res["info"]

@@ -136,6 +136,16 @@ fit needs.  voxel_align_origin, voxel_align_solve and voxel_map_align are the ho
 sums are taken about, the fit (Kabsch for six degrees of freedom, about z alone for four) and the loop -, shared by the CPU and the GPU
 path, so that both give the same poses bit for bit.  It refines a pose below voxel_map_match's step, and in roll and pitch.  The
 reference has no counterpart.
+
+voxel_map_normals (with voxel_map_normals_brute, the plain loop per voxel in Python ints and fractions, voxel_normal_dirs and
+voxel_normal_vectors) is the definition of the voxels' surface normals (sv_voxel_normals_device of include/stereo_vision_hip.h (Y);
+engine.voxel_map_normals / rig.VoxelMap.normals on the GPU): per voxel the plane through the means of the voxels around it, as the best
+of a fixed table of integer directions under an exact integer criterion.  voxel_map_align_plane_sums (with
+voxel_map_align_plane_sums_brute) is the definition of one round of point-to-plane alignment against them (sv_voxel_plane_align_*;
+engine.voxel_map_align_plane_sums): voxel_map_align_sums' pairs, reduced to the 32 integers of the normal equations.
+voxel_align_solve_plane is the host's fit, and voxel_map_align(method="plane") the loop around both - a row may slide along the plane it
+lies on, so the loop needs a few rounds on a street where the point-to-point loop creeps.  The reference has no counterpart (DESIGN.md
+§8).
 """
 import argparse
 import ctypes
@@ -1768,6 +1778,23 @@ def _voxel_align_rows(params, X, wt, pose):
     return np.flatnonzero(keep), c, 256 * c + (u >> 8)
 
 
+def _voxel_align_nearest(cells, vkey, vq, c, p):
+    """The nearest candidate of every kept row -> (d2, key, q): the voxels (vkey ascending, vq) of the up to 27 cells around the row's cell
+    c, the smallest d2 to the row's position p, then the smallest key; key -1 for a row without a candidate."""
+    K = len(c)
+    best_d2, best_key, best_q = np.full(K, VOXEL_ALIGN_D2_MAX + 1, np.int64), np.full(K, -1, np.int64), np.zeros((K, 3), np.int64)
+    for d in VOXEL_ALIGN_OFFSETS:
+        cc = c + np.array(d, np.int64)
+        on = ((cc >= 0) & (cc < cells)).all(-1)  # before a key is formed: a cell of -1 or of `cells` is no cell
+        key = np.where(on, cc[:, 0] | (cc[:, 1] << 20) | (cc[:, 2] << 40), -2)
+        at = np.minimum(np.searchsorted(vkey, key), len(vkey) - 1)
+        q = vq[at]
+        d2 = ((p - q) ** 2).sum(1)
+        take = on & (vkey[at] == key) & ((best_key < 0) | (d2 < best_d2) | ((d2 == best_d2) & (key < best_key)))
+        best_d2[take], best_key[take], best_q[take] = d2[take], key[take], q[take]
+    return best_d2, best_key, best_q
+
+
 def _voxel_align_add(sums, wt, p, q, d2, o):
     """The pairs of one frame added up: 64-bit two's complement sums."""
     with np.errstate(over="ignore"):
@@ -1815,18 +1842,8 @@ def voxel_map_align_sums(map_state, xyz, n, counts, poses, origin, max_dist=1.0,
         rows = int(min(max(int(counts[b]), 0), cap))
         wt = np.ones(rows, np.int64) if n is None else n[b, :rows].astype(np.int64)
         at_row, c, p = _voxel_align_rows(w, xyz[b, :rows].astype(np.float64), wt, poses[b])
-        K = len(at_row)
-        out["sums"][b, 0] = K
-        best_d2, best_key, best_q = np.full(K, VOXEL_ALIGN_D2_MAX + 1, np.int64), np.full(K, -1, np.int64), np.zeros((K, 3), np.int64)
-        for d in VOXEL_ALIGN_OFFSETS:
-            cc = c + np.array(d, np.int64)
-            on = ((cc >= 0) & (cc < cells)).all(-1)  # before a key is formed: a cell of -1 or of `cells` is no cell
-            key = np.where(on, cc[:, 0] | (cc[:, 1] << 20) | (cc[:, 2] << 40), -2)
-            at = np.minimum(np.searchsorted(vkey, key), len(vkey) - 1)
-            q = vq[at]
-            d2 = ((p - q) ** 2).sum(1)
-            take = on & (vkey[at] == key) & ((best_key < 0) | (d2 < best_d2) | ((d2 == best_d2) & (key < best_key)))
-            best_d2[take], best_key[take], best_q[take] = d2[take], key[take], q[take]
+        out["sums"][b, 0] = len(at_row)
+        best_d2, best_key, best_q = _voxel_align_nearest(cells, vkey, vq, c, p)
         have = best_key >= 0
         out["pair_key"][b, at_row[have]] = best_key[have]
         out["pair_d2"][b, at_row[have]] = best_d2[have]
@@ -1951,9 +1968,13 @@ def voxel_align_solve(sums, poses, origin, params, dof=6, min_pairs=6):
     return out, ok, step
 
 
-def voxel_align_loop(sums_of, params, poses, iterations=10, dof=6, min_pairs=6, eps=(1e-5, 1.0 / 256)):
+def voxel_align_loop(sums_of, params, poses, iterations=10, dof=6, min_pairs=6, eps=(1e-5, 1.0 / 256), solver=None):
     """The loop of voxel_map_align around any source of sums - sums_of(poses [B,12], origin [B,3]) -> int64 [B,19]: the numpy definition's
-    or the device's, read back.  Everything else is host numpy, the same for both."""
+    or the device's, read back.  Everything else is host numpy, the same for both.  solver: None for the point-to-point fit of
+    voxel_align_solve on 19 words, or a dict as VOXEL_ALIGN_PLANE - the words per frame, the fit, which words hold the pairs that count,
+    W and the sum of squares, and the length of one unit of that square root in 1/256 of a cell."""
+    solver = VOXEL_ALIGN_POINT if solver is None else solver
+    words, solve, at_pairs, at_W, at_D, unit = (solver[k] for k in ("words", "solve", "pairs", "W", "D", "unit"))
     if isinstance(iterations, bool) or int(iterations) != iterations or iterations < 0:
         raise ValueError("iterations must be an integer >= 0, got %r" % (iterations,))
     if dof not in (4, 6) or isinstance(dof, bool):
@@ -1962,34 +1983,421 @@ def voxel_align_loop(sums_of, params, poses, iterations=10, dof=6, min_pairs=6, 
         raise ValueError("eps must be two finite numbers >= 0: radians and cells, got %r" % (eps,))
     poses = voxel_map_pose_words(poses) if len(np.asarray(poses)) else np.zeros((0, 12))
     B = len(poses)
-    sums, ok = np.zeros((B, 19), np.int64), np.zeros(B, bool)
+    sums, ok = np.zeros((B, words), np.int64), np.zeros(B, bool)
     pairs, rms, rounds = [], [], 0
     size = np.float64(params["size"])
     for _ in range(int(iterations)):
         origin = voxel_align_origin(params, poses)
         sums = np.ascontiguousarray(sums_of(poses, origin), np.int64)
-        poses, ok, step = voxel_align_solve(sums, poses, origin, params, dof, min_pairs)
+        poses, ok, step = solve(sums, poses, origin, params, dof, min_pairs)
         rounds += 1
-        W, D = sums[:, 2].astype(np.float64), sums[:, 3].astype(np.float64)
-        pairs.append(sums[:, 1].copy())
-        rms.append(np.where(W > 0, np.sqrt(D / np.maximum(W, 1.0)) * size / 256.0, 0.0))
+        W, D = sums[:, at_W].astype(np.float64), sums[:, at_D].astype(np.float64)
+        pairs.append(sums[:, at_pairs].copy())
+        rms.append(np.where(W > 0, np.sqrt(D / np.maximum(W, 1.0)) * unit * size / 256.0, 0.0))
         if ((step[ok, 0] < eps[0]) & (step[ok, 1] < eps[1])).all():
             break
     return {"poses": poses, "ok": ok, "sums": sums, "rounds": rounds, "pairs": np.array(pairs, np.int64).reshape(rounds, B), "rms": np.array(rms, np.float64).reshape(rounds, B)}
 
 
-def voxel_map_align(map_state, xyz, n, counts, poses, iterations=10, max_dist=1.0, dof=6, min_pairs=6, eps=(1e-5, 1.0 / 256), min_n=1, min_rows=1, since=0):
+VOXEL_ALIGN_POINT = dict(words=19, solve=voxel_align_solve, pairs=1, W=2, D=3, unit=1.0)  # voxel_align_loop's solver=None
+VOXEL_ALIGN_METHODS = ("point", "plane")
+VOXEL_ALIGN_PLANE_EPS = (1e-4, 1.0 / 256)  # the plane step settles near 2e-5 rad: the pairs flicker by quantisation
+
+
+def voxel_map_align(map_state, xyz, n, counts, poses, iterations=10, max_dist=1.0, dof=6, min_pairs=6, eps=None, min_n=1, min_rows=1, since=0,
+                    method="point", normals=None):
     """Iterative closest point of B frames against a voxel map: each round takes the origin from the current poses (voxel_align_origin),
     then the sums (voxel_map_align_sums), then the fit (voxel_align_solve), and the loop stops when the step of every frame that was
     fitted is below eps = (radians, cells), or after `iterations` rounds.  poses float64 [B,12] or [B,4]: the start - voxel_map_match's
     best, or the odometry's.  -> {"poses": float64 [B,12], "ok": bool [B] - the last round fitted the frame -, "sums": the last round's
     int64 [B,19], "rounds": the rounds used, "pairs": int64 [rounds,B], "rms": float64 [rounds,B] = sqrt(D / W) size / 256, the pairs'
     root mean square distance in metres as each round found it}.  A frame with fewer than min_pairs pairs in a round keeps its pose in
-    that round.  The map is not changed."""
+    that round.  The map is not changed.  eps None: (1e-5, 1 / 256), and VOXEL_ALIGN_PLANE_EPS for the planes.
+    method="plane" (group (Y)) fits point-to-plane residuals instead - voxel_map_align_plane_sums and voxel_align_solve_plane, which let a
+    row slide along the plane it lies on: "sums" is int64 [B,32], "pairs" counts the plane pairs and "rms" is the root mean square distance
+    to the planes.  normals: what voxel_map_normals returned for this map (None: fitted here, with its defaults and these filters)."""
     voxel_align_max_d2(max_dist)
+    if method not in VOXEL_ALIGN_METHODS:
+        raise ValueError("method must be 'point' or 'plane', got %r" % (method,))
     xyz, n, counts, p, _ = _voxel_align_setup(map_state, xyz, n, counts, poses, np.zeros((np.asarray(xyz).shape[0], 3), np.int64))
-    sums_of = lambda cur, origin: voxel_map_align_sums(map_state, xyz, n, counts, cur, origin, max_dist, min_n, min_rows, since)["sums"]  # noqa: E731
-    return voxel_align_loop(sums_of, map_state["params"], p, iterations, dof, min_pairs, eps)
+    if method == "point":
+        if normals is not None:
+            raise ValueError("normals go with method='plane'")
+        sums_of = lambda cur, origin: voxel_map_align_sums(map_state, xyz, n, counts, cur, origin, max_dist, min_n, min_rows, since)["sums"]  # noqa: E731
+        return voxel_align_loop(sums_of, map_state["params"], p, iterations, dof, min_pairs, (1e-5, 1.0 / 256) if eps is None else eps)
+    if normals is None:
+        normals = voxel_map_normals(map_state, voxel_normal_dirs(), min_n=min_n, min_rows=min_rows, since=since)
+    normal, dirs = normals["normal"], normals["dirs"]
+    sums_of = lambda cur, origin: voxel_map_align_plane_sums(map_state, xyz, n, counts, cur, origin, normal, dirs, max_dist, min_n, min_rows, since)["sums"]  # noqa: E731
+    return voxel_align_loop(sums_of, map_state["params"], p, iterations, dof, min_pairs, VOXEL_ALIGN_PLANE_EPS if eps is None else eps, voxel_align_plane_solver(dirs))
+
+
+VOXEL_NORMAL_DIRS_MAX = 4096
+VOXEL_NORMAL_FIT = ("N", "lam1", "lam2", "lam3")
+VOXEL_NORMAL_COUNTS = ("members", "enough", "normals", "zero")
+VOXEL_PLANE_SUMS = ("inside", "pairs", "planes", "W", "E") + tuple("g%d" % i for i in range(6)) + tuple("A%d%d" % (i, j) for i in range(6) for j in range(i, 6))  # the 32 words
+VOXEL_PLANE_LEVER_SHIFT = 4  # the lever arm (p - o) >> 4, in 1/16 of a cell
+
+
+def voxel_normal_dirs(m=16, radius=127):
+    """The table of candidate directions, int8 [K,4] with K = 2 m^2 + 1 (513 for m = 16): the integer points with |x| + |y| + |z| = m, of
+    each antipodal pair the one whose first non-zero of (z, y, x) is positive, sorted by (z, y, x), each scaled to rint(radius v / |v|);
+    the fourth byte is 0.  m in 1 .. 45, radius in 1 .. 127 (ValueError).  The norms are nearly one: for m = 16 and radius 127 the squared
+    norm s lies in 15972 .. 16265."""
+    for v, what, most in ((m, "m", 45), (radius, "radius", 127)):
+        if isinstance(v, (bool, np.bool_)) or int(v) != v or not 1 <= v <= most:
+            raise ValueError("%s must be an integer in 1 .. %d, got %r" % (what, most, v))
+    m, pts = int(m), []
+    for z in range(-m, m + 1):
+        for y in range(-(m - abs(z)), m - abs(z) + 1):
+            for x in {m - abs(z) - abs(y), -(m - abs(z) - abs(y))}:
+                if next((c for c in (z, y, x) if c != 0), 0) > 0:
+                    pts.append((z, y, x))
+    v = np.array(sorted(pts), np.float64)[:, ::-1]  # (x, y, z), in the order of (z, y, x)
+    out = np.zeros((len(v), 4), np.int8)
+    out[:, :3] = np.rint(float(radius) * v / np.sqrt((v * v).sum(1))[:, None]).astype(np.int8)
+    return out
+
+
+def voxel_normal_vectors(dirs, normal):
+    """float64 [.,3]: the unit vector of every direction index in `normal` (any shape), (0, 0, 0) for -1 and for a zero direction."""
+    d = _voxel_normal_table(dirs)[:, :3].astype(np.float64)
+    length = np.sqrt((d * d).sum(1))
+    unit = np.concatenate([d / np.where(length > 0, length, 1.0)[:, None], np.zeros((1, 3))])
+    at = np.asarray(normal).astype(np.int64)
+    return unit[np.where((at >= 0) & (at < len(d)), at, len(d))]
+
+
+def _voxel_normal_table(dirs):
+    d = np.asarray(dirs)
+    if d.dtype != np.int8 or d.ndim != 2 or d.shape[1] != 4 or not 1 <= d.shape[0] <= VOXEL_NORMAL_DIRS_MAX:
+        raise ValueError("dirs must be int8 [K,4] with 1 <= K <= 4096, got %s %s" % (d.dtype, d.shape))
+    return d
+
+
+def _voxel_normal_words(min_nb, flat, wide):
+    for v, what, lo, hi in ((min_nb, "min_nb", 3, 27), (flat, "flat", 0, 256), (wide, "wide", 0, 256)):
+        if isinstance(v, (bool, np.bool_)) or int(v) != v or not lo <= v <= hi:
+            raise ValueError("%s must be an integer in %d .. %d, got %r" % (what, lo, hi, v))
+    return int(min_nb), int(flat), int(wide)
+
+
+def _voxel_normal_verdict(N, T, lam1, lam3, min_nb, flat, wide):
+    lam2 = T - lam1 - lam3
+    return lam2, (N >= min_nb) & (lam2 > 0) & (256 * lam3 <= flat * lam2) & (256 * lam2 >= wide * lam1)
+
+
+def voxel_map_normals(map_state, dirs, min_nb=5, flat=64, wide=16, min_n=1, min_rows=1, since=0):
+    """The definition of the voxels' surface normals, include/stereo_vision_hip.h (Y1), in numpy: per voxel the best of a fixed table of
+    integer directions under an exact integer criterion.  -> {"normal": int32 [E] - per entry of the map in ascending key, the index of
+    the direction or -1 -, "fit": int64 [E,4] = N, lam1, lam2, lam3 of every member, zeros elsewhere, "counts": int64 [4] = members,
+    members with N >= min_nb, normals given, 0, "key": int64 [E], the entries' keys, "dirs": the table}.
+
+      members     the voxels that pass voxel_map_rows' filters with n >= max(min_n, 1); a tombstone is neither a member nor a neighbour.
+      position    q_k = 256 cell_k + ((S_k // n) >> 8), voxel_map_align_sums' and the flatten's, in 1/256 of a cell.
+      neighbours  of member v the members in the up to 27 cells c + d, d in {-1, 0, 1}^3, inside the box - a cell is tested against the
+                  box before its key is formed -, v among them.  e = q_j - q_v, |e_k| <= 511; N their number, s1 = sum e, s2 = sum e e^T,
+                  C = N s2 - s1 s1^T (|C_ij| < 2^28), T = C00 + C11 + C22.
+      directions  dirs int8 [K,4], 1 <= K <= 4096, the fourth byte ignored; s_k = |d_k|^2, Q_k = d_k^T C d_k.  k is flatter than j iff
+                  Q_k s_j < Q_j s_k, or both are equal and k < j; a direction with s_k = 0 is never chosen.  best the flattest, worst the
+                  one with the largest Q / s, ties to the lower index.  lam3 = Q_best // s_best, lam1 = Q_worst // s_worst (both 0 for a
+                  table of zero vectors), lam2 = T - lam1 - lam3.
+      verdict     normal = best where N >= min_nb, lam2 > 0, 256 lam3 <= flat lam2 and 256 lam2 >= wide lam1, else -1: a pole or an
+                  edge has one wide axis and gets none, a blob neither.  min_nb in 3 .. 27, flat and wide in 0 .. 256 (ValueError).
+    An overflowed map: every normal -1, fit and counts 0."""
+    min_nb, flat, wide = _voxel_normal_words(min_nb, flat, wide)
+    d = _voxel_normal_table(dirs)
+    order = np.argsort(map_state["key"], kind="stable")
+    E = len(order)
+    out = {"normal": np.full(E, -1, np.int32), "fit": np.zeros((E, 4), np.int64), "counts": np.zeros(4, np.int64), "key": map_state["key"][order].astype(np.int64), "dirs": d}
+    if map_state["overflowed"] or not E:
+        return out
+    sel = ((map_state["n"] >= max(min_n, 1)) & (map_state["m"] >= min_rows) & (map_state["last_seq"] >= since))[order]
+    mkey, mq = _voxel_align_voxels(map_state, min_n, min_rows, since)
+    M = len(mkey)
+    if not M:
+        return out
+    cells = np.array(map_state["params"]["cells"], np.int64)
+    c = np.stack([mkey & 0xFFFFF, (mkey >> 20) & 0xFFFFF, (mkey >> 40) & 0xFFFFF], -1)
+    N, s1, s2 = np.zeros(M, np.int64), np.zeros((M, 3), np.int64), np.zeros((M, 3, 3), np.int64)
+    for off in VOXEL_ALIGN_OFFSETS:
+        cc = c + np.array(off, np.int64)
+        on = ((cc >= 0) & (cc < cells)).all(-1)  # before a key is formed
+        key = np.where(on, cc[:, 0] | (cc[:, 1] << 20) | (cc[:, 2] << 40), -2)
+        at = np.minimum(np.searchsorted(mkey, key), M - 1)
+        hit = on & (mkey[at] == key)
+        e = np.where(hit[:, None], mq[at] - mq, 0)
+        N += hit
+        s1 += e
+        s2 += e[:, :, None] * e[:, None, :]
+    C = N[:, None, None] * s2 - s1[:, :, None] * s1[:, None, :]
+    T = C[:, 0, 0] + C[:, 1, 1] + C[:, 2, 2]
+    dd = d[:, :3].astype(np.int64)
+    s = (dd * dd).sum(1)
+    best, worst = np.full(M, -1, np.int64), np.full(M, -1, np.int64)
+    bQ, bs, wQ, ws = np.zeros(M, np.int64), np.ones(M, np.int64), np.zeros(M, np.int64), np.ones(M, np.int64)
+    for k in range(len(dd)):
+        if s[k] == 0:
+            continue
+        Qk = np.einsum("i,mij,j->m", dd[k], C, dd[k])
+        flatter = (best < 0) | (Qk * bs < bQ * s[k])  # strict: a tie stays with the lower index
+        best[flatter], bQ[flatter], bs[flatter] = k, Qk[flatter], s[k]
+        wider = (worst < 0) | (Qk * ws > wQ * s[k])
+        worst[wider], wQ[wider], ws[wider] = k, Qk[wider], s[k]
+    lam3, lam1 = bQ // bs, wQ // ws
+    lam2, given = _voxel_normal_verdict(N, T, lam1, lam3, min_nb, flat, wide)
+    given &= best >= 0
+    out["normal"][sel] = np.where(given, best, -1)
+    out["fit"][sel] = np.stack([N, lam1, lam2, lam3], -1)
+    out["counts"][:3] = M, int((N >= min_nb).sum()), int(given.sum())
+    return out
+
+
+def voxel_map_normals_brute(map_state, dirs, min_nb=5, flat=64, wide=16, min_n=1, min_rows=1, since=0):
+    """voxel_map_normals by a Python loop per voxel over all voxels of the map: Python ints, every comparison of two quotients by
+    fractions.Fraction, no key is formed for a neighbour cell and nothing is looked up.  The independent model."""
+    from fractions import Fraction
+    min_nb, flat, wide = _voxel_normal_words(min_nb, flat, wide)
+    d = _voxel_normal_table(dirs)
+    order = np.argsort(map_state["key"], kind="stable")
+    E = len(order)
+    out = {"normal": np.full(E, -1, np.int32), "fit": np.zeros((E, 4), np.int64), "counts": np.zeros(4, np.int64), "key": map_state["key"][order].astype(np.int64), "dirs": d}
+    if map_state["overflowed"]:
+        return out
+    voxels = []  # (entry in ascending key, cell, q) of the members
+    for at, i in enumerate(order.tolist()):
+        key, vn, S, m, last = int(map_state["key"][i]), int(map_state["n"][i]), map_state["S"][i].tolist(), int(map_state["m"][i]), int(map_state["last_seq"][i])
+        if vn >= max(min_n, 1) and m >= min_rows and last >= since:
+            cell = [(key >> (20 * k)) & 0xFFFFF for k in range(3)]
+            voxels.append((at, cell, [256 * cell[k] + ((S[k] // vn) >> 8) for k in range(3)]))
+    table = [[int(v) for v in row[:3]] for row in d.tolist()]
+    counts = [len(voxels), 0, 0, 0]
+    for at, cell, q in voxels:
+        es = [[qj[k] - q[k] for k in range(3)] for _, cj, qj in voxels if all(abs(cj[k] - cell[k]) <= 1 for k in range(3))]
+        N = len(es)
+        s1 = [sum(e[i] for e in es) for i in range(3)]
+        C = [[N * sum(e[i] * e[j] for e in es) - s1[i] * s1[j] for j in range(3)] for i in range(3)]
+        T = C[0][0] + C[1][1] + C[2][2]
+        best = worst = None
+        for k, dk in enumerate(table):
+            sk = sum(v * v for v in dk)
+            if sk == 0:
+                continue
+            ratio = Fraction(sum(dk[i] * C[i][j] * dk[j] for i in range(3) for j in range(3)), sk)
+            if best is None or ratio < best[0]:
+                best = (ratio, k)
+            if worst is None or ratio > worst[0]:
+                worst = (ratio, k)
+        lam3, lam1 = (0, 0) if best is None else (best[0].numerator // best[0].denominator, worst[0].numerator // worst[0].denominator)
+        lam2 = T - lam1 - lam3
+        given = best is not None and N >= min_nb and lam2 > 0 and 256 * lam3 <= flat * lam2 and 256 * lam2 >= wide * lam1
+        out["fit"][at] = (N, lam1, lam2, lam3)
+        out["normal"][at] = best[1] if given else -1
+        counts[1] += N >= min_nb
+        counts[2] += bool(given)
+    out["counts"][:] = counts
+    return out
+
+
+def _voxel_plane_setup(map_state, normal, dirs):
+    """normal as int64 per entry of the map in ascending key, with the entries' keys and the table's (x, y, z) as int64."""
+    d = _voxel_normal_table(dirs)
+    nrm = np.asarray(normal)
+    if nrm.dtype != np.int32 or nrm.shape != (len(map_state["key"]),):
+        raise ValueError("normal must be int32 [%d], one word per entry of the map in ascending key, got %s %s" % (len(map_state["key"]), nrm.dtype, nrm.shape))
+    return nrm.astype(np.int64), np.sort(map_state["key"]).astype(np.int64), d[:, :3].astype(np.int64)
+
+
+def _voxel_plane_words(wt, p, q, nu, o):
+    """(b, a [.,6]) of plane pairs as int64: b = nu . (q - p), a = (l x nu, nu) with the lever arm l = (p - o) >> 4."""
+    lever = (p - o) >> VOXEL_PLANE_LEVER_SHIFT  # arithmetic: a floor
+    return (nu * (q - p)).sum(-1), np.concatenate([np.cross(lever, nu).reshape(-1, 3), nu], -1)
+
+
+def voxel_map_align_plane_sums(map_state, xyz, n, counts, poses, origin, normal, dirs, max_dist=1.0, min_n=1, min_rows=1, since=0):
+    """The definition of include/stereo_vision_hip.h (Y2) in numpy: the sums of one round of point-to-plane alignment.  Rows, world, kept,
+    p, candidates, nearest and pair are voxel_map_align_sums', word for word; normal int32, one word per entry of the map in ascending key
+    (voxel_map_normals' "normal"; the stage takes it as it is), dirs voxel_map_normals' table.
+    -> {"sums": int64 [B,32], "pair_key": int64 [B,cap], "pair_d2": int32 [B,cap], "pair_normal": int32 [B,cap]}.
+
+      plane pair  a pair whose partner's normal is a direction of the table: 0 <= normal < K.  nu = dirs[normal] as integers.
+      per pair    l = (p - o) >> 4, an arithmetic shift: the lever arm in 1/16 of a cell.  b = nu . (q - p).  a = (l x nu, nu).
+      sums        VOXEL_PLANE_SUMS: inside, pairs - voxel_map_align_sums' -, planes, and over the plane pairs W = sum w, E = sum w b^2,
+                  g[6] = sum w a_i b, A[21] = sum w a_i a_j for i <= j row-major; 64-bit two's complement sums.  Contract: sum w
+                  (256 |l|max)^2 < 2^63.
+      per row     pair_key, pair_d2: voxel_map_align_sums'; pair_normal: the normal word of the nearest candidate where that is a
+                  direction of the table, else -1.
+    For an overflowed map every sum is 0 and every per-row word is -1."""
+    max_d2 = voxel_align_max_d2(max_dist)
+    xyz, n, counts, poses, origin = _voxel_align_setup(map_state, xyz, n, counts, poses, origin)
+    nrm, ekey, dd = _voxel_plane_setup(map_state, normal, dirs)
+    B, cap = xyz.shape[:2]
+    out = {"sums": np.zeros((B, 32), np.int64), "pair_key": np.full((B, cap), -1, np.int64), "pair_d2": np.full((B, cap), -1, np.int32), "pair_normal": np.full((B, cap), -1, np.int32)}
+    if map_state["overflowed"]:
+        return out
+    w = map_state["params"]
+    cells = np.array(w["cells"], np.int64)
+    vkey, vq = _voxel_align_voxels(map_state, min_n, min_rows, since)
+    if not len(vkey):  # a stand-in that no cell's key equals
+        vkey, vq = np.array([-1], np.int64), np.zeros((1, 3), np.int64)
+    iu = np.triu_indices(6)
+    for b in range(B):
+        rows = int(min(max(int(counts[b]), 0), cap))
+        wt = np.ones(rows, np.int64) if n is None else n[b, :rows].astype(np.int64)
+        at_row, c, p = _voxel_align_rows(w, xyz[b, :rows].astype(np.float64), wt, poses[b])
+        sums = out["sums"][b]
+        sums[0] = len(at_row)
+        best_d2, best_key, best_q = _voxel_align_nearest(cells, vkey, vq, c, p)
+        have = best_key >= 0
+        of = nrm[np.minimum(np.searchsorted(ekey, np.where(have, best_key, 0)), max(len(ekey) - 1, 0))] if len(ekey) else np.full(len(have), -1, np.int64)
+        of = np.where(have & (of >= 0) & (of < len(dd)), of, -1)
+        out["pair_key"][b, at_row[have]] = best_key[have]
+        out["pair_d2"][b, at_row[have]] = best_d2[have]
+        out["pair_normal"][b, at_row[have]] = of[have]
+        pair = have & (best_d2 <= max_d2)
+        plane = pair & (of >= 0)
+        sums[1], sums[2] = int(pair.sum()), int(plane.sum())
+        wp = wt[at_row[plane]]
+        with np.errstate(over="ignore"):
+            bb, a = _voxel_plane_words(wp, p[plane], best_q[plane], dd[of[plane]], origin[b])
+            sums[3], sums[4] = wp.sum(), (wp * bb * bb).sum()
+            sums[5:11] = ((wp * bb)[:, None] * a).sum(0)
+            sums[11:32] = ((wp[:, None] * a)[:, :, None] * a[:, None, :]).sum(0)[iu]
+    return out
+
+
+def voxel_map_align_plane_sums_brute(map_state, xyz, n, counts, poses, origin, normal, dirs, max_dist=1.0, min_n=1, min_rows=1, since=0):
+    """voxel_map_align_plane_sums by voxel_map_align_sums_brute's loop per row over all voxels - Python floats and ints, nothing looked up
+    by key - with the plane words added up in Python ints and wrapped to 64 bits at the end.  The independent model."""
+    max_d2 = voxel_align_max_d2(max_dist)
+    xyz, n, counts, poses, origin = _voxel_align_setup(map_state, xyz, n, counts, poses, origin)
+    nrm, ekey, dd = _voxel_plane_setup(map_state, normal, dirs)
+    B, cap = xyz.shape[:2]
+    out = {"sums": np.zeros((B, 32), np.int64), "pair_key": np.full((B, cap), -1, np.int64), "pair_d2": np.full((B, cap), -1, np.int32), "pair_normal": np.full((B, cap), -1, np.int32)}
+    if map_state["overflowed"]:
+        return out
+    w = map_state["params"]
+    by_key = np.argsort(map_state["key"], kind="stable").tolist()
+    table = dd.tolist()
+    voxels = []
+    for at, i in enumerate(by_key):
+        key, vn, S, m, last = int(map_state["key"][i]), int(map_state["n"][i]), map_state["S"][i].tolist(), int(map_state["m"][i]), int(map_state["last_seq"][i])
+        if vn >= max(min_n, 1) and m >= min_rows and last >= since:
+            cell = [(key >> (20 * k)) & 0xFFFFF for k in range(3)]
+            voxels.append((key, cell, [256 * cell[k] + ((S[k] // vn) >> 8) for k in range(3)], int(nrm[at])))
+    wrap = lambda v: (v + 2 ** 63) % 2 ** 64 - 2 ** 63  # noqa: E731
+    for b in range(B):
+        pose, o = [float(v) for v in poses[b]], [int(v) for v in origin[b]]
+        sums = [0] * 32
+        for i in range(max(0, min(int(counts[b]), cap))):
+            wt = 1 if n is None else int(n[b, i])
+            if wt <= 0:
+                continue
+            x, y, z = (float(v) for v in xyz[b, i])
+            c, p = [], []
+            for k in range(3):
+                with np.errstate(all="ignore"):
+                    Pw = float(((np.float64(pose[3 * k]) * x + np.float64(pose[3 * k + 1]) * y) + np.float64(pose[3 * k + 2]) * z) + np.float64(pose[9 + k]))
+                if not (w["lo"][k] < Pw < w["hi"][k]):
+                    break
+                t = (Pw - w["lo"][k]) / w["size"]
+                c.append(min(int(t), w["cells"][k] - 1))
+                p.append(256 * c[k] + (min(int((t - float(c[k])) * 65536.0), 65535) >> 8))
+            if len(c) < 3:
+                continue
+            sums[0] += 1
+            best = None
+            for key, cell, q, of in voxels:
+                if all(abs(cell[k] - c[k]) <= 1 for k in range(3)):
+                    d2 = sum((p[k] - q[k]) ** 2 for k in range(3))
+                    if best is None or (d2, key) < best[:2]:
+                        best = (d2, key, q, of)
+            if best is None:
+                continue
+            of = best[3] if 0 <= best[3] < len(table) else -1
+            out["pair_key"][b, i], out["pair_d2"][b, i], out["pair_normal"][b, i] = best[1], best[0], of
+            if best[0] > max_d2:
+                continue
+            sums[1] += 1
+            if of < 0:
+                continue
+            nu, q = table[of], best[2]
+            lever = [(p[k] - o[k]) >> VOXEL_PLANE_LEVER_SHIFT for k in range(3)]
+            bb = sum(nu[k] * (q[k] - p[k]) for k in range(3))
+            a = [lever[1] * nu[2] - lever[2] * nu[1], lever[2] * nu[0] - lever[0] * nu[2], lever[0] * nu[1] - lever[1] * nu[0]] + nu
+            sums[2] += 1
+            sums[3] += wt
+            sums[4] += wt * bb * bb
+            at = 11
+            for i6 in range(6):
+                sums[5 + i6] += wt * a[i6] * bb
+                for j6 in range(i6, 6):
+                    sums[at] += wt * a[i6] * a[j6]
+                    at += 1
+        out["sums"][b] = [wrap(v) for v in sums]
+    return out
+
+
+def voxel_align_solve_plane(sums, poses, origin, params, dof=6, min_pairs=6, rcond=1e-6):
+    """The fit of one point-to-plane round: from the sums of voxel_map_align_plane_sums, the poses they were taken under and their origin
+    -> (poses' float64 [B,12], ok bool [B], step float64 [B,2]), as voxel_align_solve.  A (6 x 6, symmetric) and g are made from Python
+    integers in double and scaled by sc_i = sqrt(max(A_ii, 1)); x = lstsq(A / sc sc^T, g / sc, rcond) / sc, whose minimum-norm solution
+    leaves a direction that nothing constrains alone.  omega = x[:3] / 16 - the lever arm is in 1/16 of a cell, the residual in 1/256 -,
+    R_d Rodrigues' rotation of omega, t_d = x[3:] in 1/256 of a cell; dof=4 solves the 4 x 4 system of (omega_z, t).  The new pose and
+    step are voxel_align_solve's formulas.  A frame with planes < min_pairs, or without a finite fit, keeps its pose: ok False, step 0."""
+    if dof not in (4, 6) or isinstance(dof, bool):
+        raise ValueError("dof must be 6 (all of the rotation) or 4 (yaw only), got %r" % (dof,))
+    if isinstance(min_pairs, bool) or int(min_pairs) != min_pairs:
+        raise ValueError("min_pairs must be an integer, got %r" % (min_pairs,))
+    if not (np.isfinite(float(rcond)) and 0 <= float(rcond) < 1):
+        raise ValueError("rcond must be in 0 .. 1, got %r" % (rcond,))
+    sums, poses = np.asarray(sums), voxel_map_pose_words(poses) if len(np.asarray(poses)) else np.zeros((0, 12))
+    B = len(poses)
+    origin = np.asarray(origin)
+    if sums.shape != (B, 32) or origin.shape != (B, 3):
+        raise ValueError("sums must be [%d,32] and origin [%d,3], got %s and %s" % (B, B, sums.shape, origin.shape))
+    lo, size = np.array(params["lo"]), np.float64(params["size"])
+    out, ok, step = poses.copy(), np.zeros(B, bool), np.zeros((B, 2))
+    free = [0, 1, 2, 3, 4, 5] if dof == 6 else [2, 3, 4, 5]
+    iu = np.triu_indices(6)
+    for b in range(B):
+        s = [int(v) for v in sums[b]]
+        if s[2] < max(int(min_pairs), 1) or s[3] <= 0:
+            continue
+        A = np.zeros((6, 6))
+        A[iu] = [float(v) for v in s[11:32]]
+        A = A + np.triu(A, 1).T
+        g = np.array([float(v) for v in s[5:11]])
+        A, g = A[np.ix_(free, free)], g[free]
+        sc = np.sqrt(np.maximum(np.diag(A), 1.0))
+        try:
+            x = np.linalg.lstsq(A / np.outer(sc, sc), g / sc, rcond=float(rcond))[0] / sc
+        except np.linalg.LinAlgError:
+            continue
+        full = np.zeros(6)
+        full[free] = x
+        om, td = full[:3] / 16.0, full[3:]
+        angle = float(np.sqrt((om * om).sum()))
+        K = np.array([[0.0, -om[2], om[1]], [om[2], 0.0, -om[0]], [-om[1], om[0], 0.0]])
+        if angle > 1e-12:
+            Rd = np.eye(3) + (np.sin(angle) / angle) * K + ((1.0 - np.cos(angle)) / (angle * angle)) * (K @ K)
+        else:
+            Rd = np.eye(3) + K
+        Xo = lo + origin[b].astype(np.float64) * size / 256.0
+        new = np.concatenate([(Rd @ poses[b, :9].reshape(3, 3)).reshape(9), Rd @ (poses[b, 9:] - Xo) + Xo + td * size / 256.0])
+        if not np.isfinite(new).all():
+            continue
+        out[b], ok[b], step[b] = new, True, (angle, float(np.sqrt((td * td).sum())) / 256.0)
+    return out, ok, step
+
+
+def voxel_align_plane_solver(dirs):
+    """voxel_align_loop's solver for the plane sums of a table: the 32 words, voxel_align_solve_plane, the planes as the pairs that count,
+    and 1 / the table's mean length as the unit of sqrt(E / W)."""
+    d = _voxel_normal_table(dirs)[:, :3].astype(np.float64)
+    length = np.sqrt((d * d).sum(1))
+    mean = float(length[length > 0].mean()) if (length > 0).any() else 1.0
+    return dict(words=32, solve=voxel_align_solve_plane, pairs=2, W=3, D=4, unit=1.0 / mean)
 
 
 GROUND_BINS_MIN, GROUND_BINS_MAX = 8, 4096
@@ -3569,11 +3977,12 @@ def main(argv=None):
                              "and +-DYAW radians around its line (NX x NY x NZ x NYAW poses, odd, default 5,5,3,5; the line itself wins ties) "
                              "and inserted at the best pose.  The refined poses are written next to FILE.ply as <FILE without "
                              ".ply>.poses.txt, one 'x y z yaw' per frame")
-    parser.add_argument("--voxel-align", type=str, default="", metavar="ROUNDS[,MAX_DIST_CELLS[,DOF]]",
+    parser.add_argument("--voxel-align", type=str, default="", metavar="ROUNDS[,MAX_DIST_CELLS[,DOF[,point|plane]]]",
                         help="with --voxel-map: before a batch's frames are inserted, refine their poses - the lines of --poses, or what "
                              "--voxel-match made of them - by at most ROUNDS rounds of iterative closest point against the voxel map built "
                              "so far: every row is paired with the nearest voxel within MAX_DIST_CELLS cells (default 1) and the pairs are "
-                             "fitted in closed form, DOF 6 (default: roll and pitch as well) or 4 (yaw and the translation).  The refined "
+                             "fitted in closed form, DOF 6 (default: roll and pitch as well) or 4 (yaw and the translation); 'plane' as the "
+                             "fourth field fits the rows to the planes of the voxels' normals instead of to their means (default: point).  The refined "
                              "poses are written next to FILE.ply as <FILE without .ply>.aligned.txt, twelve words per frame: the rotation "
                              "row-major, then the translation")
     parser.add_argument("--occupancy", type=str, default="", metavar="DIR",
@@ -3860,15 +4269,17 @@ def cli_voxel_carry_text(stats):
 
 
 def cli_voxel_align_spec(text):
-    """(rounds, max_dist in cells, dof) of --voxel-align ROUNDS[,MAX_DIST_CELLS[,DOF]]; ValueError for what voxel_map_align refuses."""
+    """(rounds, max_dist in cells, dof, method) of --voxel-align ROUNDS[,MAX_DIST_CELLS[,DOF[,point|plane]]]; ValueError for what
+    voxel_map_align refuses."""
     words = text.split(",")
-    if not 1 <= len(words) <= 3:
-        raise ValueError("%d words, not ROUNDS[,MAX_DIST_CELLS[,DOF]]" % len(words))
+    if not 1 <= len(words) <= 4:
+        raise ValueError("%d words, not ROUNDS[,MAX_DIST_CELLS[,DOF[,point|plane]]]" % len(words))
     rounds, max_dist, dof = int(words[0]), float(words[1]) if len(words) > 1 else 1.0, int(words[2]) if len(words) > 2 else 6
-    if rounds < 1 or dof not in (4, 6):
-        raise ValueError("ROUNDS >= 1 and DOF 4 or 6, got %r" % (text,))
+    method = words[3] if len(words) > 3 else "point"
+    if rounds < 1 or dof not in (4, 6) or method not in VOXEL_ALIGN_METHODS:
+        raise ValueError("ROUNDS >= 1, DOF 4 or 6 and point or plane, got %r" % (text,))
     voxel_align_max_d2(max_dist)
-    return rounds, max_dist, dof
+    return rounds, max_dist, dof, method
 
 
 def cli_voxel_carve_spec(reach_m, min_miss, ratio, size):
@@ -4003,7 +4414,7 @@ def _run_batched(args, ldir, rdir, files):
                             seen = model.render(went, rig.render_camera(args.voxel), transform=(CAMERA_TO_VEHICLE, None), measured=d1, tol=args.voxel_render_spec[1])
                         if args.voxel_match_window is None:
                             if args.voxel_align_spec is not None and model.seq > 0:  # the whole batch against the frames before it
-                                went = model.align(voxels[0], voxels[3], voxels[5], went, args.voxel_align_spec[0], args.voxel_align_spec[1], args.voxel_align_spec[2])[0]
+                                went = model.align(voxels[0], voxels[3], voxels[5], went, args.voxel_align_spec[0], args.voxel_align_spec[1], args.voxel_align_spec[2], method=args.voxel_align_spec[3])[0]
                             model.update(voxels[0], voxels[1], voxels[3], voxels[5], went)
                         for k in range(len(names) if args.voxel_match_window is not None else 0):  # one at a time: against the frames before it
                             one = [t[k:k + 1] for t in (voxels[0], voxels[1], voxels[3], voxels[5])]
@@ -4012,7 +4423,7 @@ def _run_batched(args, ldir, rdir, files):
                             refined_3d.append(to)
                             went[k] = voxel_map_pose(to[0], to[1], to[3], to[2])
                             if args.voxel_align_spec is not None and model.seq > 0:
-                                went[k] = model.align(one[0], one[2], one[3], went[k:k + 1], args.voxel_align_spec[0], args.voxel_align_spec[1], args.voxel_align_spec[2])[0][0]
+                                went[k] = model.align(one[0], one[2], one[3], went[k:k + 1], args.voxel_align_spec[0], args.voxel_align_spec[1], args.voxel_align_spec[2], method=args.voxel_align_spec[3])[0][0]
                             model.update(*one, went[k:k + 1])
                         aligned_3d.extend(went)
                         if args.voxel_carve_spec is not None:  # the camera's centre is the origin of the vehicle axes: CAMERA_TO_VEHICLE only turns
