@@ -289,6 +289,14 @@ int sv_debug_set(sv_handle *h, const char *key, int value);
  *   "wta" : an integer in 0 .. disp_max, or one of dense_match's two invalid values: -10 (no triangle / low texture), -1 (no match).
  * Returns SV_OK, or SV_ERR_ARG with a text for sv_last_error (no keep_debug, unknown stage, one map missing, a value outside the contract). */
 int sv_debug_inject(sv_handle *h, const char *stage, const float *left, const float *right);
+/* The third stage of that hook, "lattice", with a signature of its own (the lattice is 16-bit): one int16 [Hc][Wc] support lattice,
+ * row-major like the dcan_raw snapshot, wc x hc = the handle's lattice size (sv_debug_get "dcan_dims").  Phase 1 of every later chunk
+ * copies it, in stream order, over the support matching's lattice of the chunk's last pair (the one the snapshots describe) before
+ * the lattice filters run and before the lattice is downloaded: the GPU filters, the host filters and dcan_raw all see it.  It stays
+ * staged beside a "wta" / "lr" injection; lattice == NULL, or sv_debug_inject(h, stage, NULL, NULL), clears it.
+ * Value contract - what the support matching can leave behind: -1 or an integer in 0 .. disp_max, lattice row 0 and column 0 all zero.
+ * Returns SV_OK, or SV_ERR_ARG with a text (no keep_debug, another lattice size, a value outside the contract). */
+int sv_debug_inject_lattice(sv_handle *h, const int16_t *lattice, int wc, int hc);
 
 /* Per-stage intermediates of the last pair processed (cfg.keep_debug != 0).  Names and layouts follow
  * oracle/elas_oracle.h: desc1 desc2 dcan_raw support tri1 tri2 planes1 planes2 grid1 grid2 wta1 wta2 lr1 lr2
@@ -319,6 +327,18 @@ int sv_host_support_filter(const sv_params *p, int16_t *dcan, int width, int hei
 /* The same filters with the lattice shared between `threads` threads, as single-pair calls do with the pool threads that sit next to the
  * calling thread (csrc/host_stage.cpp: the order-dependent filter splits into a parallel classification and a short serial pass). */
 int sv_host_support_filter_threads(const sv_params *p, int16_t *dcan, int width, int height, int32_t *support, int cap, int threads);
+/* Test hook: the same filters by the six kernels of the GPU lattice filter (csrc/kernels.hip: k_filter_*), without a handle, on the current
+ * device.  lattices: int16 [n][Hc][Wc], row-major like dcan above and the dcan_raw snapshot, n lattices of one size filtered by ONE
+ * launch of each kernel in a workspace the call allocates; prime (may be NULL): n more lattices that go through the same workspace and
+ * output buffers first and whose results are dropped.  Out: support int32 [n][cap][3] (the first counts[i] triples of list i),
+ * counts int32 [n], stats (may be NULL) int32 [n][3] = {uncertain points after the classification, refinement rounds run, points left
+ * to the sequential rest (0 when the rounds settle everything)} of the resolve step.
+ * Returns SV_OK; SV_ERR_ARG with a text for sv_last_error(NULL), and nothing runs, for what sv_create keeps on the host
+ * (incon_window_size > 5, incon_min_support > 60, incon_threshold >= 4096, a lattice beyond the resolve step's block table), for
+ * cap < (Wc-1)*(Hc-1)+6, for a lattice value outside -1 .. disp_max, and for a lattice whose row 0 or column 0 is not all zero (the
+ * support matching never writes there); SV_ERR_HIP for a failed HIP call. */
+int sv_gpu_support_filter(const sv_params *p, const int16_t *lattices, const int16_t *prime, int n, int width, int height, int32_t *support, int cap, int32_t *counts,
+                          int32_t *stats);
 int sv_host_delaunay(const int32_t *xy, int n, int32_t *tri_out, int cap);
 /* Test hook: exhaustive comparison, on the current device, of the adaptive-mean kernel's division shortcut (v_rcp_f32 + one FMA
  * correction; kernels.hip: amean_div) with the IEEE division: every float mantissa, both signs, 31 exponents, the sixteen divisors

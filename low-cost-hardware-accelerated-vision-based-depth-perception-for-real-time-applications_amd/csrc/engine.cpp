@@ -250,6 +250,8 @@ struct sv_handle {
     std::map<std::string, std::vector<uint8_t>> dbg;
     int inj_stage = 0;                         // sv_debug_inject: 0 none, 1 "wta", 2 "lr"
     std::vector<float> inj_maps[2];            // ... the staged left / right maps, [Hm][Wm] each
+    std::vector<int32_t> dbg_few;              // keep_debug: the support list of a pair with fewer than three points (it never reaches the blob)
+    std::vector<int16_t> inj_lattice;          // sv_debug_inject_lattice: the staged support lattice, transposed [Wc][Hc] like dev.dcan (empty: none)
     unsigned long long *d_counters = nullptr;  // work counters of the matching kernels (sv_debug_counters)
     uint8_t *dbg_desc = nullptr;               // keep_debug: descriptor images [cap][2][N][16] for the stage snapshot
     bool lat_trace = false;                    // SV_LAT_TRACE=1: wall-clock split of the latency path, printed by sv_destroy
@@ -621,6 +623,10 @@ void issue_phase1(sv_handle *h, Slot *s) {
     };
     launch_sobel(k, s->in_left, s->in_right, s->in_pair, s->in_stride, s->dev, s->n, h->sP1);
     launch_support(k, s->dev, s->n, h->sP1);
+    if (h->cfg.keep_debug && !h->inj_lattice.empty()) {  // tests (sv_debug_inject_lattice): a painted lattice in place of k_support's, for both filters and the snapshot
+        HIP_TRY(hipStreamSynchronize(h->sP1));
+        HIP_TRY(hipMemcpy(s->dev.dcan + (size_t)(s->n - 1) * lat, h->inj_lattice.data(), sizeof(int16_t) * (size_t)lat, hipMemcpyHostToDevice));
+    }
     lap(0);
     hipStream_t tail = h->sP1;
     if (h->gpu_filter) {
@@ -1321,6 +1327,7 @@ void run_task(sv_handle *h, HostScratch *sc, const Task &t) {
         if (meta[7]) h->gpu_tri_pairs.fetch_add(1, std::memory_order_relaxed);
     }
     if (ns < 3) {  // elas.cpp:63-69
+        if (h->cfg.keep_debug && t.pair == s->n - 1) h->dbg_few.assign(sc->sup.begin(), sc->sup.begin() + 3 * (size_t)ns);  // (read by issue_phase2, behind pair_done)
         pair_done(h, s);
         return;
     }
@@ -1565,7 +1572,8 @@ void issue_phase2(sv_handle *h, Slot *s, hipStream_t st) {
     const size_t off = s->blob_off.load();
     if (dbg) {
         const int32_t *meta = blob + (size_t)(n - 1) * META_WORDS;
-        dbg_put(h, "support", blob + meta[1], meta[0] >= 3 ? (size_t)meta[0] * 3 : 0);
+        if (meta[0] >= 3) dbg_put(h, "support", blob + meta[1], (size_t)meta[0] * 3);
+        else dbg_put(h, "support", h->dbg_few.data(), std::min(h->dbg_few.size(), (size_t)std::max(meta[0], 0) * 3));  // the oracle keeps the list of such a pair too
         dbg_put(h, "tri1", blob + meta[3], (size_t)meta[2] * 3);
         dbg_put(h, "tri2", blob + meta[5], (size_t)meta[4] * 3);
     }
@@ -2901,11 +2909,13 @@ int sv_debug_inject(sv_handle *h, const char *stage, const float *left, const fl
         h->inj_stage = 0;
         h->inj_maps[0].clear();
         h->inj_maps[1].clear();
+        h->inj_lattice.clear();
         return SV_OK;
     }
     const std::string name(stage ? stage : "");
     const int which = name == "wta" ? 1 : (name == "lr" ? 2 : 0);
-    if (!which) return refuse("unknown stage '" + name + "' (\"wta\" or \"lr\")");
+    if (name == "lattice") return refuse("stage \"lattice\" takes one int16 lattice: sv_debug_inject_lattice");
+    if (!which) return refuse("unknown stage '" + name + "' (\"wta\" or \"lr\"; \"lattice\" through sv_debug_inject_lattice)");
     if (!left || !right) return refuse("both maps or neither");
     // only values the engine itself produces at that stage: the kernels behind it were written for nothing else
     const size_t N = h->kp.d.Nm;
@@ -2924,6 +2934,52 @@ int sv_debug_inject(sv_handle *h, const char *stage, const float *left, const fl
     h->inj_maps[0].assign(left, left + N);
     h->inj_maps[1].assign(right, right + N);
     h->inj_stage = which;
+    return SV_OK;
+}
+
+// What k_support leaves in a lattice, and all the GPU filters were written for: -1 or a disparity in 0 .. disp_max, and zeros in lattice
+// row 0 and column 0 (elas.cpp:388-395 never visits them, the lattice starts out cleared).  d: row-major [Hc][Wc].
+static bool lattice_in_contract(const int16_t *d, int Wc, int Hc, int disp_max, std::string &why) {
+    char b[160];
+    for (int v = 0; v < Hc; v++)
+        for (int u = 0; u < Wc; u++) {
+            const int x = d[(size_t)v * Wc + u];
+            if (x < -1 || x > disp_max) {
+                snprintf(b, sizeof(b), "lattice point (%d,%d): %d is neither -1 nor a disparity in 0..%d", u, v, x, disp_max);
+                why = b;
+                return false;
+            }
+            if ((u == 0 || v == 0) && x != 0) {
+                snprintf(b, sizeof(b), "lattice point (%d,%d) of row 0 / column 0 holds %d, not 0", u, v, x);
+                why = b;
+                return false;
+            }
+        }
+    return true;
+}
+
+int sv_debug_inject_lattice(sv_handle *h, const int16_t *lattice, int wc, int hc) {
+    if (!h) {
+        g_create_error = "sv_debug_inject_lattice: null handle";
+        return SV_ERR_ARG;
+    }
+    (void)wait_jobs(h);  // the issuer reads the staged lattice while a pair is in flight
+    auto refuse = [h](const std::string &why) {
+        h->error = "sv_debug_inject_lattice: " + why;
+        return SV_ERR_ARG;
+    };
+    if (!h->cfg.keep_debug) return refuse("the handle was not created with keep_debug");
+    if (!lattice) {
+        h->inj_lattice.clear();
+        return SV_OK;
+    }
+    const Dims &d = h->kp.d;
+    if (wc != d.Wc || hc != d.Hc) return refuse("the handle's lattice is " + std::to_string(d.Wc) + " x " + std::to_string(d.Hc) + " (Wc x Hc), not " + std::to_string(wc) + " x " + std::to_string(hc));
+    std::string why;
+    if (!lattice_in_contract(lattice, d.Wc, d.Hc, d.disp_max, why)) return refuse(why);
+    h->inj_lattice.resize((size_t)d.Wc * d.Hc);
+    for (int v = 0; v < d.Hc; v++)
+        for (int u = 0; u < d.Wc; u++) h->inj_lattice[(size_t)u * d.Hc + v] = lattice[(size_t)v * d.Wc + u];
     return SV_OK;
 }
 
@@ -3040,6 +3096,86 @@ int sv_host_support_filter(const sv_params *p, int16_t *dcan, int width, int hei
 int sv_host_support_filter_threads(const sv_params *p, int16_t *dcan, int width, int height, int32_t *support, int cap, int threads) {
     if (!p || !dcan || !support || threads < 1) return SV_ERR_ARG;
     return support_filter_threads(*p, dcan, width, height, support, cap, threads);
+}
+
+// Test hook: the six kernels of the GPU lattice filter on lattices of the caller's choice, without a handle: `n` lattices of one size in
+// one launch, in a workspace of its own.  Refuses (SV_ERR_ARG and a text, nothing runs) what sv_create keeps on the host and what
+// k_support cannot have written.  prime (may be NULL): `n` more lattices that go through the same workspace and output buffers first and
+// whose results are dropped - whatever a launch leaves behind there is what the next chunk of a slot finds.
+int sv_gpu_support_filter(const sv_params *p, const int16_t *lattices, const int16_t *prime, int n, int width, int height, int32_t *support, int cap, int32_t *counts,
+                          int32_t *stats) {
+    auto refuse = [](const std::string &why) {
+        g_create_error = "sv_gpu_support_filter: " + why;
+        return SV_ERR_ARG;
+    };
+    if (!p || !lattices || !support || !counts) return refuse("null argument");
+    if (n < 1 || n > 4096) return refuse("n must be in 1..4096");
+    if (width < 1 || height < 1 || width > 8192 || height > 4096) return refuse("unsupported image size (1..8192 x 1..4096)");
+    if (p->candidate_stepsize < 1) return refuse("candidate_stepsize must be positive");
+    if (p->disp_max < 0 || p->disp_max > 1023) return refuse("disp_max must be in [0,1023]");
+    if (p->incon_window_size < 0 || p->incon_window_size > 5) return refuse("incon_window_size must be in 0..5 (larger windows stay on the host)");
+    if (p->incon_min_support < 0 || p->incon_min_support > 60) return refuse("incon_min_support must be in 0..60 (larger counts stay on the host)");
+    if (p->incon_threshold < 0 || p->incon_threshold >= 4096) return refuse("incon_threshold must be in 0..4095 (larger thresholds stay on the host)");
+    KParams k{};
+    Dims &d = k.d;
+    d.W = width;
+    d.H = height;
+    d.N = width * height;
+    d.step = p->candidate_stepsize + (p->subsampling ? p->candidate_stepsize % 2 : 0);  // (fill_kparams)
+    d.Wc = (d.W + d.step - 1) / d.step;
+    d.Hc = (d.H + d.step - 1) / d.step;
+    d.disp_max = p->disp_max;
+    d.D = p->disp_max + 1;
+    d.max_pts = (d.Wc - 1) * (d.Hc - 1) + 6;
+    k.add_corners = p->add_corners;
+    const size_t lat = (size_t)d.Wc * d.Hc;
+    if (lat > support_filter_max_lattice()) return refuse("a lattice of " + std::to_string(lat) + " points is beyond the resolve step's block table (" + std::to_string(support_filter_max_lattice()) + ")");
+    if (cap < d.max_pts) return refuse("cap " + std::to_string(cap) + " is below (Wc-1)*(Hc-1)+6 = " + std::to_string(d.max_pts));
+    std::string why;
+    const int16_t *passes[2] = {prime, lattices};
+    std::vector<int16_t> T[2];  // the device layout: [n][Wc][Hc]
+    for (int q = 0; q < 2; q++) {
+        if (!passes[q]) continue;
+        for (int i = 0; i < n; i++)
+            if (!lattice_in_contract(passes[q] + (size_t)i * lat, d.Wc, d.Hc, d.disp_max, why)) return refuse(std::string(q ? "" : "prime ") + "lattice " + std::to_string(i) + ", " + why);
+        T[q].resize((size_t)n * lat);
+        for (int i = 0; i < n; i++)
+            for (int v = 0; v < d.Hc; v++)
+                for (int u = 0; u < d.Wc; u++) T[q][(size_t)i * lat + (size_t)u * d.Hc + v] = passes[q][(size_t)i * lat + (size_t)v * d.Wc + u];
+    }
+    SlotDev s{};
+    s.cap = n;
+    int32_t *d_stats = nullptr;
+    int rc = SV_OK;
+    const LaunchHook saved = g_launch_hook;
+    g_launch_hook = {nullptr, nullptr};
+    try {
+        HIP_TRY(hipMalloc((void **)&s.dcan, sizeof(int16_t) * (size_t)n * lat));
+        HIP_TRY(hipMalloc((void **)&s.fsup, sizeof(int32_t) * 3 * (size_t)n * d.max_pts));
+        HIP_TRY(hipMalloc((void **)&s.fnsup, sizeof(int32_t) * (size_t)n));
+        HIP_TRY(hipMalloc(&s.flt_ws, support_filter_ws_bytes(k, n)));
+        if (stats) HIP_TRY(hipMalloc((void **)&d_stats, sizeof(int32_t) * 3 * (size_t)n));
+        for (int q = 0; q < 2; q++) {
+            if (!passes[q]) continue;
+            HIP_TRY(hipMemcpy(s.dcan, T[q].data(), sizeof(int16_t) * T[q].size(), hipMemcpyHostToDevice));
+            launch_support_filter(k, p->incon_window_size, p->incon_threshold, p->incon_min_support, s, n, nullptr, d_stats);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipDeviceSynchronize());
+        }
+        HIP_TRY(hipMemcpy(counts, s.fnsup, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+        if (stats) HIP_TRY(hipMemcpy(stats, d_stats, sizeof(int32_t) * 3 * (size_t)n, hipMemcpyDeviceToHost));
+        for (int i = 0; i < n; i++) {
+            if (counts[i] < 0 || counts[i] > d.max_pts) throw std::runtime_error("corrupt support count from the GPU filter");
+            HIP_TRY(hipMemcpy(support + (size_t)i * cap * 3, s.fsup + (size_t)i * d.max_pts * 3, sizeof(int32_t) * 3 * (size_t)counts[i], hipMemcpyDeviceToHost));
+        }
+    } catch (const std::exception &e) {
+        g_create_error = std::string("sv_gpu_support_filter: ") + e.what();
+        rc = SV_ERR_HIP;
+    }
+    g_launch_hook = saved;
+    for (void *q : {(void *)s.dcan, (void *)s.fsup, (void *)s.fnsup, s.flt_ws, (void *)d_stats})
+        if (q) (void)hipFree(q);
+    return rc;
 }
 
 int sv_host_delaunay(const int32_t *xy, int n, int32_t *tri_out, int cap) {

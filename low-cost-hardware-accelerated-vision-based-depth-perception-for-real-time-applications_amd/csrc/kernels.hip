@@ -736,7 +736,7 @@ __global__ __launch_bounds__(FCL_THREADS) void k_filter_classify(Dims d, int win
 size_t support_filter_max_lattice() { return (size_t)RSV_MAX_BLOCKS * FCL_THREADS; }
 __global__ __launch_bounds__(RSV_THREADS) void k_filter_resolve(Dims d, int win, int thr, int need, uint32_t *fcs, const uint32_t *__restrict__ useg,
                                                                 const int32_t *__restrict__ ucnt, int nb, uint32_t *__restrict__ ulist, uint32_t *__restrict__ urest, int32_t *__restrict__ bcnt,
-                                                                int nb2) {
+                                                                int nb2, int32_t *__restrict__ stats) {
     const int pair = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     for (int i = tid; i < nb2; i += RSV_THREADS) bcnt[(size_t)pair * nb2 + i] = 0;  // the collect blocks' point counts: the horizontal pass adds to them
     const int Hc = d.Hc, lat = d.Wc * Hc;
@@ -753,7 +753,14 @@ __global__ __launch_bounds__(RSV_THREADS) void k_filter_resolve(Dims d, int win,
     for (int b = b_lo; b < b_hi; b++) mine += cnt[b];
     int n_unc;
     int pos = block_exclusive_scan<RSV_THREADS>(mine, s_wave, &n_unc);
-    if (n_unc == 0) return;
+    // tests (sv_gpu_support_filter): per pair {uncertain points, rounds run, points left to the sequential rest}; the engine passes no pointer
+    auto report = [&](int rounds, int n_rest) {
+        if (stats && tid == 0) stats[3 * pair] = n_unc, stats[3 * pair + 1] = rounds, stats[3 * pair + 2] = n_rest;
+    };
+    if (n_unc == 0) {
+        report(0, 0);
+        return;
+    }
     for (int b = b_lo; b < b_hi; b++) {
         s_pref[b] = pos;
         pos += cnt[b];
@@ -775,8 +782,8 @@ __global__ __launch_bounds__(RSV_THREADS) void k_filter_resolve(Dims d, int win,
     // for sure, earlier neighbours that are certainly dropped never count.  (A round only reads states of EARLIER points and
     // only turns UNC into KEEP/DROP; both decisions stay valid whatever the remaining UNC points become, so concurrent
     // updates are benign.)  The rounds end as soon as one of them leaves nothing behind.
-    int left = 1;
-    for (int round = 0; round < 3 && left; round++) {
+    int left = 1, rounds = 0;
+    for (int round = 0; round < 3 && left; round++, rounds++) {
         int open = 0;
         for (int q = tid; q < n_unc; q += RSV_THREADS) {
             const int idx = (int)list[q];
@@ -830,7 +837,10 @@ __global__ __launch_bounds__(RSV_THREADS) void k_filter_resolve(Dims d, int win,
         __threadfence_block();
         left = __syncthreads_or(open);
     }
-    if (!left) return;
+    if (!left) {
+        report(rounds, 0);
+        return;
+    }
     // what is still uncertain, in order
     int n_rest = 0;
     {
@@ -845,6 +855,7 @@ __global__ __launch_bounds__(RSV_THREADS) void k_filter_resolve(Dims d, int win,
         __threadfence_block();
         __syncthreads();
     }
+    report(rounds, n_rest);
     // ... resolved in scan order by one wavefront: lanes = the earlier neighbours (win*(2win+1) + win <= 60 for win <= 5)
     if (tid < 64) {
         const int rowlen = 2 * win + 1, n_early = win * rowlen + win;
@@ -1133,7 +1144,7 @@ size_t support_filter_ws_bytes(const KParams &k, int cap) {  // per slot: segmen
     return (size_t)cap * (lat * (4 + 4 + 2 + 2) + filter_cs_stride((int)lat) * 4 + nb * 4 + nb2 * (4 * 8 + 4) + 16) + 256;
 }
 
-void launch_support_filter(const KParams &k, int win, int thr, int need, const SlotDev &s, int n, hipStream_t st) {
+void launch_support_filter(const KParams &k, int win, int thr, int need, const SlotDev &s, int n, hipStream_t st, int32_t *stats) {
     const size_t lat = (size_t)k.d.Wc * k.d.Hc, cap = (size_t)s.cap;
     const int nb = (int)((lat + FCL_THREADS - 1) / FCL_THREADS), nb2 = filter_collect_blocks((int)lat);
     uint8_t *base = static_cast<uint8_t *>(s.flt_ws);
@@ -1153,7 +1164,7 @@ void launch_support_filter(const KParams &k, int win, int thr, int need, const S
     if (nb > RSV_MAX_BLOCKS) throw std::runtime_error("support_filter: lattice too large for the resolve step's block table");
     // (urest: the remaining points after the rounds; they overwrite nothing the rounds' list still needs - a buffer of its own: latC is free until the horizontal pass)
     SV_LAUNCH(K_SUPPORT_FILTER, k_filter_resolve, dim3(n), dim3(RSV_THREADS), sizeof(int) * ((size_t)nb + 1), st, k.d, win, thr, need, fcs, useg, ucnt, nb, ulist,
-              reinterpret_cast<uint32_t *>(latB), bcnt, nb2);
+              reinterpret_cast<uint32_t *>(latB), bcnt, nb2, stats);
     SV_LAUNCH(K_SUPPORT_FILTER, k_filter_vertical, dim3((k.d.Wc + SW - 1) / SW, n), dim3(FRD_THREADS), v_lds, st, k.d, SW, fcs, latB);
     SV_LAUNCH(K_SUPPORT_FILTER, k_filter_horizontal, dim3((k.d.Hc + SH - 1) / SH, n), dim3(FRD_THREADS), h_lds, st, k.d, SH, latB, latC, bcnt, nb2);
     SV_LAUNCH(K_SUPPORT_FILTER, k_filter_collect, dim3(nb2, n), dim3(FLT_THREADS), 0, st, k, latC, bcnt, bkey, s.fsup);

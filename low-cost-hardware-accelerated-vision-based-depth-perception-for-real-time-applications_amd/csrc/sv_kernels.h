@@ -103,7 +103,8 @@ size_t support_filter_max_lattice();                          // lattice points 
 size_t support_filter_ws_bytes(const KParams &k, int cap);
 size_t ccl_ws_bytes(const KParams &k, int maps_cap);
 size_t ccl_lds_bytes(const KParams &k);
-void launch_support_filter(const KParams &k, int win, int thr, int need, const SlotDev &s, int n, hipStream_t st);
+void launch_support_filter(const KParams &k, int win, int thr, int need, const SlotDev &s, int n, hipStream_t st,
+                           int32_t *stats = nullptr);  // stats (tests): device int32 [n][3] = uncertain points, refinement rounds run, points left to the sequential rest
 size_t grid_masks_words(const KParams &k, int cap);  // gmaskA and tile_cnt are ONE allocation of grid_clear_bytes (cleared by one memset)
 size_t raster_tiles(const KParams &k);
 size_t grid_clear_bytes(const KParams &k, int cap);

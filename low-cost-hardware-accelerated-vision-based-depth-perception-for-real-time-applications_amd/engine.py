@@ -203,11 +203,23 @@ class StereoEngine:
 
     def debug_inject(self, stage, left=None, right=None):
         """Test hook (sv_debug_inject): float32 [map_height, map_width] maps that replace dense_match's (stage "wta") or the L/R check's
-        (stage "lr") for every later pair of this keep_debug handle; left = right = None clears them.  The library refuses values the
-        engine itself cannot produce at that stage (include/stereo_vision_hip.h)."""
+        (stage "lr") for every later pair of this keep_debug handle; left = right = None clears them.  Stage "lattice" takes ONE int16
+        [Hc, Wc] support lattice (left) that replaces the support matching's in front of the lattice filters.  The library refuses values
+        the engine itself cannot produce at that stage (include/stereo_vision_hip.h)."""
         L = lib()
         L.sv_debug_inject.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_void_p]
         L.sv_debug_inject.restype = ctypes.c_int
+        if stage == "lattice" and left is not None:
+            # the third stage (sv_debug_inject_lattice): ONE int16 [Hc, Wc] support lattice in place of the support matching's, in front
+            # of the lattice filters; -1 or 0 .. disp_max, row 0 and column 0 zero
+            if right is not None:
+                raise ValueError("stage \"lattice\" takes one lattice")
+            if not (isinstance(left, np.ndarray) and left.dtype == np.int16 and left.ndim == 2):
+                raise ValueError("the lattice must be an int16 array [Hc,Wc]")
+            lat = np.ascontiguousarray(left)
+            L.sv_debug_inject_lattice.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
+            L.sv_debug_inject_lattice.restype = ctypes.c_int
+            return self._check(L.sv_debug_inject_lattice(self._h, lat.ctypes.data, lat.shape[1], lat.shape[0]))
         if left is None and right is None:
             return self._check(L.sv_debug_inject(self._h, stage.encode(), None, None))
         maps = []
@@ -2839,6 +2851,40 @@ def host_support_filter(params, dcan, width, height, threads=0, lattice=False):
     if n < 0:
         raise StereoError("support capacity")
     return (out[:n].copy(), d) if lattice else out[:n].copy()
+
+
+def gpu_support_filter(params, lattices, width, height, stats=False, prime=None):
+    """The same filters by the kernels of the GPU lattice filter (test hook, sv_gpu_support_filter): lattices int16 [n, Hc, Wc] (or one
+    [Hc, Wc]), all filtered by one launch.  Returns (lists, counts): lists[i] the (k, 3) int32 support points of lattice i; with stats=True
+    also int32 [n, 3] = uncertain points, refinement rounds run, points left to the sequential rest.  prime: as many lattices of the same
+    size that go through the same workspace first.  The library refuses (StereoError) parameters the engine keeps on the host and lattices
+    the support matching cannot have written."""
+    share_hip_runtime_with_torch()
+    lat = np.ascontiguousarray(lattices, dtype=np.int16)
+    if lat.ndim == 2:
+        lat = lat[None]
+    if lat.ndim != 3 or lat.shape[0] < 1:
+        raise ValueError("lattices must be int16 [n,Hc,Wc]")
+    pr = None
+    if prime is not None:
+        pr = np.ascontiguousarray(prime, dtype=np.int16).reshape((-1,) + lat.shape[1:])
+        if pr.shape != lat.shape:
+            raise ValueError("prime must have the shape of lattices")
+    step = params.candidate_stepsize + (params.candidate_stepsize % 2 if params.subsampling else 0)
+    if step < 1 or lat.shape[1:] != ((height + step - 1) // step, (width + step - 1) // step):
+        raise ValueError("a %d x %d image at step %d has another lattice than %s" % (width, height, step, lat.shape[1:]))
+    n, cap = lat.shape[0], (lat.shape[1] - 1) * (lat.shape[2] - 1) + 6
+    out, counts, st = np.zeros((n, cap, 3), np.int32), np.zeros(n, np.int32), np.zeros((n, 3), np.int32)
+    L = lib()
+    L.sv_gpu_support_filter.argtypes = [ctypes.POINTER(SvParams), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                                        ctypes.c_void_p, ctypes.c_void_p]
+    L.sv_gpu_support_filter.restype = ctypes.c_int
+    rc = L.sv_gpu_support_filter(ctypes.byref(params), lat.ctypes.data, None if pr is None else pr.ctypes.data, n, int(width), int(height), out.ctypes.data, cap, counts.ctypes.data,
+                                 st.ctypes.data if stats else None)
+    if rc != 0:
+        raise StereoError("sv_gpu_support_filter failed (%d): %s" % (rc, L.sv_last_error(None).decode()))
+    lists = [out[i, :counts[i]].copy() for i in range(n)]
+    return (lists, counts, st) if stats else (lists, counts)
 
 
 def gpu_delaunay(xy, reps=1):

@@ -234,7 +234,8 @@ def _same(a, b):
 @pytest.mark.parametrize("key", cc.keys())
 def test_every_stage_matches_the_oracle(eng, oracle, key, gpu_filter):
     """One keep_debug run per case and filter placement: the first differing stage names the kernel.  (Of a pair with fewer than three
-    support points the handle keeps the descriptors and the raw lattice, no support list: its count is the status.)"""
+    support points the descriptors and the raw lattice are compared and the count, which is the status; the short list itself is
+    compared in test_lattice_filter_edges.py.)"""
     _, preset, over, L, R = cc.make(key)
     n, want = _oracle(oracle, key)
     e = eng.StereoEngine(L.shape[1], L.shape[0], cc.params(eng.SvParams, preset, over), keep_debug=True, gpu_filter=gpu_filter)
