@@ -904,6 +904,52 @@ void find_match(DenseCtx &c, int u, int v, float plane_a, float plane_b, float p
     c.D[d_addr] = min_d >= 0 ? (float)min_d : -1.0f;
 }
 
+/* elas.cpp:859-941: one triangle's corner sort, edge lines and two column loops; `pixel(u, v)` is called for every pixel the
+ * reference's loop visits, in its order.  sub: the half-resolution skips of :915-934. */
+template <class F>
+void scan_triangle(const int32_t *s, const int32_t *corners, int W, bool right_image, bool sub, F &&pixel) {
+    float tri_u[3], tri_v[3];
+    for (int k = 0; k < 3; k++) {
+        const int32_t *pt = s + 3 * corners[k];
+        tri_u[k] = right_image ? (float)(pt[0] - pt[2]) : (float)pt[0];
+        tri_v[k] = (float)pt[1];
+    }
+    for (int j = 0; j < 3; j++) /* :873-884 */
+        for (int k = 0; k < j; k++)
+            if (tri_u[k] > tri_u[j]) {
+                std::swap(tri_u[j], tri_u[k]);
+                std::swap(tri_v[j], tri_v[k]);
+            }
+    float A_u = tri_u[0], A_v = tri_v[0], B_u = tri_u[1], B_v = tri_v[1], C_u = tri_u[2], C_v = tri_v[2];
+    float AB_a = 0, AC_a = 0, BC_a = 0;
+    if ((int32_t)A_u != (int32_t)B_u)
+        AB_a = (A_v - B_v) / (A_u - B_u);
+    if ((int32_t)A_u != (int32_t)C_u)
+        AC_a = (A_v - C_v) / (A_u - C_u);
+    if ((int32_t)B_u != (int32_t)C_u)
+        BC_a = (B_v - C_v) / (B_u - C_u);
+    float AB_b = A_v - AB_a * A_u, AC_b = A_v - AC_a * A_u, BC_b = B_v - BC_a * B_u;
+
+    if ((int32_t)A_u != (int32_t)B_u)
+        for (int u = std::max((int32_t)A_u, 0); u < std::min((int32_t)B_u, W); u++) {
+            if (sub && u % 2 != 0) /* :915 */
+                continue;
+            int v_1 = f2u2i(AC_a * (float)u + AC_b), v_2 = f2u2i(AB_a * (float)u + AB_b);
+            for (int v = std::min(v_1, v_2); v < std::max(v_1, v_2); v++)
+                if (!sub || v % 2 == 0) /* :919 */
+                    pixel(u, v);
+        }
+    if ((int32_t)B_u != (int32_t)C_u)
+        for (int u = std::max((int32_t)B_u, 0); u < std::min((int32_t)C_u, W); u++) {
+            if (sub && u % 2 != 0) /* :930 */
+                continue;
+            int v_1 = f2u2i(AC_a * (float)u + AC_b), v_2 = f2u2i(BC_a * (float)u + BC_b);
+            for (int v = std::min(v_1, v_2); v < std::max(v_1, v_2); v++)
+                if (!sub || v % 2 == 0) /* :934 */
+                    pixel(u, v);
+        }
+}
+
 /* elas.cpp:804-944 (computeDisparity). */
 void dense(const elas_params &P, const int32_t *s, const int32_t *tri, const float *pl, int nt, const int32_t *grid_, const uint8_t *d1,
            const uint8_t *d2, int W, int H, bool right_image, float *D) {
@@ -927,48 +973,20 @@ void dense(const elas_params &P, const int32_t *s, const int32_t *tri, const flo
         } else {
             plane_a = t[3], plane_b = t[4], plane_c = t[5], plane_d = t[0];
         }
-        float tri_u[3], tri_v[3];
-        for (int k = 0; k < 3; k++) {
-            const int32_t *pt = s + 3 * tri[3 * i + k];
-            tri_u[k] = right_image ? (float)(pt[0] - pt[2]) : (float)pt[0];
-            tri_v[k] = (float)pt[1];
-        }
-        for (int j = 0; j < 3; j++) /* :873-884 */
-            for (int k = 0; k < j; k++)
-                if (tri_u[k] > tri_u[j]) {
-                    std::swap(tri_u[j], tri_u[k]);
-                    std::swap(tri_v[j], tri_v[k]);
-                }
-        float A_u = tri_u[0], A_v = tri_v[0], B_u = tri_u[1], B_v = tri_v[1], C_u = tri_u[2], C_v = tri_v[2];
-        float AB_a = 0, AC_a = 0, BC_a = 0;
-        if ((int32_t)A_u != (int32_t)B_u)
-            AB_a = (A_v - B_v) / (A_u - B_u);
-        if ((int32_t)A_u != (int32_t)C_u)
-            AC_a = (A_v - C_v) / (A_u - C_u);
-        if ((int32_t)B_u != (int32_t)C_u)
-            BC_a = (B_v - C_v) / (B_u - C_u);
-        float AB_b = A_v - AB_a * A_u, AC_b = A_v - AC_a * A_u, BC_b = B_v - BC_a * B_u;
         bool valid = fabs(plane_a) < 0.7 && fabs(plane_d) < 0.7; /* float |.| promoted to double against 0.7 (:910) */
-
-        if ((int32_t)A_u != (int32_t)B_u)
-            for (int u = std::max((int32_t)A_u, 0); u < std::min((int32_t)B_u, W); u++) {
-                if (sub && u % 2 != 0) /* :915 */
-                    continue;
-                int v_1 = f2u2i(AC_a * (float)u + AC_b), v_2 = f2u2i(AB_a * (float)u + AB_b);
-                for (int v = std::min(v_1, v_2); v < std::max(v_1, v_2); v++)
-                    if (!sub || v % 2 == 0) /* :919 */
-                        find_match(c, u, v, plane_a, plane_b, plane_c, valid);
-            }
-        if ((int32_t)B_u != (int32_t)C_u)
-            for (int u = std::max((int32_t)B_u, 0); u < std::min((int32_t)C_u, W); u++) {
-                if (sub && u % 2 != 0) /* :930 */
-                    continue;
-                int v_1 = f2u2i(AC_a * (float)u + AC_b), v_2 = f2u2i(BC_a * (float)u + BC_b);
-                for (int v = std::min(v_1, v_2); v < std::max(v_1, v_2); v++)
-                    if (!sub || v % 2 == 0) /* :934 */
-                        find_match(c, u, v, plane_a, plane_b, plane_c, valid);
-            }
+        scan_triangle(s, tri + 3 * i, W, right_image, sub, [&](int u, int v) { find_match(c, u, v, plane_a, plane_b, plane_c, valid); });
     }
+}
+
+/* The scan conversion alone: the index of the last triangle in list order whose loop of computeDisparity visits the pixel, -1
+ * where none does.  Full resolution whatever the subsampling; clipped to the image only (the u margin is find_match's). */
+void raster(const int32_t *s, const int32_t *tri, int nt, int W, int H, bool right_image, int32_t *tri_id) {
+    for (size_t i = 0; i < (size_t)W * H; i++) tri_id[i] = -1;
+    for (int i = 0; i < nt; i++)
+        scan_triangle(s, tri + 3 * i, W, right_image, false, [&](int u, int v) {
+            if (u >= 0 && u < W && v >= 0 && v < H)
+                tri_id[(size_t)v * W + u] = i;
+        });
 }
 
 /* ------------------------------------------------------------------------------------------------
@@ -1298,6 +1316,11 @@ int run(const elas_params &P, const uint8_t *I1, const uint8_t *I2, int W, int H
         put("grid1", g1.data(), g1.size());
         put("grid2", g2.data(), g2.size());
         put("grid_dims", gd, 3);
+        std::vector<int32_t> id((size_t)W * H);
+        raster(sp, tri1.data(), nt1, W, H, false, id.data());
+        put("tri_id1", id.data(), id.size());
+        raster(sp, tri2.data(), nt2, W, H, true, id.data());
+        put("tri_id2", id.data(), id.size());
     }
     dense(P, sp, tri1.data(), pl1.data(), nt1, g1.data(), desc1.data(), desc2.data(), W, H, false, D1);
     dense(P, sp, tri2.data(), pl2.data(), nt2, g2.data(), desc1.data(), desc2.data(), W, H, true, D2);
@@ -1408,6 +1431,10 @@ void orc_planes(const int32_t *support, const int32_t *tri, int nt, float *plane
 
 void orc_grid(const elas_params *p, const int32_t *support, int n, int W, int H, int right_image, int32_t *grid_out) {
     grid(*p, support, n, W, H, right_image != 0, grid_out);
+}
+
+void orc_raster(const int32_t *support, const int32_t *tri, int nt, int W, int H, int right_image, int32_t *tri_id) {
+    raster(support, tri, nt, W, H, right_image != 0, tri_id);
 }
 
 void orc_dense(const elas_params *p, const int32_t *support, const int32_t *tri, const float *planes_in, int nt, const int32_t *grid_in,

@@ -81,7 +81,7 @@ _STAGE_DTYPES = {
     "dcan_raw": np.int16, "dcan_dims": np.int32,
     "support": np.int32, "tri1": np.int32, "tri2": np.int32,
     "planes1": np.float32, "planes2": np.float32,
-    "grid1": np.int32, "grid2": np.int32, "grid_dims": np.int32,
+    "grid1": np.int32, "grid2": np.int32, "grid_dims": np.int32, "tri_id1": np.int32, "tri_id2": np.int32,
 }
 
 
@@ -195,6 +195,90 @@ class Oracle(_StageLib):
             f = getattr(self.lib, name)
             f.restype = None
             f.argtypes = args + [ctypes.c_int, ctypes.c_int]
+
+        ip, vp = ctypes.c_int, ctypes.c_void_p
+        for name, res, args in (("orc_descriptor", None, [vp, ip, ip, ip, vp]), ("orc_support_filter", ip, [pp, vp, ip, ip, vp, ip]),
+                                ("orc_planes", None, [vp, vp, ip, vp]), ("orc_grid", None, [pp, vp, ip, ip, ip, ip, vp]),
+                                ("orc_raster", None, [vp, vp, ip, ip, ip, ip, vp]), ("orc_dense", None, [pp, vp, vp, vp, ip, vp, vp, vp, ip, ip, ip, vp])):
+            f = getattr(self.lib, name)
+            f.restype, f.argtypes = res, args
+
+    # ---- the stages between the support lattice and the dense maps, on a support list of the caller's choice
+    @staticmethod
+    def grid_dims(params, W, H):
+        """(disp_max + 2, cells per row, cell rows): elas.cpp:88-90 (ceil of a float division)."""
+        f = np.float32
+        return params.disp_max + 2, int(np.ceil(f(W) / f(params.grid_size))), int(np.ceil(f(H) / f(params.grid_size)))
+
+    def descriptor(self, params, image):
+        """uint8 [H, W, 16]; at half resolution only the rows 4, 6, .. < H - 3 are filled (descriptor.cpp:48-93), as the pipeline does."""
+        img, _ = _u8(image)
+        H, W = img.shape
+        desc = np.zeros((H, W, 16), np.uint8)
+        self.lib.orc_descriptor(img.ctypes.data, W, H, W, desc.ctypes.data)
+        if params.subsampling:
+            desc[:4] = 0
+            desc[1::2] = 0
+        return desc
+
+    def support_filter(self, params, lattice, W, H):
+        """int16 [Hc, Wc] lattice (left unchanged) -> int32 [n, 3] support list (u, v, d)."""
+        lat = np.array(lattice, np.int16, order="C")
+        out = np.zeros((lat.size + 6, 3), np.int32)
+        n = self.lib.orc_support_filter(ctypes.byref(params), lat.ctypes.data, W, H, out.ctypes.data, out.shape[0])
+        assert 0 <= n <= out.shape[0]
+        return out[:n].copy()
+
+    def planes(self, support, tri):
+        """float32 [nt, 6]: t1a t1b t1c t2a t2b t2c per triangle."""
+        support, tri = np.ascontiguousarray(support, np.int32), np.ascontiguousarray(tri, np.int32)
+        out = np.zeros((len(tri), 6), np.float32)
+        self.lib.orc_planes(support.ctypes.data, tri.ctypes.data, len(tri), out.ctypes.data)
+        return out
+
+    def grid(self, params, support, W, H, right_image):
+        """int32 [cell rows, cells per row, disp_max + 2]: count, then the cell's candidate disparities in ascending order."""
+        support = np.ascontiguousarray(support, np.int32)
+        gd = self.grid_dims(params, W, H)
+        out = np.zeros((gd[2], gd[1], gd[0]), np.int32)
+        self.lib.orc_grid(ctypes.byref(params), support.ctypes.data, len(support), W, H, int(bool(right_image)), out.ctypes.data)
+        return out
+
+    def raster(self, support, tri, W, H, right_image):
+        """int32 [H, W]: the last triangle in list order whose scan conversion covers the pixel, -1 for none (full resolution)."""
+        support, tri = np.ascontiguousarray(support, np.int32), np.ascontiguousarray(tri, np.int32)
+        out = np.zeros((H, W), np.int32)
+        self.lib.orc_raster(support.ctypes.data, tri.ctypes.data, len(tri), W, H, int(bool(right_image)), out.ctypes.data)
+        return out
+
+    def dense(self, params, support, tri, planes, grid, desc1, desc2, right_image):
+        """float32 winner-takes-all map, [H, W] or [H // 2, W // 2] at half resolution."""
+        support, tri = np.ascontiguousarray(support, np.int32), np.ascontiguousarray(tri, np.int32)
+        planes, grid = np.ascontiguousarray(planes, np.float32), np.ascontiguousarray(grid, np.int32)
+        desc1, desc2 = np.ascontiguousarray(desc1, np.uint8), np.ascontiguousarray(desc2, np.uint8)
+        H, W = desc1.shape[:2]
+        out = np.zeros((H // 2, W // 2) if params.subsampling else (H, W), np.float32)
+        self.lib.orc_dense(ctypes.byref(params), support.ctypes.data, tri.ctypes.data, planes.ctypes.data, len(tri), grid.ctypes.data, desc1.ctypes.data,
+                           desc2.ctypes.data, W, H, int(bool(right_image)), out.ctypes.data)
+        return out
+
+    def chain_from_lattice(self, params, lattice, left, right):
+        """Everything between a support lattice and the dense maps of an image pair, stage by stage: support, tri1/2, planes1/2, grid1/2,
+        tri_id1/2, wta1/2 (the pipeline's names).  With fewer than three support points only the list."""
+        H, W = left.shape
+        sup = self.support_filter(params, lattice, W, H)
+        out = {"support": sup}
+        if len(sup) < 3:
+            return out
+        d1, d2 = self.descriptor(params, left), self.descriptor(params, right)
+        for side, key in ((0, "1"), (1, "2")):
+            xy = np.stack([sup[:, 0] - side * sup[:, 2], sup[:, 1]], 1)
+            tri = self.delaunay(xy)
+            pl = self.planes(sup, tri)
+            g = self.grid(params, sup, W, H, side)
+            out.update({"tri" + key: tri, "planes" + key: pl, "grid" + key: g, "tri_id" + key: self.raster(sup, tri, W, H, side),
+                        "wta" + key: self.dense(params, sup, tri, pl, g, d1, d2, side)})
+        return out
 
     # ---- the post-processing stages on maps of the caller's choice; each returns new float32 [H, W] maps, the arguments stay as they are
     @staticmethod
