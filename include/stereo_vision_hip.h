@@ -95,6 +95,12 @@
  *      that a row may slide along the ground or a wall it lies on and the loop converges in a few rounds where (X)'s creeps.
  *      stereo_vision.sv.voxel_map_normals and voxel_map_align_plane_sums state the definitions in numpy; voxel_align_solve_plane is the fit.
  *
+ *  (Z) Behind the engine, in front of every stage that takes a pose: stereo visual odometry (sv_flow_*) - the lattice points of frame k - 1
+ *      that carry a disparity found again in frame k by a sum of absolute differences over a window around where a guessed motion puts
+ *      them (sv_flow_match_device), and the matches reduced, under a pose, to the 32 integers of one gated Gauss-Newton round of the
+ *      camera's motion between the two frames (sv_flow_pose_sums_device).  stereo_vision.sv.flow_match and flow_pose_sums state the
+ *      definitions in numpy; flow_solve, flow_egomotion and flow_chain are the fit, the loop and the chain of poses on the host.
+ *
  * All sv_* functions return SV_OK (0) or a negative sv_status; sv_last_error() gives the text.
  * Nothing in this library calls exit().
  */
@@ -1764,6 +1770,75 @@ int sv_voxel_plane_align_device(const void *map, size_t map_bytes, const sv_voxe
  * default a member with N < min_nb, which gets no normal whatever the table says, is not searched where no fit is asked for.  The results
  * do not depend on any of them.  Returns SV_OK, or SV_ERR_ARG for other values. */
 int sv_debug_voxel_normals(int max_chunks, int flags);
+
+/* ---- (Z) stereo visual odometry: two left images + the disparity of the first -> temporal matches; matches + a pose -> the sums of one round ---- */
+
+/* The camera and the words of the two calls below.  f, cx, cy in pixels; b16 = 16 b, fb = f b and fb16 = f b16 with b the baseline in
+ * metres (1 / Q[3][2]) - the products are made once, by the caller, in double, so that host and device hold the same bits; all finite, f,
+ * b16, fb and fb16 > 0.  The match call reads step >= 1, r in 1 .. 7 (the patch is (2 r + 1)^2), wx, wy >= 0 with (2 wx + 1) (2 wy + 1) <=
+ * 16384, ratio in 0 .. 256, max_cost >= 0 and capacity in 0 .. 65536; the sums call reads the camera only.  reserved: 0.
+ * LDS limit: a wavefront holds its point's window of cur in LDS, 2 wy + 2 r + 1 rows of ((2 wx + 2 r + 1 + 3) / 4 + 1) | 1 dwords, and a
+ * workgroup of four has 64 KB: a window of more than 16384 bytes is refused (at r = 4 the cold-start window wx = 64, wy = 24 takes 8436). */
+typedef struct {
+    double f, cx, cy, b16, fb, fb16;
+    int32_t step, r, wx, wy, ratio, max_cost, capacity;
+    int32_t reserved[9];
+} sv_flow_spec;
+
+/* (Z1) temporal matches.  prev, cur: uint8 [batch][height][width], the rectified left gray images of frames k - 1 and k; d_prev float
+ * [batch][height][width]: the disparity of frame k - 1; d_cur the same of frame k, or NULL; guess double [batch][12] or NULL: the expected
+ * motion, previous camera to current camera, Xc = R X0 + t, R row-major, then t - NULL is the identity and skips the projection.
+ *   points      the pixels (u0, v0) with u0 % step == 0 and v0 % step == 0, in ascending v0 width + u0, with r <= u0 < width - r, r <= v0 <
+ *               height - r and d0q = floor(16 d + 0.5) (in double) in 1 .. 2^20 for a positive, finite d = d_prev[v0][u0].
+ *   centre      X0 = (((u0 - cx) b16) / d0q, ((v0 - cy) b16) / d0q, fb16 / d0q); Xc_k = ((R_k0 x + R_k1 y) + R_k2 z) + t_k; a point with Xc.z <=
+ *               0.1 (or NaN) is dropped; c = (floor(((f Xc.x) / Xc.z + cx) + 0.5), floor(((f Xc.y) / Xc.z + cy) + 0.5)), a point whose c is
+ *               not within +-2^20 is dropped.  Doubles, one operation at a time, nothing contracted.  Without a guess c = (u0, v0).
+ *   candidates  (dx, dy) in [-wx, wx] x [-wy, wy] with r <= c.x + dx < width - r and r <= c.y + dy < height - r; cost = the sum of absolute
+ *               differences of the patch of prev around (u0, v0) and that of cur around c + (dx, dy): at most 225 * 255.
+ *   best        the least cost, among equals the least (dy + wy) (2 wx + 1) + (dx + wx); second: the least cost among the candidates
+ *               with max(|dx - bdx|, |dy - bdy|) > 1.
+ *   match       a second exists, 256 best < ratio second, best <= max_cost, and not (wx > 0 and |bdx| == wx), not (wy > 0 and |bdy| == wy).
+ *   outputs     matches int32 [batch][capacity][6] = (u0, v0, d0q, u1, v1, d1q) in point order, (u1, v1) = c + best, d1q = floor(16
+ *               d_cur[v1][u1] + 0.5) where that is in 1 .. 2^20 for a positive finite d_cur, else -1; cost int32 [batch][capacity][2] =
+ *               (best, second); counts int32 [batch]: the matches, or -1 for a frame with more than capacity, whose rows are the first
+ *               `capacity` of them.  Rows at and behind a frame's count hold -1: every output is written in full. */
+
+/* Host only: the bytes of the workspace sv_flow_match_device needs: 32 per lattice point.  SV_ERR_ARG (bytes untouched) for a NULL
+ * bytes, batch outside 0..65535, width or height outside 1..8192, a bad word of the spec, or a window beyond the LDS limit above. */
+int sv_flow_match_workspace(int width, int height, int batch, const sv_flow_spec *spec, size_t *bytes);
+/* Enqueued on `stream` (a hipStream_t, NULL = the default stream) as two kernels - a wavefront per lattice point, a workgroup per frame
+ * that packs the matches in order - and not waited for: nothing is allocated, no host synchronisation is made, no atomic is issued, and
+ * nothing is assumed of what the outputs or the workspace held before.  All pointers device; d_prev, d_cur, matches, cost, counts and the
+ * workspace 4-byte, guess 8-byte aligned.  Returns SV_OK (nothing enqueued for batch == 0), SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued,
+ * the outputs untouched, the text in sv_last_error(NULL) - for what the workspace call refuses; with batch > 0 a NULL prev, cur, d_prev,
+ * counts or workspace, and with capacity > 0 as well a NULL matches or cost; a misaligned pointer; too small a workspace. */
+int sv_flow_match_device(const void *prev, const void *cur, const float *d_prev, const float *d_cur, const double *guess, int batch, int width, int height,
+                         const sv_flow_spec *spec, int32_t *matches, int32_t *cost, int32_t *counts, void *workspace, size_t workspace_bytes, void *stream);
+
+/* (Z2) the sums of one round.  matches, counts: (Z1)'s, capacity <= 65536 (a count of -1 or 0 gives sums of 0, a count above the capacity
+ * counts as the capacity); poses double [batch][12]: previous camera to current camera; gate_q and dgate_q in 1/16 px, 0 .. 2^20.
+ *   per match   d0q in 1 .. 2^20, else it is skipped.  X0 and Xc = (x, y, z) as in (Z1).  fz = f / z, xz = x / z, yz = y / z, bz = fb / z; pu =
+ *               floor(16 (f xz + cx) + 0.5), pv = floor(16 (f yz + cy) + 0.5), pd = floor(16 bz + 0.5).  inside: z > 0.1 and |pu|, |pv|, |pd| <=
+ *               2^30 (false for NaN).
+ *   residuals   ru = 16 u1 - pu, rv = 16 v1 - pv, rd = d1q - pd.  inlier: inside and ru^2 + rv^2 <= gate_q^2; d-inlier: an inlier with d1q > 0
+ *               and |rd| <= dgate_q.
+ *   Jacobian    with respect to (t, omega) of Xc' = exp(omega) Xc + t: a = fz xz, Ju = (fz, 0, -a, -(a y), f (1 + xz xz), -(f yz)); c = fz yz,
+ *               Jv = (0, fz, -c, -(f (1 + yz yz)), a y, f xz); e = bz / z, Jd = (0, 0, -e, -(e y), e x, 0); each entry clamp(floor(16 J +
+ *               0.5), +-2^20).
+ *   sums        int64 [batch][32]: inside, inliers, dinliers, E = sum ru^2 + rv^2, Ed = sum rd^2, g[6] = sum Jq r, A[21] = sum Jq_i Jq_j (upper
+ *               triangle, row-major) over the u and v rows of the inliers and the d rows of the d-inliers.  Contract: capacity <= 65536
+ *               and the gates <= 2^20, so a match adds less than 2^43 to a word and every sum stays below 2^59. */
+
+/* Host only: the bytes of the workspace sv_flow_pose_sums_device needs: 32 words per chunk of 256 matches.  SV_ERR_ARG (bytes untouched)
+ * for a NULL bytes, capacity outside 0..65536 or batch outside 0..65535. */
+int sv_flow_pose_sums_workspace(int capacity, int batch, size_t *bytes);
+/* Enqueued on `stream` as two kernels - a lane per match and a partial per chunk, the partials per frame - and not waited for: nothing
+ * is allocated, no atomic is issued, batch x 32 words to read back.  matches and counts 4-byte, poses, sums and the workspace 8-byte
+ * aligned.  Returns SV_OK (nothing enqueued for batch == 0), SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued, sums untouched - for a bad
+ * camera in the spec, capacity, batch or a gate outside its range, with batch > 0 a NULL counts, poses or sums, with capacity > 0 as well
+ * a NULL matches or workspace, a misaligned pointer, too small a workspace. */
+int sv_flow_pose_sums_device(const int32_t *matches, const int32_t *counts, const double *poses, int batch, int capacity, const sv_flow_spec *spec, int gate_q,
+                             int dgate_q, int64_t *sums, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- (A)the reference's exported symbols ------------------------------------------------------------- */
 

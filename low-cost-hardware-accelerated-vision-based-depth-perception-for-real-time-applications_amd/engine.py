@@ -560,6 +560,13 @@ class SvVoxelClusterSpec(ctypes.Structure):
                 ("min_voxels", ctypes.c_int32), ("capacity", ctypes.c_int32), ("drop", ctypes.c_int32), ("reserved", ctypes.c_int32 * 8)]
 
 
+class SvFlowSpec(ctypes.Structure):
+    """sv_flow_spec of include/stereo_vision_hip.h."""
+    _fields_ = [("f", ctypes.c_double), ("cx", ctypes.c_double), ("cy", ctypes.c_double), ("b16", ctypes.c_double), ("fb", ctypes.c_double), ("fb16", ctypes.c_double),
+                ("step", ctypes.c_int32), ("r", ctypes.c_int32), ("wx", ctypes.c_int32), ("wy", ctypes.c_int32), ("ratio", ctypes.c_int32), ("max_cost", ctypes.c_int32),
+                ("capacity", ctypes.c_int32), ("reserved", ctypes.c_int32 * 9)]
+
+
 def _signatures():
     """The table below: per stage group of the C API, (D) to (S), its functions and per function (restype, argtypes), parameter by
     parameter as include/stereo_vision_hip.h declares them - tests/test_stage_signatures.py holds the two against each other."""
@@ -679,6 +686,12 @@ def _signatures():
             "sv_voxel_plane_align_workspace": (ci, [ci, ci, P(sz)]),
             "sv_voxel_plane_align_device": (ci, [vp, sz, vm, vp, ci, vp, vp, vp, vp, ci, ci, ci, i64, i64, ci, vp, i64, vp, ci, vp, vp, vp, vp, vp, sz, vp]),
             "sv_debug_voxel_normals": (ci, [ci, ci]),
+        },
+        "flow": {  # (Z)
+            "sv_flow_match_workspace": (ci, [ci, ci, ci, P(SvFlowSpec), P(sz)]),
+            "sv_flow_match_device": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, P(SvFlowSpec), vp, vp, vp, vp, sz, vp]),
+            "sv_flow_pose_sums_workspace": (ci, [ci, ci, P(sz)]),
+            "sv_flow_pose_sums_device": (ci, [vp, vp, vp, ci, ci, P(SvFlowSpec), ci, ci, vp, vp, sz, vp]),
         },
     }
 
@@ -2836,6 +2849,140 @@ def debug_voxel_normals(max_chunks=0, skip=True, prune=True):
     the cells that cannot hold the nearest voxel, and whether the normals kernel leaves out the search of a member with N < min_nb where
     no fit is asked for.  The results depend on none of them.  Process-wide; a test and measurement hook."""
     return int(voxel_normals_lib().sv_debug_voxel_normals(int(max_chunks), (0 if skip else 1) | (0 if prune else 2)))
+
+
+def flow_lib():
+    """The library with the signatures of group (Z) declared."""
+    return _bind("flow")
+
+
+class FlowResult(_Result):
+    """What flow_match returns, tensors on the images' device: matches int32 [B,capacity,6] = (u0, v0, d0q, u1, v1, d1q), cost int32
+    [B,capacity,2] = (best, second), counts int32 [B] (-1: more matches than capacity).  flow_egomotion's result has sums int64 [B,32] on
+    the device and, host numpy, poses float64 [B,12], ok bool [B], rounds, inliers int64 [rounds,B], rms_px float64 [rounds,B]."""
+    __slots__ = ("matches", "cost", "counts", "sums", "poses", "ok", "rounds", "inliers", "rms_px")
+
+
+def flow_spec(camera, **words):
+    """-> SvFlowSpec from a camera dict (stereo_vision.sv.voxel_render_camera's) and flow_match's words (stereo_vision.sv.flow_words checks
+    them: ValueError)."""
+    from .stereo_vision.sv import flow_camera, flow_words
+    cam, w = flow_camera(camera), flow_words(**words)
+    return SvFlowSpec(cam["f"], cam["cx"], cam["cy"], cam["b16"], cam["fb"], cam["fb16"], w["step"], w["r"], w["wx"], w["wy"], w["ratio"], w["max_cost"], w["capacity"])
+
+
+def flow_match(prev, cur, d_prev, d_cur, camera, guess=None, step=8, r=4, wx=8, wy=8, ratio=230, max_cost=225 * 255, capacity=4096, out=None, workspace=None):
+    """Temporal matches of B frame pairs - the definition of stereo_vision.sv.flow_match on the GPU, bit for bit (sv_flow_match_device: a
+    wavefront per lattice point with its window of cur in LDS, four bytes per v_sad_u8; then the matches packed in point order; no
+    atomics).  prev, cur CUDA uint8 [B,H,W]: the rectified left gray images of frames k - 1 and k (StereoRig.frontend's); d_prev CUDA
+    float32 [B,H,W]: the disparity of frame k - 1; d_cur the same of frame k, or None; camera: voxel_render_camera's dict; guess float64
+    [B,12] (numpy, or a tensor on the device) or None: the expected motion, previous camera to current camera.  out: a FlowResult of an
+    earlier call of the same shape to write into; workspace: an int32 tensor to use (None: torch's allocator).  -> FlowResult(matches,
+    cost, counts); enqueued on torch's current stream, nothing is read back."""
+    import torch
+    spec = flow_spec(camera, step=step, r=r, wx=wx, wy=wy, ratio=ratio, max_cost=max_cost, capacity=capacity)
+    if not (isinstance(prev, torch.Tensor) and prev.is_cuda and prev.dtype == torch.uint8 and prev.dim() == 3):
+        raise ValueError("prev must be a CUDA uint8 tensor [B,H,W]")
+    dev, shape = prev.device, tuple(prev.shape)
+    B, H, W = shape
+    if B > 65535 or not (1 <= H <= 8192 and 1 <= W <= 8192):
+        raise ValueError("at most 65535 frames of at most 8192 x 8192, got %s" % (shape,))
+    for t, name, dtype in ((cur, "cur", torch.uint8), (d_prev, "d_prev", torch.float32), (d_cur, "d_cur", torch.float32)):
+        if t is None and name == "d_cur":
+            continue
+        if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dtype and tuple(t.shape) == shape):
+            raise ValueError("%s must be a %s tensor %s on %s" % (name, str(dtype).replace("torch.", ""), list(shape), dev))
+    prev, cur, d_prev = prev.contiguous(), cur.contiguous(), d_prev.contiguous()
+    d_cur = None if d_cur is None else d_cur.contiguous()
+    g = None
+    if guess is not None:
+        g = guess if isinstance(guess, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(guess, np.float64)).to(dev)
+        if g.device != dev or g.dtype != torch.float64 or tuple(g.shape) != (B, 12):
+            raise ValueError("guess must be float64 [%d,12]" % B)
+        g = g.contiguous()
+    cap = int(capacity)
+    res = out if out is not None else FlowResult(matches=torch.empty((B, cap, 6), dtype=torch.int32, device=dev), cost=torch.empty((B, cap, 2), dtype=torch.int32, device=dev),
+                                                 counts=torch.empty((B,), dtype=torch.int32, device=dev))
+    if tuple(res.matches.shape) != (B, cap, 6) or tuple(res.cost.shape) != (B, cap, 2) or tuple(res.counts.shape) != (B,):
+        raise ValueError("out is of another shape")
+    L = flow_lib()
+    need = ctypes.c_size_t()
+    _check(L.sv_flow_match_workspace(W, H, B, ctypes.byref(spec), ctypes.byref(need)), "sv_flow_match_workspace")
+    if B == 0:  # nothing to enqueue
+        return res
+    ws = workspace if workspace is not None else torch.empty((max(need.value // 4, 1),), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.sv_flow_match_device(prev.data_ptr(), cur.data_ptr(), d_prev.data_ptr(), None if d_cur is None else d_cur.data_ptr(), None if g is None else g.data_ptr(),
+                                    B, W, H, ctypes.byref(spec), _ptr(res.matches), _ptr(res.cost), res.counts.data_ptr(), ws.data_ptr(), ws.numel() * 4,
+                                    torch.cuda.current_stream(dev).cuda_stream)
+    _check(rc, "sv_flow_match_device")
+    return res  # ws goes back to torch's allocator, which hands it out again on this stream only: behind the kernels
+
+
+def _flow_matches(matches, counts):
+    import torch
+    if not (isinstance(matches, torch.Tensor) and matches.is_cuda and matches.dtype == torch.int32 and matches.dim() == 3 and matches.shape[2] == 6):
+        raise ValueError("matches must be a CUDA int32 tensor [B,capacity,6]")
+    B, cap = int(matches.shape[0]), int(matches.shape[1])
+    if B > 65535 or cap > 65536:
+        raise ValueError("at most 65535 frames of at most 65536 matches, got %s" % (tuple(matches.shape),))
+    if not (isinstance(counts, torch.Tensor) and counts.device == matches.device and counts.dtype == torch.int32 and tuple(counts.shape) == (B,)):
+        raise ValueError("counts must be an int32 tensor [%d] on the device of matches" % B)
+    return matches.contiguous(), counts.contiguous(), B, cap
+
+
+def flow_pose_sums(matches, counts, camera, poses, gate_q=None, dgate_q=None, out=None, workspace=None):
+    """The sums of one round of the egomotion fit - the definition of stereo_vision.sv.flow_pose_sums on the GPU, bit for bit
+    (sv_flow_pose_sums_device: a lane per match, two kernels, no atomics).  matches CUDA int32 [B,capacity,6] and counts int32 [B] as
+    flow_match returns them, poses float64 [B,12] (numpy, or a tensor on the device), gate_q and dgate_q in 1/16 px (None: 2^20, no
+    gate).  out: an int64 [B,32] tensor to write into.  -> int64 [B,32] on the device; enqueued on torch's current stream, nothing is
+    read back."""
+    import torch
+    from .stereo_vision.sv import _flow_gates
+    gate_q, dgate_q = _flow_gates(gate_q, dgate_q)
+    spec = flow_spec(camera)
+    matches, counts, B, cap = _flow_matches(matches, counts)
+    dev = matches.device
+    p = poses if isinstance(poses, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(poses, np.float64)).to(dev)
+    if p.device != dev or p.dtype != torch.float64 or tuple(p.shape) != (B, 12):
+        raise ValueError("poses must be float64 [%d,12]" % B)
+    p = p.contiguous()
+    sums = out if out is not None else torch.empty((B, 32), dtype=torch.int64, device=dev)
+    if tuple(sums.shape) != (B, 32) or sums.dtype != torch.int64 or sums.device != dev or not sums.is_contiguous():
+        raise ValueError("out must be a contiguous int64 tensor [%d,32] on the device of matches" % B)
+    if B == 0:
+        return sums
+    L = flow_lib()
+    need = ctypes.c_size_t()
+    _check(L.sv_flow_pose_sums_workspace(cap, B, ctypes.byref(need)), "sv_flow_pose_sums_workspace")
+    ws = workspace if workspace is not None else torch.empty((max(need.value // 8, 1),), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.sv_flow_pose_sums_device(_ptr(matches), counts.data_ptr(), p.data_ptr(), B, cap, ctypes.byref(spec), gate_q, dgate_q, sums.data_ptr(), ws.data_ptr(),
+                                        ws.numel() * 8, torch.cuda.current_stream(dev).cuda_stream)
+    _check(rc, "sv_flow_pose_sums_device")
+    return sums
+
+
+def flow_egomotion(matches, counts, camera, start=None, gates=None, dgate=2.0, iterations=10, eps=None, min_inliers=12):
+    """The camera's motion between two frames from their matches - stereo_vision.sv.flow_egomotion with the sums from the device: per
+    round flow_pose_sums and the B x 32 words read back - the stage's one wait, once per round -, then stereo_vision.sv.flow_solve on
+    them.  The fit and the loop are the numpy definition's own functions on equal sums, so the result equals the CPU path's bit for bit.
+    -> FlowResult with sums (the last round's, on the device), poses float64 numpy [B,12], ok, rounds, inliers and rms_px."""
+    import torch
+    from .stereo_vision.sv import FLOW_GATES, flow_identity, flow_loop
+    matches, counts, B, _ = _flow_matches(matches, counts)
+    start = flow_identity(B) if start is None else np.asarray(start.cpu().numpy() if isinstance(start, torch.Tensor) else start, np.float64)
+    if start.shape != (B, 12):
+        raise ValueError("start must be float64 [%d,12], got %s" % (B, start.shape))
+    res = FlowResult(matches=matches, counts=counts, sums=torch.zeros((B, 32), dtype=torch.int64, device=matches.device))
+
+    def sums_of(cur, gate_q, dgate_q):
+        flow_pose_sums(matches, counts, camera, cur, gate_q, dgate_q, out=res.sums)
+        return res.sums.cpu().numpy()  # the wait of the round
+
+    got = flow_loop(sums_of, start, FLOW_GATES if gates is None else gates, dgate, iterations, eps, min_inliers)
+    res.poses, res.ok, res.rounds, res.inliers, res.rms_px = got["poses"], got["ok"], got["rounds"], got["inliers"], got["rms_px"]
+    return res
 
 
 def host_support_filter(params, dcan, width, height, threads=0, lattice=False):

@@ -40,6 +40,7 @@ import ctypes
 
 import numpy as np
 
+from .engine import flow_egomotion, flow_match
 from .engine import (SvParams, StereoEngine, StereoError, box_positions_from_disparity, box_spec, cloud_spec, compact_cloud_from_disparity,
                      ground_from_disparity, ground_spec, lib, occupancy_from_disparity, occupancy_fuse, occupancy_match, occupancy_clearance, clearance_paths, cost_cells, cost_routes, frontier_cells, frontier_clusters, occupancy_cost_to_goal, occupancy_view, occupancy_spec, pinned_array, reproject, split_clouds, stixel_spec, stixels_from_disparity,
                      top_view_from_disparity, top_view_spec, split_voxel_clouds, voxel_cloud_from_disparity, voxel_map_align, voxel_map_carry, voxel_map_clear, voxel_map_insert, voxel_map_match, voxel_map_new,
@@ -318,6 +319,63 @@ class StereoRig:
         if not from_numpy:
             return xyz, color, n, counts
         return [(p.cpu().numpy(), None if c is None else c.cpu().numpy(), k.cpu().numpy()) for p, c, k in split_voxel_clouds(xyz, counts, color, n)]
+
+    def _flow_inputs(self, left, right, pixel_format):
+        """Front end and engine once for a batch of consecutive pairs -> (gray left [B,H,W], d1 [B,H,W], the camera, came_from_numpy)."""
+        if self.params.subsampling:
+            raise ValueError("flow and odometry do not support half-resolution maps (params.subsampling)")
+        gl, gr, _, from_numpy = self._run_frontend(left, right, pixel_format, False)
+        d1, _ = self.engine.process_device(gl, gr, want_d2=False)
+        return gl, d1, self.render_camera(1.0), from_numpy
+
+    def flow(self, left, right, pixel_format="bgr", guess=None, step=8, r=4, wx=8, wy=8, ratio=230, max_cost=225 * 255, capacity=8192):
+        """The temporal matches of a batch of B consecutive pairs (include/stereo_vision_hip.h (Z1), stereo_vision.sv.flow_match): front
+        end and engine once for the batch, then the lattice points of frame k - 1 that carry a disparity looked for in frame k, for k = 1
+        .. B - 1, in one call.  guess: float64 [B-1,12], the expected motions, previous camera to current camera, or None - the identity.
+        CUDA input: engine.FlowResult with matches int32 [B-1,capacity,6] = (u0, v0, d0q, u1, v1, d1q), cost int32 [B-1,capacity,2] and
+        counts int32 [B-1] (-1: more matches than capacity); nothing is waited for.  numpy input: a dict of these as numpy arrays."""
+        gl, d1, camera, from_numpy = self._flow_inputs(left, right, pixel_format)
+        if gl.shape[0] < 2:
+            raise ValueError("flow needs at least two consecutive pairs, got %d" % gl.shape[0])
+        res = flow_match(gl[:-1], gl[1:], d1[:-1], d1[1:], camera, guess, step, r, wx, wy, ratio, max_cost, capacity)
+        return {k: getattr(res, k).cpu().numpy() for k in ("matches", "cost", "counts")} if from_numpy else res
+
+    def odometry(self, left, right, pixel_format="bgr", start=None, transform=None, guess="velocity", **spec):
+        """Stereo visual odometry of a batch of B consecutive pairs (include/stereo_vision_hip.h (Z), stereo_vision.sv.flow_odometry): front
+        end and engine once for the batch; frame k matched against frame k - 1 and the camera's motion between them fitted by a gated
+        Gauss-Newton loop whose sums come from the device (B x 32 words read back per round); the motions chained into poses.
+        guess "velocity": the frames one after the other, each under the motion before it, the first over the cold-start window
+        spec["cold"] (or under spec["first"], a motion [12]); "identity"; or the caller's motions [B-1,12].  start: the pose of frame 0
+        ([12]; None: the identity); transform as in top_view - None, "rig" or (XR, XT), camera to frame: with (CAMERA_TO_VEHICLE, None) the
+        poses are what VoxelMap.update, .align and --poses take.  spec: the words of stereo_vision.sv.FLOW_ODOMETRY.
+        -> {"poses": float64 [B,12], frame to world; "rel": float64 [B-1,12], previous camera to current camera; "ok": bool [B-1];
+        "inliers": int64 [B-1]; "matches": the matches of the B - 1 pairs - matches, cost and counts as flow() returns them, tensors for
+        CUDA input and numpy arrays for numpy input}.  A pair whose fit was not ok repeats the motion before it in the chain."""
+        import torch
+        s = _sv.flow_odometry_spec(**spec)
+        XR, XT = self._transform(transform)
+        gl, d1, camera, from_numpy = self._flow_inputs(left, right, pixel_format)
+        B = int(gl.shape[0])
+        words = {k: s[k] for k in ("step", "r", "ratio", "max_cost", "capacity")}
+
+        def match_of(lo, hi, g, wx, wy):
+            return flow_match(gl[lo:hi], gl[lo + 1:hi + 1], d1[lo:hi], d1[lo + 1:hi + 1], camera, g, wx=wx, wy=wy, **words)
+
+        def ego_of(got, at):
+            e = flow_egomotion(got.matches, got.counts, camera, at, s["gates"], s["dgate"], s["iterations"], s["eps"], s["min_inliers"])
+            return {k: getattr(e, k) for k in ("poses", "ok", "rounds", "inliers")}
+
+        got = _sv.flow_odometry(match_of, ego_of, B - 1, guess, **spec)
+        calls = got["calls"]
+        if calls:
+            m = {k: torch.cat([getattr(c, k) for c in calls]) for k in ("matches", "cost", "counts")}
+        else:
+            dev = gl.device
+            m = {"matches": torch.empty((0, s["capacity"], 6), dtype=torch.int32, device=dev), "cost": torch.empty((0, s["capacity"], 2), dtype=torch.int32, device=dev),
+                 "counts": torch.empty((0,), dtype=torch.int32, device=dev)}
+        if from_numpy:
+            m = {k: v.cpu().numpy() for k, v in m.items()}
+        return {"poses": _sv.flow_chain(got["rel"], start, XR, XT, got["ok"]), "rel": got["rel"], "ok": got["ok"], "inliers": got["inliers"], "matches": m}
 
     def ground(self, left, right, pixel_format="bgr", transform=None, **spec):
         """Where the ground is, what stands on it and how far one can go in each image column, for B pairs: front end, engine, then

@@ -146,6 +146,16 @@ engine.voxel_map_align_plane_sums): voxel_map_align_sums' pairs, reduced to the 
 voxel_align_solve_plane is the host's fit, and voxel_map_align(method="plane") the loop around both - a row may slide along the plane it
 lies on, so the loop needs a few rounds on a street where the point-to-point loop creeps.  The reference has no counterpart (DESIGN.md
 §8).
+
+flow_match and flow_pose_sums (with flow_pose_sums_brute, the plain loop per match in Python integers) are the definition of the stereo
+visual odometry (sv_flow_* of include/stereo_vision_hip.h (Z); engine.flow_match / flow_pose_sums / flow_egomotion and
+rig.StereoRig.flow / .odometry on the GPU): the lattice points of frame k - 1 that carry a disparity, found again in frame k by a sum of
+absolute differences over a window around where a guessed motion puts them, and the matches reduced under a pose to the 32 integers of a
+gated Gauss-Newton round.  flow_solve, flow_egomotion, flow_chain and flow_odometry are the fit, the loop, the chain of poses and the
+drive, shared by the CPU and the GPU path, so that both give the same poses bit for bit.  Header comment of the details the issue left
+open: FLOW_Z_MIN = 0.1 m; b = 1 / q32 with q33 taken as 0; a disparity makes a point where floor(16 d + 0.5) is in 1 .. 2^20; a window
+centre beyond +-2^20 drops the point; rows behind a frame's count hold -1; a match is inside where z > z_min and its predicted words stay
+within +-2^30; no gate is 2^20 sixteenths of a pixel; FLOW_EPS = (2e-5 rad, 2e-4 m).  The reference has no counterpart.
 """
 import argparse
 import ctypes
@@ -2400,6 +2410,509 @@ def voxel_align_plane_solver(dirs):
     return dict(words=32, solve=voxel_align_solve_plane, pairs=2, W=3, D=4, unit=1.0 / mean)
 
 
+FLOW_Z_MIN = 0.1              # metres: a point at or nearer than this in the current camera is dropped
+FLOW_R_MAX = 7                # the patch is (2 r + 1)^2, at most 15 x 15
+FLOW_CANDIDATES_MAX = 16384   # (2 wx + 1) (2 wy + 1) at most: a candidate's index fits 14 bits beside its 16-bit cost
+FLOW_WINDOW_BYTES = 16384     # a point's window of cur, rows padded as flow_window_bytes says, at most: what a wavefront holds in LDS
+FLOW_DQ_MAX = 2 ** 20         # a disparity in 1/16 px that makes a point: 1 .. 2^20
+FLOW_CENTRE_MAX = 2.0 ** 20   # |c| of a window centre that is kept
+FLOW_COST_MAX = 225 * 255     # the largest sum of absolute differences
+FLOW_CAPACITY_MAX = 65536     # matches per frame at most: with it every one of flow_pose_sums' words stays below 2^59
+FLOW_BATCH_MAX = 65535
+FLOW_GATE_MAX = 2 ** 20       # gate_q and dgate_q at most, and what "no gate" stands for: 65536 px
+FLOW_PIXEL_MAX = 2.0 ** 30    # |pu|, |pv|, pd of a match that is inside, in 1/16 px
+FLOW_J_MAX = 2 ** 20          # a quantised Jacobian entry is clamped to +-this
+FLOW_SUMS = ("inside", "inliers", "dinliers", "E", "Ed") + tuple("g%d" % i for i in range(6)) + tuple("A%d%d" % (i, j) for i in range(6) for j in range(i, 6))  # the 32 words
+FLOW_GATES = (None, 20, 8, 4, 3)  # px: flow_egomotion's schedule
+FLOW_EPS = (2e-5, 2e-4)       # radians and metres: flow_egomotion's default eps.  A round moves a residual by 1/16 px at the least - over
+                              # some thousand matches the fit's floor is a few 1e-6 rad and 1e-5 m -, and an inlier set that flickers at the
+                              # gate moves the pose by up to 1e-5 rad and 1e-4 m (the synthetic cases of tests/flow_cases.py).
+
+
+def flow_camera(camera):
+    """The words of the temporal matcher from a camera dict (voxel_render_camera's, made from the rig's Q): f, cx, cy as they are, the
+    baseline b = 1 / q32 in metres - q32 > 0, and q33, a principal point that differs between the two cameras, is taken as 0 -, and the
+    products made once on the host in double: b16 = 16 b, fb = f b, fb16 = f b16.  ValueError for words that are not finite, f <= 0 or
+    q32 <= 0."""
+    try:
+        f, cx, cy, q32 = (float(camera[k]) for k in ("f", "cx", "cy", "q32"))
+    except (KeyError, TypeError, ValueError):
+        raise ValueError("a camera needs the numbers f, cx, cy and q32")
+    if not all(np.isfinite(v) for v in (f, cx, cy, q32)) or not f > 0 or not q32 > 0:
+        raise ValueError("the camera's words must be finite with f > 0 and q32 > 0, got f=%r cx=%r cy=%r q32=%r" % (f, cx, cy, q32))
+    b = 1.0 / q32
+    b16 = 16.0 * b
+    w = {"f": f, "cx": cx, "cy": cy, "b": b, "b16": b16, "fb": f * b, "fb16": f * b16}
+    if not all(np.isfinite(v) for v in w.values()):
+        raise ValueError("the camera's baseline is not finite")
+    return w
+
+
+def flow_window_bytes(r, wx, wy):
+    """The bytes a point's window of cur takes on the device: (2 wy + 2 r + 1) rows of an odd number of dwords, (2 wx + 2 r + 1 + 3) // 4
+    + 1 made odd - the one dword more is what a patch row that starts at the window's last bytes reads behind it."""
+    pitch = (2 * wx + 2 * r + 1 + 3) // 4 + 1
+    pitch += 1 - pitch % 2
+    return 4 * pitch * (2 * wy + 2 * r + 1)
+
+
+def flow_words(step=8, r=4, wx=8, wy=8, ratio=230, max_cost=FLOW_COST_MAX, capacity=4096):
+    """The words of a flow_match call as a dict of ints, after the checks the C entry makes (ValueError): step >= 1, r in 1 .. 7, wx and wy
+    >= 0 with (2 wx + 1) (2 wy + 1) <= 16384 and flow_window_bytes(r, wx, wy) <= 16384, ratio in 0 .. 256, max_cost >= 0, capacity in
+    0 .. 65536."""
+    w = {}
+    for k, v, lo, hi in (("step", step, 1, 2 ** 20), ("r", r, 1, FLOW_R_MAX), ("wx", wx, 0, 8192), ("wy", wy, 0, 8192), ("ratio", ratio, 0, 256),
+                         ("max_cost", max_cost, 0, 2 ** 31 - 1), ("capacity", capacity, 0, FLOW_CAPACITY_MAX)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ValueError("%s must be an integer in %d .. %d, got %r" % (k, lo, hi, v))
+        w[k] = int(v)
+    if (2 * w["wx"] + 1) * (2 * w["wy"] + 1) > FLOW_CANDIDATES_MAX:
+        raise ValueError("the window has more than %d candidates: wx=%d wy=%d" % (FLOW_CANDIDATES_MAX, w["wx"], w["wy"]))
+    if flow_window_bytes(w["r"], w["wx"], w["wy"]) > FLOW_WINDOW_BYTES:
+        raise ValueError("the window takes more than %d bytes: r=%d wx=%d wy=%d" % (FLOW_WINDOW_BYTES, w["r"], w["wx"], w["wy"]))
+    return w
+
+
+def _flow_dq(d):
+    """floor(16 d + 0.5) in double of float32 disparities, 0 where d is not positive and finite or the value leaves 1 .. 2^20."""
+    d = np.asarray(d, np.float32).astype(np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        q = np.floor(d * 16.0 + 0.5)
+        ok = np.isfinite(d) & (d > 0) & (q >= 1) & (q <= FLOW_DQ_MAX)
+    return np.where(ok, q, 0).astype(np.int64)
+
+
+def _flow_point(cam, u, v, dq):
+    """X0 of pixels (u, v) with disparity dq / 16 (arrays of equal shape, dq >= 1), in double, every operation on its own:
+    ((u - cx) b16) / dq, ((v - cy) b16) / dq, fb16 / dq."""
+    dq = np.asarray(dq, np.float64)
+    return ((np.asarray(u, np.float64) - cam["cx"]) * cam["b16"]) / dq, ((np.asarray(v, np.float64) - cam["cy"]) * cam["b16"]) / dq, cam["fb16"] / dq
+
+
+def _flow_move(pose, x, y, z):
+    """Xc = R X0 + t under one pose of twelve doubles, in voxel_map_insert's order: ((R[k,0] x + R[k,1] y) + R[k,2] z) + t[k]."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        return tuple(((pose[3 * k] * x + pose[3 * k + 1] * y) + pose[3 * k + 2] * z) + pose[9 + k] for k in range(3))
+
+
+def flow_match(prev, cur, d_prev, d_cur, camera, guess=None, step=8, r=4, wx=8, wy=8, ratio=230, max_cost=FLOW_COST_MAX, capacity=4096):
+    """Temporal matches of B frame pairs, the definition of include/stereo_vision_hip.h (Z1) in numpy.  prev, cur uint8 [B,H,W]: the
+    rectified left gray images of frames k - 1 and k; d_prev float32 [B,H,W]: the disparity of frame k - 1; d_cur float32 [B,H,W] or
+    None; camera: voxel_render_camera's dict (flow_camera reads it); guess float64 [B,12] or None: the expected motion, previous camera
+    to current camera, Xc = R X0 + t in voxel_map_pose's layout - None is the identity and skips the projection.
+      points      the pixels (u0, v0) with u0 % step == 0 and v0 % step == 0, in ascending v0 W + u0, with r <= u0 < W - r, r <= v0 < H - r
+                  and d0q = floor(16 d + 0.5) (in double) in 1 .. 2^20 for a positive, finite d = d_prev[v0, u0].
+      centre      X0 = (((u0 - cx) b16) / d0q, ((v0 - cy) b16) / d0q, fb16 / d0q), Xc = ((R_k0 x + R_k1 y) + R_k2 z) + t_k; a point with Xc.z
+                  <= FLOW_Z_MIN (0.1 m; or NaN) is dropped; c = (floor(((f Xc.x) / Xc.z + cx) + 0.5), floor(((f Xc.y) / Xc.z + cy) + 0.5)), and
+                  a point whose c is not within +-2^20 is dropped.  Without a guess c = (u0, v0).
+      candidates  (dx, dy) in [-wx, wx] x [-wy, wy] with r <= c.x + dx < W - r and r <= c.y + dy < H - r; cost = the sum of the absolute
+                  differences of the (2 r + 1)^2 patch of prev around (u0, v0) and that of cur around c + (dx, dy).
+      best        the least cost, among equals the least (dy + wy) (2 wx + 1) + (dx + wx); second: the least cost among the candidates
+                  with max(|dx - bdx|, |dy - bdy|) > 1.
+      match       a second exists, 256 best < ratio second, best <= max_cost, and the best is not on the rim: not (wx > 0 and |bdx| == wx)
+                  and not (wy > 0 and |bdy| == wy).
+    -> {"matches": int32 [B,capacity,6] = (u0, v0, d0q, u1, v1, d1q) in point order, (u1, v1) = c + best, d1q = floor(16 d_cur[v1, u1] + 0.5)
+    where that is in 1 .. 2^20 for a positive finite d_cur, else -1; "cost": int32 [B,capacity,2] = (best, second); "counts": int32 [B], -1
+    for a frame with more matches than capacity, whose rows are the first `capacity` of them}.  Rows at and behind a frame's count hold
+    -1."""
+    w = flow_words(step, r, wx, wy, ratio, max_cost, capacity)
+    cam = flow_camera(camera)
+    prev, cur = np.asarray(prev), np.asarray(cur)
+    if prev.dtype != np.uint8 or prev.ndim != 3 or cur.dtype != np.uint8 or cur.shape != prev.shape:
+        raise ValueError("prev and cur must be uint8 [B,H,W] of one shape, got %s %s and %s %s" % (prev.dtype, prev.shape, cur.dtype, cur.shape))
+    B, H, W = prev.shape
+    if B > FLOW_BATCH_MAX or not (1 <= W <= 8192 and 1 <= H <= 8192):
+        raise ValueError("at most 65535 frames of at most 8192 x 8192, got %s" % (prev.shape,))
+    d_prev = np.asarray(d_prev)
+    if d_prev.dtype != np.float32 or d_prev.shape != prev.shape or (d_cur is not None and (np.asarray(d_cur).dtype != np.float32 or np.asarray(d_cur).shape != prev.shape)):
+        raise ValueError("d_prev (and d_cur) must be float32 %s" % (prev.shape,))
+    if guess is not None:
+        guess = np.asarray(guess, np.float64)
+        if guess.shape != (B, 12):
+            raise ValueError("guess must be float64 [%d,12], got %s" % (B, guess.shape))
+    r, wx, wy, cap = w["r"], w["wx"], w["wy"], w["capacity"]
+    nwx, nwy, side = 2 * wx + 1, 2 * wy + 1, 2 * r + 1
+    BIG = 1 << 30
+    matches, cost, counts = np.full((B, cap, 6), -1, np.int32), np.full((B, cap, 2), -1, np.int32), np.zeros(B, np.int32)
+    vs, us = np.meshgrid(np.arange(0, H, w["step"]), np.arange(0, W, w["step"]), indexing="ij")
+    vs, us = vs.ravel(), us.ravel()
+    for b in range(B):
+        dq0 = _flow_dq(d_prev[b])
+        dq1 = None if d_cur is None else _flow_dq(np.asarray(d_cur)[b])
+        q = dq0[vs, us]
+        keep = (q > 0) & (us >= r) & (us < W - r) & (vs >= r) & (vs < H - r)
+        cxs, cys = us.astype(np.float64), vs.astype(np.float64)
+        if guess is not None:
+            x, y, z = _flow_point(cam, us, vs, np.maximum(q, 1))
+            X = _flow_move(guess[b], x, y, z)
+            with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+                keep &= X[2] > FLOW_Z_MIN
+                zs = np.where(keep, X[2], 1.0)
+                cxs, cys = np.floor(((cam["f"] * X[0]) / zs + cam["cx"]) + 0.5), np.floor(((cam["f"] * X[1]) / zs + cam["cy"]) + 0.5)
+                keep &= (np.abs(cxs) <= FLOW_CENTRE_MAX) & (np.abs(cys) <= FLOW_CENTRE_MAX)  # false for NaN
+        found = 0
+        P, C = prev[b].astype(np.int32), cur[b].astype(np.int32)
+        for i in np.flatnonzero(keep):
+            u0, v0, ccx, ccy = int(us[i]), int(vs[i]), int(cxs[i]), int(cys[i])
+            x_lo, x_hi, y_lo, y_hi = max(ccx - wx, r), min(ccx + wx, W - r - 1), max(ccy - wy, r), min(ccy + wy, H - r - 1)
+            if x_lo > x_hi or y_lo > y_hi:
+                continue
+            view = np.lib.stride_tricks.sliding_window_view(C[y_lo - r:y_hi + r + 1, x_lo - r:x_hi + r + 1], (side, side))
+            full = np.full((nwy, nwx), BIG, np.int64)
+            full[y_lo - ccy + wy:y_hi - ccy + wy + 1, x_lo - ccx + wx:x_hi - ccx + wx + 1] = np.abs(view - P[v0 - r:v0 + r + 1, u0 - r:u0 + r + 1]).sum((2, 3))
+            at = int(full.argmin())  # the first of equals
+            by, bx = divmod(at, nwx)
+            best = int(full[by, bx])
+            full[max(by - 1, 0):by + 2, max(bx - 1, 0):bx + 2] = BIG
+            second = int(full.min())
+            if second >= BIG or not 256 * best < w["ratio"] * second or best > w["max_cost"]:
+                continue
+            if (wx > 0 and abs(bx - wx) == wx) or (wy > 0 and abs(by - wy) == wy):
+                continue
+            if found < cap:
+                u1, v1 = ccx + bx - wx, ccy + by - wy
+                d1 = -1 if dq1 is None or dq1[v1, u1] == 0 else int(dq1[v1, u1])
+                matches[b, found], cost[b, found] = (u0, v0, int(q[i]), u1, v1, d1), (best, second)
+            found += 1
+        counts[b] = found if found <= cap else -1
+    return {"matches": matches, "cost": cost, "counts": counts}
+
+
+def _flow_gates(gate_q, dgate_q):
+    out = []
+    for v, what in ((gate_q, "gate_q"), (dgate_q, "dgate_q")):
+        v = FLOW_GATE_MAX if v is None else v
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= FLOW_GATE_MAX:
+            raise ValueError("%s must be an integer in 0 .. 2^20 (1/16 px) or None, got %r" % (what, v))
+        out.append(int(v))
+    return out
+
+
+def _flow_sums_setup(matches, counts, poses):
+    matches, counts = np.asarray(matches), np.asarray(counts)
+    if matches.dtype != np.int32 or matches.ndim != 3 or matches.shape[2] != 6 or matches.shape[1] > FLOW_CAPACITY_MAX or matches.shape[0] > FLOW_BATCH_MAX:
+        raise ValueError("matches must be int32 [B,capacity,6] with capacity <= 65536 and B <= 65535, got %s %s" % (matches.dtype, matches.shape))
+    B = matches.shape[0]
+    if counts.dtype != np.int32 or counts.shape != (B,):
+        raise ValueError("counts must be int32 [%d], got %s %s" % (B, counts.dtype, counts.shape))
+    poses = np.asarray(poses, np.float64)
+    if poses.shape != (B, 12):
+        raise ValueError("poses must be float64 [%d,12], got %s" % (B, poses.shape))
+    return matches, counts, poses
+
+
+def _flow_q(v, lim):
+    """floor(v + 0.5) of doubles, clamped to +-lim, as int64."""
+    return np.clip(np.floor(v + 0.5), -lim, lim).astype(np.int64)
+
+
+def flow_pose_sums(matches, counts, camera, poses, gate_q=None, dgate_q=None):
+    """The sums of one Gauss-Newton round of the egomotion fit, the definition of include/stereo_vision_hip.h (Z2) in numpy.  matches int32
+    [B,capacity,6] and counts int32 [B] as flow_match gives them (a count of -1 or 0 gives sums of 0; a count beyond the capacity counts as
+    the capacity), poses float64 [B,12]: previous camera to current camera, gate_q and dgate_q in 1/16 px, 0 .. 2^20, None: 2^20.
+      per match   d0q in 1 .. 2^20, else it is skipped.  X0 as in flow_match, Xc = R X0 + t in its order, (x, y, z) = Xc.  fz = f / z,
+                  xz = x / z, yz = y / z, bz = fb / z.  pu = floor(16 (f xz + cx) + 0.5), pv = floor(16 (f yz + cy) + 0.5), pd = floor(16 bz +
+                  0.5), as doubles.  inside: z > FLOW_Z_MIN and |pu|, |pv|, |pd| <= 2^30 (false for NaN).
+      residuals   ru = 16 u1 - pu, rv = 16 v1 - pv, rd = d1q - pd, integers.  inlier: inside, |ru| <= gate_q, |rv| <= gate_q and ru^2 + rv^2 <=
+                  gate_q^2; d-inlier: an inlier with d1q > 0 and |rd| <= dgate_q.
+      Jacobian    with respect to (t, omega) of Xc' = exp(omega) Xc + t: a = fz xz, Ju = (fz, 0, -a, -(a y), f (1 + xz xz), -(f yz)); c = fz yz,
+                  Jv = (0, fz, -c, -(f (1 + yz yz)), a y, f xz); e = bz / z, Jd = (0, 0, -e, -(e y), e x, 0); every entry quantised as
+                  clamp(floor(16 J + 0.5), +-2^20).
+      sums        int64 [B,32], FLOW_SUMS: inside, inliers, dinliers, E = sum ru^2 + rv^2, Ed = sum rd^2, g[6] = sum Jq r, A[21] = sum Jq_i Jq_j,
+                  the upper triangle row-major - the u and v rows of the inliers, the d rows of the d-inliers.  Every word stays below 2^59.
+    -> int64 [B,32]."""
+    gate_q, dgate_q = _flow_gates(gate_q, dgate_q)
+    cam = flow_camera(camera)
+    matches, counts, poses = _flow_sums_setup(matches, counts, poses)
+    B, cap = matches.shape[:2]
+    sums = np.zeros((B, 32), np.int64)
+    iu = np.triu_indices(6)
+    for b in range(B):
+        n = min(int(counts[b]), cap)
+        if n <= 0:
+            continue
+        m = matches[b, :n].astype(np.int64)
+        u0, v0, d0, u1, v1, d1 = (m[:, k] for k in range(6))
+        live = (d0 >= 1) & (d0 <= FLOW_DQ_MAX)
+        x0, y0, z0 = _flow_point(cam, u0, v0, np.where(live, d0, 1))
+        x, y, z = _flow_move(poses[b], x0, y0, z0)
+        with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+            live &= z > FLOW_Z_MIN
+            z = np.where(live, z, 1.0)
+            fz, xz, yz, bz = cam["f"] / z, x / z, y / z, cam["fb"] / z
+            pu, pv, pd = np.floor(16.0 * (cam["f"] * xz + cam["cx"]) + 0.5), np.floor(16.0 * (cam["f"] * yz + cam["cy"]) + 0.5), np.floor(16.0 * bz + 0.5)
+            inside = live & (np.abs(pu) <= FLOW_PIXEL_MAX) & (np.abs(pv) <= FLOW_PIXEL_MAX) & (np.abs(pd) <= FLOW_PIXEL_MAX)
+            zero = np.zeros_like(z)
+            a, c, e = fz * xz, fz * yz, bz / z
+            J = np.stack([np.stack([fz, zero, -a, -(a * y), cam["f"] * (1.0 + xz * xz), -(cam["f"] * yz)], -1),
+                          np.stack([zero, fz, -c, -(cam["f"] * (1.0 + yz * yz)), a * y, cam["f"] * xz], -1),
+                          np.stack([zero, zero, -e, -(e * y), e * x, zero], -1)], 1)  # [n,3,6]
+            J = np.where(inside[:, None, None], J, 0.0)
+            Jq = _flow_q(16.0 * J, FLOW_J_MAX)
+        pu, pv, pd = (np.where(inside, p, 0.0).astype(np.int64) for p in (pu, pv, pd))
+        ru, rv, rd = 16 * u1 - pu, 16 * v1 - pv, d1 - pd
+        inl = inside & (np.abs(ru) <= gate_q) & (np.abs(rv) <= gate_q)
+        ru, rv = np.where(inl, ru, 0), np.where(inl, rv, 0)
+        inl &= ru * ru + rv * rv <= gate_q * gate_q
+        dinl = inl & (d1 > 0) & (np.abs(rd) <= dgate_q)
+        res = np.stack([np.where(inl, ru, 0), np.where(inl, rv, 0), np.where(dinl, rd, 0)], 1)  # [n,3]
+        Jq = Jq * np.stack([inl, inl, dinl], 1)[:, :, None]
+        sums[b, 0], sums[b, 1], sums[b, 2] = inside.sum(), inl.sum(), dinl.sum()
+        sums[b, 3], sums[b, 4] = (res[:, 0] ** 2 + res[:, 1] ** 2).sum(), (res[:, 2] ** 2).sum()
+        sums[b, 5:11] = (Jq * res[:, :, None]).sum((0, 1))
+        sums[b, 11:] = np.einsum("nki,nkj->ij", Jq, Jq)[iu]
+    return sums
+
+
+def flow_pose_sums_brute(matches, counts, camera, poses, gate_q=None, dgate_q=None):
+    """flow_pose_sums match by match: Python floats in the stated order in front of the rounding, Python integers behind it."""
+    import math
+    gate_q, dgate_q = _flow_gates(gate_q, dgate_q)
+    cam = flow_camera(camera)
+    matches, counts, poses = _flow_sums_setup(matches, counts, poses)
+    f, cx, cy, b16, fb, fb16 = (cam[k] for k in ("f", "cx", "cy", "b16", "fb", "fb16"))
+    B, cap = matches.shape[:2]
+    out = np.zeros((B, 32), np.int64)
+
+    def rnd(v):
+        return math.floor(v + 0.5)
+
+    for b in range(B):
+        s = [0] * 32
+        p = [float(v) for v in poses[b]]
+        for i in range(max(min(int(counts[b]), cap), 0)):
+            u0, v0, d0, u1, v1, d1 = (int(v) for v in matches[b, i])
+            if not 1 <= d0 <= FLOW_DQ_MAX:
+                continue
+            X0 = (((u0 - cx) * b16) / d0, ((v0 - cy) * b16) / d0, fb16 / d0)
+            x, y, z = (((p[3 * k] * X0[0] + p[3 * k + 1] * X0[1]) + p[3 * k + 2] * X0[2]) + p[9 + k] for k in range(3))
+            if not z > FLOW_Z_MIN:
+                continue
+            fz, xz, yz, bz = f / z, x / z, y / z, fb / z
+            pred = (16.0 * (f * xz + cx) + 0.5, 16.0 * (f * yz + cy) + 0.5, 16.0 * bz + 0.5)
+            if not all(math.isfinite(v) and abs(math.floor(v)) <= FLOW_PIXEL_MAX for v in pred):
+                continue
+            pu, pv, pd = (math.floor(v) for v in pred)
+            s[0] += 1
+            ru, rv, rd = 16 * u1 - pu, 16 * v1 - pv, d1 - pd
+            if ru * ru + rv * rv > gate_q * gate_q:
+                continue
+            s[1] += 1
+            a, c, e = fz * xz, fz * yz, bz / z
+            rows = [((fz, 0.0, -a, -(a * y), f * (1.0 + xz * xz), -(f * yz)), ru), ((0.0, fz, -c, -(f * (1.0 + yz * yz)), a * y, f * xz), rv)]
+            s[3] += ru * ru + rv * rv
+            if d1 > 0 and abs(rd) <= dgate_q:
+                s[2] += 1
+                s[4] += rd * rd
+                rows.append(((0.0, 0.0, -e, -(e * y), e * x, 0.0), rd))
+            for J, res in rows:
+                Jq = [max(-FLOW_J_MAX, min(FLOW_J_MAX, rnd(16.0 * v))) for v in J]
+                at = 11
+                for i6 in range(6):
+                    s[5 + i6] += Jq[i6] * res
+                    for j6 in range(i6, 6):
+                        s[at] += Jq[i6] * Jq[j6]
+                        at += 1
+        out[b] = s
+    return out
+
+
+def _flow_exp(om):
+    """Rodrigues' rotation of the vector om (radians), as voxel_align_solve_plane makes it."""
+    angle = float(np.sqrt((om * om).sum()))
+    K = np.array([[0.0, -om[2], om[1]], [om[2], 0.0, -om[0]], [-om[1], om[0], 0.0]])
+    if angle > 1e-12:
+        return np.eye(3) + (np.sin(angle) / angle) * K + ((1.0 - np.cos(angle)) / (angle * angle)) * (K @ K), angle
+    return np.eye(3) + K, angle
+
+
+def flow_solve(sums, poses, min_inliers=12, rcond=1e-6):
+    """The fit of one round: from flow_pose_sums' words and the poses they were taken under -> (poses' float64 [B,12], ok bool [B], step
+    float64 [B,2] = (radians, metres)).  A (6 x 6, symmetric) and g from Python integers in double, scaled by sc_i = sqrt(max(A_ii, 1));
+    delta = lstsq(A / sc sc^T, g / sc, rcond) / sc - the minimum-norm solution, as voxel_align_solve_plane's; the residuals' and the
+    Jacobian's factors of 16 cancel, so delta = (t_d in metres, omega in radians).  R' = exp(omega) R, t' = exp(omega) t + t_d.  A frame
+    with inliers < min_inliers, or without a finite fit, keeps its pose: ok False, step 0."""
+    if isinstance(min_inliers, bool) or int(min_inliers) != min_inliers:
+        raise ValueError("min_inliers must be an integer, got %r" % (min_inliers,))
+    sums, poses = np.asarray(sums), np.asarray(poses, np.float64)
+    B = len(poses)
+    if sums.shape != (B, 32) or poses.shape != (B, 12):
+        raise ValueError("sums must be [B,32] and poses [B,12], got %s and %s" % (sums.shape, poses.shape))
+    out, ok, step = poses.copy(), np.zeros(B, bool), np.zeros((B, 2))
+    iu = np.triu_indices(6)
+    for b in range(B):
+        s = [int(v) for v in sums[b]]
+        if s[1] < max(int(min_inliers), 1):
+            continue
+        A = np.zeros((6, 6))
+        A[iu] = [float(v) for v in s[11:32]]
+        A = A + np.triu(A, 1).T
+        g = np.array([float(v) for v in s[5:11]])
+        sc = np.sqrt(np.maximum(np.diag(A), 1.0))
+        try:
+            x = np.linalg.lstsq(A / np.outer(sc, sc), g / sc, rcond=float(rcond))[0] / sc
+        except np.linalg.LinAlgError:
+            continue
+        td, om = x[:3], x[3:]
+        if not np.isfinite(x).all():
+            continue
+        Rd, angle = _flow_exp(om)
+        new = np.concatenate([(Rd @ poses[b, :9].reshape(3, 3)).reshape(9), Rd @ poses[b, 9:] + td])
+        if not np.isfinite(new).all():
+            continue
+        out[b], ok[b], step[b] = new, True, (angle, float(np.sqrt((td * td).sum())))
+    return out, ok, step
+
+
+def flow_identity(B):
+    """float64 [B,12]: B identity motions."""
+    return np.tile(np.array([1.0, 0, 0, 0, 1.0, 0, 0, 0, 1.0, 0, 0, 0]), (int(B), 1))
+
+
+def flow_loop(sums_of, start, gates=FLOW_GATES, dgate=2.0, iterations=10, eps=None, min_inliers=12):
+    """flow_egomotion's loop around any source of sums - sums_of(poses [B,12], gate_q, dgate_q) -> int64 [B,32]: the numpy definition's or
+    the device's, read back.  Everything else is host numpy, the same for both."""
+    eps = FLOW_EPS if eps is None else eps
+    if isinstance(iterations, bool) or int(iterations) != iterations or iterations < 0:
+        raise ValueError("iterations must be an integer >= 0, got %r" % (iterations,))
+    if len(eps) != 2 or not all(np.isfinite(float(e)) and float(e) >= 0 for e in eps):
+        raise ValueError("eps must be two finite numbers >= 0: radians and metres, got %r" % (eps,))
+    gates = tuple(gates)
+    if not gates or not all(g is None or (np.isfinite(float(g)) and 0 <= float(g) <= 65536) for g in gates) or not 0 <= float(dgate) <= 65536:
+        raise ValueError("gates must be pixels in 0 .. 65536 or None, at least one, and dgate pixels, got %r and %r" % (gates, dgate))
+    gates_q = [None if g is None else int(np.floor(16.0 * float(g) + 0.5)) for g in gates]
+    dgate_q = int(np.floor(16.0 * float(dgate) + 0.5))
+    poses = np.ascontiguousarray(np.asarray(start, np.float64))
+    B = len(poses)
+    sums, ok = np.zeros((B, 32), np.int64), np.zeros(B, bool)
+    inliers, rms, rounds = [], [], 0
+    for i in range(int(iterations)):
+        sums = np.ascontiguousarray(sums_of(poses, gates_q[min(i, len(gates_q) - 1)], dgate_q), np.int64)
+        poses, ok, step = flow_solve(sums, poses, min_inliers)
+        rounds += 1
+        n, E = sums[:, 1].astype(np.float64), sums[:, 3].astype(np.float64)
+        inliers.append(sums[:, 1].copy())
+        rms.append(np.where(n > 0, np.sqrt(E / np.maximum(n, 1.0)) / 16.0, 0.0))
+        if i >= len(gates_q) - 1 and ((step[ok, 0] < eps[0]) & (step[ok, 1] < eps[1])).all():
+            break
+    return {"poses": poses, "ok": ok, "rounds": rounds, "inliers": np.array(inliers, np.int64).reshape(rounds, B), "rms_px": np.array(rms, np.float64).reshape(rounds, B),
+            "sums": sums}
+
+
+def flow_egomotion(matches, counts, camera, start=None, gates=FLOW_GATES, dgate=2.0, iterations=10, eps=None, min_inliers=12):
+    """The camera's motion between two frames from their temporal matches: a gated Gauss-Newton loop over flow_pose_sums and flow_solve.
+    start float64 [B,12] or None (the identity): previous camera to current camera.  Round i gates the reprojection error at
+    gates[min(i, len - 1)] pixels (None: no gate) and the disparity's at dgate pixels; the loop stops once the schedule is through and
+    every fitted frame's step is below eps = (radians, metres) - None: FLOW_EPS -, or after `iterations` rounds.  -> {"poses": float64
+    [B,12], "ok": bool [B] - the last round fitted the frame -, "rounds", "inliers": int64 [rounds,B], "rms_px": float64 [rounds,B] = sqrt(E /
+    inliers) / 16 as each round found them, "sums": the last round's int64 [B,32]}.  The inliers of the result are those of the last round's
+    sums: counted under the pose that round started from."""
+    matches, counts = np.asarray(matches), np.asarray(counts)
+    start = flow_identity(matches.shape[0]) if start is None else start
+    _flow_sums_setup(matches, counts, start)
+    return flow_loop(lambda poses, gate_q, dgate_q: flow_pose_sums(matches, counts, camera, poses, gate_q, dgate_q), start, gates, dgate, iterations, eps, min_inliers)
+
+
+def flow_chain(rel, start=None, XR=None, XT=None, ok=None):
+    """The poses of B + 1 frames from B motions between them: float64 [B+1,12], frame to world in voxel_map_pose's layout - what update(),
+    align() and --poses take.  rel float64 [B,12]: motion k carries the camera of frame k into that of frame k + 1 (Xc' = R Xc + t,
+    flow_egomotion's); start: the pose of frame 0 ([12]; None: the identity); XR, XT: the rig's transform, camera to frame (Pf = XR Pc + XT;
+    None: the identity, zero); ok bool [B] or None: a motion that is not ok is replaced by the one before it, the first such by the
+    identity.  W_k = W_{k-1} M T_k^-1 M^-1 with M = (XR | XT) and T^-1 = (R^T | -(R^T t)): the inverse is the transpose, R and XR must be
+    rotations.  Every product of two rigid motions is made on its own, as voxel_render_cams makes them: (Ra | ta) (Rb | tb) = (Ra Rb | Ra
+    tb + ta) with C[i,j] = (Ra[i,0] Rb[0,j] + Ra[i,1] Rb[1,j]) + Ra[i,2] Rb[2,j] and o[i] = ((Ra[i,0] tb[0] + Ra[i,1] tb[1]) + Ra[i,2] tb[2]) +
+    ta[i], taken from the left: ((W M) T^-1) M^-1."""
+    rel = np.asarray(rel, np.float64).reshape(-1, 12)
+    B = len(rel)
+    ok = np.ones(B, bool) if ok is None else np.asarray(ok, bool).reshape(B)
+    XR = np.eye(3) if XR is None else np.asarray(XR, np.float64).reshape(3, 3)
+    XT = np.zeros(3) if XT is None else np.asarray(XT, np.float64).reshape(3)
+    start = flow_identity(1)[0] if start is None else np.asarray(start, np.float64).reshape(12)
+
+    def mul(Ra, ta, Rb, tb):
+        C = np.array([[(Ra[i, 0] * Rb[0, j] + Ra[i, 1] * Rb[1, j]) + Ra[i, 2] * Rb[2, j] for j in range(3)] for i in range(3)])
+        o = np.array([((Ra[i, 0] * tb[0] + Ra[i, 1] * tb[1]) + Ra[i, 2] * tb[2]) + ta[i] for i in range(3)])
+        return C, o
+
+    def inv(R, t):
+        Rt = R.T
+        return Rt, np.array([-((Rt[k, 0] * t[0] + Rt[k, 1] * t[1]) + Rt[k, 2] * t[2]) for k in range(3)])
+
+    Mi = inv(XR, XT)
+    out = [start.copy()]
+    last = flow_identity(1)[0]
+    for k in range(B):
+        last = rel[k] if ok[k] else last
+        W = (out[-1][:9].reshape(3, 3), out[-1][9:])
+        W = mul(*W, XR, XT)
+        W = mul(*W, *inv(last[:9].reshape(3, 3), last[9:]))
+        W = mul(*W, *Mi)
+        out.append(np.concatenate([W[0].reshape(9), W[1]]))
+    return np.ascontiguousarray(np.array(out))
+
+
+FLOW_ODOMETRY = dict(step=8, r=4, wx=8, wy=8, ratio=230, max_cost=FLOW_COST_MAX, capacity=8192, cold=(64, 24), first=None, gates=FLOW_GATES, dgate=2.0, iterations=10,
+                     eps=None, min_inliers=12)  # the words of flow_odometry and StereoRig.odometry, and their defaults
+
+
+def flow_odometry_spec(**spec):
+    """FLOW_ODOMETRY with the caller's words in place of the defaults; ValueError for a word it does not have."""
+    unknown = sorted(set(spec) - set(FLOW_ODOMETRY))
+    if unknown:
+        raise ValueError("unknown words %s: the odometry takes %s" % (unknown, sorted(FLOW_ODOMETRY)))
+    s = dict(FLOW_ODOMETRY, **spec)
+    if len(tuple(s["cold"])) != 2:
+        raise ValueError("cold must be (wx, wy), got %r" % (s["cold"],))
+    return s
+
+
+def flow_odometry(match_of, ego_of, pairs, guess="velocity", **spec):
+    """The motions of `pairs` consecutive frame pairs, pair k being frames (k, k + 1) - what StereoRig.odometry runs with device
+    callables and the tests with flow_match and flow_egomotion.  match_of(lo, hi, guess [hi - lo, 12] or None, wx, wy) matches the pairs
+    lo .. hi - 1 in one call and returns an object with .matches and .counts or such a dict; ego_of(that, start [hi - lo, 12]) returns
+    flow_egomotion's dict.  guess:
+      "identity"   every pair in one call, without a guess, over the cold-start window spec["cold"] = (wx, wy);
+      [pairs,12]   every pair in one call under the caller's motions, over (wx, wy);
+      "velocity"   the pairs one after the other, each under the motion of the pair before it over (wx, wy); the first pair - under
+                   spec["first"] if that is given - and every pair behind one whose fit was not ok have no guess and take the cold window.
+    The fit of a pair starts from its guess.  -> {"rel": float64 [pairs,12], "ok": bool [pairs], "inliers": int64 [pairs] - the last
+    round's -, "rounds": [calls], "calls": the match results, one per call, in pair order}."""
+    s = flow_odometry_spec(**spec)
+    rel, ok, inliers, rounds, calls = np.zeros((pairs, 12)), np.zeros(pairs, bool), np.zeros(pairs, np.int64), [], []
+
+    def run(lo, hi, g, wx, wy):
+        got = match_of(lo, hi, g, int(wx), int(wy))
+        ego = ego_of(got, flow_identity(hi - lo) if g is None else g)
+        rel[lo:hi], ok[lo:hi], inliers[lo:hi] = ego["poses"], ego["ok"], ego["inliers"][-1] if ego["rounds"] else 0
+        rounds.append(ego["rounds"])
+        calls.append(got)
+
+    if pairs <= 0:
+        pass
+    elif isinstance(guess, str) and guess == "identity":
+        run(0, pairs, None, *s["cold"])
+    elif isinstance(guess, str) and guess == "velocity":
+        last = None if s["first"] is None else np.asarray(s["first"], np.float64).reshape(1, 12)
+        for k in range(pairs):
+            run(k, k + 1, last, *((s["wx"], s["wy"]) if last is not None else s["cold"]))
+            last = rel[k:k + 1].copy() if ok[k] else None
+    elif isinstance(guess, str):
+        raise ValueError("guess must be 'velocity', 'identity' or motions [%d,12], got %r" % (pairs, guess))
+    else:
+        g = np.asarray(guess, np.float64)
+        if g.shape != (pairs, 12):
+            raise ValueError("guess must be 'velocity', 'identity' or motions [%d,12], got shape %s" % (pairs, g.shape))
+        run(0, pairs, np.ascontiguousarray(g), s["wx"], s["wy"])
+    return {"rel": rel, "ok": ok, "inliers": inliers, "rounds": rounds, "calls": calls}
+
+
+def flow_pose_lines(poses):
+    """'x y yaw' per frame, the lines --poses reads, from poses float64 [B,12] (frame to world): x = t[0], y = t[1], yaw = atan2(R[1,0],
+    R[0,0]); the numbers by repr, so that reading gives back the doubles."""
+    p = np.asarray(poses, np.float64).reshape(-1, 12)
+    return ["%r %r %r" % (float(q[9]), float(q[10]), float(np.arctan2(q[3], q[0]))) for q in p]
+
+
 GROUND_BINS_MIN, GROUND_BINS_MAX = 8, 4096
 GROUND_VH_MIN, GROUND_TOL_MAX, GROUND_G_TOL_MAX, GROUND_HEIGHT_MAX = -32768, 16, 4096, 32768
 GROUND_LABELS = {"invalid": 0, "ground": 1, "obstacle": 2, "below": 3}
@@ -3997,6 +4510,12 @@ def main(argv=None):
     parser.add_argument("--poses", type=str, default="", metavar="FILE",
                         help="for --occupancy-map and --voxel-map: a text file with one line 'x y yaw' per frame - the vehicle in the world, metres and "
                              "radians, yaw counter-clockwise")
+    parser.add_argument("--odometry", type=str, default="", metavar="FILE",
+                        help="with --batch: stereo visual odometry of the folder, before anything else runs - every frame matched against "
+                             "the one before it and the camera's motion fitted (StereoRig.odometry, the batches overlapping by a frame).  "
+                             "The chained poses are written to FILE, one line 'x y yaw' per frame as --poses reads them, frame 0 at the "
+                             "origin, and the motions to <FILE>.rel.txt, twelve words per pair of frames: the rotation row by row, then "
+                             "the translation, previous camera to current camera.  Without --poses the run takes FILE as its --poses")
     parser.add_argument("--match", type=str, default="", metavar="DX,DY,DYAW[,NX,NY,NYAW]",
                         help="with --occupancy-map and --poses: take the poses as guesses - frame 0 is fused where its line says; every later "
                              "frame is first matched against the map built so far over a window of +-DX, +-DY metres and +-DYAW radians "
@@ -4023,6 +4542,10 @@ def main(argv=None):
                              "through the final map; prints per frontier the heading in degrees that sees the most undecided cells and "
                              "the distinct unknown, free and occupied cells seen from there")
     args = parser.parse_args(argv)
+    if args.odometry and not args.batch:
+        parser.error("--odometry needs --batch")
+    if args.odometry and not args.poses and (args.occupancy_map or args.voxel_map):
+        args.poses = args.odometry  # written below, before anything reads it
     args.match_window = None
     args.voxel_match_window = None
     args.voxel_carve_spec = None
@@ -4173,6 +4696,8 @@ def main(argv=None):
         os.makedirs(args.occupancy, exist_ok=True)
     if args.voxel_render_spec is not None:
         os.makedirs(args.voxel_render_spec[0], exist_ok=True)
+    if args.odometry:
+        _run_odometry(args, ldir, rdir, files)
     args.pose_rows = None
     if args.voxel_map:
         try:
@@ -4376,6 +4901,34 @@ def cli_voxel_render_text(counts):
 def _write_png(path, u8):
     from PIL import Image
     Image.fromarray(u8).save(path)
+
+
+def _run_odometry(args, ldir, rdir, files):
+    """--odometry FILE: the folder through StereoRig.odometry, --batch frames at a time and the frame before them, each batch's first pair
+    under the motion of the pair before it; the chained poses to FILE, the motions to FILE.rel.txt."""
+    import torch
+    from ..rig import StereoRig
+    rig = StereoRig(1242 // args.scale, 375 // args.scale, calibration=args.camera_calibration, rectify=args.rectify, scale=args.scale)
+    rel, ok = [], []
+    try:
+        for i in range(0, len(files), args.batch):
+            names = files[max(i - 1, 0):i + args.batch]
+            lr = [(_imread_bgr(os.path.join(ldir, f), args.scale), _imread_bgr(os.path.join(rdir, f), args.scale)) for f in names]
+            if args.swap:
+                lr = [(r, l) for l, r in lr]
+            left = torch.from_numpy(np.stack([l for l, _ in lr])).cuda(rig.device)
+            right = torch.from_numpy(np.stack([r for _, r in lr])).cuda(rig.device)
+            got = rig.odometry(left, right, pixel_format="bgr", first=rel[-1] if rel and ok[-1] else None)
+            rel.extend(got["rel"])
+            ok.extend(got["ok"])
+    finally:
+        rig.close()
+    poses = flow_chain(np.array(rel).reshape(-1, 12), None, CAMERA_TO_VEHICLE, None, np.array(ok, bool))
+    with open(args.odometry, "w") as f:
+        f.write("".join(line + "\n" for line in flow_pose_lines(poses)))
+    with open(args.odometry + ".rel.txt", "w") as f:
+        f.write("".join(" ".join(repr(float(v)) for v in row) + "\n" for row in rel))
+    print("odometry: %d frames, %d of %d motions fitted, written to %s" % (len(files), int(np.sum(ok)), len(ok), args.odometry))
 
 
 def _run_batched(args, ldir, rdir, files):
