@@ -101,6 +101,12 @@
  *      camera's motion between the two frames (sv_flow_pose_sums_device).  stereo_vision.sv.flow_match and flow_pose_sums state the
  *      definitions in numpy; flow_solve, flow_egomotion and flow_chain are the fit, the loop and the chain of poses on the host.
  *
+ *  (AA) Behind the engine and (Z), in front of every stage that takes a disparity map: temporal consistency (sv_disparity_warp_*) - the
+ *      map of frame k - 1 warped into frame k under the motion between them, the nearest source per pixel kept, and the prediction held
+ *      against what frame k measured: a label per pixel (agree, nearer, farther, measured only, expected only) and a filtered map - gaps
+ *      filled from the frame before, or only what it confirms, or all but what it contradicts.  stereo_vision.sv.disparity_warp states
+ *      the definition in numpy.
+ *
  * All sv_* functions return SV_OK (0) or a negative sv_status; sv_last_error() gives the text.
  * Nothing in this library calls exit().
  */
@@ -1839,6 +1845,53 @@ int sv_flow_pose_sums_workspace(int capacity, int batch, size_t *bytes);
  * a NULL matches or workspace, a misaligned pointer, too small a workspace. */
 int sv_flow_pose_sums_device(const int32_t *matches, const int32_t *counts, const double *poses, int batch, int capacity, const sv_flow_spec *spec, int gate_q,
                              int dgate_q, int64_t *sums, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- (AA) temporal consistency: the disparity map of frame k - 1 warped into frame k under the motion between them, and compared ---- */
+
+/* The camera as in (Z) - f, cx, cy in pixels, b16 = 16 b, fb = f b, fb16 = f b16, made once by the caller in double; all finite, f, b16, fb
+ * and fb16 > 0 - and the words of the call: e_max in 0 .. 4, tol_q in 0 .. 2^20 (1/16 px), rel_q in 0 .. 256, mode 0 fill, 1 confirm,
+ * 2 reject.  reserved: 0. */
+typedef struct {
+    double f, cx, cy, b16, fb, fb16;
+    int32_t e_max, tol_q, rel_q, mode;
+    int32_t reserved[12];
+} sv_warp_spec;
+
+/* d_prev float [batch][height][width]: the disparity of frame k - 1; d_cur the same of frame k, or NULL; poses double [batch][12]: the
+ * motion, previous camera to current camera, Xc = R X0 + t, R row-major, then t ((Z)'s layout).  dq(d) = floor(16 d + 0.5) (in double)
+ * where that is in 1 .. 2^20 for a positive, finite d, else 0.
+ *   sources     every pixel (u0, v0) with d0q = dq(d_prev[v0][u0]) >= 1; its index is src = v0 width + u0.
+ *   moved       X0 = (((u0 - cx) b16) / d0q, ((v0 - cy) b16) / d0q, fb16 / d0q); Xc_k = ((R_k0 x + R_k1 y) + R_k2 z) + t_k, as in (Z1).  Doubles,
+ *               one operation at a time, nothing contracted.
+ *   kept        z = Xc.z > 0.1 (false for NaN); pd = floor(16 (fb / z) + 0.5) in 1 .. 2^20; tu = floor(((f Xc.x) / z + cx) + 0.5), tv =
+ *               floor(((f Xc.y) / z + cy) + 0.5) with |tu|, |tv| <= 2^20 (false for NaN).  Every other source is dropped.
+ *   footprint   e = min(e_max, (pd + d0q - 1) / d0q - 1) in integers: a point that came closer covers the pixels (tu + dx, tv + dy) with
+ *               dx, dy in 0 .. e that lie inside the image.
+ *   winner      per target pixel, of the sources that cover it: the largest pd, among equals the smallest src.  It does not depend
+ *               on the schedule.
+ *   outputs     expected int32 [batch][height][width]: the winner's pd, or 0; source int32 the same shape: the winner's src, or -1;
+ *               counts int32 [batch][8] = (sources kept, pixels covered - every cover inside the image, once per source -, the pixels
+ *               with label 0 .. 5).
+ *   with d_cur  mq = dq(d_cur), ex = expected, t = tol_q + ((rel_q ex) >> 8).  label uint8 [batch][height][width]: 0 neither (mq = 0, ex =
+ *               0), 1 measured only, 2 expected only, else 3 agree |mq - ex| <= t, 4 nearer mq > ex + t, 5 farther mq < ex - t.  out float
+ *               [batch][height][width]: mode 0 - d_cur's own bits where mq > 0, else (float)ex / 16 (exact) where ex > 0, else -1.0f; mode 1
+ *               - d_cur's bits where the label is 3, else -1.0f; mode 2 - d_cur's bits where the label is 1 or 3, else -1.0f.
+ *   without     label and out are neither read nor written (they may be NULL); counts takes the labels as 0 and 2. */
+
+/* Host only: the bytes of the workspace sv_disparity_warp_device needs: 8 per pixel.  SV_ERR_ARG (bytes untouched) for a NULL bytes,
+ * batch outside 0..65535, width or height outside 1..8192. */
+int sv_disparity_warp_workspace(int width, int height, int batch, size_t *bytes);
+/* Enqueued on `stream` (a hipStream_t, NULL = the default stream) as three kernels - the keys and counts cleared, a lane per source
+ * pixel with one 64-bit integer atomic max of (pd << 32) | (0xffffffff - src) per covered pixel, a lane per target pixel - and not waited
+ * for: nothing is allocated, no host synchronisation is made, no float atomic is issued, nothing is assumed of what the outputs or the
+ * workspace held before, and every output is written in full.  All pointers device; d_prev, d_cur, expected, source, out and counts
+ * 4-byte, poses and the workspace 8-byte aligned.  Returns SV_OK (nothing enqueued for batch == 0), SV_ERR_HIP, or SV_ERR_ARG - nothing
+ * enqueued, the outputs untouched, the text in sv_last_error(NULL) - for what the workspace call refuses; a NULL spec or a bad word of
+ * it; with batch > 0 a NULL d_prev, poses, expected, source, counts or workspace, and beside a d_cur a NULL label or out; a misaligned
+ * pointer; too small a workspace; an output or the workspace that shares bytes with an input or with another output. */
+int sv_disparity_warp_device(const float *d_prev, const float *d_cur, const double *poses, int batch, int width, int height, const sv_warp_spec *spec,
+                             int32_t *expected, int32_t *source, uint8_t *label, float *out, int32_t *counts, void *workspace, size_t workspace_bytes,
+                             void *stream);
 
 /* ---- (A)the reference's exported symbols ------------------------------------------------------------- */
 

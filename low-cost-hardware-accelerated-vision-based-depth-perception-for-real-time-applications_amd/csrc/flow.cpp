@@ -20,11 +20,7 @@ const char *check_camera(const char *prefix, const sv_flow_spec *s) {
     if (!s) return prefixed(prefix, "spec is NULL");
     for (int k = 0; k < 9; k++)
         if (s->reserved[k] != 0) return prefixed(prefix, "a reserved word of the spec is not 0");
-    const double w[6] = {s->f, s->cx, s->cy, s->b16, s->fb, s->fb16};
-    for (double v : w)
-        if (!isfinite(v)) return prefixed(prefix, "a word of the camera is not finite");
-    if (!(s->f > 0.0) || !(s->b16 > 0.0) || !(s->fb > 0.0) || !(s->fb16 > 0.0)) return prefixed(prefix, "f, b16, fb and fb16 must be > 0");
-    return nullptr;
+    return check_camera_words(prefix, s);
 }
 
 // NULL for the words of a match call, else what is wrong with them.
@@ -38,12 +34,6 @@ const char *check_match_words(const char *prefix, const sv_flow_spec *s) {
     if (s->ratio < 0 || s->ratio > 256) return prefixed(prefix, "ratio outside 0..256");
     if (s->max_cost < 0) return prefixed(prefix, "max_cost < 0");
     if (s->capacity < 0 || s->capacity > sv::FLOW_CAPACITY_MAX) return prefixed(prefix, "capacity outside 0..65536");
-    return nullptr;
-}
-
-const char *check_images(const char *prefix, int batch, int width, int height) {
-    if (const char *bad = check_frame(prefix, batch, width, height, 8192)) return bad;
-    if (width > 8192) return prefixed(prefix, "width > 8192");
     return nullptr;
 }
 

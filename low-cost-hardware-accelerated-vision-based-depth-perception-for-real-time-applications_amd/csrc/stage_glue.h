@@ -1,4 +1,4 @@
-// What the stage entries of groups (D) to (Z) of include/stereo_vision_hip.h share on the host (top_view.cpp ... flow.cpp): the
+// What the stage entries of groups (D) to (AA) of include/stereo_vision_hip.h share on the host (top_view.cpp ... warp.cpp): the
 // refusal of a bad call, the checks that several groups state in the same words, and the set-up of sv::ReprojectArgs.  Host code only:
 // no .hip file includes it.
 #pragma once
@@ -38,6 +38,23 @@ inline const char *check_frame(const char *prefix, int batch, int width, int hei
     if (width < 1 || height < 1) return prefixed(prefix, "width or height < 1");
     if (max_height > 0 && height > max_height) return prefixed(prefix, "height > " + std::to_string(max_height));
     if ((int64_t)width * height >= ((int64_t)1 << 31)) return prefixed(prefix, "width * height >= 2^31");
+    return nullptr;
+}
+
+// NULL for a batch of images that groups (Z) and (AA) can index - at most 8192 x 8192 -, else what is wrong with it.
+inline const char *check_images(const char *prefix, int batch, int width, int height) {
+    if (const char *bad = check_frame(prefix, batch, width, height, 8192)) return bad;
+    if (width > 8192) return prefixed(prefix, "width > 8192");
+    return nullptr;
+}
+
+// NULL for the camera words the specs of groups (Z) and (AA) begin with - f, cx, cy, b16, fb, fb16 -, else what is wrong with them.
+template <class Spec>
+inline const char *check_camera_words(const char *prefix, const Spec *s) {
+    const double w[6] = {s->f, s->cx, s->cy, s->b16, s->fb, s->fb16};
+    for (double v : w)
+        if (!isfinite(v)) return prefixed(prefix, "a word of the camera is not finite");
+    if (!(s->f > 0.0) || !(s->b16 > 0.0) || !(s->fb > 0.0) || !(s->fb16 > 0.0)) return prefixed(prefix, "f, b16, fb and fb16 must be > 0");
     return nullptr;
 }
 

@@ -567,6 +567,12 @@ class SvFlowSpec(ctypes.Structure):
                 ("capacity", ctypes.c_int32), ("reserved", ctypes.c_int32 * 9)]
 
 
+class SvWarpSpec(ctypes.Structure):
+    """sv_warp_spec of include/stereo_vision_hip.h."""
+    _fields_ = [("f", ctypes.c_double), ("cx", ctypes.c_double), ("cy", ctypes.c_double), ("b16", ctypes.c_double), ("fb", ctypes.c_double), ("fb16", ctypes.c_double),
+                ("e_max", ctypes.c_int32), ("tol_q", ctypes.c_int32), ("rel_q", ctypes.c_int32), ("mode", ctypes.c_int32), ("reserved", ctypes.c_int32 * 12)]
+
+
 def _signatures():
     """The table below: per stage group of the C API, (D) to (S), its functions and per function (restype, argtypes), parameter by
     parameter as include/stereo_vision_hip.h declares them - tests/test_stage_signatures.py holds the two against each other."""
@@ -692,6 +698,10 @@ def _signatures():
             "sv_flow_match_device": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, P(SvFlowSpec), vp, vp, vp, vp, sz, vp]),
             "sv_flow_pose_sums_workspace": (ci, [ci, ci, P(sz)]),
             "sv_flow_pose_sums_device": (ci, [vp, vp, vp, ci, ci, P(SvFlowSpec), ci, ci, vp, vp, sz, vp]),
+        },
+        "warp": {  # (AA)
+            "sv_disparity_warp_workspace": (ci, [ci, ci, ci, P(sz)]),
+            "sv_disparity_warp_device": (ci, [vp, vp, vp, ci, ci, ci, P(SvWarpSpec), vp, vp, vp, vp, vp, vp, sz, vp]),
         },
     }
 
@@ -2983,6 +2993,80 @@ def flow_egomotion(matches, counts, camera, start=None, gates=None, dgate=2.0, i
     got = flow_loop(sums_of, start, FLOW_GATES if gates is None else gates, dgate, iterations, eps, min_inliers)
     res.poses, res.ok, res.rounds, res.inliers, res.rms_px = got["poses"], got["ok"], got["rounds"], got["inliers"], got["rms_px"]
     return res
+
+
+def warp_lib():
+    """The library with the signatures of group (AA) declared."""
+    return _bind("warp")
+
+
+class WarpResult(_Result):
+    """What disparity_warp returns, tensors on the inputs' device (numpy arrays for CPU inputs): expected int32 [B,H,W], source int32
+    [B,H,W], counts int32 [B,8] (stereo_vision.sv.WARP_COUNTS) and, with a d_cur, label uint8 [B,H,W] (stereo_vision.sv.VOXEL_RENDER_LABELS)
+    and out float32 [B,H,W] - None without one."""
+    __slots__ = ("expected", "source", "label", "out", "counts")
+
+
+def warp_spec(camera, **words):
+    """-> SvWarpSpec from a camera dict (stereo_vision.sv.voxel_render_camera's) and disparity_warp's words (stereo_vision.sv.warp_words
+    checks them: ValueError)."""
+    from .stereo_vision.sv import flow_camera, warp_words
+    cam, w = flow_camera(camera), warp_words(**words)
+    return SvWarpSpec(cam["f"], cam["cx"], cam["cy"], cam["b16"], cam["fb"], cam["fb16"], w["e_max"], w["tol_q"], w["rel_q"], w["mode"])
+
+
+def disparity_warp(d_prev, d_cur, camera, poses, e_max=1, tol_q=16, rel_q=0, mode="fill", out=None, workspace=None):
+    """The disparity maps of frames k - 1 warped into frames k under the motions `poses` and compared with d_cur - the definition of
+    stereo_vision.sv.disparity_warp on the GPU, bit for bit (sv_disparity_warp_device: the keys cleared, a lane per source pixel with one
+    64-bit integer atomicMax per covered pixel, a lane per target pixel; no float atomics).  d_prev float32 [B,H,W]; d_cur the same or
+    None; camera: voxel_render_camera's dict; poses float64 [B,12] (numpy, or a tensor on the device): previous camera to current camera.
+    out: a WarpResult of an earlier call of the same shape to write into; workspace: an int64 tensor of B H W words to use (None: torch's
+    allocator).  -> WarpResult; for CUDA tensors enqueued on torch's current stream, nothing is read back.  CPU tensors (or numpy
+    arrays) run the numpy form and give numpy arrays."""
+    import torch
+    spec = warp_spec(camera, e_max=e_max, tol_q=tol_q, rel_q=rel_q, mode=mode)
+    if not (isinstance(d_prev, torch.Tensor) and d_prev.is_cuda):
+        from .stereo_vision.sv import disparity_warp as on_host
+        as_np = lambda t: t.cpu().numpy() if isinstance(t, torch.Tensor) else t
+        return WarpResult(**on_host(as_np(d_prev), None if d_cur is None else as_np(d_cur), camera, as_np(poses), e_max, tol_q, rel_q, mode))
+    if d_prev.dtype != torch.float32 or d_prev.dim() != 3:
+        raise ValueError("d_prev must be a float32 tensor [B,H,W]")
+    dev, shape = d_prev.device, tuple(d_prev.shape)
+    B, H, W = shape
+    if B > 65535 or not (1 <= H <= 8192 and 1 <= W <= 8192):
+        raise ValueError("at most 65535 frames of at most 8192 x 8192, got %s" % (shape,))
+    if d_cur is not None and not (isinstance(d_cur, torch.Tensor) and d_cur.device == dev and d_cur.dtype == torch.float32 and tuple(d_cur.shape) == shape):
+        raise ValueError("d_cur must be None or a float32 tensor %s on %s" % (list(shape), dev))
+    d_prev = d_prev.contiguous()
+    d_cur = None if d_cur is None else d_cur.contiguous()
+    p = poses if isinstance(poses, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(poses, np.float64)).to(dev)
+    if p.device != dev or p.dtype != torch.float64 or tuple(p.shape) != (B, 12):
+        raise ValueError("poses must be float64 [%d,12]" % B)
+    p = p.contiguous()
+    res = out
+    if res is None:
+        res = WarpResult(expected=torch.empty(shape, dtype=torch.int32, device=dev), source=torch.empty(shape, dtype=torch.int32, device=dev),
+                         counts=torch.empty((B, 8), dtype=torch.int32, device=dev))
+        if d_cur is not None:
+            res.label, res.out = torch.empty(shape, dtype=torch.uint8, device=dev), torch.empty(shape, dtype=torch.float32, device=dev)
+    for t, name, dtype, want in ((res.expected, "expected", torch.int32, shape), (res.source, "source", torch.int32, shape), (res.counts, "counts", torch.int32, (B, 8)),
+                                 (res.label, "label", torch.uint8, shape), (res.out, "out", torch.float32, shape)):
+        if t is None and d_cur is None and name in ("label", "out"):
+            continue
+        if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dtype and tuple(t.shape) == want and t.is_contiguous()):
+            raise ValueError("out.%s must be a contiguous %s tensor %s on %s" % (name, str(dtype).replace("torch.", ""), list(want), dev))
+    L = warp_lib()
+    need = ctypes.c_size_t()
+    _check(L.sv_disparity_warp_workspace(W, H, B, ctypes.byref(need)), "sv_disparity_warp_workspace")
+    if B == 0:  # nothing to enqueue
+        return res
+    ws = workspace if workspace is not None else torch.empty((max(need.value // 8, 1),), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.sv_disparity_warp_device(d_prev.data_ptr(), None if d_cur is None else d_cur.data_ptr(), p.data_ptr(), B, W, H, ctypes.byref(spec), res.expected.data_ptr(),
+                                        res.source.data_ptr(), None if d_cur is None else res.label.data_ptr(), None if d_cur is None else res.out.data_ptr(),
+                                        res.counts.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(), torch.cuda.current_stream(dev).cuda_stream)
+    _check(rc, "sv_disparity_warp_device")
+    return res  # ws goes back to torch's allocator, which hands it out again on this stream only: behind the kernels
 
 
 def host_support_filter(params, dcan, width, height, threads=0, lattice=False):

@@ -40,7 +40,7 @@ import ctypes
 
 import numpy as np
 
-from .engine import flow_egomotion, flow_match
+from .engine import disparity_warp, flow_egomotion, flow_match
 from .engine import (SvParams, StereoEngine, StereoError, box_positions_from_disparity, box_spec, cloud_spec, compact_cloud_from_disparity,
                      ground_from_disparity, ground_spec, lib, occupancy_from_disparity, occupancy_fuse, occupancy_match, occupancy_clearance, clearance_paths, cost_cells, cost_routes, frontier_cells, frontier_clusters, occupancy_cost_to_goal, occupancy_view, occupancy_spec, pinned_array, reproject, split_clouds, stixel_spec, stixels_from_disparity,
                      top_view_from_disparity, top_view_spec, split_voxel_clouds, voxel_cloud_from_disparity, voxel_map_align, voxel_map_carry, voxel_map_clear, voxel_map_insert, voxel_map_match, voxel_map_new,
@@ -340,6 +340,20 @@ class StereoRig:
         res = flow_match(gl[:-1], gl[1:], d1[:-1], d1[1:], camera, guess, step, r, wx, wy, ratio, max_cost, capacity)
         return {k: getattr(res, k).cpu().numpy() for k in ("matches", "cost", "counts")} if from_numpy else res
 
+    def _odometry_pairs(self, gl, d1, camera, guess, spec):
+        """stereo_vision.sv.flow_odometry over the B - 1 pairs of a batch whose front end and engine have run, with the device's calls."""
+        s = _sv.flow_odometry_spec(**spec)
+        words = {k: s[k] for k in ("step", "r", "ratio", "max_cost", "capacity")}
+
+        def match_of(lo, hi, g, wx, wy):
+            return flow_match(gl[lo:hi], gl[lo + 1:hi + 1], d1[lo:hi], d1[lo + 1:hi + 1], camera, g, wx=wx, wy=wy, **words)
+
+        def ego_of(got, at):
+            e = flow_egomotion(got.matches, got.counts, camera, at, s["gates"], s["dgate"], s["iterations"], s["eps"], s["min_inliers"])
+            return {k: getattr(e, k) for k in ("poses", "ok", "rounds", "inliers")}
+
+        return _sv.flow_odometry(match_of, ego_of, int(gl.shape[0]) - 1, guess, **spec)
+
     def odometry(self, left, right, pixel_format="bgr", start=None, transform=None, guess="velocity", **spec):
         """Stereo visual odometry of a batch of B consecutive pairs (include/stereo_vision_hip.h (Z), stereo_vision.sv.flow_odometry): front
         end and engine once for the batch; frame k matched against frame k - 1 and the camera's motion between them fitted by a gated
@@ -355,17 +369,8 @@ class StereoRig:
         s = _sv.flow_odometry_spec(**spec)
         XR, XT = self._transform(transform)
         gl, d1, camera, from_numpy = self._flow_inputs(left, right, pixel_format)
-        B = int(gl.shape[0])
-        words = {k: s[k] for k in ("step", "r", "ratio", "max_cost", "capacity")}
+        got = self._odometry_pairs(gl, d1, camera, guess, spec)
 
-        def match_of(lo, hi, g, wx, wy):
-            return flow_match(gl[lo:hi], gl[lo + 1:hi + 1], d1[lo:hi], d1[lo + 1:hi + 1], camera, g, wx=wx, wy=wy, **words)
-
-        def ego_of(got, at):
-            e = flow_egomotion(got.matches, got.counts, camera, at, s["gates"], s["dgate"], s["iterations"], s["eps"], s["min_inliers"])
-            return {k: getattr(e, k) for k in ("poses", "ok", "rounds", "inliers")}
-
-        got = _sv.flow_odometry(match_of, ego_of, B - 1, guess, **spec)
         calls = got["calls"]
         if calls:
             m = {k: torch.cat([getattr(c, k) for c in calls]) for k in ("matches", "cost", "counts")}
@@ -376,6 +381,42 @@ class StereoRig:
         if from_numpy:
             m = {k: v.cpu().numpy() for k, v in m.items()}
         return {"poses": _sv.flow_chain(got["rel"], start, XR, XT, got["ok"]), "rel": got["rel"], "ok": got["ok"], "inliers": got["inliers"], "matches": m}
+
+    def temporal(self, left, right, pixel_format="bgr", poses=None, mode="fill", **words):
+        """The disparity maps of a batch of B consecutive pairs made consistent with the frame before (include/stereo_vision_hip.h (AA),
+        stereo_vision.sv.disparity_warp): front end and engine once for the batch, then the map of every frame k - 1 warped into frame k
+        under the motion between them and compared with what frame k measured, for k = 1 .. B - 1, in one call.  poses: float64
+        [B-1,12], previous camera to current camera - a row with a word that is not finite: a pair without a motion, not ok -, or None -
+        odometry() with its defaults over the same maps.  mode "fill", "confirm"
+        or "reject"; words: e_max, tol_q, rel_q.  -> {"d1": float32 [B,H,W], the maps with frames 1 .. B - 1 replaced by out; "label"
+        uint8, "expected" and "source" int32 [B-1,H,W]; "counts" int32 [B-1,8]; "rel" float64 [B-1,12]; "ok" bool [B-1]} - tensors for
+        CUDA input (rel and ok numpy), numpy arrays for numpy input.  A pair whose odometry fit was not ok keeps its measured map, and
+        its labels are those of an empty frame before it: 0 and 1."""
+        _sv.warp_words(mode=mode, **words)
+        gl, d1, camera, from_numpy = self._flow_inputs(left, right, pixel_format)
+        B = int(gl.shape[0])
+        if B < 2:
+            raise ValueError("temporal needs at least two consecutive pairs, got %d" % B)
+        if poses is None:
+            got = self._odometry_pairs(gl, d1, camera, "velocity", {})
+            rel, ok = got["rel"], got["ok"]
+        else:
+            rel = np.array(poses, np.float64)
+            if rel.shape != (B - 1, 12):
+                raise ValueError("poses must be None or motions [%d,12], got shape %s" % (B - 1, rel.shape))
+            ok = np.isfinite(rel).all(1)  # a motion with a word that is not finite stands for a pair without one
+        used = rel.copy()
+        used[~ok] = np.nan  # no source is kept under such a motion
+        res = disparity_warp(d1[:-1], d1[1:], camera, used, mode=mode, **words)
+        new = d1.clone()
+        new[1:] = res.out
+        for k in np.flatnonzero(~ok):
+            new[k + 1] = d1[k + 1]
+        out = {"d1": new, "label": res.label, "expected": res.expected, "source": res.source, "counts": res.counts}
+        if from_numpy:
+            out = {k: v.cpu().numpy() for k, v in out.items()}
+        out["rel"], out["ok"] = rel, ok
+        return out
 
     def ground(self, left, right, pixel_format="bgr", transform=None, **spec):
         """Where the ground is, what stands on it and how far one can go in each image column, for B pairs: front end, engine, then

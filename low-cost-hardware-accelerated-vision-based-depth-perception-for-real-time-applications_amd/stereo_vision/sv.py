@@ -2913,6 +2913,209 @@ def flow_pose_lines(poses):
     return ["%r %r %r" % (float(q[9]), float(q[10]), float(np.arctan2(q[3], q[0]))) for q in p]
 
 
+WARP_E_MAX = 4            # a source covers (e + 1)^2 target pixels, e <= e_max <= 4
+WARP_PD_MAX = 2 ** 20     # a predicted disparity in 1/16 px that is kept: 1 .. 2^20
+WARP_TOL_MAX = 2 ** 20    # tol_q at most, 1/16 px
+WARP_REL_MAX = 256        # rel_q at most: t = tol_q + ((rel_q ex) >> 8)
+WARP_BATCH_MAX = 65535
+WARP_MODES = {"fill": 0, "confirm": 1, "reject": 2}
+WARP_COUNTS = ("kept", "covered") + VOXEL_RENDER_LABELS  # the eight words of counts
+
+
+def warp_words(e_max=1, tol_q=16, rel_q=0, mode="fill"):
+    """The words of a disparity_warp call as a dict of ints, after the checks the C entry makes (ValueError): e_max in 0 .. 4, tol_q in
+    0 .. 2^20 (1/16 px), rel_q in 0 .. 256, mode "fill", "confirm" or "reject" (or 0, 1, 2)."""
+    w = {}
+    for k, v, lo, hi in (("e_max", e_max, 0, WARP_E_MAX), ("tol_q", tol_q, 0, WARP_TOL_MAX), ("rel_q", rel_q, 0, WARP_REL_MAX)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ValueError("%s must be an integer in %d .. %d, got %r" % (k, lo, hi, v))
+        w[k] = int(v)
+    if isinstance(mode, str) and mode in WARP_MODES:
+        w["mode"] = WARP_MODES[mode]
+    elif not isinstance(mode, (bool, str)) and isinstance(mode, (int, np.integer)) and 0 <= mode <= 2:
+        w["mode"] = int(mode)
+    else:
+        raise ValueError("mode must be one of %s, got %r" % (sorted(WARP_MODES, key=WARP_MODES.get), mode))
+    return w
+
+
+def _warp_setup(d_prev, d_cur, poses):
+    d_prev = np.asarray(d_prev)
+    if d_prev.dtype != np.float32 or d_prev.ndim != 3:
+        raise ValueError("d_prev must be float32 [B,H,W], got %s %s" % (d_prev.dtype, d_prev.shape))
+    B, H, W = d_prev.shape
+    if B > WARP_BATCH_MAX or not (1 <= W <= 8192 and 1 <= H <= 8192):
+        raise ValueError("at most 65535 frames of at most 8192 x 8192, got %s" % (d_prev.shape,))
+    if d_cur is not None:
+        d_cur = np.asarray(d_cur)
+        if d_cur.dtype != np.float32 or d_cur.shape != d_prev.shape:
+            raise ValueError("d_cur must be float32 %s or None, got %s %s" % (d_prev.shape, d_cur.dtype, d_cur.shape))
+    poses = np.asarray(poses, np.float64)
+    if poses.shape != (B, 12):
+        raise ValueError("poses must be float64 [%d,12], got %s" % (B, poses.shape))
+    return d_prev, d_cur, poses
+
+
+def _warp_compare(d_cur, ex, w):
+    """label uint8 and out float32 of one frame from its d_cur float32 [H,W] and expected int64 [H,W]."""
+    mq = _flow_dq(d_cur)
+    t = w["tol_q"] + ((w["rel_q"] * ex) >> 8)
+    label = np.where(mq == 0, np.where(ex > 0, 2, 0), np.where(ex == 0, 1, np.where(mq > ex + t, 4, np.where(mq < ex - t, 5, 3)))).astype(np.uint8)
+    bits = np.ascontiguousarray(d_cur).view(np.uint32)
+    none = np.uint32(0xBF800000)  # -1.0f
+    if w["mode"] == 0:
+        fill = (ex.astype(np.float32) / np.float32(16.0)).view(np.uint32)  # ex <= 2^20: exact
+        o = np.where(mq > 0, bits, np.where(ex > 0, fill, none))
+    elif w["mode"] == 1:
+        o = np.where(label == 3, bits, none)
+    else:
+        o = np.where((label == 1) | (label == 3), bits, none)
+    return label, o.astype(np.uint32).view(np.float32)
+
+
+def disparity_warp(d_prev, d_cur, camera, poses, e_max=1, tol_q=16, rel_q=0, mode="fill"):
+    """The disparity maps of frames k - 1 warped into frames k and compared with what frames k measured: the definition of
+    include/stereo_vision_hip.h (AA) in numpy.  d_prev float32 [B,H,W]; d_cur float32 [B,H,W] or None; camera: voxel_render_camera's dict
+    (flow_camera reads it); poses float64 [B,12]: previous camera to current camera, in flow_egomotion's layout.
+      sources     every pixel (u0, v0) with d0q = _flow_dq(d_prev) >= 1, its index src = v0 W + u0.
+      moved       X0 = _flow_point(...), Xc = _flow_move(pose, ...): doubles, one operation at a time.
+      kept        z = Xc.z > FLOW_Z_MIN (false for NaN); pd = floor(16 (fb / z) + 0.5) in 1 .. 2^20; tu = floor(((f Xc.x) / z + cx) + 0.5), tv
+                  = floor(((f Xc.y) / z + cy) + 0.5) with |tu|, |tv| <= 2^20 - flow_match's centre.
+      footprint   e = min(e_max, (pd + d0q - 1) // d0q - 1): a point that came closer covers (tu + dx, tv + dy), dx, dy in 0 .. e, inside
+                  the image.
+      winner      per target pixel the largest pd, among equals the smallest src.
+    -> {"expected": int32 [B,H,W], the winner's pd or 0; "source": int32 [B,H,W], the winner's src or -1; "counts": int32 [B,8] =
+    WARP_COUNTS: sources kept, covers inside the image (once per source), pixels per label; "label", "out": None without a d_cur}.  With
+    d_cur: mq = _flow_dq(d_cur), ex = expected, t = tol_q + ((rel_q ex) >> 8); label uint8 [B,H,W] in VOXEL_RENDER_LABELS' order: 0
+    neither, 1 measured only, 2 expected only, 3 agree |mq - ex| <= t, 4 nearer mq > ex + t, 5 farther mq < ex - t; out float32 [B,H,W]: mode
+    "fill" - d_cur's bits where measured, else float32(ex) / 16 where expected, else -1; "confirm" - d_cur's bits where the label is 3,
+    else -1; "reject" - d_cur's bits where the label is 1 or 3, else -1.  Without d_cur the counts take the labels as 0 and 2."""
+    w = warp_words(e_max, tol_q, rel_q, mode)
+    cam = flow_camera(camera)
+    d_prev, d_cur, poses = _warp_setup(d_prev, d_cur, poses)
+    B, H, W = d_prev.shape
+    expected, source, counts = np.zeros((B, H, W), np.int32), np.full((B, H, W), -1, np.int32), np.zeros((B, 8), np.int32)
+    label = out = None
+    if d_cur is not None:
+        label, out = np.zeros((B, H, W), np.uint8), np.zeros((B, H, W), np.float32)
+    for b in range(B):
+        d0 = _flow_dq(d_prev[b]).ravel()
+        src = np.flatnonzero(d0 > 0)
+        q = d0[src]
+        x, y, z = _flow_point(cam, src % W, src // W, q)
+        X = _flow_move(poses[b], x, y, z)
+        with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+            keep = X[2] > FLOW_Z_MIN  # false for NaN
+            zs = np.where(keep, X[2], 1.0)
+            pd = np.floor(16.0 * (cam["fb"] / zs) + 0.5)
+            tu, tv = np.floor(((cam["f"] * X[0]) / zs + cam["cx"]) + 0.5), np.floor(((cam["f"] * X[1]) / zs + cam["cy"]) + 0.5)
+            keep &= (pd >= 1) & (pd <= WARP_PD_MAX) & (np.abs(tu) <= FLOW_CENTRE_MAX) & (np.abs(tv) <= FLOW_CENTRE_MAX)  # false for NaN
+        src, q, pd, tu, tv = src[keep], q[keep], pd[keep].astype(np.int64), tu[keep].astype(np.int64), tv[keep].astype(np.int64)
+        e = np.minimum(w["e_max"], (pd + q - 1) // q - 1)
+        key = (pd << 32) | (0xFFFFFFFF - src)
+        keys = np.zeros(H * W, np.int64)
+        covered = 0
+        for dy in range(w["e_max"] + 1):
+            for dx in range(w["e_max"] + 1):
+                tx, ty = tu + dx, tv + dy
+                hit = (e >= dx) & (e >= dy) & (tx >= 0) & (tx < W) & (ty >= 0) & (ty < H)
+                np.maximum.at(keys, ty[hit] * W + tx[hit], key[hit])
+                covered += int(hit.sum())
+        ex = (keys >> 32).reshape(H, W)
+        expected[b] = ex
+        source[b] = np.where(keys > 0, 0xFFFFFFFF - (keys & 0xFFFFFFFF), -1).reshape(H, W)
+        if d_cur is not None:
+            label[b], out[b] = _warp_compare(d_cur[b], ex, w)
+            lab = label[b]
+        else:
+            lab = np.where(ex > 0, 2, 0)
+        counts[b] = [len(src), covered] + [int(v) for v in np.bincount(lab.ravel(), minlength=6)]
+    return {"expected": expected, "source": source, "label": label, "out": out, "counts": counts}
+
+
+def disparity_warp_brute(d_prev, d_cur, camera, poses, e_max=1, tol_q=16, rel_q=0, mode="fill"):
+    """disparity_warp pixel by pixel in Python floats and ints: what the tests hold the numpy form against."""
+    import math
+    import struct
+    w = warp_words(e_max, tol_q, rel_q, mode)
+    cam = flow_camera(camera)
+    d_prev, d_cur, poses = _warp_setup(d_prev, d_cur, poses)
+    B, H, W = d_prev.shape
+    f, cx, cy, b16, fb, fb16 = (float(cam[k]) for k in ("f", "cx", "cy", "b16", "fb", "fb16"))
+
+    def dq(d):
+        d = float(d)
+        if not (d > 0.0) or not math.isfinite(d):
+            return 0
+        v = math.floor(d * 16.0 + 0.5)
+        return v if 1 <= v <= FLOW_DQ_MAX else 0
+
+    def rounded(v):  # floor(v + 0.5) as an int, None where v is not finite
+        v = v + 0.5
+        return math.floor(v) if math.isfinite(v) else None
+
+    expected, source, counts = np.zeros((B, H, W), np.int32), np.full((B, H, W), -1, np.int32), np.zeros((B, 8), np.int32)
+    label = out = None
+    if d_cur is not None:
+        label, out = np.zeros((B, H, W), np.uint8), np.zeros((B, H, W), np.float32)
+    for b in range(B):
+        P = [float(v) for v in poses[b]]
+        best = {}
+        kept = covered = 0
+        for v0 in range(H):
+            for u0 in range(W):
+                d0q = dq(d_prev[b, v0, u0])
+                if d0q < 1:
+                    continue
+                d = float(d0q)
+                x0, y0, z0 = ((float(u0) - cx) * b16) / d, ((float(v0) - cy) * b16) / d, fb16 / d
+                x, y, z = (((P[3 * k] * x0 + P[3 * k + 1] * y0) + P[3 * k + 2] * z0) + P[9 + k] for k in range(3))
+                if not z > FLOW_Z_MIN:
+                    continue
+                pd, tu, tv = rounded(16.0 * (fb / z)), rounded((f * x) / z + cx), rounded((f * y) / z + cy)
+                if pd is None or tu is None or tv is None or not 1 <= pd <= WARP_PD_MAX or abs(tu) > 2 ** 20 or abs(tv) > 2 ** 20:
+                    continue
+                kept += 1
+                e = min(w["e_max"], (pd + d0q - 1) // d0q - 1)
+                src = v0 * W + u0
+                for dy in range(e + 1):
+                    for dx in range(e + 1):
+                        tx, ty = tu + dx, tv + dy
+                        if 0 <= tx < W and 0 <= ty < H:
+                            covered += 1
+                            old = best.get((ty, tx))
+                            if old is None or pd > old[0] or (pd == old[0] and src < old[1]):
+                                best[(ty, tx)] = (pd, src)
+        hist = [0] * 6
+        for v in range(H):
+            for u in range(W):
+                ex, src = best.get((v, u), (0, -1))
+                expected[b, v, u], source[b, v, u] = ex, src
+                if d_cur is None:
+                    hist[2 if ex > 0 else 0] += 1
+                    continue
+                mq = dq(d_cur[b, v, u])
+                t = w["tol_q"] + ((w["rel_q"] * ex) >> 8)
+                if mq == 0:
+                    lab = 2 if ex > 0 else 0
+                elif ex == 0:
+                    lab = 1
+                else:
+                    lab = 4 if mq > ex + t else 5 if mq < ex - t else 3
+                hist[lab] += 1
+                label[b, v, u] = lab
+                own = d_cur[b, v, u:u + 1].view(np.uint32)[0]
+                if w["mode"] == 0:
+                    bits = own if mq > 0 else struct.unpack("<I", struct.pack("<f", ex / 16.0))[0] if ex > 0 else 0xBF800000
+                elif w["mode"] == 1:
+                    bits = own if lab == 3 else 0xBF800000
+                else:
+                    bits = own if lab in (1, 3) else 0xBF800000
+                out[b, v, u:u + 1].view(np.uint32)[0] = bits
+        counts[b] = [kept, covered] + hist
+    return {"expected": expected, "source": source, "label": label, "out": out, "counts": counts}
+
+
 GROUND_BINS_MIN, GROUND_BINS_MAX = 8, 4096
 GROUND_VH_MIN, GROUND_TOL_MAX, GROUND_G_TOL_MAX, GROUND_HEIGHT_MAX = -32768, 16, 4096, 32768
 GROUND_LABELS = {"invalid": 0, "ground": 1, "obstacle": 2, "below": 3}
@@ -4516,6 +4719,12 @@ def main(argv=None):
                              "The chained poses are written to FILE, one line 'x y yaw' per frame as --poses reads them, frame 0 at the "
                              "origin, and the motions to <FILE>.rel.txt, twelve words per pair of frames: the rotation row by row, then "
                              "the translation, previous camera to current camera.  Without --poses the run takes FILE as its --poses")
+    parser.add_argument("--temporal", type=str, default="", metavar="DIR[,TOL_PX[,MODE]]",
+                        help="with --batch and --odometry: every frame's disparity map compared with the map of the frame before it, warped "
+                             "under the fitted motion (StereoRig.temporal, on the odometry's batches: the front end and engine run once "
+                             "more for it) at TOL_PX pixels (default 1), MODE fill (default), confirm or reject; writes per frame "
+                             "DIR/NNNNNN.change.png (none, measured only, expected only, agree, nearer, farther) and DIR/NNNNNN.temporal.png "
+                             "(the filtered map as the 8-bit disparity image) and prints the pixels per label of each batch")
     parser.add_argument("--match", type=str, default="", metavar="DX,DY,DYAW[,NX,NY,NYAW]",
                         help="with --occupancy-map and --poses: take the poses as guesses - frame 0 is fused where its line says; every later "
                              "frame is first matched against the map built so far over a window of +-DX, +-DY metres and +-DYAW radians "
@@ -4546,6 +4755,14 @@ def main(argv=None):
         parser.error("--odometry needs --batch")
     if args.odometry and not args.poses and (args.occupancy_map or args.voxel_map):
         args.poses = args.odometry  # written below, before anything reads it
+    args.temporal_spec = None
+    if args.temporal:
+        if not args.batch or not args.odometry:
+            parser.error("--temporal needs --batch and --odometry")
+        try:
+            args.temporal_spec = cli_temporal_spec(args.temporal)
+        except ValueError as e:
+            parser.error("--temporal: %s" % e)
     args.match_window = None
     args.voxel_match_window = None
     args.voxel_carve_spec = None
@@ -4696,6 +4913,8 @@ def main(argv=None):
         os.makedirs(args.occupancy, exist_ok=True)
     if args.voxel_render_spec is not None:
         os.makedirs(args.voxel_render_spec[0], exist_ok=True)
+    if args.temporal_spec is not None:
+        os.makedirs(args.temporal_spec[0], exist_ok=True)
     if args.odometry:
         _run_odometry(args, ldir, rdir, files)
     args.pose_rows = None
@@ -4898,6 +5117,45 @@ def cli_voxel_render_text(counts):
     return ", ".join("%s %d" % (k, int(v)) for k, v in zip(VOXEL_RENDER_LABELS, counts))
 
 
+def cli_temporal_spec(text):
+    """--temporal DIR[,TOL_PX[,MODE]] -> (DIR, tol_q in 1/16 px, mode); ValueError for an empty DIR, a TOL_PX outside 0 .. 65536, a MODE
+    that is not fill, confirm or reject, or more than three parts."""
+    parts = text.split(",")
+    if not parts[0] or len(parts) > 3:
+        raise ValueError("DIR[,TOL_PX[,MODE]], got %r" % text)
+    try:
+        tol = float(parts[1]) if len(parts) > 1 else 1.0
+    except ValueError:
+        raise ValueError("TOL_PX must be a number, got %r" % parts[1])
+    if not (np.isfinite(tol) and 0.0 <= tol * 16.0 <= WARP_TOL_MAX):
+        raise ValueError("TOL_PX in 0 .. 65536, got %r" % tol)
+    mode = parts[2] if len(parts) > 2 else "fill"
+    return parts[0], warp_words(tol_q=int(np.floor(tol * 16.0 + 0.5)), mode=mode)["tol_q"], mode
+
+
+def cli_temporal_text(counts):
+    """The label counts of a batch (int [pairs,8], WARP_COUNTS) as the CLI prints them: the sums over its pairs."""
+    total = np.asarray(counts, np.int64).reshape(-1, 8).sum(0)
+    return ", ".join("%s %d" % (k, int(v)) for k, v in zip(WARP_COUNTS, total))
+
+
+def _write_temporal(args, rig, left, right, rel, ok, first, frame0):
+    """--temporal for one batch of --odometry: frames frame0 .. of the folder, whose motions `rel` the odometry has fitted (`ok`)."""
+    from ..engine import disparity_to_u8
+    folder, tol_q, mode = args.temporal_spec
+    motions = np.array(rel, np.float64).reshape(-1, 12)
+    motions[~np.asarray(ok, bool)] = np.nan  # a pair without a motion keeps its measured map
+    got = rig.temporal(left, right, pixel_format="bgr", poses=motions, mode=mode, tol_q=tol_q)
+    img = disparity_to_u8(got["d1"]).cpu().numpy()
+    lab = got["label"].cpu().numpy()
+    d0 = got["d1"][0].cpu().numpy()
+    for k in range(0 if first else 1, img.shape[0]):
+        change = lab[k - 1] if k > 0 else (_flow_dq(d0) > 0).astype(np.uint8)  # the folder's first frame: nothing is expected
+        _write_png(os.path.join(folder, "%06d.change.png" % (frame0 + k)), VOXEL_RENDER_PNG[change])
+        _write_png(os.path.join(folder, "%06d.temporal.png" % (frame0 + k)), img[k])
+    print("temporal: frames %d .. %d: %s" % (frame0 + 1, frame0 + img.shape[0] - 1, cli_temporal_text(got["counts"].cpu().numpy())))
+
+
 def _write_png(path, u8):
     from PIL import Image
     Image.fromarray(u8).save(path)
@@ -4921,6 +5179,8 @@ def _run_odometry(args, ldir, rdir, files):
             got = rig.odometry(left, right, pixel_format="bgr", first=rel[-1] if rel and ok[-1] else None)
             rel.extend(got["rel"])
             ok.extend(got["ok"])
+            if args.temporal_spec is not None and len(names) > 1:
+                _write_temporal(args, rig, left, right, got["rel"], got["ok"], i == 0, max(i - 1, 0))
     finally:
         rig.close()
     poses = flow_chain(np.array(rel).reshape(-1, 12), None, CAMERA_TO_VEHICLE, None, np.array(ok, bool))
