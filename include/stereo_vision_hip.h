@@ -107,6 +107,11 @@
  *      filled from the frame before, or only what it confirms, or all but what it contradicts.  stereo_vision.sv.disparity_warp states
  *      the definition in numpy.
  *
+ *  (AB) Behind (Z), (H) and (E): object links (sv_object_links_*) - the temporal matches of (Z1) sorted into the boxes of frames k - 1 and
+ *      k, a vote per pair of boxes, a link per previous box, and each linked box's matches reduced to the integers of its own motion, the
+ *      motion that remains once the camera's is taken out.  stereo_vision.sv.object_links states the definition in numpy; object_motion
+ *      and ObjectTracks are the metres and the bookkeeping of ids, velocities and predictions on the host.
+ *
  * All sv_* functions return SV_OK (0) or a negative sv_status; sv_last_error() gives the text.
  * Nothing in this library calls exit().
  */
@@ -1892,6 +1897,62 @@ int sv_disparity_warp_workspace(int width, int height, int batch, size_t *bytes)
 int sv_disparity_warp_device(const float *d_prev, const float *d_cur, const double *poses, int batch, int width, int height, const sv_warp_spec *spec,
                              int32_t *expected, int32_t *source, uint8_t *label, float *out, int32_t *counts, void *workspace, size_t workspace_bytes,
                              void *stream);
+
+/* ---- (AB) object links: the temporal matches of (Z1) + the boxes of both frames -> votes, a link per previous box, the sums of its motion ---- */
+
+/* The camera as in (Z) and the words of the call: the maps' width and height in 1 .. 8192; max_boxes in 0 .. 64, the rows of every box
+ * array per frame - a match's membership in the boxes of one frame is one 64-bit word -; band_q in 0 .. 2^20 (1/16 px); min_votes >= 1;
+ * share in 0 .. 256; gate_m in 0 .. 2^20 (1/1024 m; 0: no gate).  reserved: 0. */
+typedef struct {
+    double f, cx, cy, b16, fb, fb16;
+    int32_t width, height, max_boxes, band_q, min_votes, share, gate_m;
+    int32_t reserved[9];
+} sv_track_spec;
+
+/* matches int32 [batch][capacity][6] = (u0, v0, d0q, u1, v1, d1q) and counts int32 [batch]: (Z1)'s, under (Z2)'s rules - capacity <= 65536, a
+ * count of -1 or 0 gives nothing, a count above the capacity counts as the capacity, a row with d0q outside 1 .. 2^20 is skipped.  poses
+ * double [batch][12]: previous camera to current camera, (Z)'s layout.  boxes0 int32 [batch][max_boxes][4] = (x, y, w, h), n0 int32 [batch] or
+ * NULL (max_boxes each; a value outside 0 .. max_boxes is clamped, as in (E)) and q0 int32 [batch][max_boxes]: the boxes of frame k - 1 with a
+ * reference disparity each in quarter pixels - (H)'s info[3], (E)'s stat[2]; q <= 0: no depth test for the box.  boxes1, n1, q1: the same of
+ * frame k.  centre int32 [batch][max_boxes][3] or NULL.  With M = max_boxes:
+ *   members   a box's pixels are (E)'s: columns [clamp(x), clamp(x + w)), rows [clamp(y), clamp(y + h)), clamp(a) = min(max(a, 0), size - 1),
+ *             sums in 64 bits: the map's last column and row belong to no box.  in0(i): (u0, v0) in box i of frame k - 1, and q0[i] <= 0 or
+ *             |d0q - 4 q0[i]| <= band_q.  in1(j): (u1, v1) in box j of frame k, and q1[j] <= 0 or (d1q > 0 and |d1q - 4 q1[j]| <= band_q).  A
+ *             match may be a member of several boxes of a frame.
+ *   votes     int32 [batch][M][M + 1]: votes[i][j] = the matches with in0(i) and in1(j); votes[i][M] = the matches with in0(i), the members.
+ *   link      j*(i) = the j with the most votes, among equals the lowest; kept if votes[i][j*] >= min_votes and 256 votes[i][j*] >= share
+ *             members.  Of several i that keep one j only that with the most votes keeps it, among equals the lowest i: a current box
+ *             continues one track.  int32 [batch][M][4] = (j or -1, votes[i][j*], members, the most votes over j != j* - 0 for M = 1).
+ *   sums      int64 [batch][M][16] per previous box i with a link, over the matches with in0(i), in1(link[i]) and d1q in 1 .. 2^20.  Xc = the
+ *             match's point moved by the pose as in (Z1), X1 = (((u1 - cx) b16) / d1q, ((v1 - cy) b16) / d1q, fb16 / d1q); doubles, one
+ *             operation at a time.  inside: Xc.z > 0.1 (false for NaN) and (Z2)'s |pu|, |pv|, |pd| <= 2^30.  For an inside match m_a =
+ *             clamp(floor(1024 (X1_a - Xc_a) + 0.5), +-2^20), p_a = clamp(floor(1024 X1_a + 0.5), +-2^30) per axis - the scalings are by powers
+ *             of two, so the products are exact - and (Z2)'s ru, rv, rd, each clamped to +-2^20.  With a centre and gate_m > 0 a match counts
+ *             only if |m_a - centre[i][a]| <= gate_m on the three axes.  (n, inside, sum ru, sum rv, sum rd, sum ru^2 + rv^2, sum m[3], sum
+ *             m^2[3], sum p[3], 0): inside is counted in front of the gate, everything else behind it.  Every sum stays below 2^59.
+ * Rows at and behind n0 and columns at and behind n1 are 0, their link (-1, 0, 0, 0); so are the sums of a box without a link.  sum m / n /
+ * 1024 is the box's own motion per frame in metres, in the current camera's axes: Xc already carries the camera's.
+ * stereo_vision.sv.object_links restates this in numpy. */
+
+/* Host only: the bytes of the workspace sv_object_links_device needs: 16 per match.  SV_ERR_ARG (bytes untouched) for a NULL bytes,
+ * capacity outside 0..65536, batch outside 0..65535. */
+int sv_object_links_workspace(int capacity, int batch, size_t *bytes);
+/* Enqueued on `stream` (a hipStream_t, NULL = the default stream) as four kernels - votes and sums cleared; a lane per match: its two
+ * membership words, the votes added in LDS and flushed by integer atomic adds; a wavefront per frame: the links; a lane per match: the
+ * sums added in LDS and flushed by 64-bit integer atomic adds - and not waited for: nothing is allocated, no host synchronisation is made,
+ * no float atomic is issued, nothing is assumed of what the outputs or the workspace held before, and every output is written in full.
+ * All pointers device; poses, sums and the workspace 8-byte, everything else 4-byte aligned.  Returns SV_OK (nothing enqueued for batch
+ * == 0 or max_boxes == 0), SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued, the outputs untouched, the text in sv_last_error(NULL) - for what
+ * the workspace call refuses; a NULL spec or a bad word of it; with batch > 0 a NULL counts or poses, a NULL matches beside a capacity > 0,
+ * and beside max_boxes > 0 a NULL boxes0, q0, boxes1, q1, votes, link, sums or workspace; a misaligned pointer; too small a workspace; an
+ * output or the workspace that shares bytes with an input or with another output. */
+int sv_object_links_device(const int32_t *matches, const int32_t *counts, const double *poses, int batch, int capacity, const int32_t *boxes0, const int32_t *n0,
+                           const int32_t *q0, const int32_t *boxes1, const int32_t *n1, const int32_t *q1, const int32_t *centre, const sv_track_spec *spec,
+                           int32_t *votes, int32_t *link, int64_t *sums, void *workspace, size_t workspace_bytes, void *stream);
+/* Measurement hook for the call above, process-wide: flags = 1 .. 3 leaves kernels out from the end, for timing by difference only - 1 the
+ * sums, 2 the links too, 3 the votes too -, and what they would have written is then undefined.  0 is the default.  Returns SV_OK, or
+ * SV_ERR_ARG for a value outside 0 .. 3. */
+int sv_debug_object_links(int flags);
 
 /* ---- (A)the reference's exported symbols ------------------------------------------------------------- */
 

@@ -1,4 +1,4 @@
-// What the stage entries of groups (D) to (AA) of include/stereo_vision_hip.h share on the host (top_view.cpp ... warp.cpp): the
+// What the stage entries of groups (D) to (AB) of include/stereo_vision_hip.h share on the host (top_view.cpp ... track.cpp): the
 // refusal of a bad call, the checks that several groups state in the same words, and the set-up of sv::ReprojectArgs.  Host code only:
 // no .hip file includes it.
 #pragma once
@@ -48,7 +48,7 @@ inline const char *check_images(const char *prefix, int batch, int width, int he
     return nullptr;
 }
 
-// NULL for the camera words the specs of groups (Z) and (AA) begin with - f, cx, cy, b16, fb, fb16 -, else what is wrong with them.
+// NULL for the camera words the specs of groups (Z), (AA) and (AB) begin with - f, cx, cy, b16, fb, fb16 -, else what is wrong with them.
 template <class Spec>
 inline const char *check_camera_words(const char *prefix, const Spec *s) {
     const double w[6] = {s->f, s->cx, s->cy, s->b16, s->fb, s->fb16};

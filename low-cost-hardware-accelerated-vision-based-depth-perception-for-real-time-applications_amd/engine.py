@@ -573,6 +573,13 @@ class SvWarpSpec(ctypes.Structure):
                 ("e_max", ctypes.c_int32), ("tol_q", ctypes.c_int32), ("rel_q", ctypes.c_int32), ("mode", ctypes.c_int32), ("reserved", ctypes.c_int32 * 12)]
 
 
+class SvTrackSpec(ctypes.Structure):
+    """sv_track_spec of include/stereo_vision_hip.h."""
+    _fields_ = [("f", ctypes.c_double), ("cx", ctypes.c_double), ("cy", ctypes.c_double), ("b16", ctypes.c_double), ("fb", ctypes.c_double), ("fb16", ctypes.c_double),
+                ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("max_boxes", ctypes.c_int32), ("band_q", ctypes.c_int32), ("min_votes", ctypes.c_int32),
+                ("share", ctypes.c_int32), ("gate_m", ctypes.c_int32), ("reserved", ctypes.c_int32 * 9)]
+
+
 def _signatures():
     """The table below: per stage group of the C API, (D) to (S), its functions and per function (restype, argtypes), parameter by
     parameter as include/stereo_vision_hip.h declares them - tests/test_stage_signatures.py holds the two against each other."""
@@ -702,6 +709,11 @@ def _signatures():
         "warp": {  # (AA)
             "sv_disparity_warp_workspace": (ci, [ci, ci, ci, P(sz)]),
             "sv_disparity_warp_device": (ci, [vp, vp, vp, ci, ci, ci, P(SvWarpSpec), vp, vp, vp, vp, vp, vp, sz, vp]),
+        },
+        "track": {  # (AB)
+            "sv_object_links_workspace": (ci, [ci, ci, P(sz)]),
+            "sv_object_links_device": (ci, [vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, P(SvTrackSpec), vp, vp, vp, vp, sz, vp]),
+            "sv_debug_object_links": (ci, [ci]),
         },
     }
 
@@ -3067,6 +3079,85 @@ def disparity_warp(d_prev, d_cur, camera, poses, e_max=1, tol_q=16, rel_q=0, mod
                                         res.counts.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(), torch.cuda.current_stream(dev).cuda_stream)
     _check(rc, "sv_disparity_warp_device")
     return res  # ws goes back to torch's allocator, which hands it out again on this stream only: behind the kernels
+
+
+def track_lib():
+    """The library with the signatures of group (AB) declared."""
+    return _bind("track")
+
+
+def track_spec(camera, max_boxes, width, height, **words):
+    """-> SvTrackSpec from a camera dict (stereo_vision.sv.voxel_render_camera's) and object_links' words (stereo_vision.sv.track_words
+    checks them: ValueError)."""
+    from .stereo_vision.sv import flow_camera, track_words
+    cam, w = flow_camera(camera), track_words(max_boxes, width, height, **words)
+    return SvTrackSpec(cam["f"], cam["cx"], cam["cy"], cam["b16"], cam["fb"], cam["fb16"], w["width"], w["height"], w["max_boxes"], w["band_q"], w["min_votes"],
+                       w["share"], w["gate_m"])
+
+
+def object_links(matches, counts, poses, boxes0, n0, q0, boxes1, n1, q1, camera, width, height, band_q=48, min_votes=3, share=128, gate_m=0, centre=None, out=None,
+                 workspace=None):
+    """The boxes of frames k - 1 linked to those of frames k by the temporal matches that lie in both, and the sums of each linked box's own
+    motion - the definition of stereo_vision.sv.object_links on the GPU, bit for bit (sv_object_links_device: four kernels, integer
+    atomics only).  matches CUDA int32 [B,capacity,6] and counts int32 [B] as flow_match returns them; poses float64 [B,12] (numpy, or a
+    tensor on the device): previous camera to current camera; boxes0 int32 [B,M,4], n0 int32 [B] or None, q0 int32 [B,M] - the boxes of
+    frames k - 1, their counts and reference disparities in quarter pixels (objects' info[..., 3], box_positions' stat[..., 2]) -; boxes1,
+    n1, q1 the same of frames k; M <= 64; camera: voxel_render_camera's dict; width, height: of the maps; band_q (1/16 px), min_votes,
+    share, gate_m (1/1024 m, 0: no gate) and centre int32 [B,M,3] or None as there.  out: the dict of an earlier call of the same shape to
+    write into; workspace: an int64 tensor of 2 B capacity words to use (None: torch's allocator).  -> {"votes": int32 [B,M,M+1], "link":
+    int32 [B,M,4], "sums": int64 [B,M,16]}; for CUDA tensors enqueued on torch's current stream, nothing is read back.  CPU tensors (or
+    numpy arrays) run the numpy form and give numpy arrays."""
+    import torch
+    if not (isinstance(matches, torch.Tensor) and matches.is_cuda):
+        from .stereo_vision.sv import object_links as on_host
+        as_np = lambda t: t.cpu().numpy() if isinstance(t, torch.Tensor) else t
+        return on_host(*[as_np(t) for t in (matches, counts, poses, boxes0, n0, q0, boxes1, n1, q1)], camera, width, height, band_q, min_votes, share, gate_m, as_np(centre))
+    matches, counts, B, cap = _flow_matches(matches, counts)
+    dev = matches.device
+    if not (isinstance(boxes0, torch.Tensor) and boxes0.device == dev and boxes0.dtype == torch.int32 and boxes0.dim() == 3 and boxes0.shape[0] == B and boxes0.shape[2] == 4):
+        raise ValueError("boxes0 must be an int32 tensor [%d,max_boxes,4] on the device of matches" % B)
+    M = int(boxes0.shape[1])
+    spec = track_spec(camera, M, width, height, band_q=band_q, min_votes=min_votes, share=share, gate_m=gate_m)
+    p = poses if isinstance(poses, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(poses, np.float64)).to(dev)
+    if p.device != dev or p.dtype != torch.float64 or tuple(p.shape) != (B, 12):
+        raise ValueError("poses must be float64 [%d,12]" % B)
+    c = None if centre is None else centre if isinstance(centre, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(centre)).to(dev)
+    ins = []
+    for t, name, want, optional in ((boxes0, "boxes0", (B, M, 4), False), (n0, "n0", (B,), True), (q0, "q0", (B, M), False), (boxes1, "boxes1", (B, M, 4), False),
+                                    (n1, "n1", (B,), True), (q1, "q1", (B, M), False), (c, "centre", (B, M, 3), True)):
+        if t is None and optional:
+            ins.append(None)
+            continue
+        if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == torch.int32 and tuple(t.shape) == want):
+            raise ValueError("%s must be %san int32 tensor %s on %s" % (name, "None or " if optional else "", list(want), dev))
+        ins.append(t.contiguous())
+    boxes0, n0, q0, boxes1, n1, q1, c = ins
+    p = p.contiguous()
+    res = out if out is not None else {"votes": torch.empty((B, M, M + 1), dtype=torch.int32, device=dev), "link": torch.empty((B, M, 4), dtype=torch.int32, device=dev),
+                                       "sums": torch.empty((B, M, 16), dtype=torch.int64, device=dev)}
+    for name, dtype, want in (("votes", torch.int32, (B, M, M + 1)), ("link", torch.int32, (B, M, 4)), ("sums", torch.int64, (B, M, 16))):
+        t = res.get(name)
+        if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dtype and tuple(t.shape) == want and t.is_contiguous()):
+            raise ValueError("out[%r] must be a contiguous %s tensor %s on %s" % (name, str(dtype).replace("torch.", ""), list(want), dev))
+    L = track_lib()
+    need = ctypes.c_size_t()
+    _check(L.sv_object_links_workspace(cap, B, ctypes.byref(need)), "sv_object_links_workspace")
+    if B == 0 or M == 0:  # nothing to enqueue
+        return res
+    ws = workspace if workspace is not None else torch.empty((max(need.value // 8, 1),), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.sv_object_links_device(_ptr(matches), counts.data_ptr(), p.data_ptr(), B, cap, boxes0.data_ptr(), None if n0 is None else n0.data_ptr(), q0.data_ptr(),
+                                      boxes1.data_ptr(), None if n1 is None else n1.data_ptr(), q1.data_ptr(), None if c is None else c.data_ptr(), ctypes.byref(spec),
+                                      res["votes"].data_ptr(), res["link"].data_ptr(), res["sums"].data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(),
+                                      torch.cuda.current_stream(dev).cuda_stream)
+    _check(rc, "sv_object_links_device")
+    return res  # ws goes back to torch's allocator, which hands it out again on this stream only: behind the kernels
+
+
+def debug_object_links(stop=0):
+    """sv_debug_object_links: stop = 1 .. 3 leaves the sums, the link and the votes kernel out, from the end - for timing by difference
+    only: what they would have written is undefined.  0 is the default.  Process-wide; a measurement hook."""
+    _check(track_lib().sv_debug_object_links(int(stop)), "sv_debug_object_links")
 
 
 def host_support_filter(params, dcan, width, height, threads=0, lattice=False):

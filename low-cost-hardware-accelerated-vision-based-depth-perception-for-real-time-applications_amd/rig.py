@@ -40,7 +40,7 @@ import ctypes
 
 import numpy as np
 
-from .engine import disparity_warp, flow_egomotion, flow_match
+from .engine import disparity_warp, flow_egomotion, flow_match, object_links
 from .engine import (SvParams, StereoEngine, StereoError, box_positions_from_disparity, box_spec, cloud_spec, compact_cloud_from_disparity,
                      ground_from_disparity, ground_spec, lib, occupancy_from_disparity, occupancy_fuse, occupancy_match, occupancy_clearance, clearance_paths, cost_cells, cost_routes, frontier_cells, frontier_clusters, occupancy_cost_to_goal, occupancy_view, occupancy_spec, pinned_array, reproject, split_clouds, stixel_spec, stixels_from_disparity,
                      top_view_from_disparity, top_view_spec, split_voxel_clouds, voxel_cloud_from_disparity, voxel_map_align, voxel_map_carry, voxel_map_clear, voxel_map_insert, voxel_map_match, voxel_map_new,
@@ -416,6 +416,73 @@ class StereoRig:
         if from_numpy:
             out = {k: v.cpu().numpy() for k, v in out.items()}
         out["rel"], out["ok"] = rel, ok
+        return out
+
+    def track(self, left, right, pixel_format="bgr", boxes=None, n_boxes=None, transform=None, guess="velocity", band_q=48, min_votes=3, share=128, gate_m=256,
+              objects=None, **spec):
+        """The objects of a batch of B consecutive pairs carried from frame to frame (include/stereo_vision_hip.h (AB),
+        stereo_vision.sv.object_links): front end and engine once for the batch; odometry()'s matches and motions (guess and spec: its
+        words); per frame the boxes of objects() (`objects`: a dict of its spec words, or None) or the caller's - boxes int32 [B,M,4] = (x,
+        y, w, h), n_boxes int32 [B] or None - with box_positions(select="near") for their positions and reference disparities; then
+        engine.object_links for the B - 1 consecutive pairs in one call, twice for gate_m > 0: a round without a gate and one gated, in
+        1/1024 m, about the first round's mean motion, whose B x M x 16 words are read back.  At most 64 boxes per frame take part: the
+        first 64, and "left_out" [B] says how many did not.  band_q, min_votes, share: object_links' words.  transform as in top_view, for
+        the positions only.
+        -> {"boxes" int32 [B,M,4], "n" int32 [B], "positions" float64 [B,M,3], "stat" int32 [B,M,4], "votes" int32 [B-1,M,M+1], "link" int32
+        [B-1,M,4], "sums" int64 [B-1,M,16]: tensors for CUDA input, numpy arrays for numpy input; and on the host "left_out" int64 [B], "centre"
+        int32 [B-1,M,3] or None, "motion" float64 [B-1,M,3] - per box of frame k - 1 its own motion to frame k in metres per frame, in the
+        current camera's axes, NaN without a link or a match -, "count" int64 [B-1,M] - the matches behind it -, "rel" float64 [B-1,12],
+        "ok" bool [B-1], "matches": odometry()'s}.  A pair whose odometry fit was not ok gets links from the votes but NaN motions."""
+        import torch
+        _sv.track_words(0, self.width, self.height, band_q, min_votes, share, gate_m)  # argument errors before any work
+        _sv.flow_odometry_spec(**spec)
+        XR, XT = self._transform(transform)
+        gl, d1, camera, from_numpy = self._flow_inputs(left, right, pixel_format)
+        B, dev = int(gl.shape[0]), gl.device
+        if B < 2:
+            raise ValueError("track needs at least two consecutive pairs, got %d" % B)
+        if boxes is None:
+            words = dict(objects or {})
+            if words.get("min_support") is None:
+                words["min_support"] = self.width
+            stixel_words = {k: words.pop(k) for k in ("q_min", "sim", "max_gap", "min_rows", "max_layers", "col_step", "sim_cols", "min_cols") if k in words}
+            g = ground_from_disparity(d1, self.params.disp_max, want_vdisp=False, want_free=False, **words)
+            st = stixels_from_disparity(d1, g.labels, self.params.disp_max, capacity=_sv.TRACK_BOXES_MAX, want_stixels=False, **stixel_words)
+            bx, found = st.boxes, st.counts
+        else:
+            bx = boxes if isinstance(boxes, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(boxes, np.int32))
+            if bx.dtype != torch.int32 or bx.dim() != 3 or tuple(bx.shape[::2]) != (B, 4):
+                raise ValueError("boxes must be int32 [%d,M,4], got %s %s" % (B, bx.dtype, tuple(bx.shape)))
+            bx = bx.to(dev)
+            found = torch.full((B,), int(bx.shape[1]), dtype=torch.int32, device=dev) if n_boxes is None else \
+                (n_boxes if isinstance(n_boxes, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(n_boxes, np.int32))).to(dev)
+            if found.dtype != torch.int32 or tuple(found.shape) != (B,):
+                raise ValueError("n_boxes must be None or int32 [%d]" % B)
+            found = found.clamp(0, int(bx.shape[1]))
+        bx = bx[:, :_sv.TRACK_BOXES_MAX].contiguous()
+        M = int(bx.shape[1])
+        n = found.clamp(0, M).to(torch.int32)
+        left_out = (found.to(torch.int64) - M).clamp(min=0).cpu().numpy()
+        if M:
+            pos, stat = box_positions_from_disparity(d1, self.Q, bx, n, XR=XR, XT=XT, select="near", disparity="d1")
+        else:
+            pos, stat = torch.empty((B, 0, 3), dtype=torch.float64, device=dev), torch.empty((B, 0, 4), dtype=torch.int32, device=dev)
+        q = stat[:, :, 2].contiguous()
+
+        got = self._odometry_pairs(gl, d1, camera, guess, spec)
+        rel, ok = got["rel"], got["ok"]
+        m = {k: torch.cat([getattr(c, k) for c in got["calls"]]) for k in ("matches", "cost", "counts")}
+        used = rel.copy()
+        used[~ok] = np.nan  # no match is inside under such a motion: no sums, NaN motions
+        res = _sv.object_links_rounds(lambda gate, centre: object_links(m["matches"], m["counts"], used, bx[:-1], n[:-1], q[:-1], bx[1:], n[1:], q[1:], camera, self.width,
+                                                                        self.height, band_q, min_votes, share, gate, centre), gate_m)
+        sums, link = res["sums"].cpu().numpy(), res["link"].cpu().numpy()
+        mo = _sv.object_motion(sums, link)
+        out = {"boxes": bx, "n": n, "positions": pos, "stat": stat, "votes": res["votes"], "link": res["link"], "sums": res["sums"]}
+        if from_numpy:
+            out = {k: v.cpu().numpy() for k, v in out.items()}
+            m = {k: v.cpu().numpy() for k, v in m.items()}
+        out.update(left_out=left_out, centre=res["centre"], motion=mo["motion"], count=mo["n"], rel=rel, ok=ok, matches=m)
         return out
 
     def ground(self, left, right, pixel_format="bgr", transform=None, **spec):

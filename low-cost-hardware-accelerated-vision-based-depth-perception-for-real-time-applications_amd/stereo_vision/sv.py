@@ -3116,6 +3116,339 @@ def disparity_warp_brute(d_prev, d_cur, camera, poses, e_max=1, tol_q=16, rel_q=
     return {"expected": expected, "source": source, "label": label, "out": out, "counts": counts}
 
 
+TRACK_BOXES_MAX = 64         # boxes per frame: a match's membership in the boxes of one frame is one 64-bit word
+TRACK_BAND_MAX = 2 ** 20     # band_q at most, 1/16 px
+TRACK_GATE_MAX = 2 ** 20     # gate_m at most, 1/1024 m; 0: no gate
+TRACK_SHARE_MAX = 256        # share at most: 256 votes >= share members
+TRACK_M_MAX = 2 ** 20        # |m|, |ru|, |rv|, |rd| of a match are clamped to it: 1024 m, 65536 px
+TRACK_P_MAX = 2 ** 30        # |p| of a match is clamped to it
+TRACK_BATCH_MAX = 65535
+TRACK_SUMS = ("n", "inside", "ru", "rv", "rd", "E", "mx", "my", "mz", "mxx", "myy", "mzz", "px", "py", "pz", "zero")  # the 16 words per box
+TRACK_WORDS = dict(band_q=48, min_votes=3, share=128, gate_m=0)  # the defaults: 3 px about the box's disparity, half of the members
+
+
+def track_words(max_boxes, width, height, band_q=48, min_votes=3, share=128, gate_m=0):
+    """The words of an object_links call as a dict of ints, after the checks the C entry makes (ValueError): max_boxes in 0 .. 64, width
+    and height in 1 .. 8192, band_q in 0 .. 2^20 (1/16 px), min_votes >= 1, share in 0 .. 256, gate_m in 0 .. 2^20 (1/1024 m, 0: no gate)."""
+    w = {}
+    for k, v, lo, hi in (("max_boxes", max_boxes, 0, TRACK_BOXES_MAX), ("width", width, 1, 8192), ("height", height, 1, 8192), ("band_q", band_q, 0, TRACK_BAND_MAX),
+                         ("min_votes", min_votes, 1, 2 ** 31 - 1), ("share", share, 0, TRACK_SHARE_MAX), ("gate_m", gate_m, 0, TRACK_GATE_MAX)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ValueError("%s must be an integer in %d .. %d, got %r" % (k, lo, hi, v))
+        w[k] = int(v)
+    return w
+
+
+def _track_setup(matches, counts, poses, boxes0, n0, q0, boxes1, n1, q1, centre):
+    matches, counts, poses = _flow_sums_setup(matches, counts, poses)
+    B = matches.shape[0]
+    boxes0 = np.asarray(boxes0)
+    if boxes0.dtype != np.int32 or boxes0.ndim != 3 or boxes0.shape[0] != B or boxes0.shape[2] != 4 or boxes0.shape[1] > TRACK_BOXES_MAX:
+        raise ValueError("boxes0 must be int32 [%d,max_boxes,4] with max_boxes <= 64, got %s %s" % (B, boxes0.dtype, boxes0.shape))
+    M = boxes0.shape[1]
+    boxes1 = np.asarray(boxes1)
+    if boxes1.dtype != np.int32 or boxes1.shape != (B, M, 4):
+        raise ValueError("boxes1 must be int32 [%d,%d,4], got %s %s" % (B, M, boxes1.dtype, boxes1.shape))
+    out = [matches, counts, poses, boxes0, boxes1]
+    for n, what in ((n0, "n0"), (n1, "n1")):
+        n = np.full(B, M, np.int32) if n is None else np.asarray(n)
+        if n.dtype != np.int32 or n.shape != (B,):
+            raise ValueError("%s must be None or int32 [%d], got %s %s" % (what, B, n.dtype, n.shape))
+        out.append(np.clip(n.astype(np.int64), 0, M))
+    for q, what in ((q0, "q0"), (q1, "q1")):
+        q = np.asarray(q)
+        if q.dtype != np.int32 or q.shape != (B, M):
+            raise ValueError("%s must be int32 [%d,%d], got %s %s" % (what, B, M, q.dtype, q.shape))
+        out.append(q.astype(np.int64))
+    if centre is not None:
+        centre = np.asarray(centre)
+        if centre.dtype != np.int32 or centre.shape != (B, M, 3):
+            raise ValueError("centre must be None or int32 [%d,%d,3], got %s %s" % (B, M, centre.dtype, centre.shape))
+        centre = centre.astype(np.int64)
+    return out + [centre]
+
+
+def _track_link(votes, M, min_votes, share):
+    """Rule 3 on the votes int [M, M + 1] of one frame, in Python integers -> link int [M, 4]."""
+    link = np.zeros((M, 4), np.int64)
+    link[:, 0] = -1
+    keep = []
+    for i in range(M):
+        row = [int(v) for v in votes[i, :M]]
+        members = int(votes[i, M])
+        best = max(row)
+        j = row.index(best)  # the lowest among equals
+        second = max(row[:j] + row[j + 1:], default=0)
+        link[i] = (-1, best, members, second)
+        if best >= min_votes and 256 * best >= share * members:
+            keep.append((j, -best, i))
+    taken = set()
+    for j, _, i in sorted(keep):  # per j the most votes, among equals the lowest i
+        if j not in taken:
+            taken.add(j)
+            link[i, 0] = j
+    return link
+
+
+def object_links(matches, counts, poses, boxes0, n0, q0, boxes1, n1, q1, camera, width, height, band_q=48, min_votes=3, share=128, gate_m=0, centre=None):
+    """The boxes of frame k - 1 linked to those of frame k by the temporal matches that lie in both, and each linked box's matches reduced
+    to the box's own motion - the definition of include/stereo_vision_hip.h (AB) in numpy.  matches int32 [B,capacity,6] and counts int32
+    [B]: flow_match's, under flow_pose_sums' rules (a count of -1 or 0 gives nothing, a count above the capacity counts as the capacity, a
+    row with d0q outside 1 .. 2^20 is skipped); poses float64 [B,12]: previous camera to current camera; boxes0 int32 [B,M,4] = (x, y, w, h),
+    n0 int32 [B] or None (M each; clamped to 0 .. M) and q0 int32 [B,M]: the boxes of frame k - 1 with a reference disparity each in
+    quarter pixels - objects' info[..., 3], box_positions' stat[..., 2]; q <= 0: no depth test -; boxes1, n1, q1: the same of frame k; M
+    <= 64; camera: voxel_render_camera's dict; band_q in 1/16 px, min_votes >= 1, share in 0 .. 256, gate_m in 1/1024 m (0: no gate),
+    centre int32 [B,M,3] or None.
+      members   a box's pixels are box_bounds': columns [clamp(x), clamp(x + w)), rows [clamp(y), clamp(y + h)).  in0(i): (u0, v0) in box i of
+                frame k - 1, and q0[i] <= 0 or |d0q - 4 q0[i]| <= band_q.  in1(j): (u1, v1) in box j of frame k, and q1[j] <= 0 or (d1q > 0
+                and |d1q - 4 q1[j]| <= band_q).
+      votes     int32 [B,M,M+1]: votes[i][j] = the matches with in0(i) and in1(j); votes[i][M] = the matches with in0(i).
+      link      j*(i) = the j with the most votes, among equals the lowest; kept if votes[i][j*] >= min_votes and 256 votes[i][j*] >= share
+                members; of several i that keep one j only that with the most votes keeps it, among equals the lowest i.  int32 [B,M,4]
+                = (j or -1, votes[i][j*], members, the most votes over j != j*).
+      sums      int64 [B,M,16], TRACK_SUMS, per linked box i over the matches with in0(i), in1(link[i]) and d1q in 1 .. 2^20: Xc = the
+                match's point moved by the pose (_flow_point, _flow_move), X1 = _flow_point of (u1, v1, d1q); inside: Xc.z > FLOW_Z_MIN and
+                flow_pose_sums' |pu|, |pv|, |pd| <= 2^30.  m_a = clamp(floor(1024 (X1_a - Xc_a) + 0.5), +-2^20), p_a = clamp(floor(1024 X1_a +
+                0.5), +-2^30), ru, rv, rd flow_pose_sums' residuals clamped to +-2^20.  With a centre and gate_m > 0 a match counts only if
+                |m_a - centre[i][a]| <= gate_m on the three axes.  (n, inside, sum ru, rv, rd, sum ru^2 + rv^2, sum m[3], sum m^2[3], sum p[3],
+                0): inside is counted in front of the gate, everything else behind it.
+    Rows at and behind n0 and columns at and behind n1 are 0, their link (-1, 0, 0, 0).  -> {"votes", "link", "sums"}."""
+    matches, counts, poses, boxes0, boxes1, n0, n1, q0, q1, centre = _track_setup(matches, counts, poses, boxes0, n0, q0, boxes1, n1, q1, centre)
+    B, cap = matches.shape[:2]
+    M = boxes0.shape[1]
+    w = track_words(M, width, height, band_q, min_votes, share, gate_m)
+    cam = flow_camera(camera)
+    votes, link, sums = np.zeros((B, M, M + 1), np.int32), np.zeros((B, M, 4), np.int32), np.zeros((B, M, 16), np.int64)
+    link[:, :, 0] = -1
+    gated = centre is not None and w["gate_m"] > 0
+
+    def members(u, v, d, boxes, n, q, needs_d):
+        bounds = np.array([box_bounds(bx, width, height) for bx in boxes], np.int64).reshape(M, 4)
+        ok = (u[:, None] >= bounds[:, 0]) & (u[:, None] < bounds[:, 1]) & (v[:, None] >= bounds[:, 2]) & (v[:, None] < bounds[:, 3]) & (np.arange(M) < n)
+        near = np.abs(d[:, None] - 4 * q) <= w["band_q"]
+        if needs_d:
+            near &= d[:, None] > 0
+        return ok & ((q <= 0) | near)
+
+    for b in range(B):
+        n = min(int(counts[b]), cap)
+        if n <= 0 or M == 0:
+            continue
+        m = matches[b, :n].astype(np.int64)
+        u0, v0, d0, u1, v1, d1 = (m[:, k] for k in range(6))
+        live = (d0 >= 1) & (d0 <= FLOW_DQ_MAX)
+        in0 = members(u0, v0, d0, boxes0[b], n0[b], q0[b], False) & live[:, None]
+        in1 = members(u1, v1, d1, boxes1[b], n1[b], q1[b], True)
+        votes[b, :, :M] = in0.T.astype(np.int64) @ in1.astype(np.int64)
+        votes[b, :, M] = in0.sum(0)
+        link[b] = _track_link(votes[b], M, w["min_votes"], w["share"])
+        if not (link[b, :, 0] >= 0).any():
+            continue
+        both = live & (d1 >= 1) & (d1 <= FLOW_DQ_MAX)
+        x0, y0, z0 = _flow_point(cam, u0, v0, np.where(live, d0, 1))
+        x, y, z = _flow_move(poses[b], x0, y0, z0)
+        X1 = _flow_point(cam, u1, v1, np.where(both, d1, 1))
+        with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+            ok = both & (z > FLOW_Z_MIN)
+            zs = np.where(ok, z, 1.0)
+            xz, yz, bz = x / zs, y / zs, cam["fb"] / zs
+            pu, pv, pd = np.floor(16.0 * (cam["f"] * xz + cam["cx"]) + 0.5), np.floor(16.0 * (cam["f"] * yz + cam["cy"]) + 0.5), np.floor(16.0 * bz + 0.5)
+            inside = ok & (np.abs(pu) <= FLOW_PIXEL_MAX) & (np.abs(pv) <= FLOW_PIXEL_MAX) & (np.abs(pd) <= FLOW_PIXEL_MAX)
+            mv = [np.where(inside, _flow_q(1024.0 * (np.where(inside, X1[a] - c, 0.0)), TRACK_M_MAX), 0) for a, c in enumerate((x, y, z))]
+            pq = [np.where(inside, _flow_q(1024.0 * X1[a], TRACK_P_MAX), 0) for a in range(3)]
+        pu, pv, pd = (np.where(inside, p, 0.0).astype(np.int64) for p in (pu, pv, pd))
+        r = [np.where(inside, np.clip(v, -TRACK_M_MAX, TRACK_M_MAX), 0) for v in (16 * u1 - pu, 16 * v1 - pv, d1 - pd)]
+        for i in np.flatnonzero(link[b, :, 0] >= 0):
+            fed = in0[:, i] & in1[:, link[b, i, 0]] & both
+            ins = fed & inside
+            cnt = ins
+            if gated:
+                cnt = ins & np.logical_and.reduce([np.abs(mv[a] - centre[b, i, a]) <= w["gate_m"] for a in range(3)])
+            s = [cnt.sum(), ins.sum(), r[0][cnt].sum(), r[1][cnt].sum(), r[2][cnt].sum(), (r[0][cnt] ** 2 + r[1][cnt] ** 2).sum()]
+            s += [mv[a][cnt].sum() for a in range(3)] + [(mv[a][cnt] ** 2).sum() for a in range(3)] + [pq[a][cnt].sum() for a in range(3)] + [0]
+            sums[b, i] = s
+    return {"votes": votes, "link": link, "sums": sums}
+
+
+def object_links_brute(matches, counts, poses, boxes0, n0, q0, boxes1, n1, q1, camera, width, height, band_q=48, min_votes=3, share=128, gate_m=0, centre=None):
+    """object_links match by match: Python floats in the stated order in front of the rounding, Python integers behind it."""
+    import math
+    matches, counts, poses, boxes0, boxes1, n0, n1, q0, q1, centre = _track_setup(matches, counts, poses, boxes0, n0, q0, boxes1, n1, q1, centre)
+    B, cap = matches.shape[:2]
+    M = boxes0.shape[1]
+    w = track_words(M, width, height, band_q, min_votes, share, gate_m)
+    cam = flow_camera(camera)
+    f, cx, cy, b16, fb, fb16 = (cam[k] for k in ("f", "cx", "cy", "b16", "fb", "fb16"))
+    votes, link, sums = np.zeros((B, M, M + 1), np.int32), np.zeros((B, M, 4), np.int32), np.zeros((B, M, 16), np.int64)
+    link[:, :, 0] = -1
+
+    def rnd(v, lim):  # clamp(floor(v + 0.5), +-lim) of a double that is not NaN
+        t = v + 0.5
+        return lim if t >= lim else -lim if t <= -lim else math.floor(t)
+
+    def inside_box(u, v, box):
+        i_lb, i_ub, j_lb, j_ub = box_bounds(box, width, height)
+        return i_lb <= u < i_ub and j_lb <= v < j_ub
+
+    for b in range(B):
+        rows = [[int(v) for v in matches[b, i]] for i in range(max(min(int(counts[b]), cap), 0))]
+        rows = [r for r in rows if 1 <= r[2] <= FLOW_DQ_MAX]
+        mem = []
+        for u0, v0, d0, u1, v1, d1 in rows:
+            a0 = [i for i in range(int(n0[b])) if inside_box(u0, v0, boxes0[b, i]) and (q0[b, i] <= 0 or abs(d0 - 4 * int(q0[b, i])) <= w["band_q"])]
+            a1 = [j for j in range(int(n1[b])) if inside_box(u1, v1, boxes1[b, j]) and (q1[b, j] <= 0 or (d1 > 0 and abs(d1 - 4 * int(q1[b, j])) <= w["band_q"]))]
+            mem.append((a0, a1))
+            for i in a0:
+                votes[b, i, M] += 1
+                for j in a1:
+                    votes[b, i, j] += 1
+        link[b] = _track_link(votes[b], M, w["min_votes"], w["share"])
+        p = [float(v) for v in poses[b]]
+        for (u0, v0, d0, u1, v1, d1), (a0, a1) in zip(rows, mem):
+            feeds = [i for i in a0 if link[b, i, 0] in a1]
+            if not feeds or not 1 <= d1 <= FLOW_DQ_MAX:
+                continue
+            X0 = (((u0 - cx) * b16) / d0, ((v0 - cy) * b16) / d0, fb16 / d0)
+            X1 = (((u1 - cx) * b16) / d1, ((v1 - cy) * b16) / d1, fb16 / d1)
+            Xc = [((p[3 * k] * X0[0] + p[3 * k + 1] * X0[1]) + p[3 * k + 2] * X0[2]) + p[9 + k] for k in range(3)]
+            z = Xc[2]
+            if not z > FLOW_Z_MIN:
+                continue
+            xz, yz, bz = Xc[0] / z, Xc[1] / z, fb / z
+            pred = (16.0 * (f * xz + cx) + 0.5, 16.0 * (f * yz + cy) + 0.5, 16.0 * bz + 0.5)
+            if not all(math.isfinite(v) and abs(math.floor(v)) <= FLOW_PIXEL_MAX for v in pred):
+                continue
+            pu, pv, pd = (math.floor(v) for v in pred)
+            res = [max(-TRACK_M_MAX, min(TRACK_M_MAX, v)) for v in (16 * u1 - pu, 16 * v1 - pv, d1 - pd)]
+            mv = [rnd(1024.0 * (X1[a] - Xc[a]), TRACK_M_MAX) for a in range(3)]
+            pq = [rnd(1024.0 * X1[a], TRACK_P_MAX) for a in range(3)]
+            for i in feeds:
+                s = [int(v) for v in sums[b, i]]
+                s[1] += 1
+                if centre is None or w["gate_m"] == 0 or all(abs(mv[a] - int(centre[b, i, a])) <= w["gate_m"] for a in range(3)):
+                    add = [1, 0, res[0], res[1], res[2], res[0] ** 2 + res[1] ** 2] + mv + [v * v for v in mv] + pq + [0]
+                    s = [x + y for x, y in zip(s, add)]
+                sums[b, i] = s
+    return {"votes": votes, "link": link, "sums": sums}
+
+
+def object_centre(sums):
+    """The centre of a gated round from the sums of a round: floor(sum m / n + 1/2) per axis in Python integers, int32 [...,3]; 0 where n = 0."""
+    s = np.asarray(sums, np.int64)
+    out = np.zeros(s.shape[:-1] + (3,), np.int32)
+    for at in np.ndindex(*s.shape[:-1]):
+        n = int(s[at][0])
+        if n > 0:
+            out[at] = [(2 * int(s[at][6 + a]) + n) // (2 * n) for a in range(3)]
+    return out
+
+
+def object_motion(sums, link=None, dt=1.0):
+    """What the sums of object_links say per box of frame k - 1, in the current camera's axes: {"motion": float64 [...,3] = sum m / n / 1024 /
+    dt - metres per frame for dt = 1, metres per second for the frames' distance in seconds; the object's own motion, because Xc already
+    carries the camera's -, "position": float64 [...,3] = sum p / n / 1024, the mean of the box's points in frame k, "n": int64 [...]}.  NaN
+    where n = 0, or where `link` is given and says -1."""
+    s = np.asarray(sums, np.int64)
+    n = s[..., 0].copy()
+    if link is not None:
+        n = np.where(np.asarray(link)[..., 0] >= 0, n, 0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        den = np.where(n > 0, n, 1).astype(np.float64)[..., None]
+        motion = np.where(n[..., None] > 0, s[..., 6:9].astype(np.float64) / den / 1024.0 / float(dt), np.nan)
+        position = np.where(n[..., None] > 0, s[..., 12:15].astype(np.float64) / den / 1024.0, np.nan)
+    return {"motion": motion, "position": position, "n": n}
+
+
+def object_links_rounds(links_of, gate_m):
+    """flow_egomotion's idiom for a gate: a round without one, then - for gate_m > 0 - a round gated about the first round's mean.
+    links_of(gate_m, centre) -> object_links' dict, from the numpy definition or from the device; -> the last round's dict, with
+    "centre" int32 [B,M,3] (None for gate_m = 0)."""
+    got = dict(links_of(0, None))
+    got["centre"] = None
+    if gate_m > 0:
+        centre = object_centre(np.asarray(got["sums"].cpu().numpy() if hasattr(got["sums"], "cpu") else got["sums"]))
+        got = dict(links_of(int(gate_m), centre))
+        got["centre"] = centre
+    return got
+
+
+class ObjectTracks:
+    """Host bookkeeping over object_links' results, in plain Python - the role of the reference's tracker: a track keeps its id along
+    links, an unlinked current box opens a new id (in ascending j), a track without a link ends.  Per track the last `history` motions
+    (those with n >= min_n), their mean, the velocity = mean / dt in m/s, moving = |velocity| > move_m, and predicted = pos + mean: the
+    constant-velocity prediction of where the box is a frame later, in the current camera's axes."""
+
+    def __init__(self, history=5, min_n=8, move_m=1.0, dt=0.1):
+        if int(history) < 1 or not float(dt) > 0:
+            raise ValueError("history must be >= 1 and dt > 0, got %r and %r" % (history, dt))
+        self.history, self.min_n, self.move_m, self.dt = int(history), int(min_n), float(move_m), float(dt)
+        self.frame, self.next_id, self.tracks = -1, 0, []  # tracks: one per box of the last frame, in box order
+
+    def _open(self, box, pos):
+        t = {"id": self.next_id, "box": tuple(int(v) for v in box), "pos": tuple(float(v) for v in pos), "motions": [], "n": 0}
+        self.next_id += 1
+        return self._derive(t)
+
+    def _derive(self, t):
+        if t["motions"]:
+            mean = tuple(sum(m[a] for m in t["motions"]) / len(t["motions"]) for a in range(3))
+        else:
+            mean = (float("nan"),) * 3
+        t["mean"] = mean
+        t["velocity"] = tuple(v / self.dt for v in mean)
+        speed = sum(v * v for v in t["velocity"]) ** 0.5
+        t["moving"] = bool(speed > self.move_m)  # False for NaN
+        t["predicted"] = tuple(p + (0.0 if v != v else v) for p, v in zip(t["pos"], mean))
+        return t
+
+    def start(self, boxes, positions):
+        """The first frame: every box opens a track.  boxes [n,4], positions [n,3] -> the tracks."""
+        self.frame, self.tracks = self.frame + 1, [self._open(bx, ps) for bx, ps in zip(boxes, positions)]
+        return self.tracks
+
+    def step(self, link, motion, n, boxes, positions):
+        """One pair: link [n_prev] = the current box of each box of the last frame or -1 (object_links' link[..., 0]), motion [n_prev,3] in
+        metres per frame and n [n_prev] (object_motion's), boxes [n_cur,4] and positions [n_cur,3] of the current frame -> its tracks."""
+        if self.frame < 0:
+            raise ValueError("step() before start()")
+        if len(link) < len(self.tracks):
+            raise ValueError("link has %d rows for %d tracks" % (len(link), len(self.tracks)))
+        new = [None] * len(boxes)
+        for i, old in enumerate(self.tracks):
+            j = int(link[i])
+            if j < 0 or j >= len(boxes) or new[j] is not None:
+                continue  # the track ends
+            mv = tuple(float(v) for v in motion[i])
+            motions = list(old["motions"])
+            if int(n[i]) >= self.min_n and all(v == v for v in mv):
+                motions = (motions + [mv])[-self.history:]
+            new[j] = self._derive({"id": old["id"], "box": tuple(int(v) for v in boxes[j]), "pos": tuple(float(v) for v in positions[j]), "motions": motions,
+                                   "n": int(n[i])})
+        for j in range(len(boxes)):
+            if new[j] is None:
+                new[j] = self._open(boxes[j], positions[j])
+        self.frame, self.tracks = self.frame + 1, new
+        return self.tracks
+
+    def feed(self, tracked):
+        """A batch as StereoRig.track returns it (numpy): {"boxes" [F,M,4], "n" [F], "positions" [F,M,3], "link" [F-1,M,4], "motion" [F-1,M,3],
+        "count" [F-1,M]}.  The first frame of a batch that is not the first one fed is the last frame of the batch before it and is not
+        counted again.  -> per frame that was new, (frame, a copy of its tracks)."""
+        out = []
+        boxes, n, pos = np.asarray(tracked["boxes"]), np.asarray(tracked["n"]), np.asarray(tracked["positions"])
+        if self.frame < 0 and len(boxes):
+            out.append((0, [dict(t) for t in self.start(boxes[0][:n[0]], pos[0][:n[0]])]))
+        for k in range(1, len(boxes)):
+            link = np.asarray(tracked["link"])[k - 1][:n[k - 1], 0]
+            tr = self.step(link, np.asarray(tracked["motion"])[k - 1], np.asarray(tracked["count"])[k - 1], boxes[k][:n[k]], pos[k][:n[k]])
+            out.append((self.frame, [dict(t) for t in tr]))
+        return out
+
+    def lines(self, frame, tracks):
+        """'frame id x y w h X Y Z vx vy vz n moving' per track: what --tracks writes; floats by repr."""
+        return ["%d %d %d %d %d %d %r %r %r %r %r %r %d %d" % ((frame, t["id"]) + t["box"] + t["pos"] + t["velocity"] + (t["n"], int(t["moving"]))) for t in tracks]
+
+
 GROUND_BINS_MIN, GROUND_BINS_MAX = 8, 4096
 GROUND_VH_MIN, GROUND_TOL_MAX, GROUND_G_TOL_MAX, GROUND_HEIGHT_MAX = -32768, 16, 4096, 32768
 GROUND_LABELS = {"invalid": 0, "ground": 1, "obstacle": 2, "below": 3}
@@ -4719,6 +5052,12 @@ def main(argv=None):
                              "The chained poses are written to FILE, one line 'x y yaw' per frame as --poses reads them, frame 0 at the "
                              "origin, and the motions to <FILE>.rel.txt, twelve words per pair of frames: the rotation row by row, then "
                              "the translation, previous camera to current camera.  Without --poses the run takes FILE as its --poses")
+    parser.add_argument("--tracks", type=str, default="", metavar="FILE",
+                        help="with --batch and --odometry: the objects of every frame (StereoRig.objects' boxes) linked to those of the frame "
+                             "before it by the odometry's matches and followed through the folder (StereoRig.track on the odometry's batches, "
+                             "ObjectTracks at 10 frames a second); writes one line per frame and track to FILE: 'frame id x y w h X Y Z vx vy vz "
+                             "n moving' - the box in pixels, its position in metres and its own velocity in m/s in the camera's axes (nan "
+                             "until a motion is known), the matches behind the last motion, and whether it moves")
     parser.add_argument("--temporal", type=str, default="", metavar="DIR[,TOL_PX[,MODE]]",
                         help="with --batch and --odometry: every frame's disparity map compared with the map of the frame before it, warped "
                              "under the fitted motion (StereoRig.temporal, on the odometry's batches: the front end and engine run once "
@@ -4755,6 +5094,8 @@ def main(argv=None):
         parser.error("--odometry needs --batch")
     if args.odometry and not args.poses and (args.occupancy_map or args.voxel_map):
         args.poses = args.odometry  # written below, before anything reads it
+    if args.tracks and (not args.batch or not args.odometry):
+        parser.error("--tracks needs --batch and --odometry")
     args.temporal_spec = None
     if args.temporal:
         if not args.batch or not args.odometry:
@@ -5168,6 +5509,7 @@ def _run_odometry(args, ldir, rdir, files):
     from ..rig import StereoRig
     rig = StereoRig(1242 // args.scale, 375 // args.scale, calibration=args.camera_calibration, rectify=args.rectify, scale=args.scale)
     rel, ok = [], []
+    tracks, track_lines = ObjectTracks(), []
     try:
         for i in range(0, len(files), args.batch):
             names = files[max(i - 1, 0):i + args.batch]
@@ -5176,7 +5518,12 @@ def _run_odometry(args, ldir, rdir, files):
                 lr = [(r, l) for l, r in lr]
             left = torch.from_numpy(np.stack([l for l, _ in lr])).cuda(rig.device)
             right = torch.from_numpy(np.stack([r for _, r in lr])).cuda(rig.device)
-            got = rig.odometry(left, right, pixel_format="bgr", first=rel[-1] if rel and ok[-1] else None)
+            first = rel[-1] if rel and ok[-1] else None
+            got = rig.odometry(left, right, pixel_format="bgr", first=first)
+            if args.tracks and len(names) > 1:  # the same odometry once more, with the boxes: the batch's first frame is the last one's last
+                tracked = rig.track(left, right, pixel_format="bgr", first=first)
+                for frame, rows in tracks.feed({k: v.cpu().numpy() if hasattr(v, "cpu") else v for k, v in tracked.items() if k != "matches"}):
+                    track_lines += tracks.lines(frame, rows)
             rel.extend(got["rel"])
             ok.extend(got["ok"])
             if args.temporal_spec is not None and len(names) > 1:
@@ -5189,6 +5536,10 @@ def _run_odometry(args, ldir, rdir, files):
     with open(args.odometry + ".rel.txt", "w") as f:
         f.write("".join(" ".join(repr(float(v)) for v in row) + "\n" for row in rel))
     print("odometry: %d frames, %d of %d motions fitted, written to %s" % (len(files), int(np.sum(ok)), len(ok), args.odometry))
+    if args.tracks:
+        with open(args.tracks, "w") as f:
+            f.write("".join(line + "\n" for line in track_lines))
+        print("tracks: %d ids over %d frames, %d lines written to %s" % (tracks.next_id, tracks.frame + 1, len(track_lines), args.tracks))
 
 
 def _run_batched(args, ldir, rdir, files):
