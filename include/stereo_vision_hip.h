@@ -112,6 +112,12 @@
  *      motion that remains once the camera's is taken out.  stereo_vision.sv.object_links states the definition in numpy; object_motion
  *      and ObjectTracks are the metres and the bookkeeping of ids, velocities and predictions on the host.
  *
+ *  (AC) Beside (Q) and behind (L): place recognition (sv_place_*) - a frame of rows reduced to a polar height image around the vehicle,
+ *      rings x sectors bytes that a turn of the vehicle rolls along the sectors (AC1), and query descriptors searched among stored ones
+ *      under every roll, the best key per query by the least sum of absolute differences over the sum of both descriptors (AC2).
+ *      stereo_vision.sv.place_descriptor and place_match state the definitions in numpy; place_yaw and place_guess turn a key and a
+ *      shift into the guess the voxel map's localisation takes.  What to do with a confirmed loop stays with the caller.
+ *
  * All sv_* functions return SV_OK (0) or a negative sv_status; sv_last_error() gives the text.
  * Nothing in this library calls exit().
  */
@@ -1953,6 +1959,82 @@ int sv_object_links_device(const int32_t *matches, const int32_t *counts, const 
  * sums, 2 the links too, 3 the votes too -, and what they would have written is then undefined.  0 is the default.  Returns SV_OK, or
  * SV_ERR_ARG for a value outside 0 .. 3. */
 int sv_debug_object_links(int flags);
+
+/* ---- (AC) place recognition: frames of rows -> polar height descriptors; queries x keys x rolls -> the best key and its shift ---- */
+
+/* The words of a descriptor: rows within r_max (metres, finite, > 0) of the vehicle on both axes, z_lo <= z < z_hi, and at least r_min (0
+ * <= r_min < r_max) away; rings in 1 .. 64; sectors a multiple of 4 in 8 .. 128; rings * sectors <= 4096.  reserved: 0.  With them, in
+ * double: unit = r_max / 1024, z_unit = (z_hi - z_lo) / 255, ring_edge2[r] = (1024 r / rings)^2 (integer division), r_min2 = floor(r_min /
+ * unit)^2. */
+typedef struct {
+    double r_max, z_lo, z_hi, r_min;
+    int32_t rings, sectors;
+    int32_t reserved[10];
+} sv_place_spec;
+
+/* (AC1) xyz float [batch][capacity][3] (dtype SV_CLOUD_F32) or double (SV_CLOUD_F64) in the vehicle's axes - x forward, y left, z up -, n
+ * int32 [batch][capacity] or NULL (every weight 1), counts int32 [batch]: the rows (Q)'s insert takes - frame b has its first min(counts[b],
+ * capacity) rows, none for counts[b] <= 0.  poses double [batch][12] or NULL: applied to a row first, by the insert's transform, ((R[k][0] x
+ * + R[k][1] y) + R[k][2] z) + t[k] in double and in that order; with the world-to-vehicle words of a pose (stereo_vision.sv.voxel_render_cams
+ * makes them) a descriptor is taken from a map's rows around any pose.  dirs int32 [sectors][2] = (rint(2^14 cos(2 pi k / sectors)),
+ * rint(2^14 sin(2 pi k / sectors))): made on the host (stereo_vision.sv.place_params), the device computes no trigonometric function.
+ *   kept      n >= 1; x, y, z finite; |x| < r_max and |y| < r_max; z_lo <= z < z_hi; and with qx = (int)floor(x / unit), qy likewise, d2 =
+ *             qx^2 + qy^2: r_min2 <= d2 < 1024^2 and (qx, qy) != (0, 0).  Doubles, one operation at a time, each division one division.
+ *   ring      the largest r with ring_edge2[r] <= d2.
+ *   sector    the one k with cross(dir[k], q) >= 0 and cross(dir[(k + 1) % sectors], q) < 0, cross(a, b) = a.x b.y - a.y b.x.
+ *   code      1 + min(254, (int)floor((z - z_lo) / z_unit)).
+ * desc uint8 [batch][rings][sectors]: per bin the largest code, 0 for an empty bin.  ring uint8 [batch][rings]: the occupied sectors per
+ * ring.  words int32 [batch][4] = (the sum of the codes, the occupied bins, the kept rows, the dropped rows of the frame's rows).
+ * stereo_vision.sv.place_descriptor restates this in numpy. */
+
+/* Host only: the bytes of the workspace sv_place_descriptor_device needs: 4 (4 + rings * sectors) per frame.  SV_ERR_ARG (bytes
+ * untouched) for a NULL bytes, batch outside 0..65535, rings or sectors outside what sv_place_spec admits. */
+int sv_place_descriptor_workspace(int batch, int rings, int sectors, size_t *bytes);
+/* Enqueued on `stream` (a hipStream_t, NULL = the default stream) as three kernels - the workspace cleared; a lane per row: the maxima of
+ * a chunk of 4096 rows in LDS, flushed by integer atomic maxima; a workgroup per frame: bytes, ring counts, words - and not waited for:
+ * nothing is allocated, no host synchronisation is made, no float atomic is issued, nothing is assumed of what the outputs or the
+ * workspace held before, and every output is written in full.  All pointers device; xyz (double) and poses 8-byte, everything else 4-byte
+ * aligned, ring 1-byte.  Returns SV_OK (nothing enqueued for batch == 0), SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued, the outputs
+ * untouched, the text in sv_last_error(NULL) - for batch outside 0..65535, capacity outside 0..2^24, a dtype that is neither, a NULL spec or
+ * a bad word of it; with batch > 0 a NULL counts, dirs, desc, ring, words or workspace, a NULL xyz beside a capacity > 0; a misaligned
+ * pointer; too small a workspace; an output or the workspace that shares bytes with an input or with another output. */
+int sv_place_descriptor_device(const void *xyz, int dtype, const int32_t *n, const int32_t *counts, const double *poses, int batch, int capacity,
+                               const int32_t *dirs, const sv_place_spec *spec, uint8_t *desc, uint8_t *ring, int32_t *words, void *workspace,
+                               size_t workspace_bytes, void *stream);
+
+/* (AC2) q_desc uint8 [queries][rings][sectors], q_words int32 [queries][4], q_ring uint8 [queries][rings]: (AC1)'s; q_seq int32 [queries]: the
+ * queries' sequence numbers.  k_desc, k_words, k_ring, k_seq: the same of the keys.  rings and sectors as in sv_place_spec; min_gap >= 0;
+ * ring_gate >= -1; max_shift in 0 .. 128, or -1: every shift; accept in 0 .. 2^20.
+ *   candidate key k is one of query q iff both sums (words[0]) are > 0 and |q_seq - k_seq| >= min_gap, and, unless ring_gate < 0, sum_r
+ *             |q_ring[r] - k_ring[r]| <= ring_gate: a turn of the vehicle does not change a ring's count.
+ *   pair      sad(s) = sum_{r,c} |q[r][c] - k[r][(c + s) % sectors]| for s in 0 .. sectors - 1 with min(s, sectors - s) <= max_shift; the
+ *             pair's result is the least sad, among equals the least s; norm = q_sum + k_sum.  A query that stands where the key stood,
+ *             turned by 2 pi s / sectors to the left, has shift s.
+ *   best      the candidate with the least sad / norm, by sad_a norm_b < sad_b norm_a in 64 bits, among equals the least k; accepted
+ *             iff 256 sad <= accept norm.
+ * best int32 [queries][4] = (k, or -1 where nothing is accepted; the shift, sad and norm of the best candidate even where it is refused);
+ * (-1, 0, -1, 0) without a candidate.  counts int32 [queries][3] = (the keys that pass the sums and the gap, those that also pass the gate,
+ * accepted ? 1 : 0).  pair int32 [queries][keys][2] or NULL = (sad, shift) per candidate, (-1, 0) for any other key.
+ * stereo_vision.sv.place_match restates this in numpy. */
+
+/* Host only: the bytes of the workspace sv_place_match_device needs: 32 per query and group of 64 keys.  SV_ERR_ARG (bytes untouched) for a
+ * NULL bytes, queries outside 0..65535, keys outside 0..2^20. */
+int sv_place_match_workspace(int queries, int keys, size_t *bytes);
+/* Enqueued on `stream` as two kernels - per query and group of 64 keys the tests, then a wavefront per candidate with a lane per shift,
+ * four bytes per v_sad_u8, and the group's best as a partial; a workgroup per query: the best of the partials - and not waited for:
+ * nothing is allocated, no host synchronisation is made, no atomic touches a result, nothing is assumed of what the outputs or the
+ * workspace held before, and every output is written in full.  All pointers device; the descriptors, words, sequence numbers, outputs and
+ * the workspace 4-byte aligned.  Returns SV_OK (nothing enqueued for queries == 0; for keys == 0 every query gets "no candidate"),
+ * SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued, the outputs untouched, the text in sv_last_error(NULL) - for what the workspace call
+ * refuses; a bad rings, sectors, min_gap, ring_gate, max_shift or accept; with queries > 0 a NULL q_desc, q_words, q_ring, q_seq, best or
+ * counts, and with keys > 0 too a NULL k_desc, k_words, k_ring, k_seq or workspace; a misaligned pointer; too small a workspace; an output
+ * or the workspace that shares bytes with an input or with another output. */
+int sv_place_match_device(const uint8_t *q_desc, const int32_t *q_words, const uint8_t *q_ring, const int32_t *q_seq, int queries, const uint8_t *k_desc,
+                          const int32_t *k_words, const uint8_t *k_ring, const int32_t *k_seq, int keys, int rings, int sectors, int min_gap, int ring_gate,
+                          int max_shift, int accept, int32_t *best, int32_t *counts, int32_t *pair, void *workspace, size_t workspace_bytes, void *stream);
+/* Measurement hook for the search above, process-wide: flags = 1 takes one key per pass of a wavefront instead of four - the same
+ * results, for timing only.  0 is the default.  Returns SV_OK, or SV_ERR_ARG for a value outside 0 .. 1. */
+int sv_debug_place(int flags);
 
 /* ---- (A)the reference's exported symbols ------------------------------------------------------------- */
 

@@ -1,4 +1,4 @@
-// What the stage entries of groups (D) to (AB) of include/stereo_vision_hip.h share on the host (top_view.cpp ... track.cpp): the
+// What the stage entries of groups (D) to (AC) of include/stereo_vision_hip.h share on the host (top_view.cpp ... place.cpp): the
 // refusal of a bad call, the checks that several groups state in the same words, and the set-up of sv::ReprojectArgs.  Host code only:
 // no .hip file includes it.
 #pragma once

@@ -148,14 +148,20 @@ __device__ __forceinline__ void vmap_load_row(const void *xyz, size_t o, double 
     }
 }
 
-// A row's way into the map on axis k: the world coordinate under `pose` (R row-major, then t) with every product and sum rounded on
-// its own, in this order (the build has -ffp-contract=off); the kept rule, which NaN and inf never pass, and-ed with `keep` and
+// A row's coordinate on axis k under `pose` (R row-major, then t): every product and sum rounded on its own, in this order (the build
+// has -ffp-contract=off).  The insert's transform; the place descriptor (place_kernels.hip) takes its rows through the same function.
+__device__ __forceinline__ double vmap_world(const double *pose, int k, double x, double y, double z) {
+    const double P = ((pose[3 * k] * x + pose[3 * k + 1] * y) + pose[3 * k + 2] * z) + pose[9 + k];
+    return P;
+}
+
+// A row's way into the map on axis k: the world coordinate under `pose`, by vmap_world; the kept rule, which NaN and inf never pass, and-ed with `keep` and
 // returned; t in cells from lo, by a real division, 0 for a row that is not kept; the cell c, clamped into the box.  A caller walks k =
 // 0, 1, 2 and hands each axis the `keep` of the one before, so a row that fails on an axis has t = 0 on the ones behind it.  `keep` goes
 // in and out by value: by reference the kernels' code came out different.  Args has the map's lo, hi, size and nc.
 template <class Args>
 __device__ __forceinline__ bool vmap_cell(const Args &a, const double *pose, int k, double x, double y, double z, bool keep, double &t, long long &c) {
-    const double P = ((pose[3 * k] * x + pose[3 * k + 1] * y) + pose[3 * k + 2] * z) + pose[9 + k];
+    const double P = vmap_world(pose, k, x, y, z);
     keep = keep && a.lo[k] < P && P < a.hi[k];  // false for NaN
     t = keep ? (P - a.lo[k]) / a.size : 0.0;
     c = (long long)t;

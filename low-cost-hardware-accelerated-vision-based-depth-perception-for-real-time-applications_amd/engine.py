@@ -580,6 +580,12 @@ class SvTrackSpec(ctypes.Structure):
                 ("share", ctypes.c_int32), ("gate_m", ctypes.c_int32), ("reserved", ctypes.c_int32 * 9)]
 
 
+class SvPlaceSpec(ctypes.Structure):
+    """sv_place_spec of include/stereo_vision_hip.h."""
+    _fields_ = [("r_max", ctypes.c_double), ("z_lo", ctypes.c_double), ("z_hi", ctypes.c_double), ("r_min", ctypes.c_double),
+                ("rings", ctypes.c_int32), ("sectors", ctypes.c_int32), ("reserved", ctypes.c_int32 * 10)]
+
+
 def _signatures():
     """The table below: per stage group of the C API, (D) to (S), its functions and per function (restype, argtypes), parameter by
     parameter as include/stereo_vision_hip.h declares them - tests/test_stage_signatures.py holds the two against each other."""
@@ -714,6 +720,13 @@ def _signatures():
             "sv_object_links_workspace": (ci, [ci, ci, P(sz)]),
             "sv_object_links_device": (ci, [vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, P(SvTrackSpec), vp, vp, vp, vp, sz, vp]),
             "sv_debug_object_links": (ci, [ci]),
+        },
+        "place": {  # (AC)
+            "sv_place_descriptor_workspace": (ci, [ci, ci, ci, P(sz)]),
+            "sv_place_descriptor_device": (ci, [vp, ci, vp, vp, vp, ci, ci, vp, P(SvPlaceSpec), vp, vp, vp, vp, sz, vp]),
+            "sv_place_match_workspace": (ci, [ci, ci, P(sz)]),
+            "sv_place_match_device": (ci, [vp, vp, vp, vp, ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, sz, vp]),
+            "sv_debug_place": (ci, [ci]),
         },
     }
 
@@ -3158,6 +3171,131 @@ def debug_object_links(stop=0):
     """sv_debug_object_links: stop = 1 .. 3 leaves the sums, the link and the votes kernel out, from the end - for timing by difference
     only: what they would have written is undefined.  0 is the default.  Process-wide; a measurement hook."""
     _check(track_lib().sv_debug_object_links(int(stop)), "sv_debug_object_links")
+
+
+def place_lib():
+    """The library with the signatures of group (AC) declared."""
+    return _bind("place")
+
+
+def place_spec(params):
+    """-> SvPlaceSpec from place_params' dict (stereo_vision.sv.place_params checks the words again: ValueError)."""
+    from .stereo_vision.sv import place_params
+    w = place_params(params["r_max"], params["rings"], params["sectors"], params["z_lo"], params["z_hi"], params["r_min"])
+    return SvPlaceSpec(w["r_max"], w["z_lo"], w["z_hi"], w["r_min"], w["rings"], w["sectors"])
+
+
+_place_dirs = {}  # (sectors, device) -> the sector table on the device: made once on the host
+
+
+def _place_outputs(res, wanted, dev):
+    """The tensors of `wanted` = ((name, dtype, shape), ...): new ones, or those of the dict `res` of an earlier call, checked."""
+    import torch
+    if res is None:
+        return {name: torch.empty(shape, dtype=dtype, device=dev) for name, dtype, shape in wanted}
+    for name, dtype, shape in wanted:
+        t = res.get(name)
+        if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.is_contiguous()):
+            raise ValueError("out[%r] must be a contiguous %s tensor %s on %s" % (name, str(dtype).replace("torch.", ""), list(shape), dev))
+    return res
+
+
+def place_descriptor(xyz, n, counts, params, poses=None, out=None, workspace=None):
+    """The polar height descriptors of B frames of rows - the definition of stereo_vision.sv.place_descriptor on the GPU, bit for bit
+    (sv_place_descriptor_device: three kernels, integer atomics only).  xyz CUDA float32 or float64 [B,cap,3], n int32 [B,cap] or None,
+    counts int32 [B]: the rows voxel_map_insert takes; params: place_params' dict; poses float64 [B,12] (numpy, or a tensor on the device) or
+    None.  out: the dict of an earlier call of the same shape to write into; workspace: an int32 tensor of B (4 + rings sectors) words to
+    use (None: torch's allocator).  -> {"desc": uint8 [B,R,S], "ring": uint8 [B,R], "words": int32 [B,4]}; for CUDA tensors enqueued on
+    torch's current stream, nothing is read back.  CPU tensors (or numpy arrays) run the numpy form and give numpy arrays."""
+    import torch
+    if not (isinstance(xyz, torch.Tensor) and xyz.is_cuda):
+        from .stereo_vision.sv import place_descriptor as on_host
+        as_np = lambda t: t.cpu().numpy() if isinstance(t, torch.Tensor) else t
+        return on_host(as_np(xyz), as_np(n), as_np(counts), params, as_np(poses))
+    spec = place_spec(params)
+    R, S, dev = spec.rings, spec.sectors, xyz.device
+    if not (xyz.dtype in (torch.float32, torch.float64) and xyz.dim() == 3 and xyz.shape[2] == 3):
+        raise ValueError("xyz must be a float32 or float64 tensor [B,cap,3]")
+    B, cap = int(xyz.shape[0]), int(xyz.shape[1])
+    for t, name, shape in ((n, "n", (B, cap)), (counts, "counts", (B,))):
+        if t is None and name != "counts":
+            continue
+        if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == torch.int32 and tuple(t.shape) == shape):
+            raise ValueError("%s must be an int32 tensor %s on the device of xyz" % (name, list(shape)))
+    p = None
+    if poses is not None:
+        p = poses if isinstance(poses, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(poses, np.float64)).to(dev)
+        if p.device != dev or p.dtype != torch.float64 or tuple(p.shape) != (B, 12):
+            raise ValueError("poses must be None or float64 [%d,12]" % B)
+        p = p.contiguous()
+    res = _place_outputs(out, (("desc", torch.uint8, (B, R, S)), ("ring", torch.uint8, (B, R)), ("words", torch.int32, (B, 4))), dev)
+    L = place_lib()
+    need = ctypes.c_size_t()
+    _check(L.sv_place_descriptor_workspace(B, R, S, ctypes.byref(need)), "sv_place_descriptor_workspace")
+    if B == 0:  # nothing to enqueue
+        return res
+    if (S, dev) not in _place_dirs:
+        from .stereo_vision.sv import place_params
+        _place_dirs[(S, dev)] = torch.from_numpy(place_params(1.0, 1, S)["dirs"]).to(dev)
+    dirs = _place_dirs[(S, dev)]
+    xyz, counts = xyz.contiguous(), counts.contiguous()
+    n = None if n is None else n.contiguous()
+    ws = workspace if workspace is not None else torch.empty((need.value // 4,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.sv_place_descriptor_device(_ptr(xyz), 0 if xyz.dtype == torch.float32 else 1, _ptr(n), counts.data_ptr(), None if p is None else p.data_ptr(), B, cap,
+                                          dirs.data_ptr(), ctypes.byref(spec), res["desc"].data_ptr(), res["ring"].data_ptr(), res["words"].data_ptr(), ws.data_ptr(),
+                                          ws.numel() * ws.element_size(), torch.cuda.current_stream(dev).cuda_stream)
+    _check(rc, "sv_place_descriptor_device")
+    return res  # ws goes back to torch's allocator, which hands it out again on this stream only: behind the kernels
+
+
+def place_match(q_desc, q_words, q_ring, q_seq, k_desc, k_words, k_ring, k_seq, min_gap, ring_gate=-1, max_shift=None, accept=256, want_pair=False, out=None,
+                workspace=None):
+    """Q query descriptors against K stored ones under every rotation - the definition of stereo_vision.sv.place_match on the GPU, bit
+    for bit (sv_place_match_device: two kernels, no atomics).  q_desc CUDA uint8 [Q,R,S], q_words int32 [Q,4], q_ring uint8 [Q,R], q_seq
+    int32 [Q] and the same of the K keys, on one device; min_gap, ring_gate, max_shift, accept, want_pair as there.  out: the dict of an
+    earlier call of the same shape to write into; workspace: an int32 tensor of 8 Q ceil(K / 64) words to use (None: torch's allocator).
+    -> {"best": int32 [Q,4], "counts": int32 [Q,3]} and with want_pair "pair": int32 [Q,K,2]; for CUDA tensors enqueued on torch's current
+    stream, nothing is read back.  CPU tensors (or numpy arrays) run the numpy form and give numpy arrays."""
+    import torch
+    from .stereo_vision import sv as _sv
+    if not (isinstance(q_desc, torch.Tensor) and q_desc.is_cuda):
+        as_np = lambda t: t.cpu().numpy() if isinstance(t, torch.Tensor) else t
+        return _sv.place_match(*[as_np(t) for t in (q_desc, q_words, q_ring, q_seq, k_desc, k_words, k_ring, k_seq)], min_gap, ring_gate, max_shift, accept, want_pair)
+    dev = q_desc.device
+    if not (q_desc.dtype == torch.uint8 and q_desc.dim() == 3 and isinstance(k_desc, torch.Tensor) and k_desc.device == dev and k_desc.dtype == torch.uint8
+            and k_desc.dim() == 3 and tuple(k_desc.shape[1:]) == tuple(q_desc.shape[1:])):
+        raise ValueError("q_desc and k_desc must be uint8 tensors [Q,R,S] and [K,R,S] on one device")
+    (Q, R, S), K = (int(v) for v in q_desc.shape), int(k_desc.shape[0])
+    ins = []
+    for t, name, dtype, shape in ((q_desc, "q_desc", torch.uint8, (Q, R, S)), (q_words, "q_words", torch.int32, (Q, 4)), (q_ring, "q_ring", torch.uint8, (Q, R)),
+                                  (q_seq, "q_seq", torch.int32, (Q,)), (k_desc, "k_desc", torch.uint8, (K, R, S)), (k_words, "k_words", torch.int32, (K, 4)),
+                                  (k_ring, "k_ring", torch.uint8, (K, R)), (k_seq, "k_seq", torch.int32, (K,))):
+        if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dtype and tuple(t.shape) == shape):
+            raise ValueError("%s must be a %s tensor %s on %s" % (name, str(dtype).replace("torch.", ""), list(shape), dev))
+        t = t.contiguous()
+        ins.append(t.clone() if t.data_ptr() % 4 and name.endswith("desc") else t)  # the C entry reads a descriptor by dwords
+    min_gap, ring_gate = _sv._place_int(min_gap, 0, 2 ** 31 - 1, "min_gap"), _sv._place_int(ring_gate, -1, 2 ** 31 - 1, "ring_gate")
+    max_shift = -1 if max_shift is None else _sv._place_int(max_shift, 0, _sv.PLACE_SECTORS_MAX, "max_shift")
+    accept = _sv._place_int(accept, 0, _sv.PLACE_ACCEPT_MAX, "accept")
+    wanted = (("best", torch.int32, (Q, 4)), ("counts", torch.int32, (Q, 3))) + ((("pair", torch.int32, (Q, K, 2)),) if want_pair else ())
+    res = _place_outputs(out, wanted, dev)
+    L = place_lib()
+    need = ctypes.c_size_t()
+    _check(L.sv_place_match_workspace(Q, K, ctypes.byref(need)), "sv_place_match_workspace")
+    ws = workspace if workspace is not None else torch.empty((max(need.value // 4, 1),), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.sv_place_match_device(*[_ptr(t) for t in ins[:4]], Q, *[_ptr(t) for t in ins[4:]], K, R, S, min_gap, ring_gate, max_shift, accept, _ptr(res["best"]),
+                                     _ptr(res["counts"]), _ptr(res["pair"]) if want_pair else None, ws.data_ptr(), ws.numel() * ws.element_size(),
+                                     torch.cuda.current_stream(dev).cuda_stream)
+    _check(rc, "sv_place_match_device")
+    return res  # ws goes back to torch's allocator, which hands it out again on this stream only: behind the kernels
+
+
+def debug_place(one_key=0):
+    """sv_debug_place: one_key = 1 lets a wavefront of the search take one key per pass instead of four - the same results, for timing
+    only.  0 is the default.  Process-wide; a measurement hook."""
+    _check(place_lib().sv_debug_place(int(one_key)), "sv_debug_place")
 
 
 def host_support_filter(params, dcan, width, height, threads=0, lattice=False):

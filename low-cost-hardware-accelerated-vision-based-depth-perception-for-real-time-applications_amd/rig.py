@@ -40,7 +40,7 @@ import ctypes
 
 import numpy as np
 
-from .engine import disparity_warp, flow_egomotion, flow_match, object_links
+from .engine import disparity_warp, flow_egomotion, flow_match, object_links, place_descriptor, place_match
 from .engine import (SvParams, StereoEngine, StereoError, box_positions_from_disparity, box_spec, cloud_spec, compact_cloud_from_disparity,
                      ground_from_disparity, ground_spec, lib, occupancy_from_disparity, occupancy_fuse, occupancy_match, occupancy_clearance, clearance_paths, cost_cells, cost_routes, frontier_cells, frontier_clusters, occupancy_cost_to_goal, occupancy_view, occupancy_spec, pinned_array, reproject, split_clouds, stixel_spec, stixels_from_disparity,
                      top_view_from_disparity, top_view_spec, split_voxel_clouds, voxel_cloud_from_disparity, voxel_map_align, voxel_map_carry, voxel_map_clear, voxel_map_insert, voxel_map_match, voxel_map_new,
@@ -595,6 +595,11 @@ class StereoRig:
         the caller's odometry."""
         return VoxelMap(lo, hi, size, capacity, device=self.device)
 
+    def place_index(self, r_max, capacity=1024, **words):
+        """-> PlaceIndex: a database of places on the rig's device, to be fed with the voxel rows of keyframes and their poses; words:
+        stereo_vision.sv.place_params' rings, sectors, z_lo, z_hi and r_min."""
+        return PlaceIndex(_sv.place_params(r_max, **words), capacity, device=self.device)
+
     def render_camera(self, size, footprint=1.0):
         """-> the camera VoxelMap.render draws into, from the rig's own Q, width and height and the map's voxel size
         (stereo_vision.sv.voxel_render_camera): `m.render(poses, rig.render_camera(m.params["size"]), transform=..., measured=d1)` is
@@ -990,6 +995,101 @@ class VoxelMap:
             raise RuntimeError("the voxel map overflowed its capacity of %d voxels: raise it" % self.params["capacity"])
         _sv.write_ply(path, res["xyz"].cpu().numpy(), res["color"].cpu().numpy())
         return res["count"]
+
+
+class PlaceIndex:
+    """A growing database of places (include/stereo_vision_hip.h (AC), stereo_vision.sv.place_descriptor / place_match): per keyframe its
+    polar height descriptor, ring key, words, sequence number and pose, on `device` - a CUDA device ("cuda", "cuda:1", an index):
+    engine.place_descriptor and engine.place_match -, or "cpu": the numpy definitions on CPU tensors, the same methods and the same bits.
+    params: stereo_vision.sv.place_params' dict; capacity: the keyframes the tensors hold at first - add() doubles it by one copy when it
+    runs out.  count is the number of keyframes; desc, ring, words, seq and poses are the tensors, of which the first count rows are
+    used.  What to do with a confirmed loop stays with the caller: guess() gives the start VoxelMap.localize, then .align, refine."""
+
+    def __init__(self, params, capacity, device="cuda"):
+        import torch
+        self.params = _sv.place_params(params["r_max"], params["rings"], params["sectors"], params["z_lo"], params["z_hi"], params["r_min"])
+        if isinstance(capacity, bool) or int(capacity) != capacity or not 1 <= capacity <= _sv.PLACE_KEYS_MAX:
+            raise ValueError("capacity must be an integer in 1 .. 2^20, got %r" % (capacity,))
+        self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.count = 0
+        self._pose_host = np.zeros((0, 12))  # the poses once more, on the host: guess() reads back the best keys only
+        self._allocate(int(capacity))
+
+    _FIELDS = ("desc", "ring", "words", "seq", "poses")
+
+    def _allocate(self, capacity):
+        import torch
+        R, S = self.params["rings"], self.params["sectors"]
+        old = [getattr(self, f, None) for f in self._FIELDS]
+        self.desc = torch.zeros((capacity, R, S), dtype=torch.uint8, device=self.device)
+        self.ring = torch.zeros((capacity, R), dtype=torch.uint8, device=self.device)
+        self.words = torch.zeros((capacity, 4), dtype=torch.int32, device=self.device)
+        self.seq = torch.zeros((capacity,), dtype=torch.int32, device=self.device)
+        self.poses = torch.zeros((capacity, 12), dtype=torch.float64, device=self.device)
+        for f, t in zip(self._FIELDS, old):
+            if t is not None:
+                getattr(self, f)[:self.count].copy_(t[:self.count])
+        self.capacity = capacity
+
+    def _on_device(self, t, dtype):
+        import torch
+        t = t if isinstance(t, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(t))
+        return t.to(device=self.device, dtype=dtype)
+
+    def _seq(self, seq, B):
+        s = np.asarray(seq, np.int64)
+        s = s + np.arange(B) if s.ndim == 0 else s
+        if s.shape != (B,) or (s < 0).any() or (s > 2 ** 31 - 1).any():
+            raise ValueError("seq must be an integer - the first frame's, the others count on - or [%d] of them in 0 .. 2^31 - 1" % B)
+        return s.astype(np.int32)
+
+    def descriptor(self, xyz, n, counts, poses=None):
+        """The descriptors of B frames of rows - xyz [B,cap,3], n [B,cap] or None, counts [B], as VoxelMap.update takes them, under poses
+        [B,12] or None -> {"desc" uint8 [B,R,S], "ring" uint8 [B,R], "words" int32 [B,4]}: tensors on the index's device.  Not waited for."""
+        import torch
+        res = place_descriptor(xyz, n, counts, self.params, poses)
+        return {k: v if isinstance(v, torch.Tensor) else torch.from_numpy(v) for k, v in res.items()}
+
+    def add(self, desc_result, seq, poses):
+        """Stores B keyframes: desc_result as descriptor() returns it, seq their sequence numbers ([B], or the first one's), poses float64
+        [B,12]: where the vehicle stood (stereo_vision.sv.voxel_map_pose's layout; numpy).  Not waited for."""
+        B = int(desc_result["desc"].shape[0])
+        p = np.ascontiguousarray(poses, np.float64)
+        if p.shape != (B, 12):
+            raise ValueError("poses must be float64 [%d,12], got %s" % (B, p.shape))
+        s = self._seq(seq, B)
+        if self.count + B > _sv.PLACE_KEYS_MAX:
+            raise ValueError("an index holds at most 2^20 keyframes")
+        if self.count + B > self.capacity:
+            self._allocate(min(_sv.PLACE_KEYS_MAX, max(2 * self.capacity, self.count + B)))
+        at = slice(self.count, self.count + B)
+        self.desc[at], self.ring[at], self.words[at] = (self._on_device(desc_result[k], d) for k, d in (("desc", self.desc.dtype), ("ring", self.ring.dtype), ("words", self.words.dtype)))
+        self.seq[at], self.poses[at] = self._on_device(s, self.seq.dtype), self._on_device(p, self.poses.dtype)
+        self._pose_host = np.concatenate([self._pose_host, p])
+        self.count += B
+
+    def query(self, desc_result, seq, min_gap, ring_gate=-1, max_shift=None, accept=256, want_pair=False):
+        """The best keyframe per query (stereo_vision.sv.place_match): desc_result as descriptor() returns it, seq the queries' sequence
+        numbers; a keyframe is a candidate if its sequence number is at least min_gap away.  -> {"best" int32 [Q,4] = (key or -1, shift,
+        sad, norm), "counts" int32 [Q,3], and with want_pair "pair" int32 [Q,count,2]}: tensors on the index's device.  Not waited for."""
+        import torch
+        Q, n = int(desc_result["desc"].shape[0]), self.count
+        q = [self._on_device(desc_result[k], d) for k, d in (("desc", self.desc.dtype), ("words", self.words.dtype), ("ring", self.ring.dtype))]
+        res = place_match(q[0], q[1], q[2], self._on_device(self._seq(seq, Q), self.seq.dtype), self.desc[:n], self.words[:n], self.ring[:n], self.seq[:n], min_gap,
+                          ring_gate, max_shift, accept, want_pair)
+        return {k: v if isinstance(v, torch.Tensor) else torch.from_numpy(v) for k, v in res.items()}
+
+    def guess(self, result):
+        """query()'s result -> (ok bool [Q], xyzyaw float64 [Q,4]): per accepted query the start VoxelMap.localize takes - the key's
+        position with its heading turned by the shift (stereo_vision.sv.place_guess) -, NaN where nothing was accepted.  Reads back the
+        Q x 4 words of best."""
+        best = result["best"].cpu().numpy()
+        ok = best[:, 0] >= 0
+        out = np.full((len(best), 4), np.nan)
+        out[ok] = _sv.place_guess(self._pose_host[best[ok, 0]], best[ok, 1], self.params["sectors"])
+        return ok, out
 
 
 class OccupancyMap:

@@ -610,6 +610,15 @@ def voxel_map_state(params):
             "m": np.zeros(0, np.int64), "first_seq": np.zeros(0, np.int64), "last_seq": np.zeros(0, np.int64), "dropped": 0, "overflowed": False}
 
 
+def _voxel_map_world(xyz, poses):
+    """float64 [B,cap,3]: the rows xyz [B,cap,3], widened exactly to double, under the poses [B,12] - Pw[k] = ((R[k,0] x + R[k,1] y) +
+    R[k,2] z) + t[k], in double and in that order: the insert's transform, which place_descriptor shares.  The caller holds np.errstate."""
+    R = poses[:, None, :]
+    P = xyz.astype(np.float64)
+    x, y, z = P[..., 0], P[..., 1], P[..., 2]
+    return np.stack([((R[..., 3 * k] * x + R[..., 3 * k + 1] * y) + R[..., 3 * k + 2] * z) + R[..., 9 + k] for k in range(3)], -1)
+
+
 def voxel_map_insert(map_state, xyz, color, n, counts, poses, seq0=0):
     """Adds B frames of rows to a world-fixed voxel map, the definition of include/stereo_vision_hip.h (Q) in numpy; map_state
     (voxel_map_state's dict) is changed in place and returned.
@@ -640,11 +649,8 @@ def voxel_map_insert(map_state, xyz, color, n, counts, poses, seq0=0):
     if isinstance(seq0, bool) or int(seq0) != seq0 or seq0 < 0 or seq0 + B - 1 > VOXEL_MAP_SEQ_MAX:
         raise ValueError("the sequence numbers seq0 .. seq0 + B - 1 must stay in 0 .. 2^31 - 2, got seq0 = %r" % (seq0,))
     rows = np.arange(cap)[None, :] < np.minimum(counts.astype(np.int64), cap)[:, None]  # [B,cap]: the rows a frame contributes
-    R = poses[:, None, :]
     with np.errstate(invalid="ignore", over="ignore"):  # rows beyond counts may hold anything
-        P = xyz.astype(np.float64)
-        x, y, z = P[..., 0], P[..., 1], P[..., 2]
-        Pw = np.stack([((R[..., 3 * k] * x + R[..., 3 * k + 1] * y) + R[..., 3 * k + 2] * z) + R[..., 9 + k] for k in range(3)], -1)
+        Pw = _voxel_map_world(xyz, poses)
         inside = ((lo < Pw) & (Pw < hi)).all(-1)
     wt = np.ones((B, cap), np.int64) if n is None else np.asarray(n).astype(np.int64)
     keep = rows & inside & (wt > 0)
@@ -3449,6 +3455,268 @@ class ObjectTracks:
         return ["%d %d %d %d %d %d %r %r %r %r %r %r %d %d" % ((frame, t["id"]) + t["box"] + t["pos"] + t["velocity"] + (t["n"], int(t["moving"]))) for t in tracks]
 
 
+PLACE_RINGS_MAX = 64         # rings of a descriptor at most: a ring key is 64 bytes
+PLACE_SECTORS_MIN, PLACE_SECTORS_MAX = 8, 128  # sectors: a multiple of 4 - four bytes per v_sad_u8 -, two shifts per lane at most
+PLACE_BINS_MAX = 4096        # rings * sectors at most: 255 * 4096 < 2^20, so (sad << 8) | shift fits 32 bits
+PLACE_Q = 1024               # a row's x and y in units of r_max / 1024
+PLACE_DIR = 2 ** 14          # the length of a sector's direction
+PLACE_QUERIES_MAX = 65535
+PLACE_KEYS_MAX = 2 ** 20
+PLACE_BATCH_MAX = 65535
+PLACE_ACCEPT_MAX = 2 ** 20   # accept at most: 256 sad <= accept norm, 256 = every candidate (sad <= norm)
+PLACE_WORDS = ("sum", "occupied", "kept", "dropped")  # the four words of a descriptor
+PLACE_NONE = (-1, 0, -1, 0)  # best of a query without a candidate
+
+
+def _place_int(v, lo, hi, what):
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+        raise ValueError("%s must be an integer in %d .. %d, got %r" % (what, lo, hi, v))
+    return int(v)
+
+
+def place_params(r_max, rings=20, sectors=60, z_lo=-0.5, z_hi=4.5, r_min=0.0):
+    """The words of place recognition (sv_place_spec) as a dict, after the checks the C entry makes (ValueError): r_max finite > 0, z_lo <
+    z_hi finite, 0 <= r_min < r_max, rings in 1 .. 64, sectors a multiple of 4 in 8 .. 128, rings * sectors <= 4096.  With them unit =
+    r_max / 1024 and z_unit = (z_hi - z_lo) / 255 in double, ring_edge2 int64 [rings + 1] = (1024 r // rings)^2, r_min2 = floor(r_min /
+    unit)^2, and dirs int32 [sectors,2] = (rint(2^14 cos(2 pi k / S)), rint(2^14 sin(2 pi k / S))): the table the device takes as it is."""
+    R, S = _place_int(rings, 1, PLACE_RINGS_MAX, "rings"), _place_int(sectors, PLACE_SECTORS_MIN, PLACE_SECTORS_MAX, "sectors")
+    if S % 4 or R * S > PLACE_BINS_MAX:
+        raise ValueError("sectors must be a multiple of 4 and rings * sectors <= 4096, got %d and %d" % (R, S))
+    r_max, z_lo, z_hi, r_min = (float(v) for v in (r_max, z_lo, z_hi, r_min))
+    if not (np.isfinite([r_max, z_lo, z_hi, r_min]).all() and r_max > 0 and z_lo < z_hi and 0 <= r_min < r_max):
+        raise ValueError("place_params needs finite words with r_max > 0, z_lo < z_hi and 0 <= r_min < r_max, got %r" % ((r_max, z_lo, z_hi, r_min),))
+    unit, z_unit = np.float64(r_max) / 1024.0, (np.float64(z_hi) - np.float64(z_lo)) / 255.0
+    if not (unit > 0 and np.isfinite(z_unit) and z_unit > 0):
+        raise ValueError("r_max / 1024 and (z_hi - z_lo) / 255 must be finite and > 0")
+    ang = 2.0 * np.pi * np.arange(S, dtype=np.float64) / S
+    dirs = np.stack([np.rint(PLACE_DIR * np.cos(ang)), np.rint(PLACE_DIR * np.sin(ang))], -1).astype(np.int32)
+    return {"r_max": r_max, "rings": R, "sectors": S, "z_lo": z_lo, "z_hi": z_hi, "r_min": r_min, "unit": float(unit), "z_unit": float(z_unit),
+            "ring_edge2": (PLACE_Q * np.arange(R + 1, dtype=np.int64) // R) ** 2, "r_min2": int(np.floor(np.float64(r_min) / unit)) ** 2, "dirs": dirs}
+
+
+def _place_setup(xyz, n, counts, params, poses):
+    """The checked arguments of place_descriptor, and per row of [B,cap]: is it one of the frame's, x, y, z in double (in the vehicle's
+    axes: under the pose where there is one), its weight."""
+    w = place_params(params["r_max"], params["rings"], params["sectors"], params["z_lo"], params["z_hi"], params["r_min"])
+    xyz = np.asarray(xyz)
+    if xyz.dtype not in (np.float32, np.float64) or xyz.ndim != 3 or xyz.shape[2] != 3 or xyz.shape[0] > PLACE_BATCH_MAX:
+        raise ValueError("xyz must be float32 or float64 [B,cap,3] with B <= 65535, got %s %s" % (xyz.dtype, xyz.shape))
+    B, cap = xyz.shape[:2]
+    counts = np.asarray(counts)
+    if counts.shape != (B,) or counts.dtype.kind != "i":
+        raise ValueError("counts must be an integer array [%d], got %s %s" % (B, counts.dtype, counts.shape))
+    if n is not None and (np.asarray(n).shape != (B, cap) or np.asarray(n).dtype.kind != "i"):
+        raise ValueError("n must be an integer array [B,cap] or None")
+    rows = np.arange(cap)[None, :] < np.minimum(counts.astype(np.int64), cap)[:, None]
+    with np.errstate(invalid="ignore", over="ignore"):  # rows beyond counts may hold anything
+        if poses is None:
+            P = xyz.astype(np.float64)
+        else:
+            poses = np.asarray(poses, np.float64)
+            if poses.shape != (B, 12):
+                raise ValueError("poses must be None or [%d,12], got %s" % (B, poses.shape))
+            P = _voxel_map_world(xyz, poses)
+    wt = np.ones((B, cap), np.int64) if n is None else np.asarray(n).astype(np.int64)
+    return w, B, cap, rows, P, wt
+
+
+def _place_outputs(B, R, S):
+    return {"desc": np.zeros((B, R, S), np.uint8), "ring": np.zeros((B, R), np.uint8), "words": np.zeros((B, 4), np.int32)}
+
+
+def _place_finish(out):
+    """ring and words[:, :2] from desc."""
+    out["ring"][:] = (out["desc"] > 0).sum(2)  # at most 128
+    out["words"][:, 0] = out["desc"].astype(np.int64).sum((1, 2))
+    out["words"][:, 1] = (out["desc"] > 0).sum((1, 2))
+    return out
+
+
+def place_descriptor(xyz, n, counts, params, poses=None):
+    """The polar height descriptors of B frames of rows, the definition of include/stereo_vision_hip.h (AC1) in numpy.  xyz float32 or
+    float64 [B,cap,3] in the vehicle's axes (x forward, y left, z up), n int [B,cap] or None (every weight 1), counts int [B] - frame b has
+    its first min(counts[b], cap) rows, none for counts[b] <= 0 -, params: place_params' dict; poses float64 [B,12] or None: applied first,
+    by voxel_map_insert's transform.  A row is kept iff n >= 1, x, y, z are finite, |x| < r_max and |y| < r_max and z_lo <= z < z_hi in
+    double, and with qx = int(floor(x / unit)), qy likewise, d2 = qx^2 + qy^2: r_min2 <= d2 < 1024^2 and (qx, qy) != (0, 0).  Its ring is
+    the largest r with ring_edge2[r] <= d2, its sector the one k with cross(dir[k], q) >= 0 and cross(dir[k + 1 mod S], q) < 0 (all S are
+    evaluated and exactly one must hold), its code 1 + min(254, int(floor((z - z_lo) / z_unit))).
+    -> {"desc" uint8 [B,R,S]: per bin the largest code, 0 for an empty bin; "ring" uint8 [B,R]: the occupied sectors per ring; "words"
+    int32 [B,4] = (the sum of the codes, the occupied bins, the kept rows, the dropped rows)}."""
+    w, B, cap, rows, P, wt = _place_setup(xyz, n, counts, params, poses)
+    R, S, dirs = w["rings"], w["sectors"], w["dirs"].astype(np.int64)
+    out = _place_outputs(B, R, S)
+    x, y, z = P[..., 0], P[..., 1], P[..., 2]
+    with np.errstate(invalid="ignore", over="ignore"):
+        keep = rows & (wt >= 1) & np.isfinite(x) & np.isfinite(y) & np.isfinite(z)
+        keep &= (np.abs(x) < w["r_max"]) & (np.abs(y) < w["r_max"]) & (w["z_lo"] <= z) & (z < w["z_hi"])
+    b_of = np.broadcast_to(np.arange(B)[:, None], (B, cap))[keep]
+    qx, qy = np.floor(x[keep] / np.float64(w["unit"])).astype(np.int64), np.floor(y[keep] / np.float64(w["unit"])).astype(np.int64)
+    d2 = qx * qx + qy * qy
+    ok = (w["r_min2"] <= d2) & (d2 < PLACE_Q * PLACE_Q) & ((qx != 0) | (qy != 0))
+    b_of, qx, qy, d2, zk = b_of[ok], qx[ok], qy[ok], d2[ok], z[keep][ok]
+    ring = np.searchsorted(w["ring_edge2"], d2, side="right") - 1
+    cross = dirs[None, :, 0] * qy[:, None] - dirs[None, :, 1] * qx[:, None]  # [N,S]
+    hit = (cross >= 0) & (np.roll(cross, -1, axis=1) < 0)
+    assert (hit.sum(1) == 1).all(), "a row lies in no sector or in two"
+    sector = hit.argmax(1)
+    code = 1 + np.minimum(254, np.floor((zk - np.float64(w["z_lo"])) / np.float64(w["z_unit"])).astype(np.int64))
+    np.maximum.at(out["desc"], (b_of, ring, sector), code.astype(np.uint8))
+    out["words"][:, 2] = np.bincount(b_of, minlength=B)
+    out["words"][:, 3] = rows.sum(1) - out["words"][:, 2]
+    return _place_finish(out)
+
+
+def place_descriptor_brute(xyz, n, counts, params, poses=None):
+    """place_descriptor row by row, in Python numbers."""
+    w, B, cap, rows, P, wt = _place_setup(xyz, n, counts, params, poses)
+    R, S = w["rings"], w["sectors"]
+    dirs, edge2 = [(int(a), int(b)) for a, b in w["dirs"]], [int(e) for e in w["ring_edge2"]]
+    unit, z_unit, z_lo = np.float64(w["unit"]), np.float64(w["z_unit"]), np.float64(w["z_lo"])
+    out = _place_outputs(B, R, S)
+    for b in range(B):
+        for i in range(cap):
+            if not rows[b, i]:
+                continue
+            x, y, z = P[b, i]
+            good = wt[b, i] >= 1 and np.isfinite(x) and np.isfinite(y) and np.isfinite(z) and abs(x) < w["r_max"] and abs(y) < w["r_max"] and w["z_lo"] <= z < w["z_hi"]
+            if good:
+                qx, qy = int(np.floor(x / unit)), int(np.floor(y / unit))
+                d2 = qx * qx + qy * qy
+                good = w["r_min2"] <= d2 < PLACE_Q * PLACE_Q and (qx, qy) != (0, 0)
+            if not good:
+                out["words"][b, 3] += 1
+                continue
+            ring = max(r for r in range(R) if edge2[r] <= d2)
+            cr = [d[0] * qy - d[1] * qx for d in dirs]
+            ks = [k for k in range(S) if cr[k] >= 0 and cr[(k + 1) % S] < 0]
+            assert len(ks) == 1, "a row lies in no sector or in two"
+            code = 1 + min(254, int(np.floor((z - z_lo) / z_unit)))
+            out["desc"][b, ring, ks[0]] = max(int(out["desc"][b, ring, ks[0]]), code)
+            out["words"][b, 2] += 1
+    return _place_finish(out)
+
+
+def _place_match_setup(q_desc, q_words, q_ring, q_seq, k_desc, k_words, k_ring, k_seq, min_gap, ring_gate, max_shift, accept):
+    q_desc, k_desc = np.asarray(q_desc), np.asarray(k_desc)
+    if q_desc.dtype != np.uint8 or q_desc.ndim != 3 or k_desc.dtype != np.uint8 or k_desc.ndim != 3 or q_desc.shape[1:] != k_desc.shape[1:]:
+        raise ValueError("q_desc and k_desc must be uint8 [Q,R,S] and [K,R,S], got %s %s and %s %s" % (q_desc.dtype, q_desc.shape, k_desc.dtype, k_desc.shape))
+    (Q, R, S), K = q_desc.shape, k_desc.shape[0]
+    _place_int(R, 1, PLACE_RINGS_MAX, "rings"), _place_int(S, PLACE_SECTORS_MIN, PLACE_SECTORS_MAX, "sectors")
+    if S % 4 or R * S > PLACE_BINS_MAX or Q > PLACE_QUERIES_MAX or K > PLACE_KEYS_MAX:
+        raise ValueError("place_match needs sectors a multiple of 4, rings * sectors <= 4096, Q <= 65535 and K <= 2^20")
+    arrays = []
+    for a, what, shape, dtype in ((q_words, "q_words", (Q, 4), np.int32), (q_ring, "q_ring", (Q, R), np.uint8), (q_seq, "q_seq", (Q,), np.int32),
+                                  (k_words, "k_words", (K, 4), np.int32), (k_ring, "k_ring", (K, R), np.uint8), (k_seq, "k_seq", (K,), np.int32)):
+        a = np.asarray(a)
+        if a.dtype != dtype or a.shape != shape:
+            raise ValueError("%s must be %s %s, got %s %s" % (what, np.dtype(dtype).name, list(shape), a.dtype, a.shape))
+        arrays.append(a.astype(np.int64))
+    min_gap, ring_gate = _place_int(min_gap, 0, 2 ** 31 - 1, "min_gap"), _place_int(ring_gate, -1, 2 ** 31 - 1, "ring_gate")
+    max_shift = S if max_shift is None else _place_int(max_shift, 0, PLACE_SECTORS_MAX, "max_shift")
+    accept = _place_int(accept, 0, PLACE_ACCEPT_MAX, "accept")
+    shifts = [s for s in range(S) if min(s, S - s) <= max_shift]
+    return [q_desc.astype(np.int64), k_desc.astype(np.int64)] + arrays + [Q, K, R, S, min_gap, ring_gate, shifts, accept]
+
+
+def _place_better(sad_a, norm_a, sad_b, norm_b):
+    """sad_a / norm_a < sad_b / norm_b by the cross-multiplied compare, in Python integers."""
+    return int(sad_a) * int(norm_b) < int(sad_b) * int(norm_a)
+
+
+def _place_pick(Q, K, evaluated, accept, want_pair):
+    """The outputs of place_match from evaluated(q) -> (before the gate, [(key, sad, shift, norm), ...] in key order)."""
+    best, counts = np.zeros((Q, 4), np.int32), np.zeros((Q, 3), np.int32)
+    pair = np.zeros((Q, K, 2), np.int32) if want_pair else None
+    if want_pair:
+        pair[:, :, 0] = -1
+    for q in range(Q):
+        before, cands = evaluated(q)
+        top = None
+        for k, sad, s, norm in cands:
+            if want_pair:
+                pair[q, k] = (sad, s)
+            if top is None or _place_better(sad, norm, top[1], top[3]):  # ties keep the lower key
+                top = (k, sad, s, norm)
+        ok = top is not None and 256 * top[1] <= accept * top[3]
+        best[q] = PLACE_NONE if top is None else (top[0] if ok else -1, top[2], top[1], top[3])
+        counts[q] = (before, len(cands), int(ok))
+    out = {"best": best, "counts": counts}
+    if want_pair:
+        out["pair"] = pair
+    return out
+
+
+def place_match(q_desc, q_words, q_ring, q_seq, k_desc, k_words, k_ring, k_seq, min_gap, ring_gate=-1, max_shift=None, accept=256, want_pair=False):
+    """Q query descriptors against K stored ones under every rotation, the definition of include/stereo_vision_hip.h (AC2) in numpy.
+    q_desc uint8 [Q,R,S], q_words int32 [Q,4], q_ring uint8 [Q,R] (place_descriptor's), q_seq int32 [Q]: the queries' sequence numbers;
+    k_* the same of the K keys.  Key k is a candidate of query q iff both sums (words[0]) are > 0 and |q_seq - k_seq| >= min_gap - counted
+    in counts[q, 0] -, and, unless ring_gate < 0, sum_r |q_ring[r] - k_ring[r]| <= ring_gate - counts[q, 1].  For a candidate sad(s) = sum
+    |q[r,c] - k[r,(c + s) mod S]| over s in 0 .. S - 1 with min(s, S - s) <= max_shift (None: every s); its result is the least sad, among
+    equals the least s; norm = q_sum + k_sum.  The best key has the least sad / norm by sad_a norm_b < sad_b norm_a, among equals the
+    least index; it is accepted iff 256 sad <= accept norm.
+    -> {"best" int32 [Q,4] = (key or -1, shift, sad, norm; (-1, 0, -1, 0) without a candidate), "counts" int32 [Q,3] = (before the gate,
+    behind it, accepted ? 1 : 0), and with want_pair "pair" int32 [Q,K,2] = (sad or -1, shift; (-1, 0) where not evaluated)}."""
+    qd, kd, qw, qr, qs, kw, kr, ks, Q, K, R, S, min_gap, ring_gate, shifts, accept = _place_match_setup(
+        q_desc, q_words, q_ring, q_seq, k_desc, k_words, k_ring, k_seq, min_gap, ring_gate, max_shift, accept)
+
+    def evaluated(q):
+        pre = (kw[:, 0] > 0) & (qw[q, 0] > 0) & (np.abs(qs[q] - ks) >= min_gap)
+        post = pre if ring_gate < 0 else pre & (np.abs(qr[q][None] - kr).sum(1) <= ring_gate)
+        idx = np.flatnonzero(post)
+        if not len(idx):
+            return int(pre.sum()), []
+        sad = np.stack([np.abs(qd[q][None] - np.roll(kd[idx], -s, axis=2)).sum((1, 2)) for s in shifts], 1)  # [C, shifts]
+        at = sad.argmin(1)  # the first of the least: the least s
+        return int(pre.sum()), [(int(k), int(sad[i, at[i]]), shifts[at[i]], int(qw[q, 0] + kw[k, 0])) for i, k in enumerate(idx)]
+
+    return _place_pick(Q, K, evaluated, accept, want_pair)
+
+
+def place_match_brute(q_desc, q_words, q_ring, q_seq, k_desc, k_words, k_ring, k_seq, min_gap, ring_gate=-1, max_shift=None, accept=256, want_pair=False):
+    """place_match pair by pair and shift by shift."""
+    qd, kd, qw, qr, qs, kw, kr, ks, Q, K, R, S, min_gap, ring_gate, shifts, accept = _place_match_setup(
+        q_desc, q_words, q_ring, q_seq, k_desc, k_words, k_ring, k_seq, min_gap, ring_gate, max_shift, accept)
+    cols = np.arange(S)
+
+    def evaluated(q):
+        before, cands = 0, []
+        for k in range(K):
+            if not (qw[q, 0] > 0 and kw[k, 0] > 0 and abs(int(qs[q]) - int(ks[k])) >= min_gap):
+                continue
+            before += 1
+            if ring_gate >= 0 and sum(abs(int(a) - int(b)) for a, b in zip(qr[q], kr[k])) > ring_gate:
+                continue
+            top = None
+            for s in shifts:
+                sad = int(np.abs(qd[q] - kd[k][:, (cols + s) % S]).sum())
+                if top is None or sad < top[0]:
+                    top = (sad, s)
+            cands.append((k, top[0], top[1], int(qw[q, 0]) + int(kw[k, 0])))
+        return before, cands
+
+    return _place_pick(Q, K, evaluated, accept, want_pair)
+
+
+def place_yaw(shift, sectors):
+    """The heading of the query in the key's frame, in radians, for place_match's shift: 2 pi shift / sectors wrapped to (-pi, pi]."""
+    s = np.asarray(shift, np.int64) % int(sectors)
+    return np.pi * (2.0 * np.where(2 * s > sectors, s - sectors, s) / float(sectors))  # the quotient first: half a turn is pi itself
+
+
+def place_guess(key_pose, shift, sectors):
+    """float64 [..., 4] = (x, y, z, yaw), the guess VoxelMap.localize takes: the key's position - key_pose [..., 12], voxel_map_pose's
+    layout - with its heading, atan2(R[1,0], R[0,0]), turned by place_yaw(shift, sectors) and wrapped to (-pi, pi]."""
+    p = np.asarray(key_pose, np.float64)
+    yaw = np.arctan2(p[..., 3], p[..., 0]) + place_yaw(shift, sectors)
+    yaw = np.pi - np.mod(np.pi - yaw, 2.0 * np.pi)  # (-pi, pi]
+    return np.stack([p[..., 9], p[..., 10], p[..., 11], yaw], -1)
+
+
+def place_lines(frames, best, sectors):
+    """'frame key shift sad norm yaw_deg' per accepted query: what --places writes; the angle by repr."""
+    return ["%d %d %d %d %d %r" % (f, b[0], b[1], b[2], b[3], float(np.degrees(place_yaw(b[1], sectors)))) for f, b in zip(frames, np.asarray(best)) if b[0] >= 0]
+
+
 GROUND_BINS_MIN, GROUND_BINS_MAX = 8, 4096
 GROUND_VH_MIN, GROUND_TOL_MAX, GROUND_G_TOL_MAX, GROUND_HEIGHT_MAX = -32768, 16, 4096, 32768
 GROUND_LABELS = {"invalid": 0, "ground": 1, "obstacle": 2, "below": 3}
@@ -5058,6 +5326,11 @@ def main(argv=None):
                              "ObjectTracks at 10 frames a second); writes one line per frame and track to FILE: 'frame id x y w h X Y Z vx vy vz "
                              "n moving' - the box in pixels, its position in metres and its own velocity in m/s in the camera's axes (nan "
                              "until a motion is known), the matches behind the last motion, and whether it moves")
+    parser.add_argument("--places", type=str, default="", metavar="FILE[,MIN_GAP[,ACCEPT]]",
+                        help="with --voxel-map: place recognition (rig.PlaceIndex) - every frame's voxel rows get a polar height descriptor, "
+                             "which is searched among the frames at least MIN_GAP (default 50) before it under every rotation and then "
+                             "stored; a best candidate with 256 sad <= ACCEPT norm (default 64) writes one line to FILE: 'frame key shift "
+                             "sad norm yaw_deg' - the frame it recognised, the shift in sectors and the heading against that frame in degrees")
     parser.add_argument("--temporal", type=str, default="", metavar="DIR[,TOL_PX[,MODE]]",
                         help="with --batch and --odometry: every frame's disparity map compared with the map of the frame before it, warped "
                              "under the fitted motion (StereoRig.temporal, on the odometry's batches: the front end and engine run once "
@@ -5096,6 +5369,14 @@ def main(argv=None):
         args.poses = args.odometry  # written below, before anything reads it
     if args.tracks and (not args.batch or not args.odometry):
         parser.error("--tracks needs --batch and --odometry")
+    args.places_spec = None
+    if args.places:
+        if not args.voxel_map:
+            parser.error("--places needs --voxel-map")
+        try:
+            args.places_spec = cli_places_spec(args.places)
+        except ValueError as e:
+            parser.error("--places: %s" % e)
     args.temporal_spec = None
     if args.temporal:
         if not args.batch or not args.odometry:
@@ -5458,6 +5739,24 @@ def cli_voxel_render_text(counts):
     return ", ".join("%s %d" % (k, int(v)) for k, v in zip(VOXEL_RENDER_LABELS, counts))
 
 
+CLI_PLACE = dict(r_max=40.0, z_lo=-1.4, z_hi=1.0)  # --places: the reach and the heights of CLI_CLOUD_CROP, 20 rings of 60 sectors
+
+
+def cli_places_spec(text):
+    """--places FILE[,MIN_GAP[,ACCEPT]] -> (FILE, min_gap, accept); ValueError for an empty FILE, a MIN_GAP < 0, an ACCEPT outside 0 ..
+    2^20 or more than three parts."""
+    parts = text.split(",")
+    if not parts[0] or len(parts) > 3:
+        raise ValueError("FILE[,MIN_GAP[,ACCEPT]], got %r" % text)
+    try:
+        min_gap, accept = int(parts[1]) if len(parts) > 1 else 50, int(parts[2]) if len(parts) > 2 else 64
+    except ValueError:
+        raise ValueError("MIN_GAP and ACCEPT must be integers, got %r" % text)
+    if not 0 <= min_gap <= 2 ** 31 - 1 or not 0 <= accept <= PLACE_ACCEPT_MAX:
+        raise ValueError("MIN_GAP >= 0 and ACCEPT in 0 .. 2^20, got %r" % text)
+    return parts[0], min_gap, accept
+
+
 def cli_temporal_spec(text):
     """--temporal DIR[,TOL_PX[,MODE]] -> (DIR, tol_q in 1/16 px, mode); ValueError for an empty DIR, a TOL_PX outside 0 .. 65536, a MODE
     that is not fill, confirm or reject, or more than three parts."""
@@ -5552,6 +5851,7 @@ def _run_batched(args, ldir, rdir, files):
     rig = StereoRig(1242 // args.scale, 375 // args.scale, calibration=args.camera_calibration, rectify=args.rectify, scale=args.scale)
     world = rig.occupancy_map(args.map_ranges[0], args.map_ranges[1], CLI_TOP_VIEW["scale"]) if args.occupancy_map else None
     model = rig.voxel_map(args.voxel_map_box[0], args.voxel_map_box[1], args.voxel, CLI_VOXEL_MAP_CAPACITY) if args.voxel_map else None
+    places, recognised = (rig.place_index(**CLI_PLACE) if args.places_spec is not None else None), []
     n, busy, refined, refined_3d, aligned_3d = 0, 0.0, [], [], []
     try:
         for i in range(0, len(files), args.batch):
@@ -5590,6 +5890,12 @@ def _run_batched(args, ldir, rdir, files):
                                 went[k] = model.align(one[0], one[2], one[3], went[k:k + 1], args.voxel_align_spec[0], args.voxel_align_spec[1], args.voxel_align_spec[2], method=args.voxel_align_spec[3])[0][0]
                             model.update(*one, went[k:k + 1])
                         aligned_3d.extend(went)
+                        if places is not None:  # a frame at a time: stored, then searched among the frames at least MIN_GAP before it
+                            found = places.descriptor(voxels[0], voxels[3], voxels[5])
+                            for k in range(len(names)):
+                                one = {f: t[k:k + 1] for f, t in found.items()}
+                                places.add(one, i + k, np.asarray(went[k:k + 1]))
+                                recognised.append(places.query(one, i + k, args.places_spec[1], accept=args.places_spec[2])["best"])
                         if args.voxel_carve_spec is not None:  # the camera's centre is the origin of the vehicle axes: CAMERA_TO_VEHICLE only turns
                             reach_m, min_miss, ratio = args.voxel_carve_spec
                             res = model.carve(voxels[0], voxels[3], voxels[5], went, reach_m=reach_m, min_miss=min_miss, ratio=ratio)
@@ -5639,6 +5945,11 @@ def _run_batched(args, ldir, rdir, files):
             print("batch of %d (%d, %d): %.1f pairs/s so far" % (len(names), rig.height, rig.width, n / busy))
         if model is not None:
             print("voxel map: %d voxels of %g m written to %s" % (model.write_ply(args.voxel_map), args.voxel, args.voxel_map))
+            if places is not None:
+                lines = place_lines(range(len(recognised)), torch.cat(recognised).cpu().numpy(), places.params["sectors"]) if recognised else []
+                with open(args.places_spec[0], "w") as f:
+                    f.write("".join(line + "\n" for line in lines))
+                print("places: %d of %d frames recognised an earlier one, written to %s" % (len(lines), len(recognised), args.places_spec[0]))
             if args.voxel_match_window is not None:
                 with open(os.path.splitext(args.voxel_map)[0] + ".poses.txt", "w") as f:
                     f.write("".join("%r %r %r %r\n" % tuple(float(v) for v in to) for to in refined_3d))
