@@ -1455,8 +1455,10 @@ __global__ __launch_bounds__(256) void k_raster_tiles(KParams k, const int32_t *
     if (blob[pair * META_WORDS] < 3) return;
     const int ntx = (d.W + RT_W - 1) / RT_W;
     const int tx0 = (blockIdx.x % ntx) * RT_W, ty0 = (blockIdx.x / ntx) * RT_H;
-    __shared__ int32_t tile[RT_H][RT_W];
-    for (int i = threadIdx.x; i < RT_H * RT_W; i += 256) (&tile[0][0])[i] = -1;
+    __shared__ __align__(16) int32_t tile[RT_H][RT_W];
+    static_assert(RT_H * RT_W == 2 * 4 * 256, "two 16-byte stores per thread clear the tile");
+    reinterpret_cast<int4 *>(&tile[0][0])[threadIdx.x] = make_int4(-1, -1, -1, -1);
+    reinterpret_cast<int4 *>(&tile[0][0])[threadIdx.x + 256] = make_int4(-1, -1, -1, -1);
     __syncthreads();
     const size_t gt = (size_t)(pair * 2 + side) * gridDim.x + blockIdx.x;
     // A tile whose list overflowed (more than rt_cap triangles touch it: pathological triangulations) walks ALL triangles of its
@@ -1482,31 +1484,53 @@ __global__ __launch_bounds__(256) void k_raster_tiles(KParams k, const int32_t *
             r_next = recs[t_next];
         }
         const int u_begin = max(max(r.a_u, 0), tx0), u_end = min(min(r.c_u, d.W), x_end);
-        for (int base = u_begin; base < u_end; base += 8) {
+        int col = 4 * (u_begin + sub - tx0 - ty0 * RT_W);  // byte offset of the lane's tile column less the tile's first row: + image row * 4 RT_W = the pixel
+        for (int base = u_begin; base < u_end; base += 8, col += 4 * 8) {
             const int u = base + sub;
-            int lo = 0x7FFFFFFF, hi = -0x7FFFFFFF;
+            int lo = ty0, n = 0;  // the lane's column piece: rows [lo, lo + n), none for a lane beyond the triangle
             if (u < u_end) {
                 const bool second = u >= r.b_u;
                 const float e_a = second ? r.bc_a : r.ab_a, e_b = second ? r.bc_b : r.ab_b;
                 const int v_1 = (int)(r.ac_a * (float)u + r.ac_b), v_2 = (int)(e_a * (float)u + e_b);
                 lo = max(max(min(v_1, v_2), 0), ty0);
-                hi = min(min(max(v_1, v_2), d.H), y_end);
-                if (lo >= hi) {
-                    lo = 0x7FFFFFFF;
-                    hi = -0x7FFFFFFF;
-                }
+                n = min(min(max(v_1, v_2), d.H), y_end) - lo;
             }
-            // every lane walks its own column piece [lo, hi) (nothing is shared between the lanes of a group here: a loop over the
+            // every lane walks its own column piece (nothing is shared between the lanes of a group here: a loop over the
             // group's common row range with a per-lane test cost two cross-lane reductions and two compares per row more)
-            int32_t *p = lo < hi ? &tile[lo - ty0][u - tx0] : nullptr;
-            for (int v = lo; v < hi; v++, p += RT_W) atomicMax(p, t);
+            int32_t *p = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(&tile[0][0]) + (lo * (4 * RT_W) + col));  // (row lo - ty0 of the tile whenever n > 0; not read otherwise)
+            // two rows per trip (the second at the immediate offset of one tile row), an odd last row after the loop: the loop's
+            // counter, compare and address step are spent once per two rows
+            for (; n >= 2; n -= 2, p += 2 * RT_W) {
+                atomicMax(p, t);
+                atomicMax(p + RT_W, t);
+            }
+            if (n > 0) atomicMax(p, t);
         }
     }
     __syncthreads();
     int32_t *ids = tri_id + (size_t)(pair * 2 + side) * d.N;
-    for (int i = threadIdx.x; i < RT_H * RT_W; i += 256) {
-        const int r = i / RT_W, c = i - r * RT_W;
-        if (ty0 + r < d.H && tx0 + c < d.W) map_st(ids, (uint32_t)((ty0 + r) * d.W + tx0 + c), tile[r][c]);
+    // A thread owns one column pair of the tile and the rows threadIdx.x / 32 + 8 k: its column test, LDS address and global offset are
+    // computed once.  Even widths store the pair with one 8-byte store (tx0 is a multiple of 64 and N is even: every row start of the
+    // id map is 8-byte aligned); odd widths, and with them the last column of the map, keep 4-byte stores.
+    static_assert(RT_W == 64 && RT_H == 32, "32 column pairs x 8 rows per pass, four passes");
+    const int cp = 2 * (threadIdx.x & 31), x = tx0 + cp;
+    const int r0 = threadIdx.x >> 5, rows = d.H - ty0 - r0;  // rows of the image from this thread's first one down
+    if (x >= d.W) return;
+    const int32_t *src = &tile[r0][cp];
+    const uint32_t at = (uint32_t)((ty0 + r0) * d.W + x);
+    if ((d.W & 1) == 0) {
+#pragma unroll
+        for (int j = 0; j < RT_H / 8; j++)
+            if (8 * j < rows) map_st(reinterpret_cast<int2 *>(ids), (at + (uint32_t)(8 * j * d.W)) >> 1, *reinterpret_cast<const int2 *>(src + 8 * j * RT_W));
+    } else {
+        const bool second = x + 1 < d.W;
+#pragma unroll
+        for (int j = 0; j < RT_H / 8; j++)
+            if (8 * j < rows) {
+                const int2 t = *reinterpret_cast<const int2 *>(src + 8 * j * RT_W);
+                map_st(ids, at + (uint32_t)(8 * j * d.W), t.x);
+                if (second) map_st(ids, at + (uint32_t)(8 * j * d.W) + 1u, t.y);
+            }
     }
 }
 
@@ -1884,8 +1908,28 @@ __global__ __launch_bounds__(256) void k_lr2(KParams k, const int32_t *__restric
     const size_t row = (size_t)v * d.W;  // (uniform: the row's pointers are scalar, the columns 32-bit offsets - map_ld)
     const int16_t *W1 = wta + (size_t)(pair * 2) * d.N + row, *W2 = W1 + d.N;
     const short2 a = map_ld(reinterpret_cast<const short2 *>(W1), (uint32_t)u >> 1), b = map_ld(reinterpret_cast<const short2 *>(W2), (uint32_t)u >> 1);
-    const float thr = (float)k.lr_threshold;
     float o1[2], o2[2];
+    if constexpr (!SUB) {
+        // Full resolution in integers: the WTA values are integers (a disparity, -1 or -10) and so are the warped columns and the
+        // threshold, so the range tests, the partner's column and |partner - d| > lr_threshold are exact on the int16 values; one
+        // conversion per value stored.  (Half resolution warps by d / 2 and keeps the float arithmetic below.)
+        // |x - d| <= thr as one unsigned compare of x - d + thr with 2 thr (scalar: a negative threshold keeps nothing, one beyond any
+        // difference of two int16 values is as good as 2^20)
+        const int thr = min(k.lr_threshold, 1 << 20);
+        const bool some = thr >= 0;
+        const uint32_t span = some ? 2u * (uint32_t)thr : 0u;
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            const int d1 = j ? a.y : a.x, d2 = j ? b.y : b.x;
+            const int p1 = u + j - d1, p2 = u + j + d2;
+            bool keep1 = false, keep2 = false;
+            if (d1 >= 0 && (unsigned)p1 < (unsigned)d.W) keep1 = some && (uint32_t)((int)map_ld(W2, (uint32_t)p1) - d1 + thr) <= span;
+            if (d2 >= 0 && (unsigned)p2 < (unsigned)d.W) keep2 = some && (uint32_t)((int)map_ld(W1, (uint32_t)p2) - d2 + thr) <= span;
+            o1[j] = keep1 ? (float)d1 : -10.0f;
+            o2[j] = keep2 ? (float)d2 : -10.0f;
+        }
+    } else {
+    const float thr = (float)k.lr_threshold;
 #pragma unroll
     for (int j = 0; j < 2; j++) {
         const float d1 = (float)(j ? a.y : a.x), d2 = (float)(j ? b.y : b.x);
@@ -1895,6 +1939,7 @@ __global__ __launch_bounds__(256) void k_lr2(KParams k, const int32_t *__restric
         const float uw1 = SUB ? (float)uj - d1 / 2 : (float)uj - d1, uw2 = SUB ? (float)uj + d2 / 2 : (float)uj + d2;
         if (d1 >= 0 && uw1 >= 0 && uw1 < (float)d.W) o1[j] = (fabsf((float)map_ld(W2, (uint32_t)(int)uw1) - d1) > thr) ? -10.0f : d1;
         if (d2 >= 0 && uw2 >= 0 && uw2 < (float)d.W) o2[j] = (fabsf((float)map_ld(W1, (uint32_t)(int)uw2) - d2) > thr) ? -10.0f : d2;
+    }
     }
     float *D1r = disp + (size_t)(pair * 2) * d.N + row;
     map_st(reinterpret_cast<float2 *>(D1r), (uint32_t)u >> 1, make_float2(o1[0], o1[1]));
@@ -2315,7 +2360,8 @@ __global__ __launch_bounds__(256) void k_ccl_border(int nproc, int epoch, const 
     const int m = blockIdx.y;
     if (blob[(m / nproc) * META_WORDS] < 3 || ws.flag[m] == epoch) return;
     const int nch = ws.nch, nb = ws.nb;
-    const int idx = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;  // wave-uniform word index
+    // wave-uniform word index, in a scalar register: the word's masks come through scalar loads and the link mask is scalar arithmetic
+    const int idx = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (idx >= (nb - 1) * nch) return;
     const int b = 1 + idx / nch, c = idx - (b - 1) * nch;
     const uint64_t *bwb = ws.bwords + ((size_t)m * nb + b) * 5 * nch, *bwp = bwb - 5 * nch;
@@ -2431,10 +2477,10 @@ __global__ __launch_bounds__(GAPR_THREADS) void k_gap_rows(KParams k, int nproc,
     const int m = blockIdx.y;
     if (blob[(m / nproc) * META_WORDS] < 3) return;
     float *D = disp + map_offset(d, m, nproc) + (size_t)blockIdx.x * d.W;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = GAPR_THREADS / 64;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = GAPR_THREADS / 64;  // (wave-uniform: the word loops count in scalar registers)
     const int nch = (d.W + 63) / 64;
     __shared__ unsigned long long mw[SV_MAX_LINE_WORDS];
-    __shared__ int prevb[SV_MAX_LINE_WORDS], nextb[SV_MAX_LINE_WORDS];
+    __shared__ int2 ends[SV_MAX_LINE_WORDS];  // per word: last valid pixel before it (.x), first valid pixel after it (.y); beside mw[c] at one index
     for (int c = wave; c < nch; c += nw) {
         const int u = c * 64 + lane;
         const float val = u < d.W ? map_ld(D, (uint32_t)u) : -1.0f;
@@ -2456,7 +2502,7 @@ __global__ __launch_bounds__(GAPR_THREADS) void k_gap_rows(KParams k, int nproc,
             }
             int excl = __shfl_up(last, 1, 64);
             if (lane == 0) excl = -1;
-            if (c < nch) prevb[c] = max(excl, carry);
+            if (c < nch) ends[c].x = max(excl, carry);
             carry = max(carry, __shfl(last, 63, 64));
         }
     } else if (wave == 1) {
@@ -2473,20 +2519,28 @@ __global__ __launch_bounds__(GAPR_THREADS) void k_gap_rows(KParams k, int nproc,
             int excl = __shfl_down(first, 1, 64);
             if (lane == 63) excl = 0x7FFFFFFF;
             const int nb = min(excl, carry);
-            if (c < nch) nextb[c] = nb == 0x7FFFFFFF ? -1 : nb;
+            if (c < nch) ends[c].y = nb == 0x7FFFFFFF ? -1 : nb;
             carry = min(carry, __shfl(first, 0, 64));
         }
     }
     __syncthreads();
     const int gw = k.gap_width;
+    // The lane's own bit and the bits below / above it are built once per thread, as 32-bit halves; per word that leaves ANDs with the
+    // word's halves in front of the bit scans (no per-lane 64-bit shifts).  The word index is wave-uniform: the loop, the LDS
+    // addresses and the word's first column count in scalar registers.
+    const unsigned long long lt = (1ull << lane) - 1ull, gt = ~((lt << 1) | 1ull);
+    const uint32_t lt_lo = (uint32_t)lt, lt_hi = (uint32_t)(lt >> 32), gt_lo = (uint32_t)gt, gt_hi = (uint32_t)(gt >> 32);
+    const uint32_t me_lo = ~(lt_lo | gt_lo), me_hi = ~(lt_hi | gt_hi);
     for (int c = wave; c < nch; c += nw) {
         const int u = c * 64 + lane;
         const unsigned long long w = mw[c];
-        if (u >= d.W || ((w >> lane) & 1ull)) continue;
-        const unsigned long long below = w & ((1ull << lane) - 1ull);
-        const unsigned long long above = lane == 63 ? 0ull : (w >> (lane + 1));
-        const int pl = below ? c * 64 + 63 - __clzll((long long)below) : prevb[c];
-        const int nr = above ? u + __ffsll((long long)above) : nextb[c];
+        const int2 e = ends[c];
+        const uint32_t w_lo = (uint32_t)w, w_hi = (uint32_t)(w >> 32);
+        if (u >= d.W || ((w_lo & me_lo) | (w_hi & me_hi))) continue;
+        const unsigned long long below = ((unsigned long long)(w_hi & lt_hi) << 32) | (w_lo & lt_lo);
+        const unsigned long long above = ((unsigned long long)(w_hi & gt_hi) << 32) | (w_lo & gt_lo);
+        const int pl = below ? (c * 64 + 63) ^ __clzll((long long)below) : e.x;  // (63 - clz as one XOR with the word's scalar last column)
+        const int nr = above ? (c * 64 - 1) + __ffsll((long long)above) : e.y;
         if (pl >= 0 && nr >= 0) {
             if (nr - pl - 1 <= gw) map_st(D, (uint32_t)u, gap_value(map_ld(D, (uint32_t)pl), map_ld(D, (uint32_t)nr)));  // :1158-1176
         } else if (k.add_corners) {
