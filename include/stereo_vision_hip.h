@@ -116,7 +116,13 @@
  *      rings x sectors bytes that a turn of the vehicle rolls along the sectors (AC1), and query descriptors searched among stored ones
  *      under every roll, the best key per query by the least sum of absolute differences over the sum of both descriptors (AC2).
  *      stereo_vision.sv.place_descriptor and place_match state the definitions in numpy; place_yaw and place_guess turn a key and a
- *      shift into the guess the voxel map's localisation takes.  What to do with a confirmed loop stays with the caller.
+ *      shift into the guess the voxel map's localisation takes.  The solver for a confirmed loop stays with the caller; its result goes to (AD).
+ *
+ *  (AD) Behind (AC), (S) and (Q): a voxel map re-posed after a loop closure (sv_voxel_repose_device) - every voxel of a map of (Q) moved
+ *      by the rigid correction of the frame that saw it last, one of K corrections chosen by the voxel's last_seq, and accumulated into a
+ *      second map with (Q)'s integer atomics: what a caller's pose graph returns - a corrected pose per frame - applied to a map whose
+ *      frames are gone.  stereo_vision.sv.voxel_map_repose states the definition in numpy; pose_corrections and loop_spread are the
+ *      host's helpers for one confirmed loop.
  *
  * All sv_* functions return SV_OK (0) or a negative sv_status; sv_last_error() gives the text.
  * Nothing in this library calls exit().
@@ -2035,6 +2041,49 @@ int sv_place_match_device(const uint8_t *q_desc, const int32_t *q_words, const u
 /* Measurement hook for the search above, process-wide: flags = 1 takes one key per pass of a wavefront instead of four - the same
  * results, for timing only.  0 is the default.  Returns SV_OK, or SV_ERR_ARG for a value outside 0 .. 1. */
 int sv_debug_place(int flags);
+
+/* ---- (AD) a voxel map re-posed: (Q)'s table + a rigid correction per frame -> every voxel moved and accumulated into a second table of (Q) ---- */
+
+/* (S) moves a map by whole cells.  This moves every voxel of one map (src, only read) by a rigid motion of its own and adds it into
+ * another (dst): the corrected poses of a pose graph applied to a map whose frames are gone.  Every value of dst is an integer changed by
+ * integer atomics whose result does not depend on their order, so dst stays bit-exact against stereo_vision.sv.voxel_map_repose, which
+ * restates this in numpy.  Box, size and capacity of the two maps may all differ.
+ *
+ *   qualifies  a voxel of src with n >= max(min_n, 1), m >= min_rows and last_seq >= since; a voxel that does not counts into `filtered`.
+ *              An emptied voxel (n = 0, what (T) and (W) leave) never qualifies, whatever min_n is.
+ *   position   p: the centre the read-out of (Q) reports for dtype 1, lo + (c + (S + 0.5 n) / (65536 n)) * size of src per axis, as written
+ *   correction corr[k], k = min(max(last_seq - seq0, 0), n_corr - 1) in 64 bits: last_seq alone chooses, so a voxel that two passes of a
+ *              drive share moves with the later pass.  Pw[a] = ((R[a,0] px + R[a,1] py) + R[a,2] pz) + t[a]: the insert's transform, in
+ *              its order, no FMA.  Any twelve words are taken as they are.
+ *   outside    a qualifying voxel for which lo < Pw < hi of dst fails strictly on an axis counts into `outside`; NaN and inf never pass,
+ *              so neither does a correction with a word that is not finite
+ *   carried    every other voxel: with the insert's cell c = min((int64)t, cells - 1), t = (Pw - lo) / size, and offset u = min((int64)((t -
+ *              c) * 65536), 65535) of dst, the voxel of dst with c's key gets n += n, S += n u, C += C, m += m, first_seq = min(.,
+ *              first_seq), last_seq = max(., last_seq): an insert of one row of weight n at the voxel's mean, with (S)'s bookkeeping.
+ *              `carried` counts them, `claimed` those whose voxel dst did not hold before.  Several voxels of src may land in one of dst.
+ *   head       (S)'s: dst's dropped += src's dropped; dst is overflowed after the call iff it was before, or src is, or dst now holds more
+ *              than its capacity.  Where src or dst is overflowed as the call starts nothing is carried: carried = -1, the other counts 0.
+ *              Where dst overflows during the call its content and `claimed` are undefined; carried, filtered and outside are exact.
+ *   widths     (Q)'s contract: the total weight of a voxel of dst stays below 2^47 after the call.
+ *
+ * There is no shortcut for the identity: a voxel's points collapse to their mean, S becomes n times a whole offset - floor(S / n + 1 / 2), the centre's -, and a re-pose costs
+ * up to 1 / 65536 of a cell of position, once per call.
+ *
+ * Enqueues two kernels on `stream` (a hipStream_t, NULL = the default stream) - the head, then a lane per slot of src - and does not wait:
+ * nothing is allocated and no host synchronisation is made.  Uses the first word of the read-out scratch of dst.  No other call on either
+ * map may run at the same time.
+ *   dst, dst_bytes, dst_spec : the map that receives, as (Q)'s entries take it; it must have been cleared or filled before
+ *   src, src_bytes, src_spec : the map that is read
+ *   corr         : double [n_corr][12] device, 8-byte aligned: R row-major, then t; n_corr in 1 .. 2^22
+ *   seq0         : the sequence number corr[0] belongs to, 0 .. 2^31 - 2
+ *   min_n, min_rows, since : the filters of sv_voxel_map_rows_device
+ *   stats        : int64 [4] device, 8-byte aligned - carried, filtered, outside, claimed, written by the call whatever it held -, or NULL
+ * Returns SV_OK, SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued, both maps untouched, the text in sv_last_error(NULL) - for: what the clear
+ * entry of (Q) refuses, for either map; a NULL or misaligned corr; n_corr outside 1 .. 2^22; seq0 outside 0 .. 2^31 - 2; maps that share a
+ * byte; corr inside dst; stats not 8-byte aligned or inside a map or corr.  These checks run before any HIP call.
+ * (The name has no "voxel_map" in it: tests/test_voxel_map.py pins the set of "sv_*voxel_map*(" declarations to group (Q)'s seven.) */
+int sv_voxel_repose_device(void *dst, size_t dst_bytes, const sv_voxel_map_spec *dst_spec, const void *src, size_t src_bytes, const sv_voxel_map_spec *src_spec,
+                           const double *corr, int n_corr, int seq0, int64_t min_n, int64_t min_rows, int since, int64_t *stats, void *stream);
 
 /* ---- (A)the reference's exported symbols ------------------------------------------------------------- */
 

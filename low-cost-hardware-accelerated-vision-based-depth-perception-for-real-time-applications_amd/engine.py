@@ -728,6 +728,9 @@ def _signatures():
             "sv_place_match_device": (ci, [vp, vp, vp, vp, ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, sz, vp]),
             "sv_debug_place": (ci, [ci]),
         },
+        "voxel_repose": {  # (AD)
+            "sv_voxel_repose_device": (ci, [vp, sz, vm, vp, sz, vm, vp, ci, ci, i64, i64, ci, vp, vp]),
+        },
     }
 
 
@@ -742,6 +745,7 @@ _GROUP_NEEDS["voxel_flatten"] = ("voxel_map", "occupancy_map")
 _GROUP_NEEDS["voxel_clusters"] = ("voxel_map", "occupancy_map")
 _GROUP_NEEDS["voxel_align"] = ("voxel_map",)
 _GROUP_NEEDS["voxel_normals"] = ("voxel_map",)
+_GROUP_NEEDS["voxel_repose"] = ("voxel_map",)
 _bound_groups = set()
 
 
@@ -2225,6 +2229,50 @@ def voxel_map_carry(dst_buf, dst_params, src_buf, src_params, shift=(0, 0, 0), m
                                                          torch.cuda.current_stream(dev).cuda_stream)
     _check(rc, "sv_voxel_map_carry_device")
     return stats
+
+
+def voxel_repose_lib():
+    """The library with the signatures of group (AD) declared."""
+    return _bind("voxel_repose")
+
+
+def voxel_map_repose(dst_buf, dst_params, src_buf, src_params, corr, seq0=0, min_n=1, min_rows=1, since=0):
+    """Adds the voxels of the map in src_buf - those with n >= max(min_n, 1), m >= min_rows and last_seq >= since, each moved by the rigid
+    correction corr[min(max(last_seq - seq0, 0), K - 1)] - into the map in dst_buf: the definition of stereo_vision.sv.voxel_map_repose on
+    the GPU, bit for bit (sv_voxel_repose_device: two kernels).  Both maps are voxel_map_new's buffers with their params, on one device
+    and sharing no memory; box, size and capacity may differ; src is only read.  corr: float64 [K,12], K in 1 .. 2^22 - a numpy array,
+    uploaded here, or a tensor on the maps' device.  -> an int64 [4] tensor on the device: carried (-1 where either map was overflowed:
+    nothing is carried), filtered, outside, claimed - stereo_vision.sv.VOXEL_CARRY_STATS.  Enqueued on torch's current stream, not waited
+    for; no other work on either map may run on another stream meanwhile."""
+    import torch
+    from .stereo_vision.sv import VOXEL_MAP_SEQ_MAX, VOXEL_REPOSE_CORR_MAX
+    dst_spec, src_spec = voxel_map_spec(dst_params), voxel_map_spec(src_params)
+    dst_bytes, src_bytes = _voxel_map_buffer(dst_buf, dst_spec), _voxel_map_buffer(src_buf, src_spec)
+    if src_buf.device != dst_buf.device:
+        raise ValueError("the two maps must lie on one device, got %s and %s" % (dst_buf.device, src_buf.device))
+    dev = dst_buf.device
+    if not isinstance(corr, torch.Tensor):
+        try:
+            corr = torch.from_numpy(np.ascontiguousarray(corr, dtype=np.float64)).to(dev)
+        except (TypeError, ValueError):
+            raise ValueError("corr must be float64 [K,12]")
+    if corr.device != dev or corr.dtype != torch.float64 or corr.dim() != 2 or corr.shape[1] != 12 or not 1 <= corr.shape[0] <= VOXEL_REPOSE_CORR_MAX:
+        raise ValueError("corr must be float64 [K,12] with K in 1 .. 2^22 on the device (%s) of the maps" % (dev,))
+    corr = corr.contiguous()
+    if isinstance(seq0, bool) or int(seq0) != seq0 or not 0 <= seq0 <= VOXEL_MAP_SEQ_MAX:
+        raise ValueError("seq0 must be an integer in 0 .. 2^31 - 2, got %r" % (seq0,))
+    for v, what in ((min_n, "min_n"), (min_rows, "min_rows")):
+        if isinstance(v, bool) or int(v) != v or not -2 ** 63 <= v < 2 ** 63:
+            raise ValueError("%s must be an integer, got %r" % (what, v))
+    if isinstance(since, bool) or int(since) != since or not -2 ** 31 <= since < 2 ** 31:
+        raise ValueError("since must be a 32-bit integer, got %r" % (since,))
+    stats = torch.empty((4,), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        rc = voxel_repose_lib().sv_voxel_repose_device(dst_buf.data_ptr(), dst_bytes, ctypes.byref(dst_spec), src_buf.data_ptr(), src_bytes, ctypes.byref(src_spec),
+                                                       corr.data_ptr(), int(corr.shape[0]), int(seq0), int(min_n), int(min_rows), int(since), stats.data_ptr(),
+                                                       torch.cuda.current_stream(dev).cuda_stream)
+    _check(rc, "sv_voxel_repose_device")
+    return stats  # corr goes back to torch's allocator, which hands it out again on this stream only: behind the kernels
 
 
 def voxel_carve_lib():

@@ -43,7 +43,7 @@ import numpy as np
 from .engine import disparity_warp, flow_egomotion, flow_match, object_links, place_descriptor, place_match
 from .engine import (SvParams, StereoEngine, StereoError, box_positions_from_disparity, box_spec, cloud_spec, compact_cloud_from_disparity,
                      ground_from_disparity, ground_spec, lib, occupancy_from_disparity, occupancy_fuse, occupancy_match, occupancy_clearance, clearance_paths, cost_cells, cost_routes, frontier_cells, frontier_clusters, occupancy_cost_to_goal, occupancy_view, occupancy_spec, pinned_array, reproject, split_clouds, stixel_spec, stixels_from_disparity,
-                     top_view_from_disparity, top_view_spec, split_voxel_clouds, voxel_cloud_from_disparity, voxel_map_align, voxel_map_carry, voxel_map_clear, voxel_map_insert, voxel_map_match, voxel_map_new,
+                     top_view_from_disparity, top_view_spec, split_voxel_clouds, voxel_cloud_from_disparity, voxel_map_align, voxel_map_carry, voxel_map_clear, voxel_map_insert, voxel_map_match, voxel_map_new, voxel_map_repose,
                      voxel_map_rows, voxel_map_stats, voxel_spec)
 from .stereo_vision.sv import CAMERA_TO_VEHICLE, DEFAULT_CALIBRATION  # noqa: F401 (CAMERA_TO_VEHICLE: re-exported for top_view)
 from .stereo_vision.sv import free_space_points, ground_pose
@@ -626,7 +626,10 @@ class VoxelMap:
     stereo_vision.sv.voxel_map_clusters: the connected components of the voxels - a row of counts, sums and a box per object, a label per
     voxel - and the components below a size emptied.  align() is group (X), stereo_vision.sv.voxel_map_align: a frame's pose refined by
     iterative closest point against the voxels' means, below localize's step and in roll and pitch as well.  normals() is group (Y),
-    stereo_vision.sv.voxel_map_normals: a plane per voxel through the means around it, which align(method="plane") fits the rows to."""
+    stereo_vision.sv.voxel_map_normals: a plane per voxel through the means around it, which align(method="plane") fits the rows to.
+    repose() and merge(pose=...) are group (AD), stereo_vision.sv.voxel_map_repose: the voxels moved by the rigid correction of the frame
+    that saw them last - the corrected poses of a loop closure applied to the map - or another map's voxels taken in under one rigid
+    transform."""
 
     def __init__(self, lo, hi, size, capacity, device="cuda"):
         import torch
@@ -805,6 +808,36 @@ class VoxelMap:
         self.params = params
         return stats
 
+    def repose(self, corr, seq0=0, params=None, **filters):
+        """Re-poses the map after a loop closure (include/stereo_vision_hip.h (AD), stereo_vision.sv.voxel_map_repose): every voxel is moved
+        by the rigid correction of the frame that saw it last - corr float64 [K,12], numpy or a tensor on the map's device, what
+        stereo_vision.sv.pose_corrections makes of the drive's poses and the corrected ones; the correction of a voxel is corr[min(max(
+        last_seq - seq0, 0), K - 1)] - and accumulated into an empty table, which becomes the map: the spare buffer, as prune() uses
+        it.  params: a new box and capacity (stereo_vision.sv.voxel_map_params' dict; the size may differ too) for corrections that move
+        the map's extent; None keeps the map's.  filters: min_n, min_rows, since prune on the way.  A re-pose costs up to 1 / 65536 of a
+        cell of position: a voxel's points collapse to their mean.  seq stays; what normals() kept is stale.  -> the counts, as
+        prune()."""
+        f = self._filters(filters)
+        params = self.params if params is None else _sv.voxel_map_params(params["lo"], params["hi"], params["size"], params["capacity"])
+        self._stale()
+        if self._state is not None:
+            corr = corr.cpu().numpy() if hasattr(corr, "cpu") else corr
+            state = _sv.voxel_map_state(params)
+            stats = _sv.voxel_map_repose(state, self._state, corr, seq0, *f)
+            self._state, self.params = state, state["params"]
+            return stats
+        same = params["capacity"] == self.params["capacity"]
+        if same and self._spare is None:
+            self._spare = voxel_map_new(params, self.device)
+        into = voxel_map_clear(self._spare, params) if same else voxel_map_new(params, self.device)
+        stats = voxel_map_repose(into, params, self.buffer, self.params, corr, seq0, *f)
+        if same:
+            self.buffer, self._spare = into, self.buffer
+        else:
+            self.buffer, self._spare = into, None  # the old pair goes back to torch's allocator, behind the kernels of this stream
+        self.params = params
+        return stats
+
     def prune(self, min_n=1, min_rows=1, since=0):
         """Forgets: keeps the voxels with n >= min_n, m >= min_rows and last_seq >= since - rows()' filters - in the same box and
         capacity, with every sum as it was.  -> the counts carried, filtered, outside, claimed (stereo_vision.sv.VOXEL_CARRY_STATS): an
@@ -830,9 +863,12 @@ class VoxelMap:
         stays lost).  The filters prune on the way.  -> the counts, as prune()."""
         return self._carry_over(_sv.voxel_map_params(self.params["lo"], self.params["hi"], self.params["size"], capacity), (0, 0, 0), filters)
 
-    def merge(self, other, **filters):
-        """Adds the voxels of `other` - those that pass the filters and lie in this map's box - to this map; `other` is not changed.  Both
-        maps lie on one device and have the same size, and other's box must start a whole number of cells from this one's: the shift is
+    def merge(self, other, pose=None, **filters):
+        """Adds the voxels of `other` - those that pass the filters and lie in this map's box - to this map; `other` is not changed.  With
+        pose float64 [12] (stereo_vision.sv.voxel_map_pose's layout) the other map's voxels come in under that one rigid transform, from
+        other's world into this one's (group (AD), stereo_vision.sv.voxel_map_repose with K = 1): two sessions or ranks whose frames
+        differ by more than whole cells; the maps may then differ in box, size and capacity, and each voxel comes in as one row at its
+        mean.  Without a pose (group (S)) both maps lie on one device and have the same size, and other's box must start a whole number of cells from this one's: the shift is
         round((other.lo - self.lo) / size), and ValueError is raised where that quotient misses it by more than
         stereo_vision.sv.VOXEL_MERGE_TOLERANCE = 1 / 65536 of a cell - the unit of the sub-cell offsets the voxels hold: a box that is
         off by less displaces no point by more than the map resolves, and the roundings voxel_map_shifted leaves in lo are smaller by
@@ -841,6 +877,17 @@ class VoxelMap:
         f = self._filters(filters)
         if not isinstance(other, VoxelMap) or other is self or other.device != self.device:
             raise ValueError("merge needs another VoxelMap on %s" % (self.device,))
+        if pose is not None:
+            corr = np.ascontiguousarray(pose.cpu().numpy() if hasattr(pose, "cpu") else pose, np.float64)
+            if corr.shape != (12,):
+                raise ValueError("merge: pose must be float64 [12], got shape %s" % (corr.shape,))
+            if self._state is not None:
+                stats = _sv.voxel_map_repose(self._state, other._state, corr[None], 0, *f)
+            else:
+                stats = voxel_map_repose(self.buffer, self.params, other.buffer, other.params, corr[None], 0, *f)
+            self.seq = max(self.seq, other.seq)
+            self._stale()
+            return stats
         size = np.float64(self.params["size"])
         if np.float64(other.params["size"]).tobytes() != size.tobytes():
             raise ValueError("merge needs maps of one size, got %r and %r" % (self.params["size"], other.params["size"]))
@@ -1003,7 +1050,8 @@ class PlaceIndex:
     engine.place_descriptor and engine.place_match -, or "cpu": the numpy definitions on CPU tensors, the same methods and the same bits.
     params: stereo_vision.sv.place_params' dict; capacity: the keyframes the tensors hold at first - add() doubles it by one copy when it
     runs out.  count is the number of keyframes; desc, ring, words, seq and poses are the tensors, of which the first count rows are
-    used.  What to do with a confirmed loop stays with the caller: guess() gives the start VoxelMap.localize, then .align, refine."""
+    used.  The solver for a confirmed loop stays with the caller: guess() gives the start VoxelMap.localize, then .align, refine;
+    repose() takes the corrections the solver - or stereo_vision.sv.loop_spread - arrives at, as VoxelMap.repose does."""
 
     def __init__(self, params, capacity, device="cuda"):
         import torch
@@ -1080,6 +1128,16 @@ class PlaceIndex:
         res = place_match(q[0], q[1], q[2], self._on_device(self._seq(seq, Q), self.seq.dtype), self.desc[:n], self.words[:n], self.ring[:n], self.seq[:n], min_gap,
                           ring_gate, max_shift, accept, want_pair)
         return {k: v if isinstance(v, torch.Tensor) else torch.from_numpy(v) for k, v in res.items()}
+
+    def repose(self, corr, seq0=0):
+        """The stored key poses after a loop closure: pose r becomes corr[k] o pose r with k = min(max(seq[r] - seq0, 0), K - 1) -
+        VoxelMap.repose's index rule on the keys' sequence numbers, by stereo_vision.sv.pose_repose on a read-back copy (96 bytes a
+        key) -, so that guess() points into the re-posed map.  corr float64 [K,12], numpy or a tensor.  Reads back the sequence numbers."""
+        n = self.count
+        corr = corr.cpu().numpy() if hasattr(corr, "cpu") else corr
+        moved = _sv.pose_repose(self.poses[:n].cpu().numpy(), self.seq[:n].cpu().numpy(), corr, seq0)
+        self.poses[:n] = self._on_device(moved, self.poses.dtype)
+        self._pose_host = moved
 
     def guess(self, result):
         """query()'s result -> (ok bool [Q], xyzyaw float64 [Q,4]): per accepted query the start VoxelMap.localize takes - the key's

@@ -156,6 +156,14 @@ drive, shared by the CPU and the GPU path, so that both give the same poses bit 
 open: FLOW_Z_MIN = 0.1 m; b = 1 / q32 with q33 taken as 0; a disparity makes a point where floor(16 d + 0.5) is in 1 .. 2^20; a window
 centre beyond +-2^20 drops the point; rows behind a frame's count hold -1; a match is inside where z > z_min and its predicted words stay
 within +-2^30; no gate is 2^20 sixteenths of a pixel; FLOW_EPS = (2e-5 rad, 2e-4 m).  The reference has no counterpart.
+
+voxel_map_repose (with voxel_map_repose_brute, the plain loop per voxel) is the definition of a voxel map re-posed after a loop closure
+(sv_voxel_repose_device of include/stereo_vision_hip.h (AD); engine.voxel_map_repose / rig.VoxelMap.repose and .merge(pose=...) on the
+GPU): every voxel moved by the rigid correction of the frame that saw it last and accumulated into a second map, in the insert's
+integers.  pose_corrections, loop_spread (with pose_log and pose_exp) and pose_repose are the host's helpers in doubles, shared by the
+CPU and the GPU path: the corrections between two sets of poses, one loop's error spread along the chain, and the stored poses of a
+PlaceIndex under the same corrections.  The solver of a pose graph stays with the caller.  The reference has no counterpart (DESIGN.md
+§8).
 """
 import argparse
 import ctypes
@@ -860,6 +868,257 @@ def voxel_map_carry(dst_state, src_state, shift=(0, 0, 0), min_n=1, min_rows=1, 
     if V > wd["capacity"]:
         dst_state["overflowed"] = True
     return stats
+
+
+VOXEL_REPOSE_CORR_MAX = 2 ** 22  # corrections per call of voxel_map_repose
+
+
+def _voxel_repose_setup(dst_state, src_state, corr, seq0, min_n, min_rows, since):
+    """voxel_map_repose's checks (ValueError) -> (corr float64 [K,12], seq0, min_n, min_rows, since) as the definition takes them."""
+    if dst_state is src_state:
+        raise ValueError("voxel_map_repose needs two distinct maps")
+    try:
+        corr = np.ascontiguousarray(corr, np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("corr must be float64 [K,12]")
+    if corr.ndim != 2 or corr.shape[1] != 12 or not 1 <= corr.shape[0] <= VOXEL_REPOSE_CORR_MAX:
+        raise ValueError("corr must be float64 [K,12] with K in 1 .. 2^22, got shape %s" % (corr.shape,))
+    seq0 = _whole(seq0, "seq0")
+    if not 0 <= seq0 <= VOXEL_MAP_SEQ_MAX:
+        raise ValueError("seq0 must be an integer in 0 .. 2^31 - 2, got %r" % (seq0,))
+    return corr, seq0, _whole(min_n, "min_n"), _whole(min_rows, "min_rows"), _whole(since, "since")
+
+
+def voxel_map_repose(dst_state, src_state, corr, seq0=0, min_n=1, min_rows=1, since=0):
+    """Adds the voxels of one voxel map, each moved by the rigid correction of the frame that saw it last, into another: the definition
+    of include/stereo_vision_hip.h (AD) in numpy.  dst_state (voxel_map_state's dict) is changed in place, src_state is only read; -> a
+    dict of counts in VOXEL_CARRY_STATS' order.
+
+    The two maps must be distinct; box, size and capacity may all differ.  corr is float64 [K,12] in voxel_map_pose's layout, K in 1 ..
+    2^22, any twelve words taken as they are (as the insert takes any pose); seq0 an integer in 0 .. 2^31 - 2 (ValueError otherwise).  A
+    voxel of src qualifies iff n >= max(min_n, 1), m >= min_rows and last_seq >= since; one that does not counts into "filtered" - a
+    tombstone (n = 0, what carve and despeckle leave) never qualifies, whatever min_n is: the next step divides by n.  A qualifying
+    voxel stands at p, the read-out's centre (voxel_map_rows' xyz for "f64", as written there), and is moved by corr[k], k = min(max(
+    last_seq - seq0, 0), K - 1): last_seq is the one rule, so a voxel that two passes of a drive share is moved with the later pass.  Pw
+    = _voxel_map_world(p, corr[k]), the insert's transform in its order, no FMA.  Where lo < Pw < hi of dst fails strictly on an axis
+    the voxel counts into "outside" - NaN and inf never pass, so neither does a correction that is not finite.  Every other voxel is
+    carried: with the insert's cell c = min(int(t), cells - 1), t = (Pw - lo) / size, and offset u = min(int((t - c) * 65536), 65535) the
+    voxel of dst with c's key gets n += n, S += n u, C += C, m += m, first_seq = min(., first_seq), last_seq = max(., last_seq): an
+    insert of one row of weight n at the voxel's mean, with the carry's bookkeeping.  "carried" counts them, "claimed" the voxels dst
+    did not hold before.  The head is the carry's: dst["dropped"] += src["dropped"]; where src or dst is overflowed as the call starts
+    nothing is carried, "carried" is -1 and the other counts 0; dst is overflowed afterwards iff it was, or src is, or it now holds
+    more than its capacity.  Contract: the total weight of a voxel of dst stays below 2^47.
+
+    There is no shortcut for the identity: a voxel's points collapse to their mean, and S becomes n times a whole offset - floor(S / n + 1 / 2), the centre's -, so a re-pose
+    costs up to 1 / 65536 of a cell of position, once per call, whatever the corrections are."""
+    corr, seq0, min_n, min_rows, since = _voxel_repose_setup(dst_state, src_state, corr, seq0, min_n, min_rows, since)
+    ws, wd = src_state["params"], dst_state["params"]
+    stats = dict.fromkeys(VOXEL_CARRY_STATS, 0)
+    dst_state["dropped"] += src_state["dropped"]
+    if src_state["overflowed"] or dst_state["overflowed"]:
+        dst_state["overflowed"] = True
+        stats["carried"] = -1
+        return stats
+    q = (src_state["n"] >= max(min_n, 1)) & (src_state["m"] >= min_rows) & (src_state["last_seq"] >= since)
+    key, n = src_state["key"][q], src_state["n"][q]
+    c = np.stack([key & 0xFFFFF, (key >> 20) & 0xFFFFF, (key >> 40) & 0xFFFFF], -1)
+    nf = n.astype(np.float64)[:, None]
+    p = np.array(ws["lo"]) + (c.astype(np.float64) + (src_state["S"][q].astype(np.float64) + 0.5 * nf) / (65536.0 * nf)) * np.float64(ws["size"])
+    k = np.clip(src_state["last_seq"][q].astype(np.int64) - seq0, 0, len(corr) - 1)
+    lo, hi, size, cells = np.array(wd["lo"]), np.array(wd["hi"]), np.float64(wd["size"]), np.array(wd["cells"], np.int64)
+    with np.errstate(invalid="ignore", over="ignore"):  # a correction may hold anything
+        Pw = _voxel_map_world(p[:, None, :], corr[k])[:, 0, :]
+        inside = ((lo < Pw) & (Pw < hi)).all(-1)
+    stats["filtered"], stats["outside"], stats["carried"] = int((~q).sum()), int((~inside).sum()), int(inside.sum())
+    t = (Pw[inside] - lo) / size
+    c = np.minimum(t.astype(np.int64), cells - 1)
+    u = np.minimum(((t - c.astype(np.float64)) * 65536.0).astype(np.int64), 65535)
+    moved = c[:, 0] | (c[:, 1] << 20) | (c[:, 2] << 40)
+    take = np.flatnonzero(q)[inside]
+    had = len(dst_state["key"])
+    ukey, inv = np.unique(np.concatenate([dst_state["key"], moved]), return_inverse=True)
+    inv = inv.reshape(-1)
+    V = len(ukey)
+    acc = {"n": np.zeros(V, np.int64), "S": np.zeros((V, 3), np.int64), "C": np.zeros((V, 4), np.int64), "m": np.zeros(V, np.int64),
+           "first_seq": np.full(V, np.iinfo(np.int64).max), "last_seq": np.full(V, -1, np.int64)}
+    old, new = inv[:had], inv[had:]
+    for f in ("n", "S", "C", "m", "first_seq", "last_seq"):
+        acc[f][old] = dst_state[f]
+    nk = src_state["n"][take]
+    np.add.at(acc["n"], new, nk)
+    np.add.at(acc["S"], new, nk[:, None] * u)
+    np.add.at(acc["C"], new, src_state["C"][take])
+    np.add.at(acc["m"], new, src_state["m"][take])
+    np.minimum.at(acc["first_seq"], new, src_state["first_seq"][take])
+    np.maximum.at(acc["last_seq"], new, src_state["last_seq"][take])
+    dst_state.update(acc, key=ukey)
+    stats["claimed"] = V - had
+    if V > wd["capacity"]:
+        dst_state["overflowed"] = True
+    return stats
+
+
+def voxel_map_repose_brute(dst_state, src_state, corr, seq0=0, min_n=1, min_rows=1, since=0):
+    """voxel_map_repose voxel by voxel: a Python loop over the entries of src with a dict for dst, Python floats and ints only."""
+    corr, seq0, min_n, min_rows, since = _voxel_repose_setup(dst_state, src_state, corr, seq0, min_n, min_rows, since)
+    ws, wd = src_state["params"], dst_state["params"]
+    stats = dict.fromkeys(VOXEL_CARRY_STATS, 0)
+    dst_state["dropped"] += src_state["dropped"]
+    if src_state["overflowed"] or dst_state["overflowed"]:
+        dst_state["overflowed"] = True
+        stats["carried"] = -1
+        return stats
+    fields = ("n", "S", "C", "m", "first_seq", "last_seq")
+    vox = {int(key): [dst_state[f][i].tolist() for f in fields] for i, key in enumerate(dst_state["key"])}
+    had = len(vox)
+    for i, key in enumerate(src_state["key"].tolist()):
+        n, S, C, m, first, last = (src_state[f][i].tolist() for f in fields)
+        if not (n >= max(min_n, 1) and m >= min_rows and last >= since):
+            stats["filtered"] += 1
+            continue
+        w = [float(v) for v in corr[min(max(last - seq0, 0), len(corr) - 1)]]
+        p = [ws["lo"][a] + (float((key >> (20 * a)) & 0xFFFFF) + (float(S[a]) + 0.5 * float(n)) / (65536.0 * float(n))) * float(ws["size"]) for a in range(3)]
+        moved, u = 0, []
+        for a in range(3):
+            with np.errstate(invalid="ignore", over="ignore"):  # numpy scalars: inf and NaN by IEEE, where Python floats would raise
+                P = float(((np.float64(w[3 * a]) * p[0] + np.float64(w[3 * a + 1]) * p[1]) + np.float64(w[3 * a + 2]) * p[2]) + np.float64(w[9 + a]))
+            if not (wd["lo"][a] < P < wd["hi"][a]):  # false for NaN, and for inf: lo and hi are finite
+                moved = None
+                break
+            t = (P - wd["lo"][a]) / float(wd["size"])
+            c = min(int(t), wd["cells"][a] - 1)
+            u.append(min(int((t - float(c)) * 65536.0), 65535))
+            moved |= c << (20 * a)
+        if moved is None:
+            stats["outside"] += 1
+            continue
+        stats["carried"] += 1
+        v = vox.setdefault(moved, [0, [0, 0, 0], [0, 0, 0, 0], 0, None, None])
+        v[0] += n
+        v[1] = [v[1][a] + n * u[a] for a in range(3)]
+        v[2] = [v[2][j] + C[j] for j in range(4)]
+        v[3] += m
+        v[4], v[5] = first if v[4] is None else min(v[4], first), last if v[5] is None else max(v[5], last)
+    keys = sorted(vox)
+    V = len(keys)
+    dst_state.update(key=np.array(keys, np.int64).reshape(V), n=np.array([vox[k][0] for k in keys], np.int64).reshape(V),
+                     S=np.array([vox[k][1] for k in keys], np.int64).reshape(V, 3), C=np.array([vox[k][2] for k in keys], np.int64).reshape(V, 4),
+                     m=np.array([vox[k][3] for k in keys], np.int64).reshape(V), first_seq=np.array([vox[k][4] for k in keys], np.int64).reshape(V),
+                     last_seq=np.array([vox[k][5] for k in keys], np.int64).reshape(V))
+    stats["claimed"] = V - had
+    if V > wd["capacity"]:
+        dst_state["overflowed"] = True
+    return stats
+
+
+def _pose_mul(a, b):
+    """a o b of two [12] motions (R row-major, then t): (Ra Rb | Ra tb + ta), in double."""
+    Ra, Rb = a[:9].reshape(3, 3), b[:9].reshape(3, 3)
+    return np.concatenate([(Ra @ Rb).reshape(9), Ra @ b[9:] + a[9:]])
+
+
+def _pose_inv(a):
+    """The rigid inverse (R^T | -R^T t) of a [12] motion."""
+    Rt = a[:9].reshape(3, 3).T
+    return np.concatenate([Rt.reshape(9), -(Rt @ a[9:])])
+
+
+def _pose_V(om, angle):
+    """The matrix V of se(3)'s exponential: exp((om, v)) = (exp(om) | V v)."""
+    K = np.array([[0.0, -om[2], om[1]], [om[2], 0.0, -om[0]], [-om[1], om[0], 0.0]])
+    if angle > 1e-2:
+        return np.eye(3) + ((1.0 - np.cos(angle)) / (angle * angle)) * K + ((angle - np.sin(angle)) / (angle ** 3)) * (K @ K)
+    a2 = angle * angle  # the series: the closed forms cancel below; the terms left out are below 3e-17
+    return np.eye(3) + (0.5 - a2 / 24.0 + a2 * a2 / 720.0) * K + (1.0 / 6.0 - a2 / 120.0 + a2 * a2 / 5040.0) * (K @ K)
+
+
+def pose_exp(xi):
+    """exp of xi = (om [3] radians, v [3]) in se(3) as a [12] motion: the rotation is _flow_exp's, the translation V(om) v."""
+    xi = np.asarray(xi, np.float64).reshape(6)
+    R, angle = _flow_exp(xi[:3])
+    return np.concatenate([R.reshape(9), _pose_V(xi[:3], angle) @ xi[3:]])
+
+
+def pose_log(pose):
+    """log of a rigid [12] motion in se(3): (om, v) float64 [6] with pose_exp(pose_log(P)) = P.  ValueError for a rotation within 1e-6
+    of pi, where the axis is not determined by R - R^T."""
+    P = np.asarray(pose, np.float64).reshape(12)
+    R = P[:9].reshape(3, 3)
+    a = 0.5 * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])  # sin(angle) * axis
+    s = float(np.sqrt((a * a).sum()))
+    angle = float(np.arctan2(s, 0.5 * (np.trace(R) - 1.0)))
+    if not np.isfinite(angle) or angle > np.pi - 1e-6:
+        raise ValueError("the rotation is within 1e-6 of pi (or not finite): its logarithm is not determined")
+    om = a * (angle / s) if s > 1e-12 else a
+    return np.concatenate([om, np.linalg.solve(_pose_V(om, angle), P[9:])])
+
+
+def _poses_12(poses, what):
+    p = np.ascontiguousarray(poses, np.float64)
+    if p.ndim != 2 or p.shape[1] != 12:
+        raise ValueError("%s must be float64 [N,12], got shape %s" % (what, p.shape))
+    return p
+
+
+def pose_corrections(old, new):
+    """float64 [N,12]: new[k] o old[k]^-1 with the rigid inverse (R^T | -R^T t) - what moves a world point placed under old[k] to where
+    new[k] places it: the corrections voxel_map_repose and PlaceIndex.repose take, from any caller's pose graph.  old, new float64
+    [N,12] rigid poses in voxel_map_pose's layout."""
+    old, new = _poses_12(old, "old"), _poses_12(new, "new")
+    if old.shape != new.shape:
+        raise ValueError("old and new must hold one pose per frame each, got %s and %s" % (old.shape, new.shape))
+    return np.ascontiguousarray(np.array([_pose_mul(new[k], _pose_inv(old[k])) for k in range(len(old))]).reshape(len(old), 12))
+
+
+def loop_spread(poses, i, j, target, weights=None):
+    """Spreads the error of one confirmed loop along the chain of poses: float64 [N,12] from poses [N,12], the frames i < j the loop
+    ties and `target` [12], the pose frame j should have (the loop's: PlaceIndex.guess refined by VoxelMap.localize and .align).  E =
+    poses[j]^-1 o target, xi = log E in se(3) (pose_log).  P'_k = P_k for k < i, bit for bit; P'_k = P_k o exp(f_k xi) for i <= k <= j, so
+    P'_j = target; P'_k = target o P_j^-1 o P_k for k > j: the frames behind the loop keep their motions relative to frame j.  f_k = (k - i)
+    / (j - i), or with weights - [j - i], the weight of the step from frame i + s to i + s + 1, or [N - 1], of every step of the chain; say
+    the distance travelled - the cumulative weight from i to k over its total.  Not a solver: one loop, no covariance.  ValueError for i
+    >= j or outside the chain, a rotation of E within 1e-6 of pi, and weights that are negative, not finite or sum to zero."""
+    P = _poses_12(poses, "poses")
+    N = len(P)
+    i, j = _whole(i, "i"), _whole(j, "j")
+    if not 0 <= i < j < N:
+        raise ValueError("loop_spread needs 0 <= i < j < %d, got i = %d, j = %d" % (N, i, j))
+    target = np.asarray(target, np.float64)
+    if target.shape != (12,):
+        raise ValueError("target must be float64 [12], got shape %s" % (target.shape,))
+    if weights is None:
+        f = np.arange(j - i + 1, dtype=np.float64) / float(j - i)
+    else:
+        w = np.asarray(weights, np.float64)
+        if w.shape == (N - 1,) and N - 1 != j - i:
+            w = w[i:j]
+        if w.shape != (j - i,):
+            raise ValueError("weights must be [%d] or [%d], got shape %s" % (j - i, N - 1, w.shape))
+        if not np.isfinite(w).all() or (w < 0).any() or not w.sum() > 0:
+            raise ValueError("weights must be finite, not negative, and sum to more than zero")
+        f = np.concatenate([[0.0], np.cumsum(w)]) / w.sum()
+        f[-1] = 1.0
+    xi = pose_log(_pose_mul(_pose_inv(P[j]), target))
+    out = P.copy()
+    for k in range(i, j + 1):
+        out[k] = _pose_mul(P[k], pose_exp(f[k - i] * xi))
+    tail = _pose_mul(target, _pose_inv(P[j]))
+    for k in range(j + 1, N):
+        out[k] = _pose_mul(tail, P[k])
+    return out
+
+
+def pose_repose(poses, seq, corr, seq0=0):
+    """float64 [N,12]: corr[k] o poses[r] with k = min(max(seq[r] - seq0, 0), K - 1) - voxel_map_repose's index rule on the sequence
+    numbers seq [N] of stored poses: what PlaceIndex.repose makes of its key poses."""
+    P = _poses_12(poses, "poses")
+    corr = _poses_12(corr, "corr")
+    seq = np.asarray(seq, np.int64)
+    seq0 = _whole(seq0, "seq0")
+    if seq.shape != (len(P),) or not 1 <= len(corr) <= VOXEL_REPOSE_CORR_MAX or not 0 <= seq0 <= VOXEL_MAP_SEQ_MAX:
+        raise ValueError("seq must be [%d], corr [K,12] with K in 1 .. 2^22 and seq0 in 0 .. 2^31 - 2" % len(P))
+    k = np.clip(seq - seq0, 0, len(corr) - 1)
+    return np.ascontiguousarray(np.array([_pose_mul(corr[k[r]], P[r]) for r in range(len(P))]).reshape(len(P), 12))
 
 
 VOXEL_CARVE_REACH_MAX = 1023  # cells a ray of voxel_map_carve may span on its major axis: 2 k d + nst stays below 2^22
@@ -5331,6 +5590,11 @@ def main(argv=None):
                              "which is searched among the frames at least MIN_GAP (default 50) before it under every rotation and then "
                              "stored; a best candidate with 256 sad <= ACCEPT norm (default 64) writes one line to FILE: 'frame key shift "
                              "sad norm yaw_deg' - the frame it recognised, the shift in sectors and the heading against that frame in degrees")
+    parser.add_argument("--voxel-repose", type=str, default="", metavar="CORRECTED_POSES",
+                        help="with --voxel-map: at the end of the run, re-pose the map from the poses its frames were inserted at to those of "
+                             "CORRECTED_POSES - a file as --poses takes, the result of a pose graph or of loop_spread - (rig.VoxelMap.repose: "
+                             "every voxel moved by the correction of the frame that saw it last, into the box of the corrected "
+                             "trajectory); writes <FILE>.reposed.ply beside the map and prints the counts")
     parser.add_argument("--temporal", type=str, default="", metavar="DIR[,TOL_PX[,MODE]]",
                         help="with --batch and --odometry: every frame's disparity map compared with the map of the frame before it, warped "
                              "under the fitted motion (StereoRig.temporal, on the odometry's batches: the front end and engine run once "
@@ -5486,6 +5750,8 @@ def main(argv=None):
             args.voxel_render_spec = cli_voxel_render_spec(args.voxel_render)
         except ValueError as e:
             parser.error("--voxel-render: %s" % e)
+    if args.voxel_repose and not args.voxel_map:
+        parser.error("--voxel-repose needs --voxel-map")
     if (args.voxel_window or args.voxel_forget) and not args.voxel_map:
         parser.error("--voxel-window and --voxel-forget need --voxel-map")
     if args.voxel_forget < 0:
@@ -5547,6 +5813,14 @@ def main(argv=None):
             voxel_map_params(args.voxel_map_box[0], args.voxel_map_box[1], args.voxel, CLI_VOXEL_MAP_CAPACITY)
         except (OSError, ValueError) as e:
             parser.error("--poses / --voxel-map: %s" % e)
+        args.repose_rows = None
+        if args.voxel_repose:
+            try:
+                args.repose_rows = read_poses(args.voxel_repose, len(files))
+                args.repose_box = cli_voxel_map_box(args.repose_rows)
+                voxel_map_params(args.repose_box[0], args.repose_box[1], args.voxel, CLI_VOXEL_MAP_CAPACITY)
+            except (OSError, ValueError) as e:
+                parser.error("--voxel-repose: %s" % e)
     if args.occupancy_map:
         try:
             args.pose_rows = read_poses(args.poses, len(files))
@@ -5956,6 +6230,12 @@ def _run_batched(args, ldir, rdir, files):
             if args.voxel_align_spec is not None:
                 with open(os.path.splitext(args.voxel_map)[0] + ".aligned.txt", "w") as f:
                     f.write("".join(" ".join("%r" % float(v) for v in to) + "\n" for to in aligned_3d))
+            if args.repose_rows is not None:  # from where the frames went to where the corrected poses put them; the stages below read the re-posed map
+                fixed = voxel_map_pose(args.repose_rows[:, 0], args.repose_rows[:, 1], args.repose_rows[:, 2])
+                box = voxel_map_params(args.repose_box[0], args.repose_box[1], args.voxel, CLI_VOXEL_MAP_CAPACITY)
+                text = cli_voxel_carry_text(model.repose(pose_corrections(np.asarray(aligned_3d, np.float64).reshape(-1, 12), fixed), params=box))
+                out = os.path.splitext(args.voxel_map)[0] + ".reposed.ply"
+                print("voxel map re-posed: %s; %d voxels written to %s" % (text, model.write_ply(out), out))
             if args.voxel_flatten_spec is not None:  # the planner's map from the voxel map's evidence
                 x_range, y_range, scale, step, height = args.voxel_flatten_spec
                 stem = os.path.splitext(args.voxel_map)[0] + ".flat"
