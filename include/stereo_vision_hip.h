@@ -116,13 +116,19 @@
  *      rings x sectors bytes that a turn of the vehicle rolls along the sectors (AC1), and query descriptors searched among stored ones
  *      under every roll, the best key per query by the least sum of absolute differences over the sum of both descriptors (AC2).
  *      stereo_vision.sv.place_descriptor and place_match state the definitions in numpy; place_yaw and place_guess turn a key and a
- *      shift into the guess the voxel map's localisation takes.  The solver for a confirmed loop stays with the caller; its result goes to (AD).
+ *      shift into the guess the voxel map's localisation takes.  The solver for the confirmed loops is (AE); its result goes to (AD).
  *
  *  (AD) Behind (AC), (S) and (Q): a voxel map re-posed after a loop closure (sv_voxel_repose_device) - every voxel of a map of (Q) moved
  *      by the rigid correction of the frame that saw it last, one of K corrections chosen by the voxel's last_seq, and accumulated into a
- *      second map with (Q)'s integer atomics: what a caller's pose graph returns - a corrected pose per frame - applied to a map whose
- *      frames are gone.  stereo_vision.sv.voxel_map_repose states the definition in numpy; pose_corrections and loop_spread are the
- *      host's helpers for one confirmed loop.
+ *      second map with (Q)'s integer atomics: what the pose graph of (AE) returns - a corrected pose per frame - applied to a map whose
+ *      frames are gone.  stereo_vision.sv.voxel_map_repose states the definition in numpy; pose_corrections turns the old and the new
+ *      poses into the corrections, and loop_spread is the host's helper for one confirmed loop without a graph.
+ *
+ *  (AE) Between (AC) and (AD): the pose graph of confirmed loops (sv_pose_graph_*) - a pose per frame, odometry edges along the chain and
+ *      loop edges across it, each a measured relative pose with two weights; one Gauss-Newton linearisation in doubles without
+ *      trigonometry (AE1) and preconditioned conjugate gradients on it, matrix-free, with the state of the iteration on the device
+ *      (AE2).  stereo_vision.sv.pose_graph_linearize, pose_graph_pcg and pose_graph_sum state the definitions in numpy;
+ *      pose_graph_optimize is the loop of rounds on the host, with the gate that switches a wrong loop off.
  *
  * All sv_* functions return SV_OK (0) or a negative sv_status; sv_last_error() gives the text.
  * Nothing in this library calls exit().
@@ -2084,6 +2090,62 @@ int sv_debug_place(int flags);
  * (The name has no "voxel_map" in it: tests/test_voxel_map.py pins the set of "sv_*voxel_map*(" declarations to group (Q)'s seven.) */
 int sv_voxel_repose_device(void *dst, size_t dst_bytes, const sv_voxel_map_spec *dst_spec, const void *src, size_t src_bytes, const sv_voxel_map_spec *src_spec,
                            const double *corr, int n_corr, int seq0, int64_t min_n, int64_t min_rows, int since, int64_t *stats, void *stream);
+
+/* ---- (AE) the pose graph of confirmed loops: poses + relative-pose edges -> one linearisation; the linearisation -> a step per pose by PCG ---- */
+
+/* A graph holds n_poses poses (1 .. 2^20), double [12] each - R row-major, then t, world from frame, (Q)'s layout -, a byte per pose that
+ * is not 0 where the pose is held fixed, and n_edges edges (0 .. 2^22): the poses i != j it ties (int32, in either order, duplicates
+ * allowed), the measured Z = P_i^-1 o P_j (double [12]) and the weights w = (w_rot, w_trans) >= 0 as they count now - a switched-off edge
+ * has both 0.  The incidence lists come from the host (stereo_vision.sv.pose_graph_words): row_start int32 [n_poses + 1] and inc int32 [2
+ * n_edges]; pose k's entries are inc[row_start[k] .. row_start[k + 1]), ascending, 2 e where k is edge e's j and 2 e + 1 where it is its i.
+ * Every double is formed one operation at a time in the order stereo_vision.sv.pose_graph_linearize and pose_graph_pcg state, without
+ * a fused multiply-add, a trigonometric function or a square root, so the device equals the numpy forms bit for bit.  No entry reads the
+ * data it is given: an edge or an entry that points outside the graph is skipped by the kernels, everything else is the caller's to
+ * check (rig.PoseGraph and stereo_vision.sv.pose_graph do).  lam > 0 is added to the diagonal of H; tol >= 0 is PCG's.  reserved: 0. */
+typedef struct {
+    double lam, tol;
+    int32_t reserved[12];
+} sv_pose_graph_spec;
+
+/* (AE1) One linearisation about P_k <- P_k o exp(delta_k), delta = (om, v):
+ *   M       P_j^-1 o P_i per edge: all a linearised edge needs, since d r / d delta_j = I and d r / d delta_i = -Ad_M, Ad_M = [[R, 0], [[t]x R, R]]
+ *   Wr      W r, r = (a, t_D) of D = Z^-1 o P_i^-1 o P_j with a = 1/2 vee(R_D - R_D^T): no trigonometry
+ *   chi2    w_rot |a|^2 + w_trans |t_D|^2
+ *   b       - sum J^T W r per pose over its entries in ascending order; 0 for a fixed pose
+ *   factor  the 6 x 6 diagonal block of H = sum J^T W J + lam I per pose, 21 words (row p, column q <= p), factored in place as L D L^T
+ * Enqueues two kernels on `stream` (a hipStream_t, NULL = the default stream) - a lane per edge, then a lane per pose - and does not wait;
+ * nothing is allocated.
+ *   poses [n_poses][12], fixed uint8 [n_poses], ei, ej int32 [n_edges], Z [n_edges][12], w [n_edges][2], row_start, inc : device, inputs
+ *   M [n_edges][12], Wr [n_edges][6], chi2 [n_edges], b [n_poses][6], factor [n_poses][21] : device doubles, outputs
+ * Returns SV_OK, SV_ERR_HIP, or SV_ERR_ARG - nothing enqueued, the text in sv_last_error(NULL) - for: n_poses or n_edges outside their
+ * ranges; a NULL spec, a reserved word that is not 0, lam not finite or <= 0, tol negative or not finite; a NULL or misaligned array (the
+ * edges' may be NULL where n_edges is 0); an output that shares a byte with an input or another output. */
+int sv_pose_graph_linearize_device(const double *poses, const uint8_t *fixed, int n_poses, const int32_t *ei, const int32_t *ej, const double *Z, const double *w,
+                                   int n_edges, const int32_t *row_start, const int32_t *inc, const sv_pose_graph_spec *spec, double *M, double *Wr, double *chi2,
+                                   double *b, double *factor, void *stream);
+
+/* Host only: the bytes of the workspace sv_pose_graph_pcg_device needs: 64 of state, four vectors of 6 doubles per pose, 6 doubles per
+ * edge, five rows of a double per 256 poses, each part rounded up to 16.  SV_ERR_ARG (bytes untouched) for a NULL bytes or a count
+ * outside its range. */
+int sv_pose_graph_workspace(int n_poses, int n_edges, size_t *bytes);
+
+/* (AE2) Preconditioned conjugate gradients on H x = b from x = 0, H x formed in two passes - g_e = W (x_j - Ad_M x_i) per edge; per pose, over
+ * its entries in ascending order, + g_e where it is j and - Ad_M^T g_e where it is i, then + lam x_k -, the preconditioner (AE1)'s factor.
+ * A dot product is the poses' six products added left to right, reduced in chunks of 256 by a halving tree and the chunks' partials by
+ * the same rule (stereo_vision.sv.pose_graph_sum); every workgroup finishes it for itself, no atomic is used.  The state words - int32
+ * iteration, int32 done, double rr, double rr0 - are the first 24 bytes of the workspace: done is set, in double on the device, once rr
+ * <= tol^2 rr0, and from then on every kernel returns at its first instruction, so x, iteration and rr stay what they were.
+ * Enqueues, on `stream` and without waiting: for iter0 == 0 the start (two kernels: x = 0, r = b, z, the state words); `iters` iterations
+ * of three kernels each, numbered iter0 .. iter0 + iters - 1; one workgroup that brings rr and done up to date.  A solve is continued by
+ * a call with iter0 = the iterations enqueued so far and everything else as before.
+ *   fixed, ei, ej, w, row_start, inc : as (AE1) took them;  M, b, factor : as it wrote them
+ *   x         : double [n_poses][6] device, written from iter0 == 0 on
+ *   workspace : device, 16-byte aligned, at least sv_pose_graph_workspace's bytes, untouched between the calls of one solve
+ * Returns as (AE1), and SV_ERR_ARG besides for iter0 outside 0 .. 2^30, iters outside 0 .. 1024, a workspace that is NULL, misaligned or
+ * too small, and x or the workspace sharing a byte with one another or an input. */
+int sv_pose_graph_pcg_device(const uint8_t *fixed, int n_poses, const int32_t *ei, const int32_t *ej, const double *w, int n_edges, const int32_t *row_start,
+                             const int32_t *inc, const double *M, const double *b, const double *factor, const sv_pose_graph_spec *spec, int iter0, int iters,
+                             double *x, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- (A)the reference's exported symbols ------------------------------------------------------------- */
 

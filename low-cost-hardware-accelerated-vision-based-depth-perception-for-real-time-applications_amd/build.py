@@ -13,9 +13,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libstereo_vision_hip.so")
-SOURCES = ["kernels.hip", "delaunay_gpu.hip", "legacy_kernels.hip", "rig_kernels.hip", "top_view_kernels.hip", "box_kernels.hip", "cloud_kernels.hip", "ground_kernels.hip", "stixel_kernels.hip", "voxel_kernels.hip", "occupancy_kernels.hip", "occupancy_map_kernels.hip", "map_match_kernels.hip", "clearance_kernels.hip", "cost_kernels.hip", "frontier_kernels.hip", "view_kernels.hip", "voxel_map_kernels.hip", "voxel_match_kernels.hip", "voxel_carry_kernels.hip", "voxel_carve_kernels.hip", "voxel_render_kernels.hip", "voxel_flatten_kernels.hip", "voxel_cluster_kernels.hip", "voxel_align_kernels.hip", "voxel_normal_kernels.hip", "flow_kernels.hip", "warp_kernels.hip", "track_kernels.hip", "place_kernels.hip", "voxel_repose_kernels.hip", "engine.cpp", "host_stage.cpp", "legacy.cpp", "calib.cpp", "rig.cpp", "top_view.cpp", "box_positions.cpp",
-           "cloud.cpp", "ground.cpp", "stixels.cpp", "voxel.cpp", "occupancy.cpp", "occupancy_map.cpp", "map_match.cpp", "clearance.cpp", "cost.cpp", "frontier.cpp", "view.cpp", "voxel_map.cpp", "voxel_match.cpp", "voxel_carry.cpp", "voxel_carve.cpp", "voxel_render.cpp", "voxel_flatten.cpp", "voxel_cluster.cpp", "voxel_align.cpp", "voxel_normals.cpp", "flow.cpp", "warp.cpp", "track.cpp", "place.cpp", "voxel_repose.cpp", "dma_lanes.cpp"]
-HEADERS = ["sv_kernels.h", "host_stage.h", "calib.h", "rig_kernels.h", "reproject.h", "top_view_kernels.h", "box_kernels.h", "cloud_kernels.h", "ground_kernels.h", "stixel_kernels.h", "voxel_kernels.h", "occupancy_kernels.h", "occupancy_map_kernels.h", "occupancy_map_cells.h", "map_match_kernels.h", "clearance_kernels.h", "cost_kernels.h", "frontier_kernels.h", "view_kernels.h", "voxel_map_kernels.h", "voxel_map_table.h", "voxel_match_kernels.h", "voxel_carry_kernels.h", "voxel_carve_kernels.h", "voxel_render_kernels.h", "voxel_flatten_kernels.h", "voxel_cluster_kernels.h", "voxel_align_kernels.h", "voxel_normal_kernels.h", "flow_kernels.h", "flow_point.h", "warp_kernels.h", "track_kernels.h", "place_kernels.h", "voxel_repose_kernels.h", "stage_glue.h", "dma_lanes.h", "wave_ops.h", os.path.join("..", "..", "include", "stereo_vision_hip.h")]
+SOURCES = ["kernels.hip", "delaunay_gpu.hip", "legacy_kernels.hip", "rig_kernels.hip", "top_view_kernels.hip", "box_kernels.hip", "cloud_kernels.hip", "ground_kernels.hip", "stixel_kernels.hip", "voxel_kernels.hip", "occupancy_kernels.hip", "occupancy_map_kernels.hip", "map_match_kernels.hip", "clearance_kernels.hip", "cost_kernels.hip", "frontier_kernels.hip", "view_kernels.hip", "voxel_map_kernels.hip", "voxel_match_kernels.hip", "voxel_carry_kernels.hip", "voxel_carve_kernels.hip", "voxel_render_kernels.hip", "voxel_flatten_kernels.hip", "voxel_cluster_kernels.hip", "voxel_align_kernels.hip", "voxel_normal_kernels.hip", "flow_kernels.hip", "warp_kernels.hip", "track_kernels.hip", "place_kernels.hip", "voxel_repose_kernels.hip", "pose_graph_kernels.hip", "engine.cpp", "host_stage.cpp", "legacy.cpp", "calib.cpp", "rig.cpp", "top_view.cpp", "box_positions.cpp",
+           "cloud.cpp", "ground.cpp", "stixels.cpp", "voxel.cpp", "occupancy.cpp", "occupancy_map.cpp", "map_match.cpp", "clearance.cpp", "cost.cpp", "frontier.cpp", "view.cpp", "voxel_map.cpp", "voxel_match.cpp", "voxel_carry.cpp", "voxel_carve.cpp", "voxel_render.cpp", "voxel_flatten.cpp", "voxel_cluster.cpp", "voxel_align.cpp", "voxel_normals.cpp", "flow.cpp", "warp.cpp", "track.cpp", "place.cpp", "voxel_repose.cpp", "pose_graph.cpp", "dma_lanes.cpp"]
+HEADERS = ["sv_kernels.h", "host_stage.h", "calib.h", "rig_kernels.h", "reproject.h", "top_view_kernels.h", "box_kernels.h", "cloud_kernels.h", "ground_kernels.h", "stixel_kernels.h", "voxel_kernels.h", "occupancy_kernels.h", "occupancy_map_kernels.h", "occupancy_map_cells.h", "map_match_kernels.h", "clearance_kernels.h", "cost_kernels.h", "frontier_kernels.h", "view_kernels.h", "voxel_map_kernels.h", "voxel_map_table.h", "voxel_match_kernels.h", "voxel_carry_kernels.h", "voxel_carve_kernels.h", "voxel_render_kernels.h", "voxel_flatten_kernels.h", "voxel_cluster_kernels.h", "voxel_align_kernels.h", "voxel_normal_kernels.h", "flow_kernels.h", "flow_point.h", "warp_kernels.h", "track_kernels.h", "place_kernels.h", "voxel_repose_kernels.h", "pose_graph_kernels.h", "stage_glue.h", "dma_lanes.h", "wave_ops.h", os.path.join("..", "..", "include", "stereo_vision_hip.h")]
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function", "-Wno-unused-value"]
 HOST = ["-x", "c++", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"]
 DEVICE = ["--offload-arch=gfx950", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-gpu-rdc"]

@@ -586,6 +586,11 @@ class SvPlaceSpec(ctypes.Structure):
                 ("rings", ctypes.c_int32), ("sectors", ctypes.c_int32), ("reserved", ctypes.c_int32 * 10)]
 
 
+class SvPoseGraphSpec(ctypes.Structure):
+    """sv_pose_graph_spec of include/stereo_vision_hip.h (AE)."""
+    _fields_ = [("lam", ctypes.c_double), ("tol", ctypes.c_double), ("reserved", ctypes.c_int32 * 12)]
+
+
 def _signatures():
     """The table below: per stage group of the C API, (D) to (S), its functions and per function (restype, argtypes), parameter by
     parameter as include/stereo_vision_hip.h declares them - tests/test_stage_signatures.py holds the two against each other."""
@@ -730,6 +735,11 @@ def _signatures():
         },
         "voxel_repose": {  # (AD)
             "sv_voxel_repose_device": (ci, [vp, sz, vm, vp, sz, vm, vp, ci, ci, i64, i64, ci, vp, vp]),
+        },
+        "pose_graph": {  # (AE)
+            "sv_pose_graph_linearize_device": (ci, [vp, vp, ci, vp, vp, vp, vp, ci, vp, vp, P(SvPoseGraphSpec), vp, vp, vp, vp, vp, vp]),
+            "sv_pose_graph_workspace": (ci, [ci, ci, P(sz)]),
+            "sv_pose_graph_pcg_device": (ci, [vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, P(SvPoseGraphSpec), ci, ci, vp, vp, sz, vp]),
         },
     }
 
@@ -3338,6 +3348,181 @@ def place_match(q_desc, q_words, q_ring, q_seq, k_desc, k_words, k_ring, k_seq, 
                                      torch.cuda.current_stream(dev).cuda_stream)
     _check(rc, "sv_place_match_device")
     return res  # ws goes back to torch's allocator, which hands it out again on this stream only: behind the kernels
+
+
+def pose_graph_lib():
+    """The library with the signatures of group (AE) declared."""
+    return _bind("pose_graph")
+
+
+def _pose_graph_tensor(t, dtype, shape, dev, name):
+    """A contiguous tensor of `dtype` and `shape` on dev from a tensor there or a numpy array (uploaded)."""
+    import torch
+    if not isinstance(t, torch.Tensor):
+        try:
+            t = torch.from_numpy(np.ascontiguousarray(t, dtype={torch.float64: np.float64, torch.int32: np.int32, torch.uint8: np.uint8}[dtype]).reshape(shape)).to(dev)
+        except (TypeError, ValueError):
+            raise ValueError("%s must be %s %s" % (name, str(dtype).replace("torch.", ""), list(shape)))
+    if t.dtype == torch.bool and dtype == torch.uint8:
+        t = t.to(torch.uint8)
+    if t.device != dev or t.dtype != dtype or tuple(t.shape) != tuple(shape):
+        raise ValueError("%s must be a %s tensor %s on %s" % (name, str(dtype).replace("torch.", ""), list(shape), dev))
+    return t.contiguous()
+
+
+def _pose_graph_spec(lam, tol):
+    lam, tol = float(lam), float(tol)
+    if not (lam > 0.0 and np.isfinite(lam)):
+        raise ValueError("lam must be a finite number > 0, got %r" % (lam,))
+    if not (tol >= 0.0 and np.isfinite(tol)):
+        raise ValueError("tol must be finite and not negative, got %r" % (tol,))
+    return SvPoseGraphSpec(lam, tol)
+
+
+def _pose_graph_edges(fixed, i, j, w, words, dev):
+    """fixed, i, j, w and the incidence lists as the C entries take them -> (N, E, the six tensors).  words: pose_graph_words' pair (numpy
+    or tensors), or None to make it here - which reads i and j back where they are tensors."""
+    import torch
+    from .stereo_vision import sv as _sv
+    N = int(fixed.shape[0]) if hasattr(fixed, "shape") else len(fixed)
+    E = int(i.shape[0]) if hasattr(i, "shape") else len(i)
+    if not (1 <= N <= _sv.POSE_GRAPH_POSES_MAX and 0 <= E <= _sv.POSE_GRAPH_EDGES_MAX):
+        raise ValueError("a pose graph holds 1 .. 2^20 poses and 0 .. 2^22 edges, got %d and %d" % (N, E))
+    if words is None:
+        as_np = lambda t: t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+        i_np, j_np = as_np(i).astype(np.int64), as_np(j).astype(np.int64)
+        if ((i_np < 0) | (i_np >= N) | (j_np < 0) | (j_np >= N) | (i_np == j_np)).any():
+            raise ValueError("an edge names a pose outside 0 .. %d, or one pose twice" % (N - 1))
+        words = _sv.pose_graph_words(N, i_np, j_np)
+    fixed = _pose_graph_tensor(fixed, torch.uint8, (N,), dev, "fixed")
+    i, j = _pose_graph_tensor(i, torch.int32, (E,), dev, "i"), _pose_graph_tensor(j, torch.int32, (E,), dev, "j")
+    w = _pose_graph_tensor(w, torch.float64, (E, 2), dev, "w")
+    row_start = _pose_graph_tensor(words[0], torch.int32, (N + 1,), dev, "row_start")
+    inc = _pose_graph_tensor(words[1], torch.int32, (2 * E,), dev, "inc")
+    return N, E, (fixed, i, j, w, row_start, inc)
+
+
+def pose_graph_linearize(poses, fixed, i, j, Z, w, lam, words=None, out=None):
+    """One linearisation of a pose graph - the definition of stereo_vision.sv.pose_graph_linearize on the GPU, bit for bit
+    (sv_pose_graph_linearize_device: two kernels, doubles, no atomics).  poses a CUDA float64 tensor [N,12]; fixed bool or uint8 [N], i,
+    j int32 [E], Z float64 [E,12], w float64 [E,2] - tensors on that device or numpy arrays, uploaded; words: pose_graph_words' pair, made
+    here where None; out: the dict of an earlier call of the same shape to write into.  -> {"M" [E,12], "Wr" [E,6], "chi2" [E], "b"
+    [N,6], "factor" [N,21]: float64 tensors, "words": the pair on the device}, enqueued on torch's current stream; nothing is read back
+    where words is given.  The checks of the graph are stereo_vision.sv.pose_graph's: this entry only skips what points outside.  CPU
+    tensors (or numpy arrays) run the numpy form and give numpy arrays."""
+    import torch
+    if not (isinstance(poses, torch.Tensor) and poses.is_cuda):
+        from .stereo_vision.sv import pose_graph_linearize as on_host
+        as_np = lambda t: t.cpu().numpy() if isinstance(t, torch.Tensor) else t
+        return on_host(as_np(poses), as_np(fixed), as_np(i), as_np(j), as_np(Z), as_np(w), lam, None if words is None else tuple(as_np(t) for t in words))
+    dev = poses.device
+    spec = _pose_graph_spec(lam, 0.0)
+    N, E, (fixed, i, j, w, row_start, inc) = _pose_graph_edges(fixed, i, j, w, words, dev)
+    poses = _pose_graph_tensor(poses, torch.float64, (N, 12), dev, "poses")
+    Z = _pose_graph_tensor(Z, torch.float64, (E, 12), dev, "Z")
+    res = _place_outputs(None if out is None else {k: v for k, v in out.items() if k != "words"},
+                         (("M", torch.float64, (E, 12)), ("Wr", torch.float64, (E, 6)), ("chi2", torch.float64, (E,)), ("b", torch.float64, (N, 6)),
+                          ("factor", torch.float64, (N, 21))), dev)
+    with torch.cuda.device(dev):
+        rc = pose_graph_lib().sv_pose_graph_linearize_device(poses.data_ptr(), fixed.data_ptr(), N, _ptr(i), _ptr(j), _ptr(Z), _ptr(w), E, row_start.data_ptr(), _ptr(inc),
+                                                             ctypes.byref(spec), _ptr(res["M"]), _ptr(res["Wr"]), _ptr(res["chi2"]), res["b"].data_ptr(),
+                                                             res["factor"].data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    _check(rc, "sv_pose_graph_linearize_device")
+    res["words"] = (row_start, inc)
+    return res
+
+
+def pose_graph_solve(fixed, i, j, w, lin, lam, max_iters=1000, tol=1e-8, round=16, x=None, workspace=None):
+    """Preconditioned conjugate gradients on a linearised pose graph - the definition of stereo_vision.sv.pose_graph_pcg on the GPU, bit
+    for bit (sv_pose_graph_pcg_device: three kernels per iteration, no atomics).  lin: pose_graph_linearize's dict, CUDA tensors; fixed,
+    i, j, w as given there.  x: a float64 tensor [N,6] to write into; workspace: a uint8 tensor of at least sv_pose_graph_workspace's
+    bytes to reuse.  The C entry is called in rounds of `round` iterations (1 .. 1024; the last is cut to what max_iters leaves) and
+    enqueues on torch's current stream without waiting; after each round the 16 bytes of iteration, done and rr are read back - the only
+    wait - and the rounds stop once done is set, or after max_iters.  -> x, {"iteration", "done", "rr", "rr0"}, the state as
+    pose_graph_pcg gives it.  CPU tensors (or numpy arrays) run the numpy form."""
+    import torch
+    from .stereo_vision import sv as _sv
+    if not (isinstance(lin["b"], torch.Tensor) and lin["b"].is_cuda):
+        as_np = lambda t: t.cpu().numpy() if isinstance(t, torch.Tensor) else t
+        return _sv.pose_graph_pcg(as_np(fixed), as_np(i), as_np(j), as_np(w), as_np(lin["M"]), as_np(lin["b"]), as_np(lin["factor"]), lam, max_iters, tol,
+                                  None if lin.get("words") is None else tuple(as_np(t) for t in lin["words"]))
+    dev = lin["b"].device
+    spec = _pose_graph_spec(lam, tol)
+    for v, lo, hi, what in ((max_iters, 0, 2 ** 30, "max_iters"), (round, 1, 1024, "round")):
+        if isinstance(v, bool) or int(v) != v or not lo <= v <= hi:
+            raise ValueError("%s must be an integer in %d .. %d, got %r" % (what, lo, hi, v))
+    N, E, (fixed, i, j, w, row_start, inc) = _pose_graph_edges(fixed, i, j, w, lin.get("words"), dev)
+    M = _pose_graph_tensor(lin["M"], torch.float64, (E, 12), dev, "M")
+    b = _pose_graph_tensor(lin["b"], torch.float64, (N, 6), dev, "b")
+    F = _pose_graph_tensor(lin["factor"], torch.float64, (N, 21), dev, "factor")
+    x = torch.empty((N, 6), dtype=torch.float64, device=dev) if x is None else _pose_graph_tensor(x, torch.float64, (N, 6), dev, "x")
+    L = pose_graph_lib()
+    nbytes = ctypes.c_size_t()
+    _check(L.sv_pose_graph_workspace(N, E, ctypes.byref(nbytes)), "sv_pose_graph_workspace")
+    if workspace is None:
+        workspace = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    elif not (isinstance(workspace, torch.Tensor) and workspace.device == dev and workspace.dtype == torch.uint8 and workspace.is_contiguous()
+              and workspace.numel() >= nbytes.value):
+        raise ValueError("workspace must be a contiguous uint8 tensor of at least %d bytes on %s" % (nbytes.value, dev))
+    enqueued, first, state = 0, True, None
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        while first or (enqueued < max_iters and not state[1]):
+            n = min(int(round), int(max_iters) - enqueued)
+            rc = L.sv_pose_graph_pcg_device(fixed.data_ptr(), N, _ptr(i), _ptr(j), _ptr(w), E, row_start.data_ptr(), _ptr(inc), _ptr(M), b.data_ptr(), F.data_ptr(),
+                                            ctypes.byref(spec), enqueued, n, x.data_ptr(), workspace.data_ptr(), workspace.numel(), stream)
+            _check(rc, "sv_pose_graph_pcg_device")
+            state = workspace[:16].cpu().numpy().view(np.int32)  # 16 bytes: the wait of the round
+            enqueued += n
+            first = False
+        words = workspace[:24].cpu().numpy()
+    return x, {"iteration": int(words[:4].view(np.int32)[0]), "done": bool(words[4:8].view(np.int32)[0]), "rr": float(words[8:16].view(np.float64)[0]),
+               "rr0": float(words[16:24].view(np.float64)[0])}
+
+
+def pose_graph_optimize(graph, rounds=10, gate=None, eps=1e-9, lam=1e-6, max_iters=None, tol=1e-8, device=None, device_edges=None, checked=False, wrap_step=None):
+    """stereo_vision.sv.pose_graph_optimize with every round's linearise and solve on the GPU: the same poses, costs, iterations and
+    switched-off edges as the numpy form, bit for bit, since the device gives the same delta and chi2 and everything else is the same
+    host code.  graph: stereo_vision.sv.pose_graph's dict; its arrays may be numpy arrays or tensors.  The GPU path is taken where
+    `device` names a CUDA device or graph["poses"] is a CUDA tensor; the edges, the incidence lists and the fixed mask are uploaded once,
+    poses and weights once per round, and delta [N,6] and chi2 [E] are read back once per round - the round's one wait besides the
+    solver's 16 bytes per sixteen iterations.  device_edges: {"i", "j", "Z"} as tensors on the device that hold the graph's edges already
+    (rig.PoseGraph's), used where they lie instead of an upload; checked=True: graph is stereo_vision.sv.pose_graph's own dict, all numpy,
+    and is not checked again; wrap_step: a function that takes the round's step and returns the one to call - a hook for timing.
+    max_iters None is max(1000, 20 N).  -> poses (numpy [N,12]), the stats dict."""
+    import torch
+    from .stereo_vision import sv as _sv
+    as_np = lambda t: t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+    if device is None and isinstance(graph["poses"], torch.Tensor) and graph["poses"].is_cuda:
+        device = graph["poses"].device
+    if checked:
+        host = graph
+    else:
+        host = {k: as_np(v) for k, v in graph.items()}
+        host = _sv.pose_graph(host["poses"], [(host["i"], host["j"], host["Z"], host["w"], host["kind"])], host["fixed"].astype(bool))
+    wrap = (lambda f: f) if wrap_step is None else wrap_step
+    if device is None:
+        return _sv.pose_graph_optimize(host, rounds, gate, eps, lam, max_iters, tol, step=wrap(_sv.pose_graph_step))
+    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    N, E = len(host["poses"]), len(host["i"])
+    kept = {}
+
+    def step(g, poses, w, lam, max_iters, tol, words):
+        if not kept:
+            on = device_edges or g
+            _, _, t = _pose_graph_edges(g["fixed"], on["i"], on["j"], w, words, dev)
+            kept["fixed"], kept["i"], kept["j"], kept["words"] = t[0], t[1], t[2], (t[4], t[5])
+            kept["Z"] = _pose_graph_tensor(on["Z"], torch.float64, (E, 12), dev, "Z")
+            kept["lin"], kept["x"] = None, None
+        P, w = torch.from_numpy(np.ascontiguousarray(poses)).to(dev), torch.from_numpy(np.ascontiguousarray(w)).to(dev)
+        kept["lin"] = pose_graph_linearize(P, kept["fixed"], kept["i"], kept["j"], kept["Z"], w, lam, kept["words"], kept["lin"])
+        x, state = pose_graph_solve(kept["fixed"], kept["i"], kept["j"], w, kept["lin"], lam, max_iters, tol, x=kept["x"])
+        kept["x"] = x
+        return x.cpu().numpy(), kept["lin"]["chi2"].cpu().numpy(), state
+
+    return _sv.pose_graph_optimize(host, rounds, gate, eps, lam, max_iters, tol, step=wrap(step))
 
 
 def debug_place(one_key=0):

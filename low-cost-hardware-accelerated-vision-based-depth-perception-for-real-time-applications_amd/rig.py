@@ -40,7 +40,7 @@ import ctypes
 
 import numpy as np
 
-from .engine import disparity_warp, flow_egomotion, flow_match, object_links, place_descriptor, place_match
+from .engine import disparity_warp, flow_egomotion, flow_match, object_links, place_descriptor, place_match, pose_graph_optimize
 from .engine import (SvParams, StereoEngine, StereoError, box_positions_from_disparity, box_spec, cloud_spec, compact_cloud_from_disparity,
                      ground_from_disparity, ground_spec, lib, occupancy_from_disparity, occupancy_fuse, occupancy_match, occupancy_clearance, clearance_paths, cost_cells, cost_routes, frontier_cells, frontier_clusters, occupancy_cost_to_goal, occupancy_view, occupancy_spec, pinned_array, reproject, split_clouds, stixel_spec, stixels_from_disparity,
                      top_view_from_disparity, top_view_spec, split_voxel_clouds, voxel_cloud_from_disparity, voxel_map_align, voxel_map_carry, voxel_map_clear, voxel_map_insert, voxel_map_match, voxel_map_new, voxel_map_repose,
@@ -600,6 +600,11 @@ class StereoRig:
         stereo_vision.sv.place_params' rings, sectors, z_lo, z_hi and r_min."""
         return PlaceIndex(_sv.place_params(r_max, **words), capacity, device=self.device)
 
+    def pose_graph(self, capacity=1024):
+        """-> PoseGraph: the pose graph of a drive on the rig's device: add_chain(odometry's poses), add_loop per confirmed loop,
+        optimize(), and corrections() into VoxelMap.repose and PlaceIndex.repose."""
+        return PoseGraph(capacity, device=self.device)
+
     def render_camera(self, size, footprint=1.0):
         """-> the camera VoxelMap.render draws into, from the rig's own Q, width and height and the map's voxel size
         (stereo_vision.sv.voxel_render_camera): `m.render(poses, rig.render_camera(m.params["size"]), transform=..., measured=d1)` is
@@ -1050,8 +1055,8 @@ class PlaceIndex:
     engine.place_descriptor and engine.place_match -, or "cpu": the numpy definitions on CPU tensors, the same methods and the same bits.
     params: stereo_vision.sv.place_params' dict; capacity: the keyframes the tensors hold at first - add() doubles it by one copy when it
     runs out.  count is the number of keyframes; desc, ring, words, seq and poses are the tensors, of which the first count rows are
-    used.  The solver for a confirmed loop stays with the caller: guess() gives the start VoxelMap.localize, then .align, refine;
-    repose() takes the corrections the solver - or stereo_vision.sv.loop_spread - arrives at, as VoxelMap.repose does."""
+    used.  guess() gives the start VoxelMap.localize, then .align, refine; the refined pose becomes a loop edge of a PoseGraph, and
+    repose() takes the corrections PoseGraph.corrections() - or stereo_vision.sv.loop_spread - arrives at, as VoxelMap.repose does."""
 
     def __init__(self, params, capacity, device="cuda"):
         import torch
@@ -1148,6 +1153,110 @@ class PlaceIndex:
         out = np.full((len(best), 4), np.nan)
         out[ok] = _sv.place_guess(self._pose_host[best[ok, 0]], best[ok, 1], self.params["sectors"])
         return ok, out
+
+
+class PoseGraph:
+    """The pose graph of a drive (include/stereo_vision_hip.h (AE), stereo_vision.sv.pose_graph_optimize): a pose per frame, the
+    odometry edges of the chain and the loop edges PlaceIndex and VoxelMap.localize / .align confirm, on `device` - a CUDA device:
+    engine.pose_graph_optimize, every round's linearise and solve in HIP -, or "cpu": the numpy definition, the same methods and the same
+    bits.  An edge is checked when it is added and kept twice: on the host, where the loop of rounds reads weights and kinds, and on the
+    device - i, j int32, Z float64 [.,12], of which the first n_edges rows are used -, where the kernels read it without another upload.
+    Both grow by doubling with one copy; the device's rows are filled by one copy per optimize() for all edges added since the last.
+    capacity is what they hold at first."""
+
+    _FIELDS = (("i", np.int32, ()), ("j", np.int32, ()), ("Z", np.float64, (12,)), ("w", np.float64, (2,)), ("kind", np.int32, ()))
+    _ON_DEVICE = ("i", "j", "Z")
+
+    def __init__(self, capacity=1024, device="cuda"):
+        import torch
+        if isinstance(capacity, bool) or int(capacity) != capacity or not 1 <= capacity <= _sv.POSE_GRAPH_EDGES_MAX:
+            raise ValueError("capacity must be an integer in 1 .. 2^22, got %r" % (capacity,))
+        self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.n_edges, self._sent, self.poses, self.fixed, self.optimized = 0, 0, np.zeros((0, 12)), np.zeros(0, bool), None
+        self._host = {}
+        self._allocate(int(capacity))
+
+    def _allocate(self, capacity):
+        import torch
+        for name, dtype, shape in self._FIELDS:
+            old = self._host.get(name)
+            self._host[name] = np.zeros((capacity,) + shape, dtype)
+            if old is not None:
+                self._host[name][:self.n_edges] = old[:self.n_edges]
+            if name in self._ON_DEVICE:
+                was = getattr(self, name, None)
+                setattr(self, name, torch.zeros((capacity,) + shape, dtype=torch.from_numpy(self._host[name][:0]).dtype, device=self.device))
+                if was is not None:
+                    getattr(self, name)[:self._sent].copy_(was[:self._sent])
+        self.capacity = capacity
+
+    def _add(self, edges):
+        n = len(edges[0])
+        if self.n_edges + n > _sv.POSE_GRAPH_EDGES_MAX:
+            raise ValueError("a pose graph holds at most 2^22 edges")
+        if self.n_edges + n > self.capacity:
+            self._allocate(min(_sv.POSE_GRAPH_EDGES_MAX, max(2 * self.capacity, self.n_edges + n)))
+        for (name, _, _), a in zip(self._FIELDS, edges):
+            self._host[name][self.n_edges:self.n_edges + n] = a
+        self.n_edges += n
+
+    def _send(self):
+        import torch
+        at = slice(self._sent, self.n_edges)
+        for name in self._ON_DEVICE:
+            getattr(self, name)[at] = torch.from_numpy(self._host[name][at]).to(self.device)
+        self._sent = self.n_edges
+
+    def add_chain(self, poses, w_rot=1.0, w_trans=1.0, fixed=(0,)):
+        """The poses of the drive, float64 [N,12] world from frame (numpy: odometry's), and the odometry edges between neighbours with
+        the weights given (scalars or [N - 1]); fixed: the poses held, indices or a bool mask.  Once per graph, before any loop."""
+        if len(self.poses):
+            raise ValueError("the graph has its chain already")
+        g = _sv.pose_graph(poses, [_sv.pose_graph_chain(poses, w_rot, w_trans)], fixed)  # the checks
+        self.poses, self.fixed = g["poses"], g["fixed"]
+        self._add((g["i"], g["j"], g["Z"], g["w"], g["kind"]))
+
+    def add_loop(self, i, j, Z, w_rot=1.0, w_trans=1.0):
+        """A loop edge: frames i and j and the measured Z = P_i^-1 o P_j [12] - say stereo_vision.sv.pose_between(the key's pose, the
+        pose VoxelMap.align arrived at for frame j) - with its weights.  ValueError for what stereo_vision.sv.pose_graph refuses of an
+        edge, and before add_chain."""
+        e = _sv.pose_graph_loop(i, j, Z, w_rot, w_trans)
+        N = len(self.poses)
+        if N == 0:
+            raise ValueError("add_chain comes first")
+        if not (0 <= e[0][0] < N and 0 <= e[1][0] < N) or e[0][0] == e[1][0]:
+            raise ValueError("a loop ties two different frames in 0 .. %d, got %d and %d" % (N - 1, e[0][0], e[1][0]))
+        if not np.isfinite(e[2]).all() or not np.isfinite(e[3]).all() or (e[3] < 0).any():
+            raise ValueError("Z must be finite, the weights finite and not negative")
+        self._add(e)
+
+    def graph(self):
+        """stereo_vision.sv.pose_graph's dict of the graph as it stands, on the host: views, checked when they were added."""
+        n = self.n_edges
+        return dict({"poses": self.poses, "fixed": self.fixed}, **{name: self._host[name][:n] for name, _, _ in self._FIELDS})
+
+    def optimize(self, rounds=10, gate=None, eps=1e-9, lam=1e-6, max_iters=None, tol=1e-8):
+        """stereo_vision.sv.pose_graph_optimize on the graph -> (the corrected poses float64 [N,12], numpy; the stats dict: costs, cost,
+        iterations, converged, off, rounds).  max_iters caps PCG per round, None is max(1000, 20 N); a round that stops at the cap is an
+        inexact step and shows as False in stats["converged"].  The poses of the chain stay what they were: corrections() holds the two
+        against each other."""
+        if not len(self.poses):
+            raise ValueError("add_chain comes first")
+        on = None
+        if self.device.type == "cuda":
+            self._send()
+            on = {name: getattr(self, name)[:self.n_edges] for name in self._ON_DEVICE}
+        self.optimized, stats = pose_graph_optimize(self.graph(), rounds, gate, eps, lam, max_iters, tol, device=self.device if on else None, device_edges=on, checked=True)
+        return self.optimized, stats
+
+    def corrections(self):
+        """stereo_vision.sv.pose_corrections(the chain's poses, the optimised ones): float64 [N,12], what VoxelMap.repose and
+        PlaceIndex.repose take."""
+        if self.optimized is None:
+            raise ValueError("optimize() has not run")
+        return _sv.pose_corrections(self.poses, self.optimized)
 
 
 class OccupancyMap:

@@ -162,8 +162,15 @@ voxel_map_repose (with voxel_map_repose_brute, the plain loop per voxel) is the 
 GPU): every voxel moved by the rigid correction of the frame that saw it last and accumulated into a second map, in the insert's
 integers.  pose_corrections, loop_spread (with pose_log and pose_exp) and pose_repose are the host's helpers in doubles, shared by the
 CPU and the GPU path: the corrections between two sets of poses, one loop's error spread along the chain, and the stored poses of a
-PlaceIndex under the same corrections.  The solver of a pose graph stays with the caller.  The reference has no counterpart (DESIGN.md
-§8).
+PlaceIndex under the same corrections.  The reference has no counterpart.
+
+pose_graph_linearize and pose_graph_pcg (with their *_brute twins, plain loops in Python floats) and pose_graph_sum are the definition
+of the pose graph of confirmed loops (sv_pose_graph_* of include/stereo_vision_hip.h (AE); engine.pose_graph_linearize /
+pose_graph_solve / pose_graph_optimize and rig.PoseGraph on the GPU): a trig-free residual per edge, the linearisation about a right
+perturbation that needs only M = P_j^-1 o P_i per edge, a matrix-free H in two passes, a block-Jacobi preconditioner factored as L D
+L^T, and conjugate gradients whose dot products follow one stated tree.  pose_graph, pose_graph_chain, pose_graph_loop and pose_between
+build a checked graph; pose_graph_optimize is the loop of Gauss-Newton rounds with the gate on loop edges, host code shared by the CPU
+and the GPU path, so that both give the same poses bit for bit.  The reference has no counterpart.
 """
 import argparse
 import ctypes
@@ -1062,7 +1069,7 @@ def _poses_12(poses, what):
 
 def pose_corrections(old, new):
     """float64 [N,12]: new[k] o old[k]^-1 with the rigid inverse (R^T | -R^T t) - what moves a world point placed under old[k] to where
-    new[k] places it: the corrections voxel_map_repose and PlaceIndex.repose take, from any caller's pose graph.  old, new float64
+    new[k] places it: the corrections voxel_map_repose and PlaceIndex.repose take, from pose_graph_optimize or any caller's pose graph.  old, new float64
     [N,12] rigid poses in voxel_map_pose's layout."""
     old, new = _poses_12(old, "old"), _poses_12(new, "new")
     if old.shape != new.shape:
@@ -1119,6 +1126,554 @@ def pose_repose(poses, seq, corr, seq0=0):
         raise ValueError("seq must be [%d], corr [K,12] with K in 1 .. 2^22 and seq0 in 0 .. 2^31 - 2" % len(P))
     k = np.clip(seq - seq0, 0, len(corr) - 1)
     return np.ascontiguousarray(np.array([_pose_mul(corr[k[r]], P[r]) for r in range(len(P))]).reshape(len(P), 12))
+
+
+# ---- (AE) the pose graph of confirmed loops: batch least squares by Gauss-Newton rounds, each solved by preconditioned conjugate
+# gradients.  Every double below is formed one operation at a time, in one stated order, with no fused multiply-add and no library sum:
+# the numpy forms, the *_brute loops and the kernels of pose_graph_kernels.hip give the same bits.  Trigonometry (pose_exp) stays in
+# pose_graph_optimize, which is host code shared by the CPU and the GPU path.
+
+POSE_GRAPH_POSES_MAX = 1 << 20
+POSE_GRAPH_EDGES_MAX = 1 << 22
+POSE_GRAPH_CHUNK = 256   # poses per chunk of a dot product: a workgroup of the pose kernels
+POSE_GRAPH_ROUND = 16    # PCG iterations the engine enqueues between two looks at the state words
+POSE_GRAPH_ODOMETRY, POSE_GRAPH_LOOP = 0, 1
+_PG_TRI = tuple((p, q) for p in range(6) for q in range(p + 1))          # the 21 words of a symmetric 6 x 6 block: row p, column q <= p
+_PG_AT = {pq: n for n, pq in enumerate(_PG_TRI)}
+_PG_DIAG = tuple(_PG_AT[(p, p)] for p in range(6))
+
+
+def pose_graph_sum(v):
+    """The sum every dot product of the pose graph ends in: the values in chunks of 256, zero padded, each chunk reduced by a halving
+    tree - v[k] + v[k + h] for k < h, h = 128 .. 1 -, and the chunks' partials by the same rule until one value is left.  No value
+    gives 0.0.  -> float."""
+    v = np.ascontiguousarray(v, np.float64).reshape(-1)
+    if v.size == 0:
+        return 0.0
+    while True:
+        c = -(-v.size // POSE_GRAPH_CHUNK)
+        a = np.zeros(c * POSE_GRAPH_CHUNK)
+        a[:v.size] = v
+        a = a.reshape(c, POSE_GRAPH_CHUNK)
+        h = POSE_GRAPH_CHUNK // 2
+        while h >= 1:
+            a = a[:, :h] + a[:, h:2 * h]
+            h //= 2
+        v = a[:, 0]
+        if c == 1:
+            return float(v[0])
+
+
+def pose_graph_sum_brute(v):
+    v = [float(t) for t in np.asarray(v, np.float64).reshape(-1)]
+    if not v:
+        return 0.0
+    while True:
+        partials = []
+        for c0 in range(0, len(v), POSE_GRAPH_CHUNK):
+            a = v[c0:c0 + POSE_GRAPH_CHUNK]
+            a += [0.0] * (POSE_GRAPH_CHUNK - len(a))
+            h = POSE_GRAPH_CHUNK // 2
+            while h >= 1:
+                for k in range(h):
+                    a[k] = a[k] + a[k + h]
+                h //= 2
+            partials.append(a[0])
+        v = partials
+        if len(v) == 1:
+            return v[0]
+
+
+def pose_graph_words(n_poses, i, j):
+    """The incidence lists of a graph, CSR: -> row_start int32 [N + 1], inc int32 [2 E].  Pose k's entries are inc[row_start[k] :
+    row_start[k + 1]], ascending; an entry is 2 e for edge e where k is its j, 2 e + 1 where k is its i.  A stable sort on the host."""
+    i, j = np.asarray(i, np.int64).reshape(-1), np.asarray(j, np.int64).reshape(-1)
+    pose = np.stack([j, i], 1).reshape(-1)
+    order = np.argsort(pose, kind="stable")
+    row_start = np.concatenate([[0], np.cumsum(np.bincount(pose, minlength=n_poses))])
+    return row_start.astype(np.int32), order.astype(np.int32)
+
+
+def _pg_mv(R, x):
+    return np.stack([(R[..., 3 * a] * x[..., 0] + R[..., 3 * a + 1] * x[..., 1]) + R[..., 3 * a + 2] * x[..., 2] for a in range(3)], -1)
+
+
+def _pg_mtv(R, x):
+    return np.stack([(R[..., a] * x[..., 0] + R[..., 3 + a] * x[..., 1]) + R[..., 6 + a] * x[..., 2] for a in range(3)], -1)
+
+
+def _pg_cross(t, u):
+    return np.stack([t[..., 1] * u[..., 2] - t[..., 2] * u[..., 1], t[..., 2] * u[..., 0] - t[..., 0] * u[..., 2],
+                     t[..., 0] * u[..., 1] - t[..., 1] * u[..., 0]], -1)
+
+
+def _pg_ad(M, x):
+    """Ad_M x of x = (om, v): (R om, t x (R om) + R v)."""
+    u = _pg_mv(M[..., :9], x[..., :3])
+    return np.concatenate([u, _pg_cross(M[..., 9:], u) + _pg_mv(M[..., :9], x[..., 3:])], -1)
+
+
+def _pg_adt(M, g):
+    """Ad_M^T g of g = (g_rot, g_trans): (R^T (g_rot - t x g_trans), R^T g_trans)."""
+    return np.concatenate([_pg_mtv(M[..., :9], g[..., :3] - _pg_cross(M[..., 9:], g[..., 3:])), _pg_mtv(M[..., :9], g[..., 3:])], -1)
+
+
+def _pg_dot6(a, b):
+    s = a[..., 0] * b[..., 0]
+    for c in range(1, 6):
+        s = s + a[..., c] * b[..., c]
+    return s
+
+
+def _pg_ranks(row_start, inc):
+    """The incidence lists by rank: [(poses with more than d entries, the edge of their d-th entry, whether they are its i)] for d = 0,
+    1, ...: a pose occurs once per rank, so a rank is one vectorised step of every pose's left-to-right sum."""
+    row_start, inc = np.asarray(row_start, np.int64), np.asarray(inc, np.int64)
+    deg = np.diff(row_start)
+    out = []
+    for d in range(int(deg.max()) if deg.size else 0):
+        k = np.nonzero(deg > d)[0]
+        c = inc[row_start[k] + d]
+        out.append((k, c >> 1, (c & 1).astype(bool)))
+    return out
+
+
+def _pg_arrays(poses, fixed, i, j, Z, w):
+    P = _poses_12(poses, "poses")
+    N = len(P)
+    i, j = np.asarray(i, np.int64).reshape(-1), np.asarray(j, np.int64).reshape(-1)
+    E = len(i)
+    Z = np.ascontiguousarray(Z, np.float64).reshape(E, 12)
+    w = np.ascontiguousarray(w, np.float64).reshape(E, 2)
+    fixed = np.asarray(fixed).astype(bool).reshape(-1)
+    if fixed.shape != (N,) or j.shape != (E,):
+        raise ValueError("fixed must be [%d] and i, j of one length" % N)
+    return P, fixed, i, j, Z, w
+
+
+def pose_graph_linearize(poses, fixed, i, j, Z, w, lam, words=None):
+    """One linearisation of a pose graph - the definition of include/stereo_vision_hip.h (AE1) in numpy.  poses float64 [N,12] world
+    from frame, fixed bool [N], edges i, j int [E], Z float64 [E,12] the measured P_i^-1 o P_j, w float64 [E,2] = (w_rot, w_trans) as
+    they count now (a switched-off edge has both 0), lam > 0.  -> {"M" [E,12], "Wr" [E,6], "chi2" [E], "b" [N,6], "factor" [N,21]}.
+
+      M        P_j^-1 o P_i: R_M[a,b] = (Rj[0,a] Ri[0,b] + Rj[1,a] Ri[1,b]) + Rj[2,a] Ri[2,b]; t_M = Rj^T (t_i - t_j), every three-term sum
+               (p0 + p1) + p2.
+      residual Q = M o Z (R_Q = R_M R_Z, t_Q = R_M t_Z + t_M), D = Q^-1; a = 0.5 (Q[1,2] - Q[2,1], Q[2,0] - Q[0,2], Q[0,1] - Q[1,0]),
+               t_D = -(R_Q^T t_Q); Wr = (w_rot a, w_trans t_D); chi2 = w_rot ((a0 a0 + a1 a1) + a2 a2) + w_trans ((t0 t0 + t1 t1) + t2 t2).
+      b        per pose, from 0.0 over its entries in ascending order: - Wr where it is the edge's j, + Ad_M^T Wr where it is its i; 0 for a
+               fixed pose.
+      block    the 6 x 6 diagonal block of H as 21 words (row p, column q <= p), from 0.0 over the same entries: + diag(w) where the pose
+               is j; + A^T W A where it is i, A = Ad_M = [[R, 0], [T, R]], T[a,b] = (t x column b of R)[a], each word the six products (A[m,p]
+               w[m]) A[m,q], m = 0 .. 5, added left to right; then + lam on the diagonal.
+      factor   its L D L^T, in place: d_p = B[p,p] - sum_q<p (L[p,q] d_q) L[p,q]; L[r,p] = (B[r,p] - sum_q<p (L[r,q] d_q) L[p,q]) / d_p; the
+               sums subtracted one by one, q ascending.  d on the diagonal words, L below."""
+    P, fixed, i, j, Z, w = _pg_arrays(poses, fixed, i, j, Z, w)
+    N, E = len(P), len(i)
+    lam = float(lam)
+    row_start, inc = pose_graph_words(N, i, j) if words is None else words
+    Pi, Pj = P[i], P[j]
+    RM = np.stack([(Pj[:, a] * Pi[:, b] + Pj[:, 3 + a] * Pi[:, 3 + b]) + Pj[:, 6 + a] * Pi[:, 6 + b] for a in range(3) for b in range(3)], -1).reshape(E, 9)
+    M = np.concatenate([RM, _pg_mtv(Pj[:, :9], Pi[:, 9:] - Pj[:, 9:])], -1).reshape(E, 12)
+    RQ = np.stack([(RM[:, 3 * a] * Z[:, b] + RM[:, 3 * a + 1] * Z[:, 3 + b]) + RM[:, 3 * a + 2] * Z[:, 6 + b] for a in range(3) for b in range(3)], -1).reshape(E, 9)
+    tQ = _pg_mv(RM, Z[:, 9:]) + M[:, 9:]
+    a = np.stack([0.5 * (RQ[:, 5] - RQ[:, 7]), 0.5 * (RQ[:, 6] - RQ[:, 2]), 0.5 * (RQ[:, 1] - RQ[:, 3])], -1).reshape(E, 3)
+    tD = -_pg_mtv(RQ, tQ)
+    Wr = np.concatenate([w[:, :1] * a, w[:, 1:] * tD], -1).reshape(E, 6)
+    chi2 = w[:, 0] * ((a[:, 0] * a[:, 0] + a[:, 1] * a[:, 1]) + a[:, 2] * a[:, 2]) + w[:, 1] * ((tD[:, 0] * tD[:, 0] + tD[:, 1] * tD[:, 1]) + tD[:, 2] * tD[:, 2])
+    # A = Ad_M, [E,6,6], and the edge's own block A^T W A
+    A = np.zeros((E, 6, 6))
+    R3 = RM.reshape(E, 3, 3)
+    A[:, :3, :3] = R3
+    A[:, 3:, 3:] = R3
+    for c in range(3):
+        A[:, 3:, c] = _pg_cross(M[:, 9:], R3[:, :, c])
+    w6 = np.concatenate([np.repeat(w[:, :1], 3, 1), np.repeat(w[:, 1:], 3, 1)], 1).reshape(E, 6)
+    Be = np.zeros((E, 21))
+    for n, (p, q) in enumerate(_PG_TRI):
+        s = (A[:, 0, p] * w6[:, 0]) * A[:, 0, q]
+        for m in range(1, 6):
+            s = s + (A[:, m, p] * w6[:, m]) * A[:, m, q]
+        Be[:, n] = s
+    up = _pg_adt(M, Wr)
+    b, B = np.zeros((N, 6)), np.zeros((N, 21))
+    diag = np.array(_PG_DIAG)
+    for k, e, is_i in _pg_ranks(row_start, inc):
+        b[k] = np.where(is_i[:, None], b[k] + up[e], b[k] - Wr[e])
+        B[k[is_i]] = B[k[is_i]] + Be[e[is_i]]
+        kj = k[~is_i]
+        B[kj[:, None], diag[None, :]] = B[kj[:, None], diag[None, :]] + w6[e[~is_i]]
+    b[fixed] = 0.0
+    B[:, diag] = B[:, diag] + lam
+    F = B.copy()
+    at = _PG_AT
+    for p in range(6):
+        s = F[:, at[(p, p)]]
+        for q in range(p):
+            s = s - (F[:, at[(p, q)]] * F[:, at[(q, q)]]) * F[:, at[(p, q)]]
+        F[:, at[(p, p)]] = s
+        for r in range(p + 1, 6):
+            s = F[:, at[(r, p)]]
+            for q in range(p):
+                s = s - (F[:, at[(r, q)]] * F[:, at[(q, q)]]) * F[:, at[(p, q)]]
+            F[:, at[(r, p)]] = s / F[:, at[(p, p)]]
+    return {"M": M, "Wr": Wr, "chi2": chi2, "b": b, "factor": F}
+
+
+def _pg_precondition(F, r):
+    """z = (L D L^T)^-1 r per pose: forward y_p = r_p - sum_q<p L[p,q] y_q, then y_p / d_p, then backward z_p = y_p - sum_q>p L[q,p] z_q,
+    the sums subtracted one by one with q ascending."""
+    at = _PG_AT
+    y = [None] * 6
+    for p in range(6):
+        s = r[..., p]
+        for q in range(p):
+            s = s - F[..., at[(p, q)]] * y[q]
+        y[p] = s
+    y = [y[p] / F[..., at[(p, p)]] for p in range(6)]
+    z = [None] * 6
+    for p in range(5, -1, -1):
+        s = y[p]
+        for q in range(p + 1, 6):
+            s = s - F[..., at[(q, p)]] * z[q]
+        z[p] = s
+    return np.stack(z, -1)
+
+
+def _pg_operator(x, fixed, i, j, w6, M, ranks, lam):
+    """H x in the two passes of the definition: g_e = W (x_j - Ad_M x_i) per edge; per pose, from 0.0 over its entries in ascending order,
+    + g_e where it is j and - Ad_M^T g_e where it is i, then + lam x_k; 0 for a fixed pose."""
+    g = w6 * (x[j] - _pg_ad(M, x[i]))
+    down = _pg_adt(M, g)
+    q = np.zeros_like(x)
+    for k, e, is_i in ranks:
+        q[k] = np.where(is_i[:, None], q[k] - down[e], q[k] + g[e])
+    q = q + lam * x
+    q[fixed] = 0.0
+    return q
+
+
+def pose_graph_pcg(fixed, i, j, w, M, b, factor, lam, max_iters, tol, words=None):
+    """Preconditioned conjugate gradients on H x = b from x = 0 - the definition of include/stereo_vision_hip.h (AE2) in numpy, over what
+    pose_graph_linearize gave.  -> x float64 [N,6], {"iteration", "done", "rr", "rr0"}.
+
+      start     r = b, z = F^-1 r per pose (_pg_precondition), rr0 = rr = <r, r>, rz = <r, z>; every <a, b> is pose_graph_sum of the poses'
+                six products added left to right.
+      verdict   done = rr <= (tol tol) rr0, in double, before the first iteration and after every one; nothing moves once it holds.
+      iteration p = z in the first, else z + (rz / rz_before) p; q = H p (_pg_operator); alpha = rz / <p, q>; x = x + alpha p; r = r -
+                alpha q; z = F^-1 r; rr = <r, r>; rz = <r, z>."""
+    i, j = np.asarray(i, np.int64).reshape(-1), np.asarray(j, np.int64).reshape(-1)
+    fixed = np.asarray(fixed).astype(bool).reshape(-1)
+    N, E = len(fixed), len(i)
+    w = np.asarray(w, np.float64).reshape(E, 2)
+    w6 = np.concatenate([np.repeat(w[:, :1], 3, 1), np.repeat(w[:, 1:], 3, 1)], 1).reshape(E, 6)
+    M, b, F = np.asarray(M, np.float64).reshape(E, 12), np.asarray(b, np.float64).reshape(N, 6), np.asarray(factor, np.float64).reshape(N, 21)
+    lam, tol2 = float(lam), float(tol) * float(tol)
+    ranks = _pg_ranks(*(pose_graph_words(N, i, j) if words is None else words))
+    x, r = np.zeros((N, 6)), b.copy()
+    z = _pg_precondition(F, r)
+    p = np.zeros((N, 6))
+    rr0 = rr = pose_graph_sum(_pg_dot6(r, r))
+    rz, rz_before = pose_graph_sum(_pg_dot6(r, z)), None
+    it, done = 0, rr <= tol2 * rr0
+    while not done and it < max_iters:
+        p = z.copy() if it == 0 else z + (rz / rz_before) * p
+        q = _pg_operator(p, fixed, i, j, w6, M, ranks, lam)
+        alpha = rz / pose_graph_sum(_pg_dot6(p, q))
+        x = x + alpha * p
+        r = r - alpha * q
+        z = _pg_precondition(F, r)
+        rr = pose_graph_sum(_pg_dot6(r, r))
+        rz_before, rz = rz, pose_graph_sum(_pg_dot6(r, z))
+        it += 1
+        done = rr <= tol2 * rr0
+    return x, {"iteration": it, "done": bool(done), "rr": float(rr), "rr0": float(rr0)}
+
+
+def _pgb_mv(R, x):
+    return [(R[3 * a] * x[0] + R[3 * a + 1] * x[1]) + R[3 * a + 2] * x[2] for a in range(3)]
+
+
+def _pgb_mtv(R, x):
+    return [(R[a] * x[0] + R[3 + a] * x[1]) + R[6 + a] * x[2] for a in range(3)]
+
+
+def _pgb_cross(t, u):
+    return [t[1] * u[2] - t[2] * u[1], t[2] * u[0] - t[0] * u[2], t[0] * u[1] - t[1] * u[0]]
+
+
+def _pgb_ad(M, x):
+    u, v = _pgb_mv(M[:9], x[:3]), _pgb_mv(M[:9], x[3:])
+    c = _pgb_cross(M[9:], u)
+    return u + [c[a] + v[a] for a in range(3)]
+
+
+def _pgb_adt(M, g):
+    c = _pgb_cross(M[9:], g[3:])
+    return _pgb_mtv(M[:9], [g[a] - c[a] for a in range(3)]) + _pgb_mtv(M[:9], g[3:])
+
+
+def _pgb_lists(n_poses, i, j):
+    lists = [[] for _ in range(n_poses)]
+    for e in range(len(i)):
+        lists[j[e]].append((e, False))
+        lists[i[e]].append((e, True))
+    return lists
+
+
+def pose_graph_linearize_brute(poses, fixed, i, j, Z, w, lam):
+    """pose_graph_linearize as plain loops over edges and poses, in Python floats."""
+    P, fixed, i, j, Z, w = _pg_arrays(poses, fixed, i, j, Z, w)
+    N, E = len(P), len(i)
+    P, Z, w, i, j, lam = P.tolist(), Z.tolist(), w.tolist(), i.tolist(), j.tolist(), float(lam)
+    M, Wr, chi2, Be = [], [], [], []
+    for e in range(E):
+        Pi, Pj, Ze, (wr, wt) = P[i[e]], P[j[e]], Z[e], w[e]
+        RM = [(Pj[a] * Pi[b] + Pj[3 + a] * Pi[3 + b]) + Pj[6 + a] * Pi[6 + b] for a in range(3) for b in range(3)]
+        tM = _pgb_mtv(Pj[:9], [Pi[9 + a] - Pj[9 + a] for a in range(3)])
+        RQ = [(RM[3 * a] * Ze[b] + RM[3 * a + 1] * Ze[3 + b]) + RM[3 * a + 2] * Ze[6 + b] for a in range(3) for b in range(3)]
+        u = _pgb_mv(RM, Ze[9:])
+        tQ = [u[a] + tM[a] for a in range(3)]
+        a = [0.5 * (RQ[5] - RQ[7]), 0.5 * (RQ[6] - RQ[2]), 0.5 * (RQ[1] - RQ[3])]
+        tD = [-v for v in _pgb_mtv(RQ, tQ)]
+        M.append(RM + tM)
+        Wr.append([wr * v for v in a] + [wt * v for v in tD])
+        chi2.append(wr * ((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]) + wt * ((tD[0] * tD[0] + tD[1] * tD[1]) + tD[2] * tD[2]))
+        A = [[0.0] * 6 for _ in range(6)]
+        for c in range(3):
+            T = _pgb_cross(tM, [RM[c], RM[3 + c], RM[6 + c]])
+            for a_ in range(3):
+                A[a_][c] = RM[3 * a_ + c]
+                A[3 + a_][3 + c] = RM[3 * a_ + c]
+                A[3 + a_][c] = T[a_]
+        w6 = [wr, wr, wr, wt, wt, wt]
+        blk = []
+        for p, q in _PG_TRI:
+            s = (A[0][p] * w6[0]) * A[0][q]
+            for m in range(1, 6):
+                s = s + (A[m][p] * w6[m]) * A[m][q]
+            blk.append(s)
+        Be.append(blk)
+    b, F = [], []
+    for k, entries in enumerate(_pgb_lists(N, i, j)):
+        acc, B = [0.0] * 6, [0.0] * 21
+        for e, is_i in entries:
+            if is_i:
+                up = _pgb_adt(M[e], Wr[e])
+                acc = [acc[c] + up[c] for c in range(6)]
+                B = [B[n] + Be[e][n] for n in range(21)]
+            else:
+                acc = [acc[c] - Wr[e][c] for c in range(6)]
+                for p in range(6):
+                    B[_PG_AT[(p, p)]] = B[_PG_AT[(p, p)]] + (w[e][0] if p < 3 else w[e][1])
+        for p in range(6):
+            B[_PG_AT[(p, p)]] = B[_PG_AT[(p, p)]] + lam
+        at = _PG_AT
+        for p in range(6):
+            s = B[at[(p, p)]]
+            for q in range(p):
+                s = s - (B[at[(p, q)]] * B[at[(q, q)]]) * B[at[(p, q)]]
+            B[at[(p, p)]] = s
+            for r in range(p + 1, 6):
+                s = B[at[(r, p)]]
+                for q in range(p):
+                    s = s - (B[at[(r, q)]] * B[at[(q, q)]]) * B[at[(p, q)]]
+                B[at[(r, p)]] = s / B[at[(p, p)]]
+        b.append([0.0] * 6 if fixed[k] else acc)
+        F.append(B)
+    f64 = np.float64
+    return {"M": np.array(M, f64).reshape(E, 12), "Wr": np.array(Wr, f64).reshape(E, 6), "chi2": np.array(chi2, f64).reshape(E),
+            "b": np.array(b, f64).reshape(N, 6), "factor": np.array(F, f64).reshape(N, 21)}
+
+
+def pose_graph_pcg_brute(fixed, i, j, w, M, b, factor, lam, max_iters, tol):
+    """pose_graph_pcg as plain loops over edges and poses, in Python floats."""
+    i, j = np.asarray(i, np.int64).reshape(-1).tolist(), np.asarray(j, np.int64).reshape(-1).tolist()
+    fixed = np.asarray(fixed).astype(bool).reshape(-1).tolist()
+    N, E = len(fixed), len(i)
+    w, M = np.asarray(w, np.float64).reshape(E, 2).tolist(), np.asarray(M, np.float64).reshape(E, 12).tolist()
+    b, F = np.asarray(b, np.float64).reshape(N, 6).tolist(), np.asarray(factor, np.float64).reshape(N, 21).tolist()
+    lam, tol2, at = float(lam), float(tol) * float(tol), _PG_AT
+    lists = _pgb_lists(N, i, j)
+
+    def dot(u, v):
+        return pose_graph_sum_brute([((((u[k][0] * v[k][0] + u[k][1] * v[k][1]) + u[k][2] * v[k][2]) + u[k][3] * v[k][3]) + u[k][4] * v[k][4])
+                                     + u[k][5] * v[k][5] for k in range(N)])
+
+    def precondition(k, r):
+        y = []
+        for p in range(6):
+            s = r[p]
+            for q in range(p):
+                s = s - F[k][at[(p, q)]] * y[q]
+            y.append(s)
+        y = [y[p] / F[k][at[(p, p)]] for p in range(6)]
+        z = [0.0] * 6
+        for p in range(5, -1, -1):
+            s = y[p]
+            for q in range(p + 1, 6):
+                s = s - F[k][at[(q, p)]] * z[q]
+            z[p] = s
+        return z
+
+    x, r = [[0.0] * 6 for _ in range(N)], [row[:] for row in b]
+    z = [precondition(k, r[k]) for k in range(N)]
+    p = [[0.0] * 6 for _ in range(N)]
+    rr0 = rr = dot(r, r)
+    rz, rz_before = dot(r, z), None
+    it, done = 0, rr <= tol2 * rr0
+    while not done and it < max_iters:
+        if it == 0:
+            p = [row[:] for row in z]
+        else:
+            beta = rz / rz_before
+            p = [[z[k][c] + beta * p[k][c] for c in range(6)] for k in range(N)]
+        g = []
+        for e in range(E):
+            ad = _pgb_ad(M[e], p[i[e]])
+            g.append([(w[e][0] if c < 3 else w[e][1]) * (p[j[e]][c] - ad[c]) for c in range(6)])
+        q = []
+        for k in range(N):
+            acc = [0.0] * 6
+            for e, is_i in lists[k]:
+                if is_i:
+                    down = _pgb_adt(M[e], g[e])
+                    acc = [acc[c] - down[c] for c in range(6)]
+                else:
+                    acc = [acc[c] + g[e][c] for c in range(6)]
+            q.append([0.0] * 6 if fixed[k] else [acc[c] + lam * p[k][c] for c in range(6)])
+        alpha = rz / dot(p, q)
+        x = [[x[k][c] + alpha * p[k][c] for c in range(6)] for k in range(N)]
+        r = [[r[k][c] - alpha * q[k][c] for c in range(6)] for k in range(N)]
+        z = [precondition(k, r[k]) for k in range(N)]
+        rr = dot(r, r)
+        rz_before, rz = rz, dot(r, z)
+        it += 1
+        done = rr <= tol2 * rr0
+    return np.array(x, np.float64).reshape(N, 6), {"iteration": it, "done": bool(done), "rr": float(rr), "rr0": float(rr0)}
+
+
+def pose_between(a, b):
+    """a^-1 o b of two [12] poses: the relative pose an edge of the pose graph measures, Z = P_i^-1 o P_j."""
+    return _pose_mul(_pose_inv(np.asarray(a, np.float64).reshape(12)), np.asarray(b, np.float64).reshape(12))
+
+
+def pose_graph_chain(poses, w_rot=1.0, w_trans=1.0):
+    """The odometry edges of a chain of poses [N,12]: edge k ties frames k and k + 1 with Z = poses[k]^-1 o poses[k + 1] and the weights
+    given (scalars, or [N - 1]).  -> (i, j, Z, w, kind), the edge tuple pose_graph takes."""
+    P = _poses_12(poses, "poses")
+    n = max(len(P) - 1, 0)
+    Z = np.array([_pose_mul(_pose_inv(P[k]), P[k + 1]) for k in range(n)], np.float64).reshape(n, 12)
+    w = np.stack([np.broadcast_to(np.asarray(w_rot, np.float64), (n,)), np.broadcast_to(np.asarray(w_trans, np.float64), (n,))], 1).reshape(n, 2)
+    return np.arange(n, dtype=np.int32), np.arange(1, n + 1, dtype=np.int32), Z, np.ascontiguousarray(w), np.zeros(n, np.int32)
+
+
+def pose_graph_loop(i, j, Z, w_rot=1.0, w_trans=1.0):
+    """One loop edge: frames i and j with the measured Z = P_i^-1 o P_j [12] - say pose_mul(inverse of key i's pose, the pose
+    VoxelMap.align arrived at for frame j) - and its weights.  -> the edge tuple pose_graph takes."""
+    Z = np.asarray(Z, np.float64)
+    if Z.shape != (12,):
+        raise ValueError("Z must be float64 [12], got shape %s" % (Z.shape,))
+    return (np.array([_whole(i, "i")], np.int32), np.array([_whole(j, "j")], np.int32), Z.reshape(1, 12).copy(),
+            np.array([[float(w_rot), float(w_trans)]], np.float64), np.ones(1, np.int32))
+
+
+def pose_graph(poses, edges, fixed=(0,)):
+    """A pose graph, checked: poses float64 [N,12] (world from frame, N in 1 .. 2^20), edges a list of edge tuples (pose_graph_chain's,
+    pose_graph_loop's) joined in the order given (at most 2^22), fixed the indices of the poses held (or a bool mask [N]).  -> {"poses",
+    "i", "j", "Z", "w", "kind", "fixed"}.  ValueError for i == j, an index outside 0 .. N - 1, a weight that is negative or not finite,
+    poses or Z that are not finite, a kind that is neither 0 nor 1, and no fixed pose."""
+    P = _poses_12(poses, "poses").copy()
+    N = len(P)
+    if not 1 <= N <= POSE_GRAPH_POSES_MAX:
+        raise ValueError("a pose graph holds 1 .. 2^20 poses, got %d" % N)
+    if not np.isfinite(P).all():
+        raise ValueError("a pose is not finite")
+    parts = [tuple(np.asarray(a) for a in t) for t in edges]
+    for t in parts:
+        if len(t) != 5 or not (len(t[0]) == len(t[1]) == len(t[2]) == len(t[3]) == len(t[4])) or t[2].shape[1:] != (12,) or t[3].shape[1:] != (2,):
+            raise ValueError("an edge tuple is (i [E], j [E], Z [E,12], w [E,2], kind [E])")
+    cat = lambda n, dt, shape: (np.concatenate([t[n].astype(dt) for t in parts]) if parts else np.zeros((0,) + shape, dt)).reshape((-1,) + shape)
+    i, j, Z, w, kind = cat(0, np.int64, ()), cat(1, np.int64, ()), cat(2, np.float64, (12,)), cat(3, np.float64, (2,)), cat(4, np.int64, ())
+    if len(i) > POSE_GRAPH_EDGES_MAX:
+        raise ValueError("a pose graph holds at most 2^22 edges, got %d" % len(i))
+    if ((i < 0) | (i >= N) | (j < 0) | (j >= N)).any():
+        raise ValueError("an edge names a pose outside 0 .. %d" % (N - 1))
+    if (i == j).any():
+        raise ValueError("an edge ties a pose to itself")
+    if not np.isfinite(w).all() or (w < 0).any():
+        raise ValueError("a weight is negative or not finite")
+    if not np.isfinite(Z).all():
+        raise ValueError("a measurement Z is not finite")
+    if ((kind != POSE_GRAPH_ODOMETRY) & (kind != POSE_GRAPH_LOOP)).any():
+        raise ValueError("a kind is neither 0 (odometry) nor 1 (loop)")
+    f = np.asarray(fixed)
+    if f.dtype == bool:
+        if f.shape != (N,):
+            raise ValueError("a fixed mask must be [%d]" % N)
+        mask = f.copy()
+    else:
+        f = f.astype(np.int64).reshape(-1)
+        if ((f < 0) | (f >= N)).any():
+            raise ValueError("a fixed pose lies outside 0 .. %d" % (N - 1))
+        mask = np.zeros(N, bool)
+        mask[f] = True
+    if not mask.any():
+        raise ValueError("a pose graph needs a fixed pose: without one the whole trajectory floats")
+    return {"poses": P, "i": i.astype(np.int32), "j": j.astype(np.int32), "Z": np.ascontiguousarray(Z), "w": np.ascontiguousarray(w),
+            "kind": kind.astype(np.int32), "fixed": mask}
+
+
+def pose_graph_step(graph, poses, w, lam, max_iters, tol, words):
+    """One round's linearise and solve in numpy -> (delta [N,6], chi2 [E], PCG's state): what pose_graph_optimize calls where no device
+    step is given."""
+    lin = pose_graph_linearize(poses, graph["fixed"], graph["i"], graph["j"], graph["Z"], w, lam, words)
+    x, state = pose_graph_pcg(graph["fixed"], graph["i"], graph["j"], w, lin["M"], lin["b"], lin["factor"], lam, max_iters, tol, words)
+    return x, lin["chi2"], state
+
+
+def pose_graph_optimize(graph, rounds=10, gate=None, eps=1e-9, lam=1e-6, max_iters=None, tol=1e-8, step=None):
+    """Gauss-Newton on a pose graph (pose_graph's dict): per round linearise and solve (step: pose_graph_step, or the device's with the
+    same signature), then on the host P_k <- P_k o pose_exp(delta_k), then every loop edge whose chi2 - at this round's linearisation -
+    exceeds `gate` is switched off for the rounds after (odometry edges never; gate=None gates nothing).  Stops after `rounds`, or when
+    max |delta| < eps.  max_iters caps PCG per round; None is max(1000, 20 N) - block-Jacobi needs 6 to 12 N iterations on a chain with
+    few loops, and a round that stops at the cap is an inexact Gauss-Newton step: "converged" says which did.  -> poses [N,12], {"costs": the sum of chi2 (pose_graph_sum) at each round's linearisation, "cost": the same at the
+    poses returned, "iterations": PCG's per round, "converged": PCG's verdicts, "off": the loop edges switched off, ascending, "rounds"}.
+    Host code shared by the CPU and the GPU path: the same delta gives the same poses bit for bit."""
+    lam, tol = float(lam), float(tol)
+    if not (lam > 0.0 and np.isfinite(lam)):
+        raise ValueError("lam must be a finite number > 0: it keeps a pose without a live edge solvable")
+    if not (tol >= 0.0) or not np.isfinite(tol):
+        raise ValueError("tol must be finite and not negative")
+    rounds, max_iters = _whole(rounds, "rounds"), _whole(max(1000, 20 * len(graph["poses"])) if max_iters is None else max_iters, "max_iters")
+    if rounds < 0 or max_iters < 0:
+        raise ValueError("rounds and max_iters must not be negative")
+    if gate is not None and not float(gate) >= 0.0:
+        raise ValueError("gate must be None or a number >= 0")
+    step = pose_graph_step if step is None else step
+    P = graph["poses"].copy()
+    N = len(P)
+    words = pose_graph_words(N, graph["i"], graph["j"])
+    live = np.ones(len(graph["i"]), bool)
+    is_loop = graph["kind"] == POSE_GRAPH_LOOP
+    costs, iterations, converged, done_rounds = [], [], [], 0
+    for _ in range(rounds):
+        w = graph["w"] * live[:, None]
+        delta, chi2, state = step(graph, P, w, lam, max_iters, tol, words)
+        costs.append(pose_graph_sum(chi2))
+        iterations.append(int(state["iteration"]))
+        converged.append(bool(state["done"]))
+        for k in range(N):
+            if not graph["fixed"][k]:
+                P[k] = _pose_mul(P[k], pose_exp(delta[k]))
+        done_rounds += 1
+        if gate is not None:
+            live &= ~(is_loop & (chi2 > float(gate)))
+        if not np.abs(delta).max() >= eps:
+            break
+    w = graph["w"] * live[:, None]
+    cost = pose_graph_sum(pose_graph_linearize(P, graph["fixed"], graph["i"], graph["j"], graph["Z"], w, lam, words)["chi2"])
+    return P, {"costs": costs, "cost": cost, "iterations": iterations, "converged": converged, "off": np.nonzero(is_loop & ~live)[0].astype(np.int32),
+               "rounds": done_rounds}
 
 
 VOXEL_CARVE_REACH_MAX = 1023  # cells a ray of voxel_map_carve may span on its major axis: 2 k d + nst stays below 2^22
@@ -5590,9 +6145,16 @@ def main(argv=None):
                              "which is searched among the frames at least MIN_GAP (default 50) before it under every rotation and then "
                              "stored; a best candidate with 256 sad <= ACCEPT norm (default 64) writes one line to FILE: 'frame key shift "
                              "sad norm yaw_deg' - the frame it recognised, the shift in sectors and the heading against that frame in degrees")
+    parser.add_argument("--pose-graph", type=str, default="", metavar="OUT[,ROUNDS[,GATE]]",
+                        help="with --places: at the end of the run, the pose graph of the drive (rig.PoseGraph) - the chain of --poses or "
+                             "--odometry, and a loop edge per frame that recognised an earlier one: the relative pose of the two as "
+                             "--voxel-match and --voxel-align refined them where those are given, else the two at one place under the "
+                             "recognised heading - optimised in ROUNDS rounds (default 10), a loop edge whose chi2 exceeds GATE switched "
+                             "off (default: none); writes the corrected poses to OUT, twelve words a line (R row-major, then t): a file "
+                             "--voxel-repose takes")
     parser.add_argument("--voxel-repose", type=str, default="", metavar="CORRECTED_POSES",
                         help="with --voxel-map: at the end of the run, re-pose the map from the poses its frames were inserted at to those of "
-                             "CORRECTED_POSES - a file as --poses takes, the result of a pose graph or of loop_spread - (rig.VoxelMap.repose: "
+                             "CORRECTED_POSES - a file as --poses takes or --pose-graph writes, the result of a pose graph or of loop_spread - (rig.VoxelMap.repose: "
                              "every voxel moved by the correction of the frame that saw it last, into the box of the corrected "
                              "trajectory); writes <FILE>.reposed.ply beside the map and prints the counts")
     parser.add_argument("--temporal", type=str, default="", metavar="DIR[,TOL_PX[,MODE]]",
@@ -5641,6 +6203,14 @@ def main(argv=None):
             args.places_spec = cli_places_spec(args.places)
         except ValueError as e:
             parser.error("--places: %s" % e)
+    args.pose_graph_spec = None
+    if args.pose_graph:
+        if not args.places:
+            parser.error("--pose-graph needs --places: the loops are the frames it recognises")
+        try:
+            args.pose_graph_spec = cli_pose_graph_spec(args.pose_graph)
+        except ValueError as e:
+            parser.error("--pose-graph: %s" % e)
     args.temporal_spec = None
     if args.temporal:
         if not args.batch or not args.odometry:
@@ -5816,8 +6386,8 @@ def main(argv=None):
         args.repose_rows = None
         if args.voxel_repose:
             try:
-                args.repose_rows = read_poses(args.voxel_repose, len(files))
-                args.repose_box = cli_voxel_map_box(args.repose_rows)
+                args.repose_rows = read_poses12(args.voxel_repose, len(files))
+                args.repose_box = cli_voxel_map_box(np.stack([args.repose_rows[:, 9], args.repose_rows[:, 10], np.arctan2(args.repose_rows[:, 3], args.repose_rows[:, 0])], 1))
                 voxel_map_params(args.repose_box[0], args.repose_box[1], args.voxel, CLI_VOXEL_MAP_CAPACITY)
             except (OSError, ValueError) as e:
                 parser.error("--voxel-repose: %s" % e)
@@ -5873,6 +6443,76 @@ def read_poses(path, n):
     if not np.isfinite(out).all():
         raise ValueError("%s holds a pose that is not finite" % path)
     return out
+
+
+def read_poses12(path, n):
+    """float64 [n, 12] poses (R row-major, then t) from a text file with one line per frame, all of one form: 'x y yaw' as read_poses
+    takes them, expanded by voxel_map_pose, or twelve words as --pose-graph writes them.  ValueError as read_poses, and for a file
+    whose lines differ in form."""
+    rows = []
+    with open(path) as f:
+        for line in f:
+            line = line.strip()
+            if line and not line.startswith("#"):
+                rows.append(line.split())
+    if not rows or len(rows[0]) != 12:
+        xyyaw = read_poses(path, n)
+        return voxel_map_pose(xyyaw[:, 0], xyyaw[:, 1], xyyaw[:, 2])
+    if any(len(r) != 12 for r in rows):
+        raise ValueError("a line of %s has not the twelve words of the first" % path)
+    if len(rows) != n:
+        raise ValueError("%s holds %d poses for %d frames" % (path, len(rows), n))
+    out = np.array([[float(w) for w in r] for r in rows], np.float64).reshape(n, 12)
+    if not np.isfinite(out).all():
+        raise ValueError("%s holds a pose that is not finite" % path)
+    return out
+
+
+def cli_pose_graph_spec(text):
+    """--pose-graph OUT[,ROUNDS[,GATE]] -> (OUT, rounds, gate or None); ValueError for an empty OUT, ROUNDS outside 1 .. 1000, a GATE
+    that is negative or not finite, or more than three parts."""
+    parts = text.split(",")
+    if not parts[0] or len(parts) > 3:
+        raise ValueError("OUT[,ROUNDS[,GATE]], got %r" % text)
+    try:
+        rounds, gate = int(parts[1]) if len(parts) > 1 else 10, float(parts[2]) if len(parts) > 2 else None
+    except ValueError:
+        raise ValueError("ROUNDS must be an integer and GATE a number, got %r" % text)
+    if not 1 <= rounds <= 1000 or (gate is not None and not (gate >= 0.0 and np.isfinite(gate))):
+        raise ValueError("ROUNDS in 1 .. 1000 and GATE finite and >= 0, got %r" % text)
+    return parts[0], rounds, gate
+
+
+CLI_POSE_GRAPH = dict(odometry=(1.0e4, 100.0),  # (w_rot, w_trans) of a step of the chain: 10 mrad and 0.1 m
+                      refined=(1.0e4, 100.0),   # of a loop whose two poses the map's localisation refined: the same
+                      coarse=(100.0, 1.0))      # of a loop known from the descriptor alone: a sector and a metre
+
+
+def cli_pose_graph(path, xyyaw, went, found, sectors, refined, rounds=10, gate=None, device="cuda"):
+    """--pose-graph's work: the chain of the run's poses xyyaw [N,3], a loop edge per (frame, key, shift) of `found` with frame != key -
+    Z = went[key]^-1 o went[frame] where `refined` (went [N,12]: the poses the frames were inserted at), else went[key]^-1 o (the key's
+    place under the recognised heading, place_guess) -, optimised by rig.PoseGraph on `device`, written to `path` twelve words a line by
+    repr.  -> the corrected poses [N,12], the stats of pose_graph_optimize, the loop edges as (key, frame, Z)."""
+    from ..rig import PoseGraph
+    went = _poses_12(went, "went")
+    g = PoseGraph(device=device)
+    g.add_chain(voxel_map_pose(xyyaw[:, 0], xyyaw[:, 1], xyyaw[:, 2]), *CLI_POSE_GRAPH["odometry"])
+    loops = []
+    for frame, key, shift in found:
+        if frame == key:
+            continue
+        if refined:
+            there = went[frame]
+        else:
+            at = place_guess(went[key:key + 1], np.array([shift]), sectors)[0]
+            there = voxel_map_pose(at[0], at[1], at[3], at[2])
+        Z = pose_between(went[key], there)
+        g.add_loop(key, frame, Z, *CLI_POSE_GRAPH["refined" if refined else "coarse"])
+        loops.append((key, frame, Z))
+    poses, stats = g.optimize(rounds=rounds, gate=gate)
+    with open(path, "w") as f:
+        f.write("".join(" ".join("%r" % float(v) for v in row) + "\n" for row in poses))
+    return poses, stats, loops
 
 
 def occupancy_map_cover(poses_xyyaw, x_range, y_range):
@@ -6224,6 +6864,15 @@ def _run_batched(args, ldir, rdir, files):
                 with open(args.places_spec[0], "w") as f:
                     f.write("".join(line + "\n" for line in lines))
                 print("places: %d of %d frames recognised an earlier one, written to %s" % (len(lines), len(recognised), args.places_spec[0]))
+                if args.pose_graph_spec is not None:
+                    best = torch.cat(recognised).cpu().numpy() if recognised else np.zeros((0, 4), np.int32)
+                    found = [(f, int(b[0]), int(b[1])) for f, b in enumerate(best) if b[0] >= 0]
+                    refined = args.voxel_match_window is not None or args.voxel_align_spec is not None
+                    _, stats, loops = cli_pose_graph(args.pose_graph_spec[0], args.pose_rows, np.asarray(aligned_3d, np.float64).reshape(-1, 12), found,
+                                                     places.params["sectors"], refined, args.pose_graph_spec[1], args.pose_graph_spec[2], device=rig.device)
+                    print("pose graph: %d frames, %d loop edges (%d switched off), %d rounds, cost %r -> %r, written to %s" % (
+                        len(args.pose_rows), len(loops), len(stats["off"]), stats["rounds"], stats["costs"][0] if stats["costs"] else stats["cost"], stats["cost"],
+                        args.pose_graph_spec[0]))
             if args.voxel_match_window is not None:
                 with open(os.path.splitext(args.voxel_map)[0] + ".poses.txt", "w") as f:
                     f.write("".join("%r %r %r %r\n" % tuple(float(v) for v in to) for to in refined_3d))
@@ -6231,7 +6880,7 @@ def _run_batched(args, ldir, rdir, files):
                 with open(os.path.splitext(args.voxel_map)[0] + ".aligned.txt", "w") as f:
                     f.write("".join(" ".join("%r" % float(v) for v in to) + "\n" for to in aligned_3d))
             if args.repose_rows is not None:  # from where the frames went to where the corrected poses put them; the stages below read the re-posed map
-                fixed = voxel_map_pose(args.repose_rows[:, 0], args.repose_rows[:, 1], args.repose_rows[:, 2])
+                fixed = args.repose_rows
                 box = voxel_map_params(args.repose_box[0], args.repose_box[1], args.voxel, CLI_VOXEL_MAP_CAPACITY)
                 text = cli_voxel_carry_text(model.repose(pose_corrections(np.asarray(aligned_3d, np.float64).reshape(-1, 12), fixed), params=box))
                 out = os.path.splitext(args.voxel_map)[0] + ".reposed.ply"
